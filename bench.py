@@ -14,6 +14,7 @@ touched a GPU); under an external launcher (WORLD_SIZE set) it is one of the ran
 Prints ONE JSON line on rank 0.
 """
 import argparse
+import io
 import json
 import os
 import statistics
@@ -28,7 +29,9 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 K = 31
 READ_LEN = 150
 ERR = 0.01
-HBM_PEAK = 8.0e12      # B/s, /opt/skills/guides/MI355X_MICROARCH.md
+HBM_PEAK = 8.0e12      # B/s, MI355X peak HBM bandwidth
+DUMP_SAMPLE = 1 << 20  # weak-map entries --dump-outputs writes over all ranks (28 bytes each)
+DUMP_LIMIT = 64 << 20  # bytes --dump-outputs may write over all ranks
 
 
 def parse_args():
@@ -55,7 +58,12 @@ def parse_args():
     ap.add_argument("--tune", action="append", default=[], metavar="KNOB=VALUE", help="kmr_tune knob of the handle (measurement sweeps), e.g. partition_blocks=192")
     ap.add_argument("--no-check", action="store_true", help="development: skip the conservation assert (ablation runs of a debug build)")
     ap.add_argument("--build-mode", type=int, default=0, help="kmr_config.build_mode: 0 auto, 1 device table, 2 two-level k-mer partition, 3 super-k-mer lists")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed as DIR/<name>.npy "
+                    "(float32 / float64, at most 64 MB; see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def launch_ranks(args):
@@ -135,6 +143,96 @@ def cpu_baseline(torch, n_reads, quality, dev):
                       "median of 3 runs" % (n_reads, raw, 5 * n_reads, best_t, n_sweep),
             "seconds": secs, "run_seconds": [r[1] for r in runs], "kmers_per_s_by_threads_on_sweep": sweep,
             "host": {"nproc": os.cpu_count(), "threads_available": cores, "cpu_model": model}}
+
+
+def _mix64(x):
+    """splitmix64's finaliser on a uint64 array (a bijection: distinct keys mix to distinct values)"""
+    import numpy as np
+    with np.errstate(over="ignore"):
+        x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        return x ^ (x >> np.uint64(31))
+
+
+def dump_outputs(sp, out_dir, rank, world):
+    """--dump-outputs: what the caller of the timed path holds after its last step, as float .npy files in out_dir (one set per
+    rank, suffixed _rank<r>, when world > 1; every rank writes at most DUMP_LIMIT / world bytes, so the whole dump stays within
+    DUMP_LIMIT):
+      stats               float64[8]  kmr_get_stats: raw, raw good, unique, singleton k-mers, discarded, weak entries,
+                                      singleton entries, reads
+      weak_digest         float64[8]  kmr_map_digest of the weak map: entries, count_sum, dir_sum, hash_sum hi / lo, hash_xor hi / lo
+                                      (32-bit halves), weighted_sum
+      weak_histogram      float64[256] entries of the weak map by count (last bin: the rest); weak_histogram_weight: their
+                                      weightedCount sums
+      weak_sample_*       the weak map's entries (decoded from its image, the reference's map layout) whose keys mix to the
+                          DUMP_SAMPLE / world smallest values of the rank -- a function of the rank's key set alone, so builds
+                          that agree dump the same k-mers -- sorted by key: key_hi / key_lo (float64, 32-bit halves of the
+                          big-endian key word), count and direction_bias (float32, exact u16), weighted_count (float32, as stored)
+    Integers are exact in float64; about 28 MiB in all at any world size.  The weightedCount values (weak_sample_weighted_count,
+    weak_histogram_weight, weak_digest[7]) are float sums whose last bits depend on the order of addition, as in the reference:
+    compare them within a tolerance and everything else bit for bit."""
+    import numpy as np
+    import kmernator_amd as ka
+    kb = (K + 3) // 4
+    assert kb <= 8          # one key word
+    vsize = 12              # KMR_VALUE_COUNT_DIR: u16 count @0, f32 weightedCount @4, u16 directionBias @8
+    buf = sp.image(ka.KMR_MAP_WEAK)
+
+    def gather(pos, nbytes, big=False):
+        """unsigned integers of nbytes at the byte positions pos of the image"""
+        v = np.zeros(pos.shape, dtype=np.uint64)
+        for j in range(nbytes):
+            v |= buf[pos + j].astype(np.uint64) << np.uint64(8 * (nbytes - 1 - j) if big else 8 * j)
+        return v
+
+    nb = int(buf[:8].view(np.uint64)[0])
+    offs = buf[16:16 + 8 * nb].view(np.uint64).astype(np.int64)
+    n = gather(offs, 4).astype(np.int64)                          # entries per bucket
+    ends = np.cumsum(n)
+    total = int(ends[-1]) if nb else 0
+    bucket = np.repeat(np.arange(nb, dtype=np.int64), n)           # every entry's bucket
+    slot = np.arange(total, dtype=np.int64) - (ends - n)[bucket]   # and its place in the bucket
+    keys = gather(offs[bucket] + 4 + slot * kb, kb, big=True)
+    sample = DUMP_SAMPLE // world
+    if total > sample:
+        sel = np.argpartition(_mix64(keys), sample - 1)[:sample]
+    else:
+        sel = np.arange(total, dtype=np.int64)
+    sel = sel[np.argsort(keys[sel], kind="stable")]
+    b = bucket[sel]
+    vpos = offs[b] + 4 + n[b] * kb + slot[sel] * vsize
+    k_sel = keys[sel]
+    del bucket, slot, keys
+
+    st = sp.stats()
+    dg = sp.digest(ka.KMR_MAP_WEAK)
+    counts, weights = sp.histogram(256)
+    arrays = {
+        "stats": np.array([st[f] for f in ("raw_kmers", "raw_good_kmers", "unique_kmers", "singleton_kmers", "discarded", "weak_entries",
+                                           "singleton_entries", "reads")], dtype=np.float64),
+        "weak_digest": np.array([dg["entries"], dg["count_sum"], dg["dir_sum"], dg["hash_sum"] >> 32, dg["hash_sum"] & 0xFFFFFFFF,
+                                 dg["hash_xor"] >> 32, dg["hash_xor"] & 0xFFFFFFFF, dg["weighted_sum"]], dtype=np.float64),
+        "weak_histogram": counts.astype(np.float64),
+        "weak_histogram_weight": weights.astype(np.float64),
+        "weak_sample_key_hi": (k_sel >> np.uint64(32)).astype(np.float64),
+        "weak_sample_key_lo": (k_sel & np.uint64(0xFFFFFFFF)).astype(np.float64),
+        "weak_sample_count": gather(vpos, 2).astype(np.float32),
+        "weak_sample_weighted_count": gather(vpos + 4, 4).astype(np.uint32).view(np.float32),
+        "weak_sample_direction_bias": gather(vpos + 8, 2).astype(np.float32),
+    }
+    assert total == st["weak_entries"], (total, st["weak_entries"])
+    files = {}
+    for name, a in arrays.items():
+        f = io.BytesIO()
+        np.save(f, a)
+        files[name] = f.getvalue()
+    size = sum(len(v) for v in files.values())
+    assert size <= DUMP_LIMIT // world, (size, DUMP_LIMIT // world)
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "_rank%d" % rank if world > 1 else ""
+    for name, data in files.items():
+        with open(os.path.join(out_dir, name + suffix + ".npy"), "wb") as f:
+            f.write(data)
 
 
 def main():
@@ -284,6 +382,10 @@ def main():
                             "what": "sum over ranks of kmr_get_stats and kmr_map_digest against the serial CPU oracle's (keys, counts, direction biases bit for bit; weightedCount sum within 1e-6)"}
     except Exception as e:      # the check must never cost a bench line
         oracle_check = {"error": repr(e)}
+
+    # the spectrum of the last timed step, before the PCIe-inclusive legs below build it again
+    if args.dump_outputs:
+        dump_outputs(sp, args.dump_outputs, rank, world)
 
     # PCIe-inclusive legs (t_build from "first byte of in-memory reads available"): the reads start in pinned host memory and
     # go to the device in eight pieces on a copy stream while the library's stream builds the pieces that have arrived.  Twice: as

@@ -4,9 +4,9 @@ Vectors are re-typed from the reference's own unit tests and self-test driver:
   test/TwoBitSequenceTest.cpp:119-170 (shiftLeft), :172-252 (reverseComplement),
   :285-350 (markups), test/KmerTest.cpp:253-306 (window extraction / last-byte mask),
   src/lookup3.h:981-1000 (driver5), plus the KATs SURVEY.md 8(c) generated from the
-  reference's lookup3.h + TwoBitSequence.cpp.  When oracle/_ref/libref_lookup3.so (the
-  reference's own lookup3.h compiled from /root/reference) is present the hash is also
-  cross-checked on random inputs.
+  reference's lookup3.h + TwoBitSequence.cpp.  The hash is also checked on random inputs
+  against the reference's own lookup3 (its answers stored in tests/golden/ref_lookup3_hashes.npz;
+  live as well when oracle/_ref/libref_lookup3.so, compiled from the reference checkout, is present).
 """
 import ctypes as C
 import os
@@ -14,7 +14,7 @@ import os
 import numpy as np
 import pytest
 
-from helpers import (REF_SO, default_config, oracle_lib, oracle_weighted_kmers, _ptr)
+from helpers import (GOLDEN, REF_SO, default_config, oracle_lib, oracle_weighted_kmers, _ptr)
 
 
 def compress(s):
@@ -163,21 +163,30 @@ def test_kmer_kats(k, fasta, fwd, rc, least, h, bucket, owner):
     assert can2.tobytes() == can.tobytes()
 
 
-@pytest.mark.skipif(not os.path.exists(REF_SO), reason="oracle/_ref not built (no reference checkout)")
 def test_hash_against_reference_lookup3():
-    ref = C.CDLL(REF_SO)
-    ref.ref_get_hash.restype = C.c_uint64
-    ref.ref_get_hash.argtypes = [C.c_char_p, C.c_uint64]
+    """2000 random keys of 1..40 bytes: the oracle's hash equals what the reference's own lookup3 gave for them
+    (tests/golden/ref_lookup3_hashes.npz, written by make_ref_lookup3_hashes.py), and when oracle/_ref is built, equals
+    what it gives live on the same keys."""
     lib = oracle_lib()
-    rng = np.random.default_rng(11)
-    for n in range(1, 41):
-        for _ in range(50):
-            key = rng.integers(0, 256, n, dtype=np.uint8).tobytes()
+    g = np.load(os.path.join(GOLDEN, "ref_lookup3_hashes.npz"))
+    ref = None
+    if os.path.exists(REF_SO):
+        ref = C.CDLL(REF_SO)
+        ref.ref_get_hash.restype = C.c_uint64
+        ref.ref_get_hash.argtypes = [C.c_char_p, C.c_uint64]
+    assert g["lengths"].size == 2000
+    end = 0
+    for n, h in zip(g["lengths"].tolist(), g["hashes"].tolist()):
+        key = g["keys"][end:end + n].tobytes()
+        end += n
+        assert lib.orc_hash(key, n) == h
+        if ref is not None:
             buf = C.create_string_buffer(key, n)   # 8-byte aligned copy -> the reference's aligned path
-            assert lib.orc_hash(key, n) == ref.ref_get_hash(buf, n)
+            assert ref.ref_get_hash(buf, n) == h
             # misaligned start exercises the reference's byte-wise path
             buf2 = C.create_string_buffer(b"x" + key, n + 1)
-            assert lib.orc_hash(key, n) == ref.ref_get_hash(C.cast(C.addressof(buf2) + 1, C.c_char_p), n)
+            assert ref.ref_get_hash(C.cast(C.addressof(buf2) + 1, C.c_char_p), n) == h
+    assert end == g["keys"].size
 
 
 def test_window_extraction_and_mask():
