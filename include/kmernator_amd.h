@@ -204,6 +204,15 @@ int kmr_lookup(kmr_handle *h, const uint8_t *packed_kmers, uint64_t n, uint32_t 
 int kmr_lookup_reads(kmr_handle *h, const char *bases, const uint64_t *offsets,
                      uint64_t n_reads, uint32_t *counts_out, const uint64_t *out_offsets);
 
+/* KmerSpectrum::getCount(kmer, true) / getCounts(KmerWeights&, true) (src/KmerSpectrum.h:670-680, 701-716; the reference's
+ * default, TrackingData::useWeightedByDefault, src/Kmer.cpp:77): weightedCount of the weak entry, else the singleton's
+ * (_weight - 1) / 254 (TrackingDataSingleton::getWeightedCount, src/KmerTrackingData.h:657-659), else 0.0.  One f64 per key;
+ * the weak value's f32 converts exactly.  Same keys, state rules and error codes as kmr_lookup. */
+int kmr_lookup_weighted(kmr_handle *h, const uint8_t *packed_kmers, uint64_t n, double *weights);
+/* The same per k-mer position of whole reads: weights_out[out_offsets[r] + i] as kmr_lookup_reads lays out its counts. */
+int kmr_lookup_reads_weighted(kmr_handle *h, const char *bases, const uint64_t *offsets, uint64_t n_reads,
+                              double *weights_out, const uint64_t *out_offsets);
+
 /* Trim and score whole reads against the weak map: ReadSelector::scoreAndTrimReads
  * (src/ReadSelector.h:1182-1207) = per-position counts (getValue :924-931, weak map only), cut at the first
  * N/X markup (_setNumKmers :1037-1047), first longest run of k-mers with count >= minimum_kmer_score
@@ -452,6 +461,10 @@ int kmr_insert_records(kmr_handle *h, const void *host_records, uint64_t n_recor
 int kmr_lookup_requests_dev(kmr_handle *h, const void *dev_bases, const void *dev_offsets, uint64_t n_reads, uint64_t total_bases,
                             void *dev_keys, void *dev_pos, uint64_t seg_capacity, void *dev_seg_counts);
 int kmr_lookup_keys_dev(kmr_handle *h, const void *dev_keys, uint64_t n, void *dev_counts);
+/* kmr_lookup_keys_weighted_dev: n keys in the form of kmr_lookup_keys_dev answered as KmerSpectrum::getCount(kmer, true)
+ * (src/KmerSpectrum.h:670-680, as kmr_lookup_weighted): f64 dev_weights[n].  Unlike kmr_lookup_keys_dev, which reads the weak map
+ * only (ReadSelector::getValue), it consults the weak map AND the singleton map.  Asynchronous on the handle's stream. */
+int kmr_lookup_keys_weighted_dev(kmr_handle *h, const void *dev_keys, uint64_t n, void *dev_weights);
 int kmr_scatter_counts_dev(kmr_handle *h, const void *dev_counts, const void *dev_pos, uint64_t n, void *dev_position_counts);
 int kmr_score_counts_dev(kmr_handle *h, const void *dev_bases, const void *dev_offsets, uint64_t n_reads, const void *dev_position_counts,
                          double minimum_kmer_score, int scoring_type, uint32_t *trim_offset, uint32_t *trim_length,

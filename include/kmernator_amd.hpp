@@ -7,6 +7,7 @@
  *     buildKmerSpectrum       buildKmerSpectrum(const ReadSet&)           :2081-2115 (flat arrays or a device ReadSet)
  *     purgeMinDepth           purgeMinDepth + optimize                     :1805-1815, :460-466
  *     getCount                getCount(kmer, false)                        :701-725
+ *     getCount(.., useWeights) getCount(kmer, useWeights) as double         :670-691, :701-716
  *     getRawKmers ...         :455-459
  *     subtractReference       :472-474
  *     getHistogram            Histogram(256).set(*this) + toString         :909-1071
@@ -143,6 +144,14 @@ public:
 	std::vector<uint32_t> getCount(const std::vector<uint8_t> &packedKmers) {
 		std::vector<uint32_t> out(packedKmers.size() / keyBytes());
 		if (!out.empty()) check(kmr_lookup(_h, packedKmers.data(), out.size(), out.data()), "kmr_lookup");
+		return out;
+	}
+	/* getCount(kmer, useWeights): with useWeights the weak entry's weightedCount, else the singleton's (_weight - 1) / 254,
+	 * else 0 (the reference's default, TrackingData::useWeightedByDefault); without, the counts above as double */
+	std::vector<double> getCount(const std::vector<uint8_t> &packedKmers, bool useWeights) {
+		if (!useWeights) { const std::vector<uint32_t> c = getCount(packedKmers); return std::vector<double>(c.begin(), c.end()); }
+		std::vector<double> out(packedKmers.size() / keyBytes());
+		if (!out.empty()) check(kmr_lookup_weighted(_h, packedKmers.data(), out.size(), out.data()), "kmr_lookup_weighted");
 		return out;
 	}
 	Histogram getHistogram(unsigned int zoomMax = 256, double logBase = 2.0) {

@@ -105,6 +105,15 @@ public:
 		requireHandle();
 		check(kmr_lookup(_handle.get(), &packedCanonicalKmers[0], counts.size(), &counts[0]), "kmr_lookup");
 	}
+	/* the same as getCounts(KmerWeights&, true) (src/KmerSpectrum.h:708-716): weak weightedCount, else the singleton's
+	 * (_weight - 1) / 254, else 0 */
+	void getCounts(const std::vector<uint8_t> &packedCanonicalKmers, std::vector<double> &weights) {
+		const size_t kb = KmerSizer::getByteSize();
+		weights.resize(packedCanonicalKmers.size() / kb);
+		if (weights.empty()) return;
+		requireHandle();
+		check(kmr_lookup_weighted(_handle.get(), &packedCanonicalKmers[0], weights.size(), &weights[0]), "kmr_lookup_weighted");
+	}
 
 	/* The artifact filter on the device, in place of FilterKnownOddities::applyFilter(reads) at apps/FilterReads.cpp:110-114:
 	 *     spectrum.applyArtifactFilter(reads, FilterKnownOddities::getArtifactFasta() [+ repeat / PhiX tables], cfg);

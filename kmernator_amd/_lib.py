@@ -73,6 +73,7 @@ EXPORTS = [
     "kmr_artifact_config_init", "kmr_artifact_filter_create", "kmr_artifact_filter_info", "kmr_artifact_filter_entries",
     "kmr_artifact_filter_free", "kmr_artifact_filter_apply",
     "kmr_tune", "kmr_set_stream_origin", "kmr_size_tracker", "kmr_exchange_unique_id", "kmr_exchange_init", "kmr_exchange_init_transport", "kmr_exchange_add_reads_dev", "kmr_exchange_add_read_batch", "kmr_exchange_stats", "kmr_copy_to_host", "kmr_copy_to_device", "kmr_sk_exchange_begin", "kmr_sk_exchange_counts", "kmr_sk_exchange_pack_dev", "kmr_sk_exchange_adopt_dev", "kmr_extract_by_owner_host", "kmr_insert_records", "kmr_reads_from_host", "kmr_reads_from_twobit", "kmr_reads_twobit", "kmr_lookup_requests_dev", "kmr_lookup_keys_dev", "kmr_scatter_counts_dev", "kmr_score_counts_dev",
+    "kmr_lookup_weighted", "kmr_lookup_reads_weighted", "kmr_lookup_keys_weighted_dev",
     "kmr_map_digest", "kmr_synth_reads_dev", "kmr_build_info", "kmr_sk_exchange_uniform", "kmr_sk_exchange_peer_uniform", "kmr_sk_exchange_range", "kmr_count_lists_prefix",
 ]
 
@@ -106,6 +107,8 @@ def load():
     lib.kmr_get_stats.argtypes = [vp, C.POINTER(KmrStats)]
     lib.kmr_lookup.argtypes = [vp, u8p, C.c_uint64, u32p]
     lib.kmr_lookup_reads.argtypes = [vp, vp, u64p, C.c_uint64, u32p, u64p]
+    lib.kmr_lookup_weighted.argtypes = [vp, u8p, C.c_uint64, f64p]
+    lib.kmr_lookup_reads_weighted.argtypes = [vp, vp, u64p, C.c_uint64, f64p, u64p]
     lib.kmr_image_size.argtypes = [vp, C.c_int, u64p]
     lib.kmr_write_image.argtypes = [vp, C.c_int, vp, C.c_uint64]
     lib.kmr_load_image.argtypes = [vp, C.c_int, vp, C.c_uint64]
@@ -145,6 +148,7 @@ def load():
     lib.kmr_reads_from_host.argtypes = [vp, vp, vp, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(vp)]
     lib.kmr_lookup_requests_dev.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64, vp, vp, C.c_uint64, vp]
     lib.kmr_lookup_keys_dev.argtypes = [vp, vp, C.c_uint64, vp]
+    lib.kmr_lookup_keys_weighted_dev.argtypes = [vp, vp, C.c_uint64, vp]
     lib.kmr_scatter_counts_dev.argtypes = [vp, vp, vp, C.c_uint64, vp]
     lib.kmr_score_counts_dev.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_double, C.c_int, u32p, u32p, C.POINTER(C.c_float), u8p]
     lib.kmr_artifact_config_init.argtypes = [C.POINTER(KmrArtifactConfig)]

@@ -694,14 +694,17 @@ template <int W> int merge_image_t(kmr_handle *h, DevMap &m, bool weakMap, const
 	return 0;
 }
 
-template <int W> int lookup_t(kmr_handle *h, const uint8_t *packed, uint64_t n, uint32_t *counts) {
-	uint8_t *dk; uint32_t *dc;
-	HIPCHK(h, dev_malloc((void **)&dk, std::max<uint64_t>(8, n * h->kb))); HIPCHK(h, dev_malloc((void **)&dc, std::max<uint64_t>(8, 4 * n)));
+/* packed host keys -> counts (u32) or weights (f64, getCount(kmer, true)); exactly one of the two outputs is given */
+template <int W> int lookup_t(kmr_handle *h, const uint8_t *packed, uint64_t n, uint32_t *counts, double *weights = nullptr) {
+	const uint64_t ob = counts ? 4 : 8;
+	uint8_t *dk; void *dc;
+	HIPCHK(h, dev_malloc((void **)&dk, std::max<uint64_t>(8, n * h->kb))); HIPCHK(h, dev_malloc((void **)&dc, std::max<uint64_t>(8, ob * n)));
 	HIPCHK(h, hipMemcpyAsync(dk, packed, n * h->kb, hipMemcpyHostToDevice, h->stream));
 	const uint32_t vw = h->ext ? 15 : 3;
-	hipLaunchKernelGGL(lookup_keys_kernel<W>, dim3(grid_for(n)), dim3(256), 0, h->stream, view_of<W>(h->weak, vw), view_of<W>(h->sing, vw), dk, n, h->hkb, dc);
+	hipLaunchKernelGGL(lookup_keys_kernel<W>, dim3(grid_for(n)), dim3(256), 0, h->stream, view_of<W>(h->weak, vw), view_of<W>(h->sing, vw), dk, n, h->hkb,
+	                   counts ? (uint32_t *)dc : nullptr, counts ? nullptr : (double *)dc);
 	HIPCHK(h, hipGetLastError());
-	HIPCHK(h, hipMemcpyAsync(counts, dc, 4 * n, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipMemcpyAsync(counts ? (void *)counts : (void *)weights, dc, ob * n, hipMemcpyDeviceToHost, h->stream));
 	HIPCHK(h, hipStreamSynchronize(h->stream));
 	hipFree(dk); hipFree(dc);
 	return 0;
@@ -734,6 +737,11 @@ template <int W> LutView<W> lut_of(kmr_handle *h) {
 template <int W> int lookup_reads_t(kmr_handle *h, const ReadsView &rv, uint32_t *dout, const uint64_t *dout_off, bool weak_only = false) {
 	LookupOp<W> op; const uint32_t vw = h->ext ? 15 : 3; op.weak_only = weak_only;
 	op.lut = weak_only ? lut_of<W>(h) : LutView<W>{nullptr, 0, 0};
+	op.weak = view_of<W>(h->weak, vw); op.sing = view_of<W>(h->sing, vw); op.out = dout; op.out_offsets = dout_off; op.first_read_idx = rv.first_read_idx;
+	return launch_extract<W, false>(h, rv, op);
+}
+template <int W> int lookup_reads_weighted_t(kmr_handle *h, const ReadsView &rv, double *dout, const uint64_t *dout_off) {
+	LookupWeightOp<W> op; const uint32_t vw = h->ext ? 15 : 3;
 	op.weak = view_of<W>(h->weak, vw); op.sing = view_of<W>(h->sing, vw); op.out = dout; op.out_offsets = dout_off; op.first_read_idx = rv.first_read_idx;
 	return launch_extract<W, false>(h, rv, op);
 }
@@ -2595,10 +2603,8 @@ int kmr_lookup(kmr_handle *h, const uint8_t *packed, uint64_t n, uint32_t *count
 	case 3: return lookup_t<3>(h, packed, n, counts); default: return lookup_t<4>(h, packed, n, counts); }
 }
 
-int kmr_lookup_reads(kmr_handle *h, const char *bases, const uint64_t *offsets, uint64_t n_reads, uint32_t *counts_out, const uint64_t *out_offsets) {
-	if (!h || !bases || !offsets || !counts_out || !out_offsets) return KMR_ERR_INVALID_ARG;
-	if (!h->finalized) return fail(h, KMR_ERR_STATE, "kmr_lookup_reads before kmr_finalize");
-	if (n_reads == 0) return KMR_OK;
+/* kmr_lookup_reads and kmr_lookup_reads_weighted: one output element (u32 count or f64 weight) per k-mer position */
+static int lookup_reads_host(kmr_handle *h, const char *bases, const uint64_t *offsets, uint64_t n_reads, void *out, const uint64_t *out_offsets, bool weighted) {
 	hipSetDevice(h->device);
 	StagedReads s; uint64_t total = 0;
 	int rc = stage_reads(h, bases, nullptr, offsets, n_reads, nullptr, s, total);
@@ -2606,18 +2612,48 @@ int kmr_lookup_reads(kmr_handle *h, const char *bases, const uint64_t *offsets, 
 	/* size of the output = last offset + k-mers of the last read */
 	uint64_t outN = 0;
 	for (uint64_t r = 0; r < n_reads; r++) { uint64_t L = offsets[r + 1] - offsets[r]; uint64_t nk = L >= h->k ? L - h->k + 1 : 0; outN = std::max(outN, out_offsets[r] + nk); }
-	uint32_t *dout; uint64_t *doff;
-	HIPCHK(h, dev_malloc((void **)&dout, std::max<uint64_t>(8, 4 * outN))); HIPCHK(h, dev_malloc((void **)&doff, 8 * n_reads));
-	HIPCHK(h, hipMemsetAsync(dout, 0, 4 * outN, h->stream));
+	const uint64_t eb = weighted ? 8 : 4;
+	void *dout; uint64_t *doff;
+	HIPCHK(h, dev_malloc((void **)&dout, std::max<uint64_t>(8, eb * outN))); HIPCHK(h, dev_malloc((void **)&doff, 8 * n_reads));
+	HIPCHK(h, hipMemsetAsync(dout, 0, eb * outN, h->stream));
 	HIPCHK(h, hipMemcpyAsync(doff, out_offsets, 8 * n_reads, hipMemcpyHostToDevice, h->stream));
 	ReadsView rv; rv.bases = s.b; rv.quals = nullptr; rv.offsets = s.o; rv.discarded = nullptr; rv.n_reads = n_reads; rv.stream_base = 0; rv.first_read_idx = 0; rv.u_start = rv.u_end = rv.u_read = nullptr; rv.n_units = 0;
 	{ int urc = prepare_units(h, rv); if (urc) { s.release(); return urc; } }
-	switch (h->W) { case 1: rc = lookup_reads_t<1>(h, rv, dout, doff); break; case 2: rc = lookup_reads_t<2>(h, rv, dout, doff); break;
-	case 3: rc = lookup_reads_t<3>(h, rv, dout, doff); break; default: rc = lookup_reads_t<4>(h, rv, dout, doff); }
-	if (!rc) { HIPCHK(h, hipMemcpyAsync(counts_out, dout, 4 * outN, hipMemcpyDeviceToHost, h->stream)); rc = sync_state(h); }
+	if (weighted) {
+		double *d = (double *)dout;
+		switch (h->W) { case 1: rc = lookup_reads_weighted_t<1>(h, rv, d, doff); break; case 2: rc = lookup_reads_weighted_t<2>(h, rv, d, doff); break;
+		case 3: rc = lookup_reads_weighted_t<3>(h, rv, d, doff); break; default: rc = lookup_reads_weighted_t<4>(h, rv, d, doff); }
+	} else {
+		uint32_t *d = (uint32_t *)dout;
+		switch (h->W) { case 1: rc = lookup_reads_t<1>(h, rv, d, doff); break; case 2: rc = lookup_reads_t<2>(h, rv, d, doff); break;
+		case 3: rc = lookup_reads_t<3>(h, rv, d, doff); break; default: rc = lookup_reads_t<4>(h, rv, d, doff); }
+	}
+	if (!rc) { HIPCHK(h, hipMemcpyAsync(out, dout, eb * outN, hipMemcpyDeviceToHost, h->stream)); rc = sync_state(h); }
 	else hipStreamSynchronize(h->stream);
 	hipFree(dout); hipFree(doff); s.release();
 	return rc;
+}
+int kmr_lookup_reads(kmr_handle *h, const char *bases, const uint64_t *offsets, uint64_t n_reads, uint32_t *counts_out, const uint64_t *out_offsets) {
+	if (!h || !bases || !offsets || !counts_out || !out_offsets) return KMR_ERR_INVALID_ARG;
+	if (!h->finalized) return fail(h, KMR_ERR_STATE, "kmr_lookup_reads before kmr_finalize");
+	if (n_reads == 0) return KMR_OK;
+	return lookup_reads_host(h, bases, offsets, n_reads, counts_out, out_offsets, false);
+}
+
+int kmr_lookup_weighted(kmr_handle *h, const uint8_t *packed, uint64_t n, double *weights) {
+	if (!h || (n && (!packed || !weights))) return KMR_ERR_INVALID_ARG;
+	if (!h->finalized) return fail(h, KMR_ERR_STATE, "kmr_lookup_weighted before kmr_finalize");
+	if (n == 0) return KMR_OK;
+	hipSetDevice(h->device);
+	switch (h->W) { case 1: return lookup_t<1>(h, packed, n, nullptr, weights); case 2: return lookup_t<2>(h, packed, n, nullptr, weights);
+	case 3: return lookup_t<3>(h, packed, n, nullptr, weights); default: return lookup_t<4>(h, packed, n, nullptr, weights); }
+}
+
+int kmr_lookup_reads_weighted(kmr_handle *h, const char *bases, const uint64_t *offsets, uint64_t n_reads, double *weights_out, const uint64_t *out_offsets) {
+	if (!h || !bases || !offsets || !weights_out || !out_offsets) return KMR_ERR_INVALID_ARG;
+	if (!h->finalized) return fail(h, KMR_ERR_STATE, "kmr_lookup_reads_weighted before kmr_finalize");
+	if (n_reads == 0) return KMR_OK;
+	return lookup_reads_host(h, bases, offsets, n_reads, weights_out, out_offsets, true);
 }
 
 }  // extern "C"
@@ -3599,6 +3635,19 @@ int kmr_lookup_keys_dev(kmr_handle *h, const void *dev_keys, uint64_t n, void *d
 	hipSetDevice(h->device);
 	const uint32_t vw = h->ext ? 15 : 3;
 #define LK(Wv) hipLaunchKernelGGL(lookup_words_kernel<Wv>, dim3(grid_for(n)), dim3(256), 0, h->stream, view_of<Wv>(h->weak, vw), lut_of<Wv>(h), (const uint64_t *)dev_keys, n, h->hkb, (uint32_t *)dev_counts)
+	switch (h->W) { case 1: LK(1); break; case 2: LK(2); break; case 3: LK(3); break; default: LK(4); }
+#undef LK
+	HIPCHK(h, hipGetLastError());
+	return KMR_OK;
+}
+int kmr_lookup_keys_weighted_dev(kmr_handle *h, const void *dev_keys, uint64_t n, void *dev_weights) {
+	if (!h || (n && (!dev_keys || !dev_weights))) return KMR_ERR_INVALID_ARG;
+	if (!h->finalized) return fail(h, KMR_ERR_STATE, "kmr_lookup_keys_weighted_dev before kmr_finalize");
+	if (n == 0) return KMR_OK;
+	hipSetDevice(h->device);
+	const uint32_t vw = h->ext ? 15 : 3;
+#define LK(Wv) hipLaunchKernelGGL(lookup_words_weight_kernel<Wv>, dim3(grid_for(n)), dim3(256), 0, h->stream, view_of<Wv>(h->weak, vw), view_of<Wv>(h->sing, vw), lut_of<Wv>(h), \
+	                          (const uint64_t *)dev_keys, n, h->hkb, (double *)dev_weights)
 	switch (h->W) { case 1: LK(1); break; case 2: LK(2); break; case 3: LK(3); break; default: LK(4); }
 #undef LK
 	HIPCHK(h, hipGetLastError());

@@ -47,7 +47,8 @@ static const int PD_THREADS = 1024, PD_RPT = 8, PD_LINE = 4;
 	KMR_EX_OP(W, false, InsertOp<W, false>) KMR_EX_OP(W, true, InsertOp<W, true>) \
 	KMR_EX_OP(W, false, LinearOp<W, false, false>) KMR_EX_OP(W, false, LinearOp<W, false, true>) \
 	KMR_EX_OP(W, true, LinearOp<W, true, false>) KMR_EX_OP(W, true, LinearOp<W, true, true>) \
-	KMR_T __global__ void extract_kernel<W, false, LookupOp<W>, false>(ReadsView, DevParams, LookupOp<W>);
+	KMR_T __global__ void extract_kernel<W, false, LookupOp<W>, false>(ReadsView, DevParams, LookupOp<W>); \
+	KMR_T __global__ void extract_kernel<W, false, LookupWeightOp<W>, false>(ReadsView, DevParams, LookupWeightOp<W>);
 
 /* build_mode 2: partition passes, owner scatter, count pass over k-mer records */
 #define KMR_PD(W, EXT, LEVEL) KMR_T __global__ void partition_direct_kernel<W, EXT, LEVEL, PD_THREADS, PD_RPT, PD_LINE>(PartSource<W>, PoolView, unsigned int *, const int, const int);

@@ -13,12 +13,15 @@
  *                     the exchange [_buildKmerSpectrumMPI src/DistributedFunctions.h:418-438]
  *     Op = LookupOp   per-position count lookup [ReadSelector::setKmerValues
  *                     src/ReadSelector.h:1064-1076]
+ *     Op = LookupWeightOp  per-position weighted count [KmerSpectrum::getCounts(KmerWeights&, true)
+ *                     src/KmerSpectrum.h:708-716]
  *  insert_records_kernel      records -> table  [StoreKmerMessageHeaderProcessor::process :323]
  *  rehash_kernel              table growth
  *  classify/scatter/sort/image kernels: table -> bucketed sorted maps in the
  *        reference's store() layout [purgeMinDepth src/KmerSpectrum.h:1805,
  *        KmerMapByKmerArrayPair::store src/Kmer.h:3143, resort :3079]
- *  lookup_keys_kernel         packed keys -> counts [getElementIfExists src/Kmer.h:2617]
+ *  lookup_keys_kernel         packed keys -> counts and/or weighted counts [getElementIfExists src/Kmer.h:2617,
+ *                             DataPointers::getCount src/KmerSpectrum.h:670-691]
  *
  * Mapping to CDNA4: one read per lane (64 reads per wavefront) so the fp64
  * weight recurrence -- sequential per read, and it decides which k-mers are
@@ -383,6 +386,17 @@ template <int W> __device__ __forceinline__ uint32_t maps_count(const MapView<W>
 	if (i >= 0) return sing.sweight[i] == 0 ? 0u : 1u;
 	return 0u;
 }
+/* DataPointers::getCount(true), src/KmerSpectrum.h:670-680: the weak entry's weightedCount (the f32 in word 1 of the value, in the
+ * 12-byte and the 60-byte layout alike), else the singleton's (_weight - 1) / 254 (TrackingDataSingleton::getWeightedCount,
+ * src/KmerTrackingData.h:657-659), else 0 */
+__device__ __forceinline__ double sing_weighted(uint32_t b) { return b == 0 ? 0.0 : (double)(int)(b - 1) / 254.0; }
+template <int W> __device__ __forceinline__ double maps_weight(const MapView<W> &weak, const MapView<W> &sing, const Key<W> &key, uint64_t hash) {
+	int64_t i = map_find<W>(weak, key, hash);
+	if (i >= 0) return (double)__uint_as_float(weak.vals[(uint64_t)i * weak.vw + 1]);
+	i = map_find<W>(sing, key, hash);
+	if (i >= 0) return sing_weighted(sing.sweight[i]);
+	return 0.0;
+}
 
 /* ----------------------------------------------------------------------- */
 /* compressBase (src/TwoBitSequence.cpp:124-147) without branches: 0..3 for ACGT/acgt, 4 = markup.
@@ -692,8 +706,8 @@ void extract_kernel(ReadsView rv, DevParams p, Op op) {
 template <int W, bool EXT> __device__ __forceinline__ bool op_keeps_all_owners(const InsertOp<W, EXT> &) { return false; }
 template <int W, bool EXT> __device__ __forceinline__ uint32_t op_fail_code(const InsertOp<W, EXT> &) { return ERR_TABLE_FULL; }
 
-/* Lookup accelerator for read scoring: the weak map once more as an open-addressed table, slot = {key words, count}
- * ((W + 1) u64), at most half full, slot index from the same lookup3 hash.  A sorted bucket costs ~7 dependent loads per
+/* Lookup accelerator for read scoring: the weak map once more as an open-addressed table, slot = {key words, value word}
+ * ((W + 1) u64; value word = count | weightedCount's f32 bits << 32), at most half full, slot index from the same lookup3 hash.  A sorted bucket costs ~7 dependent loads per
  * k-mer (two bucket bounds, the binary search, the value); a slot of this table is one 16-byte load at k <= 32.  Built on the
  * first scoring call after a finalize (lut_build_kernel), dropped when the map changes. */
 template <int W> struct LutView { const uint64_t *slots; uint64_t mask; uint32_t shift; };
@@ -702,6 +716,27 @@ __host__ __device__ __forceinline__ uint64_t lut_slot(uint64_t hash, uint32_t sh
  * canonical), but the first word of a longer key can be (k >= 64: T^32...A^32 is its own reverse complement): such keys
  * are not put into the table, lookups of them search the sorted buckets. */
 template <int W> __device__ __forceinline__ bool lut_holds(const Key<W> &key) { return W == 1 || key.w[0] != EMPTY_KEY; }
+/* the slot's value word of a key the table holds; false when the weak map does not have the key */
+template <int W> __device__ __forceinline__ bool lut_find(const LutView<W> &t, const Key<W> &key, uint64_t hash, uint64_t &val) {
+	uint64_t s = lut_slot(hash, t.shift);
+	for (;;) {
+		const uint64_t *p = t.slots + s * (W + 1);
+		if (W == 1) {
+			const ulonglong2 v = *(const ulonglong2 *)p;
+			if (v.x == key.w[0]) { val = v.y; return true; }
+			if (v.x == EMPTY_KEY) return false;
+		} else {
+			const uint64_t k0 = p[0];
+			if (k0 == EMPTY_KEY) return false;
+			bool eq = k0 == key.w[0];
+#pragma unroll
+			for (int i = 1; i < W; i++) eq = eq && p[i] == key.w[i];
+			if (eq) { val = p[W]; return true; }
+		}
+		s = (s + 1) & t.mask;
+	}
+}
+/* (lut_find's search once more: the count path's instances keep the code they had) */
 template <int W> __device__ __forceinline__ uint32_t lut_count(const LutView<W> &t, const Key<W> &key, uint64_t hash) {
 	uint64_t s = lut_slot(hash, t.shift);
 	for (;;) {
@@ -734,7 +769,7 @@ __global__ void lut_build_kernel(MapView<W> weak, uint64_t n, uint64_t *slots, u
 			if (atomicCAS(p, (unsigned long long)EMPTY_KEY, (unsigned long long)key.w[0]) == (unsigned long long)EMPTY_KEY) {
 #pragma unroll
 				for (int j = 1; j < W; j++) p[j] = key.w[j];
-				p[W] = weak.vals[i * weak.vw] & 0xffffu;
+				p[W] = (weak.vals[i * weak.vw] & 0xffffu) | (uint64_t)weak.vals[i * weak.vw + 1] << 32;
 				break;
 			}
 			s = (s + 1) & mask;
@@ -776,12 +811,44 @@ template <int W> struct LookupOp {
 template <int W> __device__ __forceinline__ bool op_keeps_all_owners(const LookupOp<W> &) { return true; }
 template <int W> __device__ __forceinline__ uint32_t op_fail_code(const LookupOp<W> &) { return 0; }
 
+/* LookupOp's weighted sibling: DataPointers::getCount(true) (maps_weight) as f64 per k-mer position, at the positions LookupOp
+ * writes its counts (KmerSpectrum::getCounts(KmerWeights&, true), src/KmerSpectrum.h:708-716).  A type of its own, so that the
+ * count lookup's instance stays the code it was. */
+template <int W> struct LookupWeightOp {
+	MapView<W> weak, sing;
+	double *out;
+	const uint64_t *out_offsets;   /* per read, indexed by global read index - first_read_idx */
+	uint64_t first_read_idx;
+	static const bool NEEDS_WEIGHT = false;
+	static const bool COUNTS_STATS = false;
+	static const bool NEEDS_HASH = true;
+	struct State {};
+	__device__ __forceinline__ void wave_begin(State &, int) const {}
+	__device__ __forceinline__ void wave_end(State &, int) const {}
+	__device__ __forceinline__ void tile_begin(State &, uint32_t *, uint64_t, int) const {}
+	__device__ __forceinline__ void tile_end(State &, uint64_t, int) const {}
+	__device__ __forceinline__ void emit(State &, bool valid, const DevParams &, const Key<W> &key, uint64_t hash, const Occurrence &,
+	                                     uint64_t readIdx, uint32_t pos, unsigned &, bool &) const {
+		if (valid) out[out_offsets[readIdx - first_read_idx] + pos] = maps_weight<W>(weak, sing, key, hash);
+	}
+};
+template <int W> __device__ __forceinline__ bool op_keeps_all_owners(const LookupWeightOp<W> &) { return true; }
+template <int W> __device__ __forceinline__ uint32_t op_fail_code(const LookupWeightOp<W> &) { return 0; }
+
+/* packed host keys: getCount(kmer, false) into counts and getCount(kmer, true) into weights, either one null when not wanted
+ * (one search of the maps serves both) */
 template <int W>
-__global__ void lookup_keys_kernel(MapView<W> weak, MapView<W> sing, const uint8_t *packed, uint64_t n, uint32_t kb, uint32_t *out) {
+__global__ void lookup_keys_kernel(MapView<W> weak, MapView<W> sing, const uint8_t *packed, uint64_t n, uint32_t kb, uint32_t *counts, double *weights) {
 	for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
 		Key<W> key;
 		key_from_bytes<W>(key, packed + i * (kb & 0xffffu), kb & 0xffffu);      /* (kb carries the hash kind above bit 16) */
-		out[i] = maps_count<W>(weak, sing, key, key_hash<W>(key, kb));
+		const uint64_t hash = key_hash<W>(key, kb);
+		uint32_t c = 0u; double w = 0.0;
+		int64_t e = map_find<W>(weak, key, hash);
+		if (e >= 0) { c = weak.vals[(uint64_t)e * weak.vw] & 0xffffu; w = (double)__uint_as_float(weak.vals[(uint64_t)e * weak.vw + 1]); }
+		else if ((e = map_find<W>(sing, key, hash)) >= 0) { const uint32_t b = sing.sweight[e]; c = b == 0 ? 0u : 1u; w = sing_weighted(b); }
+		if (counts) counts[i] = c;
+		if (weights) weights[i] = w;
 	}
 }
 
@@ -797,6 +864,26 @@ __global__ void lookup_words_kernel(MapView<W> weak, LutView<W> lut, const uint6
 		if (lut.slots && lut_holds<W>(key)) { out[i] = lut_count<W>(lut, key, hash); continue; }
 		const int64_t e = map_find<W>(weak, key, hash);
 		out[i] = e >= 0 ? (weak.vals[(uint64_t)e * weak.vw] & 0xffffu) : 0u;
+	}
+}
+/* the same keys answered as KmerSpectrum::getCount(kmer, true) (maps_weight): weak map, then singleton map.  The table holds
+ * every weak key that lut_holds admits, with weightedCount in its value word, so a key it holds is answered by its slot and a
+ * miss goes straight to the singleton map; the other keys (or no table) search the weak map's buckets first. */
+template <int W>
+__global__ void lookup_words_weight_kernel(MapView<W> weak, MapView<W> sing, LutView<W> lut, const uint64_t *keys, uint64_t n, uint32_t kb, double *out) {
+	for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+		Key<W> key;
+#pragma unroll
+		for (int j = 0; j < W; j++) key.w[j] = keys[i * W + j];
+		const uint64_t hash = key_hash<W>(key, kb);
+		if (lut.slots && lut_holds<W>(key)) {
+			uint64_t v;
+			if (lut_find<W>(lut, key, hash, v)) { out[i] = (double)__uint_as_float((uint32_t)(v >> 32)); continue; }
+			const int64_t e = map_find<W>(sing, key, hash);
+			out[i] = e >= 0 ? sing_weighted(sing.sweight[e]) : 0.0;
+			continue;
+		}
+		out[i] = maps_weight<W>(weak, sing, key, hash);
 	}
 }
 /* processRespond (:848-854): the answer to request i belongs to the k-mer at position pos[i] of the read batch */

@@ -271,6 +271,10 @@ class KmerSpectrum:
     def lookup_keys(self, keys, n, counts):
         self._call("lookup_keys_dev", self.h, keys.data_ptr(), n, counts.data_ptr())
 
+    def lookup_keys_weighted(self, keys, n, weights):
+        """lookup_keys answered as KmerSpectrum::getCount(kmer, true): weights (f64) from the weak map, else the singleton map."""
+        self._call("lookup_keys_weighted_dev", self.h, keys.data_ptr(), n, weights.data_ptr())
+
     def scatter_counts(self, counts, pos, n, position_counts):
         self._call("scatter_counts_dev", self.h, counts.data_ptr(), pos.data_ptr(), n, position_counts.data_ptr())
 
@@ -311,10 +315,17 @@ class KmerSpectrum:
         self._call("num_buckets", self.h, which, C.byref(v))
         return v.value
 
-    def getCount(self, packed_kmers):
-        """KmerSpectrum::getCount(kmer, false) for packed canonical k-mers [n, kb]."""
+    def getCount(self, packed_kmers, useWeights=False):
+        """KmerSpectrum::getCount(kmer, useWeights) for packed canonical k-mers [n, kb]: u32 counts, or with useWeights f64
+        weighted counts (weak weightedCount, else the singleton's (_weight - 1) / 254, else 0).  The reference's own default
+        is the weighted form (TrackingData::useWeightedByDefault); this wrapper's has always been the count."""
         keys = _u8(packed_kmers)
         n = keys.size // self.kb
+        if useWeights:
+            out = np.zeros(n, dtype=np.float64)
+            if n:
+                self._call("lookup_weighted", self.h, keys.ctypes.data_as(C.POINTER(C.c_uint8)), n, out.ctypes.data_as(C.POINTER(C.c_double)))
+            return out
         out = np.zeros(n, dtype=np.uint32)
         if n:
             self._call("lookup", self.h, keys.ctypes.data_as(C.POINTER(C.c_uint8)), n, out.ctypes.data_as(C.POINTER(C.c_uint32)))
@@ -322,8 +333,9 @@ class KmerSpectrum:
 
     lookup = getCount
 
-    def getCountsForReads(self, bases, offsets):
-        """Per-position counts of every read (ReadSelector::setKmerValues)."""
+    def getCountsForReads(self, bases, offsets, useWeights=False):
+        """Per-position counts of every read (ReadSelector::setKmerValues); with useWeights the f64 weighted counts of
+        getCount(kmer, true) at the same positions (KmerSpectrum::getCounts(KmerWeights&, true), the reference's default)."""
         bases = _u8(bases)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         n = offsets.size - 1
@@ -331,10 +343,11 @@ class KmerSpectrum:
         nk = np.maximum(lens - self.k + 1, 0).astype(np.uint64)
         out_off = np.zeros(n + 1, dtype=np.uint64)
         np.cumsum(nk, out=out_off[1:])
-        out = np.zeros(int(out_off[-1]), dtype=np.uint32)
+        name, dt, ct = ("lookup_reads_weighted", np.float64, C.c_double) if useWeights else ("lookup_reads", np.uint32, C.c_uint32)
+        out = np.zeros(int(out_off[-1]), dtype=dt)
         if n:
-            self._call("lookup_reads", self.h, bases.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), n,
-                       out.ctypes.data_as(C.POINTER(C.c_uint32)), out_off.ctypes.data_as(C.POINTER(C.c_uint64)))
+            self._call(name, self.h, bases.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), n,
+                       out.ctypes.data_as(C.POINTER(ct)), out_off.ctypes.data_as(C.POINTER(C.c_uint64)))
         return out, out_off
 
     SCORING = {"SUM": 0, "MEDIAN": 1, "MIN": 2, "MAX": 3, "AVG": 4}

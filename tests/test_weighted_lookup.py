@@ -1,0 +1,291 @@
+"""Weighted k-mer lookups: KmerSpectrum::getCount(kmer, true) / getCounts(KmerWeights&, true) (src/KmerSpectrum.h:670-716),
+the reference's default form (TrackingData::useWeightedByDefault, src/Kmer.cpp:77).  A weak entry answers its f32
+weightedCount, a singleton (_weight - 1) / 254 (src/KmerTrackingData.h:657-659), an absent k-mer 0.0; every answer is compared
+bit for bit with the bytes of a stored map."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import kmernator_amd as ka
+from kmernator_amd import _lib
+from helpers import (KMR_MAP_SINGLETON, KMR_MAP_WEAK, KMR_VALUE_EXT, OracleSpectrum, ReadBatch, default_config,
+                     oracle_weighted_kmers, parse_image, synth_reads)
+
+KMR_ERR_INVALID_ARG, KMR_ERR_STATE = -1, -5
+NEW_ENTRIES = ("kmr_lookup_weighted", "kmr_lookup_reads_weighted", "kmr_lookup_keys_weighted_dev")
+
+
+# ------------------------------------------------------------------------------------------------------------------ CPU
+def test_weighted_entry_points_are_exported_and_bound():
+    lib = ka.load()
+    for name in NEW_ENTRIES:
+        assert name in _lib.EXPORTS
+        assert getattr(lib, name).argtypes is not None, name
+    for meth in ("getCount", "getCountsForReads", "lookup_keys_weighted"):
+        assert callable(getattr(ka.KmerSpectrum, meth)), meth
+    import inspect
+    for meth in ("getCount", "getCountsForReads"):
+        p = inspect.signature(getattr(ka.KmerSpectrum, meth)).parameters["useWeights"]
+        assert p.default is False        # the wrapper's default stays the count
+
+
+def test_weighted_entry_points_refuse_bad_arguments_without_a_device():
+    lib = ka.load()
+    d = C.c_double()
+    u = C.c_uint64(0)
+    assert lib.kmr_lookup_weighted(None, None, 0, None) == KMR_ERR_INVALID_ARG
+    assert lib.kmr_lookup_weighted(None, None, 4, C.byref(d)) == KMR_ERR_INVALID_ARG
+    assert lib.kmr_lookup_reads_weighted(None, b"ACGT", C.byref(u), 0, C.byref(d), C.byref(u)) == KMR_ERR_INVALID_ARG
+    assert lib.kmr_lookup_keys_weighted_dev(None, None, 0, None) == KMR_ERR_INVALID_ARG
+
+
+def test_no_gpu_means_loud_failure_for_weighted_lookups():
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("GPU present")
+    with pytest.raises(ka.KmerSpectrumError, match="NO_DEVICE"):
+        ka.KmerSpectrum(ka.default_config(31)).getCount(np.zeros((1, 8), np.uint8), useWeights=True)
+
+
+# ------------------------------------------------------------------------------------------------------------------ GPU
+def product(cfg, mode=0, **tune):
+    c = ka.default_config(cfg.k)
+    for name, _ in cfg._fields_:
+        setattr(c, name, getattr(cfg, name))
+    c.build_mode = mode
+    return ka.KmerSpectrum(c).tune(**tune)
+
+
+def image_entries(img, kb, singleton, ext):
+    """keys [n, kb] and the weighted answer each entry must give, from a stored map's bytes"""
+    vsize = (5 if ext else 1) if singleton else (60 if ext else 12)
+    _, _, buckets = parse_image(img, kb, vsize)
+    keys = np.concatenate([b[0] for b in buckets]) if buckets else np.zeros((0, kb), np.uint8)
+    vals = np.concatenate([b[1] for b in buckets]) if buckets else np.zeros((0, vsize), np.uint8)
+    if singleton:
+        w8 = vals[:, 0].astype(np.float64)
+        want = np.where(w8 != 0, (w8 - 1.0) / 254.0, 0.0)
+        cnt = (w8 != 0).astype(np.uint32)
+    else:
+        want = np.ascontiguousarray(vals[:, 4:8]).view(np.float32).reshape(-1).astype(np.float64)
+        cnt = np.ascontiguousarray(vals[:, 0:2]).view(np.uint16).reshape(-1).astype(np.uint32)
+    return np.ascontiguousarray(keys), want, cnt
+
+
+def absent_keys(k, present, n=64, seed=5):
+    """random canonical-looking keys that neither map holds (the unused low bits of the last byte stay zero)"""
+    rng = np.random.default_rng(seed)
+    kb = (k + 3) // 4
+    keys = rng.integers(0, 256, size=(n, kb), dtype=np.uint8)
+    if k % 4:
+        keys[:, -1] &= np.uint8((0xff << (2 * (4 - k % 4))) & 0xff)
+    have = {bytes(r) for r in present}
+    return keys[[bytes(r) not in have for r in keys]]
+
+
+def same_bits(a, b):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
+
+
+def noisy_ragged_reads(k, n, seed):
+    rl = max(100, k + 40)
+    rb = synth_reads(n, read_len=rl, seed=seed, quality="noisy", n_rate=0.003)
+    rng = np.random.default_rng(seed)
+    seqs, quals = [], []
+    for i in range(rb.n):
+        L = rl
+        r = rng.random()
+        if r < 0.05:
+            L = int(rng.integers(0, k + 3))        # shorter than k, some empty
+        elif r < 0.3:
+            L = int(rng.integers(k, rl + 1))
+        seqs.append(rb.seq(i)[:L])
+        quals.append(rb.qual(i)[:L])
+    return ReadBatch(seqs, quals)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ext", [False, True])
+@pytest.mark.parametrize("mode", [1, 2, 3])
+@pytest.mark.parametrize("k", [21, 31, 32, 33, 51, 64, 65, 95, 127])
+def test_weighted_lookup_matches_own_image(k, mode, ext):
+    """getCount(keys, useWeights=True) against the handle's own weak and singleton images; the count path unchanged; the
+    reads form agrees position by position with the keyed form"""
+    rb = noisy_ragged_reads(k, 1200, seed=k + 7 * mode)
+    cfg = default_config(k, estimated_raw_kmers=1200 * 140, value_kind=KMR_VALUE_EXT if ext else 0)
+    p = product(cfg, mode)
+    p.buildKmerSpectrum(rb.bases, rb.quals, rb.offsets, 0, rb.discarded)
+    p.finalize(1)          # min_depth 1 keeps the singleton map
+    kw, ww, cw = image_entries(p.image(KMR_MAP_WEAK), p.kb, False, ext)
+    ks, ws, cs = image_entries(p.image(KMR_MAP_SINGLETON), p.kb, True, ext)
+    assert len(kw) > 0 and len(ks) > 0
+    ka_ = absent_keys(k, np.concatenate([kw, ks]))
+    keys = np.concatenate([kw, ks, ka_])
+    want = np.concatenate([ww, ws, np.zeros(len(ka_))])
+    got = p.getCount(keys, useWeights=True)
+    assert got.dtype == np.float64
+    assert same_bits(got, want)
+    cnt = p.getCount(keys)
+    assert cnt.dtype == np.uint32
+    assert np.array_equal(cnt, np.concatenate([cw, cs, np.zeros(len(ka_), np.uint32)]))
+    assert np.all(got[cnt == 0] == 0.0)
+
+    # reads form: same layout as the counts, every position = the keyed answer of its canonical k-mer
+    wr, off_w = p.getCountsForReads(rb.bases, rb.offsets, useWeights=True)
+    cr, off_c = p.getCountsForReads(rb.bases, rb.offsets)
+    assert wr.dtype == np.float64 and np.array_equal(off_w, off_c) and wr.size == cr.size
+    assert np.all(wr[cr == 0] == 0.0)
+    checked = with_n = 0
+    for i in range(rb.n):
+        s, q = rb.seq(i), rb.qual(i)
+        lo, hi = int(off_w[i]), int(off_w[i + 1])
+        if len(s) < k:
+            assert hi == lo
+            continue
+        if checked >= 40 and (with_n >= 3 or b"N" not in s):
+            continue
+        # the k-mers of the read as the lookup sees them (a markup base is looked up as the 'A' compressSequence stores)
+        kk, _, _ = oracle_weighted_kmers(cfg, s, q)
+        assert len(kk) == hi - lo
+        assert same_bits(wr[lo:hi], p.getCount(kk, useWeights=True))
+        assert np.array_equal(cr[lo:hi], p.getCount(kk))
+        checked += 1
+        with_n += b"N" in s
+    assert checked > 10 and with_n > 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ext", [False, True])
+@pytest.mark.parametrize("k", [21, 33, 65, 127])
+def test_weighted_lookup_of_oracle_images(k, ext):
+    """the oracle's images loaded into a product handle: weighted answers equal the oracle's own entries (no ordering freedom:
+    the stored f32 and _weight bytes are what is looked up), counts still equal the oracle's lookups"""
+    rb = noisy_ragged_reads(k, 1500, seed=3 * k)
+    cfg = default_config(k, estimated_raw_kmers=1500 * 140, value_kind=KMR_VALUE_EXT if ext else 0)
+    o = OracleSpectrum(cfg)
+    o.add_reads(rb)
+    o.finalize(1)
+    p = product(cfg)
+    p.load_image(KMR_MAP_WEAK, o.image(KMR_MAP_WEAK))
+    p.load_image(KMR_MAP_SINGLETON, o.image(KMR_MAP_SINGLETON))
+    ko, cnt_o, _, w_o, _ = o.entries()
+    assert len(ko) > 0
+    assert same_bits(p.getCount(ko, useWeights=True), w_o.astype(np.float64))
+    ks, ws, _ = image_entries(o.image(KMR_MAP_SINGLETON), p.kb, True, ext)
+    assert len(ks) > 0
+    assert same_bits(p.getCount(ks, useWeights=True), ws)
+    ka_ = absent_keys(k, np.concatenate([ko, ks]))
+    keys = np.concatenate([ko, ks, ka_])
+    got = p.getCount(keys, useWeights=True)
+    assert np.all(got[len(ko) + len(ks):] == 0.0)
+    cnt = p.getCount(keys)
+    assert np.array_equal(cnt, o.lookup(keys))
+    assert np.all(got[cnt == 0] == 0.0)
+
+
+@pytest.mark.gpu
+def test_weighted_entries_before_finalize_are_state_errors():
+    import torch
+    p = ka.KmerSpectrum(ka.default_config(31, device=0))
+    lib, h = ka.load(), p.h
+    key = np.zeros(8, np.uint8)
+    w = np.zeros(4, np.float64)
+    off = np.array([0, 40], np.uint64)
+    oo = np.zeros(1, np.uint64)
+    dk = torch.zeros(4, dtype=torch.int64, device="cuda:0")
+    dw = torch.zeros(4, dtype=torch.float64, device="cuda:0")
+    assert lib.kmr_lookup_weighted(h, key.ctypes.data_as(C.POINTER(C.c_uint8)), 1, w.ctypes.data_as(C.POINTER(C.c_double))) == KMR_ERR_STATE
+    assert lib.kmr_lookup_reads_weighted(h, b"A" * 40, off.ctypes.data_as(C.POINTER(C.c_uint64)), 1, w.ctypes.data_as(C.POINTER(C.c_double)),
+                                         oo.ctypes.data_as(C.POINTER(C.c_uint64))) == KMR_ERR_STATE
+    assert lib.kmr_lookup_keys_weighted_dev(h, dk.data_ptr(), 1, dw.data_ptr()) == KMR_ERR_STATE
+    with pytest.raises(ka.KmerSpectrumError, match="STATE"):
+        p.getCount(key, useWeights=True)
+    # n == 0 is a no-op once the maps exist
+    p.finalize(2)
+    assert lib.kmr_lookup_weighted(h, None, 0, None) == 0
+    assert lib.kmr_lookup_keys_weighted_dev(h, None, 0, None) == 0
+
+
+def words_to_packed(words, kb):
+    """Key<W>::w words (big-endian bytes of the packed key, zero padded) -> packed keys [n, kb]"""
+    n, W = words.shape
+    return np.ascontiguousarray(words.astype(">u8").view(np.uint8).reshape(n, 8 * W)[:, :kb])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", [31, 127])
+def test_weighted_device_lookup_three_owners(k):
+    """kmr_lookup_keys_weighted_dev on the owner side of the distributed request path (three owners on one GPU): each owner's
+    answers equal its keyed weighted lookups, through the lookup table and through the bucket search"""
+    import torch
+    world, n = 3, 12000
+    rl = k + 60
+    rb = synth_reads(n, read_len=rl, genome_len=4 * n, seed=11, quality="noisy", n_rate=0.002)
+    seqs = [rb.seq(i) for i in range(rb.n)]
+    quals = [rb.qual(i) for i in range(rb.n)]
+    if k == 127:
+        # T^32 A^95: canonical, and the first key word is all ones -- the lookup table cannot hold it (lut_holds)
+        hot = b"T" * 32 + b"A" * 95
+        for _ in range(5):
+            seqs.append(b"C" * 10 + hot + b"G" * 10)
+            quals.append(b"I" * (len(hot) + 20))
+    rb = ReadBatch(seqs, quals)
+    n = rb.n
+    dev = torch.device("cuda", 0)
+    tb = torch.from_numpy(np.concatenate([rb.bases, np.zeros(64, np.uint8)])).to(dev)
+    tq = torch.from_numpy(np.concatenate([rb.quals, np.zeros(64, np.uint8)])).to(dev)
+    to = torch.from_numpy(rb.offsets.astype(np.int64)).to(dev)
+    total = int(rb.offsets[-1])
+    owners = []
+    for r in range(world):
+        s = ka.KmerSpectrum(ka.default_config(k, estimated_raw_kmers=n * rl, device=0, rank=r, world_size=world))
+        s.buildKmerSpectrumDevice(tb.data_ptr(), tq.data_ptr(), to.data_ptr(), n, total, 0)
+        s.finalize(1)
+        owners.append(s)
+    kb = owners[0].kb
+    words = (kb + 7) // 8
+    seg_cap = total
+    keys = torch.empty((world, seg_cap, words), dtype=torch.int64, device=dev)
+    pos = torch.empty((world, seg_cap), dtype=torch.int32, device=dev)
+    cnt = torch.zeros(world, dtype=torch.int64, device=dev)
+    req = owners[1]
+    torch.cuda.synchronize()
+    req.lookup_requests(tb, to, 0, n, total, keys, pos, seg_cap, cnt)
+    req.sync()
+    sc = [int(x) for x in cnt.cpu().tolist()]
+    assert min(sc) > 0.2 * sum(sc)
+    hot_seen = False
+    n_weak = n_sing = 0
+    for s in range(world):
+        packed = words_to_packed(keys[s, :sc[s]].cpu().numpy().view(np.uint64), kb)
+        want = owners[s].getCount(packed, useWeights=True)
+        c = owners[s].getCount(packed)
+        sk, _, _ = image_entries(owners[s].image(KMR_MAP_SINGLETON), kb, True, False)
+        sing = {bytes(r) for r in sk}
+        n_weak += int((c > 1).sum())
+        n_sing += sum(bytes(r) in sing for r in packed)
+        for lut in (1, 0):
+            owners[s].tune(lookup_table=lut)
+            ans = torch.full((sc[s],), -1.0, dtype=torch.float64, device=dev)
+            torch.cuda.synchronize()
+            owners[s].lookup_keys_weighted(keys[s], sc[s], ans)
+            owners[s].sync()
+            assert same_bits(ans.cpu().numpy(), want), (s, lut)
+        # the count form of the same requests is still the weak-map-only count
+        ans_c = torch.zeros(sc[s], dtype=torch.int32, device=dev)
+        torch.cuda.synchronize()
+        owners[s].lookup_keys(keys[s], sc[s], ans_c)
+        owners[s].sync()
+        wk, _, cw = image_entries(owners[s].image(KMR_MAP_WEAK), kb, False, False)
+        weak_of = {bytes(r): int(v) for r, v in zip(wk, cw)}
+        assert np.array_equal(ans_c.cpu().numpy().astype(np.uint32), np.array([weak_of.get(bytes(r), 0) for r in packed], np.uint32))
+        if k == 127:
+            hit = np.all(packed[:, :8] == 0xff, axis=1)
+            if hit.any():
+                hot_seen = True
+                assert np.all(want[hit] > 1.0)       # a weak entry, answered by the bucket search
+    assert n_weak > 0 and n_sing > 0
+    if k == 127:
+        assert hot_seen
