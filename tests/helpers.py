@@ -567,7 +567,7 @@ def full_size_golden(name):
     """tests/golden/full_size_digests.json[name] (written by tests/golden/make_full_size_digests.py from the oracle)"""
     import json
     with open(os.path.join(GOLDEN, "full_size_digests.json")) as f:
-        return json.load(f)[name]
+        return dict(json.load(f)[name], name=name)
 
 
 def oracle_extract_by_owner(cfg, rb, seg_capacity):
@@ -607,3 +607,229 @@ def oracle_parse_fastq(text, start_char=33, input_base=33, store_comment=True):
     rb = ReadBatch.from_arrays(bases[:tot].copy(), quals[:tot].copy(), offsets[:n + 1].copy())
     rb.names = [text[int(noff[i]):int(noff[i]) + int(nlen[i])] for i in range(n)]
     return rb, fb.value
+
+
+# ---------------------------------------------------------------- weight profiles
+# weightedCount is a float sum whose order of addition the reference does not fix, so the map digest above leaves it out and
+# sums it over the whole map, where per-entry errors vanish in the slack.  A weight profile holds it per key-hash bin and per
+# sampled entry instead (tests/golden/full_size_weights.npz, written by tests/golden/make_full_size_weights.py).
+PROFILE_BINS = 2048          # chosen by the top 11 bits of key_mix
+PROFILE_SAMPLE = 2048        # the entries whose keys mix to the smallest values
+_BIN_SHIFT = np.uint64(64 - 11)
+
+
+def key_words(keys):
+    """packed keys [n, kb] -> big-endian uint64 words [n, W], zero padded (the word layout of digest_of_image)"""
+    n, kb = keys.shape
+    W = (kb + 7) // 8
+    padded = np.zeros((n, 8 * W), dtype=np.uint8)
+    padded[:, :kb] = keys
+    return padded.reshape(n, W, 8)[:, :, ::-1].copy().view(np.uint64).reshape(n, W)
+
+
+def key_mix(keys):
+    """x = 0; x = _dmix(x ^ word) over the key's big-endian words: depends on the key alone"""
+    words = key_words(np.asarray(keys, dtype=np.uint8))
+    x = np.zeros(words.shape[0], dtype=np.uint64)
+    for j in range(words.shape[1]):
+        x = _dmix(x ^ words[:, j])
+    return x
+
+
+def profile_bin(x):
+    """the bin of a key_mix value: its top 11 bits"""
+    return (x >> _BIN_SHIFT).astype(np.int64)
+
+
+def empty_profile(kb):
+    return {"entries": np.zeros(PROFILE_BINS, np.int64), "count_sum": np.zeros(PROFILE_BINS, np.int64),
+            "wsum": np.zeros(PROFILE_BINS, np.float64), "nwsum": np.zeros(PROFILE_BINS, np.float64),
+            "sample_keys": np.zeros((0, kb), np.uint8), "sample_count": np.zeros(0, np.uint32), "sample_w": np.zeros(0, np.float32)}
+
+
+def _profile_piece(keys, counts, weights):
+    keys = np.ascontiguousarray(keys, dtype=np.uint8)
+    counts = np.asarray(counts).astype(np.int64)
+    w = np.asarray(weights, dtype=np.float32)
+    x = key_mix(keys)
+    b = profile_bin(x)
+    w64 = w.astype(np.float64)
+    p = {"entries": np.bincount(b, minlength=PROFILE_BINS).astype(np.int64),
+         "count_sum": np.bincount(b, weights=counts, minlength=PROFILE_BINS).astype(np.int64),
+         "wsum": np.bincount(b, weights=w64, minlength=PROFILE_BINS),
+         "nwsum": np.bincount(b, weights=(counts + 2) * w64, minlength=PROFILE_BINS)}
+    take = np.argpartition(x, PROFILE_SAMPLE)[:PROFILE_SAMPLE] if x.size > PROFILE_SAMPLE else np.arange(x.size)
+    take = take[np.argsort(x[take], kind="stable")]
+    p.update(sample_keys=keys[take], sample_count=counts[take].astype(np.uint32), sample_w=w[take])
+    return p
+
+
+def add_profiles(a, b):
+    """profiles of disjoint key sets (parts, pieces of an image) combine into the union's: bins add, samples merge by smallest key_mix"""
+    out = {key: a[key] + b[key] for key in ("entries", "count_sum", "wsum", "nwsum")}
+    keys = np.concatenate([a["sample_keys"], b["sample_keys"]])
+    take = np.argsort(key_mix(keys), kind="stable")[:PROFILE_SAMPLE]
+    out["sample_keys"] = keys[take]
+    out["sample_count"] = np.concatenate([a["sample_count"], b["sample_count"]])[take]
+    out["sample_w"] = np.concatenate([a["sample_w"], b["sample_w"]])[take]
+    return out
+
+
+def weight_profile(keys, counts, weights):
+    """the weight profile of a weak map given as entries (OracleSpectrum.entries(): keys [n, kb], counts, f32 weightedCount)"""
+    return add_profiles(empty_profile(keys.shape[1]), _profile_piece(keys, counts, weights))
+
+
+def image_pieces(buf, kb, vsize, cols=None, buckets_per_piece=1 << 16):
+    """(keys [m, kb], values [m, cols]) of a stored map (parse_image's layout), a run of buckets at a time, without a Python loop
+    over buckets: what parse_image gives, for images of any size at a few hundred MB of working memory"""
+    cols = vsize if cols is None else cols
+    buf = np.asarray(buf, dtype=np.uint8)
+    nb = int(buf[:8].view(np.uint64)[0])
+    offs = buf[16:16 + 8 * nb].view(np.uint64).astype(np.int64)
+    for lo in range(0, nb, buckets_per_piece):
+        o = offs[lo:lo + buckets_per_piece]
+        n = buf[o[:, None] + np.arange(4)].copy().view(np.uint32).reshape(-1).astype(np.int64)
+        m = int(n.sum())
+        if m == 0:
+            continue
+        bi = np.repeat(np.arange(o.size), n)
+        i = np.arange(m) - np.repeat(np.cumsum(n) - n, n)
+        kstart = o[bi] + 4 + i * kb
+        vstart = o[bi] + 4 + n[bi] * kb + i * vsize
+        yield buf[kstart[:, None] + np.arange(kb)], buf[vstart[:, None] + np.arange(cols)]
+
+
+def weight_profile_of_image(buf, kb, ext=False, buckets_per_piece=1 << 16):
+    """the weight profile of a weak map from the bytes of its stored image (12- or 60-byte values: count u16 at 0, f32 at 4)"""
+    vsize = 60 if ext else 12
+    prof = empty_profile(kb)
+    for keys, vals in image_pieces(buf, kb, vsize, cols=8, buckets_per_piece=buckets_per_piece):
+        counts = np.ascontiguousarray(vals[:, 0:2]).view(np.uint16).reshape(-1)
+        w = np.ascontiguousarray(vals[:, 4:8]).view(np.float32).reshape(-1)
+        prof = add_profiles(prof, _profile_piece(keys, counts, w))
+    return prof
+
+
+def read_cut_keys(cfg, seed, reads, read_len, genome, noisy, n_end=256):
+    """canonical k-mers cut from positions 0, 60 and the last of the job's first and last n_end reads (duplicates dropped)"""
+    k = cfg.k
+    last = read_len - k
+    pos = sorted({0, min(60, last), last})
+    out = []
+    for first in (0, reads - n_end):
+        rb = synth_reads_8d(seed, first, n_end, read_len, genome, noisy, threads=1)
+        for i in range(rb.n):
+            kk, _, _ = oracle_weighted_kmers(cfg, rb.seq(i), rb.qual(i))
+            out.append(kk[pos])
+    keys = np.concatenate(out)
+    _, first_at = np.unique(keys_as_void(keys), return_index=True)
+    return np.ascontiguousarray(keys[np.sort(first_at)])
+
+
+def keys_as_void(keys):
+    keys = np.ascontiguousarray(keys, dtype=np.uint8)
+    return keys.view(np.dtype((np.void, keys.shape[1]))).reshape(-1)
+
+
+def match_keys(want, have):
+    """index into `have` of every row of `want`, -1 where absent (both [n, kb] uint8)"""
+    idx = np.full(want.shape[0], -1, np.int64)
+    if have.shape[0] == 0 or want.shape[0] == 0:
+        return idx
+    hv, wv = keys_as_void(have), keys_as_void(want)
+    order = np.argsort(hv, kind="stable")
+    pos = np.searchsorted(hv[order], wv)
+    pos = np.minimum(pos, hv.size - 1)
+    hit = hv[order][pos] == wv
+    idx[hit] = order[pos[hit]]
+    return idx
+
+
+RC_ABSENT, RC_SINGLETON, RC_WEAK = 0, 1, 2
+
+
+def weighted_answers(keys, weak_keys, weak_counts, weak_w, sing_keys, sing_w8):
+    """(kind, count, f64 answer) of getCount(keys) / getCount(keys, useWeights=True) against a weak map and a singleton map given as
+    entries: a weak entry answers its count and f32 weightedCount, a singleton count (w8 != 0) and (w8 - 1) / 254, an absent key 0"""
+    n = keys.shape[0]
+    kind = np.zeros(n, np.uint8)
+    cnt = np.zeros(n, np.uint32)
+    ans = np.zeros(n, np.float64)
+    iw = match_keys(keys, weak_keys)
+    hit = iw >= 0
+    kind[hit], cnt[hit], ans[hit] = RC_WEAK, weak_counts[iw[hit]], weak_w[iw[hit]].astype(np.float64)
+    isg = match_keys(keys, sing_keys)
+    hs = (isg >= 0) & ~hit
+    w8 = sing_w8[isg[hs]].astype(np.float64)
+    kind[hs], cnt[hs], ans[hs] = RC_SINGLETON, (w8 != 0), np.where(w8 != 0, (w8 - 1.0) / 254.0, 0.0)
+    return kind, cnt, ans
+
+
+def singleton_entries(buf, kb, ext=False):
+    """keys [n, kb] and _weight bytes of a stored singleton map"""
+    pieces = list(image_pieces(buf, kb, 5 if ext else 1, cols=1))
+    if not pieces:
+        return np.zeros((0, kb), np.uint8), np.zeros(0, np.uint8)
+    return np.concatenate([p[0] for p in pieces]), np.concatenate([p[1][:, 0] for p in pieces])
+
+
+def full_size_weights(name):
+    """the committed weight profile of full_size_digests.json[name] (tests/golden/full_size_weights.npz), None if there is none"""
+    path = os.path.join(GOLDEN, "full_size_weights.npz")
+    with np.load(path) as z:
+        pre = name + "/"
+        got = {key[len(pre):]: z[key] for key in z.files if key.startswith(pre)}
+    return got or None
+
+
+SK_ORDERED_FROM = 256          # kmernator_amd/csrc/kmr_superkmer.hpp: the default build redoes such k-mers' weights in input order
+
+
+def weight_bin_bound(want):
+    """what |wsum_got - wsum_want| of a bin may be: both sides add the same positive f32 weights on top of the same quantised first
+    sighting; the reference adds in order, each addition off by at most 2^-24 of a partial sum <= w, the product rounds once, so
+    |d| <= (n + 1) 2^-24 w per entry and the bin's sum of (n + 2) 2^-24 w leaves one term of slack (a theorem)"""
+    return 2.0 ** -24 * want["nwsum"] * (1.0 + 1e-6) + 1e-12 * np.abs(want["wsum"])
+
+
+def weight_entry_bound(count, w, build_mode):
+    """what |weightedCount_got - weightedCount_want| of one weak entry of `count` sightings may be: (n + 2) 2^-24 w; the super-k-mer
+    build (modes 0 and 3) is held to 1e-5 n below SK_ORDERED_FROM too, and bit for bit from there on (it adds in input order)"""
+    n = np.asarray(count, np.float64)
+    b = (n + 2.0) * 2.0 ** -24 * np.abs(np.asarray(w, np.float64))
+    if build_mode in (0, 3):
+        b = np.where(n >= SK_ORDERED_FROM, 0.0, np.minimum(1e-5 * n, b))
+    return b
+
+
+def _ratio(d, bound):
+    d = np.abs(d)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = np.where(bound > 0, d / np.where(bound > 0, bound, 1.0), np.where(d == 0, 0.0, np.inf))
+    return float(r.max()) if r.size else 0.0
+
+
+def weight_bin_ratio(got, want):
+    """largest |d wsum| / weight_bin_bound over the bins (<= 1 passes); entries and count_sum of every bin must be equal"""
+    assert np.array_equal(np.asarray(got["entries"], np.int64), np.asarray(want["entries"], np.int64)), "entries per bin differ"
+    assert np.array_equal(np.asarray(got["count_sum"], np.int64), np.asarray(want["count_sum"], np.int64)), "count_sum per bin differs"
+    return _ratio(np.asarray(got["wsum"]) - want["wsum"], weight_bin_bound(want))
+
+
+def weight_entry_ratio(count, w, want_count, want_w, build_mode):
+    """largest |d weightedCount| / weight_entry_bound over entries (<= 1 passes); the counts must be equal"""
+    assert np.array_equal(np.asarray(count, np.int64), np.asarray(want_count, np.int64)), "counts differ"
+    return _ratio(np.asarray(w, np.float64) - np.asarray(want_w, np.float64), weight_entry_bound(want_count, want_w, build_mode))
+
+
+def weight_profile_agrees(got, want, build_mode=1):
+    """the bins, the sample's keys and counts and the sample's weights of two profiles within their bounds"""
+    try:
+        if "entries" in want and weight_bin_ratio(got, want) > 1.0:
+            return False
+        if not np.array_equal(got["sample_keys"], want["sample_keys"]):
+            return False
+        return weight_entry_ratio(got["sample_count"], got["sample_w"], want["sample_count"], want["sample_w"], build_mode) <= 1.0
+    except AssertionError:
+        return False

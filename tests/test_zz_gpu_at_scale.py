@@ -7,14 +7,21 @@ the serial oracle (oracle/kmr_oracle.cpp) makes of the same reads -- SURVEY.md 8
 include/kmernator_amd.h (kmr_map_digest); tests/golden/make_full_size_digests.py wrote it, part by part, in the build container.
 Integer fields (keys, counts, direction biases, extension tallies, singleton bytes) are held bit for bit through the digest's
 hash; weightedCount is a float accumulation whose order the reference itself does not fix (src/KmerTrackingData.h:427-448), so
-its sum over the map is held to WEIGHT_REL.  The build modes are still compared with each other where that is cheap."""
+its sum over the map is held to WEIGHT_REL -- and, where tests/golden/full_size_weights.npz holds a weight profile of the configuration
+(tests/golden/make_full_size_weights.py), per entry: per key-hash bin (entries and count sums exact, the weight sum within the
+rounding bound of helpers.weight_bin_bound), per sampled entry and per k-mer cut from the job's first and last reads through
+getCount in both forms (counts exact, weights within helpers.weight_entry_bound, singleton and absent answers exact).  The build
+modes are still compared with each other where that is cheap."""
 import ctypes as C
+import time
 
 import numpy as np
 import pytest
 
 import kmernator_amd as ka
-from helpers import KMR_MAP_SINGLETON, KMR_MAP_WEAK, add_digests, digests_agree, full_size_golden, synth_reads
+from helpers import (KMR_MAP_SINGLETON, KMR_MAP_WEAK, KMR_VALUE_EXT, PROFILE_SAMPLE, RC_ABSENT, RC_SINGLETON, RC_WEAK, add_digests,
+                     digests_agree, full_size_golden, full_size_weights, synth_reads, weight_bin_ratio, weight_entry_ratio,
+                     weight_profile_of_image)
 
 pytestmark = pytest.mark.gpu
 
@@ -53,8 +60,9 @@ def _build(g, b, q, o, mode=0, **kw):
     return p
 
 
-def _assert_oracle(p, g):
-    """statistics and map digests of a finalized product spectrum == the oracle's"""
+def _assert_oracle(p, g, img=None):
+    """statistics and map digests of a finalized product spectrum == the oracle's; weightedCount per bin and per entry too where a
+    weight profile of the configuration is committed (img: the product's weak image, when the caller has it already)"""
     st = p.stats()
     assert st == g["stats"], (st, g["stats"])
     d = p.digest(KMR_MAP_WEAK)
@@ -62,6 +70,53 @@ def _assert_oracle(p, g):
     if g["config"]["min_depth"] == 1 and g.get("singleton_digest"):
         ds = p.digest(KMR_MAP_SINGLETON)
         assert digests_agree(ds, g["singleton_digest"], 1e-9), (ds, g["singleton_digest"])
+    _assert_weights(p, g, img)
+
+
+def _same_bits(a, b):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
+
+
+def _assert_weights(p, g, img=None):
+    """the committed weight profile of g's configuration against the product: bins from its weak image (entries and count_sum
+    exact, |d wsum| <= helpers.weight_bin_bound), the sample and the read-cut keys through getCount (counts exact, weak entries'
+    weights within helpers.weight_entry_bound for the build mode, singleton and absent answers bit for bit), and the weighted
+    lookup of the sampled keys == the image's f32 bit for bit.  Prints the largest |d| / bound per bin and per entry."""
+    want = full_size_weights(g["name"])
+    if want is None:
+        return
+    t0 = time.time()
+    mode = int(p.cfg.build_mode)
+    seen = {}
+    if "entries" in want:          # a profile without bins (c4_flat's: an 8 GB image is not read back) is held through getCount only
+        img = p.image(KMR_MAP_WEAK) if img is None else img
+        got = weight_profile_of_image(img, p.kb, ext=p.cfg.value_kind == KMR_VALUE_EXT)
+        seen["bin"] = weight_bin_ratio(got, want)
+        assert np.array_equal(got["sample_keys"], want["sample_keys"])
+        assert _same_bits(p.getCount(got["sample_keys"], useWeights=True), got["sample_w"])
+        assert np.array_equal(p.getCount(got["sample_keys"]), got["sample_count"])
+    keys = want["sample_keys"]
+    assert keys.shape[0] == min(PROFILE_SAMPLE, g["stats"]["weak_entries"]) > 0
+    seen["entry"] = weight_entry_ratio(p.getCount(keys), p.getCount(keys, useWeights=True), want["sample_count"], want["sample_w"], mode)
+    rk, kind = want["rc_keys"], want["rc_kind"]
+    assert rk.shape[0] > 0
+    cnt, w = p.getCount(rk), p.getCount(rk, useWeights=True)
+    assert np.array_equal(cnt, want["rc_count"])
+    weak = kind == RC_WEAK
+    seen["read_cut"] = weight_entry_ratio(cnt[weak], w[weak], want["rc_count"][weak], want["rc_w"][weak], mode)
+    assert _same_bits(w[~weak], want["rc_w"][~weak])
+    # not vacuous: purged / discarded k-mers answer 0 where the configuration drops some, singletons where it keeps them
+    c = g["config"]
+    if c["min_depth"] >= 2:
+        assert (kind == RC_ABSENT).any()
+    elif c.get("cfg", {}).get("separate_singletons", 1):
+        assert (kind == RC_SINGLETON).any()
+    assert weak.any()
+    print("weight profile %s mode %d: max |d|/bound %s; read-cut keys %d weak, %d singleton, %d absent; %.1f s" % (
+        g["name"], mode, " ".join("%s %.3g" % kv for kv in seen.items()), weak.sum(), (kind == RC_SINGLETON).sum(),
+        (kind == RC_ABSENT).sum(), time.time() - t0))
+    assert max(seen.values()) <= 1.0, seen
 
 
 def _image_digest(sp, which=KMR_MAP_WEAK):
@@ -101,8 +156,9 @@ def test_small_golden_digests_every_mode(name, mode):
     from helpers import digest_of_image
     g, b, q, o, n, L = _golden_reads(name)
     p = _build(g, b, q, o, mode)
-    _assert_oracle(p, g)
-    assert digests_agree(p.digest(KMR_MAP_WEAK), digest_of_image(p.image(KMR_MAP_WEAK), p.kb), 1e-9)
+    img = p.image(KMR_MAP_WEAK)
+    _assert_oracle(p, g, img)
+    assert digests_agree(p.digest(KMR_MAP_WEAK), digest_of_image(img, p.kb), 1e-9)
     p.close()
 
 
@@ -336,8 +392,8 @@ def test_c2_full_size_against_the_oracle():
         st = p.stats()
         assert st["raw_kmers"] == n * 120 == st["raw_good_kmers"]
         _bookkeeping(p, st)
-        _assert_oracle(p, g)
         imgs.append(p.image(KMR_MAP_WEAK))
+        _assert_oracle(p, g, imgs[-1])
     assert np.array_equal(imgs[0], imgs[1])          # deterministic, including the f32 weight sums
     img = imgs[0]
     nb = int(np.frombuffer(img[:8].tobytes(), dtype=np.uint64)[0])
