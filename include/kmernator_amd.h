@@ -620,7 +620,9 @@ int kmr_tune(kmr_handle *h, const char *knob, double value);
 /* What the current build decided, for tests and measurement tools (the reference logs such figures, LOG_VERBOSE): "lists" = super-k-mer
  * lists of the build (0 before the first reads, or in another build mode), "uniform_count" = 1 if the last kmr_finalize ran the
  * count pass's one-weight form, "chunk_pool_chunks" = 1 KB chunks the pool holds, "superkmer_window" = the minimizer window in use, "early_lists" / "early_entries" = the bound below which the last
- * kmr_finalize took its lists' entries from kmr_count_lists_prefix (0: it counted everything itself) and how many entries those were.  KMR_ERR_INVALID_ARG for an unknown name. */
+ * kmr_finalize took its lists' entries from kmr_count_lists_prefix (0: it counted everything itself) and how many entries those were,
+ * "device_blocks_live" = blocks of device memory the library holds at this moment in the whole process (every handle, read batch
+ * and artifact filter; not only h's).  KMR_ERR_INVALID_ARG for an unknown name. */
 int kmr_build_info(kmr_handle *h, const char *what, double *value);
 
 /* Timing of the hot path measured with HIP events on the handle's stream

@@ -13,6 +13,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -39,25 +40,123 @@ namespace {
 
 std::string g_create_error;
 
+/* Every device allocation of the library goes through dev_malloc.  An allocation that fails for lack of memory although the card
+ * as a whole could hold it is tried again for a bounded time (memory another handle or torch has just freed is handed back by the
+ * driver with a delay, and work still running on other streams may hold what it is about to free); what was asked for and what the
+ * device had is kept for the error text (oom_note), so that a KMR_ERR_OOM says how far off it was. */
+thread_local char g_oom_note[160] = "";
+std::atomic<long long> g_blocks_live{0};      /* blocks dev_malloc has handed out and DevBuf has not freed (kmr_build_info "device_blocks_live") */
+hipError_t dev_malloc(void **p, size_t bytes) {
+	hipError_t e = hipMalloc(p, bytes);
+	if (e == hipSuccess) { if (*p) g_blocks_live++; return e; }      /* (a 0-byte request may succeed with no block) */
+	if (e != hipErrorOutOfMemory) return e;
+	size_t fr = 0, tot = 0;
+	for (int attempt = 0; attempt < 6; attempt++) {
+		(void)hipGetLastError();
+		hipDeviceSynchronize();
+		if (hipMemGetInfo(&fr, &tot) != hipSuccess || bytes > tot) break;
+		usleep(20000u << attempt);      /* 20 ms ... 640 ms: 1.3 s at most */
+		e = hipMalloc(p, bytes);
+		if (e == hipSuccess && *p) g_blocks_live++;
+		if (e != hipErrorOutOfMemory) return e;
+	}
+	(void)hipGetLastError();
+	hipMemGetInfo(&fr, &tot);
+	snprintf(g_oom_note, sizeof(g_oom_note), " [requested %.3f GB; device has %.3f GB free of %.3f GB]", bytes / 1e9, fr / 1e9, tot / 1e9);
+	*p = nullptr;
+	return hipErrorOutOfMemory;
+}
+
+/* One block of device memory and its size in bytes, freed when the owner goes: every device allocation of the library is one.
+ * Kernels take get<T>(); alloc() replaces the block by one of exactly `bytes`, reserve() (below kmr_handle) grows it only. */
+class DevBuf {
+public:
+	DevBuf() = default;
+	DevBuf(DevBuf &&o) noexcept : p_(o.p_), cap_(o.cap_) { o.p_ = nullptr; o.cap_ = 0; }
+	DevBuf &operator=(DevBuf &&o) noexcept { if (this != &o) { reset(); std::swap(p_, o.p_); std::swap(cap_, o.cap_); } return *this; }
+	~DevBuf() { reset(); }
+	void reset() { if (p_) { hipFree(p_); g_blocks_live--; } p_ = nullptr; cap_ = 0; }
+	hipError_t alloc(size_t bytes) {      /* empty on failure */
+		reset();
+		void *p = nullptr;
+		const hipError_t e = dev_malloc(&p, bytes);
+		if (e == hipSuccess) { p_ = p; cap_ = bytes; }
+		return e;
+	}
+	/* grow-only: a block of `bytes` (default: need) unless the one held has `need`; drains the handle's stream before freeing it.
+	 * A failure sets the handle's error text, naming the buffer (`what`). */
+	int reserve(kmr_handle *h, const char *what, size_t need, size_t bytes = 0);
+	template <class T = void> T *get() const { return (T *)p_; }
+	size_t cap() const { return cap_; }
+	explicit operator bool() const { return p_ != nullptr; }
+private:
+	void *p_ = nullptr;
+	size_t cap_ = 0;
+};
+
 struct DevMap {                      /* a finalized map resident in HBM */
 	uint64_t nb = 0, n = 0;
-	uint64_t *start = nullptr;       /* [nb+1] */
-	uint64_t *keys = nullptr;        /* [n][W] */
-	uint32_t *vals = nullptr;        /* weak: [n][vw] */
-	uint8_t *sweight = nullptr;      /* singleton */
-	uint32_t *spkt = nullptr;        /* singleton, EXT */
-	uint8_t *image = nullptr;        /* reference layout, built lazily */
-	uint64_t image_bytes = 0;
+	DevBuf start;                    /* [nb+1] */
+	DevBuf keys;                     /* [n][W] */
+	DevBuf vals;                     /* weak: [n][vw] */
+	DevBuf sweight;                  /* singleton */
+	DevBuf spkt;                     /* singleton, EXT */
+	DevBuf image;                    /* reference layout, built lazily */
 	bool present = false;
-	/* bytes allocated behind start / keys / vals / sweight: kmr_reset() keeps the buffers of the streaming path for the next build */
-	size_t c_start = 0, c_keys = 0, c_vals = 0, c_sw = 0, c_pkt = 0;
 };
 
 struct HostPool {                    /* owner of one chunk pool */
-	uint8_t *base = nullptr; uint32_t *chunk_list = nullptr, *chunk_count = nullptr; unsigned int *head = nullptr;
+	DevBuf base, chunk_list, chunk_count, head;
 	uint32_t cap = 0; size_t chunk_bytes = 0;
 	uint64_t used_ub = 0;            /* host-side upper bound of chunks handed out */
 	uint64_t presize = 0;            /* chunks the next allocation takes beyond what is asked for (a job fed in many calls, see sk_add_reads) */
+};
+
+/* The handle's device memory, grouped by when it is given back: */
+struct HandleMem {                   /* ... by kmr_destroy */
+	DevBuf slots, extslots;          /* device table */
+	DevBuf dP, dstats, derr;
+	DevMap weak, sing;
+	/* streaming lookups (sk_index_* / sk_lookup_kernel): the weak map's entries grouped by minimizer list, of map generation ix_gen */
+	DevBuf ix_start, ix_keys, ix_counts;
+	DevBuf scratch_stats;
+	DevBuf adopt_buf;                /* kmr_sk_exchange_adopt_dev's scan */
+	DevBuf trk;                      /* size tracker: one record per read of the last call */
+	DevBuf scan_sums;
+	DevBuf score_buf;                /* temporaries of kmr_score_reads*, grow-only */
+	DevBuf lut;                      /* lookup accelerator over the weak map (LutView) */
+	DevBuf dPk;                      /* build_mode 3: table of k-fold quality products */
+	DevBuf d_uni;                    /* uniform-weight flags of adopted records */
+	DevBuf qrange;                   /* sk_qual_range_kernel's answer */
+	DevBuf sk_fine_state;            /* fine list state of an exchange (2^(sk_bits + sk_fine_shift) words) */
+	/* an exchange in steps over the list space (kmr_sk_exchange_range) and the lists below `hi` counted early (kmr_count_lists_prefix):
+	 * their entries wait in buffers of their own until kmr_finalize has counted the rest */
+	struct Early { bool active = false; uint64_t hi = 0; uint32_t min_depth = 0; DevBuf ue, cursor, fc; } early;
+	DevBuf xo_dev;                   /* kmr_extract_by_owner_host: owner segments of one batch kept on the device between the sizing call and the copy-out */
+};
+struct BuildMem {                    /* ... by kmr_release_table too: the streaming build's state */
+	DevBuf sk_state;                 /* build_mode 3 (kmr_superkmer.hpp): list words */
+	HostPool l1;                     /* the record pool of every partition level */
+	DevBuf work_counter;
+	DevBuf l1_state; bool l1_state_dirty = false;      /* see PartSource::state */
+	/* temporaries of kmr_finalize (chunk CSRs, work items, counters): one grow-only block handed out by bumping a
+	 * cursor, so a finalize neither allocates nor frees device memory once the handle has seen one build */
+	DevBuf arena; size_t arena_used = 0, arena_want = 0; std::vector<DevBuf> arena_overflow;
+	DevBuf linear;                   /* records */
+	DevBuf tile_count, kcap, koff;
+	/* work units of batches that contain reads longer than one tile */
+	DevBuf ucnt, ufirst, u_start, u_end, u_read, umax;
+	/* kmr_add_reads_twobit*: the unpacked batch (ASCII bases, one quality character throughout, offsets counted from the call's first read) */
+	DevBuf tb_bases, tb_quals, tb_rel, tb_off, tb_len;
+	uint64_t tb_quals_filled = 0; int tb_quals_char = -1;
+	DevBuf tb_stage[2][8];           /* kmr_add_reads_twobit: two sets of staging buffers for the pieces on the bus */
+	DevBuf uw_keys, uw_vals, us_keys, us_b8, us_pkt;
+	/* build_mode 3: the count pass's weak entries packed (kmr_buckets.hpp: W key words + one value word), and the radix partition's scratch of the same layout */
+	DevBuf ue, ue2;
+};
+struct ExchangeMem {                 /* ... after the communicator that uses it (kmr_exchange_rccl.hpp): gather scratch, grow-only send / receive buffers */
+	DevBuf xc_small, xc_dcounts;
+	DevBuf xc_send, xc_send2, xc_recv, xc_recv2;
 };
 
 }  // namespace
@@ -83,7 +182,7 @@ struct Tuning {
 	bool no_coarse_lists = true;       /* exchange: scatter into the job's fine lists (default) or, kmr_tune("coarse_lists", 1), into coarse ones that the owner splits before the count pass (sk_refine_kernel: not yet fast enough to pay) */
 };
 
-struct kmr_handle {
+struct kmr_handle : HandleMem, BuildMem, ExchangeMem {
 	kmr_config cfg;
 	Tuning tune;
 	uint32_t k = 0, kb = 0, hkb = 0, W = 0;
@@ -92,30 +191,21 @@ struct kmr_handle {
 	hipStream_t stream = nullptr;
 	std::string err;
 	/* device table */
-	void *slots = nullptr;
-	ExtSlot *extslots = nullptr;
 	uint32_t log2cap = 0;
 	uint64_t occupied = 0;           /* exact as of the last sync */
 	uint64_t pending_kmers = 0;      /* upper bound of keys added since */
-	double *dP = nullptr;
-	DevStats *dstats = nullptr;
-	uint32_t *derr = nullptr;
 	uint64_t stream_base = 0, reads = 0;
 	uint64_t nb_weak = 0, nb_sing = 0;
 	bool finalized = false, has_singletons = true;
 	kmr_handle *subtract = nullptr;    /* finalized spectrum whose k-mers are skipped (kmr_subtract_reference) */
 	uint64_t subtracted = 0;
-	DevMap weak, sing;
 	kmr_stats stats;
 	/* streaming (partition) build path */
 	bool partition_mode = false;
 	bool superkmer_mode = false;       /* build_mode 3: super-k-mer lists (kmr_superkmer.hpp); implies partition_mode */
-	/* streaming lookups (sk_index_* / sk_lookup_kernel): the weak map's entries grouped by minimizer list, of map generation ix_gen */
-	uint64_t *ix_start = nullptr, *ix_keys = nullptr; uint32_t *ix_counts = nullptr; uint64_t ix_cap = 0, ix_lists = 0, ix_gen = ~0ull;
-	DevStats *scratch_stats = nullptr;
-	uint8_t *adopt_buf = nullptr; size_t adopt_cap = 0;      /* kmr_sk_exchange_adopt_dev's scan */
-	/* size tracker (kmr_config.size_tracker): one record per read fed so far, and the elements made of them at kmr_finalize */
-	SkTrackRec *trk = nullptr; uint64_t trk_cap = 0, trk_n = 0; std::vector<uint64_t> trk_elems;
+	uint64_t ix_lists = 0, ix_gen = ~0ull;      /* the streaming lookups' index (ix_*): its list count and map generation */
+	/* size tracker (kmr_config.size_tracker): records of the reads fed by the last call (trk), and the elements made of them at kmr_finalize */
+	uint64_t trk_n = 0; std::vector<uint64_t> trk_elems;
 	/* the thresholds passed so far (SizeTracker::nextToTrack and the elements' first two counters), found call by call while the
 	 * reads are still at hand: the stream ordinal behind the k-mer at which rawKmers reached the threshold, rawKmers, rawGoodKmers */
 	long trk_next = 128; uint64_t trk_raw = 0, trk_good = 0; std::vector<unsigned long long> trk_bounds; std::vector<uint64_t> trk_snap_raw, trk_snap_good;
@@ -123,59 +213,33 @@ struct kmr_handle {
 	bool sender_launch = false;        /* extract_by_owner_t, build (not request) mode: dev_params tells the kernel to count what it does not send */
 	bool sk_exchange = false;          /* kmr_sk_exchange_begin: the lists are the whole job's, every owner's k-mers are kept until the exchange */
 	bool auto_mode = false;            /* build_mode 0: a handle that is fed k-mer records (the owner exchange) before any reads falls back to mode 2 */
-	HostPool l1;                       /* the record pool of every partition level */
 	int bits1 = 0;
 	uint64_t inserted_records = 0;     /* records fed through kmr_insert_records_dev (counted on the host) */
 	uint64_t call_bases_hint = 0;      /* a host batch goes to the device in pieces: the bases of the WHOLE call, for what the first piece sizes (lists, chunk pool) */
-	unsigned int *work_counter = nullptr;
-	uint8_t *l1_state = nullptr; size_t l1_state_bytes = 0; bool l1_state_dirty = false;   /* see PartSource::state */
-	/* temporaries of kmr_finalize (chunk CSRs, work items, counters): one grow-only block handed out by bumping a
-	 * cursor, so a finalize neither allocates nor frees device memory once the handle has seen one build */
-	uint8_t *arena = nullptr; size_t arena_cap = 0, arena_used = 0, arena_want = 0; std::vector<void *> arena_overflow;
-	unsigned long long *scan_sums = nullptr; uint64_t scan_sums_n = 0;
-	uint8_t *score_buf = nullptr; size_t score_buf_bytes = 0;        /* temporaries of kmr_score_reads*, grow-only */
-	uint64_t *lut = nullptr; size_t lut_bytes = 0; uint32_t lut_log2 = 0;      /* lookup accelerator over the weak map (LutView) */
-	uint64_t lut_gen = ~0ull, map_gen = 0;                           /* the table belongs to the maps of generation lut_gen */
-	void *linear = nullptr; uint64_t linear_cap = 0;         /* records */
-	uint32_t *tile_count = nullptr; uint64_t tile_cap = 0;
-	uint32_t *kcap = nullptr; uint64_t *koff = nullptr; uint64_t kcap_n = 0, koff_n = 0;
-	/* work units of batches that contain reads longer than one tile */
-	uint32_t *ucnt = nullptr; uint64_t *ufirst = nullptr, *u_start = nullptr, *u_end = nullptr, *u_read = nullptr;
-	uint64_t ucnt_n = 0, ufirst_n = 0, units_n = 0; unsigned int *umax = nullptr;
-	/* kmr_add_reads_twobit*: the unpacked batch (ASCII bases, one quality character throughout, offsets counted from the call's first read) */
-	uint8_t *tb_bases = nullptr, *tb_quals = nullptr; uint64_t *tb_rel = nullptr, *tb_off = nullptr; uint32_t *tb_len = nullptr;
-	uint64_t tb_bases_cap = 0, tb_quals_cap = 0, tb_quals_filled = 0, tb_n = 0; int tb_quals_char = -1;
+	uint32_t lut_log2 = 0;
+	uint64_t lut_gen = ~0ull, map_gen = 0;                           /* the lookup table belongs to the maps of generation lut_gen */
 	hipStream_t tb_copy_stream = nullptr; hipEvent_t tb_ready[2] = {nullptr, nullptr}, tb_consumed[2] = {nullptr, nullptr}; bool tb_set_used[2] = {false, false};
-	uint8_t *tb_stage[2][8] = {{nullptr}}; size_t tb_stage_cap[2][8] = {{0}};      /* kmr_add_reads_twobit: two sets of staging buffers for the pieces on the bus */
 	const SkPacked *packed_direct = nullptr;      /* set while kmr_add_reads_twobit_dev feeds a batch that sk_extract_lean_kernel<.., PACKED> takes as it is */
 	int uniform_q_hint = -1;           /* >= 0 while kmr_add_reads_twobit_dev feeds a batch whose qualities are this one character */
-	void *uw_keys = nullptr, *uw_vals = nullptr, *us_keys = nullptr, *us_b8 = nullptr, *us_pkt = nullptr; uint64_t uw_cap = 0, us_cap = 0;
-	/* build_mode 3: the count pass's weak entries packed (kmr_buckets.hpp: W key words + one value word), and the radix partition's scratch of the same layout */
-	uint64_t *ue = nullptr, *ue2 = nullptr; uint64_t ue_cap = 0, ue2_cap = 0;
-	/* build_mode 3 (kmr_superkmer.hpp): list words, minimizer geometry, table of k-fold quality products */
-	unsigned long long *sk_state = nullptr; uint32_t sk_bits = 0, sk_m = 0, sk_off = 0, sk_win = 0; double *dPk = nullptr;
+	/* build_mode 3 (kmr_superkmer.hpp): list count and minimizer geometry */
+	uint32_t sk_bits = 0, sk_m = 0, sk_off = 0, sk_win = 0;
 	double hP[256], hPk[256];              /* host copies of the probability table and of its k-fold products */
 	/* does every record of the lists carry ONE weight (all calls went through the lean extraction with the same quality character)?  The
-	 * host knows for its own calls (sk_uni_w: SK_UNI_NONE before the first; sk_uni_mixed), a device pair collects it for adopted records */
-	uint32_t sk_uni_w = 0xffffffffu; bool sk_uni_mixed = false; uint32_t *d_uni = nullptr; bool last_count_uniform = false;
+	 * host knows for its own calls (sk_uni_w: SK_UNI_NONE before the first; sk_uni_mixed), a device pair collects it for adopted records (d_uni) */
+	uint32_t sk_uni_w = 0xffffffffu; bool sk_uni_mixed = false; bool last_count_uniform = false;
 	/* ... or the senders say so themselves (kmr_sk_exchange_peer_uniform): then nothing is looked at on arrival */
 	uint32_t peer_uni_w = 0xffffffffu; bool peer_uni_mixed = false, peers_declare = false;
-	/* an exchange in steps over the list space (kmr_sk_exchange_range) and the lists below `hi` counted early (kmr_count_lists_prefix):
-	 * their entries wait in buffers of their own until kmr_finalize has counted the rest */
-	uint64_t xr_lo = 0, xr_hi = ~0ull;
-	struct Early { bool active = false; uint64_t hi = 0; uint32_t min_depth = 0; uint64_t *ue = nullptr; uint64_t cap = 0; unsigned long long *cursor = nullptr; void *fc = nullptr; } early;
+	uint64_t xr_lo = 0, xr_hi = ~0ull;      /* kmr_sk_exchange_range */
 	uint64_t last_early_hi = 0, last_early_entries = 0;      /* what the last kmr_finalize took over from an early count (kmr_build_info) */
-	unsigned int *qrange = nullptr; bool qual_mixed = false;      /* sk_qual_range_kernel's answer; a build that has seen two different quality characters stops asking */
+	bool qual_mixed = false;           /* a build that has seen two different quality characters stops asking (qrange) */
 	/* exchange with world_size > 1: sk_bits are the COARSE lists reads are scattered into and that travel; each holds 2^sk_fine_shift
-	 * fine lists, made by sk_refine_kernel before the count pass (fine state: sk_fine_state, 2^(sk_bits + sk_fine_shift) words) */
-	uint32_t sk_fine_shift = 0; unsigned long long *sk_fine_state = nullptr; uint64_t sk_fine_cap = 0;
+	 * fine lists, made by sk_refine_kernel before the count pass (fine state: sk_fine_state) */
+	uint32_t sk_fine_shift = 0;
 	uint32_t sk_min_override = 0;
-	/* kmr_extract_by_owner_host: owner segments of one batch kept on the device between the sizing call and the copy-out */
-	/* kmr_exchange_* (kmr_exchange_rccl.hpp): communicator, gather scratch, grow-only send / receive buffers, what the job was fed so far */
-	void *xc_comm = nullptr; unsigned long long *xc_small = nullptr, *xc_dcounts = nullptr; kmr_transport xc_tr = {nullptr, nullptr, nullptr};
-	void *xc_send = nullptr, *xc_send2 = nullptr, *xc_recv = nullptr, *xc_recv2 = nullptr;
-	uint64_t xc_send_cap = 0, xc_send2_cap = 0, xc_recv_cap = 0, xc_recv2_cap = 0, xc_job_bases = 0, xc_bytes_to_peers = 0;
-	void *xo_dev = nullptr; uint64_t xo_segcap = 0; std::vector<uint64_t> xo_counts; const void *xo_batch = nullptr; uint64_t xo_first = 0;
+	uint64_t xo_segcap = 0; std::vector<uint64_t> xo_counts; const void *xo_batch = nullptr; uint64_t xo_first = 0;      /* xo_dev's segments */
+	/* kmr_exchange_* (kmr_exchange_rccl.hpp): communicator, transport, what the job was fed so far */
+	void *xc_comm = nullptr; kmr_transport xc_tr = {nullptr, nullptr, nullptr};
+	uint64_t xc_job_bases = 0, xc_bytes_to_peers = 0;
 	/* timing */
 	hipEvent_t ev0 = nullptr, ev1 = nullptr;
 	double ms[KMR_TIME_GROUPS] = {0};
@@ -186,38 +250,15 @@ struct kmr_handle {
 /* device-resident read batch produced by kmr_ingest_fastq* */
 struct kmr_reads {
 	int device = 0;
-	uint8_t *bases = nullptr, *quals = nullptr;   /* 64 bytes of padding behind the data: extract_kernel stages 16-byte blocks */
-	uint64_t *offsets = nullptr;                  /* [n + 1] */
-	uint64_t *name_off = nullptr; uint32_t *name_len = nullptr;
+	DevBuf bases, quals;                          /* 64 bytes of padding behind the data: extract_kernel stages 16-byte blocks */
+	DevBuf offsets;                               /* [n + 1] */
+	DevBuf name_off, name_len;
 	uint64_t n = 0, total = 0, filtered = 0;
 	uint32_t input_base = 0;
 };
 
 namespace {
 
-/* Every device allocation of the library goes through dev_malloc.  An allocation that fails for lack of memory although the card
- * as a whole could hold it is tried again for a bounded time (memory another handle or torch has just freed is handed back by the
- * driver with a delay, and work still running on other streams may hold what it is about to free); what was asked for and what the
- * device had is kept for the error text (oom_note), so that a KMR_ERR_OOM says how far off it was. */
-thread_local char g_oom_note[160] = "";
-hipError_t dev_malloc(void **p, size_t bytes) {
-	hipError_t e = hipMalloc(p, bytes);
-	if (e != hipErrorOutOfMemory) return e;
-	size_t fr = 0, tot = 0;
-	for (int attempt = 0; attempt < 6; attempt++) {
-		(void)hipGetLastError();
-		hipDeviceSynchronize();
-		if (hipMemGetInfo(&fr, &tot) != hipSuccess || bytes > tot) break;
-		usleep(20000u << attempt);      /* 20 ms ... 640 ms: 1.3 s at most */
-		e = hipMalloc(p, bytes);
-		if (e != hipErrorOutOfMemory) return e;
-	}
-	(void)hipGetLastError();
-	hipMemGetInfo(&fr, &tot);
-	snprintf(g_oom_note, sizeof(g_oom_note), " [requested %.3f GB; device has %.3f GB free of %.3f GB]", bytes / 1e9, fr / 1e9, tot / 1e9);
-	*p = nullptr;
-	return hipErrorOutOfMemory;
-}
 std::string oom_note() { std::string s(g_oom_note); g_oom_note[0] = 0; return s; }
 
 std::string hip_err_text(hipError_t e) { return std::string(hipGetErrorString(e)) + (e == hipErrorOutOfMemory ? oom_note() : std::string()); }
@@ -225,6 +266,16 @@ std::string hip_err_text(hipError_t e) { return std::string(hipGetErrorString(e)
 #define HIPCHK(h, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
 	(h)->err = std::string(#call) + ": " + hip_err_text(e_); \
 	return e_ == hipErrorOutOfMemory ? KMR_ERR_OOM : KMR_ERR_HIP; } } while (0)
+
+int DevBuf::reserve(kmr_handle *h, const char *what, size_t need, size_t bytes) {
+	if (p_ && cap_ >= need) return 0;
+	if (!bytes) bytes = need;
+	hipError_t e = p_ ? hipStreamSynchronize(h->stream) : hipSuccess;      /* kernels in flight may still read it */
+	if (e == hipSuccess) e = alloc(bytes);
+	if (e == hipSuccess) return 0;
+	h->err = std::string("device buffer ") + what + " (" + std::to_string(bytes) + " bytes): " + hip_err_text(e);
+	return e == hipErrorOutOfMemory ? KMR_ERR_OOM : KMR_ERR_HIP;
+}
 
 /* diagnostics on stderr and the measurement-only hooks exist in a -DKMR_DEBUG_HOOKS build alone: the shipped library reads no
  * environment variable */
@@ -265,12 +316,12 @@ DevParams dev_params(kmr_handle *h) {
 	p.qzero = h->cfg.fastq_start_char + std::max<uint32_t>(1u, h->cfg.min_quality_score);   /* Q0 has probability 0 too */
 	p.subsample = h->cfg.kmer_subsample; p.rank = h->cfg.rank; p.world = h->cfg.world_size; p.num_parts = h->cfg.num_parts; p.part_idx = h->cfg.part_idx;
 	p.count_sender_bad = h->sender_launch ? 1u : 0u;
-	p.P = h->dP; p.stats = h->dstats; p.err = h->derr;
+	p.P = h->dP.get<double>(); p.stats = h->dstats.get<DevStats>(); p.err = h->derr.get<uint32_t>();
 	p.sub_wstart = p.sub_wkeys = p.sub_sstart = p.sub_skeys = nullptr; p.sub_wvals = nullptr; p.sub_sweight = nullptr; p.sub_wnb = p.sub_snb = 0; p.sub_vw = 0;
 	if (h->subtract) {
 		const kmr_handle *o = h->subtract;
-		if (o->weak.present && o->weak.n) { p.sub_wstart = o->weak.start; p.sub_wkeys = o->weak.keys; p.sub_wvals = o->weak.vals; p.sub_wnb = o->weak.nb; p.sub_vw = o->ext ? 15 : 3; }
-		if (o->sing.present && o->sing.n) { p.sub_sstart = o->sing.start; p.sub_skeys = o->sing.keys; p.sub_sweight = o->sing.sweight; p.sub_snb = o->sing.nb; }
+		if (o->weak.present && o->weak.n) { p.sub_wstart = o->weak.start.get<uint64_t>(); p.sub_wkeys = o->weak.keys.get<uint64_t>(); p.sub_wvals = o->weak.vals.get<uint32_t>(); p.sub_wnb = o->weak.nb; p.sub_vw = o->ext ? 15 : 3; }
+		if (o->sing.present && o->sing.n) { p.sub_sstart = o->sing.start.get<uint64_t>(); p.sub_skeys = o->sing.keys.get<uint64_t>(); p.sub_sweight = o->sing.sweight.get<uint8_t>(); p.sub_snb = o->sing.nb; }
 	}
 	return p;
 }
@@ -282,7 +333,7 @@ int grid_for(uint64_t n, int block = 256, int maxBlocks = 256 * 16) {
 	return (int)g;
 }
 
-template <int W> Table<W> table_of(kmr_handle *h) { Table<W> t; t.slots = (Slot<W> *)h->slots; t.ext = h->extslots; t.log2cap = h->log2cap; return t; }
+template <int W> Table<W> table_of(kmr_handle *h) { Table<W> t; t.slots = h->slots.get<Slot<W>>(); t.ext = h->extslots.get<ExtSlot>(); t.log2cap = h->log2cap; return t; }
 
 template <int W> int clear_table(kmr_handle *h, void *slots, ExtSlot *ext, uint32_t log2cap) {
 	hipLaunchKernelGGL(table_clear_kernel<W>, dim3(grid_for(1ull << log2cap)), dim3(256), 0, h->stream, (Slot<W> *)slots, ext, 1ull << log2cap);
@@ -294,11 +345,15 @@ int clear_table_any(kmr_handle *h, void *slots, ExtSlot *ext, uint32_t log2cap) 
 	case 3: return clear_table<3>(h, slots, ext, log2cap); default: return clear_table<4>(h, slots, ext, log2cap); }
 }
 
-int alloc_table(kmr_handle *h, uint32_t log2cap, void **slots, ExtSlot **ext) {
-	*slots = nullptr; *ext = nullptr;
-	HIPCHK(h, dev_malloc(slots, slot_bytes(h->W) << log2cap));
-	if (h->ext) { hipError_t e = dev_malloc((void **)ext, sizeof(ExtSlot) << log2cap); if (e != hipSuccess) { hipFree(*slots); *slots = nullptr; h->err = "dev_malloc(ext slots)"; return KMR_ERR_OOM; } }
-	return clear_table_any(h, *slots, *ext, log2cap);
+/* slots (and extension slots) of a cleared table; `slots` and `ext` are replaced only when all of it succeeded */
+int alloc_table(kmr_handle *h, uint32_t log2cap, DevBuf &slots, DevBuf &ext) {
+	DevBuf s, x;
+	HIPCHK(h, s.alloc(slot_bytes(h->W) << log2cap));
+	if (h->ext) HIPCHK(h, x.alloc(sizeof(ExtSlot) << log2cap));
+	const int rc = clear_table_any(h, s.get(), x.get<ExtSlot>(), log2cap);
+	if (rc) return rc;
+	slots = std::move(s); ext = std::move(x);
+	return 0;
 }
 
 /* read the device error word and counters; synchronises the stream */
@@ -313,8 +368,8 @@ int sync_state(kmr_handle *h) {
 		h->pending_events[which].clear();
 	}
 	uint32_t e = 0; DevStats s;
-	HIPCHK(h, hipMemcpy(&e, h->derr, sizeof(e), hipMemcpyDeviceToHost));
-	HIPCHK(h, hipMemcpy(&s, h->dstats, sizeof(s), hipMemcpyDeviceToHost));
+	HIPCHK(h, hipMemcpy(&e, h->derr.get<uint32_t>(), sizeof(e), hipMemcpyDeviceToHost));
+	HIPCHK(h, hipMemcpy(&s, h->dstats.get<DevStats>(), sizeof(s), hipMemcpyDeviceToHost));
 #ifdef KMR_DEBUG_HOOKS
 	if (h->superkmer_mode) { if (dbg()) fprintf(stderr, "sk_extract windows: %llu general, %llu fast\n", s.claimed, s.inserted); s.claimed = 0; s.inserted = 0; }
 #endif
@@ -330,15 +385,14 @@ int sync_state(kmr_handle *h) {
 }
 
 template <int W, bool EXT> int grow_table_t(kmr_handle *h, uint32_t newlog) {
-	void *ns; ExtSlot *ne;
-	int rc = alloc_table(h, newlog, &ns, &ne);
+	DevBuf ns, ne;
+	int rc = alloc_table(h, newlog, ns, ne);
 	if (rc) return rc;
-	Table<W> src = table_of<W>(h), dst; dst.slots = (Slot<W> *)ns; dst.ext = ne; dst.log2cap = newlog;
-	hipLaunchKernelGGL((rehash_kernel<W, EXT>), dim3(grid_for(1ull << h->log2cap)), dim3(256), 0, h->stream, src, dst, h->hkb, h->derr);
+	Table<W> src = table_of<W>(h), dst; dst.slots = ns.get<Slot<W>>(); dst.ext = ne.get<ExtSlot>(); dst.log2cap = newlog;
+	hipLaunchKernelGGL((rehash_kernel<W, EXT>), dim3(grid_for(1ull << h->log2cap)), dim3(256), 0, h->stream, src, dst, h->hkb, h->derr.get<uint32_t>());
 	HIPCHK(h, hipGetLastError());
 	HIPCHK(h, hipStreamSynchronize(h->stream));
-	hipFree(h->slots); if (h->extslots) hipFree(h->extslots);
-	h->slots = ns; h->extslots = ne; h->log2cap = newlog;
+	h->slots = std::move(ns); h->extslots = std::move(ne); h->log2cap = newlog;
 	return 0;
 }
 int grow_table(kmr_handle *h, uint32_t newlog) {
@@ -382,28 +436,26 @@ int prepare_units(kmr_handle *h, ReadsView &rv, uint32_t span = (uint32_t)TILE_S
 	rv.u_start = rv.u_end = rv.u_read = nullptr; rv.n_units = 0;
 	const uint64_t n = rv.n_reads;
 	if (n == 0) return 0;
-	if (!h->umax) HIPCHK(h, dev_malloc((void **)&h->umax, 4));
-	HIPCHK(h, hipMemsetAsync(h->umax, 0, 4, h->stream));
-	if (!h->ucnt || h->ucnt_n < n + 1) { if (h->ucnt) { HIPCHK(h, hipStreamSynchronize(h->stream)); hipFree(h->ucnt); } h->ucnt = nullptr; HIPCHK(h, dev_malloc((void **)&h->ucnt, 4 * (n + 1))); h->ucnt_n = n + 1; }
-	hipLaunchKernelGGL(unit_count_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, rv.offsets, n, h->k, span, h->ucnt, h->umax);
+	int rc = h->umax.reserve(h, "umax", 4); if (rc) return rc;
+	HIPCHK(h, hipMemsetAsync(h->umax.get<unsigned int>(), 0, 4, h->stream));
+	rc = h->ucnt.reserve(h, "ucnt", 4 * (n + 1)); if (rc) return rc;
+	hipLaunchKernelGGL(unit_count_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, rv.offsets, n, h->k, span, h->ucnt.get<uint32_t>(), h->umax.get<unsigned int>());
 	HIPCHK(h, hipGetLastError());
 	unsigned int mx = 0;
-	HIPCHK(h, hipMemcpyAsync(&mx, h->umax, 4, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipMemcpyAsync(&mx, h->umax.get<unsigned int>(), 4, hipMemcpyDeviceToHost, h->stream));
 	HIPCHK(h, hipStreamSynchronize(h->stream));
 	if (mx <= span) return 0;                   /* the usual case: every read is one unit */
-	if (!h->ufirst || h->ufirst_n < n + 1) { if (h->ufirst) hipFree(h->ufirst); h->ufirst = nullptr; HIPCHK(h, dev_malloc((void **)&h->ufirst, 8 * (n + 1))); h->ufirst_n = n + 1; }
-	int rc = exclusive_scan(h, h->ucnt, n, h->ufirst); if (rc) return rc;
+	rc = h->ufirst.reserve(h, "ufirst", 8 * (n + 1)); if (rc) return rc;
+	rc = exclusive_scan(h, h->ucnt.get<uint32_t>(), n, h->ufirst.get<uint64_t>()); if (rc) return rc;
 	uint64_t U = 0;
-	HIPCHK(h, hipMemcpy(&U, h->ufirst + n, 8, hipMemcpyDeviceToHost));
-	if (h->units_n < U) {
-		if (h->u_start) { hipFree(h->u_start); hipFree(h->u_end); hipFree(h->u_read); }
-		h->u_start = h->u_end = h->u_read = nullptr; h->units_n = 0;
-		HIPCHK(h, dev_malloc((void **)&h->u_start, 8 * U)); HIPCHK(h, dev_malloc((void **)&h->u_end, 8 * U)); HIPCHK(h, dev_malloc((void **)&h->u_read, 8 * U));
-		h->units_n = U;
+	HIPCHK(h, hipMemcpy(&U, h->ufirst.get<uint64_t>() + n, 8, hipMemcpyDeviceToHost));
+	if (h->u_read.cap() < 8 * U) {      /* (u_read is allocated last) */
+		h->u_start.reset(); h->u_end.reset(); h->u_read.reset();
+		HIPCHK(h, h->u_start.alloc(8 * U)); HIPCHK(h, h->u_end.alloc(8 * U)); HIPCHK(h, h->u_read.alloc(8 * U));
 	}
-	hipLaunchKernelGGL(unit_fill_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, rv.offsets, n, h->k, span, h->ufirst, h->u_start, h->u_end, h->u_read);
+	hipLaunchKernelGGL(unit_fill_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, rv.offsets, n, h->k, span, h->ufirst.get<uint64_t>(), h->u_start.get<uint64_t>(), h->u_end.get<uint64_t>(), h->u_read.get<uint64_t>());
 	HIPCHK(h, hipGetLastError());
-	rv.u_start = h->u_start; rv.u_end = h->u_end; rv.u_read = h->u_read; rv.n_units = U;
+	rv.u_start = h->u_start.get<uint64_t>(); rv.u_end = h->u_end.get<uint64_t>(); rv.u_read = h->u_read.get<uint64_t>(); rv.n_units = U;
 	return 0;
 }
 
@@ -461,14 +513,9 @@ int add_reads_dev_any(kmr_handle *h, const ReadsView &rv, uint64_t total_bases) 
 
 int exclusive_scan(kmr_handle *h, const uint32_t *in, uint64_t n, uint64_t *out /* n+1 */) {
 	const uint64_t nblocks = (n + SCAN_ITEMS - 1) / SCAN_ITEMS;
-	unsigned long long *sums, *total;
-	if (h->scan_sums_n < nblocks + 1) {
-		if (h->scan_sums) { HIPCHK(h, hipStreamSynchronize(h->stream)); hipFree(h->scan_sums); h->scan_sums = nullptr; h->scan_sums_n = 0; }
-		const uint64_t want = std::max<uint64_t>(nblocks + 1, 4096);
-		HIPCHK(h, dev_malloc((void **)&h->scan_sums, sizeof(unsigned long long) * want)); h->scan_sums_n = want;
-	}
-	sums = h->scan_sums;
-	total = sums + nblocks;
+	const size_t eb = sizeof(unsigned long long);
+	int rc = h->scan_sums.reserve(h, "scan_sums", eb * (nblocks + 1), eb * std::max<uint64_t>(nblocks + 1, 4096)); if (rc) return rc;
+	unsigned long long *sums = h->scan_sums.get<unsigned long long>(), *total = sums + nblocks;
 	hipLaunchKernelGGL(scan_block_sums_kernel, dim3((unsigned)nblocks), dim3(256), 0, h->stream, in, n, sums);
 	hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(256), 0, h->stream, sums, nblocks, total);
 	hipLaunchKernelGGL(scan_apply_kernel, dim3((unsigned)nblocks), dim3(256), 0, h->stream, in, n, sums, out);
@@ -481,51 +528,32 @@ int exclusive_scan(kmr_handle *h, const uint32_t *in, uint64_t n, uint64_t *out 
  * arena_reset() and added to the size the arena gets next time */
 int arena_alloc(kmr_handle *h, void **out, size_t bytes) {
 	const size_t need = (bytes + 255) & ~(size_t)255;
-	if (h->arena && h->arena_used + need <= h->arena_cap) { *out = h->arena + h->arena_used; h->arena_used += need; h->arena_want += need; return 0; }
+	if (h->arena && h->arena_used + need <= h->arena.cap()) { *out = h->arena.get<uint8_t>() + h->arena_used; h->arena_used += need; h->arena_want += need; return 0; }
 	h->arena_want += need;
-	HIPCHK(h, dev_malloc(out, std::max<size_t>(need, 256)));
-	h->arena_overflow.push_back(*out);
+	DevBuf b;
+	HIPCHK(h, b.alloc(std::max<size_t>(need, 256)));
+	*out = b.get();
+	h->arena_overflow.push_back(std::move(b));
 	return 0;
 }
 /* start of a finalize: everything handed out before is dead (the stream is idle) */
 int arena_reset(kmr_handle *h) {
 	HIPCHK(h, hipStreamSynchronize(h->stream));
-	for (void *p : h->arena_overflow) hipFree(p);
 	h->arena_overflow.clear();
-	if (h->arena_want > h->arena_cap) {
-		if (h->arena) hipFree(h->arena);
-		h->arena = nullptr; h->arena_cap = 0;
-		const size_t want = h->arena_want + h->arena_want / 8 + (1 << 20);
-		if (dev_malloc((void **)&h->arena, want) == hipSuccess) h->arena_cap = want; else { h->arena = nullptr; (void)hipGetLastError(); }
+	if (h->arena_want > h->arena.cap()) {
+		if (h->arena.alloc(h->arena_want + h->arena_want / 8 + (1 << 20)) != hipSuccess) (void)hipGetLastError();
 	}
 	h->arena_used = 0; h->arena_want = 0;
 	return 0;
 }
 template <class T> int arena_get(kmr_handle *h, T **out, size_t count) { return arena_alloc(h, (void **)out, count * sizeof(T)); }
 
-void free_map(DevMap &m) {
-	if (m.start) hipFree(m.start); if (m.keys) hipFree(m.keys); if (m.vals) hipFree(m.vals);
-	if (m.sweight) hipFree(m.sweight); if (m.spkt) hipFree(m.spkt); if (m.image) hipFree(m.image);
-	m = DevMap();
-}
-
 /* empty the map but keep its buffers */
-void clear_map(DevMap &m) {
-	if (m.image) hipFree(m.image);
-	m.image = nullptr; m.image_bytes = 0; m.n = 0; m.present = false;
-}
-int reserve_bytes(kmr_handle *h, void **ptr, size_t &cap, size_t need) {
-	need = std::max<size_t>(need, 8);
-	if (*ptr && cap >= need) return 0;
-	if (*ptr) hipFree(*ptr);
-	*ptr = nullptr; cap = 0;
-	HIPCHK(h, dev_malloc(ptr, need));
-	cap = need;
-	return 0;
-}
+void clear_map(DevMap &m) { m.image.reset(); m.n = 0; m.present = false; }
+
 
 template <int W> MapView<W> view_of(const DevMap &m, uint32_t vw) {
-	MapView<W> v; v.start = m.start; v.keys = m.keys; v.vals = m.vals; v.sweight = m.sweight; v.nb = m.present ? m.nb : 0; v.vw = vw;
+	MapView<W> v; v.start = m.start.get<uint64_t>(); v.keys = m.keys.get<uint64_t>(); v.vals = m.vals.get<uint32_t>(); v.sweight = m.sweight.get<uint8_t>(); v.nb = m.present ? m.nb : 0; v.vw = vw;
 	return v;
 }
 
@@ -535,8 +563,9 @@ template <int W, bool EXT> int finalize_t(kmr_handle *h, uint32_t min_depth) {
 	hipEvent_t ea, eb; time_begin(h, 1, &ea, &eb);
 	FinalizeParams f; f.kb = h->hkb; f.min_depth = min_depth; f.has_singletons = h->cfg.separate_singletons ? 1 : 0; f.nb_weak = h->nb_weak; f.nb_sing = h->nb_sing; f.uni_wbits = 0;
 	const bool keepSing = f.has_singletons && min_depth <= 1;
-	uint32_t *wc = nullptr, *sc = nullptr; FinalizeCounters *fc = nullptr;
-	HIPCHK(h, dev_malloc((void **)&wc, 4 * h->nb_weak)); HIPCHK(h, dev_malloc((void **)&sc, 4 * h->nb_sing)); HIPCHK(h, dev_malloc((void **)&fc, sizeof(FinalizeCounters)));
+	DevBuf wcb, scb, fcb;
+	HIPCHK(h, wcb.alloc(4 * h->nb_weak)); HIPCHK(h, scb.alloc(4 * h->nb_sing)); HIPCHK(h, fcb.alloc(sizeof(FinalizeCounters)));
+	uint32_t *wc = wcb.get<uint32_t>(), *sc = scb.get<uint32_t>(); FinalizeCounters *fc = fcb.get<FinalizeCounters>();
 	HIPCHK(h, hipMemsetAsync(wc, 0, 4 * h->nb_weak, h->stream)); HIPCHK(h, hipMemsetAsync(sc, 0, 4 * h->nb_sing, h->stream)); HIPCHK(h, hipMemsetAsync(fc, 0, sizeof(FinalizeCounters), h->stream));
 	Table<W> t = table_of<W>(h);
 	const int g = grid_for(1ull << h->log2cap);
@@ -549,29 +578,28 @@ template <int W, bool EXT> int finalize_t(kmr_handle *h, uint32_t min_depth) {
 	/* singletonKmers only moves inside the hasSingletons branches of append() (src/KmerSpectrum.h:1625,1649) */
 	h->stats.singleton_kmers = f.has_singletons ? c.singletons : 0;
 	DevMap &wm = h->weak, &sm = h->sing;
-	free_map(wm); free_map(sm);
+	wm = DevMap(); sm = DevMap();
 	wm.nb = h->nb_weak; wm.n = c.weak_kept; wm.present = true;
 	sm.nb = h->nb_sing; sm.n = c.sing_kept; sm.present = keepSing;
 	const uint32_t vw = EXT ? 15 : 3;
-	HIPCHK(h, dev_malloc((void **)&wm.start, 8 * (wm.nb + 1))); HIPCHK(h, dev_malloc((void **)&sm.start, 8 * (sm.nb + 1)));
-	rc = exclusive_scan(h, wc, wm.nb, wm.start); if (rc) return rc;
-	rc = exclusive_scan(h, sc, sm.nb, sm.start); if (rc) return rc;
-	HIPCHK(h, dev_malloc((void **)&wm.keys, std::max<uint64_t>(8, 8ull * W * wm.n))); HIPCHK(h, dev_malloc((void **)&wm.vals, std::max<uint64_t>(8, 4ull * vw * wm.n)));
-	HIPCHK(h, dev_malloc((void **)&sm.keys, std::max<uint64_t>(8, 8ull * W * sm.n))); HIPCHK(h, dev_malloc((void **)&sm.sweight, std::max<uint64_t>(8, sm.n)));
-	if (EXT) HIPCHK(h, dev_malloc((void **)&sm.spkt, std::max<uint64_t>(8, 4ull * sm.n)));
+	HIPCHK(h, wm.start.alloc(8 * (wm.nb + 1))); HIPCHK(h, sm.start.alloc(8 * (sm.nb + 1)));
+	rc = exclusive_scan(h, wc, wm.nb, wm.start.get<uint64_t>()); if (rc) return rc;
+	rc = exclusive_scan(h, sc, sm.nb, sm.start.get<uint64_t>()); if (rc) return rc;
+	HIPCHK(h, wm.keys.alloc(std::max<uint64_t>(8, 8ull * W * wm.n))); HIPCHK(h, wm.vals.alloc(std::max<uint64_t>(8, 4ull * vw * wm.n)));
+	HIPCHK(h, sm.keys.alloc(std::max<uint64_t>(8, 8ull * W * sm.n))); HIPCHK(h, sm.sweight.alloc(std::max<uint64_t>(8, sm.n)));
+	if (EXT) HIPCHK(h, sm.spkt.alloc(std::max<uint64_t>(8, 4ull * sm.n)));
 	HIPCHK(h, hipMemsetAsync(wc, 0, 4 * h->nb_weak, h->stream)); HIPCHK(h, hipMemsetAsync(sc, 0, 4 * h->nb_sing, h->stream));
-	hipLaunchKernelGGL((scatter_kernel<W, EXT>), dim3(g), dim3(256), 0, h->stream, t, f, wm.start, wc, wm.keys, wm.vals, sm.start, sc, sm.keys, sm.sweight, sm.spkt);
+	hipLaunchKernelGGL((scatter_kernel<W, EXT>), dim3(g), dim3(256), 0, h->stream, t, f, wm.start.get<uint64_t>(), wc, wm.keys.get<uint64_t>(), wm.vals.get<uint32_t>(), sm.start.get<uint64_t>(), sc, sm.keys.get<uint64_t>(), sm.sweight.get<uint8_t>(), sm.spkt.get<uint32_t>());
 	HIPCHK(h, hipGetLastError());
-	SortView<W> sv; sv.keys = wm.keys; sv.vals = wm.vals; sv.b8 = nullptr; sv.pkt = nullptr; sv.vw = vw;
-	hipLaunchKernelGGL((sort_buckets_kernel<W, EXT ? 15 : 3>), dim3(grid_for(wm.nb, 4, 1 << 20)), dim3(256), 0, h->stream, sv, wm.start, wm.nb);
+	SortView<W> sv; sv.keys = wm.keys.get<uint64_t>(); sv.vals = wm.vals.get<uint32_t>(); sv.b8 = nullptr; sv.pkt = nullptr; sv.vw = vw;
+	hipLaunchKernelGGL((sort_buckets_kernel<W, EXT ? 15 : 3>), dim3(grid_for(wm.nb, 4, 1 << 20)), dim3(256), 0, h->stream, sv, wm.start.get<uint64_t>(), wm.nb);
 	if (sm.n) {
-		SortView<W> ss; ss.keys = sm.keys; ss.vals = nullptr; ss.b8 = sm.sweight; ss.pkt = sm.spkt; ss.vw = 0;
-		hipLaunchKernelGGL((sort_buckets_kernel<W, 0>), dim3(grid_for(sm.nb, 4, 1 << 20)), dim3(256), 0, h->stream, ss, sm.start, sm.nb);
+		SortView<W> ss; ss.keys = sm.keys.get<uint64_t>(); ss.vals = nullptr; ss.b8 = sm.sweight.get<uint8_t>(); ss.pkt = sm.spkt.get<uint32_t>(); ss.vw = 0;
+		hipLaunchKernelGGL((sort_buckets_kernel<W, 0>), dim3(grid_for(sm.nb, 4, 1 << 20)), dim3(256), 0, h->stream, ss, sm.start.get<uint64_t>(), sm.nb);
 	}
 	HIPCHK(h, hipGetLastError());
 	time_end(h, 1, ea, eb);
 	HIPCHK(h, hipStreamSynchronize(h->stream));
-	hipFree(wc); hipFree(sc); hipFree(fc);
 	/* the table allocation is kept for kmr_reset(); kmr_release_table() frees it */
 	h->has_singletons = keepSing;
 	if (!keepSing) { sm.n = 0; }
@@ -584,11 +612,10 @@ template <int W> int build_image_t(kmr_handle *h, DevMap &m, bool weakMap) {
 	if (m.image) return 0;
 	const uint32_t vw = h->ext ? 15 : 3;
 	const uint32_t vbytes = weakMap ? (h->ext ? 60 : 12) : (h->ext ? 5 : 1);
-	m.image_bytes = 8 * (2 + m.nb) + 4 * m.nb + m.n * (h->kb + vbytes);
-	HIPCHK(h, dev_malloc((void **)&m.image, m.image_bytes));
-	hipLaunchKernelGGL(image_header_kernel, dim3(grid_for(m.nb)), dim3(256), 0, h->stream, m.image, m.start, m.nb, h->kb, vbytes);
-	if (m.n) hipLaunchKernelGGL(image_entries_kernel<W>, dim3(grid_for(m.n)), dim3(256), 0, h->stream, m.image, m.start, m.nb, h->kb, vbytes,
-	                           m.keys, weakMap ? m.vals : nullptr, vw, m.sweight, m.spkt, m.n);
+	HIPCHK(h, m.image.alloc(8 * (2 + m.nb) + 4 * m.nb + m.n * (h->kb + vbytes)));
+	hipLaunchKernelGGL(image_header_kernel, dim3(grid_for(m.nb)), dim3(256), 0, h->stream, m.image.get<uint8_t>(), m.start.get<uint64_t>(), m.nb, h->kb, vbytes);
+	if (m.n) hipLaunchKernelGGL(image_entries_kernel<W>, dim3(grid_for(m.n)), dim3(256), 0, h->stream, m.image.get<uint8_t>(), m.start.get<uint64_t>(), m.nb, h->kb, vbytes,
+	                           m.keys.get<uint64_t>(), weakMap ? m.vals.get<uint32_t>() : nullptr, vw, m.sweight.get<uint8_t>(), m.spkt.get<uint32_t>(), m.n);
 	HIPCHK(h, hipGetLastError());
 	HIPCHK(h, hipStreamSynchronize(h->stream));
 	return 0;
@@ -605,7 +632,7 @@ template <int W> int load_image_t(kmr_handle *h, DevMap &m, bool weakMap, const 
 	const uint32_t vw = h->ext ? 15 : 3;
 	const uint32_t vbytes = weakMap ? (h->ext ? 60 : 12) : (h->ext ? 5 : 1);
 	if ((len - 8 * (2 + nb) - 4 * nb) % (h->kb + vbytes) != 0) return fail(h, KMR_ERR_INVALID_ARG, "image size does not match k / value type");
-	free_map(m);
+	m = DevMap();
 	m.nb = nb; m.n = (len - 8 * (2 + nb) - 4 * nb) / (h->kb + vbytes); m.present = true;
 	/* validate offsets on the host before any kernel dereferences them */
 	const uint64_t *offs = (const uint64_t *)(src + 16);
@@ -617,96 +644,90 @@ template <int W> int load_image_t(kmr_handle *h, DevMap &m, bool weakMap, const 
 		if (expect > len) return fail(h, KMR_ERR_INVALID_ARG, "image bucket runs past the end");
 	}
 	if (expect != len) return fail(h, KMR_ERR_INVALID_ARG, "image length mismatch");
-	HIPCHK(h, dev_malloc((void **)&m.image, len)); m.image_bytes = len;
-	HIPCHK(h, hipMemcpy(m.image, src, len, hipMemcpyHostToDevice));
-	uint32_t *counts; HIPCHK(h, dev_malloc((void **)&counts, 4 * nb));
-	hipLaunchKernelGGL(image_counts_kernel, dim3(grid_for(nb)), dim3(256), 0, h->stream, m.image, nb, counts);
-	HIPCHK(h, dev_malloc((void **)&m.start, 8 * (nb + 1)));
-	int rc = exclusive_scan(h, counts, nb, m.start); hipFree(counts); if (rc) return rc;
-	HIPCHK(h, dev_malloc((void **)&m.keys, std::max<uint64_t>(8, 8ull * W * m.n)));
-	if (weakMap) HIPCHK(h, dev_malloc((void **)&m.vals, std::max<uint64_t>(8, 4ull * vw * m.n)));
-	else { HIPCHK(h, dev_malloc((void **)&m.sweight, std::max<uint64_t>(8, m.n))); if (h->ext) HIPCHK(h, dev_malloc((void **)&m.spkt, std::max<uint64_t>(8, 4 * m.n))); }
-	if (m.n) hipLaunchKernelGGL(image_unpack_kernel<W>, dim3(grid_for(m.n)), dim3(256), 0, h->stream, m.image, m.start, nb, h->kb, vbytes, m.keys, m.vals, vw, m.sweight, m.spkt, m.n);
+	HIPCHK(h, m.image.alloc(len));
+	HIPCHK(h, hipMemcpy(m.image.get<uint8_t>(), src, len, hipMemcpyHostToDevice));
+	{
+		DevBuf counts; HIPCHK(h, counts.alloc(4 * nb));
+		hipLaunchKernelGGL(image_counts_kernel, dim3(grid_for(nb)), dim3(256), 0, h->stream, m.image.get<uint8_t>(), nb, counts.get<uint32_t>());
+		HIPCHK(h, m.start.alloc(8 * (nb + 1)));
+		int rc = exclusive_scan(h, counts.get<uint32_t>(), nb, m.start.get<uint64_t>()); if (rc) return rc;
+	}
+	HIPCHK(h, m.keys.alloc(std::max<uint64_t>(8, 8ull * W * m.n)));
+	if (weakMap) HIPCHK(h, m.vals.alloc(std::max<uint64_t>(8, 4ull * vw * m.n)));
+	else { HIPCHK(h, m.sweight.alloc(std::max<uint64_t>(8, m.n))); if (h->ext) HIPCHK(h, m.spkt.alloc(std::max<uint64_t>(8, 4 * m.n))); }
+	if (m.n) hipLaunchKernelGGL(image_unpack_kernel<W>, dim3(grid_for(m.n)), dim3(256), 0, h->stream, m.image.get<uint8_t>(), m.start.get<uint64_t>(), nb, h->kb, vbytes, m.keys.get<uint64_t>(), m.vals.get<uint32_t>(), vw, m.sweight.get<uint8_t>(), m.spkt.get<uint32_t>(), m.n);
 	/* restore() accepts unsorted buckets (setLastSorted); lookups here need them sorted */
-	SortView<W> sv; sv.keys = m.keys; sv.vals = m.vals; sv.b8 = m.sweight; sv.pkt = m.spkt; sv.vw = weakMap ? vw : 0;
-	if (!weakMap) hipLaunchKernelGGL((sort_buckets_kernel<W, 0>), dim3(grid_for(nb, 4, 1 << 20)), dim3(256), 0, h->stream, sv, m.start, nb);
-	else if (h->ext) hipLaunchKernelGGL((sort_buckets_kernel<W, 15>), dim3(grid_for(nb, 4, 1 << 20)), dim3(256), 0, h->stream, sv, m.start, nb);
-	else hipLaunchKernelGGL((sort_buckets_kernel<W, 3>), dim3(grid_for(nb, 4, 1 << 20)), dim3(256), 0, h->stream, sv, m.start, nb);
+	SortView<W> sv; sv.keys = m.keys.get<uint64_t>(); sv.vals = m.vals.get<uint32_t>(); sv.b8 = m.sweight.get<uint8_t>(); sv.pkt = m.spkt.get<uint32_t>(); sv.vw = weakMap ? vw : 0;
+	if (!weakMap) hipLaunchKernelGGL((sort_buckets_kernel<W, 0>), dim3(grid_for(nb, 4, 1 << 20)), dim3(256), 0, h->stream, sv, m.start.get<uint64_t>(), nb);
+	else if (h->ext) hipLaunchKernelGGL((sort_buckets_kernel<W, 15>), dim3(grid_for(nb, 4, 1 << 20)), dim3(256), 0, h->stream, sv, m.start.get<uint64_t>(), nb);
+	else hipLaunchKernelGGL((sort_buckets_kernel<W, 3>), dim3(grid_for(nb, 4, 1 << 20)), dim3(256), 0, h->stream, sv, m.start.get<uint64_t>(), nb);
 	HIPCHK(h, hipGetLastError());
 	HIPCHK(h, hipStreamSynchronize(h->stream));
-	hipFree(m.image); m.image = nullptr; m.image_bytes = 0;    /* rebuilt (sorted) on demand */
+	m.image.reset();    /* rebuilt (sorted) on demand */
+
 	return 0;
 }
 
 template <int W, int VW> void launch_sort(kmr_handle *h, DevMap &m, bool weakMap) {
-	SortView<W> sv; sv.keys = m.keys; sv.vals = weakMap ? m.vals : nullptr; sv.b8 = m.sweight; sv.pkt = m.spkt; sv.vw = weakMap ? VW : 0;
-	hipLaunchKernelGGL((sort_buckets_kernel<W, VW>), dim3(grid_for(m.nb, 4, 1 << 20)), dim3(256), 0, h->stream, sv, m.start, m.nb);
+	SortView<W> sv; sv.keys = m.keys.get<uint64_t>(); sv.vals = weakMap ? m.vals.get<uint32_t>() : nullptr; sv.b8 = m.sweight.get<uint8_t>(); sv.pkt = m.spkt.get<uint32_t>(); sv.vw = weakMap ? VW : 0;
+	hipLaunchKernelGGL((sort_buckets_kernel<W, VW>), dim3(grid_for(m.nb, 4, 1 << 20)), dim3(256), 0, h->stream, sv, m.start.get<uint64_t>(), m.nb);
 }
 /* union of the handle's map with a stored map of the same shape (see merge_copy_kernel) */
 template <int W> int merge_image_t(kmr_handle *h, DevMap &m, bool weakMap, const uint8_t *src, uint64_t len) {
 	DevMap t;
 	int rc = load_image_t<W>(h, t, weakMap, src, len);
-	if (rc) { free_map(t); return rc; }
-	if (t.nb != m.nb) { free_map(t); return fail(h, KMR_ERR_INVALID_ARG, "Can not merge two maps of differing sizes (src/Kmer.h:3210)"); }
+	if (rc) return rc;
+	if (t.nb != m.nb) return fail(h, KMR_ERR_INVALID_ARG, "Can not merge two maps of differing sizes (src/Kmer.h:3210)");
 	const uint32_t vw = h->ext ? 15 : 3;
 	DevMap d; d.nb = m.nb; d.n = m.n + t.n; d.present = true;
-	uint32_t *counts = nullptr, *dup = nullptr;
-	auto bail = [&](int code) { free_map(t); free_map(d); if (counts) hipFree(counts); if (dup) hipFree(dup); return code; };
-#define MCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { h->err = std::string(#call) + ": " + hip_err_text(e_); return bail(e_ == hipErrorOutOfMemory ? KMR_ERR_OOM : KMR_ERR_HIP); } } while (0)
-	MCHK(dev_malloc((void **)&counts, 4 * m.nb)); MCHK(dev_malloc((void **)&dup, 4)); MCHK(hipMemsetAsync(dup, 0, 4, h->stream));
-	MCHK(dev_malloc((void **)&d.start, 8 * (m.nb + 1)));
-	hipLaunchKernelGGL(merge_counts_kernel, dim3(grid_for(m.nb)), dim3(256), 0, h->stream, m.start, t.start, m.nb, counts);
-	rc = exclusive_scan(h, counts, m.nb, d.start); if (rc) return bail(rc);
-	MCHK(dev_malloc((void **)&d.keys, std::max<uint64_t>(8, 8ull * W * d.n)));
-	if (weakMap) MCHK(dev_malloc((void **)&d.vals, std::max<uint64_t>(8, 4ull * vw * d.n)));
-	else { MCHK(dev_malloc((void **)&d.sweight, std::max<uint64_t>(8, d.n))); if (h->ext) MCHK(dev_malloc((void **)&d.spkt, std::max<uint64_t>(8, 4 * d.n))); }
-	if (m.n) hipLaunchKernelGGL(merge_copy_kernel<W>, dim3(grid_for(m.n)), dim3(256), 0, h->stream, m.start, t.start, false, m.nb, m.n, m.keys, weakMap ? m.vals : nullptr, vw, m.sweight, m.spkt, d.start, d.keys, d.vals, d.sweight, d.spkt);
-	if (t.n) hipLaunchKernelGGL(merge_copy_kernel<W>, dim3(grid_for(t.n)), dim3(256), 0, h->stream, t.start, m.start, true, m.nb, t.n, t.keys, weakMap ? t.vals : nullptr, vw, t.sweight, t.spkt, d.start, d.keys, d.vals, d.sweight, d.spkt);
+	DevBuf countsb, dupb;
+	HIPCHK(h, countsb.alloc(4 * m.nb)); HIPCHK(h, dupb.alloc(4));
+	uint32_t *counts = countsb.get<uint32_t>(), *dup = dupb.get<uint32_t>();
+	HIPCHK(h, hipMemsetAsync(dup, 0, 4, h->stream));
+	HIPCHK(h, d.start.alloc(8 * (m.nb + 1)));
+	hipLaunchKernelGGL(merge_counts_kernel, dim3(grid_for(m.nb)), dim3(256), 0, h->stream, m.start.get<uint64_t>(), t.start.get<uint64_t>(), m.nb, counts);
+	rc = exclusive_scan(h, counts, m.nb, d.start.get<uint64_t>()); if (rc) return rc;
+	HIPCHK(h, d.keys.alloc(std::max<uint64_t>(8, 8ull * W * d.n)));
+	if (weakMap) HIPCHK(h, d.vals.alloc(std::max<uint64_t>(8, 4ull * vw * d.n)));
+	else { HIPCHK(h, d.sweight.alloc(std::max<uint64_t>(8, d.n))); if (h->ext) HIPCHK(h, d.spkt.alloc(std::max<uint64_t>(8, 4 * d.n))); }
+	if (m.n) hipLaunchKernelGGL(merge_copy_kernel<W>, dim3(grid_for(m.n)), dim3(256), 0, h->stream, m.start.get<uint64_t>(), t.start.get<uint64_t>(), false, m.nb, m.n, m.keys.get<uint64_t>(), weakMap ? m.vals.get<uint32_t>() : nullptr, vw, m.sweight.get<uint8_t>(), m.spkt.get<uint32_t>(), d.start.get<uint64_t>(), d.keys.get<uint64_t>(), d.vals.get<uint32_t>(), d.sweight.get<uint8_t>(), d.spkt.get<uint32_t>());
+	if (t.n) hipLaunchKernelGGL(merge_copy_kernel<W>, dim3(grid_for(t.n)), dim3(256), 0, h->stream, t.start.get<uint64_t>(), m.start.get<uint64_t>(), true, m.nb, t.n, t.keys.get<uint64_t>(), weakMap ? t.vals.get<uint32_t>() : nullptr, vw, t.sweight.get<uint8_t>(), t.spkt.get<uint32_t>(), d.start.get<uint64_t>(), d.keys.get<uint64_t>(), d.vals.get<uint32_t>(), d.sweight.get<uint8_t>(), d.spkt.get<uint32_t>());
 	if (!weakMap) launch_sort<W, 0>(h, d, false); else if (h->ext) launch_sort<W, 15>(h, d, true); else launch_sort<W, 3>(h, d, true);
-	hipLaunchKernelGGL(duplicate_keys_kernel<W>, dim3(grid_for(d.nb)), dim3(256), 0, h->stream, d.start, d.nb, d.keys, dup);
-	MCHK(hipGetLastError());
+	hipLaunchKernelGGL(duplicate_keys_kernel<W>, dim3(grid_for(d.nb)), dim3(256), 0, h->stream, d.start.get<uint64_t>(), d.nb, d.keys.get<uint64_t>(), dup);
+	HIPCHK(h, hipGetLastError());
 	uint32_t hdup = 0;
-	MCHK(hipMemcpyAsync(&hdup, dup, 4, hipMemcpyDeviceToHost, h->stream)); MCHK(hipStreamSynchronize(h->stream));
-	if (hdup && !weakMap) {
-#undef MCHK
-		/* (a k-mer in both singleton maps would have to be promoted into the weak map: KmerMap::mergePromote, which the reference
-		 * itself refuses -- "This method is broken", src/Kmer.h:2675-2677) */
-		bail(0); return fail(h, KMR_ERR_UNSUPPORTED, "the two singleton maps share k-mers: merging them means promoting those into the weak map (mergePromote, which the reference refuses too)");
-	}
+	HIPCHK(h, hipMemcpyAsync(&hdup, dup, 4, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
+	/* (a k-mer in both singleton maps would have to be promoted into the weak map: KmerMap::mergePromote, which the reference
+	 * itself refuses -- "This method is broken", src/Kmer.h:2675-2677) */
+	if (hdup && !weakMap) return fail(h, KMR_ERR_UNSUPPORTED, "the two singleton maps share k-mers: merging them means promoting those into the weak map (mergePromote, which the reference refuses too)");
 	if (hdup) {      /* mergeAdd proper: the k-mers both maps hold add their values */
-#define MCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { h->err = std::string(#call) + ": " + hip_err_text(e_); free_map(d2); return bail(e_ == hipErrorOutOfMemory ? KMR_ERR_OOM : KMR_ERR_HIP); } } while (0)
 		DevMap d2; d2.nb = d.nb; d2.present = true;
-		hipLaunchKernelGGL(merge_distinct_kernel<W>, dim3(grid_for(d.nb)), dim3(256), 0, h->stream, d.start, d.nb, d.keys, counts);
-		MCHK(dev_malloc((void **)&d2.start, 8 * (d.nb + 1)));
-		rc = exclusive_scan(h, counts, d.nb, d2.start); if (rc) { free_map(d2); return bail(rc); }
-		MCHK(hipMemcpyAsync(&d2.n, d2.start + d.nb, 8, hipMemcpyDeviceToHost, h->stream)); MCHK(hipStreamSynchronize(h->stream));
-		MCHK(dev_malloc((void **)&d2.keys, std::max<uint64_t>(8, 8ull * W * d2.n)));
-		MCHK(dev_malloc((void **)&d2.vals, std::max<uint64_t>(8, 4ull * vw * d2.n)));
-		hipLaunchKernelGGL(merge_add_kernel<W>, dim3(grid_for(d.nb)), dim3(256), 0, h->stream, d.start, d.nb, d.keys, d.vals, vw, d2.start, d2.keys, d2.vals);
-		MCHK(hipGetLastError()); MCHK(hipStreamSynchronize(h->stream));
-#undef MCHK
-		free_map(d);
-		d = d2;
+		hipLaunchKernelGGL(merge_distinct_kernel<W>, dim3(grid_for(d.nb)), dim3(256), 0, h->stream, d.start.get<uint64_t>(), d.nb, d.keys.get<uint64_t>(), counts);
+		HIPCHK(h, d2.start.alloc(8 * (d.nb + 1)));
+		rc = exclusive_scan(h, counts, d.nb, d2.start.get<uint64_t>()); if (rc) return rc;
+		HIPCHK(h, hipMemcpyAsync(&d2.n, d2.start.get<uint64_t>() + d.nb, 8, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
+		HIPCHK(h, d2.keys.alloc(std::max<uint64_t>(8, 8ull * W * d2.n)));
+		HIPCHK(h, d2.vals.alloc(std::max<uint64_t>(8, 4ull * vw * d2.n)));
+		hipLaunchKernelGGL(merge_add_kernel<W>, dim3(grid_for(d.nb)), dim3(256), 0, h->stream, d.start.get<uint64_t>(), d.nb, d.keys.get<uint64_t>(), d.vals.get<uint32_t>(), vw, d2.start.get<uint64_t>(), d2.keys.get<uint64_t>(), d2.vals.get<uint32_t>());
+		HIPCHK(h, hipGetLastError()); HIPCHK(h, hipStreamSynchronize(h->stream));
+		d = std::move(d2);
 	}
-	hipFree(counts); hipFree(dup); free_map(t);
-	free_map(m);
-	m = d;
+	m = std::move(d);
 	return 0;
 }
 
 /* packed host keys -> counts (u32) or weights (f64, getCount(kmer, true)); exactly one of the two outputs is given */
 template <int W> int lookup_t(kmr_handle *h, const uint8_t *packed, uint64_t n, uint32_t *counts, double *weights = nullptr) {
 	const uint64_t ob = counts ? 4 : 8;
-	uint8_t *dk; void *dc;
-	HIPCHK(h, dev_malloc((void **)&dk, std::max<uint64_t>(8, n * h->kb))); HIPCHK(h, dev_malloc((void **)&dc, std::max<uint64_t>(8, ob * n)));
-	HIPCHK(h, hipMemcpyAsync(dk, packed, n * h->kb, hipMemcpyHostToDevice, h->stream));
+	DevBuf dk, dc;
+	HIPCHK(h, dk.alloc(std::max<uint64_t>(8, n * h->kb))); HIPCHK(h, dc.alloc(std::max<uint64_t>(8, ob * n)));
+	HIPCHK(h, hipMemcpyAsync(dk.get(), packed, n * h->kb, hipMemcpyHostToDevice, h->stream));
 	const uint32_t vw = h->ext ? 15 : 3;
-	hipLaunchKernelGGL(lookup_keys_kernel<W>, dim3(grid_for(n)), dim3(256), 0, h->stream, view_of<W>(h->weak, vw), view_of<W>(h->sing, vw), dk, n, h->hkb,
-	                   counts ? (uint32_t *)dc : nullptr, counts ? nullptr : (double *)dc);
+	hipLaunchKernelGGL(lookup_keys_kernel<W>, dim3(grid_for(n)), dim3(256), 0, h->stream, view_of<W>(h->weak, vw), view_of<W>(h->sing, vw), dk.get<uint8_t>(), n, h->hkb,
+	                   counts ? dc.get<uint32_t>() : nullptr, counts ? nullptr : dc.get<double>());
 	HIPCHK(h, hipGetLastError());
-	HIPCHK(h, hipMemcpyAsync(counts ? (void *)counts : (void *)weights, dc, ob * n, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipMemcpyAsync(counts ? (void *)counts : (void *)weights, dc.get(), ob * n, hipMemcpyDeviceToHost, h->stream));
 	HIPCHK(h, hipStreamSynchronize(h->stream));
-	hipFree(dk); hipFree(dc);
 	return 0;
 }
 
@@ -718,19 +739,19 @@ template <int W> LutView<W> lut_of(kmr_handle *h) {
 	if (!(h->lut && h->lut_gen == h->map_gen)) {
 		uint32_t l2 = 10; while ((1ull << l2) < 2 * h->weak.n) l2++;
 		const size_t bytes = (size_t)(W + 1) * 8 << l2;
-		if (h->lut_bytes < bytes) {
-			if (h->lut) { hipStreamSynchronize(h->stream); hipFree(h->lut); h->lut = nullptr; h->lut_bytes = 0; }
+		if (h->lut.cap() < bytes) {
+			if (h->lut) { hipStreamSynchronize(h->stream); h->lut.reset(); }
 			size_t fr = 0, tot = 0;
-			if (hipMemGetInfo(&fr, &tot) != hipSuccess || fr < bytes + (1ull << 30) || dev_malloc((void **)&h->lut, bytes) != hipSuccess) { h->lut = nullptr; (void)hipGetLastError(); return v; }
-			h->lut_bytes = bytes;
+			if (hipMemGetInfo(&fr, &tot) != hipSuccess || fr < bytes + (1ull << 30) || h->lut.alloc(bytes) != hipSuccess) { (void)hipGetLastError(); return v; }
 		}
+
 		const uint32_t vw = h->ext ? 15 : 3;
-		hipLaunchKernelGGL(lut_clear_kernel, dim3(4096), dim3(256), 0, h->stream, h->lut, 1ull << l2, (uint32_t)(W + 1));
-		hipLaunchKernelGGL(lut_build_kernel<W>, dim3(grid_for(h->weak.n)), dim3(256), 0, h->stream, view_of<W>(h->weak, vw), h->weak.n, h->lut, (1ull << l2) - 1, 64 - l2, h->hkb);
+		hipLaunchKernelGGL(lut_clear_kernel, dim3(4096), dim3(256), 0, h->stream, h->lut.get<uint64_t>(), 1ull << l2, (uint32_t)(W + 1));
+		hipLaunchKernelGGL(lut_build_kernel<W>, dim3(grid_for(h->weak.n)), dim3(256), 0, h->stream, view_of<W>(h->weak, vw), h->weak.n, h->lut.get<uint64_t>(), (1ull << l2) - 1, 64 - l2, h->hkb);
 		if (hipGetLastError() != hipSuccess) return v;
 		h->lut_log2 = l2; h->lut_gen = h->map_gen;
 	}
-	v.slots = h->lut; v.mask = (1ull << h->lut_log2) - 1; v.shift = 64 - h->lut_log2;
+	v.slots = h->lut.get<uint64_t>(); v.mask = (1ull << h->lut_log2) - 1; v.shift = 64 - h->lut_log2;
 	return v;
 }
 
@@ -747,16 +768,13 @@ template <int W> int lookup_reads_weighted_t(kmr_handle *h, const ReadsView &rv,
 }
 
 /* stage host read arrays on the device (padded so 16-byte tile loads stay inside the allocation) */
-struct StagedReads { uint8_t *b = nullptr, *q = nullptr, *d = nullptr; uint64_t *o = nullptr; void release() { if (b) hipFree(b); if (q) hipFree(q); if (d) hipFree(d); if (o) hipFree(o); b = q = d = nullptr; o = nullptr; } };
-int stage_reads(kmr_handle *h, const char *bases, const char *quals, const uint64_t *offsets, uint64_t n, const uint8_t *disc, StagedReads &s, uint64_t &total) {
-	total = n ? offsets[n] - offsets[0] : 0;
-	HIPCHK(h, dev_malloc((void **)&s.b, total + 64)); HIPCHK(h, dev_malloc((void **)&s.o, 8 * (n + 1)));
-	HIPCHK(h, hipMemcpyAsync(s.b, bases + (n ? offsets[0] : 0), total, hipMemcpyHostToDevice, h->stream));
+int stage_reads(kmr_handle *h, const char *bases, const uint64_t *offsets, uint64_t n, DevBuf &b, DevBuf &o) {
+	const uint64_t total = n ? offsets[n] - offsets[0] : 0;
+	HIPCHK(h, b.alloc(total + 64)); HIPCHK(h, o.alloc(8 * (n + 1)));
+	HIPCHK(h, hipMemcpyAsync(b.get(), bases + (n ? offsets[0] : 0), total, hipMemcpyHostToDevice, h->stream));
 	std::vector<uint64_t> rel(n + 1);
 	for (uint64_t i = 0; i <= n; i++) rel[i] = n ? offsets[i] - offsets[0] : 0;
-	HIPCHK(h, hipMemcpyAsync(s.o, rel.data(), 8 * (n + 1), hipMemcpyHostToDevice, h->stream));
-	if (quals) { HIPCHK(h, dev_malloc((void **)&s.q, total + 64)); HIPCHK(h, hipMemcpyAsync(s.q, quals + (n ? offsets[0] : 0), total, hipMemcpyHostToDevice, h->stream)); }
-	if (disc) { HIPCHK(h, dev_malloc((void **)&s.d, n + 8)); HIPCHK(h, hipMemcpyAsync(s.d, disc, n, hipMemcpyHostToDevice, h->stream)); }
+	HIPCHK(h, hipMemcpyAsync(o.get(), rel.data(), 8 * (n + 1), hipMemcpyHostToDevice, h->stream));
 	HIPCHK(h, hipStreamSynchronize(h->stream));   /* rel[] goes out of scope */
 	return 0;
 }
@@ -770,12 +788,15 @@ const uint64_t L2_ITEM_CHUNKS = 16384;       /* level-2 work item = up to 1M rec
 const uint64_t SUB_BATCH_BASES = 1ull << 30;      /* linear records of one sub-batch: <= 17 GB at 16 bytes; 2^28 cost 2 ms per C2 step in launch tails */
 
 size_t rec_bytes(kmr_handle *h) { return h->superkmer_mode ? 16 : 8 * h->W + (h->ext ? 16 : 8); }      /* Record<W> / RecordX<W>; a 16-byte granule of a super-k-mer record */
+/* entries an entry buffer of the count pass holds: keys apart from their values (uw_* / us_*), or packed with a value word (ue, ue2, early.ue) */
+uint64_t key_entries(kmr_handle *h, const DevBuf &keys) { return keys.cap() / (8ull * h->W); }
+uint64_t packed_entries(kmr_handle *h, const DevBuf &ue) { return ue.cap() / (8ull * (h->W + 1)); }
 /* partition kernel shape: one 1024-thread block per compute unit, 8 records per thread per batch, a
  * 4-record write-combining line per list in LDS (see partition_direct_kernel) */
 /* (PD_THREADS, PD_RPT, PD_LINE and COUNT_LOG2S: kmr_instances.hpp) */
 /* partition bits per level that keep the per-list book-keeping and lines inside the 160 KB of LDS */
 int max_part_bits(kmr_handle *h) { return rec_bytes(h) <= 24 ? 10 : 9; }
-PoolView pool_view(kmr_handle *h, HostPool &p) { PoolView v; v.base = p.base; v.chunk_list = p.chunk_list; v.chunk_count = p.chunk_count; v.head = p.head; v.cap = p.cap; v.err = h->derr; return v; }
+PoolView pool_view(kmr_handle *h, HostPool &p) { PoolView v; v.base = p.base.get<uint8_t>(); v.chunk_list = p.chunk_list.get<uint32_t>(); v.chunk_count = p.chunk_count.get<uint32_t>(); v.head = p.head.get<unsigned int>(); v.cap = p.cap; v.err = h->derr.get<uint32_t>(); return v; }
 /* log2 of the weak map's bucket count: the partition is cut along the bucket index (part_order) */
 uint32_t part_rot(kmr_handle *h) { uint32_t r = 0; while ((1ull << (r + 1)) <= h->nb_weak) r++; return r; }
 template <int W, bool EXT, int LEVEL> int launch_partition(kmr_handle *h, const PartSource<W> &S, HostPool &pool, int grid, int bits, int shift) {
@@ -784,15 +805,11 @@ template <int W, bool EXT, int LEVEL> int launch_partition(kmr_handle *h, const 
 	if (dbg()) fprintf(stderr, "partition level %d W=%d bits=%d shift=%d smem=%zu grid=%d\n", LEVEL, W, bits, shift, smem, grid);
 	HIPCHK(h, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
 	                              (int)partition_direct_smem_bytes<W, EXT, PD_THREADS, PD_RPT, PD_LINE>(max_part_bits(h))));
-	hipLaunchKernelGGL(kern, dim3(grid), dim3(PD_THREADS), smem, h->stream, S, pool_view(h, pool), h->work_counter, bits, shift);
+	hipLaunchKernelGGL(kern, dim3(grid), dim3(PD_THREADS), smem, h->stream, S, pool_view(h, pool), h->work_counter.get<unsigned int>(), bits, shift);
 	HIPCHK(h, hipGetLastError());
 	return 0;
 }
 
-void pool_free(HostPool &p) {
-	if (p.base) hipFree(p.base); if (p.chunk_list) hipFree(p.chunk_list); if (p.chunk_count) hipFree(p.chunk_count); if (p.head) hipFree(p.head);
-	p = HostPool();
-}
 /* make sure the pool can take 'extra' more chunks (keeps the used prefix when it has to move) */
 int pool_reserve(kmr_handle *h, HostPool &p, uint64_t extra, bool keep) {
 	unsigned int used = 0;
@@ -801,46 +818,36 @@ int pool_reserve(kmr_handle *h, HostPool &p, uint64_t extra, bool keep) {
 		/* the host keeps an upper bound of the chunks handed out so far (every launch adds what it reserved); only
 		 * when that bound no longer fits is the stream drained and the real allocator head read back */
 		if (p.base && p.used_ub + extra + 64 <= p.cap) { p.used_ub += extra; return 0; }
-		HIPCHK(h, hipStreamSynchronize(h->stream)); HIPCHK(h, hipMemcpy(&used, p.head, 4, hipMemcpyDeviceToHost)); if (used > p.cap) used = p.cap;
+		HIPCHK(h, hipStreamSynchronize(h->stream)); HIPCHK(h, hipMemcpy(&used, p.head.get<unsigned int>(), 4, hipMemcpyDeviceToHost)); if (used > p.cap) used = p.cap;
 	}
 	p.used_ub = (uint64_t)used + extra;
 	const uint64_t need = (uint64_t)used + extra + 64;
 	if (need >= 0xffffffffull) return fail(h, KMR_ERR_CAPACITY, "record pool would exceed 2^32 chunks");
-	if (!p.head) { HIPCHK(h, dev_malloc((void **)&p.head, 4)); HIPCHK(h, hipMemset(p.head, 0, 4)); }
-	if (!keep) HIPCHK(h, hipMemsetAsync(p.head, 0, 4, h->stream));
+	if (!p.head) { HIPCHK(h, p.head.alloc(4)); HIPCHK(h, hipMemset(p.head.get(), 0, 4)); }
+	if (!keep) HIPCHK(h, hipMemsetAsync(p.head.get<unsigned int>(), 0, 4, h->stream));
 	if (need <= p.cap) return 0;
 	uint64_t ncap = keep && used ? need + need / 4 : need;
 	if (p.presize && need + p.presize < 0xffffffffull) ncap = std::max(ncap, need + p.presize);
 	p.presize = 0;
 	p.chunk_bytes = (size_t)CH * rec_bytes(h);
-	uint8_t *nb; uint32_t *nl, *nc;
-	HIPCHK(h, dev_malloc((void **)&nb, ncap * p.chunk_bytes));
-	HIPCHK(h, dev_malloc((void **)&nl, 4 * ncap)); HIPCHK(h, dev_malloc((void **)&nc, 4 * ncap));
+	DevBuf nb, nl, nc;
+	HIPCHK(h, nb.alloc(ncap * p.chunk_bytes));
+	HIPCHK(h, nl.alloc(4 * ncap)); HIPCHK(h, nc.alloc(4 * ncap));
 	if (used) {
-		HIPCHK(h, hipMemcpy(nb, p.base, (size_t)used * p.chunk_bytes, hipMemcpyDeviceToDevice));
-		HIPCHK(h, hipMemcpy(nl, p.chunk_list, 4ull * used, hipMemcpyDeviceToDevice));
-		HIPCHK(h, hipMemcpy(nc, p.chunk_count, 4ull * used, hipMemcpyDeviceToDevice));
+		HIPCHK(h, hipMemcpy(nb.get(), p.base.get(), (size_t)used * p.chunk_bytes, hipMemcpyDeviceToDevice));
+		HIPCHK(h, hipMemcpy(nl.get(), p.chunk_list.get(), 4ull * used, hipMemcpyDeviceToDevice));
+		HIPCHK(h, hipMemcpy(nc.get(), p.chunk_count.get(), 4ull * used, hipMemcpyDeviceToDevice));
 		/* device-to-device copies may return before they have run: the sources are freed next */
 		HIPCHK(h, hipDeviceSynchronize());
 	}
-	if (p.base) hipFree(p.base); if (p.chunk_list) hipFree(p.chunk_list); if (p.chunk_count) hipFree(p.chunk_count);
-	p.base = nb; p.chunk_list = nl; p.chunk_count = nc; p.cap = (uint32_t)ncap;
+	p.base = std::move(nb); p.chunk_list = std::move(nl); p.chunk_count = std::move(nc); p.cap = (uint32_t)ncap;
 	return 0;
 }
 
-template <class T> int ensure_buf(kmr_handle *h, T *&ptr, uint64_t &cap, uint64_t need, size_t elem) {
-	if (need <= cap && ptr) return 0;
-	if (ptr) { HIPCHK(h, hipStreamSynchronize(h->stream)); hipFree((void *)ptr); }   /* kernels in flight may still read it */
-	ptr = nullptr; cap = 0;
-	const uint64_t n = std::max<uint64_t>(need, 16);
-	HIPCHK(h, dev_malloc((void **)&ptr, n * elem));
-	cap = n;
-	return 0;
-}
 
 int zero_work_counter(kmr_handle *h) {
-	if (!h->work_counter) HIPCHK(h, dev_malloc((void **)&h->work_counter, 4));
-	HIPCHK(h, hipMemsetAsync(h->work_counter, 0, 4, h->stream));
+	int rc = h->work_counter.reserve(h, "work_counter", 4); if (rc) return rc;
+	HIPCHK(h, hipMemsetAsync(h->work_counter.get<unsigned int>(), 0, 4, h->stream));
 	return 0;
 }
 
@@ -859,10 +866,10 @@ int partition_blocks(kmr_handle *h) { return h->tune.part_blocks > 0 ? h->tune.p
 /* per-block level-1 state, allocated (and emptied) on first use */
 template <int W, bool EXT> int ensure_l1_state(kmr_handle *h) {
 	const size_t stride = partition_state_bytes<W, EXT, PD_LINE>(h->bits1), need = stride * (size_t)partition_blocks(h);
-	if (h->l1_state && h->l1_state_bytes == need) return 0;
-	if (h->l1_state) { HIPCHK(h, hipStreamSynchronize(h->stream)); hipFree(h->l1_state); h->l1_state = nullptr; }
-	HIPCHK(h, dev_malloc((void **)&h->l1_state, need)); h->l1_state_bytes = need;
-	hipLaunchKernelGGL(partition_state_init_kernel, dim3(partition_blocks(h)), dim3(256), 0, h->stream, h->l1_state, stride, h->bits1, (uint32_t)partition_blocks(h));
+	if (h->l1_state.cap() == need) return 0;
+	if (h->l1_state) HIPCHK(h, hipStreamSynchronize(h->stream));
+	HIPCHK(h, h->l1_state.alloc(need));
+	hipLaunchKernelGGL(partition_state_init_kernel, dim3(partition_blocks(h)), dim3(256), 0, h->stream, h->l1_state.get<uint8_t>(), stride, h->bits1, (uint32_t)partition_blocks(h));
 	HIPCHK(h, hipGetLastError());
 	h->l1_state_dirty = false;
 	return 0;
@@ -873,7 +880,7 @@ template <int W, bool EXT> int flush_l1_state(kmr_handle *h) {
 	int rc = pool_reserve(h, h->l1, (uint64_t)partition_blocks(h) * ((1ull << h->bits1) + 512) + 64, true); if (rc) return rc;
 	rc = zero_work_counter(h); if (rc) return rc;
 	PartSource<W> S; memset(&S, 0, sizeof(S));
-	S.kb = h->hkb; S.rot = part_rot(h); S.state = h->l1_state; S.state_final = 1;
+	S.kb = h->hkb; S.rot = part_rot(h); S.state = h->l1_state.get<uint8_t>(); S.state_final = 1;
 	rc = launch_partition<W, EXT, 1>(h, S, h->l1, partition_blocks(h), h->bits1, 0);
 	h->l1_state_dirty = false;
 	return rc;
@@ -895,9 +902,7 @@ template <int W, bool EXT> int partition_level1(kmr_handle *h, const void *linea
 			size_t mfree = 0, mtotal = 0;
 			if (hipMemGetInfo(&mfree, &mtotal) == hipSuccess && (double)mfree < (double)chunks * CH * rec_bytes(h) * 1.02 + (double)(2ull << 30)) {
 				HIPCHK(h, hipStreamSynchronize(h->stream));
-				if (h->uw_keys) hipFree(h->uw_keys); if (h->uw_vals) hipFree(h->uw_vals); if (h->us_keys) hipFree(h->us_keys); if (h->us_b8) hipFree(h->us_b8); if (h->us_pkt) hipFree(h->us_pkt);
-	if (h->ue) hipFree(h->ue); if (h->ue2) hipFree(h->ue2); h->ue = h->ue2 = nullptr; h->ue_cap = h->ue2_cap = 0;
-				h->uw_keys = h->uw_vals = h->us_keys = h->us_b8 = h->us_pkt = nullptr; h->uw_cap = h->us_cap = 0;
+				h->uw_keys.reset(); h->uw_vals.reset(); h->us_keys.reset(); h->us_b8.reset(); h->us_pkt.reset(); h->ue.reset(); h->ue2.reset();
 			}
 		}
 		uint64_t want = est / CH + launches * (uint64_t)grid * ((1ull << h->bits1) + 512) + 64 + l2_allowance;
@@ -917,7 +922,7 @@ template <int W, bool EXT> int partition_level1(kmr_handle *h, const void *linea
 	S.valid_counter = valid_counter; S.kb = h->hkb; S.rot = part_rot(h); S.packed_words = packed_words; S.ordinal_base = ordinal_base;
 	if (!h->tune.no_l1_state) {
 		rc = ensure_l1_state<W, EXT>(h); if (rc) return rc;
-		S.state = h->l1_state; S.state_final = 0; h->l1_state_dirty = true;
+		S.state = h->l1_state.get<uint8_t>(); S.state_final = 0; h->l1_state_dirty = true;
 	}
 	hipEvent_t ta, tb; time_begin(h, KMR_TIME_PARTITION1, &ta, &tb);
 	rc = launch_partition<W, EXT, 1>(h, S, h->l1, grid, h->bits1, 0);
@@ -948,17 +953,17 @@ template <int W, bool EXT> int extract_by_owner_t(kmr_handle *h, const ReadsView
 		rv.first_read_idx = rvAll.first_read_idx + r;
 		int rc = prepare_units(h, rv); if (rc) return rc;
 		const uint64_t nu = rv.u_start ? rv.n_units : m;
-		rc = ensure_buf(h, h->kcap, h->kcap_n, nu + 1, 4); if (rc) return rc;
-		rc = ensure_buf(h, h->koff, h->koff_n, nu + 1, 8); if (rc) return rc;
-		hipLaunchKernelGGL(kmer_capacity_kernel, dim3(grid_for(nu)), dim3(256), 0, h->stream, rv, h->k, h->kcap);
+		rc = h->kcap.reserve(h, "kcap", 4 * std::max<uint64_t>(nu + 1, 16)); if (rc) return rc;
+		rc = h->koff.reserve(h, "koff", 8 * std::max<uint64_t>(nu + 1, 16)); if (rc) return rc;
+		hipLaunchKernelGGL(kmer_capacity_kernel, dim3(grid_for(nu)), dim3(256), 0, h->stream, rv, h->k, h->kcap.get<uint32_t>());
 		HIPCHK(h, hipGetLastError());
-		rc = exclusive_scan(h, h->kcap, nu, h->koff); if (rc) return rc;
+		rc = exclusive_scan(h, h->kcap.get<uint32_t>(), nu, h->koff.get<uint64_t>()); if (rc) return rc;
 		uint64_t total_cap = 0;
-		HIPCHK(h, hipMemcpy(&total_cap, h->koff + nu, 8, hipMemcpyDeviceToHost));
+		HIPCHK(h, hipMemcpy(&total_cap, h->koff.get<uint64_t>() + nu, 8, hipMemcpyDeviceToHost));
 		const uint64_t tiles = (nu + 63) / 64;
-		rc = ensure_buf(h, h->linear, h->linear_cap, total_cap, sizeof(typename PoolRec<W, EXT>::type)); if (rc) return rc;      /* (rec_bytes() is the granule size on a super-k-mer handle) */
-		rc = ensure_buf(h, h->tile_count, h->tile_cap, tiles, 4); if (rc) return rc;
-		LinearOp<W, EXT, false> op; op.records = (typename PoolRec<W, EXT>::type *)h->linear; op.koff = h->koff; op.tile_count = h->tile_count; op.first_read_idx = rv.first_read_idx;
+		rc = h->linear.reserve(h, "linear", sizeof(typename PoolRec<W, EXT>::type) * std::max<uint64_t>(total_cap, 16)); if (rc) return rc;      /* (rec_bytes() is the granule size on a super-k-mer handle) */
+		rc = h->tile_count.reserve(h, "tile_count", 4 * std::max<uint64_t>(tiles, 16)); if (rc) return rc;
+		LinearOp<W, EXT, false> op; op.records = (typename PoolRec<W, EXT>::type *)h->linear.get(); op.koff = h->koff.get<uint64_t>(); op.tile_count = h->tile_count.get<uint32_t>(); op.first_read_idx = rv.first_read_idx;
 		h->sender_launch = dev_pos == nullptr;
 		rc = launch_extract<W, EXT>(h, rv, op);
 		h->sender_launch = false;
@@ -969,11 +974,11 @@ template <int W, bool EXT> int extract_by_owner_t(kmr_handle *h, const ReadsView
 		OwnerFn of; of.m = 0; of.off = of.win = of.list_bits = 0;
 		if (h->superkmer_mode && h->sk_exchange) { of.m = h->sk_m; of.off = h->sk_off; of.win = h->sk_win; of.list_bits = h->sk_bits; }
 		if (dev_pos)
-			hipLaunchKernelGGL((owner_scatter_kernel<W, EXT, true>), dim3(grid), dim3(OWNER_THREADS), 0, h->stream, (const typename PoolRec<W, EXT>::type *)h->linear, h->koff, h->tile_count, tiles, h->hkb,
-			                   h->cfg.world_size, (uint32_t *)dev_records, seg_capacity, (unsigned long long *)dev_seg_counts, h->work_counter, h->derr, dev_pos, of);
+			hipLaunchKernelGGL((owner_scatter_kernel<W, EXT, true>), dim3(grid), dim3(OWNER_THREADS), 0, h->stream, (const typename PoolRec<W, EXT>::type *)h->linear.get(), h->koff.get<uint64_t>(), h->tile_count.get<uint32_t>(), tiles, h->hkb,
+			                   h->cfg.world_size, (uint32_t *)dev_records, seg_capacity, (unsigned long long *)dev_seg_counts, h->work_counter.get<unsigned int>(), h->derr.get<uint32_t>(), dev_pos, of);
 		else
-			hipLaunchKernelGGL((owner_scatter_kernel<W, EXT>), dim3(grid), dim3(OWNER_THREADS), 0, h->stream, (const typename PoolRec<W, EXT>::type *)h->linear, h->koff, h->tile_count, tiles, h->hkb,
-			                   h->cfg.world_size, (uint32_t *)dev_records, seg_capacity, (unsigned long long *)dev_seg_counts, h->work_counter, h->derr, (uint32_t *)nullptr, of);
+			hipLaunchKernelGGL((owner_scatter_kernel<W, EXT>), dim3(grid), dim3(OWNER_THREADS), 0, h->stream, (const typename PoolRec<W, EXT>::type *)h->linear.get(), h->koff.get<uint64_t>(), h->tile_count.get<uint32_t>(), tiles, h->hkb,
+			                   h->cfg.world_size, (uint32_t *)dev_records, seg_capacity, (unsigned long long *)dev_seg_counts, h->work_counter.get<unsigned int>(), h->derr.get<uint32_t>(), (uint32_t *)nullptr, of);
 		HIPCHK(h, hipGetLastError());
 	}
 	return 0;
@@ -994,17 +999,17 @@ template <int W, bool EXT> int add_reads_partition_t(kmr_handle *h, const ReadsV
 		/* k-mer capacity of every work unit -> region of each 64-unit tile in the linear buffer */
 		int rc = prepare_units(h, rv); if (rc) return rc;
 		const uint64_t nu = rv.u_start ? rv.n_units : m;
-		rc = ensure_buf(h, h->kcap, h->kcap_n, nu + 1, 4); if (rc) return rc;
-		rc = ensure_buf(h, h->koff, h->koff_n, nu + 1, 8); if (rc) return rc;
-		hipLaunchKernelGGL(kmer_capacity_kernel, dim3(grid_for(nu)), dim3(256), 0, h->stream, rv, h->k, h->kcap);
+		rc = h->kcap.reserve(h, "kcap", 4 * std::max<uint64_t>(nu + 1, 16)); if (rc) return rc;
+		rc = h->koff.reserve(h, "koff", 8 * std::max<uint64_t>(nu + 1, 16)); if (rc) return rc;
+		hipLaunchKernelGGL(kmer_capacity_kernel, dim3(grid_for(nu)), dim3(256), 0, h->stream, rv, h->k, h->kcap.get<uint32_t>());
 		HIPCHK(h, hipGetLastError());
-		rc = exclusive_scan(h, h->kcap, nu, h->koff); if (rc) return rc;
+		rc = exclusive_scan(h, h->kcap.get<uint32_t>(), nu, h->koff.get<uint64_t>()); if (rc) return rc;
 		uint64_t total_cap = 0;
-		HIPCHK(h, hipMemcpy(&total_cap, h->koff + nu, 8, hipMemcpyDeviceToHost));
+		HIPCHK(h, hipMemcpy(&total_cap, h->koff.get<uint64_t>() + nu, 8, hipMemcpyDeviceToHost));
 		const uint64_t tiles = (nu + 63) / 64;
-		rc = ensure_buf(h, h->linear, h->linear_cap, total_cap, rec_bytes(h)); if (rc) return rc;
-		rc = ensure_buf(h, h->tile_count, h->tile_cap, tiles, 4); if (rc) return rc;
-		LinearOp<W, EXT> op; op.records = (typename PoolRec<W, EXT>::type *)h->linear; op.koff = h->koff; op.tile_count = h->tile_count; op.first_read_idx = rv.first_read_idx;
+		rc = h->linear.reserve(h, "linear", rec_bytes(h) * std::max<uint64_t>(total_cap, 16)); if (rc) return rc;
+		rc = h->tile_count.reserve(h, "tile_count", 4 * std::max<uint64_t>(tiles, 16)); if (rc) return rc;
+		LinearOp<W, EXT> op; op.records = (typename PoolRec<W, EXT>::type *)h->linear.get(); op.koff = h->koff.get<uint64_t>(); op.tile_count = h->tile_count.get<uint32_t>(); op.first_read_idx = rv.first_read_idx;
 		hipEvent_t a, b, a2, b2; time_begin(h, KMR_TIME_BUILD, &a, &b);
 		time_begin(h, KMR_TIME_EXTRACT, &a2, &b2);
 		rc = launch_extract<W, EXT>(h, rv, op);
@@ -1015,10 +1020,10 @@ template <int W, bool EXT> int add_reads_partition_t(kmr_handle *h, const ReadsV
 			 * input comes out of L2 and only the scatter writes go to HBM -- what the pass would cost if extract fed it from
 			 * registers.  The result is not a spectrum. */
 			const uint64_t distinct = std::max<uint64_t>(1, strtoull(getenv("KMR_DEBUG_SAME_TILE"), nullptr, 10));
-			hipLaunchKernelGGL(same_tile_kernel, dim3(grid_for(tiles)), dim3(256), 0, h->stream, h->koff, tiles, distinct, total_cap / std::max<uint64_t>(tiles, 1));
+			hipLaunchKernelGGL(same_tile_kernel, dim3(grid_for(tiles)), dim3(256), 0, h->stream, h->koff.get<uint64_t>(), tiles, distinct, total_cap / std::max<uint64_t>(tiles, 1));
 		}
 #endif
-		if (!rc) rc = partition_level1<W, EXT>(h, h->linear, h->koff, h->tile_count, tiles, 64, 0, 0, total_cap);
+		if (!rc) rc = partition_level1<W, EXT>(h, h->linear.get(), h->koff.get<uint64_t>(), h->tile_count.get<uint32_t>(), tiles, 64, 0, 0, total_cap);
 		time_end(h, KMR_TIME_BUILD, a, b);
 		if (rc) return rc;
 	}
@@ -1034,7 +1039,7 @@ int add_reads_partition(kmr_handle *h, const ReadsView &rv, uint64_t total_bases
 int build_csr(kmr_handle *h, HostPool &p, uint64_t nl, uint32_t first, uint64_t **list_start, uint64_t **list_chunks, uint32_t *n_chunks_out) {
 	unsigned int used = 0;
 	HIPCHK(h, hipStreamSynchronize(h->stream));
-	HIPCHK(h, hipMemcpy(&used, p.head, 4, hipMemcpyDeviceToHost));
+	HIPCHK(h, hipMemcpy(&used, p.head.get<unsigned int>(), 4, hipMemcpyDeviceToHost));
 	if (used > p.cap) used = p.cap;
 	used = used > first ? used - first : 0;            /* only chunks [first, head) are looked at */
 	uint32_t *cnt;
@@ -1042,22 +1047,24 @@ int build_csr(kmr_handle *h, HostPool &p, uint64_t nl, uint32_t first, uint64_t 
 	  arc = arena_get(h, list_chunks, std::max<unsigned>(used, 1)); if (arc) return arc; }
 	HIPCHK(h, hipMemsetAsync(cnt, 0, 4 * nl, h->stream));
 	const unsigned csr_grid = (unsigned)(((uint64_t)used + CSR_THREADS * CSR_ITEMS - 1) / (CSR_THREADS * CSR_ITEMS));
-	if (used) hipLaunchKernelGGL(chunk_hist_kernel, dim3(csr_grid), dim3(CSR_THREADS), 0, h->stream, p.chunk_list + first, used, cnt, (uint32_t)nl);
+	if (used) hipLaunchKernelGGL(chunk_hist_kernel, dim3(csr_grid), dim3(CSR_THREADS), 0, h->stream, p.chunk_list.get<uint32_t>() + first, used, cnt, (uint32_t)nl);
 	int rc = exclusive_scan(h, cnt, nl, *list_start); if (rc) return rc;
 	HIPCHK(h, hipMemsetAsync(cnt, 0, 4 * nl, h->stream));
-	if (used) hipLaunchKernelGGL(chunk_scatter_kernel, dim3(csr_grid), dim3(CSR_THREADS), 0, h->stream, p.chunk_list + first, p.chunk_count + first, used, first, *list_start, cnt, *list_chunks, (uint32_t)nl);
+	if (used) hipLaunchKernelGGL(chunk_scatter_kernel, dim3(csr_grid), dim3(CSR_THREADS), 0, h->stream, p.chunk_list.get<uint32_t>() + first, p.chunk_count.get<uint32_t>() + first, used, first, *list_start, cnt, *list_chunks, (uint32_t)nl);
 	HIPCHK(h, hipGetLastError());
 	*n_chunks_out = used;
 	if (dbg()) {
-		unsigned long long *d, hv[2] = {0, 0};
-		HIPCHK(h, dev_malloc((void **)&d, 16)); HIPCHK(h, hipMemset(d, 0, 16));
-		if (used) hipLaunchKernelGGL(pool_records_kernel, dim3(grid_for(used)), dim3(256), 0, h->stream, p.chunk_list, p.chunk_count, used, d, d + 1);
+		unsigned long long hv[2] = {0, 0};
+		DevBuf db; HIPCHK(h, db.alloc(16)); HIPCHK(h, hipMemset(db.get(), 0, 16));
+		unsigned long long *d = db.get<unsigned long long>();
+		if (used) hipLaunchKernelGGL(pool_records_kernel, dim3(grid_for(used)), dim3(256), 0, h->stream, p.chunk_list.get<uint32_t>(), p.chunk_count.get<uint32_t>(), used, d, d + 1);
 		HIPCHK(h, hipStreamSynchronize(h->stream));
-		HIPCHK(h, hipMemcpy(hv, d, 16, hipMemcpyDeviceToHost)); hipFree(d);
+		HIPCHK(h, hipMemcpy(hv, d, 16, hipMemcpyDeviceToHost));
 		fprintf(stderr, "build_csr: lists %llu chunks %u valid %llu records %llu (expected %llu)\n", (unsigned long long)nl, used, hv[1], hv[0], (unsigned long long)h->stats.raw_good_kmers);
-		unsigned long long *v, vv[3] = {0, 0, 0};
+		unsigned long long vv[3] = {0, 0, 0};
 		int bits = 0; while ((1ull << bits) < nl) bits++;
-		HIPCHK(h, dev_malloc((void **)&v, 24)); HIPCHK(h, hipMemset(v, 0, 24));
+		DevBuf vb; HIPCHK(h, vb.alloc(24)); HIPCHK(h, hipMemset(vb.get(), 0, 24));
+		unsigned long long *v = vb.get<unsigned long long>();
 		PoolView pvw = pool_view(h, p);
 #define VLK(Wv, E) hipLaunchKernelGGL((verify_lists_kernel<Wv, E>), dim3(4096), dim3(256), 0, h->stream, pvw, *list_start, *list_chunks, nl, bits, h->hkb, part_rot(h), v, v + 1, v + 2)
 		switch (h->W) {
@@ -1068,7 +1075,7 @@ int build_csr(kmr_handle *h, HostPool &p, uint64_t nl, uint32_t first, uint64_t 
 		}
 #undef VLK
 		HIPCHK(h, hipStreamSynchronize(h->stream));
-		HIPCHK(h, hipMemcpy(vv, v, 24, hipMemcpyDeviceToHost)); hipFree(v);
+		HIPCHK(h, hipMemcpy(vv, v, 24, hipMemcpyDeviceToHost));
 		fprintf(stderr, "verify_lists: records via CSR %llu misfiled %llu zero-weight %llu\n", vv[0], vv[1], vv[2]);
 	}
 	return 0;
@@ -1133,7 +1140,7 @@ template <int W, bool EXT> int finalize_partition_t(kmr_handle *h, uint32_t min_
 		 * (compact, slab by slab: the faster writes); without, a block recycles the chunks it has just read. */
 		const uint64_t partials = ib.size() * (1ull << nbits) + (uint64_t)part_grid(h) * 512 + 64;
 		unsigned int head_before = 0;
-		HIPCHK(h, hipMemcpy(&head_before, h->l1.head, 4, hipMemcpyDeviceToHost));
+		HIPCHK(h, hipMemcpy(&head_before, h->l1.head.get<unsigned int>(), 4, hipMemcpyDeviceToHost));
 		const bool recycle = h->tune.recycle >= 0 ? h->tune.recycle != 0 : (uint64_t)head_before + G / CH + partials + 64 > h->l1.cap;
 		h->l1.used_ub = head_before;
 		rc = pool_reserve(h, h->l1, (recycle ? 0 : G / CH) + partials, true); if (rc) return rc;
@@ -1175,11 +1182,9 @@ template <int W, bool EXT> int finalize_partition_t(kmr_handle *h, uint32_t min_
 	if (h->tune.entry_share >= 0) {       /* kmr_tune "entry_share": start from a given (e.g. hopeless) estimate so that the retry below has to run */
 		const double sh = h->tune.entry_share;
 		wcap = std::min<uint64_t>(wmax, (uint64_t)((double)G * sh) + 16384); if (keepSing) scap = std::min<uint64_t>(smax, (uint64_t)((double)G * sh) + 16384);
-		if (h->uw_keys) { hipFree(h->uw_keys); hipFree(h->uw_vals); h->uw_keys = h->uw_vals = nullptr; h->uw_cap = 0; }
-		if (h->us_keys) { hipFree(h->us_keys); hipFree(h->us_b8); if (h->us_pkt) hipFree(h->us_pkt); h->us_keys = h->us_b8 = h->us_pkt = nullptr; h->us_cap = 0; }
+		h->uw_keys.reset(); h->uw_vals.reset(); h->us_keys.reset(); h->us_b8.reset(); h->us_pkt.reset();
 	}
-	if (h->uw_keys && h->uw_cap >= wcap) wcap = h->uw_cap;
-	if (h->us_keys && h->us_cap >= scap) scap = h->us_cap;
+	wcap = std::max(wcap, key_entries(h, h->uw_keys)); scap = std::max(scap, key_entries(h, h->us_keys));
 	uint32_t *wc = nullptr, *sc = nullptr; FinalizeCounters *fc = nullptr; unsigned long long *cursors = nullptr;
 	rc = arena_get(h, &wc, h->nb_weak); if (rc) return rc; rc = arena_get(h, &sc, h->nb_sing); if (rc) return rc;
 	rc = arena_get(h, &fc, 1); if (rc) return rc; rc = arena_get(h, &cursors, 2); if (rc) return rc;
@@ -1187,26 +1192,26 @@ template <int W, bool EXT> int finalize_partition_t(kmr_handle *h, uint32_t min_
 	hipEvent_t tca, tcb; time_begin(h, KMR_TIME_COUNT, &tca, &tcb);
 	for (int attempt = 0; ; attempt++) {
 	{	/* the linear record buffer is dead during finalize: given back when the entry buffers would not fit beside it */
-		const double need = (!h->uw_keys || h->uw_cap < wcap ? (8.0 * W + 4.0 * vw) * (double)wcap : 0.0) + (!h->us_keys || h->us_cap < scap ? (8.0 * W + 1.0) * (double)scap : 0.0);
+		const double need = (key_entries(h, h->uw_keys) < wcap ? (8.0 * W + 4.0 * vw) * (double)wcap : 0.0) + (key_entries(h, h->us_keys) < scap ? (8.0 * W + 1.0) * (double)scap : 0.0);
 		size_t mfree = 0, mtotal = 0;
 		if (need > 0 && h->linear && hipMemGetInfo(&mfree, &mtotal) == hipSuccess && (double)mfree < need + (double)G * 0.3 * (8.0 * W + 12.0) + (double)(2ull << 30)) {
 			HIPCHK(h, hipStreamSynchronize(h->stream));
-			hipFree(h->linear); h->linear = nullptr; h->linear_cap = 0;
+			h->linear.reset();
 		}
 	}
-	if (!h->uw_keys || h->uw_cap < wcap) {
-		if (h->uw_keys) hipFree(h->uw_keys); if (h->uw_vals) hipFree(h->uw_vals); h->uw_keys = h->uw_vals = nullptr; h->uw_cap = 0;
-		HIPCHK(h, dev_malloc(&h->uw_keys, 8ull * W * wcap)); HIPCHK(h, dev_malloc(&h->uw_vals, 4ull * vw * wcap)); h->uw_cap = wcap;
+	if (key_entries(h, h->uw_keys) < wcap || !h->uw_vals) {
+		h->uw_keys.reset(); h->uw_vals.reset();
+		HIPCHK(h, h->uw_keys.alloc(8ull * W * wcap)); HIPCHK(h, h->uw_vals.alloc(4ull * vw * wcap));
 	}
-	if (!h->us_keys || h->us_cap < scap) {
-		if (h->us_keys) hipFree(h->us_keys); if (h->us_b8) hipFree(h->us_b8); if (h->us_pkt) hipFree(h->us_pkt); h->us_keys = h->us_b8 = h->us_pkt = nullptr; h->us_cap = 0;
-		HIPCHK(h, dev_malloc(&h->us_keys, 8ull * W * scap)); HIPCHK(h, dev_malloc(&h->us_b8, scap)); if (EXT) HIPCHK(h, dev_malloc(&h->us_pkt, 4 * scap)); h->us_cap = scap;
+	if (key_entries(h, h->us_keys) < scap || !h->us_b8 || (EXT && !h->us_pkt)) {
+		h->us_keys.reset(); h->us_b8.reset(); h->us_pkt.reset();
+		HIPCHK(h, h->us_keys.alloc(8ull * W * scap)); HIPCHK(h, h->us_b8.alloc(scap)); if (EXT) HIPCHK(h, h->us_pkt.alloc(4 * scap));
 	}
 	HIPCHK(h, hipMemsetAsync(wc, 0, 4 * h->nb_weak, h->stream)); HIPCHK(h, hipMemsetAsync(sc, 0, 4 * h->nb_sing, h->stream));
 	HIPCHK(h, hipMemsetAsync(fc, 0, sizeof(FinalizeCounters), h->stream)); HIPCHK(h, hipMemsetAsync(cursors, 0, 16, h->stream));
-	CountOut out; out.wkeys = (uint64_t *)h->uw_keys; out.wvals = (uint32_t *)h->uw_vals; out.wentries = nullptr; out.wcursor = cursors; out.wcap = h->uw_cap;
-	out.skeys = (uint64_t *)h->us_keys; out.sweight = (uint8_t *)h->us_b8; out.spkt = (uint32_t *)h->us_pkt; out.scursor = cursors + 1; out.scap = h->us_cap;
-	out.weakCount = wc; out.singCount = sc; out.fc = fc; out.err = h->derr;
+	CountOut out; out.wkeys = h->uw_keys.get<uint64_t>(); out.wvals = h->uw_vals.get<uint32_t>(); out.wentries = nullptr; out.wcursor = cursors; out.wcap = key_entries(h, h->uw_keys);
+	out.skeys = h->us_keys.get<uint64_t>(); out.sweight = h->us_b8.get<uint8_t>(); out.spkt = h->us_pkt.get<uint32_t>(); out.scursor = cursors + 1; out.scap = key_entries(h, h->us_keys);
+	out.weakCount = wc; out.singCount = sc; out.fc = fc; out.err = h->derr.get<uint32_t>();
 	rc = zero_work_counter(h); if (rc) return rc;
 	#ifdef KMR_DEBUG_HOOKS
 	const int count_reps = getenv("KMR_COUNT_CHECK") ? atoi(getenv("KMR_COUNT_CHECK")) : 0;
@@ -1229,44 +1234,44 @@ template <int W, bool EXT> int finalize_partition_t(kmr_handle *h, uint32_t min_
 			auto kern = count_kernel<W, EXT, 11>;
 			const size_t smem = count_smem_bytes<W, EXT, 11>();
 			HIPCHK(h, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-			hipLaunchKernelGGL(kern, dim3(grid), dim3(COUNT_THREADS), smem, h->stream, pool_view(h, h->l1), ls2, lc2, nl2, out, f, h->work_counter, 0);
+			hipLaunchKernelGGL(kern, dim3(grid), dim3(COUNT_THREADS), smem, h->stream, pool_view(h, h->l1), ls2, lc2, nl2, out, f, h->work_counter.get<unsigned int>(), 0);
 		} else if (EXT && W == 1 && !h->tune.no_narrow) {
 			/* extension values at k <= 32: 16-bit tallies for every list of at most 65 535 records (two blocks per CU), then
 			 * the wide table for whatever is longer */
 			auto kn = count_kernel<W, EXT, COUNT_LOG2S, true>;
 			const size_t sn = count_smem_bytes<W, EXT, COUNT_LOG2S, true>();
 			HIPCHK(h, hipFuncSetAttribute((const void *)kn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sn));
-			hipLaunchKernelGGL(kn, dim3(grid), dim3(COUNT_THREADS), sn, h->stream, pool_view(h, h->l1), ls2, lc2, nl2, out, f, h->work_counter, 1);
+			hipLaunchKernelGGL(kn, dim3(grid), dim3(COUNT_THREADS), sn, h->stream, pool_view(h, h->l1), ls2, lc2, nl2, out, f, h->work_counter.get<unsigned int>(), 1);
 			HIPCHK(h, hipGetLastError());
 			/* is any list longer than the narrow tallies can take?  (the work counter word doubles as the maximum) */
 			rc = zero_work_counter(h); if (rc) return rc;
-			hipLaunchKernelGGL(max_list_chunks_kernel, dim3(grid_for(nl2)), dim3(256), 0, h->stream, ls2, nl2, h->work_counter);
+			hipLaunchKernelGGL(max_list_chunks_kernel, dim3(grid_for(nl2)), dim3(256), 0, h->stream, ls2, nl2, h->work_counter.get<unsigned int>());
 			unsigned int longest = 0;
-			HIPCHK(h, hipMemcpyAsync(&longest, h->work_counter, 4, hipMemcpyDeviceToHost, h->stream));
+			HIPCHK(h, hipMemcpyAsync(&longest, h->work_counter.get<unsigned int>(), 4, hipMemcpyDeviceToHost, h->stream));
 			HIPCHK(h, hipStreamSynchronize(h->stream));
 			rc = zero_work_counter(h); if (rc) return rc;
 			if (longest > COUNT_NARROW_CHUNKS) {
 				auto kern = count_kernel<W, EXT, COUNT_LOG2S>;
 				const size_t smem = count_smem_bytes<W, EXT, COUNT_LOG2S>();
 				HIPCHK(h, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-				hipLaunchKernelGGL(kern, dim3(std::min(grid, part_grid(h))), dim3(COUNT_THREADS), smem, h->stream, pool_view(h, h->l1), ls2, lc2, nl2, out, f, h->work_counter, 2);
+				hipLaunchKernelGGL(kern, dim3(std::min(grid, part_grid(h))), dim3(COUNT_THREADS), smem, h->stream, pool_view(h, h->l1), ls2, lc2, nl2, out, f, h->work_counter.get<unsigned int>(), 2);
 			}
 		} else {
 			auto kern = count_kernel<W, EXT, COUNT_LOG2S>;
 			const size_t smem = count_smem_bytes<W, EXT, COUNT_LOG2S>();
 			HIPCHK(h, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-			hipLaunchKernelGGL(kern, dim3(grid), dim3(COUNT_THREADS), smem, h->stream, pool_view(h, h->l1), ls2, lc2, nl2, out, f, h->work_counter, 0);
+			hipLaunchKernelGGL(kern, dim3(grid), dim3(COUNT_THREADS), smem, h->stream, pool_view(h, h->l1), ls2, lc2, nl2, out, f, h->work_counter.get<unsigned int>(), 0);
 		}
 		HIPCHK(h, hipGetLastError());
 	}
 	uint32_t cerr = 0;
 	HIPCHK(h, hipMemcpyAsync(&c, fc, sizeof(c), hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipMemcpyAsync(cur, cursors, 16, hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(h, hipMemcpyAsync(&cerr, h->derr, 4, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipMemcpyAsync(&cerr, h->derr.get<uint32_t>(), 4, hipMemcpyDeviceToHost, h->stream));
 	HIPCHK(h, hipStreamSynchronize(h->stream));
 	if (!(cerr & ERR_ENTRIES_FULL) || (wcap >= wmax && scap >= smax) || attempt >= 8) break;
 	/* more kept entries than the probe promised: larger buffers, same pass again */
 	cerr &= ~(uint32_t)ERR_ENTRIES_FULL;
-	HIPCHK(h, hipMemcpy(h->derr, &cerr, 4, hipMemcpyHostToDevice));
+	HIPCHK(h, hipMemcpy(h->derr.get<uint32_t>(), &cerr, 4, hipMemcpyHostToDevice));
 	wcap = std::min<uint64_t>(wmax, wcap * 2); if (keepSing) scap = std::min<uint64_t>(smax, scap * 2);
 	if (dbg()) fprintf(stderr, "count pass: entry buffers too small, retrying with %llu / %llu\n", (unsigned long long)wcap, (unsigned long long)scap);
 	}
@@ -1274,7 +1279,7 @@ template <int W, bool EXT> int finalize_partition_t(kmr_handle *h, uint32_t min_
 	{	/* still full with the buffers at their bounds (or after the last retry): the cursors point past the buffers, nothing
 		 * downstream may use them */
 		uint32_t cerr2 = 0;
-		HIPCHK(h, hipMemcpy(&cerr2, h->derr, 4, hipMemcpyDeviceToHost));
+		HIPCHK(h, hipMemcpy(&cerr2, h->derr.get<uint32_t>(), 4, hipMemcpyDeviceToHost));
 		if (cerr2 & ERR_ENTRIES_FULL) { time_end(h, 1, ea, eb); return fail(h, KMR_ERR_CAPACITY, "entry buffers of the count pass overflowed at their upper bound (internal sizing error)"); }
 	}
 
@@ -1315,25 +1320,20 @@ template <int W> int binned_buckets_t(kmr_handle *h, uint64_t wslots, uint64_t w
 	rc = arena_get(h, &dmax, 1); if (rc) return rc;
 	if (bits2) { rc = arena_get(h, &hist2, groups); if (rc) return rc; rc = arena_get(h, &pad1, bins1); if (rc) return rc; rc = arena_get(h, &gstart, groups + 1); if (rc) return rc; }
 	HIPCHK(h, hipMemsetAsync(hist1, 0, 4 * bins1, h->stream)); HIPCHK(h, hipMemsetAsync(dmax, 0, 4, h->stream));
-	BbInput in1; in1.entries = h->ue; in1.seg_start = nullptr; in1.seg_count = nullptr; in1.n_seg = 1; in1.n_slots = wslots; in1.holes = 1;
+	BbInput in1; in1.entries = h->ue.get<uint64_t>(); in1.seg_start = nullptr; in1.seg_count = nullptr; in1.n_seg = 1; in1.n_slots = wslots; in1.holes = 1;
 	auto hist_grid = [&](uint64_t n_slots, uint32_t &tpb) { const uint64_t tiles = (n_slots + BB_TILE - 1) / BB_TILE; tpb = (uint32_t)std::max<uint64_t>(1, (tiles + 2047) / 2048); return (unsigned)((tiles + tpb - 1) / tpb); };
 	auto scatter_grid = [&](uint64_t n_slots) { const uint64_t tiles = (n_slots + BB_TILE - 1) / BB_TILE; return (unsigned)std::min<uint64_t>(tiles, (uint64_t)num_cus(h) * 8); };
-	auto scratch = [&](uint64_t entries) -> int {      /* h->ue2: the other side of the partition's ping-pong */
-		if (h->ue2 && h->ue2_cap >= entries) return 0;
-		if (h->ue2) hipFree(h->ue2); h->ue2 = nullptr; h->ue2_cap = 0;
-		HIPCHK(h, dev_malloc((void **)&h->ue2, 8ull * (W + 1) * entries)); h->ue2_cap = entries;
-		return 0;
-	};
+	auto scratch = [&](uint64_t entries) { return h->ue2.reserve(h, "ue2", 8ull * (W + 1) * entries); };      /* h->ue2: the other side of the partition's ping-pong */
 	auto group_launch = [&](const uint64_t *entries, const uint64_t *gs, const uint32_t *gc) -> int {
-		int rc2 = reserve_bytes(h, (void **)&wm.keys, wm.c_keys, 8ull * W * wn); if (rc2) return rc2;
-		rc2 = reserve_bytes(h, (void **)&wm.vals, wm.c_vals, 12ull * wn); if (rc2) return rc2;
+		int rc2 = wm.keys.reserve(h, "weak map keys", std::max<uint64_t>(8ull * W * wn, 8)); if (rc2) return rc2;
+		rc2 = wm.vals.reserve(h, "weak map vals", std::max<uint64_t>(12ull * wn, 8)); if (rc2) return rc2;
 		auto gk = bb_group_kernel<W>;
 		HIPCHK(h, hipFuncSetAttribute((const void *)gk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bb_group_smem_bytes<W>()));
 		/* the blocks stride over the groups: as many of them as fit the chip at once, so that they all get the same number of groups */
 		int per_cu = 0;
 		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)gk, BB_GROUP_THREADS, bb_group_smem_bytes<W>()) != hipSuccess || per_cu < 1) per_cu = 4;
 		if (dbg()) fprintf(stderr, "bb_group<W=%d>: %d blocks per CU, %llu groups\n", W, per_cu, (unsigned long long)groups);
-		hipLaunchKernelGGL(gk, dim3((unsigned)std::min<uint64_t>(groups, (uint64_t)num_cus(h) * per_cu)), dim3(BB_GROUP_THREADS), bb_group_smem_bytes<W>(), h->stream, entries, wm.keys, wm.vals, gs, gc, groups, g, h->hkb, nb, wm.start, wn, h->derr);
+		hipLaunchKernelGGL(gk, dim3((unsigned)std::min<uint64_t>(groups, (uint64_t)num_cus(h) * per_cu)), dim3(BB_GROUP_THREADS), bb_group_smem_bytes<W>(), h->stream, entries, wm.keys.get<uint64_t>(), wm.vals.get<uint32_t>(), gs, gc, groups, g, h->hkb, nb, wm.start.get<uint64_t>(), wn, h->derr.get<uint32_t>());
 		HIPCHK(h, hipGetLastError());
 		return 0;
 	};
@@ -1349,8 +1349,8 @@ template <int W> int binned_buckets_t(kmr_handle *h, uint64_t wslots, uint64_t w
 		if (mx > bb_group_cap<W>()) return 0;
 		rc = scratch(wn); if (rc) return rc;
 		hipLaunchKernelGGL(bb_cursor_init_kernel, dim3(grid_for(bins1)), dim3(256), 0, h->stream, (const uint64_t *)start1, bins1, cursor);
-		hipLaunchKernelGGL(bb_scatter_kernel<W>, dim3(scatter_grid(wslots)), dim3(BB_THREADS), 0, h->stream, in1, shift1, bits1, h->hkb, nb, cursor, h->ue2);
-		rc = group_launch(h->ue2, start1, hist1); if (rc) return rc;
+		hipLaunchKernelGGL(bb_scatter_kernel<W>, dim3(scatter_grid(wslots)), dim3(BB_THREADS), 0, h->stream, in1, shift1, bits1, h->hkb, nb, cursor, h->ue2.get<uint64_t>());
+		rc = group_launch(h->ue2.get<uint64_t>(), start1, hist1); if (rc) return rc;
 		done = true;
 		return 0;
 	}
@@ -1361,8 +1361,8 @@ template <int W> int binned_buckets_t(kmr_handle *h, uint64_t wslots, uint64_t w
 	HIPCHK(h, hipMemcpy(&padded_total, start1 + bins1, 8, hipMemcpyDeviceToHost));
 	rc = scratch(std::max(padded_total, wn)); if (rc) return rc;
 	hipLaunchKernelGGL(bb_cursor_init_kernel, dim3(grid_for(bins1)), dim3(256), 0, h->stream, (const uint64_t *)start1, bins1, cursor);
-	hipLaunchKernelGGL(bb_scatter_kernel<W>, dim3(scatter_grid(wslots)), dim3(BB_THREADS), 0, h->stream, in1, shift1, bits1, h->hkb, nb, cursor, h->ue2);
-	BbInput in2; in2.entries = h->ue2; in2.seg_start = start1; in2.seg_count = hist1; in2.n_seg = (uint32_t)bins1; in2.n_slots = padded_total; in2.holes = 0;
+	hipLaunchKernelGGL(bb_scatter_kernel<W>, dim3(scatter_grid(wslots)), dim3(BB_THREADS), 0, h->stream, in1, shift1, bits1, h->hkb, nb, cursor, h->ue2.get<uint64_t>());
+	BbInput in2; in2.entries = h->ue2.get<uint64_t>(); in2.seg_start = start1; in2.seg_count = hist1; in2.n_seg = (uint32_t)bins1; in2.n_slots = padded_total; in2.holes = 0;
 	const uint32_t shift2 = g;
 	HIPCHK(h, hipMemsetAsync(hist2, 0, 4 * groups, h->stream)); HIPCHK(h, hipMemsetAsync(dmax, 0, 4, h->stream));
 	grid = hist_grid(padded_total, tpb);
@@ -1372,10 +1372,10 @@ template <int W> int binned_buckets_t(kmr_handle *h, uint64_t wslots, uint64_t w
 	rc = exclusive_scan(h, hist2, groups, gstart); if (rc) return rc;
 	/* the packed entries the count pass wrote are about to be overwritten (the second level writes where the first one read): a
 	 * group too large for the LDS arrays sends the build down the other path BEFORE that */
-	if (mx > bb_group_cap<W>() || h->ue_cap < wn) return 0;
+	if (mx > bb_group_cap<W>() || packed_entries(h, h->ue) < wn) return 0;
 	hipLaunchKernelGGL(bb_cursor_init_kernel, dim3(grid_for(groups)), dim3(256), 0, h->stream, (const uint64_t *)gstart, groups, cursor);
-	hipLaunchKernelGGL(bb_scatter_kernel<W>, dim3(scatter_grid(padded_total)), dim3(BB_THREADS), 0, h->stream, in2, shift2, bits2, h->hkb, nb, cursor, h->ue);
-	rc = group_launch(h->ue, gstart, hist2); if (rc) return rc;
+	hipLaunchKernelGGL(bb_scatter_kernel<W>, dim3(scatter_grid(padded_total)), dim3(BB_THREADS), 0, h->stream, in2, shift2, bits2, h->hkb, nb, cursor, h->ue.get<uint64_t>());
+	rc = group_launch(h->ue.get<uint64_t>(), gstart, hist2); if (rc) return rc;
 	done = true;
 	return 0;
 }
@@ -1388,55 +1388,55 @@ template <int W> int finish_maps_t(kmr_handle *h, uint32_t *wc, uint32_t *sc, ui
 	clear_map(wm); clear_map(sm);          /* the buffers of the previous build are reused when they are large enough */
 	wm.nb = h->nb_weak; wm.n = wn; wm.present = true;
 	sm.nb = h->nb_sing; sm.n = keepSing ? sn : 0; sm.present = keepSing;
-	int rc = reserve_bytes(h, (void **)&wm.start, wm.c_start, 8 * (wm.nb + 1)); if (rc) return rc;
-	rc = reserve_bytes(h, (void **)&sm.start, sm.c_start, 8 * (sm.nb + 1)); if (rc) return rc;
+	int rc = wm.start.reserve(h, "weak map start", 8 * (wm.nb + 1)); if (rc) return rc;
+	rc = sm.start.reserve(h, "singleton map start", 8 * (sm.nb + 1)); if (rc) return rc;
 	bool weakDone = false;
 	if (weak_uncounted) {
 		rc = binned_buckets_t<W>(h, wslots, wn, weakDone); if (rc) return rc;
 		if (!weakDone) {      /* the other path wants keys and values apart and a count per bucket */
-			if (!h->uw_keys || h->uw_cap < wslots) {
-				if (h->uw_keys) hipFree(h->uw_keys); if (h->uw_vals) hipFree(h->uw_vals); h->uw_keys = h->uw_vals = nullptr; h->uw_cap = 0;
+			if (key_entries(h, h->uw_keys) < wslots || !h->uw_vals) {
+				h->uw_keys.reset(); h->uw_vals.reset();
 				const uint64_t cap = std::max<uint64_t>(wslots, 16);
-				HIPCHK(h, dev_malloc(&h->uw_keys, 8ull * W * cap)); HIPCHK(h, dev_malloc(&h->uw_vals, 12ull * cap)); h->uw_cap = cap;
+				HIPCHK(h, h->uw_keys.alloc(8ull * W * cap)); HIPCHK(h, h->uw_vals.alloc(12ull * cap));
 			}
 			HIPCHK(h, hipMemsetAsync(wc, 0, 4 * wm.nb, h->stream));
-			if (wslots) hipLaunchKernelGGL(bb_unpack_kernel<W>, dim3(grid_for(wslots)), dim3(256), 0, h->stream, (const uint64_t *)h->ue, wslots, h->hkb, wm.nb, (uint64_t *)h->uw_keys, (uint32_t *)h->uw_vals, wc);
+			if (wslots) hipLaunchKernelGGL(bb_unpack_kernel<W>, dim3(grid_for(wslots)), dim3(256), 0, h->stream, (const uint64_t *)h->ue.get<uint64_t>(), wslots, h->hkb, wm.nb, (uint64_t *)h->uw_keys.get(), (uint32_t *)h->uw_vals.get(), wc);
 			HIPCHK(h, hipGetLastError());
 		}
 	}
-	if (!weakDone) { rc = exclusive_scan(h, wc, wm.nb, wm.start); if (rc) return rc; }
-	if (keepSing) { rc = exclusive_scan(h, sc, sm.nb, sm.start); if (rc) return rc; }
-	else HIPCHK(h, hipMemsetAsync(sm.start, 0, 8 * (sm.nb + 1), h->stream));      /* no singleton map is kept: every bucket starts (and ends) at 0 */
+	if (!weakDone) { rc = exclusive_scan(h, wc, wm.nb, wm.start.get<uint64_t>()); if (rc) return rc; }
+	if (keepSing) { rc = exclusive_scan(h, sc, sm.nb, sm.start.get<uint64_t>()); if (rc) return rc; }
+	else HIPCHK(h, hipMemsetAsync(sm.start.get<uint64_t>(), 0, 8 * (sm.nb + 1), h->stream));      /* no singleton map is kept: every bucket starts (and ends) at 0 */
 	if (!weakDone) {
-		rc = reserve_bytes(h, (void **)&wm.keys, wm.c_keys, 8ull * W * wm.n); if (rc) return rc;
-		rc = reserve_bytes(h, (void **)&wm.vals, wm.c_vals, 4ull * vw * wm.n); if (rc) return rc;
+		rc = wm.keys.reserve(h, "weak map keys", std::max<uint64_t>(8ull * W * wm.n, 8)); if (rc) return rc;
+		rc = wm.vals.reserve(h, "weak map vals", std::max<uint64_t>(4ull * vw * wm.n, 8)); if (rc) return rc;
 	}
-	rc = reserve_bytes(h, (void **)&sm.keys, sm.c_keys, 8ull * W * sm.n); if (rc) return rc;
-	rc = reserve_bytes(h, (void **)&sm.sweight, sm.c_sw, sm.n); if (rc) return rc;
-	if (h->ext) { rc = reserve_bytes(h, (void **)&sm.spkt, sm.c_pkt, 4 * sm.n); if (rc) return rc; }
+	rc = sm.keys.reserve(h, "singleton map keys", std::max<uint64_t>(8ull * W * sm.n, 8)); if (rc) return rc;
+	rc = sm.sweight.reserve(h, "singleton map sweight", std::max<uint64_t>(sm.n, 8)); if (rc) return rc;
+	if (h->ext) { rc = sm.spkt.reserve(h, "singleton map spkt", std::max<uint64_t>(4 * sm.n, 8)); if (rc) return rc; }
 	HIPCHK(h, hipMemsetAsync(wc, 0, 4 * wm.nb, h->stream)); HIPCHK(h, hipMemsetAsync(sc, 0, 4 * sm.nb, h->stream));
 	if (weakDone) { /* keys, values and bucket starts are in place */ }
-	else if (wm.n && vw > 4) hipLaunchKernelGGL((entry_scatter_kernel<W, true>), dim3(grid_for(wslots)), dim3(256), 0, h->stream, (const uint64_t *)h->uw_keys, (const uint32_t *)h->uw_vals,
-	                            (const uint8_t *)nullptr, (const uint32_t *)nullptr, wslots, vw, h->hkb, wm.nb, wm.start, wc, wm.keys, wm.vals, (uint8_t *)nullptr, (uint32_t *)nullptr);
+	else if (wm.n && vw > 4) hipLaunchKernelGGL((entry_scatter_kernel<W, true>), dim3(grid_for(wslots)), dim3(256), 0, h->stream, (const uint64_t *)h->uw_keys.get(), (const uint32_t *)h->uw_vals.get(),
+	                            (const uint8_t *)nullptr, (const uint32_t *)nullptr, wslots, vw, h->hkb, wm.nb, wm.start.get<uint64_t>(), wc, wm.keys.get<uint64_t>(), wm.vals.get<uint32_t>(), (uint8_t *)nullptr, (uint32_t *)nullptr);
 	else if (wm.n) {
 		/* lists cut by minimizer (build_mode 3) scatter their entries over unrelated buckets: 64-bit cursors that start at the buckets'
 		 * first entries, one returning add per entry */
 		unsigned long long *cur64 = nullptr;
-		if (h->superkmer_mode && arena_get(h, &cur64, wm.nb) == 0) HIPCHK(h, hipMemcpyAsync(cur64, wm.start, 8 * wm.nb, hipMemcpyDeviceToDevice, h->stream));
+		if (h->superkmer_mode && arena_get(h, &cur64, wm.nb) == 0) HIPCHK(h, hipMemcpyAsync(cur64, wm.start.get<uint64_t>(), 8 * wm.nb, hipMemcpyDeviceToDevice, h->stream));
 		else cur64 = nullptr;
-		hipLaunchKernelGGL(entry_scatter_kernel<W>, dim3(grid_for(wslots)), dim3(256), 0, h->stream, (const uint64_t *)h->uw_keys, (const uint32_t *)h->uw_vals,
-		                            (const uint8_t *)nullptr, (const uint32_t *)nullptr, wslots, vw, h->hkb, wm.nb, wm.start, wc, wm.keys, wm.vals, (uint8_t *)nullptr, (uint32_t *)nullptr, cur64, 6);
+		hipLaunchKernelGGL(entry_scatter_kernel<W>, dim3(grid_for(wslots)), dim3(256), 0, h->stream, (const uint64_t *)h->uw_keys.get(), (const uint32_t *)h->uw_vals.get(),
+		                            (const uint8_t *)nullptr, (const uint32_t *)nullptr, wslots, vw, h->hkb, wm.nb, wm.start.get<uint64_t>(), wc, wm.keys.get<uint64_t>(), wm.vals.get<uint32_t>(), (uint8_t *)nullptr, (uint32_t *)nullptr, cur64, 6);
 	}
-	if (sm.n) hipLaunchKernelGGL(entry_scatter_kernel<W>, dim3(grid_for(sslots)), dim3(256), 0, h->stream, (const uint64_t *)h->us_keys, (const uint32_t *)nullptr,
-	                            (const uint8_t *)h->us_b8, (const uint32_t *)h->us_pkt, sslots, 0u, h->hkb, sm.nb, sm.start, sc, sm.keys, (uint32_t *)nullptr, sm.sweight, h->ext ? sm.spkt : (uint32_t *)nullptr);
+	if (sm.n) hipLaunchKernelGGL(entry_scatter_kernel<W>, dim3(grid_for(sslots)), dim3(256), 0, h->stream, (const uint64_t *)h->us_keys.get(), (const uint32_t *)nullptr,
+	                            (const uint8_t *)h->us_b8.get(), (const uint32_t *)h->us_pkt.get(), sslots, 0u, h->hkb, sm.nb, sm.start.get<uint64_t>(), sc, sm.keys.get<uint64_t>(), (uint32_t *)nullptr, sm.sweight.get<uint8_t>(), h->ext ? sm.spkt.get<uint32_t>() : (uint32_t *)nullptr);
 	HIPCHK(h, hipGetLastError());
-	SortView<W> sv; sv.keys = wm.keys; sv.vals = wm.vals; sv.b8 = nullptr; sv.pkt = nullptr; sv.vw = vw;
+	SortView<W> sv; sv.keys = wm.keys.get<uint64_t>(); sv.vals = wm.vals.get<uint32_t>(); sv.b8 = nullptr; sv.pkt = nullptr; sv.vw = vw;
 	if (weakDone) { /* sorted by bb_group_kernel */ }
-	else if (h->ext) hipLaunchKernelGGL((sort_buckets_kernel<W, 15>), dim3(grid_for(wm.nb, 4, 1 << 20)), dim3(256), 0, h->stream, sv, wm.start, wm.nb);
-	else hipLaunchKernelGGL((sort_buckets_kernel<W, 3>), dim3(grid_for(wm.nb, 4, 1 << 20)), dim3(256), 0, h->stream, sv, wm.start, wm.nb);
+	else if (h->ext) hipLaunchKernelGGL((sort_buckets_kernel<W, 15>), dim3(grid_for(wm.nb, 4, 1 << 20)), dim3(256), 0, h->stream, sv, wm.start.get<uint64_t>(), wm.nb);
+	else hipLaunchKernelGGL((sort_buckets_kernel<W, 3>), dim3(grid_for(wm.nb, 4, 1 << 20)), dim3(256), 0, h->stream, sv, wm.start.get<uint64_t>(), wm.nb);
 	if (sm.n) {
-		SortView<W> ss; ss.keys = sm.keys; ss.vals = nullptr; ss.b8 = sm.sweight; ss.pkt = h->ext ? sm.spkt : nullptr; ss.vw = 0;
-		hipLaunchKernelGGL((sort_buckets_kernel<W, 0>), dim3(grid_for(sm.nb, 4, 1 << 20)), dim3(256), 0, h->stream, ss, sm.start, sm.nb);
+		SortView<W> ss; ss.keys = sm.keys.get<uint64_t>(); ss.vals = nullptr; ss.b8 = sm.sweight.get<uint8_t>(); ss.pkt = h->ext ? sm.spkt.get<uint32_t>() : nullptr; ss.vw = 0;
+		hipLaunchKernelGGL((sort_buckets_kernel<W, 0>), dim3(grid_for(sm.nb, 4, 1 << 20)), dim3(256), 0, h->stream, ss, sm.start.get<uint64_t>(), sm.nb);
 	}
 	HIPCHK(h, hipGetLastError());
 	HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1455,7 +1455,7 @@ template <int W, bool EXT> int insert_records_partition_t(kmr_handle *h, const v
 	if (!h->l1.head) choose_bits1(h, n);
 	hipEvent_t a, b; time_begin(h, 0, &a, &b);
 	/* received segments contain holes (weight 0): the device counts the real records into stats.raw/good */
-	int rc = partition_level1<W, EXT>(h, recs, nullptr, nullptr, (n + 8191) / 8192, 0, 8192, n, n, &h->dstats->inserted,
+	int rc = partition_level1<W, EXT>(h, recs, nullptr, nullptr, (n + 8191) / 8192, 0, 8192, n, n, &h->dstats.get<DevStats>()->inserted,
 	                             2 * W + (h->ext ? 2 : 1), h->stream_base);
 	time_end(h, 0, a, b);
 	return rc;
@@ -1533,13 +1533,13 @@ int sk_uniform_weight(kmr_handle *h, const ReadsView &rv, bool &lean, float &wK)
 		lean = true; wK = (float)h->hPk[q0];
 		return 0;
 	}
-	if (!h->qrange) HIPCHK(h, dev_malloc((void **)&h->qrange, 8));
+	{ int rc = h->qrange.reserve(h, "qrange", 8); if (rc) return rc; }
 	const unsigned int init[2] = {255u, 0u};
-	HIPCHK(h, hipMemcpyAsync(h->qrange, init, 8, hipMemcpyHostToDevice, h->stream));
-	hipLaunchKernelGGL(sk_qual_range_kernel, dim3(num_cus(h) * 8), dim3(256), 0, h->stream, rv.quals, rv.offsets, rv.n_reads, h->qrange);
+	HIPCHK(h, hipMemcpyAsync(h->qrange.get<unsigned int>(), init, 8, hipMemcpyHostToDevice, h->stream));
+	hipLaunchKernelGGL(sk_qual_range_kernel, dim3(num_cus(h) * 8), dim3(256), 0, h->stream, rv.quals, rv.offsets, rv.n_reads, h->qrange.get<unsigned int>());
 	HIPCHK(h, hipGetLastError());
 	unsigned int got[2] = {0, 0};
-	HIPCHK(h, hipMemcpyAsync(got, h->qrange, 8, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipMemcpyAsync(got, h->qrange.get<unsigned int>(), 8, hipMemcpyDeviceToHost, h->stream));
 	HIPCHK(h, hipStreamSynchronize(h->stream));
 	if (got[0] != got[1]) { h->qual_mixed = got[0] < got[1]; return 0; }      /* (255 > 0: no quality byte at all) */
 	const unsigned int q0 = got[0];
@@ -1555,7 +1555,7 @@ uint32_t sk_dbg_flags(const char *name) {
 	(void)name; return 0u;
 #endif
 }
-SkParams sk_params(kmr_handle *h) { SkParams sp; sp.dbg = sk_dbg_flags("KMR_SK_EXTRACT_DBG"); sp.keep_all_owners = h->sk_exchange ? 1u : 0u; sp.track = nullptr; sp.m = h->sk_m; sp.off = h->sk_off; sp.list_bits = h->sk_bits; sp.state = h->sk_state; sp.Pk = h->dPk; sp.Rp = h->dPk + 256; sp.fast_div = h->sk_fast_div ? 1u : 0u; return sp; }
+SkParams sk_params(kmr_handle *h) { SkParams sp; sp.dbg = sk_dbg_flags("KMR_SK_EXTRACT_DBG"); sp.keep_all_owners = h->sk_exchange ? 1u : 0u; sp.track = nullptr; sp.m = h->sk_m; sp.off = h->sk_off; sp.list_bits = h->sk_bits; sp.state = h->sk_state.get<unsigned long long>(); sp.Pk = h->dPk.get<double>(); sp.Rp = h->dPk.get<double>() + 256; sp.fast_div = h->sk_fast_div ? 1u : 0u; return sp; }
 template <int W> int add_reads_superkmer_t(kmr_handle *h, const ReadsView &rvAll, uint64_t total_bases) {
 	const uint64_t n = rvAll.n_reads;
 	const DevParams dp = dev_params(h);
@@ -1607,8 +1607,8 @@ template <int W> int add_reads_superkmer_t(kmr_handle *h, const ReadsView &rvAll
 			if (nlists > 64 && (nlists < (1ull << bits) || h->tune.list_aim) && nlists < (1ull << 31)) h->sk_bits = (uint32_t)nlists;
 		}
 		const uint64_t nl0 = sk_list_count(h->sk_bits);
-		HIPCHK(h, dev_malloc((void **)&h->sk_state, 8 * nl0));
-		hipLaunchKernelGGL(sk_state_init_kernel, dim3(grid_for(nl0)), dim3(256), 0, h->stream, h->sk_state, nl0);
+		HIPCHK(h, h->sk_state.alloc(8 * nl0));
+		hipLaunchKernelGGL(sk_state_init_kernel, dim3(grid_for(nl0)), dim3(256), 0, h->stream, h->sk_state.get<unsigned long long>(), nl0);
 		HIPCHK(h, hipGetLastError());
 	}
 	const uint64_t avg = n ? std::max<uint64_t>(1, total_bases / n) : 1;
@@ -1616,11 +1616,8 @@ template <int W> int add_reads_superkmer_t(kmr_handle *h, const ReadsView &rvAll
 	const uint64_t chunk = std::max<uint64_t>(64, (sub_bases / avg) & ~63ull);
 	if (h->cfg.size_tracker && n) {      /* per-read records of this call (raw and good k-mers, end ordinal) */
 		h->trk_n = 0;
-		if (n > h->trk_cap) {
-			if (h->trk) { HIPCHK(h, hipStreamSynchronize(h->stream)); hipFree(h->trk); h->trk = nullptr; h->trk_cap = 0; }
-			HIPCHK(h, dev_malloc((void **)&h->trk, n * sizeof(SkTrackRec))); h->trk_cap = n;
-		}
-		HIPCHK(h, hipMemsetAsync(h->trk, 0, n * sizeof(SkTrackRec), h->stream));
+		{ int rc = h->trk.reserve(h, "trk", n * sizeof(SkTrackRec)); if (rc) return rc; }
+		HIPCHK(h, hipMemsetAsync(h->trk.get<SkTrackRec>(), 0, n * sizeof(SkTrackRec), h->stream));
 	}
 	for (uint64_t r = 0; r < n; r += chunk) {
 		const uint64_t m = std::min(chunk, n - r);
@@ -1650,7 +1647,7 @@ template <int W> int add_reads_superkmer_t(kmr_handle *h, const ReadsView &rvAll
 		rc = pool_reserve(h, h->l1, (h->ext ? 2 : 1) * bases / SK_CHUNK_G + ((h->l1.base && !h->sk_exchange) ? 0 : sk_list_count(h->sk_bits)) + (uint64_t)num_cus(h) * SK_EXTRACT_WAVES_PER_CU * 130 + 64, true); if (rc) return rc;
 		hipEvent_t a, b, a2, b2; time_begin(h, KMR_TIME_BUILD, &a, &b); time_begin(h, KMR_TIME_EXTRACT, &a2, &b2);
 		SkParams sp = sk_params(h);
-		if (h->cfg.size_tracker) sp.track = h->trk + r;
+		if (h->cfg.size_tracker) sp.track = h->trk.get<SkTrackRec>() + r;
 #define SKX(WINv) (h->ext ? (filt ? launch_sk_extract<W, WINv, true, true>(h, rv, sp) : launch_sk_extract<W, WINv, false, true>(h, rv, sp)) : \
                    (filt ? launch_sk_extract<W, WINv, true>(h, rv, sp) : (lean ? launch_sk_extract_lean<W, WINv>(h, rv, sp, wK) : launch_sk_extract<W, WINv, false>(h, rv, sp))))
 		if (h->packed_direct) {
@@ -1667,7 +1664,7 @@ template <int W> int add_reads_superkmer_t(kmr_handle *h, const ReadsView &rvAll
 		/* SizeTracker::track (src/KmerSpectrum.h:879-894) is called before every k-mer: the thresholds this call's reads pass, each at
 		 * the t-th raw k-mer of some read; the walk of those reads (sk_track_boundary_kernel) gives the ordinal and the good k-mers */
 		std::vector<SkTrackRec> recs(n);
-		HIPCHK(h, hipMemcpyAsync(recs.data(), h->trk, n * sizeof(SkTrackRec), hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, hipMemcpyAsync(recs.data(), h->trk.get<SkTrackRec>(), n * sizeof(SkTrackRec), hipMemcpyDeviceToHost, h->stream));
 		HIPCHK(h, hipStreamSynchronize(h->stream));
 		std::vector<SkBoundary> bd; std::vector<uint64_t> good_before;
 		const bool walkable = (dp.sub_wnb | dp.sub_snb) == 0;      /* (a subtracting reference decides per k-mer what is raw: read ends there) */
@@ -1685,8 +1682,8 @@ template <int W> int add_reads_superkmer_t(kmr_handle *h, const ReadsView &rvAll
 		}
 		if (h->trk_bounds.size() + bd.size() > SK_TRACK_MAX) return fail(h, KMR_ERR_UNSUPPORTED, "size tracker: more than 512 elements");
 		if (!bd.empty() && walkable) {
-			SkBoundary *dbd = nullptr;
-			HIPCHK(h, dev_malloc((void **)&dbd, bd.size() * sizeof(SkBoundary)));
+			DevBuf dbdb; HIPCHK(h, dbdb.alloc(bd.size() * sizeof(SkBoundary)));
+			SkBoundary *dbd = dbdb.get<SkBoundary>();
 			hipError_t e = hipMemcpyAsync(dbd, bd.data(), bd.size() * sizeof(SkBoundary), hipMemcpyHostToDevice, h->stream);
 			if (e == hipSuccess) {
 				ReadsView rv = rvAll; rv.u_start = rv.u_end = rv.u_read = nullptr; rv.n_units = 0;
@@ -1695,7 +1692,6 @@ template <int W> int add_reads_superkmer_t(kmr_handle *h, const ReadsView &rvAll
 			}
 			if (e == hipSuccess) e = hipMemcpyAsync(bd.data(), dbd, bd.size() * sizeof(SkBoundary), hipMemcpyDeviceToHost, h->stream);
 			if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-			hipFree(dbd);
 			if (e != hipSuccess) return fail(h, KMR_ERR_HIP, std::string("size tracker boundaries: ") + hipGetErrorString(e));
 		}
 		for (size_t i = 0; i < bd.size(); i++) { h->trk_bounds.push_back(bd[i].ordinal); h->trk_snap_good.push_back(good_before[i] + bd[i].good); }
@@ -1714,26 +1710,25 @@ template <int W> int saturated_fix_t(kmr_handle *h, const uint64_t *ls, const ui
 	if (!n_clamped || !wm.n) return 0;
 	uint32_t list_bits = 0; while ((1ull << list_bits) < nl) list_bits++;
 	if ((1ull << list_bits) != nl) list_bits = (uint32_t)nl;      /* a list count that is not a power of two is its own code (sk_list_of) */
-	unsigned long long *dfound = nullptr; uint64_t *d_entry = nullptr; uint32_t *d_list = nullptr;
-	std::vector<void *> owned;
-	auto release = [&]() { for (void *p : owned) hipFree(p); owned.clear(); };
-#define SATCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { release(); h->err = std::string(#call) + ": " + hip_err_text(e_); return e_ == hipErrorOutOfMemory ? KMR_ERR_OOM : KMR_ERR_HIP; } } while (0)
-	auto dalloc = [&](void **p, size_t bytes) -> hipError_t { hipError_t e = dev_malloc(p, std::max<size_t>(bytes, 256)); if (e == hipSuccess) owned.push_back(*p); return e; };
-	SATCHK(dalloc((void **)&dfound, 8));
+	DevBuf bfound, bentry, blist, bc0, bc1, bitems, bk_in, bk_out, bv_in, bv_out, btmp;      /* scratch of this call */
+	auto dalloc = [](DevBuf &b, size_t bytes) { return b.alloc(std::max<size_t>(bytes, 256)); };
+	HIPCHK(h, dalloc(bfound, 8));
+	unsigned long long *dfound = bfound.get<unsigned long long>(); uint64_t *d_entry = nullptr; uint32_t *d_list = nullptr;
 	uint64_t cap = std::min<uint64_t>(wm.n, 4 * n_clamped + 1024);
 	unsigned long long found = 0;
 	for (;;) {
-		SATCHK(dalloc((void **)&d_entry, 8 * cap)); SATCHK(dalloc((void **)&d_list, 4 * cap));
-		SATCHK(hipMemsetAsync(dfound, 0, 8, h->stream));
-		hipLaunchKernelGGL(sat_find_kernel<W>, dim3(grid_for(wm.n)), dim3(256), 0, h->stream, (const uint64_t *)wm.keys, (const uint32_t *)wm.vals, wm.n, h->sk_m, h->sk_off, h->sk_win, list_bits, dfound, cap, d_entry, d_list, h->ext ? 15u : 3u);
-		SATCHK(hipGetLastError());
-		SATCHK(hipMemcpyAsync(&found, dfound, 8, hipMemcpyDeviceToHost, h->stream)); SATCHK(hipStreamSynchronize(h->stream));
+		HIPCHK(h, dalloc(bentry, 8 * cap)); HIPCHK(h, dalloc(blist, 4 * cap));
+		d_entry = bentry.get<uint64_t>(); d_list = blist.get<uint32_t>();
+		HIPCHK(h, hipMemsetAsync(dfound, 0, 8, h->stream));
+		hipLaunchKernelGGL(sat_find_kernel<W>, dim3(grid_for(wm.n)), dim3(256), 0, h->stream, (const uint64_t *)wm.keys.get<uint64_t>(), (const uint32_t *)wm.vals.get<uint32_t>(), wm.n, h->sk_m, h->sk_off, h->sk_win, list_bits, dfound, cap, d_entry, d_list, h->ext ? 15u : 3u);
+		HIPCHK(h, hipGetLastError());
+		HIPCHK(h, hipMemcpyAsync(&found, dfound, 8, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
 		if (found <= cap) break;
 		cap = found;      /* more entries at exactly 65 535 than expected: again with room for all */
 	}
-	if (found >= (1ull << 23)) { release(); return 0; }      /* (more than 8 x 10^6 saturated keys: left as the count pass made them) */
+	if (found >= (1ull << 23)) return 0;      /* (more than 8 x 10^6 saturated keys: left as the count pass made them) */
 	std::vector<uint64_t> entry(found); std::vector<uint32_t> lst(found);
-	SATCHK(hipMemcpy(entry.data(), d_entry, 8 * found, hipMemcpyDeviceToHost)); SATCHK(hipMemcpy(lst.data(), d_list, 4 * found, hipMemcpyDeviceToHost));
+	HIPCHK(h, hipMemcpy(entry.data(), d_entry, 8 * found, hipMemcpyDeviceToHost)); HIPCHK(h, hipMemcpy(lst.data(), d_list, 4 * found, hipMemcpyDeviceToHost));
 	std::vector<uint32_t> order(found);
 	for (uint32_t i = 0; i < found; i++) order[i] = i;
 	std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return lst[a] != lst[b] ? lst[a] < lst[b] : entry[a] < entry[b]; });
@@ -1743,45 +1738,43 @@ template <int W> int saturated_fix_t(kmr_handle *h, const uint64_t *ls, const ui
 		const uint32_t l = lst[order[i]];
 		if (dl.empty() || dl.back() != l) { dl.push_back(l); le0.push_back(i); le1.push_back(i + 1); } else le1.back() = i + 1;
 	}
-	SATCHK(hipMemcpy(d_entry, sentry.data(), 8 * found, hipMemcpyHostToDevice));
-	SATCHK(hipMemcpy(d_list, dl.data(), 4 * dl.size(), hipMemcpyHostToDevice));
-	uint64_t *d_c0 = nullptr, *d_c1 = nullptr;
-	SATCHK(dalloc((void **)&d_c0, 8 * dl.size())); SATCHK(dalloc((void **)&d_c1, 8 * dl.size()));
+	HIPCHK(h, hipMemcpy(d_entry, sentry.data(), 8 * found, hipMemcpyHostToDevice));
+	HIPCHK(h, hipMemcpy(d_list, dl.data(), 4 * dl.size(), hipMemcpyHostToDevice));
+	HIPCHK(h, dalloc(bc0, 8 * dl.size())); HIPCHK(h, dalloc(bc1, 8 * dl.size()));
+	uint64_t *d_c0 = bc0.get<uint64_t>(), *d_c1 = bc1.get<uint64_t>();
 	hipLaunchKernelGGL(sat_gather_kernel, dim3(grid_for(dl.size())), dim3(256), 0, h->stream, ls, (const uint32_t *)d_list, (uint64_t)dl.size(), d_c0, d_c1);
-	SATCHK(hipGetLastError());
+	HIPCHK(h, hipGetLastError());
 	std::vector<uint64_t> c0(dl.size()), c1(dl.size());
-	SATCHK(hipMemcpy(c0.data(), d_c0, 8 * dl.size(), hipMemcpyDeviceToHost)); SATCHK(hipMemcpy(c1.data(), d_c1, 8 * dl.size(), hipMemcpyDeviceToHost));
+	HIPCHK(h, hipMemcpy(c0.data(), d_c0, 8 * dl.size(), hipMemcpyDeviceToHost)); HIPCHK(h, hipMemcpy(c1.data(), d_c1, 8 * dl.size(), hipMemcpyDeviceToHost));
 	/* work items: pieces of 256 chunks of those lists */
 	std::vector<uint64_t> ic0, ic1, ie0, ie1;
 	for (size_t i = 0; i < dl.size(); i++)
 		for (uint64_t a = c0[i]; a < c1[i]; a += 256) { ic0.push_back(a); ic1.push_back(std::min(c1[i], a + 256)); ie0.push_back(le0[i]); ie1.push_back(le1[i]); }
-	if (ic0.empty()) { release(); return 0; }
-	uint64_t *d_items = nullptr;
+	if (ic0.empty()) return 0;
 	const size_t ni = ic0.size();
-	SATCHK(dalloc((void **)&d_items, 32 * ni));
-	SATCHK(hipMemcpy(d_items, ic0.data(), 8 * ni, hipMemcpyHostToDevice)); SATCHK(hipMemcpy(d_items + ni, ic1.data(), 8 * ni, hipMemcpyHostToDevice));
-	SATCHK(hipMemcpy(d_items + 2 * ni, ie0.data(), 8 * ni, hipMemcpyHostToDevice)); SATCHK(hipMemcpy(d_items + 3 * ni, ie1.data(), 8 * ni, hipMemcpyHostToDevice));
+	HIPCHK(h, dalloc(bitems, 32 * ni));
+	uint64_t *d_items = bitems.get<uint64_t>();
+	HIPCHK(h, hipMemcpy(d_items, ic0.data(), 8 * ni, hipMemcpyHostToDevice)); HIPCHK(h, hipMemcpy(d_items + ni, ic1.data(), 8 * ni, hipMemcpyHostToDevice));
+	HIPCHK(h, hipMemcpy(d_items + 2 * ni, ie0.data(), 8 * ni, hipMemcpyHostToDevice)); HIPCHK(h, hipMemcpy(d_items + 3 * ni, ie1.data(), 8 * ni, hipMemcpyHostToDevice));
 	/* every sighting of those keys (the count pass has added up their true counts; entries of a map merged in later add theirs) */
 	const uint64_t pcap = n_sightings + (found - std::min<unsigned long long>(found, n_clamped)) * 65535ull + 64;
-	unsigned long long *pk_in = nullptr, *pk_out = nullptr; uint32_t *pv_in = nullptr, *pv_out = nullptr;
-	SATCHK(dalloc((void **)&pk_in, 8 * pcap)); SATCHK(dalloc((void **)&pk_out, 8 * pcap)); SATCHK(dalloc((void **)&pv_in, 4 * pcap)); SATCHK(dalloc((void **)&pv_out, 4 * pcap));
-	SATCHK(hipMemsetAsync(dfound, 0, 8, h->stream));
-	int rc = zero_work_counter(h); if (rc) { release(); return rc; }
-	hipLaunchKernelGGL(sat_collect_kernel<W>, dim3((unsigned)std::min<uint64_t>(ni, (uint64_t)num_cus(h) * 4)), dim3(256), 0, h->stream, pool_view(h, h->l1), lc, h->k, (const uint64_t *)wm.keys, (const uint64_t *)d_entry,
-	                   (const uint64_t *)d_items, (const uint64_t *)(d_items + ni), (const uint64_t *)(d_items + 2 * ni), (const uint64_t *)(d_items + 3 * ni), (uint64_t)ni, dfound, pcap, pk_in, pv_in, h->work_counter);
-	SATCHK(hipGetLastError());
+	HIPCHK(h, dalloc(bk_in, 8 * pcap)); HIPCHK(h, dalloc(bk_out, 8 * pcap)); HIPCHK(h, dalloc(bv_in, 4 * pcap)); HIPCHK(h, dalloc(bv_out, 4 * pcap));
+	unsigned long long *pk_in = bk_in.get<unsigned long long>(), *pk_out = bk_out.get<unsigned long long>(); uint32_t *pv_in = bv_in.get<uint32_t>(), *pv_out = bv_out.get<uint32_t>();
+	HIPCHK(h, hipMemsetAsync(dfound, 0, 8, h->stream));
+	int rc = zero_work_counter(h); if (rc) return rc;
+	hipLaunchKernelGGL(sat_collect_kernel<W>, dim3((unsigned)std::min<uint64_t>(ni, (uint64_t)num_cus(h) * 4)), dim3(256), 0, h->stream, pool_view(h, h->l1), lc, h->k, (const uint64_t *)wm.keys.get<uint64_t>(), (const uint64_t *)d_entry,
+	                   (const uint64_t *)d_items, (const uint64_t *)(d_items + ni), (const uint64_t *)(d_items + 2 * ni), (const uint64_t *)(d_items + 3 * ni), (uint64_t)ni, dfound, pcap, pk_in, pv_in, h->work_counter.get<unsigned int>());
+	HIPCHK(h, hipGetLastError());
 	unsigned long long n_pairs = 0;
-	SATCHK(hipMemcpyAsync(&n_pairs, dfound, 8, hipMemcpyDeviceToHost, h->stream)); SATCHK(hipStreamSynchronize(h->stream));
-	if (n_pairs > pcap) { release(); return fail(h, KMR_ERR_CAPACITY, "sightings of saturated k-mers (internal sizing error)"); }
-	size_t tmp_bytes = 0; void *tmp = nullptr;
-	if (kmr::sort_pairs_u64_u32(nullptr, &tmp_bytes, pk_in, pk_out, pv_in, pv_out, n_pairs, h->stream) != 0) { release(); return fail(h, KMR_ERR_HIP, "radix sort (size query)"); }
-	SATCHK(dalloc(&tmp, tmp_bytes));
-	if (kmr::sort_pairs_u64_u32(tmp, &tmp_bytes, pk_in, pk_out, pv_in, pv_out, n_pairs, h->stream) != 0) { release(); return fail(h, KMR_ERR_HIP, "radix sort"); }
-	hipLaunchKernelGGL(sat_reduce_kernel, dim3((unsigned)std::min<uint64_t>(found, 4096)), dim3(256), 0, h->stream, (const unsigned long long *)pk_out, (const uint32_t *)pv_out, (uint64_t)n_pairs, (const uint64_t *)d_entry, (uint64_t)found, has_singletons, wm.vals, h->ext ? 15u : 3u);
-	SATCHK(hipGetLastError());
-	SATCHK(hipStreamSynchronize(h->stream));
-	release();
-#undef SATCHK
+	HIPCHK(h, hipMemcpyAsync(&n_pairs, dfound, 8, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
+	if (n_pairs > pcap) return fail(h, KMR_ERR_CAPACITY, "sightings of saturated k-mers (internal sizing error)");
+	size_t tmp_bytes = 0;
+	if (kmr::sort_pairs_u64_u32(nullptr, &tmp_bytes, pk_in, pk_out, pv_in, pv_out, n_pairs, h->stream) != 0) return fail(h, KMR_ERR_HIP, "radix sort (size query)");
+	HIPCHK(h, dalloc(btmp, tmp_bytes));
+	if (kmr::sort_pairs_u64_u32(btmp.get(), &tmp_bytes, pk_in, pk_out, pv_in, pv_out, n_pairs, h->stream) != 0) return fail(h, KMR_ERR_HIP, "radix sort");
+	hipLaunchKernelGGL(sat_reduce_kernel, dim3((unsigned)std::min<uint64_t>(found, 4096)), dim3(256), 0, h->stream, (const unsigned long long *)pk_out, (const uint32_t *)pv_out, (uint64_t)n_pairs, (const uint64_t *)d_entry, (uint64_t)found, has_singletons, wm.vals.get<uint32_t>(), h->ext ? 15u : 3u);
+	HIPCHK(h, hipGetLastError());
+	HIPCHK(h, hipStreamSynchronize(h->stream));
 	return 0;
 }
 
@@ -1796,7 +1789,7 @@ template <int W> int finalize_superkmer_t(kmr_handle *h, uint32_t min_depth) {
 	rc = arena_reset(h); if (rc) return rc;
 	uint64_t nl = h->sk_state ? sk_list_count(h->sk_bits) : 1;
 	if (h->sk_state) {
-		hipLaunchKernelGGL(sk_close_kernel, dim3(grid_for(nl)), dim3(256), 0, h->stream, h->sk_state, nl, h->l1.chunk_count, h->l1.cap);
+		hipLaunchKernelGGL(sk_close_kernel, dim3(grid_for(nl)), dim3(256), 0, h->stream, h->sk_state.get<unsigned long long>(), nl, h->l1.chunk_count.get<uint32_t>(), h->l1.cap);
 		HIPCHK(h, hipGetLastError());
 	}
 	const bool refined = h->sk_state && h->sk_fine_shift > 0;
@@ -1806,19 +1799,15 @@ template <int W> int finalize_superkmer_t(kmr_handle *h, uint32_t min_depth) {
 		const uint64_t nlf = 1ull << fine_bits;
 		unsigned int head = 0;
 		HIPCHK(h, hipStreamSynchronize(h->stream));
-		HIPCHK(h, hipMemcpy(&head, h->l1.head, 4, hipMemcpyDeviceToHost));
+		HIPCHK(h, hipMemcpy(&head, h->l1.head.get<unsigned int>(), 4, hipMemcpyDeviceToHost));
 		if (head > h->l1.cap) head = h->l1.cap;
-		if (h->sk_fine_cap < nlf) {
-			if (h->sk_fine_state) hipFree(h->sk_fine_state);
-			h->sk_fine_state = nullptr; h->sk_fine_cap = 0;
-			HIPCHK(h, dev_malloc((void **)&h->sk_fine_state, 8 * nlf)); h->sk_fine_cap = nlf;
-		}
-		hipLaunchKernelGGL(sk_state_init_kernel, dim3(grid_for(nlf)), dim3(256), 0, h->stream, h->sk_fine_state, nlf);
+		rc = h->sk_fine_state.reserve(h, "sk_fine_state", 8 * nlf); if (rc) return rc;
+		hipLaunchKernelGGL(sk_state_init_kernel, dim3(grid_for(nlf)), dim3(256), 0, h->stream, h->sk_fine_state.get<unsigned long long>(), nlf);
 		const int rgrid = (int)std::min<uint64_t>(((uint64_t)head + SK_REFINE_WAVES - 1) / SK_REFINE_WAVES + 1, (uint64_t)num_cus(h) * 8);
 		/* every old chunk's records again, cut into at most 2^shift pieces per chunk (a piece may open a chunk), an open chunk per owned fine list */
 		rc = pool_reserve(h, h->l1, (uint64_t)head * 2 + nlf / h->cfg.world_size + (uint64_t)rgrid * SK_REFINE_WAVES * 130 + 64, true); if (rc) return rc;
-		if (head) hipLaunchKernelGGL(sk_refine_kernel, dim3(rgrid), dim3(SK_REFINE_WAVES * 64), 0, h->stream, pool_view(h, h->l1), head, fine_bits, h->sk_fine_state);
-		hipLaunchKernelGGL(sk_close_kernel, dim3(grid_for(nlf)), dim3(256), 0, h->stream, h->sk_fine_state, nlf, h->l1.chunk_count, h->l1.cap);
+		if (head) hipLaunchKernelGGL(sk_refine_kernel, dim3(rgrid), dim3(SK_REFINE_WAVES * 64), 0, h->stream, pool_view(h, h->l1), head, fine_bits, h->sk_fine_state.get<unsigned long long>());
+		hipLaunchKernelGGL(sk_close_kernel, dim3(grid_for(nlf)), dim3(256), 0, h->stream, h->sk_fine_state.get<unsigned long long>(), nlf, h->l1.chunk_count.get<uint32_t>(), h->l1.cap);
 		HIPCHK(h, hipGetLastError());
 		nl = nlf;
 	}
@@ -1836,11 +1825,8 @@ template <int W> int finalize_superkmer_t(kmr_handle *h, uint32_t min_depth) {
 	 * buffers when that was not enough */
 	uint64_t wcap = std::min<uint64_t>(wmax, G / (f.has_singletons ? 8 : 3) + slack), scap = keepSing ? std::min<uint64_t>(smax, G / 3 + slack) : 16;
 	if (h->tune.entry_share >= 0) { wcap = std::min<uint64_t>(wmax, (uint64_t)((double)G * h->tune.entry_share) + 16384); if (keepSing) scap = std::min<uint64_t>(smax, (uint64_t)((double)G * h->tune.entry_share) + 16384);
-		if (h->ue) { hipFree(h->ue); h->ue = nullptr; h->ue_cap = 0; }
-		if (h->us_keys) { hipFree(h->us_keys); hipFree(h->us_b8); if (h->us_pkt) hipFree(h->us_pkt); h->us_keys = h->us_b8 = h->us_pkt = nullptr; h->us_cap = 0; } }
-	if (!ext && h->ue && h->ue_cap >= wcap) wcap = h->ue_cap;
-	if (ext && h->uw_keys && h->uw_cap >= wcap) wcap = h->uw_cap;
-	if (h->us_keys && h->us_cap >= scap) scap = h->us_cap;
+		h->ue.reset(); h->us_keys.reset(); h->us_b8.reset(); h->us_pkt.reset(); }
+	wcap = std::max(wcap, ext ? key_entries(h, h->uw_keys) : packed_entries(h, h->ue)); scap = std::max(scap, key_entries(h, h->us_keys));
 	uint32_t *wc = nullptr, *sc = nullptr; FinalizeCounters *fc = nullptr; unsigned long long *cursors = nullptr;
 	rc = arena_get(h, &wc, h->nb_weak); if (rc) return rc; rc = arena_get(h, &sc, h->nb_sing); if (rc) return rc;
 	rc = arena_get(h, &fc, 1); if (rc) return rc; rc = arena_get(h, &cursors, 2); if (rc) return rc;
@@ -1859,7 +1845,7 @@ template <int W> int finalize_superkmer_t(kmr_handle *h, uint32_t min_depth) {
 		else if (h->peer_uni_w != SK_UNI_NONE) { if (w == SK_UNI_NONE) w = h->peer_uni_w; else if (w != h->peer_uni_w) mixed = true; }
 		if (h->d_uni) {
 			uint32_t dv[2] = {SK_UNI_NONE, 0u};
-			HIPCHK(h, hipMemcpy(dv, h->d_uni, 8, hipMemcpyDeviceToHost));
+			HIPCHK(h, hipMemcpy(dv, h->d_uni.get<uint32_t>(), 8, hipMemcpyDeviceToHost));
 			if (dv[1]) mixed = true;
 			else if (dv[0] != SK_UNI_NONE) { if (w == SK_UNI_NONE) w = dv[0]; else if (w != dv[0]) mixed = true; }
 		}
@@ -1885,11 +1871,11 @@ template <int W> int finalize_superkmer_t(kmr_handle *h, uint32_t min_depth) {
 	h->last_early_hi = 0; h->last_early_entries = 0;
 	if (h->early.active) {
 		uint32_t cerr0 = 0;
-		HIPCHK(h, hipMemcpy(&cerr0, h->derr, 4, hipMemcpyDeviceToHost));
+		HIPCHK(h, hipMemcpy(&cerr0, h->derr.get<uint32_t>(), 4, hipMemcpyDeviceToHost));
 		unsigned long long ecur = 0;
-		HIPCHK(h, hipMemcpy(&ecur, h->early.cursor, 8, hipMemcpyDeviceToHost)); HIPCHK(h, hipMemcpy(&early_c, h->early.fc, sizeof(early_c), hipMemcpyDeviceToHost));
-		const bool ok = !(cerr0 & ERR_ENTRIES_FULL) && ecur <= h->early.cap && h->early.min_depth == min_depth && !tracking && !ext && !keepSing && !refined;
-		if (cerr0 & ERR_ENTRIES_FULL) { cerr0 &= ~(uint32_t)ERR_ENTRIES_FULL; HIPCHK(h, hipMemcpy(h->derr, &cerr0, 4, hipMemcpyHostToDevice)); }
+		HIPCHK(h, hipMemcpy(&ecur, h->early.cursor.get<unsigned long long>(), 8, hipMemcpyDeviceToHost)); HIPCHK(h, hipMemcpy(&early_c, h->early.fc.get(), sizeof(early_c), hipMemcpyDeviceToHost));
+		const bool ok = !(cerr0 & ERR_ENTRIES_FULL) && ecur <= packed_entries(h, h->early.ue) && h->early.min_depth == min_depth && !tracking && !ext && !keepSing && !refined;
+		if (cerr0 & ERR_ENTRIES_FULL) { cerr0 &= ~(uint32_t)ERR_ENTRIES_FULL; HIPCHK(h, hipMemcpy(h->derr.get<uint32_t>(), &cerr0, 4, hipMemcpyHostToDevice)); }
 		if (ok) {
 			early_slots = ecur;
 			h->last_early_hi = h->early.hi; h->last_early_entries = early_c.weak_kept;
@@ -1922,24 +1908,21 @@ template <int W> int finalize_superkmer_t(kmr_handle *h, uint32_t min_depth) {
 	uint32_t merge_log2 = 16;
 	hipEvent_t tca, tcb; time_begin(h, KMR_TIME_COUNT, &tca, &tcb);
 	for (int attempt = 0; ; attempt++) {
-		if (!ext && (!h->ue || h->ue_cap < wcap)) {
-			if (h->ue) hipFree(h->ue); h->ue = nullptr; h->ue_cap = 0;
-			HIPCHK(h, dev_malloc((void **)&h->ue, 8ull * (W + 1) * wcap)); h->ue_cap = wcap;
+		if (!ext && packed_entries(h, h->ue) < wcap) { h->ue.reset(); HIPCHK(h, h->ue.alloc(8ull * (W + 1) * wcap)); }
+		if (ext && (key_entries(h, h->uw_keys) < wcap || !h->uw_vals)) {
+			h->uw_keys.reset(); h->uw_vals.reset();
+			HIPCHK(h, h->uw_keys.alloc(8ull * W * wcap)); HIPCHK(h, h->uw_vals.alloc(4ull * vw * wcap));
 		}
-		if (ext && (!h->uw_keys || h->uw_cap < wcap)) {
-			if (h->uw_keys) hipFree(h->uw_keys); if (h->uw_vals) hipFree(h->uw_vals); h->uw_keys = h->uw_vals = nullptr; h->uw_cap = 0;
-			HIPCHK(h, dev_malloc(&h->uw_keys, 8ull * W * wcap)); HIPCHK(h, dev_malloc(&h->uw_vals, 4ull * vw * wcap)); h->uw_cap = wcap;
-		}
-		if (!h->us_keys || h->us_cap < scap || (ext && !h->us_pkt)) {
-			if (h->us_keys) hipFree(h->us_keys); if (h->us_b8) hipFree(h->us_b8); if (h->us_pkt) hipFree(h->us_pkt); h->us_keys = h->us_b8 = h->us_pkt = nullptr; h->us_cap = 0;
-			HIPCHK(h, dev_malloc(&h->us_keys, 8ull * W * scap)); HIPCHK(h, dev_malloc(&h->us_b8, scap)); if (ext) HIPCHK(h, dev_malloc(&h->us_pkt, 4 * scap)); h->us_cap = scap;
+		if (key_entries(h, h->us_keys) < scap || !h->us_b8 || (ext && !h->us_pkt)) {
+			h->us_keys.reset(); h->us_b8.reset(); h->us_pkt.reset();
+			HIPCHK(h, h->us_keys.alloc(8ull * W * scap)); HIPCHK(h, h->us_b8.alloc(scap)); if (ext) HIPCHK(h, h->us_pkt.alloc(4 * scap));
 		}
 		HIPCHK(h, hipMemsetAsync(wc, 0, 4 * h->nb_weak, h->stream)); HIPCHK(h, hipMemsetAsync(sc, 0, 4 * h->nb_sing, h->stream));
 		HIPCHK(h, hipMemsetAsync(fc, 0, sizeof(FinalizeCounters), h->stream)); HIPCHK(h, hipMemsetAsync(cursors, 0, 16, h->stream));
-		CountOut out; out.wkeys = nullptr; out.wvals = nullptr; out.wentries = h->ue; out.wcursor = cursors; out.wcap = h->ue_cap;
-		out.skeys = (uint64_t *)h->us_keys; out.sweight = (uint8_t *)h->us_b8; out.spkt = nullptr; out.scursor = cursors + 1; out.scap = h->us_cap;
-		out.weakCount = nullptr; out.singCount = sc; out.fc = fc; out.err = h->derr;      /* weak entries are bucketed without a per-bucket histogram (kmr_buckets.hpp) */
-		if (ext) { out.wkeys = (uint64_t *)h->uw_keys; out.wvals = (uint32_t *)h->uw_vals; out.wentries = nullptr; out.wcap = h->uw_cap; out.spkt = (uint32_t *)h->us_pkt; out.weakCount = wc; }
+		CountOut out; out.wkeys = nullptr; out.wvals = nullptr; out.wentries = h->ue.get<uint64_t>(); out.wcursor = cursors; out.wcap = packed_entries(h, h->ue);
+		out.skeys = h->us_keys.get<uint64_t>(); out.sweight = h->us_b8.get<uint8_t>(); out.spkt = nullptr; out.scursor = cursors + 1; out.scap = key_entries(h, h->us_keys);
+		out.weakCount = nullptr; out.singCount = sc; out.fc = fc; out.err = h->derr.get<uint32_t>();      /* weak entries are bucketed without a per-bucket histogram (kmr_buckets.hpp) */
+		if (ext) { out.wkeys = h->uw_keys.get<uint64_t>(); out.wvals = h->uw_vals.get<uint32_t>(); out.wentries = nullptr; out.wcap = key_entries(h, h->uw_keys); out.spkt = h->us_pkt.get<uint32_t>(); out.weakCount = wc; }
 		rc = zero_work_counter(h); if (rc) return rc;
 		const int grid = (int)std::min<uint64_t>((uint64_t)num_cus(h) * 4, (nl / lgMain.list_stride + SK_LBATCH) / SK_LBATCH);
 		auto kern = ext ? sk_count_kernel<W, COUNT_LOG2S_EXT, false, true> : (tracking ? sk_count_kernel<W, COUNT_LOG2S, true> : (uni ? sk_count_kernel<W, COUNT_LOG2S, false, false, true> : sk_count_kernel<W, COUNT_LOG2S, false>));
@@ -1947,39 +1930,37 @@ template <int W> int finalize_superkmer_t(kmr_handle *h, uint32_t min_depth) {
 		if (tracking) HIPCHK(h, hipMemsetAsync(tv.d_unique, 0, 8 * (tv.n + 1), h->stream));
 		HIPCHK(h, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
 		if (dbg()) { int nb = 0; hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)kern, SKC_THREADS, smem); fprintf(stderr, "sk_count<W=%d>: %d blocks per CU (LDS %zu), %llu lists, %u chunks\n", W, nb, smem, (unsigned long long)nl, nch); }
-		hipLaunchKernelGGL(kern, dim3(grid), dim3(SKC_THREADS), smem, h->stream, pool_view(h, h->l1), ls, lc, nl, h->k, out, f, h->work_counter, sk_dbg_flags("KMR_SK_COUNT_DBG"), tv, lgMain);
+		hipLaunchKernelGGL(kern, dim3(grid), dim3(SKC_THREADS), smem, h->stream, pool_view(h, h->l1), ls, lc, nl, h->k, out, f, h->work_counter.get<unsigned int>(), sk_dbg_flags("KMR_SK_COUNT_DBG"), tv, lgMain);
 		HIPCHK(h, hipGetLastError());
-		Slot<W> *mslots = nullptr; ExtSlot *mext = nullptr;
+		DevBuf mslots, mext;      /* freed at the end of the attempt */
 		if (n_items) {
 			/* the merge table holds the distinct keys of the long lists: few when a list is long because a k-mer repeats, at most the
 			 * k-mers of those lists; it starts small and the attempt is repeated with a larger one if it fills */
-			if (dev_malloc((void **)&mslots, sizeof(Slot<W>) << merge_log2) != hipSuccess) return fail(h, KMR_ERR_OOM, "merge table of the long lists");
-			if (ext && dev_malloc((void **)&mext, sizeof(ExtSlot) << merge_log2) != hipSuccess) { hipFree(mslots); return fail(h, KMR_ERR_OOM, "merge table of the long lists"); }
-			hipLaunchKernelGGL(table_clear_kernel<W>, dim3(grid_for(1ull << merge_log2)), dim3(256), 0, h->stream, mslots, mext, 1ull << merge_log2);
-			lgItems.merge.slots = mslots; lgItems.merge.ext = mext; lgItems.merge.log2cap = merge_log2;
+			if (mslots.alloc(sizeof(Slot<W>) << merge_log2) != hipSuccess) return fail(h, KMR_ERR_OOM, "merge table of the long lists");
+			if (ext && mext.alloc(sizeof(ExtSlot) << merge_log2) != hipSuccess) return fail(h, KMR_ERR_OOM, "merge table of the long lists");
+			hipLaunchKernelGGL(table_clear_kernel<W>, dim3(grid_for(1ull << merge_log2)), dim3(256), 0, h->stream, mslots.get<Slot<W>>(), mext.get<ExtSlot>(), 1ull << merge_log2);
+			lgItems.merge.slots = mslots.get<Slot<W>>(); lgItems.merge.ext = mext.get<ExtSlot>(); lgItems.merge.log2cap = merge_log2;
 			HIPCHK(h, hipMemsetAsync(lgItems.merge_used, 0, 8, h->stream));
-			rc = zero_work_counter(h); if (rc) { hipFree(mslots); if (mext) hipFree(mext); return rc; }
+			rc = zero_work_counter(h); if (rc) return rc;
 			const int grid2 = (int)std::min<uint64_t>((uint64_t)num_cus(h) * 4, n_items);
-			hipLaunchKernelGGL(kern, dim3(grid2), dim3(SKC_THREADS), smem, h->stream, pool_view(h, h->l1), ls, lc, nl, h->k, out, f, h->work_counter, sk_dbg_flags("KMR_SK_COUNT_DBG"), tv, lgItems);
+			hipLaunchKernelGGL(kern, dim3(grid2), dim3(SKC_THREADS), smem, h->stream, pool_view(h, h->l1), ls, lc, nl, h->k, out, f, h->work_counter.get<unsigned int>(), sk_dbg_flags("KMR_SK_COUNT_DBG"), tv, lgItems);
 			hipLaunchKernelGGL(sk_merge_emit_kernel<W>, dim3(grid_for(1ull << merge_log2)), dim3(256), 0, h->stream, lgItems.merge, out, f);
-			if (hipGetLastError() != hipSuccess) { hipFree(mslots); if (mext) hipFree(mext); return fail(h, KMR_ERR_HIP, "long-list launches"); }
+			if (hipGetLastError() != hipSuccess) return fail(h, KMR_ERR_HIP, "long-list launches");
 		}
 		uint32_t cerr = 0;
 		HIPCHK(h, hipMemcpyAsync(&c, fc, sizeof(c), hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipMemcpyAsync(cur, cursors, 16, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(h, hipMemcpyAsync(&cerr, h->derr, 4, hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, hipMemcpyAsync(&cerr, h->derr.get<uint32_t>(), 4, hipMemcpyDeviceToHost, h->stream));
 		HIPCHK(h, hipStreamSynchronize(h->stream));
-		if (mslots) hipFree(mslots);
-		if (mext) hipFree(mext);
 		if (n_items && (cerr & ERR_TABLE_FULL) && merge_log2 < 30) {      /* the merge table filled: again with a larger one */
 			cerr &= ~(uint32_t)(ERR_TABLE_FULL | ERR_ENTRIES_FULL);
-			HIPCHK(h, hipMemcpy(h->derr, &cerr, 4, hipMemcpyHostToDevice));
+			HIPCHK(h, hipMemcpy(h->derr.get<uint32_t>(), &cerr, 4, hipMemcpyHostToDevice));
 			merge_log2 += 3;
 			continue;
 		}
 		if (!(cerr & ERR_ENTRIES_FULL)) break;
 		if ((wcap >= wmax && scap >= smax) || attempt >= 8) { time_end(h, KMR_TIME_COUNT, tca, tcb); time_end(h, 1, ea, eb); return fail(h, KMR_ERR_CAPACITY, "entry buffers of the count pass overflowed at their upper bound (internal sizing error)"); }
 		cerr &= ~(uint32_t)ERR_ENTRIES_FULL;
-		HIPCHK(h, hipMemcpy(h->derr, &cerr, 4, hipMemcpyHostToDevice));
+		HIPCHK(h, hipMemcpy(h->derr.get<uint32_t>(), &cerr, 4, hipMemcpyHostToDevice));
 		wcap = std::min<uint64_t>(wmax, wcap * 2); if (keepSing) scap = std::min<uint64_t>(smax, scap * 2);
 		if (dbg()) fprintf(stderr, "sk count pass: entry buffers too small, retrying with %llu / %llu\n", (unsigned long long)wcap, (unsigned long long)scap);
 	}
@@ -2000,13 +1981,13 @@ template <int W> int finalize_superkmer_t(kmr_handle *h, uint32_t min_depth) {
 	}
 	if (early_slots) {      /* the early count's entries behind this pass's (the slabs' unused tails are holes in both) */
 		const size_t eb = 8ull * (W + 1);
-		if (cur[0] + early_slots > h->ue_cap) {
-			uint64_t *bigger = nullptr; const uint64_t ncap = cur[0] + early_slots + 4096;
-			HIPCHK(h, dev_malloc((void **)&bigger, eb * ncap));
-			HIPCHK(h, hipMemcpyAsync(bigger, h->ue, eb * cur[0], hipMemcpyDeviceToDevice, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
-			hipFree(h->ue); h->ue = bigger; h->ue_cap = ncap;
+		if (cur[0] + early_slots > packed_entries(h, h->ue)) {
+			DevBuf bigger;
+			HIPCHK(h, bigger.alloc(eb * (cur[0] + early_slots + 4096)));
+			HIPCHK(h, hipMemcpyAsync(bigger.get(), h->ue.get(), eb * cur[0], hipMemcpyDeviceToDevice, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
+			h->ue = std::move(bigger);
 		}
-		HIPCHK(h, hipMemcpyAsync((uint8_t *)h->ue + eb * cur[0], h->early.ue, eb * early_slots, hipMemcpyDeviceToDevice, h->stream));
+		HIPCHK(h, hipMemcpyAsync((uint8_t *)h->ue.get<uint64_t>() + eb * cur[0], h->early.ue.get<uint64_t>(), eb * early_slots, hipMemcpyDeviceToDevice, h->stream));
 		cur[0] += early_slots;
 		c.unique += early_c.unique; c.singletons += early_c.singletons; c.weak_kept += early_c.weak_kept; c.sing_kept += early_c.sing_kept;
 		c.saturated += early_c.saturated; c.sat_sightings += early_c.sat_sightings;
@@ -2040,7 +2021,7 @@ template <int W> int count_prefix_superkmer_t(kmr_handle *h, uint32_t min_depth,
 	if (hi > nl) hi = nl;
 	if (hi == 0) return KMR_OK;
 	rc = arena_reset(h); if (rc) return rc;
-	hipLaunchKernelGGL(sk_close_kernel, dim3(grid_for(nl)), dim3(256), 0, h->stream, h->sk_state, nl, h->l1.chunk_count, h->l1.cap);
+	hipLaunchKernelGGL(sk_close_kernel, dim3(grid_for(nl)), dim3(256), 0, h->stream, h->sk_state.get<unsigned long long>(), nl, h->l1.chunk_count.get<uint32_t>(), h->l1.cap);
 	HIPCHK(h, hipGetLastError());
 	uint64_t *ls = nullptr, *lc = nullptr; uint32_t nch = 0;
 	rc = build_csr(h, h->l1, nl, 0, &ls, &lc, &nch); if (rc) return rc;
@@ -2049,20 +2030,17 @@ template <int W> int count_prefix_superkmer_t(kmr_handle *h, uint32_t min_depth,
 	const uint64_t G = h->stats.raw_good_kmers;      /* (an owner's lists hold about as many k-mers as its own reads gave: the job's share of one rank) */
 	const uint64_t slack = (uint64_t)num_cus(h) * 4 * 8192 + 16;
 	const uint64_t want = (uint64_t)((double)G * ((double)hi / (double)nl) / (f.has_singletons ? 6.0 : 2.5)) + slack;
-	if (!h->early.ue || h->early.cap < want) {
-		if (h->early.ue) hipFree(h->early.ue); h->early.ue = nullptr; h->early.cap = 0;
-		HIPCHK(h, dev_malloc((void **)&h->early.ue, 8ull * (W + 1) * want)); h->early.cap = want;
-	}
-	if (!h->early.cursor) HIPCHK(h, dev_malloc((void **)&h->early.cursor, 16));
-	if (!h->early.fc) HIPCHK(h, dev_malloc((void **)&h->early.fc, sizeof(FinalizeCounters)));
-	HIPCHK(h, hipMemsetAsync(h->early.cursor, 0, 16, h->stream)); HIPCHK(h, hipMemsetAsync(h->early.fc, 0, sizeof(FinalizeCounters), h->stream));
+	rc = h->early.ue.reserve(h, "early count ue", 8ull * (W + 1) * want); if (rc) return rc;
+	rc = h->early.cursor.reserve(h, "early count cursor", 16); if (rc) return rc;
+	rc = h->early.fc.reserve(h, "early count fc", sizeof(FinalizeCounters)); if (rc) return rc;
+	HIPCHK(h, hipMemsetAsync(h->early.cursor.get<unsigned long long>(), 0, 16, h->stream)); HIPCHK(h, hipMemsetAsync(h->early.fc.get(), 0, sizeof(FinalizeCounters), h->stream));
 	bool uni = false;
 	if (!h->sk_uni_mixed && !h->tune.no_uniform_count && !h->peer_uni_mixed && (W == 1 || (h->k & 31u) != 0)) {
 		uint32_t w = h->sk_uni_w; bool mixed = false;
 		if (h->peer_uni_w != SK_UNI_NONE) { if (w == SK_UNI_NONE) w = h->peer_uni_w; else if (w != h->peer_uni_w) mixed = true; }
 		if (h->d_uni) {
 			uint32_t dv[2] = {SK_UNI_NONE, 0u};
-			HIPCHK(h, hipMemcpy(dv, h->d_uni, 8, hipMemcpyDeviceToHost));
+			HIPCHK(h, hipMemcpy(dv, h->d_uni.get<uint32_t>(), 8, hipMemcpyDeviceToHost));
 			if (dv[1]) mixed = true;
 			else if (dv[0] != SK_UNI_NONE) { if (w == SK_UNI_NONE) w = dv[0]; else if (w != dv[0]) mixed = true; }
 		}
@@ -2077,9 +2055,9 @@ template <int W> int count_prefix_superkmer_t(kmr_handle *h, uint32_t min_depth,
 	uint32_t *sc = nullptr;
 	rc = arena_get(h, &sc, h->nb_sing); if (rc) return rc;
 	HIPCHK(h, hipMemsetAsync(sc, 0, 4 * h->nb_sing, h->stream));
-	CountOut out; out.wkeys = nullptr; out.wvals = nullptr; out.wentries = h->early.ue; out.wcursor = h->early.cursor; out.wcap = h->early.cap;
-	out.skeys = nullptr; out.sweight = nullptr; out.spkt = nullptr; out.scursor = h->early.cursor + 1; out.scap = 0;
-	out.weakCount = nullptr; out.singCount = sc; out.fc = (FinalizeCounters *)h->early.fc; out.err = h->derr;
+	CountOut out; out.wkeys = nullptr; out.wvals = nullptr; out.wentries = h->early.ue.get<uint64_t>(); out.wcursor = h->early.cursor.get<unsigned long long>(); out.wcap = packed_entries(h, h->early.ue);
+	out.skeys = nullptr; out.sweight = nullptr; out.spkt = nullptr; out.scursor = h->early.cursor.get<unsigned long long>() + 1; out.scap = 0;
+	out.weakCount = nullptr; out.singCount = sc; out.fc = (FinalizeCounters *)h->early.fc.get(); out.err = h->derr.get<uint32_t>();
 	rc = zero_work_counter(h); if (rc) return rc;
 	const uint64_t n_work = hi > lg.list_first ? (hi - lg.list_first + lg.list_stride - 1) / lg.list_stride : 0;
 	if (n_work) {
@@ -2088,7 +2066,7 @@ template <int W> int count_prefix_superkmer_t(kmr_handle *h, uint32_t min_depth,
 		const size_t smem = uni ? sk_count_smem_bytes<W, COUNT_LOG2S, false, false, true>() : sk_count_smem_bytes<W, COUNT_LOG2S, false>();
 		HIPCHK(h, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
 		hipEvent_t a, b; time_begin(h, KMR_TIME_COUNT, &a, &b);
-		hipLaunchKernelGGL(kern, dim3(grid), dim3(SKC_THREADS), smem, h->stream, pool_view(h, h->l1), ls, lc, hi, h->k, out, f, h->work_counter, sk_dbg_flags("KMR_SK_COUNT_DBG"), tv, lg);
+		hipLaunchKernelGGL(kern, dim3(grid), dim3(SKC_THREADS), smem, h->stream, pool_view(h, h->l1), ls, lc, hi, h->k, out, f, h->work_counter.get<unsigned int>(), sk_dbg_flags("KMR_SK_COUNT_DBG"), tv, lg);
 		time_end(h, KMR_TIME_COUNT, a, b);
 		HIPCHK(h, hipGetLastError());
 	}
@@ -2105,25 +2083,12 @@ int finalize_superkmer(kmr_handle *h, uint32_t min_depth) {
 	case 3: return finalize_superkmer_t<3>(h, min_depth); default: return finalize_superkmer_t<4>(h, min_depth); }
 }
 
+/* the device memory of group M of the handle goes back (kmr_handle's bases) */
+template <class M> void release(kmr_handle *h) { static_cast<M &>(*h) = M(); }
+
 void free_partition_state(kmr_handle *h) {
-	if (h->sk_state) hipFree(h->sk_state); h->sk_state = nullptr;
-	pool_free(h->l1);
-	if (h->l1_state) hipFree(h->l1_state); h->l1_state = nullptr; h->l1_state_bytes = 0; h->l1_state_dirty = false;
-	for (void *p : h->arena_overflow) hipFree(p);
-	h->arena_overflow.clear();
-	if (h->arena) hipFree(h->arena); h->arena = nullptr; h->arena_cap = h->arena_used = h->arena_want = 0;
-	if (h->work_counter) hipFree(h->work_counter); if (h->linear) hipFree(h->linear); if (h->tile_count) hipFree(h->tile_count);
-	if (h->kcap) hipFree(h->kcap); if (h->koff) hipFree(h->koff);
-	if (h->ucnt) hipFree(h->ucnt); if (h->ufirst) hipFree(h->ufirst); if (h->u_start) { hipFree(h->u_start); hipFree(h->u_end); hipFree(h->u_read); } if (h->umax) hipFree(h->umax);
-	for (int a = 0; a < 2; a++) for (int b = 0; b < 8; b++) { if (h->tb_stage[a][b]) hipFree(h->tb_stage[a][b]); h->tb_stage[a][b] = nullptr; h->tb_stage_cap[a][b] = 0; }
+	release<BuildMem>(h);
 	if (h->tb_copy_stream) { hipStreamDestroy(h->tb_copy_stream); h->tb_copy_stream = nullptr; for (int a = 0; a < 2; a++) { hipEventDestroy(h->tb_ready[a]); hipEventDestroy(h->tb_consumed[a]); h->tb_set_used[a] = false; } }
-	if (h->tb_bases) hipFree(h->tb_bases); if (h->tb_quals) hipFree(h->tb_quals); if (h->tb_rel) hipFree(h->tb_rel); if (h->tb_off) hipFree(h->tb_off); if (h->tb_len) hipFree(h->tb_len);
-	h->tb_bases = h->tb_quals = nullptr; h->tb_rel = h->tb_off = nullptr; h->tb_len = nullptr; h->tb_bases_cap = h->tb_quals_cap = h->tb_quals_filled = h->tb_n = 0; h->tb_quals_char = -1;
-	h->ucnt = nullptr; h->ufirst = nullptr; h->u_start = h->u_end = h->u_read = nullptr; h->umax = nullptr; h->ucnt_n = h->ufirst_n = h->units_n = 0;
-	if (h->uw_keys) hipFree(h->uw_keys); if (h->uw_vals) hipFree(h->uw_vals); if (h->us_keys) hipFree(h->us_keys); if (h->us_b8) hipFree(h->us_b8); if (h->us_pkt) hipFree(h->us_pkt);
-	if (h->ue) hipFree(h->ue); if (h->ue2) hipFree(h->ue2); h->ue = h->ue2 = nullptr; h->ue_cap = h->ue2_cap = 0;
-	h->us_pkt = nullptr; h->work_counter = nullptr; h->linear = nullptr; h->tile_count = nullptr; h->kcap = nullptr; h->koff = nullptr;
-	h->uw_keys = h->uw_vals = h->us_keys = h->us_b8 = nullptr; h->linear_cap = h->tile_cap = h->kcap_n = h->koff_n = h->uw_cap = h->us_cap = 0;
 }
 
 }  // namespace
@@ -2184,8 +2149,8 @@ int kmr_create(const kmr_config *cfg, kmr_handle **out) {
 		uint32_t lg = 16; while ((1ull << lg) < want && lg < 40) lg++;
 		h->log2cap = lg;
 		double P[256]; quality_table(P, cfg->min_quality_score, cfg->fastq_start_char);
-		if (dev_malloc((void **)&h->dP, sizeof(P)) != hipSuccess || dev_malloc((void **)&h->dstats, sizeof(DevStats)) != hipSuccess || dev_malloc((void **)&h->derr, 4) != hipSuccess) { rc = fail(nullptr, KMR_ERR_OOM, "hipMalloc failed"); break; }
-		hipMemcpy(h->dP, P, sizeof(P), hipMemcpyHostToDevice); hipMemset(h->dstats, 0, sizeof(DevStats)); hipMemset(h->derr, 0, 4);
+		if (h->dP.alloc(sizeof(P)) != hipSuccess || h->dstats.alloc(sizeof(DevStats)) != hipSuccess || h->derr.alloc(4) != hipSuccess) { rc = fail(nullptr, KMR_ERR_OOM, "hipMalloc failed"); break; }
+		hipMemcpy(h->dP.get<double>(), P, sizeof(P), hipMemcpyHostToDevice); hipMemset(h->dstats.get<DevStats>(), 0, sizeof(DevStats)); hipMemset(h->derr.get<uint32_t>(), 0, 4);
 		/* build_mode: 0 auto (streaming partition path unless EXT values), 1 table, 2 partition */
 		if (cfg->build_mode > 3) { rc = fail(nullptr, KMR_ERR_INVALID_ARG, "bad build_mode"); break; }
 		h->partition_mode = cfg->build_mode != 1;
@@ -2203,8 +2168,8 @@ int kmr_create(const kmr_config *cfg, kmr_handle **out) {
 			double Pk[256];
 			for (int cidx = 0; cidx < 256; cidx++) { double wv = 1.0; for (uint32_t jj = 0; jj < h->k; jj++) wv *= P[cidx]; Pk[cidx] = wv; }      /* the loop of buildWeightedKmers, src/KmerReadUtils.h:205-208 */
 			memcpy(h->hPk, Pk, sizeof(Pk)); memcpy(h->hP, P, sizeof(h->hP));
-			if (dev_malloc((void **)&h->dPk, 2 * sizeof(Pk)) != hipSuccess) { rc = fail(nullptr, KMR_ERR_OOM, "hipMalloc failed"); break; }
-			hipMemcpy(h->dPk, Pk, sizeof(Pk), hipMemcpyHostToDevice);
+			if (h->dPk.alloc(2 * sizeof(Pk)) != hipSuccess) { rc = fail(nullptr, KMR_ERR_OOM, "hipMalloc failed"); break; }
+			hipMemcpy(h->dPk.get<double>(), Pk, sizeof(Pk), hipMemcpyHostToDevice);
 			/* reciprocals for the chain's divide, usable only if multiply-and-correct reproduces the correctly rounded quotient of every
 			 * pair of table entries (all 256 x 256 are tried; the kernel divides otherwise) */
 			double Rp[256]; bool fast = true;
@@ -2215,11 +2180,11 @@ int kmr_create(const kmr_config *cfg, kmr_handle **out) {
 				if (std::fma(std::fma(-q0, P[b], P[a]), Rp[b], q0) != P[a] / P[b]) { fast = false; break; }
 			}
 			h->sk_fast_div = fast;
-			hipMemcpy(h->dPk + 256, Rp, sizeof(Rp), hipMemcpyHostToDevice);
+			hipMemcpy(h->dPk.get<double>() + 256, Rp, sizeof(Rp), hipMemcpyHostToDevice);
 		}
 		if (cfg->size_tracker && (!h->superkmer_mode || h->ext || cfg->world_size > 1)) { rc = fail(nullptr, KMR_ERR_UNSUPPORTED, "size_tracker: kept by the super-k-mer build (build_mode 0 / 3, direction-counting values, k >= 13) of a single partition"); break; }
 		if (!h->partition_mode) {
-			rc = alloc_table(h, h->log2cap, &h->slots, &h->extslots);
+			rc = alloc_table(h, h->log2cap, h->slots, h->extslots);
 			if (rc) { g_create_error = h->err; break; }
 		}
 		if (hipStreamSynchronize(h->stream) != hipSuccess) { rc = fail(nullptr, KMR_ERR_HIP, std::string("table clear failed: ") + hipGetErrorString(hipGetLastError())); break; }
@@ -2229,27 +2194,15 @@ int kmr_create(const kmr_config *cfg, kmr_handle **out) {
 	return KMR_OK;
 }
 
-static void exchange_free(kmr_handle *h);
+static void exchange_destroy_comm(kmr_handle *h);
 void kmr_destroy(kmr_handle *h) {
 	if (!h) return;
 	if (h->stream) hipStreamSynchronize(h->stream);
 	for (int which = 0; which < KMR_TIME_GROUPS; which++) for (auto &pr : h->pending_events[which]) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
-	if (h->slots) hipFree(h->slots); if (h->extslots) hipFree(h->extslots);
-	if (h->qrange) hipFree(h->qrange);
-	if (h->dP) hipFree(h->dP); if (h->dPk) hipFree(h->dPk); if (h->dstats) hipFree(h->dstats); if (h->derr) hipFree(h->derr);
-	free_map(h->weak); free_map(h->sing);
+	release<HandleMem>(h);
 	free_partition_state(h);
-	if (h->scan_sums) hipFree(h->scan_sums);
-	if (h->score_buf) hipFree(h->score_buf);
-	if (h->lut) hipFree(h->lut);
-	if (h->xo_dev) hipFree(h->xo_dev);
-	if (h->trk) hipFree(h->trk);
-	if (h->adopt_buf) hipFree(h->adopt_buf);
-	if (h->sk_fine_state) hipFree(h->sk_fine_state);
-	if (h->d_uni) hipFree(h->d_uni);
-	if (h->early.ue) hipFree(h->early.ue); if (h->early.cursor) hipFree(h->early.cursor); if (h->early.fc) hipFree(h->early.fc);
-	if (h->ix_start) hipFree(h->ix_start); if (h->ix_keys) hipFree(h->ix_keys); if (h->ix_counts) hipFree(h->ix_counts); if (h->scratch_stats) hipFree(h->scratch_stats);
-	exchange_free(h);
+	exchange_destroy_comm(h);
+	release<ExchangeMem>(h);      /* what the communicator used */
 	if (h->stream) hipStreamDestroy(h->stream);
 	delete h;
 }
@@ -2271,26 +2224,26 @@ int kmr_reset(kmr_handle *h) {
 	clear_map(h->weak); clear_map(h->sing);      /* empty maps, allocations kept (reset(false)) */
 	int rc = 0;
 	if (h->partition_mode) {
-		if (h->l1.head) HIPCHK(h, hipMemsetAsync(h->l1.head, 0, 4, h->stream));
+		if (h->l1.head) HIPCHK(h, hipMemsetAsync(h->l1.head.get<unsigned int>(), 0, 4, h->stream));
 		h->l1.used_ub = 0;
 		h->inserted_records = 0;
 		h->qual_mixed = false;
 		h->sk_uni_w = SK_UNI_NONE; h->sk_uni_mixed = false; h->peer_uni_w = SK_UNI_NONE; h->peer_uni_mixed = false;
 		h->xr_lo = 0; h->xr_hi = ~0ull; h->early.active = false;
-		if (h->d_uni) { const uint32_t init[2] = {SK_UNI_NONE, 0u}; HIPCHK(h, hipMemcpyAsync(h->d_uni, init, 8, hipMemcpyHostToDevice, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream)); }
-		if (h->sk_state) hipLaunchKernelGGL(sk_state_init_kernel, dim3(grid_for(sk_list_count(h->sk_bits))), dim3(256), 0, h->stream, h->sk_state, sk_list_count(h->sk_bits));
+		if (h->d_uni) { const uint32_t init[2] = {SK_UNI_NONE, 0u}; HIPCHK(h, hipMemcpyAsync(h->d_uni.get<uint32_t>(), init, 8, hipMemcpyHostToDevice, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream)); }
+		if (h->sk_state) hipLaunchKernelGGL(sk_state_init_kernel, dim3(grid_for(sk_list_count(h->sk_bits))), dim3(256), 0, h->stream, h->sk_state.get<unsigned long long>(), sk_list_count(h->sk_bits));
 		if (h->l1_state) {      /* what an unfinished build kept back is dropped with its pool */
-			hipLaunchKernelGGL(partition_state_init_kernel, dim3(partition_blocks(h)), dim3(256), 0, h->stream, h->l1_state,
-			                   h->l1_state_bytes / (size_t)partition_blocks(h), h->bits1, (uint32_t)partition_blocks(h));
+			hipLaunchKernelGGL(partition_state_init_kernel, dim3(partition_blocks(h)), dim3(256), 0, h->stream, h->l1_state.get<uint8_t>(),
+			                   h->l1_state.cap() / (size_t)partition_blocks(h), h->bits1, (uint32_t)partition_blocks(h));
 			h->l1_state_dirty = false;
 		}
 	} else {
-		if (!h->slots) rc = alloc_table(h, h->log2cap, &h->slots, &h->extslots);
-		else rc = clear_table_any(h, h->slots, h->extslots, h->log2cap);
+		if (!h->slots) rc = alloc_table(h, h->log2cap, h->slots, h->extslots);
+		else rc = clear_table_any(h, h->slots.get(), h->extslots.get<ExtSlot>(), h->log2cap);
 		if (rc) return rc;
 	}
-	HIPCHK(h, hipMemsetAsync(h->dstats, 0, sizeof(DevStats), h->stream));
-	HIPCHK(h, hipMemsetAsync(h->derr, 0, 4, h->stream));
+	HIPCHK(h, hipMemsetAsync(h->dstats.get<DevStats>(), 0, sizeof(DevStats), h->stream));
+	HIPCHK(h, hipMemsetAsync(h->derr.get<uint32_t>(), 0, 4, h->stream));
 	memset(&h->stats, 0, sizeof(h->stats));
 	h->occupied = h->pending_kmers = 0; h->stream_base = 0; h->reads = 0; h->subtracted = 0; h->xc_job_bases = 0; h->xc_bytes_to_peers = 0;
 	h->trk_n = 0; h->trk_elems.clear();
@@ -2302,8 +2255,7 @@ int kmr_release_table(kmr_handle *h) {
 	if (!h) return KMR_ERR_INVALID_ARG;
 	if (!h->finalized) return fail(h, KMR_ERR_STATE, "kmr_release_table before kmr_finalize");
 	hipSetDevice(h->device);
-	if (h->slots) { hipFree(h->slots); h->slots = nullptr; }
-	if (h->extslots) { hipFree(h->extslots); h->extslots = nullptr; }
+	h->slots.reset(); h->extslots.reset();
 	if (h->partition_mode) free_partition_state(h);
 	return KMR_OK;
 }
@@ -2361,6 +2313,7 @@ int kmr_build_info(kmr_handle *h, const char *what, double *value) {
 	else if (k == "superkmer_window") *value = (double)h->sk_win;
 	else if (k == "early_lists") *value = (double)h->last_early_hi;
 	else if (k == "early_entries") *value = (double)h->last_early_entries;
+	else if (k == "device_blocks_live") *value = (double)g_blocks_live.load();
 	else return fail(h, KMR_ERR_INVALID_ARG, "unknown build figure '" + k + "'");
 	return KMR_OK;
 }
@@ -2389,14 +2342,13 @@ int kmr_add_reads_dev(kmr_handle *h, const void *dev_bases, const void *dev_qual
 
 /* one piece of a host batch onto the device: staging set `set` of the handle (grow-only), the copy on the handle's copy stream */
 static hipError_t tb_stage_copy(kmr_handle *h, int set, int which, const void *src, size_t bytes, void **dst) {
-	uint8_t *&buf = h->tb_stage[set][which]; size_t &cap = h->tb_stage_cap[set][which];
-	if (cap < bytes + 64) {
-		if (buf) { hipError_t e0 = hipStreamSynchronize(h->stream); if (e0 != hipSuccess) return e0; hipFree(buf); buf = nullptr; cap = 0; }
-		hipError_t e = dev_malloc((void **)&buf, bytes + bytes / 8 + 4096); if (e != hipSuccess) return e;
-		cap = bytes + bytes / 8 + 4096 - 64;
+	DevBuf &buf = h->tb_stage[set][which];
+	if (buf.cap() < bytes + 128) {      /* the piece, 64 bytes of padding behind it and 64 to spare */
+		if (buf) { hipError_t e0 = hipStreamSynchronize(h->stream); if (e0 != hipSuccess) return e0; }
+		hipError_t e = buf.alloc(bytes + bytes / 8 + 4096); if (e != hipSuccess) return e;
 	}
-	*dst = buf;
-	return bytes ? hipMemcpyAsync(buf, src, bytes, hipMemcpyHostToDevice, h->tb_copy_stream) : hipSuccess;
+	*dst = buf.get();
+	return bytes ? hipMemcpyAsync(buf.get(), src, bytes, hipMemcpyHostToDevice, h->tb_copy_stream) : hipSuccess;
 }
 static int tb_pipeline_ready(kmr_handle *h) {
 	if (h->tb_copy_stream) return 0;
@@ -2466,29 +2418,29 @@ int kmr_add_reads_twobit_dev(kmr_handle *h, const void *dev_twobit, const void *
 	/* grow-only scratch of the handle; everything below is ordered on the handle's stream, so the next call's unpack waits for
 	 * this call's extraction */
 	const bool direct = sk_packed_direct_ok(h, dev_quals != nullptr, uniform_quality);
-	if (!direct && h->tb_bases_cap < total_bases + 64) {
-		if (h->tb_bases) { HIPCHK(h, hipStreamSynchronize(h->stream)); hipFree(h->tb_bases); h->tb_bases = nullptr; h->tb_bases_cap = 0; }
-		HIPCHK(h, dev_malloc((void **)&h->tb_bases, total_bases + 64)); h->tb_bases_cap = total_bases + 64;
-		HIPCHK(h, hipMemsetAsync(h->tb_bases, 0, total_bases + 64, h->stream));
+	if (!direct && h->tb_bases.cap() < total_bases + 64) {
+		if (h->tb_bases) HIPCHK(h, hipStreamSynchronize(h->stream));
+		HIPCHK(h, h->tb_bases.alloc(total_bases + 64));
+		HIPCHK(h, hipMemsetAsync(h->tb_bases.get<uint8_t>(), 0, total_bases + 64, h->stream));
 	}
-	if (h->tb_n < n_reads + 1) {
-		if (h->tb_rel) { HIPCHK(h, hipStreamSynchronize(h->stream)); hipFree(h->tb_rel); hipFree(h->tb_off); hipFree(h->tb_len); h->tb_rel = h->tb_off = nullptr; h->tb_len = nullptr; h->tb_n = 0; }
-		HIPCHK(h, dev_malloc((void **)&h->tb_rel, 8 * (n_reads + 1))); HIPCHK(h, dev_malloc((void **)&h->tb_off, 8 * (n_reads + 1))); HIPCHK(h, dev_malloc((void **)&h->tb_len, 4 * (n_reads + 1)));
-		h->tb_n = n_reads + 1;
+	if (h->tb_len.cap() < 4 * (n_reads + 1)) {      /* (tb_len is allocated last) */
+		if (h->tb_len) HIPCHK(h, hipStreamSynchronize(h->stream));
+		h->tb_rel.reset(); h->tb_off.reset(); h->tb_len.reset();
+		HIPCHK(h, h->tb_rel.alloc(8 * (n_reads + 1))); HIPCHK(h, h->tb_off.alloc(8 * (n_reads + 1))); HIPCHK(h, h->tb_len.alloc(4 * (n_reads + 1)));
 	}
 	const uint64_t *tboff = (const uint64_t *)dev_twobit_offsets;
 	if (!tboff) {      /* every read on the byte behind the one before it: ceil(L / 4) bytes each */
-		hipLaunchKernelGGL(twobit_bytes_kernel, dim3(grid_for(n_reads)), dim3(256), 0, h->stream, (const uint64_t *)dev_offsets, n_reads, h->tb_len);
+		hipLaunchKernelGGL(twobit_bytes_kernel, dim3(grid_for(n_reads)), dim3(256), 0, h->stream, (const uint64_t *)dev_offsets, n_reads, h->tb_len.get<uint32_t>());
 		HIPCHK(h, hipGetLastError());
-		int rc = exclusive_scan(h, h->tb_len, n_reads, h->tb_off); if (rc) return rc;
-		tboff = h->tb_off;
+		int rc = exclusive_scan(h, h->tb_len.get<uint32_t>(), n_reads, h->tb_off.get<uint64_t>()); if (rc) return rc;
+		tboff = h->tb_off.get<uint64_t>();
 	}
 	if (direct) {
 		/* the lean extraction stages the packed bytes as they are: no unpacked copy of the batch, no quality bytes */
-		hipLaunchKernelGGL(offsets_rel_kernel, dim3(grid_for(n_reads + 1)), dim3(256), 0, h->stream, (const uint64_t *)dev_offsets, n_reads, h->tb_rel);
+		hipLaunchKernelGGL(offsets_rel_kernel, dim3(grid_for(n_reads + 1)), dim3(256), 0, h->stream, (const uint64_t *)dev_offsets, n_reads, h->tb_rel.get<uint64_t>());
 		HIPCHK(h, hipGetLastError());
 		if (h->stream_base + total_bases > MAX_STREAM_ORDINAL) return fail(h, KMR_ERR_CAPACITY, "more than 2^40 input bases on one handle");
-		ReadsView rv; rv.bases = nullptr; rv.quals = nullptr; rv.offsets = h->tb_rel; rv.discarded = (const uint8_t *)dev_discarded; rv.n_reads = n_reads;
+		ReadsView rv; rv.bases = nullptr; rv.quals = nullptr; rv.offsets = h->tb_rel.get<uint64_t>(); rv.discarded = (const uint8_t *)dev_discarded; rv.n_reads = n_reads;
 		rv.stream_base = h->stream_base; rv.first_read_idx = first_global_read_idx; rv.u_start = rv.u_end = rv.u_read = nullptr; rv.n_units = 0;
 		SkPacked pkd; pkd.bytes = (const uint8_t *)dev_twobit; pkd.off = tboff; pkd.mk_off = (const uint64_t *)dev_markup_offsets; pkd.mk_pos = (const uint32_t *)dev_markup_pos; pkd.mk_char = (const uint8_t *)dev_markup_char;
 		h->packed_direct = &pkd; h->uniform_q_hint = uniform_quality ? uniform_quality : -1;
@@ -2498,28 +2450,28 @@ int kmr_add_reads_twobit_dev(kmr_handle *h, const void *dev_twobit, const void *
 		return rc;
 	}
 	hipLaunchKernelGGL(twobit_unpack_kernel, dim3((unsigned)std::min<uint64_t>((n_reads + 255) / 256, (uint64_t)num_cus(h) * 32)), dim3(256), 0, h->stream,
-	                   (const uint8_t *)dev_twobit, tboff, (const uint64_t *)dev_offsets, n_reads, h->tb_bases, h->tb_rel);
+	                   (const uint8_t *)dev_twobit, tboff, (const uint64_t *)dev_offsets, n_reads, h->tb_bases.get<uint8_t>(), h->tb_rel.get<uint64_t>());
 	HIPCHK(h, hipGetLastError());
 	if (dev_markup_offsets) {
 		hipLaunchKernelGGL(twobit_markup_kernel, dim3(grid_for(n_reads)), dim3(256), 0, h->stream, (const uint64_t *)dev_markup_offsets, (const uint32_t *)dev_markup_pos,
-		                   (const uint8_t *)dev_markup_char, (const uint64_t *)h->tb_rel, n_reads, h->tb_bases);
+		                   (const uint8_t *)dev_markup_char, (const uint64_t *)h->tb_rel.get<uint64_t>(), n_reads, h->tb_bases.get<uint8_t>());
 		HIPCHK(h, hipGetLastError());
 	}
 	const void *q = dev_quals;
 	if (!dev_quals && uniform_quality) {
-		if (h->tb_quals_cap < total_bases + 64) {
-			if (h->tb_quals) { HIPCHK(h, hipStreamSynchronize(h->stream)); hipFree(h->tb_quals); h->tb_quals = nullptr; h->tb_quals_cap = 0; }
-			HIPCHK(h, dev_malloc((void **)&h->tb_quals, total_bases + 64)); h->tb_quals_cap = total_bases + 64; h->tb_quals_filled = 0; h->tb_quals_char = -1;
+		if (h->tb_quals.cap() < total_bases + 64) {
+			if (h->tb_quals) HIPCHK(h, hipStreamSynchronize(h->stream));
+			HIPCHK(h, h->tb_quals.alloc(total_bases + 64)); h->tb_quals_filled = 0; h->tb_quals_char = -1;
 		}
 		if (h->tb_quals_char != uniform_quality || h->tb_quals_filled < total_bases) {      /* (a buffer the last call filled with the same character stands) */
-			HIPCHK(h, hipMemsetAsync(h->tb_quals, uniform_quality, h->tb_quals_cap, h->stream));
-			h->tb_quals_char = uniform_quality; h->tb_quals_filled = h->tb_quals_cap;
+			HIPCHK(h, hipMemsetAsync(h->tb_quals.get(), uniform_quality, h->tb_quals.cap(), h->stream));
+			h->tb_quals_char = uniform_quality; h->tb_quals_filled = h->tb_quals.cap();
 		}
-		q = h->tb_quals;
+		q = h->tb_quals.get<uint8_t>();
 	}
 	/* (dev_quals[0] is the quality of the call's first base: the unpacked batch and its offsets start there too) */
 	h->uniform_q_hint = (!dev_quals && uniform_quality) ? uniform_quality : -1;
-	const int rc = kmr_add_reads_dev(h, h->tb_bases, q, h->tb_rel, n_reads, total_bases, first_global_read_idx, dev_discarded);
+	const int rc = kmr_add_reads_dev(h, h->tb_bases.get<uint8_t>(), q, h->tb_rel.get<uint64_t>(), n_reads, total_bases, first_global_read_idx, dev_discarded);
 	h->uniform_q_hint = -1;
 	return rc;
 }
@@ -2606,19 +2558,19 @@ int kmr_lookup(kmr_handle *h, const uint8_t *packed, uint64_t n, uint32_t *count
 /* kmr_lookup_reads and kmr_lookup_reads_weighted: one output element (u32 count or f64 weight) per k-mer position */
 static int lookup_reads_host(kmr_handle *h, const char *bases, const uint64_t *offsets, uint64_t n_reads, void *out, const uint64_t *out_offsets, bool weighted) {
 	hipSetDevice(h->device);
-	StagedReads s; uint64_t total = 0;
-	int rc = stage_reads(h, bases, nullptr, offsets, n_reads, nullptr, s, total);
-	if (rc) { s.release(); return rc; }
+	DevBuf sb, so;
+	int rc = stage_reads(h, bases, offsets, n_reads, sb, so); if (rc) return rc;
 	/* size of the output = last offset + k-mers of the last read */
 	uint64_t outN = 0;
 	for (uint64_t r = 0; r < n_reads; r++) { uint64_t L = offsets[r + 1] - offsets[r]; uint64_t nk = L >= h->k ? L - h->k + 1 : 0; outN = std::max(outN, out_offsets[r] + nk); }
 	const uint64_t eb = weighted ? 8 : 4;
-	void *dout; uint64_t *doff;
-	HIPCHK(h, dev_malloc((void **)&dout, std::max<uint64_t>(8, eb * outN))); HIPCHK(h, dev_malloc((void **)&doff, 8 * n_reads));
+	DevBuf doutb, doffb;
+	HIPCHK(h, doutb.alloc(std::max<uint64_t>(8, eb * outN))); HIPCHK(h, doffb.alloc(8 * n_reads));
+	void *dout = doutb.get(); uint64_t *doff = doffb.get<uint64_t>();
 	HIPCHK(h, hipMemsetAsync(dout, 0, eb * outN, h->stream));
 	HIPCHK(h, hipMemcpyAsync(doff, out_offsets, 8 * n_reads, hipMemcpyHostToDevice, h->stream));
-	ReadsView rv; rv.bases = s.b; rv.quals = nullptr; rv.offsets = s.o; rv.discarded = nullptr; rv.n_reads = n_reads; rv.stream_base = 0; rv.first_read_idx = 0; rv.u_start = rv.u_end = rv.u_read = nullptr; rv.n_units = 0;
-	{ int urc = prepare_units(h, rv); if (urc) { s.release(); return urc; } }
+	ReadsView rv; rv.bases = sb.get<uint8_t>(); rv.quals = nullptr; rv.offsets = so.get<uint64_t>(); rv.discarded = nullptr; rv.n_reads = n_reads; rv.stream_base = 0; rv.first_read_idx = 0; rv.u_start = rv.u_end = rv.u_read = nullptr; rv.n_units = 0;
+	rc = prepare_units(h, rv); if (rc) return rc;
 	if (weighted) {
 		double *d = (double *)dout;
 		switch (h->W) { case 1: rc = lookup_reads_weighted_t<1>(h, rv, d, doff); break; case 2: rc = lookup_reads_weighted_t<2>(h, rv, d, doff); break;
@@ -2630,7 +2582,6 @@ static int lookup_reads_host(kmr_handle *h, const char *bases, const uint64_t *o
 	}
 	if (!rc) { HIPCHK(h, hipMemcpyAsync(out, dout, eb * outN, hipMemcpyDeviceToHost, h->stream)); rc = sync_state(h); }
 	else hipStreamSynchronize(h->stream);
-	hipFree(dout); hipFree(doff); s.release();
 	return rc;
 }
 int kmr_lookup_reads(kmr_handle *h, const char *bases, const uint64_t *offsets, uint64_t n_reads, uint32_t *counts_out, const uint64_t *out_offsets) {
@@ -2667,20 +2618,20 @@ template <int W> int sk_index_t(kmr_handle *h) {
 	if (h->ix_gen == h->map_gen && h->ix_start) return 0;
 	const uint64_t nl = sk_list_count(h->sk_bits), n = h->weak.n;
 	const uint32_t vw = h->ext ? 15 : 3;
-	if (h->ix_lists != nl) { if (h->ix_start) hipFree(h->ix_start); h->ix_start = nullptr; HIPCHK(h, dev_malloc((void **)&h->ix_start, 8 * (nl + 1))); h->ix_lists = nl; }
-	if (h->ix_cap < n) {
-		if (h->ix_keys) hipFree(h->ix_keys); if (h->ix_counts) hipFree(h->ix_counts); h->ix_keys = nullptr; h->ix_counts = nullptr; h->ix_cap = 0;
-		HIPCHK(h, dev_malloc((void **)&h->ix_keys, 8ull * W * n)); HIPCHK(h, dev_malloc((void **)&h->ix_counts, 4 * n)); h->ix_cap = n;
+	if (h->ix_lists != nl) { h->ix_lists = 0; HIPCHK(h, h->ix_start.alloc(8 * (nl + 1))); h->ix_lists = nl; }
+	if (h->ix_counts.cap() < 4 * n) {      /* (ix_counts is allocated last) */
+		h->ix_keys.reset(); h->ix_counts.reset();
+		HIPCHK(h, h->ix_keys.alloc(8ull * W * n)); HIPCHK(h, h->ix_counts.alloc(4 * n));
 	}
 	uint32_t *elist = nullptr, *hist = nullptr;
 	int rc = arena_get(h, &elist, n); if (rc) return rc;
 	rc = arena_get(h, &hist, nl); if (rc) return rc;
 	HIPCHK(h, hipMemsetAsync(hist, 0, 4 * nl, h->stream));
-	hipLaunchKernelGGL(sk_index_hist_kernel<W>, dim3(grid_for(n)), dim3(256), 0, h->stream, (const uint64_t *)h->weak.keys, n, h->sk_m, h->sk_off, h->sk_win, h->sk_bits, elist, hist);
+	hipLaunchKernelGGL(sk_index_hist_kernel<W>, dim3(grid_for(n)), dim3(256), 0, h->stream, (const uint64_t *)h->weak.keys.get<uint64_t>(), n, h->sk_m, h->sk_off, h->sk_win, h->sk_bits, elist, hist);
 	HIPCHK(h, hipGetLastError());
-	rc = exclusive_scan(h, hist, nl, h->ix_start); if (rc) return rc;
+	rc = exclusive_scan(h, hist, nl, h->ix_start.get<uint64_t>()); if (rc) return rc;
 	HIPCHK(h, hipMemsetAsync(hist, 0, 4 * nl, h->stream));
-	hipLaunchKernelGGL(sk_index_scatter_kernel<W>, dim3(grid_for(n)), dim3(256), 0, h->stream, (const uint64_t *)h->weak.keys, (const uint32_t *)h->weak.vals, vw, n, elist, h->ix_start, hist, h->ix_keys, h->ix_counts);
+	hipLaunchKernelGGL(sk_index_scatter_kernel<W>, dim3(grid_for(n)), dim3(256), 0, h->stream, (const uint64_t *)h->weak.keys.get<uint64_t>(), (const uint32_t *)h->weak.vals.get<uint32_t>(), vw, n, elist, h->ix_start.get<uint64_t>(), hist, h->ix_keys.get<uint64_t>(), h->ix_counts.get<uint32_t>());
 	HIPCHK(h, hipGetLastError());
 	h->ix_gen = h->map_gen;
 	return 0;
@@ -2690,26 +2641,26 @@ template <int W> int lookup_stream_t(kmr_handle *h, const ReadsView &rvAll, uint
 	if (!h->sk_state) {      /* a handle that was not built on the lists (loaded image, other build mode): lists sized for this batch */
 		uint32_t bits = 6; while (bits < 24 && (total_bases >> bits) > h->tune.target_list / 2 + 200) bits++;
 		h->sk_bits = bits;
-		HIPCHK(h, dev_malloc((void **)&h->sk_state, 8ull << bits));
+		HIPCHK(h, h->sk_state.alloc(8ull << bits));
 	}
-	if (!h->scratch_stats) HIPCHK(h, dev_malloc((void **)&h->scratch_stats, sizeof(DevStats)));
+	rc = h->scratch_stats.reserve(h, "scratch_stats", sizeof(DevStats)); if (rc) return rc;
 	rc = sk_index_t<W>(h); if (rc) return rc;
 	const uint64_t nl = sk_list_count(h->sk_bits);
-	hipLaunchKernelGGL(sk_state_init_kernel, dim3(grid_for(nl)), dim3(256), 0, h->stream, h->sk_state, nl);
-	if (h->l1.head) HIPCHK(h, hipMemsetAsync(h->l1.head, 0, 4, h->stream));
+	hipLaunchKernelGGL(sk_state_init_kernel, dim3(grid_for(nl)), dim3(256), 0, h->stream, h->sk_state.get<unsigned long long>(), nl);
+	if (h->l1.head) HIPCHK(h, hipMemsetAsync(h->l1.head.get<unsigned int>(), 0, 4, h->stream));
 	h->l1.used_ub = 0;
 	ReadsView rv = rvAll;
 	rc = prepare_units(h, rv); if (rc) return rc;
 	rc = pool_reserve(h, h->l1, total_bases / SK_CHUNK_G + nl + (uint64_t)num_cus(h) * SK_EXTRACT_WAVES_PER_CU * 130 + 64, true); if (rc) return rc;
 	/* every k-mer without an N is asked for: no qualities (weight 1, or 0 with an N), no filters, nothing added to the handle's counters */
 	DevParams dp = dev_params(h);
-	dp.min_weight = 0.5f; dp.subsample = 1; dp.world = 1; dp.num_parts = 1; dp.sub_wnb = 0; dp.sub_snb = 0; dp.stats = h->scratch_stats;
+	dp.min_weight = 0.5f; dp.subsample = 1; dp.world = 1; dp.num_parts = 1; dp.sub_wnb = 0; dp.sub_snb = 0; dp.stats = h->scratch_stats.get<DevStats>();
 	SkParams sp = sk_params(h); sp.keep_all_owners = 1; sp.track = nullptr;
 	if (W > 1 && h->sk_win == 32) rc = (!rv.quals && !h->tune.no_lean_extract) ? launch_sk_extract_lean<W, (W > 1 ? 32 : 16)>(h, rv, sp, 1.0f, &dp) : launch_sk_extract<W, (W > 1 ? 32 : 16), false>(h, rv, sp, &dp);
 	else if (!rv.quals && !h->tune.no_lean_extract) rc = h->sk_win == 16 ? launch_sk_extract_lean<W, 16>(h, rv, sp, 1.0f, &dp) : (h->sk_win == 8 ? launch_sk_extract_lean<W, 8>(h, rv, sp, 1.0f, &dp) : launch_sk_extract_lean<W, 4>(h, rv, sp, 1.0f, &dp));
 	else rc = h->sk_win == 16 ? launch_sk_extract<W, 16, false>(h, rv, sp, &dp) : (h->sk_win == 8 ? launch_sk_extract<W, 8, false>(h, rv, sp, &dp) : launch_sk_extract<W, 4, false>(h, rv, sp, &dp));
 	if (rc) return rc;
-	hipLaunchKernelGGL(sk_close_kernel, dim3(grid_for(nl)), dim3(256), 0, h->stream, h->sk_state, nl, h->l1.chunk_count, h->l1.cap);
+	hipLaunchKernelGGL(sk_close_kernel, dim3(grid_for(nl)), dim3(256), 0, h->stream, h->sk_state.get<unsigned long long>(), nl, h->l1.chunk_count.get<uint32_t>(), h->l1.cap);
 	HIPCHK(h, hipGetLastError());
 	uint64_t *ls = nullptr, *lc = nullptr; uint32_t nch = 0;
 	rc = build_csr(h, h->l1, nl, 0, &ls, &lc, &nch); if (rc) return rc;
@@ -2733,13 +2684,13 @@ template <int W> int lookup_stream_t(kmr_handle *h, const ReadsView &rvAll, uint
 		if (hn > cap) return fail(h, KMR_ERR_CAPACITY, "long-list work items (internal sizing error)");
 		n_items = hn;
 	}
-	hipLaunchKernelGGL(kern, dim3(grid), dim3(COUNT_THREADS), smem, h->stream, pool_view(h, h->l1), ls, lc, nl, h->k, h->ix_start, h->ix_keys, h->ix_counts, position_counts, out_n, h->work_counter,
+	hipLaunchKernelGGL(kern, dim3(grid), dim3(COUNT_THREADS), smem, h->stream, pool_view(h, h->l1), ls, lc, nl, h->k, h->ix_start.get<uint64_t>(), h->ix_keys.get<uint64_t>(), h->ix_counts.get<uint32_t>(), position_counts, out_n, h->work_counter.get<unsigned int>(),
 	                   (const uint64_t *)nullptr, (const uint64_t *)nullptr, (const uint32_t *)nullptr, (uint64_t)0, n_items ? LONG_CHUNKS : (uint64_t)0);
 	HIPCHK(h, hipGetLastError());
 	if (n_items) {
 		rc = zero_work_counter(h); if (rc) return rc;
-		hipLaunchKernelGGL(kern, dim3((unsigned)std::min<uint64_t>((uint64_t)num_cus(h) * 4, n_items)), dim3(COUNT_THREADS), smem, h->stream, pool_view(h, h->l1), ls, lc, nl, h->k, h->ix_start, h->ix_keys, h->ix_counts,
-		                   position_counts, out_n, h->work_counter, (const uint64_t *)ic0, (const uint64_t *)ic1, (const uint32_t *)il, n_items, (uint64_t)0);
+		hipLaunchKernelGGL(kern, dim3((unsigned)std::min<uint64_t>((uint64_t)num_cus(h) * 4, n_items)), dim3(COUNT_THREADS), smem, h->stream, pool_view(h, h->l1), ls, lc, nl, h->k, h->ix_start.get<uint64_t>(), h->ix_keys.get<uint64_t>(), h->ix_counts.get<uint32_t>(),
+		                   position_counts, out_n, h->work_counter.get<unsigned int>(), (const uint64_t *)ic0, (const uint64_t *)ic1, (const uint32_t *)il, n_items, (uint64_t)0);
 		HIPCHK(h, hipGetLastError());
 	}
 	return 0;
@@ -2757,14 +2708,11 @@ static int score_reads_core(kmr_handle *h, const uint8_t *s_b, const uint64_t *s
 	int rc = 0;
 	ReadsView rv; rv.bases = s_b; rv.quals = nullptr; rv.offsets = s_o; rv.discarded = nullptr; rv.n_reads = n_reads; rv.stream_base = 0; rv.first_read_idx = 0; rv.u_start = rv.u_end = rv.u_read = nullptr; rv.n_units = 0;
 	/* per-read k-mer counts and their exclusive scan on the device (no host pass over the reads); one grow-only block for
-	 * every temporary (a hipFree of the ~GB count array costs more than the scoring) */
+	 * every temporary (freeing the ~GB count array costs more than the scoring) */
 	auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
 	const size_t fixed = al(4 * (n_reads + 1)) + al(8 * (n_reads + 1)) + 3 * al(4 * n_reads) + al(n_reads);
-	if (h->score_buf_bytes < fixed) {
-		if (h->score_buf) { HIPCHK(h, hipStreamSynchronize(h->stream)); hipFree(h->score_buf); h->score_buf = nullptr; h->score_buf_bytes = 0; }
-		HIPCHK(h, dev_malloc((void **)&h->score_buf, fixed + fixed / 4)); h->score_buf_bytes = fixed + fixed / 4;
-	}
-	uint8_t *p = h->score_buf;
+	rc = h->score_buf.reserve(h, "score_buf", fixed, fixed + fixed / 4); if (rc) return rc;
+	uint8_t *p = h->score_buf.get<uint8_t>();
 	uint32_t *dkc = (uint32_t *)p; p += al(4 * (n_reads + 1));
 	uint64_t *dcoff = (uint64_t *)p;
 	/* counts per k-mer: as a streaming pass over minimizer lists (indexed by the k-mer's base position: the reads' own offsets are the
@@ -2780,13 +2728,13 @@ static int score_reads_core(kmr_handle *h, const uint8_t *s_b, const uint64_t *s
 		HIPCHK(h, hipMemcpy(&outN, dcoff + n_reads, 8, hipMemcpyDeviceToHost));
 	}
 	const size_t need = fixed + al(std::max<uint64_t>(8, 4 * outN));
-	if (h->score_buf_bytes < need) {         /* grow, keeping the scan */
-		uint8_t *nbuf; HIPCHK(h, dev_malloc((void **)&nbuf, need + need / 8));
-		HIPCHK(h, hipMemcpy(nbuf, h->score_buf, al(4 * (n_reads + 1)) + al(8 * (n_reads + 1)), hipMemcpyDeviceToDevice));
+	if (h->score_buf.cap() < need) {         /* grow, keeping the scan */
+		DevBuf nbuf; HIPCHK(h, nbuf.alloc(need + need / 8));
+		HIPCHK(h, hipMemcpy(nbuf.get(), h->score_buf.get(), al(4 * (n_reads + 1)) + al(8 * (n_reads + 1)), hipMemcpyDeviceToDevice));
 		HIPCHK(h, hipDeviceSynchronize());
-		hipFree(h->score_buf); h->score_buf = nbuf; h->score_buf_bytes = need + need / 8;
+		h->score_buf = std::move(nbuf);
 	}
-	p = h->score_buf + al(4 * (n_reads + 1));
+	p = h->score_buf.get<uint8_t>() + al(4 * (n_reads + 1));
 	dcoff = (uint64_t *)p; p += al(8 * (n_reads + 1));
 	uint32_t *dto = (uint32_t *)p; p += al(4 * n_reads);
 	uint32_t *dtl = (uint32_t *)p; p += al(4 * n_reads);
@@ -2819,13 +2767,9 @@ int kmr_score_reads(kmr_handle *h, const char *bases, const uint64_t *offsets, u
 	if (!h->finalized) return fail(h, KMR_ERR_STATE, "kmr_score_reads before kmr_finalize");
 	if (n_reads == 0) return KMR_OK;
 	hipSetDevice(h->device);
-	StagedReads s; uint64_t total = 0;
-	int rc = stage_reads(h, bases, nullptr, offsets, n_reads, nullptr, s, total);
-	if (!rc) {
-		rc = score_reads_core(h, s.b, s.o, n_reads, minimum_kmer_score, scoring_type, trim_offset, trim_length, score, was_trimmed);
-	}
-	s.release();
-	return rc;
+	DevBuf sb, so;
+	int rc = stage_reads(h, bases, offsets, n_reads, sb, so); if (rc) return rc;
+	return score_reads_core(h, sb.get<uint8_t>(), so.get<uint64_t>(), n_reads, minimum_kmer_score, scoring_type, trim_offset, trim_length, score, was_trimmed);
 }
 /* the same on a device-resident read batch (kmr_ingest_fastq): FASTQ text -> reads -> spectrum -> trim/score without the
  * reads ever being staged by the host */
@@ -2837,7 +2781,7 @@ int kmr_score_read_batch(kmr_handle *h, const kmr_reads *r, double minimum_kmer_
 	if (r->device != h->device) return fail(h, KMR_ERR_INVALID_ARG, "read batch lives on another device");
 	if (r->n == 0) return KMR_OK;
 	hipSetDevice(h->device);
-	return score_reads_core(h, r->bases, r->offsets, r->n, minimum_kmer_score, scoring_type, trim_offset, trim_length, score, was_trimmed);
+	return score_reads_core(h, r->bases.get<uint8_t>(), r->offsets.get<uint64_t>(), r->n, minimum_kmer_score, scoring_type, trim_offset, trim_length, score, was_trimmed);
 }
 
 static DevMap *map_of(kmr_handle *h, int which) {
@@ -2869,7 +2813,7 @@ int kmr_write_image(kmr_handle *h, int which, void *dst, uint64_t capacity) {
 		return KMR_OK;
 	}
 	rc = build_image(h, *m, which == KMR_MAP_WEAK); if (rc) return rc;
-	HIPCHK(h, hipMemcpy(dst, m->image, need, hipMemcpyDeviceToHost));
+	HIPCHK(h, hipMemcpy(dst, m->image.get(), need, hipMemcpyDeviceToHost));
 	return KMR_OK;
 }
 
@@ -2885,7 +2829,7 @@ int kmr_load_image(kmr_handle *h, int which, const void *src, uint64_t len) {
 	case 3: rc = load_image_t<3>(h, *m, which == KMR_MAP_WEAK, (const uint8_t *)src, len); break;
 	default: rc = load_image_t<4>(h, *m, which == KMR_MAP_WEAK, (const uint8_t *)src, len); }
 	if (rc) return rc;
-	if (h->slots) { hipFree(h->slots); h->slots = nullptr; if (h->extslots) { hipFree(h->extslots); h->extslots = nullptr; } }
+	h->slots.reset(); h->extslots.reset();
 	if (which == KMR_MAP_WEAK) { h->nb_weak = m->nb; h->stats.weak_entries = m->n; if (!h->sing.present) { h->has_singletons = false; h->sing.nb = h->nb_sing; } }
 	else { h->nb_sing = m->nb; h->stats.singleton_entries = m->n; h->has_singletons = true; if (!h->weak.present) h->weak.nb = h->nb_weak; }
 	h->finalized = true; h->map_gen++;
@@ -2896,16 +2840,16 @@ int kmr_count_histogram(kmr_handle *h, uint64_t *counts, double *weights, uint32
 	if (!h || !counts || n_bins < 2) return KMR_ERR_INVALID_ARG;
 	if (!h->finalized) return fail(h, KMR_ERR_STATE, "kmr_count_histogram before kmr_finalize");
 	hipSetDevice(h->device);
-	unsigned long long *dc; double *dw = nullptr;
-	HIPCHK(h, dev_malloc((void **)&dc, 8 * n_bins)); HIPCHK(h, hipMemsetAsync(dc, 0, 8 * n_bins, h->stream));
-	if (weights) { HIPCHK(h, dev_malloc((void **)&dw, 8 * n_bins)); HIPCHK(h, hipMemsetAsync(dw, 0, 8 * n_bins, h->stream)); }
+	DevBuf dcb, dwb;
+	HIPCHK(h, dcb.alloc(8 * n_bins)); HIPCHK(h, hipMemsetAsync(dcb.get(), 0, 8 * n_bins, h->stream));
+	if (weights) { HIPCHK(h, dwb.alloc(8 * n_bins)); HIPCHK(h, hipMemsetAsync(dwb.get(), 0, 8 * n_bins, h->stream)); }
+	unsigned long long *dc = dcb.get<unsigned long long>(); double *dw = dwb.get<double>();
 	if (h->weak.present && h->weak.n)
-		hipLaunchKernelGGL(histogram_kernel, dim3(grid_for(h->weak.n)), dim3(256), 0, h->stream, h->weak.vals, h->ext ? 15u : 3u, h->weak.n, n_bins, dc, dw);
+		hipLaunchKernelGGL(histogram_kernel, dim3(grid_for(h->weak.n)), dim3(256), 0, h->stream, h->weak.vals.get<uint32_t>(), h->ext ? 15u : 3u, h->weak.n, n_bins, dc, dw);
 	HIPCHK(h, hipGetLastError());
 	HIPCHK(h, hipMemcpyAsync(counts, dc, 8 * n_bins, hipMemcpyDeviceToHost, h->stream));
 	if (weights) HIPCHK(h, hipMemcpyAsync(weights, dw, 8 * n_bins, hipMemcpyDeviceToHost, h->stream));
 	HIPCHK(h, hipStreamSynchronize(h->stream));
-	hipFree(dc); if (dw) hipFree(dw);
 	return KMR_OK;
 }
 
@@ -2921,16 +2865,16 @@ int kmr_map_digest(kmr_handle *h, int which_map, kmr_digest *out) {
 	const DevMap &m = which_map == KMR_MAP_WEAK ? h->weak : h->sing;
 	if (which_map == KMR_MAP_SINGLETON && !h->has_singletons) return KMR_OK;
 	if (!m.present || !m.n) return KMR_OK;
-	synth::Digest *d;
-	HIPCHK(h, dev_malloc((void **)&d, sizeof(synth::Digest))); HIPCHK(h, hipMemsetAsync(d, 0, sizeof(synth::Digest), h->stream));
+	DevBuf db; HIPCHK(h, db.alloc(sizeof(synth::Digest)));
+	synth::Digest *d = db.get<synth::Digest>();
+	HIPCHK(h, hipMemsetAsync(d, 0, sizeof(synth::Digest), h->stream));
 	if (which_map == KMR_MAP_WEAK)
-		hipLaunchKernelGGL(synth::map_digest_kernel, dim3(grid_for(m.n, 256, 4096)), dim3(256), 0, h->stream, m.keys, (uint32_t)h->W, m.vals, h->ext ? 15u : 3u, (const uint8_t *)nullptr, (const uint32_t *)nullptr, m.n, d);
+		hipLaunchKernelGGL(synth::map_digest_kernel, dim3(grid_for(m.n, 256, 4096)), dim3(256), 0, h->stream, m.keys.get<uint64_t>(), (uint32_t)h->W, m.vals.get<uint32_t>(), h->ext ? 15u : 3u, (const uint8_t *)nullptr, (const uint32_t *)nullptr, m.n, d);
 	else
-		hipLaunchKernelGGL(synth::map_digest_kernel, dim3(grid_for(m.n, 256, 4096)), dim3(256), 0, h->stream, m.keys, (uint32_t)h->W, (const uint32_t *)nullptr, 0u, m.sweight, h->ext ? m.spkt : (const uint32_t *)nullptr, m.n, d);
+		hipLaunchKernelGGL(synth::map_digest_kernel, dim3(grid_for(m.n, 256, 4096)), dim3(256), 0, h->stream, m.keys.get<uint64_t>(), (uint32_t)h->W, (const uint32_t *)nullptr, 0u, m.sweight.get<uint8_t>(), h->ext ? m.spkt.get<uint32_t>() : (const uint32_t *)nullptr, m.n, d);
 	HIPCHK(h, hipGetLastError());
 	HIPCHK(h, hipMemcpyAsync(out, d, sizeof(synth::Digest), hipMemcpyDeviceToHost, h->stream));
 	HIPCHK(h, hipStreamSynchronize(h->stream));
-	hipFree(d);
 	out->entries = m.n;
 	return KMR_OK;
 }
@@ -3005,19 +2949,19 @@ int kmr_histogram(kmr_handle *h, uint32_t zoom_max, double log_base, uint64_t *v
 	const double logFactor = log(log_base);
 	const unsigned int zoomLogSkip = (unsigned int)(log((double)zoom_max + 1.0) / logFactor - 1.0);
 	for (uint32_t c = 1; c < 65536; c++) lut[c] = c <= zoom_max ? c : (unsigned int)(log((double)c) / logFactor - zoomLogSkip + zoom_max);
-	uint32_t *dl; unsigned long long *dv, *dc; double *dw;
-	HIPCHK(h, dev_malloc((void **)&dl, 4 * 65536)); HIPCHK(h, dev_malloc((void **)&dv, 8ull * nb)); HIPCHK(h, dev_malloc((void **)&dc, 8ull * nb)); HIPCHK(h, dev_malloc((void **)&dw, 8ull * nb));
+	DevBuf dlb, dvb, dcb, dwb;
+	HIPCHK(h, dlb.alloc(4 * 65536)); HIPCHK(h, dvb.alloc(8ull * nb)); HIPCHK(h, dcb.alloc(8ull * nb)); HIPCHK(h, dwb.alloc(8ull * nb));
+	uint32_t *dl = dlb.get<uint32_t>(); unsigned long long *dv = dvb.get<unsigned long long>(), *dc = dcb.get<unsigned long long>(); double *dw = dwb.get<double>();
 	HIPCHK(h, hipMemcpyAsync(dl, lut.data(), 4 * 65536, hipMemcpyHostToDevice, h->stream));
 	HIPCHK(h, hipMemsetAsync(dv, 0, 8ull * nb, h->stream)); HIPCHK(h, hipMemsetAsync(dc, 0, 8ull * nb, h->stream)); HIPCHK(h, hipMemsetAsync(dw, 0, 8ull * nb, h->stream));
 	if (h->weak.present && h->weak.n)
-		hipLaunchKernelGGL(ref_histogram_kernel, dim3(grid_for(h->weak.n, 256, 2048)), dim3(256), 0, h->stream, h->weak.vals, h->ext ? 15u : 3u, (const uint8_t *)nullptr, h->weak.n, dl, dv, dc, dw);
+		hipLaunchKernelGGL(ref_histogram_kernel, dim3(grid_for(h->weak.n, 256, 2048)), dim3(256), 0, h->stream, h->weak.vals.get<uint32_t>(), h->ext ? 15u : 3u, (const uint8_t *)nullptr, h->weak.n, dl, dv, dc, dw);
 	if (h->has_singletons && h->sing.present && h->sing.n)
-		hipLaunchKernelGGL(ref_histogram_kernel, dim3(grid_for(h->sing.n, 256, 2048)), dim3(256), 0, h->stream, (const uint32_t *)nullptr, 0u, h->sing.sweight, h->sing.n, dl, dv, dc, dw);
+		hipLaunchKernelGGL(ref_histogram_kernel, dim3(grid_for(h->sing.n, 256, 2048)), dim3(256), 0, h->stream, (const uint32_t *)nullptr, 0u, h->sing.sweight.get<uint8_t>(), h->sing.n, dl, dv, dc, dw);
 	HIPCHK(h, hipGetLastError());
 	HIPCHK(h, hipMemcpyAsync(visits, dv, 8ull * nb, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipMemcpyAsync(visited_count, dc, 8ull * nb, hipMemcpyDeviceToHost, h->stream));
 	HIPCHK(h, hipMemcpyAsync(visited_weight, dw, 8ull * nb, hipMemcpyDeviceToHost, h->stream));
 	HIPCHK(h, hipStreamSynchronize(h->stream));
-	hipFree(dl); hipFree(dv); hipFree(dc); hipFree(dw);
 	return KMR_OK;
 }
 
@@ -3030,7 +2974,7 @@ static int dump_text(kmr_handle *h, const char *path, uint32_t min_depth, bool g
 	const uint32_t vw = h->ext ? 15 : 3, W = h->W, k = h->k;
 	const uint64_t n = h->weak.n;
 	std::vector<uint64_t> keys(n * W); std::vector<uint32_t> vals(n * vw);
-	if (n) { HIPCHK(h, hipMemcpy(keys.data(), h->weak.keys, 8 * n * W, hipMemcpyDeviceToHost)); HIPCHK(h, hipMemcpy(vals.data(), h->weak.vals, 4 * n * vw, hipMemcpyDeviceToHost)); }
+	if (n) { HIPCHK(h, hipMemcpy(keys.data(), h->weak.keys.get<uint64_t>(), 8 * n * W, hipMemcpyDeviceToHost)); HIPCHK(h, hipMemcpy(vals.data(), h->weak.vals.get<uint32_t>(), 4 * n * vw, hipMemcpyDeviceToHost)); }
 	FILE *f = fopen(path, "a");
 	if (!f) return fail(h, KMR_ERR_INVALID_ARG, std::string("cannot open ") + path);
 	std::string fa(k, 'A'), rfa(k, 'A');
@@ -3065,74 +3009,66 @@ static int ingest_dev(kmr_handle *h, const uint8_t *text, uint64_t len, uint32_t
 	if (input_base == 0) input_base = start;
 	if ((input_base != 33 && input_base != 64) || (start != 33 && start != 64))
 		return fail(h, KMR_ERR_INVALID_ARG, "fastq quality base must be 33 or 64 (src/Options.h:490)");
-	kmr_reads *R = new kmr_reads(); R->device = h->device; R->input_base = input_base;
-	uint32_t *blk = nullptr, *derr = nullptr, *llen = nullptr, *keep = nullptr, *klen = nullptr;
-	uint64_t *bbase = nullptr, *lstart = nullptr, *kidx = nullptr, *boff = nullptr;
-	auto cleanup = [&]() { hipFree(blk); hipFree(derr); hipFree(llen); hipFree(keep); hipFree(klen); hipFree(bbase); hipFree(lstart); hipFree(kidx); hipFree(boff); };
-#define ING(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { h->err = std::string(#call) + ": " + hip_err_text(e_); cleanup(); kmr_reads_free(R); \
-	return e_ == hipErrorOutOfMemory ? KMR_ERR_OOM : KMR_ERR_HIP; } } while (0)
-#define INGRC(expr) do { int rc_ = (expr); if (rc_) { cleanup(); kmr_reads_free(R); return rc_; } } while (0)
+	std::unique_ptr<kmr_reads, void (*)(kmr_reads *)> R(new kmr_reads, kmr_reads_free);
+	R->device = h->device; R->input_base = input_base;
+	DevBuf blk, derr, llen, keep, klen, bbase, lstart, kidx, boff;      /* scratch of this call */
 	const uint64_t nblk = (len + (uint64_t)ING_THREADS * ING_BYTES - 1) / ((uint64_t)ING_THREADS * ING_BYTES);
 	uint64_t n_lines = 0;
-	ING(dev_malloc((void **)&derr, 8)); ING(hipMemsetAsync(derr, 0, 8, h->stream));
+	HIPCHK(h, derr.alloc(8)); HIPCHK(h, hipMemsetAsync(derr.get<uint32_t>(), 0, 8, h->stream));
 	if (nblk) {
-		if (nblk > 0x7fffffffull) { cleanup(); kmr_reads_free(R); return fail(h, KMR_ERR_INVALID_ARG, "FASTQ block too large for one call"); }
-		ING(dev_malloc((void **)&blk, 4 * nblk)); ING(dev_malloc((void **)&bbase, 8 * (nblk + 1)));
-		hipLaunchKernelGGL(ingest_count_lines, dim3((unsigned)nblk), dim3(ING_THREADS), 0, h->stream, text, len, blk);
-		ING(hipGetLastError());
-		INGRC(exclusive_scan(h, blk, nblk, bbase));
-		ING(hipMemcpy(&n_lines, bbase + nblk, 8, hipMemcpyDeviceToHost));
+		if (nblk > 0x7fffffffull) return fail(h, KMR_ERR_INVALID_ARG, "FASTQ block too large for one call");
+		HIPCHK(h, blk.alloc(4 * nblk)); HIPCHK(h, bbase.alloc(8 * (nblk + 1)));
+		hipLaunchKernelGGL(ingest_count_lines, dim3((unsigned)nblk), dim3(ING_THREADS), 0, h->stream, text, len, blk.get<uint32_t>());
+		HIPCHK(h, hipGetLastError());
+		{ int rc = exclusive_scan(h, blk.get<uint32_t>(), nblk, bbase.get<uint64_t>()); if (rc) return rc; }
+		HIPCHK(h, hipMemcpy(&n_lines, bbase.get<uint64_t>() + nblk, 8, hipMemcpyDeviceToHost));
 	}
-	if (n_lines % 4 != 0) { cleanup(); kmr_reads_free(R); return fail(h, KMR_ERR_INVALID_ARG, "malformed FASTQ: " + std::to_string(n_lines) + " non-empty lines is not a multiple of 4 (truncated record)"); }
+	if (n_lines % 4 != 0) return fail(h, KMR_ERR_INVALID_ARG, "malformed FASTQ: " + std::to_string(n_lines) + " non-empty lines is not a multiple of 4 (truncated record)");
 	const uint64_t nrec = n_lines / 4;
 	uint64_t n_kept = 0, total = 0;
 	if (nrec) {
-		ING(dev_malloc((void **)&lstart, 8 * n_lines)); ING(dev_malloc((void **)&llen, 4 * n_lines));
-		hipLaunchKernelGGL(ingest_index_lines, dim3((unsigned)nblk), dim3(ING_THREADS), 0, h->stream, text, len, bbase, lstart);
-		hipLaunchKernelGGL(ingest_line_lengths, dim3(grid_for(n_lines)), dim3(256), 0, h->stream, text, len, lstart, n_lines, llen, derr);
-		ING(dev_malloc((void **)&keep, 4 * nrec)); ING(dev_malloc((void **)&klen, 4 * nrec));
-		ING(dev_malloc((void **)&kidx, 8 * (nrec + 1))); ING(dev_malloc((void **)&boff, 8 * (nrec + 1)));
-		hipLaunchKernelGGL(ingest_records, dim3(grid_for(nrec)), dim3(256), 0, h->stream, text, lstart, llen, nrec, store_comment, keep, klen, derr);
-		ING(hipGetLastError());
-		INGRC(exclusive_scan(h, keep, nrec, kidx));
-		INGRC(exclusive_scan(h, klen, nrec, boff));
+		HIPCHK(h, lstart.alloc(8 * n_lines)); HIPCHK(h, llen.alloc(4 * n_lines));
+		hipLaunchKernelGGL(ingest_index_lines, dim3((unsigned)nblk), dim3(ING_THREADS), 0, h->stream, text, len, bbase.get<uint64_t>(), lstart.get<uint64_t>());
+		hipLaunchKernelGGL(ingest_line_lengths, dim3(grid_for(n_lines)), dim3(256), 0, h->stream, text, len, lstart.get<uint64_t>(), n_lines, llen.get<uint32_t>(), derr.get<uint32_t>());
+		HIPCHK(h, keep.alloc(4 * nrec)); HIPCHK(h, klen.alloc(4 * nrec));
+		HIPCHK(h, kidx.alloc(8 * (nrec + 1))); HIPCHK(h, boff.alloc(8 * (nrec + 1)));
+		hipLaunchKernelGGL(ingest_records, dim3(grid_for(nrec)), dim3(256), 0, h->stream, text, lstart.get<uint64_t>(), llen.get<uint32_t>(), nrec, store_comment, keep.get<uint32_t>(), klen.get<uint32_t>(), derr.get<uint32_t>());
+		HIPCHK(h, hipGetLastError());
+		{ int rc = exclusive_scan(h, keep.get<uint32_t>(), nrec, kidx.get<uint64_t>()); if (rc) return rc; }
+		{ int rc = exclusive_scan(h, klen.get<uint32_t>(), nrec, boff.get<uint64_t>()); if (rc) return rc; }
 		uint32_t e = 0;
-		ING(hipMemcpy(&e, derr, 4, hipMemcpyDeviceToHost));
+		HIPCHK(h, hipMemcpy(&e, derr.get<uint32_t>(), 4, hipMemcpyDeviceToHost));
 		if (e) {
 			std::string why;
 			if (e & ING_ERR_NAME) why += " a record does not start with '@' or has an empty name;";
 			if (e & ING_ERR_BLANK) why += " an empty line inside a record;";
 			if (e & ING_ERR_PLUS) why += " missing '+' line;";
 			if (e & ING_ERR_LEN) why += " number of bases and quals not equal;";
-			cleanup(); kmr_reads_free(R);
 			return fail(h, KMR_ERR_INVALID_ARG, "malformed FASTQ:" + why);
 		}
-		ING(hipMemcpy(&n_kept, kidx + nrec, 8, hipMemcpyDeviceToHost)); ING(hipMemcpy(&total, boff + nrec, 8, hipMemcpyDeviceToHost));
+		HIPCHK(h, hipMemcpy(&n_kept, kidx.get<uint64_t>() + nrec, 8, hipMemcpyDeviceToHost)); HIPCHK(h, hipMemcpy(&total, boff.get<uint64_t>() + nrec, 8, hipMemcpyDeviceToHost));
 	}
 	R->n = n_kept; R->total = total; R->filtered = nrec - n_kept;
-	ING(dev_malloc((void **)&R->bases, total + 64)); ING(dev_malloc((void **)&R->quals, total + 64)); ING(dev_malloc((void **)&R->offsets, 8 * (n_kept + 1)));
-	ING(dev_malloc((void **)&R->name_off, 8 * std::max<uint64_t>(1, n_kept))); ING(dev_malloc((void **)&R->name_len, 4 * std::max<uint64_t>(1, n_kept)));
-	ING(hipMemsetAsync(R->bases + total, 0, 64, h->stream)); ING(hipMemsetAsync(R->quals + total, 0, 64, h->stream));
-	ING(hipMemcpyAsync(R->offsets + n_kept, &total, 8, hipMemcpyHostToDevice, h->stream));
+	HIPCHK(h, R->bases.alloc(total + 64)); HIPCHK(h, R->quals.alloc(total + 64)); HIPCHK(h, R->offsets.alloc(8 * (n_kept + 1)));
+	HIPCHK(h, R->name_off.alloc(8 * std::max<uint64_t>(1, n_kept))); HIPCHK(h, R->name_len.alloc(4 * std::max<uint64_t>(1, n_kept)));
+	HIPCHK(h, hipMemsetAsync(R->bases.get<uint8_t>() + total, 0, 64, h->stream)); HIPCHK(h, hipMemsetAsync(R->quals.get<uint8_t>() + total, 0, 64, h->stream));
+	HIPCHK(h, hipMemcpyAsync(R->offsets.get<uint64_t>() + n_kept, &total, 8, hipMemcpyHostToDevice, h->stream));
 	if (nrec) {
 		/* appendFasta rescales every read from the input base to Read::FASTQ_START_CHAR as it is read (src/ReadSet.cpp:324,336) */
-		hipLaunchKernelGGL(ingest_copy, dim3(grid_for(nrec, 4, 1 << 16)), dim3(256), 0, h->stream, text, len, lstart, llen, nrec, keep, kidx, boff,
-		                   (int)start - (int)input_base, start, R->bases, R->quals, R->offsets, R->name_off, R->name_len, derr + 1);
-		ING(hipGetLastError());
+		hipLaunchKernelGGL(ingest_copy, dim3(grid_for(nrec, 4, 1 << 16)), dim3(256), 0, h->stream, text, len, lstart.get<uint64_t>(), llen.get<uint32_t>(), nrec, keep.get<uint32_t>(), kidx.get<uint64_t>(), boff.get<uint64_t>(),
+		                   (int)start - (int)input_base, start, R->bases.get<uint8_t>(), R->quals.get<uint8_t>(), R->offsets.get<uint64_t>(), R->name_off.get<uint64_t>(), R->name_len.get<uint32_t>(), derr.get<uint32_t>() + 1);
+		HIPCHK(h, hipGetLastError());
 		uint32_t flip = 0;
-		ING(hipMemcpyAsync(&flip, derr + 1, 4, hipMemcpyDeviceToHost, h->stream)); ING(hipStreamSynchronize(h->stream));
+		HIPCHK(h, hipMemcpyAsync(&flip, derr.get<uint32_t>() + 1, 4, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
 		const uint32_t want = start == 33 ? 64u : 33u;        /* __setFastqStart(the other base), src/ReadSet.h:174-186 */
 		if (flip && want != input_base) {
-			if (total) hipLaunchKernelGGL(ingest_shift_quals, dim3(grid_for(total)), dim3(256), 0, h->stream, R->quals, total, (int)input_base - (int)want);
-			ING(hipGetLastError());
+			if (total) hipLaunchKernelGGL(ingest_shift_quals, dim3(grid_for(total)), dim3(256), 0, h->stream, R->quals.get<uint8_t>(), total, (int)input_base - (int)want);
+			HIPCHK(h, hipGetLastError());
 			R->input_base = want;
 		}
 	}
-	ING(hipStreamSynchronize(h->stream));
-#undef ING
-#undef INGRC
-	cleanup();
-	*out = R;
+	HIPCHK(h, hipStreamSynchronize(h->stream));
+	*out = R.release();
 	return KMR_OK;
 }
 
@@ -3146,13 +3082,11 @@ int kmr_ingest_fastq(kmr_handle *h, const char *text, uint64_t len, uint32_t inp
 	if (!h || !out || (len && !text)) return KMR_ERR_INVALID_ARG;
 	*out = nullptr;
 	hipSetDevice(h->device);
-	uint8_t *d = nullptr;
-	HIPCHK(h, dev_malloc((void **)&d, len + 16));
-	hipError_t e = hipMemcpy(d, text, len, hipMemcpyHostToDevice);
-	if (e != hipSuccess) { hipFree(d); h->err = std::string("hipMemcpy(FASTQ text): ") + hipGetErrorString(e); return KMR_ERR_HIP; }
-	const int rc = ingest_dev(h, d, len, input_quality_base, store_comment, out);
-	hipFree(d);
-	return rc;
+	DevBuf d;
+	HIPCHK(h, d.alloc(len + 16));
+	hipError_t e = hipMemcpy(d.get(), text, len, hipMemcpyHostToDevice);
+	if (e != hipSuccess) { h->err = std::string("hipMemcpy(FASTQ text): ") + hipGetErrorString(e); return KMR_ERR_HIP; }
+	return ingest_dev(h, d.get<uint8_t>(), len, input_quality_base, store_comment, out);
 }
 /* a device-resident batch from reads the host already parsed (the reference's ReadSet flattened as for kmr_add_reads) */
 int kmr_reads_from_host(kmr_handle *h, const char *bases, const char *quals, const uint64_t *offsets, uint64_t n_reads, kmr_reads **out) {
@@ -3162,24 +3096,22 @@ int kmr_reads_from_host(kmr_handle *h, const char *bases, const char *quals, con
 	const uint64_t first = offsets[0], total = offsets[n_reads] - first;
 	std::unique_ptr<kmr_reads, void (*)(kmr_reads *)> r(new kmr_reads, kmr_reads_free);
 	r->device = h->device; r->n = n_reads; r->total = total; r->input_base = h->cfg.fastq_start_char;
-	HIPCHK(h, dev_malloc((void **)&r->bases, total + 64)); HIPCHK(h, dev_malloc((void **)&r->quals, total + 64));
-	HIPCHK(h, dev_malloc((void **)&r->offsets, 8 * (n_reads + 1)));
-	HIPCHK(h, dev_malloc((void **)&r->name_off, 8 * std::max<uint64_t>(n_reads, 1))); HIPCHK(h, dev_malloc((void **)&r->name_len, 4 * std::max<uint64_t>(n_reads, 1)));
-	HIPCHK(h, hipMemset(r->bases + total, 0, 64)); HIPCHK(h, hipMemset(r->quals + total, 0, 64));
-	HIPCHK(h, hipMemset(r->name_off, 0, 8 * std::max<uint64_t>(n_reads, 1))); HIPCHK(h, hipMemset(r->name_len, 0, 4 * std::max<uint64_t>(n_reads, 1)));
-	if (total) { HIPCHK(h, hipMemcpy(r->bases, bases + first, total, hipMemcpyHostToDevice)); HIPCHK(h, hipMemcpy(r->quals, quals + first, total, hipMemcpyHostToDevice)); }
+	HIPCHK(h, r->bases.alloc(total + 64)); HIPCHK(h, r->quals.alloc(total + 64));
+	HIPCHK(h, r->offsets.alloc(8 * (n_reads + 1)));
+	HIPCHK(h, r->name_off.alloc(8 * std::max<uint64_t>(n_reads, 1))); HIPCHK(h, r->name_len.alloc(4 * std::max<uint64_t>(n_reads, 1)));
+	HIPCHK(h, hipMemset(r->bases.get<uint8_t>() + total, 0, 64)); HIPCHK(h, hipMemset(r->quals.get<uint8_t>() + total, 0, 64));
+	HIPCHK(h, hipMemset(r->name_off.get<uint64_t>(), 0, 8 * std::max<uint64_t>(n_reads, 1))); HIPCHK(h, hipMemset(r->name_len.get<uint32_t>(), 0, 4 * std::max<uint64_t>(n_reads, 1)));
+	if (total) { HIPCHK(h, hipMemcpy(r->bases.get<uint8_t>(), bases + first, total, hipMemcpyHostToDevice)); HIPCHK(h, hipMemcpy(r->quals.get<uint8_t>(), quals + first, total, hipMemcpyHostToDevice)); }
 	std::vector<uint64_t> rel(n_reads + 1);
 	for (uint64_t i = 0; i <= n_reads; i++) rel[i] = offsets[i] - first;
-	HIPCHK(h, hipMemcpy(r->offsets, rel.data(), 8 * (n_reads + 1), hipMemcpyHostToDevice));
+	HIPCHK(h, hipMemcpy(r->offsets.get<uint64_t>(), rel.data(), 8 * (n_reads + 1), hipMemcpyHostToDevice));
 	*out = r.release();
 	return KMR_OK;
 }
 void kmr_reads_free(kmr_reads *r) {
 	if (!r) return;
 	hipSetDevice(r->device);
-	if (r->bases) hipFree(r->bases); if (r->quals) hipFree(r->quals); if (r->offsets) hipFree(r->offsets);
-	if (r->name_off) hipFree(r->name_off); if (r->name_len) hipFree(r->name_len);
-	delete r;
+	delete r;      /* (its buffers are freed on this device) */
 }
 int kmr_reads_info(const kmr_reads *r, uint64_t *n_reads, uint64_t *total_bases, uint32_t *input_quality_base, uint64_t *n_filtered) {
 	if (!r) return KMR_ERR_INVALID_ARG;
@@ -3189,24 +3121,24 @@ int kmr_reads_info(const kmr_reads *r, uint64_t *n_reads, uint64_t *total_bases,
 }
 int kmr_reads_device_ptrs(const kmr_reads *r, void **bases, void **quals, void **offsets) {
 	if (!r) return KMR_ERR_INVALID_ARG;
-	if (bases) *bases = r->bases; if (quals) *quals = r->quals; if (offsets) *offsets = r->offsets;
+	if (bases) *bases = r->bases.get<uint8_t>(); if (quals) *quals = r->quals.get<uint8_t>(); if (offsets) *offsets = r->offsets.get<uint64_t>();
 	return KMR_OK;
 }
 int kmr_reads_copy(const kmr_reads *r, char *bases, char *quals, uint64_t *offsets, uint64_t *name_off, uint32_t *name_len) {
 	if (!r) return KMR_ERR_INVALID_ARG;
 	hipSetDevice(r->device);
 	hipError_t e = hipSuccess;
-	if (bases && r->total && e == hipSuccess) e = hipMemcpy(bases, r->bases, r->total, hipMemcpyDeviceToHost);
-	if (quals && r->total && e == hipSuccess) e = hipMemcpy(quals, r->quals, r->total, hipMemcpyDeviceToHost);
-	if (offsets && e == hipSuccess) e = hipMemcpy(offsets, r->offsets, 8 * (r->n + 1), hipMemcpyDeviceToHost);
-	if (name_off && r->n && e == hipSuccess) e = hipMemcpy(name_off, r->name_off, 8 * r->n, hipMemcpyDeviceToHost);
-	if (name_len && r->n && e == hipSuccess) e = hipMemcpy(name_len, r->name_len, 4 * r->n, hipMemcpyDeviceToHost);
+	if (bases && r->total && e == hipSuccess) e = hipMemcpy(bases, r->bases.get<uint8_t>(), r->total, hipMemcpyDeviceToHost);
+	if (quals && r->total && e == hipSuccess) e = hipMemcpy(quals, r->quals.get<uint8_t>(), r->total, hipMemcpyDeviceToHost);
+	if (offsets && e == hipSuccess) e = hipMemcpy(offsets, r->offsets.get<uint64_t>(), 8 * (r->n + 1), hipMemcpyDeviceToHost);
+	if (name_off && r->n && e == hipSuccess) e = hipMemcpy(name_off, r->name_off.get<uint64_t>(), 8 * r->n, hipMemcpyDeviceToHost);
+	if (name_len && r->n && e == hipSuccess) e = hipMemcpy(name_len, r->name_len.get<uint32_t>(), 4 * r->n, hipMemcpyDeviceToHost);
 	return e == hipSuccess ? KMR_OK : KMR_ERR_HIP;
 }
 int kmr_add_read_batch(kmr_handle *h, const kmr_reads *r, uint64_t first_global_read_idx) {
 	if (!h || !r) return KMR_ERR_INVALID_ARG;
 	if (r->device != h->device) return fail(h, KMR_ERR_INVALID_ARG, "read batch lives on another device");
-	int rc = kmr_add_reads_dev(h, r->bases, r->quals, r->offsets, r->n, r->total, first_global_read_idx, nullptr);
+	int rc = kmr_add_reads_dev(h, r->bases.get<uint8_t>(), r->quals.get<uint8_t>(), r->offsets.get<uint64_t>(), r->n, r->total, first_global_read_idx, nullptr);
 	if (!rc) rc = kmr_sync(h);
 	return rc;
 }
@@ -3219,8 +3151,8 @@ struct kmr_artifact_filter {
 	kmr_artifact_config cfg;
 	uint32_t n_seq = 0, remaining_edits = 0, log2cap = 0;
 	uint64_t n_keys = 0;
-	uint64_t *d_keys = nullptr; uint32_t *d_vals = nullptr;      /* open-addressed lookup table */
-	uint32_t *d_bits = nullptr;                                    /* presence filter in front of it (ART_FILTER_LOG2 bits) */
+	DevBuf d_keys, d_vals;                                         /* open-addressed lookup table */
+	DevBuf d_bits;                                                 /* presence filter in front of it (ART_FILTER_LOG2 bits) */
 	std::vector<uint64_t> keys; std::vector<uint32_t> vals;        /* the same entries on the host, ascending keys */
 };
 
@@ -3228,11 +3160,8 @@ namespace {
 
 uint32_t art_log2cap(uint64_t n) { uint32_t l = 10; while ((1ull << l) < 2 * n + 16) l++; return l; }
 
-struct ArtBuf {          /* device scratch of one call, released on every exit path */
-	std::vector<void *> p;
-	~ArtBuf() { for (void *q : p) if (q) hipFree(q); }
-	template <typename T> hipError_t get(T **out, size_t n) { void *q = nullptr; hipError_t e = dev_malloc(&q, std::max<size_t>(sizeof(T) * n, 256)); if (e == hipSuccess) p.push_back(q); *out = (T *)q; return e; }
-};
+/* a scratch block of n elements of T (256 bytes at least) */
+template <class T> hipError_t alloc_n(DevBuf &b, T **p, size_t n) { const hipError_t e = b.alloc(std::max<size_t>(sizeof(T) * n, 256)); *p = b.get<T>(); return e; }
 
 uint64_t art_pack(const char *s, uint32_t len) {      /* TwoBitSequence::compressSequence: anything but ACGT packs as A */
 	uint64_t v = 0;
@@ -3243,18 +3172,18 @@ uint64_t art_revcomp_host(uint64_t v, uint32_t len) { uint64_t r = 0; for (uint3
 
 /* (re)build the lookup table of the filter from its host entries */
 int art_upload(kmr_handle *h, kmr_artifact_filter *f) {
-	if (f->d_keys) { hipFree(f->d_keys); f->d_keys = nullptr; } if (f->d_vals) { hipFree(f->d_vals); f->d_vals = nullptr; }
+	f->d_keys.reset(); f->d_vals.reset();
 	f->n_keys = f->keys.size();
 	f->log2cap = art_log2cap(f->n_keys);
 	const uint64_t cap = 1ull << f->log2cap;
-	HIPCHK(h, dev_malloc((void **)&f->d_keys, 8 * cap)); HIPCHK(h, dev_malloc((void **)&f->d_vals, 4 * cap));
-	if (!f->d_bits) HIPCHK(h, dev_malloc((void **)&f->d_bits, (1u << ART_FILTER_LOG2) / 8));
-	HIPCHK(h, hipMemsetAsync(f->d_bits, 0, (1u << ART_FILTER_LOG2) / 8, h->stream));
-	ArtBuf tmp; uint64_t *dk; uint32_t *dv;
-	HIPCHK(h, tmp.get(&dk, f->n_keys)); HIPCHK(h, tmp.get(&dv, f->n_keys));
+	HIPCHK(h, f->d_keys.alloc(8 * cap)); HIPCHK(h, f->d_vals.alloc(4 * cap));
+	if (!f->d_bits) HIPCHK(h, f->d_bits.alloc((1u << ART_FILTER_LOG2) / 8));
+	HIPCHK(h, hipMemsetAsync(f->d_bits.get<uint32_t>(), 0, (1u << ART_FILTER_LOG2) / 8, h->stream));
+	DevBuf b_dk, b_dv; uint64_t *dk; uint32_t *dv;
+	HIPCHK(h, alloc_n(b_dk, &dk, f->n_keys)); HIPCHK(h, alloc_n(b_dv, &dv, f->n_keys));
 	if (f->n_keys) { HIPCHK(h, hipMemcpyAsync(dk, f->keys.data(), 8 * f->n_keys, hipMemcpyHostToDevice, h->stream)); HIPCHK(h, hipMemcpyAsync(dv, f->vals.data(), 4 * f->n_keys, hipMemcpyHostToDevice, h->stream)); }
-	ArtifactTable t{f->d_keys, f->d_vals, nullptr, f->log2cap, f->d_bits};
-	hipLaunchKernelGGL(artifact_fill, dim3(1024), dim3(256), 0, h->stream, f->d_keys, (uint32_t *)nullptr, cap);
+	ArtifactTable t{f->d_keys.get<uint64_t>(), f->d_vals.get<uint32_t>(), nullptr, f->log2cap, f->d_bits.get<uint32_t>()};
+	hipLaunchKernelGGL(artifact_fill, dim3(1024), dim3(256), 0, h->stream, f->d_keys.get<uint64_t>(), (uint32_t *)nullptr, cap);
 	if (f->n_keys) hipLaunchKernelGGL(artifact_insert, dim3((unsigned)std::min<uint64_t>((f->n_keys + 255) / 256, 4096)), dim3(256), 0, h->stream, t, dk, dv, f->n_keys);
 	HIPCHK(h, hipGetLastError());
 	HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -3280,9 +3209,9 @@ int art_build_round(kmr_handle *h, kmr_artifact_filter *f) {
 	if (worst > (1ull << 32)) return fail(h, KMR_ERR_UNSUPPORTED, "artifact filter: an edit round over " + std::to_string(n) + " keys does not fit the build table");
 	const uint32_t log2cap = art_log2cap(worst);
 	const uint64_t cap = 1ull << log2cap;
-	ArtBuf tmp; uint64_t *tk, *dk, *ok; uint32_t *tv, *tr, *dv, *ov; unsigned long long *cnt;
-	HIPCHK(h, tmp.get(&tk, cap)); HIPCHK(h, tmp.get(&tv, cap)); HIPCHK(h, tmp.get(&tr, cap));
-	HIPCHK(h, tmp.get(&dk, n)); HIPCHK(h, tmp.get(&dv, n)); HIPCHK(h, tmp.get(&cnt, 1));
+	DevBuf b_tk, b_tv, b_tr, b_dk, b_dv, b_cnt, b_ok, b_ov; uint64_t *tk, *dk, *ok; uint32_t *tv, *tr, *dv, *ov; unsigned long long *cnt;
+	HIPCHK(h, alloc_n(b_tk, &tk, cap)); HIPCHK(h, alloc_n(b_tv, &tv, cap)); HIPCHK(h, alloc_n(b_tr, &tr, cap));
+	HIPCHK(h, alloc_n(b_dk, &dk, n)); HIPCHK(h, alloc_n(b_dv, &dv, n)); HIPCHK(h, alloc_n(b_cnt, &cnt, 1));
 	HIPCHK(h, hipMemcpyAsync(dk, sk.data(), 8 * n, hipMemcpyHostToDevice, h->stream));
 	HIPCHK(h, hipMemcpyAsync(dv, sv.data(), 4 * n, hipMemcpyHostToDevice, h->stream));
 	HIPCHK(h, hipMemsetAsync(cnt, 0, 8, h->stream));
@@ -3293,7 +3222,7 @@ int art_build_round(kmr_handle *h, kmr_artifact_filter *f) {
 	HIPCHK(h, hipGetLastError());
 	HIPCHK(h, hipStreamSynchronize(h->stream));
 	/* the table is sparse (<= 50 % by construction, a few % in practice): count first, then compact */
-	HIPCHK(h, tmp.get(&ok, worst)); HIPCHK(h, tmp.get(&ov, worst));
+	HIPCHK(h, alloc_n(b_ok, &ok, worst)); HIPCHK(h, alloc_n(b_ov, &ov, worst));
 	hipLaunchKernelGGL(artifact_compact, dim3(2048), dim3(256), 0, h->stream, t, dv, ok, ov, cnt);
 	HIPCHK(h, hipGetLastError());
 	unsigned long long m = 0;
@@ -3382,8 +3311,7 @@ int kmr_artifact_filter_entries(const kmr_artifact_filter *f, uint64_t *keys, ui
 void kmr_artifact_filter_free(kmr_artifact_filter *f) {
 	if (!f) return;
 	hipSetDevice(f->device);
-	if (f->d_keys) hipFree(f->d_keys); if (f->d_vals) hipFree(f->d_vals); if (f->d_bits) hipFree(f->d_bits);
-	delete f;
+	delete f;      /* (its buffers are freed on this device) */
 }
 
 int kmr_artifact_filter_apply(kmr_handle *h, const kmr_artifact_filter *f, const kmr_reads *in, const int64_t *mate,
@@ -3394,33 +3322,33 @@ int kmr_artifact_filter_apply(kmr_handle *h, const kmr_artifact_filter *f, const
 	if (f->device != h->device || in->device != h->device) return fail(h, KMR_ERR_INVALID_ARG, "filter, reads and handle must live on one device");
 	hipSetDevice(h->device);
 	const uint64_t n = in->n;
-	ArtifactTable t{f->d_keys, f->d_vals, nullptr, f->log2cap, f->d_bits};
+	ArtifactTable t{f->d_keys.get<uint64_t>(), f->d_vals.get<uint32_t>(), nullptr, f->log2cap, f->d_bits.get<uint32_t>()};
 	ArtifactParams P;
 	P.length = f->cfg.match_length; P.nSeq = f->n_seq; P.numErrors = f->remaining_edits;
 	P.srBegin = f->cfg.simple_repeat_begin; P.srEnd = f->cfg.simple_repeat_end; P.phix = f->cfg.phix_idx; P.refBegin = f->cfg.reference_begin;
 	P.minQualChar = (int32_t)(int8_t)(uint8_t)(f->cfg.fastq_start_char + f->cfg.min_quality);
 	P.minReadLength = f->cfg.min_read_length;
-	ArtBuf tmp;
+	DevBuf b_dval, b_dmin, b_dmax, b_dro, b_drl, b_dact, b_dflag, b_dridx, b_dmate, b_dlen, b_dsrc;
 	uint32_t *dval, *dmin, *dmax, *dro, *drl, *dlen, *dflag; uint8_t *dact; int64_t *dmate = nullptr; uint64_t *dridx, *dsrc;
-	HIPCHK(h, tmp.get(&dval, n)); HIPCHK(h, tmp.get(&dmin, n)); HIPCHK(h, tmp.get(&dmax, n)); HIPCHK(h, tmp.get(&dro, n)); HIPCHK(h, tmp.get(&drl, n));
-	HIPCHK(h, tmp.get(&dact, n)); HIPCHK(h, tmp.get(&dflag, n)); HIPCHK(h, tmp.get(&dridx, n + 1));
-	if (mate && n) { HIPCHK(h, tmp.get(&dmate, n)); HIPCHK(h, hipMemcpyAsync(dmate, mate, 8 * n, hipMemcpyHostToDevice, h->stream)); }
+	HIPCHK(h, alloc_n(b_dval, &dval, n)); HIPCHK(h, alloc_n(b_dmin, &dmin, n)); HIPCHK(h, alloc_n(b_dmax, &dmax, n)); HIPCHK(h, alloc_n(b_dro, &dro, n)); HIPCHK(h, alloc_n(b_drl, &drl, n));
+	HIPCHK(h, alloc_n(b_dact, &dact, n)); HIPCHK(h, alloc_n(b_dflag, &dflag, n)); HIPCHK(h, alloc_n(b_dridx, &dridx, n + 1));
+	if (mate && n) { HIPCHK(h, alloc_n(b_dmate, &dmate, n)); HIPCHK(h, hipMemcpyAsync(dmate, mate, 8 * n, hipMemcpyHostToDevice, h->stream)); }
 	uint64_t n_rem = 0;
 	if (n) {
 		const unsigned blocks = (unsigned)((n + 255) / 256);
-		hipLaunchKernelGGL(artifact_screen, dim3(blocks), dim3(256), 0, h->stream, in->bases, in->quals, in->offsets, n, t, P, dval, dmin, dmax, dro, drl);
+		hipLaunchKernelGGL(artifact_screen, dim3(blocks), dim3(256), 0, h->stream, in->bases.get<uint8_t>(), in->quals.get<uint8_t>(), in->offsets.get<uint64_t>(), n, t, P, dval, dmin, dmax, dro, drl);
 		HIPCHK(h, hipGetLastError());
 	}
 	/* lengths after the filter: n reads, then the remnants */
-	HIPCHK(h, tmp.get(&dlen, 2 * n + 1));
+	HIPCHK(h, alloc_n(b_dlen, &dlen, 2 * n + 1));
 	if (n) {
 		const unsigned blocks = (unsigned)((n + 255) / 256);
-		hipLaunchKernelGGL(artifact_action, dim3(blocks), dim3(256), 0, h->stream, in->offsets, n, dmate, P, dval, dmin, dmax, drl, dact, dlen, dflag);
+		hipLaunchKernelGGL(artifact_action, dim3(blocks), dim3(256), 0, h->stream, in->offsets.get<uint64_t>(), n, dmate, P, dval, dmin, dmax, drl, dact, dlen, dflag);
 		HIPCHK(h, hipGetLastError());
 		int rc = exclusive_scan(h, dflag, n, dridx); if (rc) return rc;
 		HIPCHK(h, hipMemcpy(&n_rem, dridx + n, 8, hipMemcpyDeviceToHost));
 	}
-	HIPCHK(h, tmp.get(&dsrc, n_rem));
+	HIPCHK(h, alloc_n(b_dsrc, &dsrc, n_rem));
 	if (n_rem) {
 		hipLaunchKernelGGL(artifact_remnants, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, n, drl, dridx, dlen, dsrc);
 		HIPCHK(h, hipGetLastError());
@@ -3440,15 +3368,15 @@ int kmr_artifact_filter_apply(kmr_handle *h, const kmr_artifact_filter *f, const
 	const uint64_t n_out = n + n_rem;
 	std::unique_ptr<kmr_reads, void (*)(kmr_reads *)> r(new kmr_reads, kmr_reads_free);
 	r->device = h->device; r->n = n_out; r->input_base = in->input_base; r->filtered = in->filtered;
-	HIPCHK(h, dev_malloc((void **)&r->offsets, 8 * (n_out + 1)));
-	if (n_out) { int rc = exclusive_scan(h, dlen, n_out, r->offsets); if (rc) return rc; HIPCHK(h, hipMemcpy(&r->total, r->offsets + n_out, 8, hipMemcpyDeviceToHost)); }
-	else HIPCHK(h, hipMemset(r->offsets, 0, 8));
-	HIPCHK(h, dev_malloc((void **)&r->bases, r->total + 64)); HIPCHK(h, dev_malloc((void **)&r->quals, r->total + 64));
-	HIPCHK(h, hipMemsetAsync(r->bases + r->total, 0, 64, h->stream)); HIPCHK(h, hipMemsetAsync(r->quals + r->total, 0, 64, h->stream));
-	HIPCHK(h, dev_malloc((void **)&r->name_off, 8 * std::max<uint64_t>(n_out, 1))); HIPCHK(h, dev_malloc((void **)&r->name_len, 4 * std::max<uint64_t>(n_out, 1)));
+	HIPCHK(h, r->offsets.alloc(8 * (n_out + 1)));
+	if (n_out) { int rc = exclusive_scan(h, dlen, n_out, r->offsets.get<uint64_t>()); if (rc) return rc; HIPCHK(h, hipMemcpy(&r->total, r->offsets.get<uint64_t>() + n_out, 8, hipMemcpyDeviceToHost)); }
+	else HIPCHK(h, hipMemset(r->offsets.get<uint64_t>(), 0, 8));
+	HIPCHK(h, r->bases.alloc(r->total + 64)); HIPCHK(h, r->quals.alloc(r->total + 64));
+	HIPCHK(h, hipMemsetAsync(r->bases.get<uint8_t>() + r->total, 0, 64, h->stream)); HIPCHK(h, hipMemsetAsync(r->quals.get<uint8_t>() + r->total, 0, 64, h->stream));
+	HIPCHK(h, r->name_off.alloc(8 * std::max<uint64_t>(n_out, 1))); HIPCHK(h, r->name_len.alloc(4 * std::max<uint64_t>(n_out, 1)));
 	if (n_out) {
 		hipLaunchKernelGGL(artifact_gather, dim3((unsigned)std::min<uint64_t>((n_out + 3) / 4, 1u << 16)), dim3(256), 0, h->stream,
-		                   in->bases, in->quals, in->offsets, in->name_off, in->name_len, n, n_out, dact, dmin, dro, dsrc, r->offsets, r->bases, r->quals, r->name_off, r->name_len);
+		                   in->bases.get<uint8_t>(), in->quals.get<uint8_t>(), in->offsets.get<uint64_t>(), in->name_off.get<uint64_t>(), in->name_len.get<uint32_t>(), n, n_out, dact, dmin, dro, dsrc, r->offsets.get<uint64_t>(), r->bases.get<uint8_t>(), r->quals.get<uint8_t>(), r->name_off.get<uint64_t>(), r->name_len.get<uint32_t>());
 		HIPCHK(h, hipGetLastError());
 	}
 	HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -3464,11 +3392,11 @@ int kmr_reads_twobit(kmr_handle *h, const kmr_reads *r, uint8_t *twobit, uint64_
 	if (r->device != h->device) return fail(h, KMR_ERR_INVALID_ARG, "read batch lives on another device");
 	hipSetDevice(h->device);
 	const uint64_t n = r->n;
-	ArtBuf tmp; uint32_t *dlen, *dcnt; uint64_t *dtb, *dmk;
-	HIPCHK(h, tmp.get(&dlen, n + 1)); HIPCHK(h, tmp.get(&dcnt, n + 1)); HIPCHK(h, tmp.get(&dtb, n + 1)); HIPCHK(h, tmp.get(&dmk, n + 1));
+	DevBuf b_dlen, b_dcnt, b_dtb, b_dmk, b_dtw, b_dmp, b_dmc; uint32_t *dlen, *dcnt; uint64_t *dtb, *dmk;
+	HIPCHK(h, alloc_n(b_dlen, &dlen, n + 1)); HIPCHK(h, alloc_n(b_dcnt, &dcnt, n + 1)); HIPCHK(h, alloc_n(b_dtb, &dtb, n + 1)); HIPCHK(h, alloc_n(b_dmk, &dmk, n + 1));
 	uint64_t tb_total = 0, mk_total = 0;
 	if (n) {
-		hipLaunchKernelGGL(twobit_count_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, r->bases, r->offsets, n, dlen, dcnt);
+		hipLaunchKernelGGL(twobit_count_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, r->bases.get<uint8_t>(), r->offsets.get<uint64_t>(), n, dlen, dcnt);
 		HIPCHK(h, hipGetLastError());
 		int rc = exclusive_scan(h, dlen, n, dtb); if (rc) return rc;
 		rc = exclusive_scan(h, dcnt, n, dmk); if (rc) return rc;
@@ -3478,9 +3406,9 @@ int kmr_reads_twobit(kmr_handle *h, const kmr_reads *r, uint8_t *twobit, uint64_
 	if (!twobit && !markup_pos && !markup_char && !twobit_offsets && !markup_offsets) return KMR_OK;      /* sizes only */
 	if ((twobit && twobit_capacity < tb_total) || ((markup_pos || markup_char) && markup_capacity < mk_total)) return KMR_ERR_CAPACITY;
 	uint8_t *dtw, *dmc; uint32_t *dmp;
-	HIPCHK(h, tmp.get(&dtw, tb_total)); HIPCHK(h, tmp.get(&dmp, mk_total)); HIPCHK(h, tmp.get(&dmc, mk_total));
+	HIPCHK(h, alloc_n(b_dtw, &dtw, tb_total)); HIPCHK(h, alloc_n(b_dmp, &dmp, mk_total)); HIPCHK(h, alloc_n(b_dmc, &dmc, mk_total));
 	if (n) {
-		hipLaunchKernelGGL(twobit_pack_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, r->bases, r->offsets, n, dtb, dmk, dtw, dmp, dmc);
+		hipLaunchKernelGGL(twobit_pack_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, r->bases.get<uint8_t>(), r->offsets.get<uint64_t>(), n, dtb, dmk, dtw, dmp, dmc);
 		HIPCHK(h, hipGetLastError());
 	}
 	HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -3505,28 +3433,28 @@ int kmr_reads_from_twobit(kmr_handle *h, const uint8_t *twobit, const uint64_t *
 	const uint64_t nm = markup_offsets ? markup_offsets[n_reads] - markup_offsets[0] : 0;
 	std::unique_ptr<kmr_reads, void (*)(kmr_reads *)> r(new kmr_reads, kmr_reads_free);
 	r->device = h->device; r->n = n_reads; r->total = total; r->input_base = h->cfg.fastq_start_char;
-	HIPCHK(h, dev_malloc((void **)&r->bases, total + 64)); HIPCHK(h, dev_malloc((void **)&r->quals, total + 64));
-	HIPCHK(h, dev_malloc((void **)&r->offsets, 8 * (n_reads + 1)));
-	HIPCHK(h, dev_malloc((void **)&r->name_off, 8 * std::max<uint64_t>(n_reads, 1))); HIPCHK(h, dev_malloc((void **)&r->name_len, 4 * std::max<uint64_t>(n_reads, 1)));
-	HIPCHK(h, hipMemset(r->bases + total, 0, 64)); HIPCHK(h, hipMemset(r->quals + total, 0, 64));
-	HIPCHK(h, hipMemset(r->name_off, 0, 8 * std::max<uint64_t>(n_reads, 1))); HIPCHK(h, hipMemset(r->name_len, 0, 4 * std::max<uint64_t>(n_reads, 1)));
+	HIPCHK(h, r->bases.alloc(total + 64)); HIPCHK(h, r->quals.alloc(total + 64));
+	HIPCHK(h, r->offsets.alloc(8 * (n_reads + 1)));
+	HIPCHK(h, r->name_off.alloc(8 * std::max<uint64_t>(n_reads, 1))); HIPCHK(h, r->name_len.alloc(4 * std::max<uint64_t>(n_reads, 1)));
+	HIPCHK(h, hipMemset(r->bases.get<uint8_t>() + total, 0, 64)); HIPCHK(h, hipMemset(r->quals.get<uint8_t>() + total, 0, 64));
+	HIPCHK(h, hipMemset(r->name_off.get<uint64_t>(), 0, 8 * std::max<uint64_t>(n_reads, 1))); HIPCHK(h, hipMemset(r->name_len.get<uint32_t>(), 0, 4 * std::max<uint64_t>(n_reads, 1)));
 	/* qualities: the array, the one character, or Read::REF_QUAL (a batch always has a quality array; REF_QUAL reads weigh 1) */
-	if (quals) { if (total) HIPCHK(h, hipMemcpy(r->quals, quals + first, total, hipMemcpyHostToDevice)); }
-	else HIPCHK(h, hipMemset(r->quals, uniform_quality ? uniform_quality : 127, total));
-	if (!n_reads) { HIPCHK(h, hipMemset(r->offsets, 0, 8)); *out = r.release(); return KMR_OK; }
-	ArtBuf tmp; uint8_t *dtb, *dmc = nullptr; uint64_t *dto, *doff, *dmo = nullptr; uint32_t *dmp = nullptr;
-	HIPCHK(h, tmp.get(&dtb, tbytes + 64)); HIPCHK(h, tmp.get(&dto, n_reads + 1)); HIPCHK(h, tmp.get(&doff, n_reads + 1));
+	if (quals) { if (total) HIPCHK(h, hipMemcpy(r->quals.get<uint8_t>(), quals + first, total, hipMemcpyHostToDevice)); }
+	else HIPCHK(h, hipMemset(r->quals.get<uint8_t>(), uniform_quality ? uniform_quality : 127, total));
+	if (!n_reads) { HIPCHK(h, hipMemset(r->offsets.get<uint64_t>(), 0, 8)); *out = r.release(); return KMR_OK; }
+	DevBuf b_dtb, b_dto, b_doff, b_dmo, b_dmp, b_dmc; uint8_t *dtb, *dmc = nullptr; uint64_t *dto, *doff, *dmo = nullptr; uint32_t *dmp = nullptr;
+	HIPCHK(h, alloc_n(b_dtb, &dtb, tbytes + 64)); HIPCHK(h, alloc_n(b_dto, &dto, n_reads + 1)); HIPCHK(h, alloc_n(b_doff, &doff, n_reads + 1));
 	std::vector<uint64_t> rel(n_reads + 1), trel(n_reads + 1), mrel(markup_offsets ? n_reads + 1 : 0);
 	for (uint64_t i = 0; i <= n_reads; i++) { rel[i] = offsets[i] - first; trel[i] = twobit_offsets[i] - twobit_offsets[0]; if (markup_offsets) mrel[i] = markup_offsets[i] - markup_offsets[0]; }
 	if (tbytes) HIPCHK(h, hipMemcpy(dtb, twobit + twobit_offsets[0], tbytes, hipMemcpyHostToDevice));
 	HIPCHK(h, hipMemcpy(dto, trel.data(), 8 * (n_reads + 1), hipMemcpyHostToDevice)); HIPCHK(h, hipMemcpy(doff, rel.data(), 8 * (n_reads + 1), hipMemcpyHostToDevice));
-	hipLaunchKernelGGL(twobit_unpack_kernel, dim3((unsigned)std::min<uint64_t>((n_reads + 255) / 256, (uint64_t)num_cus(h) * 32)), dim3(256), 0, h->stream, (const uint8_t *)dtb, (const uint64_t *)dto, (const uint64_t *)doff, n_reads, r->bases, r->offsets);
+	hipLaunchKernelGGL(twobit_unpack_kernel, dim3((unsigned)std::min<uint64_t>((n_reads + 255) / 256, (uint64_t)num_cus(h) * 32)), dim3(256), 0, h->stream, (const uint8_t *)dtb, (const uint64_t *)dto, (const uint64_t *)doff, n_reads, r->bases.get<uint8_t>(), r->offsets.get<uint64_t>());
 	HIPCHK(h, hipGetLastError());
 	if (nm) {
-		HIPCHK(h, tmp.get(&dmo, n_reads + 1)); HIPCHK(h, tmp.get(&dmp, nm)); HIPCHK(h, tmp.get(&dmc, nm));
+		HIPCHK(h, alloc_n(b_dmo, &dmo, n_reads + 1)); HIPCHK(h, alloc_n(b_dmp, &dmp, nm)); HIPCHK(h, alloc_n(b_dmc, &dmc, nm));
 		HIPCHK(h, hipMemcpy(dmo, mrel.data(), 8 * (n_reads + 1), hipMemcpyHostToDevice));
 		HIPCHK(h, hipMemcpy(dmp, markup_pos + markup_offsets[0], 4 * nm, hipMemcpyHostToDevice)); HIPCHK(h, hipMemcpy(dmc, markup_char + markup_offsets[0], nm, hipMemcpyHostToDevice));
-		hipLaunchKernelGGL(twobit_markup_kernel, dim3(grid_for(n_reads)), dim3(256), 0, h->stream, (const uint64_t *)dmo, (const uint32_t *)dmp, (const uint8_t *)dmc, (const uint64_t *)r->offsets, n_reads, r->bases);
+		hipLaunchKernelGGL(twobit_markup_kernel, dim3(grid_for(n_reads)), dim3(256), 0, h->stream, (const uint64_t *)dmo, (const uint32_t *)dmp, (const uint8_t *)dmc, (const uint64_t *)r->offsets.get<uint64_t>(), n_reads, r->bases.get<uint8_t>());
 		HIPCHK(h, hipGetLastError());
 	}
 	HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -3667,8 +3595,9 @@ int kmr_score_counts_dev(kmr_handle *h, const void *dev_bases, const void *dev_o
 	if (scoring_type < 0 || scoring_type > 4) return fail(h, KMR_ERR_INVALID_ARG, "bad scoring_type");
 	if (n_reads == 0) return KMR_OK;
 	hipSetDevice(h->device);
-	uint32_t *dto, *dtl; float *dsc; uint8_t *dwt;
-	HIPCHK(h, dev_malloc((void **)&dto, 4 * n_reads)); HIPCHK(h, dev_malloc((void **)&dtl, 4 * n_reads)); HIPCHK(h, dev_malloc((void **)&dsc, 4 * n_reads)); HIPCHK(h, dev_malloc((void **)&dwt, n_reads));
+	DevBuf b_dto, b_dtl, b_dsc, b_dwt;
+	HIPCHK(h, b_dto.alloc(4 * n_reads)); HIPCHK(h, b_dtl.alloc(4 * n_reads)); HIPCHK(h, b_dsc.alloc(4 * n_reads)); HIPCHK(h, b_dwt.alloc(n_reads));
+	uint32_t *dto = b_dto.get<uint32_t>(), *dtl = b_dtl.get<uint32_t>(); float *dsc = b_dsc.get<float>(); uint8_t *dwt = b_dwt.get<uint8_t>();
 	/* k-mer i of read r sits at position offsets[r] + i: the offsets are their own count offsets */
 	hipLaunchKernelGGL(score_reads_kernel, dim3((unsigned)std::min<uint64_t>(((n_reads + 63) / 64 + SC_WAVES - 1) / SC_WAVES, 1u << 16)), dim3(SC_WAVES * 64), 0, h->stream, (const uint8_t *)dev_bases, (const uint64_t *)dev_offsets, n_reads, h->k,
 	                   (const uint32_t *)dev_position_counts, (const uint64_t *)dev_offsets, (float)minimum_kmer_score, scoring_type, dto, dtl, dsc, dwt);
@@ -3678,7 +3607,6 @@ int kmr_score_counts_dev(kmr_handle *h, const void *dev_bases, const void *dev_o
 	if (e == hipSuccess) e = hipMemcpyAsync(score, dsc, 4 * n_reads, hipMemcpyDeviceToHost, h->stream);
 	if (e == hipSuccess) e = hipMemcpyAsync(was_trimmed, dwt, n_reads, hipMemcpyDeviceToHost, h->stream);
 	hipStreamSynchronize(h->stream);
-	hipFree(dto); hipFree(dtl); hipFree(dsc); hipFree(dwt);
 	HIPCHK(h, e);
 	return KMR_OK;
 }
@@ -3716,31 +3644,29 @@ int kmr_extract_by_owner_host(kmr_handle *h, const kmr_reads *batch, uint64_t fi
 	hipSetDevice(h->device);
 	const uint32_t world = h->cfg.world_size, rb = KMR_RECORD_BYTES(h->k, h->cfg.value_kind);
 	if (!(h->xo_dev && h->xo_batch == (const void *)batch && h->xo_first == first_global_read_idx)) {
-		if (h->xo_dev) { hipFree(h->xo_dev); h->xo_dev = nullptr; }
+		h->xo_dev.reset();
 		h->xo_counts.assign(world, 0); h->xo_batch = nullptr;
-		unsigned long long *dcounts = nullptr;
-		HIPCHK(h, dev_malloc((void **)&dcounts, 8 * world));
+		DevBuf dcounts;
+		HIPCHK(h, dcounts.alloc(8 * world));
 		const uint64_t upper = batch->total + 64;          /* k-mers <= bases */
 		uint64_t segcap = std::min<uint64_t>(upper, upper / world + upper / (4 * world) + 4096);
 		const uint64_t sb = h->stream_base, rd = h->reads;
-		unsigned long long bad0 = 0; hipMemcpy(&bad0, &h->dstats->sender_bad, 8, hipMemcpyDeviceToHost);      /* a repeated attempt must not count the dropped k-mers twice */
+		unsigned long long bad0 = 0; hipMemcpy(&bad0, &h->dstats.get<DevStats>()->sender_bad, 8, hipMemcpyDeviceToHost);      /* a repeated attempt must not count the dropped k-mers twice */
 		for (;;) {
-			if (dev_malloc(&h->xo_dev, (size_t)world * segcap * rb) != hipSuccess) { hipFree(dcounts); h->xo_dev = nullptr; return fail(h, KMR_ERR_OOM, "owner segments"); }
+			if (h->xo_dev.alloc((size_t)world * segcap * rb) != hipSuccess) return fail(h, KMR_ERR_OOM, "owner segments");
 			h->stream_base = sb; h->reads = rd;             /* a repeated attempt stamps the same ordinals */
-			int rc = kmr_extract_by_owner_dev(h, batch->bases, batch->quals, batch->offsets, batch->n, batch->total, first_global_read_idx, nullptr, h->xo_dev, segcap, dcounts);
+			int rc = kmr_extract_by_owner_dev(h, batch->bases.get<uint8_t>(), batch->quals.get<uint8_t>(), batch->offsets.get<uint64_t>(), batch->n, batch->total, first_global_read_idx, nullptr, h->xo_dev.get(), segcap, dcounts.get());
 			if (!rc) rc = sync_state(h);
 			if (rc == KMR_ERR_CAPACITY && segcap < upper) {      /* a skewed batch: one owner takes more than its share */
-				uint32_t e = 0; hipMemcpy(&e, h->derr, 4, hipMemcpyDeviceToHost); e &= ~(uint32_t)ERR_SEGMENT_OVERFLOW; hipMemcpy(h->derr, &e, 4, hipMemcpyHostToDevice); hipMemcpy(&h->dstats->sender_bad, &bad0, 8, hipMemcpyHostToDevice);
-				hipFree(h->xo_dev); h->xo_dev = nullptr;
+				uint32_t e = 0; hipMemcpy(&e, h->derr.get<uint32_t>(), 4, hipMemcpyDeviceToHost); e &= ~(uint32_t)ERR_SEGMENT_OVERFLOW; hipMemcpy(h->derr.get<uint32_t>(), &e, 4, hipMemcpyHostToDevice); hipMemcpy(&h->dstats.get<DevStats>()->sender_bad, &bad0, 8, hipMemcpyHostToDevice);
+				h->xo_dev.reset();
 				segcap = std::min<uint64_t>(upper, segcap * 2);
 				continue;
 			}
-			if (rc) { hipFree(dcounts); hipFree(h->xo_dev); h->xo_dev = nullptr; return rc; }
+			if (rc) { h->xo_dev.reset(); return rc; }
 			break;
 		}
-		hipError_t e = hipMemcpy(h->xo_counts.data(), dcounts, 8 * world, hipMemcpyDeviceToHost);
-		hipFree(dcounts);
-		HIPCHK(h, e);
+		HIPCHK(h, hipMemcpy(h->xo_counts.data(), dcounts.get(), 8 * world, hipMemcpyDeviceToHost));
 		h->xo_segcap = segcap; h->xo_batch = batch; h->xo_first = first_global_read_idx;
 	}
 	uint64_t total = 0;
@@ -3749,10 +3675,10 @@ int kmr_extract_by_owner_host(kmr_handle *h, const kmr_reads *batch, uint64_t fi
 	if (capacity_bytes < total * rb) return fail(h, KMR_ERR_CAPACITY, "record buffer too small");
 	uint8_t *dst = (uint8_t *)records;
 	for (uint32_t r = 0; r < world; r++) {
-		if (h->xo_counts[r]) HIPCHK(h, hipMemcpy(dst, (const uint8_t *)h->xo_dev + (size_t)r * h->xo_segcap * rb, (size_t)h->xo_counts[r] * rb, hipMemcpyDeviceToHost));
+		if (h->xo_counts[r]) HIPCHK(h, hipMemcpy(dst, (const uint8_t *)h->xo_dev.get() + (size_t)r * h->xo_segcap * rb, (size_t)h->xo_counts[r] * rb, hipMemcpyDeviceToHost));
 		dst += (size_t)h->xo_counts[r] * rb;
 	}
-	hipFree(h->xo_dev); h->xo_dev = nullptr; h->xo_batch = nullptr;
+	h->xo_dev.reset(); h->xo_batch = nullptr;
 	return KMR_OK;
 }
 int kmr_insert_records(kmr_handle *h, const void *host_records, uint64_t n) {
@@ -3760,12 +3686,11 @@ int kmr_insert_records(kmr_handle *h, const void *host_records, uint64_t n) {
 	if (n == 0) return KMR_OK;
 	hipSetDevice(h->device);
 	const size_t bytes = (size_t)n * KMR_RECORD_BYTES(h->k, h->cfg.value_kind);
-	void *d = nullptr;
-	HIPCHK(h, dev_malloc(&d, bytes));
-	hipError_t e = hipMemcpy(d, host_records, bytes, hipMemcpyHostToDevice);
-	int rc = e == hipSuccess ? kmr_insert_records_dev(h, d, n) : KMR_ERR_HIP;
+	DevBuf d;
+	HIPCHK(h, d.alloc(bytes));
+	hipError_t e = hipMemcpy(d.get(), host_records, bytes, hipMemcpyHostToDevice);
+	int rc = e == hipSuccess ? kmr_insert_records_dev(h, d.get(), n) : KMR_ERR_HIP;
 	if (!rc) rc = sync_state(h); else hipStreamSynchronize(h->stream);
-	hipFree(d);
 	return rc;
 }
 
@@ -3799,17 +3724,17 @@ int kmr_sk_exchange_counts(kmr_handle *h, uint64_t *chunks, uint64_t *granules) 
 	const uint32_t world = h->cfg.world_size;
 	const uint64_t nl = sk_list_count(h->sk_bits);
 	unsigned int head = 0;
-	HIPCHK(h, hipMemcpy(&head, h->l1.head, 4, hipMemcpyDeviceToHost));
+	HIPCHK(h, hipMemcpy(&head, h->l1.head.get<unsigned int>(), 4, hipMemcpyDeviceToHost));
 	if (head > h->l1.cap) head = h->l1.cap;
-	unsigned long long *d = nullptr;
-	HIPCHK(h, dev_malloc((void **)&d, 16 * SK_OWNER_MAX)); HIPCHK(h, hipMemsetAsync(d, 0, 16 * SK_OWNER_MAX, h->stream));
-	hipLaunchKernelGGL(sk_close_kernel, dim3(grid_for(nl)), dim3(256), 0, h->stream, h->sk_state, nl, h->l1.chunk_count, h->l1.cap);
-	if (head) hipLaunchKernelGGL(sk_owner_count_kernel, dim3(grid_for(head)), dim3(256), 0, h->stream, h->l1.chunk_list, h->l1.chunk_count, head, world, d, d + SK_OWNER_MAX, h->xr_lo, h->xr_hi);
+	DevBuf db; HIPCHK(h, db.alloc(16 * SK_OWNER_MAX));
+	unsigned long long *d = db.get<unsigned long long>();
+	HIPCHK(h, hipMemsetAsync(d, 0, 16 * SK_OWNER_MAX, h->stream));
+	hipLaunchKernelGGL(sk_close_kernel, dim3(grid_for(nl)), dim3(256), 0, h->stream, h->sk_state.get<unsigned long long>(), nl, h->l1.chunk_count.get<uint32_t>(), h->l1.cap);
+	if (head) hipLaunchKernelGGL(sk_owner_count_kernel, dim3(grid_for(head)), dim3(256), 0, h->stream, h->l1.chunk_list.get<uint32_t>(), h->l1.chunk_count.get<uint32_t>(), head, world, d, d + SK_OWNER_MAX, h->xr_lo, h->xr_hi);
 	hipError_t e = hipGetLastError();
 	std::vector<unsigned long long> hv(2 * SK_OWNER_MAX, 0);
 	if (e == hipSuccess) e = hipMemcpyAsync(hv.data(), d, 16 * SK_OWNER_MAX, hipMemcpyDeviceToHost, h->stream);
 	if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-	hipFree(d);
 	HIPCHK(h, e);
 	for (uint32_t r = 0; r < world; r++) { chunks[r] = hv[r]; granules[r] = hv[SK_OWNER_MAX + r]; }
 	return KMR_OK;
@@ -3820,21 +3745,20 @@ int kmr_sk_exchange_pack_dev(kmr_handle *h, void *dev_data, void *dev_meta, cons
 	hipSetDevice(h->device);
 	const uint32_t world = h->cfg.world_size;
 	unsigned int head = 0;
-	HIPCHK(h, hipMemcpy(&head, h->l1.head, 4, hipMemcpyDeviceToHost));
+	HIPCHK(h, hipMemcpy(&head, h->l1.head.get<unsigned int>(), 4, hipMemcpyDeviceToHost));
 	if (head > h->l1.cap) head = h->l1.cap;
-	unsigned long long *d = nullptr;
-	HIPCHK(h, dev_malloc((void **)&d, 32 * SK_OWNER_MAX));
+	DevBuf db; HIPCHK(h, db.alloc(32 * SK_OWNER_MAX));
+	unsigned long long *d = db.get<unsigned long long>();
 	std::vector<unsigned long long> hv(4 * SK_OWNER_MAX, 0);
 	for (uint32_t r = 0; r < world; r++) { hv[r] = granule_offset[r]; hv[SK_OWNER_MAX + r] = chunk_offset[r]; }
 	hipError_t e = hipMemcpyAsync(d, hv.data(), 32 * SK_OWNER_MAX, hipMemcpyHostToDevice, h->stream);
 	if (e == hipSuccess && head) {
 		hipLaunchKernelGGL(sk_pack_kernel, dim3(grid_for((uint64_t)head * 64, 256, num_cus(h) * 8)), dim3(256), 0, h->stream, pool_view(h, h->l1), head, world, h->cfg.rank,
 		                   d, d + SK_OWNER_MAX, d + 2 * SK_OWNER_MAX, d + 3 * SK_OWNER_MAX, (uint4 *)dev_data, (uint2 *)dev_meta, h->xr_lo, h->xr_hi);
-		hipLaunchKernelGGL(sk_state_drop_kernel, dim3(grid_for(sk_list_count(h->sk_bits))), dim3(256), 0, h->stream, h->sk_state, sk_list_count(h->sk_bits), world, h->cfg.rank, h->xr_lo, h->xr_hi);
+		hipLaunchKernelGGL(sk_state_drop_kernel, dim3(grid_for(sk_list_count(h->sk_bits))), dim3(256), 0, h->stream, h->sk_state.get<unsigned long long>(), sk_list_count(h->sk_bits), world, h->cfg.rank, h->xr_lo, h->xr_hi);
 		e = hipGetLastError();
 	}
 	if (e == hipSuccess) e = hipStreamSynchronize(h->stream);      /* hv and d go out of scope */
-	hipFree(d);
 	HIPCHK(h, e);
 	return KMR_OK;
 }
@@ -3879,20 +3803,17 @@ int kmr_sk_exchange_adopt_dev(kmr_handle *h, const void *dev_data, const void *d
 	rc = pool_reserve(h, h->l1, n_chunks + n_granules / SK_CHUNK_G + (sk_list_count(h->sk_bits) / h->cfg.world_size) + (uint64_t)grid * SK_ADOPT_WAVES * 130 + 64, true); if (rc) return rc;
 	/* per-chunk counts and their scan: a grow-only buffer of the handle (a job adopts once per piece and batch) */
 	const size_t need = 8 * (n_chunks + 1) + 4 * (n_chunks + 1) + 256;
-	if (h->adopt_cap < need) {
-		if (h->adopt_buf) { hipStreamSynchronize(h->stream); hipFree(h->adopt_buf); h->adopt_buf = nullptr; h->adopt_cap = 0; }
-		HIPCHK(h, dev_malloc((void **)&h->adopt_buf, need + need / 4)); h->adopt_cap = need + need / 4;
-	}
-	uint64_t *start = (uint64_t *)h->adopt_buf; uint32_t *cnt = (uint32_t *)(h->adopt_buf + 8 * (n_chunks + 1));
+	rc = h->adopt_buf.reserve(h, "adopt_buf", need, need + need / 4); if (rc) return rc;
+	uint64_t *start = (uint64_t *)h->adopt_buf.get<uint8_t>(); uint32_t *cnt = (uint32_t *)(h->adopt_buf.get<uint8_t>() + 8 * (n_chunks + 1));
 	hipLaunchKernelGGL(sk_meta_counts_kernel, dim3(grid_for(n_chunks)), dim3(256), 0, h->stream, (const uint2 *)dev_meta, n_chunks, cnt);
 	rc = exclusive_scan(h, cnt, n_chunks, start);
 	if (!rc && !h->d_uni && !h->peers_declare) {
-		if (dev_malloc((void **)&h->d_uni, 8) != hipSuccess) rc = fail(h, KMR_ERR_OOM, "uniform-weight flags");
-		else { const uint32_t init[2] = {SK_UNI_NONE, 0u}; if (hipMemcpyAsync(h->d_uni, init, 8, hipMemcpyHostToDevice, h->stream) != hipSuccess) rc = fail(h, KMR_ERR_HIP, "uniform-weight flags"); else hipStreamSynchronize(h->stream); }
+		if (h->d_uni.alloc(8) != hipSuccess) rc = fail(h, KMR_ERR_OOM, "uniform-weight flags");
+		else { const uint32_t init[2] = {SK_UNI_NONE, 0u}; if (hipMemcpyAsync(h->d_uni.get<uint32_t>(), init, 8, hipMemcpyHostToDevice, h->stream) != hipSuccess) rc = fail(h, KMR_ERR_HIP, "uniform-weight flags"); else hipStreamSynchronize(h->stream); }
 	}
 	/* (senders that declare their weights -- kmr_sk_exchange_peer_uniform, what both drivers do -- spare the owner this look at every
 	 * received header: 3.5 ms for 4.2 GB at 8 ranks) */
-	if (!rc && !h->peers_declare) hipLaunchKernelGGL(sk_uniform_check_kernel, dim3(grid_for(n_chunks)), dim3(256), 0, h->stream, (const uint4 *)dev_data, start, cnt, n_chunks, h->d_uni);
+	if (!rc && !h->peers_declare) hipLaunchKernelGGL(sk_uniform_check_kernel, dim3(grid_for(n_chunks)), dim3(256), 0, h->stream, (const uint4 *)dev_data, start, cnt, n_chunks, h->d_uni.get<uint32_t>());
 	if (!rc) {
 		hipLaunchKernelGGL(sk_adopt_kernel, dim3(grid), dim3(SK_ADOPT_WAVES * 64), 0, h->stream, (const uint4 *)dev_data, (const uint2 *)dev_meta, start, n_chunks, sk_params(h), pool_view(h, h->l1));
 		if (hipGetLastError() != hipSuccess) rc = fail(h, KMR_ERR_HIP, "sk_adopt_kernel launch");

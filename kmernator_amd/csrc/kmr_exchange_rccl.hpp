@@ -75,7 +75,7 @@ int kmr_exchange_init(kmr_handle *h, const void *id) {
 	ncclComm_t comm = nullptr;
 	RCCLCHK(h, g_rccl.CommInitRank(&comm, (int)h->cfg.world_size, u, (int)h->cfg.rank));
 	h->xc_comm = comm;
-	HIPCHK(h, dev_malloc((void **)&h->xc_small, 8ull * (2 * SK_OWNER_MAX + 2) * (SK_OWNER_MAX + 1)));
+	HIPCHK(h, h->xc_small.alloc(8ull * (2 * SK_OWNER_MAX + 2) * (SK_OWNER_MAX + 1)));
 	h->xc_tr.user = h; h->xc_tr.allgather_u64 = rccl_allgather_u64; h->xc_tr.alltoallv_dev = rccl_alltoallv_dev;
 	return exchange_ready(h);
 }
@@ -85,28 +85,18 @@ int kmr_exchange_init_transport(kmr_handle *h, const kmr_transport *t) {
 	h->xc_tr = *t;
 	return exchange_ready(h);
 }
-static void exchange_free(kmr_handle *h) {      /* kmr_destroy */
+static void exchange_destroy_comm(kmr_handle *h) {      /* kmr_destroy: before the buffers it used */
 	if (h->xc_comm && g_rccl.CommDestroy) g_rccl.CommDestroy((ncclComm_t)h->xc_comm);
 	h->xc_comm = nullptr;
-	for (void **p : {&h->xc_send, &h->xc_send2, &h->xc_recv, &h->xc_recv2}) { if (*p) hipFree(*p); *p = nullptr; }
-	if (h->xc_small) hipFree(h->xc_small);
-	if (h->xc_dcounts) hipFree(h->xc_dcounts);
-	h->xc_small = nullptr; h->xc_dcounts = nullptr;
 }
-static int xc_reserve(kmr_handle *h, void **p, uint64_t &cap, uint64_t bytes) {
-	if (bytes <= cap && *p) return 0;
-	if (*p) { HIPCHK(h, hipStreamSynchronize(h->stream)); hipFree(*p); *p = nullptr; cap = 0; }
-	bytes = std::max<uint64_t>(bytes + bytes / 8, 4096);
-	if (dev_malloc(p, bytes) != hipSuccess) { *p = nullptr; return fail(h, KMR_ERR_OOM, "exchange buffers"); }
-	cap = bytes;
-	return 0;
-}
+/* grow-only send / receive buffers: an eighth to spare, 4 KB at least */
+static int xc_grow(kmr_handle *h, DevBuf &b, const char *what, uint64_t bytes) { return b.reserve(h, what, bytes, std::max<uint64_t>(bytes + bytes / 8, 4096)); }
 /* ---- the built-in transport: RCCL on the handle's stream */
 static int rccl_allgather_u64(void *user, const uint64_t *mine, uint64_t n, uint64_t *all) {
 	kmr_handle *h = (kmr_handle *)user;
 	const uint32_t world = h->cfg.world_size;
 	if (n > 2 * SK_OWNER_MAX + 2) return fail(h, KMR_ERR_INVALID_ARG, "allgather row too long");
-	unsigned long long *d = h->xc_small;      /* [n] mine, then [world][n] */
+	unsigned long long *d = h->xc_small.get<unsigned long long>();      /* [n] mine, then [world][n] */
 	HIPCHK(h, hipMemcpyAsync(d, mine, 8 * n, hipMemcpyHostToDevice, h->stream));
 	RCCLCHK(h, g_rccl.AllGather(d, d + n, n, ncclUint64, (ncclComm_t)h->xc_comm, h->stream));
 	HIPCHK(h, hipMemcpyAsync(all, d + n, 8 * n * world, hipMemcpyDeviceToHost, h->stream));
@@ -208,9 +198,9 @@ int kmr_exchange_add_reads_dev(kmr_handle *h, const void *dev_bases, const void 
 				goff[r] = ag; coff[r] = ac; ag += granules[r]; ac += chunks[r];
 			}
 		}
-		if (!lrc) lrc = xc_reserve(h, &h->xc_send, h->xc_send_cap, 16 * std::max<uint64_t>(ag, 1));
-		if (!lrc) lrc = xc_reserve(h, &h->xc_send2, h->xc_send2_cap, 8 * std::max<uint64_t>(ac, 1));
-		if (!lrc) lrc = kmr_sk_exchange_pack_dev(h, h->xc_send, h->xc_send2, goff.data(), coff.data());
+		if (!lrc) lrc = xc_grow(h, h->xc_send, "exchange buffer xc_send", 16 * std::max<uint64_t>(ag, 1));
+		if (!lrc) lrc = xc_grow(h, h->xc_send2, "exchange buffer xc_send2", 8 * std::max<uint64_t>(ac, 1));
+		if (!lrc) lrc = kmr_sk_exchange_pack_dev(h, h->xc_send.get(), h->xc_send2.get(), goff.data(), coff.data());
 		std::fill(mine.begin(), mine.end(), 0);
 		if (!lrc) for (uint32_t r = 0; r < world; r++) { mine[r] = chunks[r]; mine[world + r] = granules[r]; }
 		if (!lrc) { uint64_t ust = 0; kmr_sk_exchange_uniform(h, &ust); mine[2 * world] = ust; }
@@ -228,19 +218,19 @@ int kmr_exchange_add_reads_dev(kmr_handle *h, const void *dev_bases, const void 
 		}
 		const uint64_t slices = std::max<uint64_t>(1, (biggest + XC_MAX_MESSAGE - 1) / XC_MAX_MESSAGE);
 		/* the receive buffers are the last thing that can fail on one rank alone: one more (status-only) agreement before anything moves */
-		lrc = xc_reserve(h, &h->xc_recv, h->xc_recv_cap, std::max<uint64_t>(rg, 16));
-		if (!lrc) lrc = xc_reserve(h, &h->xc_recv2, h->xc_recv2_cap, std::max<uint64_t>(rcn, 8));
+		lrc = xc_grow(h, h->xc_recv, "exchange buffer xc_recv", std::max<uint64_t>(rg, 16));
+		if (!lrc) lrc = xc_grow(h, h->xc_recv2, "exchange buffer xc_recv2", std::max<uint64_t>(rcn, 8));
 		std::fill(mine.begin(), mine.end(), 0); status(lrc);
 		rc = xc_allgather_rows(h, mine, all); if (rc) return rc;
 		rc = xc_agree(h, lrc, all, row); if (rc) return rc;
 		time_begin(h, KMR_TIME_EXCHANGE, &ea, &eb);
-		rc = xc_alltoallv(h, (const uint8_t *)h->xc_send2, sco, scb, (uint8_t *)h->xc_recv2, rco, rc_c, 1, 8);
-		if (!rc) rc = xc_alltoallv(h, (const uint8_t *)h->xc_send, sgo, sgb, (uint8_t *)h->xc_recv, rgo, rc_g, slices, 16);
+		rc = xc_alltoallv(h, (const uint8_t *)h->xc_send2.get(), sco, scb, (uint8_t *)h->xc_recv2.get(), rco, rc_c, 1, 8);
+		if (!rc) rc = xc_alltoallv(h, (const uint8_t *)h->xc_send.get(), sgo, sgb, (uint8_t *)h->xc_recv.get(), rgo, rc_g, slices, 16);
 		time_end(h, KMR_TIME_EXCHANGE, ea, eb);
 		if (rc) return rc;
 		HIPCHK(h, hipStreamSynchronize(h->stream));
 		h->xc_bytes_to_peers += 16 * ag + 8 * ac;
-		if (rcn) { rc = kmr_sk_exchange_adopt_dev(h, h->xc_recv, h->xc_recv2, rcn / 8, rg / 16); if (rc) return rc; }
+		if (rcn) { rc = kmr_sk_exchange_adopt_dev(h, h->xc_recv.get(), h->xc_recv2.get(), rcn / 8, rg / 16); if (rc) return rc; }
 		return KMR_OK;
 	}
 	/* k-mer records: every owner's segment of this batch, the counts, the records, the insert */
@@ -248,18 +238,18 @@ int kmr_exchange_add_reads_dev(kmr_handle *h, const void *dev_bases, const void 
 	const uint64_t upper = total_bases + 64;
 	uint64_t segcap = std::min<uint64_t>(upper, upper / world + upper / (4 * world) + 4096);
 	const uint64_t sb = h->stream_base, rd = h->reads;
-	unsigned long long bad0 = 0; hipMemcpy(&bad0, &h->dstats->sender_bad, 8, hipMemcpyDeviceToHost);      /* a repeated attempt must not count the dropped k-mers twice */
+	unsigned long long bad0 = 0; hipMemcpy(&bad0, &h->dstats.get<DevStats>()->sender_bad, 8, hipMemcpyDeviceToHost);      /* a repeated attempt must not count the dropped k-mers twice */
 	std::vector<uint64_t> counts(world, 0);
-	if (!lrc && !h->xc_dcounts && dev_malloc((void **)&h->xc_dcounts, 8 * SK_OWNER_MAX) != hipSuccess) { h->xc_dcounts = nullptr; lrc = fail(h, KMR_ERR_OOM, "exchange counters"); }
-	unsigned long long *dcounts = h->xc_dcounts;
+	if (!lrc && !h->xc_dcounts && h->xc_dcounts.alloc(8 * SK_OWNER_MAX) != hipSuccess) lrc = fail(h, KMR_ERR_OOM, "exchange counters");
+	unsigned long long *dcounts = h->xc_dcounts.get<unsigned long long>();
 	while (!lrc) {      /* a skewed batch (one owner takes more than its share) is extracted again into larger segments */
-		lrc = xc_reserve(h, &h->xc_send, h->xc_send_cap, (uint64_t)world * segcap * rb); if (lrc) break;
+		lrc = xc_grow(h, h->xc_send, "exchange buffer xc_send", (uint64_t)world * segcap * rb); if (lrc) break;
 		h->stream_base = sb; h->reads = rd;
-		if (n_reads) lrc = kmr_extract_by_owner_dev(h, dev_bases, dev_quals, dev_offsets, n_reads, total_bases, first_global_read_idx, dev_discarded, h->xc_send, segcap, dcounts);
+		if (n_reads) lrc = kmr_extract_by_owner_dev(h, dev_bases, dev_quals, dev_offsets, n_reads, total_bases, first_global_read_idx, dev_discarded, h->xc_send.get(), segcap, dcounts);
 		else if (hipMemsetAsync(dcounts, 0, 8 * world, h->stream) != hipSuccess) lrc = fail(h, KMR_ERR_HIP, "hipMemsetAsync(exchange counters)");
 		if (!lrc) lrc = sync_state(h);
 		if (lrc == KMR_ERR_CAPACITY && segcap < upper) {
-			uint32_t e = 0; hipMemcpy(&e, h->derr, 4, hipMemcpyDeviceToHost); e &= ~(uint32_t)ERR_SEGMENT_OVERFLOW; hipMemcpy(h->derr, &e, 4, hipMemcpyHostToDevice); hipMemcpy(&h->dstats->sender_bad, &bad0, 8, hipMemcpyHostToDevice);
+			uint32_t e = 0; hipMemcpy(&e, h->derr.get<uint32_t>(), 4, hipMemcpyDeviceToHost); e &= ~(uint32_t)ERR_SEGMENT_OVERFLOW; hipMemcpy(h->derr.get<uint32_t>(), &e, 4, hipMemcpyHostToDevice); hipMemcpy(&h->dstats.get<DevStats>()->sender_bad, &bad0, 8, hipMemcpyHostToDevice);
 			segcap = std::min<uint64_t>(upper, segcap * 2);
 			lrc = 0;
 			continue;
@@ -279,18 +269,18 @@ int kmr_exchange_add_reads_dev(kmr_handle *h, const void *dev_bases, const void 
 		for (uint32_t q = 0; q < world; q++) if (q != r) biggest = std::max<uint64_t>(biggest, all[(size_t)r * row + q] * rb);
 	}
 	const uint64_t slices = std::max<uint64_t>(1, (biggest + XC_MAX_MESSAGE - 1) / XC_MAX_MESSAGE);
-	lrc = xc_reserve(h, &h->xc_recv, h->xc_recv_cap, std::max<uint64_t>(got, 16));
+	lrc = xc_grow(h, h->xc_recv, "exchange buffer xc_recv", std::max<uint64_t>(got, 16));
 	std::fill(mine.begin(), mine.end(), 0); status(lrc);
 	rc = xc_allgather_rows(h, mine, all); if (rc) return rc;
 	rc = xc_agree(h, lrc, all, row); if (rc) return rc;
 	time_begin(h, KMR_TIME_EXCHANGE, &ea, &eb);
-	rc = xc_alltoallv(h, (const uint8_t *)h->xc_send, soff, sbytes, (uint8_t *)h->xc_recv, roff, rbytes, slices, rb);
+	rc = xc_alltoallv(h, (const uint8_t *)h->xc_send.get(), soff, sbytes, (uint8_t *)h->xc_recv.get(), roff, rbytes, slices, rb);
 	time_end(h, KMR_TIME_EXCHANGE, ea, eb);
 	if (rc) return rc;
 	HIPCHK(h, hipStreamSynchronize(h->stream));
 	h->xc_bytes_to_peers += sent;
-	if (counts[rank]) { rc = kmr_insert_records_dev(h, (const uint8_t *)h->xc_send + (uint64_t)rank * segcap * rb, counts[rank]); if (rc) return rc; }
-	if (got) { rc = kmr_insert_records_dev(h, h->xc_recv, got / rb); if (rc) return rc; }
+	if (counts[rank]) { rc = kmr_insert_records_dev(h, (const uint8_t *)h->xc_send.get() + (uint64_t)rank * segcap * rb, counts[rank]); if (rc) return rc; }
+	if (got) { rc = kmr_insert_records_dev(h, h->xc_recv.get(), got / rb); if (rc) return rc; }
 	return sync_state(h);
 }
 int kmr_copy_to_host(kmr_handle *h, void *host_dst, const void *dev_src, uint64_t bytes) {
@@ -310,7 +300,7 @@ int kmr_copy_to_device(kmr_handle *h, void *dev_dst, const void *host_src, uint6
 int kmr_exchange_add_read_batch(kmr_handle *h, const kmr_reads *r, uint64_t first_global_read_idx) {
 	if (!h) return KMR_ERR_INVALID_ARG;
 	if (r && r->device != h->device) return fail(h, KMR_ERR_INVALID_ARG, "read batch lives on another device");
-	int rc = r ? kmr_exchange_add_reads_dev(h, r->bases, r->quals, r->offsets, r->n, r->total, first_global_read_idx, nullptr)
+	int rc = r ? kmr_exchange_add_reads_dev(h, r->bases.get<uint8_t>(), r->quals.get<uint8_t>(), r->offsets.get<uint64_t>(), r->n, r->total, first_global_read_idx, nullptr)
 	           : kmr_exchange_add_reads_dev(h, nullptr, nullptr, nullptr, 0, 0, first_global_read_idx, nullptr);
 	if (!rc) rc = kmr_sync(h);
 	return rc;
