@@ -11,6 +11,11 @@ shared genome and the k-mers travel to their owner over RCCL.  `python bench.py 
 the N ranks itself (python -m torch.distributed.run as a child process, before this process has
 touched a GPU); under an external launcher (WORLD_SIZE set) it is one of the ranks.
 
+A plain run sets up, warms up, times the steps, writes --dump-outputs if asked and prints its line: the headline, and the
+roofline and per-kernel figures of the timed steps themselves.  --full adds what takes runs or checks of its own: the CPU
+baseline (--no-cpu leaves it out), the PCIe-inclusive legs (--no-h2d), and the check of the line against the oracle's
+committed digests (oracle_check).
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -42,9 +47,11 @@ def parse_args():
     ap.add_argument("--reads", type=int, default=0, help="reads per GPU (default: C2 = 10M; with --gpus 8 C3 = 12.5M per GPU)")
     ap.add_argument("--quality", choices=["flat", "noisy"], default="flat", help="SURVEY 8(d): flat Q40 (the headline), or noisy "
                     "(Q in {40,30,20,10,2} with p = {.80,.10,.05,.04,.01}, errors at Q10: the divide chain and the discard path are live)")
-    ap.add_argument("--cpu-reads", type=int, default=1_000_000, help="reads of the CPU baseline's sample")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-h2d", action="store_true", help="skip the PCIe-inclusive leg")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline does not need: the CPU baseline, the "
+                    "PCIe-inclusive legs and the oracle check (each a run or check of its own, outside the timed steps)")
+    ap.add_argument("--cpu-reads", type=int, default=1_000_000, help="reads of the CPU baseline's sample (--full)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-h2d", action="store_true", help="--full without the PCIe-inclusive legs")
     ap.add_argument("--h2d-pieces", type=int, default=4, help="pieces the packed PCIe-inclusive leg sends a batch in")
     ap.add_argument("--force-exchange", action="store_true", help="run the owner-exchange path even on one GPU (sanity/timing of the N>1 code)")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true", help="development: all ranks share GPU 0 and talk over gloo (RCCL refuses two "
@@ -339,60 +346,61 @@ def main():
     # ones they receive, so the flat-quality case -- nothing discarded -- is the one that can be checked there)
     assert args.no_check or raw_total == total_kmers or (exchange and mode_num != 3 and args.quality != "flat"), (raw_total, total_kmers)
 
-    # The line checks itself against the ORACLE (outside the timed region): the ranks' statistics and map digests (kmr_map_digest: additive over
-    # owners) must add up to what the serial CPU oracle made of the same job (tests/golden/full_size_digests.json, written by
-    # tests/golden/make_full_size_digests.py in the build container) -- C2 flat / noisy on one GPU, the weak-scaling jobs at N = 2 / 4, and
-    # BASELINE config 3 at N = 8.  Configurations without a committed digest report null.
+    # --full: the line checks itself against the ORACLE (outside the timed region): the ranks' statistics and map digests (kmr_map_digest:
+    # additive over owners) must add up to what the serial CPU oracle made of the same job (tests/golden/full_size_digests.json, written
+    # by tests/golden/make_full_size_digests.py) -- C2 flat / noisy on one GPU, the weak-scaling jobs at N = 2 / 4, and BASELINE config 3
+    # at N = 8.  Configurations without a committed digest report null.
     oracle_check = None
-    try:
-        from helpers import add_digests, digests_agree, full_size_golden
-        gname = None
-        if args.build_mode in (0, 3) and not args.tune:
-            if world == 1 and n_reads == 10_000_000:
-                gname = "c2_flat" if args.quality == "flat" else "c2_noisy"
-            elif c3 and args.quality == "flat":
-                gname = "c3_flat"
-            elif world in (2, 4) and n_reads == 10_000_000 and args.quality == "flat":
-                gname = "scale_n%d" % world
+    if args.full:
         try:
-            gold = full_size_golden(gname) if gname else None
-        except KeyError:
-            gold = None
-        if gold is not None:
-            dg = sp.digest(0)
-            keys = ("raw_kmers", "raw_good_kmers", "unique_kmers", "singleton_kmers", "discarded", "weak_entries", "reads")
-            ints = [st[k_] for k_ in keys] + [dg[k_] for k_ in ("entries", "count_sum", "dir_sum", "hash_sum", "hash_xor")]
-            if dist is not None:
-                t = torch.tensor([v - (1 << 64) if v >= (1 << 63) else v for v in ints], dtype=torch.int64, device=red_dev)
-                every = [torch.zeros_like(t) for _ in range(world)]
-                dist.all_gather(every, t)
-                w = torch.tensor([dg["weighted_sum"]], dtype=torch.float64, device=red_dev)
-                dist.all_reduce(w)
-                rows = [[int(x) & 0xFFFFFFFFFFFFFFFF for x in e.cpu().tolist()] for e in every]
-                wsum = float(w.item())
-            else:
-                rows, wsum = [ints], dg["weighted_sum"]
-            stats_sum = {k_: sum(r[i] for r in rows) for i, k_ in enumerate(keys)}
-            dsum = None
-            for r in rows:
-                dsum = add_digests(dsum, dict(entries=r[7], count_sum=r[8], dir_sum=r[9], hash_sum=r[10], hash_xor=r[11], weighted_sum=0.0))
-            dsum["weighted_sum"] = wsum
-            oracle_check = {"config": gname, "statistics_equal": all(stats_sum[k_] == gold["stats"][k_] for k_ in keys),
-                            "weak_map_digest_equal": bool(digests_agree(dsum, gold["weak_digest"], 1e-6)),
-                            "what": "sum over ranks of kmr_get_stats and kmr_map_digest against the serial CPU oracle's (keys, counts, direction biases bit for bit; weightedCount sum within 1e-6)"}
-    except Exception as e:      # the check must never cost a bench line
-        oracle_check = {"error": repr(e)}
+            from helpers import add_digests, digests_agree, full_size_golden
+            gname = None
+            if args.build_mode in (0, 3) and not args.tune:
+                if world == 1 and n_reads == 10_000_000:
+                    gname = "c2_flat" if args.quality == "flat" else "c2_noisy"
+                elif c3 and args.quality == "flat":
+                    gname = "c3_flat"
+                elif world in (2, 4) and n_reads == 10_000_000 and args.quality == "flat":
+                    gname = "scale_n%d" % world
+            try:
+                gold = full_size_golden(gname) if gname else None
+            except KeyError:
+                gold = None
+            if gold is not None:
+                dg = sp.digest(0)
+                keys = ("raw_kmers", "raw_good_kmers", "unique_kmers", "singleton_kmers", "discarded", "weak_entries", "reads")
+                ints = [st[k_] for k_ in keys] + [dg[k_] for k_ in ("entries", "count_sum", "dir_sum", "hash_sum", "hash_xor")]
+                if dist is not None:
+                    t = torch.tensor([v - (1 << 64) if v >= (1 << 63) else v for v in ints], dtype=torch.int64, device=red_dev)
+                    every = [torch.zeros_like(t) for _ in range(world)]
+                    dist.all_gather(every, t)
+                    w = torch.tensor([dg["weighted_sum"]], dtype=torch.float64, device=red_dev)
+                    dist.all_reduce(w)
+                    rows = [[int(x) & 0xFFFFFFFFFFFFFFFF for x in e.cpu().tolist()] for e in every]
+                    wsum = float(w.item())
+                else:
+                    rows, wsum = [ints], dg["weighted_sum"]
+                stats_sum = {k_: sum(r[i] for r in rows) for i, k_ in enumerate(keys)}
+                dsum = None
+                for r in rows:
+                    dsum = add_digests(dsum, dict(entries=r[7], count_sum=r[8], dir_sum=r[9], hash_sum=r[10], hash_xor=r[11], weighted_sum=0.0))
+                dsum["weighted_sum"] = wsum
+                oracle_check = {"config": gname, "statistics_equal": all(stats_sum[k_] == gold["stats"][k_] for k_ in keys),
+                                "weak_map_digest_equal": bool(digests_agree(dsum, gold["weak_digest"], 1e-6)),
+                                "what": "sum over ranks of kmr_get_stats and kmr_map_digest against the serial CPU oracle's (keys, counts, direction biases bit for bit; weightedCount sum within 1e-6)"}
+        except Exception as e:      # the check must never cost a bench line
+            oracle_check = {"error": repr(e)}
 
     # the spectrum of the last timed step, before the PCIe-inclusive legs below build it again
     if args.dump_outputs:
         dump_outputs(sp, args.dump_outputs, rank, world)
 
-    # PCIe-inclusive legs (t_build from "first byte of in-memory reads available"): the reads start in pinned host memory and
+    # --full: PCIe-inclusive legs (t_build from "first byte of in-memory reads available"): the reads start in pinned host memory and
     # go to the device in eight pieces on a copy stream while the library's stream builds the pieces that have arrived.  Twice: as
     # text (kmr_add_reads_dev: a byte per base and per quality), and as the reference's Read keeps them (kmr_add_reads_twobit_dev:
     # bases 2-bit packed, every read on bytes of its own; one quality character for all bases where the input has just one)
     h2d = None
-    if not args.no_h2d and not exchange and rank == 0:
+    if args.full and not args.no_h2d and not exchange and rank == 0:
         lib_stream = torch.cuda.ExternalStream(sp.stream(), device=dev)
         copy_stream = torch.cuda.Stream(device=dev)
         uniform_q = args.quality == "flat"
@@ -534,7 +542,8 @@ def main():
                 out["roofline"]["dominant_kernel"] = {"name": dom["name"], "ms_per_launch": dom["ms_per_launch"],
                                                       "bytes_per_launch": dom["bytes_per_step"] / max(1, dom["launches_per_step"]),
                                                       "achieved_GBps": dom["achieved_GBps"], "frac": dom["frac"]}
-        out["oracle_check"] = oracle_check
+        if args.full:
+            out["oracle_check"] = oracle_check
         if exchange:
             out["exchange"] = {k: (v / max(1, args.steps) if isinstance(v, (int, float)) else v) for k, v in xstats.items()}
         # HBM bytes from the PMC counters: bench.py cannot run rocprofv3 on itself, so the committed summary of the same command
@@ -554,7 +563,7 @@ def main():
             # included: that figure, beside `value` (inputs resident in HBM, as the bench contract asks)
             out.update({"value_incl_h2d": h2d["value_incl_h2d"], "t_build_ms_incl_h2d": h2d["ms_per_step_incl_h2d"], "h2d_ms": h2d["h2d_ms"]})
             out["h2d"] = h2d
-        if not args.no_cpu and world == 1:
+        if args.full and not args.no_cpu and world == 1:
             out["cpu_baseline"] = cpu_baseline(torch, min(args.cpu_reads, n_reads), args.quality, dev)
         os.write(real_stdout, (json.dumps(out) + "\n").encode())
     if dist is not None:
