@@ -363,8 +363,9 @@ int kmr_sk_exchange_adopt_dev(kmr_handle *h, const void *dev_data, const void *d
 /* Do all records of this rank's lists carry ONE weight (every call so far took the bases-only extraction with the same quality
  * character)?  *state = kind << 32 | weight bits; kind 0: no record yet, 1: one weight, 2: several.  A sender hands its state to the
  * owners along with its chunk counts, an owner folds it in with kmr_sk_exchange_peer_uniform BEFORE adopting that sender's chunks: if all
- * agree, kmr_finalize counts with the one-weight form of the count pass.  An owner that is told nothing checks the received records
- * itself (a pass over every received header).  Nothing in the reference corresponds (its wire records carry a weight per k-mer,
+ * agree, kmr_finalize counts with the one-weight form of the count pass.  A declaration covers the NEXT kmr_sk_exchange_adopt_dev only
+ * (that call clears it, and so does kmr_reset): declare, before each adopt, for every sender whose chunks it carries.  An adopt that
+ * nobody declared for checks the received records itself (a pass over every received header).  Nothing in the reference corresponds (its wire records carry a weight per k-mer,
  * src/DistributedFunctions.h:274-303). */
 int kmr_sk_exchange_uniform(kmr_handle *h, uint64_t *state);
 int kmr_sk_exchange_peer_uniform(kmr_handle *h, uint64_t state);
@@ -374,7 +375,10 @@ int kmr_sk_exchange_peer_uniform(kmr_handle *h, uint64_t state);
  * list_hi NOW -- asynchronously on the handle's stream, into entry buffers of their own -- once everything those lists will ever get
  * has been adopted; kmr_finalize (same min_depth) then counts the lists from list_hi on and takes the early entries over.  The
  * result is that of kmr_finalize alone.  What cannot be counted early (extension values, a kept singleton map, the size tracker,
- * coarse lists, early buffers that turn out too small) is quietly left to kmr_finalize.  The reference's MPI build has no such
+ * coarse lists, early buffers that turn out too small) is quietly left to kmr_finalize.  The early pass has an error word of its
+ * own: an overflow of its buffers fails no call (not the next adopt, not a second kmr_count_lists_prefix, which replaces the early
+ * count and its flag, not kmr_finalize); kmr_finalize voids that early count and counts every list itself (kmr_build_info
+ * "early_overflowed"; kmr_tune "early_entry_share" sizes the buffers).  The reference's MPI build has no such
  * phase: its owners insert k-mers as messages arrive (src/DistributedFunctions.h:323-328) and purge at the end. */
 int kmr_sk_exchange_range(kmr_handle *h, uint64_t list_lo, uint64_t list_hi);
 int kmr_count_lists_prefix(kmr_handle *h, uint32_t min_depth, uint64_t list_hi);
@@ -615,12 +619,18 @@ void *kmr_stream(kmr_handle *h);
  *   unpack to text first).
  *   "uniform_count" (0: never the one-weight form of the count pass), "lean_extract" (0: never the bases-only extraction),
  *   "superkmer_window" (the widest minimizer window build_mode 3 may take: 32 (k >= 45) / 16 / 8 / 4).
+ *   "early_entry_share" (>= 0: kmr_count_lists_prefix's entry buffers hold that share of the good k-mers + 16 384 entries; < 0 = from the
+ *   list share, the default), "saturated_batch_bytes" (scratch budget of one batch of kmr_finalize's ordered pass over k-mers seen 256
+ *   times or more, 0 = 1 GiB; a key whose sightings alone exceed it is a batch of its own).
  * Call before the first kmr_add_reads* of a build.  KMR_ERR_INVALID_ARG for an unknown knob. */
 int kmr_tune(kmr_handle *h, const char *knob, double value);
 /* What the current build decided, for tests and measurement tools (the reference logs such figures, LOG_VERBOSE): "lists" = super-k-mer
  * lists of the build (0 before the first reads, or in another build mode), "uniform_count" = 1 if the last kmr_finalize ran the
  * count pass's one-weight form, "chunk_pool_chunks" = 1 KB chunks the pool holds, "superkmer_window" = the minimizer window in use, "early_lists" / "early_entries" = the bound below which the last
  * kmr_finalize took its lists' entries from kmr_count_lists_prefix (0: it counted everything itself) and how many entries those were,
+ * "early_overflowed" = 1 if the last kmr_finalize voided an early count because its buffers had overflowed, "saturated_keys" /
+ * "saturated_batches" = the weak entries of count 256 or more the last kmr_finalize of build_mode 3 redid in input order (all of them,
+ * every time) and in how many batches,
  * "device_blocks_live" = blocks of device memory the library holds at this moment in the whole process (every handle, read batch
  * and artifact filter; not only h's).  KMR_ERR_INVALID_ARG for an unknown name. */
 int kmr_build_info(kmr_handle *h, const char *what, double *value);

@@ -131,7 +131,7 @@ struct HandleMem {                   /* ... by kmr_destroy */
 	DevBuf sk_fine_state;            /* fine list state of an exchange (2^(sk_bits + sk_fine_shift) words) */
 	/* an exchange in steps over the list space (kmr_sk_exchange_range) and the lists below `hi` counted early (kmr_count_lists_prefix):
 	 * their entries wait in buffers of their own until kmr_finalize has counted the rest */
-	struct Early { bool active = false; uint64_t hi = 0; uint32_t min_depth = 0; DevBuf ue, cursor, fc; } early;
+	struct Early { bool active = false; uint64_t hi = 0; uint32_t min_depth = 0; DevBuf ue, cursor, fc, err; } early;      /* err: the early pass's own error word, read by kmr_finalize alone */
 	DevBuf xo_dev;                   /* kmr_extract_by_owner_host: owner segments of one batch kept on the device between the sizing call and the copy-out */
 };
 struct BuildMem {                    /* ... by kmr_release_table too: the streaming build's state */
@@ -169,6 +169,8 @@ struct Tuning {
 	int recycle = -1;                 /* -1 auto, 0 fresh chunks, 1 recycle the chunks a pass has just read */
 	int part_blocks = 0;              /* 0 = one partition block per CU */
 	double entry_share = -1.0;        /* >= 0: initial size of the count pass's entry buffers as a share of the records */
+	double early_entry_share = -1.0;  /* >= 0: size of kmr_count_lists_prefix's entry buffers as a share of the good k-mers (no CU slack) */
+	uint64_t saturated_batch_bytes = 0;      /* scratch budget of one batch of the saturated-key pass (0: SAT_BATCH_BYTES) */
 	bool no_lut = false, no_narrow = false, no_l1_state = false, no_stream_lookups = false;
 	uint64_t long_list_chunks = 0;     /* lists of more chunks are counted in pieces (0: 1024) */
 	uint64_t binned_min = 1ull << 18;  /* weak maps of at least this many entries are bucketed by the radix partition of kmr_buckets.hpp (build_mode 3) */
@@ -231,6 +233,8 @@ struct kmr_handle : HandleMem, BuildMem, ExchangeMem {
 	uint32_t peer_uni_w = 0xffffffffu; bool peer_uni_mixed = false, peers_declare = false;
 	uint64_t xr_lo = 0, xr_hi = ~0ull;      /* kmr_sk_exchange_range */
 	uint64_t last_early_hi = 0, last_early_entries = 0;      /* what the last kmr_finalize took over from an early count (kmr_build_info) */
+	bool last_early_overflowed = false;                       /* ... or that it voided one because its buffers overflowed */
+	uint64_t last_saturated_keys = 0, last_saturated_batches = 0;      /* what the last kmr_finalize's saturated-key pass redid, in how many batches */
 	bool qual_mixed = false;           /* a build that has seen two different quality characters stops asking (qrange) */
 	/* exchange with world_size > 1: sk_bits are the COARSE lists reads are scattered into and that travel; each holds 2^sk_fine_shift
 	 * fine lists, made by sk_refine_kernel before the count pass (fine state: sk_fine_state) */
@@ -1704,77 +1708,126 @@ int add_reads_superkmer(kmr_handle *h, const ReadsView &rv, uint64_t total_bases
 }
 /* k-mers seen SK_ORDERED_FROM times or more (sat_*_kernel in kmr_superkmer.hpp): weightedCount and directionBias of their entries in the
  * finished weak map from their first 65 535 sightings in input order, added into a float one after the other as the serial reference
- * does.  n_clamped: how many such keys the count pass kept, n_sightings: their sightings. */
+ * does.  n_clamped: how many such keys the count pass kept, n_sightings: their sightings.
+ * On high-coverage input (a small genome, an amplicon, a dominant species) nearly every key qualifies, and every sighting costs the
+ * pass 24 bytes of scratch (two key and two value arrays of the sort) -- more than the record pool the sightings came from.  So the
+ * keys are redone in batches of whole keys, taken in (list, entry) order: a batch is a run of lists (or of one list's keys) whose
+ * sightings, estimated from their chunks at the density of the whole pass, fit SAT_BATCH_BYTES, and holds fewer than 2^23 keys (the
+ * key's index in a batch has bits 41-63 of the sort key, sat_collect_kernel).  One list whose sightings alone exceed the budget (a
+ * homopolymer: 10^6 sightings and more) is a batch of its own.  A batch's scratch lives while that batch runs. */
+/* 1 GiB: ~4.5 x 10^7 sightings per batch, enough for the radix sort to run at full rate, and small against the 288 GB of a GPU and the
+ * record pool of any build that has that many sightings of hot keys (the pool holds them and all their neighbours) */
+static const uint64_t SAT_BATCH_BYTES = 1ull << 30;
+static const uint64_t SAT_BATCH_KEYS = (1ull << 23) - 1;
+static const uint64_t SAT_PAIR_BYTES = 24;
 template <int W> int saturated_fix_t(kmr_handle *h, const uint64_t *ls, const uint64_t *lc, uint64_t nl, unsigned long long n_clamped, unsigned long long n_sightings, uint32_t has_singletons) {
 	DevMap &wm = h->weak;
+	h->last_saturated_keys = 0; h->last_saturated_batches = 0;
 	if (!n_clamped || !wm.n) return 0;
 	uint32_t list_bits = 0; while ((1ull << list_bits) < nl) list_bits++;
 	if ((1ull << list_bits) != nl) list_bits = (uint32_t)nl;      /* a list count that is not a power of two is its own code (sk_list_of) */
-	DevBuf bfound, bentry, blist, bc0, bc1, bitems, bk_in, bk_out, bv_in, bv_out, btmp;      /* scratch of this call */
+	auto no_mem = [&](const char *what, size_t bytes) { return fail(h, KMR_ERR_OOM, std::string("saturated-key pass (weights of k-mers seen 256 times or more): no device memory for ") + what + " (" + std::to_string(bytes) + " bytes)"); };
 	auto dalloc = [](DevBuf &b, size_t bytes) { return b.alloc(std::max<size_t>(bytes, 256)); };
-	HIPCHK(h, dalloc(bfound, 8));
+	DevBuf bfound, bentry, blist;
+	if (dalloc(bfound, 8) != hipSuccess) return no_mem("a counter", 8);
 	unsigned long long *dfound = bfound.get<unsigned long long>(); uint64_t *d_entry = nullptr; uint32_t *d_list = nullptr;
 	uint64_t cap = std::min<uint64_t>(wm.n, 4 * n_clamped + 1024);
 	unsigned long long found = 0;
 	for (;;) {
-		HIPCHK(h, dalloc(bentry, 8 * cap)); HIPCHK(h, dalloc(blist, 4 * cap));
+		if (dalloc(bentry, 8 * cap) != hipSuccess || dalloc(blist, 4 * cap) != hipSuccess) return no_mem("the key list", 12 * cap);
 		d_entry = bentry.get<uint64_t>(); d_list = blist.get<uint32_t>();
 		HIPCHK(h, hipMemsetAsync(dfound, 0, 8, h->stream));
 		hipLaunchKernelGGL(sat_find_kernel<W>, dim3(grid_for(wm.n)), dim3(256), 0, h->stream, (const uint64_t *)wm.keys.get<uint64_t>(), (const uint32_t *)wm.vals.get<uint32_t>(), wm.n, h->sk_m, h->sk_off, h->sk_win, list_bits, dfound, cap, d_entry, d_list, h->ext ? 15u : 3u);
 		HIPCHK(h, hipGetLastError());
 		HIPCHK(h, hipMemcpyAsync(&found, dfound, 8, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
 		if (found <= cap) break;
-		cap = found;      /* more entries at exactly 65 535 than expected: again with room for all */
+		cap = found;      /* more entries at 256 or more than expected: again with room for all */
 	}
-	if (found >= (1ull << 23)) return 0;      /* (more than 8 x 10^6 saturated keys: left as the count pass made them) */
+	if (!found) return 0;
 	std::vector<uint64_t> entry(found); std::vector<uint32_t> lst(found);
 	HIPCHK(h, hipMemcpy(entry.data(), d_entry, 8 * found, hipMemcpyDeviceToHost)); HIPCHK(h, hipMemcpy(lst.data(), d_list, 4 * found, hipMemcpyDeviceToHost));
-	std::vector<uint32_t> order(found);
-	for (uint32_t i = 0; i < found; i++) order[i] = i;
-	std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return lst[a] != lst[b] ? lst[a] < lst[b] : entry[a] < entry[b]; });
+	std::vector<uint64_t> order(found);
+	for (uint64_t i = 0; i < found; i++) order[i] = i;
+	std::sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) { return lst[a] != lst[b] ? lst[a] < lst[b] : entry[a] < entry[b]; });
 	std::vector<uint64_t> sentry(found); std::vector<uint32_t> dl; std::vector<uint64_t> le0, le1;
-	for (uint32_t i = 0; i < found; i++) {
+	for (uint64_t i = 0; i < found; i++) {
 		sentry[i] = entry[order[i]];
 		const uint32_t l = lst[order[i]];
 		if (dl.empty() || dl.back() != l) { dl.push_back(l); le0.push_back(i); le1.push_back(i + 1); } else le1.back() = i + 1;
 	}
+	std::vector<uint64_t>().swap(entry); std::vector<uint32_t>().swap(lst); std::vector<uint64_t>().swap(order);
 	HIPCHK(h, hipMemcpy(d_entry, sentry.data(), 8 * found, hipMemcpyHostToDevice));
 	HIPCHK(h, hipMemcpy(d_list, dl.data(), 4 * dl.size(), hipMemcpyHostToDevice));
-	HIPCHK(h, dalloc(bc0, 8 * dl.size())); HIPCHK(h, dalloc(bc1, 8 * dl.size()));
-	uint64_t *d_c0 = bc0.get<uint64_t>(), *d_c1 = bc1.get<uint64_t>();
-	hipLaunchKernelGGL(sat_gather_kernel, dim3(grid_for(dl.size())), dim3(256), 0, h->stream, ls, (const uint32_t *)d_list, (uint64_t)dl.size(), d_c0, d_c1);
-	HIPCHK(h, hipGetLastError());
 	std::vector<uint64_t> c0(dl.size()), c1(dl.size());
-	HIPCHK(h, hipMemcpy(c0.data(), d_c0, 8 * dl.size(), hipMemcpyDeviceToHost)); HIPCHK(h, hipMemcpy(c1.data(), d_c1, 8 * dl.size(), hipMemcpyDeviceToHost));
-	/* work items: pieces of 256 chunks of those lists */
-	std::vector<uint64_t> ic0, ic1, ie0, ie1;
+	{
+		DevBuf bc0, bc1;
+		if (dalloc(bc0, 8 * dl.size()) != hipSuccess || dalloc(bc1, 8 * dl.size()) != hipSuccess) return no_mem("the chunk ranges", 16 * dl.size());
+		hipLaunchKernelGGL(sat_gather_kernel, dim3(grid_for(dl.size())), dim3(256), 0, h->stream, ls, (const uint32_t *)d_list, (uint64_t)dl.size(), bc0.get<uint64_t>(), bc1.get<uint64_t>());
+		HIPCHK(h, hipGetLastError());
+		HIPCHK(h, hipMemcpy(c0.data(), bc0.get<uint64_t>(), 8 * dl.size(), hipMemcpyDeviceToHost)); HIPCHK(h, hipMemcpy(c1.data(), bc1.get<uint64_t>(), 8 * dl.size(), hipMemcpyDeviceToHost));
+	}
+	blist = DevBuf();
+	/* segments: a list's keys, cut into runs of at most SAT_BATCH_KEYS (a run re-reads its list's chunks); their sightings estimated at
+	 * the pass's density (the count pass's sightings of such keys over the chunks of the lists that hold them) */
+	struct Seg { uint32_t li; uint64_t e0, e1, est; };
+	std::vector<Seg> segs;
+	uint64_t all_chunks = 0;
+	for (size_t i = 0; i < dl.size(); i++) all_chunks += c1[i] - c0[i];
+	const double per_chunk = all_chunks ? (double)n_sightings / (double)all_chunks : 0.0;
 	for (size_t i = 0; i < dl.size(); i++)
-		for (uint64_t a = c0[i]; a < c1[i]; a += 256) { ic0.push_back(a); ic1.push_back(std::min(c1[i], a + 256)); ie0.push_back(le0[i]); ie1.push_back(le1[i]); }
-	if (ic0.empty()) return 0;
-	const size_t ni = ic0.size();
-	HIPCHK(h, dalloc(bitems, 32 * ni));
-	uint64_t *d_items = bitems.get<uint64_t>();
-	HIPCHK(h, hipMemcpy(d_items, ic0.data(), 8 * ni, hipMemcpyHostToDevice)); HIPCHK(h, hipMemcpy(d_items + ni, ic1.data(), 8 * ni, hipMemcpyHostToDevice));
-	HIPCHK(h, hipMemcpy(d_items + 2 * ni, ie0.data(), 8 * ni, hipMemcpyHostToDevice)); HIPCHK(h, hipMemcpy(d_items + 3 * ni, ie1.data(), 8 * ni, hipMemcpyHostToDevice));
-	/* every sighting of those keys (the count pass has added up their true counts; entries of a map merged in later add theirs) */
-	const uint64_t pcap = n_sightings + (found - std::min<unsigned long long>(found, n_clamped)) * 65535ull + 64;
-	HIPCHK(h, dalloc(bk_in, 8 * pcap)); HIPCHK(h, dalloc(bk_out, 8 * pcap)); HIPCHK(h, dalloc(bv_in, 4 * pcap)); HIPCHK(h, dalloc(bv_out, 4 * pcap));
-	unsigned long long *pk_in = bk_in.get<unsigned long long>(), *pk_out = bk_out.get<unsigned long long>(); uint32_t *pv_in = bv_in.get<uint32_t>(), *pv_out = bv_out.get<uint32_t>();
-	HIPCHK(h, hipMemsetAsync(dfound, 0, 8, h->stream));
-	int rc = zero_work_counter(h); if (rc) return rc;
-	hipLaunchKernelGGL(sat_collect_kernel<W>, dim3((unsigned)std::min<uint64_t>(ni, (uint64_t)num_cus(h) * 4)), dim3(256), 0, h->stream, pool_view(h, h->l1), lc, h->k, (const uint64_t *)wm.keys.get<uint64_t>(), (const uint64_t *)d_entry,
-	                   (const uint64_t *)d_items, (const uint64_t *)(d_items + ni), (const uint64_t *)(d_items + 2 * ni), (const uint64_t *)(d_items + 3 * ni), (uint64_t)ni, dfound, pcap, pk_in, pv_in, h->work_counter.get<unsigned int>());
-	HIPCHK(h, hipGetLastError());
-	unsigned long long n_pairs = 0;
-	HIPCHK(h, hipMemcpyAsync(&n_pairs, dfound, 8, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
-	if (n_pairs > pcap) return fail(h, KMR_ERR_CAPACITY, "sightings of saturated k-mers (internal sizing error)");
-	size_t tmp_bytes = 0;
-	if (kmr::sort_pairs_u64_u32(nullptr, &tmp_bytes, pk_in, pk_out, pv_in, pv_out, n_pairs, h->stream) != 0) return fail(h, KMR_ERR_HIP, "radix sort (size query)");
-	HIPCHK(h, dalloc(btmp, tmp_bytes));
-	if (kmr::sort_pairs_u64_u32(btmp.get(), &tmp_bytes, pk_in, pk_out, pv_in, pv_out, n_pairs, h->stream) != 0) return fail(h, KMR_ERR_HIP, "radix sort");
-	hipLaunchKernelGGL(sat_reduce_kernel, dim3((unsigned)std::min<uint64_t>(found, 4096)), dim3(256), 0, h->stream, (const unsigned long long *)pk_out, (const uint32_t *)pv_out, (uint64_t)n_pairs, (const uint64_t *)d_entry, (uint64_t)found, has_singletons, wm.vals.get<uint32_t>(), h->ext ? 15u : 3u);
-	HIPCHK(h, hipGetLastError());
-	HIPCHK(h, hipStreamSynchronize(h->stream));
+		for (uint64_t a = le0[i]; a < le1[i]; a += SAT_BATCH_KEYS) {
+			const uint64_t b = std::min<uint64_t>(le1[i], a + SAT_BATCH_KEYS);
+			const double share = (double)(b - a) / (double)(le1[i] - le0[i]);
+			segs.push_back(Seg{(uint32_t)i, a, b, (uint64_t)(per_chunk * (double)(c1[i] - c0[i]) * share) + 1});
+		}
+	const uint64_t budget = h->tune.saturated_batch_bytes ? h->tune.saturated_batch_bytes : SAT_BATCH_BYTES;
+	uint64_t batches = 0;
+	for (size_t s0 = 0; s0 < segs.size(); ) {
+		/* the batch: segments s0 .. s1 - 1 (at least one) */
+		size_t s1 = s0 + 1; uint64_t est = segs[s0].est;
+		while (s1 < segs.size() && segs[s1].e1 - segs[s0].e0 <= SAT_BATCH_KEYS && (est + segs[s1].est) * SAT_PAIR_BYTES <= budget) est += segs[s1++].est;
+		const uint64_t k0 = segs[s0].e0, nk = segs[s1 - 1].e1 - k0;
+		/* work items: pieces of 256 chunks of the batch's lists, key indices relative to the batch */
+		std::vector<uint64_t> items;
+		for (size_t g = s0; g < s1; g++)
+			for (uint64_t a = c0[segs[g].li]; a < c1[segs[g].li]; a += 256) { items.push_back(a); items.push_back(std::min(c1[segs[g].li], a + 256)); items.push_back(segs[g].e0 - k0); items.push_back(segs[g].e1 - k0); }
+		const size_t ni = items.size() / 4;
+		std::vector<uint64_t> soa(4 * ni);
+		for (size_t i = 0; i < ni; i++) for (int q = 0; q < 4; q++) soa[q * ni + i] = items[4 * i + q];
+		uint64_t pcap = est + est / 4 + 1024;
+		for (int attempt = 0; ni; attempt++) {
+			DevBuf bitems, bk_in, bk_out, bv_in, bv_out, btmp;      /* the batch's scratch */
+			if (dalloc(bitems, 32 * ni) != hipSuccess) return no_mem("its work items", 32 * ni);
+			uint64_t *d_items = bitems.get<uint64_t>();
+			HIPCHK(h, hipMemcpy(d_items, soa.data(), 32 * ni, hipMemcpyHostToDevice));
+			if (dalloc(bk_in, 8 * pcap) != hipSuccess || dalloc(bk_out, 8 * pcap) != hipSuccess || dalloc(bv_in, 4 * pcap) != hipSuccess || dalloc(bv_out, 4 * pcap) != hipSuccess)
+				return no_mem("the sightings of one batch", SAT_PAIR_BYTES * pcap);
+			unsigned long long *pk_in = bk_in.get<unsigned long long>(), *pk_out = bk_out.get<unsigned long long>(); uint32_t *pv_in = bv_in.get<uint32_t>(), *pv_out = bv_out.get<uint32_t>();
+			HIPCHK(h, hipMemsetAsync(dfound, 0, 8, h->stream));
+			int rc = zero_work_counter(h); if (rc) return rc;
+			hipLaunchKernelGGL(sat_collect_kernel<W>, dim3((unsigned)std::min<uint64_t>(ni, (uint64_t)num_cus(h) * 4)), dim3(256), 0, h->stream, pool_view(h, h->l1), lc, h->k, (const uint64_t *)wm.keys.get<uint64_t>(), (const uint64_t *)(d_entry + k0),
+			                   (const uint64_t *)d_items, (const uint64_t *)(d_items + ni), (const uint64_t *)(d_items + 2 * ni), (const uint64_t *)(d_items + 3 * ni), (uint64_t)ni, dfound, pcap, pk_in, pv_in, h->work_counter.get<unsigned int>());
+			HIPCHK(h, hipGetLastError());
+			unsigned long long n_pairs = 0;
+			HIPCHK(h, hipMemcpyAsync(&n_pairs, dfound, 8, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
+			if (n_pairs > pcap) {      /* denser than the estimate: the batch again with room for exactly what it holds */
+				if (attempt) return fail(h, KMR_ERR_CAPACITY, "saturated-key pass: sightings of a batch changed between two passes (internal error)");
+				pcap = n_pairs;
+				continue;
+			}
+			size_t tmp_bytes = 0;
+			if (kmr::sort_pairs_u64_u32(nullptr, &tmp_bytes, pk_in, pk_out, pv_in, pv_out, n_pairs, h->stream) != 0) return fail(h, KMR_ERR_HIP, "saturated-key pass: radix sort (size query)");
+			if (dalloc(btmp, tmp_bytes) != hipSuccess) return no_mem("the sort's temporary storage", tmp_bytes);
+			if (kmr::sort_pairs_u64_u32(btmp.get(), &tmp_bytes, pk_in, pk_out, pv_in, pv_out, n_pairs, h->stream) != 0) return fail(h, KMR_ERR_HIP, "saturated-key pass: radix sort");
+			hipLaunchKernelGGL(sat_reduce_kernel, dim3((unsigned)std::min<uint64_t>(nk, 4096)), dim3(256), 0, h->stream, (const unsigned long long *)pk_out, (const uint32_t *)pv_out, (uint64_t)n_pairs, (const uint64_t *)(d_entry + k0), (uint64_t)nk, has_singletons, wm.vals.get<uint32_t>(), h->ext ? 15u : 3u);
+			HIPCHK(h, hipGetLastError());
+			HIPCHK(h, hipStreamSynchronize(h->stream));
+			break;
+		}
+		batches++;
+		s0 = s1;
+	}
+	h->last_saturated_keys = found; h->last_saturated_batches = batches;
 	return 0;
 }
 
@@ -1868,14 +1921,20 @@ template <int W> int finalize_superkmer_t(kmr_handle *h, uint32_t min_depth) {
 	/* lists below early.hi were counted by kmr_count_lists_prefix: this pass starts behind them and their entries are taken over below.
 	 * An early count that overflowed its buffers, or was made for another min-depth or map layout, is void: everything is counted here */
 	uint64_t early_slots = 0; FinalizeCounters early_c; memset(&early_c, 0, sizeof(early_c));
-	h->last_early_hi = 0; h->last_early_entries = 0;
+	h->last_early_hi = 0; h->last_early_entries = 0; h->last_early_overflowed = false;
 	if (h->early.active) {
-		uint32_t cerr0 = 0;
-		HIPCHK(h, hipMemcpy(&cerr0, h->derr.get<uint32_t>(), 4, hipMemcpyDeviceToHost));
+		uint32_t eerr = 0;      /* (the early pass's own word: its overflow never reaches h->derr, sync_state or another call) */
+		HIPCHK(h, hipMemcpy(&eerr, h->early.err.get<uint32_t>(), 4, hipMemcpyDeviceToHost));
 		unsigned long long ecur = 0;
 		HIPCHK(h, hipMemcpy(&ecur, h->early.cursor.get<unsigned long long>(), 8, hipMemcpyDeviceToHost)); HIPCHK(h, hipMemcpy(&early_c, h->early.fc.get(), sizeof(early_c), hipMemcpyDeviceToHost));
-		const bool ok = !(cerr0 & ERR_ENTRIES_FULL) && ecur <= packed_entries(h, h->early.ue) && h->early.min_depth == min_depth && !tracking && !ext && !keepSing && !refined;
-		if (cerr0 & ERR_ENTRIES_FULL) { cerr0 &= ~(uint32_t)ERR_ENTRIES_FULL; HIPCHK(h, hipMemcpy(h->derr.get<uint32_t>(), &cerr0, 4, hipMemcpyHostToDevice)); }
+		if (eerr & ~(uint32_t)ERR_ENTRIES_FULL) {      /* anything but an overflow is the build's error as ever */
+			uint32_t e = 0; HIPCHK(h, hipMemcpy(&e, h->derr.get<uint32_t>(), 4, hipMemcpyDeviceToHost)); e |= eerr & ~(uint32_t)ERR_ENTRIES_FULL;
+			HIPCHK(h, hipMemcpy(h->derr.get<uint32_t>(), &e, 4, hipMemcpyHostToDevice)); h->early.active = false;
+			time_end(h, 1, ea, eb); return sync_state(h);
+		}
+		const bool overflowed = (eerr & ERR_ENTRIES_FULL) || ecur > packed_entries(h, h->early.ue);
+		const bool ok = !overflowed && h->early.min_depth == min_depth && !tracking && !ext && !keepSing && !refined;
+		h->last_early_overflowed = overflowed;
 		if (ok) {
 			early_slots = ecur;
 			h->last_early_hi = h->early.hi; h->last_early_entries = early_c.weak_kept;
@@ -1998,6 +2057,7 @@ template <int W> int finalize_superkmer_t(kmr_handle *h, uint32_t min_depth) {
 	rc = finish_maps_from_entries(h, wc, sc, cur[0], cur[1], c.weak_kept, c.sing_kept, keepSing, !ext);
 	time_end(h, KMR_TIME_BUCKETS, tma, tmb);
 	if (rc) return rc;
+	h->last_saturated_keys = 0; h->last_saturated_batches = 0;
 	if (c.saturated) { rc = saturated_fix_t<W>(h, ls, lc, nl, c.saturated, c.sat_sightings, f.has_singletons); if (rc) return rc; }
 	time_end(h, 1, ea, eb);
 	h->has_singletons = keepSing;
@@ -2025,15 +2085,19 @@ template <int W> int count_prefix_superkmer_t(kmr_handle *h, uint32_t min_depth,
 	HIPCHK(h, hipGetLastError());
 	uint64_t *ls = nullptr, *lc = nullptr; uint32_t nch = 0;
 	rc = build_csr(h, h->l1, nl, 0, &ls, &lc, &nch); if (rc) return rc;
-	/* room: the share of the good k-mers that lies below hi, at the rate kmr_finalize starts with; too little is found out by
-	 * kmr_finalize (ERR_ENTRIES_FULL), which then counts everything itself */
+	/* room: the share of the good k-mers that lies below hi, at the rate kmr_finalize starts with.  Too little (low coverage, or an
+	 * owner whose lists hold more than its own reads' share) sets ERR_ENTRIES_FULL in the early pass's own error word, which only
+	 * kmr_finalize reads: it voids the early count and counts every list itself (kmr_build_info "early_overflowed") */
 	const uint64_t G = h->stats.raw_good_kmers;      /* (an owner's lists hold about as many k-mers as its own reads gave: the job's share of one rank) */
 	const uint64_t slack = (uint64_t)num_cus(h) * 4 * 8192 + 16;
-	const uint64_t want = (uint64_t)((double)G * ((double)hi / (double)nl) / (f.has_singletons ? 6.0 : 2.5)) + slack;
+	uint64_t want = (uint64_t)((double)G * ((double)hi / (double)nl) / (f.has_singletons ? 6.0 : 2.5)) + slack;
+	if (h->tune.early_entry_share >= 0) { want = (uint64_t)((double)G * h->tune.early_entry_share) + 16384; h->early.ue.reset(); }      /* kmr_tune "early_entry_share" */
 	rc = h->early.ue.reserve(h, "early count ue", 8ull * (W + 1) * want); if (rc) return rc;
 	rc = h->early.cursor.reserve(h, "early count cursor", 16); if (rc) return rc;
 	rc = h->early.fc.reserve(h, "early count fc", sizeof(FinalizeCounters)); if (rc) return rc;
+	rc = h->early.err.reserve(h, "early count error word", 4); if (rc) return rc;
 	HIPCHK(h, hipMemsetAsync(h->early.cursor.get<unsigned long long>(), 0, 16, h->stream)); HIPCHK(h, hipMemsetAsync(h->early.fc.get(), 0, sizeof(FinalizeCounters), h->stream));
+	HIPCHK(h, hipMemsetAsync(h->early.err.get<uint32_t>(), 0, 4, h->stream));      /* (a replaced early count leaves no flag behind) */
 	bool uni = false;
 	if (!h->sk_uni_mixed && !h->tune.no_uniform_count && !h->peer_uni_mixed && (W == 1 || (h->k & 31u) != 0)) {
 		uint32_t w = h->sk_uni_w; bool mixed = false;
@@ -2057,7 +2121,7 @@ template <int W> int count_prefix_superkmer_t(kmr_handle *h, uint32_t min_depth,
 	HIPCHK(h, hipMemsetAsync(sc, 0, 4 * h->nb_sing, h->stream));
 	CountOut out; out.wkeys = nullptr; out.wvals = nullptr; out.wentries = h->early.ue.get<uint64_t>(); out.wcursor = h->early.cursor.get<unsigned long long>(); out.wcap = packed_entries(h, h->early.ue);
 	out.skeys = nullptr; out.sweight = nullptr; out.spkt = nullptr; out.scursor = h->early.cursor.get<unsigned long long>() + 1; out.scap = 0;
-	out.weakCount = nullptr; out.singCount = sc; out.fc = (FinalizeCounters *)h->early.fc.get(); out.err = h->derr.get<uint32_t>();
+	out.weakCount = nullptr; out.singCount = sc; out.fc = (FinalizeCounters *)h->early.fc.get(); out.err = h->early.err.get<uint32_t>();
 	rc = zero_work_counter(h); if (rc) return rc;
 	const uint64_t n_work = hi > lg.list_first ? (hi - lg.list_first + lg.list_stride - 1) / lg.list_stride : 0;
 	if (n_work) {
@@ -2228,7 +2292,7 @@ int kmr_reset(kmr_handle *h) {
 		h->l1.used_ub = 0;
 		h->inserted_records = 0;
 		h->qual_mixed = false;
-		h->sk_uni_w = SK_UNI_NONE; h->sk_uni_mixed = false; h->peer_uni_w = SK_UNI_NONE; h->peer_uni_mixed = false;
+		h->sk_uni_w = SK_UNI_NONE; h->sk_uni_mixed = false; h->peer_uni_w = SK_UNI_NONE; h->peer_uni_mixed = false; h->peers_declare = false;
 		h->xr_lo = 0; h->xr_hi = ~0ull; h->early.active = false;
 		if (h->d_uni) { const uint32_t init[2] = {SK_UNI_NONE, 0u}; HIPCHK(h, hipMemcpyAsync(h->d_uni.get<uint32_t>(), init, 8, hipMemcpyHostToDevice, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream)); }
 		if (h->sk_state) hipLaunchKernelGGL(sk_state_init_kernel, dim3(grid_for(sk_list_count(h->sk_bits))), dim3(256), 0, h->stream, h->sk_state.get<unsigned long long>(), sk_list_count(h->sk_bits));
@@ -2280,6 +2344,8 @@ int kmr_tune(kmr_handle *h, const char *knob, double value) {
 	else if (k == "recycle_chunks") h->tune.recycle = value < 0 ? -1 : (value != 0 ? 1 : 0);
 	else if (k == "partition_blocks") h->tune.part_blocks = value >= 1 ? (int)value : 0;
 	else if (k == "entry_share") h->tune.entry_share = value;
+	else if (k == "early_entry_share") h->tune.early_entry_share = value;
+	else if (k == "saturated_batch_bytes") h->tune.saturated_batch_bytes = value >= 1 ? (uint64_t)value : 0;
 	else if (k == "lookup_table") h->tune.no_lut = value == 0;
 	else if (k == "stream_lookups") h->tune.no_stream_lookups = value == 0;
 	else if (k == "long_list_chunks") h->tune.long_list_chunks = value < 2 ? 2 : (uint64_t)value;
@@ -2313,6 +2379,9 @@ int kmr_build_info(kmr_handle *h, const char *what, double *value) {
 	else if (k == "superkmer_window") *value = (double)h->sk_win;
 	else if (k == "early_lists") *value = (double)h->last_early_hi;
 	else if (k == "early_entries") *value = (double)h->last_early_entries;
+	else if (k == "early_overflowed") *value = h->last_early_overflowed ? 1.0 : 0.0;
+	else if (k == "saturated_keys") *value = (double)h->last_saturated_keys;
+	else if (k == "saturated_batches") *value = (double)h->last_saturated_batches;
 	else if (k == "device_blocks_live") *value = (double)g_blocks_live.load();
 	else return fail(h, KMR_ERR_INVALID_ARG, "unknown build figure '" + k + "'");
 	return KMR_OK;
@@ -3787,7 +3856,7 @@ int kmr_sk_exchange_peer_uniform(kmr_handle *h, uint64_t state) {
 	if (!h) return KMR_ERR_INVALID_ARG;
 	const uint32_t kind = (uint32_t)(state >> 32), w = (uint32_t)state;
 	if (kind > 2) return fail(h, KMR_ERR_INVALID_ARG, "bad uniform-weight state");
-	h->peers_declare = true;
+	h->peers_declare = true;      /* arms the next kmr_sk_exchange_adopt_dev only */
 	if (kind == 2) h->peer_uni_mixed = true;
 	else if (kind == 1) { if (h->peer_uni_w == SK_UNI_NONE) h->peer_uni_w = w; else if (h->peer_uni_w != w) h->peer_uni_mixed = true; }
 	return KMR_OK;
@@ -3795,6 +3864,9 @@ int kmr_sk_exchange_peer_uniform(kmr_handle *h, uint64_t state) {
 int kmr_sk_exchange_adopt_dev(kmr_handle *h, const void *dev_data, const void *dev_meta, uint64_t n_chunks, uint64_t n_granules) {
 	if (!h || (n_chunks && (!dev_data || !dev_meta))) return KMR_ERR_INVALID_ARG;
 	int rc = sk_exchange_ready(h, "kmr_sk_exchange_adopt_dev"); if (rc) return rc;
+	/* the senders' declarations (kmr_sk_exchange_peer_uniform) cover this adopt and no other: one that nobody armed looks at the records */
+	const bool declared = h->peers_declare;
+	h->peers_declare = false;
 	if (n_chunks == 0) return KMR_OK;
 	hipSetDevice(h->device);
 	rc = sk_ensure_state(h); if (rc) return rc;
@@ -3807,13 +3879,13 @@ int kmr_sk_exchange_adopt_dev(kmr_handle *h, const void *dev_data, const void *d
 	uint64_t *start = (uint64_t *)h->adopt_buf.get<uint8_t>(); uint32_t *cnt = (uint32_t *)(h->adopt_buf.get<uint8_t>() + 8 * (n_chunks + 1));
 	hipLaunchKernelGGL(sk_meta_counts_kernel, dim3(grid_for(n_chunks)), dim3(256), 0, h->stream, (const uint2 *)dev_meta, n_chunks, cnt);
 	rc = exclusive_scan(h, cnt, n_chunks, start);
-	if (!rc && !h->d_uni && !h->peers_declare) {
+	if (!rc && !h->d_uni && !declared) {
 		if (h->d_uni.alloc(8) != hipSuccess) rc = fail(h, KMR_ERR_OOM, "uniform-weight flags");
 		else { const uint32_t init[2] = {SK_UNI_NONE, 0u}; if (hipMemcpyAsync(h->d_uni.get<uint32_t>(), init, 8, hipMemcpyHostToDevice, h->stream) != hipSuccess) rc = fail(h, KMR_ERR_HIP, "uniform-weight flags"); else hipStreamSynchronize(h->stream); }
 	}
 	/* (senders that declare their weights -- kmr_sk_exchange_peer_uniform, what both drivers do -- spare the owner this look at every
 	 * received header: 3.5 ms for 4.2 GB at 8 ranks) */
-	if (!rc && !h->peers_declare) hipLaunchKernelGGL(sk_uniform_check_kernel, dim3(grid_for(n_chunks)), dim3(256), 0, h->stream, (const uint4 *)dev_data, start, cnt, n_chunks, h->d_uni.get<uint32_t>());
+	if (!rc && !declared) hipLaunchKernelGGL(sk_uniform_check_kernel, dim3(grid_for(n_chunks)), dim3(256), 0, h->stream, (const uint4 *)dev_data, start, cnt, n_chunks, h->d_uni.get<uint32_t>());
 	if (!rc) {
 		hipLaunchKernelGGL(sk_adopt_kernel, dim3(grid), dim3(SK_ADOPT_WAVES * 64), 0, h->stream, (const uint4 *)dev_data, (const uint2 *)dev_meta, start, n_chunks, sk_params(h), pool_view(h, h->l1));
 		if (hipGetLastError() != hipSuccess) rc = fail(h, KMR_ERR_HIP, "sk_adopt_kernel launch");

@@ -765,6 +765,230 @@ def test_lists_counted_early_then_finalize(k, quality, share, n_rate):
     assert plain.stats() == early.stats() and np.array_equal(plain.image(KMR_MAP_WEAK), early.image(KMR_MAP_WEAK))
 
 
+def _world_handles(k, parts, est, **tune):
+    """one build_mode 3 handle per rank of an owner exchange, rank r fed parts[r] (global read indices and stream ordinals follow
+    the parts in order); handles for the same ranks and parts can be made again and adopt the same packed chunks"""
+    hs, first, base = [], 0, 0
+    for r, rb in enumerate(parts):
+        c = ka.default_config(k, estimated_raw_kmers=est, device=0, rank=r, world_size=len(parts), build_mode=3)
+        h = ka.KmerSpectrum(c).tune(**tune)
+        h.sk_exchange_begin()
+        if rb.n:
+            h.set_stream_origin(base)
+            add(h, rb, first)
+        h.sync()
+        first += rb.n
+        base += int(rb.offsets[-1])
+        hs.append(h)
+    return hs
+
+
+def _pack(h, rank, lo=None, hi=None):
+    """the chunks rank `rank` holds for every other owner (of the lists in [lo, hi) if given), packed on the device"""
+    import torch
+    dev = torch.device("cuda", 0)
+    if lo is not None:
+        h.sk_exchange_range(lo, hi)
+    chunks, granules = h.sk_exchange_counts()
+    sc = [int(x) if j != rank else 0 for j, x in enumerate(chunks)]
+    sg = [int(x) if j != rank else 0 for j, x in enumerate(granules)]
+    goff = [int(x) for x in np.concatenate([[0], np.cumsum(sg)[:-1]])]
+    coff = [int(x) for x in np.concatenate([[0], np.cumsum(sc)[:-1]])]
+    data = torch.empty((max(sum(sg), 1), 4), dtype=torch.int32, device=dev)
+    meta = torch.empty((max(sum(sc), 1), 2), dtype=torch.int32, device=dev)
+    h.sk_exchange_pack(data.data_ptr(), meta.data_ptr(), goff, coff)
+    return data, meta, sc, sg, goff, coff
+
+
+def _adopt(h, owner, packed):
+    data, meta, sc, sg, goff, coff = packed
+    assert sc[owner] > 0
+    h.sk_exchange_adopt(data[goff[owner]:].data_ptr(), meta[coff[owner]:].data_ptr(), sc[owner], sg[owner])
+
+
+@pytest.mark.parametrize("k,quality,share,n_rate", [(31, "flat", 0.5, 0.0), (51, "flat", 0.3, 0.0), (31, "noisy", 0.3, 0.001), (51, "noisy", 1.0, 0.001),
+                                                   (31, "flat", 1.0, 0.0), (51, "noisy", 0.5, 0.001)])
+def test_early_count_that_overflows_falls_back(k, quality, share, n_rate):
+    """kmr_count_lists_prefix sizes its entry buffers from a guess; when they turn out too small (low coverage, an owner with more than
+    its share of the lists) the early count is void and kmr_finalize counts every list itself -- the build does not fail.  The knob
+    early_entry_share = 0 leaves room for 16 384 entries only.  Statistics and weak image must be those of kmr_finalize alone, byte for
+    byte, after: overflow -> finalize; overflow -> a second early count with room (which is then taken) -> finalize."""
+    rb = synth_reads(40000, read_len=150, genome_len=300000, seed=660 + k, quality=quality, n_rate=n_rate)
+    cfg = default_config(k, estimated_raw_kmers=40000 * (150 - k + 1))
+    plain, early = product(cfg, 3), product(cfg, 3, early_entry_share=0.0)
+    add(plain, rb)
+    add(early, rb)
+    nl = int(early.build_info("lists"))
+    assert nl > 64
+    early.count_lists_prefix(2, int(nl * share))
+    plain.finalize(2)
+    early.finalize(2)
+    assert early.build_info("early_overflowed") == 1.0 and early.build_info("early_lists") == 0
+    assert plain.build_info("early_overflowed") == 0.0
+    assert plain.stats()["weak_entries"] * share > 4 * 16384          # (the overflow is real, not a near miss)
+    assert plain.stats() == early.stats()
+    assert np.array_equal(plain.image(KMR_MAP_WEAK), early.image(KMR_MAP_WEAK))
+    uni = 1.0 if (quality == "flat" and n_rate == 0.0) else 0.0
+    assert plain.build_info("uniform_count") == early.build_info("uniform_count") == uni
+    # an overflowing early count replaced by one with room: its flag must not outlive it, the second one is taken over
+    plain.reset()
+    early.reset()
+    add(plain, rb)
+    add(early, rb)
+    early.count_lists_prefix(2, int(nl * share))
+    early.tune(early_entry_share=-1)
+    early.count_lists_prefix(2, int(nl * share))
+    plain.finalize(2)
+    early.finalize(2)
+    assert early.build_info("early_overflowed") == 0.0 and early.build_info("early_lists") == int(nl * share)
+    assert early.build_info("early_entries") > 4 * 16384
+    assert plain.stats() == early.stats()
+    assert np.array_equal(plain.image(KMR_MAP_WEAK), early.image(KMR_MAP_WEAK))
+
+
+@pytest.mark.parametrize("k,quality,n_rate", [(31, "flat", 0.0), (51, "noisy", 0.001)])
+def test_early_count_that_overflows_then_adopt(k, quality, n_rate):
+    """An owner of a two-step exchange (world 2, two handles on this GPU): the lower half of the list space is adopted and counted early
+    -- into buffers that overflow --, then the upper half is adopted.  Neither the adopt nor kmr_finalize may fail on that overflow
+    (the early pass has an error word of its own); the owner's result is that of the same owner without an early count, byte for byte."""
+    rb = synth_reads(40000, read_len=150, genome_len=300000, seed=680 + k, quality=quality, n_rate=n_rate)
+    parts = [rb.slice(0, 22000), rb.slice(22000, 40000)]
+    est = 40000 * (150 - k + 1)
+    sender = _world_handles(k, parts, est)[1]
+    owners = [_world_handles(k, [parts[0], parts[1].slice(0, 0)], est)[0] for _ in range(2)]      # (rank 0 of the same job, twice)
+    owners[1].tune(early_entry_share=0.0)
+    nl = int(sender.build_info("lists"))
+    mid = nl // 2
+    for lo, hi in ((0, mid), (mid, 0xFFFFFFFFFFFFFFFF)):
+        pk = _pack(sender, 1, lo, hi)
+        for o in owners:
+            o.sk_exchange_peer_uniform(sender.sk_exchange_uniform())
+            _adopt(o, 0, pk)
+        if lo == 0:
+            owners[1].count_lists_prefix(2, mid)
+    for o in owners:
+        o.finalize(2)
+    assert owners[1].build_info("early_overflowed") == 1.0 and owners[1].build_info("early_lists") == 0
+    assert owners[0].stats() == owners[1].stats()
+    assert owners[0].stats()["weak_entries"] > 4 * 16384
+    assert np.array_equal(owners[0].image(KMR_MAP_WEAK), owners[1].image(KMR_MAP_WEAK))
+
+
+def _uniform_world(seed, flat=(True, True, False)):
+    """three ranks' reads: flat qualities without N (one weight per record: the bases-only extraction) or noisy with N"""
+    return [synth_reads(12000, read_len=150, genome_len=200000, seed=seed + r, quality="flat" if f else "noisy", n_rate=0.0 if f else 0.001)
+            for r, f in enumerate(flat)]
+
+
+def _same_owner_result(a, b):
+    assert a.stats() == b.stats()
+    assert np.array_equal(a.image(KMR_MAP_WEAK), b.image(KMR_MAP_WEAK))
+
+
+def _owner_pair(parts, est):
+    """two handles of rank 0 with its own reads only (the senders' parts empty): the one told things and the one told nothing"""
+    own = [parts[0]] + [p.slice(0, 0) for p in parts[1:]]
+    return _world_handles(31, own, est)[0], _world_handles(31, own, est)[0]
+
+
+def test_peer_declaration_covers_one_adopt():
+    """kmr_sk_exchange_peer_uniform arms the NEXT kmr_sk_exchange_adopt_dev only.  Owner 0 has flat reads; sender 1 (flat) declares and
+    is adopted; sender 2 (noisy) declares nothing and is adopted in a later call: its records must be looked at, the owner must count
+    with the general pass (uniform_count 0) and give what an owner told nothing at all gives, byte for byte"""
+    parts = _uniform_world(700)
+    est = sum(p.n for p in parts) * 120
+    snd = _world_handles(31, parts, est)
+    pk = {r: _pack(snd[r], r) for r in (1, 2)}
+    told, plain = _owner_pair(parts, est)
+    told.sk_exchange_peer_uniform(snd[1].sk_exchange_uniform())
+    _adopt(told, 0, pk[1])
+    _adopt(told, 0, pk[2])
+    _adopt(plain, 0, pk[1])
+    _adopt(plain, 0, pk[2])
+    told.finalize(2)
+    plain.finalize(2)
+    assert told.build_info("uniform_count") == 0.0 and plain.build_info("uniform_count") == 0.0
+    _same_owner_result(told, plain)
+
+
+def test_peer_declaration_does_not_survive_reset():
+    """a declaration made in one build is gone after kmr_reset: the next build's undeclared adopt of noisy records is looked at"""
+    parts = _uniform_world(710)
+    est = sum(p.n for p in parts) * 120
+    snd = _world_handles(31, parts, est)
+    pk = {r: _pack(snd[r], r) for r in (1, 2)}
+    told, plain = _owner_pair(parts, est)
+    told.sk_exchange_peer_uniform(snd[1].sk_exchange_uniform())
+    _adopt(told, 0, pk[1])
+    told.finalize(2)
+    assert told.build_info("uniform_count") == 1.0          # all flat and declared: the one-weight form
+    told.reset()
+    told.set_stream_origin(0)
+    add(told, parts[0], 0)
+    _adopt(told, 0, pk[2])
+    _adopt(plain, 0, pk[2])
+    told.finalize(2)
+    plain.finalize(2)
+    assert told.build_info("uniform_count") == 0.0 and plain.build_info("uniform_count") == 0.0
+    _same_owner_result(told, plain)
+
+
+def test_peer_declarations_keep_the_one_weight_pass():
+    """every sender flat and declaring before every adopt: the owner still counts with the one-weight form, and gives what the owner
+    that looked at the records itself gives"""
+    parts = _uniform_world(720, flat=(True, True, True))
+    est = sum(p.n for p in parts) * 120
+    snd = _world_handles(31, parts, est)
+    pk = {r: _pack(snd[r], r) for r in (1, 2)}
+    told, plain = _owner_pair(parts, est)
+    for r in (1, 2):
+        told.sk_exchange_peer_uniform(snd[r].sk_exchange_uniform())
+        _adopt(told, 0, pk[r])
+        _adopt(plain, 0, pk[r])
+    told.finalize(2)
+    plain.finalize(2)
+    assert told.build_info("uniform_count") == 1.0 and plain.build_info("uniform_count") == 1.0
+    _same_owner_result(told, plain)
+
+
+def test_partly_declared_owners_against_the_oracle():
+    """every rank of a world of three owns its lists; each one is told by its first sender only and adopts the other in a later call.
+    The union of the owners' weak maps must be the serial oracle's over all reads: keys, counts and directionBias exact, weightedCount
+    within the usual 1e-5 * count"""
+    parts = _uniform_world(730)
+    est = sum(p.n for p in parts) * 120
+    hs = _world_handles(31, parts, est)
+    pk = [_pack(hs[r], r) for r in range(3)]
+    for owner in range(3):
+        senders = [r for r in range(3) if r != owner]
+        hs[owner].sk_exchange_peer_uniform(hs[senders[0]].sk_exchange_uniform())
+        _adopt(hs[owner], owner, pk[senders[0]])
+        _adopt(hs[owner], owner, pk[senders[1]])
+    o = OracleSpectrum(default_config(31, estimated_raw_kmers=est))
+    first = 0
+    for p in parts:
+        o.add_reads(p, first_idx=first)
+        first += p.n
+    o.finalize(2)
+    okeys, ocnt, odir, ow, _ = o.entries()
+    want = {bytes(kk): i for i, kk in enumerate(okeys)}
+    seen = 0
+    for h in hs:
+        h.finalize(2)
+        assert h.build_info("uniform_count") == 0.0          # every owner holds noisy records
+        _, _, buckets = parse_image(h.image(KMR_MAP_WEAK), h.kb, 12)
+        for kk, v in buckets:
+            if not len(kk):
+                continue
+            v32 = np.ascontiguousarray(v).view(np.uint32).reshape(len(kk), 3)
+            idx = np.array([want[bytes(x)] for x in kk])
+            assert np.array_equal(v32[:, 0] & 0xffff, ocnt[idx])
+            assert np.array_equal(v32[:, 2] & 0xffff, odir[idx])
+            assert np.all(np.abs(v32[:, 1].view(np.float32).astype(np.float64) - ow[idx]) <= 1e-5 * ocnt[idx])
+            seen += len(kk)
+    assert seen == len(okeys) == o.stats()["weak_entries"]
+
+
 def test_host_batch_in_pieces_sizes_lists_from_the_whole_call():
     """kmr_add_reads / kmr_add_reads_twobit send a host batch to the device in pieces; without an estimate of the job's k-mers the first
     piece must size the lists (and the chunk pool) for the WHOLE call, as one device call does -- not for itself"""
@@ -1083,9 +1307,12 @@ def test_low_complexity_reads(mode):
         sat = sum(int(((np.ascontiguousarray(v).view(np.uint32).reshape(len(v), 3)[:, 0] & 0xffff) == 65535).sum()) for _, v in buckets if len(v))
         assert sat >= 3          # poly-A / poly-T and the two phases of the AC repeat
         # without a singleton map (no first sighting to set aside) and with the lists counted in pieces (merge table path)
-        for kw, tune in ((dict(separate_singletons=0), dict()), (dict(), dict(long_list_chunks=8))):
+        # ... and with a scratch budget of the ordered pass below one hot key's sightings: a batch that exceeds it alone still runs
+        for kw, tune in ((dict(separate_singletons=0), dict()), (dict(), dict(long_list_chunks=8)), (dict(), dict(saturated_batch_bytes=1 << 16))):
             o2, p2 = run_both(default_config(31, estimated_raw_kmers=24000 * 120, **kw), rb, mode=3, **tune)
             assert compare_weak_images(o2.image(KMR_MAP_WEAK), p2.image(KMR_MAP_WEAK), p2.kb, False) == o2.stats()["weak_entries"]
+            if "saturated_batch_bytes" in tune:
+                assert p2.build_info("saturated_batches") >= 1 and p2.build_info("saturated_keys") == int((o2.entries()[1] >= 256).sum()) >= 3
 
 
 @pytest.mark.parametrize("k,ext,kw,tune", [(31, False, {}, {}), (31, False, dict(separate_singletons=0), {}), (51, False, {}, dict(long_list_chunks=8)),
@@ -1121,6 +1348,42 @@ def test_high_count_kmers_keep_the_reference_order(k, ext, kw, tune):
     assert cnt.max() > 20000
     n = compare_weak_images(o.image(KMR_MAP_WEAK), p.image(KMR_MAP_WEAK), p.kb, ext, exact_from=256)
     assert n == o.stats()["weak_entries"]
+
+
+@pytest.mark.parametrize("k,kw,tune", [(31, {}, {}), (31, dict(separate_singletons=0), {}), (51, {}, {}), (51, dict(separate_singletons=0), {}),
+                                       (31, {}, dict(long_list_chunks=4))])
+def test_deep_coverage_redoes_every_hot_key_in_batches(k, kw, tune):
+    """High coverage (a 25 kb genome under 150 000 reads of 150 bases: several hundred sightings per key) puts nearly every genomic key
+    at 256 sightings or more, so the ordered pass (sat_*_kernel) redoes tens of thousands of keys and ~10^7 sightings.  It works in
+    batches of whole keys under a scratch budget: with a budget that makes several batches and with the default one (one batch here),
+    every entry must be the serial oracle's -- weightedCount bit for bit from 256 on --, and every such key must have been redone
+    (saturated_keys is the oracle's count of entries at 256 or more).  The pass's scratch lives only while it runs."""
+    rb = synth_reads(150000, read_len=150, genome_len=25000, seed=900 + k, err=0.002, quality="noisy", n_rate=0.0005)
+    cfg = default_config(k, estimated_raw_kmers=150000 * (150 - k + 1), **kw)
+    o = OracleSpectrum(cfg)
+    o.add_reads(rb)
+    o.finalize(2)
+    _, cnt, _, _, _ = o.entries()
+    hot = int((cnt >= 256).sum())
+    assert hot > 20000
+    for budget in (32 << 20, 0):
+        p = product(cfg, 3, saturated_batch_bytes=budget, **tune)
+        add(p, rb)
+        p.finalize(2)
+        assert p.build_info("saturated_keys") == hot
+        if budget:
+            assert p.build_info("saturated_batches") >= max(3, hot * 256 * 24 // budget // 2)      # (the budget cuts, not the key ceiling)
+        else:
+            assert p.build_info("saturated_batches") == 1
+        assert o.stats() == p.stats()
+        assert compare_weak_images(o.image(KMR_MAP_WEAK), p.image(KMR_MAP_WEAK), p.kb, False, exact_from=256) == o.stats()["weak_entries"]
+        # what finalize holds is the maps, not the pass: a second build in the same handle ends with no more device blocks than the first
+        live = p.build_info("device_blocks_live")
+        p.reset()
+        add(p, rb)
+        p.finalize(2)
+        assert p.build_info("device_blocks_live") <= live
+        p.close()
 
 
 @pytest.mark.parametrize("k,chunks", [(31, 2), (51, 3), (27, 16)])

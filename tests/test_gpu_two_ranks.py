@@ -202,3 +202,69 @@ def test_bench_n2_code_path_on_one_gpu(how):
     assert d["value"] > 0 and d["roofline"]["frac"] > 0
     assert abs(d["roofline"]["achieved"] * 1e9 - d["roofline"]["algorithmic_bytes_per_step"] / (d["ms_per_step"] / 1e3)) < 1e-3 * d["roofline"]["achieved"] * 1e9
     assert d["exchange"]["bytes_to_peers"] > 0 and d["exchange"]["alltoall_ms"] > 0
+
+
+def _skewed_reads():
+    """_reads() with every other read poly-A (one k-mer, one list, one owner that gets far more than its share of the lists)"""
+    rb = _reads()
+    bases = rb.bases.copy().reshape(N_READS, READ_LEN)
+    bases[::2] = ord("A")
+    return type(rb).from_arrays(bases.reshape(-1), rb.quals, rb.offsets)
+
+
+def _worker_early(rank, world, port, tmp, k):
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    torch.cuda.set_device(0)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        import kmernator_amd as ka
+        from kmernator_amd.distributed import build_partitioned_superkmers
+        dev = torch.device("cuda", 0)
+        lo, hi = _slice(rank, world)
+        rb = _skewed_reads().slice(lo, hi)
+        tb = torch.from_numpy(np.concatenate([rb.bases, np.zeros(64, np.uint8)])).to(dev)
+        tq = torch.from_numpy(np.concatenate([rb.quals, np.zeros(64, np.uint8)])).to(dev)
+        to = torch.from_numpy(rb.offsets.astype(np.int64)).to(dev)
+        sp = ka.KmerSpectrum(ka.default_config(k, estimated_raw_kmers=N_READS * (READ_LEN - k + 1), device=0, rank=rank, world_size=world, build_mode=3))
+        sp.tune(early_entry_share=0.0)          # the early count's buffers hold 16 384 entries: it overflows on every rank
+        build_partitioned_superkmers(sp, tb, tq, to, first_read_idx=lo, list_steps=2, early_min_depth=2)
+        sp.finalize(2)
+        np.save(os.path.join(tmp, "image.%d.npy" % rank), sp.image(KMR_MAP_WEAK))
+        st = sp.stats()
+        np.save(os.path.join(tmp, "stats.%d.npy" % rank), np.array([st["raw_kmers"], st["raw_good_kmers"], st["weak_entries"], st["unique_kmers"],
+                                                                     int(sp.build_info("early_overflowed")), int(sp.build_info("early_lists"))], dtype=np.int64))
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("world,k", [(2, 31), (3, 51)])
+def test_two_step_exchange_with_an_overflowing_early_count(world, k):
+    """build_partitioned_superkmers(list_steps=2, early_min_depth=2) with the early count's buffers far too small on every rank (skewed
+    reads: half of them poly-A): every rank's early count overflows and is voided, no rank fails, and the union of the ranks' weak
+    maps is the one-handle build's over the same reads -- keys, counts and directionBias."""
+    import kmernator_amd as ka
+    port = 33700 + (os.getpid() % 1500) + 7 * world + k
+    with tempfile.TemporaryDirectory() as tmp:
+        mp.spawn(_worker_early, args=(world, port, tmp, k), nprocs=world, join=True)
+        rb = _skewed_reads()
+        multi = ka.KmerSpectrum(ka.default_config(k, estimated_raw_kmers=N_READS * (READ_LEN - k + 1), device=0, build_mode=3))
+        for r in range(world):
+            lo, hi = _slice(r, world)
+            part = rb.slice(lo, hi)
+            multi.buildKmerSpectrum(part.bases, part.quals, part.offsets)
+        multi.finalize(2)
+        ms = multi.stats()
+        per = [np.load(os.path.join(tmp, "stats.%d.npy" % r)) for r in range(world)]
+        assert all(int(s[4]) == 1 and int(s[5]) == 0 for s in per), per
+        stats = sum(per)
+        assert (int(stats[0]), int(stats[1]), int(stats[2]), int(stats[3])) == (ms["raw_kmers"], ms["raw_good_kmers"], ms["weak_entries"], ms["unique_kmers"]), (stats, ms)
+        _, _, whole = parse_image(multi.image(KMR_MAP_WEAK), multi.kb, 12)
+        want = {bytes(kk): bytes(v[:2]) + bytes(v[8:]) for b_ in whole if len(b_[0]) for kk, v in zip(*b_)}      # count and directionBias
+        seen = 0
+        for r in range(world):
+            _, _, buckets = parse_image(np.load(os.path.join(tmp, "image.%d.npy" % r)), multi.kb, 12)
+            for kk, v in ((kk, v) for b_ in buckets if len(b_[0]) for kk, v in zip(*b_)):
+                assert want[bytes(kk)] == bytes(v[:2]) + bytes(v[8:])
+                seen += 1
+        assert seen == len(want) == ms["weak_entries"]

@@ -13,6 +13,7 @@ rounding bound of helpers.weight_bin_bound), per sampled entry and per k-mer cut
 getCount in both forms (counts exact, weights within helpers.weight_entry_bound, singleton and absent answers exact).  The build
 modes are still compared with each other where that is cheap."""
 import ctypes as C
+import hashlib
 import time
 
 import numpy as np
@@ -20,7 +21,7 @@ import pytest
 
 import kmernator_amd as ka
 from helpers import (KMR_MAP_SINGLETON, KMR_MAP_WEAK, KMR_VALUE_EXT, PROFILE_SAMPLE, RC_ABSENT, RC_SINGLETON, RC_WEAK, add_digests,
-                     digests_agree, full_size_golden, full_size_weights, synth_reads, weight_bin_ratio, weight_entry_ratio,
+                     digests_agree, full_size_golden, full_size_weights, parse_image, synth_reads, weight_bin_ratio, weight_entry_ratio,
                      weight_profile_of_image)
 
 pytestmark = pytest.mark.gpu
@@ -545,3 +546,54 @@ def test_config3_whole_input_on_one_gpu_against_the_oracle():
     sp.finalize(c["min_depth"])
     _assert_oracle(sp, g)
     sp.close()
+
+
+def test_low_coverage_early_count_overflows_and_falls_back():
+    """Low coverage (3 M reads on a 150 Mb genome: ~1.8 error-free sightings per genomic k-mer) keeps more weak entries per good k-mer
+    (~0.22) than kmr_count_lists_prefix's default buffers hold (1/6 of the good k-mers and a slack of 8192 per count block): with every
+    list counted early, the early pass overflows at its DEFAULT sizing.  kmr_finalize must then void it and count everything itself --
+    statistics and weak image those of kmr_finalize alone, byte for byte -- instead of failing on an "entry buffer overflow"."""
+    import torch
+    n, L, G, k = 3_000_000, 150, 150_000_000, 31
+    dev = torch.device("cuda", 0)
+    b, q, o = ka.synth_reads_device(torch, 41, 0, n, L, G, False, dev)
+    got = []
+    for early in (False, True):
+        p = ka.KmerSpectrum(ka.default_config(k, estimated_raw_kmers=n * (L - k + 1), device=0, build_mode=3))
+        p.buildKmerSpectrumDevice(b.data_ptr(), q.data_ptr(), o.data_ptr(), n, n * L, 0)
+        if early:
+            p.count_lists_prefix(2, int(p.build_info("lists")))
+        p.finalize(2)
+        if early:
+            assert p.build_info("early_overflowed") == 1.0 and p.build_info("early_lists") == 0
+        got.append((p.stats(), _image_digest(p)))
+        p.close()
+    assert got[0][1][0] > 16 + 20 * 60_000_000          # (more than 6 x 10^7 weak entries)
+    assert got[0] == got[1]
+
+
+def test_more_than_2_23_hot_keys_in_batches():
+    """More than 2^23 keys at 256 sightings or more (a 10 Mb genome under 34 M reads of 150 bases, k = 31: ~300 error-free sightings
+    per genomic k-mer): the ordered pass redoes every one of them -- no key ceiling -- in batches (the key index of a batch has 23 bits,
+    and its sightings a scratch budget).  saturated_keys must be the image's count of entries at 256 or more, and the weak image must
+    not depend on where the batches are cut: the default budget and one an eighth of it give the same bytes.  (A serial oracle is too
+    slow at this size; test_deep_coverage_redoes_every_hot_key_in_batches pins the values against it.)"""
+    import torch
+    n, L, G, k = 34_000_000, 150, 10_000_000, 31
+    dev = torch.device("cuda", 0)
+    b, q, o = ka.synth_reads_device(torch, 43, 0, n, L, G, False, dev)
+    got = []
+    for budget in (0, 1 << 27):
+        p = ka.KmerSpectrum(ka.default_config(k, estimated_raw_kmers=n * (L - k + 1), device=0, build_mode=3)).tune(saturated_batch_bytes=budget)
+        p.buildKmerSpectrumDevice(b.data_ptr(), q.data_ptr(), o.data_ptr(), n, n * L, 0)
+        p.finalize(2)
+        keys, batches = p.build_info("saturated_keys"), p.build_info("saturated_batches")
+        assert keys > 2 ** 23 and batches >= 2
+        img = p.image(KMR_MAP_WEAK)
+        _, _, buckets = parse_image(img, p.kb, 12)
+        assert keys == sum(int(((np.ascontiguousarray(v).view(np.uint32).reshape(len(v), 3)[:, 0] & 0xffff) >= 256).sum()) for _, v in buckets if len(v))
+        got.append((p.stats(), img.size, hashlib.blake2b(memoryview(img), digest_size=16).hexdigest(), batches))
+        del img, buckets
+        p.close()
+    assert got[1][3] > got[0][3]
+    assert got[0][:3] == got[1][:3]
