@@ -600,6 +600,79 @@ int kmr_artifact_filter_apply(kmr_handle *h, const kmr_artifact_filter *f, const
                               uint32_t *value, uint32_t *min_pass, uint32_t *max_pass, uint8_t *action,
                               uint32_t *remnant_off, uint32_t *remnant_len, kmr_reads **out);
 
+/* ---- selectReads / writePicks: pick the passing reads and write FilterReads' output on the device ----------
+ * selectReads (apps/FilterReads.h:159-279) with --max-kmer-output-depth and --partition-by-depth off:
+ * ReadSelector::pickAllPassingReads / pickAllPassingPairs (src/ReadSelector.h:547-596) and writePicks (:1242-1262).
+ * Per read i of a device-resident batch -- the reads as the artifact filter left them (kmr_artifact_filter_apply's *out)
+ * or an unfiltered batch -- and its results of the earlier stages:
+ *   passing[i]  isPassingRead (:550-557): not discarded (af_action[i] != 2), score[i] >= minimum_score and
+ *               passesLength(trim_length[i], length of read i in the batch, min_read_length) (:209-228, in float as there:
+ *               a length <= 1 fails; a minimum <= 1 is a fraction of the read, above 1 a number of bases)
+ *   pairs       mate[i] = index of the paired read or -1, the convention of kmr_artifact_filter_apply; NULL = every read
+ *               is single (pickAllPassingReads).  isPassingPair (:558-568): both reads must pass if both_pass is set
+ *               (--min-passing-in-pair 2), else either.  Every read of a passing pair is picked, also a mate that failed or
+ *               was discarded (pickIfNew only asks for availability, :513-542)
+ *   order       optimizePickOrder sorts the picks (:1212-1221): records appear in ascending read index
+ *   record      Read::toFastq / toFasta (src/Sequence.cpp:761-779): "@name[ label]\n" bases "\n+\n" quals "\n", or
+ *               ">name[ label]\n" bases "\n"; bases and quals are [trim_offset, trim_offset + trim_length) of the read.  A
+ *               discarded read, or a trim of at most one base, prints as the base N with the quality output_quality_base + 1
+ *               (src/Sequence.cpp:305-311, 729-733).  Qualities move from the handle's fastq_start_char to
+ *               output_quality_base (--fastq-output-base-quality)
+ *   name        the read's name span (name_off / name_len of kmr_reads_copy) in `text`, the FASTQ text the batch was
+ *               ingested from, up to the first blank or tab.  The caller hands that text in again (the library keeps no copy)
+ *   label       parts joined by single blanks (Read::LABEL_SEP): "AFTrim:<min_pass>+<max_pass - min_pass>" if af_action[i]
+ *               is 1, "Trim:<offset>+<length>" if was_trimmed[i], "<Label>:<(int)(score + 0.5)>" with Label = Score /
+ *               MedianScore / MinScore / MaxScore / AvgScore (getKmerScoringTypeLabel, :248-257, in kmr_scoring's order).
+ *               A discarded read was never scored (:1195-1197) and has no label
+ * Not covered: stored comments are not printed and a Casava "name 1:Y" is not rewritten to "name/1";
+ * --max-kmer-output-depth, --partition-by-depth and its remainder trim, per-input-file outputs, the unmasked formats and
+ * bimodal trimming.  Markup characters other than N, X and '.' are outside the parity claim: the reference applies a read's
+ * markup positions to the already trimmed string (src/Sequence.cpp:322-325, src/TwoBitSequence.cpp:317-327), so such a
+ * character lands on the wrong base when the trim offset is not 0, while the device prints the batch's own characters where
+ * they are (N and X never lie inside a k-mer trim: it ends before the first of them).
+ * Bounds: a batch holds fewer than 2^32 - 1 reads (KMR_ERR_UNSUPPORTED beyond); byte offsets of the output are 64-bit, its
+ * size is bounded by device memory alone.
+ * Every per-read array is host memory of kmr_reads_info's n_reads entries (the remnants the artifact filter appended
+ * included: mate -1, af_action 0 for them); mate may be NULL, the three af_* arrays may be NULL together.  An empty batch
+ * and zero picks are valid and give 0 bytes. */
+typedef struct kmr_select_config {
+	uint32_t struct_size;            /* = sizeof(kmr_select_config), ABI guard                                  */
+	uint32_t both_pass;              /* --min-passing-in-pair 2                                                 */
+	double   minimum_score;          /* --min-depth: the read's score must reach it (2)                         */
+	float    min_read_length;        /* --min-read-length (0.40): fraction of the read if <= 1, bases otherwise */
+	uint32_t output_quality_base;    /* --fastq-output-base-quality: 33 or 64 (33)                              */
+	uint32_t format;                 /* 0 = FASTQ, 1 = FASTA                                                    */
+	uint32_t scoring_type;           /* kmr_scoring: the score of the fused form, and the label (MEDIAN)        */
+} kmr_select_config;
+int kmr_select_config_init(kmr_select_config *cfg);      /* the reference's defaults */
+typedef struct kmr_picks kmr_picks;
+/* selection and output from host arrays as kmr_score_read_batch / kmr_score_counts_dev and kmr_artifact_filter_apply return them */
+int kmr_select_reads(kmr_handle *h, const kmr_reads *reads, const char *text, uint64_t text_len, const int64_t *mate,
+                     const uint8_t *af_action, const uint32_t *af_min_pass, const uint32_t *af_max_pass,
+                     const uint32_t *trim_offset, const uint32_t *trim_length, const float *score, const uint8_t *was_trimmed,
+                     const kmr_select_config *cfg, kmr_picks **out);
+/* The fused form: scoreAndTrimReads as kmr_score_read_batch (needs a finalized handle, KMR_ERR_STATE otherwise), then the
+ * selection, with the trims kept on the device.  cfg->minimum_score is both the k-mer threshold of the trim and the read
+ * threshold of the selection, as FilterReads hands minDepth to both (apps/FilterReads.cpp:197-199). */
+int kmr_filter_read_batch(kmr_handle *h, const kmr_reads *reads, const char *text, uint64_t text_len, const int64_t *mate,
+                          const uint8_t *af_action, const uint32_t *af_min_pass, const uint32_t *af_max_pass,
+                          const kmr_select_config *cfg, kmr_picks **out);
+/* the same two with the FASTQ text already in device memory */
+int kmr_select_reads_dev(kmr_handle *h, const kmr_reads *reads, const void *dev_text, uint64_t text_len, const int64_t *mate,
+                         const uint8_t *af_action, const uint32_t *af_min_pass, const uint32_t *af_max_pass,
+                         const uint32_t *trim_offset, const uint32_t *trim_length, const float *score, const uint8_t *was_trimmed,
+                         const kmr_select_config *cfg, kmr_picks **out);
+int kmr_filter_read_batch_dev(kmr_handle *h, const kmr_reads *reads, const void *dev_text, uint64_t text_len, const int64_t *mate,
+                              const uint8_t *af_action, const uint32_t *af_min_pass, const uint32_t *af_max_pass,
+                              const kmr_select_config *cfg, kmr_picks **out);
+/* picks (ReadSelector::getNumPicks) and the size of the output text */
+int kmr_picks_info(const kmr_picks *p, uint64_t *n_picked, uint64_t *bytes);
+/* the text to host memory (KMR_ERR_CAPACITY if capacity < bytes) and, unless NULL, one flag per read of the batch: 1 = picked */
+int kmr_picks_copy(const kmr_picks *p, char *dst, uint64_t capacity, uint8_t *picked_flags);
+/* the text where it lies (for a compressor or a device-aware MPI-IO); valid until kmr_picks_free */
+int kmr_picks_device_ptr(const kmr_picks *p, void **dev_text);
+void kmr_picks_free(kmr_picks *p);
+
 /* Raw HIP stream of the handle (hipStream_t) so callers can order their own
  * work (torch.cuda.ExternalStream) against it. */
 void *kmr_stream(kmr_handle *h);
@@ -622,6 +695,7 @@ void *kmr_stream(kmr_handle *h);
  *   "early_entry_share" (>= 0: kmr_count_lists_prefix's entry buffers hold that share of the good k-mers + 16 384 entries; < 0 = from the
  *   list share, the default), "saturated_batch_bytes" (scratch budget of one batch of kmr_finalize's ordered pass over k-mers seen 256
  *   times or more, 0 = 1 GiB; a key whose sightings alone exceed it is a batch of its own).
+ *   "select_timing" (1: kmr_select_reads* / kmr_filter_read_batch* time their phases with HIP events, see kmr_build_info; default 0).
  * Call before the first kmr_add_reads* of a build.  KMR_ERR_INVALID_ARG for an unknown knob. */
 int kmr_tune(kmr_handle *h, const char *knob, double value);
 /* What the current build decided, for tests and measurement tools (the reference logs such figures, LOG_VERBOSE): "lists" = super-k-mer
@@ -632,7 +706,8 @@ int kmr_tune(kmr_handle *h, const char *knob, double value);
  * "saturated_batches" = the weak entries of count 256 or more the last kmr_finalize of build_mode 3 redid in input order (all of them,
  * every time) and in how many batches,
  * "device_blocks_live" = blocks of device memory the library holds at this moment in the whole process (every handle, read batch
- * and artifact filter; not only h's).  KMR_ERR_INVALID_ARG for an unknown name. */
+ * and artifact filter; not only h's), "filter_score_ms" / "select_ms" / "select_write_ms" = HIP-event times of the last kmr_filter_read_batch* /
+ * kmr_select_reads* on this handle: its scoring, its selection with the writer, the writer alone (0 unless kmr_tune "select_timing" is set).  KMR_ERR_INVALID_ARG for an unknown name. */
 int kmr_build_info(kmr_handle *h, const char *what, double *value);
 
 /* Timing of the hot path measured with HIP events on the handle's stream

@@ -22,6 +22,7 @@
 #ifndef KMERNATOR_AMD_HPP_
 #define KMERNATOR_AMD_HPP_
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -90,6 +91,7 @@ public:
 	const kmr_reads *raw() const { return _r; }
 private:
 	friend class FilterKnownOddities;
+	friend class ReadSelector;
 	ReadSet(const std::string &text, kmr_reads *r) : _text(text), _r(r) { load(); }      /* a batch the library derived from another one */
 	void load();
 	std::string _text; kmr_reads *_r = nullptr; uint64_t _n = 0, _bases = 0, _filtered = 0; uint32_t _qbase = 0;
@@ -238,6 +240,66 @@ public:
 	}
 private:
 	KmerSpectrum &_sp; kmr_artifact_filter *_f = nullptr;
+};
+
+/* ReadSelector (src/ReadSelector.h) over a device-resident ReadSet: pickAllPassingReads / pickAllPassingPairs (:576-596) and writePicks
+ * (:1242-1262), selection and output text made on the device (kmr_select_reads, kmr_filter_read_batch).  mate = paired read or -1 per
+ * read of the batch `reads` was filtered from (nullptr: all single); af = the artifact filter's results for that batch.  Both are copied
+ * and extended over the remnants the filter appended to `reads` (single, untouched reads), so the arrays handed on always have
+ * reads.getSize() entries */
+class ReadSelector {
+public:
+	static kmr_select_config defaults() { kmr_select_config c; kmr_select_config_init(&c); return c; }
+	/* nMate = entries of mate (0: reads.getSize()) */
+	ReadSelector(KmerSpectrum &sp, const ReadSet &reads, const int64_t *mate = nullptr, const FilterKnownOddities::Results *af = nullptr, uint64_t nMate = 0) : _sp(sp), _reads(reads) {
+		const uint64_t n = reads.getSize(), m = n ? n : 1;
+		if (mate) {
+			if (!nMate) nMate = n;
+			if (nMate > n) throw KmerSpectrumError(KMR_ERR_INVALID_ARG, "ReadSelector: more mates than reads");
+			_mate.assign(m, -1); std::copy(mate, mate + nMate, _mate.begin());
+		}
+		if (af) {
+			const uint64_t k = std::min<uint64_t>(af->action.size(), std::min<uint64_t>(af->minPass.size(), af->maxPass.size()));
+			if (k > m) throw KmerSpectrumError(KMR_ERR_INVALID_ARG, "ReadSelector: more artifact filter results than reads");
+			_action.assign(m, 0); _minPass.assign(m, 0); _maxPass.assign(m, 0);
+			std::copy(af->action.begin(), af->action.begin() + k, _action.begin()); std::copy(af->minPass.begin(), af->minPass.begin() + k, _minPass.begin()); std::copy(af->maxPass.begin(), af->maxPass.begin() + k, _maxPass.begin());
+		}
+	}
+	~ReadSelector() { kmr_picks_free(_p); }
+	ReadSelector(const ReadSelector &) = delete; ReadSelector &operator=(const ReadSelector &) = delete;
+	/* scoreAndTrimReads + the selection in one call that keeps the trims on the device; returns the number of picks */
+	uint64_t filterReads(const kmr_select_config &cfg) {
+		reset();
+		_sp.check(kmr_filter_read_batch(_sp.raw(), _reads.raw(), _reads._text.data(), _reads._text.size(), mate(), action(), minPass(), maxPass(), &cfg, &_p), "kmr_filter_read_batch");
+		return getNumPicks();
+	}
+	/* the selection over trims the caller holds (KmerSpectrum::scoreAndTrimReads) */
+	uint64_t pickAllPassingPairs(const KmerSpectrum::TrimResult &t, const kmr_select_config &cfg) {
+		reset();
+		_sp.check(kmr_select_reads(_sp.raw(), _reads.raw(), _reads._text.data(), _reads._text.size(), mate(), action(), minPass(), maxPass(),
+		                           t.trimOffset.data(), t.trimLength.data(), t.score.data(), t.wasTrimmed.data(), &cfg, &_p), "kmr_select_reads");
+		return getNumPicks();
+	}
+	uint64_t getNumPicks() const { uint64_t n = 0; kmr_picks_info(_p, &n, nullptr); return n; }
+	/* the text of the picks; picked (optional) receives one flag per read of the batch */
+	std::string writePicks(std::vector<uint8_t> *picked = nullptr) const {
+		uint64_t bytes = 0;
+		if (kmr_picks_info(_p, nullptr, &bytes) != KMR_OK) throw KmerSpectrumError(KMR_ERR_STATE, "writePicks: nothing has been picked");
+		std::string out(bytes, '\0');
+		if (picked) picked->assign(_reads.getSize() ? _reads.getSize() : 1, 0);
+		const int rc = kmr_picks_copy(_p, &out[0], bytes, picked ? picked->data() : nullptr);
+		if (rc != KMR_OK) throw KmerSpectrumError(rc, "kmr_picks_copy");
+		if (picked) picked->resize(_reads.getSize());
+		return out;
+	}
+	const kmr_picks *raw() const { return _p; }
+private:
+	void reset() { kmr_picks_free(_p); _p = nullptr; }
+	const int64_t *mate() const { return _mate.empty() ? nullptr : _mate.data(); }
+	const uint8_t *action() const { return _action.empty() ? nullptr : _action.data(); }
+	const uint32_t *minPass() const { return _minPass.empty() ? nullptr : _minPass.data(); }
+	const uint32_t *maxPass() const { return _maxPass.empty() ? nullptr : _maxPass.data(); }
+	KmerSpectrum &_sp; const ReadSet &_reads; std::vector<int64_t> _mate; std::vector<uint8_t> _action; std::vector<uint32_t> _minPass, _maxPass; kmr_picks *_p = nullptr;
 };
 
 }  // namespace kmernator

@@ -60,6 +60,12 @@ class KmrArtifactConfig(C.Structure):
                                           "phix_idx", "reference_begin", "min_quality", "fastq_start_char")] + [("min_read_length", C.c_float)]
 
 
+class KmrSelectConfig(C.Structure):
+    """kmr_select_config"""
+    _fields_ = [("struct_size", C.c_uint32), ("both_pass", C.c_uint32), ("minimum_score", C.c_double), ("min_read_length", C.c_float),
+                ("output_quality_base", C.c_uint32), ("format", C.c_uint32), ("scoring_type", C.c_uint32)]
+
+
 # every symbol include/kmernator_amd.h declares
 EXPORTS = [
     "kmr_abi_version", "kmr_config_init", "kmr_create", "kmr_destroy", "kmr_last_error", "kmr_num_buckets",
@@ -74,6 +80,8 @@ EXPORTS = [
     "kmr_artifact_filter_free", "kmr_artifact_filter_apply",
     "kmr_tune", "kmr_set_stream_origin", "kmr_size_tracker", "kmr_exchange_unique_id", "kmr_exchange_init", "kmr_exchange_init_transport", "kmr_exchange_add_reads_dev", "kmr_exchange_add_read_batch", "kmr_exchange_stats", "kmr_copy_to_host", "kmr_copy_to_device", "kmr_sk_exchange_begin", "kmr_sk_exchange_counts", "kmr_sk_exchange_pack_dev", "kmr_sk_exchange_adopt_dev", "kmr_extract_by_owner_host", "kmr_insert_records", "kmr_reads_from_host", "kmr_reads_from_twobit", "kmr_reads_twobit", "kmr_lookup_requests_dev", "kmr_lookup_keys_dev", "kmr_scatter_counts_dev", "kmr_score_counts_dev",
     "kmr_lookup_weighted", "kmr_lookup_reads_weighted", "kmr_lookup_keys_weighted_dev",
+    "kmr_select_config_init", "kmr_select_reads", "kmr_select_reads_dev", "kmr_filter_read_batch", "kmr_filter_read_batch_dev",
+    "kmr_picks_info", "kmr_picks_copy", "kmr_picks_device_ptr", "kmr_picks_free",
     "kmr_map_digest", "kmr_synth_reads_dev", "kmr_build_info", "kmr_sk_exchange_uniform", "kmr_sk_exchange_peer_uniform", "kmr_sk_exchange_range", "kmr_count_lists_prefix",
 ]
 
@@ -187,6 +195,17 @@ def load():
     lib.kmr_sk_exchange_range.argtypes = [vp, C.c_uint64, C.c_uint64]
     lib.kmr_count_lists_prefix.argtypes = [vp, C.c_uint32, C.c_uint64]
     lib.kmr_synth_reads_dev.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, vp, vp, vp]
+    i64p, f32p, scp = C.POINTER(C.c_int64), C.POINTER(C.c_float), C.POINTER(KmrSelectConfig)
+    lib.kmr_select_config_init.argtypes = [scp]
+    for name in ("kmr_select_reads", "kmr_select_reads_dev"):
+        getattr(lib, name).argtypes = [vp, vp, vp, C.c_uint64, i64p, u8p, u32p, u32p, u32p, u32p, f32p, u8p, scp, C.POINTER(vp)]
+    for name in ("kmr_filter_read_batch", "kmr_filter_read_batch_dev"):
+        getattr(lib, name).argtypes = [vp, vp, vp, C.c_uint64, i64p, u8p, u32p, u32p, scp, C.POINTER(vp)]
+    lib.kmr_picks_info.argtypes = [vp, u64p, u64p]
+    lib.kmr_picks_copy.argtypes = [vp, vp, C.c_uint64, u8p]
+    lib.kmr_picks_device_ptr.argtypes = [vp, C.POINTER(vp)]
+    lib.kmr_picks_free.argtypes = [vp]
+    lib.kmr_picks_free.restype = None
     _lib = lib
     return lib
 

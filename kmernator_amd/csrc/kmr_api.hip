@@ -28,6 +28,7 @@
 #include "kmr_partition.hpp"
 #include "kmr_ingest.hpp"
 #include "kmr_artifact.hpp"
+#include "kmr_select.hpp"
 #include "kmr_superkmer.hpp"
 #include "kmr_buckets.hpp"
 #include "kmr_synth.hpp"
@@ -181,6 +182,7 @@ struct Tuning {
 	bool no_uniform_count = false;     /* never take sk_count_kernel<.., UNI> (A/B runs, tests of the general count pass on one-weight builds) */
 	bool no_lean_extract = false;      /* never take sk_extract_lean_kernel (A/B runs, tests of the general kernel on uniform qualities) */
 	bool exchange_fail_once = false;   /* tests: the next kmr_exchange_add_reads_dev of this rank fails locally (the other ranks must come back with an error, not hang) */
+	bool select_timing = false;        /* kmr_select_* / kmr_filter_*: time scoring, selection and writer with HIP events (kmr_build_info; measurement tools) */
 	bool no_coarse_lists = true;       /* exchange: scatter into the job's fine lists (default) or, kmr_tune("coarse_lists", 1), into coarse ones that the owner splits before the count pass (sk_refine_kernel: not yet fast enough to pay) */
 };
 
@@ -234,6 +236,7 @@ struct kmr_handle : HandleMem, BuildMem, ExchangeMem {
 	uint64_t xr_lo = 0, xr_hi = ~0ull;      /* kmr_sk_exchange_range */
 	uint64_t last_early_hi = 0, last_early_entries = 0;      /* what the last kmr_finalize took over from an early count (kmr_build_info) */
 	bool last_early_overflowed = false;                       /* ... or that it voided one because its buffers overflowed */
+	double last_score_ms = 0, last_select_ms = 0, last_write_ms = 0;      /* the last kmr_filter_read_batch* / kmr_select_reads*: scoring, selection + writer, writer alone (HIP events, taken with kmr_tune "select_timing" only; kmr_build_info) */
 	uint64_t last_saturated_keys = 0, last_saturated_batches = 0;      /* what the last kmr_finalize's saturated-key pass redid, in how many batches */
 	bool qual_mixed = false;           /* a build that has seen two different quality characters stops asking (qrange) */
 	/* exchange with world_size > 1: sk_bits are the COARSE lists reads are scattered into and that travel; each holds 2^sk_fine_shift
@@ -249,6 +252,13 @@ struct kmr_handle : HandleMem, BuildMem, ExchangeMem {
 	double ms[KMR_TIME_GROUPS] = {0};
 	uint64_t launches[KMR_TIME_GROUPS] = {0};
 	std::vector<std::pair<hipEvent_t, hipEvent_t> > pending_events[KMR_TIME_GROUPS];
+};
+
+/* what kmr_select_reads* / kmr_filter_read_batch* leave on the device: the output text and the per-read pick flags */
+struct kmr_picks {
+	int device = 0;
+	DevBuf text, picked;
+	uint64_t n = 0, n_picked = 0, bytes = 0;
 };
 
 /* device-resident read batch produced by kmr_ingest_fastq* */
@@ -2358,6 +2368,7 @@ int kmr_tune(kmr_handle *h, const char *knob, double value) {
 	else if (k == "exchange_fail_once") h->tune.exchange_fail_once = value != 0;
 	else if (k == "binned_buckets_min") h->tune.binned_min = value >= 0 ? (uint64_t)value : ~0ull;        /* < 0: never */
 	else if (k == "coarse_lists") h->tune.no_coarse_lists = value == 0;
+	else if (k == "select_timing") h->tune.select_timing = value != 0;
 	else if (k == "narrow_tallies") h->tune.no_narrow = value == 0;
 	else if (k == "keep_level1_state") h->tune.no_l1_state = value == 0;
 	else if (k == "superkmer_window") {      /* largest minimizer window the geometry may take (32 / 16 / 8 / 4): A/B runs, tests of the narrower windows at large k */
@@ -2383,6 +2394,9 @@ int kmr_build_info(kmr_handle *h, const char *what, double *value) {
 	else if (k == "saturated_keys") *value = (double)h->last_saturated_keys;
 	else if (k == "saturated_batches") *value = (double)h->last_saturated_batches;
 	else if (k == "device_blocks_live") *value = (double)g_blocks_live.load();
+	else if (k == "filter_score_ms") *value = h->last_score_ms;
+	else if (k == "select_ms") *value = h->last_select_ms;
+	else if (k == "select_write_ms") *value = h->last_write_ms;
 	else return fail(h, KMR_ERR_INVALID_ARG, "unknown build figure '" + k + "'");
 	return KMR_OK;
 }
@@ -2772,8 +2786,9 @@ int lookup_stream(kmr_handle *h, const ReadsView &rv, uint64_t total_bases, uint
 extern "C" {
 /* ReadSelector::scoreAndTrimReads (src/ReadSelector.h:1182-1207) on the weak map; s_b / s_o: device bases and offsets,
  * offsets: the same offsets on the host */
+struct ScoreDev { uint32_t *trim_offset, *trim_length; float *score; uint8_t *was_trimmed; };      /* the results in score_buf, good until the handle's next scoring call */
 static int score_reads_core(kmr_handle *h, const uint8_t *s_b, const uint64_t *s_o, uint64_t n_reads, double minimum_kmer_score, int scoring_type,
-                            uint32_t *trim_offset, uint32_t *trim_length, float *score, uint8_t *was_trimmed) {
+                            uint32_t *trim_offset, uint32_t *trim_length, float *score, uint8_t *was_trimmed, ScoreDev *keep = nullptr) {
 	int rc = 0;
 	ReadsView rv; rv.bases = s_b; rv.quals = nullptr; rv.offsets = s_o; rv.discarded = nullptr; rv.n_reads = n_reads; rv.stream_base = 0; rv.first_read_idx = 0; rv.u_start = rv.u_end = rv.u_read = nullptr; rv.n_units = 0;
 	/* per-read k-mer counts and their exclusive scan on the device (no host pass over the reads); one grow-only block for
@@ -2823,8 +2838,11 @@ static int score_reads_core(kmr_handle *h, const uint8_t *s_b, const uint64_t *s
 		hipLaunchKernelGGL(score_reads_kernel, dim3((unsigned)std::min<uint64_t>(((n_reads + 63) / 64 + SC_WAVES - 1) / SC_WAVES, 1u << 16)), dim3(SC_WAVES * 64), 0, h->stream, s_b, s_o, n_reads, h->k, dcounts, dcoff,
 		                   (float)minimum_kmer_score, scoring_type, dto, dtl, dsc, dwt);
 		HIPCHK(h, hipGetLastError());
-		HIPCHK(h, hipMemcpyAsync(trim_offset, dto, 4 * n_reads, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipMemcpyAsync(trim_length, dtl, 4 * n_reads, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(h, hipMemcpyAsync(score, dsc, 4 * n_reads, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipMemcpyAsync(was_trimmed, dwt, n_reads, hipMemcpyDeviceToHost, h->stream));
+		if (keep) { keep->trim_offset = dto; keep->trim_length = dtl; keep->score = dsc; keep->was_trimmed = dwt; }      /* the results stay on the device */
+		else {
+			HIPCHK(h, hipMemcpyAsync(trim_offset, dto, 4 * n_reads, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipMemcpyAsync(trim_length, dtl, 4 * n_reads, hipMemcpyDeviceToHost, h->stream));
+			HIPCHK(h, hipMemcpyAsync(score, dsc, 4 * n_reads, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipMemcpyAsync(was_trimmed, dwt, n_reads, hipMemcpyDeviceToHost, h->stream));
+		}
 		rc = sync_state(h);
 	} else hipStreamSynchronize(h->stream);
 	return rc;
@@ -3451,6 +3469,189 @@ int kmr_artifact_filter_apply(kmr_handle *h, const kmr_artifact_filter *f, const
 	HIPCHK(h, hipStreamSynchronize(h->stream));
 	*out = r.release();
 	return KMR_OK;
+}
+
+/* ---- selectReads / writePicks on the device (kmr_select.hpp) ---------------- */
+int kmr_select_config_init(kmr_select_config *c) {
+	if (!c) return KMR_ERR_INVALID_ARG;
+	memset(c, 0, sizeof(*c));
+	c->struct_size = (uint32_t)sizeof(kmr_select_config);
+	c->minimum_score = 2.0;            /* --min-depth, apps/FilterReads.cpp:197-199 */
+	c->min_read_length = 0.40f;        /* --min-read-length, src/ReadSelector.h:72 */
+	c->both_pass = 0;                  /* --min-passing-in-pair 1, src/ReadSelector.h:72 */
+	c->output_quality_base = 33;       /* --fastq-output-base-quality */
+	c->format = 0;                     /* --format-output 0 = FASTQ */
+	c->scoring_type = KMR_SCORE_MEDIAN;
+	return KMR_OK;
+}
+
+static int select_check_config(kmr_handle *h, const kmr_select_config *c) {
+	if (!c) return fail(h, KMR_ERR_INVALID_ARG, "kmr_select_config: NULL");
+	if (c->struct_size != sizeof(kmr_select_config)) return fail(h, KMR_ERR_INVALID_ARG, "kmr_select_config: struct_size " + std::to_string(c->struct_size) + " is not " + std::to_string(sizeof(kmr_select_config)));
+	if (c->format > 1) return fail(h, KMR_ERR_INVALID_ARG, "kmr_select_config: format must be 0 (FASTQ) or 1 (FASTA)");
+	if (c->output_quality_base != 33 && c->output_quality_base != 64) return fail(h, KMR_ERR_INVALID_ARG, "kmr_select_config: output_quality_base must be 33 or 64");
+	if (c->scoring_type > 4) return fail(h, KMR_ERR_INVALID_ARG, "kmr_select_config: bad scoring_type");
+	if (!(c->min_read_length >= 0.0f)) return fail(h, KMR_ERR_INVALID_ARG, "kmr_select_config: min_read_length must not be negative");
+	return 0;
+}
+
+/* up to three HIP events on the handle's stream, created and recorded only while kmr_tune "select_timing" is set */
+struct SelectTimer {
+	hipEvent_t ev[3] = {nullptr, nullptr, nullptr}; bool on;
+	explicit SelectTimer(bool enabled) : on(enabled) { if (on) for (auto &e : ev) if (hipEventCreate(&e) != hipSuccess) { e = nullptr; on = false; } }
+	~SelectTimer() { for (auto e : ev) if (e) hipEventDestroy(e); }
+	void mark(int i, hipStream_t s) { if (on) hipEventRecord(ev[i], s); }
+	double ms(int a, int b) const { float t = 0; return on && hipEventElapsedTime(&t, ev[a], ev[b]) == hipSuccess ? t : 0.0; }      /* after the stream has been waited for */
+};
+
+/* every pointer but the last is device memory (mate and the three af_* may be null) */
+static int select_core(kmr_handle *h, const kmr_reads *r, const uint8_t *dtext, uint64_t text_len, const int64_t *dmate, const uint8_t *dact, const uint32_t *dmin,
+                       const uint32_t *dmax, const uint32_t *dto, const uint32_t *dtl, const float *dsc, const uint8_t *dwt, const kmr_select_config *cfg, kmr_picks **out) {
+	const uint64_t n = r->n;
+	std::unique_ptr<kmr_picks, void (*)(kmr_picks *)> pk(new kmr_picks, kmr_picks_free);
+	pk->device = h->device; pk->n = n;
+	h->last_select_ms = h->last_write_ms = 0;
+	if (n == 0) { *out = pk.release(); return KMR_OK; }
+	SelectParams P;
+	P.bases = r->bases.get<uint8_t>(); P.quals = r->quals.get<uint8_t>(); P.offsets = r->offsets.get<uint64_t>(); P.name_off = r->name_off.get<uint64_t>(); P.name_len = r->name_len.get<uint32_t>();
+	P.text = dtext; P.text_len = text_len; P.mate = dmate; P.af_action = dact; P.af_min = dmin; P.af_max = dmax;
+	P.trim_off = dto; P.trim_len = dtl; P.score = dsc; P.was_trimmed = dwt; P.n = n;
+	P.min_score = (float)cfg->minimum_score; P.min_read_length = cfg->min_read_length; P.both_pass = cfg->both_pass ? 1u : 0u; P.fasta = cfg->format; P.scoring = cfg->scoring_type;
+	P.out_base = cfg->output_quality_base; P.qual_shift = (int32_t)cfg->output_quality_base - (int32_t)h->cfg.fastq_start_char;
+	DevBuf b_flag, b_len, b_nlen, b_pscan, b_bscan, b_pread, b_poff, b_tot;
+	uint32_t *flag, *len, *nlen, *pread; uint64_t *pscan, *bscan, *poff, *tot; uint8_t *picked;
+	HIPCHK(h, alloc_n(b_flag, &flag, n)); HIPCHK(h, alloc_n(b_len, &len, n)); HIPCHK(h, alloc_n(b_nlen, &nlen, n)); HIPCHK(h, alloc_n(b_pread, &pread, n));
+	HIPCHK(h, alloc_n(b_pscan, &pscan, n + 1)); HIPCHK(h, alloc_n(b_bscan, &bscan, n + 1)); HIPCHK(h, alloc_n(b_poff, &poff, n + 1)); HIPCHK(h, alloc_n(b_tot, &tot, 3));
+	HIPCHK(h, alloc_n(pk->picked, &picked, n));
+	SelectTimer timer(h->tune.select_timing);
+	timer.mark(0, h->stream);
+	HIPCHK(h, hipMemsetAsync(tot, 0, 24, h->stream));
+	hipLaunchKernelGGL(select_count_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, P, flag, len, nlen, picked, (uint32_t *)(tot + 2));
+	HIPCHK(h, hipGetLastError());
+	int rc = exclusive_scan(h, flag, n, pscan); if (rc) return rc;
+	rc = exclusive_scan(h, len, n, bscan); if (rc) return rc;
+	hipLaunchKernelGGL(select_compact_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, (const uint32_t *)flag, (const uint64_t *)pscan, (const uint64_t *)bscan, n, pread, poff, tot);
+	HIPCHK(h, hipGetLastError());
+	uint64_t totals[3] = {0, 0, 0};
+	HIPCHK(h, hipMemcpyAsync(totals, tot, 24, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));      /* the one copy that brings sizes back */
+	if (totals[2] & SEL_ERR_MATE) return fail(h, KMR_ERR_INVALID_ARG, "a mate index lies outside the batch");
+	if (totals[2] & SEL_ERR_NAME) return fail(h, KMR_ERR_INVALID_ARG, "a read's name span lies outside the text handed in (pass the text the batch was ingested from)");
+	pk->n_picked = totals[0]; pk->bytes = totals[1];
+	timer.mark(1, h->stream);
+	if (pk->bytes) {
+		HIPCHK(h, pk->text.alloc((pk->bytes + 15) & ~(uint64_t)15));
+		uint8_t *dout = pk->text.get<uint8_t>();
+		hipLaunchKernelGGL(select_write_kernel, dim3((unsigned)std::min<uint64_t>((pk->n_picked + SEL_WAVES - 1) / SEL_WAVES, (uint64_t)num_cus(h) * 8)), dim3(SEL_THREADS), 0, h->stream, P, (const uint32_t *)nlen, (const uint32_t *)pread, (const uint64_t *)poff, pk->n_picked, dout);
+		HIPCHK(h, hipGetLastError());
+	}
+	timer.mark(2, h->stream);
+	HIPCHK(h, hipStreamSynchronize(h->stream));
+	h->last_select_ms = timer.ms(0, 2); h->last_write_ms = timer.ms(1, 2);
+	*out = pk.release();
+	return KMR_OK;
+}
+
+extern "C++" {
+template <class T> static int select_upload(kmr_handle *h, DevBuf &b, const T *host, uint64_t n, const T **dev) {
+	*dev = nullptr;
+	if (!host || !n) return 0;
+	T *p = nullptr;
+	HIPCHK(h, alloc_n(b, &p, n));
+	HIPCHK(h, hipMemcpyAsync(p, host, sizeof(T) * n, hipMemcpyHostToDevice, h->stream));
+	*dev = p;
+	return 0;
+}
+}
+
+static int select_check_args(kmr_handle *h, const kmr_reads *r, const void *text, uint64_t text_len, const uint8_t *af_action, const uint32_t *af_min, const uint32_t *af_max,
+                             const kmr_select_config *cfg, kmr_picks **out, const char *who) {
+	if (out) *out = nullptr;
+	int rc = select_check_config(h, cfg); if (rc) return rc;
+	if (!h) return fail(h, KMR_ERR_INVALID_ARG, std::string(who) + ": NULL handle");
+	if (!r || !out || (text_len && !text)) return fail(h, KMR_ERR_INVALID_ARG, std::string(who) + ": NULL argument");
+	if ((af_action != nullptr) != (af_min != nullptr) || (af_action != nullptr) != (af_max != nullptr)) return fail(h, KMR_ERR_INVALID_ARG, std::string(who) + ": af_action, af_min_pass and af_max_pass go together");
+	if (r->device != h->device) return fail(h, KMR_ERR_INVALID_ARG, "read batch lives on another device");
+	if (r->n >= 0xffffffffull) return fail(h, KMR_ERR_UNSUPPORTED, std::string(who) + ": a batch holds fewer than 2^32 - 1 reads (pick indices are 32-bit)");
+	return 0;
+}
+
+/* text_on_device: `text` is device memory already */
+static int select_reads_any(kmr_handle *h, const kmr_reads *r, const void *text, uint64_t text_len, bool text_on_device, const int64_t *mate, const uint8_t *af_action,
+                            const uint32_t *af_min, const uint32_t *af_max, const uint32_t *trim_offset, const uint32_t *trim_length, const float *score,
+                            const uint8_t *was_trimmed, const kmr_select_config *cfg, kmr_picks **out, bool fused, const char *who) {
+	int rc = select_check_args(h, r, text, text_len, af_action, af_min, af_max, cfg, out, who); if (rc) return rc;
+	if (fused) { if (!h->finalized) return fail(h, KMR_ERR_STATE, std::string(who) + " before kmr_finalize"); }
+	else if (r->n && (!trim_offset || !trim_length || !score || !was_trimmed)) return fail(h, KMR_ERR_INVALID_ARG, std::string(who) + ": NULL argument");
+	hipSetDevice(h->device);
+	const uint64_t n = r->n;
+	DevBuf b_text, b_mate, b_act, b_min, b_max, b_to, b_tl, b_sc, b_wt;
+	const uint8_t *dtext = (const uint8_t *)text, *dact = nullptr, *dwt = nullptr; const int64_t *dmate = nullptr; const uint32_t *dmin = nullptr, *dmax = nullptr, *dto = nullptr, *dtl = nullptr; const float *dsc = nullptr;
+	if (!text_on_device) { rc = select_upload(h, b_text, (const uint8_t *)text, text_len, &dtext); if (rc) return rc; }
+	rc = select_upload(h, b_mate, mate, n, &dmate); if (rc) return rc;
+	rc = select_upload(h, b_act, af_action, n, &dact); if (rc) return rc;
+	rc = select_upload(h, b_min, af_min, n, &dmin); if (rc) return rc;
+	rc = select_upload(h, b_max, af_max, n, &dmax); if (rc) return rc;
+	h->last_score_ms = 0;
+	if (fused && n) {
+		SelectTimer timer(h->tune.select_timing);
+		timer.mark(0, h->stream);
+		ScoreDev sd;
+		rc = score_reads_core(h, r->bases.get<uint8_t>(), r->offsets.get<uint64_t>(), n, cfg->minimum_score, (int)cfg->scoring_type, nullptr, nullptr, nullptr, nullptr, &sd); if (rc) return rc;
+		timer.mark(1, h->stream);
+		if (timer.on) { HIPCHK(h, hipStreamSynchronize(h->stream)); h->last_score_ms = timer.ms(0, 1); }
+		dto = sd.trim_offset; dtl = sd.trim_length; dsc = sd.score; dwt = sd.was_trimmed;
+	} else if (!fused) {
+		rc = select_upload(h, b_to, trim_offset, n, &dto); if (rc) return rc;
+		rc = select_upload(h, b_tl, trim_length, n, &dtl); if (rc) return rc;
+		rc = select_upload(h, b_sc, score, n, &dsc); if (rc) return rc;
+		rc = select_upload(h, b_wt, was_trimmed, n, &dwt); if (rc) return rc;
+	}
+	rc = select_core(h, r, dtext, text_len, dmate, dact, dmin, dmax, dto, dtl, dsc, dwt, cfg, out);
+	if (rc) hipStreamSynchronize(h->stream);      /* the uploads above must have landed before their buffers go */
+	return rc;
+}
+
+int kmr_select_reads(kmr_handle *h, const kmr_reads *reads, const char *text, uint64_t text_len, const int64_t *mate, const uint8_t *af_action, const uint32_t *af_min_pass,
+                     const uint32_t *af_max_pass, const uint32_t *trim_offset, const uint32_t *trim_length, const float *score, const uint8_t *was_trimmed,
+                     const kmr_select_config *cfg, kmr_picks **out) {
+	return select_reads_any(h, reads, text, text_len, false, mate, af_action, af_min_pass, af_max_pass, trim_offset, trim_length, score, was_trimmed, cfg, out, false, "kmr_select_reads");
+}
+int kmr_select_reads_dev(kmr_handle *h, const kmr_reads *reads, const void *dev_text, uint64_t text_len, const int64_t *mate, const uint8_t *af_action, const uint32_t *af_min_pass,
+                         const uint32_t *af_max_pass, const uint32_t *trim_offset, const uint32_t *trim_length, const float *score, const uint8_t *was_trimmed,
+                         const kmr_select_config *cfg, kmr_picks **out) {
+	return select_reads_any(h, reads, dev_text, text_len, true, mate, af_action, af_min_pass, af_max_pass, trim_offset, trim_length, score, was_trimmed, cfg, out, false, "kmr_select_reads_dev");
+}
+int kmr_filter_read_batch(kmr_handle *h, const kmr_reads *reads, const char *text, uint64_t text_len, const int64_t *mate, const uint8_t *af_action, const uint32_t *af_min_pass,
+                          const uint32_t *af_max_pass, const kmr_select_config *cfg, kmr_picks **out) {
+	return select_reads_any(h, reads, text, text_len, false, mate, af_action, af_min_pass, af_max_pass, nullptr, nullptr, nullptr, nullptr, cfg, out, true, "kmr_filter_read_batch");
+}
+int kmr_filter_read_batch_dev(kmr_handle *h, const kmr_reads *reads, const void *dev_text, uint64_t text_len, const int64_t *mate, const uint8_t *af_action, const uint32_t *af_min_pass,
+                              const uint32_t *af_max_pass, const kmr_select_config *cfg, kmr_picks **out) {
+	return select_reads_any(h, reads, dev_text, text_len, true, mate, af_action, af_min_pass, af_max_pass, nullptr, nullptr, nullptr, nullptr, cfg, out, true, "kmr_filter_read_batch_dev");
+}
+int kmr_picks_info(const kmr_picks *p, uint64_t *n_picked, uint64_t *bytes) {
+	if (!p) return KMR_ERR_INVALID_ARG;
+	if (n_picked) *n_picked = p->n_picked; if (bytes) *bytes = p->bytes;
+	return KMR_OK;
+}
+int kmr_picks_copy(const kmr_picks *p, char *dst, uint64_t capacity, uint8_t *picked_flags) {
+	if (!p || (p->bytes && !dst)) return KMR_ERR_INVALID_ARG;
+	if (capacity < p->bytes) return KMR_ERR_CAPACITY;
+	hipSetDevice(p->device);
+	hipError_t e = hipSuccess;
+	if (p->bytes) e = hipMemcpy(dst, p->text.get<uint8_t>(), p->bytes, hipMemcpyDeviceToHost);
+	if (picked_flags && p->n && e == hipSuccess) e = hipMemcpy(picked_flags, p->picked.get<uint8_t>(), p->n, hipMemcpyDeviceToHost);
+	return e == hipSuccess ? KMR_OK : KMR_ERR_HIP;
+}
+int kmr_picks_device_ptr(const kmr_picks *p, void **dev_text) {
+	if (!p || !dev_text) return KMR_ERR_INVALID_ARG;
+	*dev_text = p->text.get<uint8_t>();
+	return KMR_OK;
+}
+void kmr_picks_free(kmr_picks *p) {
+	if (!p) return;
+	hipSetDevice(p->device);
+	delete p;      /* (its buffers are freed on this device) */
 }
 
 /* ---- f2: the batch as 2-bit packed reads + markups -------------------------- */

@@ -1,0 +1,191 @@
+/*
+ * kmr_select.hpp -- read selection and FASTQ / FASTA output of FilterReads on the device.
+ *
+ * Replaces selectReads (apps/FilterReads.h:159-279) with max-kmer-output-depth and partition-by-depth off:
+ * ReadSelector::pickAllPassingReads / pickAllPassingPairs (src/ReadSelector.h:547-596), optimizePickOrder (:1212-1221)
+ * and writePicks (:1242-1262) = Read::toFastq / toFasta (src/Sequence.cpp:761-779) of every picked read in ascending read
+ * index, over the per-read results of the artifact filter and of scoreAndTrimReads.
+ *
+ *   select_count_kernel    per read: isPassingRead of the read and of its mate (:550-568, passesLength :209-228 in float as
+ *                          the reference computes it), the pair decision, the printed length of its name, and the exact byte
+ *                          count of its record (decimal digits are counted, not printed)
+ *   (two exclusive scans: pick index, byte offset)
+ *   select_compact_kernel  pick p -> (read index, byte offset of its record); totals and the error word in one block of 24 bytes
+ *   select_write_kernel    one wavefront per record: name, label with integer-to-decimal, base slice, shifted quality slice,
+ *                          consecutive lanes taking consecutive bytes of the record
+ * A second writer, which assembled 16 KiB tiles of the output in LDS and stored them as 16-byte vectors, was measured against this
+ * one and lost ("Read selection and output text"); it is not kept.
+ *
+ * The number of launches does not depend on the number of reads.
+ */
+#ifndef KMR_SELECT_HPP_
+#define KMR_SELECT_HPP_
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace kmr {
+
+enum { SEL_ERR_MATE = 1, SEL_ERR_NAME = 2 };
+static const int SEL_THREADS = 256, SEL_WAVES = SEL_THREADS / 64, SEL_LABEL_CAP = 128;
+
+struct SelectParams {
+	const uint8_t *bases, *quals;            /* the batch */
+	const uint64_t *offsets, *name_off;
+	const uint32_t *name_len;
+	const uint8_t *text; uint64_t text_len;  /* what name_off / name_len point into */
+	const int64_t *mate;                     /* may be null */
+	const uint8_t *af_action;                /* the three may be null together */
+	const uint32_t *af_min, *af_max;
+	const uint32_t *trim_off, *trim_len;
+	const float *score;
+	const uint8_t *was_trimmed;
+	uint64_t n;
+	float min_score, min_read_length;
+	uint32_t both_pass, fasta, scoring;
+	uint32_t out_base;                       /* 33 or 64 */
+	int32_t qual_shift;                      /* out_base - the batch's quality base */
+};
+
+/* ReadSelectorUtil::passesLength (src/ReadSelector.h:219-228), all in float */
+__device__ __forceinline__ bool sel_passes_length(float length, uint32_t read_length, float minimum) {
+	if (length <= 1.0f) return false;
+	if (minimum <= 1.0f) return (float)read_length * minimum <= length;
+	return minimum <= length;
+}
+__device__ __forceinline__ bool sel_discarded(const SelectParams &P, uint64_t i) { return P.af_action && P.af_action[i] == 2; }
+/* isPassingRead(readIdx, minimumScore, minimumLength) (:550-557) */
+__device__ __forceinline__ bool sel_passing(const SelectParams &P, uint64_t i) {
+	if (sel_discarded(P, i)) return false;
+	const uint32_t len = (uint32_t)(P.offsets[i + 1] - P.offsets[i]);
+	return P.score[i] >= P.min_score && sel_passes_length((float)P.trim_len[i], len, P.min_read_length);
+}
+
+__device__ __forceinline__ uint32_t sel_put_char(uint8_t *dst, uint32_t at, char c, bool write) { if (write) dst[at] = (uint8_t)c; return at + 1; }
+__device__ __forceinline__ uint32_t sel_put_str(uint8_t *dst, uint32_t at, const char *s, bool write) {
+	for (; *s; s++) at = sel_put_char(dst, at, *s, write);
+	return at;
+}
+__device__ __forceinline__ uint32_t sel_put_int(uint8_t *dst, uint32_t at, int64_t sv, bool write) {
+	if (sv < 0) { at = sel_put_char(dst, at, '-', write); sv = -sv; }
+	uint64_t v = (uint64_t)sv;
+	uint32_t d = 1;
+	for (uint64_t t = v; t >= 10; t /= 10) d++;
+	if (write) for (uint32_t j = d; j-- > 0;) { dst[at + j] = (uint8_t)('0' + v % 10); v /= 10; }
+	return at + d;
+}
+/* getKmerScoringTypeLabel (src/ReadSelector.h:248-257) */
+__device__ __forceinline__ const char *sel_score_label(uint32_t scoring) {
+	switch (scoring) { case 0: return "Score:"; case 1: return "MedianScore:"; case 2: return "MinScore:"; case 3: return "MaxScore:"; default: return "AvgScore:"; }
+}
+/* The label of read i with its leading blank (Read::LABEL_SEP), as FilterKnownOddities (AFTrim) and setTrimHeaders
+ * (src/ReadSelector.h:1015-1036) compose it; a discarded read has none.  Returns the length; writes only when asked to
+ * (at most 92 bytes: three tags of 7 + 5 + 12 characters, five numbers of at most 11, four separators). */
+__device__ __forceinline__ uint32_t sel_label(const SelectParams &P, uint64_t i, uint8_t *dst, bool write) {
+	if (sel_discarded(P, i)) return 0;
+	uint32_t at = 0;
+	if (P.af_action && P.af_action[i] == 1) {
+		at = sel_put_str(dst, at, " AFTrim:", write);
+		at = sel_put_int(dst, at, P.af_min[i], write); at = sel_put_char(dst, at, '+', write); at = sel_put_int(dst, at, (int64_t)P.af_max[i] - (int64_t)P.af_min[i], write);
+	}
+	if (P.was_trimmed[i]) {
+		at = sel_put_str(dst, at, " Trim:", write);
+		at = sel_put_int(dst, at, P.trim_off[i], write); at = sel_put_char(dst, at, '+', write); at = sel_put_int(dst, at, P.trim_len[i], write);
+	}
+	at = sel_put_char(dst, at, ' ', write);
+	at = sel_put_str(dst, at, sel_score_label(P.scoring), write);
+	double s = (double)P.score[i] + 0.5;      /* (int)(score + 0.5), src/ReadSelector.h:1032 */
+	s = s > 2147483647.0 ? 2147483647.0 : (s < -2147483648.0 ? -2147483648.0 : s);
+	at = sel_put_int(dst, at, (int64_t)(int32_t)s, write);
+	return at;
+}
+
+/* What is printed of read i's bases: masked = the single base N with quality out_base + 1 (a discarded read, or a trim of
+ * at most one base: Sequence::getFasta src/Sequence.cpp:305-311, Read::getQuals :729-733); otherwise `len` bases from `from`. */
+struct SelSlice { uint64_t from; uint32_t len; bool masked; };
+__device__ __forceinline__ SelSlice sel_slice(const SelectParams &P, uint64_t i) {
+	SelSlice s;
+	const uint64_t b0 = P.offsets[i], L = P.offsets[i + 1] - b0;
+	const uint64_t to = P.trim_off[i]; uint64_t tl = P.trim_len[i];
+	if (to >= L) tl = 0; else if (tl > L - to) tl = L - to;      /* getQuals clamps the same way (:738-739) */
+	s.masked = sel_discarded(P, i) || tl <= 1;
+	s.from = b0 + to; s.len = s.masked ? 1u : (uint32_t)tl;
+	return s;
+}
+__device__ __forceinline__ uint32_t sel_record_bytes(const SelectParams &P, uint32_t nlen, uint32_t lablen, uint32_t slice_len) {
+	return 1 + nlen + lablen + 1 + slice_len + 1 + (P.fasta ? 0u : 2u + slice_len + 1u);
+}
+
+__global__ __launch_bounds__(256)
+void select_count_kernel(SelectParams P, uint32_t *pick_flag, uint32_t *rec_len, uint32_t *name_printed, uint8_t *picked, uint32_t *err) {
+	for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < P.n; i += (uint64_t)gridDim.x * blockDim.x) {
+		bool pick = sel_passing(P, i);
+		const int64_t m = P.mate ? P.mate[i] : -1;
+		if (m >= 0) {
+			if ((uint64_t)m >= P.n) atomicOr(err, (uint32_t)SEL_ERR_MATE);
+			else { const bool other = sel_passing(P, (uint64_t)m); pick = P.both_pass ? (pick && other) : (pick || other); }      /* isPassingPair :558-568 */
+		}
+		uint32_t bytes = 0, nlen = 0;
+		if (pick) {
+			const uint64_t no = P.name_off[i]; const uint32_t nl = P.name_len[i];
+			if (no > P.text_len || nl > P.text_len - no) atomicOr(err, (uint32_t)SEL_ERR_NAME);
+			else while (nlen < nl && P.text[no + nlen] != ' ' && P.text[no + nlen] != '\t') nlen++;
+			bytes = sel_record_bytes(P, nlen, sel_label(P, i, nullptr, false), sel_slice(P, i).len);
+		}
+		pick_flag[i] = pick ? 1u : 0u; picked[i] = pick ? 1 : 0; rec_len[i] = bytes; name_printed[i] = nlen;
+	}
+}
+
+/* totals[0] = picks, totals[1] = bytes, totals[2] = error word (written by select_count_kernel) */
+__global__ __launch_bounds__(256)
+void select_compact_kernel(const uint32_t *pick_flag, const uint64_t *pick_scan, const uint64_t *byte_scan, uint64_t n, uint32_t *pick_read, uint64_t *pick_off, uint64_t *totals) {
+	for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
+		if (pick_flag[i]) { const uint64_t p = pick_scan[i]; pick_read[p] = (uint32_t)i; pick_off[p] = byte_scan[i]; }
+	if (blockIdx.x == 0 && threadIdx.x == 0) { pick_off[pick_scan[n]] = byte_scan[n]; totals[0] = pick_scan[n]; totals[1] = byte_scan[n]; }
+}
+
+/* Read i's record of `bytes` bytes, by one wavefront, to dst; s_label: SEL_LABEL_CAP bytes of LDS of this wavefront.
+ * Consecutive lanes take consecutive bytes, so the loads from the name, the bases and the qualities and the stores coalesce. */
+__device__ __forceinline__ void sel_emit(const SelectParams &P, uint64_t i, uint32_t nlen, uint32_t bytes, uint8_t *dst, int lane, uint8_t *s_label) {
+	const uint32_t lablen = sel_label(P, i, s_label, lane == 0);
+	const SelSlice sl = sel_slice(P, i);
+	const uint64_t noff = P.name_off[i];
+	const uint32_t hdr = 1 + nlen + lablen + 1;
+	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
+	for (uint32_t p = lane; p < bytes; p += 64) {
+		uint8_t c;
+		if (p < hdr) {
+			if (p == 0) c = P.fasta ? '>' : '@';
+			else if (p <= nlen) c = P.text[noff + p - 1];
+			else if (p < hdr - 1) c = s_label[p - 1 - nlen];
+			else c = '\n';
+		} else {
+			uint32_t q = p - hdr;
+			if (q < sl.len) c = sl.masked ? (uint8_t)'N' : P.bases[sl.from + q];
+			else if (q == sl.len) c = '\n';
+			else {
+				q -= sl.len + 1;      /* FASTQ only: "+\n", the qualities, "\n" */
+				if (q == 0) c = '+';
+				else if (q == 1) c = '\n';
+				else if (q - 2 < sl.len) c = sl.masked ? (uint8_t)(P.out_base + 1) : (uint8_t)(P.quals[sl.from + q - 2] + P.qual_shift);
+				else c = '\n';
+			}
+		}
+		dst[p] = c;
+	}
+	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();      /* s_label is rewritten for the next record */
+}
+
+__global__ __launch_bounds__(SEL_THREADS)
+void select_write_kernel(SelectParams P, const uint32_t *name_printed, const uint32_t *pick_read, const uint64_t *pick_off, uint64_t n_picked, uint8_t *out) {
+	__shared__ uint8_t s_label[SEL_WAVES][SEL_LABEL_CAP];
+	const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+	for (uint64_t p = (uint64_t)blockIdx.x * SEL_WAVES + wave; p < n_picked; p += (uint64_t)gridDim.x * SEL_WAVES) {
+		const uint64_t rs = pick_off[p];
+		const uint32_t r = pick_read[p];
+		sel_emit(P, r, name_printed[r], (uint32_t)(pick_off[p + 1] - rs), out + rs, lane, s_label[wave]);
+	}
+}
+
+}  // namespace kmr
+#endif

@@ -671,6 +671,167 @@ class FilterKnownOddities:
             pass
 
 
+class ReadSelector:
+    """ReadSelector over a device-resident ReadSet (src/ReadSelector.h): scoreAndTrimReads (:1182-1207), pickAllPassingReads /
+    pickAllPassingPairs (:576-596) and writePicks (:1242-1262), selection and text produced on the device (kmr_select_reads,
+    kmr_filter_read_batch).  `mate` = index of each read's pair or -1 (None: every read is single); `filter_results` = the dict
+    FilterKnownOddities.applyFilter returned for the batch `read_set` was made from (the remnants it appended count as single,
+    untouched reads).  The output text stays on the device until writePicks copies it."""
+
+    FORMAT = {"fastq": 0, "fasta": 1}
+
+    def __init__(self, spectrum, read_set, mate=None, filter_results=None):
+        self.sp, self.reads = spectrum, read_set
+        n = read_set.n
+        self.mate = None
+        if mate is not None:
+            self.mate = np.full(n, -1, dtype=np.int64)
+            m = np.ascontiguousarray(mate, dtype=np.int64)
+            assert m.size <= n
+            self.mate[:m.size] = m
+        self.af = None
+        if filter_results is not None:
+            act = np.zeros(n, dtype=np.uint8); lo = np.zeros(n, dtype=np.uint32); hi = np.zeros(n, dtype=np.uint32)
+            k = filter_results["action"].size
+            assert k <= n
+            act[:k] = filter_results["action"]; lo[:k] = filter_results["min_pass"]; hi[:k] = filter_results["max_pass"]
+            self.af = (act, lo, hi)
+        self.trims = None
+        self.scoring = "MEDIAN"
+        self._picks = None
+        self._sel = None
+        self.picked_flags = np.zeros(n, dtype=bool)
+
+    @staticmethod
+    def _p(a, ct):
+        return None if a is None else a.ctypes.data_as(C.POINTER(ct))
+
+    def _config(self, min_score, min_read_length, both_pass, output_quality_base, format, scoring):
+        cfg = _lib.KmrSelectConfig()
+        self.sp.lib.kmr_select_config_init(C.byref(cfg))
+        cfg.minimum_score = float(min_score)
+        if min_read_length is not None:
+            cfg.min_read_length = float(min_read_length)
+        cfg.both_pass = 1 if both_pass else 0
+        cfg.output_quality_base = int(output_quality_base)
+        cfg.format = self.FORMAT[format] if isinstance(format, str) else int(format)
+        cfg.scoring_type = KmerSpectrum.SCORING[scoring]
+        return cfg
+
+    def _text_args(self):
+        buf = np.frombuffer(self.reads.text, dtype=np.uint8)
+        return buf, (buf.ctypes.data_as(C.c_void_p) if buf.size else None), buf.size
+
+    def _af_args(self):
+        a = self.af or (None, None, None)
+        return self._p(a[0], C.c_uint8), self._p(a[1], C.c_uint32), self._p(a[2], C.c_uint32)
+
+    def _adopt(self, handle):
+        self._free()
+        self._picks = handle
+        n, b = C.c_uint64(), C.c_uint64()
+        self.sp.lib.kmr_picks_info(handle, C.byref(n), C.byref(b))
+        self.n_picked, self.bytes = n.value, b.value
+        self._text = None
+
+    def scoreAndTrimReads(self, min_score, scoring="MEDIAN"):
+        """ReadSelector::scoreAndTrimReads(minimumKmerScore): (trim_offset, trim_length, score, was_trimmed) per read"""
+        self.scoring = scoring
+        self.trims = self.sp.scoreAndTrimReadSet(self.reads, min_score, scoring)
+        return self.trims
+
+    def _select(self, min_score, min_read_length, both_pass):
+        if self.trims is None:
+            raise KmerSpectrumError("pickAllPassing*: scoreAndTrimReads has not run")
+        self._sel = (min_score, min_read_length, both_pass)
+        return self._run(33, "fastq")
+
+    def _run(self, output_quality_base, format):
+        min_score, min_read_length, both_pass = self._sel
+        cfg = self._config(min_score, min_read_length, both_pass, output_quality_base, format, self.scoring)
+        to, tl, sc, wt = self.trims
+        to = np.ascontiguousarray(to, dtype=np.uint32); tl = np.ascontiguousarray(tl, dtype=np.uint32)
+        sc = np.ascontiguousarray(sc, dtype=np.float32); wt = np.ascontiguousarray(wt, dtype=np.uint8)
+        keep, tp, tn = self._text_args()
+        out = C.c_void_p()
+        self.sp._call("select_reads", self.sp.h, self.reads.r, tp, tn, self._p(self.mate, C.c_int64), *self._af_args(),
+                      self._p(to, C.c_uint32), self._p(tl, C.c_uint32), self._p(sc, C.c_float), self._p(wt, C.c_uint8), C.byref(cfg), C.byref(out))
+        self._adopt(out)
+        self._fmt = (output_quality_base, cfg.format)
+        return self.n_picked
+
+    def pickAllPassingReads(self, min_score=0.0, min_read_length=None):
+        """every read on its own, whatever `mate` says (:576-583); returns the number of picks"""
+        mate, self.mate = self.mate, None
+        try:
+            return self._select(min_score, min_read_length, False)
+        finally:
+            self.mate = mate
+
+    def pickAllPassingPairs(self, min_score=0.0, min_read_length=None, both_pass=False):
+        """:585-596 over the pairs of `mate`; returns the number of picked reads"""
+        return self._select(min_score, min_read_length, both_pass)
+
+    def filterReads(self, min_score=2.0, min_read_length=None, both_pass=False, scoring="MEDIAN", output_quality_base=33, format="fastq"):
+        """scoreAndTrimReads + pickAllPassingPairs + writePicks in one call that keeps the trims on the device
+        (kmr_filter_read_batch); returns the text"""
+        cfg = self._config(min_score, min_read_length, both_pass, output_quality_base, format, scoring)
+        keep, tp, tn = self._text_args()
+        out = C.c_void_p()
+        self.sp._call("filter_read_batch", self.sp.h, self.reads.r, tp, tn, self._p(self.mate, C.c_int64), *self._af_args(), C.byref(cfg), C.byref(out))
+        self._adopt(out)
+        self._sel, self._fmt = None, (output_quality_base, cfg.format)
+        return self._copy()
+
+    def _copy(self):
+        buf = np.zeros(max(1, self.bytes), dtype=np.uint8)
+        flags = np.zeros(max(1, self.reads.n), dtype=np.uint8)
+        rc = self.sp.lib.kmr_picks_copy(self._picks, buf.ctypes.data_as(C.c_void_p), self.bytes, flags.ctypes.data_as(C.POINTER(C.c_uint8)))
+        if rc != 0:
+            raise KmerSpectrumError("kmr_picks_copy: %s" % _lib.STATUS.get(rc, rc))
+        self.picked_flags = flags[:self.reads.n].astype(bool)
+        self._text = buf[:self.bytes].tobytes()
+        return self._text
+
+    def writePicks(self, output_quality_base=33, format="fastq"):
+        """the text of the picks (Read::toFastq / toFasta per picked read, ascending read index) as bytes"""
+        if self._picks is None:
+            raise KmerSpectrumError("writePicks: nothing has been picked")
+        fmt = (output_quality_base, self.FORMAT[format] if isinstance(format, str) else int(format))
+        if fmt != self._fmt:
+            if self._sel is None:
+                raise KmerSpectrumError("writePicks: filterReads fixed the format; call it again with the other one")
+            self._run(output_quality_base, format)
+        return self._text if self._text is not None else self._copy()
+
+    @property
+    def picks(self):
+        """indices of the picked reads, ascending"""
+        if self._picks is not None and self._text is None:
+            self._copy()
+        return np.nonzero(self.picked_flags)[0]
+
+    def device_text(self):
+        """(device pointer, bytes) of the output text (kmr_picks_device_ptr); valid until the next pick or close()"""
+        p = C.c_void_p()
+        self.sp._call("picks_device_ptr", self._picks, C.byref(p))
+        return p.value, self.bytes
+
+    def _free(self):
+        if getattr(self, "_picks", None):
+            self.sp.lib.kmr_picks_free(self._picks)
+            self._picks = None
+
+    def close(self):
+        self._free()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def synth_reads_device(torch, seed, first_read, n_reads, read_len, genome_len, noisy, device):
     """kmr_synth_reads_dev into torch tensors on `device`: (bases u8, quals u8, offsets i64).  The buffers carry 64 spare bytes behind
     the last read, as the device entry points of the build ask for."""
