@@ -6,6 +6,10 @@
  * scatter -> sort -> image) and the stateless helpers.  There is no CPU
  * fallback: every compute entry point needs a HIP device and fails with
  * KMR_ERR_NO_DEVICE otherwise.
+ * Shared decisions have one place each: key width / value kind / minimizer window as template arguments (with_w, with_w_ext,
+ * with_win), kernel-argument structs (reads_view, finalize_params, count_out, sk_own_lists), the plan of the count pass over
+ * super-k-mer lists (sk_count_uniform, sk_count_select), the host-to-device piece pipeline (tb_feed_pieces).  The heavy kernel
+ * templates are compiled elsewhere (kmr_instances.hpp, kmr_inst.hip); the headers' plain kernels here.
  */
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -21,6 +25,7 @@
 #include <cctype>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/kmernator_amd.h"
@@ -33,7 +38,7 @@
 #include "kmr_buckets.hpp"
 #include "kmr_synth.hpp"
 #define KMR_INSTANCES_EXTERN
-#include "kmr_instances.hpp"      /* the heavy kernels are compiled in kmr_inst_*.hip */
+#include "kmr_instances.hpp"      /* the heavy kernels are compiled in the objects made of kmr_inst.hip */
 
 using namespace kmr;
 
@@ -320,8 +325,42 @@ void quality_table(double P[256], unsigned minQ, unsigned startChar) {
 	}
 }
 
-size_t slot_bytes(uint32_t W) {
-	switch (W) { case 1: return sizeof(Slot<1>); case 2: return sizeof(Slot<2>); case 3: return sizeof(Slot<3>); default: return sizeof(Slot<4>); }
+/* The one place where the key width (h->W: 1-4 words, anything else behaves as 4) and, where wanted, the value kind (h->ext) turn into
+ * compile-time constants: with_w(h, [&](auto W) { return finalize_superkmer_t<W()>(h, min_depth); }), with_w_ext(h, [&](auto W, auto EXT) { ... }) */
+template <int N> using int_c = std::integral_constant<int, N>;
+template <class F> auto with_w(const kmr_handle *h, F &&f) {
+	switch (h->W) { case 1: return f(int_c<1>()); case 2: return f(int_c<2>()); case 3: return f(int_c<3>()); default: return f(int_c<4>()); }
+}
+template <class F> auto with_w_ext(const kmr_handle *h, F &&f) {
+	return with_w(h, [&](auto W) { return h->ext ? f(W, std::true_type()) : f(W, std::false_type()); });
+}
+/* ... and the minimizer window of build_mode 3 (h->sk_win: 32 for keys of two words and more only -- no window-32 instance exists for
+ * one-word keys --, 16, 8, anything else behaves as 4) */
+template <int W, class F> auto with_win(uint32_t win, F &&f) {
+	if (W > 1 && win == 32) return f(int_c<(W > 1 ? 32 : 16)>());
+	return win == 16 ? f(int_c<16>()) : (win == 8 ? f(int_c<8>()) : f(int_c<4>()));
+}
+
+size_t slot_bytes(kmr_handle *h) { return with_w(h, [](auto W) { return sizeof(Slot<W()>); }); }
+
+/* Kernel-argument structs leave their makers with every field set, a site states only what differs.  reads_view: a batch of reads on
+ * the device (no work units: prepare_units cuts them where a read is longer than a tile) */
+ReadsView reads_view(const void *bases, const void *quals, const void *offsets, uint64_t n_reads, const void *discarded = nullptr, uint64_t stream_base = 0, uint64_t first_read_idx = 0) {
+	ReadsView rv{};
+	rv.bases = (const uint8_t *)bases; rv.quals = (const uint8_t *)quals; rv.offsets = (const uint64_t *)offsets; rv.discarded = (const uint8_t *)discarded;
+	rv.n_reads = n_reads; rv.stream_base = stream_base; rv.first_read_idx = first_read_idx;
+	return rv;
+}
+/* reads [r, r + m) of a batch (bases and qualities stay: the offsets address them) */
+ReadsView reads_slice(const ReadsView &all, uint64_t r, uint64_t m) {
+	ReadsView rv = all;
+	rv.offsets = all.offsets + r; rv.n_reads = m; rv.discarded = all.discarded ? all.discarded + r : nullptr; rv.first_read_idx = all.first_read_idx + r;
+	return rv;
+}
+FinalizeParams finalize_params(kmr_handle *h, uint32_t min_depth) {
+	FinalizeParams f{};      /* (uni_wbits: sk_count_uniform) */
+	f.kb = h->hkb; f.ext_min_q = h->cfg.ext_min_quality; f.min_depth = min_depth; f.has_singletons = h->cfg.separate_singletons ? 1 : 0; f.nb_weak = h->nb_weak; f.nb_sing = h->nb_sing;
+	return f;
 }
 
 DevParams dev_params(kmr_handle *h) {
@@ -354,15 +393,12 @@ template <int W> int clear_table(kmr_handle *h, void *slots, ExtSlot *ext, uint3
 	HIPCHK(h, hipGetLastError());
 	return 0;
 }
-int clear_table_any(kmr_handle *h, void *slots, ExtSlot *ext, uint32_t log2cap) {
-	switch (h->W) { case 1: return clear_table<1>(h, slots, ext, log2cap); case 2: return clear_table<2>(h, slots, ext, log2cap);
-	case 3: return clear_table<3>(h, slots, ext, log2cap); default: return clear_table<4>(h, slots, ext, log2cap); }
-}
+int clear_table_any(kmr_handle *h, void *slots, ExtSlot *ext, uint32_t log2cap) { return with_w(h, [&](auto W) { return clear_table<W()>(h, slots, ext, log2cap); }); }
 
 /* slots (and extension slots) of a cleared table; `slots` and `ext` are replaced only when all of it succeeded */
 int alloc_table(kmr_handle *h, uint32_t log2cap, DevBuf &slots, DevBuf &ext) {
 	DevBuf s, x;
-	HIPCHK(h, s.alloc(slot_bytes(h->W) << log2cap));
+	HIPCHK(h, s.alloc(slot_bytes(h) << log2cap));
 	if (h->ext) HIPCHK(h, x.alloc(sizeof(ExtSlot) << log2cap));
 	const int rc = clear_table_any(h, s.get(), x.get<ExtSlot>(), log2cap);
 	if (rc) return rc;
@@ -409,11 +445,7 @@ template <int W, bool EXT> int grow_table_t(kmr_handle *h, uint32_t newlog) {
 	h->slots = std::move(ns); h->extslots = std::move(ne); h->log2cap = newlog;
 	return 0;
 }
-int grow_table(kmr_handle *h, uint32_t newlog) {
-#define GROW(Wv) (h->ext ? grow_table_t<Wv, true>(h, newlog) : grow_table_t<Wv, false>(h, newlog))
-	switch (h->W) { case 1: return GROW(1); case 2: return GROW(2); case 3: return GROW(3); default: return GROW(4); }
-#undef GROW
-}
+int grow_table(kmr_handle *h, uint32_t newlog) { return with_w_ext(h, [&](auto W, auto EXT) { return grow_table_t<W(), EXT()>(h, newlog); }); }
 
 /* make room for up to 'incoming' new keys: keep the load factor below 0.85 even if all are new */
 int ensure_capacity(kmr_handle *h, uint64_t incoming) {
@@ -505,10 +537,7 @@ template <int W, bool EXT> int add_reads_dev_t(kmr_handle *h, const ReadsView &r
 		const uint64_t bases = off2[1] - off2[0];
 		int rc = ensure_capacity(h, bases);     /* #k-mers <= #bases */
 		if (rc) return rc;
-		ReadsView rv = rvAll;
-		rv.offsets = rvAll.offsets + r; rv.n_reads = m;
-		rv.discarded = rvAll.discarded ? rvAll.discarded + r : nullptr;
-		rv.first_read_idx = rvAll.first_read_idx + r;
+		ReadsView rv = reads_slice(rvAll, r, m);
 		rc = prepare_units(h, rv); if (rc) return rc;
 		InsertOp<W, EXT> op; op.table = table_of<W>(h);
 		hipEvent_t a, b; time_begin(h, 0, &a, &b);
@@ -519,11 +548,7 @@ template <int W, bool EXT> int add_reads_dev_t(kmr_handle *h, const ReadsView &r
 	return 0;
 }
 
-int add_reads_dev_any(kmr_handle *h, const ReadsView &rv, uint64_t total_bases) {
-#define ADD(Wv) (h->ext ? add_reads_dev_t<Wv, true>(h, rv, total_bases) : add_reads_dev_t<Wv, false>(h, rv, total_bases))
-	switch (h->W) { case 1: return ADD(1); case 2: return ADD(2); case 3: return ADD(3); default: return ADD(4); }
-#undef ADD
-}
+int add_reads_dev_any(kmr_handle *h, const ReadsView &rv, uint64_t total_bases) { return with_w_ext(h, [&](auto W, auto EXT) { return add_reads_dev_t<W(), EXT()>(h, rv, total_bases); }); }
 
 int exclusive_scan(kmr_handle *h, const uint32_t *in, uint64_t n, uint64_t *out /* n+1 */) {
 	const uint64_t nblocks = (n + SCAN_ITEMS - 1) / SCAN_ITEMS;
@@ -575,7 +600,7 @@ template <int W, bool EXT> int finalize_t(kmr_handle *h, uint32_t min_depth) {
 	int rc = sync_state(h);
 	if (rc) return rc;
 	hipEvent_t ea, eb; time_begin(h, 1, &ea, &eb);
-	FinalizeParams f; f.kb = h->hkb; f.min_depth = min_depth; f.has_singletons = h->cfg.separate_singletons ? 1 : 0; f.nb_weak = h->nb_weak; f.nb_sing = h->nb_sing; f.uni_wbits = 0;
+	const FinalizeParams f = finalize_params(h, min_depth);
 	const bool keepSing = f.has_singletons && min_depth <= 1;
 	DevBuf wcb, scb, fcb;
 	HIPCHK(h, wcb.alloc(4 * h->nb_weak)); HIPCHK(h, scb.alloc(4 * h->nb_sing)); HIPCHK(h, fcb.alloc(sizeof(FinalizeCounters)));
@@ -634,10 +659,7 @@ template <int W> int build_image_t(kmr_handle *h, DevMap &m, bool weakMap) {
 	HIPCHK(h, hipStreamSynchronize(h->stream));
 	return 0;
 }
-int build_image(kmr_handle *h, DevMap &m, bool weakMap) {
-	switch (h->W) { case 1: return build_image_t<1>(h, m, weakMap); case 2: return build_image_t<2>(h, m, weakMap);
-	case 3: return build_image_t<3>(h, m, weakMap); default: return build_image_t<4>(h, m, weakMap); }
-}
+int build_image(kmr_handle *h, DevMap &m, bool weakMap) { return with_w(h, [&](auto W) { return build_image_t<W()>(h, m, weakMap); }); }
 
 template <int W> int load_image_t(kmr_handle *h, DevMap &m, bool weakMap, const uint8_t *src, uint64_t len) {
 	if (len < 16) return fail(h, KMR_ERR_INVALID_ARG, "image too short");
@@ -961,10 +983,7 @@ template <int W, bool EXT> int extract_by_owner_t(kmr_handle *h, const ReadsView
 	const uint64_t chunk = std::max<uint64_t>(64, (SUB_BATCH_BASES / avg) & ~63ull);
 	for (uint64_t r = 0; r < n; r += chunk) {
 		const uint64_t m = std::min(chunk, n - r);
-		ReadsView rv = rvAll;
-		rv.offsets = rvAll.offsets + r; rv.n_reads = m;
-		rv.discarded = rvAll.discarded ? rvAll.discarded + r : nullptr;
-		rv.first_read_idx = rvAll.first_read_idx + r;
+		ReadsView rv = reads_slice(rvAll, r, m);
 		int rc = prepare_units(h, rv); if (rc) return rc;
 		const uint64_t nu = rv.u_start ? rv.n_units : m;
 		rc = h->kcap.reserve(h, "kcap", 4 * std::max<uint64_t>(nu + 1, 16)); if (rc) return rc;
@@ -1006,10 +1025,7 @@ template <int W, bool EXT> int add_reads_partition_t(kmr_handle *h, const ReadsV
 	const uint64_t chunk = std::max<uint64_t>(64, (sub_bases / avg) & ~63ull);
 	for (uint64_t r = 0; r < n; r += chunk) {
 		const uint64_t m = std::min(chunk, n - r);
-		ReadsView rv = rvAll;
-		rv.offsets = rvAll.offsets + r; rv.n_reads = m;
-		rv.discarded = rvAll.discarded ? rvAll.discarded + r : nullptr;
-		rv.first_read_idx = rvAll.first_read_idx + r;
+		ReadsView rv = reads_slice(rvAll, r, m);
 		/* k-mer capacity of every work unit -> region of each 64-unit tile in the linear buffer */
 		int rc = prepare_units(h, rv); if (rc) return rc;
 		const uint64_t nu = rv.u_start ? rv.n_units : m;
@@ -1043,11 +1059,7 @@ template <int W, bool EXT> int add_reads_partition_t(kmr_handle *h, const ReadsV
 	}
 	return 0;
 }
-int add_reads_partition(kmr_handle *h, const ReadsView &rv, uint64_t total_bases) {
-#define ARP(Wv) (h->ext ? add_reads_partition_t<Wv, true>(h, rv, total_bases) : add_reads_partition_t<Wv, false>(h, rv, total_bases))
-	switch (h->W) { case 1: return ARP(1); case 2: return ARP(2); case 3: return ARP(3); default: return ARP(4); }
-#undef ARP
-}
+int add_reads_partition(kmr_handle *h, const ReadsView &rv, uint64_t total_bases) { return with_w_ext(h, [&](auto W, auto EXT) { return add_reads_partition_t<W(), EXT()>(h, rv, total_bases); }); }
 
 /* chunk CSR of a pool: list_start[nl+1] (device) and list_chunks[n_chunks] (device) */
 int build_csr(kmr_handle *h, HostPool &p, uint64_t nl, uint32_t first, uint64_t **list_start, uint64_t **list_chunks, uint32_t *n_chunks_out) {
@@ -1080,14 +1092,7 @@ int build_csr(kmr_handle *h, HostPool &p, uint64_t nl, uint32_t first, uint64_t 
 		DevBuf vb; HIPCHK(h, vb.alloc(24)); HIPCHK(h, hipMemset(vb.get(), 0, 24));
 		unsigned long long *v = vb.get<unsigned long long>();
 		PoolView pvw = pool_view(h, p);
-#define VLK(Wv, E) hipLaunchKernelGGL((verify_lists_kernel<Wv, E>), dim3(4096), dim3(256), 0, h->stream, pvw, *list_start, *list_chunks, nl, bits, h->hkb, part_rot(h), v, v + 1, v + 2)
-		switch (h->W) {
-		case 1: if (h->ext) VLK(1, true); else VLK(1, false); break;
-		case 2: if (h->ext) VLK(2, true); else VLK(2, false); break;
-		case 3: if (h->ext) VLK(3, true); else VLK(3, false); break;
-		default: if (h->ext) VLK(4, true); else VLK(4, false); break;
-		}
-#undef VLK
+		with_w_ext(h, [&](auto W, auto EXT) { hipLaunchKernelGGL((verify_lists_kernel<W(), EXT()>), dim3(4096), dim3(256), 0, h->stream, pvw, *list_start, *list_chunks, nl, bits, h->hkb, part_rot(h), v, v + 1, v + 2); });
 		HIPCHK(h, hipStreamSynchronize(h->stream));
 		HIPCHK(h, hipMemcpy(vv, v, 24, hipMemcpyDeviceToHost));
 		fprintf(stderr, "verify_lists: records via CSR %llu misfiled %llu zero-weight %llu\n", vv[0], vv[1], vv[2]);
@@ -1096,13 +1101,24 @@ int build_csr(kmr_handle *h, HostPool &p, uint64_t nl, uint32_t first, uint64_t 
 }
 
 int finish_maps_from_entries(kmr_handle *h, uint32_t *wc, uint32_t *sc, uint64_t wslots, uint64_t sslots, uint64_t wn, uint64_t sn, bool keepSing, bool weak_uncounted = false);
+CountOut count_out(kmr_handle *h, bool packed, unsigned long long *cursors, uint32_t *wc, uint32_t *sc, FinalizeCounters *fc);
+
+/* one launch of the count pass over k-mer records: the kernel for (W, EXT, table size, NARROW) with the dynamic LDS it wants;
+ * list_filter: 0 every list, 1 / 2 those the narrow tallies can / cannot take */
+template <int W, bool EXT, int LOG2S, bool NARROW = false> int launch_count(kmr_handle *h, int grid, const uint64_t *ls, const uint64_t *lc, uint64_t nl, const CountOut &out, const FinalizeParams &f, int list_filter) {
+	auto kern = count_kernel<W, EXT, LOG2S, NARROW>;
+	const size_t smem = count_smem_bytes<W, EXT, LOG2S, NARROW>();
+	HIPCHK(h, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+	hipLaunchKernelGGL(kern, dim3(grid), dim3(COUNT_THREADS), smem, h->stream, pool_view(h, h->l1), ls, lc, nl, out, f, h->work_counter.get<unsigned int>(), list_filter);
+	return 0;
+}
 
 template <int W, bool EXT> int finalize_partition_t(kmr_handle *h, uint32_t min_depth) {
 	int rc = sync_state(h);
 	if (rc) return rc;
 	hipEvent_t ea, eb; time_begin(h, 1, &ea, &eb);
 	const uint64_t G = h->stats.raw_good_kmers;     /* records in the level-1 pool */
-	FinalizeParams f; f.kb = h->hkb; f.ext_min_q = h->cfg.ext_min_quality; f.min_depth = min_depth; f.has_singletons = h->cfg.separate_singletons ? 1 : 0; f.nb_weak = h->nb_weak; f.nb_sing = h->nb_sing; f.uni_wbits = 0;
+	const FinalizeParams f = finalize_params(h, min_depth);
 	const bool keepSing = f.has_singletons && min_depth <= 1;
 	if (!h->l1.head) { rc = pool_reserve(h, h->l1, 0, false); if (rc) return rc; }
 	rc = arena_reset(h); if (rc) return rc;
@@ -1223,9 +1239,7 @@ template <int W, bool EXT> int finalize_partition_t(kmr_handle *h, uint32_t min_
 	}
 	HIPCHK(h, hipMemsetAsync(wc, 0, 4 * h->nb_weak, h->stream)); HIPCHK(h, hipMemsetAsync(sc, 0, 4 * h->nb_sing, h->stream));
 	HIPCHK(h, hipMemsetAsync(fc, 0, sizeof(FinalizeCounters), h->stream)); HIPCHK(h, hipMemsetAsync(cursors, 0, 16, h->stream));
-	CountOut out; out.wkeys = h->uw_keys.get<uint64_t>(); out.wvals = h->uw_vals.get<uint32_t>(); out.wentries = nullptr; out.wcursor = cursors; out.wcap = key_entries(h, h->uw_keys);
-	out.skeys = h->us_keys.get<uint64_t>(); out.sweight = h->us_b8.get<uint8_t>(); out.spkt = h->us_pkt.get<uint32_t>(); out.scursor = cursors + 1; out.scap = key_entries(h, h->us_keys);
-	out.weakCount = wc; out.singCount = sc; out.fc = fc; out.err = h->derr.get<uint32_t>();
+	const CountOut out = count_out(h, false, cursors, wc, sc, fc);
 	rc = zero_work_counter(h); if (rc) return rc;
 	#ifdef KMR_DEBUG_HOOKS
 	const int count_reps = getenv("KMR_COUNT_CHECK") ? atoi(getenv("KMR_COUNT_CHECK")) : 0;
@@ -1245,17 +1259,11 @@ template <int W, bool EXT> int finalize_partition_t(kmr_handle *h, uint32_t min_
 		}
 		const int grid = (int)std::min<uint64_t>((uint64_t)part_grid(h) * 2, nl2);
 		if (count_log2s == 11) {
-			auto kern = count_kernel<W, EXT, 11>;
-			const size_t smem = count_smem_bytes<W, EXT, 11>();
-			HIPCHK(h, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-			hipLaunchKernelGGL(kern, dim3(grid), dim3(COUNT_THREADS), smem, h->stream, pool_view(h, h->l1), ls2, lc2, nl2, out, f, h->work_counter.get<unsigned int>(), 0);
+			rc = launch_count<W, EXT, 11>(h, grid, ls2, lc2, nl2, out, f, 0); if (rc) return rc;
 		} else if (EXT && W == 1 && !h->tune.no_narrow) {
 			/* extension values at k <= 32: 16-bit tallies for every list of at most 65 535 records (two blocks per CU), then
 			 * the wide table for whatever is longer */
-			auto kn = count_kernel<W, EXT, COUNT_LOG2S, true>;
-			const size_t sn = count_smem_bytes<W, EXT, COUNT_LOG2S, true>();
-			HIPCHK(h, hipFuncSetAttribute((const void *)kn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sn));
-			hipLaunchKernelGGL(kn, dim3(grid), dim3(COUNT_THREADS), sn, h->stream, pool_view(h, h->l1), ls2, lc2, nl2, out, f, h->work_counter.get<unsigned int>(), 1);
+			rc = launch_count<W, EXT, COUNT_LOG2S, true>(h, grid, ls2, lc2, nl2, out, f, 1); if (rc) return rc;
 			HIPCHK(h, hipGetLastError());
 			/* is any list longer than the narrow tallies can take?  (the work counter word doubles as the maximum) */
 			rc = zero_work_counter(h); if (rc) return rc;
@@ -1264,17 +1272,9 @@ template <int W, bool EXT> int finalize_partition_t(kmr_handle *h, uint32_t min_
 			HIPCHK(h, hipMemcpyAsync(&longest, h->work_counter.get<unsigned int>(), 4, hipMemcpyDeviceToHost, h->stream));
 			HIPCHK(h, hipStreamSynchronize(h->stream));
 			rc = zero_work_counter(h); if (rc) return rc;
-			if (longest > COUNT_NARROW_CHUNKS) {
-				auto kern = count_kernel<W, EXT, COUNT_LOG2S>;
-				const size_t smem = count_smem_bytes<W, EXT, COUNT_LOG2S>();
-				HIPCHK(h, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-				hipLaunchKernelGGL(kern, dim3(std::min(grid, part_grid(h))), dim3(COUNT_THREADS), smem, h->stream, pool_view(h, h->l1), ls2, lc2, nl2, out, f, h->work_counter.get<unsigned int>(), 2);
-			}
+			if (longest > COUNT_NARROW_CHUNKS) { rc = launch_count<W, EXT, COUNT_LOG2S>(h, std::min(grid, part_grid(h)), ls2, lc2, nl2, out, f, 2); if (rc) return rc; }
 		} else {
-			auto kern = count_kernel<W, EXT, COUNT_LOG2S>;
-			const size_t smem = count_smem_bytes<W, EXT, COUNT_LOG2S>();
-			HIPCHK(h, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-			hipLaunchKernelGGL(kern, dim3(grid), dim3(COUNT_THREADS), smem, h->stream, pool_view(h, h->l1), ls2, lc2, nl2, out, f, h->work_counter.get<unsigned int>(), 0);
+			rc = launch_count<W, EXT, COUNT_LOG2S>(h, grid, ls2, lc2, nl2, out, f, 0); if (rc) return rc;
 		}
 		HIPCHK(h, hipGetLastError());
 	}
@@ -1457,14 +1457,9 @@ template <int W> int finish_maps_t(kmr_handle *h, uint32_t *wc, uint32_t *sc, ui
 	return 0;
 }
 int finish_maps_from_entries(kmr_handle *h, uint32_t *wc, uint32_t *sc, uint64_t wslots, uint64_t sslots, uint64_t wn, uint64_t sn, bool keepSing, bool weak_uncounted) {
-	switch (h->W) { case 1: return finish_maps_t<1>(h, wc, sc, wslots, sslots, wn, sn, keepSing, weak_uncounted); case 2: return finish_maps_t<2>(h, wc, sc, wslots, sslots, wn, sn, keepSing, weak_uncounted);
-	case 3: return finish_maps_t<3>(h, wc, sc, wslots, sslots, wn, sn, keepSing, weak_uncounted); default: return finish_maps_t<4>(h, wc, sc, wslots, sslots, wn, sn, keepSing, weak_uncounted); }
+	return with_w(h, [&](auto W) { return finish_maps_t<W()>(h, wc, sc, wslots, sslots, wn, sn, keepSing, weak_uncounted); });
 }
-int finalize_partition(kmr_handle *h, uint32_t min_depth) {
-#define FPT(Wv) (h->ext ? finalize_partition_t<Wv, true>(h, min_depth) : finalize_partition_t<Wv, false>(h, min_depth))
-	switch (h->W) { case 1: return FPT(1); case 2: return FPT(2); case 3: return FPT(3); default: return FPT(4); }
-#undef FPT
-}
+int finalize_partition(kmr_handle *h, uint32_t min_depth) { return with_w_ext(h, [&](auto W, auto EXT) { return finalize_partition_t<W(), EXT()>(h, min_depth); }); }
 template <int W, bool EXT> int insert_records_partition_t(kmr_handle *h, const void *recs, uint64_t n) {
 	if (!h->l1.head) choose_bits1(h, n);
 	hipEvent_t a, b; time_begin(h, 0, &a, &b);
@@ -1474,11 +1469,7 @@ template <int W, bool EXT> int insert_records_partition_t(kmr_handle *h, const v
 	time_end(h, 0, a, b);
 	return rc;
 }
-int insert_records_partition(kmr_handle *h, const void *recs, uint64_t n) {
-#define IRP(Wv) (h->ext ? insert_records_partition_t<Wv, true>(h, recs, n) : insert_records_partition_t<Wv, false>(h, recs, n))
-	switch (h->W) { case 1: return IRP(1); case 2: return IRP(2); case 3: return IRP(3); default: return IRP(4); }
-#undef IRP
-}
+int insert_records_partition(kmr_handle *h, const void *recs, uint64_t n) { return with_w_ext(h, [&](auto W, auto EXT) { return insert_records_partition_t<W(), EXT()>(h, recs, n); }); }
 /* ---------------------------------------------------------------------- */
 /* build_mode 3: super-k-mer lists (kmr_superkmer.hpp)                        */
 /* Minimizer geometry for k: the window of WIN m-mer offsets sits in the middle of the k-mer (2 * off + WIN = k - m + 1), m is
@@ -1521,7 +1512,7 @@ uint32_t sk_dbg_flags(const char *name);
 bool sp_debug_extract(kmr_handle *h) { (void)h; return sk_dbg_flags("KMR_SK_EXTRACT_DBG") != 0; }      /* the ablation switches live in the general kernel */
 template <int W, int WIN, bool PACKED = false> int launch_sk_extract_lean(kmr_handle *h, const ReadsView &rv, const SkParams &sp, float wK, const DevParams *override_params = nullptr, const SkPacked *packed = nullptr) {
 	auto kern = sk_extract_lean_kernel<W, WIN, PACKED>;
-	SkPacked pkd; pkd.bytes = nullptr; pkd.off = nullptr; pkd.mk_off = nullptr; pkd.mk_pos = nullptr; pkd.mk_char = nullptr;
+	SkPacked pkd{};
 	if (PACKED) pkd = *packed;
 	HIPCHK(h, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SKL_EXTRACT_SMEM));
 	const uint64_t tiles = ((rv.u_start ? rv.n_units : rv.n_reads) + 63) / 64;
@@ -1635,10 +1626,7 @@ template <int W> int add_reads_superkmer_t(kmr_handle *h, const ReadsView &rvAll
 	}
 	for (uint64_t r = 0; r < n; r += chunk) {
 		const uint64_t m = std::min(chunk, n - r);
-		ReadsView rv = rvAll;
-		rv.offsets = rvAll.offsets + r; rv.n_reads = m;
-		rv.discarded = rvAll.discarded ? rvAll.discarded + r : nullptr;
-		rv.first_read_idx = rvAll.first_read_idx + r;
+		ReadsView rv = reads_slice(rvAll, r, m);
 		int rc = prepare_units(h, rv, h->packed_direct ? SK_PACKED_SPAN : (uint32_t)TILE_SPAN); if (rc) return rc;
 		/* room for this launch: a granule per k-mer is more than any input takes (flat qualities: a quarter of that), one open
 		 * chunk per list and two slabs of 64 chunks per wavefront */
@@ -1662,15 +1650,14 @@ template <int W> int add_reads_superkmer_t(kmr_handle *h, const ReadsView &rvAll
 		hipEvent_t a, b, a2, b2; time_begin(h, KMR_TIME_BUILD, &a, &b); time_begin(h, KMR_TIME_EXTRACT, &a2, &b2);
 		SkParams sp = sk_params(h);
 		if (h->cfg.size_tracker) sp.track = h->trk.get<SkTrackRec>() + r;
-#define SKX(WINv) (h->ext ? (filt ? launch_sk_extract<W, WINv, true, true>(h, rv, sp) : launch_sk_extract<W, WINv, false, true>(h, rv, sp)) : \
-                   (filt ? launch_sk_extract<W, WINv, true>(h, rv, sp) : (lean ? launch_sk_extract_lean<W, WINv>(h, rv, sp, wK) : launch_sk_extract<W, WINv, false>(h, rv, sp))))
 		if (h->packed_direct) {
 			SkPacked pkd = *h->packed_direct; pkd.off += r; if (pkd.mk_off) pkd.mk_off += r;
-			if (W > 1 && h->sk_win == 32) rc = launch_sk_extract_lean<W, (W > 1 ? 32 : 16), true>(h, rv, sp, wK, nullptr, &pkd);
-			else rc = h->sk_win == 16 ? launch_sk_extract_lean<W, 16, true>(h, rv, sp, wK, nullptr, &pkd) : (h->sk_win == 8 ? launch_sk_extract_lean<W, 8, true>(h, rv, sp, wK, nullptr, &pkd) : launch_sk_extract_lean<W, 4, true>(h, rv, sp, wK, nullptr, &pkd));
-		} else
-		rc = (W > 1 && h->sk_win == 32) ? SKX((W > 1 ? 32 : 16)) : (h->sk_win == 16 ? SKX(16) : (h->sk_win == 8 ? SKX(8) : SKX(4)));
-#undef SKX
+			rc = with_win<W>(h->sk_win, [&](auto WIN) { return launch_sk_extract_lean<W, WIN(), true>(h, rv, sp, wK, nullptr, &pkd); });
+		} else rc = with_win<W>(h->sk_win, [&](auto WIN) {
+			if (h->ext) return filt ? launch_sk_extract<W, WIN(), true, true>(h, rv, sp) : launch_sk_extract<W, WIN(), false, true>(h, rv, sp);
+			if (filt) return launch_sk_extract<W, WIN(), true>(h, rv, sp);
+			return lean ? launch_sk_extract_lean<W, WIN()>(h, rv, sp, wK) : launch_sk_extract<W, WIN(), false>(h, rv, sp);
+		});
 		time_end(h, KMR_TIME_EXTRACT, a2, b2); time_end(h, KMR_TIME_BUILD, a, b);
 		if (rc) return rc;
 	}
@@ -1700,7 +1687,7 @@ template <int W> int add_reads_superkmer_t(kmr_handle *h, const ReadsView &rvAll
 			SkBoundary *dbd = dbdb.get<SkBoundary>();
 			hipError_t e = hipMemcpyAsync(dbd, bd.data(), bd.size() * sizeof(SkBoundary), hipMemcpyHostToDevice, h->stream);
 			if (e == hipSuccess) {
-				ReadsView rv = rvAll; rv.u_start = rv.u_end = rv.u_read = nullptr; rv.n_units = 0;
+				ReadsView rv = rvAll; rv.u_start = rv.u_end = rv.u_read = nullptr; rv.n_units = 0;      /* (whole reads: the caller's work units do not apply) */
 				hipLaunchKernelGGL(sk_track_boundary_kernel<W>, dim3((unsigned)((bd.size() + 63) / 64)), dim3(64), 0, h->stream, rv, dp, dbd, (uint32_t)bd.size());
 				e = hipGetLastError();
 			}
@@ -1712,10 +1699,7 @@ template <int W> int add_reads_superkmer_t(kmr_handle *h, const ReadsView &rvAll
 	}
 	return 0;
 }
-int add_reads_superkmer(kmr_handle *h, const ReadsView &rv, uint64_t total_bases) {
-	switch (h->W) { case 1: return add_reads_superkmer_t<1>(h, rv, total_bases); case 2: return add_reads_superkmer_t<2>(h, rv, total_bases);
-	case 3: return add_reads_superkmer_t<3>(h, rv, total_bases); default: return add_reads_superkmer_t<4>(h, rv, total_bases); }
-}
+int add_reads_superkmer(kmr_handle *h, const ReadsView &rv, uint64_t total_bases) { return with_w(h, [&](auto W) { return add_reads_superkmer_t<W()>(h, rv, total_bases); }); }
 /* k-mers seen SK_ORDERED_FROM times or more (sat_*_kernel in kmr_superkmer.hpp): weightedCount and directionBias of their entries in the
  * finished weak map from their first 65 535 sightings in input order, added into a float one after the other as the serial reference
  * does.  n_clamped: how many such keys the count pass kept, n_sightings: their sightings.
@@ -1841,139 +1825,200 @@ template <int W> int saturated_fix_t(kmr_handle *h, const uint64_t *ls, const ui
 	return 0;
 }
 
-template <int W> int finalize_superkmer_t(kmr_handle *h, uint32_t min_depth) {
-	int rc = sync_state(h);
-	if (rc) return rc;
-	hipEvent_t ea, eb; time_begin(h, 1, &ea, &eb);
-	const uint64_t G = h->stats.raw_good_kmers;
-	FinalizeParams f; f.kb = h->hkb; f.ext_min_q = h->cfg.ext_min_quality; f.min_depth = min_depth; f.has_singletons = h->cfg.separate_singletons ? 1 : 0; f.nb_weak = h->nb_weak; f.nb_sing = h->nb_sing; f.uni_wbits = 0;
-	const bool keepSing = f.has_singletons && min_depth <= 1;
-	if (!h->l1.head) { rc = pool_reserve(h, h->l1, 0, false); if (rc) return rc; }
-	rc = arena_reset(h); if (rc) return rc;
-	uint64_t nl = h->sk_state ? sk_list_count(h->sk_bits) : 1;
-	if (h->sk_state) {
-		hipLaunchKernelGGL(sk_close_kernel, dim3(grid_for(nl)), dim3(256), 0, h->stream, h->sk_state.get<unsigned long long>(), nl, h->l1.chunk_count.get<uint32_t>(), h->l1.cap);
-		HIPCHK(h, hipGetLastError());
+/* ---- The count pass over super-k-mer lists as kmr_finalize (finalize_superkmer_t) and kmr_count_lists_prefix (count_prefix_superkmer_t)
+ * plan it.  The two must agree: kmr_finalize takes the early count's entries over as they are, so an early pass that decides "one
+ * weight" while the final pass decides otherwise would mix two roundings in one map. */
+
+/* One weight for every record of the lists (own calls: host state; adopted records: what the senders declared, else the device
+ * pair)?  Then the count pass's UNI form, with that weight in uni_wbits. */
+template <int W> int sk_count_uniform(kmr_handle *h, bool tracking, bool &uni, uint32_t &uni_wbits) {
+	uni = false; uni_wbits = 0;
+	if (tracking || h->ext || h->sk_uni_mixed || h->tune.no_uniform_count) return 0;
+	if (W > 1 && (h->k & 31u) == 0) return 0;      /* (multi-word keys: the one-weight pass has no state words, it needs pad bits in the last key word) */
+	uint32_t w = h->sk_uni_w; bool mixed = false;
+	if (h->peer_uni_mixed) mixed = true;
+	else if (h->peer_uni_w != SK_UNI_NONE) { if (w == SK_UNI_NONE) w = h->peer_uni_w; else if (w != h->peer_uni_w) mixed = true; }
+	if (h->d_uni) {
+		uint32_t dv[2] = {SK_UNI_NONE, 0u};
+		HIPCHK(h, hipMemcpy(dv, h->d_uni.get<uint32_t>(), 8, hipMemcpyDeviceToHost));
+		if (dv[1]) mixed = true;
+		else if (dv[0] != SK_UNI_NONE) { if (w == SK_UNI_NONE) w = dv[0]; else if (w != dv[0]) mixed = true; }
 	}
-	const bool refined = h->sk_state && h->sk_fine_shift > 0;
-	if (refined) {
-		/* the coarse lists this rank owns (its own share and what it adopted) -> fine lists (sk_refine_kernel) */
-		const uint32_t fine_bits = h->sk_bits + h->sk_fine_shift;
-		const uint64_t nlf = 1ull << fine_bits;
-		unsigned int head = 0;
-		HIPCHK(h, hipStreamSynchronize(h->stream));
-		HIPCHK(h, hipMemcpy(&head, h->l1.head.get<unsigned int>(), 4, hipMemcpyDeviceToHost));
-		if (head > h->l1.cap) head = h->l1.cap;
-		rc = h->sk_fine_state.reserve(h, "sk_fine_state", 8 * nlf); if (rc) return rc;
-		hipLaunchKernelGGL(sk_state_init_kernel, dim3(grid_for(nlf)), dim3(256), 0, h->stream, h->sk_fine_state.get<unsigned long long>(), nlf);
-		const int rgrid = (int)std::min<uint64_t>(((uint64_t)head + SK_REFINE_WAVES - 1) / SK_REFINE_WAVES + 1, (uint64_t)num_cus(h) * 8);
-		/* every old chunk's records again, cut into at most 2^shift pieces per chunk (a piece may open a chunk), an open chunk per owned fine list */
-		rc = pool_reserve(h, h->l1, (uint64_t)head * 2 + nlf / h->cfg.world_size + (uint64_t)rgrid * SK_REFINE_WAVES * 130 + 64, true); if (rc) return rc;
-		if (head) hipLaunchKernelGGL(sk_refine_kernel, dim3(rgrid), dim3(SK_REFINE_WAVES * 64), 0, h->stream, pool_view(h, h->l1), head, fine_bits, h->sk_fine_state.get<unsigned long long>());
-		hipLaunchKernelGGL(sk_close_kernel, dim3(grid_for(nlf)), dim3(256), 0, h->stream, h->sk_fine_state.get<unsigned long long>(), nlf, h->l1.chunk_count.get<uint32_t>(), h->l1.cap);
-		HIPCHK(h, hipGetLastError());
-		nl = nlf;
-	}
-	uint64_t *ls = nullptr, *lc = nullptr; uint32_t nch = 0;
-	rc = build_csr(h, h->l1, nl, 0, &ls, &lc, &nch); if (rc) return rc;
-	const uint32_t vw = h->ext ? 15 : 3;
-	const bool ext = h->ext;      /* extension values: entries of 15 value words, keys and values apart, bucketed by the scatter + per-bucket sort */
+	if (!mixed && w != SK_UNI_NONE) { uni = true; uni_wbits = w; }
+	return 0;
+}
+/* the lists this rank's pass looks at (SkLong, list mode): all of them, or -- inside an owner exchange whose lists were not refined --
+ * rank, rank + world_size, ...: the other lists went to their owners.  No long-list threshold, no work items, no merge table. */
+template <int W> SkLong<W> sk_own_lists(kmr_handle *h, bool refined) {
+	SkLong<W> lg{};
+	lg.list_first = 0; lg.list_stride = 1;
+	if (h->sk_exchange && h->cfg.world_size > 1 && !refined) { lg.list_first = h->cfg.rank; lg.list_stride = h->cfg.world_size; }
+	return lg;
+}
+/* sk_count_kernel's form for (W, ext, tracking, uni) together with the dynamic LDS it wants, the attribute set */
+template <int W> struct SkCountLaunch {
+	void (*kern)(PoolView, const uint64_t *, const uint64_t *, uint64_t, uint32_t, CountOut, FinalizeParams, unsigned int *, uint32_t, SkTrackView, SkLong<W>);
+	size_t smem;
+};
+template <int W, int LOG2S, bool TRACK, bool EXT, bool UNI> SkCountLaunch<W> sk_count_form() { return {sk_count_kernel<W, LOG2S, TRACK, EXT, UNI>, sk_count_smem_bytes<W, LOG2S, TRACK, EXT, UNI>()}; }
+template <int W> int sk_count_select(kmr_handle *h, bool ext, bool tracking, bool uni, SkCountLaunch<W> &k) {
+	k = ext ? sk_count_form<W, COUNT_LOG2S_EXT, false, true, false>() : (tracking ? sk_count_form<W, COUNT_LOG2S, true, false, false>() :
+	    (uni ? sk_count_form<W, COUNT_LOG2S, false, false, true>() : sk_count_form<W, COUNT_LOG2S, false, false, false>()));
+	const auto kern = k.kern; const size_t smem = k.smem;
+	HIPCHK(h, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+	return 0;
+}
+
+/* what the phases of finalize_superkmer_t hand to one another */
+template <int W> struct SkFinalize {
+	FinalizeParams f{}; bool keepSing = false, ext = false, tracking = false, refined = false, uni = false;
+	uint64_t nl = 1; uint64_t *ls = nullptr, *lc = nullptr; uint32_t nch = 0;      /* the lists and their chunk CSR */
+	uint64_t wcap = 0, scap = 0, wmax = 0, smax = 0;                             /* entry buffers: entries now, upper bounds */
+	uint32_t *wc = nullptr, *sc = nullptr; FinalizeCounters *fc = nullptr; unsigned long long *cursors = nullptr;
+	SkTrackView tv{};
+	SkLong<W> lgMain{}, lgItems{}; uint64_t n_items = 0;                         /* the pass over lists, the pass over work items of long lists */
+	uint64_t early_slots = 0; FinalizeCounters early_c{};                        /* an early count that is taken over */
+	FinalizeCounters c{}; unsigned long long cur[2] = {0, 0};                    /* what the count pass reported */
+};
+
+/* the coarse lists this rank owns (its own share and what it adopted) -> fine lists (sk_refine_kernel); nl: how many */
+int sk_refine_lists(kmr_handle *h, uint64_t &nl) {
+	const uint32_t fine_bits = h->sk_bits + h->sk_fine_shift;
+	const uint64_t nlf = 1ull << fine_bits;
+	unsigned int head = 0;
+	HIPCHK(h, hipStreamSynchronize(h->stream));
+	HIPCHK(h, hipMemcpy(&head, h->l1.head.get<unsigned int>(), 4, hipMemcpyDeviceToHost));
+	if (head > h->l1.cap) head = h->l1.cap;
+	int rc = h->sk_fine_state.reserve(h, "sk_fine_state", 8 * nlf); if (rc) return rc;
+	hipLaunchKernelGGL(sk_state_init_kernel, dim3(grid_for(nlf)), dim3(256), 0, h->stream, h->sk_fine_state.get<unsigned long long>(), nlf);
+	const int rgrid = (int)std::min<uint64_t>(((uint64_t)head + SK_REFINE_WAVES - 1) / SK_REFINE_WAVES + 1, (uint64_t)num_cus(h) * 8);
+	/* every old chunk's records again, cut into at most 2^shift pieces per chunk (a piece may open a chunk), an open chunk per owned fine list */
+	rc = pool_reserve(h, h->l1, (uint64_t)head * 2 + nlf / h->cfg.world_size + (uint64_t)rgrid * SK_REFINE_WAVES * 130 + 64, true); if (rc) return rc;
+	if (head) hipLaunchKernelGGL(sk_refine_kernel, dim3(rgrid), dim3(SK_REFINE_WAVES * 64), 0, h->stream, pool_view(h, h->l1), head, fine_bits, h->sk_fine_state.get<unsigned long long>());
+	hipLaunchKernelGGL(sk_close_kernel, dim3(grid_for(nlf)), dim3(256), 0, h->stream, h->sk_fine_state.get<unsigned long long>(), nlf, h->l1.chunk_count.get<uint32_t>(), h->l1.cap);
+	HIPCHK(h, hipGetLastError());
+	nl = nlf;
+	return 0;
+}
+/* entry buffers of the pass over G good k-mers: how many entries to start with and their upper bounds; the per-bucket counts, counters and cursors */
+template <int W> int sk_entry_buffers(kmr_handle *h, SkFinalize<W> &p, uint64_t G) {
+	const FinalizeParams &f = p.f; const bool keepSing = p.keepSing;
 	const uint64_t slack = (uint64_t)num_cus(h) * 4 * 8192 + 16;
 	const uint64_t wbound = f.has_singletons ? G / 2 : G, sbound = keepSing ? G : 0;
 	/* (after an owner exchange the lists this rank counts hold other ranks' k-mers too -- G only knows this rank's own reads: no upper
 	 * bound then, the pass is repeated with doubled buffers until the entries fit) */
 	const bool adopted = h->sk_exchange && h->cfg.world_size > 1;
-	const uint64_t wmax = adopted ? (1ull << 40) : wbound + wbound / 8 + slack, smax = keepSing ? (adopted ? (1ull << 40) : sbound + sbound / 8 + slack) : 16;
+	p.wmax = adopted ? (1ull << 40) : wbound + wbound / 8 + slack; p.smax = keepSing ? (adopted ? (1ull << 40) : sbound + sbound / 8 + slack) : 16;
 	/* entry buffers: sequencing data keeps a few per cent of its k-mers as weak entries; the pass is run again with larger
 	 * buffers when that was not enough */
-	uint64_t wcap = std::min<uint64_t>(wmax, G / (f.has_singletons ? 8 : 3) + slack), scap = keepSing ? std::min<uint64_t>(smax, G / 3 + slack) : 16;
-	if (h->tune.entry_share >= 0) { wcap = std::min<uint64_t>(wmax, (uint64_t)((double)G * h->tune.entry_share) + 16384); if (keepSing) scap = std::min<uint64_t>(smax, (uint64_t)((double)G * h->tune.entry_share) + 16384);
+	p.wcap = std::min<uint64_t>(p.wmax, G / (f.has_singletons ? 8 : 3) + slack); p.scap = keepSing ? std::min<uint64_t>(p.smax, G / 3 + slack) : 16;
+	if (h->tune.entry_share >= 0) { p.wcap = std::min<uint64_t>(p.wmax, (uint64_t)((double)G * h->tune.entry_share) + 16384); if (keepSing) p.scap = std::min<uint64_t>(p.smax, (uint64_t)((double)G * h->tune.entry_share) + 16384);
 		h->ue.reset(); h->us_keys.reset(); h->us_b8.reset(); h->us_pkt.reset(); }
-	wcap = std::max(wcap, ext ? key_entries(h, h->uw_keys) : packed_entries(h, h->ue)); scap = std::max(scap, key_entries(h, h->us_keys));
-	uint32_t *wc = nullptr, *sc = nullptr; FinalizeCounters *fc = nullptr; unsigned long long *cursors = nullptr;
-	rc = arena_get(h, &wc, h->nb_weak); if (rc) return rc; rc = arena_get(h, &sc, h->nb_sing); if (rc) return rc;
-	rc = arena_get(h, &fc, 1); if (rc) return rc; rc = arena_get(h, &cursors, 2); if (rc) return rc;
-	FinalizeCounters c; unsigned long long cur[2];
-	/* size tracker: SizeTracker::track (src/KmerSpectrum.h:879-894) applied after every read, in stream order; what it pushes is known
-	 * from the per-read records alone except the unique / singleton counters, which the count pass fills in per boundary */
-	std::vector<unsigned long long> bounds; std::vector<uint64_t> snap_raw, snap_good;
-	SkTrackView tv; tv.bounds = nullptr; tv.n = 0; tv.d_unique = tv.d_single = nullptr;
-	const bool tracking = h->cfg.size_tracker != 0;
-	/* one weight for every record of the lists (own calls: host state; adopted records: the device pair)?  Then the count pass's UNI form */
-	bool uni = false;
-	f.uni_wbits = 0;
-	if (!tracking && !ext && !h->sk_uni_mixed && !h->tune.no_uniform_count && (W == 1 || (h->k & 31u) != 0)) {      /* (multi-word keys: the one-weight pass has no state words, it needs pad bits in the last key word) */
-		uint32_t w = h->sk_uni_w; bool mixed = false;
-		if (h->peer_uni_mixed) mixed = true;
-		else if (h->peer_uni_w != SK_UNI_NONE) { if (w == SK_UNI_NONE) w = h->peer_uni_w; else if (w != h->peer_uni_w) mixed = true; }
-		if (h->d_uni) {
-			uint32_t dv[2] = {SK_UNI_NONE, 0u};
-			HIPCHK(h, hipMemcpy(dv, h->d_uni.get<uint32_t>(), 8, hipMemcpyDeviceToHost));
-			if (dv[1]) mixed = true;
-			else if (dv[0] != SK_UNI_NONE) { if (w == SK_UNI_NONE) w = dv[0]; else if (w != dv[0]) mixed = true; }
-		}
-		if (!mixed && w != SK_UNI_NONE) { uni = true; f.uni_wbits = w; }
+	p.wcap = std::max(p.wcap, p.ext ? key_entries(h, h->uw_keys) : packed_entries(h, h->ue)); p.scap = std::max(p.scap, key_entries(h, h->us_keys));
+	int rc = arena_get(h, &p.wc, h->nb_weak); if (rc) return rc; rc = arena_get(h, &p.sc, h->nb_sing); if (rc) return rc;
+	rc = arena_get(h, &p.fc, 1); if (rc) return rc; rc = arena_get(h, &p.cursors, 2); if (rc) return rc;
+	return 0;
+}
+/* size tracker: SizeTracker::track (src/KmerSpectrum.h:879-894) applied after every read, in stream order; what it pushes is known
+ * from the per-read records alone except the unique / singleton counters, which the count pass fills in per boundary (tv) */
+int sk_track_view(kmr_handle *h, SkTrackView &tv) {
+	const std::vector<unsigned long long> &bounds = h->trk_bounds;
+	if (bounds.size() > SK_TRACK_MAX) return fail(h, KMR_ERR_UNSUPPORTED, "size tracker: more than 512 elements");
+	unsigned long long *db = nullptr; unsigned int *dd = nullptr;
+	int rc = arena_get(h, &db, bounds.size() + 1); if (rc) return rc;
+	rc = arena_get(h, &dd, 2 * (bounds.size() + 1)); if (rc) return rc;
+	if (!bounds.empty()) HIPCHK(h, hipMemcpyAsync(db, bounds.data(), 8 * bounds.size(), hipMemcpyHostToDevice, h->stream));
+	tv.bounds = db; tv.n = (uint32_t)bounds.size(); tv.d_unique = dd; tv.d_single = dd + bounds.size() + 1;
+	return 0;
+}
+/* ... and after the pass: the tracker's elements out of the per-boundary counters */
+int sk_track_elements(kmr_handle *h, const SkTrackView &tv, uint32_t has_singletons) {
+	std::vector<unsigned int> dd(2 * (tv.n + 1), 0);
+	HIPCHK(h, hipMemcpy(dd.data(), tv.d_unique, 8 * (tv.n + 1), hipMemcpyDeviceToHost));
+	h->trk_elems.clear();
+	uint64_t uniq = 0; int64_t single = 0;
+	const uint64_t sub = h->cfg.kmer_subsample > 1 ? h->cfg.kmer_subsample : 1;      /* track() scales what it stores, :882-887 */
+	for (uint32_t i = 0; i < tv.n; i++) {
+		uniq += dd[i]; single += (int32_t)dd[tv.n + 1 + i];
+		h->trk_elems.push_back(h->trk_snap_raw[i] * sub); h->trk_elems.push_back(h->trk_snap_good[i] * sub);
+		h->trk_elems.push_back(uniq * sub); h->trk_elems.push_back(has_singletons ? (uint64_t)single * sub : 0);
 	}
-	h->last_count_uniform = uni;
-	if (tracking) {
-		bounds = h->trk_bounds; snap_raw = h->trk_snap_raw; snap_good = h->trk_snap_good;
-		if (bounds.size() > SK_TRACK_MAX) return fail(h, KMR_ERR_UNSUPPORTED, "size tracker: more than 512 elements");
-		unsigned long long *db = nullptr; unsigned int *dd = nullptr;
-		rc = arena_get(h, &db, bounds.size() + 1); if (rc) return rc;
-		rc = arena_get(h, &dd, 2 * (bounds.size() + 1)); if (rc) return rc;
-		if (!bounds.empty()) HIPCHK(h, hipMemcpyAsync(db, bounds.data(), 8 * bounds.size(), hipMemcpyHostToDevice, h->stream));
-		tv.bounds = db; tv.n = (uint32_t)bounds.size(); tv.d_unique = dd; tv.d_single = dd + bounds.size() + 1;
-	}
-	/* long lists (SkLong in kmr_superkmer.hpp): found from the CSR, cut into work items, counted by a second launch into a merge table */
-	SkLong<W> lgMain; lgMain.item_c0 = lgMain.item_c1 = nullptr; lgMain.n_items = 0; lgMain.long_threshold = 0; lgMain.merge.slots = nullptr; lgMain.merge.ext = nullptr; lgMain.merge.log2cap = 0; lgMain.merge_used = nullptr;
-	lgMain.list_first = 0; lgMain.list_stride = 1;
-	if (h->sk_exchange && h->cfg.world_size > 1 && !refined) { lgMain.list_first = h->cfg.rank; lgMain.list_stride = h->cfg.world_size; }      /* the other lists went to their owners */
-	/* lists below early.hi were counted by kmr_count_lists_prefix: this pass starts behind them and their entries are taken over below.
-	 * An early count that overflowed its buffers, or was made for another min-depth or map layout, is void: everything is counted here */
-	uint64_t early_slots = 0; FinalizeCounters early_c; memset(&early_c, 0, sizeof(early_c));
+	return 0;
+}
+/* Lists below early.hi were counted by kmr_count_lists_prefix: the pass starts behind them (p.lgMain.list_first) and their entries are
+ * taken over afterwards (sk_append_early).  An early count that overflowed its buffers, or was made for another min-depth or map
+ * layout, is void: everything is counted here.  device_error: the early pass left an error other than an overflow in the build's
+ * error word; the caller ends its timing and reports it through sync_state. */
+template <int W> int sk_early_takeover(kmr_handle *h, SkFinalize<W> &p, uint32_t min_depth, bool &device_error) {
+	device_error = false;
+	FinalizeCounters &early_c = p.early_c;
 	h->last_early_hi = 0; h->last_early_entries = 0; h->last_early_overflowed = false;
-	if (h->early.active) {
-		uint32_t eerr = 0;      /* (the early pass's own word: its overflow never reaches h->derr, sync_state or another call) */
-		HIPCHK(h, hipMemcpy(&eerr, h->early.err.get<uint32_t>(), 4, hipMemcpyDeviceToHost));
-		unsigned long long ecur = 0;
-		HIPCHK(h, hipMemcpy(&ecur, h->early.cursor.get<unsigned long long>(), 8, hipMemcpyDeviceToHost)); HIPCHK(h, hipMemcpy(&early_c, h->early.fc.get(), sizeof(early_c), hipMemcpyDeviceToHost));
-		if (eerr & ~(uint32_t)ERR_ENTRIES_FULL) {      /* anything but an overflow is the build's error as ever */
-			uint32_t e = 0; HIPCHK(h, hipMemcpy(&e, h->derr.get<uint32_t>(), 4, hipMemcpyDeviceToHost)); e |= eerr & ~(uint32_t)ERR_ENTRIES_FULL;
-			HIPCHK(h, hipMemcpy(h->derr.get<uint32_t>(), &e, 4, hipMemcpyHostToDevice)); h->early.active = false;
-			time_end(h, 1, ea, eb); return sync_state(h);
-		}
-		const bool overflowed = (eerr & ERR_ENTRIES_FULL) || ecur > packed_entries(h, h->early.ue);
-		const bool ok = !overflowed && h->early.min_depth == min_depth && !tracking && !ext && !keepSing && !refined;
-		h->last_early_overflowed = overflowed;
-		if (ok) {
-			early_slots = ecur;
-			h->last_early_hi = h->early.hi; h->last_early_entries = early_c.weak_kept;
-			const uint64_t stride0 = lgMain.list_stride, first0 = lgMain.list_first;
-			uint64_t first = h->early.hi;
-			if (stride0 > 1) first += (first0 + stride0 - first % stride0) % stride0;      /* the first list at or behind hi that is this rank's */
-			lgMain.list_first = first;
-		} else { h->early.active = false; memset(&early_c, 0, sizeof(early_c)); }
+	if (!h->early.active) return 0;
+	uint32_t eerr = 0;      /* (the early pass's own word: its overflow never reaches h->derr, sync_state or another call) */
+	HIPCHK(h, hipMemcpy(&eerr, h->early.err.get<uint32_t>(), 4, hipMemcpyDeviceToHost));
+	unsigned long long ecur = 0;
+	HIPCHK(h, hipMemcpy(&ecur, h->early.cursor.get<unsigned long long>(), 8, hipMemcpyDeviceToHost)); HIPCHK(h, hipMemcpy(&early_c, h->early.fc.get(), sizeof(early_c), hipMemcpyDeviceToHost));
+	if (eerr & ~(uint32_t)ERR_ENTRIES_FULL) {      /* anything but an overflow is the build's error as ever */
+		uint32_t e = 0; HIPCHK(h, hipMemcpy(&e, h->derr.get<uint32_t>(), 4, hipMemcpyDeviceToHost)); e |= eerr & ~(uint32_t)ERR_ENTRIES_FULL;
+		HIPCHK(h, hipMemcpy(h->derr.get<uint32_t>(), &e, 4, hipMemcpyHostToDevice)); h->early.active = false;
+		device_error = true;
+		return 0;
 	}
-	SkLong<W> lgItems = lgMain;
-	uint64_t n_items = 0, long_chunks = 0;
+	const bool overflowed = (eerr & ERR_ENTRIES_FULL) || ecur > packed_entries(h, h->early.ue);
+	const bool ok = !overflowed && h->early.min_depth == min_depth && !p.tracking && !p.ext && !p.keepSing && !p.refined;
+	h->last_early_overflowed = overflowed;
+	if (ok) {
+		p.early_slots = ecur;
+		h->last_early_hi = h->early.hi; h->last_early_entries = early_c.weak_kept;
+		const uint64_t stride0 = p.lgMain.list_stride, first0 = p.lgMain.list_first;
+		uint64_t first = h->early.hi;
+		if (stride0 > 1) first += (first0 + stride0 - first % stride0) % stride0;      /* the first list at or behind hi that is this rank's */
+		p.lgMain.list_first = first;
+	} else { h->early.active = false; memset(&early_c, 0, sizeof(early_c)); }
+	return 0;
+}
+/* long lists (SkLong in kmr_superkmer.hpp): found from the CSR, cut into work items (p.lgItems), counted by a second launch into a merge table */
+template <int W> int sk_long_items(kmr_handle *h, SkFinalize<W> &p) {
+	p.lgItems = p.lgMain; p.n_items = 0;
 	/* (extension values: the 16-bit tallies of a block's table are exact below 65 536 k-mers, SK_EXT_LONG_CHUNKS) */
-	const uint64_t LONG_CHUNKS = ext ? std::min<uint64_t>(h->tune.long_list_chunks ? h->tune.long_list_chunks : SK_EXT_LONG_CHUNKS, SK_EXT_LONG_CHUNKS) : (h->tune.long_list_chunks ? h->tune.long_list_chunks : 1024), PIECE = std::max<uint64_t>(1, LONG_CHUNKS / 2);
-	if (!tracking && nch > LONG_CHUNKS) {
-		const uint64_t cap = (uint64_t)nch / PIECE + 2 * 1024 + 16;
-		uint64_t *ic0 = nullptr, *ic1 = nullptr; unsigned long long *dn = nullptr;
-		rc = arena_get(h, &ic0, cap); if (rc) return rc; rc = arena_get(h, &ic1, cap); if (rc) return rc; rc = arena_get(h, &dn, 1); if (rc) return rc;
-		HIPCHK(h, hipMemsetAsync(dn, 0, 8, h->stream));
-		hipLaunchKernelGGL(sk_long_items_kernel, dim3(grid_for(nl)), dim3(256), 0, h->stream, ls, nl, LONG_CHUNKS, PIECE, ic0, ic1, cap, dn);
-		HIPCHK(h, hipGetLastError());
-		unsigned long long hn = 0;
-		HIPCHK(h, hipMemcpyAsync(&hn, dn, 8, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
-		if (hn > cap) return fail(h, KMR_ERR_CAPACITY, "long-list work items (internal sizing error)");
-		n_items = hn; long_chunks = n_items * PIECE;
-		if (n_items) {
-			lgMain.long_threshold = LONG_CHUNKS;
-			lgItems.item_c0 = ic0; lgItems.item_c1 = ic1; lgItems.n_items = n_items; lgItems.merge_used = dn;
-		}
+	const uint64_t LONG_CHUNKS = p.ext ? std::min<uint64_t>(h->tune.long_list_chunks ? h->tune.long_list_chunks : SK_EXT_LONG_CHUNKS, SK_EXT_LONG_CHUNKS) : (h->tune.long_list_chunks ? h->tune.long_list_chunks : 1024), PIECE = std::max<uint64_t>(1, LONG_CHUNKS / 2);
+	if (p.tracking || p.nch <= LONG_CHUNKS) return 0;
+	const uint64_t cap = (uint64_t)p.nch / PIECE + 2 * 1024 + 16;
+	uint64_t *ic0 = nullptr, *ic1 = nullptr; unsigned long long *dn = nullptr;
+	int rc = arena_get(h, &ic0, cap); if (rc) return rc; rc = arena_get(h, &ic1, cap); if (rc) return rc; rc = arena_get(h, &dn, 1); if (rc) return rc;
+	HIPCHK(h, hipMemsetAsync(dn, 0, 8, h->stream));
+	hipLaunchKernelGGL(sk_long_items_kernel, dim3(grid_for(p.nl)), dim3(256), 0, h->stream, p.ls, p.nl, LONG_CHUNKS, PIECE, ic0, ic1, cap, dn);
+	HIPCHK(h, hipGetLastError());
+	unsigned long long hn = 0;
+	HIPCHK(h, hipMemcpyAsync(&hn, dn, 8, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
+	if (hn > cap) return fail(h, KMR_ERR_CAPACITY, "long-list work items (internal sizing error)");
+	p.n_items = hn;
+	if (p.n_items) {
+		p.lgMain.long_threshold = LONG_CHUNKS;
+		p.lgItems.item_c0 = ic0; p.lgItems.item_c1 = ic1; p.lgItems.n_items = p.n_items; p.lgItems.merge_used = dn;
 	}
+	return 0;
+}
+/* where a count pass puts its entries: the weak ones packed (h->ue: build_mode 3 without extension values, bucketed without a per-bucket
+ * histogram, kmr_buckets.hpp) or keys and values apart with their per-bucket counts (h->uw_*), singletons in h->us_* */
+CountOut count_out(kmr_handle *h, bool packed, unsigned long long *cursors, uint32_t *wc, uint32_t *sc, FinalizeCounters *fc) {
+	CountOut out{};
+	if (packed) { out.wentries = h->ue.get<uint64_t>(); out.wcap = packed_entries(h, h->ue); }
+	else { out.wkeys = h->uw_keys.get<uint64_t>(); out.wvals = h->uw_vals.get<uint32_t>(); out.wcap = key_entries(h, h->uw_keys); out.spkt = h->us_pkt.get<uint32_t>(); out.weakCount = wc; }
+	out.wcursor = cursors; out.scursor = cursors + 1;
+	out.skeys = h->us_keys.get<uint64_t>(); out.sweight = h->us_b8.get<uint8_t>(); out.scap = key_entries(h, h->us_keys);
+	out.singCount = sc; out.fc = fc; out.err = h->derr.get<uint32_t>();
+	return out;
+}
+/* The count pass, repeated with doubled entry buffers while they overflow and with a larger merge table while that fills.  overflowed:
+ * the entries did not fit buffers at their upper bounds (the count's timing is closed; the caller closes its own and fails). */
+template <int W> int sk_count_pass(kmr_handle *h, SkFinalize<W> &p, bool &overflowed) {
+	overflowed = false;
+	const bool ext = p.ext, keepSing = p.keepSing, tracking = p.tracking; const uint32_t vw = ext ? 15 : 3;
+	uint64_t &wcap = p.wcap, &scap = p.scap; const uint64_t wmax = p.wmax, smax = p.smax, nl = p.nl, n_items = p.n_items;
+	uint32_t *wc = p.wc, *sc = p.sc; FinalizeCounters *fc = p.fc; unsigned long long *cursors = p.cursors;
+	FinalizeCounters &c = p.c; unsigned long long *cur = p.cur; const SkTrackView &tv = p.tv; const FinalizeParams &f = p.f;
+	int rc = 0;
 	uint32_t merge_log2 = 16;
 	hipEvent_t tca, tcb; time_begin(h, KMR_TIME_COUNT, &tca, &tcb);
 	for (int attempt = 0; ; attempt++) {
@@ -1988,23 +2033,20 @@ template <int W> int finalize_superkmer_t(kmr_handle *h, uint32_t min_depth) {
 		}
 		HIPCHK(h, hipMemsetAsync(wc, 0, 4 * h->nb_weak, h->stream)); HIPCHK(h, hipMemsetAsync(sc, 0, 4 * h->nb_sing, h->stream));
 		HIPCHK(h, hipMemsetAsync(fc, 0, sizeof(FinalizeCounters), h->stream)); HIPCHK(h, hipMemsetAsync(cursors, 0, 16, h->stream));
-		CountOut out; out.wkeys = nullptr; out.wvals = nullptr; out.wentries = h->ue.get<uint64_t>(); out.wcursor = cursors; out.wcap = packed_entries(h, h->ue);
-		out.skeys = h->us_keys.get<uint64_t>(); out.sweight = h->us_b8.get<uint8_t>(); out.spkt = nullptr; out.scursor = cursors + 1; out.scap = key_entries(h, h->us_keys);
-		out.weakCount = nullptr; out.singCount = sc; out.fc = fc; out.err = h->derr.get<uint32_t>();      /* weak entries are bucketed without a per-bucket histogram (kmr_buckets.hpp) */
-		if (ext) { out.wkeys = h->uw_keys.get<uint64_t>(); out.wvals = h->uw_vals.get<uint32_t>(); out.wentries = nullptr; out.wcap = key_entries(h, h->uw_keys); out.spkt = h->us_pkt.get<uint32_t>(); out.weakCount = wc; }
+		const CountOut out = count_out(h, !ext, cursors, wc, sc, fc);
 		rc = zero_work_counter(h); if (rc) return rc;
-		const int grid = (int)std::min<uint64_t>((uint64_t)num_cus(h) * 4, (nl / lgMain.list_stride + SK_LBATCH) / SK_LBATCH);
-		auto kern = ext ? sk_count_kernel<W, COUNT_LOG2S_EXT, false, true> : (tracking ? sk_count_kernel<W, COUNT_LOG2S, true> : (uni ? sk_count_kernel<W, COUNT_LOG2S, false, false, true> : sk_count_kernel<W, COUNT_LOG2S, false>));
-		const size_t smem = ext ? sk_count_smem_bytes<W, COUNT_LOG2S_EXT, false, true>() : (tracking ? sk_count_smem_bytes<W, COUNT_LOG2S, true>() : (uni ? sk_count_smem_bytes<W, COUNT_LOG2S, false, false, true>() : sk_count_smem_bytes<W, COUNT_LOG2S, false>()));
+		const int grid = (int)std::min<uint64_t>((uint64_t)num_cus(h) * 4, (nl / p.lgMain.list_stride + SK_LBATCH) / SK_LBATCH);
+		SkCountLaunch<W> k;
+		rc = sk_count_select<W>(h, ext, tracking, p.uni, k); if (rc) return rc;
 		if (tracking) HIPCHK(h, hipMemsetAsync(tv.d_unique, 0, 8 * (tv.n + 1), h->stream));
-		HIPCHK(h, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-		if (dbg()) { int nb = 0; hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)kern, SKC_THREADS, smem); fprintf(stderr, "sk_count<W=%d>: %d blocks per CU (LDS %zu), %llu lists, %u chunks\n", W, nb, smem, (unsigned long long)nl, nch); }
-		hipLaunchKernelGGL(kern, dim3(grid), dim3(SKC_THREADS), smem, h->stream, pool_view(h, h->l1), ls, lc, nl, h->k, out, f, h->work_counter.get<unsigned int>(), sk_dbg_flags("KMR_SK_COUNT_DBG"), tv, lgMain);
+		if (dbg()) { int nb = 0; hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)k.kern, SKC_THREADS, k.smem); fprintf(stderr, "sk_count<W=%d>: %d blocks per CU (LDS %zu), %llu lists, %u chunks\n", W, nb, k.smem, (unsigned long long)nl, p.nch); }
+		hipLaunchKernelGGL(k.kern, dim3(grid), dim3(SKC_THREADS), k.smem, h->stream, pool_view(h, h->l1), p.ls, p.lc, nl, h->k, out, f, h->work_counter.get<unsigned int>(), sk_dbg_flags("KMR_SK_COUNT_DBG"), tv, p.lgMain);
 		HIPCHK(h, hipGetLastError());
 		DevBuf mslots, mext;      /* freed at the end of the attempt */
 		if (n_items) {
 			/* the merge table holds the distinct keys of the long lists: few when a list is long because a k-mer repeats, at most the
 			 * k-mers of those lists; it starts small and the attempt is repeated with a larger one if it fills */
+			SkLong<W> &lgItems = p.lgItems;
 			if (mslots.alloc(sizeof(Slot<W>) << merge_log2) != hipSuccess) return fail(h, KMR_ERR_OOM, "merge table of the long lists");
 			if (ext && mext.alloc(sizeof(ExtSlot) << merge_log2) != hipSuccess) return fail(h, KMR_ERR_OOM, "merge table of the long lists");
 			hipLaunchKernelGGL(table_clear_kernel<W>, dim3(grid_for(1ull << merge_log2)), dim3(256), 0, h->stream, mslots.get<Slot<W>>(), mext.get<ExtSlot>(), 1ull << merge_log2);
@@ -2012,7 +2054,7 @@ template <int W> int finalize_superkmer_t(kmr_handle *h, uint32_t min_depth) {
 			HIPCHK(h, hipMemsetAsync(lgItems.merge_used, 0, 8, h->stream));
 			rc = zero_work_counter(h); if (rc) return rc;
 			const int grid2 = (int)std::min<uint64_t>((uint64_t)num_cus(h) * 4, n_items);
-			hipLaunchKernelGGL(kern, dim3(grid2), dim3(SKC_THREADS), smem, h->stream, pool_view(h, h->l1), ls, lc, nl, h->k, out, f, h->work_counter.get<unsigned int>(), sk_dbg_flags("KMR_SK_COUNT_DBG"), tv, lgItems);
+			hipLaunchKernelGGL(k.kern, dim3(grid2), dim3(SKC_THREADS), k.smem, h->stream, pool_view(h, h->l1), p.ls, p.lc, nl, h->k, out, f, h->work_counter.get<unsigned int>(), sk_dbg_flags("KMR_SK_COUNT_DBG"), tv, lgItems);
 			hipLaunchKernelGGL(sk_merge_emit_kernel<W>, dim3(grid_for(1ull << merge_log2)), dim3(256), 0, h->stream, lgItems.merge, out, f);
 			if (hipGetLastError() != hipSuccess) return fail(h, KMR_ERR_HIP, "long-list launches");
 		}
@@ -2027,51 +2069,78 @@ template <int W> int finalize_superkmer_t(kmr_handle *h, uint32_t min_depth) {
 			continue;
 		}
 		if (!(cerr & ERR_ENTRIES_FULL)) break;
-		if ((wcap >= wmax && scap >= smax) || attempt >= 8) { time_end(h, KMR_TIME_COUNT, tca, tcb); time_end(h, 1, ea, eb); return fail(h, KMR_ERR_CAPACITY, "entry buffers of the count pass overflowed at their upper bound (internal sizing error)"); }
+		if ((wcap >= wmax && scap >= smax) || attempt >= 8) { overflowed = true; break; }
 		cerr &= ~(uint32_t)ERR_ENTRIES_FULL;
 		HIPCHK(h, hipMemcpy(h->derr.get<uint32_t>(), &cerr, 4, hipMemcpyHostToDevice));
 		wcap = std::min<uint64_t>(wmax, wcap * 2); if (keepSing) scap = std::min<uint64_t>(smax, scap * 2);
 		if (dbg()) fprintf(stderr, "sk count pass: entry buffers too small, retrying with %llu / %llu\n", (unsigned long long)wcap, (unsigned long long)scap);
 	}
 	time_end(h, KMR_TIME_COUNT, tca, tcb);
-	h->stats.unique_kmers = c.unique;
-	h->stats.singleton_kmers = f.has_singletons ? c.singletons : 0;
-	if (tracking) {
-		std::vector<unsigned int> dd(2 * (tv.n + 1), 0);
-		HIPCHK(h, hipMemcpy(dd.data(), tv.d_unique, 8 * (tv.n + 1), hipMemcpyDeviceToHost));
-		h->trk_elems.clear();
-		uint64_t uniq = 0; int64_t single = 0;
-		const uint64_t sub = h->cfg.kmer_subsample > 1 ? h->cfg.kmer_subsample : 1;      /* track() scales what it stores, :882-887 */
-		for (uint32_t i = 0; i < tv.n; i++) {
-			uniq += dd[i]; single += (int32_t)dd[tv.n + 1 + i];
-			h->trk_elems.push_back(snap_raw[i] * sub); h->trk_elems.push_back(snap_good[i] * sub);
-			h->trk_elems.push_back(uniq * sub); h->trk_elems.push_back(f.has_singletons ? (uint64_t)single * sub : 0);
-		}
+	return 0;
+}
+/* the early count's entries behind this pass's (the slabs' unused tails are holes in both), its counters added */
+template <int W> int sk_append_early(kmr_handle *h, SkFinalize<W> &p) {
+	FinalizeCounters &c = p.c; const FinalizeCounters &early_c = p.early_c; unsigned long long *cur = p.cur; const uint64_t early_slots = p.early_slots;
+	const size_t eb = 8ull * (W + 1);
+	if (cur[0] + early_slots > packed_entries(h, h->ue)) {
+		DevBuf bigger;
+		HIPCHK(h, bigger.alloc(eb * (cur[0] + early_slots + 4096)));
+		HIPCHK(h, hipMemcpyAsync(bigger.get(), h->ue.get(), eb * cur[0], hipMemcpyDeviceToDevice, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
+		h->ue = std::move(bigger);
 	}
-	if (early_slots) {      /* the early count's entries behind this pass's (the slabs' unused tails are holes in both) */
-		const size_t eb = 8ull * (W + 1);
-		if (cur[0] + early_slots > packed_entries(h, h->ue)) {
-			DevBuf bigger;
-			HIPCHK(h, bigger.alloc(eb * (cur[0] + early_slots + 4096)));
-			HIPCHK(h, hipMemcpyAsync(bigger.get(), h->ue.get(), eb * cur[0], hipMemcpyDeviceToDevice, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
-			h->ue = std::move(bigger);
-		}
-		HIPCHK(h, hipMemcpyAsync((uint8_t *)h->ue.get<uint64_t>() + eb * cur[0], h->early.ue.get<uint64_t>(), eb * early_slots, hipMemcpyDeviceToDevice, h->stream));
-		cur[0] += early_slots;
-		c.unique += early_c.unique; c.singletons += early_c.singletons; c.weak_kept += early_c.weak_kept; c.sing_kept += early_c.sing_kept;
-		c.saturated += early_c.saturated; c.sat_sightings += early_c.sat_sightings;
-		h->stats.unique_kmers = c.unique; h->stats.singleton_kmers = f.has_singletons ? c.singletons : 0;
+	HIPCHK(h, hipMemcpyAsync((uint8_t *)h->ue.get<uint64_t>() + eb * cur[0], h->early.ue.get<uint64_t>(), eb * early_slots, hipMemcpyDeviceToDevice, h->stream));
+	cur[0] += early_slots;
+	c.unique += early_c.unique; c.singletons += early_c.singletons; c.weak_kept += early_c.weak_kept; c.sing_kept += early_c.sing_kept;
+	c.saturated += early_c.saturated; c.sat_sightings += early_c.sat_sightings;
+	h->stats.unique_kmers = c.unique; h->stats.singleton_kmers = p.f.has_singletons ? c.singletons : 0;
+	return 0;
+}
+
+template <int W> int finalize_superkmer_t(kmr_handle *h, uint32_t min_depth) {
+	int rc = sync_state(h);
+	if (rc) return rc;
+	hipEvent_t ea, eb; time_begin(h, 1, &ea, &eb);
+	SkFinalize<W> p;
+	p.f = finalize_params(h, min_depth);
+	p.keepSing = p.f.has_singletons && min_depth <= 1;
+	p.ext = h->ext;      /* extension values: entries of 15 value words, keys and values apart, bucketed by the scatter + per-bucket sort */
+	p.tracking = h->cfg.size_tracker != 0;
+	if (!h->l1.head) { rc = pool_reserve(h, h->l1, 0, false); if (rc) return rc; }
+	rc = arena_reset(h); if (rc) return rc;
+	p.nl = h->sk_state ? sk_list_count(h->sk_bits) : 1;
+	if (h->sk_state) {
+		hipLaunchKernelGGL(sk_close_kernel, dim3(grid_for(p.nl)), dim3(256), 0, h->stream, h->sk_state.get<unsigned long long>(), p.nl, h->l1.chunk_count.get<uint32_t>(), h->l1.cap);
+		HIPCHK(h, hipGetLastError());
 	}
+	p.refined = h->sk_state && h->sk_fine_shift > 0;
+	if (p.refined) { rc = sk_refine_lists(h, p.nl); if (rc) return rc; }
+	rc = build_csr(h, h->l1, p.nl, 0, &p.ls, &p.lc, &p.nch); if (rc) return rc;
+	rc = sk_entry_buffers<W>(h, p, h->stats.raw_good_kmers); if (rc) return rc;
+	rc = sk_count_uniform<W>(h, p.tracking, p.uni, p.f.uni_wbits); if (rc) return rc;
+	h->last_count_uniform = p.uni;
+	if (p.tracking) { rc = sk_track_view(h, p.tv); if (rc) return rc; }
+	p.lgMain = sk_own_lists<W>(h, p.refined);
+	bool device_error = false;
+	rc = sk_early_takeover<W>(h, p, min_depth, device_error); if (rc) return rc;
+	if (device_error) { time_end(h, 1, ea, eb); return sync_state(h); }
+	rc = sk_long_items<W>(h, p); if (rc) return rc;
+	bool overflowed = false;
+	rc = sk_count_pass<W>(h, p, overflowed); if (rc) return rc;
+	if (overflowed) { time_end(h, 1, ea, eb); return fail(h, KMR_ERR_CAPACITY, "entry buffers of the count pass overflowed at their upper bound (internal sizing error)"); }
+	h->stats.unique_kmers = p.c.unique;
+	h->stats.singleton_kmers = p.f.has_singletons ? p.c.singletons : 0;
+	if (p.tracking) { rc = sk_track_elements(h, p.tv, p.f.has_singletons); if (rc) return rc; }
+	if (p.early_slots) { rc = sk_append_early<W>(h, p); if (rc) return rc; }
 	h->early.active = false;
 	hipEvent_t tma, tmb; time_begin(h, KMR_TIME_BUCKETS, &tma, &tmb);
-	rc = finish_maps_from_entries(h, wc, sc, cur[0], cur[1], c.weak_kept, c.sing_kept, keepSing, !ext);
+	rc = finish_maps_from_entries(h, p.wc, p.sc, p.cur[0], p.cur[1], p.c.weak_kept, p.c.sing_kept, p.keepSing, !p.ext);
 	time_end(h, KMR_TIME_BUCKETS, tma, tmb);
 	if (rc) return rc;
 	h->last_saturated_keys = 0; h->last_saturated_batches = 0;
-	if (c.saturated) { rc = saturated_fix_t<W>(h, ls, lc, nl, c.saturated, c.sat_sightings, f.has_singletons); if (rc) return rc; }
+	if (p.c.saturated) { rc = saturated_fix_t<W>(h, p.ls, p.lc, p.nl, p.c.saturated, p.c.sat_sightings, p.f.has_singletons); if (rc) return rc; }
 	time_end(h, 1, ea, eb);
-	h->has_singletons = keepSing;
-	h->stats.weak_entries = h->weak.n; h->stats.singleton_entries = keepSing ? h->sing.n : 0;
+	h->has_singletons = p.keepSing;
+	h->stats.weak_entries = h->weak.n; h->stats.singleton_entries = p.keepSing ? h->sing.n : 0;
 	h->finalized = true; h->map_gen++;
 	rc = sync_state(h);
 	if (!rc && !h->arena_overflow.empty()) rc = arena_reset(h);
@@ -2083,7 +2152,7 @@ template <int W> int finalize_superkmer_t(kmr_handle *h, uint32_t min_depth) {
  * anything else, or buffers that turn out too small, leaves the lists to kmr_finalize. */
 template <int W> int count_prefix_superkmer_t(kmr_handle *h, uint32_t min_depth, uint64_t hi) {
 	int rc = sync_state(h); if (rc) return rc;
-	FinalizeParams f; f.kb = h->hkb; f.ext_min_q = h->cfg.ext_min_quality; f.min_depth = min_depth; f.has_singletons = h->cfg.separate_singletons ? 1 : 0; f.nb_weak = h->nb_weak; f.nb_sing = h->nb_sing; f.uni_wbits = 0;
+	FinalizeParams f = finalize_params(h, min_depth);
 	const bool keepSing = f.has_singletons && min_depth <= 1;
 	h->early.active = false;      /* an earlier early count is replaced */
 	if (h->ext || h->cfg.size_tracker || keepSing || (h->sk_state && h->sk_fine_shift > 0) || !h->sk_state) return KMR_OK;      /* nothing counted early: kmr_finalize does it all */
@@ -2109,53 +2178,34 @@ template <int W> int count_prefix_superkmer_t(kmr_handle *h, uint32_t min_depth,
 	HIPCHK(h, hipMemsetAsync(h->early.cursor.get<unsigned long long>(), 0, 16, h->stream)); HIPCHK(h, hipMemsetAsync(h->early.fc.get(), 0, sizeof(FinalizeCounters), h->stream));
 	HIPCHK(h, hipMemsetAsync(h->early.err.get<uint32_t>(), 0, 4, h->stream));      /* (a replaced early count leaves no flag behind) */
 	bool uni = false;
-	if (!h->sk_uni_mixed && !h->tune.no_uniform_count && !h->peer_uni_mixed && (W == 1 || (h->k & 31u) != 0)) {
-		uint32_t w = h->sk_uni_w; bool mixed = false;
-		if (h->peer_uni_w != SK_UNI_NONE) { if (w == SK_UNI_NONE) w = h->peer_uni_w; else if (w != h->peer_uni_w) mixed = true; }
-		if (h->d_uni) {
-			uint32_t dv[2] = {SK_UNI_NONE, 0u};
-			HIPCHK(h, hipMemcpy(dv, h->d_uni.get<uint32_t>(), 8, hipMemcpyDeviceToHost));
-			if (dv[1]) mixed = true;
-			else if (dv[0] != SK_UNI_NONE) { if (w == SK_UNI_NONE) w = dv[0]; else if (w != dv[0]) mixed = true; }
-		}
-		if (!mixed && w != SK_UNI_NONE) { uni = true; f.uni_wbits = w; }
-	}
-	SkTrackView tv; tv.bounds = nullptr; tv.n = 0; tv.d_unique = tv.d_single = nullptr;
-	SkLong<W> lg; lg.item_c0 = lg.item_c1 = nullptr; lg.n_items = 0; lg.merge.slots = nullptr; lg.merge.ext = nullptr; lg.merge.log2cap = 0; lg.merge_used = nullptr;
-	lg.list_first = 0; lg.list_stride = 1;
-	if (h->sk_exchange && h->cfg.world_size > 1) { lg.list_first = h->cfg.rank; lg.list_stride = h->cfg.world_size; }
+	if (!h->peer_uni_mixed) { rc = sk_count_uniform<W>(h, false, uni, f.uni_wbits); if (rc) return rc; }      /* (senders that declared mixed weights settle it here without a look at the device pair) */
+	const SkTrackView tv{};
+	SkLong<W> lg = sk_own_lists<W>(h, false);
 	/* (lists too long for one block are left to kmr_finalize's pass over work items, which covers the whole list space) */
 	lg.long_threshold = h->tune.long_list_chunks ? h->tune.long_list_chunks : 1024;
 	uint32_t *sc = nullptr;
 	rc = arena_get(h, &sc, h->nb_sing); if (rc) return rc;
 	HIPCHK(h, hipMemsetAsync(sc, 0, 4 * h->nb_sing, h->stream));
-	CountOut out; out.wkeys = nullptr; out.wvals = nullptr; out.wentries = h->early.ue.get<uint64_t>(); out.wcursor = h->early.cursor.get<unsigned long long>(); out.wcap = packed_entries(h, h->early.ue);
-	out.skeys = nullptr; out.sweight = nullptr; out.spkt = nullptr; out.scursor = h->early.cursor.get<unsigned long long>() + 1; out.scap = 0;
-	out.weakCount = nullptr; out.singCount = sc; out.fc = (FinalizeCounters *)h->early.fc.get(); out.err = h->early.err.get<uint32_t>();
+	CountOut out{};      /* packed weak entries only, everything in the early pass's own buffers */
+	out.wentries = h->early.ue.get<uint64_t>(); out.wcursor = h->early.cursor.get<unsigned long long>(); out.wcap = packed_entries(h, h->early.ue);
+	out.scursor = h->early.cursor.get<unsigned long long>() + 1;
+	out.singCount = sc; out.fc = (FinalizeCounters *)h->early.fc.get(); out.err = h->early.err.get<uint32_t>();
 	rc = zero_work_counter(h); if (rc) return rc;
 	const uint64_t n_work = hi > lg.list_first ? (hi - lg.list_first + lg.list_stride - 1) / lg.list_stride : 0;
 	if (n_work) {
 		const int grid = (int)std::min<uint64_t>((uint64_t)num_cus(h) * 4, (n_work + SK_LBATCH) / SK_LBATCH);
-		auto kern = uni ? sk_count_kernel<W, COUNT_LOG2S, false, false, true> : sk_count_kernel<W, COUNT_LOG2S, false>;
-		const size_t smem = uni ? sk_count_smem_bytes<W, COUNT_LOG2S, false, false, true>() : sk_count_smem_bytes<W, COUNT_LOG2S, false>();
-		HIPCHK(h, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+		SkCountLaunch<W> k;
+		rc = sk_count_select<W>(h, false, false, uni, k); if (rc) return rc;
 		hipEvent_t a, b; time_begin(h, KMR_TIME_COUNT, &a, &b);
-		hipLaunchKernelGGL(kern, dim3(grid), dim3(SKC_THREADS), smem, h->stream, pool_view(h, h->l1), ls, lc, hi, h->k, out, f, h->work_counter.get<unsigned int>(), sk_dbg_flags("KMR_SK_COUNT_DBG"), tv, lg);
+		hipLaunchKernelGGL(k.kern, dim3(grid), dim3(SKC_THREADS), k.smem, h->stream, pool_view(h, h->l1), ls, lc, hi, h->k, out, f, h->work_counter.get<unsigned int>(), sk_dbg_flags("KMR_SK_COUNT_DBG"), tv, lg);
 		time_end(h, KMR_TIME_COUNT, a, b);
 		HIPCHK(h, hipGetLastError());
 	}
 	h->early.active = true; h->early.hi = hi; h->early.min_depth = min_depth;
 	return KMR_OK;      /* asynchronous: the handle's stream carries the pass; kmr_finalize (or kmr_sync) waits for it */
 }
-int count_prefix_superkmer(kmr_handle *h, uint32_t min_depth, uint64_t hi) {
-	switch (h->W) { case 1: return count_prefix_superkmer_t<1>(h, min_depth, hi); case 2: return count_prefix_superkmer_t<2>(h, min_depth, hi);
-	case 3: return count_prefix_superkmer_t<3>(h, min_depth, hi); default: return count_prefix_superkmer_t<4>(h, min_depth, hi); }
-}
-
-int finalize_superkmer(kmr_handle *h, uint32_t min_depth) {
-	switch (h->W) { case 1: return finalize_superkmer_t<1>(h, min_depth); case 2: return finalize_superkmer_t<2>(h, min_depth);
-	case 3: return finalize_superkmer_t<3>(h, min_depth); default: return finalize_superkmer_t<4>(h, min_depth); }
-}
+int count_prefix_superkmer(kmr_handle *h, uint32_t min_depth, uint64_t hi) { return with_w(h, [&](auto W) { return count_prefix_superkmer_t<W()>(h, min_depth, hi); }); }
+int finalize_superkmer(kmr_handle *h, uint32_t min_depth) { return with_w(h, [&](auto W) { return finalize_superkmer_t<W()>(h, min_depth); }); }
 
 /* the device memory of group M of the handle goes back (kmr_handle's bases) */
 template <class M> void release(kmr_handle *h) { static_cast<M &>(*h) = M(); }
@@ -2410,9 +2460,7 @@ int kmr_add_reads_dev(kmr_handle *h, const void *dev_bases, const void *dev_qual
 	if (n_reads == 0) return KMR_OK;
 	if (!dev_bases || !dev_offsets) return fail(h, KMR_ERR_INVALID_ARG, "null device buffer");
 	hipSetDevice(h->device);
-	ReadsView rv; rv.bases = (const uint8_t *)dev_bases; rv.quals = (const uint8_t *)dev_quals; rv.offsets = (const uint64_t *)dev_offsets;
-	rv.discarded = (const uint8_t *)dev_discarded; rv.n_reads = n_reads; rv.stream_base = h->stream_base; rv.first_read_idx = first_global_read_idx;
-	rv.u_start = rv.u_end = rv.u_read = nullptr; rv.n_units = 0;
+	const ReadsView rv = reads_view(dev_bases, dev_quals, dev_offsets, n_reads, dev_discarded, h->stream_base, first_global_read_idx);
 	/* the stream ordinal of an occurrence decides which sighting of a k-mer was its first (directionBias, the quantised first
 	 * weight): 40 bits in the table slots, and the 16-byte records of build_mode 2 without extension values carry 32 of them */
 	if (h->stream_base + total_bases > MAX_STREAM_ORDINAL) return fail(h, KMR_ERR_CAPACITY, "more than 2^40 input bases on one handle");
@@ -2440,18 +2488,16 @@ static int tb_pipeline_ready(kmr_handle *h) {
 	return 0;
 }
 
-int kmr_add_reads(kmr_handle *h, const char *bases, const char *quals, const uint64_t *offsets, uint64_t n_reads,
-                  uint64_t first_global_read_idx, const uint8_t *discarded) {
-	if (!h) return KMR_ERR_INVALID_ARG;
-	if (h->finalized) return fail(h, KMR_ERR_STATE, "kmr_add_reads after kmr_finalize");
-	if (n_reads == 0) return KMR_OK;
-	if (!bases || !offsets) return fail(h, KMR_ERR_INVALID_ARG, "null buffer");
-	hipSetDevice(h->device);
-	/* pieces of about 2^28 bases through two sets of staging buffers and the handle's copy stream: piece i + 1 is on the bus while the
-	 * device extracts piece i; the offsets go over as they are (the device arrays are addressed through pointers moved back by the
-	 * piece's first offset) */
-	{ int rcp = tb_pipeline_ready(h); if (rcp) return rcp; }
+/* a failed HIP call of the piece pipeline: both streams drained before the error goes back */
 #define TBCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { hipStreamSynchronize(h->tb_copy_stream); hipStreamSynchronize(h->stream); h->err = std::string(#call) + ": " + hip_err_text(e_); return e_ == hipErrorOutOfMemory ? KMR_ERR_OOM : KMR_ERR_HIP; } } while (0)
+/* A host batch goes over in pieces of about 2^28 bases (kmr_tune "twobit_piece_bases") through two sets of staging buffers and a copy
+ * stream of the handle's own: while the device extracts piece i, piece i + 1 is on the bus (the host's pageable memory: the calling
+ * thread feeds the copies, the device does not wait for it).  stage(set, r0, r1) puts the copies of reads [r0, r1) on the copy stream
+ * (tb_stage_copy into staging set `set`), feed(r0, r1) hands the staged piece to the device entry; both return a KMR code.  Per piece:
+ * wait for the set's last piece to be consumed, stage, record ready, the handle's stream waits for it, feed, record consumed. */
+}  // extern "C"
+template <class Stage, class Feed> static int tb_feed_pieces(kmr_handle *h, const uint64_t *offsets, uint64_t n_reads, Stage &&stage, Feed &&feed) {
+	{ int rcp = tb_pipeline_ready(h); if (rcp) return rcp; }
 	const uint64_t piece_bases = h->tune.twobit_piece_bases ? h->tune.twobit_piece_bases : (1ull << 28);
 	int rc = KMR_OK; int set = 0;
 	h->call_bases_hint = n_reads ? offsets[n_reads] - offsets[0] : 0;      /* what the first piece sizes is the whole call's */
@@ -2459,24 +2505,43 @@ int kmr_add_reads(kmr_handle *h, const char *bases, const char *quals, const uin
 	for (uint64_t r0 = 0; r0 < n_reads && rc == KMR_OK; set ^= 1) {
 		uint64_t r1 = r0 + 1;
 		while (r1 < n_reads && offsets[r1 + 1] - offsets[r0] <= piece_bases) r1++;
-		const uint64_t m = r1 - r0, total = offsets[r1] - offsets[r0];
-		void *db = nullptr, *dq = nullptr, *doff = nullptr, *dd = nullptr;
-		if (h->tb_set_used[set]) TBCHK(hipStreamWaitEvent(h->tb_copy_stream, h->tb_consumed[set], 0));
-		TBCHK(tb_stage_copy(h, set, 0, bases + offsets[r0], total, &db)); TBCHK(tb_stage_copy(h, set, 2, offsets + r0, 8 * (m + 1), &doff));
-		if (quals) TBCHK(tb_stage_copy(h, set, 6, quals + offsets[r0], total, &dq));
-		if (discarded) TBCHK(tb_stage_copy(h, set, 7, discarded + r0, m, &dd));
-		TBCHK(hipMemsetAsync((uint8_t *)db + total, 0, 64, h->tb_copy_stream)); if (dq) TBCHK(hipMemsetAsync((uint8_t *)dq + total, 0, 64, h->tb_copy_stream));
+		if (h->tb_set_used[set]) TBCHK(hipStreamWaitEvent(h->tb_copy_stream, h->tb_consumed[set], 0));      /* the piece that used this set last has been extracted */
+		{ int rcs = stage(set, r0, r1); if (rcs) return rcs; }
 		TBCHK(hipEventRecord(h->tb_ready[set], h->tb_copy_stream));
 		TBCHK(hipStreamWaitEvent(h->stream, h->tb_ready[set], 0));
-		rc = kmr_add_reads_dev(h, (uint8_t *)db - offsets[r0], dq ? (uint8_t *)dq - offsets[r0] : nullptr, doff, m, total, first_global_read_idx + r0, dd);
+		rc = feed(r0, r1);
 		TBCHK(hipEventRecord(h->tb_consumed[set], h->stream)); h->tb_set_used[set] = true;
 		r0 = r1;
 	}
-#undef TBCHK
 	hipStreamSynchronize(h->tb_copy_stream);
 	if (!rc) rc = sync_state(h);
 	else hipStreamSynchronize(h->stream);
 	return rc;
+}
+extern "C" {
+
+int kmr_add_reads(kmr_handle *h, const char *bases, const char *quals, const uint64_t *offsets, uint64_t n_reads,
+                  uint64_t first_global_read_idx, const uint8_t *discarded) {
+	if (!h) return KMR_ERR_INVALID_ARG;
+	if (h->finalized) return fail(h, KMR_ERR_STATE, "kmr_add_reads after kmr_finalize");
+	if (n_reads == 0) return KMR_OK;
+	if (!bases || !offsets) return fail(h, KMR_ERR_INVALID_ARG, "null buffer");
+	hipSetDevice(h->device);
+	/* the offsets go over as they are (the device arrays are addressed through pointers moved back by the piece's first offset) */
+	void *db = nullptr, *dq = nullptr, *doff = nullptr, *dd = nullptr;
+	auto stage = [&](int set, uint64_t r0, uint64_t r1) -> int {
+		const uint64_t m = r1 - r0, total = offsets[r1] - offsets[r0];
+		dq = nullptr; dd = nullptr;
+		TBCHK(tb_stage_copy(h, set, 0, bases + offsets[r0], total, &db)); TBCHK(tb_stage_copy(h, set, 2, offsets + r0, 8 * (m + 1), &doff));
+		if (quals) TBCHK(tb_stage_copy(h, set, 6, quals + offsets[r0], total, &dq));
+		if (discarded) TBCHK(tb_stage_copy(h, set, 7, discarded + r0, m, &dd));
+		TBCHK(hipMemsetAsync((uint8_t *)db + total, 0, 64, h->tb_copy_stream)); if (dq) TBCHK(hipMemsetAsync((uint8_t *)dq + total, 0, 64, h->tb_copy_stream));
+		return KMR_OK;
+	};
+	auto feed = [&](uint64_t r0, uint64_t r1) {
+		return kmr_add_reads_dev(h, (uint8_t *)db - offsets[r0], dq ? (uint8_t *)dq - offsets[r0] : nullptr, doff, r1 - r0, offsets[r1] - offsets[r0], first_global_read_idx + r0, dd);
+	};
+	return tb_feed_pieces(h, offsets, n_reads, stage, feed);
 }
 
 /* May sk_extract_lean_kernel<.., PACKED> take a packed batch as it is?  Whenever add_reads_superkmer_t would hand the unpacked
@@ -2523,8 +2588,7 @@ int kmr_add_reads_twobit_dev(kmr_handle *h, const void *dev_twobit, const void *
 		hipLaunchKernelGGL(offsets_rel_kernel, dim3(grid_for(n_reads + 1)), dim3(256), 0, h->stream, (const uint64_t *)dev_offsets, n_reads, h->tb_rel.get<uint64_t>());
 		HIPCHK(h, hipGetLastError());
 		if (h->stream_base + total_bases > MAX_STREAM_ORDINAL) return fail(h, KMR_ERR_CAPACITY, "more than 2^40 input bases on one handle");
-		ReadsView rv; rv.bases = nullptr; rv.quals = nullptr; rv.offsets = h->tb_rel.get<uint64_t>(); rv.discarded = (const uint8_t *)dev_discarded; rv.n_reads = n_reads;
-		rv.stream_base = h->stream_base; rv.first_read_idx = first_global_read_idx; rv.u_start = rv.u_end = rv.u_read = nullptr; rv.n_units = 0;
+		const ReadsView rv = reads_view(nullptr, nullptr, h->tb_rel.get<uint64_t>(), n_reads, dev_discarded, h->stream_base, first_global_read_idx);
 		SkPacked pkd; pkd.bytes = (const uint8_t *)dev_twobit; pkd.off = tboff; pkd.mk_off = (const uint64_t *)dev_markup_offsets; pkd.mk_pos = (const uint32_t *)dev_markup_pos; pkd.mk_char = (const uint8_t *)dev_markup_char;
 		h->packed_direct = &pkd; h->uniform_q_hint = uniform_quality ? uniform_quality : -1;
 		const int rc = add_reads_superkmer(h, rv, total_bases);
@@ -2567,44 +2631,27 @@ int kmr_add_reads_twobit(kmr_handle *h, const uint8_t *twobit, const uint64_t *t
 	if (n_reads == 0) return KMR_OK;
 	if (!twobit || !twobit_offsets || !offsets) return fail(h, KMR_ERR_INVALID_ARG, "null buffer");
 	hipSetDevice(h->device);
-	/* The batch goes over in pieces of about 2^28 bases through two sets of staging buffers and a copy stream of the handle's own:
-	 * while the device unpacks and extracts piece i, piece i + 1 is on the bus (the host's pageable memory: the calling thread feeds
-	 * the copies, the device does not wait for it). */
-	{ int rcp = tb_pipeline_ready(h); if (rcp) return rcp; }
-	auto stage = [&](int set, int which, const void *src, size_t bytes, void **dst) -> hipError_t { return tb_stage_copy(h, set, which, src, bytes, dst); };
-#define TBCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { hipStreamSynchronize(h->tb_copy_stream); hipStreamSynchronize(h->stream); h->err = std::string(#call) + ": " + hip_err_text(e_); return e_ == hipErrorOutOfMemory ? KMR_ERR_OOM : KMR_ERR_HIP; } } while (0)
-	const uint64_t piece_bases = h->tune.twobit_piece_bases ? h->tune.twobit_piece_bases : (1ull << 28);
-	int rc = KMR_OK; int set = 0;
-	h->call_bases_hint = n_reads ? offsets[n_reads] - offsets[0] : 0;      /* what the first piece sizes is the whole call's */
-	struct HintReset { kmr_handle *h; ~HintReset() { h->call_bases_hint = 0; } } hint_reset{h};
-	for (uint64_t r0 = 0; r0 < n_reads && rc == KMR_OK; set ^= 1) {
-		uint64_t r1 = r0 + 1;
-		while (r1 < n_reads && offsets[r1 + 1] - offsets[r0] <= piece_bases) r1++;
+	void *dtb = nullptr, *dto = nullptr, *doff = nullptr, *dmo = nullptr, *dmp = nullptr, *dmc = nullptr, *dq = nullptr, *dd = nullptr;
+	/* (the offset arrays go over as they are: the unpack kernel counts base offsets from the piece's first one itself, and the packed
+	 * bytes / markups are addressed through pointers moved back by the piece's first offset -- no pass over the reads on the host) */
+	auto stage = [&](int set, uint64_t r0, uint64_t r1) -> int {
 		const uint64_t m = r1 - r0, total = offsets[r1] - offsets[r0], tbytes = twobit_offsets[r1] - twobit_offsets[r0];
 		const uint64_t nm = markup_offsets ? markup_offsets[r1] - markup_offsets[r0] : 0;
-		void *dtb = nullptr, *dto = nullptr, *doff = nullptr, *dmo = nullptr, *dmp = nullptr, *dmc = nullptr, *dq = nullptr, *dd = nullptr;
-		/* (the offset arrays go over as they are: the unpack kernel counts base offsets from the piece's first one itself, and the packed
-		 * bytes / markups are addressed through pointers moved back by the piece's first offset -- no pass over the reads on the host) */
-		if (h->tb_set_used[set]) TBCHK(hipStreamWaitEvent(h->tb_copy_stream, h->tb_consumed[set], 0));      /* the piece that used this set last has been unpacked and extracted */
-		TBCHK(stage(set, 0, twobit + twobit_offsets[r0], tbytes, &dtb)); TBCHK(stage(set, 1, twobit_offsets + r0, 8 * (m + 1), &dto)); TBCHK(stage(set, 2, offsets + r0, 8 * (m + 1), &doff));
+		dmo = dmp = dmc = dq = dd = nullptr;
+		TBCHK(tb_stage_copy(h, set, 0, twobit + twobit_offsets[r0], tbytes, &dtb)); TBCHK(tb_stage_copy(h, set, 1, twobit_offsets + r0, 8 * (m + 1), &dto)); TBCHK(tb_stage_copy(h, set, 2, offsets + r0, 8 * (m + 1), &doff));
 		dtb = (uint8_t *)dtb - twobit_offsets[r0];
 		if (nm) {
-			TBCHK(stage(set, 3, markup_offsets + r0, 8 * (m + 1), &dmo)); TBCHK(stage(set, 4, markup_pos + markup_offsets[r0], 4 * nm, &dmp)); TBCHK(stage(set, 5, markup_char + markup_offsets[r0], nm, &dmc));
+			TBCHK(tb_stage_copy(h, set, 3, markup_offsets + r0, 8 * (m + 1), &dmo)); TBCHK(tb_stage_copy(h, set, 4, markup_pos + markup_offsets[r0], 4 * nm, &dmp)); TBCHK(tb_stage_copy(h, set, 5, markup_char + markup_offsets[r0], nm, &dmc));
 			dmp = (uint32_t *)dmp - markup_offsets[r0]; dmc = (uint8_t *)dmc - markup_offsets[r0];
 		}
-		if (quals) TBCHK(stage(set, 6, quals + offsets[r0], total, &dq));
-		if (discarded) TBCHK(stage(set, 7, discarded + r0, m, &dd));
-		TBCHK(hipEventRecord(h->tb_ready[set], h->tb_copy_stream));
-		TBCHK(hipStreamWaitEvent(h->stream, h->tb_ready[set], 0));
-		rc = kmr_add_reads_twobit_dev(h, dtb, dto, doff, dmo, dmp, dmc, dq, quals ? 0 : uniform_quality, m, total, first_global_read_idx + r0, dd);
-		TBCHK(hipEventRecord(h->tb_consumed[set], h->stream)); h->tb_set_used[set] = true;
-		r0 = r1;
-	}
-#undef TBCHK
-	hipStreamSynchronize(h->tb_copy_stream);
-	if (!rc) rc = sync_state(h);
-	else hipStreamSynchronize(h->stream);
-	return rc;
+		if (quals) TBCHK(tb_stage_copy(h, set, 6, quals + offsets[r0], total, &dq));
+		if (discarded) TBCHK(tb_stage_copy(h, set, 7, discarded + r0, m, &dd));
+		return KMR_OK;
+	};
+	auto feed = [&](uint64_t r0, uint64_t r1) {
+		return kmr_add_reads_twobit_dev(h, dtb, dto, doff, dmo, dmp, dmc, dq, quals ? 0 : uniform_quality, r1 - r0, offsets[r1] - offsets[r0], first_global_read_idx + r0, dd);
+	};
+	return tb_feed_pieces(h, offsets, n_reads, stage, feed);
 }
 
 int kmr_finalize(kmr_handle *h, uint32_t min_depth) {
@@ -2615,9 +2662,7 @@ int kmr_finalize(kmr_handle *h, uint32_t min_depth) {
 	h->subtract = nullptr;                             /* optimize(): subtractingReference.reset() */
 	if (h->superkmer_mode) return finalize_superkmer(h, min_depth);
 	if (h->partition_mode) return finalize_partition(h, min_depth);
-#define FIN(Wv) (h->ext ? finalize_t<Wv, true>(h, min_depth) : finalize_t<Wv, false>(h, min_depth))
-	switch (h->W) { case 1: return FIN(1); case 2: return FIN(2); case 3: return FIN(3); default: return FIN(4); }
-#undef FIN
+	return with_w_ext(h, [&](auto W, auto EXT) { return finalize_t<W(), EXT()>(h, min_depth); });
 }
 
 int kmr_get_stats(kmr_handle *h, kmr_stats *out) {
@@ -2634,8 +2679,7 @@ int kmr_lookup(kmr_handle *h, const uint8_t *packed, uint64_t n, uint32_t *count
 	if (!h->finalized) return fail(h, KMR_ERR_STATE, "kmr_lookup before kmr_finalize");
 	if (n == 0) return KMR_OK;
 	hipSetDevice(h->device);
-	switch (h->W) { case 1: return lookup_t<1>(h, packed, n, counts); case 2: return lookup_t<2>(h, packed, n, counts);
-	case 3: return lookup_t<3>(h, packed, n, counts); default: return lookup_t<4>(h, packed, n, counts); }
+	return with_w(h, [&](auto W) { return lookup_t<W()>(h, packed, n, counts); });
 }
 
 /* kmr_lookup_reads and kmr_lookup_reads_weighted: one output element (u32 count or f64 weight) per k-mer position */
@@ -2652,17 +2696,9 @@ static int lookup_reads_host(kmr_handle *h, const char *bases, const uint64_t *o
 	void *dout = doutb.get(); uint64_t *doff = doffb.get<uint64_t>();
 	HIPCHK(h, hipMemsetAsync(dout, 0, eb * outN, h->stream));
 	HIPCHK(h, hipMemcpyAsync(doff, out_offsets, 8 * n_reads, hipMemcpyHostToDevice, h->stream));
-	ReadsView rv; rv.bases = sb.get<uint8_t>(); rv.quals = nullptr; rv.offsets = so.get<uint64_t>(); rv.discarded = nullptr; rv.n_reads = n_reads; rv.stream_base = 0; rv.first_read_idx = 0; rv.u_start = rv.u_end = rv.u_read = nullptr; rv.n_units = 0;
+	ReadsView rv = reads_view(sb.get(), nullptr, so.get(), n_reads);
 	rc = prepare_units(h, rv); if (rc) return rc;
-	if (weighted) {
-		double *d = (double *)dout;
-		switch (h->W) { case 1: rc = lookup_reads_weighted_t<1>(h, rv, d, doff); break; case 2: rc = lookup_reads_weighted_t<2>(h, rv, d, doff); break;
-		case 3: rc = lookup_reads_weighted_t<3>(h, rv, d, doff); break; default: rc = lookup_reads_weighted_t<4>(h, rv, d, doff); }
-	} else {
-		uint32_t *d = (uint32_t *)dout;
-		switch (h->W) { case 1: rc = lookup_reads_t<1>(h, rv, d, doff); break; case 2: rc = lookup_reads_t<2>(h, rv, d, doff); break;
-		case 3: rc = lookup_reads_t<3>(h, rv, d, doff); break; default: rc = lookup_reads_t<4>(h, rv, d, doff); }
-	}
+	rc = with_w(h, [&](auto W) { return weighted ? lookup_reads_weighted_t<W()>(h, rv, (double *)dout, doff) : lookup_reads_t<W()>(h, rv, (uint32_t *)dout, doff); });
 	if (!rc) { HIPCHK(h, hipMemcpyAsync(out, dout, eb * outN, hipMemcpyDeviceToHost, h->stream)); rc = sync_state(h); }
 	else hipStreamSynchronize(h->stream);
 	return rc;
@@ -2679,8 +2715,7 @@ int kmr_lookup_weighted(kmr_handle *h, const uint8_t *packed, uint64_t n, double
 	if (!h->finalized) return fail(h, KMR_ERR_STATE, "kmr_lookup_weighted before kmr_finalize");
 	if (n == 0) return KMR_OK;
 	hipSetDevice(h->device);
-	switch (h->W) { case 1: return lookup_t<1>(h, packed, n, nullptr, weights); case 2: return lookup_t<2>(h, packed, n, nullptr, weights);
-	case 3: return lookup_t<3>(h, packed, n, nullptr, weights); default: return lookup_t<4>(h, packed, n, nullptr, weights); }
+	return with_w(h, [&](auto W) { return lookup_t<W()>(h, packed, n, nullptr, weights); });
 }
 
 int kmr_lookup_reads_weighted(kmr_handle *h, const char *bases, const uint64_t *offsets, uint64_t n_reads, double *weights_out, const uint64_t *out_offsets) {
@@ -2739,9 +2774,7 @@ template <int W> int lookup_stream_t(kmr_handle *h, const ReadsView &rvAll, uint
 	DevParams dp = dev_params(h);
 	dp.min_weight = 0.5f; dp.subsample = 1; dp.world = 1; dp.num_parts = 1; dp.sub_wnb = 0; dp.sub_snb = 0; dp.stats = h->scratch_stats.get<DevStats>();
 	SkParams sp = sk_params(h); sp.keep_all_owners = 1; sp.track = nullptr;
-	if (W > 1 && h->sk_win == 32) rc = (!rv.quals && !h->tune.no_lean_extract) ? launch_sk_extract_lean<W, (W > 1 ? 32 : 16)>(h, rv, sp, 1.0f, &dp) : launch_sk_extract<W, (W > 1 ? 32 : 16), false>(h, rv, sp, &dp);
-	else if (!rv.quals && !h->tune.no_lean_extract) rc = h->sk_win == 16 ? launch_sk_extract_lean<W, 16>(h, rv, sp, 1.0f, &dp) : (h->sk_win == 8 ? launch_sk_extract_lean<W, 8>(h, rv, sp, 1.0f, &dp) : launch_sk_extract_lean<W, 4>(h, rv, sp, 1.0f, &dp));
-	else rc = h->sk_win == 16 ? launch_sk_extract<W, 16, false>(h, rv, sp, &dp) : (h->sk_win == 8 ? launch_sk_extract<W, 8, false>(h, rv, sp, &dp) : launch_sk_extract<W, 4, false>(h, rv, sp, &dp));
+	rc = with_win<W>(h->sk_win, [&](auto WIN) { return (!rv.quals && !h->tune.no_lean_extract) ? launch_sk_extract_lean<W, WIN()>(h, rv, sp, 1.0f, &dp) : launch_sk_extract<W, WIN(), false>(h, rv, sp, &dp); });
 	if (rc) return rc;
 	hipLaunchKernelGGL(sk_close_kernel, dim3(grid_for(nl)), dim3(256), 0, h->stream, h->sk_state.get<unsigned long long>(), nl, h->l1.chunk_count.get<uint32_t>(), h->l1.cap);
 	HIPCHK(h, hipGetLastError());
@@ -2779,8 +2812,7 @@ template <int W> int lookup_stream_t(kmr_handle *h, const ReadsView &rvAll, uint
 	return 0;
 }
 int lookup_stream(kmr_handle *h, const ReadsView &rv, uint64_t total_bases, uint32_t *position_counts, uint64_t out_n) {
-	switch (h->W) { case 1: return lookup_stream_t<1>(h, rv, total_bases, position_counts, out_n); case 2: return lookup_stream_t<2>(h, rv, total_bases, position_counts, out_n);
-	case 3: return lookup_stream_t<3>(h, rv, total_bases, position_counts, out_n); default: return lookup_stream_t<4>(h, rv, total_bases, position_counts, out_n); }
+	return with_w(h, [&](auto W) { return lookup_stream_t<W()>(h, rv, total_bases, position_counts, out_n); });
 }
 
 extern "C" {
@@ -2790,7 +2822,7 @@ struct ScoreDev { uint32_t *trim_offset, *trim_length; float *score; uint8_t *wa
 static int score_reads_core(kmr_handle *h, const uint8_t *s_b, const uint64_t *s_o, uint64_t n_reads, double minimum_kmer_score, int scoring_type,
                             uint32_t *trim_offset, uint32_t *trim_length, float *score, uint8_t *was_trimmed, ScoreDev *keep = nullptr) {
 	int rc = 0;
-	ReadsView rv; rv.bases = s_b; rv.quals = nullptr; rv.offsets = s_o; rv.discarded = nullptr; rv.n_reads = n_reads; rv.stream_base = 0; rv.first_read_idx = 0; rv.u_start = rv.u_end = rv.u_read = nullptr; rv.n_units = 0;
+	ReadsView rv = reads_view(s_b, nullptr, s_o, n_reads);
 	/* per-read k-mer counts and their exclusive scan on the device (no host pass over the reads); one grow-only block for
 	 * every temporary (freeing the ~GB count array costs more than the scoring) */
 	auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
@@ -2831,8 +2863,7 @@ static int score_reads_core(kmr_handle *h, const uint8_t *s_b, const uint64_t *s
 		dcoff = (uint64_t *)s_o;
 	} else {
 		{ int urc = prepare_units(h, rv); if (urc) return urc; }
-		switch (h->W) { case 1: rc = lookup_reads_t<1>(h, rv, dcounts, dcoff, true); break; case 2: rc = lookup_reads_t<2>(h, rv, dcounts, dcoff, true); break;
-		case 3: rc = lookup_reads_t<3>(h, rv, dcounts, dcoff, true); break; default: rc = lookup_reads_t<4>(h, rv, dcounts, dcoff, true); }
+		rc = with_w(h, [&](auto W) { return lookup_reads_t<W()>(h, rv, dcounts, dcoff, true); });
 	}
 	if (!rc) {
 		hipLaunchKernelGGL(score_reads_kernel, dim3((unsigned)std::min<uint64_t>(((n_reads + 63) / 64 + SC_WAVES - 1) / SC_WAVES, 1u << 16)), dim3(SC_WAVES * 64), 0, h->stream, s_b, s_o, n_reads, h->k, dcounts, dcoff,
@@ -2910,11 +2941,7 @@ int kmr_load_image(kmr_handle *h, int which, const void *src, uint64_t len) {
 	DevMap *m = map_of(h, which);
 	if (!m) return fail(h, KMR_ERR_UNSUPPORTED, "solid map is not built on this path");
 	hipSetDevice(h->device);
-	int rc;
-	switch (h->W) { case 1: rc = load_image_t<1>(h, *m, which == KMR_MAP_WEAK, (const uint8_t *)src, len); break;
-	case 2: rc = load_image_t<2>(h, *m, which == KMR_MAP_WEAK, (const uint8_t *)src, len); break;
-	case 3: rc = load_image_t<3>(h, *m, which == KMR_MAP_WEAK, (const uint8_t *)src, len); break;
-	default: rc = load_image_t<4>(h, *m, which == KMR_MAP_WEAK, (const uint8_t *)src, len); }
+	const int rc = with_w(h, [&](auto W) { return load_image_t<W()>(h, *m, which == KMR_MAP_WEAK, (const uint8_t *)src, len); });
 	if (rc) return rc;
 	h->slots.reset(); h->extslots.reset();
 	if (which == KMR_MAP_WEAK) { h->nb_weak = m->nb; h->stats.weak_entries = m->n; if (!h->sing.present) { h->has_singletons = false; h->sing.nb = h->nb_sing; } }
@@ -3013,9 +3040,7 @@ int kmr_merge_image(kmr_handle *h, int which, const void *src, uint64_t len) {
 	if (!m->present) return fail(h, KMR_ERR_STATE, "this map is not present in the handle (singletons purged?)");
 	hipSetDevice(h->device);
 	const bool weakMap = which == KMR_MAP_WEAK;
-	int rc;
-	switch (h->W) { case 1: rc = merge_image_t<1>(h, *m, weakMap, (const uint8_t *)src, len); break; case 2: rc = merge_image_t<2>(h, *m, weakMap, (const uint8_t *)src, len); break;
-	case 3: rc = merge_image_t<3>(h, *m, weakMap, (const uint8_t *)src, len); break; default: rc = merge_image_t<4>(h, *m, weakMap, (const uint8_t *)src, len); }
+	const int rc = with_w(h, [&](auto W) { return merge_image_t<W()>(h, *m, weakMap, (const uint8_t *)src, len); });
 	h->map_gen++;
 	if (rc) return rc;
 	if (weakMap) h->stats.weak_entries = m->n; else h->stats.singleton_entries = m->n;
@@ -3786,19 +3811,9 @@ int kmr_extract_by_owner_dev(kmr_handle *h, const void *dev_bases, const void *d
 	if (h->superkmer_mode && h->auto_mode && !h->sk_state) h->superkmer_mode = false;      /* auto: the k-mer record exchange runs on the two-level partition */
 	if (h->superkmer_mode) return fail(h, KMR_ERR_UNSUPPORTED, "k-mer records by owner are a build_mode 1 / 2 path");
 	hipSetDevice(h->device);
-	ReadsView rv; rv.bases = (const uint8_t *)dev_bases; rv.quals = (const uint8_t *)dev_quals; rv.offsets = (const uint64_t *)dev_offsets;
-	rv.discarded = (const uint8_t *)dev_discarded; rv.n_reads = n_reads; rv.stream_base = h->stream_base; rv.first_read_idx = first_global_read_idx;
-	rv.u_start = rv.u_end = rv.u_read = nullptr; rv.n_units = 0;
+	const ReadsView rv = reads_view(dev_bases, dev_quals, dev_offsets, n_reads, dev_discarded, h->stream_base, first_global_read_idx);
 	HIPCHK(h, hipMemsetAsync(dev_seg_counts, 0, 8 * h->cfg.world_size, h->stream));
-	int rc = 0;
-#define REC(Wv, E) rc = extract_by_owner_t<Wv, E>(h, rv, total_bases, dev_records, seg_capacity, dev_seg_counts);
-	switch (h->W) {
-	case 1: if (h->ext) REC(1, true) else REC(1, false) break;
-	case 2: if (h->ext) REC(2, true) else REC(2, false) break;
-	case 3: if (h->ext) REC(3, true) else REC(3, false) break;
-	default: if (h->ext) REC(4, true) else REC(4, false)
-	}
-#undef REC
+	const int rc = with_w_ext(h, [&](auto W, auto EXT) { return extract_by_owner_t<W(), EXT()>(h, rv, total_bases, dev_records, seg_capacity, dev_seg_counts); });
 	h->stream_base += total_bases; h->reads += n_reads;
 	return rc;
 }
@@ -3810,21 +3825,10 @@ int kmr_lookup_requests_dev(kmr_handle *h, const void *dev_bases, const void *de
 	if (h->cfg.world_size > (uint32_t)OWNER_MAX) return fail(h, KMR_ERR_UNSUPPORTED, "owner exchange supports up to 8 ranks per node");
 	if (total_bases >= (1ull << 32)) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_lookup_requests_dev: positions are 32-bit, pass at most 2^32 - 1 bases per call");
 	hipSetDevice(h->device);
-	ReadsView rv; rv.bases = (const uint8_t *)dev_bases; rv.quals = nullptr; rv.offsets = (const uint64_t *)dev_offsets;
-	rv.discarded = nullptr; rv.n_reads = n_reads; rv.stream_base = 0; rv.first_read_idx = 0;
-	rv.u_start = rv.u_end = rv.u_read = nullptr; rv.n_units = 0;
+	const ReadsView rv = reads_view(dev_bases, nullptr, dev_offsets, n_reads);
 	HIPCHK(h, hipMemsetAsync(dev_seg_counts, 0, 8 * h->cfg.world_size, h->stream));
 	if (n_reads == 0) return KMR_OK;
-	int rc = 0;
-#define REC(Wv, E) rc = extract_by_owner_t<Wv, E>(h, rv, total_bases, dev_keys, seg_capacity, dev_seg_counts, (uint32_t *)dev_pos);
-	switch (h->W) {
-	case 1: if (h->ext) REC(1, true) else REC(1, false) break;
-	case 2: if (h->ext) REC(2, true) else REC(2, false) break;
-	case 3: if (h->ext) REC(3, true) else REC(3, false) break;
-	default: if (h->ext) REC(4, true) else REC(4, false)
-	}
-#undef REC
-	return rc;
+	return with_w_ext(h, [&](auto W, auto EXT) { return extract_by_owner_t<W(), EXT()>(h, rv, total_bases, dev_keys, seg_capacity, dev_seg_counts, (uint32_t *)dev_pos); });
 }
 int kmr_lookup_keys_dev(kmr_handle *h, const void *dev_keys, uint64_t n, void *dev_counts) {
 	if (!h || (n && (!dev_keys || !dev_counts))) return KMR_ERR_INVALID_ARG;
@@ -3832,9 +3836,7 @@ int kmr_lookup_keys_dev(kmr_handle *h, const void *dev_keys, uint64_t n, void *d
 	if (n == 0) return KMR_OK;
 	hipSetDevice(h->device);
 	const uint32_t vw = h->ext ? 15 : 3;
-#define LK(Wv) hipLaunchKernelGGL(lookup_words_kernel<Wv>, dim3(grid_for(n)), dim3(256), 0, h->stream, view_of<Wv>(h->weak, vw), lut_of<Wv>(h), (const uint64_t *)dev_keys, n, h->hkb, (uint32_t *)dev_counts)
-	switch (h->W) { case 1: LK(1); break; case 2: LK(2); break; case 3: LK(3); break; default: LK(4); }
-#undef LK
+	with_w(h, [&](auto W) { hipLaunchKernelGGL(lookup_words_kernel<W()>, dim3(grid_for(n)), dim3(256), 0, h->stream, view_of<W()>(h->weak, vw), lut_of<W()>(h), (const uint64_t *)dev_keys, n, h->hkb, (uint32_t *)dev_counts); });
 	HIPCHK(h, hipGetLastError());
 	return KMR_OK;
 }
@@ -3844,10 +3846,8 @@ int kmr_lookup_keys_weighted_dev(kmr_handle *h, const void *dev_keys, uint64_t n
 	if (n == 0) return KMR_OK;
 	hipSetDevice(h->device);
 	const uint32_t vw = h->ext ? 15 : 3;
-#define LK(Wv) hipLaunchKernelGGL(lookup_words_weight_kernel<Wv>, dim3(grid_for(n)), dim3(256), 0, h->stream, view_of<Wv>(h->weak, vw), view_of<Wv>(h->sing, vw), lut_of<Wv>(h), \
-	                          (const uint64_t *)dev_keys, n, h->hkb, (double *)dev_weights)
-	switch (h->W) { case 1: LK(1); break; case 2: LK(2); break; case 3: LK(3); break; default: LK(4); }
-#undef LK
+	with_w(h, [&](auto W) { hipLaunchKernelGGL(lookup_words_weight_kernel<W()>, dim3(grid_for(n)), dim3(256), 0, h->stream, view_of<W()>(h->weak, vw), view_of<W()>(h->sing, vw), lut_of<W()>(h),
+	                                           (const uint64_t *)dev_keys, n, h->hkb, (double *)dev_weights); });
 	HIPCHK(h, hipGetLastError());
 	return KMR_OK;
 }
@@ -3891,14 +3891,7 @@ int kmr_insert_records_dev(kmr_handle *h, const void *dev_records, uint64_t n) {
 	if (h->partition_mode) { int prc = insert_records_partition(h, dev_records, n); h->stream_base += n; return prc; }
 	int rc = ensure_capacity(h, n); if (rc) return rc;
 	hipEvent_t a, b; time_begin(h, 0, &a, &b);
-#define INS(Wv, E) hipLaunchKernelGGL((insert_records_kernel<Wv, E>), dim3(grid_for(n)), dim3(256), 0, h->stream, table_of<Wv>(h), (const uint32_t *)dev_records, n, dev_params(h), h->stream_base)
-	switch (h->W) {
-	case 1: if (h->ext) INS(1, true); else INS(1, false); break;
-	case 2: if (h->ext) INS(2, true); else INS(2, false); break;
-	case 3: if (h->ext) INS(3, true); else INS(3, false); break;
-	default: if (h->ext) INS(4, true); else INS(4, false);
-	}
-#undef INS
+	with_w_ext(h, [&](auto W, auto EXT) { hipLaunchKernelGGL((insert_records_kernel<W(), EXT()>), dim3(grid_for(n)), dim3(256), 0, h->stream, table_of<W()>(h), (const uint32_t *)dev_records, n, dev_params(h), h->stream_base); });
 	time_end(h, 0, a, b);
 	HIPCHK(h, hipGetLastError());
 	h->stream_base += n;
@@ -3982,8 +3975,7 @@ int kmr_sk_exchange_begin(kmr_handle *h) {
 }
 static int sk_ensure_state(kmr_handle *h) {      /* a rank without reads still owns lists */
 	if (h->sk_state) return 0;
-	ReadsView rv; memset(&rv, 0, sizeof(rv));
-	return add_reads_superkmer(h, rv, 0);
+	return add_reads_superkmer(h, reads_view(nullptr, nullptr, nullptr, 0), 0);
 }
 int kmr_sk_exchange_counts(kmr_handle *h, uint64_t *chunks, uint64_t *granules) {
 	if (!h || !chunks || !granules) return KMR_ERR_INVALID_ARG;

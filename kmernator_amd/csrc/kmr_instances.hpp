@@ -1,9 +1,10 @@
 /*
- * kmr_instances.hpp -- the heavy kernel templates are compiled in translation units of their own (kmr_inst_*.hip), in
- * parallel; kmr_api.hip only sees `extern template` declarations of them.  One list, two readings:
+ * kmr_instances.hpp -- the heavy kernel templates are compiled in translation units of their own, in parallel: kmr_inst.hip,
+ * once per group and key width (build/kmr_inst_<group><w>.o); kmr_api.hip only sees `extern template` declarations of them.
+ * One list, two readings:
  *   KMR_INSTANCES_EXTERN defined   every line is an explicit instantiation DECLARATION (kmr_api.hip)
- *   otherwise                      the lines of the groups selected with KMR_INST_<GROUP> (and KMR_INST_W = key words)
- *                                  are explicit instantiation DEFINITIONS
+ *   otherwise                      the lines of the group selected with -DKMR_INST_<GROUP> (SKX, SKC, EX, PART) for the key
+ *                                  words -DKMR_INST_W are explicit instantiation DEFINITIONS (kmr_inst.hip, the Makefile's rules)
  * A kernel launched from kmr_api.hip with template arguments that are not listed here fails at link time
  * (-Wl,-z,defs in the Makefile), not at load time.
  */
