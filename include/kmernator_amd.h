@@ -289,6 +289,35 @@ int kmr_histogram(kmr_handle *h, uint32_t zoom_max, double log_base, uint64_t *v
  * count >= min_depth, both orientations.  Appends to the file at 'path'. */
 int kmr_dump_mercount(kmr_handle *h, const char *path, uint32_t min_depth);
 int kmr_dump_mergraph(kmr_handle *h, const char *path, uint32_t min_depth);
+/* The two write their file in pieces: the text of a run of entries is made on the device (kmr_dump_text), copied to the host
+ * and appended.  A piece's run is sized so that its text stays under this staging bound whatever its numbers are (kmr_tune
+ * "dump_piece_bytes" overrides it). */
+#define KMR_DUMP_PIECE_BYTES (256ull << 20)
+
+/* The same text in device memory (src/Meraculous.h:107-134: dumpCounts :107-120 writes "<k-mer>\t<count>\n" for the k-mer and
+ * for its reverse complement, dumpGraphs :121-133 "<k-mer>\t<ExtensionTracking::toTextValues>\n" = twelve tallies with a blank
+ * behind each, then "0", the reverse line with ExtensionTracking::getReverseComplement, src/KmerTrackingData.h:219-226) for
+ * the weak entries [entry_lo, entry_hi) in map order (bucket by bucket, sorted inside a bucket: the reference's iteration
+ * order) whose count passes (int)count >= (int)min_depth.  entry_hi is clamped to the weak map's entry count (UINT64_MAX = to
+ * the end); entry_lo > entry_hi after that is KMR_ERR_INVALID_ARG.  The texts of consecutive ranges that partition [0, n)
+ * concatenate to the text of the whole map: a caller streams a file larger than it wants to stage that way, and every rank of
+ * a distributed build dumps its own entries (each rank of the reference writes its own part, DistributedOfstreamMap :108, :122).
+ * KMR_ERR_STATE before kmr_finalize and for KMR_DUMP_MERGRAPH without KMR_VALUE_EXT; KMR_ERR_INVALID_ARG for a NULL handle or
+ * output pointer and for an unknown kind.  An empty map, an empty range and a range without a kept entry are valid and give
+ * 0 bytes.  Byte offsets are 64-bit: the size of a text is bounded by device memory alone. */
+enum kmr_dump_kind { KMR_DUMP_MERCOUNT = 0, KMR_DUMP_MERGRAPH = 1 };
+typedef struct kmr_text kmr_text;
+/* size only: kept entries and bytes of the text */
+int kmr_dump_text_size(kmr_handle *h, int kind, uint32_t min_depth, uint64_t entry_lo, uint64_t entry_hi,
+                       uint64_t *kept, uint64_t *bytes);
+/* the text itself, in device memory */
+int kmr_dump_text(kmr_handle *h, int kind, uint32_t min_depth, uint64_t entry_lo, uint64_t entry_hi, kmr_text **out);
+int kmr_text_info(const kmr_text *t, uint64_t *kept, uint64_t *bytes);      /* either may be NULL */
+/* the text to host memory (KMR_ERR_CAPACITY if capacity < bytes) */
+int kmr_text_copy(const kmr_text *t, char *dst, uint64_t capacity);
+/* the text where it lies (for a compressor or a device-aware MPI-IO); valid until kmr_text_free */
+int kmr_text_device_ptr(const kmr_text *t, void **dev_text);
+void kmr_text_free(kmr_text *t);
 
 /* ---- stateless helpers (bit-identical to the reference functions) -------- */
 
@@ -696,6 +725,8 @@ void *kmr_stream(kmr_handle *h);
  *   list share, the default), "saturated_batch_bytes" (scratch budget of one batch of kmr_finalize's ordered pass over k-mers seen 256
  *   times or more, 0 = 1 GiB; a key whose sightings alone exceed it is a batch of its own).
  *   "select_timing" (1: kmr_select_reads* / kmr_filter_read_batch* time their phases with HIP events, see kmr_build_info; default 0).
+ *   "dump_timing" (1: kmr_dump_text_size / kmr_dump_text time their size pass and writer with HIP events, see kmr_build_info; default 0),
+ *   "dump_piece_bytes" (staging bound of one piece of kmr_dump_mercount / kmr_dump_mergraph's file, 0 = KMR_DUMP_PIECE_BYTES; may be set at any time).
  * Call before the first kmr_add_reads* of a build.  KMR_ERR_INVALID_ARG for an unknown knob. */
 int kmr_tune(kmr_handle *h, const char *knob, double value);
 /* What the current build decided, for tests and measurement tools (the reference logs such figures, LOG_VERBOSE): "lists" = super-k-mer
@@ -707,7 +738,9 @@ int kmr_tune(kmr_handle *h, const char *knob, double value);
  * every time) and in how many batches,
  * "device_blocks_live" = blocks of device memory the library holds at this moment in the whole process (every handle, read batch
  * and artifact filter; not only h's), "filter_score_ms" / "select_ms" / "select_write_ms" = HIP-event times of the last kmr_filter_read_batch* /
- * kmr_select_reads* on this handle: its scoring, its selection with the writer, the writer alone (0 unless kmr_tune "select_timing" is set).  KMR_ERR_INVALID_ARG for an unknown name. */
+ * kmr_select_reads* on this handle: its scoring, its selection with the writer, the writer alone (0 unless kmr_tune "select_timing" is set),
+ * "dump_size_ms" / "dump_write_ms" = HIP-event times of the last kmr_dump_text_size / kmr_dump_text on this handle: its size pass with
+ * the scan, its writer (0 unless kmr_tune "dump_timing" is set).  KMR_ERR_INVALID_ARG for an unknown name. */
 int kmr_build_info(kmr_handle *h, const char *what, double *value);
 
 /* Timing of the hot path measured with HIP events on the handle's stream

@@ -191,7 +191,21 @@ public:
 	}
 	void dumpCounts(const std::string &filename, uint32_t minDepth) { check(kmr_dump_mercount(_h, filename.c_str(), minDepth), "kmr_dump_mercount"); }
 	void dumpGraphs(const std::string &filename, uint32_t minDepth) { check(kmr_dump_mergraph(_h, filename.c_str(), minDepth), "kmr_dump_mergraph"); }
+	/* the same text, made on the device, for the weak entries [lo, hi) in map order (kmr_dump_text) */
+	std::string dumpCountsText(uint32_t minDepth, uint64_t lo = 0, uint64_t hi = UINT64_MAX) { return dumpText(KMR_DUMP_MERCOUNT, minDepth, lo, hi); }
+	std::string dumpGraphsText(uint32_t minDepth, uint64_t lo = 0, uint64_t hi = UINT64_MAX) { return dumpText(KMR_DUMP_MERGRAPH, minDepth, lo, hi); }
 
+	std::string dumpText(int kind, uint32_t minDepth, uint64_t lo, uint64_t hi) {
+		kmr_text *t = nullptr;
+		check(kmr_dump_text(_h, kind, minDepth, lo, hi, &t), "kmr_dump_text");
+		std::unique_ptr<kmr_text, void (*)(kmr_text *)> tx(t, kmr_text_free);
+		uint64_t bytes = 0;
+		kmr_text_info(t, nullptr, &bytes);
+		std::string out(bytes, '\0');
+		const int rc = kmr_text_copy(t, bytes ? &out[0] : nullptr, bytes);
+		if (rc != KMR_OK) throw KmerSpectrumError(rc, "kmr_text_copy");
+		return out;
+	}
 	void check(int rc, const char *what) const { if (rc != KMR_OK) throw KmerSpectrumError(rc, std::string(what) + ": " + kmr_last_error(_h)); }
 private:
 	static void write(const std::string &f, const std::vector<uint8_t> &b) { std::ofstream o(f, std::ios::binary); o.write((const char *)b.data(), (std::streamsize)b.size()); if (!o) throw KmerSpectrumError(KMR_ERR_INVALID_ARG, "cannot write " + f); }

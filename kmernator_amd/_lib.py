@@ -82,6 +82,7 @@ EXPORTS = [
     "kmr_lookup_weighted", "kmr_lookup_reads_weighted", "kmr_lookup_keys_weighted_dev",
     "kmr_select_config_init", "kmr_select_reads", "kmr_select_reads_dev", "kmr_filter_read_batch", "kmr_filter_read_batch_dev",
     "kmr_picks_info", "kmr_picks_copy", "kmr_picks_device_ptr", "kmr_picks_free",
+    "kmr_dump_text_size", "kmr_dump_text", "kmr_text_info", "kmr_text_copy", "kmr_text_device_ptr", "kmr_text_free",
     "kmr_map_digest", "kmr_synth_reads_dev", "kmr_build_info", "kmr_sk_exchange_uniform", "kmr_sk_exchange_peer_uniform", "kmr_sk_exchange_range", "kmr_count_lists_prefix",
 ]
 
@@ -206,6 +207,13 @@ def load():
     lib.kmr_picks_device_ptr.argtypes = [vp, C.POINTER(vp)]
     lib.kmr_picks_free.argtypes = [vp]
     lib.kmr_picks_free.restype = None
+    lib.kmr_dump_text_size.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint64, C.c_uint64, u64p, u64p]
+    lib.kmr_dump_text.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(vp)]
+    lib.kmr_text_info.argtypes = [vp, u64p, u64p]
+    lib.kmr_text_copy.argtypes = [vp, vp, C.c_uint64]
+    lib.kmr_text_device_ptr.argtypes = [vp, C.POINTER(vp)]
+    lib.kmr_text_free.argtypes = [vp]
+    lib.kmr_text_free.restype = None
     _lib = lib
     return lib
 

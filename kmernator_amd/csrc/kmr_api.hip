@@ -34,6 +34,7 @@
 #include "kmr_ingest.hpp"
 #include "kmr_artifact.hpp"
 #include "kmr_select.hpp"
+#include "kmr_dump.hpp"
 #include "kmr_superkmer.hpp"
 #include "kmr_buckets.hpp"
 #include "kmr_synth.hpp"
@@ -187,6 +188,8 @@ struct Tuning {
 	bool no_uniform_count = false;     /* never take sk_count_kernel<.., UNI> (A/B runs, tests of the general count pass on one-weight builds) */
 	bool no_lean_extract = false;      /* never take sk_extract_lean_kernel (A/B runs, tests of the general kernel on uniform qualities) */
 	bool exchange_fail_once = false;   /* tests: the next kmr_exchange_add_reads_dev of this rank fails locally (the other ranks must come back with an error, not hang) */
+	uint64_t dump_piece_bytes = 0;     /* kmr_dump_mercount / kmr_dump_mergraph: staging bound of one piece of the file (0 = KMR_DUMP_PIECE_BYTES) */
+	bool dump_timing = false;          /* kmr_dump_text*: time the size pass and the writer with HIP events (kmr_build_info; measurement tools) */
 	bool select_timing = false;        /* kmr_select_* / kmr_filter_*: time scoring, selection and writer with HIP events (kmr_build_info; measurement tools) */
 	bool no_coarse_lists = true;       /* exchange: scatter into the job's fine lists (default) or, kmr_tune("coarse_lists", 1), into coarse ones that the owner splits before the count pass (sk_refine_kernel: not yet fast enough to pay) */
 };
@@ -242,6 +245,7 @@ struct kmr_handle : HandleMem, BuildMem, ExchangeMem {
 	uint64_t last_early_hi = 0, last_early_entries = 0;      /* what the last kmr_finalize took over from an early count (kmr_build_info) */
 	bool last_early_overflowed = false;                       /* ... or that it voided one because its buffers overflowed */
 	double last_score_ms = 0, last_select_ms = 0, last_write_ms = 0;      /* the last kmr_filter_read_batch* / kmr_select_reads*: scoring, selection + writer, writer alone (HIP events, taken with kmr_tune "select_timing" only; kmr_build_info) */
+	double last_dump_size_ms = 0, last_dump_write_ms = 0;      /* the last kmr_dump_text_size / kmr_dump_text: size pass with its scan, writer (HIP events, taken with kmr_tune "dump_timing" only; kmr_build_info) */
 	uint64_t last_saturated_keys = 0, last_saturated_batches = 0;      /* what the last kmr_finalize's saturated-key pass redid, in how many batches */
 	bool qual_mixed = false;           /* a build that has seen two different quality characters stops asking (qrange) */
 	/* exchange with world_size > 1: sk_bits are the COARSE lists reads are scattered into and that travel; each holds 2^sk_fine_shift
@@ -264,6 +268,13 @@ struct kmr_picks {
 	int device = 0;
 	DevBuf text, picked;
 	uint64_t n = 0, n_picked = 0, bytes = 0;
+};
+
+/* what kmr_dump_text leaves on the device: the mercount / mergraph text of a range of weak entries */
+struct kmr_text {
+	int device = 0;
+	DevBuf text;
+	uint64_t kept = 0, bytes = 0;
 };
 
 /* device-resident read batch produced by kmr_ingest_fastq* */
@@ -2419,6 +2430,8 @@ int kmr_tune(kmr_handle *h, const char *knob, double value) {
 	else if (k == "binned_buckets_min") h->tune.binned_min = value >= 0 ? (uint64_t)value : ~0ull;        /* < 0: never */
 	else if (k == "coarse_lists") h->tune.no_coarse_lists = value == 0;
 	else if (k == "select_timing") h->tune.select_timing = value != 0;
+	else if (k == "dump_timing") h->tune.dump_timing = value != 0;
+	else if (k == "dump_piece_bytes") h->tune.dump_piece_bytes = value >= 1 ? (uint64_t)value : 0;
 	else if (k == "narrow_tallies") h->tune.no_narrow = value == 0;
 	else if (k == "keep_level1_state") h->tune.no_l1_state = value == 0;
 	else if (k == "superkmer_window") {      /* largest minimizer window the geometry may take (32 / 16 / 8 / 4): A/B runs, tests of the narrower windows at large k */
@@ -2447,6 +2460,8 @@ int kmr_build_info(kmr_handle *h, const char *what, double *value) {
 	else if (k == "filter_score_ms") *value = h->last_score_ms;
 	else if (k == "select_ms") *value = h->last_select_ms;
 	else if (k == "select_write_ms") *value = h->last_write_ms;
+	else if (k == "dump_size_ms") *value = h->last_dump_size_ms;
+	else if (k == "dump_write_ms") *value = h->last_dump_write_ms;
 	else return fail(h, KMR_ERR_INVALID_ARG, "unknown build figure '" + k + "'");
 	return KMR_OK;
 }
@@ -3077,44 +3092,6 @@ int kmr_histogram(kmr_handle *h, uint32_t zoom_max, double log_base, uint64_t *v
 	return KMR_OK;
 }
 
-/* text dumps (src/Meraculous.h:107-134): formatting is host work on the downloaded weak map */
-static int dump_text(kmr_handle *h, const char *path, uint32_t min_depth, bool graph) {
-	if (!h || !path) return KMR_ERR_INVALID_ARG;
-	if (!h->finalized) return fail(h, KMR_ERR_STATE, "dump before kmr_finalize");
-	if (graph && !h->ext) return fail(h, KMR_ERR_STATE, "mergraph needs value_kind = KMR_VALUE_EXT");
-	hipSetDevice(h->device);
-	const uint32_t vw = h->ext ? 15 : 3, W = h->W, k = h->k;
-	const uint64_t n = h->weak.n;
-	std::vector<uint64_t> keys(n * W); std::vector<uint32_t> vals(n * vw);
-	if (n) { HIPCHK(h, hipMemcpy(keys.data(), h->weak.keys.get<uint64_t>(), 8 * n * W, hipMemcpyDeviceToHost)); HIPCHK(h, hipMemcpy(vals.data(), h->weak.vals.get<uint32_t>(), 4 * n * vw, hipMemcpyDeviceToHost)); }
-	FILE *f = fopen(path, "a");
-	if (!f) return fail(h, KMR_ERR_INVALID_ARG, std::string("cannot open ") + path);
-	std::string fa(k, 'A'), rfa(k, 'A');
-	static const char dec[] = "ACGT";
-	static const int rcIdx[6] = {3, 2, 1, 0, 4, 5};
-	for (uint64_t e = 0; e < n; e++) {
-		const uint32_t *v = &vals[e * vw];
-		const uint32_t count = v[0] & 0xffff;
-		if ((int)count < (int)min_depth) continue;
-		for (uint32_t p = 0; p < k; p++) {
-			const uint32_t code = (uint32_t)(keys[e * W + (p >> 5)] >> (62 - 2 * (p & 31))) & 3;
-			fa[p] = dec[code]; rfa[k - 1 - p] = dec[3 - code];
-		}
-		if (!graph) fprintf(f, "%s\t%u\n%s\t%u\n", fa.c_str(), count, rfa.c_str(), count);
-		else {
-			const uint32_t *t = v + 3;
-			fprintf(f, "%s\t%u %u %u %u %u %u %u %u %u %u %u %u 0\n", fa.c_str(), t[0], t[1], t[2], t[3], t[4], t[5], t[6], t[7], t[8], t[9], t[10], t[11]);
-			uint32_t r[12];   /* ExtensionTracking::getReverseComplement, src/KmerTrackingData.h:219-226 */
-			for (int i = 0; i < 6; i++) { r[rcIdx[i]] = t[6 + i]; r[6 + rcIdx[i]] = t[i]; }
-			fprintf(f, "%s\t%u %u %u %u %u %u %u %u %u %u %u %u 0\n", rfa.c_str(), r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7], r[8], r[9], r[10], r[11]);
-		}
-	}
-	fclose(f);
-	return KMR_OK;
-}
-int kmr_dump_mercount(kmr_handle *h, const char *path, uint32_t min_depth) { return dump_text(h, path, min_depth, false); }
-int kmr_dump_mergraph(kmr_handle *h, const char *path, uint32_t min_depth) { return dump_text(h, path, min_depth, true); }
-
 /* ---- f2: FASTQ ingest on the device (kmr_ingest.hpp) ------------------------ */
 static int ingest_dev(kmr_handle *h, const uint8_t *text, uint64_t len, uint32_t input_base, int store_comment, kmr_reads **out) {
 	const uint32_t start = h->cfg.fastq_start_char;
@@ -3678,6 +3655,116 @@ void kmr_picks_free(kmr_picks *p) {
 	hipSetDevice(p->device);
 	delete p;      /* (its buffers are freed on this device) */
 }
+
+/* ---- a14: the mercount / mergraph text on the device (kmr_dump.hpp) ---------- */
+/* The common part of kmr_dump_text_size and kmr_dump_text: argument checks, the size pass over weak entries [lo, hi) and, when `out`
+ * is given, the writer. */
+static int dump_core(kmr_handle *h, int kind, uint32_t min_depth, uint64_t lo, uint64_t hi, uint64_t *kept, uint64_t *bytes, kmr_text **out) {
+	if (out) *out = nullptr;
+	if (!h) return KMR_ERR_INVALID_ARG;
+	if (kind != KMR_DUMP_MERCOUNT && kind != KMR_DUMP_MERGRAPH) return fail(h, KMR_ERR_INVALID_ARG, "unknown kmr_dump_kind");
+	if (!h->finalized) return fail(h, KMR_ERR_STATE, "dump before kmr_finalize");
+	const bool graph = kind == KMR_DUMP_MERGRAPH;
+	if (graph && !h->ext) return fail(h, KMR_ERR_STATE, "mergraph needs value_kind = KMR_VALUE_EXT");
+	const uint64_t n_map = h->weak.present ? h->weak.n : 0;
+	if (hi > n_map) hi = n_map;
+	if (lo > hi) return fail(h, KMR_ERR_INVALID_ARG, "dump: entry_lo lies behind entry_hi (entry_hi is clamped to the weak map's entries)");
+	hipSetDevice(h->device);
+	std::unique_ptr<kmr_text, void (*)(kmr_text *)> tx(new kmr_text, kmr_text_free);
+	tx->device = h->device;
+	h->last_dump_size_ms = h->last_dump_write_ms = 0;
+	const uint64_t n = hi - lo;
+	if (n) {
+		DumpParams P;
+		P.keys = h->weak.keys.get<uint64_t>(); P.vals = h->weak.vals.get<uint32_t>(); P.vw = h->ext ? 15u : 3u; P.k = h->k; P.graph = graph ? 1u : 0u;
+		P.min_depth = (int32_t)min_depth; P.lo = lo; P.n = n;
+		DevBuf b_len, b_off; uint32_t *len; uint64_t *off;      /* off[n] = bytes, off[n + 1] = kept entries */
+		HIPCHK(h, alloc_n(b_len, &len, n)); HIPCHK(h, alloc_n(b_off, &off, n + 2));
+		SelectTimer timer(h->tune.dump_timing);
+		timer.mark(0, h->stream);
+		HIPCHK(h, hipMemsetAsync(off + n + 1, 0, 8, h->stream));
+		hipLaunchKernelGGL(dump_size_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, P, len, (unsigned long long *)(off + n + 1));
+		HIPCHK(h, hipGetLastError());
+		int rc = exclusive_scan(h, len, n, off); if (rc) return rc;
+		uint64_t totals[2] = {0, 0};
+		HIPCHK(h, hipMemcpyAsync(totals, off + n, 16, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));      /* the one copy that brings sizes back */
+		tx->bytes = totals[0]; tx->kept = totals[1];
+		if (out && tx->bytes) HIPCHK(h, tx->text.alloc((tx->bytes + 15) & ~(uint64_t)15));
+		timer.mark(1, h->stream);      /* (behind the allocation: the events then bracket the writer alone) */
+		if (out && tx->bytes) {
+			const uint64_t tiles = (tx->bytes + DUMP_TILE - 1) / DUMP_TILE;
+			const uint64_t per_block = (tiles + (uint64_t)num_cus(h) * 16 - 1) / ((uint64_t)num_cus(h) * 16);
+			const unsigned blocks = (unsigned)((tiles + per_block - 1) / per_block);
+			uint8_t *dout = tx->text.get<uint8_t>();
+			with_w(h, [&](auto W) { hipLaunchKernelGGL(dump_write_kernel<W()>, dim3(blocks), dim3(DUMP_THREADS), 0, h->stream, P, (const uint64_t *)off, tx->bytes, per_block, dout); return 0; });
+			HIPCHK(h, hipGetLastError());
+		}
+		timer.mark(2, h->stream);
+		HIPCHK(h, hipStreamSynchronize(h->stream));
+		h->last_dump_size_ms = timer.ms(0, 1); h->last_dump_write_ms = timer.ms(1, 2);
+	}
+	if (kept) *kept = tx->kept;
+	if (bytes) *bytes = tx->bytes;
+	if (out) *out = tx.release();
+	return KMR_OK;
+}
+
+int kmr_dump_text_size(kmr_handle *h, int kind, uint32_t min_depth, uint64_t entry_lo, uint64_t entry_hi, uint64_t *kept, uint64_t *bytes) {
+	if (!h || !kept || !bytes) return KMR_ERR_INVALID_ARG;
+	return dump_core(h, kind, min_depth, entry_lo, entry_hi, kept, bytes, nullptr);
+}
+int kmr_dump_text(kmr_handle *h, int kind, uint32_t min_depth, uint64_t entry_lo, uint64_t entry_hi, kmr_text **out) {
+	if (!h || !out) { if (out) *out = nullptr; return KMR_ERR_INVALID_ARG; }
+	return dump_core(h, kind, min_depth, entry_lo, entry_hi, nullptr, nullptr, out);
+}
+int kmr_text_info(const kmr_text *t, uint64_t *kept, uint64_t *bytes) {
+	if (!t) return KMR_ERR_INVALID_ARG;
+	if (kept) *kept = t->kept; if (bytes) *bytes = t->bytes;
+	return KMR_OK;
+}
+int kmr_text_copy(const kmr_text *t, char *dst, uint64_t capacity) {
+	if (!t || (t->bytes && !dst)) return KMR_ERR_INVALID_ARG;
+	if (capacity < t->bytes) return KMR_ERR_CAPACITY;
+	hipSetDevice(t->device);
+	return !t->bytes || hipMemcpy(dst, t->text.get<uint8_t>(), t->bytes, hipMemcpyDeviceToHost) == hipSuccess ? KMR_OK : KMR_ERR_HIP;
+}
+int kmr_text_device_ptr(const kmr_text *t, void **dev_text) {
+	if (!t || !dev_text) return KMR_ERR_INVALID_ARG;
+	*dev_text = t->text.get<uint8_t>();
+	return KMR_OK;
+}
+void kmr_text_free(kmr_text *t) {
+	if (!t) return;
+	hipSetDevice(t->device);
+	delete t;      /* (its buffer is freed on this device) */
+}
+
+/* The file-appending forms: the text in pieces of entries whose text stays under the staging bound whatever their numbers are (a
+ * count has at most 5 digits, a tally at most 10), each copied to the host and appended. */
+static int dump_file(kmr_handle *h, const char *path, uint32_t min_depth, bool graph) {
+	if (!h || !path) return KMR_ERR_INVALID_ARG;
+	if (!h->finalized) return fail(h, KMR_ERR_STATE, "dump before kmr_finalize");
+	if (graph && !h->ext) return fail(h, KMR_ERR_STATE, "mergraph needs value_kind = KMR_VALUE_EXT");
+	const uint64_t n = h->weak.present ? h->weak.n : 0;
+	const uint64_t bound = h->tune.dump_piece_bytes ? h->tune.dump_piece_bytes : (uint64_t)KMR_DUMP_PIECE_BYTES;
+	const uint64_t entry_max = graph ? 2ull * (h->k + 15 + 12 * 10) : 2ull * (h->k + 2 + 5);
+	const uint64_t step = std::max<uint64_t>(1, bound / entry_max);
+	std::unique_ptr<FILE, int (*)(FILE *)> f(fopen(path, "a"), fclose);
+	if (!f) return fail(h, KMR_ERR_INVALID_ARG, std::string("cannot open ") + path);
+	std::vector<char> stage;
+	for (uint64_t lo = 0; lo < n; lo += step) {
+		kmr_text *t = nullptr;
+		int rc = dump_core(h, graph ? KMR_DUMP_MERGRAPH : KMR_DUMP_MERCOUNT, min_depth, lo, std::min(n, lo + step), nullptr, nullptr, &t); if (rc) return rc;
+		std::unique_ptr<kmr_text, void (*)(kmr_text *)> tx(t, kmr_text_free);
+		if (!tx->bytes) continue;
+		if (stage.size() < tx->bytes) stage.resize(tx->bytes);
+		HIPCHK(h, hipMemcpy(stage.data(), tx->text.get<uint8_t>(), tx->bytes, hipMemcpyDeviceToHost));
+		if (fwrite(stage.data(), 1, tx->bytes, f.get()) != tx->bytes) return fail(h, KMR_ERR_INVALID_ARG, std::string("cannot write ") + path);
+	}
+	return KMR_OK;
+}
+int kmr_dump_mercount(kmr_handle *h, const char *path, uint32_t min_depth) { return dump_file(h, path, min_depth, false); }
+int kmr_dump_mergraph(kmr_handle *h, const char *path, uint32_t min_depth) { return dump_file(h, path, min_depth, true); }
 
 /* ---- f2: the batch as 2-bit packed reads + markups -------------------------- */
 int kmr_reads_twobit(kmr_handle *h, const kmr_reads *r, uint8_t *twobit, uint64_t twobit_capacity, uint64_t *twobit_offsets,

@@ -454,6 +454,27 @@ class KmerSpectrum:
     def dumpGraphs(self, filename, min_depth):
         self._call("dump_mergraph", self.h, filename.encode(), min_depth)
 
+    DUMP_KIND = {"mercount": 0, "mergraph": 1}
+
+    def dumpTextSize(self, kind, min_depth, lo=0, hi=None):
+        """(kept entries, bytes) of the text kmr_dump_text would make for the weak entries [lo, hi) (kmr_dump_text_size); kind: "mercount" / "mergraph" or 0 / 1"""
+        kept, nbytes = C.c_uint64(), C.c_uint64()
+        self._call("dump_text_size", self.h, self.DUMP_KIND.get(kind, kind), min_depth, lo, _U64_MAX if hi is None else hi, C.byref(kept), C.byref(nbytes))
+        return kept.value, nbytes.value
+
+    def _dump_text(self, kind, min_depth, lo, hi):
+        out = C.c_void_p()
+        self._call("dump_text", self.h, kind, min_depth, lo, _U64_MAX if hi is None else hi, C.byref(out))
+        return DumpText(self, out)
+
+    def dumpCountsText(self, min_depth, lo=0, hi=None):
+        """dumpCounts' text (src/Meraculous.h:107-120) for the weak entries [lo, hi) in map order, left in device memory: a DumpText"""
+        return self._dump_text(0, min_depth, lo, hi)
+
+    def dumpGraphsText(self, min_depth, lo=0, hi=None):
+        """dumpGraphs' text (src/Meraculous.h:121-133) likewise; needs KMR_VALUE_EXT"""
+        return self._dump_text(1, min_depth, lo, hi)
+
     def kernel_time(self, which=0):
         ms, n = C.c_double(), C.c_uint64()
         self._call("kernel_time", self.h, which, C.byref(ms), C.byref(n))
@@ -461,6 +482,62 @@ class KmerSpectrum:
 
     def kernel_time_reset(self):
         self._call("kernel_time_reset", self.h)
+
+
+_U64_MAX = (1 << 64) - 1
+
+
+class DumpText:
+    """A mercount / mergraph text in device memory (kmr_text): .kept entries, .bytes; numpy() copies it to the host,
+    device_tensor() is a torch uint8 view of it where it lies, valid until close()."""
+
+    def __init__(self, sp, handle):
+        self.sp, self._t = sp, handle
+        kept, nbytes = C.c_uint64(), C.c_uint64()
+        sp._call("text_info", handle, C.byref(kept), C.byref(nbytes))
+        self.kept, self.bytes = kept.value, nbytes.value
+
+    def _live(self):
+        if not self._t:
+            raise KmerSpectrumError("DumpText: closed")
+        return self._t
+
+    def numpy(self):
+        buf = np.zeros(self.bytes, dtype=np.uint8)
+        rc = self.sp.lib.kmr_text_copy(self._live(), buf.ctypes.data_as(C.c_void_p) if self.bytes else None, self.bytes)
+        if rc != 0:
+            raise KmerSpectrumError("kmr_text_copy: %s" % _lib.STATUS.get(rc, rc))
+        return buf
+
+    def device_ptr(self):
+        p = C.c_void_p()
+        self.sp._call("text_device_ptr", self._live(), C.byref(p))
+        return p.value or 0
+
+    def device_tensor(self):
+        import torch
+        ptr = self.device_ptr()
+        if not self.bytes:
+            return torch.empty(0, dtype=torch.uint8, device="cuda")
+        view = type("_DeviceBytes", (), {"__cuda_array_interface__": {"shape": (self.bytes,), "typestr": "|u1", "data": (ptr, False), "version": 2, "strides": None}})()
+        return torch.as_tensor(view, device="cuda")
+
+    def close(self):
+        if getattr(self, "_t", None):
+            self.sp.lib.kmr_text_free(self._t)
+            self._t = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Histogram:
