@@ -702,6 +702,52 @@ int kmr_picks_copy(const kmr_picks *p, char *dst, uint64_t capacity, uint8_t *pi
 int kmr_picks_device_ptr(const kmr_picks *p, void **dev_text);
 void kmr_picks_free(kmr_picks *p);
 
+/* ---- ReadSet::identifyPairs: which reads of a batch are the two ends of one fragment, on the device ----------
+ * One call equals one ReadSet::identifyPairs() (src/ReadSet.cpp:446-570) on a fresh ReadSet that holds the batch's reads in
+ * batch order: no earlier pairs, previousReadName empty.  apps/FilterReads.cpp:103 and importAndProcessReadset of FilterReads-P
+ * call it after the input is read; the artifact filter, isPassingPair and ReadSet::hasPairs (which chooses between
+ * pickAllPassingPairs and pickAllPassingReads) use what it finds.
+ *   name        a read's name and comment are what trimName (src/Utils.h:561-598) makes of its name span (name_off / name_len of
+ *               kmr_reads_copy) in `text`, the FASTQ text the batch was ingested from: the name runs to the first blank, tab, CR
+ *               or LF, the comment is the rest if at least one character follows the separator.  With store_comment == 0 a
+ *               Casava-1.8 comment (isCommentCasava18, :678-685) on a name that does not already end in "/x" rewrites the name
+ *               to name/1 or name/2 and the read keeps no comment; with store_comment != 0 the comment is kept and the name is
+ *               not rewritten.  Pass the value the batch was ingested with
+ *   readNum     (:689-713) 1 or 2 from a Casava comment if there is one, else from a trailing /1 /A /F -> 1 or /2 /B /R -> 2, else 0
+ *   commonName  (:669-676) the name without its last character if it is longer than 2 and its second-to-last character is '/'
+ *   phase 1     sequential pairs (:467-478 over _isSequentialPair, :94-118): the reads in order with one pending read; a read
+ *               with readNum 0 clears it, a read that isPair()s with it (:719-733: same common name, different non-zero read
+ *               numbers) forms Pair(i - 1, i) and clears it, any other read becomes the pending one.  The earlier index is read1
+ *   phase 2     by name (:500-565) over the reads phase 1 left unpaired, in index order, with a map from common name to pair:
+ *               without an entry the read pushes a half pair (read2 if readNum == 2, else read1) and enters the map if
+ *               readNum > 0; with an entry it fills the free side (readNum == 2 -> read2, anything else, 0 included, -> read1)
+ *               and the entry is erased, or, if that side is taken, the entry is erased and the read pushes a half pair of its
+ *               own that is not entered (the two warning branches, :522-543: n_conflicts)
+ *   result      mate[i] = the read paired with i or -1 (the convention of kmr_artifact_filter_apply and kmr_select_reads);
+ *               the pair list (read1, read2) with -1 for MAX_READ_IDX in the reference's order: phase-1 pairs ascending, then
+ *               the phase-2 records in the order of the reads that pushed them.  n_pairs = getPairSize(), n_full = pairs with
+ *               both reads, n_sequential = phase-1 pairs, has_pairs = hasPairs(): 0 < n_pairs < n_reads (src/ReadSet.h:526-529)
+ * Names are matched through a 64-bit hash of the common name and then byte for byte, so a hash collision does not change the
+ * result (kmr_tune "pair_hash_bits", kmr_build_info "pair_hash_collisions").  Nothing per read crosses the bus inside the call.
+ * A batch without names (kmr_reads_from_host, kmr_reads_from_twobit: text_len 0) is valid: every read is a half pair of its
+ * own and has_pairs is 0.  An empty batch is valid.  A name span outside the text is KMR_ERR_INVALID_ARG.
+ * Not covered: a second identifyPairs() on a set that already has pairs (the reference stores a read index where a pair
+ * index is read back, :492-495 against :520, which coincides only by accident); the per-file identifyPairs and re-ordering
+ * of appendAllFiles (:216-239) -- one call over the concatenated batch gives the same pairs for an R1 file followed by an R2
+ * file; printing name/1 for rewritten Casava names in writePicks (see above).
+ * Bounds: a batch holds fewer than 2^32 - 1 reads (KMR_ERR_UNSUPPORTED beyond). */
+typedef struct kmr_pairs kmr_pairs;
+int kmr_identify_pairs(kmr_handle *h, const kmr_reads *reads, const char *text, uint64_t text_len, int store_comment, kmr_pairs **out);
+/* the same with the FASTQ text already in device memory */
+int kmr_identify_pairs_dev(kmr_handle *h, const kmr_reads *reads, const void *dev_text, uint64_t text_len, int store_comment, kmr_pairs **out);
+/* any pointer may be NULL */
+int kmr_pairs_info(const kmr_pairs *p, uint64_t *n_reads, uint64_t *n_pairs, uint64_t *n_full, uint64_t *n_sequential, uint64_t *n_conflicts, int *has_pairs);
+/* to host memory: mate[n_reads], read1[n_pairs], read2[n_pairs]; any may be NULL */
+int kmr_pairs_copy(const kmr_pairs *p, int64_t *mate, int64_t *read1, int64_t *read2);
+/* the three arrays (int64) where they lie; any may be NULL; valid until kmr_pairs_free */
+int kmr_pairs_device_ptrs(const kmr_pairs *p, void **dev_mate, void **dev_read1, void **dev_read2);
+void kmr_pairs_free(kmr_pairs *p);
+
 /* Raw HIP stream of the handle (hipStream_t) so callers can order their own
  * work (torch.cuda.ExternalStream) against it. */
 void *kmr_stream(kmr_handle *h);
@@ -727,6 +773,9 @@ void *kmr_stream(kmr_handle *h);
  *   "select_timing" (1: kmr_select_reads* / kmr_filter_read_batch* time their phases with HIP events, see kmr_build_info; default 0).
  *   "dump_timing" (1: kmr_dump_text_size / kmr_dump_text time their size pass and writer with HIP events, see kmr_build_info; default 0),
  *   "dump_piece_bytes" (staging bound of one piece of kmr_dump_mercount / kmr_dump_mergraph's file, 0 = KMR_DUMP_PIECE_BYTES; may be set at any time).
+ *   "pair_hash_bits" (bits of the common name's hash that kmr_identify_pairs* sorts by, 1 - 64, default 64: with a few bits distinct names
+ *   share a key, which tests use to reach the byte-for-byte grouping), "pairs_timing" (1: kmr_identify_pairs* times its phases with HIP
+ *   events, see kmr_build_info; default 0); both may be set at any time.
  * Call before the first kmr_add_reads* of a build.  KMR_ERR_INVALID_ARG for an unknown knob. */
 int kmr_tune(kmr_handle *h, const char *knob, double value);
 /* What the current build decided, for tests and measurement tools (the reference logs such figures, LOG_VERBOSE): "lists" = super-k-mer
@@ -740,7 +789,10 @@ int kmr_tune(kmr_handle *h, const char *knob, double value);
  * and artifact filter; not only h's), "filter_score_ms" / "select_ms" / "select_write_ms" = HIP-event times of the last kmr_filter_read_batch* /
  * kmr_select_reads* on this handle: its scoring, its selection with the writer, the writer alone (0 unless kmr_tune "select_timing" is set),
  * "dump_size_ms" / "dump_write_ms" = HIP-event times of the last kmr_dump_text_size / kmr_dump_text on this handle: its size pass with
- * the scan, its writer (0 unless kmr_tune "dump_timing" is set).  KMR_ERR_INVALID_ARG for an unknown name. */
+ * the scan, its writer (0 unless kmr_tune "dump_timing" is set), "pairs_ms" / "pairs_parse_ms" / "pairs_sort_ms" = HIP-event times of the
+ * last kmr_identify_pairs* on this handle: the whole call, its name parse, its radix sort (0 unless kmr_tune "pairs_timing" is set),
+ * "pair_hash_collisions" = runs of equal sort keys of that call that held more than one distinct common name.
+ * KMR_ERR_INVALID_ARG for an unknown name. */
 int kmr_build_info(kmr_handle *h, const char *what, double *value);
 
 /* Timing of the hot path measured with HIP events on the handle's stream

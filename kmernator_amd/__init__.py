@@ -6,7 +6,7 @@ KmerSpectrum interface plus the one-process-per-GPU owner-partitioned driver.
 """
 from ._lib import (KMR_MAP_SINGLETON, KMR_MAP_WEAK, KMR_VALUE_COUNT_DIR, KMR_VALUE_EXT, KmrConfig, KmrSelectConfig, default_config, load,
                    record_bytes)
-from .spectrum import DumpText, FilterKnownOddities, KmerSpectrum, KmerSpectrumError, Histogram, ReadSelector, ReadSet, synth_reads_device
+from .spectrum import DumpText, FilterKnownOddities, KmerSpectrum, KmerSpectrumError, Histogram, ReadPairs, ReadSelector, ReadSet, synth_reads_device
 
-__all__ = ["KmerSpectrum", "DumpText", "KmerSpectrumError", "ReadSet", "Histogram", "FilterKnownOddities", "ReadSelector", "synth_reads_device", "KmrConfig", "KmrSelectConfig", "default_config", "load", "record_bytes",
+__all__ = ["KmerSpectrum", "DumpText", "KmerSpectrumError", "ReadSet", "ReadPairs", "Histogram", "FilterKnownOddities", "ReadSelector", "synth_reads_device", "KmrConfig", "KmrSelectConfig", "default_config", "load", "record_bytes",
            "KMR_MAP_WEAK", "KMR_MAP_SINGLETON", "KMR_VALUE_COUNT_DIR", "KMR_VALUE_EXT"]

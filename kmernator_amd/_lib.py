@@ -83,6 +83,7 @@ EXPORTS = [
     "kmr_select_config_init", "kmr_select_reads", "kmr_select_reads_dev", "kmr_filter_read_batch", "kmr_filter_read_batch_dev",
     "kmr_picks_info", "kmr_picks_copy", "kmr_picks_device_ptr", "kmr_picks_free",
     "kmr_dump_text_size", "kmr_dump_text", "kmr_text_info", "kmr_text_copy", "kmr_text_device_ptr", "kmr_text_free",
+    "kmr_identify_pairs", "kmr_identify_pairs_dev", "kmr_pairs_info", "kmr_pairs_copy", "kmr_pairs_device_ptrs", "kmr_pairs_free",
     "kmr_map_digest", "kmr_synth_reads_dev", "kmr_build_info", "kmr_sk_exchange_uniform", "kmr_sk_exchange_peer_uniform", "kmr_sk_exchange_range", "kmr_count_lists_prefix",
 ]
 
@@ -214,6 +215,13 @@ def load():
     lib.kmr_text_device_ptr.argtypes = [vp, C.POINTER(vp)]
     lib.kmr_text_free.argtypes = [vp]
     lib.kmr_text_free.restype = None
+    for name in ("kmr_identify_pairs", "kmr_identify_pairs_dev"):
+        getattr(lib, name).argtypes = [vp, vp, vp, C.c_uint64, C.c_int, C.POINTER(vp)]
+    lib.kmr_pairs_info.argtypes = [vp, u64p, u64p, u64p, u64p, u64p, C.POINTER(C.c_int)]
+    lib.kmr_pairs_copy.argtypes = [vp, i64p, i64p, i64p]
+    lib.kmr_pairs_device_ptrs.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    lib.kmr_pairs_free.argtypes = [vp]
+    lib.kmr_pairs_free.restype = None
     _lib = lib
     return lib
 

@@ -34,6 +34,7 @@
 #include "kmr_ingest.hpp"
 #include "kmr_artifact.hpp"
 #include "kmr_select.hpp"
+#include "kmr_pairs.hpp"
 #include "kmr_dump.hpp"
 #include "kmr_superkmer.hpp"
 #include "kmr_buckets.hpp"
@@ -191,6 +192,8 @@ struct Tuning {
 	uint64_t dump_piece_bytes = 0;     /* kmr_dump_mercount / kmr_dump_mergraph: staging bound of one piece of the file (0 = KMR_DUMP_PIECE_BYTES) */
 	bool dump_timing = false;          /* kmr_dump_text*: time the size pass and the writer with HIP events (kmr_build_info; measurement tools) */
 	bool select_timing = false;        /* kmr_select_* / kmr_filter_*: time scoring, selection and writer with HIP events (kmr_build_info; measurement tools) */
+	bool pairs_timing = false;         /* kmr_identify_pairs*: time the name parse, the sort and the whole call with HIP events (kmr_build_info; measurement tools) */
+	uint32_t pair_hash_bits = 64;      /* kmr_identify_pairs*: bits of the common name's hash the phase-2 sort keys keep (tests: a few bits, so that distinct names share a key) */
 	bool no_coarse_lists = true;       /* exchange: scatter into the job's fine lists (default) or, kmr_tune("coarse_lists", 1), into coarse ones that the owner splits before the count pass (sk_refine_kernel: not yet fast enough to pay) */
 };
 
@@ -246,6 +249,8 @@ struct kmr_handle : HandleMem, BuildMem, ExchangeMem {
 	bool last_early_overflowed = false;                       /* ... or that it voided one because its buffers overflowed */
 	double last_score_ms = 0, last_select_ms = 0, last_write_ms = 0;      /* the last kmr_filter_read_batch* / kmr_select_reads*: scoring, selection + writer, writer alone (HIP events, taken with kmr_tune "select_timing" only; kmr_build_info) */
 	double last_dump_size_ms = 0, last_dump_write_ms = 0;      /* the last kmr_dump_text_size / kmr_dump_text: size pass with its scan, writer (HIP events, taken with kmr_tune "dump_timing" only; kmr_build_info) */
+	double last_pairs_ms = 0, last_pairs_parse_ms = 0, last_pairs_sort_ms = 0;      /* the last kmr_identify_pairs*: the whole call, its name parse, its radix sort (HIP events, taken with kmr_tune "pairs_timing" only; kmr_build_info) */
+	uint64_t last_pair_hash_collisions = 0;      /* ... and how many of its runs of equal hash keys held more than one distinct common name */
 	uint64_t last_saturated_keys = 0, last_saturated_batches = 0;      /* what the last kmr_finalize's saturated-key pass redid, in how many batches */
 	bool qual_mixed = false;           /* a build that has seen two different quality characters stops asking (qrange) */
 	/* exchange with world_size > 1: sk_bits are the COARSE lists reads are scattered into and that travel; each holds 2^sk_fine_shift
@@ -268,6 +273,13 @@ struct kmr_picks {
 	int device = 0;
 	DevBuf text, picked;
 	uint64_t n = 0, n_picked = 0, bytes = 0;
+};
+
+/* what kmr_identify_pairs* leaves on the device: the mate of every read and the pair list */
+struct kmr_pairs {
+	int device = 0;
+	DevBuf mate, read1, read2;
+	uint64_t n = 0, n_pairs = 0, n_full = 0, n_seq = 0, n_conflicts = 0;
 };
 
 /* what kmr_dump_text leaves on the device: the mercount / mergraph text of a range of weak entries */
@@ -2431,6 +2443,8 @@ int kmr_tune(kmr_handle *h, const char *knob, double value) {
 	else if (k == "coarse_lists") h->tune.no_coarse_lists = value == 0;
 	else if (k == "select_timing") h->tune.select_timing = value != 0;
 	else if (k == "dump_timing") h->tune.dump_timing = value != 0;
+	else if (k == "pairs_timing") h->tune.pairs_timing = value != 0;
+	else if (k == "pair_hash_bits") h->tune.pair_hash_bits = value >= 1 && value < 64 ? (uint32_t)value : 64;
 	else if (k == "dump_piece_bytes") h->tune.dump_piece_bytes = value >= 1 ? (uint64_t)value : 0;
 	else if (k == "narrow_tallies") h->tune.no_narrow = value == 0;
 	else if (k == "keep_level1_state") h->tune.no_l1_state = value == 0;
@@ -2460,6 +2474,10 @@ int kmr_build_info(kmr_handle *h, const char *what, double *value) {
 	else if (k == "filter_score_ms") *value = h->last_score_ms;
 	else if (k == "select_ms") *value = h->last_select_ms;
 	else if (k == "select_write_ms") *value = h->last_write_ms;
+	else if (k == "pairs_ms") *value = h->last_pairs_ms;
+	else if (k == "pairs_parse_ms") *value = h->last_pairs_parse_ms;
+	else if (k == "pairs_sort_ms") *value = h->last_pairs_sort_ms;
+	else if (k == "pair_hash_collisions") *value = (double)h->last_pair_hash_collisions;
 	else if (k == "dump_size_ms") *value = h->last_dump_size_ms;
 	else if (k == "dump_write_ms") *value = h->last_dump_write_ms;
 	else return fail(h, KMR_ERR_INVALID_ARG, "unknown build figure '" + k + "'");
@@ -3497,14 +3515,17 @@ static int select_check_config(kmr_handle *h, const kmr_select_config *c) {
 	return 0;
 }
 
-/* up to three HIP events on the handle's stream, created and recorded only while kmr_tune "select_timing" is set */
-struct SelectTimer {
-	hipEvent_t ev[3] = {nullptr, nullptr, nullptr}; bool on;
-	explicit SelectTimer(bool enabled) : on(enabled) { if (on) for (auto &e : ev) if (hipEventCreate(&e) != hipSuccess) { e = nullptr; on = false; } }
-	~SelectTimer() { for (auto e : ev) if (e) hipEventDestroy(e); }
+/* up to N HIP events on the handle's stream, created and recorded only while the call's timing knob (kmr_tune "select_timing", "pairs_timing") is set */
+extern "C++" {
+template <int N> struct EventTimer {
+	hipEvent_t ev[N] = {}; bool on;
+	explicit EventTimer(bool enabled) : on(enabled) { if (on) for (auto &e : ev) if (hipEventCreate(&e) != hipSuccess) { e = nullptr; on = false; } }
+	~EventTimer() { for (auto e : ev) if (e) hipEventDestroy(e); }
 	void mark(int i, hipStream_t s) { if (on) hipEventRecord(ev[i], s); }
 	double ms(int a, int b) const { float t = 0; return on && hipEventElapsedTime(&t, ev[a], ev[b]) == hipSuccess ? t : 0.0; }      /* after the stream has been waited for */
 };
+}
+typedef EventTimer<3> SelectTimer;
 
 /* every pointer but the last is device memory (mate and the three af_* may be null) */
 static int select_core(kmr_handle *h, const kmr_reads *r, const uint8_t *dtext, uint64_t text_len, const int64_t *dmate, const uint8_t *dact, const uint32_t *dmin,
@@ -3651,6 +3672,144 @@ int kmr_picks_device_ptr(const kmr_picks *p, void **dev_text) {
 	return KMR_OK;
 }
 void kmr_picks_free(kmr_picks *p) {
+	if (!p) return;
+	hipSetDevice(p->device);
+	delete p;      /* (its buffers are freed on this device) */
+}
+
+/* ---- ReadSet::identifyPairs on the device (kmr_pairs.hpp) ---------------- */
+/* dtext: device memory */
+static int pairs_core(kmr_handle *h, const kmr_reads *r, const uint8_t *dtext, uint64_t text_len, int store_comment, kmr_pairs **out) {
+	const uint64_t n = r->n;
+	std::unique_ptr<kmr_pairs, void (*)(kmr_pairs *)> pr(new kmr_pairs, kmr_pairs_free);
+	pr->device = h->device; pr->n = n;
+	h->last_pairs_ms = h->last_pairs_parse_ms = h->last_pairs_sort_ms = 0; h->last_pair_hash_collisions = 0;
+	if (n == 0) { *out = pr.release(); return KMR_OK; }
+	PairsParams P;
+	P.name_off = r->name_off.get<uint64_t>(); P.name_len = r->name_len.get<uint32_t>(); P.text = dtext; P.text_len = text_len; P.n = n; P.store_comment = store_comment ? 1u : 0u;
+	const dim3 grid(grid_for(n)), block(256);
+	DevBuf b_hash, b_cn, b_fl, b_link, b_brk, b_bscan, b_run, b_sec, b_unp, b_sscan, b_uscan, b_tot;
+	uint64_t *hash, *bscan, *sscan, *uscan, *tot; uint32_t *cn, *brk, *run, *sec, *unp; uint8_t *fl, *link; int64_t *mate;
+	HIPCHK(h, alloc_n(b_hash, &hash, n)); HIPCHK(h, alloc_n(b_cn, &cn, n)); HIPCHK(h, alloc_n(b_fl, &fl, n)); HIPCHK(h, alloc_n(b_tot, &tot, (size_t)PAIRS_T_WORDS));
+	HIPCHK(h, alloc_n(pr->mate, &mate, n));
+	EventTimer<5> timer(h->tune.pairs_timing);
+	timer.mark(0, h->stream);
+	HIPCHK(h, hipMemsetAsync(tot, 0, 8 * PAIRS_T_WORDS, h->stream));
+	hipLaunchKernelGGL(pairs_parse_kernel, grid, block, 0, h->stream, P, hash, cn, fl, tot);
+	HIPCHK(h, hipGetLastError());
+	timer.mark(1, h->stream);
+	uint64_t totals[PAIRS_T_WORDS] = {0};
+	if (text_len == 0) {      /* no names (kmr_reads_from_host, kmr_reads_from_twobit): every read is a half pair of its own */
+		int64_t *r1, *r2;
+		HIPCHK(h, alloc_n(pr->read1, &r1, n)); HIPCHK(h, alloc_n(pr->read2, &r2, n));
+		hipLaunchKernelGGL(pairs_single_kernel, grid, block, 0, h->stream, n, mate, r1, r2);
+		HIPCHK(h, hipGetLastError());
+		HIPCHK(h, hipMemcpyAsync(totals, tot, 8 * PAIRS_T_WORDS, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
+		if (totals[PAIRS_T_ERR] & PAIRS_ERR_NAME) return fail(h, KMR_ERR_INVALID_ARG, "a read's name span lies outside the text handed in (pass the text the batch was ingested from)");
+		pr->n_pairs = n;
+		*out = pr.release();
+		return KMR_OK;
+	}
+	const PairsNames N = {hash, cn, fl};
+	/* phase 1 */
+	HIPCHK(h, alloc_n(b_link, &link, n)); HIPCHK(h, alloc_n(b_brk, &brk, n)); HIPCHK(h, alloc_n(b_bscan, &bscan, n + 1)); HIPCHK(h, alloc_n(b_run, &run, n + 1));
+	HIPCHK(h, alloc_n(b_sec, &sec, n)); HIPCHK(h, alloc_n(b_unp, &unp, n)); HIPCHK(h, alloc_n(b_sscan, &sscan, n + 1)); HIPCHK(h, alloc_n(b_uscan, &uscan, n + 1));
+	hipLaunchKernelGGL(pairs_link_kernel, grid, block, 0, h->stream, P, N, link, brk);
+	HIPCHK(h, hipGetLastError());
+	int rc = exclusive_scan(h, brk, n, bscan); if (rc) return rc;
+	hipLaunchKernelGGL(pairs_runstart_kernel, grid, block, 0, h->stream, (const uint8_t *)link, (const uint64_t *)bscan, n, run);
+	hipLaunchKernelGGL(pairs_seq_kernel, grid, block, 0, h->stream, (const uint8_t *)link, (const uint64_t *)bscan, (const uint32_t *)run, n, sec, unp, mate);
+	HIPCHK(h, hipGetLastError());
+	rc = exclusive_scan(h, sec, n, sscan); if (rc) return rc;
+	rc = exclusive_scan(h, unp, n, uscan); if (rc) return rc;
+	/* the first of the call's two fixed-size copies: phase 1's totals size phase 2 (an interleaved file leaves it nothing) */
+	HIPCHK(h, hipMemcpyAsync(&totals[PAIRS_T_SEQ], sscan + n, 8, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipMemcpyAsync(&totals[PAIRS_T_UNPAIRED], uscan + n, 8, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipMemcpyAsync(&totals[PAIRS_T_ERR], tot + PAIRS_T_ERR, 8, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipStreamSynchronize(h->stream));
+	if (totals[PAIRS_T_ERR] & PAIRS_ERR_NAME) return fail(h, KMR_ERR_INVALID_ARG, "a read's name span lies outside the text handed in (pass the text the batch was ingested from)");
+	const uint64_t n_seq = totals[PAIRS_T_SEQ], m = totals[PAIRS_T_UNPAIRED];
+	/* phase 2 */
+	DevBuf b_kin, b_kout, b_vin, b_vout, b_tmp, b_push, b_side, b_pscan;
+	unsigned long long *kin, *kout; uint32_t *vin, *vout, *push = nullptr; uint8_t *side = nullptr; uint64_t *pscan = nullptr;
+	timer.mark(2, h->stream); timer.mark(3, h->stream);
+	if (m) {
+		HIPCHK(h, alloc_n(b_kin, &kin, m)); HIPCHK(h, alloc_n(b_kout, &kout, m)); HIPCHK(h, alloc_n(b_vin, &vin, m)); HIPCHK(h, alloc_n(b_vout, &vout, m));
+		HIPCHK(h, alloc_n(b_push, &push, n)); HIPCHK(h, alloc_n(b_side, &side, n)); HIPCHK(h, alloc_n(b_pscan, &pscan, n + 1));
+		const uint32_t bits = h->tune.pair_hash_bits;
+		hipLaunchKernelGGL(pairs_keys_kernel, grid, block, 0, h->stream, (const uint32_t *)unp, (const uint64_t *)uscan, (const uint64_t *)hash, bits >= 64 ? ~0ull : (1ull << bits) - 1, n, kin, vin);
+		HIPCHK(h, hipGetLastError());
+		HIPCHK(h, hipMemsetAsync(push, 0, 4 * n, h->stream)); HIPCHK(h, hipMemsetAsync(side, 0, n, h->stream));
+		size_t tmp_bytes = 0;
+		if (kmr::sort_pairs_u64_u32(nullptr, &tmp_bytes, kin, kout, vin, vout, m, h->stream) != 0) return fail(h, KMR_ERR_HIP, "kmr_identify_pairs: radix sort (size query)");
+		HIPCHK(h, b_tmp.alloc(std::max<size_t>(tmp_bytes, 256)));
+		timer.mark(2, h->stream);
+		if (kmr::sort_pairs_u64_u32(b_tmp.get(), &tmp_bytes, kin, kout, vin, vout, m, h->stream) != 0) return fail(h, KMR_ERR_HIP, "kmr_identify_pairs: radix sort");
+		timer.mark(3, h->stream);
+		hipLaunchKernelGGL(pairs_group_kernel, dim3(grid_for(m)), block, 0, h->stream, P, N, (const unsigned long long *)kout, (const uint32_t *)vout, m, mate, push, side, tot);
+		HIPCHK(h, hipGetLastError());
+		rc = exclusive_scan(h, push, n, pscan); if (rc) return rc;
+		/* the second: what phase 2 made */
+		HIPCHK(h, hipMemcpyAsync(&totals[PAIRS_T_PUSHED], pscan + n, 8, hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, hipMemcpyAsync(&totals[PAIRS_T_FULL2], tot + PAIRS_T_FULL2, 8 * (PAIRS_T_WORDS - PAIRS_T_FULL2), hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, hipStreamSynchronize(h->stream));
+	}
+	pr->n_seq = n_seq; pr->n_pairs = n_seq + totals[PAIRS_T_PUSHED]; pr->n_full = n_seq + totals[PAIRS_T_FULL2];
+	pr->n_conflicts = totals[PAIRS_T_CONFLICT1] + totals[PAIRS_T_CONFLICT2];
+	h->last_pair_hash_collisions = totals[PAIRS_T_COLLISIONS];
+	int64_t *r1, *r2;
+	HIPCHK(h, alloc_n(pr->read1, &r1, pr->n_pairs)); HIPCHK(h, alloc_n(pr->read2, &r2, pr->n_pairs));
+	hipLaunchKernelGGL(pairs_scatter_kernel, grid, block, 0, h->stream, (const uint32_t *)sec, (const uint64_t *)sscan, (const uint32_t *)push, (const uint64_t *)pscan, (const uint8_t *)side, (const int64_t *)mate,
+	                   n, n_seq, r1, r2);
+	HIPCHK(h, hipGetLastError());
+	timer.mark(4, h->stream);
+	HIPCHK(h, hipStreamSynchronize(h->stream));
+	h->last_pairs_ms = timer.ms(0, 4); h->last_pairs_parse_ms = timer.ms(0, 1); h->last_pairs_sort_ms = m ? timer.ms(2, 3) : 0.0;
+	*out = pr.release();
+	return KMR_OK;
+}
+
+static int identify_pairs_any(kmr_handle *h, const kmr_reads *r, const void *text, uint64_t text_len, bool text_on_device, int store_comment, kmr_pairs **out) {
+	if (!h || !r || !out || (text_len && !text)) return KMR_ERR_INVALID_ARG;
+	*out = nullptr;
+	if (r->device != h->device) return fail(h, KMR_ERR_INVALID_ARG, "read batch lives on another device");
+	if (r->n >= 0xffffffffull) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_identify_pairs: a batch holds fewer than 2^32 - 1 reads (read indices of the sort are 32-bit)");
+	hipSetDevice(h->device);
+	DevBuf b_text;
+	const uint8_t *dtext = (const uint8_t *)text;
+	if (!text_on_device && r->n) { int rc = select_upload(h, b_text, (const uint8_t *)text, text_len, &dtext); if (rc) return rc; }
+	const int rc = pairs_core(h, r, dtext, text_len, store_comment, out);
+	if (rc) hipStreamSynchronize(h->stream);      /* the upload above must have landed before its buffer goes */
+	return rc;
+}
+int kmr_identify_pairs(kmr_handle *h, const kmr_reads *reads, const char *text, uint64_t text_len, int store_comment, kmr_pairs **out) {
+	return identify_pairs_any(h, reads, text, text_len, false, store_comment, out);
+}
+int kmr_identify_pairs_dev(kmr_handle *h, const kmr_reads *reads, const void *dev_text, uint64_t text_len, int store_comment, kmr_pairs **out) {
+	return identify_pairs_any(h, reads, dev_text, text_len, true, store_comment, out);
+}
+int kmr_pairs_info(const kmr_pairs *p, uint64_t *n_reads, uint64_t *n_pairs, uint64_t *n_full, uint64_t *n_sequential, uint64_t *n_conflicts, int *has_pairs) {
+	if (!p) return KMR_ERR_INVALID_ARG;
+	if (n_reads) *n_reads = p->n; if (n_pairs) *n_pairs = p->n_pairs; if (n_full) *n_full = p->n_full;
+	if (n_sequential) *n_sequential = p->n_seq; if (n_conflicts) *n_conflicts = p->n_conflicts;
+	if (has_pairs) *has_pairs = p->n_pairs > 0 && p->n_pairs < p->n;      /* ReadSet::hasPairs, src/ReadSet.h:526-529 */
+	return KMR_OK;
+}
+int kmr_pairs_copy(const kmr_pairs *p, int64_t *mate, int64_t *read1, int64_t *read2) {
+	if (!p) return KMR_ERR_INVALID_ARG;
+	hipSetDevice(p->device);
+	hipError_t e = hipSuccess;
+	if (mate && p->n) e = hipMemcpy(mate, p->mate.get<int64_t>(), 8 * p->n, hipMemcpyDeviceToHost);
+	if (read1 && p->n_pairs && e == hipSuccess) e = hipMemcpy(read1, p->read1.get<int64_t>(), 8 * p->n_pairs, hipMemcpyDeviceToHost);
+	if (read2 && p->n_pairs && e == hipSuccess) e = hipMemcpy(read2, p->read2.get<int64_t>(), 8 * p->n_pairs, hipMemcpyDeviceToHost);
+	return e == hipSuccess ? KMR_OK : KMR_ERR_HIP;
+}
+int kmr_pairs_device_ptrs(const kmr_pairs *p, void **dev_mate, void **dev_read1, void **dev_read2) {
+	if (!p) return KMR_ERR_INVALID_ARG;
+	if (dev_mate) *dev_mate = p->mate.get<int64_t>(); if (dev_read1) *dev_read1 = p->read1.get<int64_t>(); if (dev_read2) *dev_read2 = p->read2.get<int64_t>();
+	return KMR_OK;
+}
+void kmr_pairs_free(kmr_pairs *p) {
 	if (!p) return;
 	hipSetDevice(p->device);
 	delete p;      /* (its buffers are freed on this device) */

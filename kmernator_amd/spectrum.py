@@ -593,6 +593,7 @@ class ReadSet:
     def __init__(self, spectrum, text, input_quality_base=0, store_comment=True):
         self.sp = spectrum
         self.text = bytes(text)
+        self.store_comment = bool(store_comment)
         r = C.c_void_p()
         buf = np.frombuffer(self.text, dtype=np.uint8)
         spectrum._call("ingest_fastq", spectrum.h, buf.ctypes.data_as(C.c_void_p) if buf.size else None, buf.size,
@@ -603,10 +604,11 @@ class ReadSet:
         self.n, self.total_bases, self.input_quality_base, self.filtered = n.value, tot.value, qb.value, nf.value
 
     @classmethod
-    def _adopt(cls, spectrum, text, handle):
+    def _adopt(cls, spectrum, text, handle, store_comment=True):
         """wrap a kmr_reads the library produced from another batch (names still point into `text`)"""
         self = cls.__new__(cls)
         self.sp, self.text, self.r = spectrum, text, handle
+        self.store_comment = bool(store_comment)
         n, tot, qb, nf = C.c_uint64(), C.c_uint64(), C.c_uint32(), C.c_uint64()
         spectrum.lib.kmr_reads_info(self.r, C.byref(n), C.byref(tot), C.byref(qb), C.byref(nf))
         self.n, self.total_bases, self.input_quality_base, self.filtered = n.value, tot.value, qb.value, nf.value
@@ -671,10 +673,97 @@ class ReadSet:
         names = [self.text[int(no[i]):int(no[i]) + int(nl[i])] for i in range(self.n)]
         return b, q, o, names
 
+    def identifyPairs(self, store_comment=None, device_text=None):
+        """ReadSet::identifyPairs (src/ReadSet.cpp:446-570) of this batch as a fresh set, on the device (kmr_identify_pairs): a
+        ReadPairs.  `store_comment` defaults to what the batch was ingested with; `device_text` = device pointer of the FASTQ
+        text if the caller holds it there (kmr_identify_pairs_dev)."""
+        sc = self.store_comment if store_comment is None else bool(store_comment)
+        out = C.c_void_p()
+        if device_text is not None:
+            self.sp._call("identify_pairs_dev", self.sp.h, self.r, C.c_void_p(device_text), len(self.text), 1 if sc else 0, C.byref(out))
+        else:
+            buf = np.frombuffer(self.text, dtype=np.uint8)
+            self.sp._call("identify_pairs", self.sp.h, self.r, buf.ctypes.data_as(C.c_void_p) if buf.size else None, buf.size, 1 if sc else 0, C.byref(out))
+        return ReadPairs(self.sp, out)
+
     def close(self):
         if getattr(self, "r", None):
             self.sp.lib.kmr_reads_free(self.r)
             self.r = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ReadPairs:
+    """What ReadSet.identifyPairs found (kmr_pairs), kept on the device until close(): .mate[i] = the read paired with i or -1 (what
+    FilterKnownOddities.applyFilter(mate=) and ReadSelector(mate=) take), .pairs = the reference's pair list as an (n_pairs, 2)
+    int64 array of (read1, read2) with -1 for a missing side, and the counts n_reads, n_pairs, n_full, n_sequential, n_conflicts."""
+
+    def __init__(self, sp, handle):
+        self.sp, self._p = sp, handle
+        v = [C.c_uint64() for _ in range(5)]
+        hp = C.c_int()
+        rc = sp.lib.kmr_pairs_info(handle, *[C.byref(x) for x in v], C.byref(hp))
+        if rc != 0:
+            raise KmerSpectrumError("kmr_pairs_info: %s" % _lib.STATUS.get(rc, rc))
+        self.n_reads, self.n_pairs, self.n_full, self.n_sequential, self.n_conflicts = [x.value for x in v]
+        self._has_pairs = bool(hp.value)
+        self._host = None
+
+    def _live(self):
+        if not self._p:
+            raise KmerSpectrumError("ReadPairs: closed")
+        return self._p
+
+    def _copy(self):
+        if self._host is None:
+            i64 = C.POINTER(C.c_int64)
+            mate = np.zeros(max(1, self.n_reads), dtype=np.int64)
+            r1 = np.zeros(max(1, self.n_pairs), dtype=np.int64)
+            r2 = np.zeros(max(1, self.n_pairs), dtype=np.int64)
+            rc = self.sp.lib.kmr_pairs_copy(self._live(), mate.ctypes.data_as(i64), r1.ctypes.data_as(i64), r2.ctypes.data_as(i64))
+            if rc != 0:
+                raise KmerSpectrumError("kmr_pairs_copy: %s" % _lib.STATUS.get(rc, rc))
+            self._host = (mate[:self.n_reads], np.stack([r1[:self.n_pairs], r2[:self.n_pairs]], axis=1))
+        return self._host
+
+    @property
+    def mate(self):
+        return self._copy()[0]
+
+    @property
+    def pairs(self):
+        return self._copy()[1]
+
+    def getPairSize(self):
+        return self.n_pairs
+
+    def hasPairs(self):
+        """ReadSet::hasPairs (src/ReadSet.h:526-529): 0 < pairs < reads"""
+        return self._has_pairs
+
+    def device_ptrs(self):
+        """device pointers of (mate[n_reads], read1[n_pairs], read2[n_pairs]), int64 each; valid until close()"""
+        a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        rc = self.sp.lib.kmr_pairs_device_ptrs(self._live(), C.byref(a), C.byref(b), C.byref(c))
+        if rc != 0:
+            raise KmerSpectrumError("kmr_pairs_device_ptrs: %s" % _lib.STATUS.get(rc, rc))
+        return a.value or 0, b.value or 0, c.value or 0
+
+    def close(self):
+        if getattr(self, "_p", None):
+            self.sp.lib.kmr_pairs_free(self._p)
+            self._p = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
     def __del__(self):
         try:
@@ -734,7 +823,7 @@ class FilterKnownOddities:
                       res["max_pass"].ctypes.data_as(u32), res["action"].ctypes.data_as(C.POINTER(C.c_uint8)), res["remnant_off"].ctypes.data_as(u32),
                       res["remnant_len"].ctypes.data_as(u32), C.byref(out) if want_reads else None)
         res = {k: v[:n] for k, v in res.items()}
-        return res, (ReadSet._adopt(self.sp, reads.text, out) if want_reads else None)
+        return res, (ReadSet._adopt(self.sp, reads.text, out, getattr(reads, "store_comment", True)) if want_reads else None)
 
     def close(self):
         if getattr(self, "f", None):
