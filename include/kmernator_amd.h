@@ -748,6 +748,80 @@ int kmr_pairs_copy(const kmr_pairs *p, int64_t *mate, int64_t *read1, int64_t *r
 int kmr_pairs_device_ptrs(const kmr_pairs *p, void **dev_mate, void **dev_read1, void **dev_read2);
 void kmr_pairs_free(kmr_pairs *p);
 
+/* ---- DuplicateFragmentFilter: fragments with the same first bases collapse to consensus reads, on the device ----------
+ * One call equals one DuplicateFragmentFilter::_filterDuplicateFragments (src/DuplicateFragmentFilter.h:505-559) over the
+ * batch, with cutoff 2, edit distance 0 and consensus on, in the order a single-threaded reference visits the pair list:
+ * the paired pass (paired = 1) or the pass --dedup-single adds (paired = 0).  apps/FilterReads.cpp:120-141 runs the stage
+ * between the artifact filter and the spectrum build when --dedup-mode is 1 or 2.  `pairs` is what kmr_identify_pairs* left
+ * for this batch, `text` the FASTQ text the batch was ingested from (names), `discarded` one byte per read, non-zero =
+ * Read::isDiscarded (the artifact filter's action == 2), NULL = none.
+ *   candidates  (:194-279) the pair list in its own order.  Paired pass: a record with both ends takes part, one with a
+ *               single end counts as skipped[2] (unpaired); single pass: a record with exactly one end takes part, one with
+ *               two counts as unpaired.  A member with a discarded read counts as skipped[0]; one with a read shorter than
+ *               start_offset + L up to its first X or x (getFirstMarkupXLength, src/Sequence.cpp:432-439) as skipped[1],
+ *               read 1 tested before read 2, one count per record; a read index outside the batch as skipped[3].  L is
+ *               dedup_length in the paired pass and 2 * dedup_length in the single pass (:188-190)
+ *   key         (:217-241) the 2-bit code (anything but ACGT packs as A) of read 1's bases [start_offset, start_offset + L)
+ *               followed by the reverse complement of read 2's, or of the one read's window in the single pass.  With
+ *               dedup_mode 2 the paired pass takes the smaller, in memcmp order, of the key and its reverse complement
+ *               (buildLeastComplement, src/Kmer.h:356-364: a tie keeps the key) and a member whose key was replaced is
+ *               flipped: its read2 counts as side 1
+ *   groups      members with equal keys, in ascending position in the pair list (the instance order of a serial build,
+ *               src/KmerTrackingData.h:810-841); those of two members and more are collapsed
+ *   consensus   (:420-503, :361-418) per collapsed group one read per side -- two in the paired pass, side 1 then side 2, one
+ *               in the single pass --: ReadSet::getConsensusRead(min_quality_score) of the side's reads in member order
+ *               (src/ReadSet.cpp:572-629; Read::getProbabilityBases and ProbabilityBase, src/Sequence.cpp:563-582, 807-967,
+ *               src/Sequence.h:304-338, the copy constructor's setTop included), named "C" + the member count + "-" + the
+ *               name of the side's first member up to its first blank or tab (what kmr_select_reads prints of a name)
+ *   discards    every read of every member of a collapsed group (:475-491); affected = reads so discarded
+ * The consensus reads are a batch of their own, owned by the kmr_dedup: bases and qualities at the handle's
+ * fastq_start_char, name spans pointing into a name text of its own (the names back to back, each followed by a newline).
+ * kmr_artifact_filter_apply, kmr_add_read_batch, kmr_identify_pairs* and kmr_filter_read_batch* take it as any other batch;
+ * the reference appends it behind the last read (:552), so its output text follows the main batch's.  In the paired pass read
+ * 2g and read 2g + 1 are the two sides of group g.
+ * dedup_mode 0 is the reference's default and means the stage is off (:563-566): a valid call that collapses nothing.
+ * An empty batch, a batch without pairs and a batch without duplicates are valid: no groups, an empty consensus batch.
+ * Nothing per read crosses the bus inside the call but `discarded`; three fixed-size copies bring sizes back.
+ * Not covered: the order of the consensus reads among themselves -- the reference's follows the bucket iteration of its map
+ * and, under OpenMP, the thread that met the group; here groups come out in ascending position of their first member, and the
+ * parity claim is on the set of consensus reads, each byte for byte, the discard flags and the counters; dedup-edit-distance 1
+ * (its consolidation order depends on a sort of equal counts and on thread timing) and dedup-consensus 0 (it draws from
+ * LongRand): KMR_ERR_UNSUPPORTED; keys of more than 128 bases (2 * dedup_length > 128): KMR_ERR_UNSUPPORTED; the artifact
+ * filter's run over the new reads (:534-550) and reads.append stay with the caller; the Casava rewrite of a first member's
+ * name, as in kmr_select_reads.  dedup_length or start_offset not a multiple of 4 is KMR_ERR_INVALID_ARG (the option check, :137).
+ * Bounds: a batch holds fewer than 2^32 - 1 reads; a group's member count enters getA .. getT as a short, as in the reference. */
+typedef struct kmr_dedup_config {
+	uint32_t struct_size;
+	uint32_t dedup_mode;        /* 0 off, 1 one orientation, 2 both orientations */
+	uint32_t paired;            /* 1: the pass over pairs, 0: the --dedup-single pass over single reads */
+	uint32_t dedup_length;      /* 24 */
+	uint32_t start_offset;      /* 0 */
+	uint32_t edit_distance;     /* 0 */
+	uint32_t consensus;         /* 1 */
+} kmr_dedup_config;
+int kmr_dedup_config_init(kmr_dedup_config *cfg);      /* the reference's defaults (:60-61), paired = 1 */
+typedef struct kmr_dedup kmr_dedup;
+int kmr_dedup_fragments(kmr_handle *h, const kmr_reads *reads, const char *text, uint64_t text_len, const kmr_pairs *pairs,
+                        const uint8_t *discarded, const kmr_dedup_config *cfg, kmr_dedup **out);
+/* the same with the FASTQ text already in device memory (`discarded` is host memory in both) */
+int kmr_dedup_fragments_dev(kmr_handle *h, const kmr_reads *reads, const void *dev_text, uint64_t text_len, const kmr_pairs *pairs,
+                            const uint8_t *discarded, const kmr_dedup_config *cfg, kmr_dedup **out);
+/* any pointer may be NULL; skipped = discarded, too short, unpaired, invalid */
+int kmr_dedup_info(const kmr_dedup *d, uint64_t *n_groups, uint64_t *n_new_reads, uint64_t *affected, uint64_t skipped[4]);
+/* to host memory: discarded_out[n_reads] = the flags handed in OR the new discards; per collapsed group, in output order, the
+ * pair-list position of its first member and its member count; any may be NULL */
+int kmr_dedup_copy(const kmr_dedup *d, uint8_t *discarded_out, uint64_t *group_first, uint32_t *group_size);
+/* the same three arrays where they lie; valid until kmr_dedup_free */
+int kmr_dedup_device_ptrs(const kmr_dedup *d, void **dev_discarded, void **dev_group_first, void **dev_group_size);
+/* the consensus batch (owned by d: do not kmr_reads_free it), its name text on the device and that text's length */
+int kmr_dedup_reads(const kmr_dedup *d, const kmr_reads **consensus, const void **dev_name_text, uint64_t *name_text_len);
+/* the name text to host memory (KMR_ERR_CAPACITY if capacity < name_text_len) */
+int kmr_dedup_names_copy(const kmr_dedup *d, char *dst, uint64_t capacity);
+void kmr_dedup_free(kmr_dedup *d);
+/* BaseQual::getQualChar (src/Sequence.cpp:807-819) without FASTQ_START_CHAR: 40 from 0.9999, else (char)(-10. * log10(1.0 - prob)),
+ * answered from the 39 doubles at which that expression steps -- the table the device compares against.  prob >= 0.  Needs no device. */
+char kmr_consensus_qual(double prob);
+
 /* Raw HIP stream of the handle (hipStream_t) so callers can order their own
  * work (torch.cuda.ExternalStream) against it. */
 void *kmr_stream(kmr_handle *h);
@@ -776,6 +850,7 @@ void *kmr_stream(kmr_handle *h);
  *   "pair_hash_bits" (bits of the common name's hash that kmr_identify_pairs* sorts by, 1 - 64, default 64: with a few bits distinct names
  *   share a key, which tests use to reach the byte-for-byte grouping), "pairs_timing" (1: kmr_identify_pairs* times its phases with HIP
  *   events, see kmr_build_info; default 0); both may be set at any time.
+ *   "dedup_timing" (1: kmr_dedup_fragments* times its phases with HIP events, see kmr_build_info; default 0; may be set at any time).
  * Call before the first kmr_add_reads* of a build.  KMR_ERR_INVALID_ARG for an unknown knob. */
 int kmr_tune(kmr_handle *h, const char *knob, double value);
 /* What the current build decided, for tests and measurement tools (the reference logs such figures, LOG_VERBOSE): "lists" = super-k-mer
@@ -791,7 +866,9 @@ int kmr_tune(kmr_handle *h, const char *knob, double value);
  * "dump_size_ms" / "dump_write_ms" = HIP-event times of the last kmr_dump_text_size / kmr_dump_text on this handle: its size pass with
  * the scan, its writer (0 unless kmr_tune "dump_timing" is set), "pairs_ms" / "pairs_parse_ms" / "pairs_sort_ms" = HIP-event times of the
  * last kmr_identify_pairs* on this handle: the whole call, its name parse, its radix sort (0 unless kmr_tune "pairs_timing" is set),
- * "pair_hash_collisions" = runs of equal sort keys of that call that held more than one distinct common name.
+ * "pair_hash_collisions" = runs of equal sort keys of that call that held more than one distinct common name,
+ * "dedup_ms" / "dedup_key_ms" / "dedup_sort_ms" / "dedup_consensus_ms" = HIP-event times of the last kmr_dedup_fragments* on this
+ * handle: the whole call, its key kernel, its radix sorts, its consensus kernel (0 unless kmr_tune "dedup_timing" is set).
  * KMR_ERR_INVALID_ARG for an unknown name. */
 int kmr_build_info(kmr_handle *h, const char *what, double *value);
 

@@ -60,6 +60,11 @@ class KmrArtifactConfig(C.Structure):
                                           "phix_idx", "reference_begin", "min_quality", "fastq_start_char")] + [("min_read_length", C.c_float)]
 
 
+class KmrDedupConfig(C.Structure):
+    """kmr_dedup_config"""
+    _fields_ = [(n, C.c_uint32) for n in ("struct_size", "dedup_mode", "paired", "dedup_length", "start_offset", "edit_distance", "consensus")]
+
+
 class KmrSelectConfig(C.Structure):
     """kmr_select_config"""
     _fields_ = [("struct_size", C.c_uint32), ("both_pass", C.c_uint32), ("minimum_score", C.c_double), ("min_read_length", C.c_float),
@@ -84,6 +89,8 @@ EXPORTS = [
     "kmr_picks_info", "kmr_picks_copy", "kmr_picks_device_ptr", "kmr_picks_free",
     "kmr_dump_text_size", "kmr_dump_text", "kmr_text_info", "kmr_text_copy", "kmr_text_device_ptr", "kmr_text_free",
     "kmr_identify_pairs", "kmr_identify_pairs_dev", "kmr_pairs_info", "kmr_pairs_copy", "kmr_pairs_device_ptrs", "kmr_pairs_free",
+    "kmr_dedup_config_init", "kmr_dedup_fragments", "kmr_dedup_fragments_dev", "kmr_dedup_info", "kmr_dedup_copy", "kmr_dedup_device_ptrs",
+    "kmr_dedup_reads", "kmr_dedup_names_copy", "kmr_dedup_free", "kmr_consensus_qual",
     "kmr_map_digest", "kmr_synth_reads_dev", "kmr_build_info", "kmr_sk_exchange_uniform", "kmr_sk_exchange_peer_uniform", "kmr_sk_exchange_range", "kmr_count_lists_prefix",
 ]
 
@@ -222,6 +229,19 @@ def load():
     lib.kmr_pairs_device_ptrs.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     lib.kmr_pairs_free.argtypes = [vp]
     lib.kmr_pairs_free.restype = None
+    dcp = C.POINTER(KmrDedupConfig)
+    lib.kmr_dedup_config_init.argtypes = [dcp]
+    for name in ("kmr_dedup_fragments", "kmr_dedup_fragments_dev"):
+        getattr(lib, name).argtypes = [vp, vp, vp, C.c_uint64, vp, u8p, dcp, C.POINTER(vp)]
+    lib.kmr_dedup_info.argtypes = [vp, u64p, u64p, u64p, u64p]
+    lib.kmr_dedup_copy.argtypes = [vp, u8p, u64p, u32p]
+    lib.kmr_dedup_device_ptrs.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    lib.kmr_dedup_reads.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), u64p]
+    lib.kmr_dedup_names_copy.argtypes = [vp, vp, C.c_uint64]
+    lib.kmr_dedup_free.argtypes = [vp]
+    lib.kmr_dedup_free.restype = None
+    lib.kmr_consensus_qual.argtypes = [C.c_double]
+    lib.kmr_consensus_qual.restype = C.c_char
     _lib = lib
     return lib
 

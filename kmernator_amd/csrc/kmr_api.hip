@@ -24,6 +24,7 @@
 #include <cstring>
 #include <cctype>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -35,6 +36,7 @@
 #include "kmr_artifact.hpp"
 #include "kmr_select.hpp"
 #include "kmr_pairs.hpp"
+#include "kmr_dedup.hpp"
 #include "kmr_dump.hpp"
 #include "kmr_superkmer.hpp"
 #include "kmr_buckets.hpp"
@@ -140,6 +142,7 @@ struct HandleMem {                   /* ... by kmr_destroy */
 	/* an exchange in steps over the list space (kmr_sk_exchange_range) and the lists below `hi` counted early (kmr_count_lists_prefix):
 	 * their entries wait in buffers of their own until kmr_finalize has counted the rest */
 	struct Early { bool active = false; uint64_t hi = 0; uint32_t min_depth = 0; DevBuf ue, cursor, fc, err; } early;      /* err: the early pass's own error word, read by kmr_finalize alone */
+	DevBuf dedup_tab;                /* kmr_dedup_fragments*: the probability and quality-step tables (DedupTables), made by the first call */
 	DevBuf xo_dev;                   /* kmr_extract_by_owner_host: owner segments of one batch kept on the device between the sizing call and the copy-out */
 };
 struct BuildMem {                    /* ... by kmr_release_table too: the streaming build's state */
@@ -193,6 +196,7 @@ struct Tuning {
 	bool dump_timing = false;          /* kmr_dump_text*: time the size pass and the writer with HIP events (kmr_build_info; measurement tools) */
 	bool select_timing = false;        /* kmr_select_* / kmr_filter_*: time scoring, selection and writer with HIP events (kmr_build_info; measurement tools) */
 	bool pairs_timing = false;         /* kmr_identify_pairs*: time the name parse, the sort and the whole call with HIP events (kmr_build_info; measurement tools) */
+	bool dedup_timing = false;         /* kmr_dedup_fragments*: time the key kernel, the sorts, the consensus kernel and the whole call with HIP events (kmr_build_info; measurement tools) */
 	uint32_t pair_hash_bits = 64;      /* kmr_identify_pairs*: bits of the common name's hash the phase-2 sort keys keep (tests: a few bits, so that distinct names share a key) */
 	bool no_coarse_lists = true;       /* exchange: scatter into the job's fine lists (default) or, kmr_tune("coarse_lists", 1), into coarse ones that the owner splits before the count pass (sk_refine_kernel: not yet fast enough to pay) */
 };
@@ -250,6 +254,7 @@ struct kmr_handle : HandleMem, BuildMem, ExchangeMem {
 	double last_score_ms = 0, last_select_ms = 0, last_write_ms = 0;      /* the last kmr_filter_read_batch* / kmr_select_reads*: scoring, selection + writer, writer alone (HIP events, taken with kmr_tune "select_timing" only; kmr_build_info) */
 	double last_dump_size_ms = 0, last_dump_write_ms = 0;      /* the last kmr_dump_text_size / kmr_dump_text: size pass with its scan, writer (HIP events, taken with kmr_tune "dump_timing" only; kmr_build_info) */
 	double last_pairs_ms = 0, last_pairs_parse_ms = 0, last_pairs_sort_ms = 0;      /* the last kmr_identify_pairs*: the whole call, its name parse, its radix sort (HIP events, taken with kmr_tune "pairs_timing" only; kmr_build_info) */
+	double last_dedup_ms = 0, last_dedup_key_ms = 0, last_dedup_sort_ms = 0, last_dedup_consensus_ms = 0;      /* the last kmr_dedup_fragments*: the whole call, its key kernel, its radix sorts, its consensus kernel (HIP events, taken with kmr_tune "dedup_timing" only; kmr_build_info) */
 	uint64_t last_pair_hash_collisions = 0;      /* ... and how many of its runs of equal hash keys held more than one distinct common name */
 	uint64_t last_saturated_keys = 0, last_saturated_batches = 0;      /* what the last kmr_finalize's saturated-key pass redid, in how many batches */
 	bool qual_mixed = false;           /* a build that has seen two different quality characters stops asking (qrange) */
@@ -287,6 +292,15 @@ struct kmr_text {
 	int device = 0;
 	DevBuf text;
 	uint64_t kept = 0, bytes = 0;
+};
+
+/* what kmr_dedup_fragments* leaves on the device: the discard flags, the collapsed groups, the consensus batch and its names */
+struct kmr_dedup {
+	int device = 0;
+	DevBuf disc, group_first, group_size, names;
+	kmr_reads *cons = nullptr;                    /* owned */
+	uint64_t n = 0, n_groups = 0, affected = 0, name_bytes = 0;
+	uint64_t skipped[4] = {0, 0, 0, 0};
 };
 
 /* device-resident read batch produced by kmr_ingest_fastq* */
@@ -2444,6 +2458,7 @@ int kmr_tune(kmr_handle *h, const char *knob, double value) {
 	else if (k == "select_timing") h->tune.select_timing = value != 0;
 	else if (k == "dump_timing") h->tune.dump_timing = value != 0;
 	else if (k == "pairs_timing") h->tune.pairs_timing = value != 0;
+	else if (k == "dedup_timing") h->tune.dedup_timing = value != 0;
 	else if (k == "pair_hash_bits") h->tune.pair_hash_bits = value >= 1 && value < 64 ? (uint32_t)value : 64;
 	else if (k == "dump_piece_bytes") h->tune.dump_piece_bytes = value >= 1 ? (uint64_t)value : 0;
 	else if (k == "narrow_tallies") h->tune.no_narrow = value == 0;
@@ -2478,6 +2493,10 @@ int kmr_build_info(kmr_handle *h, const char *what, double *value) {
 	else if (k == "pairs_parse_ms") *value = h->last_pairs_parse_ms;
 	else if (k == "pairs_sort_ms") *value = h->last_pairs_sort_ms;
 	else if (k == "pair_hash_collisions") *value = (double)h->last_pair_hash_collisions;
+	else if (k == "dedup_ms") *value = h->last_dedup_ms;
+	else if (k == "dedup_key_ms") *value = h->last_dedup_key_ms;
+	else if (k == "dedup_sort_ms") *value = h->last_dedup_sort_ms;
+	else if (k == "dedup_consensus_ms") *value = h->last_dedup_consensus_ms;
 	else if (k == "dump_size_ms") *value = h->last_dump_size_ms;
 	else if (k == "dump_write_ms") *value = h->last_dump_write_ms;
 	else return fail(h, KMR_ERR_INVALID_ARG, "unknown build figure '" + k + "'");
@@ -3813,6 +3832,264 @@ void kmr_pairs_free(kmr_pairs *p) {
 	if (!p) return;
 	hipSetDevice(p->device);
 	delete p;      /* (its buffers are freed on this device) */
+}
+
+/* ---- DuplicateFragmentFilter on the device (kmr_dedup.hpp) ---------------- */
+/* probToQual (src/Sequence.cpp:807-809) steps from i to i + 1 at dedup_qual_steps()[i]: the smallest double p with
+ * (char)(-10. * log10(1.0 - p)) >= i + 1, found by bisection over the bit pattern (the expression is monotone below 0.9999) */
+static char dedup_prob_to_qual(double prob) { return (char)(-10. * std::log10(1.0 - prob)); }
+static const double *dedup_qual_steps() {
+	static double step[DEDUP_QUALS];
+	static std::once_flag once;
+	std::call_once(once, [] {
+		for (int i = 0; i < DEDUP_QUALS; i++) {
+			uint64_t lo = 0, hi; const double top = 0.9999;
+			memcpy(&hi, &top, 8);
+			if (dedup_prob_to_qual(top) < i + 1) { step[i] = top; continue; }      /* never reached: getQualChar answers 40 from there */
+			while (hi - lo > 1) {
+				const uint64_t mid = lo + (hi - lo) / 2; double p; memcpy(&p, &mid, 8);
+				if (dedup_prob_to_qual(p) >= i + 1) hi = mid; else lo = mid;
+			}
+			memcpy(&step[i], &hi, 8);
+		}
+	});
+	return step;
+}
+char kmr_consensus_qual(double prob) {
+	if (prob >= 0.9999) return 40;
+	const double *step = dedup_qual_steps();
+	char q = 0;
+	while (q < DEDUP_QUALS && step[(int)q] <= prob) q++;
+	return q;
+}
+
+int kmr_dedup_config_init(kmr_dedup_config *c) {
+	if (!c) return KMR_ERR_INVALID_ARG;
+	memset(c, 0, sizeof(*c));
+	c->struct_size = (uint32_t)sizeof(kmr_dedup_config);
+	c->dedup_mode = 0; c->paired = 1; c->dedup_length = 24; c->start_offset = 0; c->edit_distance = 0; c->consensus = 1;      /* src/DuplicateFragmentFilter.h:60-61 */
+	return KMR_OK;
+}
+static int dedup_check_config(kmr_handle *h, const kmr_dedup_config *c) {
+	if (!c) return fail(h, KMR_ERR_INVALID_ARG, "kmr_dedup_config: NULL");
+	if (c->struct_size != sizeof(kmr_dedup_config)) return fail(h, KMR_ERR_INVALID_ARG, "kmr_dedup_config: struct_size " + std::to_string(c->struct_size) + " is not " + std::to_string(sizeof(kmr_dedup_config)));
+	if (c->dedup_mode > 2) return fail(h, KMR_ERR_INVALID_ARG, "kmr_dedup_config: dedup_mode must be 0 (off), 1 or 2");
+	if (c->paired > 1) return fail(h, KMR_ERR_INVALID_ARG, "kmr_dedup_config: paired must be 0 or 1");
+	if (c->dedup_length == 0 || c->dedup_length % 4 != 0 || c->start_offset % 4 != 0) return fail(h, KMR_ERR_INVALID_ARG, "kmr_dedup_config: dedup_length and start_offset must be multiples of 4, dedup_length not 0");
+	if (c->edit_distance != 0) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_dedup_config: only dedup-edit-distance 0 is built");
+	if (c->consensus == 0) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_dedup_config: only dedup-consensus 1 is built");
+	if (2 * (uint64_t)c->dedup_length > 128) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_dedup_config: a key holds at most 128 bases (2 * dedup_length)");
+	if ((uint64_t)c->start_offset + 2 * (uint64_t)c->dedup_length > 0x7fffffffull) return fail(h, KMR_ERR_INVALID_ARG, "kmr_dedup_config: start_offset is too large");
+	return 0;
+}
+
+/* the handle's DedupTables, made by the first call */
+static int dedup_tables(kmr_handle *h, const DedupTables **out) {
+	if (!h->dedup_tab) {
+		std::unique_ptr<DedupTables> t(new DedupTables);
+		double P[256]; quality_table(P, h->cfg.min_quality_score, h->cfg.fastq_start_char);
+		for (int q = 0; q < 256; q++) {      /* Read::getProbabilityBases (src/Sequence.cpp:573-576), ProbabilityBase::observe (:871) */
+			double prob = P[q];
+			if (prob < 0.2501) prob = 0.2501;
+			t->prob[q] = prob; t->other[q] = (1.0 - prob) / 3.0;
+		}
+		memcpy(t->step, dedup_qual_steps(), sizeof(t->step));
+		HIPCHK(h, h->dedup_tab.alloc(sizeof(DedupTables)));
+		HIPCHK(h, hipMemcpy(h->dedup_tab.get(), t.get(), sizeof(DedupTables), hipMemcpyHostToDevice));
+	}
+	*out = h->dedup_tab.get<DedupTables>();
+	return 0;
+}
+
+/* dtext and ddisc (may be null): device memory */
+static int dedup_core(kmr_handle *h, const kmr_reads *r, const uint8_t *dtext, uint64_t text_len, const kmr_pairs *pairs, const uint8_t *ddisc, const kmr_dedup_config *cfg, kmr_dedup **out) {
+	const uint64_t n = r->n, np = pairs->n_pairs;
+	std::unique_ptr<kmr_dedup, void (*)(kmr_dedup *)> dd(new kmr_dedup, kmr_dedup_free);
+	dd->device = h->device; dd->n = n;
+	h->last_dedup_ms = h->last_dedup_key_ms = h->last_dedup_sort_ms = h->last_dedup_consensus_ms = 0;
+	const DedupTables *tables; int rc = dedup_tables(h, &tables); if (rc) return rc;
+	uint8_t *disc;
+	HIPCHK(h, alloc_n(dd->disc, &disc, n));
+	EventTimer<7> timer(h->tune.dedup_timing);
+	timer.mark(0, h->stream);
+	if (n) { if (ddisc) HIPCHK(h, hipMemcpyAsync(disc, ddisc, n, hipMemcpyDeviceToDevice, h->stream)); else HIPCHK(h, hipMemsetAsync(disc, 0, n, h->stream)); }
+	DedupParams P;
+	P.bases = r->bases.get<uint8_t>(); P.quals = r->quals.get<uint8_t>(); P.offsets = r->offsets.get<uint64_t>(); P.name_off = r->name_off.get<uint64_t>(); P.name_len = r->name_len.get<uint32_t>();
+	P.text = dtext; P.text_len = text_len; P.n = n; P.total = r->total; P.read1 = pairs->read1.get<int64_t>(); P.read2 = pairs->read2.get<int64_t>(); P.np = np; P.discarded = ddisc;
+	P.paired = cfg->paired ? 1u : 0u; P.mode2 = cfg->dedup_mode == 2 ? 1u : 0u; P.L = cfg->paired ? cfg->dedup_length : 2 * cfg->dedup_length; P.so = cfg->start_offset;
+	P.W = (cfg->dedup_length / 2 + 7) / 8; P.sides = cfg->paired ? 2u : 1u;
+	P.min_q = h->cfg.fastq_start_char + h->cfg.min_quality_score; P.start_char = h->cfg.fastq_start_char;
+	const dim3 block(256);
+	uint64_t totals[DEDUP_T_WORDS] = {0}, c = 0, K = 0;
+	DevBuf b_keys, b_cand, b_flip, b_cscan, b_tot, b_perm, b_perm2, b_kin, b_kout, b_tmp, b_head, b_hscan, b_start, b_keep, b_kscan, b_first, b_first2, b_grp, b_grp2;
+	DevBuf b_len, b_nb, b_nscan, b_members;
+	/* declared behind the temporaries, so it goes first: a return with kernels still in flight waits for them before their buffers go */
+	struct Drain { hipStream_t s; bool armed; ~Drain() { if (armed) hipStreamSynchronize(s); } } drain = {h->stream, true};
+	unsigned long long *keys, *kin, *kout, *first, *first2; uint32_t *cand, *perm = nullptr, *perm2, *head, *keep = nullptr, *grp, *grp2; uint8_t *flip = nullptr; uint64_t *cscan, *tot, *hscan = nullptr, *start = nullptr, *kscan;
+	HIPCHK(h, alloc_n(b_tot, &tot, (size_t)DEDUP_T_WORDS));
+	HIPCHK(h, hipMemsetAsync(tot, 0, 8 * DEDUP_T_WORDS, h->stream));
+	if (n && np && cfg->dedup_mode) {
+		/* candidates and their keys */
+		HIPCHK(h, alloc_n(b_keys, &keys, (size_t)P.W * np)); HIPCHK(h, alloc_n(b_cand, &cand, np)); HIPCHK(h, alloc_n(b_flip, &flip, np)); HIPCHK(h, alloc_n(b_cscan, &cscan, np + 1));
+		hipLaunchKernelGGL(dedup_key_kernel, dim3(grid_for(np)), block, 0, h->stream, P, keys, cand, flip, tot);
+		HIPCHK(h, hipGetLastError());
+		timer.mark(1, h->stream);
+		rc = exclusive_scan(h, cand, np, cscan); if (rc) return rc;
+		/* the first of the call's three fixed-size copies: the number of candidates sizes the sorts */
+		HIPCHK(h, hipMemcpyAsync(&c, cscan + np, 8, hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, hipMemcpyAsync(totals, tot, 8 * DEDUP_T_AFFECTED, hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, hipStreamSynchronize(h->stream));
+	} else timer.mark(1, h->stream);
+	for (int i = 0; i < 4; i++) dd->skipped[i] = totals[i];
+	timer.mark(2, h->stream);
+	if (c >= 2) {
+		const dim3 cgrid(grid_for(c));
+		HIPCHK(h, alloc_n(b_perm, &perm, c)); HIPCHK(h, alloc_n(b_perm2, &perm2, c)); HIPCHK(h, alloc_n(b_kin, &kin, c)); HIPCHK(h, alloc_n(b_kout, &kout, c));
+		hipLaunchKernelGGL(dedup_compact_kernel, dim3(grid_for(np)), block, 0, h->stream, (const uint32_t *)cand, (const uint64_t *)cscan, np, perm);
+		HIPCHK(h, hipGetLastError());
+		size_t tmp_bytes = 0;
+		if (kmr::sort_pairs_u64_u32(nullptr, &tmp_bytes, kin, kout, perm, perm2, c, h->stream) != 0) return fail(h, KMR_ERR_HIP, "kmr_dedup_fragments: radix sort (size query)");
+		HIPCHK(h, b_tmp.alloc(std::max<size_t>(tmp_bytes, 256)));
+		/* least significant word first; the sort is stable, so equal keys keep ascending pair position */
+		for (uint32_t w = P.W; w-- > 0;) {
+			hipLaunchKernelGGL(dedup_gather_kernel, cgrid, block, 0, h->stream, (const unsigned long long *)(keys + (size_t)w * np), (const uint32_t *)perm, c, kin);
+			HIPCHK(h, hipGetLastError());
+			if (kmr::sort_pairs_u64_u32(b_tmp.get(), &tmp_bytes, kin, kout, perm, perm2, c, h->stream) != 0) return fail(h, KMR_ERR_HIP, "kmr_dedup_fragments: radix sort");
+			std::swap(perm, perm2);
+		}
+		timer.mark(3, h->stream);
+		/* groups, and those of two members and more */
+		HIPCHK(h, alloc_n(b_head, &head, c)); HIPCHK(h, alloc_n(b_hscan, &hscan, c + 1)); HIPCHK(h, alloc_n(b_start, &start, c + 1));
+		HIPCHK(h, alloc_n(b_keep, &keep, c)); HIPCHK(h, alloc_n(b_kscan, &kscan, c + 1)); HIPCHK(h, alloc_n(b_first, &first, c)); HIPCHK(h, alloc_n(b_grp, &grp, c));
+		hipLaunchKernelGGL(dedup_heads_kernel, cgrid, block, 0, h->stream, (const unsigned long long *)keys, np, P.W, (const uint32_t *)perm, c, head);
+		HIPCHK(h, hipGetLastError());
+		rc = exclusive_scan(h, head, c, hscan); if (rc) return rc;
+		hipLaunchKernelGGL(dedup_starts_kernel, cgrid, block, 0, h->stream, (const uint32_t *)head, (const uint64_t *)hscan, c, start);
+		hipLaunchKernelGGL(dedup_keep_kernel, cgrid, block, 0, h->stream, (const uint64_t *)hscan, (const uint64_t *)start, c, keep);
+		HIPCHK(h, hipGetLastError());
+		rc = exclusive_scan(h, keep, c, kscan); if (rc) return rc;
+		hipLaunchKernelGGL(dedup_kept_kernel, cgrid, block, 0, h->stream, (const uint32_t *)keep, (const uint64_t *)kscan, (const uint64_t *)start, (const uint32_t *)perm, c, first, grp);
+		HIPCHK(h, hipGetLastError());
+		/* the second: the number of groups sizes everything behind */
+		HIPCHK(h, hipMemcpyAsync(&K, kscan + c, 8, hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, hipStreamSynchronize(h->stream));
+	} else timer.mark(3, h->stream);
+	/* the consensus batch (empty if nothing was collapsed) */
+	const uint64_t n_new = K * P.sides;
+	if (n_new >= 0xffffffffull) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_dedup_fragments: more than 2^32 - 2 consensus reads");
+	dd->cons = new kmr_reads;
+	kmr_reads *cr = dd->cons;
+	cr->device = h->device; cr->n = n_new; cr->input_base = h->cfg.fastq_start_char;
+	uint64_t *coff, *cno, *gfirst; uint32_t *cnl, *gsize;
+	HIPCHK(h, alloc_n(cr->offsets, &coff, n_new + 1)); HIPCHK(h, alloc_n(cr->name_off, &cno, std::max<uint64_t>(n_new, 1))); HIPCHK(h, alloc_n(cr->name_len, &cnl, std::max<uint64_t>(n_new, 1)));
+	HIPCHK(h, alloc_n(dd->group_first, &gfirst, std::max<uint64_t>(K, 1))); HIPCHK(h, alloc_n(dd->group_size, &gsize, std::max<uint64_t>(K, 1)));
+	uint64_t name_total = 0;
+	timer.mark(4, h->stream);
+	if (K) {
+		/* output order: ascending position of the first member */
+		HIPCHK(h, alloc_n(b_first2, &first2, K)); HIPCHK(h, alloc_n(b_grp2, &grp2, K));
+		size_t tmp_bytes = 0;
+		if (kmr::sort_pairs_u64_u32(nullptr, &tmp_bytes, first, first2, grp, grp2, K, h->stream) != 0) return fail(h, KMR_ERR_HIP, "kmr_dedup_fragments: radix sort (size query)");
+		if (b_tmp.cap() < tmp_bytes) { HIPCHK(h, hipStreamSynchronize(h->stream)); HIPCHK(h, b_tmp.alloc(tmp_bytes)); }
+		if (kmr::sort_pairs_u64_u32(b_tmp.get(), &tmp_bytes, first, first2, grp, grp2, K, h->stream) != 0) return fail(h, KMR_ERR_HIP, "kmr_dedup_fragments: radix sort");
+		DedupGroups G; G.perm = perm; G.flip = flip; G.start = start; G.ogroup = grp2; G.K = K;
+		uint32_t *len, *nb; uint64_t *nscan; DedupMember *members;
+		HIPCHK(h, alloc_n(b_len, &len, n_new)); HIPCHK(h, alloc_n(b_nb, &nb, n_new)); HIPCHK(h, alloc_n(b_nscan, &nscan, n_new + 1)); HIPCHK(h, alloc_n(b_members, &members, (size_t)c * P.sides));
+		hipLaunchKernelGGL(dedup_size_kernel, dim3(grid_for(n_new)), block, 0, h->stream, P, G, len, nb, gfirst, gsize, tot);
+		HIPCHK(h, hipGetLastError());
+		rc = exclusive_scan(h, len, n_new, coff); if (rc) return rc;
+		rc = exclusive_scan(h, nb, n_new, nscan); if (rc) return rc;
+		/* the third: the bases and name bytes of the batch, what was collapsed, the error word */
+		HIPCHK(h, hipMemcpyAsync(&cr->total, coff + n_new, 8, hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, hipMemcpyAsync(&name_total, nscan + n_new, 8, hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, hipMemcpyAsync(&totals[DEDUP_T_AFFECTED], tot + DEDUP_T_AFFECTED, 16, hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, hipStreamSynchronize(h->stream));
+		if (totals[DEDUP_T_ERR] & DEDUP_ERR_NAME) return fail(h, KMR_ERR_INVALID_ARG, "a read's name span lies outside the text handed in (pass the text the batch was ingested from)");
+		uint8_t *cb, *cq, *names;
+		HIPCHK(h, alloc_n(cr->bases, &cb, cr->total + 64)); HIPCHK(h, alloc_n(cr->quals, &cq, cr->total + 64)); HIPCHK(h, alloc_n(dd->names, &names, name_total));
+		HIPCHK(h, hipMemsetAsync(cb + cr->total, 0, 64, h->stream)); HIPCHK(h, hipMemsetAsync(cq + cr->total, 0, 64, h->stream));
+		timer.mark(4, h->stream);
+		hipLaunchKernelGGL(dedup_consensus_kernel, dim3((unsigned)std::min<uint64_t>((n_new + DEDUP_WAVES - 1) / DEDUP_WAVES, (uint64_t)num_cus(h) * 8)), dim3(DEDUP_THREADS), 0, h->stream,
+		                   P, G, tables, (const uint64_t *)coff, (const uint64_t *)nscan, members, cb, cq, names, cno, cnl);
+		HIPCHK(h, hipGetLastError());
+		timer.mark(5, h->stream);
+		hipLaunchKernelGGL(dedup_discard_kernel, dim3(grid_for(c)), block, 0, h->stream, P, (const uint32_t *)perm, (const uint64_t *)hscan, (const uint32_t *)keep, c, disc);
+		HIPCHK(h, hipGetLastError());
+		timer.mark(6, h->stream);
+		HIPCHK(h, hipStreamSynchronize(h->stream));      /* the temporaries above go */
+	} else {
+		uint8_t *cb, *cq;
+		HIPCHK(h, alloc_n(cr->bases, &cb, (size_t)64)); HIPCHK(h, alloc_n(cr->quals, &cq, (size_t)64));
+		HIPCHK(h, hipMemsetAsync(cb, 0, 64, h->stream)); HIPCHK(h, hipMemsetAsync(cq, 0, 64, h->stream)); HIPCHK(h, hipMemsetAsync(coff, 0, 8, h->stream));
+		timer.mark(5, h->stream); timer.mark(6, h->stream);
+		HIPCHK(h, hipStreamSynchronize(h->stream));
+	}
+	dd->n_groups = K; dd->affected = totals[DEDUP_T_AFFECTED]; dd->name_bytes = name_total;
+	h->last_dedup_ms = timer.ms(0, 6); h->last_dedup_key_ms = timer.ms(0, 1); h->last_dedup_sort_ms = c >= 2 ? timer.ms(2, 3) : 0.0; h->last_dedup_consensus_ms = K ? timer.ms(4, 5) : 0.0;
+	drain.armed = false;      /* (waited for above) */
+	*out = dd.release();
+	return KMR_OK;
+}
+
+static int dedup_any(kmr_handle *h, const kmr_reads *r, const void *text, uint64_t text_len, bool text_on_device, const kmr_pairs *pairs, const uint8_t *discarded, const kmr_dedup_config *cfg, kmr_dedup **out) {
+	if (out) *out = nullptr;
+	int rc = dedup_check_config(h, cfg); if (rc) return rc;
+	if (!h || !r || !pairs || !out || (text_len && !text)) return fail(h, KMR_ERR_INVALID_ARG, "kmr_dedup_fragments: NULL argument");
+	if (r->device != h->device || pairs->device != h->device) return fail(h, KMR_ERR_INVALID_ARG, "read batch or pair list lives on another device");
+	if (pairs->n != r->n) return fail(h, KMR_ERR_INVALID_ARG, "kmr_dedup_fragments: the pair list belongs to a batch of " + std::to_string(pairs->n) + " reads, not " + std::to_string(r->n));
+	if (r->n >= 0xffffffffull) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_dedup_fragments: a batch holds fewer than 2^32 - 1 reads (pair positions of the sort are 32-bit)");
+	hipSetDevice(h->device);
+	DevBuf b_text, b_disc;
+	const uint8_t *dtext = (const uint8_t *)text, *ddisc = nullptr;
+	if (!text_on_device) { rc = select_upload(h, b_text, (const uint8_t *)text, r->n ? text_len : 0, &dtext); if (rc) return rc; }
+	rc = select_upload(h, b_disc, discarded, r->n, &ddisc); if (rc) return rc;
+	rc = dedup_core(h, r, dtext, text_len, pairs, ddisc, cfg, out);
+	if (rc) hipStreamSynchronize(h->stream);      /* the uploads above must have landed before their buffers go */
+	return rc;
+}
+int kmr_dedup_fragments(kmr_handle *h, const kmr_reads *reads, const char *text, uint64_t text_len, const kmr_pairs *pairs, const uint8_t *discarded, const kmr_dedup_config *cfg, kmr_dedup **out) {
+	return dedup_any(h, reads, text, text_len, false, pairs, discarded, cfg, out);
+}
+int kmr_dedup_fragments_dev(kmr_handle *h, const kmr_reads *reads, const void *dev_text, uint64_t text_len, const kmr_pairs *pairs, const uint8_t *discarded, const kmr_dedup_config *cfg, kmr_dedup **out) {
+	return dedup_any(h, reads, dev_text, text_len, true, pairs, discarded, cfg, out);
+}
+int kmr_dedup_info(const kmr_dedup *d, uint64_t *n_groups, uint64_t *n_new_reads, uint64_t *affected, uint64_t skipped[4]) {
+	if (!d) return KMR_ERR_INVALID_ARG;
+	if (n_groups) *n_groups = d->n_groups; if (n_new_reads) *n_new_reads = d->cons ? d->cons->n : 0; if (affected) *affected = d->affected;
+	if (skipped) for (int i = 0; i < 4; i++) skipped[i] = d->skipped[i];
+	return KMR_OK;
+}
+int kmr_dedup_copy(const kmr_dedup *d, uint8_t *discarded_out, uint64_t *group_first, uint32_t *group_size) {
+	if (!d) return KMR_ERR_INVALID_ARG;
+	hipSetDevice(d->device);
+	hipError_t e = hipSuccess;
+	if (discarded_out && d->n) e = hipMemcpy(discarded_out, d->disc.get<uint8_t>(), d->n, hipMemcpyDeviceToHost);
+	if (group_first && d->n_groups && e == hipSuccess) e = hipMemcpy(group_first, d->group_first.get<uint64_t>(), 8 * d->n_groups, hipMemcpyDeviceToHost);
+	if (group_size && d->n_groups && e == hipSuccess) e = hipMemcpy(group_size, d->group_size.get<uint32_t>(), 4 * d->n_groups, hipMemcpyDeviceToHost);
+	return e == hipSuccess ? KMR_OK : KMR_ERR_HIP;
+}
+int kmr_dedup_device_ptrs(const kmr_dedup *d, void **dev_discarded, void **dev_group_first, void **dev_group_size) {
+	if (!d) return KMR_ERR_INVALID_ARG;
+	if (dev_discarded) *dev_discarded = d->disc.get<uint8_t>(); if (dev_group_first) *dev_group_first = d->group_first.get<uint64_t>(); if (dev_group_size) *dev_group_size = d->group_size.get<uint32_t>();
+	return KMR_OK;
+}
+int kmr_dedup_reads(const kmr_dedup *d, const kmr_reads **consensus, const void **dev_name_text, uint64_t *name_text_len) {
+	if (!d) return KMR_ERR_INVALID_ARG;
+	if (consensus) *consensus = d->cons; if (dev_name_text) *dev_name_text = d->names.get<uint8_t>(); if (name_text_len) *name_text_len = d->name_bytes;
+	return KMR_OK;
+}
+int kmr_dedup_names_copy(const kmr_dedup *d, char *dst, uint64_t capacity) {
+	if (!d || (d->name_bytes && !dst)) return KMR_ERR_INVALID_ARG;
+	if (capacity < d->name_bytes) return KMR_ERR_CAPACITY;
+	hipSetDevice(d->device);
+	if (d->name_bytes && hipMemcpy(dst, d->names.get<uint8_t>(), d->name_bytes, hipMemcpyDeviceToHost) != hipSuccess) return KMR_ERR_HIP;
+	return KMR_OK;
+}
+void kmr_dedup_free(kmr_dedup *d) {
+	if (!d) return;
+	hipSetDevice(d->device);
+	delete d->cons;
+	delete d;      /* (its buffers are freed on this device) */
 }
 
 /* ---- a14: the mercount / mergraph text on the device (kmr_dump.hpp) ---------- */

@@ -998,6 +998,139 @@ class ReadSelector:
             pass
 
 
+class ConsensusReadSet(ReadSet):
+    """The consensus reads of one duplicate-fragment pass: a ReadSet whose names point into a name text of its own.  The batch
+    belongs to the DedupPass it came from and lives until that is closed."""
+
+    @classmethod
+    def _borrow(cls, owner, spectrum, name_text, handle):
+        self = cls._adopt(spectrum, name_text, handle, True)
+        self._owner = owner
+        return self
+
+    def close(self):
+        self.r = None          # the DedupPass frees it
+
+
+class DedupPass:
+    """What one kmr_dedup_fragments* call left (kmr_dedup), kept on the device until close(): .discarded (uint8 per read: the
+    flags handed in OR the new discards), .affected, .skipped = (discarded, too short, unpaired, invalid), .groups = (n_groups, 2)
+    int64 array of (pair-list position of the first member, member count), .consensus = the new reads as a ConsensusReadSet,
+    .consensus_mate = the mate of each of them (2g <-> 2g + 1 in the paired pass, -1 in the single pass); .single = the
+    --dedup-single pass that followed, or None."""
+
+    def __init__(self, sp, handle, paired, n_reads):
+        self.sp, self._d, self.paired, self.single, self.n_reads = sp, handle, bool(paired), None, n_reads
+        ng, nn, af = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        sk = (C.c_uint64 * 4)()
+        rc = sp.lib.kmr_dedup_info(handle, C.byref(ng), C.byref(nn), C.byref(af), sk)
+        if rc != 0:
+            raise KmerSpectrumError("kmr_dedup_info: %s" % _lib.STATUS.get(rc, rc))
+        self.n_groups, self.n_new_reads, self.affected, self.skipped = ng.value, nn.value, af.value, tuple(int(v) for v in sk)
+        r, nt, nl = C.c_void_p(), C.c_void_p(), C.c_uint64()
+        sp.lib.kmr_dedup_reads(handle, C.byref(r), C.byref(nt), C.byref(nl))
+        names = np.zeros(max(1, nl.value), dtype=np.uint8)
+        rc = sp.lib.kmr_dedup_names_copy(handle, names.ctypes.data_as(C.c_void_p), nl.value)
+        if rc != 0:
+            raise KmerSpectrumError("kmr_dedup_names_copy: %s" % _lib.STATUS.get(rc, rc))
+        self.device_name_text = (nt.value or 0, nl.value)
+        self.consensus = ConsensusReadSet._borrow(self, sp, names[:nl.value].tobytes(), r)
+        m = np.arange(self.n_new_reads, dtype=np.int64)
+        self.consensus_mate = (m ^ 1) if self.paired else np.full(self.n_new_reads, -1, dtype=np.int64)
+        self._host = None
+
+    def _live(self):
+        if not self._d:
+            raise KmerSpectrumError("DedupPass: closed")
+        return self._d
+
+    def _copy(self):
+        if self._host is None:
+            disc = np.zeros(max(1, self.n_reads), dtype=np.uint8)
+            gf = np.zeros(max(1, self.n_groups), dtype=np.uint64)
+            gs = np.zeros(max(1, self.n_groups), dtype=np.uint32)
+            rc = self.sp.lib.kmr_dedup_copy(self._live(), disc.ctypes.data_as(C.POINTER(C.c_uint8)), gf.ctypes.data_as(C.POINTER(C.c_uint64)), gs.ctypes.data_as(C.POINTER(C.c_uint32)))
+            if rc != 0:
+                raise KmerSpectrumError("kmr_dedup_copy: %s" % _lib.STATUS.get(rc, rc))
+            self._host = (disc[:self.n_reads], np.stack([gf[:self.n_groups].astype(np.int64), gs[:self.n_groups].astype(np.int64)], axis=1))
+        return self._host
+
+    @property
+    def discarded(self):
+        return self._copy()[0]
+
+    @property
+    def groups(self):
+        return self._copy()[1]
+
+    def device_ptrs(self):
+        """device pointers of (discarded[n_reads] uint8, group_first[n_groups] uint64, group_size[n_groups] uint32); valid until close()"""
+        a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        rc = self.sp.lib.kmr_dedup_device_ptrs(self._live(), C.byref(a), C.byref(b), C.byref(c))
+        if rc != 0:
+            raise KmerSpectrumError("kmr_dedup_device_ptrs: %s" % _lib.STATUS.get(rc, rc))
+        return a.value or 0, b.value or 0, c.value or 0
+
+    def close(self):
+        if self.single is not None:
+            self.single.close()
+        if getattr(self, "_d", None):
+            self.consensus.r = None
+            self.sp.lib.kmr_dedup_free(self._d)
+            self._d = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DuplicateFragmentFilter:
+    """DuplicateFragmentFilter::filterDuplicateFragments (src/DuplicateFragmentFilter.h:561-620) with edit distance 0 and consensus
+    on, over a device-resident ReadSet and the ReadPairs identifyPairs found for it (kmr_dedup_fragments): fragments whose first
+    dedup_length bases of both reads (from start_offset) agree collapse to consensus reads; dedup_mode 2 also folds a fragment read
+    from the other strand (B, A) onto (A, B)."""
+
+    def __init__(self, spectrum, dedup_mode=1, dedup_length=24, start_offset=0):
+        self.sp = spectrum
+        cfg = _lib.KmrDedupConfig()
+        spectrum.lib.kmr_dedup_config_init(C.byref(cfg))
+        cfg.dedup_mode, cfg.dedup_length, cfg.start_offset = int(dedup_mode), int(dedup_length), int(start_offset)
+        self.cfg = cfg
+
+    def _pass(self, read_set, pairs, discarded, paired, device_text):
+        cfg = _lib.KmrDedupConfig.from_buffer_copy(self.cfg)
+        cfg.paired = 1 if paired else 0
+        d = None
+        if discarded is not None:
+            d = np.ascontiguousarray(np.asarray(discarded) != 0, dtype=np.uint8)
+            assert d.size == read_set.n
+        dp = None if d is None or d.size == 0 else d.ctypes.data_as(C.POINTER(C.c_uint8))
+        out = C.c_void_p()
+        if device_text is not None:
+            self.sp._call("dedup_fragments_dev", self.sp.h, read_set.r, C.c_void_p(device_text), len(read_set.text), pairs._live(), dp, C.byref(cfg), C.byref(out))
+        else:
+            buf = np.frombuffer(read_set.text, dtype=np.uint8)
+            self.sp._call("dedup_fragments", self.sp.h, read_set.r, buf.ctypes.data_as(C.c_void_p) if buf.size else None, buf.size, pairs._live(), dp, C.byref(cfg), C.byref(out))
+        return DedupPass(self.sp, out, paired, read_set.n)
+
+    def filterDuplicateFragments(self, read_set, pairs, discarded=None, dedup_single=False, device_text=None):
+        """The paired pass and, with dedup_single, the pass over single reads behind it (:587-616), which is given the first pass's
+        discards.  `discarded` = per read, non-zero = discarded (FilterKnownOddities' action == 2); `device_text` = device pointer
+        of the FASTQ text if the caller holds it there.  Returns the paired pass's DedupPass, the single pass as its .single."""
+        res = self._pass(read_set, pairs, discarded, True, device_text)
+        if dedup_single:
+            res.single = self._pass(read_set, pairs, res.discarded, False, device_text)
+        return res
+
+
 def synth_reads_device(torch, seed, first_read, n_reads, read_len, genome_len, noisy, device):
     """kmr_synth_reads_dev into torch tensors on `device`: (bases u8, quals u8, offsets i64).  The buffers carry 64 spare bytes behind
     the last read, as the device entry points of the build ask for."""
