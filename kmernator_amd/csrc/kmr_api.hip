@@ -1,5 +1,6 @@
 /*
- * kmr_api.hip -- C-ABI of include/kmernator_amd.h on top of the HIP kernels.
+ * kmr_api.hip -- C-ABI of include/kmernator_amd.h on top of the HIP kernels: the spectrum (the read stages -- ingest, artifact
+ * filter, selection, pairs, duplicate fragments, dump text -- are kmr_stages.hip; kmr_host.hpp is what the two share).
  *
  * Host logic only: handle life cycle, device memory, launches on the handle's
  * stream, growth of the device table, finalize (bucket histogram -> scan ->
@@ -29,15 +30,9 @@
 #include <type_traits>
 #include <vector>
 
-#include "../../include/kmernator_amd.h"
+#include "kmr_host.hpp"
 #include "kmr_kernels.hpp"
 #include "kmr_partition.hpp"
-#include "kmr_ingest.hpp"
-#include "kmr_artifact.hpp"
-#include "kmr_select.hpp"
-#include "kmr_pairs.hpp"
-#include "kmr_dedup.hpp"
-#include "kmr_dump.hpp"
 #include "kmr_superkmer.hpp"
 #include "kmr_buckets.hpp"
 #include "kmr_synth.hpp"
@@ -48,290 +43,6 @@ using namespace kmr;
 
 namespace {
 
-std::string g_create_error;
-
-/* Every device allocation of the library goes through dev_malloc.  An allocation that fails for lack of memory although the card
- * as a whole could hold it is tried again for a bounded time (memory another handle or torch has just freed is handed back by the
- * driver with a delay, and work still running on other streams may hold what it is about to free); what was asked for and what the
- * device had is kept for the error text (oom_note), so that a KMR_ERR_OOM says how far off it was. */
-thread_local char g_oom_note[160] = "";
-std::atomic<long long> g_blocks_live{0};      /* blocks dev_malloc has handed out and DevBuf has not freed (kmr_build_info "device_blocks_live") */
-hipError_t dev_malloc(void **p, size_t bytes) {
-	hipError_t e = hipMalloc(p, bytes);
-	if (e == hipSuccess) { if (*p) g_blocks_live++; return e; }      /* (a 0-byte request may succeed with no block) */
-	if (e != hipErrorOutOfMemory) return e;
-	size_t fr = 0, tot = 0;
-	for (int attempt = 0; attempt < 6; attempt++) {
-		(void)hipGetLastError();
-		hipDeviceSynchronize();
-		if (hipMemGetInfo(&fr, &tot) != hipSuccess || bytes > tot) break;
-		usleep(20000u << attempt);      /* 20 ms ... 640 ms: 1.3 s at most */
-		e = hipMalloc(p, bytes);
-		if (e == hipSuccess && *p) g_blocks_live++;
-		if (e != hipErrorOutOfMemory) return e;
-	}
-	(void)hipGetLastError();
-	hipMemGetInfo(&fr, &tot);
-	snprintf(g_oom_note, sizeof(g_oom_note), " [requested %.3f GB; device has %.3f GB free of %.3f GB]", bytes / 1e9, fr / 1e9, tot / 1e9);
-	*p = nullptr;
-	return hipErrorOutOfMemory;
-}
-
-/* One block of device memory and its size in bytes, freed when the owner goes: every device allocation of the library is one.
- * Kernels take get<T>(); alloc() replaces the block by one of exactly `bytes`, reserve() (below kmr_handle) grows it only. */
-class DevBuf {
-public:
-	DevBuf() = default;
-	DevBuf(DevBuf &&o) noexcept : p_(o.p_), cap_(o.cap_) { o.p_ = nullptr; o.cap_ = 0; }
-	DevBuf &operator=(DevBuf &&o) noexcept { if (this != &o) { reset(); std::swap(p_, o.p_); std::swap(cap_, o.cap_); } return *this; }
-	~DevBuf() { reset(); }
-	void reset() { if (p_) { hipFree(p_); g_blocks_live--; } p_ = nullptr; cap_ = 0; }
-	hipError_t alloc(size_t bytes) {      /* empty on failure */
-		reset();
-		void *p = nullptr;
-		const hipError_t e = dev_malloc(&p, bytes);
-		if (e == hipSuccess) { p_ = p; cap_ = bytes; }
-		return e;
-	}
-	/* grow-only: a block of `bytes` (default: need) unless the one held has `need`; drains the handle's stream before freeing it.
-	 * A failure sets the handle's error text, naming the buffer (`what`). */
-	int reserve(kmr_handle *h, const char *what, size_t need, size_t bytes = 0);
-	template <class T = void> T *get() const { return (T *)p_; }
-	size_t cap() const { return cap_; }
-	explicit operator bool() const { return p_ != nullptr; }
-private:
-	void *p_ = nullptr;
-	size_t cap_ = 0;
-};
-
-struct DevMap {                      /* a finalized map resident in HBM */
-	uint64_t nb = 0, n = 0;
-	DevBuf start;                    /* [nb+1] */
-	DevBuf keys;                     /* [n][W] */
-	DevBuf vals;                     /* weak: [n][vw] */
-	DevBuf sweight;                  /* singleton */
-	DevBuf spkt;                     /* singleton, EXT */
-	DevBuf image;                    /* reference layout, built lazily */
-	bool present = false;
-};
-
-struct HostPool {                    /* owner of one chunk pool */
-	DevBuf base, chunk_list, chunk_count, head;
-	uint32_t cap = 0; size_t chunk_bytes = 0;
-	uint64_t used_ub = 0;            /* host-side upper bound of chunks handed out */
-	uint64_t presize = 0;            /* chunks the next allocation takes beyond what is asked for (a job fed in many calls, see sk_add_reads) */
-};
-
-/* The handle's device memory, grouped by when it is given back: */
-struct HandleMem {                   /* ... by kmr_destroy */
-	DevBuf slots, extslots;          /* device table */
-	DevBuf dP, dstats, derr;
-	DevMap weak, sing;
-	/* streaming lookups (sk_index_* / sk_lookup_kernel): the weak map's entries grouped by minimizer list, of map generation ix_gen */
-	DevBuf ix_start, ix_keys, ix_counts;
-	DevBuf scratch_stats;
-	DevBuf adopt_buf;                /* kmr_sk_exchange_adopt_dev's scan */
-	DevBuf trk;                      /* size tracker: one record per read of the last call */
-	DevBuf scan_sums;
-	DevBuf score_buf;                /* temporaries of kmr_score_reads*, grow-only */
-	DevBuf lut;                      /* lookup accelerator over the weak map (LutView) */
-	DevBuf dPk;                      /* build_mode 3: table of k-fold quality products */
-	DevBuf d_uni;                    /* uniform-weight flags of adopted records */
-	DevBuf qrange;                   /* sk_qual_range_kernel's answer */
-	DevBuf sk_fine_state;            /* fine list state of an exchange (2^(sk_bits + sk_fine_shift) words) */
-	/* an exchange in steps over the list space (kmr_sk_exchange_range) and the lists below `hi` counted early (kmr_count_lists_prefix):
-	 * their entries wait in buffers of their own until kmr_finalize has counted the rest */
-	struct Early { bool active = false; uint64_t hi = 0; uint32_t min_depth = 0; DevBuf ue, cursor, fc, err; } early;      /* err: the early pass's own error word, read by kmr_finalize alone */
-	DevBuf dedup_tab;                /* kmr_dedup_fragments*: the probability and quality-step tables (DedupTables), made by the first call */
-	DevBuf xo_dev;                   /* kmr_extract_by_owner_host: owner segments of one batch kept on the device between the sizing call and the copy-out */
-};
-struct BuildMem {                    /* ... by kmr_release_table too: the streaming build's state */
-	DevBuf sk_state;                 /* build_mode 3 (kmr_superkmer.hpp): list words */
-	HostPool l1;                     /* the record pool of every partition level */
-	DevBuf work_counter;
-	DevBuf l1_state; bool l1_state_dirty = false;      /* see PartSource::state */
-	/* temporaries of kmr_finalize (chunk CSRs, work items, counters): one grow-only block handed out by bumping a
-	 * cursor, so a finalize neither allocates nor frees device memory once the handle has seen one build */
-	DevBuf arena; size_t arena_used = 0, arena_want = 0; std::vector<DevBuf> arena_overflow;
-	DevBuf linear;                   /* records */
-	DevBuf tile_count, kcap, koff;
-	/* work units of batches that contain reads longer than one tile */
-	DevBuf ucnt, ufirst, u_start, u_end, u_read, umax;
-	/* kmr_add_reads_twobit*: the unpacked batch (ASCII bases, one quality character throughout, offsets counted from the call's first read) */
-	DevBuf tb_bases, tb_quals, tb_rel, tb_off, tb_len;
-	uint64_t tb_quals_filled = 0; int tb_quals_char = -1;
-	DevBuf tb_stage[2][8];           /* kmr_add_reads_twobit: two sets of staging buffers for the pieces on the bus */
-	DevBuf uw_keys, uw_vals, us_keys, us_b8, us_pkt;
-	/* build_mode 3: the count pass's weak entries packed (kmr_buckets.hpp: W key words + one value word), and the radix partition's scratch of the same layout */
-	DevBuf ue, ue2;
-};
-struct ExchangeMem {                 /* ... after the communicator that uses it (kmr_exchange_rccl.hpp): gather scratch, grow-only send / receive buffers */
-	DevBuf xc_small, xc_dcounts;
-	DevBuf xc_send, xc_send2, xc_recv, xc_recv2;
-};
-
-}  // namespace
-
-/* per-handle knobs of kmr_tune(): sizes the tests shrink to reach the multi-level / retry / sub-batch code with small inputs, and
- * switches the measurement tools flip.  None of them changes a result. */
-struct Tuning {
-	uint64_t target_list = 2048;      /* records per final list the partition bits aim for */
-	uint64_t sub_batch_bases = 0;     /* 0 = SUB_BATCH_BASES */
-	int recycle = -1;                 /* -1 auto, 0 fresh chunks, 1 recycle the chunks a pass has just read */
-	int part_blocks = 0;              /* 0 = one partition block per CU */
-	double entry_share = -1.0;        /* >= 0: initial size of the count pass's entry buffers as a share of the records */
-	double early_entry_share = -1.0;  /* >= 0: size of kmr_count_lists_prefix's entry buffers as a share of the good k-mers (no CU slack) */
-	uint64_t saturated_batch_bytes = 0;      /* scratch budget of one batch of the saturated-key pass (0: SAT_BATCH_BYTES) */
-	bool no_lut = false, no_narrow = false, no_l1_state = false, no_stream_lookups = false;
-	uint64_t long_list_chunks = 0;     /* lists of more chunks are counted in pieces (0: 1024) */
-	uint64_t binned_min = 1ull << 18;  /* weak maps of at least this many entries are bucketed by the radix partition of kmr_buckets.hpp (build_mode 3) */
-	uint64_t twobit_piece_bases = 0;   /* kmr_add_reads_twobit: bases per piece of the host-to-device pipeline (0 = 2^26) */
-	uint64_t list_aim = 0;             /* k-mers per list the list count of a single GPU's build aims for (0: the defaults of add_reads_superkmer_t) */
-	bool pow2_lists = false;           /* the list count of build_mode 3 always a power of two (A/B runs, tests of both list functions) */
-	bool no_packed_direct = false;     /* kmr_add_reads_twobit* always unpack to text first (A/B runs, tests of the unpack path) */
-	bool no_uniform_count = false;     /* never take sk_count_kernel<.., UNI> (A/B runs, tests of the general count pass on one-weight builds) */
-	bool no_lean_extract = false;      /* never take sk_extract_lean_kernel (A/B runs, tests of the general kernel on uniform qualities) */
-	bool exchange_fail_once = false;   /* tests: the next kmr_exchange_add_reads_dev of this rank fails locally (the other ranks must come back with an error, not hang) */
-	uint64_t dump_piece_bytes = 0;     /* kmr_dump_mercount / kmr_dump_mergraph: staging bound of one piece of the file (0 = KMR_DUMP_PIECE_BYTES) */
-	bool dump_timing = false;          /* kmr_dump_text*: time the size pass and the writer with HIP events (kmr_build_info; measurement tools) */
-	bool select_timing = false;        /* kmr_select_* / kmr_filter_*: time scoring, selection and writer with HIP events (kmr_build_info; measurement tools) */
-	bool pairs_timing = false;         /* kmr_identify_pairs*: time the name parse, the sort and the whole call with HIP events (kmr_build_info; measurement tools) */
-	bool dedup_timing = false;         /* kmr_dedup_fragments*: time the key kernel, the sorts, the consensus kernel and the whole call with HIP events (kmr_build_info; measurement tools) */
-	uint32_t pair_hash_bits = 64;      /* kmr_identify_pairs*: bits of the common name's hash the phase-2 sort keys keep (tests: a few bits, so that distinct names share a key) */
-	bool no_coarse_lists = true;       /* exchange: scatter into the job's fine lists (default) or, kmr_tune("coarse_lists", 1), into coarse ones that the owner splits before the count pass (sk_refine_kernel: not yet fast enough to pay) */
-};
-
-struct kmr_handle : HandleMem, BuildMem, ExchangeMem {
-	kmr_config cfg;
-	Tuning tune;
-	uint32_t k = 0, kb = 0, hkb = 0, W = 0;
-	bool ext = false;
-	int device = 0, ncu = 0;
-	hipStream_t stream = nullptr;
-	std::string err;
-	/* device table */
-	uint32_t log2cap = 0;
-	uint64_t occupied = 0;           /* exact as of the last sync */
-	uint64_t pending_kmers = 0;      /* upper bound of keys added since */
-	uint64_t stream_base = 0, reads = 0;
-	uint64_t nb_weak = 0, nb_sing = 0;
-	bool finalized = false, has_singletons = true;
-	kmr_handle *subtract = nullptr;    /* finalized spectrum whose k-mers are skipped (kmr_subtract_reference) */
-	uint64_t subtracted = 0;
-	kmr_stats stats;
-	/* streaming (partition) build path */
-	bool partition_mode = false;
-	bool superkmer_mode = false;       /* build_mode 3: super-k-mer lists (kmr_superkmer.hpp); implies partition_mode */
-	uint64_t ix_lists = 0, ix_gen = ~0ull;      /* the streaming lookups' index (ix_*): its list count and map generation */
-	/* size tracker (kmr_config.size_tracker): records of the reads fed by the last call (trk), and the elements made of them at kmr_finalize */
-	uint64_t trk_n = 0; std::vector<uint64_t> trk_elems;
-	/* the thresholds passed so far (SizeTracker::nextToTrack and the elements' first two counters), found call by call while the
-	 * reads are still at hand: the stream ordinal behind the k-mer at which rawKmers reached the threshold, rawKmers, rawGoodKmers */
-	long trk_next = 128; uint64_t trk_raw = 0, trk_good = 0; std::vector<unsigned long long> trk_bounds; std::vector<uint64_t> trk_snap_raw, trk_snap_good;
-	bool sk_fast_div = false;          /* see kmr_create: the chain's divide as multiply-and-correct */
-	bool sender_launch = false;        /* extract_by_owner_t, build (not request) mode: dev_params tells the kernel to count what it does not send */
-	bool sk_exchange = false;          /* kmr_sk_exchange_begin: the lists are the whole job's, every owner's k-mers are kept until the exchange */
-	bool auto_mode = false;            /* build_mode 0: a handle that is fed k-mer records (the owner exchange) before any reads falls back to mode 2 */
-	int bits1 = 0;
-	uint64_t inserted_records = 0;     /* records fed through kmr_insert_records_dev (counted on the host) */
-	uint64_t call_bases_hint = 0;      /* a host batch goes to the device in pieces: the bases of the WHOLE call, for what the first piece sizes (lists, chunk pool) */
-	uint32_t lut_log2 = 0;
-	uint64_t lut_gen = ~0ull, map_gen = 0;                           /* the lookup table belongs to the maps of generation lut_gen */
-	hipStream_t tb_copy_stream = nullptr; hipEvent_t tb_ready[2] = {nullptr, nullptr}, tb_consumed[2] = {nullptr, nullptr}; bool tb_set_used[2] = {false, false};
-	const SkPacked *packed_direct = nullptr;      /* set while kmr_add_reads_twobit_dev feeds a batch that sk_extract_lean_kernel<.., PACKED> takes as it is */
-	int uniform_q_hint = -1;           /* >= 0 while kmr_add_reads_twobit_dev feeds a batch whose qualities are this one character */
-	/* build_mode 3 (kmr_superkmer.hpp): list count and minimizer geometry */
-	uint32_t sk_bits = 0, sk_m = 0, sk_off = 0, sk_win = 0;
-	double hP[256], hPk[256];              /* host copies of the probability table and of its k-fold products */
-	/* does every record of the lists carry ONE weight (all calls went through the lean extraction with the same quality character)?  The
-	 * host knows for its own calls (sk_uni_w: SK_UNI_NONE before the first; sk_uni_mixed), a device pair collects it for adopted records (d_uni) */
-	uint32_t sk_uni_w = 0xffffffffu; bool sk_uni_mixed = false; bool last_count_uniform = false;
-	/* ... or the senders say so themselves (kmr_sk_exchange_peer_uniform): then nothing is looked at on arrival */
-	uint32_t peer_uni_w = 0xffffffffu; bool peer_uni_mixed = false, peers_declare = false;
-	uint64_t xr_lo = 0, xr_hi = ~0ull;      /* kmr_sk_exchange_range */
-	uint64_t last_early_hi = 0, last_early_entries = 0;      /* what the last kmr_finalize took over from an early count (kmr_build_info) */
-	bool last_early_overflowed = false;                       /* ... or that it voided one because its buffers overflowed */
-	double last_score_ms = 0, last_select_ms = 0, last_write_ms = 0;      /* the last kmr_filter_read_batch* / kmr_select_reads*: scoring, selection + writer, writer alone (HIP events, taken with kmr_tune "select_timing" only; kmr_build_info) */
-	double last_dump_size_ms = 0, last_dump_write_ms = 0;      /* the last kmr_dump_text_size / kmr_dump_text: size pass with its scan, writer (HIP events, taken with kmr_tune "dump_timing" only; kmr_build_info) */
-	double last_pairs_ms = 0, last_pairs_parse_ms = 0, last_pairs_sort_ms = 0;      /* the last kmr_identify_pairs*: the whole call, its name parse, its radix sort (HIP events, taken with kmr_tune "pairs_timing" only; kmr_build_info) */
-	double last_dedup_ms = 0, last_dedup_key_ms = 0, last_dedup_sort_ms = 0, last_dedup_consensus_ms = 0;      /* the last kmr_dedup_fragments*: the whole call, its key kernel, its radix sorts, its consensus kernel (HIP events, taken with kmr_tune "dedup_timing" only; kmr_build_info) */
-	uint64_t last_pair_hash_collisions = 0;      /* ... and how many of its runs of equal hash keys held more than one distinct common name */
-	uint64_t last_saturated_keys = 0, last_saturated_batches = 0;      /* what the last kmr_finalize's saturated-key pass redid, in how many batches */
-	bool qual_mixed = false;           /* a build that has seen two different quality characters stops asking (qrange) */
-	/* exchange with world_size > 1: sk_bits are the COARSE lists reads are scattered into and that travel; each holds 2^sk_fine_shift
-	 * fine lists, made by sk_refine_kernel before the count pass (fine state: sk_fine_state) */
-	uint32_t sk_fine_shift = 0;
-	uint32_t sk_min_override = 0;
-	uint64_t xo_segcap = 0; std::vector<uint64_t> xo_counts; const void *xo_batch = nullptr; uint64_t xo_first = 0;      /* xo_dev's segments */
-	/* kmr_exchange_* (kmr_exchange_rccl.hpp): communicator, transport, what the job was fed so far */
-	void *xc_comm = nullptr; kmr_transport xc_tr = {nullptr, nullptr, nullptr};
-	uint64_t xc_job_bases = 0, xc_bytes_to_peers = 0;
-	/* timing */
-	hipEvent_t ev0 = nullptr, ev1 = nullptr;
-	double ms[KMR_TIME_GROUPS] = {0};
-	uint64_t launches[KMR_TIME_GROUPS] = {0};
-	std::vector<std::pair<hipEvent_t, hipEvent_t> > pending_events[KMR_TIME_GROUPS];
-};
-
-/* what kmr_select_reads* / kmr_filter_read_batch* leave on the device: the output text and the per-read pick flags */
-struct kmr_picks {
-	int device = 0;
-	DevBuf text, picked;
-	uint64_t n = 0, n_picked = 0, bytes = 0;
-};
-
-/* what kmr_identify_pairs* leaves on the device: the mate of every read and the pair list */
-struct kmr_pairs {
-	int device = 0;
-	DevBuf mate, read1, read2;
-	uint64_t n = 0, n_pairs = 0, n_full = 0, n_seq = 0, n_conflicts = 0;
-};
-
-/* what kmr_dump_text leaves on the device: the mercount / mergraph text of a range of weak entries */
-struct kmr_text {
-	int device = 0;
-	DevBuf text;
-	uint64_t kept = 0, bytes = 0;
-};
-
-/* what kmr_dedup_fragments* leaves on the device: the discard flags, the collapsed groups, the consensus batch and its names */
-struct kmr_dedup {
-	int device = 0;
-	DevBuf disc, group_first, group_size, names;
-	kmr_reads *cons = nullptr;                    /* owned */
-	uint64_t n = 0, n_groups = 0, affected = 0, name_bytes = 0;
-	uint64_t skipped[4] = {0, 0, 0, 0};
-};
-
-/* device-resident read batch produced by kmr_ingest_fastq* */
-struct kmr_reads {
-	int device = 0;
-	DevBuf bases, quals;                          /* 64 bytes of padding behind the data: extract_kernel stages 16-byte blocks */
-	DevBuf offsets;                               /* [n + 1] */
-	DevBuf name_off, name_len;
-	uint64_t n = 0, total = 0, filtered = 0;
-	uint32_t input_base = 0;
-};
-
-namespace {
-
-std::string oom_note() { std::string s(g_oom_note); g_oom_note[0] = 0; return s; }
-
-std::string hip_err_text(hipError_t e) { return std::string(hipGetErrorString(e)) + (e == hipErrorOutOfMemory ? oom_note() : std::string()); }
-
-#define HIPCHK(h, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
-	(h)->err = std::string(#call) + ": " + hip_err_text(e_); \
-	return e_ == hipErrorOutOfMemory ? KMR_ERR_OOM : KMR_ERR_HIP; } } while (0)
-
-int DevBuf::reserve(kmr_handle *h, const char *what, size_t need, size_t bytes) {
-	if (p_ && cap_ >= need) return 0;
-	if (!bytes) bytes = need;
-	hipError_t e = p_ ? hipStreamSynchronize(h->stream) : hipSuccess;      /* kernels in flight may still read it */
-	if (e == hipSuccess) e = alloc(bytes);
-	if (e == hipSuccess) return 0;
-	h->err = std::string("device buffer ") + what + " (" + std::to_string(bytes) + " bytes): " + hip_err_text(e);
-	return e == hipErrorOutOfMemory ? KMR_ERR_OOM : KMR_ERR_HIP;
-}
 
 /* diagnostics on stderr and the measurement-only hooks exist in a -DKMR_DEBUG_HOOKS build alone: the shipped library reads no
  * environment variable */
@@ -341,9 +52,12 @@ bool dbg() { static const bool d = getenv("KMR_DEBUG") != nullptr; return d; }
 constexpr bool dbg() { return false; }
 #endif
 
-int fail(kmr_handle *h, int code, const std::string &msg) { const std::string m = code == KMR_ERR_OOM ? msg + oom_note() : msg; if (h) h->err = m; else g_create_error = m; return code; }
 
-uint64_t min_pow2(uint64_t n) {   /* BucketExposedMapLogic::getMinPowerOf2, src/Kmer.h:2199-2212 */
+}  // namespace
+
+namespace kmr_host {
+
+static uint64_t min_pow2(uint64_t n) {   /* BucketExposedMapLogic::getMinPowerOf2, src/Kmer.h:2199-2212 */
 	uint64_t p = n;
 	if (p == 0) p = 1;
 	else if ((p & (p - 1)) != 0) { p--; for (size_t i = 1; i < 64; i <<= 1) p |= p >> i; p++; }
@@ -362,15 +76,10 @@ void quality_table(double P[256], unsigned minQ, unsigned startChar) {
 	}
 }
 
-/* The one place where the key width (h->W: 1-4 words, anything else behaves as 4) and, where wanted, the value kind (h->ext) turn into
- * compile-time constants: with_w(h, [&](auto W) { return finalize_superkmer_t<W()>(h, min_depth); }), with_w_ext(h, [&](auto W, auto EXT) { ... }) */
-template <int N> using int_c = std::integral_constant<int, N>;
-template <class F> auto with_w(const kmr_handle *h, F &&f) {
-	switch (h->W) { case 1: return f(int_c<1>()); case 2: return f(int_c<2>()); case 3: return f(int_c<3>()); default: return f(int_c<4>()); }
-}
-template <class F> auto with_w_ext(const kmr_handle *h, F &&f) {
-	return with_w(h, [&](auto W) { return h->ext ? f(W, std::true_type()) : f(W, std::false_type()); });
-}
+}  // namespace kmr_host
+
+namespace {
+
 /* ... and the minimizer window of build_mode 3 (h->sk_win: 32 for keys of two words and more only -- no window-32 instance exists for
  * one-word keys --, 16, 8, anything else behaves as 4) */
 template <int W, class F> auto with_win(uint32_t win, F &&f) {
@@ -416,12 +125,6 @@ DevParams dev_params(kmr_handle *h) {
 	return p;
 }
 
-int grid_for(uint64_t n, int block = 256, int maxBlocks = 256 * 16) {
-	uint64_t g = (n + block - 1) / block;
-	if (g < 1) g = 1;
-	if (g > (uint64_t)maxBlocks) g = maxBlocks;
-	return (int)g;
-}
 
 template <int W> Table<W> table_of(kmr_handle *h) { Table<W> t; t.slots = h->slots.get<Slot<W>>(); t.ext = h->extslots.get<ExtSlot>(); t.log2cap = h->log2cap; return t; }
 
@@ -512,8 +215,6 @@ void time_end(kmr_handle *h, int which, hipEvent_t a, hipEvent_t b) {
 
 const size_t EXTRACT_SMEM = (size_t)WAVES_PER_BLOCK * 2 * TILE_BUF;
 
-int exclusive_scan(kmr_handle *h, const uint32_t *in, uint64_t n, uint64_t *out);
-
 /* If the batch holds reads longer than one LDS tile, cut them into work units (see ReadsView) and point rv at them. */
 int prepare_units(kmr_handle *h, ReadsView &rv, uint32_t span = (uint32_t)TILE_SPAN) {
 	rv.u_start = rv.u_end = rv.u_read = nullptr; rv.n_units = 0;
@@ -587,6 +288,8 @@ template <int W, bool EXT> int add_reads_dev_t(kmr_handle *h, const ReadsView &r
 
 int add_reads_dev_any(kmr_handle *h, const ReadsView &rv, uint64_t total_bases) { return with_w_ext(h, [&](auto W, auto EXT) { return add_reads_dev_t<W(), EXT()>(h, rv, total_bases); }); }
 
+}  // namespace
+namespace kmr_host {
 int exclusive_scan(kmr_handle *h, const uint32_t *in, uint64_t n, uint64_t *out /* n+1 */) {
 	const uint64_t nblocks = (n + SCAN_ITEMS - 1) / SCAN_ITEMS;
 	const size_t eb = sizeof(unsigned long long);
@@ -599,6 +302,8 @@ int exclusive_scan(kmr_handle *h, const uint32_t *in, uint64_t n, uint64_t *out 
 	HIPCHK(h, hipStreamSynchronize(h->stream));
 	return 0;
 }
+}  // namespace kmr_host
+namespace {
 
 /* bump allocation out of the finalize arena (256-byte aligned); what does not fit is allocated on the side, freed by
  * arena_reset() and added to the size the arena gets next time */
@@ -924,6 +629,8 @@ int zero_work_counter(kmr_handle *h) {
 	return 0;
 }
 
+}  // namespace
+namespace kmr_host {
 int num_cus(kmr_handle *h) {
 	if (h->ncu <= 0) {
 		hipDeviceProp_t pr; h->ncu = 256;
@@ -931,6 +638,8 @@ int num_cus(kmr_handle *h) {
 	}
 	return h->ncu;
 }
+}  // namespace kmr_host
+namespace {
 int part_grid(kmr_handle *h) { return num_cus(h) * 2; }
 /* the partition kernel wants a compute unit to itself: every (block, list) pair is a write stream, and the fewer of
  * those there are the longer the runs each batch appends */
@@ -2630,15 +2339,12 @@ int kmr_add_reads_twobit_dev(kmr_handle *h, const void *dev_twobit, const void *
 	}
 	const uint64_t *tboff = (const uint64_t *)dev_twobit_offsets;
 	if (!tboff) {      /* every read on the byte behind the one before it: ceil(L / 4) bytes each */
-		hipLaunchKernelGGL(twobit_bytes_kernel, dim3(grid_for(n_reads)), dim3(256), 0, h->stream, (const uint64_t *)dev_offsets, n_reads, h->tb_len.get<uint32_t>());
-		HIPCHK(h, hipGetLastError());
-		int rc = exclusive_scan(h, h->tb_len.get<uint32_t>(), n_reads, h->tb_off.get<uint64_t>()); if (rc) return rc;
+		int rc = twobit_byte_offsets(h, (const uint64_t *)dev_offsets, n_reads, h->tb_len.get<uint32_t>(), h->tb_off.get<uint64_t>()); if (rc) return rc;
 		tboff = h->tb_off.get<uint64_t>();
 	}
 	if (direct) {
 		/* the lean extraction stages the packed bytes as they are: no unpacked copy of the batch, no quality bytes */
-		hipLaunchKernelGGL(offsets_rel_kernel, dim3(grid_for(n_reads + 1)), dim3(256), 0, h->stream, (const uint64_t *)dev_offsets, n_reads, h->tb_rel.get<uint64_t>());
-		HIPCHK(h, hipGetLastError());
+		{ int rc = twobit_rel_offsets(h, (const uint64_t *)dev_offsets, n_reads, h->tb_rel.get<uint64_t>()); if (rc) return rc; }
 		if (h->stream_base + total_bases > MAX_STREAM_ORDINAL) return fail(h, KMR_ERR_CAPACITY, "more than 2^40 input bases on one handle");
 		const ReadsView rv = reads_view(nullptr, nullptr, h->tb_rel.get<uint64_t>(), n_reads, dev_discarded, h->stream_base, first_global_read_idx);
 		SkPacked pkd; pkd.bytes = (const uint8_t *)dev_twobit; pkd.off = tboff; pkd.mk_off = (const uint64_t *)dev_markup_offsets; pkd.mk_pos = (const uint32_t *)dev_markup_pos; pkd.mk_char = (const uint8_t *)dev_markup_char;
@@ -2648,14 +2354,8 @@ int kmr_add_reads_twobit_dev(kmr_handle *h, const void *dev_twobit, const void *
 		h->stream_base += total_bases; h->reads += n_reads; h->stats.reads = h->reads;
 		return rc;
 	}
-	hipLaunchKernelGGL(twobit_unpack_kernel, dim3((unsigned)std::min<uint64_t>((n_reads + 255) / 256, (uint64_t)num_cus(h) * 32)), dim3(256), 0, h->stream,
-	                   (const uint8_t *)dev_twobit, tboff, (const uint64_t *)dev_offsets, n_reads, h->tb_bases.get<uint8_t>(), h->tb_rel.get<uint64_t>());
-	HIPCHK(h, hipGetLastError());
-	if (dev_markup_offsets) {
-		hipLaunchKernelGGL(twobit_markup_kernel, dim3(grid_for(n_reads)), dim3(256), 0, h->stream, (const uint64_t *)dev_markup_offsets, (const uint32_t *)dev_markup_pos,
-		                   (const uint8_t *)dev_markup_char, (const uint64_t *)h->tb_rel.get<uint64_t>(), n_reads, h->tb_bases.get<uint8_t>());
-		HIPCHK(h, hipGetLastError());
-	}
+	{ int rc = twobit_unpack(h, (const uint8_t *)dev_twobit, tboff, (const uint64_t *)dev_offsets, (const uint64_t *)dev_markup_offsets, (const uint32_t *)dev_markup_pos,
+	                         (const uint8_t *)dev_markup_char, n_reads, h->tb_bases.get<uint8_t>(), h->tb_rel.get<uint64_t>()); if (rc) return rc; }
 	const void *q = dev_quals;
 	if (!dev_quals && uniform_quality) {
 		if (h->tb_quals.cap() < total_bases + 64) {
@@ -2867,12 +2567,11 @@ int lookup_stream(kmr_handle *h, const ReadsView &rv, uint64_t total_bases, uint
 	return with_w(h, [&](auto W) { return lookup_stream_t<W()>(h, rv, total_bases, position_counts, out_n); });
 }
 
-extern "C" {
+namespace kmr_host {
 /* ReadSelector::scoreAndTrimReads (src/ReadSelector.h:1182-1207) on the weak map; s_b / s_o: device bases and offsets,
  * offsets: the same offsets on the host */
-struct ScoreDev { uint32_t *trim_offset, *trim_length; float *score; uint8_t *was_trimmed; };      /* the results in score_buf, good until the handle's next scoring call */
-static int score_reads_core(kmr_handle *h, const uint8_t *s_b, const uint64_t *s_o, uint64_t n_reads, double minimum_kmer_score, int scoring_type,
-                            uint32_t *trim_offset, uint32_t *trim_length, float *score, uint8_t *was_trimmed, ScoreDev *keep = nullptr) {
+int score_reads_core(kmr_handle *h, const uint8_t *s_b, const uint64_t *s_o, uint64_t n_reads, double minimum_kmer_score, int scoring_type,
+                     uint32_t *trim_offset, uint32_t *trim_length, float *score, uint8_t *was_trimmed, ScoreDev *keep) {
 	int rc = 0;
 	ReadsView rv = reads_view(s_b, nullptr, s_o, n_reads);
 	/* per-read k-mer counts and their exclusive scan on the device (no host pass over the reads); one grow-only block for
@@ -2930,6 +2629,9 @@ static int score_reads_core(kmr_handle *h, const uint8_t *s_b, const uint64_t *s
 	} else hipStreamSynchronize(h->stream);
 	return rc;
 }
+}  // namespace kmr_host
+
+extern "C" {
 int kmr_score_reads(kmr_handle *h, const char *bases, const uint64_t *offsets, uint64_t n_reads, double minimum_kmer_score, int scoring_type,
                     uint32_t *trim_offset, uint32_t *trim_length, float *score, uint8_t *was_trimmed) {
 	if (!h || !bases || !offsets || !trim_offset || !trim_length || !score || !was_trimmed) return KMR_ERR_INVALID_ARG;
@@ -3129,138 +2831,6 @@ int kmr_histogram(kmr_handle *h, uint32_t zoom_max, double log_base, uint64_t *v
 	return KMR_OK;
 }
 
-/* ---- f2: FASTQ ingest on the device (kmr_ingest.hpp) ------------------------ */
-static int ingest_dev(kmr_handle *h, const uint8_t *text, uint64_t len, uint32_t input_base, int store_comment, kmr_reads **out) {
-	const uint32_t start = h->cfg.fastq_start_char;
-	if (input_base == 0) input_base = start;
-	if ((input_base != 33 && input_base != 64) || (start != 33 && start != 64))
-		return fail(h, KMR_ERR_INVALID_ARG, "fastq quality base must be 33 or 64 (src/Options.h:490)");
-	std::unique_ptr<kmr_reads, void (*)(kmr_reads *)> R(new kmr_reads, kmr_reads_free);
-	R->device = h->device; R->input_base = input_base;
-	DevBuf blk, derr, llen, keep, klen, bbase, lstart, kidx, boff;      /* scratch of this call */
-	const uint64_t nblk = (len + (uint64_t)ING_THREADS * ING_BYTES - 1) / ((uint64_t)ING_THREADS * ING_BYTES);
-	uint64_t n_lines = 0;
-	HIPCHK(h, derr.alloc(8)); HIPCHK(h, hipMemsetAsync(derr.get<uint32_t>(), 0, 8, h->stream));
-	if (nblk) {
-		if (nblk > 0x7fffffffull) return fail(h, KMR_ERR_INVALID_ARG, "FASTQ block too large for one call");
-		HIPCHK(h, blk.alloc(4 * nblk)); HIPCHK(h, bbase.alloc(8 * (nblk + 1)));
-		hipLaunchKernelGGL(ingest_count_lines, dim3((unsigned)nblk), dim3(ING_THREADS), 0, h->stream, text, len, blk.get<uint32_t>());
-		HIPCHK(h, hipGetLastError());
-		{ int rc = exclusive_scan(h, blk.get<uint32_t>(), nblk, bbase.get<uint64_t>()); if (rc) return rc; }
-		HIPCHK(h, hipMemcpy(&n_lines, bbase.get<uint64_t>() + nblk, 8, hipMemcpyDeviceToHost));
-	}
-	if (n_lines % 4 != 0) return fail(h, KMR_ERR_INVALID_ARG, "malformed FASTQ: " + std::to_string(n_lines) + " non-empty lines is not a multiple of 4 (truncated record)");
-	const uint64_t nrec = n_lines / 4;
-	uint64_t n_kept = 0, total = 0;
-	if (nrec) {
-		HIPCHK(h, lstart.alloc(8 * n_lines)); HIPCHK(h, llen.alloc(4 * n_lines));
-		hipLaunchKernelGGL(ingest_index_lines, dim3((unsigned)nblk), dim3(ING_THREADS), 0, h->stream, text, len, bbase.get<uint64_t>(), lstart.get<uint64_t>());
-		hipLaunchKernelGGL(ingest_line_lengths, dim3(grid_for(n_lines)), dim3(256), 0, h->stream, text, len, lstart.get<uint64_t>(), n_lines, llen.get<uint32_t>(), derr.get<uint32_t>());
-		HIPCHK(h, keep.alloc(4 * nrec)); HIPCHK(h, klen.alloc(4 * nrec));
-		HIPCHK(h, kidx.alloc(8 * (nrec + 1))); HIPCHK(h, boff.alloc(8 * (nrec + 1)));
-		hipLaunchKernelGGL(ingest_records, dim3(grid_for(nrec)), dim3(256), 0, h->stream, text, lstart.get<uint64_t>(), llen.get<uint32_t>(), nrec, store_comment, keep.get<uint32_t>(), klen.get<uint32_t>(), derr.get<uint32_t>());
-		HIPCHK(h, hipGetLastError());
-		{ int rc = exclusive_scan(h, keep.get<uint32_t>(), nrec, kidx.get<uint64_t>()); if (rc) return rc; }
-		{ int rc = exclusive_scan(h, klen.get<uint32_t>(), nrec, boff.get<uint64_t>()); if (rc) return rc; }
-		uint32_t e = 0;
-		HIPCHK(h, hipMemcpy(&e, derr.get<uint32_t>(), 4, hipMemcpyDeviceToHost));
-		if (e) {
-			std::string why;
-			if (e & ING_ERR_NAME) why += " a record does not start with '@' or has an empty name;";
-			if (e & ING_ERR_BLANK) why += " an empty line inside a record;";
-			if (e & ING_ERR_PLUS) why += " missing '+' line;";
-			if (e & ING_ERR_LEN) why += " number of bases and quals not equal;";
-			return fail(h, KMR_ERR_INVALID_ARG, "malformed FASTQ:" + why);
-		}
-		HIPCHK(h, hipMemcpy(&n_kept, kidx.get<uint64_t>() + nrec, 8, hipMemcpyDeviceToHost)); HIPCHK(h, hipMemcpy(&total, boff.get<uint64_t>() + nrec, 8, hipMemcpyDeviceToHost));
-	}
-	R->n = n_kept; R->total = total; R->filtered = nrec - n_kept;
-	HIPCHK(h, R->bases.alloc(total + 64)); HIPCHK(h, R->quals.alloc(total + 64)); HIPCHK(h, R->offsets.alloc(8 * (n_kept + 1)));
-	HIPCHK(h, R->name_off.alloc(8 * std::max<uint64_t>(1, n_kept))); HIPCHK(h, R->name_len.alloc(4 * std::max<uint64_t>(1, n_kept)));
-	HIPCHK(h, hipMemsetAsync(R->bases.get<uint8_t>() + total, 0, 64, h->stream)); HIPCHK(h, hipMemsetAsync(R->quals.get<uint8_t>() + total, 0, 64, h->stream));
-	HIPCHK(h, hipMemcpyAsync(R->offsets.get<uint64_t>() + n_kept, &total, 8, hipMemcpyHostToDevice, h->stream));
-	if (nrec) {
-		/* appendFasta rescales every read from the input base to Read::FASTQ_START_CHAR as it is read (src/ReadSet.cpp:324,336) */
-		hipLaunchKernelGGL(ingest_copy, dim3(grid_for(nrec, 4, 1 << 16)), dim3(256), 0, h->stream, text, len, lstart.get<uint64_t>(), llen.get<uint32_t>(), nrec, keep.get<uint32_t>(), kidx.get<uint64_t>(), boff.get<uint64_t>(),
-		                   (int)start - (int)input_base, start, R->bases.get<uint8_t>(), R->quals.get<uint8_t>(), R->offsets.get<uint64_t>(), R->name_off.get<uint64_t>(), R->name_len.get<uint32_t>(), derr.get<uint32_t>() + 1);
-		HIPCHK(h, hipGetLastError());
-		uint32_t flip = 0;
-		HIPCHK(h, hipMemcpyAsync(&flip, derr.get<uint32_t>() + 1, 4, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
-		const uint32_t want = start == 33 ? 64u : 33u;        /* __setFastqStart(the other base), src/ReadSet.h:174-186 */
-		if (flip && want != input_base) {
-			if (total) hipLaunchKernelGGL(ingest_shift_quals, dim3(grid_for(total)), dim3(256), 0, h->stream, R->quals.get<uint8_t>(), total, (int)input_base - (int)want);
-			HIPCHK(h, hipGetLastError());
-			R->input_base = want;
-		}
-	}
-	HIPCHK(h, hipStreamSynchronize(h->stream));
-	*out = R.release();
-	return KMR_OK;
-}
-
-int kmr_ingest_fastq_dev(kmr_handle *h, const void *dev_text, uint64_t len, uint32_t input_quality_base, int store_comment, kmr_reads **out) {
-	if (!h || !out || (len && !dev_text)) return KMR_ERR_INVALID_ARG;
-	*out = nullptr;
-	hipSetDevice(h->device);
-	return ingest_dev(h, (const uint8_t *)dev_text, len, input_quality_base, store_comment, out);
-}
-int kmr_ingest_fastq(kmr_handle *h, const char *text, uint64_t len, uint32_t input_quality_base, int store_comment, kmr_reads **out) {
-	if (!h || !out || (len && !text)) return KMR_ERR_INVALID_ARG;
-	*out = nullptr;
-	hipSetDevice(h->device);
-	DevBuf d;
-	HIPCHK(h, d.alloc(len + 16));
-	hipError_t e = hipMemcpy(d.get(), text, len, hipMemcpyHostToDevice);
-	if (e != hipSuccess) { h->err = std::string("hipMemcpy(FASTQ text): ") + hipGetErrorString(e); return KMR_ERR_HIP; }
-	return ingest_dev(h, d.get<uint8_t>(), len, input_quality_base, store_comment, out);
-}
-/* a device-resident batch from reads the host already parsed (the reference's ReadSet flattened as for kmr_add_reads) */
-int kmr_reads_from_host(kmr_handle *h, const char *bases, const char *quals, const uint64_t *offsets, uint64_t n_reads, kmr_reads **out) {
-	if (!h || !out || !offsets || (n_reads && (!bases || !quals))) return KMR_ERR_INVALID_ARG;
-	*out = nullptr;
-	hipSetDevice(h->device);
-	const uint64_t first = offsets[0], total = offsets[n_reads] - first;
-	std::unique_ptr<kmr_reads, void (*)(kmr_reads *)> r(new kmr_reads, kmr_reads_free);
-	r->device = h->device; r->n = n_reads; r->total = total; r->input_base = h->cfg.fastq_start_char;
-	HIPCHK(h, r->bases.alloc(total + 64)); HIPCHK(h, r->quals.alloc(total + 64));
-	HIPCHK(h, r->offsets.alloc(8 * (n_reads + 1)));
-	HIPCHK(h, r->name_off.alloc(8 * std::max<uint64_t>(n_reads, 1))); HIPCHK(h, r->name_len.alloc(4 * std::max<uint64_t>(n_reads, 1)));
-	HIPCHK(h, hipMemset(r->bases.get<uint8_t>() + total, 0, 64)); HIPCHK(h, hipMemset(r->quals.get<uint8_t>() + total, 0, 64));
-	HIPCHK(h, hipMemset(r->name_off.get<uint64_t>(), 0, 8 * std::max<uint64_t>(n_reads, 1))); HIPCHK(h, hipMemset(r->name_len.get<uint32_t>(), 0, 4 * std::max<uint64_t>(n_reads, 1)));
-	if (total) { HIPCHK(h, hipMemcpy(r->bases.get<uint8_t>(), bases + first, total, hipMemcpyHostToDevice)); HIPCHK(h, hipMemcpy(r->quals.get<uint8_t>(), quals + first, total, hipMemcpyHostToDevice)); }
-	std::vector<uint64_t> rel(n_reads + 1);
-	for (uint64_t i = 0; i <= n_reads; i++) rel[i] = offsets[i] - first;
-	HIPCHK(h, hipMemcpy(r->offsets.get<uint64_t>(), rel.data(), 8 * (n_reads + 1), hipMemcpyHostToDevice));
-	*out = r.release();
-	return KMR_OK;
-}
-void kmr_reads_free(kmr_reads *r) {
-	if (!r) return;
-	hipSetDevice(r->device);
-	delete r;      /* (its buffers are freed on this device) */
-}
-int kmr_reads_info(const kmr_reads *r, uint64_t *n_reads, uint64_t *total_bases, uint32_t *input_quality_base, uint64_t *n_filtered) {
-	if (!r) return KMR_ERR_INVALID_ARG;
-	if (n_reads) *n_reads = r->n; if (total_bases) *total_bases = r->total;
-	if (input_quality_base) *input_quality_base = r->input_base; if (n_filtered) *n_filtered = r->filtered;
-	return KMR_OK;
-}
-int kmr_reads_device_ptrs(const kmr_reads *r, void **bases, void **quals, void **offsets) {
-	if (!r) return KMR_ERR_INVALID_ARG;
-	if (bases) *bases = r->bases.get<uint8_t>(); if (quals) *quals = r->quals.get<uint8_t>(); if (offsets) *offsets = r->offsets.get<uint64_t>();
-	return KMR_OK;
-}
-int kmr_reads_copy(const kmr_reads *r, char *bases, char *quals, uint64_t *offsets, uint64_t *name_off, uint32_t *name_len) {
-	if (!r) return KMR_ERR_INVALID_ARG;
-	hipSetDevice(r->device);
-	hipError_t e = hipSuccess;
-	if (bases && r->total && e == hipSuccess) e = hipMemcpy(bases, r->bases.get<uint8_t>(), r->total, hipMemcpyDeviceToHost);
-	if (quals && r->total && e == hipSuccess) e = hipMemcpy(quals, r->quals.get<uint8_t>(), r->total, hipMemcpyDeviceToHost);
-	if (offsets && e == hipSuccess) e = hipMemcpy(offsets, r->offsets.get<uint64_t>(), 8 * (r->n + 1), hipMemcpyDeviceToHost);
-	if (name_off && r->n && e == hipSuccess) e = hipMemcpy(name_off, r->name_off.get<uint64_t>(), 8 * r->n, hipMemcpyDeviceToHost);
-	if (name_len && r->n && e == hipSuccess) e = hipMemcpy(name_len, r->name_len.get<uint32_t>(), 4 * r->n, hipMemcpyDeviceToHost);
-	return e == hipSuccess ? KMR_OK : KMR_ERR_HIP;
-}
 int kmr_add_read_batch(kmr_handle *h, const kmr_reads *r, uint64_t first_global_read_idx) {
 	if (!h || !r) return KMR_ERR_INVALID_ARG;
 	if (r->device != h->device) return fail(h, KMR_ERR_INVALID_ARG, "read batch lives on another device");
@@ -3268,1018 +2838,6 @@ int kmr_add_read_batch(kmr_handle *h, const kmr_reads *r, uint64_t first_global_
 	if (!rc) rc = kmr_sync(h);
 	return rc;
 }
-
-/* ---- f4: artifact filter (FilterKnownOddities) --------------------------- */
-}  // extern "C"
-
-struct kmr_artifact_filter {
-	int device = 0;
-	kmr_artifact_config cfg;
-	uint32_t n_seq = 0, remaining_edits = 0, log2cap = 0;
-	uint64_t n_keys = 0;
-	DevBuf d_keys, d_vals;                                         /* open-addressed lookup table */
-	DevBuf d_bits;                                                 /* presence filter in front of it (ART_FILTER_LOG2 bits) */
-	std::vector<uint64_t> keys; std::vector<uint32_t> vals;        /* the same entries on the host, ascending keys */
-};
-
-namespace {
-
-uint32_t art_log2cap(uint64_t n) { uint32_t l = 10; while ((1ull << l) < 2 * n + 16) l++; return l; }
-
-/* a scratch block of n elements of T (256 bytes at least) */
-template <class T> hipError_t alloc_n(DevBuf &b, T **p, size_t n) { const hipError_t e = b.alloc(std::max<size_t>(sizeof(T) * n, 256)); *p = b.get<T>(); return e; }
-
-uint64_t art_pack(const char *s, uint32_t len) {      /* TwoBitSequence::compressSequence: anything but ACGT packs as A */
-	uint64_t v = 0;
-	for (uint32_t i = 0; i < len; i++) { const char c = s[i]; v = (v << 2) | (uint64_t)((c == 'C') ? 1 : (c == 'G') ? 2 : (c == 'T') ? 3 : 0); }
-	return v;
-}
-uint64_t art_revcomp_host(uint64_t v, uint32_t len) { uint64_t r = 0; for (uint32_t i = 0; i < len; i++) { r = (r << 2) | (3 - (v & 3)); v >>= 2; } return r; }
-
-/* (re)build the lookup table of the filter from its host entries */
-int art_upload(kmr_handle *h, kmr_artifact_filter *f) {
-	f->d_keys.reset(); f->d_vals.reset();
-	f->n_keys = f->keys.size();
-	f->log2cap = art_log2cap(f->n_keys);
-	const uint64_t cap = 1ull << f->log2cap;
-	HIPCHK(h, f->d_keys.alloc(8 * cap)); HIPCHK(h, f->d_vals.alloc(4 * cap));
-	if (!f->d_bits) HIPCHK(h, f->d_bits.alloc((1u << ART_FILTER_LOG2) / 8));
-	HIPCHK(h, hipMemsetAsync(f->d_bits.get<uint32_t>(), 0, (1u << ART_FILTER_LOG2) / 8, h->stream));
-	DevBuf b_dk, b_dv; uint64_t *dk; uint32_t *dv;
-	HIPCHK(h, alloc_n(b_dk, &dk, f->n_keys)); HIPCHK(h, alloc_n(b_dv, &dv, f->n_keys));
-	if (f->n_keys) { HIPCHK(h, hipMemcpyAsync(dk, f->keys.data(), 8 * f->n_keys, hipMemcpyHostToDevice, h->stream)); HIPCHK(h, hipMemcpyAsync(dv, f->vals.data(), 4 * f->n_keys, hipMemcpyHostToDevice, h->stream)); }
-	ArtifactTable t{f->d_keys.get<uint64_t>(), f->d_vals.get<uint32_t>(), nullptr, f->log2cap, f->d_bits.get<uint32_t>()};
-	hipLaunchKernelGGL(artifact_fill, dim3(1024), dim3(256), 0, h->stream, f->d_keys.get<uint64_t>(), (uint32_t *)nullptr, cap);
-	if (f->n_keys) hipLaunchKernelGGL(artifact_insert, dim3((unsigned)std::min<uint64_t>((f->n_keys + 255) / 256, 4096)), dim3(256), 0, h->stream, t, dk, dv, f->n_keys);
-	HIPCHK(h, hipGetLastError());
-	HIPCHK(h, hipStreamSynchronize(h->stream));
-	return KMR_OK;
-}
-
-/* one round of prepareMaps' edit loop (src/FilterKnownOddities.h:264-282) on the device */
-int art_build_round(kmr_handle *h, kmr_artifact_filter *f) {
-	const uint32_t L = f->cfg.match_length, kb = L / 4;
-	const uint64_t n = f->keys.size();
-	/* the map's iteration order: bucket by bucket (KmerMap(512*1024): 512*1024/32+1 buckets rounded up to 2^15), sorted inside */
-	const uint64_t mask = resize_buckets(512 * 1024 / 32 + 1) - 1;
-	std::vector<std::pair<uint64_t, uint64_t>> order(n);
-	for (uint64_t i = 0; i < n; i++) {
-		uint8_t b[8];
-		for (uint32_t j = 0; j < kb; j++) b[j] = (uint8_t)(f->keys[i] >> (8 * (kb - 1 - j)));
-		order[i] = std::make_pair(kmr_hash(b, kb) & mask, i);
-	}
-	std::sort(order.begin(), order.end());       /* ties inside a bucket: ascending index = ascending key */
-	std::vector<uint64_t> sk(n); std::vector<uint32_t> sv(n);
-	for (uint64_t i = 0; i < n; i++) { sk[i] = f->keys[order[i].second]; sv[i] = f->vals[order[i].second]; }
-	const uint64_t worst = n * (3ull * L + 1);
-	if (worst > (1ull << 32)) return fail(h, KMR_ERR_UNSUPPORTED, "artifact filter: an edit round over " + std::to_string(n) + " keys does not fit the build table");
-	const uint32_t log2cap = art_log2cap(worst);
-	const uint64_t cap = 1ull << log2cap;
-	DevBuf b_tk, b_tv, b_tr, b_dk, b_dv, b_cnt, b_ok, b_ov; uint64_t *tk, *dk, *ok; uint32_t *tv, *tr, *dv, *ov; unsigned long long *cnt;
-	HIPCHK(h, alloc_n(b_tk, &tk, cap)); HIPCHK(h, alloc_n(b_tv, &tv, cap)); HIPCHK(h, alloc_n(b_tr, &tr, cap));
-	HIPCHK(h, alloc_n(b_dk, &dk, n)); HIPCHK(h, alloc_n(b_dv, &dv, n)); HIPCHK(h, alloc_n(b_cnt, &cnt, 1));
-	HIPCHK(h, hipMemcpyAsync(dk, sk.data(), 8 * n, hipMemcpyHostToDevice, h->stream));
-	HIPCHK(h, hipMemcpyAsync(dv, sv.data(), 4 * n, hipMemcpyHostToDevice, h->stream));
-	HIPCHK(h, hipMemsetAsync(cnt, 0, 8, h->stream));
-	ArtifactTable t{tk, tv, tr, log2cap, nullptr};
-	hipLaunchKernelGGL(artifact_fill, dim3(2048), dim3(256), 0, h->stream, tk, tr, cap);
-	hipLaunchKernelGGL(artifact_insert, dim3((unsigned)std::min<uint64_t>((n + 255) / 256, 4096)), dim3(256), 0, h->stream, t, dk, dv, n);
-	hipLaunchKernelGGL(artifact_neighbours, dim3((unsigned)std::min<uint64_t>((n * L + 255) / 256, 1u << 20)), dim3(256), 0, h->stream, t, dk, n, L);
-	HIPCHK(h, hipGetLastError());
-	HIPCHK(h, hipStreamSynchronize(h->stream));
-	/* the table is sparse (<= 50 % by construction, a few % in practice): count first, then compact */
-	HIPCHK(h, alloc_n(b_ok, &ok, worst)); HIPCHK(h, alloc_n(b_ov, &ov, worst));
-	hipLaunchKernelGGL(artifact_compact, dim3(2048), dim3(256), 0, h->stream, t, dv, ok, ov, cnt);
-	HIPCHK(h, hipGetLastError());
-	unsigned long long m = 0;
-	HIPCHK(h, hipMemcpyAsync(&m, cnt, 8, hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(h, hipStreamSynchronize(h->stream));
-	std::vector<uint64_t> nk(m); std::vector<uint32_t> nv(m);
-	HIPCHK(h, hipMemcpy(nk.data(), ok, 8 * m, hipMemcpyDeviceToHost)); HIPCHK(h, hipMemcpy(nv.data(), ov, 4 * m, hipMemcpyDeviceToHost));
-	std::vector<uint64_t> idx(m);
-	for (uint64_t i = 0; i < m; i++) idx[i] = i;
-	std::sort(idx.begin(), idx.end(), [&](uint64_t a, uint64_t b) { return nk[a] < nk[b]; });
-	f->keys.resize(m); f->vals.resize(m);
-	for (uint64_t i = 0; i < m; i++) { f->keys[i] = nk[idx[i]]; f->vals[i] = nv[idx[i]]; }
-	return KMR_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-void kmr_artifact_config_init(kmr_artifact_config *c) {
-	if (!c) return;
-	memset(c, 0, sizeof(*c));
-	c->match_length = 24; c->edit_distance = 2; c->build_edits = 2;      /* _FilterKnownOdditiesOptions(), src/FilterKnownOddities.h:72-75 */
-	c->min_quality = 3; c->fastq_start_char = 33; c->min_read_length = 0.40f;
-}
-
-int kmr_artifact_filter_create(kmr_handle *h, const kmr_artifact_config *cfg, const char *fasta, uint64_t len, kmr_artifact_filter **out) {
-	if (!h || !cfg || !out || (len && !fasta)) return KMR_ERR_INVALID_ARG;
-	*out = nullptr;
-	if (cfg->match_length == 0 || cfg->match_length > 28 || (cfg->match_length & 3))
-		return fail(h, KMR_ERR_INVALID_ARG, "artifact match length must be a multiple of 4 and <= 28 (src/FilterKnownOddities.h:207-209,244)");
-	hipSetDevice(h->device);
-	std::unique_ptr<kmr_artifact_filter, void (*)(kmr_artifact_filter *)> f(new kmr_artifact_filter, kmr_artifact_filter_free);
-	f->device = h->device; f->cfg = *cfg;
-	const uint32_t L = cfg->match_length;
-	/* sequences: read 0 is the empty "no match" read, then the FASTA records in file order (:213-231) */
-	std::vector<std::string> seqs(1);
-	for (uint64_t i = 0; i < len;) {
-		uint64_t e = i; while (e < len && fasta[e] != '\n') e++;
-		uint64_t le = e; if (le > i && fasta[le - 1] == '\r') le--;
-		if (le > i) {
-			if (fasta[i] == '>') seqs.push_back(std::string());
-			else if (seqs.size() > 1) for (uint64_t j = i; j < le; j++) seqs.back().push_back((char)toupper((unsigned char)fasta[j]));
-		}
-		i = e + 1;
-	}
-	f->n_seq = (uint32_t)seqs.size();
-	std::vector<std::pair<uint64_t, uint32_t>> kv;
-	for (uint32_t s = 1; s < f->n_seq; s++) {
-		std::string q = seqs[s];
-		if (cfg->reference_begin == 0 || s < cfg->reference_begin) q += seqs[s].substr(0, L);      /* ReadSet::circularize, src/ReadSet.cpp:120-130 */
-		for (size_t j = 0; j + L <= q.size(); j++) {
-			const uint64_t v = art_pack(q.data() + j, L), r = art_revcomp_host(v, L);
-			kv.push_back(std::make_pair(r < v ? r : v, s));
-		}
-	}
-	std::sort(kv.begin(), kv.end());                  /* getOrSetElement in sequence order: the lowest sequence index keeps a key */
-	for (size_t i = 0; i < kv.size(); i++) if (i == 0 || kv[i].first != kv[i - 1].first) { f->keys.push_back(kv[i].first); f->vals.push_back(kv[i].second); }
-	int edits = (int)cfg->edit_distance;
-	const int maxErrors = edits;
-	for (int error = 0; error < maxErrors; error++) {
-		if (cfg->build_edits == 1 || (cfg->build_edits == 2 && f->keys.size() < 750000)) {
-			edits--;
-			if (!f->keys.empty()) { const int rc = art_build_round(h, f.get()); if (rc) return rc; }
-		}
-	}
-	if (edits > 2) return fail(h, KMR_ERR_UNSUPPORTED, "artifact filter: more than two edits left for query time");
-	f->remaining_edits = (uint32_t)edits;
-	const int rc = art_upload(h, f.get());
-	if (rc) return rc;
-	*out = f.release();
-	return KMR_OK;
-}
-int kmr_artifact_filter_info(const kmr_artifact_filter *f, uint64_t *n_sequences, uint64_t *n_filter_kmers, uint32_t *remaining_edits) {
-	if (!f) return KMR_ERR_INVALID_ARG;
-	if (n_sequences) *n_sequences = f->n_seq; if (n_filter_kmers) *n_filter_kmers = f->n_keys; if (remaining_edits) *remaining_edits = f->remaining_edits;
-	return KMR_OK;
-}
-int kmr_artifact_filter_entries(const kmr_artifact_filter *f, uint64_t *keys, uint32_t *values, uint64_t cap) {
-	if (!f) return KMR_ERR_INVALID_ARG;
-	if (cap < f->keys.size()) return KMR_ERR_CAPACITY;
-	if (keys) memcpy(keys, f->keys.data(), 8 * f->keys.size());
-	if (values) memcpy(values, f->vals.data(), 4 * f->vals.size());
-	return KMR_OK;
-}
-void kmr_artifact_filter_free(kmr_artifact_filter *f) {
-	if (!f) return;
-	hipSetDevice(f->device);
-	delete f;      /* (its buffers are freed on this device) */
-}
-
-int kmr_artifact_filter_apply(kmr_handle *h, const kmr_artifact_filter *f, const kmr_reads *in, const int64_t *mate,
-                              uint32_t *value, uint32_t *min_pass, uint32_t *max_pass, uint8_t *action,
-                              uint32_t *remnant_off, uint32_t *remnant_len, kmr_reads **out) {
-	if (!h || !f || !in) return KMR_ERR_INVALID_ARG;
-	if (out) *out = nullptr;
-	if (f->device != h->device || in->device != h->device) return fail(h, KMR_ERR_INVALID_ARG, "filter, reads and handle must live on one device");
-	hipSetDevice(h->device);
-	const uint64_t n = in->n;
-	ArtifactTable t{f->d_keys.get<uint64_t>(), f->d_vals.get<uint32_t>(), nullptr, f->log2cap, f->d_bits.get<uint32_t>()};
-	ArtifactParams P;
-	P.length = f->cfg.match_length; P.nSeq = f->n_seq; P.numErrors = f->remaining_edits;
-	P.srBegin = f->cfg.simple_repeat_begin; P.srEnd = f->cfg.simple_repeat_end; P.phix = f->cfg.phix_idx; P.refBegin = f->cfg.reference_begin;
-	P.minQualChar = (int32_t)(int8_t)(uint8_t)(f->cfg.fastq_start_char + f->cfg.min_quality);
-	P.minReadLength = f->cfg.min_read_length;
-	DevBuf b_dval, b_dmin, b_dmax, b_dro, b_drl, b_dact, b_dflag, b_dridx, b_dmate, b_dlen, b_dsrc;
-	uint32_t *dval, *dmin, *dmax, *dro, *drl, *dlen, *dflag; uint8_t *dact; int64_t *dmate = nullptr; uint64_t *dridx, *dsrc;
-	HIPCHK(h, alloc_n(b_dval, &dval, n)); HIPCHK(h, alloc_n(b_dmin, &dmin, n)); HIPCHK(h, alloc_n(b_dmax, &dmax, n)); HIPCHK(h, alloc_n(b_dro, &dro, n)); HIPCHK(h, alloc_n(b_drl, &drl, n));
-	HIPCHK(h, alloc_n(b_dact, &dact, n)); HIPCHK(h, alloc_n(b_dflag, &dflag, n)); HIPCHK(h, alloc_n(b_dridx, &dridx, n + 1));
-	if (mate && n) { HIPCHK(h, alloc_n(b_dmate, &dmate, n)); HIPCHK(h, hipMemcpyAsync(dmate, mate, 8 * n, hipMemcpyHostToDevice, h->stream)); }
-	uint64_t n_rem = 0;
-	if (n) {
-		const unsigned blocks = (unsigned)((n + 255) / 256);
-		hipLaunchKernelGGL(artifact_screen, dim3(blocks), dim3(256), 0, h->stream, in->bases.get<uint8_t>(), in->quals.get<uint8_t>(), in->offsets.get<uint64_t>(), n, t, P, dval, dmin, dmax, dro, drl);
-		HIPCHK(h, hipGetLastError());
-	}
-	/* lengths after the filter: n reads, then the remnants */
-	HIPCHK(h, alloc_n(b_dlen, &dlen, 2 * n + 1));
-	if (n) {
-		const unsigned blocks = (unsigned)((n + 255) / 256);
-		hipLaunchKernelGGL(artifact_action, dim3(blocks), dim3(256), 0, h->stream, in->offsets.get<uint64_t>(), n, dmate, P, dval, dmin, dmax, drl, dact, dlen, dflag);
-		HIPCHK(h, hipGetLastError());
-		int rc = exclusive_scan(h, dflag, n, dridx); if (rc) return rc;
-		HIPCHK(h, hipMemcpy(&n_rem, dridx + n, 8, hipMemcpyDeviceToHost));
-	}
-	HIPCHK(h, alloc_n(b_dsrc, &dsrc, n_rem));
-	if (n_rem) {
-		hipLaunchKernelGGL(artifact_remnants, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, n, drl, dridx, dlen, dsrc);
-		HIPCHK(h, hipGetLastError());
-	}
-	HIPCHK(h, hipStreamSynchronize(h->stream));
-	hipError_t e = hipSuccess;
-	if (n) {
-		if (value && e == hipSuccess) e = hipMemcpy(value, dval, 4 * n, hipMemcpyDeviceToHost);
-		if (min_pass && e == hipSuccess) e = hipMemcpy(min_pass, dmin, 4 * n, hipMemcpyDeviceToHost);
-		if (max_pass && e == hipSuccess) e = hipMemcpy(max_pass, dmax, 4 * n, hipMemcpyDeviceToHost);
-		if (action && e == hipSuccess) e = hipMemcpy(action, dact, n, hipMemcpyDeviceToHost);
-		if (remnant_off && e == hipSuccess) e = hipMemcpy(remnant_off, dro, 4 * n, hipMemcpyDeviceToHost);
-		if (remnant_len && e == hipSuccess) e = hipMemcpy(remnant_len, drl, 4 * n, hipMemcpyDeviceToHost);
-	}
-	HIPCHK(h, e);
-	if (!out) return KMR_OK;
-	const uint64_t n_out = n + n_rem;
-	std::unique_ptr<kmr_reads, void (*)(kmr_reads *)> r(new kmr_reads, kmr_reads_free);
-	r->device = h->device; r->n = n_out; r->input_base = in->input_base; r->filtered = in->filtered;
-	HIPCHK(h, r->offsets.alloc(8 * (n_out + 1)));
-	if (n_out) { int rc = exclusive_scan(h, dlen, n_out, r->offsets.get<uint64_t>()); if (rc) return rc; HIPCHK(h, hipMemcpy(&r->total, r->offsets.get<uint64_t>() + n_out, 8, hipMemcpyDeviceToHost)); }
-	else HIPCHK(h, hipMemset(r->offsets.get<uint64_t>(), 0, 8));
-	HIPCHK(h, r->bases.alloc(r->total + 64)); HIPCHK(h, r->quals.alloc(r->total + 64));
-	HIPCHK(h, hipMemsetAsync(r->bases.get<uint8_t>() + r->total, 0, 64, h->stream)); HIPCHK(h, hipMemsetAsync(r->quals.get<uint8_t>() + r->total, 0, 64, h->stream));
-	HIPCHK(h, r->name_off.alloc(8 * std::max<uint64_t>(n_out, 1))); HIPCHK(h, r->name_len.alloc(4 * std::max<uint64_t>(n_out, 1)));
-	if (n_out) {
-		hipLaunchKernelGGL(artifact_gather, dim3((unsigned)std::min<uint64_t>((n_out + 3) / 4, 1u << 16)), dim3(256), 0, h->stream,
-		                   in->bases.get<uint8_t>(), in->quals.get<uint8_t>(), in->offsets.get<uint64_t>(), in->name_off.get<uint64_t>(), in->name_len.get<uint32_t>(), n, n_out, dact, dmin, dro, dsrc, r->offsets.get<uint64_t>(), r->bases.get<uint8_t>(), r->quals.get<uint8_t>(), r->name_off.get<uint64_t>(), r->name_len.get<uint32_t>());
-		HIPCHK(h, hipGetLastError());
-	}
-	HIPCHK(h, hipStreamSynchronize(h->stream));
-	*out = r.release();
-	return KMR_OK;
-}
-
-/* ---- selectReads / writePicks on the device (kmr_select.hpp) ---------------- */
-int kmr_select_config_init(kmr_select_config *c) {
-	if (!c) return KMR_ERR_INVALID_ARG;
-	memset(c, 0, sizeof(*c));
-	c->struct_size = (uint32_t)sizeof(kmr_select_config);
-	c->minimum_score = 2.0;            /* --min-depth, apps/FilterReads.cpp:197-199 */
-	c->min_read_length = 0.40f;        /* --min-read-length, src/ReadSelector.h:72 */
-	c->both_pass = 0;                  /* --min-passing-in-pair 1, src/ReadSelector.h:72 */
-	c->output_quality_base = 33;       /* --fastq-output-base-quality */
-	c->format = 0;                     /* --format-output 0 = FASTQ */
-	c->scoring_type = KMR_SCORE_MEDIAN;
-	return KMR_OK;
-}
-
-static int select_check_config(kmr_handle *h, const kmr_select_config *c) {
-	if (!c) return fail(h, KMR_ERR_INVALID_ARG, "kmr_select_config: NULL");
-	if (c->struct_size != sizeof(kmr_select_config)) return fail(h, KMR_ERR_INVALID_ARG, "kmr_select_config: struct_size " + std::to_string(c->struct_size) + " is not " + std::to_string(sizeof(kmr_select_config)));
-	if (c->format > 1) return fail(h, KMR_ERR_INVALID_ARG, "kmr_select_config: format must be 0 (FASTQ) or 1 (FASTA)");
-	if (c->output_quality_base != 33 && c->output_quality_base != 64) return fail(h, KMR_ERR_INVALID_ARG, "kmr_select_config: output_quality_base must be 33 or 64");
-	if (c->scoring_type > 4) return fail(h, KMR_ERR_INVALID_ARG, "kmr_select_config: bad scoring_type");
-	if (!(c->min_read_length >= 0.0f)) return fail(h, KMR_ERR_INVALID_ARG, "kmr_select_config: min_read_length must not be negative");
-	return 0;
-}
-
-/* up to N HIP events on the handle's stream, created and recorded only while the call's timing knob (kmr_tune "select_timing", "pairs_timing") is set */
-extern "C++" {
-template <int N> struct EventTimer {
-	hipEvent_t ev[N] = {}; bool on;
-	explicit EventTimer(bool enabled) : on(enabled) { if (on) for (auto &e : ev) if (hipEventCreate(&e) != hipSuccess) { e = nullptr; on = false; } }
-	~EventTimer() { for (auto e : ev) if (e) hipEventDestroy(e); }
-	void mark(int i, hipStream_t s) { if (on) hipEventRecord(ev[i], s); }
-	double ms(int a, int b) const { float t = 0; return on && hipEventElapsedTime(&t, ev[a], ev[b]) == hipSuccess ? t : 0.0; }      /* after the stream has been waited for */
-};
-}
-typedef EventTimer<3> SelectTimer;
-
-/* every pointer but the last is device memory (mate and the three af_* may be null) */
-static int select_core(kmr_handle *h, const kmr_reads *r, const uint8_t *dtext, uint64_t text_len, const int64_t *dmate, const uint8_t *dact, const uint32_t *dmin,
-                       const uint32_t *dmax, const uint32_t *dto, const uint32_t *dtl, const float *dsc, const uint8_t *dwt, const kmr_select_config *cfg, kmr_picks **out) {
-	const uint64_t n = r->n;
-	std::unique_ptr<kmr_picks, void (*)(kmr_picks *)> pk(new kmr_picks, kmr_picks_free);
-	pk->device = h->device; pk->n = n;
-	h->last_select_ms = h->last_write_ms = 0;
-	if (n == 0) { *out = pk.release(); return KMR_OK; }
-	SelectParams P;
-	P.bases = r->bases.get<uint8_t>(); P.quals = r->quals.get<uint8_t>(); P.offsets = r->offsets.get<uint64_t>(); P.name_off = r->name_off.get<uint64_t>(); P.name_len = r->name_len.get<uint32_t>();
-	P.text = dtext; P.text_len = text_len; P.mate = dmate; P.af_action = dact; P.af_min = dmin; P.af_max = dmax;
-	P.trim_off = dto; P.trim_len = dtl; P.score = dsc; P.was_trimmed = dwt; P.n = n;
-	P.min_score = (float)cfg->minimum_score; P.min_read_length = cfg->min_read_length; P.both_pass = cfg->both_pass ? 1u : 0u; P.fasta = cfg->format; P.scoring = cfg->scoring_type;
-	P.out_base = cfg->output_quality_base; P.qual_shift = (int32_t)cfg->output_quality_base - (int32_t)h->cfg.fastq_start_char;
-	DevBuf b_flag, b_len, b_nlen, b_pscan, b_bscan, b_pread, b_poff, b_tot;
-	uint32_t *flag, *len, *nlen, *pread; uint64_t *pscan, *bscan, *poff, *tot; uint8_t *picked;
-	HIPCHK(h, alloc_n(b_flag, &flag, n)); HIPCHK(h, alloc_n(b_len, &len, n)); HIPCHK(h, alloc_n(b_nlen, &nlen, n)); HIPCHK(h, alloc_n(b_pread, &pread, n));
-	HIPCHK(h, alloc_n(b_pscan, &pscan, n + 1)); HIPCHK(h, alloc_n(b_bscan, &bscan, n + 1)); HIPCHK(h, alloc_n(b_poff, &poff, n + 1)); HIPCHK(h, alloc_n(b_tot, &tot, 3));
-	HIPCHK(h, alloc_n(pk->picked, &picked, n));
-	SelectTimer timer(h->tune.select_timing);
-	timer.mark(0, h->stream);
-	HIPCHK(h, hipMemsetAsync(tot, 0, 24, h->stream));
-	hipLaunchKernelGGL(select_count_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, P, flag, len, nlen, picked, (uint32_t *)(tot + 2));
-	HIPCHK(h, hipGetLastError());
-	int rc = exclusive_scan(h, flag, n, pscan); if (rc) return rc;
-	rc = exclusive_scan(h, len, n, bscan); if (rc) return rc;
-	hipLaunchKernelGGL(select_compact_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, (const uint32_t *)flag, (const uint64_t *)pscan, (const uint64_t *)bscan, n, pread, poff, tot);
-	HIPCHK(h, hipGetLastError());
-	uint64_t totals[3] = {0, 0, 0};
-	HIPCHK(h, hipMemcpyAsync(totals, tot, 24, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));      /* the one copy that brings sizes back */
-	if (totals[2] & SEL_ERR_MATE) return fail(h, KMR_ERR_INVALID_ARG, "a mate index lies outside the batch");
-	if (totals[2] & SEL_ERR_NAME) return fail(h, KMR_ERR_INVALID_ARG, "a read's name span lies outside the text handed in (pass the text the batch was ingested from)");
-	pk->n_picked = totals[0]; pk->bytes = totals[1];
-	timer.mark(1, h->stream);
-	if (pk->bytes) {
-		HIPCHK(h, pk->text.alloc((pk->bytes + 15) & ~(uint64_t)15));
-		uint8_t *dout = pk->text.get<uint8_t>();
-		hipLaunchKernelGGL(select_write_kernel, dim3((unsigned)std::min<uint64_t>((pk->n_picked + SEL_WAVES - 1) / SEL_WAVES, (uint64_t)num_cus(h) * 8)), dim3(SEL_THREADS), 0, h->stream, P, (const uint32_t *)nlen, (const uint32_t *)pread, (const uint64_t *)poff, pk->n_picked, dout);
-		HIPCHK(h, hipGetLastError());
-	}
-	timer.mark(2, h->stream);
-	HIPCHK(h, hipStreamSynchronize(h->stream));
-	h->last_select_ms = timer.ms(0, 2); h->last_write_ms = timer.ms(1, 2);
-	*out = pk.release();
-	return KMR_OK;
-}
-
-extern "C++" {
-template <class T> static int select_upload(kmr_handle *h, DevBuf &b, const T *host, uint64_t n, const T **dev) {
-	*dev = nullptr;
-	if (!host || !n) return 0;
-	T *p = nullptr;
-	HIPCHK(h, alloc_n(b, &p, n));
-	HIPCHK(h, hipMemcpyAsync(p, host, sizeof(T) * n, hipMemcpyHostToDevice, h->stream));
-	*dev = p;
-	return 0;
-}
-}
-
-static int select_check_args(kmr_handle *h, const kmr_reads *r, const void *text, uint64_t text_len, const uint8_t *af_action, const uint32_t *af_min, const uint32_t *af_max,
-                             const kmr_select_config *cfg, kmr_picks **out, const char *who) {
-	if (out) *out = nullptr;
-	int rc = select_check_config(h, cfg); if (rc) return rc;
-	if (!h) return fail(h, KMR_ERR_INVALID_ARG, std::string(who) + ": NULL handle");
-	if (!r || !out || (text_len && !text)) return fail(h, KMR_ERR_INVALID_ARG, std::string(who) + ": NULL argument");
-	if ((af_action != nullptr) != (af_min != nullptr) || (af_action != nullptr) != (af_max != nullptr)) return fail(h, KMR_ERR_INVALID_ARG, std::string(who) + ": af_action, af_min_pass and af_max_pass go together");
-	if (r->device != h->device) return fail(h, KMR_ERR_INVALID_ARG, "read batch lives on another device");
-	if (r->n >= 0xffffffffull) return fail(h, KMR_ERR_UNSUPPORTED, std::string(who) + ": a batch holds fewer than 2^32 - 1 reads (pick indices are 32-bit)");
-	return 0;
-}
-
-/* text_on_device: `text` is device memory already */
-static int select_reads_any(kmr_handle *h, const kmr_reads *r, const void *text, uint64_t text_len, bool text_on_device, const int64_t *mate, const uint8_t *af_action,
-                            const uint32_t *af_min, const uint32_t *af_max, const uint32_t *trim_offset, const uint32_t *trim_length, const float *score,
-                            const uint8_t *was_trimmed, const kmr_select_config *cfg, kmr_picks **out, bool fused, const char *who) {
-	int rc = select_check_args(h, r, text, text_len, af_action, af_min, af_max, cfg, out, who); if (rc) return rc;
-	if (fused) { if (!h->finalized) return fail(h, KMR_ERR_STATE, std::string(who) + " before kmr_finalize"); }
-	else if (r->n && (!trim_offset || !trim_length || !score || !was_trimmed)) return fail(h, KMR_ERR_INVALID_ARG, std::string(who) + ": NULL argument");
-	hipSetDevice(h->device);
-	const uint64_t n = r->n;
-	DevBuf b_text, b_mate, b_act, b_min, b_max, b_to, b_tl, b_sc, b_wt;
-	const uint8_t *dtext = (const uint8_t *)text, *dact = nullptr, *dwt = nullptr; const int64_t *dmate = nullptr; const uint32_t *dmin = nullptr, *dmax = nullptr, *dto = nullptr, *dtl = nullptr; const float *dsc = nullptr;
-	if (!text_on_device) { rc = select_upload(h, b_text, (const uint8_t *)text, text_len, &dtext); if (rc) return rc; }
-	rc = select_upload(h, b_mate, mate, n, &dmate); if (rc) return rc;
-	rc = select_upload(h, b_act, af_action, n, &dact); if (rc) return rc;
-	rc = select_upload(h, b_min, af_min, n, &dmin); if (rc) return rc;
-	rc = select_upload(h, b_max, af_max, n, &dmax); if (rc) return rc;
-	h->last_score_ms = 0;
-	if (fused && n) {
-		SelectTimer timer(h->tune.select_timing);
-		timer.mark(0, h->stream);
-		ScoreDev sd;
-		rc = score_reads_core(h, r->bases.get<uint8_t>(), r->offsets.get<uint64_t>(), n, cfg->minimum_score, (int)cfg->scoring_type, nullptr, nullptr, nullptr, nullptr, &sd); if (rc) return rc;
-		timer.mark(1, h->stream);
-		if (timer.on) { HIPCHK(h, hipStreamSynchronize(h->stream)); h->last_score_ms = timer.ms(0, 1); }
-		dto = sd.trim_offset; dtl = sd.trim_length; dsc = sd.score; dwt = sd.was_trimmed;
-	} else if (!fused) {
-		rc = select_upload(h, b_to, trim_offset, n, &dto); if (rc) return rc;
-		rc = select_upload(h, b_tl, trim_length, n, &dtl); if (rc) return rc;
-		rc = select_upload(h, b_sc, score, n, &dsc); if (rc) return rc;
-		rc = select_upload(h, b_wt, was_trimmed, n, &dwt); if (rc) return rc;
-	}
-	rc = select_core(h, r, dtext, text_len, dmate, dact, dmin, dmax, dto, dtl, dsc, dwt, cfg, out);
-	if (rc) hipStreamSynchronize(h->stream);      /* the uploads above must have landed before their buffers go */
-	return rc;
-}
-
-int kmr_select_reads(kmr_handle *h, const kmr_reads *reads, const char *text, uint64_t text_len, const int64_t *mate, const uint8_t *af_action, const uint32_t *af_min_pass,
-                     const uint32_t *af_max_pass, const uint32_t *trim_offset, const uint32_t *trim_length, const float *score, const uint8_t *was_trimmed,
-                     const kmr_select_config *cfg, kmr_picks **out) {
-	return select_reads_any(h, reads, text, text_len, false, mate, af_action, af_min_pass, af_max_pass, trim_offset, trim_length, score, was_trimmed, cfg, out, false, "kmr_select_reads");
-}
-int kmr_select_reads_dev(kmr_handle *h, const kmr_reads *reads, const void *dev_text, uint64_t text_len, const int64_t *mate, const uint8_t *af_action, const uint32_t *af_min_pass,
-                         const uint32_t *af_max_pass, const uint32_t *trim_offset, const uint32_t *trim_length, const float *score, const uint8_t *was_trimmed,
-                         const kmr_select_config *cfg, kmr_picks **out) {
-	return select_reads_any(h, reads, dev_text, text_len, true, mate, af_action, af_min_pass, af_max_pass, trim_offset, trim_length, score, was_trimmed, cfg, out, false, "kmr_select_reads_dev");
-}
-int kmr_filter_read_batch(kmr_handle *h, const kmr_reads *reads, const char *text, uint64_t text_len, const int64_t *mate, const uint8_t *af_action, const uint32_t *af_min_pass,
-                          const uint32_t *af_max_pass, const kmr_select_config *cfg, kmr_picks **out) {
-	return select_reads_any(h, reads, text, text_len, false, mate, af_action, af_min_pass, af_max_pass, nullptr, nullptr, nullptr, nullptr, cfg, out, true, "kmr_filter_read_batch");
-}
-int kmr_filter_read_batch_dev(kmr_handle *h, const kmr_reads *reads, const void *dev_text, uint64_t text_len, const int64_t *mate, const uint8_t *af_action, const uint32_t *af_min_pass,
-                              const uint32_t *af_max_pass, const kmr_select_config *cfg, kmr_picks **out) {
-	return select_reads_any(h, reads, dev_text, text_len, true, mate, af_action, af_min_pass, af_max_pass, nullptr, nullptr, nullptr, nullptr, cfg, out, true, "kmr_filter_read_batch_dev");
-}
-int kmr_picks_info(const kmr_picks *p, uint64_t *n_picked, uint64_t *bytes) {
-	if (!p) return KMR_ERR_INVALID_ARG;
-	if (n_picked) *n_picked = p->n_picked; if (bytes) *bytes = p->bytes;
-	return KMR_OK;
-}
-int kmr_picks_copy(const kmr_picks *p, char *dst, uint64_t capacity, uint8_t *picked_flags) {
-	if (!p || (p->bytes && !dst)) return KMR_ERR_INVALID_ARG;
-	if (capacity < p->bytes) return KMR_ERR_CAPACITY;
-	hipSetDevice(p->device);
-	hipError_t e = hipSuccess;
-	if (p->bytes) e = hipMemcpy(dst, p->text.get<uint8_t>(), p->bytes, hipMemcpyDeviceToHost);
-	if (picked_flags && p->n && e == hipSuccess) e = hipMemcpy(picked_flags, p->picked.get<uint8_t>(), p->n, hipMemcpyDeviceToHost);
-	return e == hipSuccess ? KMR_OK : KMR_ERR_HIP;
-}
-int kmr_picks_device_ptr(const kmr_picks *p, void **dev_text) {
-	if (!p || !dev_text) return KMR_ERR_INVALID_ARG;
-	*dev_text = p->text.get<uint8_t>();
-	return KMR_OK;
-}
-void kmr_picks_free(kmr_picks *p) {
-	if (!p) return;
-	hipSetDevice(p->device);
-	delete p;      /* (its buffers are freed on this device) */
-}
-
-/* ---- ReadSet::identifyPairs on the device (kmr_pairs.hpp) ---------------- */
-/* dtext: device memory */
-static int pairs_core(kmr_handle *h, const kmr_reads *r, const uint8_t *dtext, uint64_t text_len, int store_comment, kmr_pairs **out) {
-	const uint64_t n = r->n;
-	std::unique_ptr<kmr_pairs, void (*)(kmr_pairs *)> pr(new kmr_pairs, kmr_pairs_free);
-	pr->device = h->device; pr->n = n;
-	h->last_pairs_ms = h->last_pairs_parse_ms = h->last_pairs_sort_ms = 0; h->last_pair_hash_collisions = 0;
-	if (n == 0) { *out = pr.release(); return KMR_OK; }
-	PairsParams P;
-	P.name_off = r->name_off.get<uint64_t>(); P.name_len = r->name_len.get<uint32_t>(); P.text = dtext; P.text_len = text_len; P.n = n; P.store_comment = store_comment ? 1u : 0u;
-	const dim3 grid(grid_for(n)), block(256);
-	DevBuf b_hash, b_cn, b_fl, b_link, b_brk, b_bscan, b_run, b_sec, b_unp, b_sscan, b_uscan, b_tot;
-	uint64_t *hash, *bscan, *sscan, *uscan, *tot; uint32_t *cn, *brk, *run, *sec, *unp; uint8_t *fl, *link; int64_t *mate;
-	HIPCHK(h, alloc_n(b_hash, &hash, n)); HIPCHK(h, alloc_n(b_cn, &cn, n)); HIPCHK(h, alloc_n(b_fl, &fl, n)); HIPCHK(h, alloc_n(b_tot, &tot, (size_t)PAIRS_T_WORDS));
-	HIPCHK(h, alloc_n(pr->mate, &mate, n));
-	EventTimer<5> timer(h->tune.pairs_timing);
-	timer.mark(0, h->stream);
-	HIPCHK(h, hipMemsetAsync(tot, 0, 8 * PAIRS_T_WORDS, h->stream));
-	hipLaunchKernelGGL(pairs_parse_kernel, grid, block, 0, h->stream, P, hash, cn, fl, tot);
-	HIPCHK(h, hipGetLastError());
-	timer.mark(1, h->stream);
-	uint64_t totals[PAIRS_T_WORDS] = {0};
-	if (text_len == 0) {      /* no names (kmr_reads_from_host, kmr_reads_from_twobit): every read is a half pair of its own */
-		int64_t *r1, *r2;
-		HIPCHK(h, alloc_n(pr->read1, &r1, n)); HIPCHK(h, alloc_n(pr->read2, &r2, n));
-		hipLaunchKernelGGL(pairs_single_kernel, grid, block, 0, h->stream, n, mate, r1, r2);
-		HIPCHK(h, hipGetLastError());
-		HIPCHK(h, hipMemcpyAsync(totals, tot, 8 * PAIRS_T_WORDS, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
-		if (totals[PAIRS_T_ERR] & PAIRS_ERR_NAME) return fail(h, KMR_ERR_INVALID_ARG, "a read's name span lies outside the text handed in (pass the text the batch was ingested from)");
-		pr->n_pairs = n;
-		*out = pr.release();
-		return KMR_OK;
-	}
-	const PairsNames N = {hash, cn, fl};
-	/* phase 1 */
-	HIPCHK(h, alloc_n(b_link, &link, n)); HIPCHK(h, alloc_n(b_brk, &brk, n)); HIPCHK(h, alloc_n(b_bscan, &bscan, n + 1)); HIPCHK(h, alloc_n(b_run, &run, n + 1));
-	HIPCHK(h, alloc_n(b_sec, &sec, n)); HIPCHK(h, alloc_n(b_unp, &unp, n)); HIPCHK(h, alloc_n(b_sscan, &sscan, n + 1)); HIPCHK(h, alloc_n(b_uscan, &uscan, n + 1));
-	hipLaunchKernelGGL(pairs_link_kernel, grid, block, 0, h->stream, P, N, link, brk);
-	HIPCHK(h, hipGetLastError());
-	int rc = exclusive_scan(h, brk, n, bscan); if (rc) return rc;
-	hipLaunchKernelGGL(pairs_runstart_kernel, grid, block, 0, h->stream, (const uint8_t *)link, (const uint64_t *)bscan, n, run);
-	hipLaunchKernelGGL(pairs_seq_kernel, grid, block, 0, h->stream, (const uint8_t *)link, (const uint64_t *)bscan, (const uint32_t *)run, n, sec, unp, mate);
-	HIPCHK(h, hipGetLastError());
-	rc = exclusive_scan(h, sec, n, sscan); if (rc) return rc;
-	rc = exclusive_scan(h, unp, n, uscan); if (rc) return rc;
-	/* the first of the call's two fixed-size copies: phase 1's totals size phase 2 (an interleaved file leaves it nothing) */
-	HIPCHK(h, hipMemcpyAsync(&totals[PAIRS_T_SEQ], sscan + n, 8, hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(h, hipMemcpyAsync(&totals[PAIRS_T_UNPAIRED], uscan + n, 8, hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(h, hipMemcpyAsync(&totals[PAIRS_T_ERR], tot + PAIRS_T_ERR, 8, hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(h, hipStreamSynchronize(h->stream));
-	if (totals[PAIRS_T_ERR] & PAIRS_ERR_NAME) return fail(h, KMR_ERR_INVALID_ARG, "a read's name span lies outside the text handed in (pass the text the batch was ingested from)");
-	const uint64_t n_seq = totals[PAIRS_T_SEQ], m = totals[PAIRS_T_UNPAIRED];
-	/* phase 2 */
-	DevBuf b_kin, b_kout, b_vin, b_vout, b_tmp, b_push, b_side, b_pscan;
-	unsigned long long *kin, *kout; uint32_t *vin, *vout, *push = nullptr; uint8_t *side = nullptr; uint64_t *pscan = nullptr;
-	timer.mark(2, h->stream); timer.mark(3, h->stream);
-	if (m) {
-		HIPCHK(h, alloc_n(b_kin, &kin, m)); HIPCHK(h, alloc_n(b_kout, &kout, m)); HIPCHK(h, alloc_n(b_vin, &vin, m)); HIPCHK(h, alloc_n(b_vout, &vout, m));
-		HIPCHK(h, alloc_n(b_push, &push, n)); HIPCHK(h, alloc_n(b_side, &side, n)); HIPCHK(h, alloc_n(b_pscan, &pscan, n + 1));
-		const uint32_t bits = h->tune.pair_hash_bits;
-		hipLaunchKernelGGL(pairs_keys_kernel, grid, block, 0, h->stream, (const uint32_t *)unp, (const uint64_t *)uscan, (const uint64_t *)hash, bits >= 64 ? ~0ull : (1ull << bits) - 1, n, kin, vin);
-		HIPCHK(h, hipGetLastError());
-		HIPCHK(h, hipMemsetAsync(push, 0, 4 * n, h->stream)); HIPCHK(h, hipMemsetAsync(side, 0, n, h->stream));
-		size_t tmp_bytes = 0;
-		if (kmr::sort_pairs_u64_u32(nullptr, &tmp_bytes, kin, kout, vin, vout, m, h->stream) != 0) return fail(h, KMR_ERR_HIP, "kmr_identify_pairs: radix sort (size query)");
-		HIPCHK(h, b_tmp.alloc(std::max<size_t>(tmp_bytes, 256)));
-		timer.mark(2, h->stream);
-		if (kmr::sort_pairs_u64_u32(b_tmp.get(), &tmp_bytes, kin, kout, vin, vout, m, h->stream) != 0) return fail(h, KMR_ERR_HIP, "kmr_identify_pairs: radix sort");
-		timer.mark(3, h->stream);
-		hipLaunchKernelGGL(pairs_group_kernel, dim3(grid_for(m)), block, 0, h->stream, P, N, (const unsigned long long *)kout, (const uint32_t *)vout, m, mate, push, side, tot);
-		HIPCHK(h, hipGetLastError());
-		rc = exclusive_scan(h, push, n, pscan); if (rc) return rc;
-		/* the second: what phase 2 made */
-		HIPCHK(h, hipMemcpyAsync(&totals[PAIRS_T_PUSHED], pscan + n, 8, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(h, hipMemcpyAsync(&totals[PAIRS_T_FULL2], tot + PAIRS_T_FULL2, 8 * (PAIRS_T_WORDS - PAIRS_T_FULL2), hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(h, hipStreamSynchronize(h->stream));
-	}
-	pr->n_seq = n_seq; pr->n_pairs = n_seq + totals[PAIRS_T_PUSHED]; pr->n_full = n_seq + totals[PAIRS_T_FULL2];
-	pr->n_conflicts = totals[PAIRS_T_CONFLICT1] + totals[PAIRS_T_CONFLICT2];
-	h->last_pair_hash_collisions = totals[PAIRS_T_COLLISIONS];
-	int64_t *r1, *r2;
-	HIPCHK(h, alloc_n(pr->read1, &r1, pr->n_pairs)); HIPCHK(h, alloc_n(pr->read2, &r2, pr->n_pairs));
-	hipLaunchKernelGGL(pairs_scatter_kernel, grid, block, 0, h->stream, (const uint32_t *)sec, (const uint64_t *)sscan, (const uint32_t *)push, (const uint64_t *)pscan, (const uint8_t *)side, (const int64_t *)mate,
-	                   n, n_seq, r1, r2);
-	HIPCHK(h, hipGetLastError());
-	timer.mark(4, h->stream);
-	HIPCHK(h, hipStreamSynchronize(h->stream));
-	h->last_pairs_ms = timer.ms(0, 4); h->last_pairs_parse_ms = timer.ms(0, 1); h->last_pairs_sort_ms = m ? timer.ms(2, 3) : 0.0;
-	*out = pr.release();
-	return KMR_OK;
-}
-
-static int identify_pairs_any(kmr_handle *h, const kmr_reads *r, const void *text, uint64_t text_len, bool text_on_device, int store_comment, kmr_pairs **out) {
-	if (!h || !r || !out || (text_len && !text)) return KMR_ERR_INVALID_ARG;
-	*out = nullptr;
-	if (r->device != h->device) return fail(h, KMR_ERR_INVALID_ARG, "read batch lives on another device");
-	if (r->n >= 0xffffffffull) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_identify_pairs: a batch holds fewer than 2^32 - 1 reads (read indices of the sort are 32-bit)");
-	hipSetDevice(h->device);
-	DevBuf b_text;
-	const uint8_t *dtext = (const uint8_t *)text;
-	if (!text_on_device && r->n) { int rc = select_upload(h, b_text, (const uint8_t *)text, text_len, &dtext); if (rc) return rc; }
-	const int rc = pairs_core(h, r, dtext, text_len, store_comment, out);
-	if (rc) hipStreamSynchronize(h->stream);      /* the upload above must have landed before its buffer goes */
-	return rc;
-}
-int kmr_identify_pairs(kmr_handle *h, const kmr_reads *reads, const char *text, uint64_t text_len, int store_comment, kmr_pairs **out) {
-	return identify_pairs_any(h, reads, text, text_len, false, store_comment, out);
-}
-int kmr_identify_pairs_dev(kmr_handle *h, const kmr_reads *reads, const void *dev_text, uint64_t text_len, int store_comment, kmr_pairs **out) {
-	return identify_pairs_any(h, reads, dev_text, text_len, true, store_comment, out);
-}
-int kmr_pairs_info(const kmr_pairs *p, uint64_t *n_reads, uint64_t *n_pairs, uint64_t *n_full, uint64_t *n_sequential, uint64_t *n_conflicts, int *has_pairs) {
-	if (!p) return KMR_ERR_INVALID_ARG;
-	if (n_reads) *n_reads = p->n; if (n_pairs) *n_pairs = p->n_pairs; if (n_full) *n_full = p->n_full;
-	if (n_sequential) *n_sequential = p->n_seq; if (n_conflicts) *n_conflicts = p->n_conflicts;
-	if (has_pairs) *has_pairs = p->n_pairs > 0 && p->n_pairs < p->n;      /* ReadSet::hasPairs, src/ReadSet.h:526-529 */
-	return KMR_OK;
-}
-int kmr_pairs_copy(const kmr_pairs *p, int64_t *mate, int64_t *read1, int64_t *read2) {
-	if (!p) return KMR_ERR_INVALID_ARG;
-	hipSetDevice(p->device);
-	hipError_t e = hipSuccess;
-	if (mate && p->n) e = hipMemcpy(mate, p->mate.get<int64_t>(), 8 * p->n, hipMemcpyDeviceToHost);
-	if (read1 && p->n_pairs && e == hipSuccess) e = hipMemcpy(read1, p->read1.get<int64_t>(), 8 * p->n_pairs, hipMemcpyDeviceToHost);
-	if (read2 && p->n_pairs && e == hipSuccess) e = hipMemcpy(read2, p->read2.get<int64_t>(), 8 * p->n_pairs, hipMemcpyDeviceToHost);
-	return e == hipSuccess ? KMR_OK : KMR_ERR_HIP;
-}
-int kmr_pairs_device_ptrs(const kmr_pairs *p, void **dev_mate, void **dev_read1, void **dev_read2) {
-	if (!p) return KMR_ERR_INVALID_ARG;
-	if (dev_mate) *dev_mate = p->mate.get<int64_t>(); if (dev_read1) *dev_read1 = p->read1.get<int64_t>(); if (dev_read2) *dev_read2 = p->read2.get<int64_t>();
-	return KMR_OK;
-}
-void kmr_pairs_free(kmr_pairs *p) {
-	if (!p) return;
-	hipSetDevice(p->device);
-	delete p;      /* (its buffers are freed on this device) */
-}
-
-/* ---- DuplicateFragmentFilter on the device (kmr_dedup.hpp) ---------------- */
-/* probToQual (src/Sequence.cpp:807-809) steps from i to i + 1 at dedup_qual_steps()[i]: the smallest double p with
- * (char)(-10. * log10(1.0 - p)) >= i + 1, found by bisection over the bit pattern (the expression is monotone below 0.9999) */
-static char dedup_prob_to_qual(double prob) { return (char)(-10. * std::log10(1.0 - prob)); }
-static const double *dedup_qual_steps() {
-	static double step[DEDUP_QUALS];
-	static std::once_flag once;
-	std::call_once(once, [] {
-		for (int i = 0; i < DEDUP_QUALS; i++) {
-			uint64_t lo = 0, hi; const double top = 0.9999;
-			memcpy(&hi, &top, 8);
-			if (dedup_prob_to_qual(top) < i + 1) { step[i] = top; continue; }      /* never reached: getQualChar answers 40 from there */
-			while (hi - lo > 1) {
-				const uint64_t mid = lo + (hi - lo) / 2; double p; memcpy(&p, &mid, 8);
-				if (dedup_prob_to_qual(p) >= i + 1) hi = mid; else lo = mid;
-			}
-			memcpy(&step[i], &hi, 8);
-		}
-	});
-	return step;
-}
-char kmr_consensus_qual(double prob) {
-	if (prob >= 0.9999) return 40;
-	const double *step = dedup_qual_steps();
-	char q = 0;
-	while (q < DEDUP_QUALS && step[(int)q] <= prob) q++;
-	return q;
-}
-
-int kmr_dedup_config_init(kmr_dedup_config *c) {
-	if (!c) return KMR_ERR_INVALID_ARG;
-	memset(c, 0, sizeof(*c));
-	c->struct_size = (uint32_t)sizeof(kmr_dedup_config);
-	c->dedup_mode = 0; c->paired = 1; c->dedup_length = 24; c->start_offset = 0; c->edit_distance = 0; c->consensus = 1;      /* src/DuplicateFragmentFilter.h:60-61 */
-	return KMR_OK;
-}
-static int dedup_check_config(kmr_handle *h, const kmr_dedup_config *c) {
-	if (!c) return fail(h, KMR_ERR_INVALID_ARG, "kmr_dedup_config: NULL");
-	if (c->struct_size != sizeof(kmr_dedup_config)) return fail(h, KMR_ERR_INVALID_ARG, "kmr_dedup_config: struct_size " + std::to_string(c->struct_size) + " is not " + std::to_string(sizeof(kmr_dedup_config)));
-	if (c->dedup_mode > 2) return fail(h, KMR_ERR_INVALID_ARG, "kmr_dedup_config: dedup_mode must be 0 (off), 1 or 2");
-	if (c->paired > 1) return fail(h, KMR_ERR_INVALID_ARG, "kmr_dedup_config: paired must be 0 or 1");
-	if (c->dedup_length == 0 || c->dedup_length % 4 != 0 || c->start_offset % 4 != 0) return fail(h, KMR_ERR_INVALID_ARG, "kmr_dedup_config: dedup_length and start_offset must be multiples of 4, dedup_length not 0");
-	if (c->edit_distance != 0) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_dedup_config: only dedup-edit-distance 0 is built");
-	if (c->consensus == 0) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_dedup_config: only dedup-consensus 1 is built");
-	if (2 * (uint64_t)c->dedup_length > 128) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_dedup_config: a key holds at most 128 bases (2 * dedup_length)");
-	if ((uint64_t)c->start_offset + 2 * (uint64_t)c->dedup_length > 0x7fffffffull) return fail(h, KMR_ERR_INVALID_ARG, "kmr_dedup_config: start_offset is too large");
-	return 0;
-}
-
-/* the handle's DedupTables, made by the first call */
-static int dedup_tables(kmr_handle *h, const DedupTables **out) {
-	if (!h->dedup_tab) {
-		std::unique_ptr<DedupTables> t(new DedupTables);
-		double P[256]; quality_table(P, h->cfg.min_quality_score, h->cfg.fastq_start_char);
-		for (int q = 0; q < 256; q++) {      /* Read::getProbabilityBases (src/Sequence.cpp:573-576), ProbabilityBase::observe (:871) */
-			double prob = P[q];
-			if (prob < 0.2501) prob = 0.2501;
-			t->prob[q] = prob; t->other[q] = (1.0 - prob) / 3.0;
-		}
-		memcpy(t->step, dedup_qual_steps(), sizeof(t->step));
-		HIPCHK(h, h->dedup_tab.alloc(sizeof(DedupTables)));
-		HIPCHK(h, hipMemcpy(h->dedup_tab.get(), t.get(), sizeof(DedupTables), hipMemcpyHostToDevice));
-	}
-	*out = h->dedup_tab.get<DedupTables>();
-	return 0;
-}
-
-/* dtext and ddisc (may be null): device memory */
-static int dedup_core(kmr_handle *h, const kmr_reads *r, const uint8_t *dtext, uint64_t text_len, const kmr_pairs *pairs, const uint8_t *ddisc, const kmr_dedup_config *cfg, kmr_dedup **out) {
-	const uint64_t n = r->n, np = pairs->n_pairs;
-	std::unique_ptr<kmr_dedup, void (*)(kmr_dedup *)> dd(new kmr_dedup, kmr_dedup_free);
-	dd->device = h->device; dd->n = n;
-	h->last_dedup_ms = h->last_dedup_key_ms = h->last_dedup_sort_ms = h->last_dedup_consensus_ms = 0;
-	const DedupTables *tables; int rc = dedup_tables(h, &tables); if (rc) return rc;
-	uint8_t *disc;
-	HIPCHK(h, alloc_n(dd->disc, &disc, n));
-	EventTimer<7> timer(h->tune.dedup_timing);
-	timer.mark(0, h->stream);
-	if (n) { if (ddisc) HIPCHK(h, hipMemcpyAsync(disc, ddisc, n, hipMemcpyDeviceToDevice, h->stream)); else HIPCHK(h, hipMemsetAsync(disc, 0, n, h->stream)); }
-	DedupParams P;
-	P.bases = r->bases.get<uint8_t>(); P.quals = r->quals.get<uint8_t>(); P.offsets = r->offsets.get<uint64_t>(); P.name_off = r->name_off.get<uint64_t>(); P.name_len = r->name_len.get<uint32_t>();
-	P.text = dtext; P.text_len = text_len; P.n = n; P.total = r->total; P.read1 = pairs->read1.get<int64_t>(); P.read2 = pairs->read2.get<int64_t>(); P.np = np; P.discarded = ddisc;
-	P.paired = cfg->paired ? 1u : 0u; P.mode2 = cfg->dedup_mode == 2 ? 1u : 0u; P.L = cfg->paired ? cfg->dedup_length : 2 * cfg->dedup_length; P.so = cfg->start_offset;
-	P.W = (cfg->dedup_length / 2 + 7) / 8; P.sides = cfg->paired ? 2u : 1u;
-	P.min_q = h->cfg.fastq_start_char + h->cfg.min_quality_score; P.start_char = h->cfg.fastq_start_char;
-	const dim3 block(256);
-	uint64_t totals[DEDUP_T_WORDS] = {0}, c = 0, K = 0;
-	DevBuf b_keys, b_cand, b_flip, b_cscan, b_tot, b_perm, b_perm2, b_kin, b_kout, b_tmp, b_head, b_hscan, b_start, b_keep, b_kscan, b_first, b_first2, b_grp, b_grp2;
-	DevBuf b_len, b_nb, b_nscan, b_members;
-	/* declared behind the temporaries, so it goes first: a return with kernels still in flight waits for them before their buffers go */
-	struct Drain { hipStream_t s; bool armed; ~Drain() { if (armed) hipStreamSynchronize(s); } } drain = {h->stream, true};
-	unsigned long long *keys, *kin, *kout, *first, *first2; uint32_t *cand, *perm = nullptr, *perm2, *head, *keep = nullptr, *grp, *grp2; uint8_t *flip = nullptr; uint64_t *cscan, *tot, *hscan = nullptr, *start = nullptr, *kscan;
-	HIPCHK(h, alloc_n(b_tot, &tot, (size_t)DEDUP_T_WORDS));
-	HIPCHK(h, hipMemsetAsync(tot, 0, 8 * DEDUP_T_WORDS, h->stream));
-	if (n && np && cfg->dedup_mode) {
-		/* candidates and their keys */
-		HIPCHK(h, alloc_n(b_keys, &keys, (size_t)P.W * np)); HIPCHK(h, alloc_n(b_cand, &cand, np)); HIPCHK(h, alloc_n(b_flip, &flip, np)); HIPCHK(h, alloc_n(b_cscan, &cscan, np + 1));
-		hipLaunchKernelGGL(dedup_key_kernel, dim3(grid_for(np)), block, 0, h->stream, P, keys, cand, flip, tot);
-		HIPCHK(h, hipGetLastError());
-		timer.mark(1, h->stream);
-		rc = exclusive_scan(h, cand, np, cscan); if (rc) return rc;
-		/* the first of the call's three fixed-size copies: the number of candidates sizes the sorts */
-		HIPCHK(h, hipMemcpyAsync(&c, cscan + np, 8, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(h, hipMemcpyAsync(totals, tot, 8 * DEDUP_T_AFFECTED, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(h, hipStreamSynchronize(h->stream));
-	} else timer.mark(1, h->stream);
-	for (int i = 0; i < 4; i++) dd->skipped[i] = totals[i];
-	timer.mark(2, h->stream);
-	if (c >= 2) {
-		const dim3 cgrid(grid_for(c));
-		HIPCHK(h, alloc_n(b_perm, &perm, c)); HIPCHK(h, alloc_n(b_perm2, &perm2, c)); HIPCHK(h, alloc_n(b_kin, &kin, c)); HIPCHK(h, alloc_n(b_kout, &kout, c));
-		hipLaunchKernelGGL(dedup_compact_kernel, dim3(grid_for(np)), block, 0, h->stream, (const uint32_t *)cand, (const uint64_t *)cscan, np, perm);
-		HIPCHK(h, hipGetLastError());
-		size_t tmp_bytes = 0;
-		if (kmr::sort_pairs_u64_u32(nullptr, &tmp_bytes, kin, kout, perm, perm2, c, h->stream) != 0) return fail(h, KMR_ERR_HIP, "kmr_dedup_fragments: radix sort (size query)");
-		HIPCHK(h, b_tmp.alloc(std::max<size_t>(tmp_bytes, 256)));
-		/* least significant word first; the sort is stable, so equal keys keep ascending pair position */
-		for (uint32_t w = P.W; w-- > 0;) {
-			hipLaunchKernelGGL(dedup_gather_kernel, cgrid, block, 0, h->stream, (const unsigned long long *)(keys + (size_t)w * np), (const uint32_t *)perm, c, kin);
-			HIPCHK(h, hipGetLastError());
-			if (kmr::sort_pairs_u64_u32(b_tmp.get(), &tmp_bytes, kin, kout, perm, perm2, c, h->stream) != 0) return fail(h, KMR_ERR_HIP, "kmr_dedup_fragments: radix sort");
-			std::swap(perm, perm2);
-		}
-		timer.mark(3, h->stream);
-		/* groups, and those of two members and more */
-		HIPCHK(h, alloc_n(b_head, &head, c)); HIPCHK(h, alloc_n(b_hscan, &hscan, c + 1)); HIPCHK(h, alloc_n(b_start, &start, c + 1));
-		HIPCHK(h, alloc_n(b_keep, &keep, c)); HIPCHK(h, alloc_n(b_kscan, &kscan, c + 1)); HIPCHK(h, alloc_n(b_first, &first, c)); HIPCHK(h, alloc_n(b_grp, &grp, c));
-		hipLaunchKernelGGL(dedup_heads_kernel, cgrid, block, 0, h->stream, (const unsigned long long *)keys, np, P.W, (const uint32_t *)perm, c, head);
-		HIPCHK(h, hipGetLastError());
-		rc = exclusive_scan(h, head, c, hscan); if (rc) return rc;
-		hipLaunchKernelGGL(dedup_starts_kernel, cgrid, block, 0, h->stream, (const uint32_t *)head, (const uint64_t *)hscan, c, start);
-		hipLaunchKernelGGL(dedup_keep_kernel, cgrid, block, 0, h->stream, (const uint64_t *)hscan, (const uint64_t *)start, c, keep);
-		HIPCHK(h, hipGetLastError());
-		rc = exclusive_scan(h, keep, c, kscan); if (rc) return rc;
-		hipLaunchKernelGGL(dedup_kept_kernel, cgrid, block, 0, h->stream, (const uint32_t *)keep, (const uint64_t *)kscan, (const uint64_t *)start, (const uint32_t *)perm, c, first, grp);
-		HIPCHK(h, hipGetLastError());
-		/* the second: the number of groups sizes everything behind */
-		HIPCHK(h, hipMemcpyAsync(&K, kscan + c, 8, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(h, hipStreamSynchronize(h->stream));
-	} else timer.mark(3, h->stream);
-	/* the consensus batch (empty if nothing was collapsed) */
-	const uint64_t n_new = K * P.sides;
-	if (n_new >= 0xffffffffull) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_dedup_fragments: more than 2^32 - 2 consensus reads");
-	dd->cons = new kmr_reads;
-	kmr_reads *cr = dd->cons;
-	cr->device = h->device; cr->n = n_new; cr->input_base = h->cfg.fastq_start_char;
-	uint64_t *coff, *cno, *gfirst; uint32_t *cnl, *gsize;
-	HIPCHK(h, alloc_n(cr->offsets, &coff, n_new + 1)); HIPCHK(h, alloc_n(cr->name_off, &cno, std::max<uint64_t>(n_new, 1))); HIPCHK(h, alloc_n(cr->name_len, &cnl, std::max<uint64_t>(n_new, 1)));
-	HIPCHK(h, alloc_n(dd->group_first, &gfirst, std::max<uint64_t>(K, 1))); HIPCHK(h, alloc_n(dd->group_size, &gsize, std::max<uint64_t>(K, 1)));
-	uint64_t name_total = 0;
-	timer.mark(4, h->stream);
-	if (K) {
-		/* output order: ascending position of the first member */
-		HIPCHK(h, alloc_n(b_first2, &first2, K)); HIPCHK(h, alloc_n(b_grp2, &grp2, K));
-		size_t tmp_bytes = 0;
-		if (kmr::sort_pairs_u64_u32(nullptr, &tmp_bytes, first, first2, grp, grp2, K, h->stream) != 0) return fail(h, KMR_ERR_HIP, "kmr_dedup_fragments: radix sort (size query)");
-		if (b_tmp.cap() < tmp_bytes) { HIPCHK(h, hipStreamSynchronize(h->stream)); HIPCHK(h, b_tmp.alloc(tmp_bytes)); }
-		if (kmr::sort_pairs_u64_u32(b_tmp.get(), &tmp_bytes, first, first2, grp, grp2, K, h->stream) != 0) return fail(h, KMR_ERR_HIP, "kmr_dedup_fragments: radix sort");
-		DedupGroups G; G.perm = perm; G.flip = flip; G.start = start; G.ogroup = grp2; G.K = K;
-		uint32_t *len, *nb; uint64_t *nscan; DedupMember *members;
-		HIPCHK(h, alloc_n(b_len, &len, n_new)); HIPCHK(h, alloc_n(b_nb, &nb, n_new)); HIPCHK(h, alloc_n(b_nscan, &nscan, n_new + 1)); HIPCHK(h, alloc_n(b_members, &members, (size_t)c * P.sides));
-		hipLaunchKernelGGL(dedup_size_kernel, dim3(grid_for(n_new)), block, 0, h->stream, P, G, len, nb, gfirst, gsize, tot);
-		HIPCHK(h, hipGetLastError());
-		rc = exclusive_scan(h, len, n_new, coff); if (rc) return rc;
-		rc = exclusive_scan(h, nb, n_new, nscan); if (rc) return rc;
-		/* the third: the bases and name bytes of the batch, what was collapsed, the error word */
-		HIPCHK(h, hipMemcpyAsync(&cr->total, coff + n_new, 8, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(h, hipMemcpyAsync(&name_total, nscan + n_new, 8, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(h, hipMemcpyAsync(&totals[DEDUP_T_AFFECTED], tot + DEDUP_T_AFFECTED, 16, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(h, hipStreamSynchronize(h->stream));
-		if (totals[DEDUP_T_ERR] & DEDUP_ERR_NAME) return fail(h, KMR_ERR_INVALID_ARG, "a read's name span lies outside the text handed in (pass the text the batch was ingested from)");
-		uint8_t *cb, *cq, *names;
-		HIPCHK(h, alloc_n(cr->bases, &cb, cr->total + 64)); HIPCHK(h, alloc_n(cr->quals, &cq, cr->total + 64)); HIPCHK(h, alloc_n(dd->names, &names, name_total));
-		HIPCHK(h, hipMemsetAsync(cb + cr->total, 0, 64, h->stream)); HIPCHK(h, hipMemsetAsync(cq + cr->total, 0, 64, h->stream));
-		timer.mark(4, h->stream);
-		hipLaunchKernelGGL(dedup_consensus_kernel, dim3((unsigned)std::min<uint64_t>((n_new + DEDUP_WAVES - 1) / DEDUP_WAVES, (uint64_t)num_cus(h) * 8)), dim3(DEDUP_THREADS), 0, h->stream,
-		                   P, G, tables, (const uint64_t *)coff, (const uint64_t *)nscan, members, cb, cq, names, cno, cnl);
-		HIPCHK(h, hipGetLastError());
-		timer.mark(5, h->stream);
-		hipLaunchKernelGGL(dedup_discard_kernel, dim3(grid_for(c)), block, 0, h->stream, P, (const uint32_t *)perm, (const uint64_t *)hscan, (const uint32_t *)keep, c, disc);
-		HIPCHK(h, hipGetLastError());
-		timer.mark(6, h->stream);
-		HIPCHK(h, hipStreamSynchronize(h->stream));      /* the temporaries above go */
-	} else {
-		uint8_t *cb, *cq;
-		HIPCHK(h, alloc_n(cr->bases, &cb, (size_t)64)); HIPCHK(h, alloc_n(cr->quals, &cq, (size_t)64));
-		HIPCHK(h, hipMemsetAsync(cb, 0, 64, h->stream)); HIPCHK(h, hipMemsetAsync(cq, 0, 64, h->stream)); HIPCHK(h, hipMemsetAsync(coff, 0, 8, h->stream));
-		timer.mark(5, h->stream); timer.mark(6, h->stream);
-		HIPCHK(h, hipStreamSynchronize(h->stream));
-	}
-	dd->n_groups = K; dd->affected = totals[DEDUP_T_AFFECTED]; dd->name_bytes = name_total;
-	h->last_dedup_ms = timer.ms(0, 6); h->last_dedup_key_ms = timer.ms(0, 1); h->last_dedup_sort_ms = c >= 2 ? timer.ms(2, 3) : 0.0; h->last_dedup_consensus_ms = K ? timer.ms(4, 5) : 0.0;
-	drain.armed = false;      /* (waited for above) */
-	*out = dd.release();
-	return KMR_OK;
-}
-
-static int dedup_any(kmr_handle *h, const kmr_reads *r, const void *text, uint64_t text_len, bool text_on_device, const kmr_pairs *pairs, const uint8_t *discarded, const kmr_dedup_config *cfg, kmr_dedup **out) {
-	if (out) *out = nullptr;
-	int rc = dedup_check_config(h, cfg); if (rc) return rc;
-	if (!h || !r || !pairs || !out || (text_len && !text)) return fail(h, KMR_ERR_INVALID_ARG, "kmr_dedup_fragments: NULL argument");
-	if (r->device != h->device || pairs->device != h->device) return fail(h, KMR_ERR_INVALID_ARG, "read batch or pair list lives on another device");
-	if (pairs->n != r->n) return fail(h, KMR_ERR_INVALID_ARG, "kmr_dedup_fragments: the pair list belongs to a batch of " + std::to_string(pairs->n) + " reads, not " + std::to_string(r->n));
-	if (r->n >= 0xffffffffull) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_dedup_fragments: a batch holds fewer than 2^32 - 1 reads (pair positions of the sort are 32-bit)");
-	hipSetDevice(h->device);
-	DevBuf b_text, b_disc;
-	const uint8_t *dtext = (const uint8_t *)text, *ddisc = nullptr;
-	if (!text_on_device) { rc = select_upload(h, b_text, (const uint8_t *)text, r->n ? text_len : 0, &dtext); if (rc) return rc; }
-	rc = select_upload(h, b_disc, discarded, r->n, &ddisc); if (rc) return rc;
-	rc = dedup_core(h, r, dtext, text_len, pairs, ddisc, cfg, out);
-	if (rc) hipStreamSynchronize(h->stream);      /* the uploads above must have landed before their buffers go */
-	return rc;
-}
-int kmr_dedup_fragments(kmr_handle *h, const kmr_reads *reads, const char *text, uint64_t text_len, const kmr_pairs *pairs, const uint8_t *discarded, const kmr_dedup_config *cfg, kmr_dedup **out) {
-	return dedup_any(h, reads, text, text_len, false, pairs, discarded, cfg, out);
-}
-int kmr_dedup_fragments_dev(kmr_handle *h, const kmr_reads *reads, const void *dev_text, uint64_t text_len, const kmr_pairs *pairs, const uint8_t *discarded, const kmr_dedup_config *cfg, kmr_dedup **out) {
-	return dedup_any(h, reads, dev_text, text_len, true, pairs, discarded, cfg, out);
-}
-int kmr_dedup_info(const kmr_dedup *d, uint64_t *n_groups, uint64_t *n_new_reads, uint64_t *affected, uint64_t skipped[4]) {
-	if (!d) return KMR_ERR_INVALID_ARG;
-	if (n_groups) *n_groups = d->n_groups; if (n_new_reads) *n_new_reads = d->cons ? d->cons->n : 0; if (affected) *affected = d->affected;
-	if (skipped) for (int i = 0; i < 4; i++) skipped[i] = d->skipped[i];
-	return KMR_OK;
-}
-int kmr_dedup_copy(const kmr_dedup *d, uint8_t *discarded_out, uint64_t *group_first, uint32_t *group_size) {
-	if (!d) return KMR_ERR_INVALID_ARG;
-	hipSetDevice(d->device);
-	hipError_t e = hipSuccess;
-	if (discarded_out && d->n) e = hipMemcpy(discarded_out, d->disc.get<uint8_t>(), d->n, hipMemcpyDeviceToHost);
-	if (group_first && d->n_groups && e == hipSuccess) e = hipMemcpy(group_first, d->group_first.get<uint64_t>(), 8 * d->n_groups, hipMemcpyDeviceToHost);
-	if (group_size && d->n_groups && e == hipSuccess) e = hipMemcpy(group_size, d->group_size.get<uint32_t>(), 4 * d->n_groups, hipMemcpyDeviceToHost);
-	return e == hipSuccess ? KMR_OK : KMR_ERR_HIP;
-}
-int kmr_dedup_device_ptrs(const kmr_dedup *d, void **dev_discarded, void **dev_group_first, void **dev_group_size) {
-	if (!d) return KMR_ERR_INVALID_ARG;
-	if (dev_discarded) *dev_discarded = d->disc.get<uint8_t>(); if (dev_group_first) *dev_group_first = d->group_first.get<uint64_t>(); if (dev_group_size) *dev_group_size = d->group_size.get<uint32_t>();
-	return KMR_OK;
-}
-int kmr_dedup_reads(const kmr_dedup *d, const kmr_reads **consensus, const void **dev_name_text, uint64_t *name_text_len) {
-	if (!d) return KMR_ERR_INVALID_ARG;
-	if (consensus) *consensus = d->cons; if (dev_name_text) *dev_name_text = d->names.get<uint8_t>(); if (name_text_len) *name_text_len = d->name_bytes;
-	return KMR_OK;
-}
-int kmr_dedup_names_copy(const kmr_dedup *d, char *dst, uint64_t capacity) {
-	if (!d || (d->name_bytes && !dst)) return KMR_ERR_INVALID_ARG;
-	if (capacity < d->name_bytes) return KMR_ERR_CAPACITY;
-	hipSetDevice(d->device);
-	if (d->name_bytes && hipMemcpy(dst, d->names.get<uint8_t>(), d->name_bytes, hipMemcpyDeviceToHost) != hipSuccess) return KMR_ERR_HIP;
-	return KMR_OK;
-}
-void kmr_dedup_free(kmr_dedup *d) {
-	if (!d) return;
-	hipSetDevice(d->device);
-	delete d->cons;
-	delete d;      /* (its buffers are freed on this device) */
-}
-
-/* ---- a14: the mercount / mergraph text on the device (kmr_dump.hpp) ---------- */
-/* The common part of kmr_dump_text_size and kmr_dump_text: argument checks, the size pass over weak entries [lo, hi) and, when `out`
- * is given, the writer. */
-static int dump_core(kmr_handle *h, int kind, uint32_t min_depth, uint64_t lo, uint64_t hi, uint64_t *kept, uint64_t *bytes, kmr_text **out) {
-	if (out) *out = nullptr;
-	if (!h) return KMR_ERR_INVALID_ARG;
-	if (kind != KMR_DUMP_MERCOUNT && kind != KMR_DUMP_MERGRAPH) return fail(h, KMR_ERR_INVALID_ARG, "unknown kmr_dump_kind");
-	if (!h->finalized) return fail(h, KMR_ERR_STATE, "dump before kmr_finalize");
-	const bool graph = kind == KMR_DUMP_MERGRAPH;
-	if (graph && !h->ext) return fail(h, KMR_ERR_STATE, "mergraph needs value_kind = KMR_VALUE_EXT");
-	const uint64_t n_map = h->weak.present ? h->weak.n : 0;
-	if (hi > n_map) hi = n_map;
-	if (lo > hi) return fail(h, KMR_ERR_INVALID_ARG, "dump: entry_lo lies behind entry_hi (entry_hi is clamped to the weak map's entries)");
-	hipSetDevice(h->device);
-	std::unique_ptr<kmr_text, void (*)(kmr_text *)> tx(new kmr_text, kmr_text_free);
-	tx->device = h->device;
-	h->last_dump_size_ms = h->last_dump_write_ms = 0;
-	const uint64_t n = hi - lo;
-	if (n) {
-		DumpParams P;
-		P.keys = h->weak.keys.get<uint64_t>(); P.vals = h->weak.vals.get<uint32_t>(); P.vw = h->ext ? 15u : 3u; P.k = h->k; P.graph = graph ? 1u : 0u;
-		P.min_depth = (int32_t)min_depth; P.lo = lo; P.n = n;
-		DevBuf b_len, b_off; uint32_t *len; uint64_t *off;      /* off[n] = bytes, off[n + 1] = kept entries */
-		HIPCHK(h, alloc_n(b_len, &len, n)); HIPCHK(h, alloc_n(b_off, &off, n + 2));
-		SelectTimer timer(h->tune.dump_timing);
-		timer.mark(0, h->stream);
-		HIPCHK(h, hipMemsetAsync(off + n + 1, 0, 8, h->stream));
-		hipLaunchKernelGGL(dump_size_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, P, len, (unsigned long long *)(off + n + 1));
-		HIPCHK(h, hipGetLastError());
-		int rc = exclusive_scan(h, len, n, off); if (rc) return rc;
-		uint64_t totals[2] = {0, 0};
-		HIPCHK(h, hipMemcpyAsync(totals, off + n, 16, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));      /* the one copy that brings sizes back */
-		tx->bytes = totals[0]; tx->kept = totals[1];
-		if (out && tx->bytes) HIPCHK(h, tx->text.alloc((tx->bytes + 15) & ~(uint64_t)15));
-		timer.mark(1, h->stream);      /* (behind the allocation: the events then bracket the writer alone) */
-		if (out && tx->bytes) {
-			const uint64_t tiles = (tx->bytes + DUMP_TILE - 1) / DUMP_TILE;
-			const uint64_t per_block = (tiles + (uint64_t)num_cus(h) * 16 - 1) / ((uint64_t)num_cus(h) * 16);
-			const unsigned blocks = (unsigned)((tiles + per_block - 1) / per_block);
-			uint8_t *dout = tx->text.get<uint8_t>();
-			with_w(h, [&](auto W) { hipLaunchKernelGGL(dump_write_kernel<W()>, dim3(blocks), dim3(DUMP_THREADS), 0, h->stream, P, (const uint64_t *)off, tx->bytes, per_block, dout); return 0; });
-			HIPCHK(h, hipGetLastError());
-		}
-		timer.mark(2, h->stream);
-		HIPCHK(h, hipStreamSynchronize(h->stream));
-		h->last_dump_size_ms = timer.ms(0, 1); h->last_dump_write_ms = timer.ms(1, 2);
-	}
-	if (kept) *kept = tx->kept;
-	if (bytes) *bytes = tx->bytes;
-	if (out) *out = tx.release();
-	return KMR_OK;
-}
-
-int kmr_dump_text_size(kmr_handle *h, int kind, uint32_t min_depth, uint64_t entry_lo, uint64_t entry_hi, uint64_t *kept, uint64_t *bytes) {
-	if (!h || !kept || !bytes) return KMR_ERR_INVALID_ARG;
-	return dump_core(h, kind, min_depth, entry_lo, entry_hi, kept, bytes, nullptr);
-}
-int kmr_dump_text(kmr_handle *h, int kind, uint32_t min_depth, uint64_t entry_lo, uint64_t entry_hi, kmr_text **out) {
-	if (!h || !out) { if (out) *out = nullptr; return KMR_ERR_INVALID_ARG; }
-	return dump_core(h, kind, min_depth, entry_lo, entry_hi, nullptr, nullptr, out);
-}
-int kmr_text_info(const kmr_text *t, uint64_t *kept, uint64_t *bytes) {
-	if (!t) return KMR_ERR_INVALID_ARG;
-	if (kept) *kept = t->kept; if (bytes) *bytes = t->bytes;
-	return KMR_OK;
-}
-int kmr_text_copy(const kmr_text *t, char *dst, uint64_t capacity) {
-	if (!t || (t->bytes && !dst)) return KMR_ERR_INVALID_ARG;
-	if (capacity < t->bytes) return KMR_ERR_CAPACITY;
-	hipSetDevice(t->device);
-	return !t->bytes || hipMemcpy(dst, t->text.get<uint8_t>(), t->bytes, hipMemcpyDeviceToHost) == hipSuccess ? KMR_OK : KMR_ERR_HIP;
-}
-int kmr_text_device_ptr(const kmr_text *t, void **dev_text) {
-	if (!t || !dev_text) return KMR_ERR_INVALID_ARG;
-	*dev_text = t->text.get<uint8_t>();
-	return KMR_OK;
-}
-void kmr_text_free(kmr_text *t) {
-	if (!t) return;
-	hipSetDevice(t->device);
-	delete t;      /* (its buffer is freed on this device) */
-}
-
-/* The file-appending forms: the text in pieces of entries whose text stays under the staging bound whatever their numbers are (a
- * count has at most 5 digits, a tally at most 10), each copied to the host and appended. */
-static int dump_file(kmr_handle *h, const char *path, uint32_t min_depth, bool graph) {
-	if (!h || !path) return KMR_ERR_INVALID_ARG;
-	if (!h->finalized) return fail(h, KMR_ERR_STATE, "dump before kmr_finalize");
-	if (graph && !h->ext) return fail(h, KMR_ERR_STATE, "mergraph needs value_kind = KMR_VALUE_EXT");
-	const uint64_t n = h->weak.present ? h->weak.n : 0;
-	const uint64_t bound = h->tune.dump_piece_bytes ? h->tune.dump_piece_bytes : (uint64_t)KMR_DUMP_PIECE_BYTES;
-	const uint64_t entry_max = graph ? 2ull * (h->k + 15 + 12 * 10) : 2ull * (h->k + 2 + 5);
-	const uint64_t step = std::max<uint64_t>(1, bound / entry_max);
-	std::unique_ptr<FILE, int (*)(FILE *)> f(fopen(path, "a"), fclose);
-	if (!f) return fail(h, KMR_ERR_INVALID_ARG, std::string("cannot open ") + path);
-	std::vector<char> stage;
-	for (uint64_t lo = 0; lo < n; lo += step) {
-		kmr_text *t = nullptr;
-		int rc = dump_core(h, graph ? KMR_DUMP_MERGRAPH : KMR_DUMP_MERCOUNT, min_depth, lo, std::min(n, lo + step), nullptr, nullptr, &t); if (rc) return rc;
-		std::unique_ptr<kmr_text, void (*)(kmr_text *)> tx(t, kmr_text_free);
-		if (!tx->bytes) continue;
-		if (stage.size() < tx->bytes) stage.resize(tx->bytes);
-		HIPCHK(h, hipMemcpy(stage.data(), tx->text.get<uint8_t>(), tx->bytes, hipMemcpyDeviceToHost));
-		if (fwrite(stage.data(), 1, tx->bytes, f.get()) != tx->bytes) return fail(h, KMR_ERR_INVALID_ARG, std::string("cannot write ") + path);
-	}
-	return KMR_OK;
-}
-int kmr_dump_mercount(kmr_handle *h, const char *path, uint32_t min_depth) { return dump_file(h, path, min_depth, false); }
-int kmr_dump_mergraph(kmr_handle *h, const char *path, uint32_t min_depth) { return dump_file(h, path, min_depth, true); }
-
-/* ---- f2: the batch as 2-bit packed reads + markups -------------------------- */
-int kmr_reads_twobit(kmr_handle *h, const kmr_reads *r, uint8_t *twobit, uint64_t twobit_capacity, uint64_t *twobit_offsets,
-                     uint32_t *markup_pos, char *markup_char, uint64_t markup_capacity, uint64_t *markup_offsets,
-                     uint64_t *twobit_bytes, uint64_t *n_markups) {
-	if (!h || !r) return KMR_ERR_INVALID_ARG;
-	if (r->device != h->device) return fail(h, KMR_ERR_INVALID_ARG, "read batch lives on another device");
-	hipSetDevice(h->device);
-	const uint64_t n = r->n;
-	DevBuf b_dlen, b_dcnt, b_dtb, b_dmk, b_dtw, b_dmp, b_dmc; uint32_t *dlen, *dcnt; uint64_t *dtb, *dmk;
-	HIPCHK(h, alloc_n(b_dlen, &dlen, n + 1)); HIPCHK(h, alloc_n(b_dcnt, &dcnt, n + 1)); HIPCHK(h, alloc_n(b_dtb, &dtb, n + 1)); HIPCHK(h, alloc_n(b_dmk, &dmk, n + 1));
-	uint64_t tb_total = 0, mk_total = 0;
-	if (n) {
-		hipLaunchKernelGGL(twobit_count_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, r->bases.get<uint8_t>(), r->offsets.get<uint64_t>(), n, dlen, dcnt);
-		HIPCHK(h, hipGetLastError());
-		int rc = exclusive_scan(h, dlen, n, dtb); if (rc) return rc;
-		rc = exclusive_scan(h, dcnt, n, dmk); if (rc) return rc;
-		HIPCHK(h, hipMemcpy(&tb_total, dtb + n, 8, hipMemcpyDeviceToHost)); HIPCHK(h, hipMemcpy(&mk_total, dmk + n, 8, hipMemcpyDeviceToHost));
-	} else { HIPCHK(h, hipMemset(dtb, 0, 8)); HIPCHK(h, hipMemset(dmk, 0, 8)); }
-	if (twobit_bytes) *twobit_bytes = tb_total; if (n_markups) *n_markups = mk_total;
-	if (!twobit && !markup_pos && !markup_char && !twobit_offsets && !markup_offsets) return KMR_OK;      /* sizes only */
-	if ((twobit && twobit_capacity < tb_total) || ((markup_pos || markup_char) && markup_capacity < mk_total)) return KMR_ERR_CAPACITY;
-	uint8_t *dtw, *dmc; uint32_t *dmp;
-	HIPCHK(h, alloc_n(b_dtw, &dtw, tb_total)); HIPCHK(h, alloc_n(b_dmp, &dmp, mk_total)); HIPCHK(h, alloc_n(b_dmc, &dmc, mk_total));
-	if (n) {
-		hipLaunchKernelGGL(twobit_pack_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, r->bases.get<uint8_t>(), r->offsets.get<uint64_t>(), n, dtb, dmk, dtw, dmp, dmc);
-		HIPCHK(h, hipGetLastError());
-	}
-	HIPCHK(h, hipStreamSynchronize(h->stream));
-	hipError_t e = hipSuccess;
-	if (twobit && tb_total) e = hipMemcpy(twobit, dtw, tb_total, hipMemcpyDeviceToHost);
-	if (e == hipSuccess && twobit_offsets) e = hipMemcpy(twobit_offsets, dtb, 8 * (n + 1), hipMemcpyDeviceToHost);
-	if (e == hipSuccess && markup_pos && mk_total) e = hipMemcpy(markup_pos, dmp, 4 * mk_total, hipMemcpyDeviceToHost);
-	if (e == hipSuccess && markup_char && mk_total) e = hipMemcpy(markup_char, dmc, mk_total, hipMemcpyDeviceToHost);
-	if (e == hipSuccess && markup_offsets) e = hipMemcpy(markup_offsets, dmk, 8 * (n + 1), hipMemcpyDeviceToHost);
-	HIPCHK(h, e);
-	return KMR_OK;
-}
-
-int kmr_reads_from_twobit(kmr_handle *h, const uint8_t *twobit, const uint64_t *twobit_offsets, const uint64_t *offsets,
-                          const uint64_t *markup_offsets, const uint32_t *markup_pos, const char *markup_char,
-                          const char *quals, int uniform_quality, uint64_t n_reads, kmr_reads **out) {
-	if (!h || !out || !offsets || !twobit_offsets || (n_reads && !twobit)) return KMR_ERR_INVALID_ARG;
-	if (uniform_quality < 0 || uniform_quality > 255 || (quals && uniform_quality)) return fail(h, KMR_ERR_INVALID_ARG, "uniform_quality: 0, or the one quality character of a batch without a quality array");
-	*out = nullptr;
-	hipSetDevice(h->device);
-	const uint64_t first = offsets[0], total = offsets[n_reads] - first, tbytes = twobit_offsets[n_reads] - twobit_offsets[0];
-	const uint64_t nm = markup_offsets ? markup_offsets[n_reads] - markup_offsets[0] : 0;
-	std::unique_ptr<kmr_reads, void (*)(kmr_reads *)> r(new kmr_reads, kmr_reads_free);
-	r->device = h->device; r->n = n_reads; r->total = total; r->input_base = h->cfg.fastq_start_char;
-	HIPCHK(h, r->bases.alloc(total + 64)); HIPCHK(h, r->quals.alloc(total + 64));
-	HIPCHK(h, r->offsets.alloc(8 * (n_reads + 1)));
-	HIPCHK(h, r->name_off.alloc(8 * std::max<uint64_t>(n_reads, 1))); HIPCHK(h, r->name_len.alloc(4 * std::max<uint64_t>(n_reads, 1)));
-	HIPCHK(h, hipMemset(r->bases.get<uint8_t>() + total, 0, 64)); HIPCHK(h, hipMemset(r->quals.get<uint8_t>() + total, 0, 64));
-	HIPCHK(h, hipMemset(r->name_off.get<uint64_t>(), 0, 8 * std::max<uint64_t>(n_reads, 1))); HIPCHK(h, hipMemset(r->name_len.get<uint32_t>(), 0, 4 * std::max<uint64_t>(n_reads, 1)));
-	/* qualities: the array, the one character, or Read::REF_QUAL (a batch always has a quality array; REF_QUAL reads weigh 1) */
-	if (quals) { if (total) HIPCHK(h, hipMemcpy(r->quals.get<uint8_t>(), quals + first, total, hipMemcpyHostToDevice)); }
-	else HIPCHK(h, hipMemset(r->quals.get<uint8_t>(), uniform_quality ? uniform_quality : 127, total));
-	if (!n_reads) { HIPCHK(h, hipMemset(r->offsets.get<uint64_t>(), 0, 8)); *out = r.release(); return KMR_OK; }
-	DevBuf b_dtb, b_dto, b_doff, b_dmo, b_dmp, b_dmc; uint8_t *dtb, *dmc = nullptr; uint64_t *dto, *doff, *dmo = nullptr; uint32_t *dmp = nullptr;
-	HIPCHK(h, alloc_n(b_dtb, &dtb, tbytes + 64)); HIPCHK(h, alloc_n(b_dto, &dto, n_reads + 1)); HIPCHK(h, alloc_n(b_doff, &doff, n_reads + 1));
-	std::vector<uint64_t> rel(n_reads + 1), trel(n_reads + 1), mrel(markup_offsets ? n_reads + 1 : 0);
-	for (uint64_t i = 0; i <= n_reads; i++) { rel[i] = offsets[i] - first; trel[i] = twobit_offsets[i] - twobit_offsets[0]; if (markup_offsets) mrel[i] = markup_offsets[i] - markup_offsets[0]; }
-	if (tbytes) HIPCHK(h, hipMemcpy(dtb, twobit + twobit_offsets[0], tbytes, hipMemcpyHostToDevice));
-	HIPCHK(h, hipMemcpy(dto, trel.data(), 8 * (n_reads + 1), hipMemcpyHostToDevice)); HIPCHK(h, hipMemcpy(doff, rel.data(), 8 * (n_reads + 1), hipMemcpyHostToDevice));
-	hipLaunchKernelGGL(twobit_unpack_kernel, dim3((unsigned)std::min<uint64_t>((n_reads + 255) / 256, (uint64_t)num_cus(h) * 32)), dim3(256), 0, h->stream, (const uint8_t *)dtb, (const uint64_t *)dto, (const uint64_t *)doff, n_reads, r->bases.get<uint8_t>(), r->offsets.get<uint64_t>());
-	HIPCHK(h, hipGetLastError());
-	if (nm) {
-		HIPCHK(h, alloc_n(b_dmo, &dmo, n_reads + 1)); HIPCHK(h, alloc_n(b_dmp, &dmp, nm)); HIPCHK(h, alloc_n(b_dmc, &dmc, nm));
-		HIPCHK(h, hipMemcpy(dmo, mrel.data(), 8 * (n_reads + 1), hipMemcpyHostToDevice));
-		HIPCHK(h, hipMemcpy(dmp, markup_pos + markup_offsets[0], 4 * nm, hipMemcpyHostToDevice)); HIPCHK(h, hipMemcpy(dmc, markup_char + markup_offsets[0], nm, hipMemcpyHostToDevice));
-		hipLaunchKernelGGL(twobit_markup_kernel, dim3(grid_for(n_reads)), dim3(256), 0, h->stream, (const uint64_t *)dmo, (const uint32_t *)dmp, (const uint8_t *)dmc, (const uint64_t *)r->offsets.get<uint64_t>(), n_reads, r->bases.get<uint8_t>());
-		HIPCHK(h, hipGetLastError());
-	}
-	HIPCHK(h, hipStreamSynchronize(h->stream));
-	*out = r.release();
-	return KMR_OK;
-}
-
 /* ---- stateless helpers ------------------------------------------------- */
 uint64_t kmr_hash(const uint8_t *key, uint32_t len) {
 	if (!key || len == 0 || len > 32) return 0;

@@ -1,0 +1,1188 @@
+/*
+ * kmr_stages.hip -- the read stages of include/kmernator_amd.h: FASTQ ingest and the kmr_reads batch, its two-bit form, the artifact
+ * filter, read selection and its output text, identifyPairs, duplicate-fragment collapse, and the mercount / mergraph text.
+ *
+ * Host logic only, as kmr_api.hip (the spectrum, which these stages read through kmr_host.hpp); the kernels are the stage headers',
+ * each of which this translation unit alone includes.  A stage costs its kernels and a page here: what the stages share is below --
+ * the call's temporaries (Scratch), inputs from host or device memory (to_device), the radix sort with its scratch (sort_reserve,
+ * sort_pairs), result objects (make_result, free_on_device, copy_out).
+ */
+#include <cctype>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <mutex>
+
+#include "kmr_host.hpp"
+#include "kmr_ingest.hpp"
+#include "kmr_artifact.hpp"
+#include "kmr_select.hpp"
+#include "kmr_pairs.hpp"
+#include "kmr_dedup.hpp"
+#include "kmr_dump.hpp"
+
+using namespace kmr;
+
+namespace {
+
+/* The temporaries of one call on the handle's stream: take() allocates a block of n elements of T (alloc_n: one allocation, 256 bytes
+ * at least) that lives until the call returns.  A return with work still queued -- an error path -- waits for the stream before the
+ * blocks go; a call that has waited for its last work itself says done().  sort_buf: the radix sort's scratch (sort_reserve). */
+class Scratch {
+public:
+	explicit Scratch(kmr_handle *h) : h_(h) {}
+	~Scratch() { if (armed_ && (!bufs_.empty() || sort_buf)) hipStreamSynchronize(h_->stream); }
+	template <class T> hipError_t take(T **p, size_t n) { bufs_.emplace_back(); return alloc_n(bufs_.back(), p, n); }
+	void done() { armed_ = false; }
+	DevBuf sort_buf; size_t sort_bytes = 0;
+private:
+	kmr_handle *h_; std::vector<DevBuf> bufs_; bool armed_ = true;
+};
+
+/* an input array as device memory: as it is if it lives there (on_device), else copied into a block of tmp on the stream; an absent
+ * or empty host array is null */
+template <class T> int to_device(kmr_handle *h, Scratch &tmp, const T *src, uint64_t n, const T **dev, bool on_device = false) {
+	*dev = on_device ? src : nullptr;
+	if (on_device || !src || !n) return 0;
+	T *p = nullptr;
+	HIPCHK(h, tmp.take(&p, n));
+	HIPCHK(h, hipMemcpyAsync(p, src, sizeof(T) * n, hipMemcpyHostToDevice, h->stream));
+	*dev = p;
+	return 0;
+}
+
+/* the library's radix sort (kmr_sort.hip) of n (u64, u32) pairs on the stream.  sort_reserve: the size query; tmp.sort_buf is grown to
+ * it (the stream drained first if the block was in use), so one reservation serves every sort of no more pairs */
+int sort_reserve(kmr_handle *h, Scratch &tmp, size_t n, const char *who) {
+	if (kmr::sort_pairs_u64_u32(nullptr, &tmp.sort_bytes, nullptr, nullptr, nullptr, nullptr, n, h->stream) != 0) return fail(h, KMR_ERR_HIP, std::string(who) + ": radix sort (size query)");
+	if (tmp.sort_buf && tmp.sort_buf.cap() >= tmp.sort_bytes) return 0;
+	if (tmp.sort_buf) HIPCHK(h, hipStreamSynchronize(h->stream));
+	HIPCHK(h, tmp.sort_buf.alloc(std::max<size_t>(tmp.sort_bytes, 256)));
+	return 0;
+}
+int sort_pairs(kmr_handle *h, Scratch &tmp, const unsigned long long *kin, unsigned long long *kout, const uint32_t *vin, uint32_t *vout, size_t n, const char *who) {
+	if (kmr::sort_pairs_u64_u32(tmp.sort_buf.get(), &tmp.sort_bytes, kin, kout, vin, vout, n, h->stream) != 0) return fail(h, KMR_ERR_HIP, std::string(who) + ": radix sort");
+	return 0;
+}
+
+const char *const NAME_SPAN_ERROR = "a read's name span lies outside the text handed in (pass the text the batch was ingested from)";
+
+/* Result objects (kmr_reads, kmr_picks, ...: OnDevice): made on the handle's device and owned until released to the caller; deleted
+ * with that device current, where their buffers are freed; copied out array by array */
+template <class T> void free_on_device(T *x) { if (!x) return; hipSetDevice(x->device); delete x; }
+template <class T> std::unique_ptr<T, void (*)(T *)> make_result(kmr_handle *h) {
+	std::unique_ptr<T, void (*)(T *)> x(new T, free_on_device<T>);
+	x->device = h->device;
+	return x;
+}
+/* copy_out(e, dst, buf, n): n elements of buf to the host array dst, if there is one and nothing failed before */
+template <class T> void copy_out(hipError_t &e, T *dst, const DevBuf &buf, uint64_t n) {
+	if (dst && n && e == hipSuccess) e = hipMemcpy(dst, buf.get<T>(), sizeof(T) * n, hipMemcpyDeviceToHost);
+}
+
+}  // namespace
+
+/* the two-bit launches of the spectrum's packed feed path (kmr_add_reads_twobit_dev) */
+namespace kmr_host {
+int twobit_byte_offsets(kmr_handle *h, const uint64_t *offsets, uint64_t n, uint32_t *len, uint64_t *off) {
+	hipLaunchKernelGGL(twobit_bytes_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, offsets, n, len);
+	HIPCHK(h, hipGetLastError());
+	return exclusive_scan(h, len, n, off);
+}
+int twobit_rel_offsets(kmr_handle *h, const uint64_t *offsets, uint64_t n, uint64_t *rel) {
+	hipLaunchKernelGGL(offsets_rel_kernel, dim3(grid_for(n + 1)), dim3(256), 0, h->stream, offsets, n, rel);
+	HIPCHK(h, hipGetLastError());
+	return 0;
+}
+int twobit_unpack(kmr_handle *h, const uint8_t *twobit, const uint64_t *twobit_off, const uint64_t *offsets, const uint64_t *mk_off, const uint32_t *mk_pos, const uint8_t *mk_char,
+                  uint64_t n, uint8_t *bases, uint64_t *rel) {
+	hipLaunchKernelGGL(twobit_unpack_kernel, dim3((unsigned)std::min<uint64_t>((n + 255) / 256, (uint64_t)num_cus(h) * 32)), dim3(256), 0, h->stream, twobit, twobit_off, offsets, n, bases, rel);
+	HIPCHK(h, hipGetLastError());
+	if (mk_off) {
+		hipLaunchKernelGGL(twobit_markup_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, mk_off, mk_pos, mk_char, (const uint64_t *)rel, n, bases);
+		HIPCHK(h, hipGetLastError());
+	}
+	return 0;
+}
+}  // namespace kmr_host
+
+extern "C" {
+
+/* ---- f2: FASTQ ingest on the device (kmr_ingest.hpp) ------------------------ */
+static int ingest_dev(kmr_handle *h, const uint8_t *text, uint64_t len, uint32_t input_base, int store_comment, kmr_reads **out) {
+	const uint32_t start = h->cfg.fastq_start_char;
+	if (input_base == 0) input_base = start;
+	if ((input_base != 33 && input_base != 64) || (start != 33 && start != 64))
+		return fail(h, KMR_ERR_INVALID_ARG, "fastq quality base must be 33 or 64 (src/Options.h:490)");
+	auto R = make_result<kmr_reads>(h);
+	R->input_base = input_base;
+	DevBuf blk, derr, llen, keep, klen, bbase, lstart, kidx, boff;      /* scratch of this call */
+	const uint64_t nblk = (len + (uint64_t)ING_THREADS * ING_BYTES - 1) / ((uint64_t)ING_THREADS * ING_BYTES);
+	uint64_t n_lines = 0;
+	HIPCHK(h, derr.alloc(8)); HIPCHK(h, hipMemsetAsync(derr.get<uint32_t>(), 0, 8, h->stream));
+	if (nblk) {
+		if (nblk > 0x7fffffffull) return fail(h, KMR_ERR_INVALID_ARG, "FASTQ block too large for one call");
+		HIPCHK(h, blk.alloc(4 * nblk)); HIPCHK(h, bbase.alloc(8 * (nblk + 1)));
+		hipLaunchKernelGGL(ingest_count_lines, dim3((unsigned)nblk), dim3(ING_THREADS), 0, h->stream, text, len, blk.get<uint32_t>());
+		HIPCHK(h, hipGetLastError());
+		{ int rc = exclusive_scan(h, blk.get<uint32_t>(), nblk, bbase.get<uint64_t>()); if (rc) return rc; }
+		HIPCHK(h, hipMemcpy(&n_lines, bbase.get<uint64_t>() + nblk, 8, hipMemcpyDeviceToHost));
+	}
+	if (n_lines % 4 != 0) return fail(h, KMR_ERR_INVALID_ARG, "malformed FASTQ: " + std::to_string(n_lines) + " non-empty lines is not a multiple of 4 (truncated record)");
+	const uint64_t nrec = n_lines / 4;
+	uint64_t n_kept = 0, total = 0;
+	if (nrec) {
+		HIPCHK(h, lstart.alloc(8 * n_lines)); HIPCHK(h, llen.alloc(4 * n_lines));
+		hipLaunchKernelGGL(ingest_index_lines, dim3((unsigned)nblk), dim3(ING_THREADS), 0, h->stream, text, len, bbase.get<uint64_t>(), lstart.get<uint64_t>());
+		hipLaunchKernelGGL(ingest_line_lengths, dim3(grid_for(n_lines)), dim3(256), 0, h->stream, text, len, lstart.get<uint64_t>(), n_lines, llen.get<uint32_t>(), derr.get<uint32_t>());
+		HIPCHK(h, keep.alloc(4 * nrec)); HIPCHK(h, klen.alloc(4 * nrec));
+		HIPCHK(h, kidx.alloc(8 * (nrec + 1))); HIPCHK(h, boff.alloc(8 * (nrec + 1)));
+		hipLaunchKernelGGL(ingest_records, dim3(grid_for(nrec)), dim3(256), 0, h->stream, text, lstart.get<uint64_t>(), llen.get<uint32_t>(), nrec, store_comment, keep.get<uint32_t>(), klen.get<uint32_t>(), derr.get<uint32_t>());
+		HIPCHK(h, hipGetLastError());
+		{ int rc = exclusive_scan(h, keep.get<uint32_t>(), nrec, kidx.get<uint64_t>()); if (rc) return rc; }
+		{ int rc = exclusive_scan(h, klen.get<uint32_t>(), nrec, boff.get<uint64_t>()); if (rc) return rc; }
+		uint32_t e = 0;
+		HIPCHK(h, hipMemcpy(&e, derr.get<uint32_t>(), 4, hipMemcpyDeviceToHost));
+		if (e) {
+			std::string why;
+			if (e & ING_ERR_NAME) why += " a record does not start with '@' or has an empty name;";
+			if (e & ING_ERR_BLANK) why += " an empty line inside a record;";
+			if (e & ING_ERR_PLUS) why += " missing '+' line;";
+			if (e & ING_ERR_LEN) why += " number of bases and quals not equal;";
+			return fail(h, KMR_ERR_INVALID_ARG, "malformed FASTQ:" + why);
+		}
+		HIPCHK(h, hipMemcpy(&n_kept, kidx.get<uint64_t>() + nrec, 8, hipMemcpyDeviceToHost)); HIPCHK(h, hipMemcpy(&total, boff.get<uint64_t>() + nrec, 8, hipMemcpyDeviceToHost));
+	}
+	R->n = n_kept; R->total = total; R->filtered = nrec - n_kept;
+	HIPCHK(h, R->bases.alloc(total + 64)); HIPCHK(h, R->quals.alloc(total + 64)); HIPCHK(h, R->offsets.alloc(8 * (n_kept + 1)));
+	HIPCHK(h, R->name_off.alloc(8 * std::max<uint64_t>(1, n_kept))); HIPCHK(h, R->name_len.alloc(4 * std::max<uint64_t>(1, n_kept)));
+	HIPCHK(h, hipMemsetAsync(R->bases.get<uint8_t>() + total, 0, 64, h->stream)); HIPCHK(h, hipMemsetAsync(R->quals.get<uint8_t>() + total, 0, 64, h->stream));
+	HIPCHK(h, hipMemcpyAsync(R->offsets.get<uint64_t>() + n_kept, &total, 8, hipMemcpyHostToDevice, h->stream));
+	if (nrec) {
+		/* appendFasta rescales every read from the input base to Read::FASTQ_START_CHAR as it is read (src/ReadSet.cpp:324,336) */
+		hipLaunchKernelGGL(ingest_copy, dim3(grid_for(nrec, 4, 1 << 16)), dim3(256), 0, h->stream, text, len, lstart.get<uint64_t>(), llen.get<uint32_t>(), nrec, keep.get<uint32_t>(), kidx.get<uint64_t>(), boff.get<uint64_t>(),
+		                   (int)start - (int)input_base, start, R->bases.get<uint8_t>(), R->quals.get<uint8_t>(), R->offsets.get<uint64_t>(), R->name_off.get<uint64_t>(), R->name_len.get<uint32_t>(), derr.get<uint32_t>() + 1);
+		HIPCHK(h, hipGetLastError());
+		uint32_t flip = 0;
+		HIPCHK(h, hipMemcpyAsync(&flip, derr.get<uint32_t>() + 1, 4, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
+		const uint32_t want = start == 33 ? 64u : 33u;        /* __setFastqStart(the other base), src/ReadSet.h:174-186 */
+		if (flip && want != input_base) {
+			if (total) hipLaunchKernelGGL(ingest_shift_quals, dim3(grid_for(total)), dim3(256), 0, h->stream, R->quals.get<uint8_t>(), total, (int)input_base - (int)want);
+			HIPCHK(h, hipGetLastError());
+			R->input_base = want;
+		}
+	}
+	HIPCHK(h, hipStreamSynchronize(h->stream));
+	*out = R.release();
+	return KMR_OK;
+}
+
+int kmr_ingest_fastq_dev(kmr_handle *h, const void *dev_text, uint64_t len, uint32_t input_quality_base, int store_comment, kmr_reads **out) {
+	if (!h || !out || (len && !dev_text)) return KMR_ERR_INVALID_ARG;
+	*out = nullptr;
+	hipSetDevice(h->device);
+	return ingest_dev(h, (const uint8_t *)dev_text, len, input_quality_base, store_comment, out);
+}
+int kmr_ingest_fastq(kmr_handle *h, const char *text, uint64_t len, uint32_t input_quality_base, int store_comment, kmr_reads **out) {
+	if (!h || !out || (len && !text)) return KMR_ERR_INVALID_ARG;
+	*out = nullptr;
+	hipSetDevice(h->device);
+	DevBuf d;
+	HIPCHK(h, d.alloc(len + 16));
+	hipError_t e = hipMemcpy(d.get(), text, len, hipMemcpyHostToDevice);
+	if (e != hipSuccess) { h->err = std::string("hipMemcpy(FASTQ text): ") + hipGetErrorString(e); return KMR_ERR_HIP; }
+	return ingest_dev(h, d.get<uint8_t>(), len, input_quality_base, store_comment, out);
+}
+/* a device-resident batch from reads the host already parsed (the reference's ReadSet flattened as for kmr_add_reads) */
+int kmr_reads_from_host(kmr_handle *h, const char *bases, const char *quals, const uint64_t *offsets, uint64_t n_reads, kmr_reads **out) {
+	if (!h || !out || !offsets || (n_reads && (!bases || !quals))) return KMR_ERR_INVALID_ARG;
+	*out = nullptr;
+	hipSetDevice(h->device);
+	const uint64_t first = offsets[0], total = offsets[n_reads] - first;
+	auto r = make_result<kmr_reads>(h);
+	r->n = n_reads; r->total = total; r->input_base = h->cfg.fastq_start_char;
+	HIPCHK(h, r->bases.alloc(total + 64)); HIPCHK(h, r->quals.alloc(total + 64));
+	HIPCHK(h, r->offsets.alloc(8 * (n_reads + 1)));
+	HIPCHK(h, r->name_off.alloc(8 * std::max<uint64_t>(n_reads, 1))); HIPCHK(h, r->name_len.alloc(4 * std::max<uint64_t>(n_reads, 1)));
+	HIPCHK(h, hipMemset(r->bases.get<uint8_t>() + total, 0, 64)); HIPCHK(h, hipMemset(r->quals.get<uint8_t>() + total, 0, 64));
+	HIPCHK(h, hipMemset(r->name_off.get<uint64_t>(), 0, 8 * std::max<uint64_t>(n_reads, 1))); HIPCHK(h, hipMemset(r->name_len.get<uint32_t>(), 0, 4 * std::max<uint64_t>(n_reads, 1)));
+	if (total) { HIPCHK(h, hipMemcpy(r->bases.get<uint8_t>(), bases + first, total, hipMemcpyHostToDevice)); HIPCHK(h, hipMemcpy(r->quals.get<uint8_t>(), quals + first, total, hipMemcpyHostToDevice)); }
+	std::vector<uint64_t> rel(n_reads + 1);
+	for (uint64_t i = 0; i <= n_reads; i++) rel[i] = offsets[i] - first;
+	HIPCHK(h, hipMemcpy(r->offsets.get<uint64_t>(), rel.data(), 8 * (n_reads + 1), hipMemcpyHostToDevice));
+	*out = r.release();
+	return KMR_OK;
+}
+void kmr_reads_free(kmr_reads *r) { free_on_device(r); }
+int kmr_reads_info(const kmr_reads *r, uint64_t *n_reads, uint64_t *total_bases, uint32_t *input_quality_base, uint64_t *n_filtered) {
+	if (!r) return KMR_ERR_INVALID_ARG;
+	if (n_reads) *n_reads = r->n; if (total_bases) *total_bases = r->total;
+	if (input_quality_base) *input_quality_base = r->input_base; if (n_filtered) *n_filtered = r->filtered;
+	return KMR_OK;
+}
+int kmr_reads_device_ptrs(const kmr_reads *r, void **bases, void **quals, void **offsets) {
+	if (!r) return KMR_ERR_INVALID_ARG;
+	if (bases) *bases = r->bases.get<uint8_t>(); if (quals) *quals = r->quals.get<uint8_t>(); if (offsets) *offsets = r->offsets.get<uint64_t>();
+	return KMR_OK;
+}
+int kmr_reads_copy(const kmr_reads *r, char *bases, char *quals, uint64_t *offsets, uint64_t *name_off, uint32_t *name_len) {
+	if (!r) return KMR_ERR_INVALID_ARG;
+	hipSetDevice(r->device);
+	hipError_t e = hipSuccess;
+	copy_out(e, (uint8_t *)bases, r->bases, r->total); copy_out(e, (uint8_t *)quals, r->quals, r->total); copy_out(e, offsets, r->offsets, r->n + 1);
+	copy_out(e, name_off, r->name_off, r->n); copy_out(e, name_len, r->name_len, r->n);
+	return e == hipSuccess ? KMR_OK : KMR_ERR_HIP;
+}
+
+/* ---- f4: artifact filter (FilterKnownOddities) --------------------------- */
+}  // extern "C"
+
+struct kmr_artifact_filter : OnDevice {
+	kmr_artifact_config cfg;
+	uint32_t n_seq = 0, remaining_edits = 0, log2cap = 0;
+	uint64_t n_keys = 0;
+	DevBuf d_keys, d_vals;                                         /* open-addressed lookup table */
+	DevBuf d_bits;                                                 /* presence filter in front of it (ART_FILTER_LOG2 bits) */
+	std::vector<uint64_t> keys; std::vector<uint32_t> vals;        /* the same entries on the host, ascending keys */
+};
+
+namespace {
+
+uint32_t art_log2cap(uint64_t n) { uint32_t l = 10; while ((1ull << l) < 2 * n + 16) l++; return l; }
+
+uint64_t art_pack(const char *s, uint32_t len) {      /* TwoBitSequence::compressSequence: anything but ACGT packs as A */
+	uint64_t v = 0;
+	for (uint32_t i = 0; i < len; i++) { const char c = s[i]; v = (v << 2) | (uint64_t)((c == 'C') ? 1 : (c == 'G') ? 2 : (c == 'T') ? 3 : 0); }
+	return v;
+}
+uint64_t art_revcomp_host(uint64_t v, uint32_t len) { uint64_t r = 0; for (uint32_t i = 0; i < len; i++) { r = (r << 2) | (3 - (v & 3)); v >>= 2; } return r; }
+
+/* (re)build the lookup table of the filter from its host entries */
+int art_upload(kmr_handle *h, kmr_artifact_filter *f) {
+	f->d_keys.reset(); f->d_vals.reset();
+	f->n_keys = f->keys.size();
+	f->log2cap = art_log2cap(f->n_keys);
+	const uint64_t cap = 1ull << f->log2cap;
+	HIPCHK(h, f->d_keys.alloc(8 * cap)); HIPCHK(h, f->d_vals.alloc(4 * cap));
+	if (!f->d_bits) HIPCHK(h, f->d_bits.alloc((1u << ART_FILTER_LOG2) / 8));
+	HIPCHK(h, hipMemsetAsync(f->d_bits.get<uint32_t>(), 0, (1u << ART_FILTER_LOG2) / 8, h->stream));
+	Scratch tmp(h); uint64_t *dk; uint32_t *dv;
+	HIPCHK(h, tmp.take(&dk, f->n_keys)); HIPCHK(h, tmp.take(&dv, f->n_keys));
+	if (f->n_keys) { HIPCHK(h, hipMemcpyAsync(dk, f->keys.data(), 8 * f->n_keys, hipMemcpyHostToDevice, h->stream)); HIPCHK(h, hipMemcpyAsync(dv, f->vals.data(), 4 * f->n_keys, hipMemcpyHostToDevice, h->stream)); }
+	ArtifactTable t{f->d_keys.get<uint64_t>(), f->d_vals.get<uint32_t>(), nullptr, f->log2cap, f->d_bits.get<uint32_t>()};
+	hipLaunchKernelGGL(artifact_fill, dim3(1024), dim3(256), 0, h->stream, f->d_keys.get<uint64_t>(), (uint32_t *)nullptr, cap);
+	if (f->n_keys) hipLaunchKernelGGL(artifact_insert, dim3((unsigned)std::min<uint64_t>((f->n_keys + 255) / 256, 4096)), dim3(256), 0, h->stream, t, dk, dv, f->n_keys);
+	HIPCHK(h, hipGetLastError());
+	HIPCHK(h, hipStreamSynchronize(h->stream));
+	tmp.done();
+	return KMR_OK;
+}
+
+/* one round of prepareMaps' edit loop (src/FilterKnownOddities.h:264-282) on the device */
+int art_build_round(kmr_handle *h, kmr_artifact_filter *f) {
+	const uint32_t L = f->cfg.match_length, kb = L / 4;
+	const uint64_t n = f->keys.size();
+	/* the map's iteration order: bucket by bucket (KmerMap(512*1024): 512*1024/32+1 buckets rounded up to 2^15), sorted inside */
+	const uint64_t mask = resize_buckets(512 * 1024 / 32 + 1) - 1;
+	std::vector<std::pair<uint64_t, uint64_t>> order(n);
+	for (uint64_t i = 0; i < n; i++) {
+		uint8_t b[8];
+		for (uint32_t j = 0; j < kb; j++) b[j] = (uint8_t)(f->keys[i] >> (8 * (kb - 1 - j)));
+		order[i] = std::make_pair(kmr_hash(b, kb) & mask, i);
+	}
+	std::sort(order.begin(), order.end());       /* ties inside a bucket: ascending index = ascending key */
+	std::vector<uint64_t> sk(n); std::vector<uint32_t> sv(n);
+	for (uint64_t i = 0; i < n; i++) { sk[i] = f->keys[order[i].second]; sv[i] = f->vals[order[i].second]; }
+	const uint64_t worst = n * (3ull * L + 1);
+	if (worst > (1ull << 32)) return fail(h, KMR_ERR_UNSUPPORTED, "artifact filter: an edit round over " + std::to_string(n) + " keys does not fit the build table");
+	const uint32_t log2cap = art_log2cap(worst);
+	const uint64_t cap = 1ull << log2cap;
+	Scratch tmp(h); uint64_t *tk, *dk, *ok; uint32_t *tv, *tr, *dv, *ov; unsigned long long *cnt;
+	HIPCHK(h, tmp.take(&tk, cap)); HIPCHK(h, tmp.take(&tv, cap)); HIPCHK(h, tmp.take(&tr, cap));
+	HIPCHK(h, tmp.take(&dk, n)); HIPCHK(h, tmp.take(&dv, n)); HIPCHK(h, tmp.take(&cnt, 1));
+	HIPCHK(h, hipMemcpyAsync(dk, sk.data(), 8 * n, hipMemcpyHostToDevice, h->stream));
+	HIPCHK(h, hipMemcpyAsync(dv, sv.data(), 4 * n, hipMemcpyHostToDevice, h->stream));
+	HIPCHK(h, hipMemsetAsync(cnt, 0, 8, h->stream));
+	ArtifactTable t{tk, tv, tr, log2cap, nullptr};
+	hipLaunchKernelGGL(artifact_fill, dim3(2048), dim3(256), 0, h->stream, tk, tr, cap);
+	hipLaunchKernelGGL(artifact_insert, dim3((unsigned)std::min<uint64_t>((n + 255) / 256, 4096)), dim3(256), 0, h->stream, t, dk, dv, n);
+	hipLaunchKernelGGL(artifact_neighbours, dim3((unsigned)std::min<uint64_t>((n * L + 255) / 256, 1u << 20)), dim3(256), 0, h->stream, t, dk, n, L);
+	HIPCHK(h, hipGetLastError());
+	HIPCHK(h, hipStreamSynchronize(h->stream));
+	/* the table is sparse (<= 50 % by construction, a few % in practice): count first, then compact */
+	HIPCHK(h, tmp.take(&ok, worst)); HIPCHK(h, tmp.take(&ov, worst));
+	hipLaunchKernelGGL(artifact_compact, dim3(2048), dim3(256), 0, h->stream, t, dv, ok, ov, cnt);
+	HIPCHK(h, hipGetLastError());
+	unsigned long long m = 0;
+	HIPCHK(h, hipMemcpyAsync(&m, cnt, 8, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipStreamSynchronize(h->stream));
+	std::vector<uint64_t> nk(m); std::vector<uint32_t> nv(m);
+	HIPCHK(h, hipMemcpy(nk.data(), ok, 8 * m, hipMemcpyDeviceToHost)); HIPCHK(h, hipMemcpy(nv.data(), ov, 4 * m, hipMemcpyDeviceToHost));
+	tmp.done();
+	std::vector<uint64_t> idx(m);
+	for (uint64_t i = 0; i < m; i++) idx[i] = i;
+	std::sort(idx.begin(), idx.end(), [&](uint64_t a, uint64_t b) { return nk[a] < nk[b]; });
+	f->keys.resize(m); f->vals.resize(m);
+	for (uint64_t i = 0; i < m; i++) { f->keys[i] = nk[idx[i]]; f->vals[i] = nv[idx[i]]; }
+	return KMR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void kmr_artifact_config_init(kmr_artifact_config *c) {
+	if (!c) return;
+	memset(c, 0, sizeof(*c));
+	c->match_length = 24; c->edit_distance = 2; c->build_edits = 2;      /* _FilterKnownOdditiesOptions(), src/FilterKnownOddities.h:72-75 */
+	c->min_quality = 3; c->fastq_start_char = 33; c->min_read_length = 0.40f;
+}
+
+int kmr_artifact_filter_create(kmr_handle *h, const kmr_artifact_config *cfg, const char *fasta, uint64_t len, kmr_artifact_filter **out) {
+	if (!h || !cfg || !out || (len && !fasta)) return KMR_ERR_INVALID_ARG;
+	*out = nullptr;
+	if (cfg->match_length == 0 || cfg->match_length > 28 || (cfg->match_length & 3))
+		return fail(h, KMR_ERR_INVALID_ARG, "artifact match length must be a multiple of 4 and <= 28 (src/FilterKnownOddities.h:207-209,244)");
+	hipSetDevice(h->device);
+	auto f = make_result<kmr_artifact_filter>(h);
+	f->cfg = *cfg;
+	const uint32_t L = cfg->match_length;
+	/* sequences: read 0 is the empty "no match" read, then the FASTA records in file order (:213-231) */
+	std::vector<std::string> seqs(1);
+	for (uint64_t i = 0; i < len;) {
+		uint64_t e = i; while (e < len && fasta[e] != '\n') e++;
+		uint64_t le = e; if (le > i && fasta[le - 1] == '\r') le--;
+		if (le > i) {
+			if (fasta[i] == '>') seqs.push_back(std::string());
+			else if (seqs.size() > 1) for (uint64_t j = i; j < le; j++) seqs.back().push_back((char)toupper((unsigned char)fasta[j]));
+		}
+		i = e + 1;
+	}
+	f->n_seq = (uint32_t)seqs.size();
+	std::vector<std::pair<uint64_t, uint32_t>> kv;
+	for (uint32_t s = 1; s < f->n_seq; s++) {
+		std::string q = seqs[s];
+		if (cfg->reference_begin == 0 || s < cfg->reference_begin) q += seqs[s].substr(0, L);      /* ReadSet::circularize, src/ReadSet.cpp:120-130 */
+		for (size_t j = 0; j + L <= q.size(); j++) {
+			const uint64_t v = art_pack(q.data() + j, L), r = art_revcomp_host(v, L);
+			kv.push_back(std::make_pair(r < v ? r : v, s));
+		}
+	}
+	std::sort(kv.begin(), kv.end());                  /* getOrSetElement in sequence order: the lowest sequence index keeps a key */
+	for (size_t i = 0; i < kv.size(); i++) if (i == 0 || kv[i].first != kv[i - 1].first) { f->keys.push_back(kv[i].first); f->vals.push_back(kv[i].second); }
+	int edits = (int)cfg->edit_distance;
+	const int maxErrors = edits;
+	for (int error = 0; error < maxErrors; error++) {
+		if (cfg->build_edits == 1 || (cfg->build_edits == 2 && f->keys.size() < 750000)) {
+			edits--;
+			if (!f->keys.empty()) { const int rc = art_build_round(h, f.get()); if (rc) return rc; }
+		}
+	}
+	if (edits > 2) return fail(h, KMR_ERR_UNSUPPORTED, "artifact filter: more than two edits left for query time");
+	f->remaining_edits = (uint32_t)edits;
+	const int rc = art_upload(h, f.get());
+	if (rc) return rc;
+	*out = f.release();
+	return KMR_OK;
+}
+int kmr_artifact_filter_info(const kmr_artifact_filter *f, uint64_t *n_sequences, uint64_t *n_filter_kmers, uint32_t *remaining_edits) {
+	if (!f) return KMR_ERR_INVALID_ARG;
+	if (n_sequences) *n_sequences = f->n_seq; if (n_filter_kmers) *n_filter_kmers = f->n_keys; if (remaining_edits) *remaining_edits = f->remaining_edits;
+	return KMR_OK;
+}
+int kmr_artifact_filter_entries(const kmr_artifact_filter *f, uint64_t *keys, uint32_t *values, uint64_t cap) {
+	if (!f) return KMR_ERR_INVALID_ARG;
+	if (cap < f->keys.size()) return KMR_ERR_CAPACITY;
+	if (keys) memcpy(keys, f->keys.data(), 8 * f->keys.size());
+	if (values) memcpy(values, f->vals.data(), 4 * f->vals.size());
+	return KMR_OK;
+}
+void kmr_artifact_filter_free(kmr_artifact_filter *f) { free_on_device(f); }
+
+int kmr_artifact_filter_apply(kmr_handle *h, const kmr_artifact_filter *f, const kmr_reads *in, const int64_t *mate,
+                              uint32_t *value, uint32_t *min_pass, uint32_t *max_pass, uint8_t *action,
+                              uint32_t *remnant_off, uint32_t *remnant_len, kmr_reads **out) {
+	if (!h || !f || !in) return KMR_ERR_INVALID_ARG;
+	if (out) *out = nullptr;
+	if (f->device != h->device || in->device != h->device) return fail(h, KMR_ERR_INVALID_ARG, "filter, reads and handle must live on one device");
+	hipSetDevice(h->device);
+	const uint64_t n = in->n;
+	ArtifactTable t{f->d_keys.get<uint64_t>(), f->d_vals.get<uint32_t>(), nullptr, f->log2cap, f->d_bits.get<uint32_t>()};
+	ArtifactParams P;
+	P.length = f->cfg.match_length; P.nSeq = f->n_seq; P.numErrors = f->remaining_edits;
+	P.srBegin = f->cfg.simple_repeat_begin; P.srEnd = f->cfg.simple_repeat_end; P.phix = f->cfg.phix_idx; P.refBegin = f->cfg.reference_begin;
+	P.minQualChar = (int32_t)(int8_t)(uint8_t)(f->cfg.fastq_start_char + f->cfg.min_quality);
+	P.minReadLength = f->cfg.min_read_length;
+	Scratch tmp(h);
+	uint32_t *dval, *dmin, *dmax, *dro, *drl, *dlen, *dflag; uint8_t *dact; int64_t *dmate = nullptr; uint64_t *dridx, *dsrc;
+	HIPCHK(h, tmp.take(&dval, n)); HIPCHK(h, tmp.take(&dmin, n)); HIPCHK(h, tmp.take(&dmax, n)); HIPCHK(h, tmp.take(&dro, n)); HIPCHK(h, tmp.take(&drl, n));
+	HIPCHK(h, tmp.take(&dact, n)); HIPCHK(h, tmp.take(&dflag, n)); HIPCHK(h, tmp.take(&dridx, n + 1));
+	if (mate && n) { HIPCHK(h, tmp.take(&dmate, n)); HIPCHK(h, hipMemcpyAsync(dmate, mate, 8 * n, hipMemcpyHostToDevice, h->stream)); }
+	uint64_t n_rem = 0;
+	if (n) {
+		const unsigned blocks = (unsigned)((n + 255) / 256);
+		hipLaunchKernelGGL(artifact_screen, dim3(blocks), dim3(256), 0, h->stream, in->bases.get<uint8_t>(), in->quals.get<uint8_t>(), in->offsets.get<uint64_t>(), n, t, P, dval, dmin, dmax, dro, drl);
+		HIPCHK(h, hipGetLastError());
+	}
+	/* lengths after the filter: n reads, then the remnants */
+	HIPCHK(h, tmp.take(&dlen, 2 * n + 1));
+	if (n) {
+		const unsigned blocks = (unsigned)((n + 255) / 256);
+		hipLaunchKernelGGL(artifact_action, dim3(blocks), dim3(256), 0, h->stream, in->offsets.get<uint64_t>(), n, dmate, P, dval, dmin, dmax, drl, dact, dlen, dflag);
+		HIPCHK(h, hipGetLastError());
+		int rc = exclusive_scan(h, dflag, n, dridx); if (rc) return rc;
+		HIPCHK(h, hipMemcpy(&n_rem, dridx + n, 8, hipMemcpyDeviceToHost));
+	}
+	HIPCHK(h, tmp.take(&dsrc, n_rem));
+	if (n_rem) {
+		hipLaunchKernelGGL(artifact_remnants, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, n, drl, dridx, dlen, dsrc);
+		HIPCHK(h, hipGetLastError());
+	}
+	HIPCHK(h, hipStreamSynchronize(h->stream));
+	hipError_t e = hipSuccess;
+	if (n) {
+		if (value && e == hipSuccess) e = hipMemcpy(value, dval, 4 * n, hipMemcpyDeviceToHost);
+		if (min_pass && e == hipSuccess) e = hipMemcpy(min_pass, dmin, 4 * n, hipMemcpyDeviceToHost);
+		if (max_pass && e == hipSuccess) e = hipMemcpy(max_pass, dmax, 4 * n, hipMemcpyDeviceToHost);
+		if (action && e == hipSuccess) e = hipMemcpy(action, dact, n, hipMemcpyDeviceToHost);
+		if (remnant_off && e == hipSuccess) e = hipMemcpy(remnant_off, dro, 4 * n, hipMemcpyDeviceToHost);
+		if (remnant_len && e == hipSuccess) e = hipMemcpy(remnant_len, drl, 4 * n, hipMemcpyDeviceToHost);
+	}
+	HIPCHK(h, e);
+	if (!out) { tmp.done(); return KMR_OK; }
+	const uint64_t n_out = n + n_rem;
+	auto r = make_result<kmr_reads>(h);
+	r->n = n_out; r->input_base = in->input_base; r->filtered = in->filtered;
+	HIPCHK(h, r->offsets.alloc(8 * (n_out + 1)));
+	if (n_out) { int rc = exclusive_scan(h, dlen, n_out, r->offsets.get<uint64_t>()); if (rc) return rc; HIPCHK(h, hipMemcpy(&r->total, r->offsets.get<uint64_t>() + n_out, 8, hipMemcpyDeviceToHost)); }
+	else HIPCHK(h, hipMemset(r->offsets.get<uint64_t>(), 0, 8));
+	HIPCHK(h, r->bases.alloc(r->total + 64)); HIPCHK(h, r->quals.alloc(r->total + 64));
+	HIPCHK(h, hipMemsetAsync(r->bases.get<uint8_t>() + r->total, 0, 64, h->stream)); HIPCHK(h, hipMemsetAsync(r->quals.get<uint8_t>() + r->total, 0, 64, h->stream));
+	HIPCHK(h, r->name_off.alloc(8 * std::max<uint64_t>(n_out, 1))); HIPCHK(h, r->name_len.alloc(4 * std::max<uint64_t>(n_out, 1)));
+	if (n_out) {
+		hipLaunchKernelGGL(artifact_gather, dim3((unsigned)std::min<uint64_t>((n_out + 3) / 4, 1u << 16)), dim3(256), 0, h->stream,
+		                   in->bases.get<uint8_t>(), in->quals.get<uint8_t>(), in->offsets.get<uint64_t>(), in->name_off.get<uint64_t>(), in->name_len.get<uint32_t>(), n, n_out, dact, dmin, dro, dsrc, r->offsets.get<uint64_t>(), r->bases.get<uint8_t>(), r->quals.get<uint8_t>(), r->name_off.get<uint64_t>(), r->name_len.get<uint32_t>());
+		HIPCHK(h, hipGetLastError());
+	}
+	HIPCHK(h, hipStreamSynchronize(h->stream));
+	tmp.done();
+	*out = r.release();
+	return KMR_OK;
+}
+
+/* ---- selectReads / writePicks on the device (kmr_select.hpp) ---------------- */
+int kmr_select_config_init(kmr_select_config *c) {
+	if (!c) return KMR_ERR_INVALID_ARG;
+	memset(c, 0, sizeof(*c));
+	c->struct_size = (uint32_t)sizeof(kmr_select_config);
+	c->minimum_score = 2.0;            /* --min-depth, apps/FilterReads.cpp:197-199 */
+	c->min_read_length = 0.40f;        /* --min-read-length, src/ReadSelector.h:72 */
+	c->both_pass = 0;                  /* --min-passing-in-pair 1, src/ReadSelector.h:72 */
+	c->output_quality_base = 33;       /* --fastq-output-base-quality */
+	c->format = 0;                     /* --format-output 0 = FASTQ */
+	c->scoring_type = KMR_SCORE_MEDIAN;
+	return KMR_OK;
+}
+
+static int select_check_config(kmr_handle *h, const kmr_select_config *c) {
+	if (!c) return fail(h, KMR_ERR_INVALID_ARG, "kmr_select_config: NULL");
+	if (c->struct_size != sizeof(kmr_select_config)) return fail(h, KMR_ERR_INVALID_ARG, "kmr_select_config: struct_size " + std::to_string(c->struct_size) + " is not " + std::to_string(sizeof(kmr_select_config)));
+	if (c->format > 1) return fail(h, KMR_ERR_INVALID_ARG, "kmr_select_config: format must be 0 (FASTQ) or 1 (FASTA)");
+	if (c->output_quality_base != 33 && c->output_quality_base != 64) return fail(h, KMR_ERR_INVALID_ARG, "kmr_select_config: output_quality_base must be 33 or 64");
+	if (c->scoring_type > 4) return fail(h, KMR_ERR_INVALID_ARG, "kmr_select_config: bad scoring_type");
+	if (!(c->min_read_length >= 0.0f)) return fail(h, KMR_ERR_INVALID_ARG, "kmr_select_config: min_read_length must not be negative");
+	return 0;
+}
+
+typedef EventTimer<3> SelectTimer;
+
+/* every pointer but the last is device memory (mate and the three af_* may be null) */
+static int select_core(kmr_handle *h, Scratch &tmp, const kmr_reads *r, const uint8_t *dtext, uint64_t text_len, const int64_t *dmate, const uint8_t *dact, const uint32_t *dmin,
+                       const uint32_t *dmax, const uint32_t *dto, const uint32_t *dtl, const float *dsc, const uint8_t *dwt, const kmr_select_config *cfg, kmr_picks *pk) {
+	const uint64_t n = r->n;
+	pk->n = n;
+	h->last_select_ms = h->last_write_ms = 0;
+	if (n == 0) return KMR_OK;
+	SelectParams P;
+	P.bases = r->bases.get<uint8_t>(); P.quals = r->quals.get<uint8_t>(); P.offsets = r->offsets.get<uint64_t>(); P.name_off = r->name_off.get<uint64_t>(); P.name_len = r->name_len.get<uint32_t>();
+	P.text = dtext; P.text_len = text_len; P.mate = dmate; P.af_action = dact; P.af_min = dmin; P.af_max = dmax;
+	P.trim_off = dto; P.trim_len = dtl; P.score = dsc; P.was_trimmed = dwt; P.n = n;
+	P.min_score = (float)cfg->minimum_score; P.min_read_length = cfg->min_read_length; P.both_pass = cfg->both_pass ? 1u : 0u; P.fasta = cfg->format; P.scoring = cfg->scoring_type;
+	P.out_base = cfg->output_quality_base; P.qual_shift = (int32_t)cfg->output_quality_base - (int32_t)h->cfg.fastq_start_char;
+	uint32_t *flag, *len, *nlen, *pread; uint64_t *pscan, *bscan, *poff, *tot; uint8_t *picked;
+	HIPCHK(h, tmp.take(&flag, n)); HIPCHK(h, tmp.take(&len, n)); HIPCHK(h, tmp.take(&nlen, n)); HIPCHK(h, tmp.take(&pread, n));
+	HIPCHK(h, tmp.take(&pscan, n + 1)); HIPCHK(h, tmp.take(&bscan, n + 1)); HIPCHK(h, tmp.take(&poff, n + 1)); HIPCHK(h, tmp.take(&tot, 3));
+	HIPCHK(h, alloc_n(pk->picked, &picked, n));
+	SelectTimer timer(h->tune.select_timing);
+	timer.mark(0, h->stream);
+	HIPCHK(h, hipMemsetAsync(tot, 0, 24, h->stream));
+	hipLaunchKernelGGL(select_count_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, P, flag, len, nlen, picked, (uint32_t *)(tot + 2));
+	HIPCHK(h, hipGetLastError());
+	int rc = exclusive_scan(h, flag, n, pscan); if (rc) return rc;
+	rc = exclusive_scan(h, len, n, bscan); if (rc) return rc;
+	hipLaunchKernelGGL(select_compact_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, (const uint32_t *)flag, (const uint64_t *)pscan, (const uint64_t *)bscan, n, pread, poff, tot);
+	HIPCHK(h, hipGetLastError());
+	uint64_t totals[3] = {0, 0, 0};
+	HIPCHK(h, hipMemcpyAsync(totals, tot, 24, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));      /* the one copy that brings sizes back */
+	if (totals[2] & SEL_ERR_MATE) return fail(h, KMR_ERR_INVALID_ARG, "a mate index lies outside the batch");
+	if (totals[2] & SEL_ERR_NAME) return fail(h, KMR_ERR_INVALID_ARG, NAME_SPAN_ERROR);
+	pk->n_picked = totals[0]; pk->bytes = totals[1];
+	timer.mark(1, h->stream);
+	if (pk->bytes) {
+		HIPCHK(h, pk->text.alloc((pk->bytes + 15) & ~(uint64_t)15));
+		uint8_t *dout = pk->text.get<uint8_t>();
+		hipLaunchKernelGGL(select_write_kernel, dim3((unsigned)std::min<uint64_t>((pk->n_picked + SEL_WAVES - 1) / SEL_WAVES, (uint64_t)num_cus(h) * 8)), dim3(SEL_THREADS), 0, h->stream, P, (const uint32_t *)nlen, (const uint32_t *)pread, (const uint64_t *)poff, pk->n_picked, dout);
+		HIPCHK(h, hipGetLastError());
+	}
+	timer.mark(2, h->stream);
+	HIPCHK(h, hipStreamSynchronize(h->stream));
+	tmp.done();
+	h->last_select_ms = timer.ms(0, 2); h->last_write_ms = timer.ms(1, 2);
+	return KMR_OK;
+}
+
+static int select_check_args(kmr_handle *h, const kmr_reads *r, const void *text, uint64_t text_len, const uint8_t *af_action, const uint32_t *af_min, const uint32_t *af_max,
+                             const kmr_select_config *cfg, kmr_picks **out, const char *who) {
+	if (out) *out = nullptr;
+	int rc = select_check_config(h, cfg); if (rc) return rc;
+	if (!h) return fail(h, KMR_ERR_INVALID_ARG, std::string(who) + ": NULL handle");
+	if (!r || !out || (text_len && !text)) return fail(h, KMR_ERR_INVALID_ARG, std::string(who) + ": NULL argument");
+	if ((af_action != nullptr) != (af_min != nullptr) || (af_action != nullptr) != (af_max != nullptr)) return fail(h, KMR_ERR_INVALID_ARG, std::string(who) + ": af_action, af_min_pass and af_max_pass go together");
+	if (r->device != h->device) return fail(h, KMR_ERR_INVALID_ARG, "read batch lives on another device");
+	if (r->n >= 0xffffffffull) return fail(h, KMR_ERR_UNSUPPORTED, std::string(who) + ": a batch holds fewer than 2^32 - 1 reads (pick indices are 32-bit)");
+	return 0;
+}
+
+/* text_on_device: `text` is device memory already (the other arrays are the host's) */
+static int select_reads_any(kmr_handle *h, const kmr_reads *r, const void *text, uint64_t text_len, bool text_on_device, const int64_t *mate, const uint8_t *af_action,
+                            const uint32_t *af_min, const uint32_t *af_max, const uint32_t *trim_offset, const uint32_t *trim_length, const float *score,
+                            const uint8_t *was_trimmed, const kmr_select_config *cfg, kmr_picks **out, bool fused, const char *who) {
+	int rc = select_check_args(h, r, text, text_len, af_action, af_min, af_max, cfg, out, who); if (rc) return rc;
+	if (fused) { if (!h->finalized) return fail(h, KMR_ERR_STATE, std::string(who) + " before kmr_finalize"); }
+	else if (r->n && (!trim_offset || !trim_length || !score || !was_trimmed)) return fail(h, KMR_ERR_INVALID_ARG, std::string(who) + ": NULL argument");
+	hipSetDevice(h->device);
+	const uint64_t n = r->n;
+	auto pk = make_result<kmr_picks>(h);      /* (ahead of tmp, as in every stage: a failed call waits for the stream before the result's buffers go too) */
+	Scratch tmp(h);
+	const uint8_t *dtext, *dact, *dwt = nullptr; const int64_t *dmate; const uint32_t *dmin, *dmax, *dto = nullptr, *dtl = nullptr; const float *dsc = nullptr;
+	rc = to_device(h, tmp, (const uint8_t *)text, text_len, &dtext, text_on_device); if (rc) return rc;
+	rc = to_device(h, tmp, mate, n, &dmate); if (rc) return rc;
+	rc = to_device(h, tmp, af_action, n, &dact); if (rc) return rc;
+	rc = to_device(h, tmp, af_min, n, &dmin); if (rc) return rc;
+	rc = to_device(h, tmp, af_max, n, &dmax); if (rc) return rc;
+	h->last_score_ms = 0;
+	if (fused && n) {
+		SelectTimer timer(h->tune.select_timing);
+		timer.mark(0, h->stream);
+		ScoreDev sd;
+		rc = score_reads_core(h, r->bases.get<uint8_t>(), r->offsets.get<uint64_t>(), n, cfg->minimum_score, (int)cfg->scoring_type, nullptr, nullptr, nullptr, nullptr, &sd); if (rc) return rc;
+		timer.mark(1, h->stream);
+		if (timer.on) { HIPCHK(h, hipStreamSynchronize(h->stream)); h->last_score_ms = timer.ms(0, 1); }
+		dto = sd.trim_offset; dtl = sd.trim_length; dsc = sd.score; dwt = sd.was_trimmed;
+	} else if (!fused) {
+		rc = to_device(h, tmp, trim_offset, n, &dto); if (rc) return rc;
+		rc = to_device(h, tmp, trim_length, n, &dtl); if (rc) return rc;
+		rc = to_device(h, tmp, score, n, &dsc); if (rc) return rc;
+		rc = to_device(h, tmp, was_trimmed, n, &dwt); if (rc) return rc;
+	}
+	rc = select_core(h, tmp, r, dtext, text_len, dmate, dact, dmin, dmax, dto, dtl, dsc, dwt, cfg, pk.get());
+	if (!rc) *out = pk.release();
+	return rc;
+}
+
+int kmr_select_reads(kmr_handle *h, const kmr_reads *reads, const char *text, uint64_t text_len, const int64_t *mate, const uint8_t *af_action, const uint32_t *af_min_pass,
+                     const uint32_t *af_max_pass, const uint32_t *trim_offset, const uint32_t *trim_length, const float *score, const uint8_t *was_trimmed,
+                     const kmr_select_config *cfg, kmr_picks **out) {
+	return select_reads_any(h, reads, text, text_len, false, mate, af_action, af_min_pass, af_max_pass, trim_offset, trim_length, score, was_trimmed, cfg, out, false, "kmr_select_reads");
+}
+int kmr_select_reads_dev(kmr_handle *h, const kmr_reads *reads, const void *dev_text, uint64_t text_len, const int64_t *mate, const uint8_t *af_action, const uint32_t *af_min_pass,
+                         const uint32_t *af_max_pass, const uint32_t *trim_offset, const uint32_t *trim_length, const float *score, const uint8_t *was_trimmed,
+                         const kmr_select_config *cfg, kmr_picks **out) {
+	return select_reads_any(h, reads, dev_text, text_len, true, mate, af_action, af_min_pass, af_max_pass, trim_offset, trim_length, score, was_trimmed, cfg, out, false, "kmr_select_reads_dev");
+}
+int kmr_filter_read_batch(kmr_handle *h, const kmr_reads *reads, const char *text, uint64_t text_len, const int64_t *mate, const uint8_t *af_action, const uint32_t *af_min_pass,
+                          const uint32_t *af_max_pass, const kmr_select_config *cfg, kmr_picks **out) {
+	return select_reads_any(h, reads, text, text_len, false, mate, af_action, af_min_pass, af_max_pass, nullptr, nullptr, nullptr, nullptr, cfg, out, true, "kmr_filter_read_batch");
+}
+int kmr_filter_read_batch_dev(kmr_handle *h, const kmr_reads *reads, const void *dev_text, uint64_t text_len, const int64_t *mate, const uint8_t *af_action, const uint32_t *af_min_pass,
+                              const uint32_t *af_max_pass, const kmr_select_config *cfg, kmr_picks **out) {
+	return select_reads_any(h, reads, dev_text, text_len, true, mate, af_action, af_min_pass, af_max_pass, nullptr, nullptr, nullptr, nullptr, cfg, out, true, "kmr_filter_read_batch_dev");
+}
+int kmr_picks_info(const kmr_picks *p, uint64_t *n_picked, uint64_t *bytes) {
+	if (!p) return KMR_ERR_INVALID_ARG;
+	if (n_picked) *n_picked = p->n_picked; if (bytes) *bytes = p->bytes;
+	return KMR_OK;
+}
+int kmr_picks_copy(const kmr_picks *p, char *dst, uint64_t capacity, uint8_t *picked_flags) {
+	if (!p || (p->bytes && !dst)) return KMR_ERR_INVALID_ARG;
+	if (capacity < p->bytes) return KMR_ERR_CAPACITY;
+	hipSetDevice(p->device);
+	hipError_t e = hipSuccess;
+	copy_out(e, (uint8_t *)dst, p->text, p->bytes); copy_out(e, picked_flags, p->picked, p->n);
+	return e == hipSuccess ? KMR_OK : KMR_ERR_HIP;
+}
+int kmr_picks_device_ptr(const kmr_picks *p, void **dev_text) {
+	if (!p || !dev_text) return KMR_ERR_INVALID_ARG;
+	*dev_text = p->text.get<uint8_t>();
+	return KMR_OK;
+}
+void kmr_picks_free(kmr_picks *p) { free_on_device(p); }
+
+/* ---- ReadSet::identifyPairs on the device (kmr_pairs.hpp) ---------------- */
+/* dtext: device memory */
+static int pairs_core(kmr_handle *h, Scratch &tmp, const kmr_reads *r, const uint8_t *dtext, uint64_t text_len, int store_comment, kmr_pairs *pr) {
+	const uint64_t n = r->n;
+	pr->n = n;
+	h->last_pairs_ms = h->last_pairs_parse_ms = h->last_pairs_sort_ms = 0; h->last_pair_hash_collisions = 0;
+	if (n == 0) return KMR_OK;
+	PairsParams P;
+	P.name_off = r->name_off.get<uint64_t>(); P.name_len = r->name_len.get<uint32_t>(); P.text = dtext; P.text_len = text_len; P.n = n; P.store_comment = store_comment ? 1u : 0u;
+	const dim3 grid(grid_for(n)), block(256);
+	uint64_t *hash, *bscan, *sscan, *uscan, *tot; uint32_t *cn, *brk, *run, *sec, *unp; uint8_t *fl, *link; int64_t *mate;
+	HIPCHK(h, tmp.take(&hash, n)); HIPCHK(h, tmp.take(&cn, n)); HIPCHK(h, tmp.take(&fl, n)); HIPCHK(h, tmp.take(&tot, (size_t)PAIRS_T_WORDS));
+	HIPCHK(h, alloc_n(pr->mate, &mate, n));
+	EventTimer<5> timer(h->tune.pairs_timing);
+	timer.mark(0, h->stream);
+	HIPCHK(h, hipMemsetAsync(tot, 0, 8 * PAIRS_T_WORDS, h->stream));
+	hipLaunchKernelGGL(pairs_parse_kernel, grid, block, 0, h->stream, P, hash, cn, fl, tot);
+	HIPCHK(h, hipGetLastError());
+	timer.mark(1, h->stream);
+	uint64_t totals[PAIRS_T_WORDS] = {0};
+	if (text_len == 0) {      /* no names (kmr_reads_from_host, kmr_reads_from_twobit): every read is a half pair of its own */
+		int64_t *r1, *r2;
+		HIPCHK(h, alloc_n(pr->read1, &r1, n)); HIPCHK(h, alloc_n(pr->read2, &r2, n));
+		hipLaunchKernelGGL(pairs_single_kernel, grid, block, 0, h->stream, n, mate, r1, r2);
+		HIPCHK(h, hipGetLastError());
+		HIPCHK(h, hipMemcpyAsync(totals, tot, 8 * PAIRS_T_WORDS, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
+		if (totals[PAIRS_T_ERR] & PAIRS_ERR_NAME) return fail(h, KMR_ERR_INVALID_ARG, NAME_SPAN_ERROR);
+		pr->n_pairs = n;
+		tmp.done();
+		return KMR_OK;
+	}
+	const PairsNames N = {hash, cn, fl};
+	/* phase 1 */
+	HIPCHK(h, tmp.take(&link, n)); HIPCHK(h, tmp.take(&brk, n)); HIPCHK(h, tmp.take(&bscan, n + 1)); HIPCHK(h, tmp.take(&run, n + 1));
+	HIPCHK(h, tmp.take(&sec, n)); HIPCHK(h, tmp.take(&unp, n)); HIPCHK(h, tmp.take(&sscan, n + 1)); HIPCHK(h, tmp.take(&uscan, n + 1));
+	hipLaunchKernelGGL(pairs_link_kernel, grid, block, 0, h->stream, P, N, link, brk);
+	HIPCHK(h, hipGetLastError());
+	int rc = exclusive_scan(h, brk, n, bscan); if (rc) return rc;
+	hipLaunchKernelGGL(pairs_runstart_kernel, grid, block, 0, h->stream, (const uint8_t *)link, (const uint64_t *)bscan, n, run);
+	hipLaunchKernelGGL(pairs_seq_kernel, grid, block, 0, h->stream, (const uint8_t *)link, (const uint64_t *)bscan, (const uint32_t *)run, n, sec, unp, mate);
+	HIPCHK(h, hipGetLastError());
+	rc = exclusive_scan(h, sec, n, sscan); if (rc) return rc;
+	rc = exclusive_scan(h, unp, n, uscan); if (rc) return rc;
+	/* the first of the call's two fixed-size copies: phase 1's totals size phase 2 (an interleaved file leaves it nothing) */
+	HIPCHK(h, hipMemcpyAsync(&totals[PAIRS_T_SEQ], sscan + n, 8, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipMemcpyAsync(&totals[PAIRS_T_UNPAIRED], uscan + n, 8, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipMemcpyAsync(&totals[PAIRS_T_ERR], tot + PAIRS_T_ERR, 8, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipStreamSynchronize(h->stream));
+	if (totals[PAIRS_T_ERR] & PAIRS_ERR_NAME) return fail(h, KMR_ERR_INVALID_ARG, NAME_SPAN_ERROR);
+	const uint64_t n_seq = totals[PAIRS_T_SEQ], m = totals[PAIRS_T_UNPAIRED];
+	/* phase 2 */
+	unsigned long long *kin, *kout; uint32_t *vin, *vout, *push = nullptr; uint8_t *side = nullptr; uint64_t *pscan = nullptr;
+	timer.mark(2, h->stream); timer.mark(3, h->stream);
+	if (m) {
+		HIPCHK(h, tmp.take(&kin, m)); HIPCHK(h, tmp.take(&kout, m)); HIPCHK(h, tmp.take(&vin, m)); HIPCHK(h, tmp.take(&vout, m));
+		HIPCHK(h, tmp.take(&push, n)); HIPCHK(h, tmp.take(&side, n)); HIPCHK(h, tmp.take(&pscan, n + 1));
+		const uint32_t bits = h->tune.pair_hash_bits;
+		hipLaunchKernelGGL(pairs_keys_kernel, grid, block, 0, h->stream, (const uint32_t *)unp, (const uint64_t *)uscan, (const uint64_t *)hash, bits >= 64 ? ~0ull : (1ull << bits) - 1, n, kin, vin);
+		HIPCHK(h, hipGetLastError());
+		HIPCHK(h, hipMemsetAsync(push, 0, 4 * n, h->stream)); HIPCHK(h, hipMemsetAsync(side, 0, n, h->stream));
+		rc = sort_reserve(h, tmp, m, "kmr_identify_pairs"); if (rc) return rc;
+		timer.mark(2, h->stream);
+		rc = sort_pairs(h, tmp, kin, kout, vin, vout, m, "kmr_identify_pairs"); if (rc) return rc;
+		timer.mark(3, h->stream);
+		hipLaunchKernelGGL(pairs_group_kernel, dim3(grid_for(m)), block, 0, h->stream, P, N, (const unsigned long long *)kout, (const uint32_t *)vout, m, mate, push, side, tot);
+		HIPCHK(h, hipGetLastError());
+		rc = exclusive_scan(h, push, n, pscan); if (rc) return rc;
+		/* the second: what phase 2 made */
+		HIPCHK(h, hipMemcpyAsync(&totals[PAIRS_T_PUSHED], pscan + n, 8, hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, hipMemcpyAsync(&totals[PAIRS_T_FULL2], tot + PAIRS_T_FULL2, 8 * (PAIRS_T_WORDS - PAIRS_T_FULL2), hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, hipStreamSynchronize(h->stream));
+	}
+	pr->n_seq = n_seq; pr->n_pairs = n_seq + totals[PAIRS_T_PUSHED]; pr->n_full = n_seq + totals[PAIRS_T_FULL2];
+	pr->n_conflicts = totals[PAIRS_T_CONFLICT1] + totals[PAIRS_T_CONFLICT2];
+	h->last_pair_hash_collisions = totals[PAIRS_T_COLLISIONS];
+	int64_t *r1, *r2;
+	HIPCHK(h, alloc_n(pr->read1, &r1, pr->n_pairs)); HIPCHK(h, alloc_n(pr->read2, &r2, pr->n_pairs));
+	hipLaunchKernelGGL(pairs_scatter_kernel, grid, block, 0, h->stream, (const uint32_t *)sec, (const uint64_t *)sscan, (const uint32_t *)push, (const uint64_t *)pscan, (const uint8_t *)side, (const int64_t *)mate,
+	                   n, n_seq, r1, r2);
+	HIPCHK(h, hipGetLastError());
+	timer.mark(4, h->stream);
+	HIPCHK(h, hipStreamSynchronize(h->stream));
+	tmp.done();
+	h->last_pairs_ms = timer.ms(0, 4); h->last_pairs_parse_ms = timer.ms(0, 1); h->last_pairs_sort_ms = m ? timer.ms(2, 3) : 0.0;
+	return KMR_OK;
+}
+
+static int identify_pairs_any(kmr_handle *h, const kmr_reads *r, const void *text, uint64_t text_len, bool text_on_device, int store_comment, kmr_pairs **out) {
+	if (!h || !r || !out || (text_len && !text)) return KMR_ERR_INVALID_ARG;
+	*out = nullptr;
+	if (r->device != h->device) return fail(h, KMR_ERR_INVALID_ARG, "read batch lives on another device");
+	if (r->n >= 0xffffffffull) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_identify_pairs: a batch holds fewer than 2^32 - 1 reads (read indices of the sort are 32-bit)");
+	hipSetDevice(h->device);
+	auto pr = make_result<kmr_pairs>(h);
+	Scratch tmp(h);
+	const uint8_t *dtext;
+	int rc = to_device(h, tmp, (const uint8_t *)text, r->n ? text_len : 0, &dtext, text_on_device); if (rc) return rc;
+	rc = pairs_core(h, tmp, r, dtext, text_len, store_comment, pr.get());
+	if (!rc) *out = pr.release();
+	return rc;
+}
+int kmr_identify_pairs(kmr_handle *h, const kmr_reads *reads, const char *text, uint64_t text_len, int store_comment, kmr_pairs **out) {
+	return identify_pairs_any(h, reads, text, text_len, false, store_comment, out);
+}
+int kmr_identify_pairs_dev(kmr_handle *h, const kmr_reads *reads, const void *dev_text, uint64_t text_len, int store_comment, kmr_pairs **out) {
+	return identify_pairs_any(h, reads, dev_text, text_len, true, store_comment, out);
+}
+int kmr_pairs_info(const kmr_pairs *p, uint64_t *n_reads, uint64_t *n_pairs, uint64_t *n_full, uint64_t *n_sequential, uint64_t *n_conflicts, int *has_pairs) {
+	if (!p) return KMR_ERR_INVALID_ARG;
+	if (n_reads) *n_reads = p->n; if (n_pairs) *n_pairs = p->n_pairs; if (n_full) *n_full = p->n_full;
+	if (n_sequential) *n_sequential = p->n_seq; if (n_conflicts) *n_conflicts = p->n_conflicts;
+	if (has_pairs) *has_pairs = p->n_pairs > 0 && p->n_pairs < p->n;      /* ReadSet::hasPairs, src/ReadSet.h:526-529 */
+	return KMR_OK;
+}
+int kmr_pairs_copy(const kmr_pairs *p, int64_t *mate, int64_t *read1, int64_t *read2) {
+	if (!p) return KMR_ERR_INVALID_ARG;
+	hipSetDevice(p->device);
+	hipError_t e = hipSuccess;
+	copy_out(e, mate, p->mate, p->n); copy_out(e, read1, p->read1, p->n_pairs); copy_out(e, read2, p->read2, p->n_pairs);
+	return e == hipSuccess ? KMR_OK : KMR_ERR_HIP;
+}
+int kmr_pairs_device_ptrs(const kmr_pairs *p, void **dev_mate, void **dev_read1, void **dev_read2) {
+	if (!p) return KMR_ERR_INVALID_ARG;
+	if (dev_mate) *dev_mate = p->mate.get<int64_t>(); if (dev_read1) *dev_read1 = p->read1.get<int64_t>(); if (dev_read2) *dev_read2 = p->read2.get<int64_t>();
+	return KMR_OK;
+}
+void kmr_pairs_free(kmr_pairs *p) { free_on_device(p); }
+
+/* ---- DuplicateFragmentFilter on the device (kmr_dedup.hpp) ---------------- */
+/* probToQual (src/Sequence.cpp:807-809) steps from i to i + 1 at dedup_qual_steps()[i]: the smallest double p with
+ * (char)(-10. * log10(1.0 - p)) >= i + 1, found by bisection over the bit pattern (the expression is monotone below 0.9999) */
+static char dedup_prob_to_qual(double prob) { return (char)(-10. * std::log10(1.0 - prob)); }
+static const double *dedup_qual_steps() {
+	static double step[DEDUP_QUALS];
+	static std::once_flag once;
+	std::call_once(once, [] {
+		for (int i = 0; i < DEDUP_QUALS; i++) {
+			uint64_t lo = 0, hi; const double top = 0.9999;
+			memcpy(&hi, &top, 8);
+			if (dedup_prob_to_qual(top) < i + 1) { step[i] = top; continue; }      /* never reached: getQualChar answers 40 from there */
+			while (hi - lo > 1) {
+				const uint64_t mid = lo + (hi - lo) / 2; double p; memcpy(&p, &mid, 8);
+				if (dedup_prob_to_qual(p) >= i + 1) hi = mid; else lo = mid;
+			}
+			memcpy(&step[i], &hi, 8);
+		}
+	});
+	return step;
+}
+char kmr_consensus_qual(double prob) {
+	if (prob >= 0.9999) return 40;
+	const double *step = dedup_qual_steps();
+	char q = 0;
+	while (q < DEDUP_QUALS && step[(int)q] <= prob) q++;
+	return q;
+}
+
+int kmr_dedup_config_init(kmr_dedup_config *c) {
+	if (!c) return KMR_ERR_INVALID_ARG;
+	memset(c, 0, sizeof(*c));
+	c->struct_size = (uint32_t)sizeof(kmr_dedup_config);
+	c->dedup_mode = 0; c->paired = 1; c->dedup_length = 24; c->start_offset = 0; c->edit_distance = 0; c->consensus = 1;      /* src/DuplicateFragmentFilter.h:60-61 */
+	return KMR_OK;
+}
+static int dedup_check_config(kmr_handle *h, const kmr_dedup_config *c) {
+	if (!c) return fail(h, KMR_ERR_INVALID_ARG, "kmr_dedup_config: NULL");
+	if (c->struct_size != sizeof(kmr_dedup_config)) return fail(h, KMR_ERR_INVALID_ARG, "kmr_dedup_config: struct_size " + std::to_string(c->struct_size) + " is not " + std::to_string(sizeof(kmr_dedup_config)));
+	if (c->dedup_mode > 2) return fail(h, KMR_ERR_INVALID_ARG, "kmr_dedup_config: dedup_mode must be 0 (off), 1 or 2");
+	if (c->paired > 1) return fail(h, KMR_ERR_INVALID_ARG, "kmr_dedup_config: paired must be 0 or 1");
+	if (c->dedup_length == 0 || c->dedup_length % 4 != 0 || c->start_offset % 4 != 0) return fail(h, KMR_ERR_INVALID_ARG, "kmr_dedup_config: dedup_length and start_offset must be multiples of 4, dedup_length not 0");
+	if (c->edit_distance != 0) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_dedup_config: only dedup-edit-distance 0 is built");
+	if (c->consensus == 0) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_dedup_config: only dedup-consensus 1 is built");
+	if (2 * (uint64_t)c->dedup_length > 128) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_dedup_config: a key holds at most 128 bases (2 * dedup_length)");
+	if ((uint64_t)c->start_offset + 2 * (uint64_t)c->dedup_length > 0x7fffffffull) return fail(h, KMR_ERR_INVALID_ARG, "kmr_dedup_config: start_offset is too large");
+	return 0;
+}
+
+/* the handle's DedupTables, made by the first call */
+static int dedup_tables(kmr_handle *h, const DedupTables **out) {
+	if (!h->dedup_tab) {
+		std::unique_ptr<DedupTables> t(new DedupTables);
+		double P[256]; quality_table(P, h->cfg.min_quality_score, h->cfg.fastq_start_char);
+		for (int q = 0; q < 256; q++) {      /* Read::getProbabilityBases (src/Sequence.cpp:573-576), ProbabilityBase::observe (:871) */
+			double prob = P[q];
+			if (prob < 0.2501) prob = 0.2501;
+			t->prob[q] = prob; t->other[q] = (1.0 - prob) / 3.0;
+		}
+		memcpy(t->step, dedup_qual_steps(), sizeof(t->step));
+		HIPCHK(h, h->dedup_tab.alloc(sizeof(DedupTables)));
+		HIPCHK(h, hipMemcpy(h->dedup_tab.get(), t.get(), sizeof(DedupTables), hipMemcpyHostToDevice));
+	}
+	*out = h->dedup_tab.get<DedupTables>();
+	return 0;
+}
+
+/* dtext and ddisc (may be null): device memory */
+static int dedup_core(kmr_handle *h, Scratch &tmp, const kmr_reads *r, const uint8_t *dtext, uint64_t text_len, const kmr_pairs *pairs, const uint8_t *ddisc, const kmr_dedup_config *cfg, kmr_dedup *dd) {
+	const uint64_t n = r->n, np = pairs->n_pairs;
+	dd->n = n;
+	h->last_dedup_ms = h->last_dedup_key_ms = h->last_dedup_sort_ms = h->last_dedup_consensus_ms = 0;
+	const DedupTables *tables; int rc = dedup_tables(h, &tables); if (rc) return rc;
+	uint8_t *disc;
+	HIPCHK(h, alloc_n(dd->disc, &disc, n));
+	EventTimer<7> timer(h->tune.dedup_timing);
+	timer.mark(0, h->stream);
+	if (n) { if (ddisc) HIPCHK(h, hipMemcpyAsync(disc, ddisc, n, hipMemcpyDeviceToDevice, h->stream)); else HIPCHK(h, hipMemsetAsync(disc, 0, n, h->stream)); }
+	DedupParams P;
+	P.bases = r->bases.get<uint8_t>(); P.quals = r->quals.get<uint8_t>(); P.offsets = r->offsets.get<uint64_t>(); P.name_off = r->name_off.get<uint64_t>(); P.name_len = r->name_len.get<uint32_t>();
+	P.text = dtext; P.text_len = text_len; P.n = n; P.total = r->total; P.read1 = pairs->read1.get<int64_t>(); P.read2 = pairs->read2.get<int64_t>(); P.np = np; P.discarded = ddisc;
+	P.paired = cfg->paired ? 1u : 0u; P.mode2 = cfg->dedup_mode == 2 ? 1u : 0u; P.L = cfg->paired ? cfg->dedup_length : 2 * cfg->dedup_length; P.so = cfg->start_offset;
+	P.W = (cfg->dedup_length / 2 + 7) / 8; P.sides = cfg->paired ? 2u : 1u;
+	P.min_q = h->cfg.fastq_start_char + h->cfg.min_quality_score; P.start_char = h->cfg.fastq_start_char;
+	const dim3 block(256);
+	uint64_t totals[DEDUP_T_WORDS] = {0}, c = 0, K = 0;
+	unsigned long long *keys, *kin, *kout, *first, *first2; uint32_t *cand, *perm = nullptr, *perm2, *head, *keep = nullptr, *grp, *grp2; uint8_t *flip = nullptr; uint64_t *cscan, *tot, *hscan = nullptr, *start = nullptr, *kscan;
+	HIPCHK(h, tmp.take(&tot, (size_t)DEDUP_T_WORDS));
+	HIPCHK(h, hipMemsetAsync(tot, 0, 8 * DEDUP_T_WORDS, h->stream));
+	if (n && np && cfg->dedup_mode) {
+		/* candidates and their keys */
+		HIPCHK(h, tmp.take(&keys, (size_t)P.W * np)); HIPCHK(h, tmp.take(&cand, np)); HIPCHK(h, tmp.take(&flip, np)); HIPCHK(h, tmp.take(&cscan, np + 1));
+		hipLaunchKernelGGL(dedup_key_kernel, dim3(grid_for(np)), block, 0, h->stream, P, keys, cand, flip, tot);
+		HIPCHK(h, hipGetLastError());
+		timer.mark(1, h->stream);
+		rc = exclusive_scan(h, cand, np, cscan); if (rc) return rc;
+		/* the first of the call's three fixed-size copies: the number of candidates sizes the sorts */
+		HIPCHK(h, hipMemcpyAsync(&c, cscan + np, 8, hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, hipMemcpyAsync(totals, tot, 8 * DEDUP_T_AFFECTED, hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, hipStreamSynchronize(h->stream));
+	} else timer.mark(1, h->stream);
+	for (int i = 0; i < 4; i++) dd->skipped[i] = totals[i];
+	timer.mark(2, h->stream);
+	if (c >= 2) {
+		const dim3 cgrid(grid_for(c));
+		HIPCHK(h, tmp.take(&perm, c)); HIPCHK(h, tmp.take(&perm2, c)); HIPCHK(h, tmp.take(&kin, c)); HIPCHK(h, tmp.take(&kout, c));
+		hipLaunchKernelGGL(dedup_compact_kernel, dim3(grid_for(np)), block, 0, h->stream, (const uint32_t *)cand, (const uint64_t *)cscan, np, perm);
+		HIPCHK(h, hipGetLastError());
+		rc = sort_reserve(h, tmp, c, "kmr_dedup_fragments"); if (rc) return rc;
+		/* least significant word first; the sort is stable, so equal keys keep ascending pair position */
+		for (uint32_t w = P.W; w-- > 0;) {
+			hipLaunchKernelGGL(dedup_gather_kernel, cgrid, block, 0, h->stream, (const unsigned long long *)(keys + (size_t)w * np), (const uint32_t *)perm, c, kin);
+			HIPCHK(h, hipGetLastError());
+			rc = sort_pairs(h, tmp, kin, kout, perm, perm2, c, "kmr_dedup_fragments"); if (rc) return rc;
+			std::swap(perm, perm2);
+		}
+		timer.mark(3, h->stream);
+		/* groups, and those of two members and more */
+		HIPCHK(h, tmp.take(&head, c)); HIPCHK(h, tmp.take(&hscan, c + 1)); HIPCHK(h, tmp.take(&start, c + 1));
+		HIPCHK(h, tmp.take(&keep, c)); HIPCHK(h, tmp.take(&kscan, c + 1)); HIPCHK(h, tmp.take(&first, c)); HIPCHK(h, tmp.take(&grp, c));
+		hipLaunchKernelGGL(dedup_heads_kernel, cgrid, block, 0, h->stream, (const unsigned long long *)keys, np, P.W, (const uint32_t *)perm, c, head);
+		HIPCHK(h, hipGetLastError());
+		rc = exclusive_scan(h, head, c, hscan); if (rc) return rc;
+		hipLaunchKernelGGL(dedup_starts_kernel, cgrid, block, 0, h->stream, (const uint32_t *)head, (const uint64_t *)hscan, c, start);
+		hipLaunchKernelGGL(dedup_keep_kernel, cgrid, block, 0, h->stream, (const uint64_t *)hscan, (const uint64_t *)start, c, keep);
+		HIPCHK(h, hipGetLastError());
+		rc = exclusive_scan(h, keep, c, kscan); if (rc) return rc;
+		hipLaunchKernelGGL(dedup_kept_kernel, cgrid, block, 0, h->stream, (const uint32_t *)keep, (const uint64_t *)kscan, (const uint64_t *)start, (const uint32_t *)perm, c, first, grp);
+		HIPCHK(h, hipGetLastError());
+		/* the second: the number of groups sizes everything behind */
+		HIPCHK(h, hipMemcpyAsync(&K, kscan + c, 8, hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, hipStreamSynchronize(h->stream));
+	} else timer.mark(3, h->stream);
+	/* the consensus batch (empty if nothing was collapsed) */
+	const uint64_t n_new = K * P.sides;
+	if (n_new >= 0xffffffffull) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_dedup_fragments: more than 2^32 - 2 consensus reads");
+	dd->cons = new kmr_reads;
+	kmr_reads *cr = dd->cons;
+	cr->device = h->device; cr->n = n_new; cr->input_base = h->cfg.fastq_start_char;
+	uint64_t *coff, *cno, *gfirst; uint32_t *cnl, *gsize;
+	HIPCHK(h, alloc_n(cr->offsets, &coff, n_new + 1)); HIPCHK(h, alloc_n(cr->name_off, &cno, std::max<uint64_t>(n_new, 1))); HIPCHK(h, alloc_n(cr->name_len, &cnl, std::max<uint64_t>(n_new, 1)));
+	HIPCHK(h, alloc_n(dd->group_first, &gfirst, std::max<uint64_t>(K, 1))); HIPCHK(h, alloc_n(dd->group_size, &gsize, std::max<uint64_t>(K, 1)));
+	uint64_t name_total = 0;
+	timer.mark(4, h->stream);
+	if (K) {
+		/* output order: ascending position of the first member */
+		HIPCHK(h, tmp.take(&first2, K)); HIPCHK(h, tmp.take(&grp2, K));
+		rc = sort_reserve(h, tmp, K, "kmr_dedup_fragments"); if (rc) return rc;
+		rc = sort_pairs(h, tmp, first, first2, grp, grp2, K, "kmr_dedup_fragments"); if (rc) return rc;
+		DedupGroups G; G.perm = perm; G.flip = flip; G.start = start; G.ogroup = grp2; G.K = K;
+		uint32_t *len, *nb; uint64_t *nscan; DedupMember *members;
+		HIPCHK(h, tmp.take(&len, n_new)); HIPCHK(h, tmp.take(&nb, n_new)); HIPCHK(h, tmp.take(&nscan, n_new + 1)); HIPCHK(h, tmp.take(&members, (size_t)c * P.sides));
+		hipLaunchKernelGGL(dedup_size_kernel, dim3(grid_for(n_new)), block, 0, h->stream, P, G, len, nb, gfirst, gsize, tot);
+		HIPCHK(h, hipGetLastError());
+		rc = exclusive_scan(h, len, n_new, coff); if (rc) return rc;
+		rc = exclusive_scan(h, nb, n_new, nscan); if (rc) return rc;
+		/* the third: the bases and name bytes of the batch, what was collapsed, the error word */
+		HIPCHK(h, hipMemcpyAsync(&cr->total, coff + n_new, 8, hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, hipMemcpyAsync(&name_total, nscan + n_new, 8, hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, hipMemcpyAsync(&totals[DEDUP_T_AFFECTED], tot + DEDUP_T_AFFECTED, 16, hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, hipStreamSynchronize(h->stream));
+		if (totals[DEDUP_T_ERR] & DEDUP_ERR_NAME) return fail(h, KMR_ERR_INVALID_ARG, NAME_SPAN_ERROR);
+		uint8_t *cb, *cq, *names;
+		HIPCHK(h, alloc_n(cr->bases, &cb, cr->total + 64)); HIPCHK(h, alloc_n(cr->quals, &cq, cr->total + 64)); HIPCHK(h, alloc_n(dd->names, &names, name_total));
+		HIPCHK(h, hipMemsetAsync(cb + cr->total, 0, 64, h->stream)); HIPCHK(h, hipMemsetAsync(cq + cr->total, 0, 64, h->stream));
+		timer.mark(4, h->stream);
+		hipLaunchKernelGGL(dedup_consensus_kernel, dim3((unsigned)std::min<uint64_t>((n_new + DEDUP_WAVES - 1) / DEDUP_WAVES, (uint64_t)num_cus(h) * 8)), dim3(DEDUP_THREADS), 0, h->stream,
+		                   P, G, tables, (const uint64_t *)coff, (const uint64_t *)nscan, members, cb, cq, names, cno, cnl);
+		HIPCHK(h, hipGetLastError());
+		timer.mark(5, h->stream);
+		hipLaunchKernelGGL(dedup_discard_kernel, dim3(grid_for(c)), block, 0, h->stream, P, (const uint32_t *)perm, (const uint64_t *)hscan, (const uint32_t *)keep, c, disc);
+		HIPCHK(h, hipGetLastError());
+		timer.mark(6, h->stream);
+		HIPCHK(h, hipStreamSynchronize(h->stream));      /* the temporaries above go */
+	} else {
+		uint8_t *cb, *cq;
+		HIPCHK(h, alloc_n(cr->bases, &cb, (size_t)64)); HIPCHK(h, alloc_n(cr->quals, &cq, (size_t)64));
+		HIPCHK(h, hipMemsetAsync(cb, 0, 64, h->stream)); HIPCHK(h, hipMemsetAsync(cq, 0, 64, h->stream)); HIPCHK(h, hipMemsetAsync(coff, 0, 8, h->stream));
+		timer.mark(5, h->stream); timer.mark(6, h->stream);
+		HIPCHK(h, hipStreamSynchronize(h->stream));
+	}
+	dd->n_groups = K; dd->affected = totals[DEDUP_T_AFFECTED]; dd->name_bytes = name_total;
+	h->last_dedup_ms = timer.ms(0, 6); h->last_dedup_key_ms = timer.ms(0, 1); h->last_dedup_sort_ms = c >= 2 ? timer.ms(2, 3) : 0.0; h->last_dedup_consensus_ms = K ? timer.ms(4, 5) : 0.0;
+	tmp.done();      /* (waited for above) */
+	return KMR_OK;
+}
+
+static int dedup_any(kmr_handle *h, const kmr_reads *r, const void *text, uint64_t text_len, bool text_on_device, const kmr_pairs *pairs, const uint8_t *discarded, const kmr_dedup_config *cfg, kmr_dedup **out) {
+	if (out) *out = nullptr;
+	int rc = dedup_check_config(h, cfg); if (rc) return rc;
+	if (!h || !r || !pairs || !out || (text_len && !text)) return fail(h, KMR_ERR_INVALID_ARG, "kmr_dedup_fragments: NULL argument");
+	if (r->device != h->device || pairs->device != h->device) return fail(h, KMR_ERR_INVALID_ARG, "read batch or pair list lives on another device");
+	if (pairs->n != r->n) return fail(h, KMR_ERR_INVALID_ARG, "kmr_dedup_fragments: the pair list belongs to a batch of " + std::to_string(pairs->n) + " reads, not " + std::to_string(r->n));
+	if (r->n >= 0xffffffffull) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_dedup_fragments: a batch holds fewer than 2^32 - 1 reads (pair positions of the sort are 32-bit)");
+	hipSetDevice(h->device);
+	auto dd = make_result<kmr_dedup>(h);
+	Scratch tmp(h);
+	const uint8_t *dtext, *ddisc;
+	rc = to_device(h, tmp, (const uint8_t *)text, r->n ? text_len : 0, &dtext, text_on_device); if (rc) return rc;
+	rc = to_device(h, tmp, discarded, r->n, &ddisc); if (rc) return rc;
+	rc = dedup_core(h, tmp, r, dtext, text_len, pairs, ddisc, cfg, dd.get());
+	if (!rc) *out = dd.release();
+	return rc;
+}
+int kmr_dedup_fragments(kmr_handle *h, const kmr_reads *reads, const char *text, uint64_t text_len, const kmr_pairs *pairs, const uint8_t *discarded, const kmr_dedup_config *cfg, kmr_dedup **out) {
+	return dedup_any(h, reads, text, text_len, false, pairs, discarded, cfg, out);
+}
+int kmr_dedup_fragments_dev(kmr_handle *h, const kmr_reads *reads, const void *dev_text, uint64_t text_len, const kmr_pairs *pairs, const uint8_t *discarded, const kmr_dedup_config *cfg, kmr_dedup **out) {
+	return dedup_any(h, reads, dev_text, text_len, true, pairs, discarded, cfg, out);
+}
+int kmr_dedup_info(const kmr_dedup *d, uint64_t *n_groups, uint64_t *n_new_reads, uint64_t *affected, uint64_t skipped[4]) {
+	if (!d) return KMR_ERR_INVALID_ARG;
+	if (n_groups) *n_groups = d->n_groups; if (n_new_reads) *n_new_reads = d->cons ? d->cons->n : 0; if (affected) *affected = d->affected;
+	if (skipped) for (int i = 0; i < 4; i++) skipped[i] = d->skipped[i];
+	return KMR_OK;
+}
+int kmr_dedup_copy(const kmr_dedup *d, uint8_t *discarded_out, uint64_t *group_first, uint32_t *group_size) {
+	if (!d) return KMR_ERR_INVALID_ARG;
+	hipSetDevice(d->device);
+	hipError_t e = hipSuccess;
+	copy_out(e, discarded_out, d->disc, d->n); copy_out(e, group_first, d->group_first, d->n_groups); copy_out(e, group_size, d->group_size, d->n_groups);
+	return e == hipSuccess ? KMR_OK : KMR_ERR_HIP;
+}
+int kmr_dedup_device_ptrs(const kmr_dedup *d, void **dev_discarded, void **dev_group_first, void **dev_group_size) {
+	if (!d) return KMR_ERR_INVALID_ARG;
+	if (dev_discarded) *dev_discarded = d->disc.get<uint8_t>(); if (dev_group_first) *dev_group_first = d->group_first.get<uint64_t>(); if (dev_group_size) *dev_group_size = d->group_size.get<uint32_t>();
+	return KMR_OK;
+}
+int kmr_dedup_reads(const kmr_dedup *d, const kmr_reads **consensus, const void **dev_name_text, uint64_t *name_text_len) {
+	if (!d) return KMR_ERR_INVALID_ARG;
+	if (consensus) *consensus = d->cons; if (dev_name_text) *dev_name_text = d->names.get<uint8_t>(); if (name_text_len) *name_text_len = d->name_bytes;
+	return KMR_OK;
+}
+int kmr_dedup_names_copy(const kmr_dedup *d, char *dst, uint64_t capacity) {
+	if (!d || (d->name_bytes && !dst)) return KMR_ERR_INVALID_ARG;
+	if (capacity < d->name_bytes) return KMR_ERR_CAPACITY;
+	hipSetDevice(d->device);
+	if (d->name_bytes && hipMemcpy(dst, d->names.get<uint8_t>(), d->name_bytes, hipMemcpyDeviceToHost) != hipSuccess) return KMR_ERR_HIP;
+	return KMR_OK;
+}
+void kmr_dedup_free(kmr_dedup *d) { free_on_device(d); }
+
+/* ---- a14: the mercount / mergraph text on the device (kmr_dump.hpp) ---------- */
+/* The common part of kmr_dump_text_size and kmr_dump_text: argument checks, the size pass over weak entries [lo, hi) and, when `out`
+ * is given, the writer. */
+static int dump_core(kmr_handle *h, int kind, uint32_t min_depth, uint64_t lo, uint64_t hi, uint64_t *kept, uint64_t *bytes, kmr_text **out) {
+	if (out) *out = nullptr;
+	if (!h) return KMR_ERR_INVALID_ARG;
+	if (kind != KMR_DUMP_MERCOUNT && kind != KMR_DUMP_MERGRAPH) return fail(h, KMR_ERR_INVALID_ARG, "unknown kmr_dump_kind");
+	if (!h->finalized) return fail(h, KMR_ERR_STATE, "dump before kmr_finalize");
+	const bool graph = kind == KMR_DUMP_MERGRAPH;
+	if (graph && !h->ext) return fail(h, KMR_ERR_STATE, "mergraph needs value_kind = KMR_VALUE_EXT");
+	const uint64_t n_map = h->weak.present ? h->weak.n : 0;
+	if (hi > n_map) hi = n_map;
+	if (lo > hi) return fail(h, KMR_ERR_INVALID_ARG, "dump: entry_lo lies behind entry_hi (entry_hi is clamped to the weak map's entries)");
+	hipSetDevice(h->device);
+	auto tx = make_result<kmr_text>(h);
+	h->last_dump_size_ms = h->last_dump_write_ms = 0;
+	const uint64_t n = hi - lo;
+	if (n) {
+		DumpParams P;
+		P.keys = h->weak.keys.get<uint64_t>(); P.vals = h->weak.vals.get<uint32_t>(); P.vw = h->ext ? 15u : 3u; P.k = h->k; P.graph = graph ? 1u : 0u;
+		P.min_depth = (int32_t)min_depth; P.lo = lo; P.n = n;
+		Scratch tmp(h); uint32_t *len; uint64_t *off;      /* off[n] = bytes, off[n + 1] = kept entries */
+		HIPCHK(h, tmp.take(&len, n)); HIPCHK(h, tmp.take(&off, n + 2));
+		SelectTimer timer(h->tune.dump_timing);
+		timer.mark(0, h->stream);
+		HIPCHK(h, hipMemsetAsync(off + n + 1, 0, 8, h->stream));
+		hipLaunchKernelGGL(dump_size_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, P, len, (unsigned long long *)(off + n + 1));
+		HIPCHK(h, hipGetLastError());
+		int rc = exclusive_scan(h, len, n, off); if (rc) return rc;
+		uint64_t totals[2] = {0, 0};
+		HIPCHK(h, hipMemcpyAsync(totals, off + n, 16, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));      /* the one copy that brings sizes back */
+		tx->bytes = totals[0]; tx->kept = totals[1];
+		if (out && tx->bytes) HIPCHK(h, tx->text.alloc((tx->bytes + 15) & ~(uint64_t)15));
+		timer.mark(1, h->stream);      /* (behind the allocation: the events then bracket the writer alone) */
+		if (out && tx->bytes) {
+			const uint64_t tiles = (tx->bytes + DUMP_TILE - 1) / DUMP_TILE;
+			const uint64_t per_block = (tiles + (uint64_t)num_cus(h) * 16 - 1) / ((uint64_t)num_cus(h) * 16);
+			const unsigned blocks = (unsigned)((tiles + per_block - 1) / per_block);
+			uint8_t *dout = tx->text.get<uint8_t>();
+			with_w(h, [&](auto W) { hipLaunchKernelGGL(dump_write_kernel<W()>, dim3(blocks), dim3(DUMP_THREADS), 0, h->stream, P, (const uint64_t *)off, tx->bytes, per_block, dout); return 0; });
+			HIPCHK(h, hipGetLastError());
+		}
+		timer.mark(2, h->stream);
+		HIPCHK(h, hipStreamSynchronize(h->stream));
+		tmp.done();
+		h->last_dump_size_ms = timer.ms(0, 1); h->last_dump_write_ms = timer.ms(1, 2);
+	}
+	if (kept) *kept = tx->kept;
+	if (bytes) *bytes = tx->bytes;
+	if (out) *out = tx.release();
+	return KMR_OK;
+}
+
+int kmr_dump_text_size(kmr_handle *h, int kind, uint32_t min_depth, uint64_t entry_lo, uint64_t entry_hi, uint64_t *kept, uint64_t *bytes) {
+	if (!h || !kept || !bytes) return KMR_ERR_INVALID_ARG;
+	return dump_core(h, kind, min_depth, entry_lo, entry_hi, kept, bytes, nullptr);
+}
+int kmr_dump_text(kmr_handle *h, int kind, uint32_t min_depth, uint64_t entry_lo, uint64_t entry_hi, kmr_text **out) {
+	if (!h || !out) { if (out) *out = nullptr; return KMR_ERR_INVALID_ARG; }
+	return dump_core(h, kind, min_depth, entry_lo, entry_hi, nullptr, nullptr, out);
+}
+int kmr_text_info(const kmr_text *t, uint64_t *kept, uint64_t *bytes) {
+	if (!t) return KMR_ERR_INVALID_ARG;
+	if (kept) *kept = t->kept; if (bytes) *bytes = t->bytes;
+	return KMR_OK;
+}
+int kmr_text_copy(const kmr_text *t, char *dst, uint64_t capacity) {
+	if (!t || (t->bytes && !dst)) return KMR_ERR_INVALID_ARG;
+	if (capacity < t->bytes) return KMR_ERR_CAPACITY;
+	hipSetDevice(t->device);
+	return !t->bytes || hipMemcpy(dst, t->text.get<uint8_t>(), t->bytes, hipMemcpyDeviceToHost) == hipSuccess ? KMR_OK : KMR_ERR_HIP;
+}
+int kmr_text_device_ptr(const kmr_text *t, void **dev_text) {
+	if (!t || !dev_text) return KMR_ERR_INVALID_ARG;
+	*dev_text = t->text.get<uint8_t>();
+	return KMR_OK;
+}
+void kmr_text_free(kmr_text *t) { free_on_device(t); }
+
+/* The file-appending forms: the text in pieces of entries whose text stays under the staging bound whatever their numbers are (a
+ * count has at most 5 digits, a tally at most 10), each copied to the host and appended. */
+static int dump_file(kmr_handle *h, const char *path, uint32_t min_depth, bool graph) {
+	if (!h || !path) return KMR_ERR_INVALID_ARG;
+	if (!h->finalized) return fail(h, KMR_ERR_STATE, "dump before kmr_finalize");
+	if (graph && !h->ext) return fail(h, KMR_ERR_STATE, "mergraph needs value_kind = KMR_VALUE_EXT");
+	const uint64_t n = h->weak.present ? h->weak.n : 0;
+	const uint64_t bound = h->tune.dump_piece_bytes ? h->tune.dump_piece_bytes : (uint64_t)KMR_DUMP_PIECE_BYTES;
+	const uint64_t entry_max = graph ? 2ull * (h->k + 15 + 12 * 10) : 2ull * (h->k + 2 + 5);
+	const uint64_t step = std::max<uint64_t>(1, bound / entry_max);
+	std::unique_ptr<FILE, int (*)(FILE *)> f(fopen(path, "a"), fclose);
+	if (!f) return fail(h, KMR_ERR_INVALID_ARG, std::string("cannot open ") + path);
+	std::vector<char> stage;
+	for (uint64_t lo = 0; lo < n; lo += step) {
+		kmr_text *t = nullptr;
+		int rc = dump_core(h, graph ? KMR_DUMP_MERGRAPH : KMR_DUMP_MERCOUNT, min_depth, lo, std::min(n, lo + step), nullptr, nullptr, &t); if (rc) return rc;
+		std::unique_ptr<kmr_text, void (*)(kmr_text *)> tx(t, kmr_text_free);
+		if (!tx->bytes) continue;
+		if (stage.size() < tx->bytes) stage.resize(tx->bytes);
+		HIPCHK(h, hipMemcpy(stage.data(), tx->text.get<uint8_t>(), tx->bytes, hipMemcpyDeviceToHost));
+		if (fwrite(stage.data(), 1, tx->bytes, f.get()) != tx->bytes) return fail(h, KMR_ERR_INVALID_ARG, std::string("cannot write ") + path);
+	}
+	return KMR_OK;
+}
+int kmr_dump_mercount(kmr_handle *h, const char *path, uint32_t min_depth) { return dump_file(h, path, min_depth, false); }
+int kmr_dump_mergraph(kmr_handle *h, const char *path, uint32_t min_depth) { return dump_file(h, path, min_depth, true); }
+
+/* ---- f2: the batch as 2-bit packed reads + markups -------------------------- */
+int kmr_reads_twobit(kmr_handle *h, const kmr_reads *r, uint8_t *twobit, uint64_t twobit_capacity, uint64_t *twobit_offsets,
+                     uint32_t *markup_pos, char *markup_char, uint64_t markup_capacity, uint64_t *markup_offsets,
+                     uint64_t *twobit_bytes, uint64_t *n_markups) {
+	if (!h || !r) return KMR_ERR_INVALID_ARG;
+	if (r->device != h->device) return fail(h, KMR_ERR_INVALID_ARG, "read batch lives on another device");
+	hipSetDevice(h->device);
+	const uint64_t n = r->n;
+	Scratch tmp(h); uint32_t *dlen, *dcnt; uint64_t *dtb, *dmk;
+	HIPCHK(h, tmp.take(&dlen, n + 1)); HIPCHK(h, tmp.take(&dcnt, n + 1)); HIPCHK(h, tmp.take(&dtb, n + 1)); HIPCHK(h, tmp.take(&dmk, n + 1));
+	uint64_t tb_total = 0, mk_total = 0;
+	if (n) {
+		hipLaunchKernelGGL(twobit_count_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, r->bases.get<uint8_t>(), r->offsets.get<uint64_t>(), n, dlen, dcnt);
+		HIPCHK(h, hipGetLastError());
+		int rc = exclusive_scan(h, dlen, n, dtb); if (rc) return rc;
+		rc = exclusive_scan(h, dcnt, n, dmk); if (rc) return rc;
+		HIPCHK(h, hipMemcpy(&tb_total, dtb + n, 8, hipMemcpyDeviceToHost)); HIPCHK(h, hipMemcpy(&mk_total, dmk + n, 8, hipMemcpyDeviceToHost));
+	} else { HIPCHK(h, hipMemset(dtb, 0, 8)); HIPCHK(h, hipMemset(dmk, 0, 8)); }
+	if (twobit_bytes) *twobit_bytes = tb_total; if (n_markups) *n_markups = mk_total;
+	if (!twobit && !markup_pos && !markup_char && !twobit_offsets && !markup_offsets) return KMR_OK;      /* sizes only */
+	if ((twobit && twobit_capacity < tb_total) || ((markup_pos || markup_char) && markup_capacity < mk_total)) return KMR_ERR_CAPACITY;
+	uint8_t *dtw, *dmc; uint32_t *dmp;
+	HIPCHK(h, tmp.take(&dtw, tb_total)); HIPCHK(h, tmp.take(&dmp, mk_total)); HIPCHK(h, tmp.take(&dmc, mk_total));
+	if (n) {
+		hipLaunchKernelGGL(twobit_pack_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, r->bases.get<uint8_t>(), r->offsets.get<uint64_t>(), n, dtb, dmk, dtw, dmp, dmc);
+		HIPCHK(h, hipGetLastError());
+	}
+	HIPCHK(h, hipStreamSynchronize(h->stream));
+	tmp.done();
+	hipError_t e = hipSuccess;
+	if (twobit && tb_total) e = hipMemcpy(twobit, dtw, tb_total, hipMemcpyDeviceToHost);
+	if (e == hipSuccess && twobit_offsets) e = hipMemcpy(twobit_offsets, dtb, 8 * (n + 1), hipMemcpyDeviceToHost);
+	if (e == hipSuccess && markup_pos && mk_total) e = hipMemcpy(markup_pos, dmp, 4 * mk_total, hipMemcpyDeviceToHost);
+	if (e == hipSuccess && markup_char && mk_total) e = hipMemcpy(markup_char, dmc, mk_total, hipMemcpyDeviceToHost);
+	if (e == hipSuccess && markup_offsets) e = hipMemcpy(markup_offsets, dmk, 8 * (n + 1), hipMemcpyDeviceToHost);
+	HIPCHK(h, e);
+	return KMR_OK;
+}
+
+int kmr_reads_from_twobit(kmr_handle *h, const uint8_t *twobit, const uint64_t *twobit_offsets, const uint64_t *offsets,
+                          const uint64_t *markup_offsets, const uint32_t *markup_pos, const char *markup_char,
+                          const char *quals, int uniform_quality, uint64_t n_reads, kmr_reads **out) {
+	if (!h || !out || !offsets || !twobit_offsets || (n_reads && !twobit)) return KMR_ERR_INVALID_ARG;
+	if (uniform_quality < 0 || uniform_quality > 255 || (quals && uniform_quality)) return fail(h, KMR_ERR_INVALID_ARG, "uniform_quality: 0, or the one quality character of a batch without a quality array");
+	*out = nullptr;
+	hipSetDevice(h->device);
+	const uint64_t first = offsets[0], total = offsets[n_reads] - first, tbytes = twobit_offsets[n_reads] - twobit_offsets[0];
+	const uint64_t nm = markup_offsets ? markup_offsets[n_reads] - markup_offsets[0] : 0;
+	auto r = make_result<kmr_reads>(h);
+	r->n = n_reads; r->total = total; r->input_base = h->cfg.fastq_start_char;
+	HIPCHK(h, r->bases.alloc(total + 64)); HIPCHK(h, r->quals.alloc(total + 64));
+	HIPCHK(h, r->offsets.alloc(8 * (n_reads + 1)));
+	HIPCHK(h, r->name_off.alloc(8 * std::max<uint64_t>(n_reads, 1))); HIPCHK(h, r->name_len.alloc(4 * std::max<uint64_t>(n_reads, 1)));
+	HIPCHK(h, hipMemset(r->bases.get<uint8_t>() + total, 0, 64)); HIPCHK(h, hipMemset(r->quals.get<uint8_t>() + total, 0, 64));
+	HIPCHK(h, hipMemset(r->name_off.get<uint64_t>(), 0, 8 * std::max<uint64_t>(n_reads, 1))); HIPCHK(h, hipMemset(r->name_len.get<uint32_t>(), 0, 4 * std::max<uint64_t>(n_reads, 1)));
+	/* qualities: the array, the one character, or Read::REF_QUAL (a batch always has a quality array; REF_QUAL reads weigh 1) */
+	if (quals) { if (total) HIPCHK(h, hipMemcpy(r->quals.get<uint8_t>(), quals + first, total, hipMemcpyHostToDevice)); }
+	else HIPCHK(h, hipMemset(r->quals.get<uint8_t>(), uniform_quality ? uniform_quality : 127, total));
+	if (!n_reads) { HIPCHK(h, hipMemset(r->offsets.get<uint64_t>(), 0, 8)); *out = r.release(); return KMR_OK; }
+	Scratch tmp(h); uint8_t *dtb, *dmc = nullptr; uint64_t *dto, *doff, *dmo = nullptr; uint32_t *dmp = nullptr;
+	HIPCHK(h, tmp.take(&dtb, tbytes + 64)); HIPCHK(h, tmp.take(&dto, n_reads + 1)); HIPCHK(h, tmp.take(&doff, n_reads + 1));
+	std::vector<uint64_t> rel(n_reads + 1), trel(n_reads + 1), mrel(markup_offsets ? n_reads + 1 : 0);
+	for (uint64_t i = 0; i <= n_reads; i++) { rel[i] = offsets[i] - first; trel[i] = twobit_offsets[i] - twobit_offsets[0]; if (markup_offsets) mrel[i] = markup_offsets[i] - markup_offsets[0]; }
+	if (tbytes) HIPCHK(h, hipMemcpy(dtb, twobit + twobit_offsets[0], tbytes, hipMemcpyHostToDevice));
+	HIPCHK(h, hipMemcpy(dto, trel.data(), 8 * (n_reads + 1), hipMemcpyHostToDevice)); HIPCHK(h, hipMemcpy(doff, rel.data(), 8 * (n_reads + 1), hipMemcpyHostToDevice));
+	hipLaunchKernelGGL(twobit_unpack_kernel, dim3((unsigned)std::min<uint64_t>((n_reads + 255) / 256, (uint64_t)num_cus(h) * 32)), dim3(256), 0, h->stream, (const uint8_t *)dtb, (const uint64_t *)dto, (const uint64_t *)doff, n_reads, r->bases.get<uint8_t>(), r->offsets.get<uint64_t>());
+	HIPCHK(h, hipGetLastError());
+	if (nm) {
+		HIPCHK(h, tmp.take(&dmo, n_reads + 1)); HIPCHK(h, tmp.take(&dmp, nm)); HIPCHK(h, tmp.take(&dmc, nm));
+		HIPCHK(h, hipMemcpy(dmo, mrel.data(), 8 * (n_reads + 1), hipMemcpyHostToDevice));
+		HIPCHK(h, hipMemcpy(dmp, markup_pos + markup_offsets[0], 4 * nm, hipMemcpyHostToDevice)); HIPCHK(h, hipMemcpy(dmc, markup_char + markup_offsets[0], nm, hipMemcpyHostToDevice));
+		hipLaunchKernelGGL(twobit_markup_kernel, dim3(grid_for(n_reads)), dim3(256), 0, h->stream, (const uint64_t *)dmo, (const uint32_t *)dmp, (const uint8_t *)dmc, (const uint64_t *)r->offsets.get<uint64_t>(), n_reads, r->bases.get<uint8_t>());
+		HIPCHK(h, hipGetLastError());
+	}
+	HIPCHK(h, hipStreamSynchronize(h->stream));
+	tmp.done();
+	*out = r.release();
+	return KMR_OK;
+}
+
+
+}  // extern "C"

@@ -37,6 +37,42 @@ def _u8(a):
     return np.ascontiguousarray(a, dtype=np.uint8)
 
 
+def _ok(rc, what):
+    """a status of the library that has no handle error text behind it"""
+    if rc != 0:
+        raise KmerSpectrumError("%s: %s" % (what, _lib.STATUS.get(rc, rc)))
+
+
+class _DeviceObject:
+    """A device object of the library owned through a handle (the attribute named _HANDLE) and given back with the library's
+    function _FREE: by close(), which may be called again, at the end of a `with` block, and when the object is collected."""
+    _HANDLE = _FREE = None
+
+    def _live(self):
+        h = getattr(self, self._HANDLE, None)
+        if not h:
+            raise KmerSpectrumError("%s: closed" % type(self).__name__)
+        return h
+
+    def close(self):
+        h = getattr(self, self._HANDLE, None)
+        if h:
+            getattr(self.sp.lib, self._FREE)(h)
+            setattr(self, self._HANDLE, None)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class KmerSpectrum:
     """One spectrum (weak + singleton maps) resident on one MI355X."""
 
@@ -487,9 +523,10 @@ class KmerSpectrum:
 _U64_MAX = (1 << 64) - 1
 
 
-class DumpText:
+class DumpText(_DeviceObject):
     """A mercount / mergraph text in device memory (kmr_text): .kept entries, .bytes; numpy() copies it to the host,
     device_tensor() is a torch uint8 view of it where it lies, valid until close()."""
+    _HANDLE, _FREE = "_t", "kmr_text_free"
 
     def __init__(self, sp, handle):
         self.sp, self._t = sp, handle
@@ -497,16 +534,9 @@ class DumpText:
         sp._call("text_info", handle, C.byref(kept), C.byref(nbytes))
         self.kept, self.bytes = kept.value, nbytes.value
 
-    def _live(self):
-        if not self._t:
-            raise KmerSpectrumError("DumpText: closed")
-        return self._t
-
     def numpy(self):
         buf = np.zeros(self.bytes, dtype=np.uint8)
-        rc = self.sp.lib.kmr_text_copy(self._live(), buf.ctypes.data_as(C.c_void_p) if self.bytes else None, self.bytes)
-        if rc != 0:
-            raise KmerSpectrumError("kmr_text_copy: %s" % _lib.STATUS.get(rc, rc))
+        _ok(self.sp.lib.kmr_text_copy(self._live(), buf.ctypes.data_as(C.c_void_p) if self.bytes else None, self.bytes), "kmr_text_copy")
         return buf
 
     def device_ptr(self):
@@ -522,22 +552,6 @@ class DumpText:
         view = type("_DeviceBytes", (), {"__cuda_array_interface__": {"shape": (self.bytes,), "typestr": "|u1", "data": (ptr, False), "version": 2, "strides": None}})()
         return torch.as_tensor(view, device="cuda")
 
-    def close(self):
-        if getattr(self, "_t", None):
-            self.sp.lib.kmr_text_free(self._t)
-            self._t = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class Histogram:
@@ -585,10 +599,11 @@ class Histogram:
         return "\n".join(out) + "\n"
 
 
-class ReadSet:
+class ReadSet(_DeviceObject):
     """Device-resident reads parsed from FASTQ text on the GPU: the reference's ReadSet::appendFastq path
     (src/ReadSet.cpp:311-345 over FastqStreamParser, src/ReadFileReader.h:768-835) incl. the Casava-1.8 filter and the
     quality-base detection of validateFastqStart (src/ReadSet.h:171-209).  Bound to the device of `spectrum`."""
+    _HANDLE, _FREE = "r", "kmr_reads_free"
 
     def __init__(self, spectrum, text, input_quality_base=0, store_comment=True):
         self.sp = spectrum
@@ -666,10 +681,8 @@ class ReadSet:
         o = np.zeros(self.n + 1, dtype=np.uint64)
         no = np.zeros(max(1, self.n), dtype=np.uint64)
         nl = np.zeros(max(1, self.n), dtype=np.uint32)
-        rc = self.sp.lib.kmr_reads_copy(self.r, b.ctypes.data_as(C.c_void_p), q.ctypes.data_as(C.c_void_p), o.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                        no.ctypes.data_as(C.POINTER(C.c_uint64)), nl.ctypes.data_as(C.POINTER(C.c_uint32)))
-        if rc != 0:
-            raise KmerSpectrumError("kmr_reads_copy: %s" % _lib.STATUS.get(rc, rc))
+        _ok(self.sp.lib.kmr_reads_copy(self.r, b.ctypes.data_as(C.c_void_p), q.ctypes.data_as(C.c_void_p), o.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                        no.ctypes.data_as(C.POINTER(C.c_uint64)), nl.ctypes.data_as(C.POINTER(C.c_uint32))), "kmr_reads_copy")
         names = [self.text[int(no[i]):int(no[i]) + int(nl[i])] for i in range(self.n)]
         return b, q, o, names
 
@@ -686,38 +699,22 @@ class ReadSet:
             self.sp._call("identify_pairs", self.sp.h, self.r, buf.ctypes.data_as(C.c_void_p) if buf.size else None, buf.size, 1 if sc else 0, C.byref(out))
         return ReadPairs(self.sp, out)
 
-    def close(self):
-        if getattr(self, "r", None):
-            self.sp.lib.kmr_reads_free(self.r)
-            self.r = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
-class ReadPairs:
+class ReadPairs(_DeviceObject):
     """What ReadSet.identifyPairs found (kmr_pairs), kept on the device until close(): .mate[i] = the read paired with i or -1 (what
     FilterKnownOddities.applyFilter(mate=) and ReadSelector(mate=) take), .pairs = the reference's pair list as an (n_pairs, 2)
     int64 array of (read1, read2) with -1 for a missing side, and the counts n_reads, n_pairs, n_full, n_sequential, n_conflicts."""
+    _HANDLE, _FREE = "_p", "kmr_pairs_free"
 
     def __init__(self, sp, handle):
         self.sp, self._p = sp, handle
         v = [C.c_uint64() for _ in range(5)]
         hp = C.c_int()
-        rc = sp.lib.kmr_pairs_info(handle, *[C.byref(x) for x in v], C.byref(hp))
-        if rc != 0:
-            raise KmerSpectrumError("kmr_pairs_info: %s" % _lib.STATUS.get(rc, rc))
+        _ok(sp.lib.kmr_pairs_info(handle, *[C.byref(x) for x in v], C.byref(hp)), "kmr_pairs_info")
         self.n_reads, self.n_pairs, self.n_full, self.n_sequential, self.n_conflicts = [x.value for x in v]
         self._has_pairs = bool(hp.value)
         self._host = None
-
-    def _live(self):
-        if not self._p:
-            raise KmerSpectrumError("ReadPairs: closed")
-        return self._p
 
     def _copy(self):
         if self._host is None:
@@ -725,9 +722,7 @@ class ReadPairs:
             mate = np.zeros(max(1, self.n_reads), dtype=np.int64)
             r1 = np.zeros(max(1, self.n_pairs), dtype=np.int64)
             r2 = np.zeros(max(1, self.n_pairs), dtype=np.int64)
-            rc = self.sp.lib.kmr_pairs_copy(self._live(), mate.ctypes.data_as(i64), r1.ctypes.data_as(i64), r2.ctypes.data_as(i64))
-            if rc != 0:
-                raise KmerSpectrumError("kmr_pairs_copy: %s" % _lib.STATUS.get(rc, rc))
+            _ok(self.sp.lib.kmr_pairs_copy(self._live(), mate.ctypes.data_as(i64), r1.ctypes.data_as(i64), r2.ctypes.data_as(i64)), "kmr_pairs_copy")
             self._host = (mate[:self.n_reads], np.stack([r1[:self.n_pairs], r2[:self.n_pairs]], axis=1))
         return self._host
 
@@ -749,34 +744,17 @@ class ReadPairs:
     def device_ptrs(self):
         """device pointers of (mate[n_reads], read1[n_pairs], read2[n_pairs]), int64 each; valid until close()"""
         a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        rc = self.sp.lib.kmr_pairs_device_ptrs(self._live(), C.byref(a), C.byref(b), C.byref(c))
-        if rc != 0:
-            raise KmerSpectrumError("kmr_pairs_device_ptrs: %s" % _lib.STATUS.get(rc, rc))
+        _ok(self.sp.lib.kmr_pairs_device_ptrs(self._live(), C.byref(a), C.byref(b), C.byref(c)), "kmr_pairs_device_ptrs")
         return a.value or 0, b.value or 0, c.value or 0
 
-    def close(self):
-        if getattr(self, "_p", None):
-            self.sp.lib.kmr_pairs_free(self._p)
-            self._p = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
-class FilterKnownOddities:
+class FilterKnownOddities(_DeviceObject):
     """The artifact filter FilterReads runs before the spectrum build (src/FilterKnownOddities.h, apps/FilterReads.cpp:107-118):
     quality-run trimming plus a screen of every 4th 24-mer of a read against the artifact sequences (and their substitution
     neighbours), on the device.  `fasta` = the sequences as FASTA text (the reference embeds its own table); keyword
     arguments are the fields of kmr_artifact_config (edit_distance, min_quality, fastq_start_char, min_read_length, ...)."""
+    _HANDLE, _FREE = "f", "kmr_artifact_filter_free"
 
     def __init__(self, spectrum, fasta, **kw):
         self.sp = spectrum
@@ -800,9 +778,7 @@ class FilterKnownOddities:
     def entries(self):
         keys = np.zeros(self.n_filter_kmers, dtype=np.uint64)
         vals = np.zeros(self.n_filter_kmers, dtype=np.uint32)
-        rc = self.sp.lib.kmr_artifact_filter_entries(self.f, keys.ctypes.data_as(C.POINTER(C.c_uint64)), vals.ctypes.data_as(C.POINTER(C.c_uint32)), keys.size)
-        if rc != 0:
-            raise KmerSpectrumError("kmr_artifact_filter_entries: %s" % _lib.STATUS.get(rc, rc))
+        _ok(self.sp.lib.kmr_artifact_filter_entries(self.f, keys.ctypes.data_as(C.POINTER(C.c_uint64)), vals.ctypes.data_as(C.POINTER(C.c_uint32)), keys.size), "kmr_artifact_filter_entries")
         return keys, vals
 
     def applyFilter(self, reads, mate=None, want_reads=True):
@@ -825,25 +801,16 @@ class FilterKnownOddities:
         res = {k: v[:n] for k, v in res.items()}
         return res, (ReadSet._adopt(self.sp, reads.text, out, getattr(reads, "store_comment", True)) if want_reads else None)
 
-    def close(self):
-        if getattr(self, "f", None):
-            self.sp.lib.kmr_artifact_filter_free(self.f)
-            self.f = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
-class ReadSelector:
+class ReadSelector(_DeviceObject):
     """ReadSelector over a device-resident ReadSet (src/ReadSelector.h): scoreAndTrimReads (:1182-1207), pickAllPassingReads /
     pickAllPassingPairs (:576-596) and writePicks (:1242-1262), selection and text produced on the device (kmr_select_reads,
     kmr_filter_read_batch).  `mate` = index of each read's pair or -1 (None: every read is single); `filter_results` = the dict
     FilterKnownOddities.applyFilter returned for the batch `read_set` was made from (the remnants it appended count as single,
     untouched reads).  The output text stays on the device until writePicks copies it."""
 
+    _HANDLE, _FREE = "_picks", "kmr_picks_free"
     FORMAT = {"fastq": 0, "fasta": 1}
 
     def __init__(self, spectrum, read_set, mate=None, filter_results=None):
@@ -893,7 +860,7 @@ class ReadSelector:
         return self._p(a[0], C.c_uint8), self._p(a[1], C.c_uint32), self._p(a[2], C.c_uint32)
 
     def _adopt(self, handle):
-        self._free()
+        self.close()
         self._picks = handle
         n, b = C.c_uint64(), C.c_uint64()
         self.sp.lib.kmr_picks_info(handle, C.byref(n), C.byref(b))
@@ -952,9 +919,7 @@ class ReadSelector:
     def _copy(self):
         buf = np.zeros(max(1, self.bytes), dtype=np.uint8)
         flags = np.zeros(max(1, self.reads.n), dtype=np.uint8)
-        rc = self.sp.lib.kmr_picks_copy(self._picks, buf.ctypes.data_as(C.c_void_p), self.bytes, flags.ctypes.data_as(C.POINTER(C.c_uint8)))
-        if rc != 0:
-            raise KmerSpectrumError("kmr_picks_copy: %s" % _lib.STATUS.get(rc, rc))
+        _ok(self.sp.lib.kmr_picks_copy(self._picks, buf.ctypes.data_as(C.c_void_p), self.bytes, flags.ctypes.data_as(C.POINTER(C.c_uint8))), "kmr_picks_copy")
         self.picked_flags = flags[:self.reads.n].astype(bool)
         self._text = buf[:self.bytes].tobytes()
         return self._text
@@ -983,19 +948,6 @@ class ReadSelector:
         self.sp._call("picks_device_ptr", self._picks, C.byref(p))
         return p.value, self.bytes
 
-    def _free(self):
-        if getattr(self, "_picks", None):
-            self.sp.lib.kmr_picks_free(self._picks)
-            self._picks = None
-
-    def close(self):
-        self._free()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class ConsensusReadSet(ReadSet):
@@ -1012,46 +964,36 @@ class ConsensusReadSet(ReadSet):
         self.r = None          # the DedupPass frees it
 
 
-class DedupPass:
+class DedupPass(_DeviceObject):
     """What one kmr_dedup_fragments* call left (kmr_dedup), kept on the device until close(): .discarded (uint8 per read: the
     flags handed in OR the new discards), .affected, .skipped = (discarded, too short, unpaired, invalid), .groups = (n_groups, 2)
     int64 array of (pair-list position of the first member, member count), .consensus = the new reads as a ConsensusReadSet,
     .consensus_mate = the mate of each of them (2g <-> 2g + 1 in the paired pass, -1 in the single pass); .single = the
     --dedup-single pass that followed, or None."""
+    _HANDLE, _FREE = "_d", "kmr_dedup_free"
 
     def __init__(self, sp, handle, paired, n_reads):
         self.sp, self._d, self.paired, self.single, self.n_reads = sp, handle, bool(paired), None, n_reads
         ng, nn, af = C.c_uint64(), C.c_uint64(), C.c_uint64()
         sk = (C.c_uint64 * 4)()
-        rc = sp.lib.kmr_dedup_info(handle, C.byref(ng), C.byref(nn), C.byref(af), sk)
-        if rc != 0:
-            raise KmerSpectrumError("kmr_dedup_info: %s" % _lib.STATUS.get(rc, rc))
+        _ok(sp.lib.kmr_dedup_info(handle, C.byref(ng), C.byref(nn), C.byref(af), sk), "kmr_dedup_info")
         self.n_groups, self.n_new_reads, self.affected, self.skipped = ng.value, nn.value, af.value, tuple(int(v) for v in sk)
         r, nt, nl = C.c_void_p(), C.c_void_p(), C.c_uint64()
         sp.lib.kmr_dedup_reads(handle, C.byref(r), C.byref(nt), C.byref(nl))
         names = np.zeros(max(1, nl.value), dtype=np.uint8)
-        rc = sp.lib.kmr_dedup_names_copy(handle, names.ctypes.data_as(C.c_void_p), nl.value)
-        if rc != 0:
-            raise KmerSpectrumError("kmr_dedup_names_copy: %s" % _lib.STATUS.get(rc, rc))
+        _ok(sp.lib.kmr_dedup_names_copy(handle, names.ctypes.data_as(C.c_void_p), nl.value), "kmr_dedup_names_copy")
         self.device_name_text = (nt.value or 0, nl.value)
         self.consensus = ConsensusReadSet._borrow(self, sp, names[:nl.value].tobytes(), r)
         m = np.arange(self.n_new_reads, dtype=np.int64)
         self.consensus_mate = (m ^ 1) if self.paired else np.full(self.n_new_reads, -1, dtype=np.int64)
         self._host = None
 
-    def _live(self):
-        if not self._d:
-            raise KmerSpectrumError("DedupPass: closed")
-        return self._d
-
     def _copy(self):
         if self._host is None:
             disc = np.zeros(max(1, self.n_reads), dtype=np.uint8)
             gf = np.zeros(max(1, self.n_groups), dtype=np.uint64)
             gs = np.zeros(max(1, self.n_groups), dtype=np.uint32)
-            rc = self.sp.lib.kmr_dedup_copy(self._live(), disc.ctypes.data_as(C.POINTER(C.c_uint8)), gf.ctypes.data_as(C.POINTER(C.c_uint64)), gs.ctypes.data_as(C.POINTER(C.c_uint32)))
-            if rc != 0:
-                raise KmerSpectrumError("kmr_dedup_copy: %s" % _lib.STATUS.get(rc, rc))
+            _ok(self.sp.lib.kmr_dedup_copy(self._live(), disc.ctypes.data_as(C.POINTER(C.c_uint8)), gf.ctypes.data_as(C.POINTER(C.c_uint64)), gs.ctypes.data_as(C.POINTER(C.c_uint32))), "kmr_dedup_copy")
             self._host = (disc[:self.n_reads], np.stack([gf[:self.n_groups].astype(np.int64), gs[:self.n_groups].astype(np.int64)], axis=1))
         return self._host
 
@@ -1066,9 +1008,7 @@ class DedupPass:
     def device_ptrs(self):
         """device pointers of (discarded[n_reads] uint8, group_first[n_groups] uint64, group_size[n_groups] uint32); valid until close()"""
         a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        rc = self.sp.lib.kmr_dedup_device_ptrs(self._live(), C.byref(a), C.byref(b), C.byref(c))
-        if rc != 0:
-            raise KmerSpectrumError("kmr_dedup_device_ptrs: %s" % _lib.STATUS.get(rc, rc))
+        _ok(self.sp.lib.kmr_dedup_device_ptrs(self._live(), C.byref(a), C.byref(b), C.byref(c)), "kmr_dedup_device_ptrs")
         return a.value or 0, b.value or 0, c.value or 0
 
     def close(self):
@@ -1076,20 +1016,7 @@ class DedupPass:
             self.single.close()
         if getattr(self, "_d", None):
             self.consensus.r = None
-            self.sp.lib.kmr_dedup_free(self._d)
-            self._d = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().close()
 
 
 class DuplicateFragmentFilter:
@@ -1140,7 +1067,5 @@ def synth_reads_device(torch, seed, first_read, n_reads, read_len, genome_len, n
         quals = torch.zeros(n_reads * read_len + 64, dtype=torch.uint8, device=device)
         offsets = torch.empty(n_reads + 1, dtype=torch.int64, device=device)
         torch.cuda.synchronize()
-        rc = lib.kmr_synth_reads_dev(seed, first_read, n_reads, read_len, genome_len, 1 if noisy else 0, bases.data_ptr(), quals.data_ptr(), offsets.data_ptr())
-        if rc:
-            raise KmerSpectrumError("kmr_synth_reads_dev: %s" % _lib.STATUS.get(rc, rc))
+        _ok(lib.kmr_synth_reads_dev(seed, first_read, n_reads, read_len, genome_len, 1 if noisy else 0, bases.data_ptr(), quals.data_ptr(), offsets.data_ptr()), "kmr_synth_reads_dev")
     return bases, quals, offsets

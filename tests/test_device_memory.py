@@ -123,3 +123,53 @@ def test_errors_after_allocating_leave_nothing_behind(probe, reads):
     wrong.close()
     p.close()
     assert _live(probe) == base
+
+
+def _stage_spectrum(text):
+    """a finalized k=31 spectrum (mode 3, EXT values, so that mergraph works) of the FASTQ `text`, and the text's batch"""
+    p = _spectrum(31, 3, ext=True)
+    rs = ka.ReadSet(p, text)
+    p.buildKmerSpectrumFromReadSet(rs)
+    p.finalize(1)
+    return p, rs
+
+
+def test_read_stages_return_every_block(probe):
+    """identifyPairs, the selector, the duplicate-fragment filter (its empty branch on 1000.fastq, its consensus branch on
+    consensus3.fastq, each with the single pass behind) and the mercount / mergraph text"""
+    base = _live(probe)
+    p, rs = _stage_spectrum(open(GOLDEN + "/1000.fastq", "rb").read())
+    pairs = rs.identifyPairs()
+    sel = ka.ReadSelector(p, rs, mate=pairs.mate)
+    sel.filterReads()
+    assert len(sel.writePicks()) == sel.bytes
+    dd = ka.DuplicateFragmentFilter(p, dedup_mode=1).filterDuplicateFragments(rs, pairs, dedup_single=True)
+    assert dd.n_groups == 0
+    counts, graphs = p.dumpCountsText(1), p.dumpGraphsText(1)
+    assert counts.bytes and graphs.bytes
+    dup = ka.ReadSet(p, open(GOLDEN + "/consensus3.fastq", "rb").read())
+    dup_pairs = dup.identifyPairs()
+    dd2 = ka.DuplicateFragmentFilter(p, dedup_mode=1).filterDuplicateFragments(dup, dup_pairs, dedup_single=True)
+    assert dd2.n_groups >= 1 and dd2.consensus.n >= 2
+    assert _live(probe) > base
+    for x in (dd2, dup_pairs, dup, counts, graphs, dd, sel, pairs, rs, p):
+        x.close()
+    assert _live(probe) == base
+
+
+def test_read_stage_errors_leave_nothing_behind(probe):
+    """a text shorter than the one the batch was ingested from (the name-span error of each stage) and a pair list of another batch"""
+    base = _live(probe)
+    p, rs = _stage_spectrum(open(GOLDEN + "/consensus3.fastq", "rb").read())
+    pairs = rs.identifyPairs()
+    dedup = ka.DuplicateFragmentFilter(p, dedup_mode=1)
+    full, rs.text = rs.text, rs.text[:10]
+    _twice(probe, rs.identifyPairs)
+    _twice(probe, lambda: ka.ReadSelector(p, rs, mate=pairs.mate).filterReads())
+    _twice(probe, lambda: dedup.filterDuplicateFragments(rs, pairs))
+    rs.text = full
+    other = ka.ReadSet(p, open(GOLDEN + "/1000.fastq", "rb").read())
+    _twice(probe, lambda: dedup.filterDuplicateFragments(other, pairs))        # "pair list belongs"
+    for x in (other, pairs, rs, p):
+        x.close()
+    assert _live(probe) == base
