@@ -121,20 +121,39 @@ void sk_track_boundary_kernel(ReadsView rv, DevParams p, SkBoundary *bd, uint32_
 }
 
 /* Record, in 16-byte granules:
- *   granule 0   { ordinal low 32 | ordinal bits 32..39, n << 8, uniform << 16, granules << 17 | minimizer hash | weight (f32 bits) }
+ *   granule 0   the header { x, y, z, w }, taken apart and put together by sk_hdr_* / sk_make_header below and by nothing else:
+ *                 x          stream ordinal of the run's first k-mer, low 32 bits (the other k-mers follow by +1)
+ *                 y  0..7    ordinal bits 32..39
+ *                    8..15   n, the record's k-mers (1 .. SK_MAX_N)
+ *                    16      uniform: one weight (w) for all n k-mers
+ *                    17..23  the record's granules, this one included
+ *                    24..30  extension records only: the base left of the first k-mer (24..26) and right of the last one (27..29),
+ *                            0..3 or SK_EXT_X = 'X' where the read ends; bit 30 marks such a record
+ *                 z          minimizer hash
+ *                 w          weight (f32 bits)
  *   granules    the run's n + k - 1 bases, 64 per granule, first base in the top two bits of the first dword
  *   granules    n f32 weights, 4 per granule -- only when the run's weights are not all equal (uniform == 0)
- * ordinal = stream ordinal of the run's first k-mer; the others follow by +1. */
-__host__ __device__ __forceinline__ uint32_t sk_base_granules(uint32_t n, uint32_t k) { return (n + k - 1 + 63) / 64; }
-/* Records of a build with extension values (KMR_VALUE_EXT: ExtensionTrackingData, src/KmerTrackingData.h:1027-1126) end in
+ * Records of a build with extension values (KMR_VALUE_EXT: ExtensionTrackingData, src/KmerTrackingData.h:1027-1126) end in
  *   granules    ceil(n / 8): two bytes per k-mer, the quality of its LEFT neighbour and of its RIGHT neighbour,
  *               as (quality char - fastq base) & 0xff, Read::REF_QUAL for a read without qualities and the minimum
  *               extension quality where the read ends (Extension('X', extMinQuality), src/KmerReadUtils.h:224-236)
- * and say in their header (bits 24..26, 27..29 of the second word; bit 30 marks such a record) which base lies left of the first
- * k-mer and right of the last one: 0..3, or 5 = 'X' where the read ends.  The neighbours in between are the record's own bases. */
+ * The neighbours between a record's first and last k-mer are the record's own bases. */
 static const uint32_t SK_EXT_X = 5u;
+__host__ __device__ __forceinline__ uint32_t sk_base_granules(uint32_t n, uint32_t k) { return (n + k - 1 + 63) / 64; }
 __host__ __device__ __forceinline__ uint32_t sk_ext_granules(uint32_t n) { return (n + 7) / 8; }
 __host__ __device__ __forceinline__ uint32_t sk_rec_granules(uint32_t n, uint32_t k, bool uniform, bool ext) { return 1 + sk_base_granules(n, k) + (uniform ? 0u : (n + 3) / 4) + (ext ? sk_ext_granules(n) : 0u); }
+__device__ __forceinline__ uint32_t sk_hdr_n(uint32_t y) { return (y >> 8) & 0xffu; }
+__device__ __forceinline__ bool sk_hdr_uniform(uint32_t y) { return ((y >> 16) & 1u) != 0; }
+__device__ __forceinline__ uint32_t sk_hdr_granules(uint32_t y) { return (y >> 17) & 0x7fu; }
+__device__ __forceinline__ uint64_t sk_hdr_ordinal(uint32_t x, uint32_t y) { return (uint64_t)x | ((uint64_t)(y & 0xffu) << 32); }
+__device__ __forceinline__ bool sk_hdr_is_ext(uint32_t y) { return ((y >> 30) & 1u) != 0; }
+__device__ __forceinline__ uint32_t sk_hdr_ext_left(uint32_t y) { return (y >> 24) & 7u; }
+__device__ __forceinline__ uint32_t sk_hdr_ext_right(uint32_t y) { return (y >> 27) & 7u; }
+/* ext: 0, or sk_hdr_ext(left code, right code) for an extension record */
+__device__ __forceinline__ uint32_t sk_hdr_ext(uint32_t left, uint32_t right) { return (left << 24) | (right << 27) | (1u << 30); }
+__device__ __forceinline__ uint4 sk_make_header(unsigned long long ord, uint32_t n, bool uniform, uint32_t granules, uint32_t ext, uint32_t mhash, uint32_t wbits) {
+	return make_uint4((uint32_t)ord, (uint32_t)(ord >> 32) | (n << 8) | ((uniform ? 1u : 0u) << 16) | (granules << 17) | ext, mhash, wbits);
+}
 
 #ifndef KMR_INSTANCE_TU
 __global__ void sk_state_init_kernel(unsigned long long *state, uint64_t n) {
@@ -514,7 +533,7 @@ void sk_extract_kernel(ReadsView rv, DevParams p, SkParams sp, PoolView pool) {
 						else if (rv.u_start && myStart > rv.offsets[myRead]) { uint32_t c = base_code(rv.bases[myStart - 1]); oL = c == 4 ? 0u : c; qL = isRef ? qref : ((uint32_t)rv.quals[myStart - 1] - p.fastq_start) & 0xffu; }
 						if (e < L) { oR = (sk_bases16(pk, rbOff + e) >> 30) & 3u; qR = isRef ? qref : ((uint32_t)rq[e] - p.fastq_start) & 0xffu; }
 						else if (rv.u_start && myEnd < rv.offsets[myRead + 1]) { uint32_t c = base_code(rv.bases[myEnd]); oR = c == 4 ? 0u : c; qR = isRef ? qref : ((uint32_t)rv.quals[myEnd] - p.fastq_start) & 0xffu; }
-						hdrExt = (oL << 24) | (oR << 27) | (1u << 30);
+						hdrExt = sk_hdr_ext(oL, oR);
 						const uint32_t neg = sk_ext_granules(n);
 						for (uint32_t g = 0; g < neg; g++) {
 							uint2 lq = make_uint2(qref * 0x01010101u, qref * 0x01010101u), rqv = lq;
@@ -531,7 +550,7 @@ void sk_extract_kernel(ReadsView rv, DevParams p, SkParams sp, PoolView pool) {
 							                                    __builtin_amdgcn_perm(rqv.y, lq.y, 0x05010400u), __builtin_amdgcn_perm(rqv.y, lq.y, 0x07030602u));
 						}
 					}
-					dst[0] = make_uint4((uint32_t)ord, (uint32_t)(ord >> 32) | (n << 8) | ((uni ? 1u : 0u) << 16) | (sk_rec_granules(n, k, uni, EXT) << 17) | hdrExt, q_mh[r], q_w0[r]);
+					dst[0] = sk_make_header(ord, n, uni, sk_rec_granules(n, k, uni, EXT), hdrExt, q_mh[r], q_w0[r]);
 					const uint32_t xb = rbOff + start;
 					for (uint32_t b = 0; b < nbg; b++)
 						dst[1 + b] = make_uint4(sk_bases16(pk, xb + 64 * b), sk_bases16(pk, xb + 64 * b + 16), sk_bases16(pk, xb + 64 * b + 32), sk_bases16(pk, xb + 64 * b + 48));
@@ -1161,7 +1180,7 @@ void sk_extract_lean_kernel(ReadsView rv, DevParams p, SkParams sp, PoolView poo
 					const uint32_t nbg = sk_base_granules(nn, k);
 					uint4 *dst = (uint4 *)pool.base + at[r];
 					const uint64_t ord = ord0 + start;
-					dst[0] = make_uint4((uint32_t)ord, (uint32_t)(ord >> 32) | (nn << 8) | (1u << 16) | ((1 + nbg) << 17), q_mh[r], wbits);
+					dst[0] = sk_make_header(ord, nn, true, 1 + nbg, 0u, q_mh[r], wbits);
 					const uint32_t xb = rbOff + start;
 					for (uint32_t b = 0; b < nbg; b++)
 						dst[1 + b] = make_uint4(sk_bases16(pk, xb + 64 * b), sk_bases16(pk, xb + 64 * b + 16), sk_bases16(pk, xb + 64 * b + 32), sk_bases16(pk, xb + 64 * b + 48));
@@ -1340,12 +1359,163 @@ template <int W> __device__ __forceinline__ Key<W> key_revcomp(const Key<W> &f, 
 	return o;
 }
 
+/* ------------------------------------------------------------------ reading a chunk of records back */
+/* What sk_count_kernel, sk_lookup_kernel, sat_collect_kernel and sk_refine_kernel share.  A wavefront holds one chunk, granule `lane` in
+ * lane `lane` (zeros past the chunk's fill count) and, but for the refine kernel, a copy in its quarter of the staging area in LDS. */
+
+/* Record starts: the 64-bit mask of the chunk's header granules, found by following the granule counts from granule 0.  y: the second
+ * word of the lane's granule; count: the chunk's fill count.
+ *   - the usual chunk holds two-granule records only (a header and up to 64 bases): if every even granule says "2" where a header keeps
+ *     its granule count, every even granule is a header (granule 0 is one, and each one vouches for the next);
+ *   - TIERS (the count pass, which knows whether its records carry extension values): the usual chunk of a build with extension values
+ *     is header, bases, qualities -- three granules a record;
+ *   - TIERS: records of mixed sizes (a weight per k-mer, extension values of long runs).  Every granule that READS like a header -- a
+ *     k-mer count and a granule count that agree -- is a candidate; the candidates are exactly the headers iff following the granule
+ *     counts maps them one-to-one onto themselves without the first (each but granule 0 is pointed at by one, the pointers only go
+ *     forward): eight ballots by distance instead of a scalar walk with a v_readlane per record.  A data granule that passes for a
+ *     header breaks the equality, and the walk decides;
+ *   - the scalar walk.  A granule count of zero would never end: the rest of such a (corrupt) chunk is dropped.
+ * Every tier gives the mask the walk gives.  (One if / else chain on purpose: written with early returns the count pass, which sits at
+ * its register limit, is allocated one or two vector registers differently.) */
+template <bool TIERS = false, bool EXT = false>
+__device__ __forceinline__ unsigned long long sk_record_starts(uint32_t y, uint32_t count, int lane, uint32_t k) {
+	const uint32_t glen = sk_hdr_granules(y);
+	unsigned long long starts = 0;
+	if (__all((lane & 1) != 0 || (uint32_t)lane >= count || glen == 2u)) starts = 0x5555555555555555ull & (count >= 64u ? ~0ull : ((1ull << count) - 1ull));
+	else if (TIERS && EXT && __all(((uint32_t)lane * 43u >> 7) * 3u != (uint32_t)lane || (uint32_t)lane >= count || glen == 3u)) starts = 0x9249249249249249ull & (count >= 64u ? ~0ull : ((1ull << count) - 1ull));
+	else {
+		unsigned long long C = 0; bool ballots = false;
+		if (TIERS) {
+			const uint32_t hn = sk_hdr_n(y);
+			const bool cand = (uint32_t)lane < count && hn >= 1u && hn <= SK_MAX_N && glen == sk_rec_granules(hn, k, sk_hdr_uniform(y), EXT) && sk_hdr_is_ext(y) == EXT;
+			const unsigned long long inRange = count >= 64u ? ~0ull : ((1ull << count) - 1ull);
+			C = __ballot(cand);
+			unsigned long long N = 0;
+#pragma unroll
+			for (uint32_t d = 2; d <= 9; d++) N |= __ballot(cand && glen == d) << d;
+			ballots = (C & 1ull) && !__any(cand && glen > 9u) && (N & inRange) == (C & ~1ull);
+		}
+		if (ballots) starts = C;
+		else for (uint32_t pos = 0; pos < count; ) {
+			starts |= 1ull << pos;
+			const uint32_t step = (uint32_t)__builtin_amdgcn_readlane((int)glen, (int)pos);
+			pos += step ? step : SK_CHUNK_G;
+		}
+	}
+	return starts;
+}
+
+/* The deal.  The chunk's k-mers are dealt out evenly: with T of them, lane l takes slots [l Lk, (l + 1) Lk), Lk = ceil(T / 64), in the
+ * order the records lie in the chunk.  The record a lane starts in is told to it by that record's header lane, which knows the slots
+ * it covers from a prefix sum of the n's and writes its lane number into wrecOf[] (64 bytes of the wavefront's own in LDS) for every
+ * lane whose first slot it covers.  A lane gets: `left`, the k-mers it has to do; rs, the granule of the record its first one lies in;
+ * j, that k-mer's index in the record; and the record's header words.  When a record runs out the lane goes on with the next one
+ * (rs + its granules, j = 0). */
+struct SkDeal { uint32_t Lk, rs, j, left, hx, hy, hw; };
+__device__ __forceinline__ SkDeal sk_deal(unsigned long long starts, const uint4 &cur, int lane, uint8_t *wrecOf) {
+	SkDeal d;
+	const bool isStart = (starts >> lane) & 1ull;
+	const uint32_t myN = isStart ? sk_hdr_n(cur.y) : 0u;
+	const uint32_t incl = sk_wave_scan_u32(myN);      /* (six LDS permutes with their address arithmetic cost the count pass 0.85 ms) */
+	const uint32_t T = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+	const uint32_t myOff = incl - myN;
+	d.Lk = (T + 63u) >> 6;
+	if (myN) {
+		/* floor(x / Lk) as (x + 0.5) * (1 / Lk): x < 2^14 and Lk <= 128 leave the product at least 0.5 / Lk away from an integer,
+		 * a thousand times the rounding error of the reciprocal and the product (two f32 divisions are 24 instructions) */
+		const float inv = __builtin_amdgcn_rcpf((float)d.Lk);
+		const uint32_t l0 = (uint32_t)(((float)(myOff + d.Lk - 1) + 0.5f) * inv), l1 = (uint32_t)(((float)(myOff + myN - 1) + 0.5f) * inv);
+		for (uint32_t l = l0; l <= l1 && l < 64u; l++) wrecOf[l] = (uint8_t)lane;
+	}
+	sk_wave_lds_order();
+	const uint32_t e0 = (uint32_t)lane * d.Lk;
+	d.left = e0 < T ? (T - e0 < d.Lk ? T - e0 : d.Lk) : 0u;
+	d.rs = d.left ? wrecOf[lane] : 0u;
+	d.j = e0 - (uint32_t)__shfl((int)myOff, (int)d.rs, 64);
+	d.hx = (uint32_t)__shfl((int)cur.x, (int)d.rs, 64); d.hy = (uint32_t)__shfl((int)cur.y, (int)d.rs, 64); d.hw = (uint32_t)__shfl((int)cur.w, (int)d.rs, 64);
+	return d;
+}
+
+/* the record whose header (words x, y) lies at granule rs of the staged chunk: its k-mers, packed bases, weights (n of them unless the
+ * record is uniform) and first ordinal */
+struct SkRec { uint32_t n; const uint32_t *bases, *weights; bool uniform; uint64_t ord0; };
+__device__ __forceinline__ SkRec sk_enter_record(const uint4 *wstage, uint32_t rs, uint32_t x, uint32_t y, uint32_t k) {
+	SkRec r;
+	r.n = sk_hdr_n(y);
+	r.bases = (const uint32_t *)(wstage + rs + 1);
+	r.weights = r.bases + 4 * sk_base_granules(r.n, k);
+	r.uniform = sk_hdr_uniform(y);
+	r.ord0 = sk_hdr_ordinal(x, y);
+	return r;
+}
+
+/* k-mer j of a record's packed bases (in LDS), left-justified in W words, 32 W bases long: whatever follows the k-mer is still in it */
+template <int W> __device__ __forceinline__ Key<W> sk_cut_kmer(const uint32_t *bases, uint32_t j) {
+	Key<W> kf;
+	const uint32_t d0 = j >> 4, sft = 2u * (j & 15u);
+#pragma unroll
+	for (int wi = 0; wi < W; wi++) {
+		const uint32_t a = bases[d0 + 2 * wi], b = bases[d0 + 2 * wi + 1], c = bases[d0 + 2 * wi + 2];
+		const uint64_t hi = ((uint64_t)a << 32) | b;
+		kf.w[wi] = sft ? (hi << sft) | ((uint64_t)c >> (32 - sft)) : hi;
+	}
+	return kf;
+}
+/* what lies behind base k goes: the pad bits of the last key word are zero */
+template <int W> __device__ __forceinline__ void key_clip_tail(Key<W> &kf, uint32_t k) {
+	const uint32_t kbits = 2u * k;
+#pragma unroll
+	for (int wi = 0; wi < W; wi++) {
+		const uint32_t lo = 64u * wi;
+		if (kbits <= lo) kf.w[wi] = 0;
+		else if (kbits < lo + 64u) kf.w[wi] &= ~0ull << (lo + 64u - kbits);
+	}
+}
+/* the canonical key of forward word kf -- the smaller of the two strands -- and whether that is the forward one */
+template <int W> __device__ __forceinline__ Key<W> key_canonical(const Key<W> &kf, uint32_t k, bool &fwd) {
+	const Key<W> kr = key_revcomp<W>(kf, k);
+	fwd = key_le<W>(kf, kr);
+	return fwd ? kf : kr;
+}
+
+/* A small set of distinct keys with a value each in LDS (arrays of the caller's: [S][W] key words, [S] values, [S] state words, S =
+ * 2^LOG2S), open addressing in steps of one.  The block clears it, puts its keys in -- a slot is claimed by compare-and-swap on its
+ * state word, the keys are distinct, so a taken slot is somebody else's -- and only after a block barrier looks keys up. */
+template <int W, int LOG2S> struct SkKeySet {
+	static constexpr int S = 1 << LOG2S;
+	uint64_t *tkeys; uint32_t *tval, *tstate;      /* state: 0 empty, 1 filled */
+	__device__ __forceinline__ void clear(int t, int threads) const { for (int i = t; i < S; i += threads) tstate[i] = 0; }
+	__device__ __forceinline__ void put(const uint64_t *key, uint32_t value) const {
+		uint64_t kw[W];
+#pragma unroll
+		for (int q = 0; q < W; q++) kw[q] = key[q];
+		uint32_t sl = (uint32_t)(slot_hash<W>(kw) >> (64 - LOG2S));
+		while (atomicCAS(&tstate[sl], 0u, 1u) != 0u) sl = (sl + 1) & (S - 1);
+#pragma unroll
+		for (int q = 0; q < W; q++) tkeys[(size_t)sl * W + q] = kw[q];
+		tval[sl] = value;
+	}
+	__device__ __forceinline__ uint32_t find(const Key<W> &key, uint32_t miss) const {
+		uint32_t sl = (uint32_t)(slot_hash<W>(key.w) >> (64 - LOG2S));
+		uint32_t value = miss;      /* (no return from inside the loop: it costs sk_lookup_kernel<2> three scalar registers, 101 instead of 98) */
+		for (int probe = 0; probe < S; probe++) {
+			if (tstate[sl] == 0) break;
+			bool eq = true;
+#pragma unroll
+			for (int q = 0; q < W; q++) eq = eq && tkeys[(size_t)sl * W + q] == key.w[q];
+			if (eq) { value = tval[sl]; break; }
+			sl = (sl + 1) & (S - 1);
+		}
+		return value;
+	}
+};
+
 /* ------------------------------------------------------------------ count over super-k-mer lists */
-/* One block per list, lists taken SK_LBATCH at a time.  The list's chunks are staged SK_STAGE_CHUNKS at a time (the next group
- * is held in registers meanwhile), every wavefront finds the record starts of one chunk by following the granule counts in
- * the headers, the records' k-mer counts are scanned, and then every thread expands and inserts k-mers t, t + 256, ... of the
- * group: the record's bases give the forward word, key_revcomp the other strand, the smaller one is the key.  Table, sub-pass
- * splitting and the emission of kept entries are those of count_kernel (COUNT_DIR values). */
+/* One block per list, lists taken SK_LBATCH at a time.  The four wavefronts take the list's chunks on their own (chunk c0 + wave, + 4,
+ * ...): a wavefront stages its chunk in its quarter of the staging area (the next one is on its way to registers meanwhile), finds the
+ * record starts, deals the chunk's k-mers evenly over its lanes (sk_record_starts, sk_deal), and every lane makes its k-mers one after
+ * the other out of a register window of its record's bases: the window gives the forward word, key_revcomp the other strand, the
+ * smaller one is the key.  Table, sub-pass splitting and the emission of kept entries are those of count_kernel (COUNT_DIR values). */
 static const int SK_STAGE_CHUNKS = 4;                          /* = wavefronts of the block */
 static const int SK_STAGE_G = SK_STAGE_CHUNKS * SK_CHUNK_G;    /* 256 granules = one per thread */
 static const uint32_t SK_LBATCH = 24;
@@ -1519,59 +1689,13 @@ void sk_count_kernel(PoolView pool, const uint64_t *list_start, const uint64_t *
 				if (firstPass) preList = ~0ull;
 				for (uint64_t ci = c0 + wv; ci < c1 && !s_overflow[fl] && s_claimed[fl] <= LIMIT; ci += SKC_WAVES) {
 					wstage[lane] = cur;
-					/* record starts: follow the granule counts from granule 0 */
-					const uint32_t glen = (cur.y >> 17) & 0x7fu;
 					uint32_t claimedHere = 0;
-					unsigned long long starts = 0;
-					/* the usual chunk holds two-granule records only (a header and up to 64 bases): if every even granule says "2" where a
-					 * header keeps its granule count, every even granule is a header (granule 0 is one, and each one vouches for the next) */
-					if (__all((lane & 1) != 0 || (uint32_t)lane >= curCount || glen == 2u)) starts = 0x5555555555555555ull & (curCount >= 64u ? ~0ull : ((1ull << curCount) - 1ull));
-					/* (the usual chunk of a build with extension values: header, bases, qualities -- three granules a record) */
-					else if (EXT && __all(((uint32_t)lane * 43u >> 7) * 3u != (uint32_t)lane || (uint32_t)lane >= curCount || glen == 3u)) starts = 0x9249249249249249ull & (curCount >= 64u ? ~0ull : ((1ull << curCount) - 1ull));
-					else {
-						/* Records of mixed sizes (a weight per k-mer, extension values of long runs).  Every granule that READS like a header -- a k-mer
-						 * count and a granule count that agree -- is a candidate; the candidates are exactly the headers iff following the granule
-						 * counts maps them one-to-one onto themselves without the first (each but granule 0 is pointed at by one, the pointers only
-						 * go forward): eight ballots by distance instead of a scalar walk with a v_readlane per record.  A data granule that
-						 * passes for a header breaks the equality, and the walk decides. */
-						const uint32_t hn = (cur.y >> 8) & 0xffu;
-						const bool cand = (uint32_t)lane < curCount && hn >= 1u && hn <= SK_MAX_N && glen == sk_rec_granules(hn, k, ((cur.y >> 16) & 1u) != 0, EXT) && ((cur.y >> 30) & 1u) == (EXT ? 1u : 0u);
-						const unsigned long long C = __ballot(cand), inRange = curCount >= 64u ? ~0ull : ((1ull << curCount) - 1ull);
-						unsigned long long N = 0;
-#pragma unroll
-						for (uint32_t d = 2; d <= 9; d++) N |= __ballot(cand && glen == d) << d;
-						if ((C & 1ull) && !__any(cand && glen > 9u) && (N & inRange) == (C & ~1ull)) starts = C;
-						else for (uint32_t pos = 0; pos < curCount; ) {
-						starts |= 1ull << pos;
-						const uint32_t step = (uint32_t)__builtin_amdgcn_readlane((int)glen, (int)pos);
-						pos += step ? step : SK_CHUNK_G;        /* a zero would never end: a corrupt chunk is dropped */
-					}
-					}
-					/* The chunk's k-mers are dealt out evenly: with T of them, lane l takes slots [l Lk, (l + 1) Lk), Lk = ceil(T / 64),
-					 * in the order the records lie in the chunk.  The record a lane starts in is told to it by that record's header
-					 * lane (which knows the slots it covers from a prefix sum of the n's); the lane cuts its first k-mer out of the
-					 * record's bases and reverse-complements it once, the others follow by rolling one base in, and when a record
-					 * runs out the lane starts the next one the same way.  The table slot of the next k-mer is read while the
-					 * current one is being added. */
-					const bool isStart = (starts >> lane) & 1ull;
-					const uint32_t myN = isStart ? (cur.y >> 8) & 0xffu : 0u;
-					const uint32_t incl = sk_wave_scan_u32(myN);      /* (six LDS permutes with their address arithmetic cost the pass 0.85 ms) */
-					const uint32_t T = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-					const uint32_t myOff = incl - myN;
-					const uint32_t Lk = (T + 63u) >> 6;
-					if (myN) {
-						/* floor(x / Lk) as (x + 0.5) * (1 / Lk): x < 2^14 and Lk <= 128 leave the product at least 0.5 / Lk away from an integer,
-						 * a thousand times the rounding error of the reciprocal and the product (two f32 divisions are 24 instructions) */
-						const float inv = __builtin_amdgcn_rcpf((float)Lk);
-						const uint32_t l0 = (uint32_t)(((float)(myOff + Lk - 1) + 0.5f) * inv), l1 = (uint32_t)(((float)(myOff + myN - 1) + 0.5f) * inv);
-						for (uint32_t l = l0; l <= l1 && l < 64u; l++) wrecOf[l] = (uint8_t)lane;
-					}
-					sk_wave_lds_order();
-					const uint32_t e0 = (uint32_t)lane * Lk;
-					uint32_t left = e0 < T ? (T - e0 < Lk ? T - e0 : Lk) : 0u;      /* k-mers this lane still has to do */
-					uint32_t rs = left ? wrecOf[lane] : 0u;
-					uint32_t j = e0 - (uint32_t)__shfl((int)myOff, (int)rs, 64);
-					uint32_t hx = (uint32_t)__shfl((int)cur.x, (int)rs, 64), hy = (uint32_t)__shfl((int)cur.y, (int)rs, 64), hw = (uint32_t)__shfl((int)cur.w, (int)rs, 64);
+					/* record starts, then the chunk's k-mers dealt evenly over the lanes; the table slot of a lane's next k-mer is read while
+					 * the current one is being added */
+					const unsigned long long starts = sk_record_starts<true, EXT>(cur.y, curCount, lane, k);
+					const SkDeal deal = sk_deal(starts, cur, lane, wrecOf);
+					const uint32_t Lk = deal.Lk;
+					uint32_t left = deal.left, rs = deal.rs, j = deal.j, hx = deal.hx, hy = deal.hy, hw = deal.hw;
 					if (SK_DBG(dbgFlags, 4)) left = 0;
 					/* The chunk is in LDS and its headers have been read: only NOW are the next chunks requested (this list's c + 4 and, once
 					 * per list, this wavefront's first chunk of the next list).  Requested at the top of the iteration -- before the current
@@ -1594,10 +1718,8 @@ void sk_count_kernel(PoolView pool, const uint64_t *list_start, const uint64_t *
 					const uint8_t *xq = nullptr;      /* EXT: the record's neighbour qualities */
 					uint32_t leftCarry = 0;           /* EXT: the base left of the next k-mer to be made, when it is a base of the same record */
 					auto enter_record = [&]() {      /* header in hx, hy, hw */
-						n = (hy >> 8) & 0xffu;
-						ww = (const uint32_t *)(wstage + rs + 1) + 4 * sk_base_granules(n, k);
-						uniformW = ((hy >> 16) & 1u) != 0;
-						ord0 = (uint64_t)hx | ((uint64_t)(hy & 0xffu) << 32);
+						const SkRec rec = sk_enter_record(wstage, rs, hx, hy, k);
+						n = rec.n; ww = rec.weights; uniformW = rec.uniform; ord0 = rec.ord0;
 						if (EXT) xq = (const uint8_t *)(ww + (uniformW ? 0u : 4u * ((n + 3) / 4)));
 					};
 					/* The bases of the k-mers a lane expands lie in REGISTERS: a window of 2 W + 2 dwords of its record's packed bases, the
@@ -1630,7 +1752,6 @@ void sk_count_kernel(PoolView pool, const uint64_t *list_start, const uint64_t *
 							const uint32_t hi = (uint32_t)(((((uint64_t)d0) << 32 | d1) << r) >> 32), lo = (uint32_t)(((((uint64_t)d1) << 32 | d2) << r) >> 32);
 							kf.w[wi] = ((uint64_t)hi << 32) | lo;
 						}
-						const uint32_t kbits = 2u * k;
 						uint32_t rcIn = 0; uint64_t kfFirst = 0;
 						if constexpr (EXT) {
 							/* the base behind the k-mer: base k of the 32 W bases just cut out of the window (k = 32 W: the next dword of the record) */
@@ -1641,15 +1762,8 @@ void sk_count_kernel(PoolView pool, const uint64_t *list_start, const uint64_t *
 								rcIn = (uint32_t)(wsel >> (62u - 2u * (k & 31u))) & 3u; }
 							else { const uint32_t b = j + k; rcIn = (((const uint32_t *)(wstage + rs + 1))[b >> 4] >> (30 - 2 * (b & 15u))) & 3u; }
 						}
-#pragma unroll
-						for (int wi = 0; wi < W; wi++) {
-							const uint32_t lo = 64u * wi;
-							if (kbits <= lo) kf.w[wi] = 0;
-							else if (kbits < lo + 64u) kf.w[wi] &= ~0ull << (lo + 64u - kbits);
-						}
-						const Key<W> kr = key_revcomp<W>(kf, k);
-						st.fwd = key_le<W>(kf, kr);
-						st.key = st.fwd ? kf : kr;
+						key_clip_tail<W>(kf, k);
+						st.key = key_canonical<W>(kf, k, st.fwd);
 						const uint64_t h = slot_hash<W>(st.key.w);
 						st.slot = (uint32_t)(h >> (64 - LOG2S));
 						/* a key that does not find its home slot free (or its own) goes on in steps of an odd number taken from other bits of its
@@ -1664,7 +1778,7 @@ void sk_count_kernel(PoolView pool, const uint64_t *list_start, const uint64_t *
 							 * what the header says lies outside the run for its first / last k-mer; in between the left one is the first base of the
 							 * k-mer made before this one (leftCarry) and the right one the base behind the k-mer in the window it was cut from; seen
 							 * from the other strand they swap and are complemented */
-							uint32_t lc = j > 0 ? leftCarry : (hy >> 24) & 7u, rc = (hy >> 27) & 7u;
+							uint32_t lc = j > 0 ? leftCarry : sk_hdr_ext_left(hy), rc = sk_hdr_ext_right(hy);
 							if (j + 1 < n) rc = rcIn;
 							leftCarry = (uint32_t)(kfFirst >> 62);
 							const uint32_t q2 = ((const uint16_t *)xq)[j];
@@ -1699,7 +1813,7 @@ void sk_count_kernel(PoolView pool, const uint64_t *list_start, const uint64_t *
 									/* the next record is fetched when the lane gets there (two LDS reads, waited for on the spot).  Its header and first window
 									 * used to be asked for a record ahead and held in registers: eight of the 128 -- without them nothing spills and the pass
 									 * is 0.45 ms faster, the exposed LDS latency notwithstanding */
-									rs = rs + ((hy >> 17) & 0x7fu);
+									rs = rs + sk_hdr_granules(hy);
 									{ const uint32_t g0 = rs < SK_CHUNK_G - 1 ? rs : SK_CHUNK_G - 1; const uint4 hh = wstage[g0]; hx = hh.x; hy = hh.y; hw = hh.w; }
 									j = 0;
 									seed_window();
@@ -2150,7 +2264,8 @@ void sk_lookup_kernel(PoolView pool, const uint64_t *list_start, const uint64_t 
 	extern __shared__ __attribute__((aligned(16))) uint8_t csm[];
 	uint64_t *tkeys = (uint64_t *)csm;                                 /* [S][W] */
 	uint32_t *tval = (uint32_t *)(tkeys + (size_t)S * W);
-	uint32_t *tstate = tval + S;                                       /* 0 empty, 1 filled (entries are put in before anybody looks) */
+	uint32_t *tstate = tval + S;
+	const SkKeySet<W, SKL_LOG2S> set = { tkeys, tval, tstate };        /* the list's entries: key -> count */
 	uint4 *stage = (uint4 *)(tstate + S);
 	uint8_t *recOf = (uint8_t *)(stage + SK_STAGE_G);
 	__shared__ uint32_t s_list;
@@ -2185,19 +2300,10 @@ void sk_lookup_kernel(PoolView pool, const uint64_t *list_start, const uint64_t 
 			 * exactly one of them) */
 			for (uint64_t eb = e0; eb < e1; eb += SKL_FILL) {
 				lds_barrier();
-				for (int i = t; i < S; i += COUNT_THREADS) tstate[i] = 0;
+				set.clear(t, COUNT_THREADS);
 				lds_barrier();
 				const uint64_t ee = eb + SKL_FILL < e1 ? eb + SKL_FILL : e1;
-				for (uint64_t e = eb + (uint64_t)t; e < ee; e += COUNT_THREADS) {
-					uint64_t kw[W];
-#pragma unroll
-					for (int q = 0; q < W; q++) kw[q] = ix_keys[e * W + q];
-					uint32_t sl = (uint32_t)(slot_hash<W>(kw) >> (64 - SKL_LOG2S));
-					while (atomicCAS(&tstate[sl], 0u, 1u) != 0u) sl = (sl + 1) & (S - 1);      /* keys are distinct: a taken slot is somebody else's */
-#pragma unroll
-					for (int q = 0; q < W; q++) tkeys[(size_t)sl * W + q] = kw[q];
-					tval[sl] = ix_counts[e];
-				}
+				for (uint64_t e = eb + (uint64_t)t; e < ee; e += COUNT_THREADS) set.put(ix_keys + e * W, ix_counts[e]);
 				lds_barrier();
 				uint4 *wstage = stage + wv * SK_CHUNK_G;
 				uint8_t *wrecOf = recOf + wv * 64;
@@ -2206,73 +2312,25 @@ void sk_lookup_kernel(PoolView pool, const uint64_t *list_start, const uint64_t 
 					const uint32_t chunk = (uint32_t)d, curCount = (uint32_t)(d >> 32);
 					uint4 cur = make_uint4(0, 0, 0, 0);
 					if ((uint32_t)lane < curCount) cur = poolg[(size_t)chunk * SK_CHUNK_G + lane];
-					__builtin_amdgcn_wave_barrier();      /* the lanes are done with the chunk before */
+					sk_wave_lds_order();      /* the lanes are done with the chunk before */
 					wstage[lane] = cur;
-					const uint32_t glen = (cur.y >> 17) & 0x7fu;
-					unsigned long long starts = 0;
-					if (__all((lane & 1) != 0 || (uint32_t)lane >= curCount || glen == 2u)) starts = 0x5555555555555555ull & (curCount >= 64u ? ~0ull : ((1ull << curCount) - 1ull));
-					else for (uint32_t pos = 0; pos < curCount; ) {
-						starts |= 1ull << pos;
-						const uint32_t step = (uint32_t)__builtin_amdgcn_readlane((int)glen, (int)pos);
-						pos += step ? step : SK_CHUNK_G;
-					}
-					/* the chunk's k-mers dealt evenly over the lanes, as in sk_count_kernel */
-					const bool isStart = (starts >> lane) & 1ull;
-					const uint32_t myN = isStart ? (cur.y >> 8) & 0xffu : 0u;
-					const uint32_t incl = sk_wave_scan_u32(myN);
-					const uint32_t T = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-					const uint32_t myOff = incl - myN;
-					const uint32_t Lk = (T + 63u) >> 6;
-					if (myN) {
-						const float inv = __builtin_amdgcn_rcpf((float)Lk);      /* as in sk_count_kernel */
-						const uint32_t l0 = (uint32_t)(((float)(myOff + Lk - 1) + 0.5f) * inv), l1 = (uint32_t)(((float)(myOff + myN - 1) + 0.5f) * inv);
-						for (uint32_t l = l0; l <= l1 && l < 64u; l++) wrecOf[l] = (uint8_t)lane;
-					}
-					__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-					const uint32_t k0 = (uint32_t)lane * Lk;
-					uint32_t left = k0 < T ? (T - k0 < Lk ? T - k0 : Lk) : 0u;
-					uint32_t rs = left ? wrecOf[lane] : 0u;
-					uint32_t j = k0 - (uint32_t)__shfl((int)myOff, (int)rs, 64);
-					uint32_t hx = (uint32_t)__shfl((int)cur.x, (int)rs, 64), hy = (uint32_t)__shfl((int)cur.y, (int)rs, 64);
-					uint32_t n = 0; const uint32_t *bw = nullptr; uint64_t ord0 = 0;
-					for (uint32_t it = 0; it < Lk; it++) {
-						if (left) {
-							if (it == 0 || j >= n) {
-								if (it != 0) { rs += (hy >> 17) & 0x7fu; const uint4 hd = wstage[rs]; hx = hd.x; hy = hd.y; j = 0; }
-								n = (hy >> 8) & 0xffu;
-								bw = (const uint32_t *)(wstage + rs + 1);
-								ord0 = (uint64_t)hx | ((uint64_t)(hy & 0xffu) << 32);
+					/* record starts, then the chunk's k-mers dealt evenly over the lanes */
+					SkDeal at = sk_deal(sk_record_starts(cur.y, curCount, lane, k), cur, lane, wrecOf);
+					SkRec rec = sk_enter_record(wstage, at.rs, at.hx, at.hy, k);
+					for (uint32_t it = 0; it < at.Lk; it++) {
+						if (at.left) {
+							if (at.j >= rec.n) {      /* the next record */
+								at.rs += sk_hdr_granules(at.hy); at.j = 0;
+								const uint4 hd = wstage[at.rs]; at.hx = hd.x; at.hy = hd.y;
+								rec = sk_enter_record(wstage, at.rs, at.hx, at.hy, k);
 							}
-							Key<W> kf;
-							const uint32_t d0 = j >> 4, sft = 2u * (j & 15u);
-#pragma unroll
-							for (int wi = 0; wi < W; wi++) {
-								const uint32_t a = bw[d0 + 2 * wi], b = bw[d0 + 2 * wi + 1], c = bw[d0 + 2 * wi + 2];
-								const uint64_t hi = ((uint64_t)a << 32) | b;
-								kf.w[wi] = sft ? (hi << sft) | ((uint64_t)c >> (32 - sft)) : hi;
-							}
-							const uint32_t kbits = 2u * k;
-#pragma unroll
-							for (int wi = 0; wi < W; wi++) {
-								const uint32_t lo = 64u * wi;
-								if (kbits <= lo) kf.w[wi] = 0;
-								else if (kbits < lo + 64u) kf.w[wi] &= ~0ull << (lo + 64u - kbits);
-							}
-							const Key<W> kr = key_revcomp<W>(kf, k);
-							const Key<W> key = key_le<W>(kf, kr) ? kf : kr;
-							uint32_t sl = (uint32_t)(slot_hash<W>(key.w) >> (64 - SKL_LOG2S));
-							uint32_t found = 0;
-							for (int probe = 0; probe < S; probe++) {
-								if (tstate[sl] == 0) break;
-								bool eq = true;
-#pragma unroll
-								for (int q = 0; q < W; q++) eq = eq && tkeys[(size_t)sl * W + q] == key.w[q];
-								if (eq) { found = tval[sl]; break; }
-								sl = (sl + 1) & (S - 1);
-							}
-							const uint64_t at = ord0 + j;
-							if (found && at < out_n) out[at] = found;
-							j++; left--;
+							Key<W> kf = sk_cut_kmer<W>(rec.bases, at.j);
+							key_clip_tail<W>(kf, k);
+							bool fwd;
+							const uint32_t found = set.find(key_canonical<W>(kf, k, fwd), 0u);
+							const uint64_t ord = rec.ord0 + at.j;
+							if (found && ord < out_n) out[ord] = found;
+							at.j++; at.left--;
 						}
 					}
 				}
@@ -2311,9 +2369,10 @@ __global__ __launch_bounds__(256)
 void sat_collect_kernel(PoolView pool, const uint64_t *list_chunks, uint32_t k, const uint64_t *map_keys, const uint64_t *sat_entry,
                         const uint64_t *item_c0, const uint64_t *item_c1, const uint64_t *item_e0, const uint64_t *item_e1, uint64_t n_items,
                         unsigned long long *cursor, uint64_t cap, unsigned long long *out_keys, uint32_t *out_vals, unsigned int *work_counter) {
-	constexpr int S = 256;
+	constexpr int LOG2S = 8, S = 1 << LOG2S;
 	__shared__ uint64_t tkeys[S * W];
 	__shared__ uint32_t tval[S], tstate[S];
+	const SkKeySet<W, LOG2S> set = { tkeys, tval, tstate };      /* this fill's saturated keys: key -> index into sat_entry */
 	__shared__ __attribute__((aligned(16))) uint4 stage[4 * SK_CHUNK_G];
 	__shared__ uint8_t recOf[4 * 64];
 	__shared__ uint32_t s_item;
@@ -2328,19 +2387,10 @@ void sat_collect_kernel(PoolView pool, const uint64_t *list_chunks, uint32_t k, 
 		const uint64_t c0 = item_c0[it], c1 = item_c1[it], e0 = item_e0[it], e1 = item_e1[it];
 		for (uint64_t eb = e0; eb < e1; eb += SAT_FILL) {
 			__syncthreads();
-			for (int i = t; i < S; i += 256) tstate[i] = 0;
+			set.clear(t, 256);
 			__syncthreads();
 			const uint64_t ee = eb + SAT_FILL < e1 ? eb + SAT_FILL : e1;
-			for (uint64_t e = eb + (uint64_t)t; e < ee; e += 256) {
-				uint64_t kw[W];
-#pragma unroll
-				for (int q = 0; q < W; q++) kw[q] = map_keys[sat_entry[e] * W + q];
-				uint32_t sl = (uint32_t)(slot_hash<W>(kw) >> 56);
-				while (atomicCAS(&tstate[sl], 0u, 1u) != 0u) sl = (sl + 1) & (S - 1);
-#pragma unroll
-				for (int q = 0; q < W; q++) tkeys[(size_t)sl * W + q] = kw[q];
-				tval[sl] = (uint32_t)e;
-			}
+			for (uint64_t e = eb + (uint64_t)t; e < ee; e += 256) set.put(map_keys + sat_entry[e] * W, (uint32_t)e);
 			__syncthreads();
 			uint4 *wstage = stage + wv * SK_CHUNK_G;
 			uint8_t *wrecOf = recOf + wv * 64;
@@ -2351,74 +2401,23 @@ void sat_collect_kernel(PoolView pool, const uint64_t *list_chunks, uint32_t k, 
 				if ((uint32_t)lane < curCount) cur = poolg[(size_t)chunk * SK_CHUNK_G + lane];
 				sk_wave_lds_order();      /* the lanes are done with the chunk before */
 				wstage[lane] = cur;
-				const uint32_t glen = (cur.y >> 17) & 0x7fu;
-				unsigned long long starts = 0;
-				if (__all((lane & 1) != 0 || (uint32_t)lane >= curCount || glen == 2u)) starts = 0x5555555555555555ull & (curCount >= 64u ? ~0ull : ((1ull << curCount) - 1ull));
-				else for (uint32_t pos = 0; pos < curCount; ) {
-					starts |= 1ull << pos;
-					const uint32_t step = (uint32_t)__builtin_amdgcn_readlane((int)glen, (int)pos);
-					pos += step ? step : SK_CHUNK_G;
-				}
-				/* the chunk's k-mers dealt evenly over the lanes, as in sk_lookup_kernel */
-				const bool isStart = (starts >> lane) & 1ull;
-				const uint32_t myN = isStart ? (cur.y >> 8) & 0xffu : 0u;
-				const uint32_t incl = sk_wave_scan_u32(myN);
-				const uint32_t T = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-				const uint32_t myOff = incl - myN;
-				const uint32_t Lk = (T + 63u) >> 6;
-				if (myN) {
-					const float inv = __builtin_amdgcn_rcpf((float)Lk);      /* as in sk_count_kernel */
-					const uint32_t l0 = (uint32_t)(((float)(myOff + Lk - 1) + 0.5f) * inv), l1 = (uint32_t)(((float)(myOff + myN - 1) + 0.5f) * inv);
-					for (uint32_t l = l0; l <= l1 && l < 64u; l++) wrecOf[l] = (uint8_t)lane;
-				}
-				sk_wave_lds_order();
-				const uint32_t k0 = (uint32_t)lane * Lk;
-				uint32_t left = k0 < T ? (T - k0 < Lk ? T - k0 : Lk) : 0u;
-				uint32_t rs = left ? wrecOf[lane] : 0u;
-				uint32_t j = k0 - (uint32_t)__shfl((int)myOff, (int)rs, 64);
-				uint32_t hx = (uint32_t)__shfl((int)cur.x, (int)rs, 64), hy = (uint32_t)__shfl((int)cur.y, (int)rs, 64), hw = (uint32_t)__shfl((int)cur.w, (int)rs, 64);
-				uint32_t n = 0; const uint32_t *bw = nullptr, *ww = nullptr; uint64_t ord0 = 0; bool uniformW = true;
-				for (uint32_t itr = 0; itr < Lk; itr++) {
+				/* record starts, then the chunk's k-mers dealt evenly over the lanes */
+				SkDeal at = sk_deal(sk_record_starts(cur.y, curCount, lane, k), cur, lane, wrecOf);
+				SkRec rec = sk_enter_record(wstage, at.rs, at.hx, at.hy, k);
+				for (uint32_t itr = 0; itr < at.Lk; itr++) {
 					uint32_t found = 0xffffffffu, wbits = 0; bool fwd = true; uint64_t ord = 0;
-					if (left) {
-						if (itr == 0 || j >= n) {
-							if (itr != 0) { rs += (hy >> 17) & 0x7fu; const uint4 hd = wstage[rs]; hx = hd.x; hy = hd.y; hw = hd.w; j = 0; }
-							n = (hy >> 8) & 0xffu;
-							bw = (const uint32_t *)(wstage + rs + 1);
-							ww = bw + 4 * sk_base_granules(n, k);
-							uniformW = ((hy >> 16) & 1u) != 0;
-							ord0 = (uint64_t)hx | ((uint64_t)(hy & 0xffu) << 32);
+					if (at.left) {
+						if (at.j >= rec.n) {      /* the next record */
+							at.rs += sk_hdr_granules(at.hy); at.j = 0;
+							const uint4 hd = wstage[at.rs]; at.hx = hd.x; at.hy = hd.y; at.hw = hd.w;
+							rec = sk_enter_record(wstage, at.rs, at.hx, at.hy, k);
 						}
-						Key<W> kf;
-						const uint32_t d0 = j >> 4, sft = 2u * (j & 15u);
-#pragma unroll
-						for (int wi = 0; wi < W; wi++) {
-							const uint32_t a = bw[d0 + 2 * wi], b = bw[d0 + 2 * wi + 1], c = bw[d0 + 2 * wi + 2];
-							const uint64_t hi = ((uint64_t)a << 32) | b;
-							kf.w[wi] = sft ? (hi << sft) | ((uint64_t)c >> (32 - sft)) : hi;
-						}
-						const uint32_t kbits = 2u * k;
-#pragma unroll
-						for (int wi = 0; wi < W; wi++) {
-							const uint32_t lo = 64u * wi;
-							if (kbits <= lo) kf.w[wi] = 0;
-							else if (kbits < lo + 64u) kf.w[wi] &= ~0ull << (lo + 64u - kbits);
-						}
-						const Key<W> kr = key_revcomp<W>(kf, k);
-						fwd = key_le<W>(kf, kr);
-						const Key<W> key = fwd ? kf : kr;
-						uint32_t sl = (uint32_t)(slot_hash<W>(key.w) >> 56);
-						for (int probe = 0; probe < S; probe++) {
-							if (tstate[sl] == 0) break;
-							bool eq = true;
-#pragma unroll
-							for (int q = 0; q < W; q++) eq = eq && tkeys[(size_t)sl * W + q] == key.w[q];
-							if (eq) { found = tval[sl]; break; }
-							sl = (sl + 1) & (S - 1);
-						}
-						wbits = uniformW ? hw : ww[j];
-						ord = ord0 + j;
-						j++; left--;
+						Key<W> kf = sk_cut_kmer<W>(rec.bases, at.j);
+						key_clip_tail<W>(kf, k);
+						found = set.find(key_canonical<W>(kf, k, fwd), 0xffffffffu);
+						wbits = rec.uniform ? at.hw : rec.weights[at.j];
+						ord = rec.ord0 + at.j;
+						at.j++; at.left--;
 					}
 					/* the lanes that hit a saturated key take consecutive places: one device atomic per wavefront and step */
 					const unsigned long long hit = __ballot(found != 0xffffffffu);
@@ -2427,8 +2426,8 @@ void sat_collect_kernel(PoolView pool, const uint64_t *list_chunks, uint32_t k, 
 						if (lane == 0) base = atomicAdd(cursor, (unsigned long long)__builtin_popcountll(hit));
 						base = ((unsigned long long)(uint32_t)__shfl((int)(base >> 32), 0, 64) << 32) | (uint32_t)__shfl((int)(uint32_t)base, 0, 64);
 						if (found != 0xffffffffu) {
-							const unsigned long long at = base + (unsigned long long)__builtin_popcountll(hit & ((1ull << lane) - 1));
-							if (at < cap) { out_keys[at] = ((unsigned long long)found << 41) | ((unsigned long long)ord << 1) | (fwd ? 1ull : 0ull); out_vals[at] = wbits; }
+							const unsigned long long place = base + (unsigned long long)__builtin_popcountll(hit & ((1ull << lane) - 1));
+							if (place < cap) { out_keys[place] = ((unsigned long long)found << 41) | ((unsigned long long)ord << 1) | (fwd ? 1ull : 0ull); out_vals[place] = wbits; }
 						}
 					}
 				}
@@ -2567,8 +2566,8 @@ __global__ void sk_uniform_check_kernel(const uint4 *data, const uint64_t *start
 		const uint32_t n = cnt[c];
 		for (uint32_t pos = 0; pos < n; ) {
 			const uint4 hd = g[pos];
-			const uint32_t glen = (hd.y >> 17) & 0x7fu;
-			if (!((hd.y >> 16) & 1u)) { uni[1] = 1; break; }
+			const uint32_t glen = sk_hdr_granules(hd.y);
+			if (!sk_hdr_uniform(hd.y)) { uni[1] = 1; break; }
 			/* (a plain look first: after the first record of a launch every thread finds the weight there -- a compare-and-swap per record
 			 * put 2 x 10^8 atomics on ONE word, 1.5 s for an eighth of a C2 batch) */
 			uint32_t was = __hip_atomic_load(&uni[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -2667,10 +2666,8 @@ void sk_refine_kernel(PoolView pool, uint32_t n_before, uint32_t fine_bits, unsi
 		if (cnt > SK_CHUNK_G) cnt = SK_CHUNK_G;
 		uint4 cur = make_uint4(0, 0, 0, 0);
 		if ((uint32_t)lane < cnt) cur = poolg[c * SK_CHUNK_G + lane];
-		const uint32_t glen = (cur.y >> 17) & 0x7fu;
-		unsigned long long starts = 0;
-		if (__all((lane & 1) != 0 || (uint32_t)lane >= cnt || glen == 2u)) starts = 0x5555555555555555ull & (cnt >= 64u ? ~0ull : ((1ull << cnt) - 1ull));
-		else for (uint32_t pos = 0; pos < cnt; ) { starts |= 1ull << pos; const uint32_t step = (uint32_t)__builtin_amdgcn_readlane((int)glen, (int)pos); pos += step ? step : SK_CHUNK_G; }
+		const uint32_t glen = sk_hdr_granules(cur.y);
+		const unsigned long long starts = sk_record_starts(cur.y, cnt, lane, 0u);      /* (k: only the count pass's tiers look at it) */
 		const bool isRec = ((starts >> lane) & 1ull) && glen && (uint32_t)lane + glen <= cnt;
 		const uint32_t fine = isRec ? sk_list_of(cur.z, fine_bits) : 0u;      /* cur.z: the record's minimizer hash */
 		/* groups: lanes with the same fine list; a lane learns its offset inside the group's piece, the group's total and its first lane */

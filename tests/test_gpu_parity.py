@@ -1283,6 +1283,38 @@ def test_streaming_lookups_equal_table_probes(k, mode, ext):
     assert a.stats() == b.stats()          # the lookup pass leaves the build's counters alone
 
 
+@pytest.mark.parametrize("k,ext", [(21, False), (21, True), (51, False), (51, True)])
+def test_streaming_lookups_on_every_record_shape(k, ext):
+    """the streaming lookups against the per-k-mer probes over one batch of flat-quality reads, noisy reads and homopolymer /
+    dinucleotide-repeat reads (records of SK_MAX_N k-mers, many granules long, all in one hot list); one- and two-word keys, plain
+    and extension values.  The build's lists hold uniform records and records with a weight per k-mer side by side (the batch is
+    mixed, so the general extraction and count pass run); the lookup pass cuts the same reads without qualities."""
+    n, L = 1000, 150
+    flat = synth_reads(n, read_len=L, genome_len=20000, seed=500 + k, quality="flat")
+    noisy = synth_reads(n, read_len=L, genome_len=20000, seed=501 + k, quality="noisy", n_rate=0.002)
+    rep = synth_reads(n, read_len=L, genome_len=20000, seed=502 + k, quality="noisy")
+    rbases, rquals = rep.bases.reshape(n, L), rep.quals.reshape(n, L)
+    rbases[0::2] = ord("A")
+    rbases[1::2, 0::2] = ord("A")
+    rbases[1::2, 1::2] = ord("C")
+    rquals[0::2] = ord("I")
+    rb = type(rep).from_arrays(np.concatenate([flat.bases, noisy.bases, rep.bases]), np.concatenate([flat.quals, noisy.quals, rep.quals]),
+                               np.arange(3 * n + 1, dtype=np.uint64) * np.uint64(L))
+    cfg = default_config(k, estimated_raw_kmers=3 * n * L, **(dict(value_kind=KMR_VALUE_EXT) if ext else {}))
+    a, b = product(cfg, 3, stream_lookups=1), product(cfg, 3, stream_lookups=0)
+    for p in (a, b):
+        add(p, rb)
+        p.finalize(2)
+    before = a.stats()
+    for batch in (rb, rb.slice(700, 2600)):
+        for scoring in ("MEDIAN", "SUM"):
+            ra = a.scoreAndTrimReads(batch.bases, batch.offsets, 2, scoring)
+            rb_ = b.scoreAndTrimReads(batch.bases, batch.offsets, 2, scoring)
+            for x, y in zip(ra, rb_):
+                assert np.array_equal(x, y)
+    assert a.stats() == b.stats() == before
+
+
 @pytest.mark.parametrize("mode", MODES)
 def test_low_complexity_reads(mode):
     """homopolymers and dinucleotide repeats: a handful of k-mers seen 10^5-10^6 times (counts saturate at 65 535), one list / one
