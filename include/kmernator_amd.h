@@ -630,7 +630,8 @@ int kmr_artifact_filter_apply(kmr_handle *h, const kmr_artifact_filter *f, const
                               uint32_t *remnant_off, uint32_t *remnant_len, kmr_reads **out);
 
 /* ---- selectReads / writePicks: pick the passing reads and write FilterReads' output on the device ----------
- * selectReads (apps/FilterReads.h:159-279) with --max-kmer-output-depth and --partition-by-depth off:
+ * selectReads (apps/FilterReads.h:159-279) with --max-kmer-output-depth off; its plain branch first (one threshold, one
+ * output), --partition-by-depth, --remainder-trim and the per-input-file outputs behind it (kmr_partition_*):
  * ReadSelector::pickAllPassingReads / pickAllPassingPairs (src/ReadSelector.h:547-596) and writePicks (:1242-1262).
  * Per read i of a device-resident batch -- the reads as the artifact filter left them (kmr_artifact_filter_apply's *out)
  * or an unfiltered batch -- and its results of the earlier stages:
@@ -654,8 +655,8 @@ int kmr_artifact_filter_apply(kmr_handle *h, const kmr_artifact_filter *f, const
  *               MedianScore / MinScore / MaxScore / AvgScore (getKmerScoringTypeLabel, :248-257, in kmr_scoring's order).
  *               A discarded read was never scored (:1195-1197) and has no label
  * Not covered: stored comments are not printed and a Casava "name 1:Y" is not rewritten to "name/1";
- * --max-kmer-output-depth, --partition-by-depth and its remainder trim, per-input-file outputs, the unmasked formats and
- * bimodal trimming.  Markup characters other than N, X and '.' are outside the parity claim: the reference applies a read's
+ * --max-kmer-output-depth (RANDOM draws from the reference's IntRand, OPTIMAL is a serial greedy heap), the unmasked formats
+ * and bimodal trimming.  Markup characters other than N, X and '.' are outside the parity claim: the reference applies a read's
  * markup positions to the already trimmed string (src/Sequence.cpp:322-325, src/TwoBitSequence.cpp:317-327), so such a
  * character lands on the wrong base when the trim offset is not 0, while the device prints the batch's own characters where
  * they are (N and X never lie inside a k-mer trim: it ends before the first of them).
@@ -701,6 +702,73 @@ int kmr_picks_copy(const kmr_picks *p, char *dst, uint64_t capacity, uint8_t *pi
 /* the text where it lies (for a compressor or a device-aware MPI-IO); valid until kmr_picks_free */
 int kmr_picks_device_ptr(const kmr_picks *p, void **dev_text);
 void kmr_picks_free(kmr_picks *p);
+
+/* ---- selectReads, the partitioned branch (apps/FilterReads.h:209-278): --partition-by-depth, --remainder-trim and one
+ * output per input file.  Everything above holds per read -- passing, pairs, record, name, label are those of
+ * scoreAndTrimReads(min depth) and do not change between rounds; what is new is that the selection runs in rounds:
+ *   rounds      maxDepth = partition_by_depth if it is > 0, else minDepth (= minimum_score, an unsigned int there, :159);
+ *               for (unsigned depth = maxDepth; depth >= minDepth; depth /= 2) selects at tmpMinDepth = max(minDepth, depth)
+ *               (:221-223), a float compared with the read's float score, with the current min_read_length and both_pass.
+ *               The sequence is not "every power of two": 16 over 2 gives 16 8 4 2, 20 over 3 gives 20 10 5 and ends without
+ *               reaching minDepth, partition_by_depth < minDepth runs no round and picks nothing
+ *   available   a picked read is no longer available (pickIfNew, src/ReadSelector.h:513-542; isPassingRead :550-557), so a
+ *               read lands in the FIRST round whose decision picks it; every read of a passing pair is picked in that round,
+ *               also a mate that failed or was discarded
+ *   remainder   if the output is partitioned, the loop reached depth == minDepth, remainder_trim > 0 and
+ *               (both_pass is set || (int) min_read_length != remainder_trim) (:256-262), one more round runs at minDepth with
+ *               --min-passing-in-pair 1 and min_read_length = remainder_trim: the mates and shorter trims the strict rounds left
+ *   order       optimizePickOrder sorts the picks of the current round only (:1212-1221): the output is round-major, ascending
+ *               read index inside a round; with --separate-outputs 0 that concatenation is the one output file
+ *   files       with --separate-outputs 1 every name gets "-MinDepth<minDepth>" (:173), a partitioned round
+ *               "-PartitionDepth<tmpMinDepth>" (:232; a float through lexical_cast: 16, not 16.0), the remainder round
+ *               "-Remainder" (:230), and writePick adds "-" + getReadFileNamePrefix(read) (src/ReadSelector.h:1252-1262), so the
+ *               reads of a round split by input file.  input_starts = n_inputs + 1 ascending read indices, the first 0, the
+ *               last n_reads: input j holds the reads [input_starts[j], input_starts[j + 1]) (it may be empty).  NULL / 0 =
+ *               one input
+ *   segment     = round * n_inputs + input.  The text of kmr_picks_copy / kmr_picks_device_ptr is the segments in that order,
+ *               each a contiguous slice; the segment table gives per segment {first pick, picks, first byte, bytes}, and
+ *               read_segment the segment of every read of the batch (-1 = not picked)
+ * partition_by_depth 0 is one round at minimum_score as kmr_select_reads runs it (any minimum_score, no remainder): with one
+ * input the same bytes and flags.  With partition_by_depth set, minimum_score must be a whole number in [0, 2^32)
+ * (KMR_ERR_INVALID_ARG otherwise), and partition_by_depth is taken as the unsigned depth of the loop (the reference reads an int;
+ * values above 2^31 - 1 cannot be given to it).
+ * Bounds: at most 33 rounds (32 halvings of a 32-bit depth and the remainder; minimum_score 0 under a depth of 2^31 or more
+ * would need 34: KMR_ERR_UNSUPPORTED); rounds x inputs <= 256 segments (KMR_ERR_UNSUPPORTED beyond): the counting pass keeps 12
+ * bytes of LDS per segment and wavefront, 3 KiB at 256, which lets 32 wavefronts share a CU's 160 KiB.
+ * Not covered: --kmer-size 0 (the tmpMinDepth = 0 special case, :224-227), --max-kmer-output-depth, bimodal trimming.
+ * KMR_ERR_INVALID_ARG: a wrong struct_size; input_starts that does not start at 0, descends or does not end at n_reads. */
+typedef struct kmr_partition_config {
+	uint32_t struct_size;            /* = sizeof(kmr_partition_config), ABI guard                                           */
+	kmr_select_config select;        /* minimum_score = --min-depth, min_read_length, both_pass, format, ...                */
+	uint32_t partition_by_depth;     /* --partition-by-depth; 0 = off: one round at minimum_score, no remainder             */
+	float    remainder_trim;         /* --remainder-trim; <= 0 = off (-1, the reference's default)                          */
+} kmr_partition_config;
+int kmr_partition_config_init(kmr_partition_config *cfg);      /* the reference's defaults: both off */
+/* The table of rounds of a configuration, without a device: n_rounds and, per round in the order they run (arrays of 33, any
+ * may be NULL), the depth (tmpMinDepth), min_read_length, both_pass and whether it is the remainder round. */
+int kmr_partition_rounds(const kmr_partition_config *cfg, uint32_t *n_rounds, float *round_depth, float *round_min_read_length,
+                         uint32_t *round_both_pass, uint8_t *round_is_remainder);
+/* as kmr_select_reads / kmr_select_reads_dev / kmr_filter_read_batch / kmr_filter_read_batch_dev */
+int kmr_partition_reads(kmr_handle *h, const kmr_reads *reads, const char *text, uint64_t text_len, const int64_t *mate,
+                        const uint8_t *af_action, const uint32_t *af_min_pass, const uint32_t *af_max_pass,
+                        const uint32_t *trim_offset, const uint32_t *trim_length, const float *score, const uint8_t *was_trimmed,
+                        const uint64_t *input_starts, uint32_t n_inputs, const kmr_partition_config *cfg, kmr_picks **out);
+int kmr_partition_reads_dev(kmr_handle *h, const kmr_reads *reads, const void *dev_text, uint64_t text_len, const int64_t *mate,
+                            const uint8_t *af_action, const uint32_t *af_min_pass, const uint32_t *af_max_pass,
+                            const uint32_t *trim_offset, const uint32_t *trim_length, const float *score, const uint8_t *was_trimmed,
+                            const uint64_t *input_starts, uint32_t n_inputs, const kmr_partition_config *cfg, kmr_picks **out);
+int kmr_partition_read_batch(kmr_handle *h, const kmr_reads *reads, const char *text, uint64_t text_len, const int64_t *mate,
+                             const uint8_t *af_action, const uint32_t *af_min_pass, const uint32_t *af_max_pass,
+                             const uint64_t *input_starts, uint32_t n_inputs, const kmr_partition_config *cfg, kmr_picks **out);
+int kmr_partition_read_batch_dev(kmr_handle *h, const kmr_reads *reads, const void *dev_text, uint64_t text_len, const int64_t *mate,
+                                 const uint8_t *af_action, const uint32_t *af_min_pass, const uint32_t *af_max_pass,
+                                 const uint64_t *input_starts, uint32_t n_inputs, const kmr_partition_config *cfg, kmr_picks **out);
+/* rounds and inputs of the picks: 1 and 1 from the plain entry points */
+int kmr_picks_segments_info(const kmr_picks *p, uint32_t *n_rounds, uint32_t *n_inputs);
+/* to host memory, any may be NULL: per round its depth and whether it is the remainder round; per segment (n_rounds x n_inputs,
+ * round-major) its first pick, picks, first byte and bytes; per read of the batch its segment, -1 = not picked */
+int kmr_picks_segments_copy(const kmr_picks *p, float *round_depth, uint8_t *round_is_remainder, uint64_t *seg_first_pick,
+                            uint64_t *seg_picks, uint64_t *seg_first_byte, uint64_t *seg_bytes, int32_t *read_segment);
 
 /* ---- ReadSet::identifyPairs: which reads of a batch are the two ends of one fragment, on the device ----------
  * One call equals one ReadSet::identifyPairs() (src/ReadSet.cpp:446-570) on a fresh ReadSet that holds the batch's reads in
@@ -844,7 +912,9 @@ void *kmr_stream(kmr_handle *h);
  *   "early_entry_share" (>= 0: kmr_count_lists_prefix's entry buffers hold that share of the good k-mers + 16 384 entries; < 0 = from the
  *   list share, the default), "saturated_batch_bytes" (scratch budget of one batch of kmr_finalize's ordered pass over k-mers seen 256
  *   times or more, 0 = 1 GiB; a key whose sightings alone exceed it is a batch of its own).
- *   "select_timing" (1: kmr_select_reads* / kmr_filter_read_batch* time their phases with HIP events, see kmr_build_info; default 0).
+ *   "select_timing" (1: kmr_select_reads* / kmr_filter_read_batch* / kmr_partition_* time their phases with HIP events, see kmr_build_info; default 0).
+ *   "partition_units" (most wavefronts, each over a contiguous range of reads, that kmr_partition_* deals the batch to, 1 - 8192; 0 = the
+ *   default, 8192 for up to 32 segments; tests set a few so that one wavefront walks many tiles of 64 reads; may be set at any time).
  *   "dump_timing" (1: kmr_dump_text_size / kmr_dump_text time their size pass and writer with HIP events, see kmr_build_info; default 0),
  *   "dump_piece_bytes" (staging bound of one piece of kmr_dump_mercount / kmr_dump_mergraph's file, 0 = KMR_DUMP_PIECE_BYTES; may be set at any time).
  *   "pair_hash_bits" (bits of the common name's hash that kmr_identify_pairs* sorts by, 1 - 64, default 64: with a few bits distinct names

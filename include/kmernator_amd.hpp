@@ -294,6 +294,56 @@ public:
 		                           t.trimOffset.data(), t.trimLength.data(), t.score.data(), t.wasTrimmed.data(), &cfg, &_p), "kmr_select_reads");
 		return getNumPicks();
 	}
+	/* selectReads (apps/FilterReads.h:159-279) with --max-kmer-output-depth off: the rounds of cfg.partition_by_depth and
+	 * cfg.remainder_trim over the inputs [inputStarts[j], inputStarts[j + 1]) (empty = one input); the fused call when trims is
+	 * null, else the selection over the trims the caller holds.  Returns the files the reference writes, in order, as (name, text):
+	 * with separateOutputs output + "-MinDepth<d>" + "-PartitionDepth<depth>" or "-Remainder" (when partitioned) + "-" + prefix +
+	 * ".fastq" / ".fasta", a file no read went to left out; without, one entry named output with the concatenation.
+	 * inputPrefixes default to "transformed-<j + 1>" (src/ReadSet.cpp:376-382). */
+	struct Segments { uint32_t nRounds = 0, nInputs = 0; std::vector<float> roundDepth; std::vector<uint8_t> roundIsRemainder; std::vector<uint64_t> firstPick, picks, firstByte, bytes; std::vector<int32_t> readSegment; };
+	static kmr_partition_config partitionDefaults() { kmr_partition_config c; kmr_partition_config_init(&c); return c; }
+	std::vector<std::pair<std::string, std::string> > selectReads(const kmr_partition_config &cfg, const std::vector<uint64_t> &inputStarts = std::vector<uint64_t>(),
+	                                                              const std::vector<std::string> &inputPrefixes = std::vector<std::string>(), const std::string &output = "",
+	                                                              bool separateOutputs = true, const KmerSpectrum::TrimResult *trims = nullptr) {
+		reset();
+		const uint64_t *starts = inputStarts.empty() ? nullptr : inputStarts.data();
+		const uint32_t nIn = inputStarts.empty() ? 0 : (uint32_t)(inputStarts.size() - 1);
+		if (trims) _sp.check(kmr_partition_reads(_sp.raw(), _reads.raw(), _reads._text.data(), _reads._text.size(), mate(), action(), minPass(), maxPass(), trims->trimOffset.data(), trims->trimLength.data(),
+		                                         trims->score.data(), trims->wasTrimmed.data(), starts, nIn, &cfg, &_p), "kmr_partition_reads");
+		else _sp.check(kmr_partition_read_batch(_sp.raw(), _reads.raw(), _reads._text.data(), _reads._text.size(), mate(), action(), minPass(), maxPass(), starts, nIn, &cfg, &_p), "kmr_partition_read_batch");
+		const std::string text = writePicks();
+		const Segments s = segments();
+		std::vector<std::pair<std::string, std::string> > files;
+		if (!separateOutputs) { files.push_back(std::make_pair(output, text)); return files; }
+		if (!inputPrefixes.empty() && inputPrefixes.size() != s.nInputs) throw KmerSpectrumError(KMR_ERR_INVALID_ARG, "selectReads: one prefix per input");
+		for (uint32_t r = 0; r < s.nRounds; r++) {
+			std::string name = output + "-MinDepth" + std::to_string((unsigned int)cfg.select.minimum_score);
+			if (cfg.partition_by_depth > 0) {
+				char depth[32]; std::snprintf(depth, sizeof depth, "%.9g", (double)s.roundDepth[r]);      /* lexical_cast<string>(float): 16, not 16.0 */
+				if (s.roundIsRemainder[r]) name += "-Remainder"; else if (s.roundDepth[r] > 0) name += std::string("-PartitionDepth") + depth;
+			}
+			for (uint32_t j = 0; j < s.nInputs; j++) {
+				const size_t g = (size_t)r * s.nInputs + j;
+				if (!s.picks[g]) continue;
+				const std::string prefix = inputPrefixes.empty() ? "transformed-" + std::to_string(j + 1) : inputPrefixes[j];
+				files.push_back(std::make_pair(name + "-" + prefix + (cfg.select.format == 1 ? ".fasta" : ".fastq"), text.substr(s.firstByte[g], s.bytes[g])));
+			}
+		}
+		return files;
+	}
+	/* the segment table of the picks (kmr_picks_segments_copy): segment = round * nInputs + input */
+	Segments segments() const {
+		Segments s;
+		if (kmr_picks_segments_info(_p, &s.nRounds, &s.nInputs) != KMR_OK) throw KmerSpectrumError(KMR_ERR_STATE, "segments: nothing has been picked");
+		const size_t g = (size_t)s.nRounds * s.nInputs, n = _reads.getSize();
+		s.roundDepth.assign(33, 0); s.roundIsRemainder.assign(33, 0);
+		s.firstPick.assign(g + 1, 0); s.picks.assign(g + 1, 0); s.firstByte.assign(g + 1, 0); s.bytes.assign(g + 1, 0); s.readSegment.assign(n + 1, -1);
+		const int rc = kmr_picks_segments_copy(_p, s.roundDepth.data(), s.roundIsRemainder.data(), s.firstPick.data(), s.picks.data(), s.firstByte.data(), s.bytes.data(), s.readSegment.data());
+		if (rc != KMR_OK) throw KmerSpectrumError(rc, "kmr_picks_segments_copy");
+		s.roundDepth.resize(s.nRounds); s.roundIsRemainder.resize(s.nRounds);
+		s.firstPick.resize(g); s.picks.resize(g); s.firstByte.resize(g); s.bytes.resize(g); s.readSegment.resize(n);
+		return s;
+	}
 	uint64_t getNumPicks() const { uint64_t n = 0; kmr_picks_info(_p, &n, nullptr); return n; }
 	/* the text of the picks; picked (optional) receives one flag per read of the batch */
 	std::string writePicks(std::vector<uint8_t> *picked = nullptr) const {

@@ -2168,6 +2168,7 @@ int kmr_tune(kmr_handle *h, const char *knob, double value) {
 	else if (k == "dump_timing") h->tune.dump_timing = value != 0;
 	else if (k == "pairs_timing") h->tune.pairs_timing = value != 0;
 	else if (k == "dedup_timing") h->tune.dedup_timing = value != 0;
+	else if (k == "partition_units") h->tune.partition_units = value >= 1 && value <= 8192 ? (uint32_t)value : 0;
 	else if (k == "pair_hash_bits") h->tune.pair_hash_bits = value >= 1 && value < 64 ? (uint32_t)value : 64;
 	else if (k == "dump_piece_bytes") h->tune.dump_piece_bytes = value >= 1 ? (uint64_t)value : 0;
 	else if (k == "narrow_tallies") h->tune.no_narrow = value == 0;

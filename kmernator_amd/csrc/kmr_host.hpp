@@ -178,6 +178,7 @@ struct KMR_HIDDEN Tuning {
 	bool select_timing = false;        /* kmr_select_* / kmr_filter_*: time scoring, selection and writer with HIP events (kmr_build_info; measurement tools) */
 	bool pairs_timing = false;         /* kmr_identify_pairs*: time the name parse, the sort and the whole call with HIP events (kmr_build_info; measurement tools) */
 	bool dedup_timing = false;         /* kmr_dedup_fragments*: time the key kernel, the sorts, the consensus kernel and the whole call with HIP events (kmr_build_info; measurement tools) */
+	uint32_t partition_units = 0;      /* kmr_partition_*: most units (wavefronts over contiguous reads) of the partition, 0 = the default of 8192 (tests: a few, so that a unit walks many tiles) */
 	uint32_t pair_hash_bits = 64;      /* kmr_identify_pairs*: bits of the common name's hash the phase-2 sort keys keep (tests: a few bits, so that distinct names share a key) */
 	bool no_coarse_lists = true;       /* exchange: scatter into the job's fine lists (default) or, kmr_tune("coarse_lists", 1), into coarse ones that the owner splits before the count pass (sk_refine_kernel: not yet fast enough to pay) */
 };
@@ -261,6 +262,13 @@ struct OnDevice { int device = 0; };
 struct KMR_HIDDEN kmr_picks : OnDevice {
 	DevBuf text, picked;
 	uint64_t n = 0, n_picked = 0, bytes = 0;
+	/* the partitioned entry points: segment = round * n_inputs + input.  Picks of the plain entry points are one round and one
+	 * input, hold no read_seg (it follows from picked) and an empty seg_table (it follows from the totals) */
+	DevBuf read_seg;                        /* int32 per read, -1 = not picked */
+	std::vector<uint64_t> seg_table;        /* per segment {first pick, picks, first byte, bytes} */
+	uint32_t n_rounds = 1, n_inputs = 1;
+	float round_depth[33] = {};
+	uint8_t round_is_remainder[33] = {};
 };
 
 /* what kmr_identify_pairs* leaves on the device: the mate of every read and the pair list */

@@ -1,7 +1,8 @@
 /*
  * kmr_select.hpp -- read selection and FASTQ / FASTA output of FilterReads on the device.
  *
- * Replaces selectReads (apps/FilterReads.h:159-279) with max-kmer-output-depth and partition-by-depth off:
+ * Replaces selectReads (apps/FilterReads.h:159-279) with max-kmer-output-depth off -- the plain branch here, the partitioned
+ * one (--partition-by-depth, --remainder-trim, one output per input file) in the second half of this file:
  * ReadSelector::pickAllPassingReads / pickAllPassingPairs (src/ReadSelector.h:547-596), optimizePickOrder (:1212-1221)
  * and writePicks (:1242-1262) = Read::toFastq / toFasta (src/Sequence.cpp:761-779) of every picked read in ascending read
  * index, over the per-read results of the artifact filter and of scoreAndTrimReads.
@@ -23,6 +24,8 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "kmr_select_rounds.hpp"
 
 namespace kmr {
 
@@ -54,12 +57,14 @@ __device__ __forceinline__ bool sel_passes_length(float length, uint32_t read_le
 	return minimum <= length;
 }
 __device__ __forceinline__ bool sel_discarded(const SelectParams &P, uint64_t i) { return P.af_action && P.af_action[i] == 2; }
-/* isPassingRead(readIdx, minimumScore, minimumLength) (:550-557) */
-__device__ __forceinline__ bool sel_passing(const SelectParams &P, uint64_t i) {
+/* isPassingRead(readIdx, minimumScore, minimumLength) (:550-557), the thresholds being those of one round of selectReads
+ * (P.min_score / P.min_read_length of the plain branch, a row of the round table of the partitioned one) */
+__device__ __forceinline__ bool sel_passing(const SelectParams &P, uint64_t i, float min_score, float min_read_length) {
 	if (sel_discarded(P, i)) return false;
 	const uint32_t len = (uint32_t)(P.offsets[i + 1] - P.offsets[i]);
-	return P.score[i] >= P.min_score && sel_passes_length((float)P.trim_len[i], len, P.min_read_length);
+	return P.score[i] >= min_score && sel_passes_length((float)P.trim_len[i], len, min_read_length);
 }
+__device__ __forceinline__ bool sel_passing(const SelectParams &P, uint64_t i) { return sel_passing(P, i, P.min_score, P.min_read_length); }
 
 __device__ __forceinline__ uint32_t sel_put_char(uint8_t *dst, uint32_t at, char c, bool write) { if (write) dst[at] = (uint8_t)c; return at + 1; }
 __device__ __forceinline__ uint32_t sel_put_str(uint8_t *dst, uint32_t at, const char *s, bool write) {
@@ -116,6 +121,16 @@ __device__ __forceinline__ uint32_t sel_record_bytes(const SelectParams &P, uint
 	return 1 + nlen + lablen + 1 + slice_len + 1 + (P.fasta ? 0u : 2u + slice_len + 1u);
 }
 
+/* the printed length of picked read i's name (up to the first blank or tab) and the exact byte count of its record */
+__device__ __forceinline__ uint32_t sel_measure(const SelectParams &P, uint64_t i, uint32_t *name_printed, uint32_t *err) {
+	uint32_t nlen = 0;
+	const uint64_t no = P.name_off[i]; const uint32_t nl = P.name_len[i];
+	if (no > P.text_len || nl > P.text_len - no) atomicOr(err, (uint32_t)SEL_ERR_NAME);
+	else while (nlen < nl && P.text[no + nlen] != ' ' && P.text[no + nlen] != '\t') nlen++;
+	*name_printed = nlen;
+	return sel_record_bytes(P, nlen, sel_label(P, i, nullptr, false), sel_slice(P, i).len);
+}
+
 __global__ __launch_bounds__(256)
 void select_count_kernel(SelectParams P, uint32_t *pick_flag, uint32_t *rec_len, uint32_t *name_printed, uint8_t *picked, uint32_t *err) {
 	for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < P.n; i += (uint64_t)gridDim.x * blockDim.x) {
@@ -126,12 +141,7 @@ void select_count_kernel(SelectParams P, uint32_t *pick_flag, uint32_t *rec_len,
 			else { const bool other = sel_passing(P, (uint64_t)m); pick = P.both_pass ? (pick && other) : (pick || other); }      /* isPassingPair :558-568 */
 		}
 		uint32_t bytes = 0, nlen = 0;
-		if (pick) {
-			const uint64_t no = P.name_off[i]; const uint32_t nl = P.name_len[i];
-			if (no > P.text_len || nl > P.text_len - no) atomicOr(err, (uint32_t)SEL_ERR_NAME);
-			else while (nlen < nl && P.text[no + nlen] != ' ' && P.text[no + nlen] != '\t') nlen++;
-			bytes = sel_record_bytes(P, nlen, sel_label(P, i, nullptr, false), sel_slice(P, i).len);
-		}
+		if (pick) bytes = sel_measure(P, i, &nlen, err);
 		pick_flag[i] = pick ? 1u : 0u; picked[i] = pick ? 1 : 0; rec_len[i] = bytes; name_printed[i] = nlen;
 	}
 }
@@ -184,6 +194,131 @@ void select_write_kernel(SelectParams P, const uint32_t *name_printed, const uin
 		const uint64_t rs = pick_off[p];
 		const uint32_t r = pick_read[p];
 		sel_emit(P, r, name_printed[r], (uint32_t)(pick_off[p + 1] - rs), out + rs, lane, s_label[wave]);
+	}
+}
+
+/* ---- the partitioned branch of selectReads (apps/FilterReads.h:209-278): --partition-by-depth, --remainder-trim and one output
+ * per input file.  A read belongs to the first round of the table (kmr_select_rounds.hpp) whose pair decision picks it -- a pick
+ * makes a read unavailable to every later round (pickIfNew, src/ReadSelector.h:513-542), and both reads of a pair are picked
+ * together -- and to the input file its index falls into.  Segment = round * n_inputs + input; the output is the segments in that
+ * order, ascending read index inside each (optimizePickOrder sorts the picks of one round only), which is a stable multi-way
+ * partition of the reads:
+ *   partition_classify_kernel  per read its segment (or -1), name length and record bytes; per unit the picks and bytes of every
+ *                              segment, summed in LDS
+ *   partition_scan_kernel      one block: exclusive scan of the [segment][unit] matrices in that (segment-major) order; the
+ *                              segment table, the totals and the sentinel of pick_off
+ *   partition_rank_kernel      per unit again: a read's pick index = its unit's base for the segment + the reads of that segment
+ *                              before it in the unit, likewise its byte offset; fills the (pick_read, pick_off) select_write_kernel
+ *                              reads
+ * A unit is one wavefront (a block of 64 threads) over a CONTIGUOUS range of reads, walked 64 reads at a time: consecutive
+ * lanes still read consecutive elements, as in a grid stride, but a unit's reads are all before the next unit's, which is what
+ * makes the partition stable.  The LDS atomics only add integers (order-free sums); ranks come from ballots and wave scans.
+ * Three launches whatever the number of reads, rounds and inputs. */
+static const int SEL_MAX_SEGMENTS = 256;      /* rounds x inputs: 3 KiB of LDS per unit (4 + 8 bytes a segment), so that 32 units fit a CU's 160 KiB */
+static const int SEL_UNIT = 64, SEL_SCAN_THREADS = 1024, SEL_SCAN_ITEMS = 4;
+
+struct PartitionParams {
+	const uint64_t *input_starts;      /* device memory, n_inputs + 1 read indices; not read when n_inputs is 1 */
+	uint32_t n_inputs, n_segments;
+	uint32_t n_units;
+	uint64_t per_unit;                 /* reads of a unit, a multiple of SEL_UNIT */
+};
+
+__global__ __launch_bounds__(SEL_UNIT)
+void partition_classify_kernel(SelectParams P, SelRounds R, PartitionParams Q, int32_t *read_seg, uint32_t *rec_len, uint32_t *name_printed, uint8_t *picked,
+                               uint32_t *unit_cnt, unsigned long long *unit_bytes, uint32_t *err) {
+	__shared__ uint32_t s_cnt[SEL_MAX_SEGMENTS];
+	__shared__ unsigned long long s_bytes[SEL_MAX_SEGMENTS];
+	const uint32_t lane = threadIdx.x, u = blockIdx.x;
+	for (uint32_t s = lane; s < Q.n_segments; s += SEL_UNIT) { s_cnt[s] = 0; s_bytes[s] = 0; }
+	__syncthreads();
+	const uint64_t lo = (uint64_t)u * Q.per_unit, hi = lo + Q.per_unit < P.n ? lo + Q.per_unit : P.n;
+	for (uint64_t i = lo + lane; i < hi; i += SEL_UNIT) {
+		const int64_t m = P.mate ? P.mate[i] : -1;
+		const bool paired = m >= 0 && (uint64_t)m < P.n;
+		if (m >= 0 && !paired) atomicOr(err, (uint32_t)SEL_ERR_MATE);
+		int32_t seg = -1;
+		for (uint32_t r = 0; r < R.n && seg < 0; r++) {
+			bool pick = sel_passing(P, i, R.min_score[r], R.min_read_length[r]);
+			if (paired) { const bool other = sel_passing(P, (uint64_t)m, R.min_score[r], R.min_read_length[r]); pick = R.both_pass[r] ? (pick && other) : (pick || other); }      /* isPassingPair :558-568 */
+			if (pick) seg = (int32_t)r;
+		}
+		uint32_t bytes = 0, nlen = 0;
+		if (seg >= 0) {
+			if (Q.n_inputs > 1) {      /* the last input that starts at or before i (input_starts[0] = 0, [n_inputs] = n > i) */
+				uint32_t a = 0, b = Q.n_inputs;
+				while (b - a > 1) { const uint32_t mid = a + (b - a) / 2; if (Q.input_starts[mid] <= i) a = mid; else b = mid; }
+				seg = seg * (int32_t)Q.n_inputs + (int32_t)a;
+			}
+			bytes = sel_measure(P, i, &nlen, err);
+			atomicAdd(&s_cnt[seg], 1u); atomicAdd(&s_bytes[seg], (unsigned long long)bytes);
+		}
+		read_seg[i] = seg; picked[i] = seg >= 0 ? 1 : 0; rec_len[i] = bytes; name_printed[i] = nlen;
+	}
+	__syncthreads();
+	for (uint32_t s = lane; s < Q.n_segments; s += SEL_UNIT) { unit_cnt[(size_t)s * Q.n_units + u] = s_cnt[s]; unit_bytes[(size_t)s * Q.n_units + u] = s_bytes[s]; }
+}
+
+/* In place: unit_cnt / unit_bytes become exclusive prefixes over the matrix in segment-major order.  seg_table: one row of four
+ * per segment {first pick, picks, first byte, bytes}; totals[0] = picks, totals[1] = bytes (totals[2] = the error word of the
+ * classification); pick_off[picks] = bytes, the end of the last record. */
+__global__ __launch_bounds__(SEL_SCAN_THREADS)
+void partition_scan_kernel(uint32_t *unit_cnt, unsigned long long *unit_bytes, uint32_t n_segments, uint32_t n_units, uint64_t *seg_table, uint64_t *pick_off, uint64_t *totals) {
+	__shared__ unsigned long long s_wc[SEL_SCAN_THREADS / 64], s_wb[SEL_SCAN_THREADS / 64];
+	const uint64_t M = (uint64_t)n_segments * n_units;
+	const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+	unsigned long long carry_c = 0, carry_b = 0;      /* the same in every thread */
+	for (uint64_t base = 0; base < M; base += (uint64_t)SEL_SCAN_THREADS * SEL_SCAN_ITEMS) {
+		const uint64_t j0 = base + (uint64_t)tid * SEL_SCAN_ITEMS;
+		uint32_t c[SEL_SCAN_ITEMS]; unsigned long long b[SEL_SCAN_ITEMS];
+		unsigned long long tc = 0, tb = 0;
+		for (int k = 0; k < SEL_SCAN_ITEMS; k++) { const bool in = j0 + k < M; c[k] = in ? unit_cnt[j0 + k] : 0u; b[k] = in ? unit_bytes[j0 + k] : 0ull; tc += c[k]; tb += b[k]; }
+		unsigned long long ic = tc, ib = tb;
+		for (int d = 1; d < 64; d <<= 1) { const unsigned long long x = __shfl_up(ic, d), y = __shfl_up(ib, d); if ((int)lane >= d) { ic += x; ib += y; } }
+		if (lane == 63) { s_wc[wave] = ic; s_wb[wave] = ib; }
+		__syncthreads();
+		unsigned long long ec = carry_c + ic - tc, eb = carry_b + ib - tb;
+		for (uint32_t w = 0; w < SEL_SCAN_THREADS / 64; w++) { if (w < wave) { ec += s_wc[w]; eb += s_wb[w]; } carry_c += s_wc[w]; carry_b += s_wb[w]; }
+		for (int k = 0; k < SEL_SCAN_ITEMS; k++) if (j0 + k < M) { unit_cnt[j0 + k] = (uint32_t)ec; unit_bytes[j0 + k] = eb; ec += c[k]; eb += b[k]; }
+		__syncthreads();      /* s_wc / s_wb are rewritten by the next tile; after the last one the prefixes are read back below */
+	}
+	for (uint32_t s = tid; s < n_segments; s += SEL_SCAN_THREADS) {
+		const uint64_t fp = unit_cnt[(size_t)s * n_units], fb = unit_bytes[(size_t)s * n_units];
+		const uint64_t ep = s + 1 < n_segments ? unit_cnt[(size_t)(s + 1) * n_units] : carry_c, eb = s + 1 < n_segments ? unit_bytes[(size_t)(s + 1) * n_units] : carry_b;
+		seg_table[4 * s] = fp; seg_table[4 * s + 1] = ep - fp; seg_table[4 * s + 2] = fb; seg_table[4 * s + 3] = eb - fb;
+	}
+	if (tid == 0) { totals[0] = carry_c; totals[1] = carry_b; pick_off[carry_c] = carry_b; }
+}
+
+__global__ __launch_bounds__(SEL_UNIT)
+void partition_rank_kernel(const int32_t *read_seg, const uint32_t *rec_len, uint64_t n, PartitionParams Q, const uint32_t *unit_cnt, const unsigned long long *unit_bytes,
+                           uint32_t *pick_read, uint64_t *pick_off) {
+	__shared__ uint32_t s_cnt[SEL_MAX_SEGMENTS];            /* where the unit's next read of the segment goes */
+	__shared__ unsigned long long s_bytes[SEL_MAX_SEGMENTS];
+	const uint32_t lane = threadIdx.x, u = blockIdx.x;
+	for (uint32_t s = lane; s < Q.n_segments; s += SEL_UNIT) { s_cnt[s] = unit_cnt[(size_t)s * Q.n_units + u]; s_bytes[s] = unit_bytes[(size_t)s * Q.n_units + u]; }
+	__syncthreads();
+	const uint64_t lo = (uint64_t)u * Q.per_unit, hi = lo + Q.per_unit < n ? lo + Q.per_unit : n;
+	for (uint64_t t = lo; t < hi; t += SEL_UNIT) {      /* the whole wavefront takes every turn */
+		const uint64_t i = t + lane;
+		const int32_t seg = i < hi ? read_seg[i] : -1;
+		const unsigned long long len = i < hi ? rec_len[i] : 0u;
+		unsigned long long todo = __ballot(seg >= 0);
+		while (todo) {      /* one turn per segment present among the 64 reads */
+			const int leader = __ffsll(todo) - 1;
+			const int32_t s0 = __shfl(seg, leader);
+			const bool mine = seg == s0;
+			const unsigned long long members = __ballot(mine);
+			unsigned long long inc = mine ? len : 0ull;
+			for (int d = 1; d < 64; d <<= 1) { const unsigned long long x = __shfl_up(inc, d); if ((int)lane >= d) inc += x; }
+			const unsigned long long all = __shfl(inc, 63);
+			const uint32_t at = s_cnt[s0]; const unsigned long long byte_at = s_bytes[s0];
+			if (mine) { const uint32_t p = at + (uint32_t)__popcll(members & ((1ull << lane) - 1)); pick_read[p] = (uint32_t)i; pick_off[p] = byte_at + inc - len; }
+			__syncthreads();
+			if ((int)lane == leader) { s_cnt[s0] = at + (uint32_t)__popcll(members); s_bytes[s0] = byte_at + all; }
+			__syncthreads();
+			todo &= ~members;
+		}
 	}
 }
 

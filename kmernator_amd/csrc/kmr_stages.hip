@@ -496,19 +496,46 @@ static int select_check_config(kmr_handle *h, const kmr_select_config *c) {
 
 typedef EventTimer<3> SelectTimer;
 
-/* every pointer but the last is device memory (mate and the three af_* may be null) */
-static int select_core(kmr_handle *h, Scratch &tmp, const kmr_reads *r, const uint8_t *dtext, uint64_t text_len, const int64_t *dmate, const uint8_t *dact, const uint32_t *dmin,
-                       const uint32_t *dmax, const uint32_t *dto, const uint32_t *dtl, const float *dsc, const uint8_t *dwt, const kmr_select_config *cfg, kmr_picks *pk) {
-	const uint64_t n = r->n;
-	pk->n = n;
-	h->last_select_ms = h->last_write_ms = 0;
-	if (n == 0) return KMR_OK;
+/* every pointer is device memory (mate and the three af_* may be null) */
+static SelectParams select_params(kmr_handle *h, const kmr_reads *r, const uint8_t *dtext, uint64_t text_len, const int64_t *dmate, const uint8_t *dact, const uint32_t *dmin,
+                                  const uint32_t *dmax, const uint32_t *dto, const uint32_t *dtl, const float *dsc, const uint8_t *dwt, const kmr_select_config *cfg) {
 	SelectParams P;
 	P.bases = r->bases.get<uint8_t>(); P.quals = r->quals.get<uint8_t>(); P.offsets = r->offsets.get<uint64_t>(); P.name_off = r->name_off.get<uint64_t>(); P.name_len = r->name_len.get<uint32_t>();
 	P.text = dtext; P.text_len = text_len; P.mate = dmate; P.af_action = dact; P.af_min = dmin; P.af_max = dmax;
-	P.trim_off = dto; P.trim_len = dtl; P.score = dsc; P.was_trimmed = dwt; P.n = n;
+	P.trim_off = dto; P.trim_len = dtl; P.score = dsc; P.was_trimmed = dwt; P.n = r->n;
 	P.min_score = (float)cfg->minimum_score; P.min_read_length = cfg->min_read_length; P.both_pass = cfg->both_pass ? 1u : 0u; P.fasta = cfg->format; P.scoring = cfg->scoring_type;
 	P.out_base = cfg->output_quality_base; P.qual_shift = (int32_t)cfg->output_quality_base - (int32_t)h->cfg.fastq_start_char;
+	return P;
+}
+
+/* The second half of a selection: the one copy that brings sizes back -- tot: picks, bytes, the error word and whatever the
+ * caller put behind them, n_tot words to host_tot --, then the text of the picks (pread, poff) by select_write_kernel.  The
+ * timer's mark 0 is the caller's. */
+static int select_write(kmr_handle *h, Scratch &tmp, const SelectParams &P, const uint32_t *nlen, const uint32_t *pread, const uint64_t *poff, const uint64_t *tot, size_t n_tot,
+                        uint64_t *host_tot, kmr_picks *pk, SelectTimer &timer) {
+	HIPCHK(h, hipMemcpyAsync(host_tot, tot, 8 * n_tot, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
+	if (host_tot[2] & SEL_ERR_MATE) return fail(h, KMR_ERR_INVALID_ARG, "a mate index lies outside the batch");
+	if (host_tot[2] & SEL_ERR_NAME) return fail(h, KMR_ERR_INVALID_ARG, NAME_SPAN_ERROR);
+	pk->n_picked = host_tot[0]; pk->bytes = host_tot[1];
+	timer.mark(1, h->stream);
+	if (pk->bytes) {
+		HIPCHK(h, pk->text.alloc((pk->bytes + 15) & ~(uint64_t)15));
+		uint8_t *dout = pk->text.get<uint8_t>();
+		hipLaunchKernelGGL(select_write_kernel, dim3((unsigned)std::min<uint64_t>((pk->n_picked + SEL_WAVES - 1) / SEL_WAVES, (uint64_t)num_cus(h) * 8)), dim3(SEL_THREADS), 0, h->stream, P, nlen, pread, poff, pk->n_picked, dout);
+		HIPCHK(h, hipGetLastError());
+	}
+	timer.mark(2, h->stream);
+	HIPCHK(h, hipStreamSynchronize(h->stream));
+	tmp.done();
+	h->last_select_ms = timer.ms(0, 2); h->last_write_ms = timer.ms(1, 2);
+	return KMR_OK;
+}
+
+static int select_core(kmr_handle *h, Scratch &tmp, const SelectParams &P, kmr_picks *pk) {
+	const uint64_t n = P.n;
+	pk->n = n; pk->round_depth[0] = P.min_score;
+	h->last_select_ms = h->last_write_ms = 0;
+	if (n == 0) return KMR_OK;
 	uint32_t *flag, *len, *nlen, *pread; uint64_t *pscan, *bscan, *poff, *tot; uint8_t *picked;
 	HIPCHK(h, tmp.take(&flag, n)); HIPCHK(h, tmp.take(&len, n)); HIPCHK(h, tmp.take(&nlen, n)); HIPCHK(h, tmp.take(&pread, n));
 	HIPCHK(h, tmp.take(&pscan, n + 1)); HIPCHK(h, tmp.take(&bscan, n + 1)); HIPCHK(h, tmp.take(&poff, n + 1)); HIPCHK(h, tmp.take(&tot, 3));
@@ -523,22 +550,82 @@ static int select_core(kmr_handle *h, Scratch &tmp, const kmr_reads *r, const ui
 	hipLaunchKernelGGL(select_compact_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, (const uint32_t *)flag, (const uint64_t *)pscan, (const uint64_t *)bscan, n, pread, poff, tot);
 	HIPCHK(h, hipGetLastError());
 	uint64_t totals[3] = {0, 0, 0};
-	HIPCHK(h, hipMemcpyAsync(totals, tot, 24, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));      /* the one copy that brings sizes back */
-	if (totals[2] & SEL_ERR_MATE) return fail(h, KMR_ERR_INVALID_ARG, "a mate index lies outside the batch");
-	if (totals[2] & SEL_ERR_NAME) return fail(h, KMR_ERR_INVALID_ARG, NAME_SPAN_ERROR);
-	pk->n_picked = totals[0]; pk->bytes = totals[1];
-	timer.mark(1, h->stream);
-	if (pk->bytes) {
-		HIPCHK(h, pk->text.alloc((pk->bytes + 15) & ~(uint64_t)15));
-		uint8_t *dout = pk->text.get<uint8_t>();
-		hipLaunchKernelGGL(select_write_kernel, dim3((unsigned)std::min<uint64_t>((pk->n_picked + SEL_WAVES - 1) / SEL_WAVES, (uint64_t)num_cus(h) * 8)), dim3(SEL_THREADS), 0, h->stream, P, (const uint32_t *)nlen, (const uint32_t *)pread, (const uint64_t *)poff, pk->n_picked, dout);
-		HIPCHK(h, hipGetLastError());
+	return select_write(h, tmp, P, nlen, pread, poff, tot, 3, totals, pk, timer);
+}
+
+/* what the four partitioned entry points add to the arguments of the plain four */
+struct PartitionArgs { const kmr_partition_config *cfg; const uint64_t *input_starts; uint32_t n_inputs; };
+
+/* the units of the partition: at most 8192 wavefronts (8 a SIMD on 256 CUs), fewer when many segments make the [segment][unit]
+ * matrices large (never above 2^18 entries beyond 1024 units; kmr_tune "partition_units" caps them for tests), each over a multiple of
+ * 64 reads */
+static void partition_units(const kmr_handle *h, uint64_t n, uint32_t n_segments, PartitionParams &Q) {
+	const uint64_t most = h->tune.partition_units ? h->tune.partition_units : std::min<uint64_t>(8192, std::max<uint64_t>(1024, (1u << 18) / n_segments));
+	Q.per_unit = (((n + most - 1) / most) + SEL_UNIT - 1) / SEL_UNIT * SEL_UNIT;
+	Q.n_units = (uint32_t)((n + Q.per_unit - 1) / Q.per_unit);
+}
+
+/* the partitioned branch: P as select_core's (its three thresholds are not read), R the rounds, dstarts the inputs' first reads in
+ * device memory (null for one input) */
+static int partition_core(kmr_handle *h, Scratch &tmp, const SelectParams &P, const SelRounds &R, const uint64_t *dstarts, uint32_t n_inputs, kmr_picks *pk) {
+	const uint64_t n = P.n;
+	const uint32_t S = R.n * n_inputs;
+	pk->n = n; pk->n_rounds = R.n; pk->n_inputs = n_inputs;
+	for (uint32_t r = 0; r < R.n; r++) { pk->round_depth[r] = R.min_score[r]; pk->round_is_remainder[r] = R.is_remainder[r]; }
+	pk->seg_table.assign((size_t)4 * S, 0);
+	h->last_select_ms = h->last_write_ms = 0;
+	if (n == 0) return KMR_OK;
+	uint8_t *picked; int32_t *seg;
+	HIPCHK(h, alloc_n(pk->picked, &picked, n)); HIPCHK(h, alloc_n(pk->read_seg, &seg, n));
+	if (S == 0) {      /* --partition-by-depth below --min-depth: no round runs */
+		HIPCHK(h, hipMemsetAsync(picked, 0, n, h->stream)); HIPCHK(h, hipMemsetAsync(seg, 0xff, 4 * n, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
+		return KMR_OK;
 	}
-	timer.mark(2, h->stream);
-	HIPCHK(h, hipStreamSynchronize(h->stream));
-	tmp.done();
-	h->last_select_ms = timer.ms(0, 2); h->last_write_ms = timer.ms(1, 2);
+	PartitionParams Q;
+	Q.input_starts = dstarts; Q.n_inputs = n_inputs; Q.n_segments = S;
+	partition_units(h, n, S, Q);
+	const size_t cells = (size_t)S * Q.n_units;
+	uint32_t *len, *nlen, *pread, *ucnt; uint64_t *poff, *tot; unsigned long long *ubytes;
+	HIPCHK(h, tmp.take(&len, n)); HIPCHK(h, tmp.take(&nlen, n)); HIPCHK(h, tmp.take(&pread, n)); HIPCHK(h, tmp.take(&poff, n + 1));
+	HIPCHK(h, tmp.take(&ucnt, cells)); HIPCHK(h, tmp.take(&ubytes, cells)); HIPCHK(h, tmp.take(&tot, 3 + (size_t)4 * S));
+	SelectTimer timer(h->tune.select_timing);
+	timer.mark(0, h->stream);
+	HIPCHK(h, hipMemsetAsync(tot, 0, 24, h->stream));
+	hipLaunchKernelGGL(partition_classify_kernel, dim3(Q.n_units), dim3(SEL_UNIT), 0, h->stream, P, R, Q, seg, len, nlen, picked, ucnt, ubytes, (uint32_t *)(tot + 2));
+	hipLaunchKernelGGL(partition_scan_kernel, dim3(1), dim3(SEL_SCAN_THREADS), 0, h->stream, ucnt, ubytes, S, Q.n_units, tot + 3, poff, tot);
+	hipLaunchKernelGGL(partition_rank_kernel, dim3(Q.n_units), dim3(SEL_UNIT), 0, h->stream, (const int32_t *)seg, (const uint32_t *)len, n, Q, (const uint32_t *)ucnt, (const unsigned long long *)ubytes, pread, poff);
+	HIPCHK(h, hipGetLastError());
+	std::vector<uint64_t> host_tot(3 + (size_t)4 * S, 0);
+	int rc = select_write(h, tmp, P, nlen, pread, poff, tot, host_tot.size(), host_tot.data(), pk, timer); if (rc) return rc;
+	std::copy(host_tot.begin() + 3, host_tot.end(), pk->seg_table.begin());
 	return KMR_OK;
+}
+
+/* cfg, the input boundaries and the table of rounds, all without a device.  *n_inputs: 1 for input_starts NULL */
+static int partition_check(kmr_handle *h, const PartitionArgs *a, SelRounds *R, uint32_t *n_inputs) {
+	const kmr_partition_config *c = a->cfg;
+	if (!c) return fail(h, KMR_ERR_INVALID_ARG, "kmr_partition_config: NULL");
+	if (c->struct_size != sizeof(kmr_partition_config)) return fail(h, KMR_ERR_INVALID_ARG, "kmr_partition_config: struct_size " + std::to_string(c->struct_size) + " is not " + std::to_string(sizeof(kmr_partition_config)));
+	int rc = select_check_config(h, &c->select); if (rc) return rc;
+	*n_inputs = 1;
+	if (a->input_starts) {
+		if (a->n_inputs == 0) return fail(h, KMR_ERR_INVALID_ARG, "input_starts without n_inputs");
+		bool ok;
+		const uint32_t at = sel_check_input_starts(a->input_starts, a->n_inputs, &ok);
+		if (!ok) return fail(h, KMR_ERR_INVALID_ARG, "input_starts[" + std::to_string(at) + "]: the read indices start at 0 and ascend");
+		*n_inputs = a->n_inputs;
+	} else if (a->n_inputs > 1) return fail(h, KMR_ERR_INVALID_ARG, "input_starts is NULL for " + std::to_string(a->n_inputs) + " inputs");
+	if (c->partition_by_depth == 0) {      /* one round with the plain branch's own thresholds: kmr_select_reads' picks */
+		R->n = 1; R->min_score[0] = (float)c->select.minimum_score; R->min_read_length[0] = c->select.min_read_length; R->both_pass[0] = c->select.both_pass ? 1 : 0; R->is_remainder[0] = 0;
+	} else {
+		const double d = c->select.minimum_score;      /* selectReads takes minDepth as an unsigned int */
+		if (!(d >= 0.0 && d <= 4294967295.0) || d != std::floor(d)) return fail(h, KMR_ERR_INVALID_ARG, "kmr_partition_config: with partition_by_depth set, minimum_score is a whole number below 2^32");
+		if (sel_round_table((unsigned int)d, c->partition_by_depth, c->remainder_trim, c->select.min_read_length, c->select.both_pass != 0, *R))
+			return fail(h, KMR_ERR_UNSUPPORTED, "kmr_partition_config: more than " + std::to_string((int)SEL_MAX_ROUNDS) + " rounds");
+	}
+	if ((uint64_t)R->n * *n_inputs > (uint64_t)SEL_MAX_SEGMENTS)
+		return fail(h, KMR_ERR_UNSUPPORTED, std::to_string(R->n) + " rounds x " + std::to_string(*n_inputs) + " inputs: more than " + std::to_string((int)SEL_MAX_SEGMENTS) + " segments");
+	return 0;
 }
 
 static int select_check_args(kmr_handle *h, const kmr_reads *r, const void *text, uint64_t text_len, const uint8_t *af_action, const uint32_t *af_min, const uint32_t *af_max,
@@ -556,8 +643,17 @@ static int select_check_args(kmr_handle *h, const kmr_reads *r, const void *text
 /* text_on_device: `text` is device memory already (the other arrays are the host's) */
 static int select_reads_any(kmr_handle *h, const kmr_reads *r, const void *text, uint64_t text_len, bool text_on_device, const int64_t *mate, const uint8_t *af_action,
                             const uint32_t *af_min, const uint32_t *af_max, const uint32_t *trim_offset, const uint32_t *trim_length, const float *score,
-                            const uint8_t *was_trimmed, const kmr_select_config *cfg, kmr_picks **out, bool fused, const char *who) {
-	int rc = select_check_args(h, r, text, text_len, af_action, af_min, af_max, cfg, out, who); if (rc) return rc;
+                            const uint8_t *was_trimmed, const kmr_select_config *cfg, kmr_picks **out, bool fused, const char *who, const PartitionArgs *part = nullptr) {
+	SelRounds R; uint32_t n_inputs = 1;
+	int rc;
+	if (part) {
+		if (out) *out = nullptr;
+		rc = partition_check(h, part, &R, &n_inputs); if (rc) return rc;
+		cfg = &part->cfg->select;
+	}
+	rc = select_check_args(h, r, text, text_len, af_action, af_min, af_max, cfg, out, who); if (rc) return rc;
+	if (part && part->input_starts && part->input_starts[n_inputs] != r->n)
+		return fail(h, KMR_ERR_INVALID_ARG, std::string(who) + ": input_starts ends at " + std::to_string(part->input_starts[n_inputs]) + ", the batch holds " + std::to_string(r->n) + " reads");
 	if (fused) { if (!h->finalized) return fail(h, KMR_ERR_STATE, std::string(who) + " before kmr_finalize"); }
 	else if (r->n && (!trim_offset || !trim_length || !score || !was_trimmed)) return fail(h, KMR_ERR_INVALID_ARG, std::string(who) + ": NULL argument");
 	hipSetDevice(h->device);
@@ -585,7 +681,12 @@ static int select_reads_any(kmr_handle *h, const kmr_reads *r, const void *text,
 		rc = to_device(h, tmp, score, n, &dsc); if (rc) return rc;
 		rc = to_device(h, tmp, was_trimmed, n, &dwt); if (rc) return rc;
 	}
-	rc = select_core(h, tmp, r, dtext, text_len, dmate, dact, dmin, dmax, dto, dtl, dsc, dwt, cfg, pk.get());
+	const SelectParams P = select_params(h, r, dtext, text_len, dmate, dact, dmin, dmax, dto, dtl, dsc, dwt, cfg);
+	if (part) {
+		const uint64_t *dstarts = nullptr;
+		if (n_inputs > 1) { rc = to_device(h, tmp, part->input_starts, (uint64_t)n_inputs + 1, &dstarts); if (rc) return rc; }
+		rc = partition_core(h, tmp, P, R, dstarts, n_inputs, pk.get());
+	} else rc = select_core(h, tmp, P, pk.get());
 	if (!rc) *out = pk.release();
 	return rc;
 }
@@ -607,6 +708,77 @@ int kmr_filter_read_batch(kmr_handle *h, const kmr_reads *reads, const char *tex
 int kmr_filter_read_batch_dev(kmr_handle *h, const kmr_reads *reads, const void *dev_text, uint64_t text_len, const int64_t *mate, const uint8_t *af_action, const uint32_t *af_min_pass,
                               const uint32_t *af_max_pass, const kmr_select_config *cfg, kmr_picks **out) {
 	return select_reads_any(h, reads, dev_text, text_len, true, mate, af_action, af_min_pass, af_max_pass, nullptr, nullptr, nullptr, nullptr, cfg, out, true, "kmr_filter_read_batch_dev");
+}
+
+/* ---- the partitioned branch: the same four with the rounds of kmr_partition_config and the inputs' boundaries ---------------- */
+int kmr_partition_config_init(kmr_partition_config *c) {
+	if (!c) return KMR_ERR_INVALID_ARG;
+	memset(c, 0, sizeof(*c));
+	c->struct_size = (uint32_t)sizeof(kmr_partition_config);
+	kmr_select_config_init(&c->select);
+	c->partition_by_depth = 0;         /* --partition-by-depth -1, src/ReadSelector.h:72: off */
+	c->remainder_trim = -1.0f;         /* --remainder-trim -1, src/ReadSelector.h:72: off */
+	return KMR_OK;
+}
+int kmr_partition_rounds(const kmr_partition_config *cfg, uint32_t *n_rounds, float *round_depth, float *round_min_read_length, uint32_t *round_both_pass, uint8_t *round_is_remainder) {
+	SelRounds R; uint32_t n_inputs;
+	const PartitionArgs a = {cfg, nullptr, 0};
+	int rc = partition_check(nullptr, &a, &R, &n_inputs); if (rc) return rc;
+	if (n_rounds) *n_rounds = R.n;
+	for (uint32_t r = 0; r < R.n; r++) {
+		if (round_depth) round_depth[r] = R.min_score[r]; if (round_min_read_length) round_min_read_length[r] = R.min_read_length[r];
+		if (round_both_pass) round_both_pass[r] = R.both_pass[r]; if (round_is_remainder) round_is_remainder[r] = R.is_remainder[r];
+	}
+	return KMR_OK;
+}
+int kmr_partition_reads(kmr_handle *h, const kmr_reads *reads, const char *text, uint64_t text_len, const int64_t *mate, const uint8_t *af_action, const uint32_t *af_min_pass,
+                        const uint32_t *af_max_pass, const uint32_t *trim_offset, const uint32_t *trim_length, const float *score, const uint8_t *was_trimmed,
+                        const uint64_t *input_starts, uint32_t n_inputs, const kmr_partition_config *cfg, kmr_picks **out) {
+	const PartitionArgs a = {cfg, input_starts, n_inputs};
+	return select_reads_any(h, reads, text, text_len, false, mate, af_action, af_min_pass, af_max_pass, trim_offset, trim_length, score, was_trimmed, nullptr, out, false, "kmr_partition_reads", &a);
+}
+int kmr_partition_reads_dev(kmr_handle *h, const kmr_reads *reads, const void *dev_text, uint64_t text_len, const int64_t *mate, const uint8_t *af_action, const uint32_t *af_min_pass,
+                            const uint32_t *af_max_pass, const uint32_t *trim_offset, const uint32_t *trim_length, const float *score, const uint8_t *was_trimmed,
+                            const uint64_t *input_starts, uint32_t n_inputs, const kmr_partition_config *cfg, kmr_picks **out) {
+	const PartitionArgs a = {cfg, input_starts, n_inputs};
+	return select_reads_any(h, reads, dev_text, text_len, true, mate, af_action, af_min_pass, af_max_pass, trim_offset, trim_length, score, was_trimmed, nullptr, out, false, "kmr_partition_reads_dev", &a);
+}
+int kmr_partition_read_batch(kmr_handle *h, const kmr_reads *reads, const char *text, uint64_t text_len, const int64_t *mate, const uint8_t *af_action, const uint32_t *af_min_pass,
+                             const uint32_t *af_max_pass, const uint64_t *input_starts, uint32_t n_inputs, const kmr_partition_config *cfg, kmr_picks **out) {
+	const PartitionArgs a = {cfg, input_starts, n_inputs};
+	return select_reads_any(h, reads, text, text_len, false, mate, af_action, af_min_pass, af_max_pass, nullptr, nullptr, nullptr, nullptr, nullptr, out, true, "kmr_partition_read_batch", &a);
+}
+int kmr_partition_read_batch_dev(kmr_handle *h, const kmr_reads *reads, const void *dev_text, uint64_t text_len, const int64_t *mate, const uint8_t *af_action, const uint32_t *af_min_pass,
+                                 const uint32_t *af_max_pass, const uint64_t *input_starts, uint32_t n_inputs, const kmr_partition_config *cfg, kmr_picks **out) {
+	const PartitionArgs a = {cfg, input_starts, n_inputs};
+	return select_reads_any(h, reads, dev_text, text_len, true, mate, af_action, af_min_pass, af_max_pass, nullptr, nullptr, nullptr, nullptr, nullptr, out, true, "kmr_partition_read_batch_dev", &a);
+}
+int kmr_picks_segments_info(const kmr_picks *p, uint32_t *n_rounds, uint32_t *n_inputs) {
+	if (!p) return KMR_ERR_INVALID_ARG;
+	if (n_rounds) *n_rounds = p->n_rounds; if (n_inputs) *n_inputs = p->n_inputs;
+	return KMR_OK;
+}
+int kmr_picks_segments_copy(const kmr_picks *p, float *round_depth, uint8_t *round_is_remainder, uint64_t *seg_first_pick, uint64_t *seg_picks, uint64_t *seg_first_byte,
+                            uint64_t *seg_bytes, int32_t *read_segment) {
+	if (!p) return KMR_ERR_INVALID_ARG;
+	for (uint32_t r = 0; r < p->n_rounds; r++) { if (round_depth) round_depth[r] = p->round_depth[r]; if (round_is_remainder) round_is_remainder[r] = p->round_is_remainder[r]; }
+	const uint64_t one[4] = {0, p->n_picked, 0, p->bytes};      /* picks of the plain entry points */
+	const size_t S = (size_t)p->n_rounds * p->n_inputs;
+	const uint64_t *t = p->seg_table.empty() ? one : p->seg_table.data();
+	for (size_t s = 0; s < S; s++) {
+		if (seg_first_pick) seg_first_pick[s] = t[4 * s]; if (seg_picks) seg_picks[s] = t[4 * s + 1];
+		if (seg_first_byte) seg_first_byte[s] = t[4 * s + 2]; if (seg_bytes) seg_bytes[s] = t[4 * s + 3];
+	}
+	if (!read_segment || !p->n) return KMR_OK;
+	hipSetDevice(p->device);
+	hipError_t e = hipSuccess;
+	if (p->read_seg) copy_out(e, read_segment, p->read_seg, p->n);
+	else {
+		std::vector<uint8_t> flags(p->n, 0);
+		if (p->picked) copy_out(e, flags.data(), p->picked, p->n);
+		for (uint64_t i = 0; i < p->n; i++) read_segment[i] = flags[i] ? 0 : -1;
+	}
+	return e == hipSuccess ? KMR_OK : KMR_ERR_HIP;
 }
 int kmr_picks_info(const kmr_picks *p, uint64_t *n_picked, uint64_t *bytes) {
 	if (!p) return KMR_ERR_INVALID_ARG;

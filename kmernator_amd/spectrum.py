@@ -834,6 +834,7 @@ class ReadSelector(_DeviceObject):
         self._picks = None
         self._sel = None
         self.picked_flags = np.zeros(n, dtype=bool)
+        self.segments, self.read_segment = None, np.full(n, -1, dtype=np.int32)
 
     @staticmethod
     def _p(a, ct):
@@ -915,6 +916,76 @@ class ReadSelector(_DeviceObject):
         self._adopt(out)
         self._sel, self._fmt = None, (output_quality_base, cfg.format)
         return self._copy()
+
+    SUFFIX = {0: ".fastq", 1: ".fasta"}
+
+    def selectReads(self, min_depth, partition_by_depth=0, remainder_trim=-1.0, min_read_length=None, both_pass=False, scoring="MEDIAN",
+                    output_quality_base=33, format="fastq", input_starts=None, input_prefixes=None, output="", separate_outputs=True):
+        """selectReads (apps/FilterReads.h:159-279) with --max-kmer-output-depth off: the rounds of --partition-by-depth and
+        --remainder-trim over the reads of `input_starts` (n_inputs + 1 ascending read indices; None = one input), on the device
+        (kmr_partition_read_batch, or kmr_partition_reads over the trims scoreAndTrimReads left).  Returns the ordered list of
+        (file name, bytes) the reference writes: with separate_outputs `output` + "-MinDepth<min_depth>" + "-PartitionDepth<depth>"
+        or "-Remainder" (only when partitioned) + "-" + the input's prefix + ".fastq" / ".fasta", round-major and by input inside
+        a round, a file nothing was written to left out (the reference opens a file at its first read); without, one entry named
+        `output` that holds the concatenation.  input_prefixes default to "transformed-<j + 1>", the reference's name for reads
+        that came from no input file (src/ReadSet.cpp:376-382).  .segments and .read_segment hold the tables."""
+        fused = self.trims is None
+        cfg = _lib.KmrPartitionConfig()
+        self.sp.lib.kmr_partition_config_init(C.byref(cfg))
+        cfg.select = self._config(min_depth, min_read_length, both_pass, output_quality_base, format, scoring if fused else self.scoring)
+        cfg.partition_by_depth, cfg.remainder_trim = int(partition_by_depth), float(remainder_trim)
+        starts, n_inputs = None, 0
+        if input_starts is not None:
+            starts = np.ascontiguousarray(input_starts, dtype=np.uint64)
+            n_inputs = starts.size - 1
+        keep, tp, tn = self._text_args()
+        out = C.c_void_p()
+        head = (self.sp.h, self.reads.r, tp, tn, self._p(self.mate, C.c_int64)) + tuple(self._af_args())
+        tail = (self._p(starts, C.c_uint64), n_inputs, C.byref(cfg), C.byref(out))
+        if fused:
+            self.sp._call("partition_read_batch", *head, *tail)
+        else:
+            to, tl, sc, wt = self.trims
+            to = np.ascontiguousarray(to, dtype=np.uint32); tl = np.ascontiguousarray(tl, dtype=np.uint32)
+            sc = np.ascontiguousarray(sc, dtype=np.float32); wt = np.ascontiguousarray(wt, dtype=np.uint8)
+            self.sp._call("partition_reads", *head, self._p(to, C.c_uint32), self._p(tl, C.c_uint32), self._p(sc, C.c_float), self._p(wt, C.c_uint8), *tail)
+        self._adopt(out)
+        self._sel, self._fmt = None, (output_quality_base, cfg.select.format)
+        text = self._copy()
+        seg = self._segments()
+        if not separate_outputs:
+            return [(output, text)]
+        n_rounds, n_inputs = seg["picks"].shape
+        prefixes = list(input_prefixes) if input_prefixes is not None else ["transformed-%d" % (j + 1) for j in range(n_inputs)]
+        if len(prefixes) != n_inputs:
+            raise KmerSpectrumError("selectReads: %d input_prefixes for %d inputs" % (len(prefixes), n_inputs))
+        files = []
+        for r in range(n_rounds):
+            name = "%s-MinDepth%d" % (output, int(min_depth))
+            if partition_by_depth > 0:      # lexical_cast<string>(float tmpMinDepth): 16, not 16.0
+                name += "-Remainder" if seg["round_is_remainder"][r] else ("-PartitionDepth%.9g" % seg["round_depth"][r] if seg["round_depth"][r] > 0 else "")
+            for j in range(n_inputs):
+                if seg["picks"][r, j]:
+                    b0 = int(seg["first_byte"][r, j])
+                    files.append((name + "-" + prefixes[j] + self.SUFFIX[cfg.select.format], text[b0:b0 + int(seg["bytes"][r, j])]))
+        return files
+
+    def _segments(self):
+        """the segment table (kmr_picks_segments_copy) into .segments -- round_depth and round_is_remainder per round, first_pick,
+        picks, first_byte and bytes as (n_rounds, n_inputs) arrays -- and .read_segment: round * n_inputs + input per read, -1 = not
+        picked"""
+        nr, ni = C.c_uint32(), C.c_uint32()
+        _ok(self.sp.lib.kmr_picks_segments_info(self._picks, C.byref(nr), C.byref(ni)), "kmr_picks_segments_info")
+        nr, ni = nr.value, ni.value
+        depth, rem = np.zeros(33, dtype=np.float32), np.zeros(33, dtype=np.uint8)
+        cols = [np.zeros(max(1, nr * ni), dtype=np.uint64) for _ in range(4)]
+        rseg = np.full(max(1, self.reads.n), -1, dtype=np.int32)
+        _ok(self.sp.lib.kmr_picks_segments_copy(self._picks, self._p(depth, C.c_float), self._p(rem, C.c_uint8), *[self._p(c, C.c_uint64) for c in cols],
+                                                self._p(rseg, C.c_int32)), "kmr_picks_segments_copy")
+        self.segments = dict(round_depth=depth[:nr], round_is_remainder=rem[:nr].astype(bool),
+                             **{k: c[:nr * ni].reshape(nr, ni) for k, c in zip(("first_pick", "picks", "first_byte", "bytes"), cols)})
+        self.read_segment = rseg[:self.reads.n]
+        return self.segments
 
     def _copy(self):
         buf = np.zeros(max(1, self.bytes), dtype=np.uint8)
