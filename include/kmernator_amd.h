@@ -929,7 +929,9 @@ int kmr_tune(kmr_handle *h, const char *knob, double value);
  * kmr_finalize took its lists' entries from kmr_count_lists_prefix (0: it counted everything itself) and how many entries those were,
  * "early_overflowed" = 1 if the last kmr_finalize voided an early count because its buffers had overflowed, "saturated_keys" /
  * "saturated_batches" = the weak entries of count 256 or more the last kmr_finalize of build_mode 3 redid in input order (all of them,
- * every time) and in how many batches,
+ * every time) and in how many batches, "bb_path" = how the last kmr_finalize bucketed the weak map (0: per-bucket scatter and sort, 1: radix
+ * partition with measured bins, 2: with bins of one capacity), "bb_fallback" = 1 if a bin overflowed its capacity and the map was made again
+ * with measured bins,
  * "device_blocks_live" = blocks of device memory the library holds at this moment in the whole process (every handle, read batch
  * and artifact filter; not only h's), "filter_score_ms" / "select_ms" / "select_write_ms" = HIP-event times of the last kmr_filter_read_batch* /
  * kmr_select_reads* on this handle: its scoring, its selection with the writer, the writer alone (0 unless kmr_tune "select_timing" is set),

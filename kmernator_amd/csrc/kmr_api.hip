@@ -290,7 +290,7 @@ int add_reads_dev_any(kmr_handle *h, const ReadsView &rv, uint64_t total_bases) 
 
 }  // namespace
 namespace kmr_host {
-int exclusive_scan(kmr_handle *h, const uint32_t *in, uint64_t n, uint64_t *out /* n+1 */) {
+int exclusive_scan_queue(kmr_handle *h, const uint32_t *in, uint64_t n, uint64_t *out /* n+1 */) {
 	const uint64_t nblocks = (n + SCAN_ITEMS - 1) / SCAN_ITEMS;
 	const size_t eb = sizeof(unsigned long long);
 	int rc = h->scan_sums.reserve(h, "scan_sums", eb * (nblocks + 1), eb * std::max<uint64_t>(nblocks + 1, 4096)); if (rc) return rc;
@@ -299,6 +299,10 @@ int exclusive_scan(kmr_handle *h, const uint32_t *in, uint64_t n, uint64_t *out 
 	hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(256), 0, h->stream, sums, nblocks, total);
 	hipLaunchKernelGGL(scan_apply_kernel, dim3((unsigned)nblocks), dim3(256), 0, h->stream, in, n, sums, out);
 	HIPCHK(h, hipGetLastError());
+	return 0;
+}
+int exclusive_scan(kmr_handle *h, const uint32_t *in, uint64_t n, uint64_t *out /* n+1 */) {
+	const int rc = exclusive_scan_queue(h, in, n, out); if (rc) return rc;
 	HIPCHK(h, hipStreamSynchronize(h->stream));
 	return 0;
 }
@@ -846,7 +850,7 @@ int build_csr(kmr_handle *h, HostPool &p, uint64_t nl, uint32_t first, uint64_t 
 	return 0;
 }
 
-int finish_maps_from_entries(kmr_handle *h, uint32_t *wc, uint32_t *sc, uint64_t wslots, uint64_t sslots, uint64_t wn, uint64_t sn, bool keepSing, bool weak_uncounted = false);
+int finish_maps_from_entries(kmr_handle *h, uint32_t *wc, uint32_t *sc, uint64_t wslots, uint64_t sslots, uint64_t wn, uint64_t sn, bool keepSing, bool weak_uncounted = false, bool fixed_bins = false);
 CountOut count_out(kmr_handle *h, bool packed, unsigned long long *cursors, uint32_t *wc, uint32_t *sc, FinalizeCounters *fc);
 
 /* one launch of the count pass over k-mer records: the kernel for (W, EXT, table size, NARROW) with the dynamic LDS it wants;
@@ -1060,10 +1064,20 @@ template <int W, bool EXT> int finalize_partition_t(kmr_handle *h, uint32_t min_
 	return rc;
 }
 
+/* Entries that one of `bins` equal shares of n hashed keys may hold (bins of one capacity, kmr_buckets.hpp): the largest count
+ * below the mean, and above it `scale` times six standard deviations of the binomial share (2^-30 a bin), 1/64 of the mean
+ * for what the hash is short of uniform, and 16.  scale = 0 leaves the bins less than n together: one of them overflows. */
+uint64_t bb_fixed_limit(uint64_t n, uint64_t bins, double scale) {
+	const double mean = (double)n / (double)bins;
+	return (n - 1) / bins + (uint64_t)(std::max(scale, 0.0) * (6.0 * std::sqrt(mean) + mean / 64.0 + 16.0));
+}
+
 /* The weak map out of the count pass's packed entries (h->ue) by the radix partition of kmr_buckets.hpp (COUNT_DIR values).
- * done = false and nothing changed when the geometry does not fit: the caller takes the scatter + per-bucket sort. */
-template <int W> int binned_buckets_t(kmr_handle *h, uint64_t wslots, uint64_t wn, bool &done) {
-	done = false;
+ * done = false and nothing changed when the geometry does not fit: the caller takes the scatter + per-bucket sort.
+ * fixed_bins: bins of one capacity -- everything is left on the stream, h->bb_overflow is the word the caller reads once the
+ * stream is drained (set: the map is void, h->ue overwritten); else, or where the buffers do not fit them, measured bins. */
+template <int W> int binned_buckets_t(kmr_handle *h, uint64_t wslots, uint64_t wn, bool fixed_bins, bool &done) {
+	done = false; h->bb_overflow = nullptr;
 	DevMap &wm = h->weak;
 	const uint64_t nb = wm.nb;
 	uint32_t B = 0; while ((1ull << (B + 1)) <= nb) B++;
@@ -1074,30 +1088,67 @@ template <int W> int binned_buckets_t(kmr_handle *h, uint64_t wslots, uint64_t w
 	const uint32_t bits1 = R <= (uint32_t)BB_MAX_BITS ? R : (R + 1) / 2, bits2 = R - bits1;
 	const uint64_t bins1 = 1ull << bits1, groups = 1ull << R;
 	uint32_t *hist1 = nullptr, *hist2 = nullptr, *pad1 = nullptr; uint64_t *start1 = nullptr, *gstart = nullptr; unsigned long long *cursor = nullptr; unsigned int *dmax = nullptr;
-	int rc = arena_get(h, &hist1, bins1); if (rc) return rc;
-	rc = arena_get(h, &start1, bins1 + 1); if (rc) return rc;
-	rc = arena_get(h, &cursor, groups); if (rc) return rc;
-	rc = arena_get(h, &dmax, 1); if (rc) return rc;
-	if (bits2) { rc = arena_get(h, &hist2, groups); if (rc) return rc; rc = arena_get(h, &pad1, bins1); if (rc) return rc; rc = arena_get(h, &gstart, groups + 1); if (rc) return rc; }
-	HIPCHK(h, hipMemsetAsync(hist1, 0, 4 * bins1, h->stream)); HIPCHK(h, hipMemsetAsync(dmax, 0, 4, h->stream));
-	BbInput in1; in1.entries = h->ue.get<uint64_t>(); in1.seg_start = nullptr; in1.seg_count = nullptr; in1.n_seg = 1; in1.n_slots = wslots; in1.holes = 1;
-	auto hist_grid = [&](uint64_t n_slots, uint32_t &tpb) { const uint64_t tiles = (n_slots + BB_TILE - 1) / BB_TILE; tpb = (uint32_t)std::max<uint64_t>(1, (tiles + 2047) / 2048); return (unsigned)((tiles + tpb - 1) / tpb); };
+	int rc = 0;
+	BbInput in1; in1.entries = h->ue.get<uint64_t>(); in1.seg_start = nullptr; in1.seg_count = nullptr; in1.n_seg = 1; in1.n_slots = wslots; in1.holes = 1; in1.seg_stride = 0;
 	auto scatter_grid = [&](uint64_t n_slots) { const uint64_t tiles = (n_slots + BB_TILE - 1) / BB_TILE; return (unsigned)std::min<uint64_t>(tiles, (uint64_t)num_cus(h) * 8); };
 	auto scratch = [&](uint64_t entries) { return h->ue2.reserve(h, "ue2", 8ull * (W + 1) * entries); };      /* h->ue2: the other side of the partition's ping-pong */
-	auto group_launch = [&](const uint64_t *entries, const uint64_t *gs, const uint32_t *gc) -> int {
+	auto map_arrays = [&]() -> int {
 		int rc2 = wm.keys.reserve(h, "weak map keys", std::max<uint64_t>(8ull * W * wn, 8)); if (rc2) return rc2;
-		rc2 = wm.vals.reserve(h, "weak map vals", std::max<uint64_t>(12ull * wn, 8)); if (rc2) return rc2;
+		return wm.vals.reserve(h, "weak map vals", std::max<uint64_t>(12ull * wn, 8));
+	};
+	/* in_stride, overflow: bins of one capacity (bb_group_kernel) */
+	auto group_launch = [&](const uint64_t *entries, const uint64_t *gs, const uint32_t *gc, uint64_t in_stride, const uint32_t *overflow) -> int {
 		auto gk = bb_group_kernel<W>;
 		HIPCHK(h, hipFuncSetAttribute((const void *)gk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bb_group_smem_bytes<W>()));
 		/* the blocks stride over the groups: as many of them as fit the chip at once, so that they all get the same number of groups */
 		int per_cu = 0;
 		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)gk, BB_GROUP_THREADS, bb_group_smem_bytes<W>()) != hipSuccess || per_cu < 1) per_cu = 4;
 		if (dbg()) fprintf(stderr, "bb_group<W=%d>: %d blocks per CU, %llu groups\n", W, per_cu, (unsigned long long)groups);
-		hipLaunchKernelGGL(gk, dim3((unsigned)std::min<uint64_t>(groups, (uint64_t)num_cus(h) * per_cu)), dim3(BB_GROUP_THREADS), bb_group_smem_bytes<W>(), h->stream, entries, wm.keys.get<uint64_t>(), wm.vals.get<uint32_t>(), gs, gc, groups, g, h->hkb, nb, wm.start.get<uint64_t>(), wn, h->derr.get<uint32_t>());
+		hipLaunchKernelGGL(gk, dim3((unsigned)std::min<uint64_t>(groups, (uint64_t)num_cus(h) * per_cu)), dim3(BB_GROUP_THREADS), bb_group_smem_bytes<W>(), h->stream, entries, wm.keys.get<uint64_t>(), wm.vals.get<uint32_t>(), gs, gc, groups, g, h->hkb, nb, wm.start.get<uint64_t>(), wn, h->derr.get<uint32_t>(), in_stride, overflow);
 		HIPCHK(h, hipGetLastError());
 		return 0;
 	};
-	const uint32_t shift1 = B - bits1;
+	const uint32_t shift1 = B - bits1, shift2 = g;
+	/* bins of one capacity: lim1 entries in a first-level bin of stride1 slots (whole tiles: the second level reads it tile by tile),
+	 * lim2 entries in a group of stride2 slots; the first level writes h->ue2, a second one back into h->ue */
+	const uint64_t lim2 = std::min<uint64_t>(bb_fixed_limit(wn, groups, h->tune.bb_slack_groups), bb_group_cap<W>()), stride2 = std::max<uint64_t>(lim2, 1);
+	const uint64_t lim1 = bits2 ? bb_fixed_limit(wn, bins1, h->tune.bb_slack_bins) : 0, stride1 = std::max<uint64_t>((lim1 + BB_TILE - 1) / BB_TILE, 1) * BB_TILE;
+	if (fixed_bins && lim1 < (1ull << 32) && (!bits2 || groups * stride2 <= packed_entries(h, h->ue))) {
+		uint32_t *fill = nullptr, *overflow = nullptr;      /* fill: [bins1] of the first level, then [groups] of the second when there are two */
+		rc = scratch(bits2 ? bins1 * stride1 : groups * stride2); if (rc) return rc;
+		rc = map_arrays(); if (rc) return rc;
+		rc = arena_get(h, &fill, bits2 ? bins1 + groups : groups); if (rc) return rc;
+		rc = arena_get(h, &gstart, groups + 1); if (rc) return rc;
+		rc = arena_get(h, &overflow, 1); if (rc) return rc;
+		HIPCHK(h, hipMemsetAsync(fill, 0, 4 * (bits2 ? bins1 + groups : groups), h->stream)); HIPCHK(h, hipMemsetAsync(overflow, 0, 4, h->stream));
+		auto scatter = [&](const BbInput &in, uint32_t shift, uint32_t bits, uint32_t *f, uint64_t limit, uint64_t stride, uint64_t *out) {
+			const unsigned grid = scatter_grid(in.n_slots);
+			if (W == 1 && !h->tune.bb_reload) hipLaunchKernelGGL((bb_scatter_fixed_kernel<W, W == 1>), dim3(grid), dim3(BB_THREADS), 0, h->stream, in, shift, bits, h->hkb, nb, f, (uint32_t)limit, stride, out, overflow);
+			else hipLaunchKernelGGL((bb_scatter_fixed_kernel<W, false>), dim3(grid), dim3(BB_THREADS), 0, h->stream, in, shift, bits, h->hkb, nb, f, (uint32_t)limit, stride, out, overflow);
+		};
+		uint32_t *gfill = fill;
+		if (!bits2) scatter(in1, shift1, bits1, fill, lim2, stride2, h->ue2.get<uint64_t>());
+		else {
+			scatter(in1, shift1, bits1, fill, lim1, stride1, h->ue2.get<uint64_t>());
+			BbInput in2; in2.entries = h->ue2.get<uint64_t>(); in2.seg_start = nullptr; in2.seg_count = fill; in2.n_seg = (uint32_t)bins1; in2.n_slots = bins1 * stride1; in2.holes = 0; in2.seg_stride = stride1;
+			gfill = fill + bins1;
+			scatter(in2, shift2, bits2, gfill, lim2, stride2, h->ue.get<uint64_t>());
+		}
+		HIPCHK(h, hipGetLastError());
+		/* the map is dense: a group's entries go where the groups before it end */
+		rc = exclusive_scan_queue(h, gfill, groups, gstart); if (rc) return rc;
+		rc = group_launch(bits2 ? h->ue.get<uint64_t>() : h->ue2.get<uint64_t>(), gstart, gfill, stride2, overflow); if (rc) return rc;
+		h->bb_overflow = overflow; h->last_bb_path = 2;
+		done = true;
+		return 0;
+	}
+	rc = arena_get(h, &hist1, bins1); if (rc) return rc;
+	rc = arena_get(h, &start1, bins1 + 1); if (rc) return rc;
+	rc = arena_get(h, &cursor, groups); if (rc) return rc;
+	rc = arena_get(h, &dmax, 1); if (rc) return rc;
+	if (bits2) { rc = arena_get(h, &hist2, groups); if (rc) return rc; rc = arena_get(h, &pad1, bins1); if (rc) return rc; rc = arena_get(h, &gstart, groups + 1); if (rc) return rc; }
+	HIPCHK(h, hipMemsetAsync(hist1, 0, 4 * bins1, h->stream)); HIPCHK(h, hipMemsetAsync(dmax, 0, 4, h->stream));
+	auto hist_grid = [&](uint64_t n_slots, uint32_t &tpb) { const uint64_t tiles = (n_slots + BB_TILE - 1) / BB_TILE; tpb = (uint32_t)std::max<uint64_t>(1, (tiles + 2047) / 2048); return (unsigned)((tiles + tpb - 1) / tpb); };
 	uint32_t tpb = 1; unsigned grid = hist_grid(wslots, tpb);
 	hipLaunchKernelGGL(bb_hist_kernel<W>, dim3(grid), dim3(BB_THREADS), 0, h->stream, in1, shift1, bits1, h->hkb, nb, tpb, hist1);
 	unsigned int mx = 0;
@@ -1110,7 +1161,9 @@ template <int W> int binned_buckets_t(kmr_handle *h, uint64_t wslots, uint64_t w
 		rc = scratch(wn); if (rc) return rc;
 		hipLaunchKernelGGL(bb_cursor_init_kernel, dim3(grid_for(bins1)), dim3(256), 0, h->stream, (const uint64_t *)start1, bins1, cursor);
 		hipLaunchKernelGGL(bb_scatter_kernel<W>, dim3(scatter_grid(wslots)), dim3(BB_THREADS), 0, h->stream, in1, shift1, bits1, h->hkb, nb, cursor, h->ue2.get<uint64_t>());
-		rc = group_launch(h->ue2.get<uint64_t>(), start1, hist1); if (rc) return rc;
+		rc = map_arrays(); if (rc) return rc;
+		rc = group_launch(h->ue2.get<uint64_t>(), start1, hist1, 0, nullptr); if (rc) return rc;
+		h->last_bb_path = 1;
 		done = true;
 		return 0;
 	}
@@ -1122,8 +1175,7 @@ template <int W> int binned_buckets_t(kmr_handle *h, uint64_t wslots, uint64_t w
 	rc = scratch(std::max(padded_total, wn)); if (rc) return rc;
 	hipLaunchKernelGGL(bb_cursor_init_kernel, dim3(grid_for(bins1)), dim3(256), 0, h->stream, (const uint64_t *)start1, bins1, cursor);
 	hipLaunchKernelGGL(bb_scatter_kernel<W>, dim3(scatter_grid(wslots)), dim3(BB_THREADS), 0, h->stream, in1, shift1, bits1, h->hkb, nb, cursor, h->ue2.get<uint64_t>());
-	BbInput in2; in2.entries = h->ue2.get<uint64_t>(); in2.seg_start = start1; in2.seg_count = hist1; in2.n_seg = (uint32_t)bins1; in2.n_slots = padded_total; in2.holes = 0;
-	const uint32_t shift2 = g;
+	BbInput in2; in2.entries = h->ue2.get<uint64_t>(); in2.seg_start = start1; in2.seg_count = hist1; in2.n_seg = (uint32_t)bins1; in2.n_slots = padded_total; in2.holes = 0; in2.seg_stride = 0;
 	HIPCHK(h, hipMemsetAsync(hist2, 0, 4 * groups, h->stream)); HIPCHK(h, hipMemsetAsync(dmax, 0, 4, h->stream));
 	grid = hist_grid(padded_total, tpb);
 	hipLaunchKernelGGL(bb_hist_kernel<W>, dim3(grid), dim3(BB_THREADS), 0, h->stream, in2, shift2, bits2, h->hkb, nb, tpb, hist2);
@@ -1135,14 +1187,16 @@ template <int W> int binned_buckets_t(kmr_handle *h, uint64_t wslots, uint64_t w
 	if (mx > bb_group_cap<W>() || packed_entries(h, h->ue) < wn) return 0;
 	hipLaunchKernelGGL(bb_cursor_init_kernel, dim3(grid_for(groups)), dim3(256), 0, h->stream, (const uint64_t *)gstart, groups, cursor);
 	hipLaunchKernelGGL(bb_scatter_kernel<W>, dim3(scatter_grid(padded_total)), dim3(BB_THREADS), 0, h->stream, in2, shift2, bits2, h->hkb, nb, cursor, h->ue.get<uint64_t>());
-	rc = group_launch(h->ue.get<uint64_t>(), gstart, hist2); if (rc) return rc;
+	rc = map_arrays(); if (rc) return rc;
+	rc = group_launch(h->ue.get<uint64_t>(), gstart, hist2, 0, nullptr); if (rc) return rc;
+	h->last_bb_path = 1;
 	done = true;
 	return 0;
 }
 
 /* weak_uncounted: the count pass kept no per-bucket counts of the weak entries (wc is scratch): the radix partition of
  * kmr_buckets.hpp needs none, and if it declines they are counted here */
-template <int W> int finish_maps_t(kmr_handle *h, uint32_t *wc, uint32_t *sc, uint64_t wslots, uint64_t sslots, uint64_t wn, uint64_t sn, bool keepSing, bool weak_uncounted) {
+template <int W> int finish_maps_t(kmr_handle *h, uint32_t *wc, uint32_t *sc, uint64_t wslots, uint64_t sslots, uint64_t wn, uint64_t sn, bool keepSing, bool weak_uncounted, bool fixed_bins) {
 	const uint32_t vw = h->ext ? 15 : 3;
 	DevMap &wm = h->weak, &sm = h->sing;
 	clear_map(wm); clear_map(sm);          /* the buffers of the previous build are reused when they are large enough */
@@ -1151,8 +1205,9 @@ template <int W> int finish_maps_t(kmr_handle *h, uint32_t *wc, uint32_t *sc, ui
 	int rc = wm.start.reserve(h, "weak map start", 8 * (wm.nb + 1)); if (rc) return rc;
 	rc = sm.start.reserve(h, "singleton map start", 8 * (sm.nb + 1)); if (rc) return rc;
 	bool weakDone = false;
+	h->last_bb_path = 0; h->bb_overflow = nullptr;
 	if (weak_uncounted) {
-		rc = binned_buckets_t<W>(h, wslots, wn, weakDone); if (rc) return rc;
+		rc = binned_buckets_t<W>(h, wslots, wn, fixed_bins, weakDone); if (rc) return rc;
 		if (!weakDone) {      /* the other path wants keys and values apart and a count per bucket */
 			if (key_entries(h, h->uw_keys) < wslots || !h->uw_vals) {
 				h->uw_keys.reset(); h->uw_vals.reset();
@@ -1165,7 +1220,7 @@ template <int W> int finish_maps_t(kmr_handle *h, uint32_t *wc, uint32_t *sc, ui
 		}
 	}
 	if (!weakDone) { rc = exclusive_scan(h, wc, wm.nb, wm.start.get<uint64_t>()); if (rc) return rc; }
-	if (keepSing) { rc = exclusive_scan(h, sc, sm.nb, sm.start.get<uint64_t>()); if (rc) return rc; }
+	if (keepSing) { rc = h->bb_overflow ? exclusive_scan_queue(h, sc, sm.nb, sm.start.get<uint64_t>()) : exclusive_scan(h, sc, sm.nb, sm.start.get<uint64_t>()); if (rc) return rc; }      /* (bins of one capacity: nothing waits here either) */
 	else HIPCHK(h, hipMemsetAsync(sm.start.get<uint64_t>(), 0, 8 * (sm.nb + 1), h->stream));      /* no singleton map is kept: every bucket starts (and ends) at 0 */
 	if (!weakDone) {
 		rc = wm.keys.reserve(h, "weak map keys", std::max<uint64_t>(8ull * W * wm.n, 8)); if (rc) return rc;
@@ -1199,11 +1254,11 @@ template <int W> int finish_maps_t(kmr_handle *h, uint32_t *wc, uint32_t *sc, ui
 		hipLaunchKernelGGL((sort_buckets_kernel<W, 0>), dim3(grid_for(sm.nb, 4, 1 << 20)), dim3(256), 0, h->stream, ss, sm.start.get<uint64_t>(), sm.nb);
 	}
 	HIPCHK(h, hipGetLastError());
-	HIPCHK(h, hipStreamSynchronize(h->stream));
+	if (!h->bb_overflow) HIPCHK(h, hipStreamSynchronize(h->stream));      /* (bins of one capacity: the caller waits once, for the overflow word) */
 	return 0;
 }
-int finish_maps_from_entries(kmr_handle *h, uint32_t *wc, uint32_t *sc, uint64_t wslots, uint64_t sslots, uint64_t wn, uint64_t sn, bool keepSing, bool weak_uncounted) {
-	return with_w(h, [&](auto W) { return finish_maps_t<W()>(h, wc, sc, wslots, sslots, wn, sn, keepSing, weak_uncounted); });
+int finish_maps_from_entries(kmr_handle *h, uint32_t *wc, uint32_t *sc, uint64_t wslots, uint64_t sslots, uint64_t wn, uint64_t sn, bool keepSing, bool weak_uncounted, bool fixed_bins) {
+	return with_w(h, [&](auto W) { return finish_maps_t<W()>(h, wc, sc, wslots, sslots, wn, sn, keepSing, weak_uncounted, fixed_bins); });
 }
 int finalize_partition(kmr_handle *h, uint32_t min_depth) { return with_w_ext(h, [&](auto W, auto EXT) { return finalize_partition_t<W(), EXT()>(h, min_depth); }); }
 template <int W, bool EXT> int insert_records_partition_t(kmr_handle *h, const void *recs, uint64_t n) {
@@ -1879,9 +1934,29 @@ template <int W> int finalize_superkmer_t(kmr_handle *h, uint32_t min_depth) {
 	if (p.early_slots) { rc = sk_append_early<W>(h, p); if (rc) return rc; }
 	h->early.active = false;
 	hipEvent_t tma, tmb; time_begin(h, KMR_TIME_BUCKETS, &tma, &tmb);
-	rc = finish_maps_from_entries(h, p.wc, p.sc, p.cur[0], p.cur[1], p.c.weak_kept, p.c.sing_kept, p.keepSing, !p.ext);
+	rc = finish_maps_from_entries(h, p.wc, p.sc, p.cur[0], p.cur[1], p.c.weak_kept, p.c.sing_kept, p.keepSing, !p.ext, h->tune.bb_fixed_bins);
 	time_end(h, KMR_TIME_BUCKETS, tma, tmb);
 	if (rc) return rc;
+	h->last_bb_fallback = false;
+	if (h->bb_overflow) {
+		/* bins of one capacity: the partition and the group kernel are on the stream, this is where the host waits for them.  A bin or
+		 * group that was fuller than its capacity voids the map, and the packed entries may be overwritten: the lists are counted
+		 * again and bucketed with measured bins */
+		uint32_t ovf = 0;
+		HIPCHK(h, hipMemcpyAsync(&ovf, h->bb_overflow, 4, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
+		h->bb_overflow = nullptr;
+		if (ovf) {
+			if (dbg()) fprintf(stderr, "bucket build: a bin of the radix partition overflowed its capacity, again with measured bins\n");
+			h->last_bb_fallback = true;
+			rc = sk_count_pass<W>(h, p, overflowed); if (rc) return rc;
+			if (overflowed) { time_end(h, 1, ea, eb); return fail(h, KMR_ERR_CAPACITY, "entry buffers of the count pass overflowed at their upper bound (internal sizing error)"); }
+			if (p.early_slots) { rc = sk_append_early<W>(h, p); if (rc) return rc; }
+			time_begin(h, KMR_TIME_BUCKETS, &tma, &tmb);
+			rc = finish_maps_from_entries(h, p.wc, p.sc, p.cur[0], p.cur[1], p.c.weak_kept, p.c.sing_kept, p.keepSing, !p.ext, false);
+			time_end(h, KMR_TIME_BUCKETS, tma, tmb);
+			if (rc) return rc;
+		}
+	}
 	h->last_saturated_keys = 0; h->last_saturated_batches = 0;
 	if (p.c.saturated) { rc = saturated_fix_t<W>(h, p.ls, p.lc, p.nl, p.c.saturated, p.c.sat_sightings, p.f.has_singletons); if (rc) return rc; }
 	time_end(h, 1, ea, eb);
@@ -2163,6 +2238,10 @@ int kmr_tune(kmr_handle *h, const char *knob, double value) {
 	else if (k == "twobit_piece_bases") h->tune.twobit_piece_bases = (uint64_t)value;
 	else if (k == "exchange_fail_once") h->tune.exchange_fail_once = value != 0;
 	else if (k == "binned_buckets_min") h->tune.binned_min = value >= 0 ? (uint64_t)value : ~0ull;        /* < 0: never */
+	else if (k == "bb_fixed_bins") h->tune.bb_fixed_bins = value != 0;
+	else if (k == "bb_slack_bins") h->tune.bb_slack_bins = value;
+	else if (k == "bb_slack_groups") h->tune.bb_slack_groups = value;
+	else if (k == "bb_reload") h->tune.bb_reload = value != 0;
 	else if (k == "coarse_lists") h->tune.no_coarse_lists = value == 0;
 	else if (k == "select_timing") h->tune.select_timing = value != 0;
 	else if (k == "dump_timing") h->tune.dump_timing = value != 0;
@@ -2193,6 +2272,8 @@ int kmr_build_info(kmr_handle *h, const char *what, double *value) {
 	else if (k == "early_lists") *value = (double)h->last_early_hi;
 	else if (k == "early_entries") *value = (double)h->last_early_entries;
 	else if (k == "early_overflowed") *value = h->last_early_overflowed ? 1.0 : 0.0;
+	else if (k == "bb_path") *value = (double)h->last_bb_path;
+	else if (k == "bb_fallback") *value = h->last_bb_fallback ? 1.0 : 0.0;
 	else if (k == "saturated_keys") *value = (double)h->last_saturated_keys;
 	else if (k == "saturated_batches") *value = (double)h->last_saturated_batches;
 	else if (k == "device_blocks_live") *value = (double)g_blocks_live.load();

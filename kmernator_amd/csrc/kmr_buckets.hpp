@@ -6,17 +6,28 @@
  * segments wrote one random 20-byte entry at a time (9 GB written for 1.16 GB of entries at C2).  Here the entries reach their
  * buckets by an MSD radix partition over the bucket index instead:
  *
- *   bb_hist_kernel      histogram of the level's bins (top bits of the bucket index below the bits already resolved)
- *   bb_scatter_kernel   a tile of 4096 entries is ranked inside LDS, one device atomic per (tile, bin) reserves the run, the
+ *   bb_scatter_*kernel  a tile of 8192 entries is ranked inside LDS, one device atomic per (tile, bin) reserves the run, the
  *                       entries of a bin leave the tile as one contiguous run
  *   (one or two such levels, <= 10 bits each, until a GROUP of 2^g neighbouring buckets holds ~512-1024 entries)
  *   bb_group_kernel     one block per group: the group's entries in LDS, counting sort by bucket, rank sort by key inside
  *                       every bucket (KmerMapByKmerArrayPair::resort order, src/Kmer.h:3079-3088), coalesced store of keys
  *                       and values at their final places and of the buckets' start offsets
  *
- * The last level's bins are the groups and their exclusive scan is the final position of every group, so the group kernel
- * sorts in place.  Values: COUNT_DIR (three words) only; anything this geometry does not fit (a group that overflows the LDS
- * arrays, more than two levels) takes the scatter + per-bucket sort it replaces (entry_scatter_kernel, sort_buckets_kernel).
+ * Where the bins lie.  The bins are slices of a lookup3 hash over distinct keys, so a bin of n / bins entries on average holds that
+ * many give or take a few sqrt(n / bins), and the host knows n before the partition starts.  The default therefore measures
+ * nothing: every bin of a level gets the same capacity (bb_fixed_limit: the mean, six standard deviations, 1/64 of the mean),
+ * bin b starts at b * stride, and how many entries it holds is what its cursor says after the scatter
+ * (bb_scatter_fixed_kernel).  The last level's bins are the groups; the exclusive scan of their counts, made on the device, is
+ * where bb_group_kernel writes a group, which it reads at G * stride.  Nothing between the count pass and the end of the group
+ * kernel waits for the host.  A run that would pass its bin's capacity is not stored and raises an overflow word instead; the
+ * next level and the group kernel begin by reading that word and do nothing when it is set, and the host, which reads it when
+ * the stream is drained at the end of the build, then counts again and takes the other way:
+ *
+ *   bb_hist_kernel + bb_pad_kernel + exclusive_scan (on the host's clock) in front of every level's bb_scatter_kernel: the
+ *   histogram of the level's bins, whose scan is where they start (kmr_tune "bb_fixed_bins" = 0 selects it outright)
+ *
+ * Values: COUNT_DIR (three words) only; anything this geometry does not fit (a group that overflows the LDS arrays, more
+ * than two levels) takes the scatter + per-bucket sort it replaces (entry_scatter_kernel, sort_buckets_kernel).
  */
 #ifndef KMR_BUCKETS_HPP_
 #define KMR_BUCKETS_HPP_
@@ -54,6 +65,7 @@ struct BbInput {
 	uint32_t n_seg;
 	uint64_t n_slots;                                /* slots in all (tiles = ceil(n_slots / BB_TILE))                                  */
 	uint32_t holes;                                  /* 1: a slot whose value word is zero is a hole                                     */
+	uint64_t seg_stride;                             /* != 0: bins of one capacity -- segment s starts at s * seg_stride (a multiple of BB_TILE), seg_start is null */
 };
 
 template <int W> __device__ __forceinline__ void bb_load_entry(const uint64_t *entries, uint64_t e, uint64_t (&w)[W + 1]) {
@@ -188,17 +200,87 @@ void bb_scatter_kernel(BbInput in, uint32_t shift, uint32_t bits, uint32_t kb, u
 	}
 }
 
+/* The same with bins of one capacity and no histogram before it: bin b of segment s is the `stride` slots of out_entries at
+ * ((s << bits) + b) * stride, fill[(s << bits) + b] counts what it holds (zero before the launch).  A run that would take its bin
+ * past `limit` (<= stride) entries is not stored and sets *overflow; a launch that finds *overflow set does nothing.
+ * KEEP: the entries of a thread stay in registers between the two sweeps (64 registers at W = 1) instead of being read again. */
+template <int W, bool KEEP>
+__global__ __launch_bounds__(BB_THREADS)
+void bb_scatter_fixed_kernel(BbInput in, uint32_t shift, uint32_t bits, uint32_t kb, uint64_t nb, uint32_t *fill, uint32_t limit, uint64_t stride, uint64_t *out_entries, uint32_t *overflow) {
+	__shared__ uint32_t lh[1 << BB_MAX_BITS];
+	__shared__ unsigned long long lbase[1 << BB_MAX_BITS];
+	/* the word may be raised by another block of this very launch: the block decides as one (a block that goes on while the word is
+	 * set stores nothing past a bin either, its own reservations are checked below) */
+	if (__syncthreads_or((int)*overflow)) return;
+	const int t = threadIdx.x;
+	const uint32_t bins = 1u << bits, mask = bins - 1;
+	const uint64_t n_tiles = (in.n_slots + BB_TILE - 1) / BB_TILE;
+	for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+		const uint64_t s0 = tile * BB_TILE;
+		const uint64_t seg = in.seg_stride ? s0 / in.seg_stride : 0;
+		const uint64_t segEnd = in.seg_stride ? seg * in.seg_stride + (in.seg_count[seg] < in.seg_stride ? in.seg_count[seg] : in.seg_stride) : in.n_slots;
+		if (s0 >= segEnd) continue;          /* (the unused tail of a bin; the same for every thread of the block) */
+		__syncthreads();
+		for (uint32_t i = t; i < bins; i += BB_THREADS) lh[i] = 0;
+		__syncthreads();
+		uint32_t where[BB_PER_THREAD];          /* bin << 16 | rank inside the tile's share of the bin; ~0: no entry */
+		uint64_t kept[KEEP ? BB_PER_THREAD : 1][W + 1];
+#pragma unroll
+		for (int i = 0; i < BB_PER_THREAD; i++) {
+			const uint64_t e = s0 + (uint64_t)i * BB_THREADS + t;
+			where[i] = 0xffffffffu;
+			if (e >= segEnd) continue;
+			uint64_t ew[W + 1];
+			bb_load_entry<W>(in.entries, e, ew);
+			if (in.holes && ew[W] == 0) continue;
+			Key<W> key;
+#pragma unroll
+			for (int q = 0; q < W; q++) key.w[q] = ew[q];
+			const uint32_t bin = (uint32_t)((key_hash<W>(key, kb) & (nb - 1)) >> shift) & mask;
+			where[i] = (bin << 16) | atomicAdd(&lh[bin], 1u);
+			if constexpr (KEEP) {
+#pragma unroll
+				for (int q = 0; q <= W; q++) kept[i][q] = ew[q];
+			}
+		}
+		__syncthreads();
+		for (uint32_t i = t; i < bins; i += BB_THREADS) {
+			const uint32_t c = lh[i];
+			if (!c) continue;
+			const uint64_t b = (seg << bits) + i;
+			const uint32_t r = atomicAdd(&fill[b], c);
+			if ((uint64_t)r + c > limit) { atomicOr(overflow, 1u); lbase[i] = ~0ull; }
+			else lbase[i] = b * stride + r;
+		}
+		__syncthreads();
+#pragma unroll
+		for (int i = 0; i < BB_PER_THREAD; i++) {
+			if (where[i] == 0xffffffffu) continue;
+			const unsigned long long base = lbase[where[i] >> 16];
+			if (base == ~0ull) continue;
+			if constexpr (KEEP) bb_store_entry<W>(out_entries, base + (where[i] & 0xffffu), kept[i]);
+			else {
+				uint64_t ew[W + 1];
+				bb_load_entry<W>(in.entries, s0 + (uint64_t)i * BB_THREADS + t, ew);
+				bb_store_entry<W>(out_entries, base + (where[i] & 0xffffu), ew);
+			}
+		}
+	}
+}
+
 static const int BB_GROUP_PER_THREAD = (BB_GROUP_CAP + BB_GROUP_THREADS - 1) / BB_GROUP_THREADS;
 template <int W> __host__ __device__ constexpr size_t bb_group_smem_bytes() { return (size_t)bb_group_cap<W>() * (8 * W + 8 + 2 + 2); }
 
-/* One block per group of 2^gbits neighbouring buckets: its entries lie at [gstart[G], gstart[G] + gcount[G]) of `entries` and go
- * to the same range of the map's key and value arrays, in (bucket, key) order.  A thread keeps its (up to six) entries in
+/* One block per group of 2^gbits neighbouring buckets: its gcount[G] entries go to [gstart[G], gstart[G] + gcount[G]) of the map's
+ * key and value arrays, in (bucket, key) order, and lie at the same place of `entries` (in_stride = 0) or, out of bins of one
+ * capacity, at G * in_stride; a launch that finds *overflow set (overflow may be null) does nothing.  A thread keeps its (up to six) entries in
  * registers while the buckets are counted and scanned, then files them into LDS bucket by bucket, so that the rank loop of an
  * entry walks the consecutive keys of its bucket (independent LDS reads, no index in between). */
 template <int W>
 __global__ __launch_bounds__(BB_GROUP_THREADS, W <= 2 ? 4 : 1)      /* (W = 2: 130 registers without the bound, three blocks per CU) */
 void bb_group_kernel(const uint64_t *entries, uint64_t *keys, uint32_t *vals, const uint64_t *gstart, const uint32_t *gcount, uint64_t n_groups, uint32_t gbits, uint32_t kb, uint64_t nb,
-                     uint64_t *start, uint64_t n_total, uint32_t *err) {
+                     uint64_t *start, uint64_t n_total, uint32_t *err, uint64_t in_stride, const uint32_t *overflow) {
+	if (overflow && *overflow) return;
 	extern __shared__ __attribute__((aligned(16))) uint8_t gsm[];
 	uint64_t *skeys = (uint64_t *)gsm;                                   /* [CAP][W] keys, grouped by bucket */
 	constexpr uint32_t CAP = bb_group_cap<W>();
@@ -209,18 +291,18 @@ void bb_group_kernel(const uint64_t *entries, uint64_t *keys, uint32_t *vals, co
 	const int t = threadIdx.x;
 	const uint32_t nbk = 1u << gbits;
 	for (uint64_t G = blockIdx.x; G < n_groups; G += gridDim.x) {
-		const uint64_t base = gstart[G];
+		const uint64_t base = gstart[G], in_base = in_stride ? G * in_stride : base;
 		const uint32_t n = gcount[G];
 		__syncthreads();
 		if ((uint32_t)t < nbk) bcnt[t] = 0;
-		if (n > CAP) { if (t == 0) atomicOr(err, (uint32_t)ERR_ENTRIES_FULL); continue; }      /* (the host looked at the largest group before the launch) */
+		if (n > CAP) { if (t == 0) atomicOr(err, (uint32_t)ERR_ENTRIES_FULL); continue; }      /* (never here: measured bins, the host looked at the largest group before the launch; bins of one capacity, the scatter's limit is <= CAP) */
 		__syncthreads();
 		uint64_t ew[BB_GROUP_PER_THREAD][W + 1]; uint32_t lb[BB_GROUP_PER_THREAD];
 #pragma unroll
 		for (int u = 0; u < BB_GROUP_PER_THREAD; u++) {
 			const uint32_t i = (uint32_t)u * BB_GROUP_THREADS + t;
 			lb[u] = 0xffffffffu;
-			if (i < n) bb_load_entry<W>(entries, base + i, ew[u]);
+			if (i < n) bb_load_entry<W>(entries, in_base + i, ew[u]);
 		}
 #pragma unroll
 		for (int u = 0; u < BB_GROUP_PER_THREAD; u++) {

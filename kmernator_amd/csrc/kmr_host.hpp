@@ -166,6 +166,9 @@ struct KMR_HIDDEN Tuning {
 	bool no_lut = false, no_narrow = false, no_l1_state = false, no_stream_lookups = false;
 	uint64_t long_list_chunks = 0;     /* lists of more chunks are counted in pieces (0: 1024) */
 	uint64_t binned_min = 1ull << 18;  /* weak maps of at least this many entries are bucketed by the radix partition of kmr_buckets.hpp (build_mode 3) */
+	bool bb_fixed_bins = true;         /* the radix partition gives every bin of a level one capacity instead of measuring the bins (0: histogram, pad and scan before every level; A/B runs, and the way a build takes when a bin overflows) */
+	double bb_slack_bins = 1.0, bb_slack_groups = 1.0;      /* scale of the room above the mean in a first-level bin / in a group (bb_fixed_limit); tests: 0 leaves less than the mean, so that the level overflows */
+	bool bb_reload = false;            /* bb_scatter_fixed_kernel reads a tile's entries a second time instead of keeping them in registers (A/B runs) */
 	uint64_t twobit_piece_bases = 0;   /* kmr_add_reads_twobit: bases per piece of the host-to-device pipeline (0 = 2^26) */
 	uint64_t list_aim = 0;             /* k-mers per list the list count of a single GPU's build aims for (0: the defaults of add_reads_superkmer_t) */
 	bool pow2_lists = false;           /* the list count of build_mode 3 always a power of two (A/B runs, tests of both list functions) */
@@ -232,6 +235,9 @@ struct KMR_HIDDEN kmr_handle : HandleMem, BuildMem, ExchangeMem {
 	uint32_t peer_uni_w = 0xffffffffu; bool peer_uni_mixed = false, peers_declare = false;
 	uint64_t xr_lo = 0, xr_hi = ~0ull;      /* kmr_sk_exchange_range */
 	uint64_t last_early_hi = 0, last_early_entries = 0;      /* what the last kmr_finalize took over from an early count (kmr_build_info) */
+	/* the radix partition of the last kmr_finalize (kmr_build_info "bb_path": 0 none, 1 measured bins, 2 bins of one capacity; "bb_fallback": a bin
+	 * overflowed and the build was made again with measured bins), and the overflow word of one that is on the stream (null: none) */
+	int last_bb_path = 0; bool last_bb_fallback = false; uint32_t *bb_overflow = nullptr;
 	bool last_early_overflowed = false;                       /* ... or that it voided one because its buffers overflowed */
 	double last_score_ms = 0, last_select_ms = 0, last_write_ms = 0;      /* the last kmr_filter_read_batch* / kmr_select_reads*: scoring, selection + writer, writer alone (HIP events, taken with kmr_tune "select_timing" only; kmr_build_info) */
 	double last_dump_size_ms = 0, last_dump_write_ms = 0;      /* the last kmr_dump_text_size / kmr_dump_text: size pass with its scan, writer (HIP events, taken with kmr_tune "dump_timing" only; kmr_build_info) */
@@ -356,6 +362,7 @@ template <int N> struct EventTimer {
 uint64_t resize_buckets(uint64_t n);
 void quality_table(double P[256], unsigned minQ, unsigned startChar);
 int exclusive_scan(kmr_handle *h, const uint32_t *in, uint64_t n, uint64_t *out /* n+1 */);
+int exclusive_scan_queue(kmr_handle *h, const uint32_t *in, uint64_t n, uint64_t *out /* n+1 */);      /* the same left on the handle's stream: the host does not wait */
 int num_cus(kmr_handle *h);
 struct ScoreDev { uint32_t *trim_offset, *trim_length; float *score; uint8_t *was_trimmed; };      /* the results in score_buf, good until the handle's next scoring call */
 int score_reads_core(kmr_handle *h, const uint8_t *s_b, const uint64_t *s_o, uint64_t n_reads, double minimum_kmer_score, int scoring_type,
