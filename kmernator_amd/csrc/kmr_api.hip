@@ -1297,32 +1297,26 @@ bool sk_geometry(uint32_t k, uint32_t m_wish, uint32_t &win, uint32_t &m, uint32
 	return false;
 }
 const uint64_t SK_EXTRACT_WAVES_PER_CU = std::max(2 * SK_WAVES, SKL_MIN_BLOCKS * SKL_WAVES);      /* wavefronts an extraction launch keeps per CU (each holds two slabs of 64 chunks) */
-template <int W, int WIN, bool FILT, bool EXT = false> int launch_sk_extract(kmr_handle *h, const ReadsView &rv, const SkParams &sp, const DevParams *override_params = nullptr) {
-	auto kern = sk_extract_kernel<W, WIN, FILT, EXT>;
-	HIPCHK(h, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SK_EXTRACT_SMEM));
+/* One extraction launch: a wavefront per tile of 64 reads (or units), `waves` of them a block, and no more blocks than are resident
+ * at per_cu a CU -- a wavefront walks tiles tile0, tile0 + stride, ...; args: what the kernel takes behind the reads */
+template <typename... P, typename... A> int launch_sk_tiles(kmr_handle *h, void (*kern)(ReadsView, P...), const char *name, int w, int win, int waves, int per_cu, size_t smem, const ReadsView &rv, const SkParams &sp, A... args) {
+	HIPCHK(h, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
 	const uint64_t tiles = ((rv.u_start ? rv.n_units : rv.n_reads) + 63) / 64;
-	uint64_t blocks = (tiles + SK_WAVES - 1) / SK_WAVES;
+	uint64_t blocks = (tiles + waves - 1) / waves;
 	if (blocks == 0) return 0;
-	blocks = std::min<uint64_t>(blocks, (uint64_t)num_cus(h) * 2);      /* resident grid: a wavefront walks tiles tile0, tile0 + stride, ... */
-	if (dbg()) { int nb = 0; hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)kern, SK_WAVES * 64, SK_EXTRACT_SMEM); fprintf(stderr, "sk_extract<W=%d,WIN=%d>: %d blocks of %d waves per CU (LDS %zu), grid %llu, m=%u off=%u bits=%u\n", W, WIN, nb, SK_WAVES, SK_EXTRACT_SMEM, (unsigned long long)blocks, sp.m, sp.off, sp.list_bits); }
-	hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(SK_WAVES * 64), SK_EXTRACT_SMEM, h->stream, rv, override_params ? *override_params : dev_params(h), sp, pool_view(h, h->l1));
+	blocks = std::min<uint64_t>(blocks, (uint64_t)num_cus(h) * per_cu);
+	if (dbg()) { int nb = 0; hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)kern, waves * 64, smem); fprintf(stderr, "%s<W=%d,WIN=%d>: %d blocks of %d waves per CU (LDS %zu), grid %llu, m=%u off=%u bits=%u\n", name, w, win, nb, waves, smem, (unsigned long long)blocks, sp.m, sp.off, sp.list_bits); }
+	hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(waves * 64), smem, h->stream, rv, args...);
 	HIPCHK(h, hipGetLastError());
 	return 0;
+}
+template <int W, int WIN, bool FILT, bool EXT = false> int launch_sk_extract(kmr_handle *h, const ReadsView &rv, const SkParams &sp, const DevParams *override_params = nullptr) {
+	return launch_sk_tiles(h, sk_extract_kernel<W, WIN, FILT, EXT>, "sk_extract", W, WIN, SK_WAVES, 2, SK_EXTRACT_SMEM, rv, sp, override_params ? *override_params : dev_params(h), sp, pool_view(h, h->l1));
 }
 uint32_t sk_dbg_flags(const char *name);
 bool sp_debug_extract(kmr_handle *h) { (void)h; return sk_dbg_flags("KMR_SK_EXTRACT_DBG") != 0; }      /* the ablation switches live in the general kernel */
 template <int W, int WIN, bool PACKED = false> int launch_sk_extract_lean(kmr_handle *h, const ReadsView &rv, const SkParams &sp, float wK, const DevParams *override_params = nullptr, const SkPacked *packed = nullptr) {
-	auto kern = sk_extract_lean_kernel<W, WIN, PACKED>;
-	SkPacked pkd{};
-	if (PACKED) pkd = *packed;
-	HIPCHK(h, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SKL_EXTRACT_SMEM));
-	const uint64_t tiles = ((rv.u_start ? rv.n_units : rv.n_reads) + 63) / 64;
-	uint64_t blocks = (tiles + SKL_WAVES - 1) / SKL_WAVES;
-	if (blocks == 0) return 0;
-	blocks = std::min<uint64_t>(blocks, (uint64_t)num_cus(h) * SKL_MIN_BLOCKS);      /* resident grid: a wavefront walks tiles tile0, tile0 + stride, ... */
-	hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(SKL_WAVES * 64), SKL_EXTRACT_SMEM, h->stream, rv, override_params ? *override_params : dev_params(h), sp, pool_view(h, h->l1), wK, pkd);
-	HIPCHK(h, hipGetLastError());
-	return 0;
+	return launch_sk_tiles(h, sk_extract_lean_kernel<W, WIN, PACKED>, "sk_extract_lean", W, WIN, SKL_WAVES, SKL_MIN_BLOCKS, SKL_EXTRACT_SMEM, rv, sp, override_params ? *override_params : dev_params(h), sp, pool_view(h, h->l1), wK, PACKED ? *packed : SkPacked{});
 }
 /* Do all k-mers without an N of these reads weigh the same (no qualities, or one quality character throughout)?  Then wK is that
  * weight as the general kernel would form it -- (float) of the k-fold product of the character's probability, 1 for REF_QUAL --

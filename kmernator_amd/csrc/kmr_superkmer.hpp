@@ -154,6 +154,17 @@ __device__ __forceinline__ uint32_t sk_hdr_ext(uint32_t left, uint32_t right) { 
 __device__ __forceinline__ uint4 sk_make_header(unsigned long long ord, uint32_t n, bool uniform, uint32_t granules, uint32_t ext, uint32_t mhash, uint32_t wbits) {
 	return make_uint4((uint32_t)ord, (uint32_t)(ord >> 32) | (n << 8) | ((uniform ? 1u : 0u) << 16) | (granules << 17) | ext, mhash, wbits);
 }
+/* A record the extraction has booked but not yet written (SkPending) is one word: the index of its first k-mer in the read | n << 16 |
+ * uniform << 24 | position of that k-mer's end in the window << 25 (where its minimizer and weights stand in the rings) |
+ * 1 << 30 when the booking gave an address rather than what an add on the list's word returned | 1 << 31 live */
+__device__ __forceinline__ uint32_t sk_pend_make(uint32_t start, uint32_t n, bool uniform, uint32_t pos) { return (1u << 31) | (pos << 25) | ((uniform ? 1u : 0u) << 24) | (n << 16) | start; }
+static const uint32_t SK_PEND_ADDRESS = 1u << 30;
+__device__ __forceinline__ uint32_t sk_pend_start(uint32_t q) { return q & 0xffffu; }
+__device__ __forceinline__ uint32_t sk_pend_n(uint32_t q) { return (q >> 16) & 0xffu; }
+__device__ __forceinline__ bool sk_pend_uniform(uint32_t q) { return ((q >> 24) & 1u) != 0; }
+__device__ __forceinline__ uint32_t sk_pend_pos(uint32_t q) { return (q >> 25) & 15u; }
+__device__ __forceinline__ bool sk_pend_is_address(uint32_t q) { return ((q >> 30) & 1u) != 0; }
+__device__ __forceinline__ bool sk_pend_live(uint32_t q) { return (q >> 31) != 0; }
 
 #ifndef KMR_INSTANCE_TU
 __global__ void sk_state_init_kernel(unsigned long long *state, uint64_t n) {
@@ -337,6 +348,258 @@ __device__ __forceinline__ double sk_fresh_product(const double *sP, const uint8
 	return w;
 }
 
+/* ------------------------------------------------------------------ the tile walk's parts, shared by the two extraction kernels */
+/* sk_extract_kernel and sk_extract_lean_kernel walk a tile of 64 reads the same way -- a lane per read, the reads staged in LDS a
+ * fitting run at a time, SK_WINDOW positions per step, the runs that ended in a window gathered into records and booked in their
+ * lists, the bookings settled one window later -- and differ in what happens to a window's positions in between: the fp64 weight
+ * chain there, one weight and the N history here.  Everything around that middle is below; a change to it reaches both. */
+
+/* the lane's item of tile `tile`: a read, or a unit of the reads cut into units (rv.u_start); REFQ: does the unit's read begin with
+ * the reference quality (a read's own first quality is in the tile, a unit's may not be) */
+struct SkTileLane { uint32_t nr; bool have; uint64_t start, end, read; bool discard, refQual; };
+template <bool REFQ> __device__ __forceinline__ SkTileLane sk_tile_lane(const ReadsView &rv, uint64_t n_items, uint64_t tile, int lane) {
+	const uint64_t r0 = tile * 64;
+	SkTileLane me = {(uint32_t)((n_items - r0) < 64 ? (n_items - r0) : 64), false, 0, 0, 0, true, false};
+	me.have = (uint32_t)lane < me.nr;
+	if (me.have) {
+		if (rv.u_start) {
+			me.start = rv.u_start[r0 + lane]; me.end = rv.u_end[r0 + lane]; me.read = rv.u_read[r0 + lane];
+			if (REFQ) { const uint64_t rs = rv.offsets[me.read]; me.refQual = rv.quals && rv.offsets[me.read + 1] > rs && rv.quals[rs] == 127; }
+		} else {
+			me.read = r0 + lane;
+			me.start = rv.offsets[me.read];
+			me.end = rv.offsets[me.read + 1];
+		}
+		me.discard = rv.discarded ? (rv.discarded[me.read] != 0) : false;
+	}
+	return me;
+}
+/* How many consecutive lanes from `done` on hold reads that fit one staging span beginning at lane done's first byte (`fits`, the
+ * caller's predicate, false below `done`)?  0: not even that read does -- it is longer than a tile, flagged here and skipped by the
+ * caller.  (ctz of 0 is undefined, hence the guard: without it a tile whose 64 reads all fit came out as 32 and every tile was
+ * staged in two halves.) */
+__device__ __forceinline__ uint32_t sk_fitting_run(bool fits, uint32_t done, uint32_t nr, int lane, unsigned int *err) {
+	const unsigned long long fm = __ballot(fits) >> done;
+	uint32_t n = ~fm ? (uint32_t)__builtin_ctzll(~fm) : 64u;
+	if (n > nr - done) n = nr - done;
+	if (n == 0 && lane == 0) atomicOr(err, (uint32_t)ERR_READ_TOO_LONG);
+	return n;
+}
+template <typename T> __device__ __forceinline__ T sk_wave_max(T x) {
+#pragma unroll
+	for (int o = 32; o > 0; o >>= 1) { const T y = __shfl_xor(x, o, 64); x = y > x ? y : x; }
+	return x;
+}
+/* sixteen ASCII bases -> one dword of 2-bit codes (the first base in the top bits; a markup packs as A) and their 16 N flags */
+__device__ __forceinline__ void sk_pack16(const uint4 &v, uint32_t &packed, uint32_t &nflags) {
+	const uint32_t w4[4] = {v.x, v.y, v.z, v.w};
+	packed = 0; nflags = 0;
+#pragma unroll
+	for (int b = 0; b < 16; b++) {
+		const uint32_t code = base_code((uint8_t)(w4[b >> 2] >> (8 * (b & 3))));
+		packed |= (code & 3u) << (30 - 2 * b);
+		nflags |= (code >> 2) << b;
+	}
+}
+/* one record's header and base granules, from the tile's packed bases at base offset xb */
+__device__ __forceinline__ void sk_write_header_and_bases(uint4 *dst, const uint4 &hdr, const uint32_t *pk, uint32_t xb, uint32_t nbg) {
+	dst[0] = hdr;
+	for (uint32_t b = 0; b < nbg; b++)
+		dst[1 + b] = make_uint4(sk_bases16(pk, xb + 64 * b), sk_bases16(pk, xb + 64 * b + 16), sk_bases16(pk, xb + 64 * b + 32), sk_bases16(pk, xb + 64 * b + 48));
+}
+
+/* Minimizer of the k-mer that ends at a position: the m-mer ending sp.off positions back, canonical, hashed; the minimum of the last
+ * WIN of them by block decomposition (prefix minimum of the current block of WB, suffix minima of the one before).  step()'s t, the
+ * position in the window, is a constant after unrolling, so hs[] stays in registers.
+ * WIN > 16: the minimum over the last WIN hashes is the smaller of the block minimum over the last 16 and the block minimum of
+ * WIN - 16 positions earlier -- a delay line of WIN - 16 registers (mprev), indexed by the position modulo its length, which is a
+ * constant after unrolling as long as that length divides the 16 positions of an iteration: WIN = 17, 18, 20, 24, 32 */
+template <int WIN> struct SkMinimizer {
+	static constexpr int WB = WIN > 16 ? 16 : WIN;
+	static constexpr int WD = WIN > 16 ? WIN - 16 : 1;
+	static_assert(WIN <= 16 || SK_WINDOW % WD == 0, "the delay line of a window above 16 has to divide SK_WINDOW");
+	uint32_t mmask, mtop;
+	uint32_t mf, mr, hs[WB], mprev[WD], pref;
+	__device__ __forceinline__ void init(uint32_t m) { mmask = m >= 16 ? 0xffffffffu : ((1u << (2 * m)) - 1u); mtop = 2 * (m - 1); }
+	__device__ __forceinline__ void reset() {
+		mf = 0; mr = 0; pref = 0xffffffffu;
+#pragma unroll
+		for (int i = 0; i < WB; i++) hs[i] = 0xffffffffu;
+#pragma unroll
+		for (int i = 0; i < WD; i++) mprev[i] = 0xffffffffu;
+	}
+	/* the 16 bases `off` positions behind base offset x of the tile (the very first positions of a tile have nothing that far back:
+	 * zeros, they end no m-mer a k-mer looks at) */
+	static __device__ __forceinline__ uint32_t bases16(const uint32_t *pk, uint32_t x, uint32_t off) {
+		const int32_t xm = (int32_t)x - (int32_t)off;
+		return xm >= 0 ? sk_bases16(pk, (uint32_t)xm) : (xm > -16 ? sk_bases16(pk, 0u) >> (2 * (uint32_t)(-xm)) : 0u);
+	}
+	__device__ __forceinline__ uint32_t step(const int t, const uint32_t mpkw) {
+		const uint32_t mc = (mpkw >> (30 - 2 * t)) & 3u;
+		mf = ((mf << 2) | mc) & mmask;
+		mr = (mr >> 2) | ((3u - mc) << mtop);
+		const uint32_t x = sk_mmer_hash(mf < mr ? mf : mr);
+		const int r = t % WB;
+		pref = r == 0 ? x : (x < pref ? x : pref);
+		hs[r] = x;
+		uint32_t M = pref;
+		if (r < WB - 1) { const uint32_t sfx = hs[r + 1 < WB ? r + 1 : 0]; M = sfx < M ? sfx : M; }
+		else {
+#pragma unroll
+			for (int u = WB - 2; u >= 0; u--) hs[u] = hs[u] < hs[u + 1] ? hs[u] : hs[u + 1];
+		}
+		if constexpr (WIN > 16) { const uint32_t m16 = M; const uint32_t before = mprev[t % WD]; M = before < M ? before : M; mprev[t % WD] = m16; }
+		return M;
+	}
+};
+
+/* Which of the last k positions were flagged (an N; in the general kernel also a quality below the floor): one bit per position,
+ * the newest in bit 0 of zbits[0], k + 1 of them in ZN words, and zc, the number of flags among the last k */
+template <int ZN> struct SkZeroHistory {
+	/* a vector, not an array: the word a flag leaves from is picked by k, and a member array indexed that way would live in scratch */
+	typedef uint64_t Words __attribute__((ext_vector_type(ZN)));
+	Words zbits; uint32_t zc;
+	__device__ __forceinline__ void reset() { zbits = (Words)(0); zc = 0; }
+	/* sixteen positions enter (zm: bit t = the flag of the window's position t); none counted, none leaves */
+	__device__ __forceinline__ void shift16(uint32_t zm) {
+		if (ZN > 2) zbits[ZN - 1] = (zbits[ZN - 1] << 16) | (zbits[ZN > 2 ? 1 : 0] >> 48);
+		if (ZN > 1) zbits[1 % ZN] = (zbits[1 % ZN] << 16) | (zbits[0] >> 48);
+		zbits[0] = (zbits[0] << 16) | (uint64_t)(__builtin_bitreverse32(zm) >> 16);
+	}
+	__device__ __forceinline__ void shift16_clean() { shift16(0u); }
+	/* sixteen positions enter and sixteen leave, k >= SK_WINDOW (what leaves the k-window during these 16 positions lies wholly in
+	 * the history).  Returns the positions of the window at which the count is above zero. */
+	__device__ __forceinline__ uint32_t advance16(uint32_t zm, uint32_t k) {
+		uint32_t field;                                                          /* history bits k-16 .. k-1 (bit b = position jb - 1 - b) */
+		{
+			const uint32_t lo = k - 16u, wi = lo >> 6, sh = lo & 63u;
+			uint64_t a = zbits[wi < (uint32_t)ZN ? wi : ZN - 1];
+			if (wi >= (uint32_t)ZN) a = 0;
+			uint64_t b = (wi + 1 < (uint32_t)ZN) ? zbits[wi + 1 < (uint32_t)ZN ? wi + 1 : ZN - 1] : 0ull;
+			field = (uint32_t)((sh ? (a >> sh) | (b << (64u - sh)) : a) & 0xffffu);
+		}
+		const uint32_t lm = __builtin_bitreverse32(field) >> 16;                 /* bit t: the flag that leaves at position jb + t */
+		uint32_t zcw = zc, zcpos = 0;
+#pragma unroll
+		for (int t = 0; t < SK_WINDOW; t++) { zcw += (zm >> t) & 1u; zcw -= (lm >> t) & 1u; zcpos |= (zcw != 0 ? 1u : 0u) << t; }
+		zc = zcw;
+		shift16(zm);
+		return zcpos;
+	}
+	/* one position enters with flag z, position j - k leaves (nothing while j < k) */
+	__device__ __forceinline__ void advance1(bool z, uint32_t k) {
+		if (ZN > 2) zbits[ZN - 1] = (zbits[ZN - 1] << 1) | (zbits[ZN > 2 ? 1 : 0] >> 63);
+		if (ZN > 1) zbits[1 % ZN] = (zbits[1 % ZN] << 1) | (zbits[0] >> 63);
+		zbits[0] = (zbits[0] << 1) | (z ? 1ull : 0ull);
+		zc += z ? 1u : 0u;
+		zc -= (uint32_t)((zbits[ZN == 1 ? 0 : (k >> 6)] >> (k & 63)) & 1ull);
+	}
+};
+
+/* The gather of a window: every run that ended in it becomes a record.  Vm: positions with a good k-mer, Sm: positions where a run
+ * began; a run breaks where a k-mer is not good or the next run begins.  pendC: the run carried into the window (cinOpen) ended in
+ * it, after `lead` more k-mers; Srem: the runs begun in the window that ended in it -- all but the last one begun when that is
+ * still open (openInWin). */
+struct SkGather {
+	uint32_t brk, lead, Srem; bool pendC;
+	__device__ __forceinline__ SkGather(uint32_t Vm, uint32_t Sm, bool cinOpen, bool openInWin) {
+		brk = (~Vm | Sm) & 0xffffu;
+		pendC = false; lead = 16;
+		if (cinOpen) { lead = (uint32_t)__builtin_ctz(brk | 0x10000u); pendC = lead < 16; }
+		Srem = Sm;
+		if (openInWin && Sm) Srem &= ~(1u << (31 - __builtin_clz(Sm)));      /* the run still open is the last one begun */
+	}
+	__device__ __forceinline__ bool more() const { return pendC || Srem; }
+	/* the next run of Srem: the window position of its first k-mer and its number of k-mers */
+	__device__ __forceinline__ void next(uint32_t &pos, uint32_t &n) {
+		pos = (uint32_t)__builtin_ctz(Srem); Srem &= Srem - 1;
+		const uint32_t end = pos + 1 + (uint32_t)__builtin_ctz((brk >> (pos + 1)) | (1u << (15 - pos)));
+		n = end - pos;
+	}
+};
+
+/* Records booked but not yet written.  RR records per lane and round: their list words are bumped back to back, and the bookings
+ * of a round are settled and the records written at the NEXT window's gather (or at the end of the tile): scattered device atomics
+ * run at ~2 x 10^10 per second chip-wide and take tens of microseconds under that load -- time the wavefront now spends walking
+ * the next 16 positions.  Settling goes in two steps: first everything that does not wait (a fit, or the one add that crossed a
+ * chunk's end and replaces it), only then the adds that have to wait for somebody else's new chunk -- a lane of this wavefront may
+ * be that somebody.
+ * info: sk_pend_*; mh: the record's minimizer hash (names its list); booked: what the booking returned.  `need` maps an info word to
+ * the record's granules; dbg: the general kernel's ablation switches (1 = no list appends, 4 = no record writes), 0 elsewhere. */
+template <int RR> struct SkPending {
+	uint32_t info[RR], mh[RR]; unsigned long long booked[RR];
+	__device__ __forceinline__ void clear() {
+#pragma unroll
+		for (int r = 0; r < RR; r++) { info[r] = 0; mh[r] = 0; booked[r] = 0; }
+	}
+	/* book slot r (info and mh set by the caller): in the wavefront's own chain when its list is the hot one, else by an add on
+	 * the list's word, whose answer is looked at when the slot is settled */
+	template <typename NEED> __device__ __forceinline__ void book(int r, NEED need, uint32_t hotNow, const SkParams &sp, SkSlab *slab, const PoolView &pool, uint32_t dbg) {
+		if (sk_pend_live(info[r]) && !SK_DBG(dbg, 1)) {
+			const uint32_t g = need(info[r]), myList = sk_list_of(mh[r], sp.list_bits);
+			if (myList == hotNow) { booked[r] = sk_append_hot(slab, myList, g, pool); info[r] |= SK_PEND_ADDRESS; }
+			else booked[r] = atomicAdd(sp.state + myList, (unsigned long long)g);
+		}
+	}
+	/* settle every live slot and hand its record's place (a granule index of the pool) to write(r, at); the slots are free afterwards */
+	template <typename NEED, typename WRITE> __device__ __forceinline__ void flush(NEED need, WRITE write, const SkParams &sp, SkSlab *slab, const PoolView &pool, uint32_t dbg) {
+		uint64_t at[RR]; bool waits[RR];
+#pragma unroll
+		for (int r = 0; r < RR; r++) {
+			waits[r] = false; at[r] = ~0ull;
+			if (sk_pend_live(info[r]) && !SK_DBG(dbg, 1)) {
+				if (sk_pend_is_address(info[r])) at[r] = booked[r];
+				else at[r] = sk_append_settle(sp.state, sk_list_of(mh[r], sp.list_bits), need(info[r]), booked[r], slab, pool, waits[r]);
+			}
+		}
+#pragma unroll
+		for (int r = 0; r < RR; r++) if (waits[r]) at[r] = sk_append(sp.state, sk_list_of(mh[r], sp.list_bits), need(info[r]), slab, pool);
+#pragma unroll
+		for (int r = 0; r < RR; r++) {
+			if (sk_pend_live(info[r]) && at[r] != ~0ull && !SK_DBG(dbg, 4)) write(r, (uint4 *)pool.base + at[r]);
+			info[r] = 0;
+		}
+	}
+};
+
+/* the wavefront's slab cache (SkSlab): two slabs of 64 chunks taken at the start, */
+__device__ __forceinline__ void sk_slab_open(SkSlab *slab, const PoolView &pool, int lane) {
+	if (lane == 0) { slab->base[0] = atomicAdd(pool.head, 64u); slab->base[1] = atomicAdd(pool.head, 64u); slab->next = 0; slab->hot_list = SK_NO_LIST; slab->hot_state = 0; }
+}
+/* ... the first one replaced when it is used up (uniform), */
+__device__ __forceinline__ void sk_slab_refill(SkSlab *slab, const PoolView &pool, int lane) {
+	if (slab->next >= 64u) {
+		__builtin_amdgcn_wave_barrier();
+		if (lane == 0) { const uint32_t used = slab->next; slab->base[0] = slab->base[1]; slab->base[1] = atomicAdd(pool.head, 64u); slab->next = used >= 128u ? 64u : used - 64u; }
+		__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+		__builtin_amdgcn_wave_barrier();
+	}
+}
+/* ... and at the end the chunks nobody took marked as belonging to no list, and the open chunk of the hot chain given its fill count */
+__device__ __forceinline__ void sk_slab_close(SkSlab *slab, const PoolView &pool, int lane) {
+	__builtin_amdgcn_wave_barrier();
+	const uint32_t used = slab->next < 128u ? slab->next : 128u;
+	for (uint32_t idx = used + (uint32_t)lane; idx < 128u; idx += 64) { const uint32_t c = slab->base[idx >> 6] + (idx & 63u); if (c < pool.cap) { pool.chunk_list[c] = NO_CHUNK; pool.chunk_count[c] = 0; } }
+	if (lane == 0 && slab->hot_list < SK_LIST_LOCKED) {
+		const uint32_t hc = (uint32_t)(slab->hot_state >> 32), hf = (uint32_t)slab->hot_state;
+		if (hc < pool.cap) pool.chunk_count[hc] = hf < SK_CHUNK_G ? hf : SK_CHUNK_G;
+	}
+}
+
+/* what the size tracker needs of the lane's read (or of its unit of a long read: the units of a read add up) */
+__device__ __forceinline__ void sk_tile_finish(const SkParams &sp, const ReadsView &rv, const SkTileLane &me, uint32_t tRaw, uint32_t tGood) {
+	if (sp.track && me.have && !me.discard) {
+		SkTrackRec *tr = sp.track + me.read;
+		if (rv.u_start) { atomicAdd(&tr->raw, tRaw); atomicAdd(&tr->good, tGood); atomicMax(&tr->end_ordinal, (unsigned long long)(rv.stream_base + me.end)); }
+		else { tr->raw = tRaw; tr->good = tGood; tr->end_ordinal = rv.stream_base + me.end; }
+	}
+}
+/* the wavefront's k-mer totals into the launch's stats */
+__device__ __forceinline__ void sk_stats_finish(const DevParams &p, unsigned long long nRaw, unsigned long long nGood, int lane) {
+	nRaw = wave_sum(nRaw); nGood = wave_sum(nGood);
+	if (lane == 0) { atomicAdd(&p.stats->raw, nRaw); atomicAdd(&p.stats->good, nGood); }
+}
+
 template <int W, int WIN, bool FILT, bool EXT = false>
 __global__ __launch_bounds__(SK_WAVES * 64, 2)
 void sk_extract_kernel(ReadsView rv, DevParams p, SkParams sp, PoolView pool) {
@@ -353,12 +616,12 @@ void sk_extract_kernel(ReadsView rv, DevParams p, SkParams sp, PoolView pool) {
 	uint32_t *mhr = (uint32_t *)(wb + SK_Q_BYTES + SK_GROUPS * 10 + 8);   /* [SK_WINDOW][64] minimizer hash         */
 	float *wtr = (float *)(mhr + SK_WINDOW * 64);                       /* [SK_WINDOW][64] weight                 */
 	SkSlab *slab = &s_slab[wave];
-	if (lane == 0) { slab->base[0] = atomicAdd(pool.head, 64u); slab->base[1] = atomicAdd(pool.head, 64u); slab->next = 0; slab->hot_list = SK_NO_LIST; slab->hot_state = 0; }
+	sk_slab_open(slab, pool, lane);
 	__syncthreads();                       /* the only block-wide barrier; waves are independent below */
 
-	const uint32_t k = p.k, m = sp.m;
-	const uint32_t mmask = m >= 16 ? 0xffffffffu : ((1u << (2 * m)) - 1u);
-	const uint32_t mtop = 2 * (m - 1);
+	const uint32_t k = p.k;
+	SkMinimizer<WIN> mz;                   /* runs sp.off positions behind the k-mer pipeline */
+	mz.init(sp.m);
 	unsigned long long nRaw = 0, nGood = 0, nSub = 0;
 #ifdef KMR_DEBUG_HOOKS
 	unsigned long long nFlatBlk = 0, nGenBlk = 0;
@@ -366,38 +629,15 @@ void sk_extract_kernel(ReadsView rv, DevParams p, SkParams sp, PoolView pool) {
 	const uint64_t n_items = rv.u_start ? rv.n_units : rv.n_reads;
 	const uint64_t n_tiles = (n_items + 63) / 64;
 	for (uint64_t tile = (uint64_t)blockIdx.x * SK_WAVES + wave; tile < n_tiles; tile += (uint64_t)gridDim.x * SK_WAVES) {
-	const uint64_t r0 = tile * 64;
-	const uint32_t nr = (uint32_t)((n_items - r0) < 64 ? (n_items - r0) : 64);
-	const bool have = (uint32_t)lane < nr;
-	uint64_t myStart = 0, myEnd = 0, myRead = 0;
-	bool myDiscard = true, myRefQual = false;
-	if (have) {
-		if (rv.u_start) {
-			myStart = rv.u_start[r0 + lane]; myEnd = rv.u_end[r0 + lane]; myRead = rv.u_read[r0 + lane];
-			const uint64_t rs = rv.offsets[myRead];
-			myRefQual = rv.quals && rv.offsets[myRead + 1] > rs && rv.quals[rs] == 127;
-		} else {
-			myRead = r0 + lane;
-			myStart = rv.offsets[myRead];
-			myEnd = rv.offsets[myRead + 1];
-		}
-		myDiscard = rv.discarded ? (rv.discarded[myRead] != 0) : false;
-	}
+	const SkTileLane me = sk_tile_lane<true>(rv, n_items, tile, lane);
 	uint32_t tRaw = 0, tGood = 0;
 
 	uint32_t done = 0;
-	while (done < nr) {
-		const uint64_t B0 = __shfl(myStart, (int)done, 64);
-		const bool fits = have && (uint32_t)lane >= done && (myEnd - B0 <= (uint64_t)TILE_SPAN);
-		unsigned long long fm = __ballot(fits) >> done;
-		uint32_t n = ~fm ? (uint32_t)__builtin_ctzll(~fm) : 64u;          /* run of fitting reads starting at 'done' (ctz of 0 is undefined: it came out as 32 and halved every tile) */
-		if (n > nr - done) n = nr - done;
-		if (n == 0) {                                        /* read longer than a tile */
-			if (lane == 0) atomicOr(p.err, (uint32_t)ERR_READ_TOO_LONG);
-			done += 1;
-			continue;
-		}
-		const uint64_t B1 = __shfl(myEnd, (int)(done + n - 1), 64);
+	while (done < me.nr) {
+		const uint64_t B0 = __shfl(me.start, (int)done, 64);
+		const uint32_t n = sk_fitting_run(me.have && (uint32_t)lane >= done && (me.end - B0 <= (uint64_t)TILE_SPAN), done, me.nr, lane, p.err);
+		if (n == 0) { done += 1; continue; }
+		const uint64_t B1 = __shfl(me.end, (int)(done + n - 1), 64);
 #ifdef KMR_DEBUG_HOOKS
 		if (lane == 0) nGenBlk += 1000000ull + n;
 #endif
@@ -421,14 +661,8 @@ void sk_extract_kernel(ReadsView rv, DevParams p, SkParams sp, PoolView pool) {
 				if (idx < nb16) vb = gbp[idx];
 				if (idx < nq16) vq = gqp[idx];
 				{
-					const uint32_t w4[4] = {vb.x, vb.y, vb.z, vb.w};
-					uint32_t packed = 0, nflags = 0;
-#pragma unroll
-					for (int b = 0; b < 16; b++) {
-						const uint32_t code = base_code((uint8_t)(w4[b >> 2] >> (8 * (b & 3))));
-						packed |= (code & 3u) << (30 - 2 * b);          /* markup packs as A */
-						nflags |= (code >> 2) << b;
-					}
+					uint32_t packed, nflags;
+					sk_pack16(vb, packed, nflags);
 					if (idx < (uint32_t)SK_GROUPS) { pk[idx] = packed; nm[idx] = (uint16_t)nflags; }
 				}
 				if (haveQuals) {
@@ -448,122 +682,84 @@ void sk_extract_kernel(ReadsView rv, DevParams p, SkParams sp, PoolView pool) {
 					carryq = (uint32_t)__builtin_amdgcn_readlane((int)(vq.w >> 24), 63);
 				}
 			}
-			/* two groups of padding behind the data so that window reads of the last positions stay defined */
+			/* four groups of padding behind the data so that window reads of the last positions stay defined */
 			if (lane < 4) { const uint32_t g = nb16 + (uint32_t)lane; if (g < (uint32_t)SK_GROUPS) { pk[g] = 0; nm[g] = 0; } const uint32_t g2 = nq16 + (uint32_t)lane; if (g2 < (uint32_t)SK_GROUPS) qe[g2] = 0; }
 		}
+		/* (not sk_wave_lds_order(): the workgroup fences also wait for the staging's global loads and LDS stores, the order the kernel is tuned with) */
 		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
 		__builtin_amdgcn_wave_barrier();
 		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 
-		const bool active = have && (uint32_t)lane >= done && (uint32_t)lane < done + n && !myDiscard;
-		const uint32_t L = active ? (uint32_t)(myEnd - myStart) : 0;
-		const uint32_t rbOff = active ? (uint32_t)(gb - ab) + (uint32_t)(myStart - B0) : 0u;
-		const uint32_t rqOff = active ? (uint32_t)(gq - aq) + (uint32_t)(myStart - B0) : 0u;
+		const bool active = me.have && (uint32_t)lane >= done && (uint32_t)lane < done + n && !me.discard;
+		const uint32_t L = active ? (uint32_t)(me.end - me.start) : 0;
+		const uint32_t rbOff = active ? (uint32_t)(gb - ab) + (uint32_t)(me.start - B0) : 0u;
+		const uint32_t rqOff = active ? (uint32_t)(gq - aq) + (uint32_t)(me.start - B0) : 0u;
 		const uint8_t *rq = tq + rqOff;
-		uint32_t Lmax = L;
-#pragma unroll
-		for (int o = 32; o > 0; o >>= 1) { uint32_t x = __shfl_xor(Lmax, o, 64); Lmax = x > Lmax ? x : Lmax; }
+		const uint32_t Lmax = sk_wave_max(L);
 
-		const bool isRef = !haveQuals || (rv.u_start ? myRefQual : (L > 0 && rq[0] == 127));
-		const uint64_t ord0 = rv.stream_base + myStart;      /* + k-mer index = stream ordinal of the occurrence */
+		const bool isRef = !haveQuals || (rv.u_start ? me.refQual : (L > 0 && rq[0] == 127));
+		const uint64_t ord0 = rv.stream_base + me.start;      /* + k-mer index = stream ordinal of the occurrence */
 		/* weight chain */
 		double w = 0.0;
-		uint32_t zc = 0;
-		constexpr int ZN = W == 1 ? 1 : (W == 2 ? 2 : 3);      /* history of zero flags, one bit per position: k + 1 bits */
-		uint64_t zbits[3] = {0, 0, 0};
+		SkZeroHistory<W == 1 ? 1 : (W == 2 ? 2 : 3)> zh;      /* flags: an N or a quality below the floor */
+		zh.reset();
 		uint32_t qrun = 0;
-		/* minimizer pipeline: runs sp.off positions behind the k-mer pipeline */
-		uint32_t mf = 0, mr = 0;
-		/* WIN > 16: the minimum over the last WIN hashes is the smaller of the block minimum over the last 16 and the block minimum of
-		 * WIN - 16 positions earlier -- a delay line of WIN - 16 registers (mprev), indexed by the position modulo its length, which is a
-		 * constant after unrolling as long as that length divides the 16 positions of an iteration: WIN = 17, 18, 20, 24, 32 */
-		constexpr int WB = WIN > 16 ? 16 : WIN;
-		constexpr int WD = WIN > 16 ? WIN - 16 : 1;
-		static_assert(WIN <= 16 || SK_WINDOW % WD == 0, "the delay line of a window above 16 has to divide SK_WINDOW");
-		uint32_t hs[WB], mprev[WD];
-#pragma unroll
-		for (int i = 0; i < WB; i++) hs[i] = 0xffffffffu;
-#pragma unroll
-		for (int i = 0; i < WD; i++) mprev[i] = 0xffffffffu;
-		uint32_t pref = 0xffffffffu;
+		mz.reset();
 		/* the run in progress */
 		bool runOpen = false, runUniform = true, runInWin = false;
 		uint32_t runStart = 0, runN = 0, runMh = 0, runW0 = 0;
 		SkRoll<FILT ? W : 1> fr;           /* forward / reverse-complement words: only the filters need the k-mer itself */
 		if (FILT) fr.r.init(k);
 
-		/* records booked but not yet written (see the gather below): start | n << 16 | uniform << 24 | window position << 25 | 1 << 31,
-		 * minimizer hash, weight bits, and what the booking add returned */
-		uint32_t q_info[SK_RR], q_mh[SK_RR], q_w0[SK_RR]; unsigned long long q_booked[SK_RR];
+		/* the pending records, and with each the weight bits of its first k-mer */
+		SkPending<SK_RR> pend; uint32_t q_w0[SK_RR];
+		pend.clear();
 #pragma unroll
-		for (int r = 0; r < SK_RR; r++) { q_info[r] = 0; q_mh[r] = 0; q_w0[r] = 0; q_booked[r] = 0; }
-		auto flush_pending = [&]() {
-			uint64_t at[SK_RR]; bool waits[SK_RR];
-#pragma unroll
-			for (int r = 0; r < SK_RR; r++) {
-				waits[r] = false; at[r] = ~0ull;
-				if ((q_info[r] >> 31) && !SK_DBG(sp.dbg, 1)) {
-					const uint32_t n = (q_info[r] >> 16) & 0xffu; const bool uni = (q_info[r] >> 24) & 1u;
-					if ((q_info[r] >> 30) & 1u) at[r] = q_booked[r];
-					else at[r] = sk_append_settle(sp.state, sk_list_of(q_mh[r], sp.list_bits), sk_rec_granules(n, k, uni, EXT), q_booked[r], slab, pool, waits[r]);
+		for (int r = 0; r < SK_RR; r++) q_w0[r] = 0;
+		const auto need = [&](uint32_t q) { return sk_rec_granules(sk_pend_n(q), k, sk_pend_uniform(q), EXT); };
+		/* a record: the extension granules and, unless it is uniform, a weight per k-mer (from this window's ring) behind header and bases */
+		const auto write_record = [&](int r, uint4 *dst) {
+			const uint32_t q = pend.info[r], start = sk_pend_start(q), n = sk_pend_n(q), pos = sk_pend_pos(q); const bool uni = sk_pend_uniform(q);
+			const uint32_t nbg = sk_base_granules(n, k), nwg = uni ? 0u : (n + 3) / 4;
+			uint32_t hdrExt = 0;
+			if constexpr (EXT) {
+				/* neighbours outside the run: the base before its first k-mer and the one behind its last (in the tile; for the first / last
+				 * k-mer of a unit of a long read in the read itself; 'X' with the minimum extension quality where the read ends), and the
+				 * qualities of every k-mer's two neighbours */
+				const uint32_t c4 = ((256u - (p.fastq_start & 0xffu)) & 0xffu) * 0x01010101u;
+				const uint32_t qref = (127u - p.fastq_start) & 0xffu;
+				const uint32_t e = start + n + k - 1;                 /* position behind the last k-mer */
+				uint32_t oL = SK_EXT_X, oR = SK_EXT_X, qL = p.ext_min_q & 0xffu, qR = p.ext_min_q & 0xffu;
+				if (start > 0) { oL = (sk_bases16(pk, rbOff + start - 1) >> 30) & 3u; qL = isRef ? qref : ((uint32_t)rq[start - 1] - p.fastq_start) & 0xffu; }
+				else if (rv.u_start && me.start > rv.offsets[me.read]) { uint32_t c = base_code(rv.bases[me.start - 1]); oL = c == 4 ? 0u : c; qL = isRef ? qref : ((uint32_t)rv.quals[me.start - 1] - p.fastq_start) & 0xffu; }
+				if (e < L) { oR = (sk_bases16(pk, rbOff + e) >> 30) & 3u; qR = isRef ? qref : ((uint32_t)rq[e] - p.fastq_start) & 0xffu; }
+				else if (rv.u_start && me.end < rv.offsets[me.read + 1]) { uint32_t c = base_code(rv.bases[me.end]); oR = c == 4 ? 0u : c; qR = isRef ? qref : ((uint32_t)rv.quals[me.end] - p.fastq_start) & 0xffu; }
+				hdrExt = sk_hdr_ext(oL, oR);
+				const uint32_t neg = sk_ext_granules(n);
+				for (uint32_t g = 0; g < neg; g++) {
+					uint2 lq = make_uint2(qref * 0x01010101u, qref * 0x01010101u), rqv = lq;
+					if (!isRef) {
+						const uint32_t offL = rqOff + start + 8 * g;      /* lq[8 g + i] is the quality at start + 8 g + i - 1 */
+						if (offL == 0) { const uint2 v = sk_lds_bytes8(tq, 0u); lq = make_uint2(v.x << 8, (v.y << 8) | (v.x >> 24)); }
+						else lq = sk_lds_bytes8(tq, offL - 1);
+						rqv = sk_lds_bytes8(tq, rqOff + start + k + 8 * g);
+						lq.x = sk_bytes_add(lq.x, c4); lq.y = sk_bytes_add(lq.y, c4); rqv.x = sk_bytes_add(rqv.x, c4); rqv.y = sk_bytes_add(rqv.y, c4);
+					}
+					if (g == 0) lq.x = (lq.x & ~0xffu) | qL;              /* (the same value again when the neighbour lies in the tile) */
+					if (g == (n - 1) >> 3) { const uint32_t b = (n - 1) & 7u; if (b < 4) rqv.x = (rqv.x & ~(0xffu << (8 * b))) | (qR << (8 * b)); else rqv.y = (rqv.y & ~(0xffu << (8 * (b - 4)))) | (qR << (8 * (b - 4))); }
+					dst[1 + nbg + nwg + g] = make_uint4(__builtin_amdgcn_perm(rqv.x, lq.x, 0x05010400u), __builtin_amdgcn_perm(rqv.x, lq.x, 0x07030602u),
+					                                    __builtin_amdgcn_perm(rqv.y, lq.y, 0x05010400u), __builtin_amdgcn_perm(rqv.y, lq.y, 0x07030602u));
 				}
 			}
+			sk_write_header_and_bases(dst, sk_make_header(ord0 + start, n, uni, need(q), hdrExt, pend.mh[r], q_w0[r]), pk, rbOff + start, nbg);
+			for (uint32_t b = 0; b < nwg; b++) {
+				uint32_t v[4];
 #pragma unroll
-			for (int r = 0; r < SK_RR; r++) if (waits[r]) {
-				const uint32_t n = (q_info[r] >> 16) & 0xffu; const bool uni = (q_info[r] >> 24) & 1u;
-				at[r] = sk_append(sp.state, sk_list_of(q_mh[r], sp.list_bits), sk_rec_granules(n, k, uni, EXT), slab, pool);
-			}
-#pragma unroll
-			for (int r = 0; r < SK_RR; r++) {
-				if ((q_info[r] >> 31) && at[r] != ~0ull && !SK_DBG(sp.dbg, 4)) {
-					const uint32_t start = q_info[r] & 0xffffu, n = (q_info[r] >> 16) & 0xffu, pos = (q_info[r] >> 25) & 15u; const bool uni = (q_info[r] >> 24) & 1u;
-					const uint32_t nbg = sk_base_granules(n, k), nwg = uni ? 0u : (n + 3) / 4;
-					uint4 *dst = (uint4 *)pool.base + at[r];
-					const uint64_t ord = ord0 + start;
-					uint32_t hdrExt = 0;
-					if constexpr (EXT) {
-						/* neighbours outside the run: the base before its first k-mer and the one behind its last (in the tile; for the first / last
-						 * k-mer of a unit of a long read in the read itself; 'X' with the minimum extension quality where the read ends), and the
-						 * qualities of every k-mer's two neighbours */
-						const uint32_t c4 = ((256u - (p.fastq_start & 0xffu)) & 0xffu) * 0x01010101u;
-						const uint32_t qref = (127u - p.fastq_start) & 0xffu;
-						const uint32_t e = start + n + k - 1;                 /* position behind the last k-mer */
-						uint32_t oL = SK_EXT_X, oR = SK_EXT_X, qL = p.ext_min_q & 0xffu, qR = p.ext_min_q & 0xffu;
-						if (start > 0) { oL = (sk_bases16(pk, rbOff + start - 1) >> 30) & 3u; qL = isRef ? qref : ((uint32_t)rq[start - 1] - p.fastq_start) & 0xffu; }
-						else if (rv.u_start && myStart > rv.offsets[myRead]) { uint32_t c = base_code(rv.bases[myStart - 1]); oL = c == 4 ? 0u : c; qL = isRef ? qref : ((uint32_t)rv.quals[myStart - 1] - p.fastq_start) & 0xffu; }
-						if (e < L) { oR = (sk_bases16(pk, rbOff + e) >> 30) & 3u; qR = isRef ? qref : ((uint32_t)rq[e] - p.fastq_start) & 0xffu; }
-						else if (rv.u_start && myEnd < rv.offsets[myRead + 1]) { uint32_t c = base_code(rv.bases[myEnd]); oR = c == 4 ? 0u : c; qR = isRef ? qref : ((uint32_t)rv.quals[myEnd] - p.fastq_start) & 0xffu; }
-						hdrExt = sk_hdr_ext(oL, oR);
-						const uint32_t neg = sk_ext_granules(n);
-						for (uint32_t g = 0; g < neg; g++) {
-							uint2 lq = make_uint2(qref * 0x01010101u, qref * 0x01010101u), rqv = lq;
-							if (!isRef) {
-								const uint32_t offL = rqOff + start + 8 * g;      /* lq[8 g + i] is the quality at start + 8 g + i - 1 */
-								if (offL == 0) { const uint2 v = sk_lds_bytes8(tq, 0u); lq = make_uint2(v.x << 8, (v.y << 8) | (v.x >> 24)); }
-								else lq = sk_lds_bytes8(tq, offL - 1);
-								rqv = sk_lds_bytes8(tq, rqOff + start + k + 8 * g);
-								lq.x = sk_bytes_add(lq.x, c4); lq.y = sk_bytes_add(lq.y, c4); rqv.x = sk_bytes_add(rqv.x, c4); rqv.y = sk_bytes_add(rqv.y, c4);
-							}
-							if (g == 0) lq.x = (lq.x & ~0xffu) | qL;              /* (the same value again when the neighbour lies in the tile) */
-							if (g == (n - 1) >> 3) { const uint32_t b = (n - 1) & 7u; if (b < 4) rqv.x = (rqv.x & ~(0xffu << (8 * b))) | (qR << (8 * b)); else rqv.y = (rqv.y & ~(0xffu << (8 * (b - 4)))) | (qR << (8 * (b - 4))); }
-							dst[1 + nbg + nwg + g] = make_uint4(__builtin_amdgcn_perm(rqv.x, lq.x, 0x05010400u), __builtin_amdgcn_perm(rqv.x, lq.x, 0x07030602u),
-							                                    __builtin_amdgcn_perm(rqv.y, lq.y, 0x05010400u), __builtin_amdgcn_perm(rqv.y, lq.y, 0x07030602u));
-						}
-					}
-					dst[0] = sk_make_header(ord, n, uni, sk_rec_granules(n, k, uni, EXT), hdrExt, q_mh[r], q_w0[r]);
-					const uint32_t xb = rbOff + start;
-					for (uint32_t b = 0; b < nbg; b++)
-						dst[1 + b] = make_uint4(sk_bases16(pk, xb + 64 * b), sk_bases16(pk, xb + 64 * b + 16), sk_bases16(pk, xb + 64 * b + 32), sk_bases16(pk, xb + 64 * b + 48));
-					for (uint32_t b = 0; b < nwg; b++) {
-						uint32_t v[4];
-#pragma unroll
-						for (int u = 0; u < 4; u++) { const uint32_t tt = pos + 4 * b + u; v[u] = tt < 16 ? __float_as_uint(wtr[tt * 64 + lane]) : 0u; }
-						dst[1 + nbg + b] = make_uint4(v[0], v[1], v[2], v[3]);
-					}
-				}
-				q_info[r] = 0;
+				for (int u = 0; u < 4; u++) { const uint32_t tt = pos + 4 * b + u; v[u] = tt < 16 ? __float_as_uint(wtr[tt * 64 + lane]) : 0u; }
+				dst[1 + nbg + b] = make_uint4(v[0], v[1], v[2], v[3]);
 			}
 		};
+		const auto flush_pending = [&]() { pend.flush(need, write_record, sp, slab, pool, sp.dbg); };
 		for (uint32_t jb = 0; jb < Lmax || __any(runOpen); jb += SK_WINDOW) {
 			/* the window's 16 positions of this lane's read: bases, N flags, quality flags; and the bases sp.off positions back */
 			const uint32_t pkw = sk_bases16(pk, rbOff + jb);
@@ -575,32 +771,11 @@ void sk_extract_kernel(ReadsView rv, DevParams p, SkParams sp, PoolView pool) {
 				qlow = (((a & 0xffffu) | (b << 16)) >> s) & 0xffffu;
 				qeq = (((a >> 16) | (b & 0xffff0000u)) >> s) & 0xffffu;
 			}
-			/* (the very first positions of a tile have nothing sp.off bases back: zeros, they end no m-mer a k-mer looks at) */
-			const int32_t xm = (int32_t)(rbOff + jb) - (int32_t)sp.off;
-			const uint32_t mpkw = xm >= 0 ? sk_bases16(pk, (uint32_t)xm) : (xm > -16 ? sk_bases16(pk, 0u) >> (2 * (uint32_t)(-xm)) : 0u);
+			const uint32_t mpkw = SkMinimizer<WIN>::bases16(pk, rbOff + jb, sp.off);
 			/* the run carried into this window (always uniform) */
 			const bool cinOpen = runOpen; const uint32_t cinStart = runStart, cinN = runN, cinMh = runMh, cinW0 = runW0;
 			uint32_t Sm = 0, Vm = 0, Cm = 0;
 			runInWin = false;
-			/* minimizer of the k-mer that ends at position jb + t: m-mer ending sp.off positions back, canonical, hashed; minimum of
-			 * the last WIN of them (t is a constant after unrolling, so hs[] stays in registers) */
-			auto minimizer_step = [&](const int t) -> uint32_t {
-				const uint32_t mc = (mpkw >> (30 - 2 * t)) & 3u;
-				mf = ((mf << 2) | mc) & mmask;
-				mr = (mr >> 2) | ((3u - mc) << mtop);
-				const uint32_t x = sk_mmer_hash(mf < mr ? mf : mr);
-				const int r = t % WB;
-				pref = r == 0 ? x : (x < pref ? x : pref);
-				hs[r] = x;
-				uint32_t M = pref;
-				if (r < WB - 1) { const uint32_t sfx = hs[r + 1 < WB ? r + 1 : 0]; M = sfx < M ? sfx : M; }
-				else {
-#pragma unroll
-					for (int u = WB - 2; u >= 0; u--) hs[u] = hs[u] < hs[u + 1] ? hs[u] : hs[u + 1];
-				}
-				if constexpr (WIN > 16) { const uint32_t m16 = M; const uint32_t before = mprev[t % WD]; M = before < M ? before : M; mprev[t % WD] = m16; }
-				return M;
-			};
 			/* Flat window: no lane sees an N or a quality below the floor (in the window or in the k positions before it), and the
 			 * qualities around every k-mer of the window are all equal -- a run of k + 1 equal chars behind each k-mer that continues
 			 * the weight chain (x / x == 1.0: the chain does not move), k equal chars where the product starts afresh (then it is
@@ -623,7 +798,7 @@ void sk_extract_kernel(ReadsView rv, DevParams p, SkParams sp, PoolView pool) {
 				const uint32_t eqm = (isRef ? 0xffffu : qeq) | (jb == 0 ? 1u : 0u);       /* position 0 has no predecessor: not looked at */
 				const uint32_t qAtTk = jb == 0 ? tk : qrun + tk + 1;           /* qrun as it will stand at position tk if the window's qualities are equal */
 				const bool ok = !live || nin <= tk ||
-				                ((nmw & inmask) == 0 && zc == 0 && (isRef || ((qlow & inmask) == 0 && (eqm & inmask) == inmask && qAtTk >= (fresh ? k - 1 : k))));
+				                ((nmw & inmask) == 0 && zh.zc == 0 && (isRef || ((qlow & inmask) == 0 && (eqm & inmask) == inmask && qAtTk >= (fresh ? k - 1 : k))));
 				if (noLaterRestart && __all(ok)) {
 					flatBlk = true;
 					const bool kmers = live && nin > tk;
@@ -635,14 +810,12 @@ void sk_extract_kernel(ReadsView rv, DevParams p, SkParams sp, PoolView pool) {
 					Vm = good ? kmask : 0u;
 					tRaw += (uint32_t)__builtin_popcount(kmask); tGood += (uint32_t)__builtin_popcount(Vm);
 					if (live) {
-						if (ZN > 2) zbits[2] = (zbits[2] << 16) | (zbits[1] >> 48);
-						if (ZN > 1) zbits[1] = (zbits[1] << 16) | (zbits[0] >> 48);
-						zbits[0] <<= 16;
+						zh.shift16_clean();
 						qrun = jb == 0 ? SK_WINDOW - 1 : qrun + SK_WINDOW;
 					}
 #pragma unroll
 					for (int t = 0; t < SK_WINDOW; t++) {
-						const uint32_t M = minimizer_step(t);
+						const uint32_t M = mz.step(t, mpkw);
 						const bool valid = ((Vm >> t) & 1u) != 0;
 						const bool cont = runOpen && M == runMh && runN < SK_MAX_N && flatWbits == runW0;
 						const bool nw = valid && !cont;
@@ -663,15 +836,13 @@ void sk_extract_kernel(ReadsView rv, DevParams p, SkParams sp, PoolView pool) {
 					flatBlk = true;
 					if (live) {
 						const uint32_t zm = nmw | (isRef ? 0u : qlow);
-						zc += (uint32_t)__builtin_popcount(zm);
-						if (ZN > 2) zbits[2] = (zbits[2] << 16) | (zbits[1] >> 48);
-						if (ZN > 1) zbits[1] = (zbits[1] << 16) | (zbits[0] >> 48);
-						zbits[0] = (zbits[0] << 16) | (uint64_t)(__builtin_bitreverse32(zm) >> 16);      /* the newest position in bit 0 */
+						zh.zc += (uint32_t)__builtin_popcount(zm);      /* (nothing leaves yet) */
+						zh.shift16(zm);
 						const uint32_t eq = (isRef ? 0xffffu : qeq) & (jb == 0 ? 0xfffeu : 0xffffu);       /* position 0 has no predecessor */
 						qrun = eq == 0xffffu ? qrun + SK_WINDOW : (uint32_t)__builtin_clz(~(eq << 16));      /* equal qualities counted back from the window's end */
 					}
 #pragma unroll
-					for (int t = 0; t < SK_WINDOW; t++) mhr[t * 64 + lane] = minimizer_step(t);
+					for (int t = 0; t < SK_WINDOW; t++) mhr[t * 64 + lane] = mz.step(t, mpkw);
 					if (!live) runOpen = false;
 				}
 			}
@@ -684,7 +855,7 @@ void sk_extract_kernel(ReadsView rv, DevParams p, SkParams sp, PoolView pool) {
 			 * 16 times it was 70 KB of code and ran out of the instruction cache (24 ms per C2 batch of noisy reads against 7 ms for the walk
 			 * of flat ones) */
 #pragma unroll
-			for (int t = 0; t < SK_WINDOW; t++) mhr[t * 64 + lane] = minimizer_step(t);
+			for (int t = 0; t < SK_WINDOW; t++) mhr[t * 64 + lane] = mz.step(t, mpkw);
 			if constexpr (!FILT) {
 			/* Without filters the case analysis is taken apart (noisy qualities: 215 vector + 147 scalar instructions per position
 			 * through the nested branches below, most of the scalar ones exec-mask bookkeeping, and a k-step product loop whenever ANY
@@ -708,22 +879,7 @@ void sk_extract_kernel(ReadsView rv, DevParams p, SkParams sp, PoolView pool) {
 				const uint32_t tk = jb + 1 >= k ? 0u : k - 1 - jb;                     /* < 16 here: jb + 16 >= k was checked by the caller's paths */
 				const uint32_t km = tk < 16u ? (inmask & ~((1u << tk) - 1u)) : 0u;
 				const uint32_t zm = (nmw | (isRef ? 0u : qlow)) & inmask;
-				uint32_t field;                                                          /* history bits k-16 .. k-1 (bit b = position jb - 1 - b) */
-				{
-					const uint32_t lo = k - 16u, wi = lo >> 6, sh = lo & 63u;
-					uint64_t a = zbits[wi < (uint32_t)ZN ? wi : ZN - 1];
-					if (wi >= (uint32_t)ZN) a = 0;
-					uint64_t b = (wi + 1 < (uint32_t)ZN) ? zbits[wi + 1 < (uint32_t)ZN ? wi + 1 : ZN - 1] : 0ull;
-					field = (uint32_t)((sh ? (a >> sh) | (b << (64u - sh)) : a) & 0xffffu);
-				}
-				const uint32_t lm = __builtin_bitreverse32(field) >> 16;                 /* bit t: the flag that leaves at position jb + t */
-				uint32_t zcw = zc, zcpos = 0;
-#pragma unroll
-				for (int t = 0; t < SK_WINDOW; t++) { zcw += (zm >> t) & 1u; zcw -= (lm >> t) & 1u; zcpos |= (zcw != 0 ? 1u : 0u) << t; }
-				zc = zcw;
-				if (ZN > 2) zbits[2] = (zbits[2] << 16) | (zbits[1] >> 48);
-				if (ZN > 1) zbits[1] = (zbits[1] << 16) | (zbits[0] >> 48);
-				zbits[0] = (zbits[0] << 16) | (uint64_t)(__builtin_bitreverse32(zm) >> 16);
+				const uint32_t zcpos = zh.advance16(zm, k);
 				zcm = zcpos & km;
 				const uint32_t t1024 = (k - 1u - jb) & 1023u;                             /* position whose k-mer index is a multiple of 1024 */
 				const uint32_t p1024 = t1024 < 16u ? (1u << t1024) : 0u;
@@ -742,14 +898,10 @@ void sk_extract_kernel(ReadsView rv, DevParams p, SkParams sp, PoolView pool) {
 				const uint32_t j = jb + t;
 				const bool in = j < L;
 				const bool z = in && ((((nmw >> t) & 1u) != 0) || (!isRef && ((qlow >> t) & 1u) != 0));
-				if (ZN > 2) zbits[2] = (zbits[2] << 1) | (zbits[1] >> 63);
-				if (ZN > 1) zbits[1] = (zbits[1] << 1) | (zbits[0] >> 63);
-				zbits[0] = (zbits[0] << 1) | (z ? 1ull : 0ull);
-				zc += z ? 1u : 0u;
-				zc -= (uint32_t)((zbits[ZN == 1 ? 0 : (k >> 6)] >> (k & 63)) & 1ull);
+				zh.advance1(z, k);
 				qrun = (j > 0 && (isRef || ((qeq >> t) & 1u))) ? qrun + 1 : 0;
 				const bool hasK = in && j + 1 >= k;
-				const bool zero = zc > 0;
+				const bool zero = zh.zc > 0;
 				zcm |= (hasK && zero) ? (1u << t) : 0u;
 				const bool fresh = hasK && !zero && !isRef && ((((j + 1 - k) & 1023u) == 0) || wz);
 				if (fresh && tR == 16) { tR = t; qrunR = qrun; }
@@ -815,11 +967,7 @@ void sk_extract_kernel(ReadsView rv, DevParams p, SkParams sp, PoolView pool) {
 				const bool in = j < L;
 				const uint32_t code = (pkw >> (30 - 2 * t)) & 3u;
 				const bool z = in && ((((nmw >> t) & 1u) != 0) || (!isRef && ((qlow >> t) & 1u) != 0));
-				if (ZN > 2) zbits[2] = (zbits[2] << 1) | (zbits[1] >> 63);
-				if (ZN > 1) zbits[1] = (zbits[1] << 1) | (zbits[0] >> 63);
-				zbits[0] = (zbits[0] << 1) | (z ? 1ull : 0ull);
-				zc += z ? 1u : 0u;
-				zc -= (uint32_t)((zbits[ZN == 1 ? 0 : (k >> 6)] >> (k & 63)) & 1ull);   /* position j-k leaves the window (0 while j < k) */
+				zh.advance1(z, k);
 				qrun = (j > 0 && (isRef || ((qeq >> t) & 1u))) ? qrun + 1 : 0;
 				if (FILT) fr.r.push(code);
 				const uint32_t M = mhr[t * 64 + lane];
@@ -827,7 +975,7 @@ void sk_extract_kernel(ReadsView rv, DevParams p, SkParams sp, PoolView pool) {
 				float wf = 0.0f;
 				if (in && j + 1 >= k) {
 					const uint32_t i = j + 1 - k;
-					if (zc > 0) w = 0.0;
+					if (zh.zc > 0) w = 0.0;
 					else if (isRef) w = 1.0;
 					else if ((i & 1023u) == 0 || w == 0.0) {
 						if (qrun + 1 >= k) w = sp.Pk[rq[j]];                 /* k equal qualities: the table holds the same sequence of products */
@@ -876,79 +1024,42 @@ void sk_extract_kernel(ReadsView rv, DevParams p, SkParams sp, PoolView pool) {
 			/* a run with unequal weights ends with its window (its weights live in this window's ring) */
 			const bool openEnd = runOpen && runUniform;
 			if (runOpen && !runUniform) runOpen = false;
-			/* gather: every run that ended in this window becomes a record of its list */
-			const uint32_t brk = (~Vm | Sm) & 0xffffu;
-			bool pendC = false; uint32_t lead = 16;
-			if (cinOpen) { lead = (uint32_t)__builtin_ctz(brk | 0x10000u); pendC = lead < 16; }
-			uint32_t Srem = Sm;
-			if (openEnd && runInWin && Sm) Srem &= ~(1u << (31 - __builtin_clz(Sm)));      /* the run still open is the last one begun */
-			if (SK_DBG(sp.dbg, 2)) { pendC = false; Srem = 0; }
-			/* Four records per lane and round: their list words are bumped back to back, and the bookings of a round are settled
-			 * and the records written at the NEXT window's gather (or at the end of the tile): scattered device atomics run at
-			 * ~2 x 10^10 per second chip-wide and take tens of microseconds under that load -- time the wavefront now spends
-			 * walking the next 16 positions.  Settling goes in two steps: first everything that does not wait (a fit, or the one
-			 * add that crossed a chunk's end and replaces it), only then the adds that have to wait for somebody else's new chunk
-			 * -- a lane of this wavefront may be that somebody.  Records with a weight per k-mer are settled at once (their
-			 * weights live in this window's ring). */
+			/* gather (SkGather, SkPending); records with a weight per k-mer are settled at once: their weights live in this window's ring */
+			SkGather g(Vm, Sm, cinOpen, openEnd && runInWin);
+			if (SK_DBG(sp.dbg, 2)) { g.pendC = false; g.Srem = 0; }
 			flush_pending();
 			bool firstRound = true;
 			const uint32_t hotNow = slab->hot_list;      /* read once per window: a stale value only delays the switch to the wavefront's own chain */
-			while (__any(pendC || Srem)) {
+			while (__any(g.more())) {
 				bool anyNow = false;
 #pragma unroll
 				for (int r = 0; r < SK_RR; r++) {
-					q_info[r] = 0;
-					if (pendC) { pendC = false; q_info[r] = (1u << 31) | (1u << 24) | ((cinN + lead) << 16) | cinStart; q_mh[r] = cinMh; q_w0[r] = cinW0; }
-					else if (Srem) {
-						const uint32_t pos = (uint32_t)__builtin_ctz(Srem); Srem &= Srem - 1;
-						const uint32_t end = pos + 1 + (uint32_t)__builtin_ctz((brk >> (pos + 1)) | (1u << (15 - pos)));
-						const uint32_t n = end - pos;
+					pend.info[r] = 0;
+					if (g.pendC) { g.pendC = false; pend.info[r] = sk_pend_make(cinStart, cinN + g.lead, true, 0u); pend.mh[r] = cinMh; q_w0[r] = cinW0; }
+					else if (g.Srem) {
+						uint32_t pos, n;
+						g.next(pos, n);
 						const bool uni = ((Cm >> (pos + 1)) & ((1u << (n - 1)) - 1u)) == 0;
-						q_info[r] = (1u << 31) | (pos << 25) | ((uni ? 1u : 0u) << 24) | (n << 16) | (jb + pos + 1 - k);
-						q_mh[r] = mhr[pos * 64 + lane]; q_w0[r] = flatBlk ? flatWbits : __float_as_uint(wtr[pos * 64 + lane]);
+						pend.info[r] = sk_pend_make(jb + pos + 1 - k, n, uni, pos);
+						pend.mh[r] = mhr[pos * 64 + lane]; q_w0[r] = flatBlk ? flatWbits : __float_as_uint(wtr[pos * 64 + lane]);
 						anyNow = anyNow || !uni;
 					}
-					if ((q_info[r] >> 31) && !SK_DBG(sp.dbg, 1)) {
-						const uint32_t n = (q_info[r] >> 16) & 0xffu; const bool uni = (q_info[r] >> 24) & 1u;
-						const uint32_t need = sk_rec_granules(n, k, uni, EXT), myList = sk_list_of(q_mh[r], sp.list_bits);
-						if (myList == hotNow) { q_booked[r] = sk_append_hot(slab, myList, need, pool); q_info[r] |= 1u << 30; }      /* an address, not what a booking add returned */
-						else q_booked[r] = atomicAdd(sp.state + myList, (unsigned long long)need);
-					}
+					pend.book(r, need, hotNow, sp, slab, pool, sp.dbg);
 				}
-				if (!firstRound || __any(anyNow) || __any(pendC || Srem)) flush_pending();      /* more rounds to come, or weights in the ring: settle now */
+				if (!firstRound || __any(anyNow) || __any(g.more())) flush_pending();      /* more rounds to come, or weights in the ring: settle now */
 				firstRound = false;
 			}
-			/* refill the slab cache of the wavefront (uniform) */
-			if (slab->next >= 64u) {
-				__builtin_amdgcn_wave_barrier();
-				if (lane == 0) { const uint32_t used = slab->next; slab->base[0] = slab->base[1]; slab->base[1] = atomicAdd(pool.head, 64u); slab->next = used >= 128u ? 64u : used - 64u; }
-				__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-				__builtin_amdgcn_wave_barrier();
-			}
+			sk_slab_refill(slab, pool, lane);
 		}
 		flush_pending();                   /* the last window's records: their bases are read from this tile */
 		done += n;
-		__builtin_amdgcn_wave_barrier();   /* all lanes are done reading the tile before it is overwritten */
+		sk_wave_lds_order();               /* all lanes are done reading the tile before it is overwritten */
 	}
 	nRaw += tRaw; nGood += tGood;
-	if (sp.track && have && !myDiscard) {      /* the lane's read (or its unit of a long read: the units of a read add up) */
-		SkTrackRec *tr = sp.track + myRead;
-		if (rv.u_start) { atomicAdd(&tr->raw, tRaw); atomicAdd(&tr->good, tGood); atomicMax(&tr->end_ordinal, (unsigned long long)(rv.stream_base + myEnd)); }
-		else { tr->raw = tRaw; tr->good = tGood; tr->end_ordinal = rv.stream_base + myEnd; }
+	sk_tile_finish(sp, rv, me, tRaw, tGood);
 	}
-	}
-	/* chunks of the slabs nobody took belong to no list */
-	__builtin_amdgcn_wave_barrier();
-	{
-		const uint32_t used = slab->next < 128u ? slab->next : 128u;
-		for (uint32_t idx = used + (uint32_t)lane; idx < 128u; idx += 64) { const uint32_t c = slab->base[idx >> 6] + (idx & 63u); if (c < pool.cap) { pool.chunk_list[c] = NO_CHUNK; pool.chunk_count[c] = 0; } }
-	if (lane == 0 && slab->hot_list < SK_LIST_LOCKED) {      /* the open chunk of the wavefront's hot chain */
-		const uint32_t hc = (uint32_t)(slab->hot_state >> 32), hf = (uint32_t)slab->hot_state;
-		if (hc < pool.cap) pool.chunk_count[hc] = hf < SK_CHUNK_G ? hf : SK_CHUNK_G;
-	}
-	}
-	nRaw = wave_sum(nRaw); nGood = wave_sum(nGood);
-	if (lane == 0) { atomicAdd(&p.stats->raw, nRaw); atomicAdd(&p.stats->good, nGood); }
+	sk_slab_close(slab, pool, lane);
+	sk_stats_finish(p, nRaw, nGood, lane);
 #ifdef KMR_DEBUG_HOOKS
 	if (lane == 0) { atomicAdd(&p.stats->claimed, nGenBlk); atomicAdd(&p.stats->inserted, nFlatBlk); }      /* windows down the general / the fast paths */
 #endif
@@ -962,7 +1073,9 @@ void sk_extract_kernel(ReadsView rv, DevParams p, SkParams sp, PoolView pool) {
  * src/KmerReadUtils.h:176-248: equal qualities leave the chain where it is, every fresh start gives the same product).  Without the
  * quality bytes, their flags and the weights ring a wavefront's tile is 7.8 KB of LDS instead of 24, and without the fp64 chain the
  * walk fits 128 registers: 16 wavefronts per CU instead of 6 -- the general kernel is bound by instruction issue at 1.5
- * wavefronts per SIMD.  The records, the list appends and their settlement one window later are the general kernel's. */
+ * wavefronts per SIMD.  The walk around that middle -- the lane's read, the fitting run, the
+ * minimizer, the N history, the gather, the bookings and their settlement one window later, the slabs -- is the shared pieces above
+ * sk_extract_kernel; the staging is this kernel's own (every round's loads are issued before the first is packed; PACKED swaps bytes). */
 static const int SKL_WAVES = 4, SKL_MIN_BLOCKS = 2;      /* 8 wavefronts per CU at 193 registers: 12 (168 registers, or fewer records booked per round) and 16 (128, spilling) were slower -- the pass runs at the chip's rate of scattered device atomics (1.8 x 10^10 per second, one per record) */      /* 168 registers: at 128 (four blocks) the walk spilled 59 dwords */
 static const int SKL_WAVE_LDS = (SK_GROUPS * 4 + SK_GROUPS * 2 + 8 + SK_WINDOW * 64 * 4 + 15) & ~15;
 static const size_t SKL_EXTRACT_SMEM = (size_t)SKL_WAVES * SKL_WAVE_LDS;
@@ -1028,51 +1141,32 @@ void sk_extract_lean_kernel(ReadsView rv, DevParams p, SkParams sp, PoolView poo
 	uint16_t *nm = (uint16_t *)(pk + SK_GROUPS);                        /* [SK_GROUPS] N flags      */
 	uint32_t *mhr = (uint32_t *)(wb + SK_GROUPS * 6 + 8);               /* [SK_WINDOW][64] minimizer hash */
 	SkSlab *slab = &s_slab[wave];
-	if (lane == 0) { slab->base[0] = atomicAdd(pool.head, 64u); slab->base[1] = atomicAdd(pool.head, 64u); slab->next = 0; slab->hot_list = SK_NO_LIST; slab->hot_state = 0; }
+	sk_slab_open(slab, pool, lane);
 	__syncthreads();                       /* the only block-wide barrier; waves are independent below */
 
-	const uint32_t k = p.k, m = sp.m;
-	const uint32_t mmask = m >= 16 ? 0xffffffffu : ((1u << (2 * m)) - 1u);
-	const uint32_t mtop = 2 * (m - 1);
+	const uint32_t k = p.k;
+	SkMinimizer<WIN> mz;
+	mz.init(sp.m);
 	const uint32_t wbits = __float_as_uint(wK);
 	const bool good = wK > p.min_weight;           /* the same for every k-mer without an N */
 	unsigned long long nRaw = 0, nGood = 0;
 	const uint64_t n_items = rv.u_start ? rv.n_units : rv.n_reads;
 	const uint64_t n_tiles = (n_items + 63) / 64;
 	for (uint64_t tile = (uint64_t)blockIdx.x * SKL_WAVES + wave; tile < n_tiles; tile += (uint64_t)gridDim.x * SKL_WAVES) {
-	const uint64_t r0 = tile * 64;
-	const uint32_t nr = (uint32_t)((n_items - r0) < 64 ? (n_items - r0) : 64);
-	const bool have = (uint32_t)lane < nr;
-	uint64_t myStart = 0, myEnd = 0, myRead = 0;
-	bool myDiscard = true;
-	if (have) {
-		if (rv.u_start) { myStart = rv.u_start[r0 + lane]; myEnd = rv.u_end[r0 + lane]; myRead = rv.u_read[r0 + lane]; }
-		else { myRead = r0 + lane; myStart = rv.offsets[myRead]; myEnd = rv.offsets[myRead + 1]; }
-		myDiscard = rv.discarded ? (rv.discarded[myRead] != 0) : false;
-	}
+	const SkTileLane me = sk_tile_lane<false>(rv, n_items, tile, lane);
 	/* PACKED: where this lane's bases are, counted in bases from pkd.bytes */
 	uint64_t myPb = 0, myPe = 0;
-	if (PACKED && have) { myPb = 4 * pkd.off[myRead] + (myStart - rv.offsets[myRead]); myPe = myPb + (myEnd - myStart); }
+	if (PACKED && me.have) { myPb = 4 * pkd.off[me.read] + (me.start - rv.offsets[me.read]); myPe = myPb + (me.end - me.start); }
 	uint32_t tRaw = 0, tGood = 0;
 	uint32_t done = 0;
-	while (done < nr) {
-		const uint64_t B0 = PACKED ? __shfl(myPb, (int)done, 64) : __shfl(myStart, (int)done, 64);
-		const bool fits = have && (uint32_t)lane >= done && (PACKED ? (myPb >= B0 && myPe - B0 <= (uint64_t)SK_PACKED_SPAN) : (myEnd - B0 <= (uint64_t)TILE_SPAN));
-		unsigned long long fm = __ballot(fits) >> done;
-		uint32_t n = ~fm ? (uint32_t)__builtin_ctzll(~fm) : 64u;
-		if (n > nr - done) n = nr - done;
-		if (n == 0) {                                        /* read longer than a tile */
-			if (lane == 0) atomicOr(p.err, (uint32_t)ERR_READ_TOO_LONG);
-			done += 1;
-			continue;
-		}
-		uint64_t B1 = __shfl(PACKED ? myPe : myEnd, (int)(done + n - 1), 64);
-		if (PACKED) {      /* (nothing says that the reads' bytes lie in the order of the reads: the tile ends where the last of its reads does) */
-			uint64_t e = ((uint32_t)lane >= done && (uint32_t)lane < done + n) ? myPe : 0;
-#pragma unroll
-			for (int o = 32; o > 0; o >>= 1) { const uint64_t x = __shfl_xor(e, o, 64); e = x > e ? x : e; }
-			B1 = e;
-		}
+	while (done < me.nr) {
+		const uint64_t B0 = PACKED ? __shfl(myPb, (int)done, 64) : __shfl(me.start, (int)done, 64);
+		const bool fits = me.have && (uint32_t)lane >= done && (PACKED ? (myPb >= B0 && myPe - B0 <= (uint64_t)SK_PACKED_SPAN) : (me.end - B0 <= (uint64_t)TILE_SPAN));
+		const uint32_t n = sk_fitting_run(fits, done, me.nr, lane, p.err);
+		if (n == 0) { done += 1; continue; }
+		uint64_t B1 = __shfl(PACKED ? myPe : me.end, (int)(done + n - 1), 64);
+		/* (nothing says that the reads' bytes lie in the order of the reads: the tile ends where the last of its reads does) */
+		if (PACKED) B1 = sk_wave_max(((uint32_t)lane >= done && (uint32_t)lane < done + n) ? myPe : (uint64_t)0);
 		const uintptr_t gb = PACKED ? (uintptr_t)pkd.bytes + (uintptr_t)(B0 >> 2) : (uintptr_t)rv.bases + B0;
 		const uintptr_t ab = gb & ~(uintptr_t)15;
 		const uint32_t nb16 = PACKED ? (uint32_t)(((uintptr_t)pkd.bytes + (uintptr_t)((B1 + 3) >> 2) - ab + 15) >> 4) : (uint32_t)(((uintptr_t)rv.bases + B1 - ab + 15) >> 4);
@@ -1102,26 +1196,20 @@ void sk_extract_lean_kernel(ReadsView rv, DevParams p, SkParams sp, PoolView poo
 #pragma unroll
 			for (int c = 0; c < STG; c++) {
 				const uint32_t idx = (uint32_t)lane + 64u * c;
-				const uint32_t w4[4] = {vb[c].x, vb[c].y, vb[c].z, vb[c].w};
-				uint32_t packed = 0, nflags = 0;
-#pragma unroll
-				for (int b = 0; b < 16; b++) {
-					const uint32_t code = base_code((uint8_t)(w4[b >> 2] >> (8 * (b & 3))));
-					packed |= (code & 3u) << (30 - 2 * b);          /* markup packs as A */
-					nflags |= (code >> 2) << b;
-				}
+				uint32_t packed, nflags;
+				sk_pack16(vb[c], packed, nflags);
 				if (idx < nb16 + 4u && idx < (uint32_t)SK_GROUPS) { pk[idx] = idx < nb16 ? packed : 0u; nm[idx] = idx < nb16 ? (uint16_t)nflags : (uint16_t)0; }      /* (four groups of padding behind the data) */
 			}
 		}
 		sk_wave_lds_order();
 
-		const bool active = have && (uint32_t)lane >= done && (uint32_t)lane < done + n && !myDiscard;
-		const uint32_t L = active ? (uint32_t)(myEnd - myStart) : 0;
-		const uint32_t rbOff = active ? (PACKED ? (uint32_t)(myPb - 4 * (uint64_t)(ab - (uintptr_t)pkd.bytes)) : (uint32_t)(gb - ab) + (uint32_t)(myStart - B0)) : 0u;
+		const bool active = me.have && (uint32_t)lane >= done && (uint32_t)lane < done + n && !me.discard;
+		const uint32_t L = active ? (uint32_t)(me.end - me.start) : 0;
+		const uint32_t rbOff = active ? (PACKED ? (uint32_t)(myPb - 4 * (uint64_t)(ab - (uintptr_t)pkd.bytes)) : (uint32_t)(gb - ab) + (uint32_t)(me.start - B0)) : 0u;
 		if (PACKED && pkd.mk_off) {      /* applyMarkup (src/TwoBitSequence.cpp:314-340) on the tile */
 			if (active) {
-				const uint64_t inRead = myStart - rv.offsets[myRead];      /* a unit of a long read starts that far inside it */
-				for (uint64_t e = pkd.mk_off[myRead]; e < pkd.mk_off[myRead + 1]; e++) {
+				const uint64_t inRead = me.start - rv.offsets[me.read];      /* a unit of a long read starts that far inside it */
+				for (uint64_t e = pkd.mk_off[me.read]; e < pkd.mk_off[me.read + 1]; e++) {
 					const uint64_t mp = pkd.mk_pos[e];
 					if (mp < inRead || mp - inRead >= L) continue;
 					const uint32_t x = rbOff + (uint32_t)(mp - inRead), code = base_code(pkd.mk_char[e]);
@@ -1131,67 +1219,26 @@ void sk_extract_lean_kernel(ReadsView rv, DevParams p, SkParams sp, PoolView poo
 			}
 			sk_wave_lds_order();
 		}
-		uint32_t Lmax = L;
-#pragma unroll
-		for (int o = 32; o > 0; o >>= 1) { uint32_t x = __shfl_xor(Lmax, o, 64); Lmax = x > Lmax ? x : Lmax; }
-		const uint64_t ord0 = rv.stream_base + myStart;      /* + k-mer index = stream ordinal of the occurrence */
-		uint32_t zc = 0;
-		constexpr int ZN = W == 1 ? 1 : (W == 2 ? 2 : 3);      /* history of N flags, one bit per position: k + 1 bits */
-		uint64_t zbits[3] = {0, 0, 0};
-		uint32_t mf = 0, mr = 0;
-		/* WIN > 16: the minimum over the last WIN hashes is the smaller of the block minimum over the last 16 and the block minimum of
-		 * WIN - 16 positions earlier -- a delay line of WIN - 16 registers (mprev), indexed by the position modulo its length, which is a
-		 * constant after unrolling as long as that length divides the 16 positions of an iteration: WIN = 17, 18, 20, 24, 32 */
-		constexpr int WB = WIN > 16 ? 16 : WIN;
-		constexpr int WD = WIN > 16 ? WIN - 16 : 1;
-		static_assert(WIN <= 16 || SK_WINDOW % WD == 0, "the delay line of a window above 16 has to divide SK_WINDOW");
-		uint32_t hs[WB], mprev[WD];
-#pragma unroll
-		for (int i = 0; i < WB; i++) hs[i] = 0xffffffffu;
-#pragma unroll
-		for (int i = 0; i < WD; i++) mprev[i] = 0xffffffffu;
-		uint32_t pref = 0xffffffffu;
+		const uint32_t Lmax = sk_wave_max(L);
+		const uint64_t ord0 = rv.stream_base + me.start;      /* + k-mer index = stream ordinal of the occurrence */
+		SkZeroHistory<W == 1 ? 1 : (W == 2 ? 2 : 3)> zh;      /* flags: an N */
+		zh.reset();
+		mz.reset();
 		bool runOpen = false, runInWin = false;
 		uint32_t runStart = 0, runN = 0, runMh = 0;
-		/* records booked but not yet written: start | n << 16 | 1 << 24 | 1 << 30 (an address, not a booking) | 1 << 31, minimizer hash, what the booking add returned */
-		uint32_t q_info[SKL_RR], q_mh[SKL_RR]; unsigned long long q_booked[SKL_RR];
-#pragma unroll
-		for (int r = 0; r < SKL_RR; r++) { q_info[r] = 0; q_mh[r] = 0; q_booked[r] = 0; }
-		auto flush_pending = [&]() {
-			uint64_t at[SKL_RR]; bool waits[SKL_RR];
-#pragma unroll
-			for (int r = 0; r < SKL_RR; r++) {
-				waits[r] = false; at[r] = ~0ull;
-				if (q_info[r] >> 31) {
-					const uint32_t nn = (q_info[r] >> 16) & 0xffu;
-					if ((q_info[r] >> 30) & 1u) at[r] = q_booked[r];
-					else at[r] = sk_append_settle(sp.state, sk_list_of(q_mh[r], sp.list_bits), 1 + sk_base_granules(nn, k), q_booked[r], slab, pool, waits[r]);
-				}
-			}
-#pragma unroll
-			for (int r = 0; r < SKL_RR; r++) if (waits[r]) {
-				const uint32_t nn = (q_info[r] >> 16) & 0xffu;
-				at[r] = sk_append(sp.state, sk_list_of(q_mh[r], sp.list_bits), 1 + sk_base_granules(nn, k), slab, pool);
-			}
-#pragma unroll
-			for (int r = 0; r < SKL_RR; r++) {
-				if ((q_info[r] >> 31) && at[r] != ~0ull) {
-					const uint32_t start = q_info[r] & 0xffffu, nn = (q_info[r] >> 16) & 0xffu;
-					const uint32_t nbg = sk_base_granules(nn, k);
-					uint4 *dst = (uint4 *)pool.base + at[r];
-					const uint64_t ord = ord0 + start;
-					dst[0] = sk_make_header(ord, nn, true, 1 + nbg, 0u, q_mh[r], wbits);
-					const uint32_t xb = rbOff + start;
-					for (uint32_t b = 0; b < nbg; b++)
-						dst[1 + b] = make_uint4(sk_bases16(pk, xb + 64 * b), sk_bases16(pk, xb + 64 * b + 16), sk_bases16(pk, xb + 64 * b + 32), sk_bases16(pk, xb + 64 * b + 48));
-				}
-				q_info[r] = 0;
-			}
+		/* the pending records: every one uniform, header and bases and nothing else */
+		SkPending<SKL_RR> pend;
+		pend.clear();
+		const auto need = [&](uint32_t q) { return 1 + sk_base_granules(sk_pend_n(q), k); };
+		const auto flush_pending = [&]() {
+			pend.flush(need, [&](int r, uint4 *dst) {
+				const uint32_t q = pend.info[r], start = sk_pend_start(q), nn = sk_pend_n(q);
+				sk_write_header_and_bases(dst, sk_make_header(ord0 + start, nn, true, need(q), 0u, pend.mh[r], wbits), pk, rbOff + start, sk_base_granules(nn, k));
+			}, sp, slab, pool, 0u);
 		};
 		for (uint32_t jb = 0; jb < Lmax || __any(runOpen); jb += SK_WINDOW) {
 			const uint32_t nmw = sk_flags16(nm, rbOff + jb);
-			const int32_t xm = (int32_t)(rbOff + jb) - (int32_t)sp.off;
-			const uint32_t mpkw = xm >= 0 ? sk_bases16(pk, (uint32_t)xm) : (xm > -16 ? sk_bases16(pk, 0u) >> (2 * (uint32_t)(-xm)) : 0u);
+			const uint32_t mpkw = SkMinimizer<WIN>::bases16(pk, rbOff + jb, sp.off);
 			const bool cinOpen = runOpen; const uint32_t cinStart = runStart, cinN = runN, cinMh = runMh;
 			uint32_t Sm = 0, Vm = 0;
 			runInWin = false;
@@ -1203,61 +1250,21 @@ void sk_extract_lean_kernel(ReadsView rv, DevParams p, SkParams sp, PoolView poo
 			const uint32_t km = tk < 16u ? (inmask & ~((1u << tk) - 1u)) : 0u;
 			const uint32_t zm = nmw & inmask;
 			uint32_t zcpos = 0;                                              /* positions at which the k bases behind hold an N */
-			if (__any(zm != 0 || zc != 0)) {
-				if (k >= (uint32_t)SK_WINDOW) {
-					uint32_t field;                                          /* history bits k-16 .. k-1 (bit b = position jb - 1 - b) */
-					{
-						const uint32_t lo = k - 16u, wi = lo >> 6, sh = lo & 63u;
-						uint64_t a = zbits[wi < (uint32_t)ZN ? wi : ZN - 1];
-						if (wi >= (uint32_t)ZN) a = 0;
-						uint64_t b = (wi + 1 < (uint32_t)ZN) ? zbits[wi + 1 < (uint32_t)ZN ? wi + 1 : ZN - 1] : 0ull;
-						field = (uint32_t)((sh ? (a >> sh) | (b << (64u - sh)) : a) & 0xffffu);
-					}
-					const uint32_t lm = __builtin_bitreverse32(field) >> 16;     /* bit t: the flag that leaves at position jb + t */
-					uint32_t zcw = zc;
-#pragma unroll
-					for (int t = 0; t < SK_WINDOW; t++) { zcw += (zm >> t) & 1u; zcw -= (lm >> t) & 1u; zcpos |= (zcw != 0 ? 1u : 0u) << t; }
-					zc = zcw;
-					if (ZN > 2) zbits[2] = (zbits[2] << 16) | (zbits[1] >> 48);
-					if (ZN > 1) zbits[1] = (zbits[1] << 16) | (zbits[0] >> 48);
-					zbits[0] = (zbits[0] << 16) | (uint64_t)(__builtin_bitreverse32(zm) >> 16);
-				} else {
+			if (__any(zm != 0 || zh.zc != 0)) {
+				if (k >= (uint32_t)SK_WINDOW) zcpos = zh.advance16(zm, k);
+				else {
 #pragma nounroll
 					for (uint32_t t = 0; t < (uint32_t)SK_WINDOW; t++) {
-						const bool z = ((zm >> t) & 1u) != 0;
-						if (ZN > 2) zbits[2] = (zbits[2] << 1) | (zbits[1] >> 63);
-						if (ZN > 1) zbits[1] = (zbits[1] << 1) | (zbits[0] >> 63);
-						zbits[0] = (zbits[0] << 1) | (z ? 1ull : 0ull);
-						zc += z ? 1u : 0u;
-						zc -= (uint32_t)((zbits[ZN == 1 ? 0 : (k >> 6)] >> (k & 63)) & 1ull);
-						zcpos |= (zc != 0 ? 1u : 0u) << t;
+						zh.advance1(((zm >> t) & 1u) != 0, k);
+						zcpos |= (zh.zc != 0 ? 1u : 0u) << t;
 					}
 				}
-			} else if (live) {      /* no N anywhere near: the histories move on by sixteen clean positions */
-				if (ZN > 2) zbits[2] = (zbits[2] << 16) | (zbits[1] >> 48);
-				if (ZN > 1) zbits[1] = (zbits[1] << 16) | (zbits[0] >> 48);
-				zbits[0] <<= 16;
-			}
+			} else if (live) zh.shift16_clean();      /* no N anywhere near: the history moves on by sixteen clean positions */
 			Vm = good ? (km & ~zcpos) : 0u;
 			tRaw += (uint32_t)__builtin_popcount(km); tGood += (uint32_t)__builtin_popcount(Vm);
 #pragma unroll
 			for (int t = 0; t < SK_WINDOW; t++) {
-				/* minimizer of the k-mer that ends at position jb + t: m-mer ending sp.off positions back, canonical, hashed; minimum of the
-				 * last WIN of them by block decomposition (prefix minimum of the current block, suffix minima of the one before) */
-				const uint32_t mc = (mpkw >> (30 - 2 * t)) & 3u;
-				mf = ((mf << 2) | mc) & mmask;
-				mr = (mr >> 2) | ((3u - mc) << mtop);
-				const uint32_t x = sk_mmer_hash(mf < mr ? mf : mr);
-				const int r = t % WB;
-				pref = r == 0 ? x : (x < pref ? x : pref);
-				hs[r] = x;
-				uint32_t M = pref;
-				if (r < WB - 1) { const uint32_t sfx = hs[r + 1 < WB ? r + 1 : 0]; M = sfx < M ? sfx : M; }
-				else {
-#pragma unroll
-					for (int u = WB - 2; u >= 0; u--) hs[u] = hs[u] < hs[u + 1] ? hs[u] : hs[u + 1];
-				}
-				if constexpr (WIN > 16) { const uint32_t m16 = M; const uint32_t before = mprev[t % WD]; M = before < M ? before : M; mprev[t % WD] = m16; }
+				const uint32_t M = mz.step(t, mpkw);
 				const bool valid = ((Vm >> t) & 1u) != 0;
 				const bool cont = runOpen && M == runMh && runN < SK_MAX_N;
 				const bool nw = valid && !cont;
@@ -1270,66 +1277,38 @@ void sk_extract_lean_kernel(ReadsView rv, DevParams p, SkParams sp, PoolView poo
 				mhr[t * 64 + lane] = M;
 			}
 			if (!live) runOpen = false;
-			/* gather: every run that ended in this window becomes a record of its list (as in sk_extract_kernel; every record is uniform) */
-			const uint32_t brk = (~Vm | Sm) & 0xffffu;
-			bool pendC = false; uint32_t lead = 16;
-			if (cinOpen) { lead = (uint32_t)__builtin_ctz(brk | 0x10000u); pendC = lead < 16; }
-			uint32_t Srem = Sm;
-			if (runOpen && runInWin && Sm) Srem &= ~(1u << (31 - __builtin_clz(Sm)));      /* the run still open is the last one begun */
+			/* gather (SkGather, SkPending): every record is uniform, so a round waits for the next window unless another follows */
+			SkGather g(Vm, Sm, cinOpen, runOpen && runInWin);
 			flush_pending();
 			bool firstRound = true;
 			const uint32_t hotNow = slab->hot_list;
-			while (__any(pendC || Srem)) {
+			while (__any(g.more())) {
 #pragma unroll
 				for (int r = 0; r < SKL_RR; r++) {
-					q_info[r] = 0;
-					if (pendC) { pendC = false; q_info[r] = (1u << 31) | (1u << 24) | ((cinN + lead) << 16) | cinStart; q_mh[r] = cinMh; }
-					else if (Srem) {
-						const uint32_t pos = (uint32_t)__builtin_ctz(Srem); Srem &= Srem - 1;
-						const uint32_t end = pos + 1 + (uint32_t)__builtin_ctz((brk >> (pos + 1)) | (1u << (15 - pos)));
-						q_info[r] = (1u << 31) | (1u << 24) | ((end - pos) << 16) | (jb + pos + 1 - k);
-						q_mh[r] = mhr[pos * 64 + lane];
+					pend.info[r] = 0;
+					if (g.pendC) { g.pendC = false; pend.info[r] = sk_pend_make(cinStart, cinN + g.lead, true, 0u); pend.mh[r] = cinMh; }
+					else if (g.Srem) {
+						uint32_t pos, nn;
+						g.next(pos, nn);
+						pend.info[r] = sk_pend_make(jb + pos + 1 - k, nn, true, 0u);
+						pend.mh[r] = mhr[pos * 64 + lane];
 					}
-					if (q_info[r] >> 31) {
-						const uint32_t nn = (q_info[r] >> 16) & 0xffu;
-						const uint32_t need = 1 + sk_base_granules(nn, k), myList = sk_list_of(q_mh[r], sp.list_bits);
-						if (myList == hotNow) { q_booked[r] = sk_append_hot(slab, myList, need, pool); q_info[r] |= 1u << 30; }
-						else q_booked[r] = atomicAdd(sp.state + myList, (unsigned long long)need);
-					}
+					pend.book(r, need, hotNow, sp, slab, pool, 0u);
 				}
-				if (!firstRound || __any(pendC || Srem)) flush_pending();      /* more rounds to come: settle now */
+				if (!firstRound || __any(g.more())) flush_pending();
 				firstRound = false;
 			}
-			if (slab->next >= 64u) {
-				__builtin_amdgcn_wave_barrier();
-				if (lane == 0) { const uint32_t used = slab->next; slab->base[0] = slab->base[1]; slab->base[1] = atomicAdd(pool.head, 64u); slab->next = used >= 128u ? 64u : used - 64u; }
-				__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-				__builtin_amdgcn_wave_barrier();
-			}
+			sk_slab_refill(slab, pool, lane);
 		}
 		flush_pending();                   /* the last window's records: their bases are read from this tile */
 		done += n;
 		sk_wave_lds_order();               /* all lanes are done reading the tile before it is overwritten */
 	}
 	nRaw += tRaw; nGood += tGood;
-	if (sp.track && have && !myDiscard) {
-		SkTrackRec *tr = sp.track + myRead;
-		if (rv.u_start) { atomicAdd(&tr->raw, tRaw); atomicAdd(&tr->good, tGood); atomicMax(&tr->end_ordinal, (unsigned long long)(rv.stream_base + myEnd)); }
-		else { tr->raw = tRaw; tr->good = tGood; tr->end_ordinal = rv.stream_base + myEnd; }
+	sk_tile_finish(sp, rv, me, tRaw, tGood);
 	}
-	}
-	/* chunks of the slabs nobody took belong to no list */
-	__builtin_amdgcn_wave_barrier();
-	{
-		const uint32_t used = slab->next < 128u ? slab->next : 128u;
-		for (uint32_t idx = used + (uint32_t)lane; idx < 128u; idx += 64) { const uint32_t c = slab->base[idx >> 6] + (idx & 63u); if (c < pool.cap) { pool.chunk_list[c] = NO_CHUNK; pool.chunk_count[c] = 0; } }
-		if (lane == 0 && slab->hot_list < SK_LIST_LOCKED) {      /* the open chunk of the wavefront's hot chain */
-			const uint32_t hc = (uint32_t)(slab->hot_state >> 32), hf = (uint32_t)slab->hot_state;
-			if (hc < pool.cap) pool.chunk_count[hc] = hf < SK_CHUNK_G ? hf : SK_CHUNK_G;
-		}
-	}
-	nRaw = wave_sum(nRaw); nGood = wave_sum(nGood);
-	if (lane == 0) { atomicAdd(&p.stats->raw, nRaw); atomicAdd(&p.stats->good, nGood); }
+	sk_slab_close(slab, pool, lane);
+	sk_stats_finish(p, nRaw, nGood, lane);
 }
 
 /* reverse complement of a left-justified k-mer of W words, left-justified again */

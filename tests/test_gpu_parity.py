@@ -3,6 +3,7 @@ bit-exact k-mer sets, counts, direction bias, extension tallies, statistics, sin
 bytes and on-disk images; weightedCount within the documented tolerance (it is order
 dependent in the reference itself: the first sighting is quantised to 1/254 steps,
 src/KmerTrackingData.h:646,658)."""
+import functools
 import os
 
 import numpy as np
@@ -1630,6 +1631,117 @@ def test_twobit_packed_bytes_staged_directly(k, uq):
         assert pa.stats() == pt.stats(), (layout, direct)
         for which in (KMR_MAP_WEAK, KMR_MAP_SINGLETON):
             assert np.array_equal(pa.image(which), pt.image(which)), (layout, direct, which)
+
+
+WALK_TILE_SPAN = 9824      # TILE_SPAN of kmr_kernels.hpp: the bytes of reads one staging pass of an extraction wavefront takes
+
+
+@functools.lru_cache(maxsize=None)
+def _walk_edge_reads(k, quality):
+    """The read set of test_extraction_walk_edges: 65 reads, the same bases for every k but for the lengths and the N distance that
+    are stated in k.  quality: 'none', 'one' (one character) or 'noisy'."""
+    rng = np.random.default_rng(77)
+    genome = np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, 12000)]
+    N = ord("N")
+
+    def frag(L):
+        st = int(rng.integers(0, genome.size - L + 1))
+        return bytearray(genome[st:st + L].tobytes())
+
+    # 50 reads of 200 bases in front: 10 000 bytes, more than one staging span, so the first tile's fitting run ends inside them
+    reads = [frag(200) for _ in range(50)]
+    reads[3][0] = N                                            # an N at the first base
+    reads[7][199] = N                                          # ... at the last
+    reads[11][60] = N; reads[11][60 + k] = N                   # two exactly k apart: one flag leaves the history as the next enters
+    reads[15][35] = N; reads[15][50] = N; reads[15][70] = N    # one in each of the windows 2, 3 and 4
+    reads += [frag(L) for L in (0, 1, k - 1, k, k + 1, 15, 16, 17)]
+    reads.append(bytearray(b"A" * 400))                        # one minimizer for 400 - k + 1 k-mers: records end at SK_MAX_N = 128
+    reads += [frag(WALK_TILE_SPAN), frag(WALK_TILE_SPAN + 1)]  # the longest read that is one unit, the shortest that is two
+    reads += [frag(200) for _ in range(4)]
+    assert len(reads) == 65                                    # the second tile has one live lane (two where the long read is two units)
+    qrng = np.random.default_rng(78)
+    qv = np.array([40, 30, 20, 10, 2]) + 33
+    quals = {"none": None, "one": [b"I" * len(r) for r in reads],
+             "noisy": [qv[qrng.choice(5, size=len(r), p=[0.80, 0.10, 0.05, 0.04, 0.01])].astype(np.uint8).tobytes() for r in reads]}[quality]
+    disc = np.zeros(65, np.uint8)
+    disc[25] = 1                                               # a discarded read in the middle of the first tile
+    return ReadBatch([bytes(r) for r in reads], quals, disc)
+
+
+def _walk_edge_config(k):
+    return default_config(k, estimated_raw_kmers=40000)
+
+
+@functools.lru_cache(maxsize=None)
+def _walk_edge_oracle(k, quality):
+    """what the serial oracle makes of the set: stats, the two images, the per-k-mer size history without / with the forced last element"""
+    o = OracleSpectrum(_walk_edge_config(k))
+    o.add_reads(_walk_edge_reads(k, quality))
+    o.finalize(1)
+    hist = tuple(o.size_tracker(per_read=False, force_last=f) for f in (False, True))
+    out = (o.stats(), o.image(KMR_MAP_WEAK), o.image(KMR_MAP_SINGLETON)) + hist
+    for a in out[1:]:
+        a.setflags(write=False)
+    return out
+
+
+def _walk_edge_feed_packed(p, rb):
+    """the set as kmr_add_reads_twobit_dev takes it: packed 2-bit bytes, the N's as markups, one quality character"""
+    torch = pytest.importorskip("torch")
+    tw, _, (mp, mc, mo) = _pack_twobit(rb)
+    dev = torch.device("cuda", 0)
+    t = lambda a, dt=None: torch.from_numpy(np.ascontiguousarray(a).view(dt) if dt else np.ascontiguousarray(a)).to(dev)
+    d_tw, d_off, d_mo, d_mp, d_mc, d_d = t(tw), t(rb.offsets, np.int64), t(mo, np.int64), t(mp, np.int32), t(mc), t(rb.discarded)
+    p.buildKmerSpectrumTwoBitDevice(d_tw.data_ptr(), None, d_off.data_ptr(), rb.n, int(rb.offsets[-1]), uniform_quality=ord("I"),
+                                    markup_offsets_ptr=d_mo.data_ptr(), markup_pos_ptr=d_mp.data_ptr(), markup_char_ptr=d_mc.data_ptr(),
+                                    first_read_idx=0, discarded_ptr=d_d.data_ptr())
+    p.sync()
+
+
+@pytest.mark.parametrize("k,win,quality,variant",
+                         [(k, win, q, "text") for k, win in ((13, 0), (21, 0), (31, 0), (51, 0), (51, 32)) for q in ("none", "one", "noisy")] +
+                         [(31, 0, "one", "tracker"), (31, 0, "noisy", "tracker"), (31, 0, "one", "packed")])
+def test_extraction_walk_edges(k, win, quality, variant):
+    """What the two extraction kernels' shared walk decides, on one tiny read set (_walk_edge_reads): a second tile with hardly a live
+    lane, reads of 0, 1, k - 1, k, k + 1, 15, 16, 17 and 200 bases, a tile whose reads need two staging passes, a read of exactly one
+    staging span and one a base longer (cut into units), N's at a read's first and last base, two N's k apart, N's in three
+    consecutive windows, a homopolymer longer than a record may be, a discarded read inside a tile.  Minimizer windows of 4, 8, 16
+    (the defaults of k = 13, 21, 31 / 51) and 32, keys of one and two words; no qualities and one quality character (the lean kernel,
+    held byte for byte to the general one as well) and qualities of their own (the general kernel).  Every case against the serial
+    oracle's stats and images; with the size tracker also its history; once from packed bytes with markups (PACKED, with units).
+    Packed input with the size tracker is left out: the library refuses that pair (it unpacks first)."""
+    rb = _walk_edge_reads(k, quality)
+    cfg = _walk_edge_config(k)
+    so, weak_o, single_o, hist_o, hist_o_forced = _walk_edge_oracle(k, quality)
+    lean = quality != "noisy"
+    images = []
+    for tune in ([dict(), dict(lean_extract=0)] if lean else [dict()]):
+        if win:
+            tune["superkmer_window"] = win
+        c = ka.default_config(k)
+        for name, _ in cfg._fields_:
+            setattr(c, name, getattr(cfg, name))
+        c.build_mode = 3
+        c.size_tracker = 1 if variant == "tracker" else 0
+        p = ka.KmerSpectrum(c).tune(**tune)
+        if win:
+            assert p.build_info("superkmer_window") == win
+        if variant == "packed":
+            _walk_edge_feed_packed(p, rb)
+        else:
+            add(p, rb)
+        p.finalize(1)
+        assert p.stats() == so, (tune, so, p.stats())
+        compare_weak_images(weak_o, p.image(KMR_MAP_WEAK), p.kb, False)
+        assert np.array_equal(single_o, p.image(KMR_MAP_SINGLETON)), tune
+        if variant == "tracker":
+            for force, want in ((False, hist_o), (True, hist_o_forced)):
+                got = p.getSizeTracker(force_last=force).elements
+                assert got.shape == want.shape and len(want) > 50
+                assert np.array_equal(got, want), (tune, np.argwhere(got != want)[:5])
+        images.append((p.image(KMR_MAP_WEAK), p.image(KMR_MAP_SINGLETON)))
+    if lean:      # the lean kernel's product and the general kernel's, byte for byte
+        assert np.array_equal(images[0][0], images[1][0]) and np.array_equal(images[0][1], images[1][1])
 
 
 @pytest.mark.parametrize("mode", [3, 2])
