@@ -218,7 +218,13 @@ int kmr_lookup_reads_weighted(kmr_handle *h, const char *bases, const uint64_t *
  * N/X markup (_setNumKmers :1037-1047), first longest run of k-mers with count >= minimum_kmer_score
  * (trimReadByMinimumKmerScore :949-1014, bimodal detection off), score of that run (scoreReadByScoringType
  * :1094-1180) and setTrimHeaders (:1015-1036).  Per read: trim_offset (bases), trim_length (bases, run + k - 1,
- * 0 = nothing left), score (-1 if nothing left; KS_SUM leaves 0 as the reference does), was_trimmed. */
+ * 0 = nothing left), score (-1 if nothing left; KS_SUM leaves 0 as the reference does), was_trimmed.
+ * A markup other than N, X and '.' (an IUPAC code, a lower-case n) does not cut: the reference looks the k-mers that hold it up
+ * with the 'A' compressSequence stores in its place (src/TwoBitSequence.cpp:253-260, getKmersForRead src/ReadSelector.h:413-415).
+ * The per-k-mer probes do that; the streaming pass answers zero for such a k-mer, so kmr_score_reads, kmr_score_read_batch and
+ * kmr_filter_read_batch* first scan the batch's bases (one pass and one host wait per call) and probe the WHOLE batch if a single
+ * such base is in it: slower by the difference of the two lookup paths, which has not been measured for such batches.
+ * kmr_build_info "score_path" tells which path the last call took.  kmr_lookup_requests_dev leaves such k-mers unasked (zero). */
 typedef enum kmr_scoring { KMR_SCORE_SUM = 0, KMR_SCORE_MEDIAN = 1, KMR_SCORE_MIN = 2, KMR_SCORE_MAX = 3, KMR_SCORE_AVG = 4 } kmr_scoring;
 int kmr_score_reads(kmr_handle *h, const char *bases, const uint64_t *offsets, uint64_t n_reads,
                     double minimum_kmer_score, int scoring_type,
@@ -489,7 +495,8 @@ int kmr_insert_records(kmr_handle *h, const void *host_records, uint64_t n_recor
  * kmr_scatter_counts_dev: position_counts[pos[j]] = counts[j] for the answers of one owner segment.
  * kmr_score_counts_dev: trimReadByMinimumKmerScore + scoring + setTrimHeaders (as kmr_score_reads) from counts indexed
  * by base position (u32 position_counts[total_bases], zero where no answer was written); dev_bases 16-byte aligned and
- * padded by 64 bytes as for kmr_add_reads_dev.
+ * padded by 64 bytes as for kmr_add_reads_dev.  Every count must be <= 65535, as every answer of kmr_lookup_keys_dev is (the
+ * count saturates there): where a group of reads fits, the kernel keeps its counts as 16-bit values.
  * All asynchronous on the handle's stream except kmr_score_counts_dev, which returns host arrays. */
 int kmr_lookup_requests_dev(kmr_handle *h, const void *dev_bases, const void *dev_offsets, uint64_t n_reads, uint64_t total_bases,
                             void *dev_keys, void *dev_pos, uint64_t seg_capacity, void *dev_seg_counts);
@@ -901,7 +908,7 @@ void *kmr_stream(kmr_handle *h);
  * (0 = one per CU), "entry_share" (initial entry-buffer share of the count pass, < 0 = from the probe), "lookup_table",
  * "narrow_tallies", "keep_level1_state" (1 / 0), "superkmer_minimizer" (minimizer length of build_mode 3, 0 = default),
  * "stream_lookups" (1: kmr_score_* gets its k-mer counts from a streaming pass over minimizer lists where k allows it; 0: per-k-mer
- * probes of the lookup table), "long_list_chunks" (super-k-mer lists of more 1 KB chunks are counted / looked up in pieces, 1024), "coarse_lists" (owner exchange:
+ * probes of the lookup table; a batch that holds a base which is neither ACGT nor N, X or '.' is probed whatever this says, see kmr_score_reads), "long_list_chunks" (super-k-mer lists of more 1 KB chunks are counted / looked up in pieces, 1024), "coarse_lists" (owner exchange:
  * 1 = scatter into and exchange coarse lists that the owner splits before the count pass, 0 = the job's fine lists; default 0).
  *   "pow2_lists" (1: the list count of build_mode 3 is always a power of two; default 0: a single GPU's build takes est / list_aim lists),
  *   "list_aim" (k-mers per list that count aims for; default 1450 when every k-mer weighs the same, 1700 raw k-mers otherwise, 800 with
@@ -931,7 +938,9 @@ int kmr_tune(kmr_handle *h, const char *knob, double value);
  * "saturated_batches" = the weak entries of count 256 or more the last kmr_finalize of build_mode 3 redid in input order (all of them,
  * every time) and in how many batches, "bb_path" = how the last kmr_finalize bucketed the weak map (0: per-bucket scatter and sort, 1: radix
  * partition with measured bins, 2: with bins of one capacity), "bb_fallback" = 1 if a bin overflowed its capacity and the map was made again
- * with measured bins,
+ * with measured bins, "score_path" = where the last kmr_score_reads / kmr_score_read_batch / kmr_filter_read_batch* on this handle got its
+ * k-mer counts (0: none yet, 1: the streaming pass, 2: per-k-mer probes because the handle or kmr_tune "stream_lookups" says so, 3: probes
+ * because the batch holds a markup other than N, X and '.'),
  * "device_blocks_live" = blocks of device memory the library holds at this moment in the whole process (every handle, read batch
  * and artifact filter; not only h's), "filter_score_ms" / "select_ms" / "select_write_ms" = HIP-event times of the last kmr_filter_read_batch* /
  * kmr_select_reads* on this handle: its scoring, its selection with the writer, the writer alone (0 unless kmr_tune "select_timing" is set),

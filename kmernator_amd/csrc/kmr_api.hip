@@ -2268,6 +2268,7 @@ int kmr_build_info(kmr_handle *h, const char *what, double *value) {
 	else if (k == "early_overflowed") *value = h->last_early_overflowed ? 1.0 : 0.0;
 	else if (k == "bb_path") *value = (double)h->last_bb_path;
 	else if (k == "bb_fallback") *value = h->last_bb_fallback ? 1.0 : 0.0;
+	else if (k == "score_path") *value = (double)h->last_score_path;
 	else if (k == "saturated_keys") *value = (double)h->last_saturated_keys;
 	else if (k == "saturated_batches") *value = (double)h->last_saturated_batches;
 	else if (k == "device_blocks_live") *value = (double)g_blocks_live.load();
@@ -2660,11 +2661,24 @@ int score_reads_core(kmr_handle *h, const uint8_t *s_b, const uint64_t *s_o, uin
 	uint64_t *dcoff = (uint64_t *)p;
 	/* counts per k-mer: as a streaming pass over minimizer lists (indexed by the k-mer's base position: the reads' own offsets are the
 	 * count offsets), or -- where the handle has no list geometry, or on request -- by probing the lookup table k-mer by k-mer */
-	const bool stream = stream_lookups_possible(h);
+	bool stream = stream_lookups_possible(h);
+	h->last_score_path = stream ? 1 : 2;
 	uint64_t outN = 0, first_off = 0;
 	if (stream) {
 		HIPCHK(h, hipMemcpy(&outN, s_o + n_reads, 8, hipMemcpyDeviceToHost)); HIPCHK(h, hipMemcpy(&first_off, s_o, 8, hipMemcpyDeviceToHost));
-	} else {
+		/* the streaming pass answers zero for a k-mer that holds any markup; that is what the reference scores only behind an
+		 * N, X or '.', so a batch with another markup (an IUPAC code, a lower-case n) is probed k-mer by k-mer: the whole
+		 * batch, for one such base.  Every streaming call pays one pass over its bases and a host wait for the answer. */
+		if (outN > first_off) {
+			uint32_t other = 0;
+			HIPCHK(h, hipMemsetAsync(dkc, 0, 4, h->stream));
+			hipLaunchKernelGGL(other_markup_kernel, dim3(grid_for((outN - first_off) / 16 + 2)), dim3(256), 0, h->stream, s_b, first_off, outN, dkc);
+			HIPCHK(h, hipGetLastError());
+			HIPCHK(h, hipMemcpyAsync(&other, dkc, 4, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
+			if (other) { stream = false; h->last_score_path = 3; }
+		}
+	}
+	if (!stream) {
 		hipLaunchKernelGGL(kmer_capacity_kernel, dim3(grid_for(n_reads)), dim3(256), 0, h->stream, rv, h->k, dkc);
 		HIPCHK(h, hipGetLastError());
 		rc = exclusive_scan(h, dkc, n_reads, dcoff); if (rc) return rc;

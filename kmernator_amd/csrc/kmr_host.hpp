@@ -238,6 +238,7 @@ struct KMR_HIDDEN kmr_handle : HandleMem, BuildMem, ExchangeMem {
 	/* the radix partition of the last kmr_finalize (kmr_build_info "bb_path": 0 none, 1 measured bins, 2 bins of one capacity; "bb_fallback": a bin
 	 * overflowed and the build was made again with measured bins), and the overflow word of one that is on the stream (null: none) */
 	int last_bb_path = 0; bool last_bb_fallback = false; uint32_t *bb_overflow = nullptr;
+	int last_score_path = 0;      /* kmr_build_info "score_path": where the last kmr_score_reads / _read_batch / kmr_filter_read_batch got its counts */
 	bool last_early_overflowed = false;                       /* ... or that it voided one because its buffers overflowed */
 	double last_score_ms = 0, last_select_ms = 0, last_write_ms = 0;      /* the last kmr_filter_read_batch* / kmr_select_reads*: scoring, selection + writer, writer alone (HIP events, taken with kmr_tune "select_timing" only; kmr_build_info) */
 	double last_dump_size_ms = 0, last_dump_write_ms = 0;      /* the last kmr_dump_text_size / kmr_dump_text: size pass with its scan, writer (HIP events, taken with kmr_tune "dump_timing" only; kmr_build_info) */

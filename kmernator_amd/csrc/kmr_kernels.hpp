@@ -993,6 +993,24 @@ void score_reads_kernel(const uint8_t *bases, const uint64_t *offsets, uint64_t 
 		}
 	}
 }
+/* Is there a base in [b0, b1) that is neither ACGT nor one of the markups that end a read's k-mers (N, X, '.')?  An IUPAC code
+ * or a lower-case n stays a markup of its own (firstMarkupNorX passes over it) and the reference looks the k-mers that hold it
+ * up with the 'A' compressSequence stores in its place (src/TwoBitSequence.cpp:253-260, ReadSelector::getKmersForRead
+ * src/ReadSelector.h:413-415): the table probes do the same, the streaming lookups leave such k-mers at zero.  bases as above. */
+__global__ void other_markup_kernel(const uint8_t *bases, uint64_t b0, uint64_t b1, uint32_t *found) {
+	bool any = false;
+	for (uint64_t q = (b0 & ~15ull) + (blockIdx.x * (uint64_t)blockDim.x + threadIdx.x) * 16; q < b1; q += (uint64_t)gridDim.x * blockDim.x * 16) {
+		const uint4 v = *(const uint4 *)(bases + q);
+		const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+		for (int j = 0; j < 16; j++) {
+			const uint8_t c = (uint8_t)(w[j >> 2] >> (8 * (j & 3)));
+			const uint64_t pp = q + j;
+			any |= base_code(c) == 4 && c != 'N' && c != 'X' && c != '.' && pp >= b0 && pp < b1;
+		}
+	}
+	if (any) *found = 1u;
+}
 #endif
 
 /* ----------------------------------------------------------------------- */

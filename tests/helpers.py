@@ -469,6 +469,25 @@ def synth_reads(n_reads, read_len=150, genome_len=None, seed=1, err=0.01, qualit
     return ReadBatch.from_arrays(np.ascontiguousarray(bases.reshape(-1)), np.ascontiguousarray(quals.reshape(-1)), offsets)
 
 
+def noisy_ragged_reads(k, n, seed):
+    """synth_reads with noisy qualities and a few N, a quarter of the reads cut to k .. read length bases and one in twenty to fewer
+    than k + 3 (some shorter than k, some empty)"""
+    rl = max(100, k + 40)
+    rb = synth_reads(n, read_len=rl, seed=seed, quality="noisy", n_rate=0.003)
+    rng = np.random.default_rng(seed)
+    seqs, quals = [], []
+    for i in range(rb.n):
+        L = rl
+        r = rng.random()
+        if r < 0.05:
+            L = int(rng.integers(0, k + 3))        # shorter than k, some empty
+        elif r < 0.3:
+            L = int(rng.integers(k, rl + 1))
+        seqs.append(rb.seq(i)[:L])
+        quals.append(rb.qual(i)[:L])
+    return ReadBatch(seqs, quals)
+
+
 def synth_reads_8d(seed, first_read, n_reads, read_len=150, genome_len=None, noisy=False, threads=8):
     """SURVEY.md 8(d)'s generator, CPU statement (orc_synth_reads): the same bytes as kmr_synth_reads_dev for the same arguments"""
     lib = oracle_lib()

@@ -38,7 +38,17 @@ def median_trim_label(counts, k, min_depth=2):
 
 def score_and_trim(counts, seq, k, min_score, scoring):
     """ReadSelector::scoreAndTrimReads for one read (src/ReadSelector.h:949-1207), returning
-    (trim_offset, trim_length_in_bases, score, was_trimmed).  counts = weak-map count per k-mer position."""
+    (trim_offset, trim_length_in_bases, score, was_trimmed).  counts = weak-map count per k-mer position.
+
+    Line by line: the markups of a read are the characters compressSequence does not know (src/TwoBitSequence.cpp:242-269, '.' stored
+    as 'N'), kept as they are -- firstMarkupNorX (:370-379) returns the 1-based position of the first 'N' or 'X' and passes over
+    every other one ('n', 'R', ...).  _setNumKmers (:1037-1047) sets numKmers = position - k (never more than the read has, the
+    markup being inside it) or 0.  setKmerValues (:1064-1076) zeroes the values below the minimum, which the comparison
+    `score >= minimumKmerScore` of trimReadByMinimumKmerScore (:949-1014) then treats as the counts themselves would be treated
+    (a count is never negative: with a minimum <= 0 everything passes either way); `test.score > best.score` keeps the first of
+    equally long runs; wasTrimmed = trimLength < numKmers, also where nothing passes.  scoreReadByScoringType (:1094-1180) sees
+    the run alone: sorted[n / 2], min, max, the f64 sum over n rounded to the f32 ScoreType, and for KS_SUM nothing (the score
+    stays 0).  setTrimHeaders (:1015-1036): a run becomes run + k - 1 bases, no run becomes offset 0, score -1."""
     n = len(counts)
     for i, c in enumerate(seq):                           # firstMarkupNorX + _setNumKmers
         ch = chr(c) if isinstance(c, int) else c

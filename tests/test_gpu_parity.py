@@ -1074,7 +1074,7 @@ def test_score_and_trim_reads_all_types(scoring, stream):
         cnt = counts[int(off[i]):int(off[i + 1])]
         eo, el, es, et = score_and_trim(cnt, rb.seq(i), k, 3, scoring)
         assert (int(to[i]), int(tl[i]), bool(wt[i])) == (eo, el, et), (i, scoring)
-        assert abs(float(sc[i]) - es) <= 1e-5 * max(1.0, abs(es)), (i, scoring, sc[i], es)
+        assert float(sc[i]) == es, (i, scoring, sc[i], es)          # every scoring type is exact in f32, the average rounded once
 
 
 @pytest.mark.parametrize("pipeline", [False, True])

@@ -10,7 +10,7 @@ import pytest
 import kmernator_amd as ka
 from kmernator_amd import _lib
 from helpers import (KMR_MAP_SINGLETON, KMR_MAP_WEAK, KMR_VALUE_EXT, OracleSpectrum, ReadBatch, default_config,
-                     oracle_weighted_kmers, parse_image, synth_reads)
+                     noisy_ragged_reads, oracle_weighted_kmers, parse_image, synth_reads)
 
 KMR_ERR_INVALID_ARG, KMR_ERR_STATE = -1, -5
 NEW_ENTRIES = ("kmr_lookup_weighted", "kmr_lookup_reads_weighted", "kmr_lookup_keys_weighted_dev")
@@ -87,23 +87,6 @@ def absent_keys(k, present, n=64, seed=5):
 def same_bits(a, b):
     a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
     return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
-
-
-def noisy_ragged_reads(k, n, seed):
-    rl = max(100, k + 40)
-    rb = synth_reads(n, read_len=rl, seed=seed, quality="noisy", n_rate=0.003)
-    rng = np.random.default_rng(seed)
-    seqs, quals = [], []
-    for i in range(rb.n):
-        L = rl
-        r = rng.random()
-        if r < 0.05:
-            L = int(rng.integers(0, k + 3))        # shorter than k, some empty
-        elif r < 0.3:
-            L = int(rng.integers(k, rl + 1))
-        seqs.append(rb.seq(i)[:L])
-        quals.append(rb.qual(i)[:L])
-    return ReadBatch(seqs, quals)
 
 
 @pytest.mark.gpu
