@@ -936,7 +936,8 @@ int kmr_tune(kmr_handle *h, const char *knob, double value);
  * kmr_finalize took its lists' entries from kmr_count_lists_prefix (0: it counted everything itself) and how many entries those were,
  * "early_overflowed" = 1 if the last kmr_finalize voided an early count because its buffers had overflowed, "saturated_keys" /
  * "saturated_batches" = the weak entries of count 256 or more the last kmr_finalize of build_mode 3 redid in input order (all of them,
- * every time) and in how many batches, "bb_path" = how the last kmr_finalize bucketed the weak map (0: per-bucket scatter and sort, 1: radix
+ * every time) and in how many batches, "count_attempts" = how often the last kmr_finalize of build_mode 2 or 3 ran its count pass before
+ * the entries fit their buffers (1 unless the first sizes were too small; kmr_tune "entry_share" forces that in tests), "bb_path" = how the last kmr_finalize bucketed the weak map (0: per-bucket scatter and sort, 1: radix
  * partition with measured bins, 2: with bins of one capacity), "bb_fallback" = 1 if a bin overflowed its capacity and the map was made again
  * with measured bins, "score_path" = where the last kmr_score_reads / kmr_score_read_batch / kmr_filter_read_batch* on this handle got its
  * k-mer counts (0: none yet, 1: the streaming pass, 2: per-k-mer probes because the handle or kmr_tune "stream_lookups" says so, 3: probes

@@ -9,7 +9,8 @@
  * KMR_ERR_NO_DEVICE otherwise.
  * Shared decisions have one place each: key width / value kind / minimizer window as template arguments (with_w, with_w_ext,
  * with_win), kernel-argument structs (reads_view, finalize_params, count_out, sk_own_lists), the plan of the count pass over
- * super-k-mer lists (sk_count_uniform, sk_count_select), the host-to-device piece pipeline (tb_feed_pieces).  The heavy kernel
+ * super-k-mer lists (sk_count_uniform, sk_count_select), the entry buffers' policy and the attempt loop of a count pass (count_entry_buffers,
+ * count_attempts), the end of a finalize (publish_maps), the host-to-device piece pipeline (tb_feed_pieces).  The heavy kernel
  * templates are compiled elsewhere (kmr_instances.hpp, kmr_inst.hip); the headers' plain kernels here.
  */
 #include <hip/hip_runtime.h>
@@ -203,16 +204,6 @@ int ensure_capacity(kmr_handle *h, uint64_t incoming) {
 	return 0;
 }
 
-void time_begin(kmr_handle *h, int which, hipEvent_t *a, hipEvent_t *b) {
-	hipEventCreate(a); hipEventCreate(b);
-	hipEventRecord(*a, h->stream);
-	(void)which;
-}
-void time_end(kmr_handle *h, int which, hipEvent_t a, hipEvent_t b) {
-	hipEventRecord(b, h->stream);
-	h->pending_events[which].push_back(std::make_pair(a, b));
-}
-
 const size_t EXTRACT_SMEM = (size_t)WAVES_PER_BLOCK * 2 * TILE_BUF;
 
 /* If the batch holds reads longer than one LDS tile, cut them into work units (see ReadsView) and point rv at them. */
@@ -278,9 +269,9 @@ template <int W, bool EXT> int add_reads_dev_t(kmr_handle *h, const ReadsView &r
 		ReadsView rv = reads_slice(rvAll, r, m);
 		rc = prepare_units(h, rv); if (rc) return rc;
 		InsertOp<W, EXT> op; op.table = table_of<W>(h);
-		hipEvent_t a, b; time_begin(h, 0, &a, &b);
+		TimeSpan t(h, 0);
 		rc = launch_extract<W, EXT>(h, rv, op);
-		time_end(h, 0, a, b);
+		t.end();
 		if (rc) return rc;
 	}
 	return 0;
@@ -332,6 +323,17 @@ int arena_reset(kmr_handle *h) {
 	return 0;
 }
 template <class T> int arena_get(kmr_handle *h, T **out, size_t count) { return arena_alloc(h, (void **)out, count * sizeof(T)); }
+/* What every kmr_finalize ends with: the maps are the handle's state (has_singletons, entry counts, a new map generation) and the
+ * device's error word and counters are read.  The finalize arena's temporaries are dead: if some of them had to be allocated on
+ * the side, the arena is brought to size now, so that it is this build (a handle's first) that pays for it and not the next one */
+int publish_maps(kmr_handle *h, bool keepSing) {
+	h->has_singletons = keepSing;
+	h->stats.weak_entries = h->weak.n; h->stats.singleton_entries = keepSing ? h->sing.n : 0;
+	h->finalized = true; h->map_gen++;
+	int rc = sync_state(h);
+	if (!rc && !h->arena_overflow.empty()) rc = arena_reset(h);
+	return rc;
+}
 
 /* empty the map but keep its buffers */
 void clear_map(DevMap &m) { m.image.reset(); m.n = 0; m.present = false; }
@@ -345,7 +347,7 @@ template <int W> MapView<W> view_of(const DevMap &m, uint32_t vw) {
 template <int W, bool EXT> int finalize_t(kmr_handle *h, uint32_t min_depth) {
 	int rc = sync_state(h);
 	if (rc) return rc;
-	hipEvent_t ea, eb; time_begin(h, 1, &ea, &eb);
+	TimeSpan whole(h, KMR_TIME_FINALIZE);
 	const FinalizeParams f = finalize_params(h, min_depth);
 	const bool keepSing = f.has_singletons && min_depth <= 1;
 	DevBuf wcb, scb, fcb;
@@ -383,14 +385,11 @@ template <int W, bool EXT> int finalize_t(kmr_handle *h, uint32_t min_depth) {
 		hipLaunchKernelGGL((sort_buckets_kernel<W, 0>), dim3(grid_for(sm.nb, 4, 1 << 20)), dim3(256), 0, h->stream, ss, sm.start.get<uint64_t>(), sm.nb);
 	}
 	HIPCHK(h, hipGetLastError());
-	time_end(h, 1, ea, eb);
+	whole.end();
 	HIPCHK(h, hipStreamSynchronize(h->stream));
 	/* the table allocation is kept for kmr_reset(); kmr_release_table() frees it */
-	h->has_singletons = keepSing;
 	if (!keepSing) { sm.n = 0; }
-	h->stats.weak_entries = wm.n; h->stats.singleton_entries = keepSing ? sm.n : 0;
-	h->finalized = true; h->map_gen++;
-	return sync_state(h);
+	return publish_maps(h, keepSing);
 }
 
 template <int W> int build_image_t(kmr_handle *h, DevMap &m, bool weakMap) {
@@ -710,16 +709,14 @@ template <int W, bool EXT> int partition_level1(kmr_handle *h, const void *linea
 		rc = ensure_l1_state<W, EXT>(h); if (rc) return rc;
 		S.state = h->l1_state.get<uint8_t>(); S.state_final = 0; h->l1_state_dirty = true;
 	}
-	hipEvent_t ta, tb; time_begin(h, KMR_TIME_PARTITION1, &ta, &tb);
-	rc = launch_partition<W, EXT, 1>(h, S, h->l1, grid, h->bits1, 0);
-	time_end(h, KMR_TIME_PARTITION1, ta, tb);
-	return rc;
+	TimeSpan t(h, KMR_TIME_PARTITION1);
+	return launch_partition<W, EXT, 1>(h, S, h->l1, grid, h->bits1, 0);
 }
 
 void choose_bits1(kmr_handle *h, uint64_t records_hint) {
 	/* total bits aim at TARGET_LIST_RECORDS per final list; level 2 takes up to max_part_bits(h) of them.  Two of
 	 * those are held back: if most k-mers turn out to be distinct the lists have to be up to 4x smaller (see the
-	 * distinct probe in finalize_partition_t). */
+	 * distinct probe, probe_distinct_share). */
 	uint64_t est = std::max<uint64_t>(records_hint, h->cfg.estimated_raw_kmers / std::max<uint32_t>(1, h->cfg.world_size));
 	const int mb = max_part_bits(h);
 	int T = 0; while (T < 2 * mb && (est >> T) > TARGET_LIST_RECORDS) T++;
@@ -790,10 +787,9 @@ template <int W, bool EXT> int add_reads_partition_t(kmr_handle *h, const ReadsV
 		rc = h->linear.reserve(h, "linear", rec_bytes(h) * std::max<uint64_t>(total_cap, 16)); if (rc) return rc;
 		rc = h->tile_count.reserve(h, "tile_count", 4 * std::max<uint64_t>(tiles, 16)); if (rc) return rc;
 		LinearOp<W, EXT> op; op.records = (typename PoolRec<W, EXT>::type *)h->linear.get(); op.koff = h->koff.get<uint64_t>(); op.tile_count = h->tile_count.get<uint32_t>(); op.first_read_idx = rv.first_read_idx;
-		hipEvent_t a, b, a2, b2; time_begin(h, KMR_TIME_BUILD, &a, &b);
-		time_begin(h, KMR_TIME_EXTRACT, &a2, &b2);
+		TimeSpan tb(h, KMR_TIME_BUILD), te(h, KMR_TIME_EXTRACT);
 		rc = launch_extract<W, EXT>(h, rv, op);
-		time_end(h, KMR_TIME_EXTRACT, a2, b2);
+		te.end();
 #ifdef KMR_DEBUG_HOOKS
 		if (!rc && getenv("KMR_DEBUG_SAME_TILE")) {
 			/* measurement aid (tools/l1_write_side.py): every tile of the level-1 pass reads the records of one of the first N tiles again, i.e. its
@@ -804,7 +800,7 @@ template <int W, bool EXT> int add_reads_partition_t(kmr_handle *h, const ReadsV
 		}
 #endif
 		if (!rc) rc = partition_level1<W, EXT>(h, h->linear.get(), h->koff.get<uint64_t>(), h->tile_count.get<uint32_t>(), tiles, 64, 0, 0, total_cap);
-		time_end(h, KMR_TIME_BUILD, a, b);
+		tb.end();
 		if (rc) return rc;
 	}
 	return 0;
@@ -863,59 +859,142 @@ template <int W, bool EXT, int LOG2S, bool NARROW = false> int launch_count(kmr_
 	return 0;
 }
 
-template <int W, bool EXT> int finalize_partition_t(kmr_handle *h, uint32_t min_depth) {
-	int rc = sync_state(h);
-	if (rc) return rc;
-	hipEvent_t ea, eb; time_begin(h, 1, &ea, &eb);
-	const uint64_t G = h->stats.raw_good_kmers;     /* records in the level-1 pool */
-	const FinalizeParams f = finalize_params(h, min_depth);
-	const bool keepSing = f.has_singletons && min_depth <= 1;
-	if (!h->l1.head) { rc = pool_reserve(h, h->l1, 0, false); if (rc) return rc; }
-	rc = arena_reset(h); if (rc) return rc;
-	rc = flush_l1_state<W, EXT>(h); if (rc) return rc;
-	/* level-1 CSR */
-	const uint64_t nl1 = 1ull << h->bits1;
-	uint64_t *ls1 = nullptr; uint64_t *lc1 = nullptr; uint32_t nch1 = 0;
-	rc = build_csr(h, h->l1, nl1, 0, &ls1, &lc1, &nch1); if (rc) return rc;
-	/* Final lists are sized by what the count pass can hold in its LDS table: measure the share of distinct keys
-	 * on a sample of level-1 lists, then take enough further bits for ~MAX_LIST_DISTINCT distinct keys per list (and
-	 * at most TARGET_LIST_RECORDS records), up to max_part_bits per pass and as many passes as that takes (C2: one,
-	 * 10 + 10 bits; C4 with 5 x 10^9 two-word records: 10 + 10 + 2). */
-	double distinct_share = 1.0, repeated_share = 0.5;      /* distinct keys, and distinct keys seen more than once, per record */
-	if (G) {
-		unsigned long long *dpr, hpr[4] = {0, 0, 0, 0};
-		const uint32_t n_probes = (uint32_t)std::min<uint64_t>(PROBE_LISTS, nl1);
-		const size_t tbytes = 8 * ((size_t)n_probes * PROBE_SLOTS + 4);
-		rc = arena_alloc(h, (void **)&dpr, tbytes); if (rc) return rc;
-		HIPCHK(h, hipMemsetAsync(dpr, 0, tbytes, h->stream));
-		hipLaunchKernelGGL((distinct_probe_kernel<W, EXT>), dim3(n_probes * PROBE_SPLIT), dim3(256), 0, h->stream, pool_view(h, h->l1), ls1, lc1, nl1, h->hkb, part_rot(h),
-		                   (int)h->bits1, n_probes, dpr + 4, dpr);
-		HIPCHK(h, hipGetLastError());
-		HIPCHK(h, hipMemcpyAsync(hpr, dpr, 32, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
-		if (hpr[0] >= 256) { distinct_share = std::min(1.0, std::max(0.01, (double)hpr[1] / (double)hpr[0])); repeated_share = std::min(0.5, (double)hpr[2] / (double)hpr[0]); }
-		if (dbg()) fprintf(stderr, "distinct probe: %llu records, %llu distinct (%llu repeated) -> shares %.3f %.3f\n", hpr[0], hpr[1], hpr[2], distinct_share, repeated_share);
+/* ---- what the counting finalizers (build_mode 2 and 3) share: the entry buffers' policy and the attempt loop (the tail: publish_maps) ---- */
+
+/* what a counting finalize carries from the sizing of its entry buffers to the maps */
+struct CountPass {
+	FinalizeParams f{}; bool keepSing = false, ext = false;
+	bool packed = false;      /* the weak entries packed in h->ue (build_mode 3 without extension values) or keys and values apart in h->uw_*, see count_out */
+	uint64_t wcap = 0, scap = 0, wmax = 0, smax = 0;                             /* entry buffers: entries now, upper bounds */
+	uint32_t *wc = nullptr, *sc = nullptr; FinalizeCounters *fc = nullptr; unsigned long long *cursors = nullptr;
+	FinalizeCounters c{}; unsigned long long cur[2] = {0, 0};                    /* what the count pass reported */
+};
+
+/* room the blocks of a count pass leave unused: one partly used output slab of 8192 slots each */
+uint64_t entry_slack(uint64_t slabs) { return slabs * 8192 + 16; }
+uint64_t sk_entry_slack(kmr_handle *h) { return entry_slack((uint64_t)num_cus(h) * 4); }
+
+/* Entry buffers of the pass over G good k-mers: how many entries to start with (wfirst / sfirst and the slack) and their upper bounds;
+ * the per-bucket counts, counters and cursors.  The worst case (every second record a weak entry, or every record a singleton) is
+ * 5-10 x what sequencing data produces, and at C4 size it is 70 GB: the buffers start from an estimate and the count pass is simply
+ * run again with larger ones if that was not enough (count_attempts).  The pass retires an output slab that cannot take a list's
+ * entries whole, so up to (entries of one list - 1) of every slab stay unused: an eighth on top of the bounds.  adopted: after an
+ * owner exchange the lists this rank counts hold other ranks' k-mers too -- G only knows this rank's own reads: no upper bound then */
+int count_entry_buffers(kmr_handle *h, CountPass &p, uint64_t G, uint64_t slack, uint64_t wfirst, uint64_t sfirst, bool adopted) {
+	const uint64_t wbound = p.f.has_singletons ? G / 2 : G, sbound = p.keepSing ? G : 0;
+	p.wmax = adopted ? (1ull << 40) : wbound + wbound / 8 + slack; p.smax = p.keepSing ? (adopted ? (1ull << 40) : sbound + sbound / 8 + slack) : 16;
+	p.wcap = std::min<uint64_t>(p.wmax, wfirst + slack); p.scap = p.keepSing ? std::min<uint64_t>(p.smax, sfirst + slack) : 16;
+	if (h->tune.entry_share >= 0) {       /* kmr_tune "entry_share": start from a given (e.g. hopeless) estimate so that the pass has to run again */
+		const uint64_t n = (uint64_t)((double)G * h->tune.entry_share) + 16384;
+		p.wcap = std::min<uint64_t>(p.wmax, n); if (p.keepSing) p.scap = std::min<uint64_t>(p.smax, n);
+		if (p.packed) h->ue.reset(); else { h->uw_keys.reset(); h->uw_vals.reset(); }
+		h->us_keys.reset(); h->us_b8.reset(); h->us_pkt.reset();
 	}
+	p.wcap = std::max(p.wcap, p.packed ? packed_entries(h, h->ue) : key_entries(h, h->uw_keys)); p.scap = std::max(p.scap, key_entries(h, h->us_keys));
+	int rc = arena_get(h, &p.wc, h->nb_weak); if (rc) return rc; rc = arena_get(h, &p.sc, h->nb_sing); if (rc) return rc;
+	rc = arena_get(h, &p.fc, 1); if (rc) return rc; rc = arena_get(h, &p.cursors, 2); if (rc) return rc;
+	return 0;
+}
+/* h->uw_keys / h->uw_vals hold n weak entries of vw value words, keys and values apart */
+int ensure_weak_apart(kmr_handle *h, uint64_t n, uint32_t vw) {
+	if (key_entries(h, h->uw_keys) >= n && h->uw_vals) return 0;
+	h->uw_keys.reset(); h->uw_vals.reset();
+	HIPCHK(h, h->uw_keys.alloc(8ull * h->W * n)); HIPCHK(h, h->uw_vals.alloc(4ull * vw * n));
+	return 0;
+}
+/* ... and the buffers of a count pass hold p.wcap weak entries in its form and p.scap singletons */
+int ensure_entry_buffers(kmr_handle *h, const CountPass &p) {
+	if (!p.packed) { const int rc = ensure_weak_apart(h, p.wcap, p.ext ? 15 : 3); if (rc) return rc; }
+	else if (packed_entries(h, h->ue) < p.wcap) { h->ue.reset(); HIPCHK(h, h->ue.alloc(8ull * (h->W + 1) * p.wcap)); }
+	if (key_entries(h, h->us_keys) < p.scap || !h->us_b8 || (p.ext && !h->us_pkt)) {
+		h->us_keys.reset(); h->us_b8.reset(); h->us_pkt.reset();
+		HIPCHK(h, h->us_keys.alloc(8ull * h->W * p.scap)); HIPCHK(h, h->us_b8.alloc(p.scap)); if (p.ext) HIPCHK(h, h->us_pkt.alloc(4 * p.scap));
+	}
+	return 0;
+}
+/* per-bucket counts, counters and cursors start at zero */
+int count_clear(kmr_handle *h, const CountPass &p) {
+	HIPCHK(h, hipMemsetAsync(p.wc, 0, 4 * h->nb_weak, h->stream)); HIPCHK(h, hipMemsetAsync(p.sc, 0, 4 * h->nb_sing, h->stream));
+	HIPCHK(h, hipMemsetAsync(p.fc, 0, sizeof(FinalizeCounters), h->stream)); HIPCHK(h, hipMemsetAsync(p.cursors, 0, 16, h->stream));
+	return 0;
+}
+/* the counters, the cursors and the device error word with one wait */
+int count_read_back(kmr_handle *h, CountPass &p, uint32_t &err) {
+	HIPCHK(h, hipMemcpyAsync(&p.c, p.fc, sizeof(p.c), hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipMemcpyAsync(p.cur, p.cursors, 16, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipMemcpyAsync(&err, h->derr.get<uint32_t>(), 4, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipStreamSynchronize(h->stream));
+	return 0;
+}
+/* The count pass, run again with doubled entry buffers while they overflow (ERR_ENTRIES_FULL), up to their bounds and eight times at
+ * most.  queue(out, repeated, repeat_on) puts one attempt's launches on the stream; it may name error flags in repeat_on that ask for
+ * the same attempt again with buffers as they are (both they and the overflow flag are cleared; `repeated` tells it so).
+ * make_room() runs before an attempt allocates: what the caller can give back.  h->last_count_attempts: how many attempts it took. */
+template <class MakeRoom, class Queue> int count_attempts(kmr_handle *h, CountPass &p, MakeRoom make_room, Queue queue) {
+	TimeSpan t(h, KMR_TIME_COUNT);
+	bool repeated = false;
+	for (int attempt = 0; ; attempt++) {
+		h->last_count_attempts = attempt + 1;
+		int rc = make_room(); if (rc) return rc;
+		rc = ensure_entry_buffers(h, p); if (rc) return rc;
+		rc = count_clear(h, p); if (rc) return rc;
+		const CountOut out = count_out(h, p.packed, p.cursors, p.wc, p.sc, p.fc);
+		rc = zero_work_counter(h); if (rc) return rc;
+		uint32_t repeat_on = 0, err = 0;
+		rc = queue(out, repeated, repeat_on); if (rc) return rc;
+		rc = count_read_back(h, p, err); if (rc) return rc;
+		repeated = (err & repeat_on) != 0;
+		if (repeated) err &= ~(repeat_on | (uint32_t)ERR_ENTRIES_FULL);
+		else if (!(err & ERR_ENTRIES_FULL)) return 0;
+		/* still full with the buffers at their bounds (or after the last attempt): the cursors point past the buffers, nothing downstream may use them */
+		else if ((p.wcap >= p.wmax && p.scap >= p.smax) || attempt >= 8) return fail(h, KMR_ERR_CAPACITY, "entry buffers of the count pass overflowed at their upper bound (internal sizing error)");
+		else {      /* more kept entries than the estimate promised: larger buffers, same pass again */
+			err &= ~(uint32_t)ERR_ENTRIES_FULL;
+			p.wcap = std::min<uint64_t>(p.wmax, p.wcap * 2); if (p.keepSing) p.scap = std::min<uint64_t>(p.smax, p.scap * 2);
+			if (dbg()) fprintf(stderr, "count pass: entry buffers too small, retrying with %llu / %llu\n", (unsigned long long)p.wcap, (unsigned long long)p.scap);
+		}
+		HIPCHK(h, hipMemcpy(h->derr.get<uint32_t>(), &err, 4, hipMemcpyHostToDevice));
+	}
+}
+/* ---- build_mode 2: the phases of finalize_partition_t ---- */
+
+/* the share of distinct keys, and of distinct keys seen more than once, per record: measured on a sample of level-1 lists */
+template <int W, bool EXT> int probe_distinct_share(kmr_handle *h, const uint64_t *ls1, const uint64_t *lc1, uint64_t nl1, uint64_t G, double &distinct_share, double &repeated_share) {
+	distinct_share = 1.0; repeated_share = 0.5;
+	if (!G) return 0;
+	unsigned long long *dpr, hpr[4] = {0, 0, 0, 0};
+	const uint32_t n_probes = (uint32_t)std::min<uint64_t>(PROBE_LISTS, nl1);
+	const size_t tbytes = 8 * ((size_t)n_probes * PROBE_SLOTS + 4);
+	int rc = arena_alloc(h, (void **)&dpr, tbytes); if (rc) return rc;
+	HIPCHK(h, hipMemsetAsync(dpr, 0, tbytes, h->stream));
+	hipLaunchKernelGGL((distinct_probe_kernel<W, EXT>), dim3(n_probes * PROBE_SPLIT), dim3(256), 0, h->stream, pool_view(h, h->l1), ls1, lc1, nl1, h->hkb, part_rot(h),
+	                   (int)h->bits1, n_probes, dpr + 4, dpr);
+	HIPCHK(h, hipGetLastError());
+	HIPCHK(h, hipMemcpyAsync(hpr, dpr, 32, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
+	if (hpr[0] >= 256) { distinct_share = std::min(1.0, std::max(0.01, (double)hpr[1] / (double)hpr[0])); repeated_share = std::min(0.5, (double)hpr[2] / (double)hpr[0]); }
+	if (dbg()) fprintf(stderr, "distinct probe: %llu records, %llu distinct (%llu repeated) -> shares %.3f %.3f\n", hpr[0], hpr[1], hpr[2], distinct_share, repeated_share);
+	return 0;
+}
+/* partition levels 2, 3, ... until the lists are cut by T bits, max_part_bits a pass; ls / lc: the chunk CSR of the current (finally:
+ * the last) level, cur_bits: its bits */
+template <int W, bool EXT> int partition_further_levels(kmr_handle *h, uint64_t G, int T, uint64_t *&ls, uint64_t *&lc, int &cur_bits) {
 	const int mb = max_part_bits(h);
-	int T = 0; while (T < 40 && ((G >> T) > TARGET_LIST_RECORDS || (double)(G >> T) * distinct_share > MAX_LIST_DISTINCT)) T++;
-	T = std::min(T, 28);                              /* list ids are 32-bit with room to spare */
-	int cur_bits = h->bits1;
-	uint64_t *ls2 = ls1, *lc2 = lc1;                  /* CSR of the current (finally: the last) level */
-	uint32_t valid_from = 0;                          /* chunks below belong to levels that were left behind by a fresh-chunk pass */
+	uint32_t nch = 0, valid_from = 0;                 /* chunks below valid_from belong to levels that were left behind by a fresh-chunk pass */
 	for (int level = 2; cur_bits < T; level++) {
 		const int nbits = std::min(mb, T - cur_bits);
 		const uint64_t nl_prev = 1ull << cur_bits;
 		/* work items: the lists of the previous level, long ones cut into equal items (every item ends with a flush of
 		 * partly filled chunks, and a short leftover item would cost as many of those as a full one) */
 		std::vector<uint64_t> hs(nl_prev + 1);
-		HIPCHK(h, hipMemcpy(hs.data(), ls2, 8 * (nl_prev + 1), hipMemcpyDeviceToHost));
+		HIPCHK(h, hipMemcpy(hs.data(), ls, 8 * (nl_prev + 1), hipMemcpyDeviceToHost));
 		std::vector<uint64_t> ib, ie; std::vector<uint32_t> il;
 		for (uint64_t l = 0; l < nl_prev; l++) {
-			const uint64_t nch = hs[l + 1] - hs[l];
-			if (!nch) continue;
-			const uint64_t nit = (nch + L2_ITEM_CHUNKS - 1) / L2_ITEM_CHUNKS, per = (nch + nit - 1) / nit;
+			const uint64_t nc = hs[l + 1] - hs[l];
+			if (!nc) continue;
+			const uint64_t nit = (nc + L2_ITEM_CHUNKS - 1) / L2_ITEM_CHUNKS, per = (nc + nit - 1) / nit;
 			for (uint64_t c = hs[l]; c < hs[l + 1]; c += per) { ib.push_back(c); ie.push_back(std::min(hs[l + 1], c + per)); il.push_back((uint32_t)l); }
 		}
-		if (ib.empty()) { cur_bits += nbits; rc = build_csr(h, h->l1, 1ull << cur_bits, valid_from, &ls2, &lc2, &nch1); if (rc) return rc; continue; }
+		int rc = 0;
+		if (ib.empty()) { cur_bits += nbits; rc = build_csr(h, h->l1, 1ull << cur_bits, valid_from, &ls, &lc, &nch); if (rc) return rc; continue; }
 		/* The pass writes into the pool it reads.  With room for a second copy of the records it appends fresh chunks
 		 * (compact, slab by slab: the faster writes); without, a block recycles the chunks it has just read. */
 		const uint64_t partials = ib.size() * (1ull << nbits) + (uint64_t)part_grid(h) * 512 + 64;
@@ -930,138 +1009,114 @@ template <int W, bool EXT> int finalize_partition_t(kmr_handle *h, uint32_t min_
 		HIPCHK(h, hipMemcpyAsync(dil, il.data(), 4 * il.size(), hipMemcpyHostToDevice, h->stream));
 		rc = zero_work_counter(h); if (rc) return rc;
 		PartSource<W> S; memset(&S, 0, sizeof(S));
-		S.src = pool_view(h, h->l1); S.list_chunks = lc2; S.item_begin = dib; S.item_end = die; S.item_list = dil; S.n_items = ib.size(); S.kb = h->hkb; S.rot = part_rot(h);
+		S.src = pool_view(h, h->l1); S.list_chunks = lc; S.item_begin = dib; S.item_end = die; S.item_list = dil; S.n_items = ib.size(); S.kb = h->hkb; S.rot = part_rot(h);
 		S.recycle = recycle ? 1 : 0;
 		const int grid = (int)std::min<uint64_t>(partition_blocks(h), ib.size());
 		if (dbg()) fprintf(stderr, "level %d: %d bits after %d, %zu items, %s\n", level, nbits, cur_bits, ib.size(), recycle ? "recycling chunks" : "fresh chunks");
-		hipEvent_t ta, tb; time_begin(h, KMR_TIME_PARTITION2, &ta, &tb);
-		rc = launch_partition<W, EXT, 2>(h, S, h->l1, grid, nbits, cur_bits);
-		time_end(h, KMR_TIME_PARTITION2, ta, tb);
+		{ TimeSpan t(h, KMR_TIME_PARTITION2); rc = launch_partition<W, EXT, 2>(h, S, h->l1, grid, nbits, cur_bits); }
 		if (rc) return rc;
 		HIPCHK(h, hipStreamSynchronize(h->stream));      /* the host vectors behind the item copies go out of scope */
 		cur_bits += nbits;
 		/* CSR of the new level: fresh chunks lie behind the old head (what is below keeps the list ids of the level
 		 * left behind and is never looked at again); recycled ones anywhere in the range that was valid before */
 		if (!recycle) valid_from = head_before;
-		rc = build_csr(h, h->l1, 1ull << cur_bits, valid_from, &ls2, &lc2, &nch1); if (rc) return rc;
+		rc = build_csr(h, h->l1, 1ull << cur_bits, valid_from, &ls, &lc, &nch); if (rc) return rc;
 	}
-	const uint64_t nl2 = 1ull << cur_bits;
-	const int count_log2s = (!EXT && (double)(G >> cur_bits) * distinct_share > MAX_LIST_DISTINCT) ? 11 : COUNT_LOG2S;      /* with extension tallies 2048 slots do not fit LDS */
-	if (dbg()) fprintf(stderr, "count pass: %llu lists of ~%llu records, table 2^%d\n", (unsigned long long)nl2, (unsigned long long)(G >> cur_bits), count_log2s);
+	return 0;
+}
+/* the count pass over the nl final lists of G records (count_attempts), with a table of 2^count_log2s slots */
+template <int W, bool EXT> int partition_count_pass(kmr_handle *h, CountPass &p, uint64_t G, const uint64_t *ls, const uint64_t *lc, uint64_t nl, int count_log2s) {
 	const uint32_t vw = EXT ? 15 : 3;
-	const uint64_t slack = (uint64_t)part_grid(h) * 8 * 8192 + 16;     /* one partly used output slab per block */
-	/* entry buffers: the worst case (every second record a weak entry, or every record a singleton) is 5-10 x what
-	 * sequencing data produces, and at C4 size it is 70 GB; they are sized from the probe's shares with 50 % headroom and
-	 * the count pass is simply run again with larger ones if that was not enough */
-	/* upper bounds of the kept entries; the count pass retires an output slab that cannot take a list's entries whole, so up to
-	 * (entries of one list - 1) of every 8192-slot slab stay unused: an eighth on top */
-	const uint64_t wbound = f.has_singletons ? G / 2 : G, sbound = keepSing ? G : 0;
-	const uint64_t wmax = wbound + wbound / 8 + slack, smax = keepSing ? sbound + sbound / 8 + slack : 16;
-	uint64_t wcap = std::min<uint64_t>(wmax, (uint64_t)((double)G * (f.has_singletons ? repeated_share : distinct_share) * 1.5) + G / 64 + slack);
-	uint64_t scap = keepSing ? std::min<uint64_t>(smax, (uint64_t)((double)G * std::max(0.0, distinct_share - repeated_share) * 1.5) + G / 64 + slack) : 16;
-	if (h->tune.entry_share >= 0) {       /* kmr_tune "entry_share": start from a given (e.g. hopeless) estimate so that the retry below has to run */
-		const double sh = h->tune.entry_share;
-		wcap = std::min<uint64_t>(wmax, (uint64_t)((double)G * sh) + 16384); if (keepSing) scap = std::min<uint64_t>(smax, (uint64_t)((double)G * sh) + 16384);
-		h->uw_keys.reset(); h->uw_vals.reset(); h->us_keys.reset(); h->us_b8.reset(); h->us_pkt.reset();
-	}
-	wcap = std::max(wcap, key_entries(h, h->uw_keys)); scap = std::max(scap, key_entries(h, h->us_keys));
-	uint32_t *wc = nullptr, *sc = nullptr; FinalizeCounters *fc = nullptr; unsigned long long *cursors = nullptr;
-	rc = arena_get(h, &wc, h->nb_weak); if (rc) return rc; rc = arena_get(h, &sc, h->nb_sing); if (rc) return rc;
-	rc = arena_get(h, &fc, 1); if (rc) return rc; rc = arena_get(h, &cursors, 2); if (rc) return rc;
-	FinalizeCounters c; unsigned long long cur[2];
-	hipEvent_t tca, tcb; time_begin(h, KMR_TIME_COUNT, &tca, &tcb);
-	for (int attempt = 0; ; attempt++) {
-	{	/* the linear record buffer is dead during finalize: given back when the entry buffers would not fit beside it */
-		const double need = (key_entries(h, h->uw_keys) < wcap ? (8.0 * W + 4.0 * vw) * (double)wcap : 0.0) + (key_entries(h, h->us_keys) < scap ? (8.0 * W + 1.0) * (double)scap : 0.0);
+	/* the linear record buffer is dead during finalize: given back when the entry buffers would not fit beside it */
+	auto make_room = [&]() -> int {
+		const double need = (key_entries(h, h->uw_keys) < p.wcap ? (8.0 * W + 4.0 * vw) * (double)p.wcap : 0.0) + (key_entries(h, h->us_keys) < p.scap ? (8.0 * W + 1.0) * (double)p.scap : 0.0);
 		size_t mfree = 0, mtotal = 0;
 		if (need > 0 && h->linear && hipMemGetInfo(&mfree, &mtotal) == hipSuccess && (double)mfree < need + (double)G * 0.3 * (8.0 * W + 12.0) + (double)(2ull << 30)) {
 			HIPCHK(h, hipStreamSynchronize(h->stream));
 			h->linear.reset();
 		}
-	}
-	if (key_entries(h, h->uw_keys) < wcap || !h->uw_vals) {
-		h->uw_keys.reset(); h->uw_vals.reset();
-		HIPCHK(h, h->uw_keys.alloc(8ull * W * wcap)); HIPCHK(h, h->uw_vals.alloc(4ull * vw * wcap));
-	}
-	if (key_entries(h, h->us_keys) < scap || !h->us_b8 || (EXT && !h->us_pkt)) {
-		h->us_keys.reset(); h->us_b8.reset(); h->us_pkt.reset();
-		HIPCHK(h, h->us_keys.alloc(8ull * W * scap)); HIPCHK(h, h->us_b8.alloc(scap)); if (EXT) HIPCHK(h, h->us_pkt.alloc(4 * scap));
-	}
-	HIPCHK(h, hipMemsetAsync(wc, 0, 4 * h->nb_weak, h->stream)); HIPCHK(h, hipMemsetAsync(sc, 0, 4 * h->nb_sing, h->stream));
-	HIPCHK(h, hipMemsetAsync(fc, 0, sizeof(FinalizeCounters), h->stream)); HIPCHK(h, hipMemsetAsync(cursors, 0, 16, h->stream));
-	const CountOut out = count_out(h, false, cursors, wc, sc, fc);
-	rc = zero_work_counter(h); if (rc) return rc;
-	#ifdef KMR_DEBUG_HOOKS
-	const int count_reps = getenv("KMR_COUNT_CHECK") ? atoi(getenv("KMR_COUNT_CHECK")) : 0;
-#else
-	const int count_reps = 0;
-#endif
-	for (int cr = 0; cr <= count_reps; cr++) {
-		if (cr) {      /* debugging aid: the count pass is repeated on the same input and must report the same numbers */
-			FinalizeCounters c0; unsigned long long cur0[2];
-			HIPCHK(h, hipStreamSynchronize(h->stream));
-			HIPCHK(h, hipMemcpy(&c0, fc, sizeof(c0), hipMemcpyDeviceToHost)); HIPCHK(h, hipMemcpy(cur0, cursors, 16, hipMemcpyDeviceToHost));
-			fprintf(stderr, "count pass %d: unique %llu singletons %llu weak_kept %llu sing_kept %llu slots %llu/%llu\n", cr - 1, (unsigned long long)c0.unique,
-			        (unsigned long long)c0.singletons, (unsigned long long)c0.weak_kept, (unsigned long long)c0.sing_kept, cur0[0], cur0[1]);
-			HIPCHK(h, hipMemsetAsync(wc, 0, 4 * h->nb_weak, h->stream)); HIPCHK(h, hipMemsetAsync(sc, 0, 4 * h->nb_sing, h->stream));
-			HIPCHK(h, hipMemsetAsync(fc, 0, sizeof(FinalizeCounters), h->stream)); HIPCHK(h, hipMemsetAsync(cursors, 0, 16, h->stream));
-			rc = zero_work_counter(h); if (rc) return rc;
-		}
-		const int grid = (int)std::min<uint64_t>((uint64_t)part_grid(h) * 2, nl2);
+		return 0;
+	};
+	auto launches = [&](const CountOut &out) -> int {
+		int rc = 0;
+		const int grid = (int)std::min<uint64_t>((uint64_t)part_grid(h) * 2, nl);
 		if (count_log2s == 11) {
-			rc = launch_count<W, EXT, 11>(h, grid, ls2, lc2, nl2, out, f, 0); if (rc) return rc;
+			rc = launch_count<W, EXT, 11>(h, grid, ls, lc, nl, out, p.f, 0); if (rc) return rc;
 		} else if (EXT && W == 1 && !h->tune.no_narrow) {
 			/* extension values at k <= 32: 16-bit tallies for every list of at most 65 535 records (two blocks per CU), then
 			 * the wide table for whatever is longer */
-			rc = launch_count<W, EXT, COUNT_LOG2S, true>(h, grid, ls2, lc2, nl2, out, f, 1); if (rc) return rc;
+			rc = launch_count<W, EXT, COUNT_LOG2S, true>(h, grid, ls, lc, nl, out, p.f, 1); if (rc) return rc;
 			HIPCHK(h, hipGetLastError());
 			/* is any list longer than the narrow tallies can take?  (the work counter word doubles as the maximum) */
 			rc = zero_work_counter(h); if (rc) return rc;
-			hipLaunchKernelGGL(max_list_chunks_kernel, dim3(grid_for(nl2)), dim3(256), 0, h->stream, ls2, nl2, h->work_counter.get<unsigned int>());
+			hipLaunchKernelGGL(max_list_chunks_kernel, dim3(grid_for(nl)), dim3(256), 0, h->stream, ls, nl, h->work_counter.get<unsigned int>());
 			unsigned int longest = 0;
 			HIPCHK(h, hipMemcpyAsync(&longest, h->work_counter.get<unsigned int>(), 4, hipMemcpyDeviceToHost, h->stream));
 			HIPCHK(h, hipStreamSynchronize(h->stream));
 			rc = zero_work_counter(h); if (rc) return rc;
-			if (longest > COUNT_NARROW_CHUNKS) { rc = launch_count<W, EXT, COUNT_LOG2S>(h, std::min(grid, part_grid(h)), ls2, lc2, nl2, out, f, 2); if (rc) return rc; }
+			if (longest > COUNT_NARROW_CHUNKS) { rc = launch_count<W, EXT, COUNT_LOG2S>(h, std::min(grid, part_grid(h)), ls, lc, nl, out, p.f, 2); if (rc) return rc; }
 		} else {
-			rc = launch_count<W, EXT, COUNT_LOG2S>(h, grid, ls2, lc2, nl2, out, f, 0); if (rc) return rc;
+			rc = launch_count<W, EXT, COUNT_LOG2S>(h, grid, ls, lc, nl, out, p.f, 0); if (rc) return rc;
 		}
 		HIPCHK(h, hipGetLastError());
-	}
-	uint32_t cerr = 0;
-	HIPCHK(h, hipMemcpyAsync(&c, fc, sizeof(c), hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipMemcpyAsync(cur, cursors, 16, hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(h, hipMemcpyAsync(&cerr, h->derr.get<uint32_t>(), 4, hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(h, hipStreamSynchronize(h->stream));
-	if (!(cerr & ERR_ENTRIES_FULL) || (wcap >= wmax && scap >= smax) || attempt >= 8) break;
-	/* more kept entries than the probe promised: larger buffers, same pass again */
-	cerr &= ~(uint32_t)ERR_ENTRIES_FULL;
-	HIPCHK(h, hipMemcpy(h->derr.get<uint32_t>(), &cerr, 4, hipMemcpyHostToDevice));
-	wcap = std::min<uint64_t>(wmax, wcap * 2); if (keepSing) scap = std::min<uint64_t>(smax, scap * 2);
-	if (dbg()) fprintf(stderr, "count pass: entry buffers too small, retrying with %llu / %llu\n", (unsigned long long)wcap, (unsigned long long)scap);
-	}
-	time_end(h, KMR_TIME_COUNT, tca, tcb);
-	{	/* still full with the buffers at their bounds (or after the last retry): the cursors point past the buffers, nothing
-		 * downstream may use them */
-		uint32_t cerr2 = 0;
-		HIPCHK(h, hipMemcpy(&cerr2, h->derr.get<uint32_t>(), 4, hipMemcpyDeviceToHost));
-		if (cerr2 & ERR_ENTRIES_FULL) { time_end(h, 1, ea, eb); return fail(h, KMR_ERR_CAPACITY, "entry buffers of the count pass overflowed at their upper bound (internal sizing error)"); }
-	}
+		return 0;
+	};
+	return count_attempts(h, p, make_room, [&](const CountOut &out, bool, uint32_t &) -> int {
+		int rc = launches(out);
+#ifdef KMR_DEBUG_HOOKS
+		/* debugging aid: the count pass is repeated on the same input and must report the same numbers */
+		for (int cr = 0, reps = getenv("KMR_COUNT_CHECK") ? atoi(getenv("KMR_COUNT_CHECK")) : 0; cr < reps && !rc; cr++) {
+			uint32_t e = 0;
+			rc = count_read_back(h, p, e); if (rc) return rc;
+			fprintf(stderr, "count pass %d: unique %llu singletons %llu weak_kept %llu sing_kept %llu slots %llu/%llu\n", cr, (unsigned long long)p.c.unique,
+			        (unsigned long long)p.c.singletons, (unsigned long long)p.c.weak_kept, (unsigned long long)p.c.sing_kept, p.cur[0], p.cur[1]);
+			rc = count_clear(h, p); if (rc) return rc;
+			rc = zero_work_counter(h); if (rc) return rc;
+			rc = launches(out);
+		}
+#endif
+		return rc;
+	});
+}
 
-	h->stats.unique_kmers = c.unique;
-	h->stats.singleton_kmers = f.has_singletons ? c.singletons : 0;
-	hipEvent_t tma, tmb; time_begin(h, KMR_TIME_BUCKETS, &tma, &tmb);
-	rc = finish_maps_from_entries(h, wc, sc, cur[0], cur[1], c.weak_kept, c.sing_kept, keepSing);
-	time_end(h, KMR_TIME_BUCKETS, tma, tmb);
+template <int W, bool EXT> int finalize_partition_t(kmr_handle *h, uint32_t min_depth) {
+	int rc = sync_state(h);
 	if (rc) return rc;
-	time_end(h, 1, ea, eb);
-	h->has_singletons = keepSing;
-	h->stats.weak_entries = h->weak.n; h->stats.singleton_entries = keepSing ? h->sing.n : 0;
-	h->finalized = true; h->map_gen++;
-	rc = sync_state(h);
-	/* the temporaries are dead: if some of them had to be allocated on the side, the arena is brought to size now,
-	 * so that it is this build (a handle's first) that pays for it and not the next one */
-	if (!rc && !h->arena_overflow.empty()) rc = arena_reset(h);
-	return rc;
+	TimeSpan whole(h, KMR_TIME_FINALIZE);
+	const uint64_t G = h->stats.raw_good_kmers;     /* records in the level-1 pool */
+	CountPass p;
+	p.f = finalize_params(h, min_depth);
+	p.keepSing = p.f.has_singletons && min_depth <= 1;
+	p.ext = EXT;
+	if (!h->l1.head) { rc = pool_reserve(h, h->l1, 0, false); if (rc) return rc; }
+	rc = arena_reset(h); if (rc) return rc;
+	rc = flush_l1_state<W, EXT>(h); if (rc) return rc;
+	/* level-1 CSR; then that of the current (finally: the last) level */
+	uint64_t *ls = nullptr, *lc = nullptr; uint32_t nch = 0;
+	rc = build_csr(h, h->l1, 1ull << h->bits1, 0, &ls, &lc, &nch); if (rc) return rc;
+	/* Final lists are sized by what the count pass can hold in its LDS table: measure the share of distinct keys
+	 * on a sample of level-1 lists, then take enough further bits for ~MAX_LIST_DISTINCT distinct keys per list (and
+	 * at most TARGET_LIST_RECORDS records), up to max_part_bits per pass and as many passes as that takes (C2: one,
+	 * 10 + 10 bits; C4 with 5 x 10^9 two-word records: 10 + 10 + 2). */
+	double distinct_share, repeated_share;
+	rc = probe_distinct_share<W, EXT>(h, ls, lc, 1ull << h->bits1, G, distinct_share, repeated_share); if (rc) return rc;
+	int T = 0; while (T < 40 && ((G >> T) > TARGET_LIST_RECORDS || (double)(G >> T) * distinct_share > MAX_LIST_DISTINCT)) T++;
+	T = std::min(T, 28);                              /* list ids are 32-bit with room to spare */
+	int cur_bits = h->bits1;
+	rc = partition_further_levels<W, EXT>(h, G, T, ls, lc, cur_bits); if (rc) return rc;
+	const uint64_t nl = 1ull << cur_bits;
+	const int count_log2s = (!EXT && (double)(G >> cur_bits) * distinct_share > MAX_LIST_DISTINCT) ? 11 : COUNT_LOG2S;      /* with extension tallies 2048 slots do not fit LDS */
+	if (dbg()) fprintf(stderr, "count pass: %llu lists of ~%llu records, table 2^%d\n", (unsigned long long)nl, (unsigned long long)(G >> cur_bits), count_log2s);
+	/* entry buffers: sized from the probe's shares with 50 % headroom */
+	rc = count_entry_buffers(h, p, G, entry_slack((uint64_t)part_grid(h) * 8), (uint64_t)((double)G * (p.f.has_singletons ? repeated_share : distinct_share) * 1.5) + G / 64,
+	                         (uint64_t)((double)G * std::max(0.0, distinct_share - repeated_share) * 1.5) + G / 64, false); if (rc) return rc;
+	rc = partition_count_pass<W, EXT>(h, p, G, ls, lc, nl, count_log2s); if (rc) return rc;
+	h->stats.unique_kmers = p.c.unique;
+	h->stats.singleton_kmers = p.f.has_singletons ? p.c.singletons : 0;
+	{ TimeSpan t(h, KMR_TIME_BUCKETS); rc = finish_maps_from_entries(h, p.wc, p.sc, p.cur[0], p.cur[1], p.c.weak_kept, p.c.sing_kept, p.keepSing); }
+	if (rc) return rc;
+	whole.end();
+	return publish_maps(h, p.keepSing);
 }
 
 /* Entries that one of `bins` equal shares of n hashed keys may hold (bins of one capacity, kmr_buckets.hpp): the largest count
@@ -1209,11 +1264,7 @@ template <int W> int finish_maps_t(kmr_handle *h, uint32_t *wc, uint32_t *sc, ui
 	if (weak_uncounted) {
 		rc = binned_buckets_t<W>(h, wslots, wn, fixed_bins, weakDone); if (rc) return rc;
 		if (!weakDone) {      /* the other path wants keys and values apart and a count per bucket */
-			if (key_entries(h, h->uw_keys) < wslots || !h->uw_vals) {
-				h->uw_keys.reset(); h->uw_vals.reset();
-				const uint64_t cap = std::max<uint64_t>(wslots, 16);
-				HIPCHK(h, h->uw_keys.alloc(8ull * W * cap)); HIPCHK(h, h->uw_vals.alloc(12ull * cap));
-			}
+			rc = ensure_weak_apart(h, std::max<uint64_t>(wslots, 16), vw); if (rc) return rc;
 			HIPCHK(h, hipMemsetAsync(wc, 0, 4 * wm.nb, h->stream));
 			if (wslots) hipLaunchKernelGGL(bb_unpack_kernel<W>, dim3(grid_for(wslots)), dim3(256), 0, h->stream, (const uint64_t *)h->ue.get<uint64_t>(), wslots, h->hkb, wm.nb, (uint64_t *)h->uw_keys.get(), (uint32_t *)h->uw_vals.get(), wc);
 			HIPCHK(h, hipGetLastError());
@@ -1263,12 +1314,10 @@ int finish_maps_from_entries(kmr_handle *h, uint32_t *wc, uint32_t *sc, uint64_t
 int finalize_partition(kmr_handle *h, uint32_t min_depth) { return with_w_ext(h, [&](auto W, auto EXT) { return finalize_partition_t<W(), EXT()>(h, min_depth); }); }
 template <int W, bool EXT> int insert_records_partition_t(kmr_handle *h, const void *recs, uint64_t n) {
 	if (!h->l1.head) choose_bits1(h, n);
-	hipEvent_t a, b; time_begin(h, 0, &a, &b);
+	TimeSpan t(h, 0);
 	/* received segments contain holes (weight 0): the device counts the real records into stats.raw/good */
-	int rc = partition_level1<W, EXT>(h, recs, nullptr, nullptr, (n + 8191) / 8192, 0, 8192, n, n, &h->dstats.get<DevStats>()->inserted,
+	return partition_level1<W, EXT>(h, recs, nullptr, nullptr, (n + 8191) / 8192, 0, 8192, n, n, &h->dstats.get<DevStats>()->inserted,
 	                             2 * W + (h->ext ? 2 : 1), h->stream_base);
-	time_end(h, 0, a, b);
-	return rc;
 }
 int insert_records_partition(kmr_handle *h, const void *recs, uint64_t n) { return with_w_ext(h, [&](auto W, auto EXT) { return insert_records_partition_t<W(), EXT()>(h, recs, n); }); }
 /* ---------------------------------------------------------------------- */
@@ -1442,7 +1491,7 @@ template <int W> int add_reads_superkmer_t(kmr_handle *h, const ReadsView &rvAll
 		}
 		/* (inside an exchange the lists of other owners start afresh after every pack: an open chunk per list for every call) */
 		rc = pool_reserve(h, h->l1, (h->ext ? 2 : 1) * bases / SK_CHUNK_G + ((h->l1.base && !h->sk_exchange) ? 0 : sk_list_count(h->sk_bits)) + (uint64_t)num_cus(h) * SK_EXTRACT_WAVES_PER_CU * 130 + 64, true); if (rc) return rc;
-		hipEvent_t a, b, a2, b2; time_begin(h, KMR_TIME_BUILD, &a, &b); time_begin(h, KMR_TIME_EXTRACT, &a2, &b2);
+		TimeSpan tb(h, KMR_TIME_BUILD), te(h, KMR_TIME_EXTRACT);
 		SkParams sp = sk_params(h);
 		if (h->cfg.size_tracker) sp.track = h->trk.get<SkTrackRec>() + r;
 		if (h->packed_direct) {
@@ -1453,7 +1502,7 @@ template <int W> int add_reads_superkmer_t(kmr_handle *h, const ReadsView &rvAll
 			if (filt) return launch_sk_extract<W, WIN(), true>(h, rv, sp);
 			return lean ? launch_sk_extract_lean<W, WIN()>(h, rv, sp, wK) : launch_sk_extract<W, WIN(), false>(h, rv, sp);
 		});
-		time_end(h, KMR_TIME_EXTRACT, a2, b2); time_end(h, KMR_TIME_BUILD, a, b);
+		te.end(); tb.end();
 		if (rc) return rc;
 	}
 	if (h->cfg.size_tracker && n) {
@@ -1664,16 +1713,13 @@ template <int W> int sk_count_select(kmr_handle *h, bool ext, bool tracking, boo
 	return 0;
 }
 
-/* what the phases of finalize_superkmer_t hand to one another */
-template <int W> struct SkFinalize {
-	FinalizeParams f{}; bool keepSing = false, ext = false, tracking = false, refined = false, uni = false;
+/* what the phases of finalize_superkmer_t hand to one another: the count pass's state (CountPass) and what the lists add */
+template <int W> struct SkFinalize : CountPass {
+	bool tracking = false, refined = false, uni = false;
 	uint64_t nl = 1; uint64_t *ls = nullptr, *lc = nullptr; uint32_t nch = 0;      /* the lists and their chunk CSR */
-	uint64_t wcap = 0, scap = 0, wmax = 0, smax = 0;                             /* entry buffers: entries now, upper bounds */
-	uint32_t *wc = nullptr, *sc = nullptr; FinalizeCounters *fc = nullptr; unsigned long long *cursors = nullptr;
 	SkTrackView tv{};
 	SkLong<W> lgMain{}, lgItems{}; uint64_t n_items = 0;                         /* the pass over lists, the pass over work items of long lists */
 	uint64_t early_slots = 0; FinalizeCounters early_c{};                        /* an early count that is taken over */
-	FinalizeCounters c{}; unsigned long long cur[2] = {0, 0};                    /* what the count pass reported */
 };
 
 /* the coarse lists this rank owns (its own share and what it adopted) -> fine lists (sk_refine_kernel); nl: how many */
@@ -1693,25 +1739,6 @@ int sk_refine_lists(kmr_handle *h, uint64_t &nl) {
 	hipLaunchKernelGGL(sk_close_kernel, dim3(grid_for(nlf)), dim3(256), 0, h->stream, h->sk_fine_state.get<unsigned long long>(), nlf, h->l1.chunk_count.get<uint32_t>(), h->l1.cap);
 	HIPCHK(h, hipGetLastError());
 	nl = nlf;
-	return 0;
-}
-/* entry buffers of the pass over G good k-mers: how many entries to start with and their upper bounds; the per-bucket counts, counters and cursors */
-template <int W> int sk_entry_buffers(kmr_handle *h, SkFinalize<W> &p, uint64_t G) {
-	const FinalizeParams &f = p.f; const bool keepSing = p.keepSing;
-	const uint64_t slack = (uint64_t)num_cus(h) * 4 * 8192 + 16;
-	const uint64_t wbound = f.has_singletons ? G / 2 : G, sbound = keepSing ? G : 0;
-	/* (after an owner exchange the lists this rank counts hold other ranks' k-mers too -- G only knows this rank's own reads: no upper
-	 * bound then, the pass is repeated with doubled buffers until the entries fit) */
-	const bool adopted = h->sk_exchange && h->cfg.world_size > 1;
-	p.wmax = adopted ? (1ull << 40) : wbound + wbound / 8 + slack; p.smax = keepSing ? (adopted ? (1ull << 40) : sbound + sbound / 8 + slack) : 16;
-	/* entry buffers: sequencing data keeps a few per cent of its k-mers as weak entries; the pass is run again with larger
-	 * buffers when that was not enough */
-	p.wcap = std::min<uint64_t>(p.wmax, G / (f.has_singletons ? 8 : 3) + slack); p.scap = keepSing ? std::min<uint64_t>(p.smax, G / 3 + slack) : 16;
-	if (h->tune.entry_share >= 0) { p.wcap = std::min<uint64_t>(p.wmax, (uint64_t)((double)G * h->tune.entry_share) + 16384); if (keepSing) p.scap = std::min<uint64_t>(p.smax, (uint64_t)((double)G * h->tune.entry_share) + 16384);
-		h->ue.reset(); h->us_keys.reset(); h->us_b8.reset(); h->us_pkt.reset(); }
-	p.wcap = std::max(p.wcap, p.ext ? key_entries(h, h->uw_keys) : packed_entries(h, h->ue)); p.scap = std::max(p.scap, key_entries(h, h->us_keys));
-	int rc = arena_get(h, &p.wc, h->nb_weak); if (rc) return rc; rc = arena_get(h, &p.sc, h->nb_sing); if (rc) return rc;
-	rc = arena_get(h, &p.fc, 1); if (rc) return rc; rc = arena_get(h, &p.cursors, 2); if (rc) return rc;
 	return 0;
 }
 /* size tracker: SizeTracker::track (src/KmerSpectrum.h:879-894) applied after every read, in stream order; what it pushes is known
@@ -1805,73 +1832,39 @@ CountOut count_out(kmr_handle *h, bool packed, unsigned long long *cursors, uint
 	out.singCount = sc; out.fc = fc; out.err = h->derr.get<uint32_t>();
 	return out;
 }
-/* The count pass, repeated with doubled entry buffers while they overflow and with a larger merge table while that fills.  overflowed:
- * the entries did not fit buffers at their upper bounds (the count's timing is closed; the caller closes its own and fails). */
-template <int W> int sk_count_pass(kmr_handle *h, SkFinalize<W> &p, bool &overflowed) {
-	overflowed = false;
-	const bool ext = p.ext, keepSing = p.keepSing, tracking = p.tracking; const uint32_t vw = ext ? 15 : 3;
-	uint64_t &wcap = p.wcap, &scap = p.scap; const uint64_t wmax = p.wmax, smax = p.smax, nl = p.nl, n_items = p.n_items;
-	uint32_t *wc = p.wc, *sc = p.sc; FinalizeCounters *fc = p.fc; unsigned long long *cursors = p.cursors;
-	FinalizeCounters &c = p.c; unsigned long long *cur = p.cur; const SkTrackView &tv = p.tv; const FinalizeParams &f = p.f;
-	int rc = 0;
+/* The count pass over the lists and, where some are long, over their work items into a merge table (count_attempts: again with doubled
+ * entry buffers while they overflow; this pass asks for a repeat with a larger merge table while that fills) */
+template <int W> int sk_count_pass(kmr_handle *h, SkFinalize<W> &p) {
+	const uint64_t nl = p.nl, n_items = p.n_items; const SkTrackView &tv = p.tv;
 	uint32_t merge_log2 = 16;
-	hipEvent_t tca, tcb; time_begin(h, KMR_TIME_COUNT, &tca, &tcb);
-	for (int attempt = 0; ; attempt++) {
-		if (!ext && packed_entries(h, h->ue) < wcap) { h->ue.reset(); HIPCHK(h, h->ue.alloc(8ull * (W + 1) * wcap)); }
-		if (ext && (key_entries(h, h->uw_keys) < wcap || !h->uw_vals)) {
-			h->uw_keys.reset(); h->uw_vals.reset();
-			HIPCHK(h, h->uw_keys.alloc(8ull * W * wcap)); HIPCHK(h, h->uw_vals.alloc(4ull * vw * wcap));
-		}
-		if (key_entries(h, h->us_keys) < scap || !h->us_b8 || (ext && !h->us_pkt)) {
-			h->us_keys.reset(); h->us_b8.reset(); h->us_pkt.reset();
-			HIPCHK(h, h->us_keys.alloc(8ull * W * scap)); HIPCHK(h, h->us_b8.alloc(scap)); if (ext) HIPCHK(h, h->us_pkt.alloc(4 * scap));
-		}
-		HIPCHK(h, hipMemsetAsync(wc, 0, 4 * h->nb_weak, h->stream)); HIPCHK(h, hipMemsetAsync(sc, 0, 4 * h->nb_sing, h->stream));
-		HIPCHK(h, hipMemsetAsync(fc, 0, sizeof(FinalizeCounters), h->stream)); HIPCHK(h, hipMemsetAsync(cursors, 0, 16, h->stream));
-		const CountOut out = count_out(h, !ext, cursors, wc, sc, fc);
-		rc = zero_work_counter(h); if (rc) return rc;
+	DevBuf mslots, mext;      /* an attempt's merge table, given back before the next one allocates */
+	return count_attempts(h, p, [&]() -> int { mslots.reset(); mext.reset(); return 0; }, [&](const CountOut &out, bool repeated, uint32_t &repeat_on) -> int {
+		if (repeated) merge_log2 += 3;
+		int rc = 0;
 		const int grid = (int)std::min<uint64_t>((uint64_t)num_cus(h) * 4, (nl / p.lgMain.list_stride + SK_LBATCH) / SK_LBATCH);
 		SkCountLaunch<W> k;
-		rc = sk_count_select<W>(h, ext, tracking, p.uni, k); if (rc) return rc;
-		if (tracking) HIPCHK(h, hipMemsetAsync(tv.d_unique, 0, 8 * (tv.n + 1), h->stream));
+		rc = sk_count_select<W>(h, p.ext, p.tracking, p.uni, k); if (rc) return rc;
+		if (p.tracking) HIPCHK(h, hipMemsetAsync(tv.d_unique, 0, 8 * (tv.n + 1), h->stream));
 		if (dbg()) { int nb = 0; hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)k.kern, SKC_THREADS, k.smem); fprintf(stderr, "sk_count<W=%d>: %d blocks per CU (LDS %zu), %llu lists, %u chunks\n", W, nb, k.smem, (unsigned long long)nl, p.nch); }
-		hipLaunchKernelGGL(k.kern, dim3(grid), dim3(SKC_THREADS), k.smem, h->stream, pool_view(h, h->l1), p.ls, p.lc, nl, h->k, out, f, h->work_counter.get<unsigned int>(), sk_dbg_flags("KMR_SK_COUNT_DBG"), tv, p.lgMain);
+		hipLaunchKernelGGL(k.kern, dim3(grid), dim3(SKC_THREADS), k.smem, h->stream, pool_view(h, h->l1), p.ls, p.lc, nl, h->k, out, p.f, h->work_counter.get<unsigned int>(), sk_dbg_flags("KMR_SK_COUNT_DBG"), tv, p.lgMain);
 		HIPCHK(h, hipGetLastError());
-		DevBuf mslots, mext;      /* freed at the end of the attempt */
-		if (n_items) {
-			/* the merge table holds the distinct keys of the long lists: few when a list is long because a k-mer repeats, at most the
-			 * k-mers of those lists; it starts small and the attempt is repeated with a larger one if it fills */
-			SkLong<W> &lgItems = p.lgItems;
-			if (mslots.alloc(sizeof(Slot<W>) << merge_log2) != hipSuccess) return fail(h, KMR_ERR_OOM, "merge table of the long lists");
-			if (ext && mext.alloc(sizeof(ExtSlot) << merge_log2) != hipSuccess) return fail(h, KMR_ERR_OOM, "merge table of the long lists");
-			hipLaunchKernelGGL(table_clear_kernel<W>, dim3(grid_for(1ull << merge_log2)), dim3(256), 0, h->stream, mslots.get<Slot<W>>(), mext.get<ExtSlot>(), 1ull << merge_log2);
-			lgItems.merge.slots = mslots.get<Slot<W>>(); lgItems.merge.ext = mext.get<ExtSlot>(); lgItems.merge.log2cap = merge_log2;
-			HIPCHK(h, hipMemsetAsync(lgItems.merge_used, 0, 8, h->stream));
-			rc = zero_work_counter(h); if (rc) return rc;
-			const int grid2 = (int)std::min<uint64_t>((uint64_t)num_cus(h) * 4, n_items);
-			hipLaunchKernelGGL(k.kern, dim3(grid2), dim3(SKC_THREADS), k.smem, h->stream, pool_view(h, h->l1), p.ls, p.lc, nl, h->k, out, f, h->work_counter.get<unsigned int>(), sk_dbg_flags("KMR_SK_COUNT_DBG"), tv, lgItems);
-			hipLaunchKernelGGL(sk_merge_emit_kernel<W>, dim3(grid_for(1ull << merge_log2)), dim3(256), 0, h->stream, lgItems.merge, out, f);
-			if (hipGetLastError() != hipSuccess) return fail(h, KMR_ERR_HIP, "long-list launches");
-		}
-		uint32_t cerr = 0;
-		HIPCHK(h, hipMemcpyAsync(&c, fc, sizeof(c), hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipMemcpyAsync(cur, cursors, 16, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(h, hipMemcpyAsync(&cerr, h->derr.get<uint32_t>(), 4, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(h, hipStreamSynchronize(h->stream));
-		if (n_items && (cerr & ERR_TABLE_FULL) && merge_log2 < 30) {      /* the merge table filled: again with a larger one */
-			cerr &= ~(uint32_t)(ERR_TABLE_FULL | ERR_ENTRIES_FULL);
-			HIPCHK(h, hipMemcpy(h->derr.get<uint32_t>(), &cerr, 4, hipMemcpyHostToDevice));
-			merge_log2 += 3;
-			continue;
-		}
-		if (!(cerr & ERR_ENTRIES_FULL)) break;
-		if ((wcap >= wmax && scap >= smax) || attempt >= 8) { overflowed = true; break; }
-		cerr &= ~(uint32_t)ERR_ENTRIES_FULL;
-		HIPCHK(h, hipMemcpy(h->derr.get<uint32_t>(), &cerr, 4, hipMemcpyHostToDevice));
-		wcap = std::min<uint64_t>(wmax, wcap * 2); if (keepSing) scap = std::min<uint64_t>(smax, scap * 2);
-		if (dbg()) fprintf(stderr, "sk count pass: entry buffers too small, retrying with %llu / %llu\n", (unsigned long long)wcap, (unsigned long long)scap);
-	}
-	time_end(h, KMR_TIME_COUNT, tca, tcb);
-	return 0;
+		if (!n_items) return 0;
+		/* the merge table holds the distinct keys of the long lists: few when a list is long because a k-mer repeats, at most the
+		 * k-mers of those lists; it starts small and the attempt is repeated with a larger one if it fills */
+		SkLong<W> &lgItems = p.lgItems;
+		if (mslots.alloc(sizeof(Slot<W>) << merge_log2) != hipSuccess) return fail(h, KMR_ERR_OOM, "merge table of the long lists");
+		if (p.ext && mext.alloc(sizeof(ExtSlot) << merge_log2) != hipSuccess) return fail(h, KMR_ERR_OOM, "merge table of the long lists");
+		hipLaunchKernelGGL(table_clear_kernel<W>, dim3(grid_for(1ull << merge_log2)), dim3(256), 0, h->stream, mslots.get<Slot<W>>(), mext.get<ExtSlot>(), 1ull << merge_log2);
+		lgItems.merge.slots = mslots.get<Slot<W>>(); lgItems.merge.ext = mext.get<ExtSlot>(); lgItems.merge.log2cap = merge_log2;
+		HIPCHK(h, hipMemsetAsync(lgItems.merge_used, 0, 8, h->stream));
+		rc = zero_work_counter(h); if (rc) return rc;
+		const int grid2 = (int)std::min<uint64_t>((uint64_t)num_cus(h) * 4, n_items);
+		hipLaunchKernelGGL(k.kern, dim3(grid2), dim3(SKC_THREADS), k.smem, h->stream, pool_view(h, h->l1), p.ls, p.lc, nl, h->k, out, p.f, h->work_counter.get<unsigned int>(), sk_dbg_flags("KMR_SK_COUNT_DBG"), tv, lgItems);
+		hipLaunchKernelGGL(sk_merge_emit_kernel<W>, dim3(grid_for(1ull << merge_log2)), dim3(256), 0, h->stream, lgItems.merge, out, p.f);
+		if (hipGetLastError() != hipSuccess) return fail(h, KMR_ERR_HIP, "long-list launches");
+		if (merge_log2 < 30) repeat_on = ERR_TABLE_FULL;
+		return 0;
+	});
 }
 /* the early count's entries behind this pass's (the slabs' unused tails are holes in both), its counters added */
 template <int W> int sk_append_early(kmr_handle *h, SkFinalize<W> &p) {
@@ -1894,11 +1887,12 @@ template <int W> int sk_append_early(kmr_handle *h, SkFinalize<W> &p) {
 template <int W> int finalize_superkmer_t(kmr_handle *h, uint32_t min_depth) {
 	int rc = sync_state(h);
 	if (rc) return rc;
-	hipEvent_t ea, eb; time_begin(h, 1, &ea, &eb);
+	TimeSpan whole(h, KMR_TIME_FINALIZE);
+	const uint64_t G = h->stats.raw_good_kmers;
 	SkFinalize<W> p;
 	p.f = finalize_params(h, min_depth);
 	p.keepSing = p.f.has_singletons && min_depth <= 1;
-	p.ext = h->ext;      /* extension values: entries of 15 value words, keys and values apart, bucketed by the scatter + per-bucket sort */
+	p.ext = h->ext; p.packed = !p.ext;      /* extension values: entries of 15 value words, keys and values apart, bucketed by the scatter + per-bucket sort */
 	p.tracking = h->cfg.size_tracker != 0;
 	if (!h->l1.head) { rc = pool_reserve(h, h->l1, 0, false); if (rc) return rc; }
 	rc = arena_reset(h); if (rc) return rc;
@@ -1910,26 +1904,23 @@ template <int W> int finalize_superkmer_t(kmr_handle *h, uint32_t min_depth) {
 	p.refined = h->sk_state && h->sk_fine_shift > 0;
 	if (p.refined) { rc = sk_refine_lists(h, p.nl); if (rc) return rc; }
 	rc = build_csr(h, h->l1, p.nl, 0, &p.ls, &p.lc, &p.nch); if (rc) return rc;
-	rc = sk_entry_buffers<W>(h, p, h->stats.raw_good_kmers); if (rc) return rc;
+	/* entry buffers: sequencing data keeps a few per cent of its k-mers as weak entries */
+	rc = count_entry_buffers(h, p, G, sk_entry_slack(h), G / (p.f.has_singletons ? 8 : 3), G / 3, h->sk_exchange && h->cfg.world_size > 1); if (rc) return rc;
 	rc = sk_count_uniform<W>(h, p.tracking, p.uni, p.f.uni_wbits); if (rc) return rc;
 	h->last_count_uniform = p.uni;
 	if (p.tracking) { rc = sk_track_view(h, p.tv); if (rc) return rc; }
 	p.lgMain = sk_own_lists<W>(h, p.refined);
 	bool device_error = false;
 	rc = sk_early_takeover<W>(h, p, min_depth, device_error); if (rc) return rc;
-	if (device_error) { time_end(h, 1, ea, eb); return sync_state(h); }
+	if (device_error) { whole.end(); return sync_state(h); }
 	rc = sk_long_items<W>(h, p); if (rc) return rc;
-	bool overflowed = false;
-	rc = sk_count_pass<W>(h, p, overflowed); if (rc) return rc;
-	if (overflowed) { time_end(h, 1, ea, eb); return fail(h, KMR_ERR_CAPACITY, "entry buffers of the count pass overflowed at their upper bound (internal sizing error)"); }
+	rc = sk_count_pass<W>(h, p); if (rc) return rc;
 	h->stats.unique_kmers = p.c.unique;
 	h->stats.singleton_kmers = p.f.has_singletons ? p.c.singletons : 0;
 	if (p.tracking) { rc = sk_track_elements(h, p.tv, p.f.has_singletons); if (rc) return rc; }
 	if (p.early_slots) { rc = sk_append_early<W>(h, p); if (rc) return rc; }
 	h->early.active = false;
-	hipEvent_t tma, tmb; time_begin(h, KMR_TIME_BUCKETS, &tma, &tmb);
-	rc = finish_maps_from_entries(h, p.wc, p.sc, p.cur[0], p.cur[1], p.c.weak_kept, p.c.sing_kept, p.keepSing, !p.ext, h->tune.bb_fixed_bins);
-	time_end(h, KMR_TIME_BUCKETS, tma, tmb);
+	{ TimeSpan t(h, KMR_TIME_BUCKETS); rc = finish_maps_from_entries(h, p.wc, p.sc, p.cur[0], p.cur[1], p.c.weak_kept, p.c.sing_kept, p.keepSing, p.packed, h->tune.bb_fixed_bins); }
 	if (rc) return rc;
 	h->last_bb_fallback = false;
 	if (h->bb_overflow) {
@@ -1942,24 +1933,16 @@ template <int W> int finalize_superkmer_t(kmr_handle *h, uint32_t min_depth) {
 		if (ovf) {
 			if (dbg()) fprintf(stderr, "bucket build: a bin of the radix partition overflowed its capacity, again with measured bins\n");
 			h->last_bb_fallback = true;
-			rc = sk_count_pass<W>(h, p, overflowed); if (rc) return rc;
-			if (overflowed) { time_end(h, 1, ea, eb); return fail(h, KMR_ERR_CAPACITY, "entry buffers of the count pass overflowed at their upper bound (internal sizing error)"); }
+			rc = sk_count_pass<W>(h, p); if (rc) return rc;
 			if (p.early_slots) { rc = sk_append_early<W>(h, p); if (rc) return rc; }
-			time_begin(h, KMR_TIME_BUCKETS, &tma, &tmb);
-			rc = finish_maps_from_entries(h, p.wc, p.sc, p.cur[0], p.cur[1], p.c.weak_kept, p.c.sing_kept, p.keepSing, !p.ext, false);
-			time_end(h, KMR_TIME_BUCKETS, tma, tmb);
+			{ TimeSpan t(h, KMR_TIME_BUCKETS); rc = finish_maps_from_entries(h, p.wc, p.sc, p.cur[0], p.cur[1], p.c.weak_kept, p.c.sing_kept, p.keepSing, p.packed, false); }
 			if (rc) return rc;
 		}
 	}
 	h->last_saturated_keys = 0; h->last_saturated_batches = 0;
 	if (p.c.saturated) { rc = saturated_fix_t<W>(h, p.ls, p.lc, p.nl, p.c.saturated, p.c.sat_sightings, p.f.has_singletons); if (rc) return rc; }
-	time_end(h, 1, ea, eb);
-	h->has_singletons = p.keepSing;
-	h->stats.weak_entries = h->weak.n; h->stats.singleton_entries = p.keepSing ? h->sing.n : 0;
-	h->finalized = true; h->map_gen++;
-	rc = sync_state(h);
-	if (!rc && !h->arena_overflow.empty()) rc = arena_reset(h);
-	return rc;
+	whole.end();
+	return publish_maps(h, p.keepSing);
 }
 /* kmr_count_lists_prefix: the count pass over this handle's lists below `hi`, now, into entry buffers of their own -- the lower part of
  * the list space is counted while the upper part is still on the wire; kmr_finalize counts what is left and takes these entries
@@ -1983,8 +1966,7 @@ template <int W> int count_prefix_superkmer_t(kmr_handle *h, uint32_t min_depth,
 	 * owner whose lists hold more than its own reads' share) sets ERR_ENTRIES_FULL in the early pass's own error word, which only
 	 * kmr_finalize reads: it voids the early count and counts every list itself (kmr_build_info "early_overflowed") */
 	const uint64_t G = h->stats.raw_good_kmers;      /* (an owner's lists hold about as many k-mers as its own reads gave: the job's share of one rank) */
-	const uint64_t slack = (uint64_t)num_cus(h) * 4 * 8192 + 16;
-	uint64_t want = (uint64_t)((double)G * ((double)hi / (double)nl) / (f.has_singletons ? 6.0 : 2.5)) + slack;
+	uint64_t want = (uint64_t)((double)G * ((double)hi / (double)nl) / (f.has_singletons ? 6.0 : 2.5)) + sk_entry_slack(h);
 	if (h->tune.early_entry_share >= 0) { want = (uint64_t)((double)G * h->tune.early_entry_share) + 16384; h->early.ue.reset(); }      /* kmr_tune "early_entry_share" */
 	rc = h->early.ue.reserve(h, "early count ue", 8ull * (W + 1) * want); if (rc) return rc;
 	rc = h->early.cursor.reserve(h, "early count cursor", 16); if (rc) return rc;
@@ -2011,9 +1993,9 @@ template <int W> int count_prefix_superkmer_t(kmr_handle *h, uint32_t min_depth,
 		const int grid = (int)std::min<uint64_t>((uint64_t)num_cus(h) * 4, (n_work + SK_LBATCH) / SK_LBATCH);
 		SkCountLaunch<W> k;
 		rc = sk_count_select<W>(h, false, false, uni, k); if (rc) return rc;
-		hipEvent_t a, b; time_begin(h, KMR_TIME_COUNT, &a, &b);
+		TimeSpan t(h, KMR_TIME_COUNT);
 		hipLaunchKernelGGL(k.kern, dim3(grid), dim3(SKC_THREADS), k.smem, h->stream, pool_view(h, h->l1), ls, lc, hi, h->k, out, f, h->work_counter.get<unsigned int>(), sk_dbg_flags("KMR_SK_COUNT_DBG"), tv, lg);
-		time_end(h, KMR_TIME_COUNT, a, b);
+		t.end();
 		HIPCHK(h, hipGetLastError());
 	}
 	h->early.active = true; h->early.hi = hi; h->early.min_depth = min_depth;
@@ -2271,6 +2253,7 @@ int kmr_build_info(kmr_handle *h, const char *what, double *value) {
 	else if (k == "score_path") *value = (double)h->last_score_path;
 	else if (k == "saturated_keys") *value = (double)h->last_saturated_keys;
 	else if (k == "saturated_batches") *value = (double)h->last_saturated_batches;
+	else if (k == "count_attempts") *value = (double)h->last_count_attempts;
 	else if (k == "device_blocks_live") *value = (double)g_blocks_live.load();
 	else if (k == "filter_score_ms") *value = h->last_score_ms;
 	else if (k == "select_ms") *value = h->last_select_ms;
@@ -3061,9 +3044,9 @@ int kmr_insert_records_dev(kmr_handle *h, const void *dev_records, uint64_t n) {
 	if (h->superkmer_mode) return fail(h, KMR_ERR_UNSUPPORTED, "k-mer records are inserted by build_mode 1 / 2");
 	if (h->partition_mode) { int prc = insert_records_partition(h, dev_records, n); h->stream_base += n; return prc; }
 	int rc = ensure_capacity(h, n); if (rc) return rc;
-	hipEvent_t a, b; time_begin(h, 0, &a, &b);
+	TimeSpan t(h, 0);
 	with_w_ext(h, [&](auto W, auto EXT) { hipLaunchKernelGGL((insert_records_kernel<W(), EXT()>), dim3(grid_for(n)), dim3(256), 0, h->stream, table_of<W()>(h), (const uint32_t *)dev_records, n, dev_params(h), h->stream_base); });
-	time_end(h, 0, a, b);
+	t.end();
 	HIPCHK(h, hipGetLastError());
 	h->stream_base += n;
 	return KMR_OK;

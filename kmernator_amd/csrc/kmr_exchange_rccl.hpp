@@ -176,7 +176,6 @@ int kmr_exchange_add_reads_dev(kmr_handle *h, const void *dev_bases, const void 
 	if (n_reads && (!dev_bases || !dev_offsets)) { lrc = fail(h, KMR_ERR_INVALID_ARG, "null device buffer"); n_reads = 0; total_bases = 0; }
 	if (h->tune.exchange_fail_once) { h->tune.exchange_fail_once = false; lrc = fail(h, KMR_ERR_OOM, "injected failure (kmr_tune exchange_fail_once: the tests' way to fail one rank of a collective step)"); n_reads = 0; total_bases = 0; }
 	std::vector<uint64_t> mine(row, 0), all;
-	hipEvent_t ea = nullptr, eb = nullptr;
 	auto status = [&](int code) { mine[row - 1] = (uint64_t)(int64_t)code; };
 	if (h->superkmer_mode) {
 		/* global ordinals: this rank's batch begins behind the batches of the lower ranks, and behind everything the job was fed before */
@@ -223,10 +222,10 @@ int kmr_exchange_add_reads_dev(kmr_handle *h, const void *dev_bases, const void 
 		std::fill(mine.begin(), mine.end(), 0); status(lrc);
 		rc = xc_allgather_rows(h, mine, all); if (rc) return rc;
 		rc = xc_agree(h, lrc, all, row); if (rc) return rc;
-		time_begin(h, KMR_TIME_EXCHANGE, &ea, &eb);
+		TimeSpan tx(h, KMR_TIME_EXCHANGE);
 		rc = xc_alltoallv(h, (const uint8_t *)h->xc_send2.get(), sco, scb, (uint8_t *)h->xc_recv2.get(), rco, rc_c, 1, 8);
 		if (!rc) rc = xc_alltoallv(h, (const uint8_t *)h->xc_send.get(), sgo, sgb, (uint8_t *)h->xc_recv.get(), rgo, rc_g, slices, 16);
-		time_end(h, KMR_TIME_EXCHANGE, ea, eb);
+		tx.end();
 		if (rc) return rc;
 		HIPCHK(h, hipStreamSynchronize(h->stream));
 		h->xc_bytes_to_peers += 16 * ag + 8 * ac;
@@ -273,9 +272,9 @@ int kmr_exchange_add_reads_dev(kmr_handle *h, const void *dev_bases, const void 
 	std::fill(mine.begin(), mine.end(), 0); status(lrc);
 	rc = xc_allgather_rows(h, mine, all); if (rc) return rc;
 	rc = xc_agree(h, lrc, all, row); if (rc) return rc;
-	time_begin(h, KMR_TIME_EXCHANGE, &ea, &eb);
+	TimeSpan tx(h, KMR_TIME_EXCHANGE);
 	rc = xc_alltoallv(h, (const uint8_t *)h->xc_send.get(), soff, sbytes, (uint8_t *)h->xc_recv.get(), roff, rbytes, slices, rb);
-	time_end(h, KMR_TIME_EXCHANGE, ea, eb);
+	tx.end();
 	if (rc) return rc;
 	HIPCHK(h, hipStreamSynchronize(h->stream));
 	h->xc_bytes_to_peers += sent;

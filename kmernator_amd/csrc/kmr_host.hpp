@@ -246,6 +246,7 @@ struct KMR_HIDDEN kmr_handle : HandleMem, BuildMem, ExchangeMem {
 	double last_dedup_ms = 0, last_dedup_key_ms = 0, last_dedup_sort_ms = 0, last_dedup_consensus_ms = 0;      /* the last kmr_dedup_fragments*: the whole call, its key kernel, its radix sorts, its consensus kernel (HIP events, taken with kmr_tune "dedup_timing" only; kmr_build_info) */
 	uint64_t last_pair_hash_collisions = 0;      /* ... and how many of its runs of equal hash keys held more than one distinct common name */
 	uint64_t last_saturated_keys = 0, last_saturated_batches = 0;      /* what the last kmr_finalize's saturated-key pass redid, in how many batches */
+	int last_count_attempts = 0;       /* how often the last count pass of a kmr_finalize ran before its entries fit (kmr_build_info "count_attempts") */
 	bool qual_mixed = false;           /* a build that has seen two different quality characters stops asking (qrange) */
 	/* exchange with world_size > 1: sk_bits are the COARSE lists reads are scattered into and that travel; each holds 2^sk_fine_shift
 	 * fine lists, made by sk_refine_kernel before the count pass (fine state: sk_fine_state) */
@@ -357,6 +358,17 @@ template <int N> struct EventTimer {
 	~EventTimer() { for (auto e : ev) if (e) hipEventDestroy(e); }
 	void mark(int i, hipStream_t s) { if (on) hipEventRecord(ev[i], s); }
 	double ms(int a, int b) const { float t = 0; return on && hipEventElapsedTime(&t, ev[a], ev[b]) == hipSuccess ? t : 0.0; }      /* after the stream has been waited for */
+};
+
+/* One timed span of work on the handle's stream for group `which` of kmr_kernel_time: the first event is recorded here, the second by
+ * end() -- or by the destructor, so that a return in between leaks no event --, and the pair waits in h->pending_events for sync_state. */
+struct TimeSpan {
+	kmr_handle *h; int which; hipEvent_t a = nullptr, b = nullptr; bool open = true;
+	TimeSpan(kmr_handle *h_, int which_) : h(h_), which(which_) { hipEventCreate(&a); hipEventCreate(&b); hipEventRecord(a, h->stream); }
+	TimeSpan(const TimeSpan &) = delete;
+	TimeSpan &operator=(const TimeSpan &) = delete;
+	~TimeSpan() { end(); }
+	void end() { if (!open) return; open = false; hipEventRecord(b, h->stream); h->pending_events[which].push_back(std::make_pair(a, b)); }
 };
 
 /* ---- defined in kmr_api.hip: what the read stages use of the spectrum ---- */

@@ -232,6 +232,8 @@ def test_reference_reads_without_quals_and_discarded(mode):
     rbn = ReadBatch([rb.seq(i) for i in range(rb.n)], None, disc)
     cfg = default_config(21, num_buckets_weak=64, num_buckets_singleton=64)
     o, p = run_both(cfg, rbn, mode=mode)
+    if mode != 1:
+        assert p.build_info("count_attempts") == 1      # entry buffers of the default size take the count pass's entries at once
     compare_weak_images(o.image(KMR_MAP_WEAK), p.image(KMR_MAP_WEAK), p.kb, False)
 
 
@@ -308,13 +310,20 @@ def test_three_partition_levels_and_chunk_recycling(k, recycle):
 
 
 @pytest.mark.parametrize("min_depth", [1, 2])
-def test_entry_buffers_grow_when_the_estimate_was_too_small(min_depth):
-    """The count pass writes kept entries into buffers sized from a sampled share of repeated keys; if they overflow the
-    pass is run again with larger ones (here the estimate is forced to almost nothing)."""
+@pytest.mark.parametrize("mode,ext", [(2, False), (3, False), (2, True), (3, True)])
+def test_entry_buffers_grow_when_the_estimate_was_too_small(min_depth, mode, ext):
+    """The count pass writes kept entries into buffers sized from an estimate (build_mode 2: a sampled share of repeated keys); if they
+    overflow the pass is run again with larger ones (here the estimate is forced to almost nothing).  Both list builds take the one
+    loop: direction-counting values (mode 3: packed entries) and extension values (mode 2: the narrow tallies, then the wide table;
+    mode 3: keys and values apart)."""
     rb = synth_reads(40000, read_len=100, seed=23, quality="noisy")
-    cfg = default_config(31, estimated_raw_kmers=40000 * 70)
-    o, p = run_both(cfg, rb, min_depth=min_depth, mode=2, entry_share=0.00001)
-    compare_weak_images(o.image(KMR_MAP_WEAK), p.image(KMR_MAP_WEAK), p.kb, False)
+    if ext:
+        cfg = default_config(21, value_kind=KMR_VALUE_EXT, min_weight=0.0, min_quality_score=2, estimated_raw_kmers=40000 * 80)
+    else:
+        cfg = default_config(31, estimated_raw_kmers=40000 * 70)
+    o, p = run_both(cfg, rb, min_depth=min_depth, mode=mode, entry_share=0.00001)
+    assert p.build_info("count_attempts") >= 2
+    compare_weak_images(o.image(KMR_MAP_WEAK), p.image(KMR_MAP_WEAK), p.kb, ext)
     assert np.array_equal(o.image(KMR_MAP_SINGLETON), p.image(KMR_MAP_SINGLETON))
 
 
