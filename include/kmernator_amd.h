@@ -526,6 +526,37 @@ int kmr_ingest_fastq(kmr_handle *h, const char *text, uint64_t len, uint32_t inp
                      int store_comment, kmr_reads **out);
 int kmr_ingest_fastq_dev(kmr_handle *h, const void *dev_text, uint64_t len, uint32_t input_quality_base,
                          int store_comment, kmr_reads **out);
+/* ---- FASTA and FASTA+QUAL ingest on the device --------------------------
+ * The '>' side of ReadSet::appendAnyFile (src/ReadFileReader.h:205-231): FastaStreamParser and, with a qual text, FastaQualStreamParser
+ * (:844-1006) over a whole in-memory text, into the same kind of batch as kmr_ingest_fastq gives -- FASTA reads, the 454 pair of
+ * reads.fasta + reads.qual, genomes and contigs for kmr_subtract_reference.  qual_text == NULL: every base gets Read::REF_QUAL (127),
+ * which kmr_add_read_batch weighs as 1.0.  Otherwise record i of the qual text belongs to record i of the FASTA (same trimmed name), a
+ * number v becomes the character min(v, 127 - start - 1) + start (convertQualIntsToChars, src/Utils.h:652-667; start = the handle's
+ * fastq_start_char), and validateFastqStart runs as for FASTQ: kmr_reads_info reports the other base if the batch was shifted.
+ *
+ * A record is a '>' line followed directly by one or more non-empty lines; its bases are those lines concatenated and upper-cased.
+ * Lines end at '\n' (the last may lack it; '\r' is content); empty lines may stand between a record and the next header and at the
+ * end.  Name, comment and the Casava-1.8 filter apply to the header as to the '@' line of FASTQ; name_off/name_len of kmr_reads_copy
+ * span the header behind '>' in `text`.  Everything accepted is parsed as the reference parses it; what its stream and mmap forms
+ * disagree on or mangle returns KMR_ERR_INVALID_ARG with the cause in kmr_last_error: text or an empty line before the first
+ * header, a header followed by a header or at the end of the text, an empty line before or between sequence lines, an empty name;
+ * in the qual text also a byte other than digit, blank and tab, more than 3 digits, a line ending in a digit where the next of the
+ * record starts with one (the reference joins them into one number), and a different record count, name or number of qualities.
+ * A record of more than 2^32 - 2 bases returns KMR_ERR_UNSUPPORTED.  An empty text is an empty batch.
+ *
+ * The host form copies the texts to the device; the _dev form reads the caller's device memory in place, at any alignment, and
+ * touches no byte outside [text, text + len) and [qual_text, qual_text + qual_len).  A record is spread over the whole device
+ * whether it is one line of 100 Mbp or 60-column lines.  The call's scratch (about 36 bytes per line and 20 per record, 44 and 8 for the
+ * qual text) stays with the handle, grow-only, until kmr_destroy.
+ *
+ * Not covered: an input quality base that differs from the start character (the reference then rescales REF_QUAL itself,
+ * src/ReadSet.cpp:324,336: there is no quality-base argument); gz / bgzf input; multi-line FASTQ; the reference's skip of up to
+ * 100 000 junk lines between records.  kmr_reads_twobit stays one thread per read (slow for a genome), and
+ * kmr_artifact_filter_create keeps its own host-side FASTA parse. */
+int kmr_ingest_fasta(kmr_handle *h, const char *text, uint64_t len, const char *qual_text, uint64_t qual_len,
+                     int store_comment, kmr_reads **out);
+int kmr_ingest_fasta_dev(kmr_handle *h, const void *dev_text, uint64_t len, const void *dev_qual_text, uint64_t qual_len,
+                         int store_comment, kmr_reads **out);
 /* n_filtered = records dropped by the Casava filter; input_quality_base = the base after detection */
 int kmr_reads_info(const kmr_reads *r, uint64_t *n_reads, uint64_t *total_bases,
                    uint32_t *input_quality_base, uint64_t *n_filtered);

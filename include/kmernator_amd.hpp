@@ -81,6 +81,8 @@ public:
 class ReadSet {
 public:
 	ReadSet(KmerSpectrum &sp, const std::string &fastqText, uint32_t inputQualityBase = 0, bool storeComment = true);
+	/* FASTA text, or a FASTA + QUAL pair (qualText != nullptr), parsed on the device: kmr_ingest_fasta */
+	static std::unique_ptr<ReadSet> fromFasta(KmerSpectrum &sp, const std::string &fastaText, const std::string *qualText = nullptr, bool storeComment = true);
 	~ReadSet() { kmr_reads_free(_r); }
 	ReadSet(const ReadSet &) = delete; ReadSet &operator=(const ReadSet &) = delete;
 	uint64_t getSize() const { return _n; }
@@ -222,6 +224,11 @@ private:
 inline ReadSet::ReadSet(KmerSpectrum &sp, const std::string &fastqText, uint32_t inputQualityBase, bool storeComment) : _text(fastqText) {
 	sp.check(kmr_ingest_fastq(sp._h, _text.data(), _text.size(), inputQualityBase, storeComment ? 1 : 0, &_r), "kmr_ingest_fastq");
 	load();
+}
+inline std::unique_ptr<ReadSet> ReadSet::fromFasta(KmerSpectrum &sp, const std::string &fastaText, const std::string *qualText, bool storeComment) {
+	kmr_reads *r = nullptr;
+	sp.check(kmr_ingest_fasta(sp._h, fastaText.data(), fastaText.size(), qualText ? qualText->c_str() : nullptr, qualText ? qualText->size() : 0, storeComment ? 1 : 0, &r), "kmr_ingest_fasta");
+	return std::unique_ptr<ReadSet>(new ReadSet(fastaText, r));
 }
 inline void ReadSet::load() {
 	kmr_reads_info(_r, &_n, &_bases, &_qbase, &_filtered);

@@ -84,7 +84,7 @@ EXPORTS = [
     "kmr_dump_mercount", "kmr_dump_mergraph", "kmr_hash", "kmr_hash_of_kind", "kmr_bucket_idx", "kmr_local_thread_id",
     "kmr_distributed_thread_id", "kmr_compress_sequence", "kmr_least_complement", "kmr_extract_by_owner_dev",
     "kmr_insert_records_dev", "kmr_stream", "kmr_kernel_time", "kmr_kernel_time_reset", "kmr_reset", "kmr_release_table", "kmr_score_reads",
-    "kmr_ingest_fastq", "kmr_ingest_fastq_dev", "kmr_reads_info", "kmr_reads_device_ptrs", "kmr_reads_copy",
+    "kmr_ingest_fastq", "kmr_ingest_fastq_dev", "kmr_ingest_fasta", "kmr_ingest_fasta_dev", "kmr_reads_info", "kmr_reads_device_ptrs", "kmr_reads_copy",
     "kmr_add_read_batch", "kmr_reads_free", "kmr_histogram", "kmr_histogram_bins", "kmr_merge_image", "kmr_subtract_reference", "kmr_subtracted", "kmr_score_read_batch",
     "kmr_artifact_config_init", "kmr_artifact_filter_create", "kmr_artifact_filter_info", "kmr_artifact_filter_entries",
     "kmr_artifact_filter_free", "kmr_artifact_filter_apply",
@@ -161,6 +161,8 @@ def load():
     lib.kmr_release_table.argtypes = [vp]
     lib.kmr_ingest_fastq.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(vp)]
     lib.kmr_ingest_fastq_dev.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(vp)]
+    lib.kmr_ingest_fasta.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, C.c_int, C.POINTER(vp)]
+    lib.kmr_ingest_fasta_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, C.c_int, C.POINTER(vp)]
     lib.kmr_reads_info.argtypes = [vp, u64p, u64p, u32p, u64p]
     lib.kmr_reads_device_ptrs.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     lib.kmr_reads_copy.argtypes = [vp, vp, vp, u64p, u64p, u32p]

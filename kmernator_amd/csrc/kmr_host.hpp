@@ -114,6 +114,7 @@ struct HandleMem {                   /* ... by kmr_destroy */
 	DevBuf trk;                      /* size tracker: one record per read of the last call */
 	DevBuf scan_sums;
 	DevBuf score_buf;                /* temporaries of kmr_score_reads*, grow-only */
+	DevBuf fasta_buf[2][3];          /* scratch of kmr_ingest_fasta* (FASTA text, QUAL text; per block, per line, per record), grow-only */
 	DevBuf lut;                      /* lookup accelerator over the weak map (LutView) */
 	DevBuf dPk;                      /* build_mode 3: table of k-fold quality products */
 	DevBuf d_uni;                    /* uniform-weight flags of adopted records */

@@ -19,6 +19,9 @@
  *                        spans, and the quality-base check of the first 19 999 kept reads
  *   ingest_shift_quals   the one-time 33 <-> 64 flip of __setFastqStart, applied to the whole batch
  *
+ * FASTA and FASTA+QUAL text (FastaStreamParser / FastaQualStreamParser, :844-1006) goes the same way into the same batch: see the
+ * fasta_* kernels below, which share the line index, trimName and the quality shift with the FASTQ side.
+ *
  * Strictness: the reference silently skips up to 100 000 lines that do not start with '@' where a
  * record should begin (readName); this parser accepts blank lines between records only and reports
  * anything else as malformed.  Every input the parser accepts is parsed exactly as the reference does.
@@ -121,17 +124,39 @@ void ingest_index_lines(const uint8_t *text, uint64_t len, const uint64_t *block
 }
 /* one thread per line: the line ends at the first '\n' at or after its start, and everything between that and the next
  * non-empty line's start is '\n' -- so the end is found from the next start (one byte looked at when no blank lines
- * intervene) instead of by reading the line; only the last line is read to its end */
-__global__ void ingest_line_lengths(const uint8_t *text, uint64_t len, const uint64_t *line_start, uint64_t n_lines, uint32_t *line_len, uint32_t *err) {
+ * intervene) instead of by reading the line; only the last line is read to its end -- or, with last_from_end (FASTA, where the
+ * last line may be a whole genome), found from the end of the text in the same way, over the newlines that close it */
+__global__ void ingest_line_lengths(const uint8_t *text, uint64_t len, const uint64_t *line_start, uint64_t n_lines, uint32_t *line_len, uint32_t *err, bool last_from_end) {
 	const bool aligned = ((uintptr_t)text & 15) == 0;
 	for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n_lines; i += (uint64_t)gridDim.x * blockDim.x) {
 		const uint64_t p = line_start[i];
 		uint64_t e;
 		if (i + 1 < n_lines) { e = line_start[i + 1] - 1; while (e > p && text[e - 1] == '\n') e--; }
+		else if (last_from_end) { e = len; while (e > p && text[e - 1] == '\n') e--; }
 		else e = ing_line_end(text, len, p, aligned);
 		if (e - p > 0xffffffffull) { atomicOr(err, (uint32_t)ING_ERR_LEN); e = p; }
 		line_len[i] = (uint32_t)(e - p);
 	}
+}
+
+/* trimName on a name line without its marker (src/Utils.h:561-598), shared by the '@' lines of FASTQ and the '>' lines of FASTA:
+ * ws = length of the name (0: an empty name, which ends the reference's stream); good = not a Casava-1.8 failed-filter read;
+ * pair = the digit the reference appends as "/1" or "/2" when it rewrites "name 1:N:..." and comments are not stored, else 0 */
+struct IngName { uint32_t ws; bool good; uint8_t pair; };
+__device__ __forceinline__ IngName ing_trim_name(const uint8_t *nm, uint32_t nl, int store_comment) {
+	IngName t; t.ws = nl; t.good = true; t.pair = 0;
+	for (uint32_t i = 0; i < nl; i++) { const uint8_t c = nm[i]; if (c == ' ' || c == '\t' || c == '\r' || c == '\n') { t.ws = i; break; } }
+	const uint32_t ws = t.ws;
+	if (ws && ws < nl && nl >= ws + 2) {
+		const uint8_t *c = nm + ws + 1; const uint32_t cl = nl - ws - 1;
+		const bool casava = cl >= 6 && c[1] == ':' && c[3] == ':' && c[5] == ':' && (c[0] == '1' || c[0] == '2') && (c[2] == 'Y' || c[2] == 'N');
+		if (casava && (ws <= 2 || nm[ws - 2] != '/')) {
+			const uint32_t p2 = store_comment ? ws : ws + 2;     /* the reference moves pos when it rewrites "name 1:Y" to "name/1" */
+			if (nm[p2 + 3] == 'Y') t.good = false;
+			if (!store_comment) t.pair = c[0];
+		}
+	}
+	return t;
 }
 
 /* one thread per record */
@@ -146,22 +171,10 @@ __global__ void ingest_records(const uint8_t *text, const uint64_t *line_start, 
 		if (text[s2] != '+') e |= ING_ERR_PLUS;
 		if (l3 != l1) e |= ING_ERR_LEN;
 		if (e) { atomicOr(err, e); keep[r] = 0; kept_len[r] = 0; continue; }
-		/* trimName on the name line without its marker (src/Utils.h:561-598) */
-		const uint8_t *nm = text + s0 + 1; const uint32_t nl = l0 - 1;
-		uint32_t ws = nl;
-		for (uint32_t i = 0; i < nl; i++) { const uint8_t c = nm[i]; if (c == ' ' || c == '\t' || c == '\r' || c == '\n') { ws = i; break; } }
-		if (ws == 0) { atomicOr(err, (uint32_t)ING_ERR_NAME); keep[r] = 0; kept_len[r] = 0; continue; }   /* an empty name ends the reference's stream */
-		bool good = true;
-		if (ws < nl && nl >= ws + 2) {
-			const uint8_t *c = nm + ws + 1; const uint32_t cl = nl - ws - 1;
-			const bool casava = cl >= 6 && c[1] == ':' && c[3] == ':' && c[5] == ':' && (c[0] == '1' || c[0] == '2') && (c[2] == 'Y' || c[2] == 'N');
-			if (casava && (ws <= 2 || nm[ws - 2] != '/')) {
-				const uint32_t p2 = store_comment ? ws : ws + 2;     /* the reference moves pos when it rewrites "name 1:Y" to "name/1" */
-				if (nm[p2 + 3] == 'Y') good = false;
-			}
-		}
-		keep[r] = good ? 1u : 0u;
-		kept_len[r] = good ? l1 : 0u;
+		const IngName t = ing_trim_name(text + s0 + 1, l0 - 1, store_comment);
+		if (t.ws == 0) { atomicOr(err, (uint32_t)ING_ERR_NAME); keep[r] = 0; kept_len[r] = 0; continue; }   /* an empty name ends the reference's stream */
+		keep[r] = t.good ? 1u : 0u;
+		kept_len[r] = t.good ? l1 : 0u;
 	}
 }
 
@@ -227,6 +240,248 @@ void ingest_copy(const uint8_t *text, uint64_t len, const uint64_t *line_start, 
 			if (j + 1 < ING_VALIDATE_READS && L > 0 && (uint8_t)(text[sq] + qdelta) != 127 && (mn < start_char || mn > start_char + 40)) atomicOr(flip, 1u);
 		}
 	}
+}
+
+/* ---- FASTA and FASTA+QUAL text -> read batch: FastaStreamParser / FastaQualStreamParser (src/ReadFileReader.h:844-1006) ----
+ * A record is a '>' line and every line up to the next '>' line, so neither the number of lines of a record nor their lengths are
+ * known in advance, and one record may be a whole genome on one line.  The lines are indexed as for FASTQ (line_start, line_len of
+ * the non-empty lines); then
+ *   fasta_classify        per line: is it a header; the structural rules, from the neighbouring lines' starts and lengths
+ *   (exclusive scan of the header flags: the record of every line)
+ *   fasta_headers         per header: first line of its record, trimName, Casava filter -> keep[r]
+ *   fasta_kept_lengths    per line: its length if it is a sequence line of a kept record, else 0
+ *   (exclusive scans: kept index of a record, place of a line in the output)
+ *   fasta_records         per kept record: offsets, name span, the 2^32 - 2 limit
+ *   fasta_copy            per 16 OUTPUT bytes: finds its line(s) in the scan by bisection, gathers, upper-cases, stores 16 bytes
+ *   qualities: a fill with Read::REF_QUAL, or for a QUAL text (indexed and classified by the same kernels)
+ *   fasta_qual_tokens<0>  per 16 text bytes: the bytes allowed, numbers of 1-3 digits; numbers per 4 KB block
+ *   (exclusive scan)
+ *   fasta_qual_tokens<1>  the running number count at every line start
+ *   fasta_qual_lines      per line: where its first number goes in the output; per record: names equal, #quals == #bases; glued lines
+ *   fasta_qual_tokens<2>  one lane per number: the clamped character (convertQualIntsToChars, src/Utils.h:652-667)
+ *   fasta_qual_flip       validateFastqStart over the first 19 999 kept reads
+ * No thread walks a sequence or quality line: a thread's loops run over its 16 bytes, over the bisection steps, over a header
+ * line (trimName) or over the empty lines that follow a line.
+ *
+ * What is refused, and what the reference does there (stream form: getBasesOrQuals :906-927 under readName :584-617; mmap form: the
+ * loop of readRecord(RecordPtr) :887-891 and SequenceRecordParser::parse, src/Utils.h:617-645):
+ *   text or an empty line before the first header   stream: readName skips up to 100 000 such lines; mmap: throws on the first byte
+ *   a header followed by a header                    stream: the second header is read as the first one's bases; mmap: no bases
+ *   a header at the end of the text                  both: a read without bases (and mmap runs strchr over the end of a text without '\n')
+ *   an empty line before or between sequence lines   stream: the record ends there and the rest is skipped as junk; mmap: concatenated
+ *   an empty name (">" or "> x")                     both: the whole input ends there without a word
+ *   QUAL: a byte other than digit, blank, tab        operator>> fails there and the rest of the record's qualities is dropped
+ *   QUAL: a line ending and the next starting in a digit   the lines are joined without a separator: two numbers become one
+ *   QUAL: more than 3 digits                         not a quality; beyond int it fails as above
+ *   QUAL: record count, names, #quals != #bases      the reference throws (readName :981-987, nextRead :317-319) */
+enum { FA_ERR_LEAD = 64, FA_ERR_HDR_HDR = 128, FA_ERR_HDR_END = 256, FA_ERR_BLANK = 512, FA_ERR_LONG = 1024, FA_ERR_QBYTE = 2048, FA_ERR_QDIGITS = 4096,
+       FA_ERR_QGLUE = 8192, FA_ERR_QNAME = 16384, FA_ERR_QCOUNT = 32768 };
+static const uint64_t FA_NONE = ~0ull;
+
+/* one thread per line */
+__global__ void fasta_classify(const uint8_t *text, const uint64_t *line_start, const uint32_t *line_len, uint64_t n_lines, uint32_t *is_header, uint32_t *err) {
+	for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n_lines; i += (uint64_t)gridDim.x * blockDim.x) {
+		const uint64_t s = line_start[i];
+		const bool hdr = text[s] == '>';
+		uint32_t e = 0;
+		if (i == 0 && (s != 0 || !hdr)) e |= FA_ERR_LEAD;
+		if (i + 1 < n_lines) {
+			const uint64_t s1 = line_start[i + 1];
+			const bool hdr1 = text[s1] == '>';
+			if (hdr && hdr1) e |= FA_ERR_HDR_HDR;
+			if (!hdr1 && s1 != s + line_len[i] + 1) e |= FA_ERR_BLANK;      /* empty lines are allowed in front of a header only */
+		} else if (hdr) e |= FA_ERR_HDR_END;
+		if (e) atomicOr(err, e);
+		is_header[i] = hdr ? 1u : 0u;
+	}
+}
+/* one thread per line, at work on headers: hdr_idx = exclusive scan of is_header, so a header's value is its record */
+__global__ void fasta_headers(const uint8_t *text, const uint64_t *line_start, const uint32_t *line_len, const uint32_t *is_header, const uint64_t *hdr_idx, uint64_t n_lines,
+                              int store_comment, uint64_t *rec_line, uint32_t *keep, uint32_t *err) {
+	for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n_lines; i += (uint64_t)gridDim.x * blockDim.x) {
+		if (!is_header[i]) continue;
+		const uint64_t r = hdr_idx[i];
+		const IngName t = ing_trim_name(text + line_start[i] + 1, line_len[i] - 1, store_comment);
+		if (t.ws == 0) atomicOr(err, (uint32_t)ING_ERR_NAME);
+		rec_line[r] = i;
+		if (keep) keep[r] = t.ws && t.good ? 1u : 0u;
+	}
+}
+__global__ void fasta_kept_lengths(const uint32_t *line_len, const uint32_t *is_header, const uint64_t *hdr_idx, const uint32_t *keep, uint64_t n_lines, uint32_t *kept_len) {
+	for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n_lines; i += (uint64_t)gridDim.x * blockDim.x)
+		kept_len[i] = !is_header[i] && hdr_idx[i] && keep[hdr_idx[i] - 1] ? line_len[i] : 0u;
+}
+/* one thread per record: line_off = exclusive scan of kept_len (n_lines + 1 values) */
+__global__ void fasta_records(const uint64_t *line_start, const uint32_t *line_len, const uint64_t *rec_line, const uint32_t *keep, const uint64_t *kept_idx,
+                              const uint64_t *line_off, uint64_t n_records, uint64_t n_lines, uint64_t *offsets, uint64_t *name_off, uint32_t *name_len, uint32_t *err) {
+	for (uint64_t r = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; r < n_records; r += (uint64_t)gridDim.x * blockDim.x) {
+		if (!keep[r]) continue;
+		const uint64_t i = rec_line[r], j = kept_idx[r], next = r + 1 < n_records ? rec_line[r + 1] : n_lines;
+		offsets[j] = line_off[i];
+		name_off[j] = line_start[i] + 1; name_len[j] = line_len[i] - 1;
+		if (line_off[next] - line_off[i] > 0xfffffffeull) atomicOr(err, (uint32_t)FA_ERR_LONG);      /* SequenceLengthType */
+	}
+}
+
+/* the last i in [lo, hi] with off[i] <= x; off ascending and off[lo] <= x */
+__device__ __forceinline__ uint64_t fa_find(const uint64_t *off, uint64_t lo, uint64_t hi, uint64_t x) {
+	while (lo < hi) { const uint64_t mid = lo + (hi - lo + 1) / 2; if (off[mid] <= x) lo = mid; else hi = mid - 1; }
+	return lo;
+}
+/* std::toupper of four bytes ('a'-'z' only, src/ReadFileReader.h:313) */
+__device__ __forceinline__ uint32_t ing_upper4(uint32_t v) {
+	const uint32_t lo7 = v & 0x7f7f7f7fu;
+	const uint32_t lower = (lo7 + 0x1f1f1f1fu) & ~(lo7 + 0x05050505u) & ~v & 0x80808080u;      /* 0x61 <= byte <= 0x7a */
+	return v - (lower >> 2);
+}
+/* The bases.  Work is dealt out by OUTPUT bytes: a block takes 4 KB of the bases array, a thread 16 bytes, whatever records and lines
+ * they come from.  Output byte x belongs to the last line i with line_off[i] <= x (the lines before it with the same offset are
+ * headers and dropped records: length 0) and is text[line_start[i] + x - line_off[i]].  The block bisects line_off once for its
+ * first and last byte, a thread bisects between those -- no steps at all inside a long line, six in 60-column lines.  Sixteen bytes
+ * from one line are five aligned dwords and a byte funnel when the text is 4-byte aligned; a dword that lies in one line is the funnel
+ * of ing_src_dword; a dword across a line end is gathered byte by byte.  Every store is one aligned 16 bytes; the bytes behind the
+ * last base (the array's zeroed slack) are stored as zeros.  grid = ceil(total / 4096) blocks. */
+__global__ __launch_bounds__(ING_THREADS)
+void fasta_copy(const uint8_t *text, uint64_t len, const uint64_t *line_start, const uint64_t *line_off, uint64_t n_lines, uint64_t total, uint8_t *bases) {
+	const bool aligned = ((uintptr_t)text & 3) == 0;
+	const uint64_t A0 = (uint64_t)blockIdx.x * (ING_THREADS * ING_BYTES);
+	if (A0 >= total) return;
+	const uint64_t A1 = (A0 + ING_THREADS * ING_BYTES < total ? A0 + ING_THREADS * ING_BYTES : total) - 1;
+	const uint64_t blo = fa_find(line_off, 0, n_lines, A0), bhi = fa_find(line_off, blo, n_lines, A1);
+	const uint64_t a = A0 + (uint64_t)threadIdx.x * ING_BYTES;
+	if (a >= total) return;
+	const uint64_t alast = (a + ING_BYTES < total ? a + ING_BYTES : total) - 1;
+	uint64_t i = fa_find(line_off, blo, bhi, a);
+	const uint64_t i1 = fa_find(line_off, i, bhi, alast);
+	const uint64_t src = line_start[i] + (a - line_off[i]);
+	uint32_t w[4];
+	if (i == i1 && a + ING_BYTES <= total && aligned && (src & ~3ull) + 20 <= len) {
+		const uint32_t *s = (const uint32_t *)(text + (src & ~3ull));
+		const uint32_t x[5] = {s[0], s[1], s[2], s[3], s[4]}, sh = 8 * (uint32_t)(src & 3);
+#pragma unroll
+		for (int d = 0; d < 4; d++) w[d] = (uint32_t)((((uint64_t)x[d + 1] << 32) | x[d]) >> sh);
+	} else {
+#pragma unroll
+		for (int d = 0; d < 4; d++) {
+			const uint64_t pos = a + 4 * d;
+			w[d] = 0;
+			if (pos >= total) continue;
+			i = fa_find(line_off, i, i1, pos);
+			if (pos + 4 <= line_off[i + 1]) w[d] = ing_src_dword(text, len, (int64_t)(line_start[i] + (pos - line_off[i])), aligned);
+			else {
+#pragma unroll
+				for (int b = 0; b < 4; b++) {
+					if (pos + b >= total) continue;
+					const uint64_t ib = fa_find(line_off, i, i1, pos + b);
+					w[d] |= (uint32_t)text[line_start[ib] + (pos + b - line_off[ib])] << (8 * b);
+				}
+			}
+		}
+	}
+	*(uint4 *)(bases + a) = make_uint4(ing_upper4(w[0]), ing_upper4(w[1]), ing_upper4(w[2]), ing_upper4(w[3]));
+}
+
+/* The numbers of a QUAL text, per 16 text bytes as ingest_index_lines looks at them (block_base = lines begun before the block).  A
+ * number begins at a digit behind a byte that is no digit, in a line that is no header.
+ * MODE 0: the bytes allowed and the 1-3 digits; block_tokens[block] = numbers that begin in the block.
+ * MODE 1: tok_at_line[i] = numbers that begin before line i (token_base = exclusive scan of block_tokens), tok_at_line[n_lines] = all.
+ * MODE 2: number t of a line whose first number goes to output byte line_out[i] (FA_NONE: a dropped record) is stored at
+ *         line_out[i] + t as min(v, 127 - start - 1) + start; a character within [start, start + 40] marks its read, if that is one
+ *         of the first 19 999 (line_read[i], else 0xffffffff), as one validateFastqStart passes: its minimum is in range. */
+template <int MODE> __global__ __launch_bounds__(ING_THREADS)
+void fasta_qual_tokens(const uint8_t *text, uint64_t len, const uint64_t *block_base, const uint32_t *is_header, uint64_t n_lines, uint32_t *block_tokens, const uint64_t *token_base,
+                       uint64_t *tok_at_line, const uint64_t *line_out, const uint32_t *line_read, uint32_t start_char, uint8_t *quals, uint32_t *in_range, uint32_t *err) {
+	const uint64_t p0 = ((uint64_t)blockIdx.x * ING_THREADS + threadIdx.x) * ING_BYTES;
+	const bool aligned = ((uintptr_t)text & 15) == 0;
+	IngChunk c;
+	uint32_t smask = 0;
+	if (p0 < len) { c = ing_load_chunk(text, len, p0, aligned); smask = ing_start_mask(c, p0, len); }
+	uint32_t tot;
+	const uint64_t first_line = block_base[blockIdx.x] + ing_block_scan((uint32_t)__builtin_popcount(smask), &tot);      /* the first line to begin in or behind these bytes */
+	auto is_digit = [](uint8_t ch) { return ch >= '0' && ch <= '9'; };
+	auto byte_at = [&](int j) -> uint8_t { return j < ING_BYTES ? c.b[j < ING_BYTES ? j : 0] : (p0 + j < len ? text[p0 + j] : (uint8_t)'\n'); };
+	uint32_t tmask = 0, e = 0;
+	if (p0 < len) {
+		uint64_t line = first_line;
+		bool hdr = line ? is_header[line - 1] != 0 : true;      /* in front of the first line there are newlines only */
+#pragma unroll
+		for (int j = 0; j < ING_BYTES; j++) {
+			if (smask & (1u << j)) hdr = is_header[line++] != 0;
+			const uint8_t ch = c.b[j];
+			if (p0 + j >= len || ch == '\n' || hdr) continue;
+			if (!is_digit(ch)) { if (ch != ' ' && ch != '\t') e |= FA_ERR_QBYTE; continue; }
+			if (is_digit(j ? c.b[j - 1] : c.prev)) continue;
+			tmask |= 1u << j;
+			if (MODE == 0 && is_digit(byte_at(j + 1)) && is_digit(byte_at(j + 2)) && is_digit(byte_at(j + 3))) e |= FA_ERR_QDIGITS;
+		}
+	}
+	const uint32_t before = ing_block_scan((uint32_t)__builtin_popcount(tmask), &tot);
+	if (MODE == 0) {
+		if (e) atomicOr(err, e);
+		if (threadIdx.x == 0) block_tokens[blockIdx.x] = tot;
+		return;
+	}
+	if (MODE == 1 && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) tok_at_line[n_lines] = token_base[gridDim.x];
+	if (!(smask | tmask)) return;
+	const uint64_t t0 = token_base[blockIdx.x] + before;
+	uint64_t line = first_line;
+#pragma unroll
+	for (int j = 0; j < ING_BYTES; j++) {
+		const uint64_t t = t0 + (uint32_t)__builtin_popcount(tmask & ((1u << j) - 1u));
+		if (smask & (1u << j)) { if (MODE == 1) tok_at_line[line] = t; line++; }
+		if (MODE == 2 && (tmask & (1u << j))) {
+			const uint64_t o = line_out[line - 1];
+			if (o == FA_NONE) continue;
+			uint32_t v = byte_at(j) - '0';
+			if (is_digit(byte_at(j + 1))) { v = 10 * v + (byte_at(j + 1) - '0'); if (is_digit(byte_at(j + 2))) v = 10 * v + (byte_at(j + 2) - '0'); }
+			const uint32_t top = 127u - start_char - 1u, q = (v > top ? top : v) + start_char;
+			quals[o + (t - tok_at_line[line - 1])] = (uint8_t)q;
+			if (q <= start_char + 40u) { const uint32_t rd = line_read[line - 1]; if (rd != 0xffffffffu) in_range[rd] = 1u; }
+		}
+	}
+}
+/* one thread per line of the QUAL text (q_*; f_* the FASTA's): record r of the one is record r of the other.  At a header: the
+ * trimmed names are equal (readName :981-987: the QUAL header goes through trimName as well), and a kept record has as many
+ * numbers as bases (nextRead :317-319).  At a quality line: it does not end in a digit where the next begins with one; where its
+ * first number goes. */
+__global__ void fasta_qual_lines(const uint8_t *q_text, const uint64_t *q_line_start, const uint32_t *q_line_len, const uint32_t *q_is_header, const uint64_t *q_hdr_idx,
+                                 const uint64_t *q_rec_line, uint64_t q_n_lines, const uint64_t *tok_at_line,
+                                 const uint8_t *f_text, const uint64_t *f_line_start, const uint32_t *f_line_len, const uint64_t *f_rec_line,
+                                 const uint32_t *keep, const uint64_t *kept_idx, const uint64_t *offsets, uint64_t n_records, int store_comment,
+                                 uint64_t *line_out, uint32_t *line_read, uint32_t *err) {
+	for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < q_n_lines; i += (uint64_t)gridDim.x * blockDim.x) {
+		const uint64_t s = q_line_start[i];
+		uint32_t e = 0;
+		line_out[i] = FA_NONE; line_read[i] = 0xffffffffu;
+		if (q_is_header[i]) {
+			const uint64_t r = q_hdr_idx[i], fi = f_rec_line[r];
+			const uint8_t *qn = q_text + s + 1, *fn = f_text + f_line_start[fi] + 1;
+			const IngName tq = ing_trim_name(qn, q_line_len[i] - 1, store_comment), tf = ing_trim_name(fn, f_line_len[fi] - 1, store_comment);
+			bool same = tq.ws == tf.ws && tq.pair == tf.pair;
+			for (uint32_t k = 0; same && k < tq.ws; k++) same = qn[k] == fn[k];
+			if (!same) e |= FA_ERR_QNAME;
+			if (keep[r]) {
+				const uint64_t j = kept_idx[r], next = r + 1 < n_records ? q_rec_line[r + 1] : q_n_lines;
+				if (tok_at_line[next] - tok_at_line[i] != offsets[j + 1] - offsets[j]) e |= FA_ERR_QCOUNT;
+			}
+		} else {
+			const uint64_t r = q_hdr_idx[i] - 1;      /* a header went before: the text was classified */
+			const uint8_t last = q_text[s + q_line_len[i] - 1];
+			if (i + 1 < q_n_lines && !q_is_header[i + 1] && last >= '0' && last <= '9') { const uint8_t nx = q_text[q_line_start[i + 1]]; if (nx >= '0' && nx <= '9') e |= FA_ERR_QGLUE; }
+			if (keep[r]) {
+				const uint64_t j = kept_idx[r];
+				line_out[i] = offsets[j] + (tok_at_line[i] - tok_at_line[q_rec_line[r]]);
+				if (j + 1 < ING_VALIDATE_READS) line_read[i] = (uint32_t)j;
+			}
+		}
+		if (e) atomicOr(err, e);
+	}
+}
+/* validateFastqStart (src/ReadSet.h:171-191, src/Sequence.h:456-479: both bounds on the minimum) over the first 19 999 kept reads:
+ * a character is never below start (it is start + a number) nor Read::REF_QUAL (the clamp), so a read fails exactly when its minimum
+ * is above start + 40: when none of its characters marked it */
+__global__ void fasta_qual_flip(const uint32_t *in_range, uint64_t n, uint32_t *flip) {
+	for (uint64_t j = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; j < n; j += (uint64_t)gridDim.x * blockDim.x) if (!in_range[j]) atomicOr(flip, 1u);
 }
 
 /* ---- 2-bit pack of a read batch: TwoBitSequence::compressSequence (src/TwoBitSequence.cpp:242-269, compressBase :114-147) ----

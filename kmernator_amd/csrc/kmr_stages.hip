@@ -134,7 +134,7 @@ static int ingest_dev(kmr_handle *h, const uint8_t *text, uint64_t len, uint32_t
 	if (nrec) {
 		HIPCHK(h, lstart.alloc(8 * n_lines)); HIPCHK(h, llen.alloc(4 * n_lines));
 		hipLaunchKernelGGL(ingest_index_lines, dim3((unsigned)nblk), dim3(ING_THREADS), 0, h->stream, text, len, bbase.get<uint64_t>(), lstart.get<uint64_t>());
-		hipLaunchKernelGGL(ingest_line_lengths, dim3(grid_for(n_lines)), dim3(256), 0, h->stream, text, len, lstart.get<uint64_t>(), n_lines, llen.get<uint32_t>(), derr.get<uint32_t>());
+		hipLaunchKernelGGL(ingest_line_lengths, dim3(grid_for(n_lines)), dim3(256), 0, h->stream, text, len, lstart.get<uint64_t>(), n_lines, llen.get<uint32_t>(), derr.get<uint32_t>(), false);
 		HIPCHK(h, keep.alloc(4 * nrec)); HIPCHK(h, klen.alloc(4 * nrec));
 		HIPCHK(h, kidx.alloc(8 * (nrec + 1))); HIPCHK(h, boff.alloc(8 * (nrec + 1)));
 		hipLaunchKernelGGL(ingest_records, dim3(grid_for(nrec)), dim3(256), 0, h->stream, text, lstart.get<uint64_t>(), llen.get<uint32_t>(), nrec, store_comment, keep.get<uint32_t>(), klen.get<uint32_t>(), derr.get<uint32_t>());
@@ -193,6 +193,197 @@ int kmr_ingest_fastq(kmr_handle *h, const char *text, uint64_t len, uint32_t inp
 	if (e != hipSuccess) { h->err = std::string("hipMemcpy(FASTQ text): ") + hipGetErrorString(e); return KMR_ERR_HIP; }
 	return ingest_dev(h, d.get<uint8_t>(), len, input_quality_base, store_comment, out);
 }
+/* ---- FASTA and FASTA+QUAL ingest on the device (kmr_ingest.hpp) ------------- */
+}  // extern "C"
+
+namespace {
+
+/* several arrays out of one grow-only block of the handle (kmr_handle::fasta_buf, as score_buf serves the scoring calls: a device
+ * allocation of more than 2 MB costs the host more than all kernels of a 16 MiB call together): take() every array, then reserve() */
+struct Piece { uint8_t *p = nullptr; template <class T> T *get() const { return (T *)p; } };
+struct Pieces {
+	std::vector<std::pair<Piece *, size_t>> taken; size_t total = 0;
+	void take(Piece &x, size_t bytes) { taken.emplace_back(&x, total); total += (bytes + 255) & ~(size_t)255; }
+	int reserve(kmr_handle *h, DevBuf &buf) {
+		const int rc = buf.reserve(h, "FASTA ingest scratch", std::max<size_t>(total, 256));
+		if (!rc) for (auto &t : taken) t.first->p = buf.get<uint8_t>() + t.second;
+		return rc;
+	}
+};
+
+/* the lines and records of a FASTA or QUAL text, in three blocks (per 4 KB block, per line, per record): starts and lengths of the
+ * non-empty lines, header flags and their exclusive scan (a header's value = its record), the header line of every record.  FASTA
+ * only: keep[r] = the Casava filter passes it, kidx its scan; klen = a line's length in the output, loff its scan.  QUAL only: numbers
+ * per block and their scan, the running count at a line start, where a line's first number goes and to which read */
+struct FastaIndex {
+	Pieces per_block, per_line, per_record;
+	Piece blk, bbase, lstart, llen, ishdr, hidx, recline, keep, kidx, klen, loff, btok, tbase, tline, lout, lread;
+	uint64_t nblk = 0, n_lines = 0, nrec = 0;
+};
+
+std::string fasta_why(uint32_t e) {
+	std::string why;
+	if (e & FA_ERR_LEAD) why += " text or an empty line before the first header;";
+	if (e & FA_ERR_HDR_HDR) why += " a header followed by a header;";
+	if (e & FA_ERR_HDR_END) why += " a header at the end of the text;";
+	if (e & FA_ERR_BLANK) why += " an empty line before or between the lines of a record;";
+	if (e & ING_ERR_NAME) why += " an empty name;";
+	if (e & FA_ERR_QBYTE) why += " a byte that is no digit, blank or tab in a quality line;";
+	if (e & FA_ERR_QDIGITS) why += " a quality of more than 3 digits;";
+	if (e & FA_ERR_QGLUE) why += " a quality line ends in a digit and the next one starts with a digit;";
+	if (e & FA_ERR_QNAME) why += " fasta and quals have different names;";
+	if (e & FA_ERR_QCOUNT) why += " number of bases and quals not equal;";
+	return why;
+}
+
+/* what the error word at derr holds after the work queued so far: 0, or the call's return code with its message */
+int fasta_check(kmr_handle *h, const uint32_t *derr, const char *what) {
+	uint32_t e = 0;
+	HIPCHK(h, hipMemcpyAsync(&e, derr, 4, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
+	if (e & (FA_ERR_LONG | ING_ERR_LEN)) return fail(h, KMR_ERR_UNSUPPORTED, std::string(what) + ": a line or record of more than 2^32 - 2 bytes (SequenceLengthType)");
+	if (e) return fail(h, KMR_ERR_INVALID_ARG, std::string("malformed ") + what + ":" + fasta_why(e));
+	return 0;
+}
+
+int fasta_index(kmr_handle *h, const uint8_t *text, uint64_t len, int store_comment, bool is_fasta, uint32_t *derr, const char *what, FastaIndex &X) {
+	DevBuf *const bufs = h->fasta_buf[is_fasta ? 0 : 1];
+	X.nblk = (len + (uint64_t)ING_THREADS * ING_BYTES - 1) / ((uint64_t)ING_THREADS * ING_BYTES);
+	if (!X.nblk) return 0;
+	if (X.nblk > 0x7fffffffull) return fail(h, KMR_ERR_INVALID_ARG, std::string(what) + " text too large for one call");
+	X.per_block.take(X.blk, 4 * X.nblk); X.per_block.take(X.bbase, 8 * (X.nblk + 1));
+	if (!is_fasta) { X.per_block.take(X.btok, 4 * X.nblk); X.per_block.take(X.tbase, 8 * (X.nblk + 1)); }
+	{ int rc = X.per_block.reserve(h, bufs[0]); if (rc) return rc; }
+	hipLaunchKernelGGL(ingest_count_lines, dim3((unsigned)X.nblk), dim3(ING_THREADS), 0, h->stream, text, len, X.blk.get<uint32_t>());
+	HIPCHK(h, hipGetLastError());
+	{ int rc = exclusive_scan(h, X.blk.get<uint32_t>(), X.nblk, X.bbase.get<uint64_t>()); if (rc) return rc; }
+	HIPCHK(h, hipMemcpy(&X.n_lines, X.bbase.get<uint64_t>() + X.nblk, 8, hipMemcpyDeviceToHost));
+	if (!X.n_lines) return fail(h, KMR_ERR_INVALID_ARG, std::string("malformed ") + what + ":" + fasta_why(FA_ERR_LEAD));      /* newlines only */
+	const uint64_t nl = X.n_lines;
+	X.per_line.take(X.lstart, 8 * nl); X.per_line.take(X.llen, 4 * nl); X.per_line.take(X.ishdr, 4 * nl); X.per_line.take(X.hidx, 8 * (nl + 1));
+	if (is_fasta) { X.per_line.take(X.klen, 4 * nl); X.per_line.take(X.loff, 8 * (nl + 1)); }
+	else { X.per_line.take(X.tline, 8 * (nl + 1)); X.per_line.take(X.lout, 8 * nl); X.per_line.take(X.lread, 4 * nl); }
+	{ int rc = X.per_line.reserve(h, bufs[1]); if (rc) return rc; }
+	hipLaunchKernelGGL(ingest_index_lines, dim3((unsigned)X.nblk), dim3(ING_THREADS), 0, h->stream, text, len, X.bbase.get<uint64_t>(), X.lstart.get<uint64_t>());
+	hipLaunchKernelGGL(ingest_line_lengths, dim3(grid_for(nl)), dim3(256), 0, h->stream, text, len, X.lstart.get<uint64_t>(), nl, X.llen.get<uint32_t>(), derr, true);
+	hipLaunchKernelGGL(fasta_classify, dim3(grid_for(nl)), dim3(256), 0, h->stream, text, X.lstart.get<uint64_t>(), X.llen.get<uint32_t>(), nl, X.ishdr.get<uint32_t>(), derr);
+	HIPCHK(h, hipGetLastError());
+	{ int rc = exclusive_scan(h, X.ishdr.get<uint32_t>(), nl, X.hidx.get<uint64_t>()); if (rc) return rc; }
+	{ int rc = fasta_check(h, derr, what); if (rc) return rc; }
+	HIPCHK(h, hipMemcpy(&X.nrec, X.hidx.get<uint64_t>() + nl, 8, hipMemcpyDeviceToHost));
+	X.per_record.take(X.recline, 8 * X.nrec);
+	if (is_fasta) { X.per_record.take(X.keep, 4 * X.nrec); X.per_record.take(X.kidx, 8 * (X.nrec + 1)); }
+	{ int rc = X.per_record.reserve(h, bufs[2]); if (rc) return rc; }
+	hipLaunchKernelGGL(fasta_headers, dim3(grid_for(nl)), dim3(256), 0, h->stream, text, X.lstart.get<uint64_t>(), X.llen.get<uint32_t>(), X.ishdr.get<uint32_t>(), X.hidx.get<uint64_t>(), nl,
+	                   store_comment, X.recline.get<uint64_t>(), X.keep.get<uint32_t>(), derr);
+	HIPCHK(h, hipGetLastError());
+	return 0;
+}
+
+int ingest_fasta_dev(kmr_handle *h, const uint8_t *text, uint64_t len, const uint8_t *qtext, uint64_t qlen, bool with_qual, int store_comment, kmr_reads **out) {
+	const uint32_t start = h->cfg.fastq_start_char;
+	if (start != 33 && start != 64) return fail(h, KMR_ERR_INVALID_ARG, "fastq quality base must be 33 or 64 (src/Options.h:490)");
+	auto R = make_result<kmr_reads>(h);
+	R->input_base = start;
+	FastaIndex F, Q;
+	DevBuf derr;
+	HIPCHK(h, derr.alloc(16)); HIPCHK(h, hipMemsetAsync(derr.get<uint32_t>(), 0, 16, h->stream));
+	uint32_t *ferr = derr.get<uint32_t>(), *qerr = ferr + 1, *flip = ferr + 2;
+	{ int rc = fasta_index(h, text, len, store_comment, true, ferr, "FASTA", F); if (rc) return rc; }
+	if (with_qual) {
+		int rc = fasta_index(h, qtext, qlen, store_comment, false, qerr, "QUAL", Q); if (rc) return rc;
+		if (Q.nrec != F.nrec) return fail(h, KMR_ERR_INVALID_ARG, "malformed QUAL: " + std::to_string(Q.nrec) + " records for the " + std::to_string(F.nrec) + " of the FASTA");
+	}
+	const uint64_t nl = F.n_lines, nrec = F.nrec;
+	uint64_t n_kept = 0, total = 0;
+	if (nrec) {
+		hipLaunchKernelGGL(fasta_kept_lengths, dim3(grid_for(nl)), dim3(256), 0, h->stream, F.llen.get<uint32_t>(), F.ishdr.get<uint32_t>(), F.hidx.get<uint64_t>(), F.keep.get<uint32_t>(), nl, F.klen.get<uint32_t>());
+		HIPCHK(h, hipGetLastError());
+		{ int rc = exclusive_scan(h, F.keep.get<uint32_t>(), nrec, F.kidx.get<uint64_t>()); if (rc) return rc; }
+		{ int rc = exclusive_scan(h, F.klen.get<uint32_t>(), nl, F.loff.get<uint64_t>()); if (rc) return rc; }
+		{ int rc = fasta_check(h, ferr, "FASTA"); if (rc) return rc; }      /* the names */
+		HIPCHK(h, hipMemcpy(&n_kept, F.kidx.get<uint64_t>() + nrec, 8, hipMemcpyDeviceToHost)); HIPCHK(h, hipMemcpy(&total, F.loff.get<uint64_t>() + nl, 8, hipMemcpyDeviceToHost));
+	}
+	R->n = n_kept; R->total = total; R->filtered = nrec - n_kept;
+	HIPCHK(h, R->bases.alloc(total + 64)); HIPCHK(h, R->quals.alloc(total + 64)); HIPCHK(h, R->offsets.alloc(8 * (n_kept + 1)));
+	HIPCHK(h, R->name_off.alloc(8 * std::max<uint64_t>(1, n_kept))); HIPCHK(h, R->name_len.alloc(4 * std::max<uint64_t>(1, n_kept)));
+	HIPCHK(h, hipMemsetAsync(R->bases.get<uint8_t>() + total, 0, 64, h->stream)); HIPCHK(h, hipMemsetAsync(R->quals.get<uint8_t>() + total, 0, 64, h->stream));
+	HIPCHK(h, hipMemcpyAsync(R->offsets.get<uint64_t>() + n_kept, &total, 8, hipMemcpyHostToDevice, h->stream));
+	if (nrec) {
+		hipLaunchKernelGGL(fasta_records, dim3(grid_for(nrec)), dim3(256), 0, h->stream, F.lstart.get<uint64_t>(), F.llen.get<uint32_t>(), F.recline.get<uint64_t>(), F.keep.get<uint32_t>(), F.kidx.get<uint64_t>(),
+		                   F.loff.get<uint64_t>(), nrec, nl, R->offsets.get<uint64_t>(), R->name_off.get<uint64_t>(), R->name_len.get<uint32_t>(), ferr);
+		HIPCHK(h, hipGetLastError());
+	}
+	if (total) {
+		const uint64_t nb = (total + (uint64_t)ING_THREADS * ING_BYTES - 1) / ((uint64_t)ING_THREADS * ING_BYTES);
+		if (nb > 0x7fffffffull) return fail(h, KMR_ERR_INVALID_ARG, "FASTA text too large for one call");
+		hipLaunchKernelGGL(fasta_copy, dim3((unsigned)nb), dim3(ING_THREADS), 0, h->stream, text, len, F.lstart.get<uint64_t>(), F.loff.get<uint64_t>(), nl, total, R->bases.get<uint8_t>());
+		HIPCHK(h, hipGetLastError());
+	}
+	if (!with_qual) {
+		if (total) HIPCHK(h, hipMemsetAsync(R->quals.get<uint8_t>(), 127, total, h->stream));      /* Read::REF_QUAL, src/ReadFileReader.h:892,901 */
+	} else if (nrec) {
+		const uint64_t ql = Q.n_lines, n_window = std::min<uint64_t>(n_kept, ING_VALIDATE_READS - 1);
+		DevBuf inrange;
+		HIPCHK(h, inrange.alloc(4 * std::max<uint64_t>(1, n_window))); HIPCHK(h, hipMemsetAsync(inrange.get<uint32_t>(), 0, 4 * std::max<uint64_t>(1, n_window), h->stream));
+		auto tokens = [&](auto mode) {
+			hipLaunchKernelGGL(fasta_qual_tokens<decltype(mode)::value>, dim3((unsigned)Q.nblk), dim3(ING_THREADS), 0, h->stream, qtext, qlen, Q.bbase.get<uint64_t>(), Q.ishdr.get<uint32_t>(), ql,
+			                   Q.btok.get<uint32_t>(), Q.tbase.get<uint64_t>(), Q.tline.get<uint64_t>(), Q.lout.get<uint64_t>(), Q.lread.get<uint32_t>(), start, R->quals.get<uint8_t>(), inrange.get<uint32_t>(), qerr);
+		};
+		tokens(int_c<0>());
+		HIPCHK(h, hipGetLastError());
+		{ int rc = exclusive_scan(h, Q.btok.get<uint32_t>(), Q.nblk, Q.tbase.get<uint64_t>()); if (rc) return rc; }
+		tokens(int_c<1>());
+		hipLaunchKernelGGL(fasta_qual_lines, dim3(grid_for(ql)), dim3(256), 0, h->stream, qtext, Q.lstart.get<uint64_t>(), Q.llen.get<uint32_t>(), Q.ishdr.get<uint32_t>(), Q.hidx.get<uint64_t>(), Q.recline.get<uint64_t>(), ql,
+		                   Q.tline.get<uint64_t>(), text, F.lstart.get<uint64_t>(), F.llen.get<uint32_t>(), F.recline.get<uint64_t>(), F.keep.get<uint32_t>(), F.kidx.get<uint64_t>(), R->offsets.get<uint64_t>(), nrec,
+		                   store_comment, Q.lout.get<uint64_t>(), Q.lread.get<uint32_t>(), qerr);
+		HIPCHK(h, hipGetLastError());
+		/* every kept record has as many numbers as bases before a single one is written */
+		{ int rc = fasta_check(h, qerr, "QUAL"); if (rc) return rc; }
+		tokens(int_c<2>());
+		if (n_window) hipLaunchKernelGGL(fasta_qual_flip, dim3(grid_for(n_window)), dim3(256), 0, h->stream, inrange.get<uint32_t>(), n_window, flip);
+		HIPCHK(h, hipGetLastError());
+		uint32_t f = 0;
+		HIPCHK(h, hipMemcpyAsync(&f, flip, 4, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
+		if (f) {      /* __setFastqStart(the other base), src/ReadSet.h:174-186, with the input base equal to the start character */
+			const uint32_t want = start == 33 ? 64u : 33u;
+			if (total) hipLaunchKernelGGL(ingest_shift_quals, dim3(grid_for(total)), dim3(256), 0, h->stream, R->quals.get<uint8_t>(), total, (int)start - (int)want);
+			HIPCHK(h, hipGetLastError());
+			R->input_base = want;
+		}
+	}
+	{ int rc = fasta_check(h, ferr, "FASTA"); if (rc) return rc; }      /* a record too long; waits for the stream */
+	*out = R.release();
+	return KMR_OK;
+}
+
+/* the text as the kernels like it: a fresh aligned copy with slack behind it */
+int fasta_upload(kmr_handle *h, const char *text, uint64_t len, const char *what, DevBuf &d) {
+	HIPCHK(h, d.alloc(len + 16));
+	const hipError_t e = len ? hipMemcpy(d.get(), text, len, hipMemcpyHostToDevice) : hipSuccess;
+	if (e != hipSuccess) { h->err = std::string("hipMemcpy(") + what + " text): " + hipGetErrorString(e); return KMR_ERR_HIP; }
+	return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kmr_ingest_fasta_dev(kmr_handle *h, const void *dev_text, uint64_t len, const void *dev_qual_text, uint64_t qual_len, int store_comment, kmr_reads **out) {
+	if (out) *out = nullptr;
+	if (!h || !out || (len && !dev_text) || (qual_len && !dev_qual_text)) return KMR_ERR_INVALID_ARG;
+	hipSetDevice(h->device);
+	return ingest_fasta_dev(h, (const uint8_t *)dev_text, len, (const uint8_t *)dev_qual_text, qual_len, dev_qual_text != nullptr, store_comment, out);
+}
+int kmr_ingest_fasta(kmr_handle *h, const char *text, uint64_t len, const char *qual_text, uint64_t qual_len, int store_comment, kmr_reads **out) {
+	if (out) *out = nullptr;
+	if (!h || !out || (len && !text) || (qual_len && !qual_text)) return KMR_ERR_INVALID_ARG;
+	hipSetDevice(h->device);
+	DevBuf d, q;
+	{ int rc = fasta_upload(h, text, len, "FASTA", d); if (rc) return rc; }
+	if (qual_text) { int rc = fasta_upload(h, qual_text, qual_len, "QUAL", q); if (rc) return rc; }
+	return ingest_fasta_dev(h, d.get<uint8_t>(), len, q.get<uint8_t>(), qual_len, qual_text != nullptr, store_comment, out);
+}
+
 /* a device-resident batch from reads the host already parsed (the reference's ReadSet flattened as for kmr_add_reads) */
 int kmr_reads_from_host(kmr_handle *h, const char *bases, const char *quals, const uint64_t *offsets, uint64_t n_reads, kmr_reads **out) {
 	if (!h || !out || !offsets || (n_reads && (!bases || !quals))) return KMR_ERR_INVALID_ARG;

@@ -630,6 +630,19 @@ class ReadSet(_DeviceObject):
         return self
 
     @classmethod
+    def from_fasta(cls, spectrum, text, qual_text=None, store_comment=True):
+        """reads parsed on the device from FASTA text (every quality Read::REF_QUAL) or, with `qual_text`, from a FASTA + QUAL pair
+        (FastaStreamParser / FastaQualStreamParser, src/ReadFileReader.h:844-1006): kmr_ingest_fasta.  A record may have any number
+        of lines and any length; names point into `text`, which the set keeps."""
+        text = bytes(text)
+        buf = np.frombuffer(text, dtype=np.uint8)
+        qbuf = None if qual_text is None else np.frombuffer(bytes(qual_text) + b"\n", dtype=np.uint8)      # never empty: NULL means no qual text
+        r = C.c_void_p()
+        spectrum._call("ingest_fasta", spectrum.h, buf.ctypes.data_as(C.c_void_p) if buf.size else None, buf.size,
+                       None if qbuf is None else qbuf.ctypes.data_as(C.c_void_p), 0 if qbuf is None else qbuf.size - 1, 1 if store_comment else 0, C.byref(r))
+        return cls._adopt(spectrum, text, r, store_comment)
+
+    @classmethod
     def from_arrays(cls, spectrum, bases, quals, offsets):
         """reads the host already holds (uint8 bases / quals scaled to the spectrum's quality base, uint64 offsets[n+1])"""
         bases = np.ascontiguousarray(bases, dtype=np.uint8)
