@@ -668,8 +668,8 @@ int kmr_artifact_filter_apply(kmr_handle *h, const kmr_artifact_filter *f, const
                               uint32_t *remnant_off, uint32_t *remnant_len, kmr_reads **out);
 
 /* ---- selectReads / writePicks: pick the passing reads and write FilterReads' output on the device ----------
- * selectReads (apps/FilterReads.h:159-279) with --max-kmer-output-depth off; its plain branch first (one threshold, one
- * output), --partition-by-depth, --remainder-trim and the per-input-file outputs behind it (kmr_partition_*):
+ * selectReads (apps/FilterReads.h:159-279): its plain branch first (one threshold, one output), --partition-by-depth,
+ * --remainder-trim and the per-input-file outputs behind it (kmr_partition_*), --max-kmer-output-depth last (kmr_normalize_*):
  * ReadSelector::pickAllPassingReads / pickAllPassingPairs (src/ReadSelector.h:547-596) and writePicks (:1242-1262).
  * Per read i of a device-resident batch -- the reads as the artifact filter left them (kmr_artifact_filter_apply's *out)
  * or an unfiltered batch -- and its results of the earlier stages:
@@ -692,8 +692,7 @@ int kmr_artifact_filter_apply(kmr_handle *h, const kmr_artifact_filter *f, const
  *               is 1, "Trim:<offset>+<length>" if was_trimmed[i], "<Label>:<(int)(score + 0.5)>" with Label = Score /
  *               MedianScore / MinScore / MaxScore / AvgScore (getKmerScoringTypeLabel, :248-257, in kmr_scoring's order).
  *               A discarded read was never scored (:1195-1197) and has no label
- * Not covered: stored comments are not printed and a Casava "name 1:Y" is not rewritten to "name/1";
- * --max-kmer-output-depth (RANDOM draws from the reference's IntRand, OPTIMAL is a serial greedy heap), the unmasked formats
+ * Not covered: stored comments are not printed and a Casava "name 1:Y" is not rewritten to "name/1"; the unmasked formats
  * and bimodal trimming.  Markup characters other than N, X and '.' are outside the parity claim: the reference applies a read's
  * markup positions to the already trimmed string (src/Sequence.cpp:322-325, src/TwoBitSequence.cpp:317-327), so such a
  * character lands on the wrong base when the trim offset is not 0, while the device prints the batch's own characters where
@@ -773,7 +772,7 @@ void kmr_picks_free(kmr_picks *p);
  * Bounds: at most 33 rounds (32 halvings of a 32-bit depth and the remainder; minimum_score 0 under a depth of 2^31 or more
  * would need 34: KMR_ERR_UNSUPPORTED); rounds x inputs <= 256 segments (KMR_ERR_UNSUPPORTED beyond): the counting pass keeps 12
  * bytes of LDS per segment and wavefront, 3 KiB at 256, which lets 32 wavefronts share a CU's 160 KiB.
- * Not covered: --kmer-size 0 (the tmpMinDepth = 0 special case, :224-227), --max-kmer-output-depth, bimodal trimming.
+ * Not covered: --kmer-size 0 (the tmpMinDepth = 0 special case, :224-227), bimodal trimming.
  * KMR_ERR_INVALID_ARG: a wrong struct_size; input_starts that does not start at 0, descends or does not end at n_reads. */
 typedef struct kmr_partition_config {
 	uint32_t struct_size;            /* = sizeof(kmr_partition_config), ABI guard                                           */
@@ -807,6 +806,75 @@ int kmr_picks_segments_info(const kmr_picks *p, uint32_t *n_rounds, uint32_t *n_
  * round-major) its first pick, picks, first byte and bytes; per read of the batch its segment, -1 = not picked */
 int kmr_picks_segments_copy(const kmr_picks *p, float *round_depth, uint8_t *round_is_remainder, uint64_t *seg_first_pick,
                             uint64_t *seg_picks, uint64_t *seg_first_byte, uint64_t *seg_bytes, int32_t *read_segment);
+
+/* ---- selectReads, the normalizing branch (apps/FilterReads.h:178-206): --max-kmer-output-depth, "targeted read normalization
+ * depth", with --normalization-method RANDOM: ReadSelector::pickCoverageNormalizedSubset and chooseRead
+ * (src/ReadSelector.h:661-749).  Reads of high coverage are thinned so that a k-mer is written about target_depth times.
+ * passing, record, name and label are those above at (minimum_score, min_read_length); what is new, with T = target_depth:
+ *   score       s(i) = passing(i) ? (long) score[i] : -1 (:685-686); the cast truncates, 0.7 becomes 0 (beyond the range of a
+ *               long, where the reference's cast is undefined, it saturates).  A missing side of a half pair has s = -1
+ *   choose      chooseRead (:661-672) of a score s > 0: true if s <= T, else (draw(g) % s) <= T -- inclusive, so T + 1 of s
+ *               residues keep the read
+ *   draw        the reference draws from one mt19937 per OpenMP thread seeded with time(NULL): no two of its runs agree.  The
+ *               rule is kept and the stream replaced: draw(g) = word 0 of Philox4x32-10 with the counter (g & 0xffffffff,
+ *               g >> 32, 0, 0) and the key (seed & 0xffffffff, seed >> 32), g = first_global_read_idx + read index.  A result
+ *               depends on (seed, g) alone: not on scheduling, not on how a job is cut into batches or ranks
+ *   pairs       the pair list (read1, read2, n_pairs) as kmr_pairs_copy returns it, -1 = no read on that side; NULL = every
+ *               read is a half pair; a read no pair names is a half pair (read, -1) of its own
+ *   by_pair 1   (the reference passes reads.hasPairs()) per pair: skipped unless isPassingPair (:558-568: both reads must pass
+ *               if both exist and both_pass is set, else either); skipped under both_pass if s1 <= 0 or s2 <= 0 (:697-702);
+ *               skipped if s1 <= 0 and s2 <= 0; else choose(max(s1, s2), g of the pair's lower read index).  A chosen pair is
+ *               one pick that holds every read of the pair, also a mate that failed or was discarded (it prints as N)
+ *   by_pair 0   read1 is kept if s1 > 0 and choose(s1, g(read1)), read2 likewise; if either is kept they form one pick (:716-733)
+ *   order       optimizePickOrder (:1212-1221) sorts picks by the lower read index of the pair (Pair::operator<,
+ *               src/ReadSet.h:118-123); a pick is written read1 then read2 (:1245-1250), and read1 may be the higher index
+ *               (phase 2 of kmr_identify_pairs).  The output therefore interleaves mates whatever their indices
+ *   files       one round at depth minimum_score and n_inputs segments; every record goes to the file of its own read's input
+ *               (:1252-1262), so the mates of an R1 file and an R2 file part again.  The reference names the files
+ *               output + "-MinDepth<d>" + "-MaxDepth<T>" + "-" + prefix + suffix (apps/FilterReads.h:173,180)
+ * Two things the reference does and this keeps: under both_pass the s <= 0 test drops EVERY half pair, although isPassingPair
+ * and pickAllPassingPairs let a passing half pair through; and a passing read whose score truncates to 0 is never chosen.
+ * Refused with KMR_ERR_UNSUPPORTED: method != 0 -- OPTIMAL is a serial greedy heap over a shared count map (:751-922) --
+ * and use_logscale (--use-logscale-above-max): its log((float) score / (float) targetDepth) binds to the float or the double
+ * overload depending on the include order and is rounded under the reference's -ffast-math, so nothing pins its value.
+ * Not covered: --max-kmer-output-depth together with --partition-by-depth (the reference refuses it, src/ReadSelector.h:137).
+ * KMR_ERR_INVALID_ARG: target_depth 0, a wrong struct_size, read1 without read2, a pair index outside [-1, n_reads), a pair
+ * without a read, a read that two pairs name, input_starts as above.  n_picked of kmr_picks_info counts records.  An empty
+ * batch and zero picks are valid.  The number of launches does not depend on the batch, nothing per read comes back to the
+ * host, and the call waits once for the totals. */
+typedef struct kmr_normalize_config {
+	uint32_t struct_size;            /* = sizeof(kmr_normalize_config), ABI guard                                          */
+	kmr_select_config select;        /* minimum_score = --min-depth, min_read_length, both_pass, format, ...               */
+	uint64_t target_depth;           /* --max-kmer-output-depth, > 0                                                       */
+	uint64_t seed;                   /* key of the draws                                                                   */
+	uint64_t first_global_read_idx;  /* global index of the batch's first read: a job cut into batches draws as one        */
+	uint32_t by_pair;                /* decide per pair (ReadSet::hasPairs of the job) or per read                         */
+	uint32_t method;                 /* 0 = RANDOM; anything else KMR_ERR_UNSUPPORTED                                      */
+	uint32_t use_logscale;           /* --use-logscale-above-max: KMR_ERR_UNSUPPORTED if set                               */
+} kmr_normalize_config;
+int kmr_normalize_config_init(kmr_normalize_config *cfg);      /* the select defaults, RANDOM, seed 0; target_depth is the caller's */
+/* as kmr_partition_reads / _reads_dev / _read_batch / _read_batch_dev with the pair list in place of mate */
+int kmr_normalize_reads(kmr_handle *h, const kmr_reads *reads, const char *text, uint64_t text_len, const int64_t *read1,
+                        const int64_t *read2, uint64_t n_pairs, const uint8_t *af_action, const uint32_t *af_min_pass,
+                        const uint32_t *af_max_pass, const uint32_t *trim_offset, const uint32_t *trim_length, const float *score,
+                        const uint8_t *was_trimmed, const uint64_t *input_starts, uint32_t n_inputs, const kmr_normalize_config *cfg,
+                        kmr_picks **out);
+int kmr_normalize_reads_dev(kmr_handle *h, const kmr_reads *reads, const void *dev_text, uint64_t text_len, const int64_t *read1,
+                            const int64_t *read2, uint64_t n_pairs, const uint8_t *af_action, const uint32_t *af_min_pass,
+                            const uint32_t *af_max_pass, const uint32_t *trim_offset, const uint32_t *trim_length, const float *score,
+                            const uint8_t *was_trimmed, const uint64_t *input_starts, uint32_t n_inputs,
+                            const kmr_normalize_config *cfg, kmr_picks **out);
+int kmr_normalize_read_batch(kmr_handle *h, const kmr_reads *reads, const char *text, uint64_t text_len, const int64_t *read1,
+                             const int64_t *read2, uint64_t n_pairs, const uint8_t *af_action, const uint32_t *af_min_pass,
+                             const uint32_t *af_max_pass, const uint64_t *input_starts, uint32_t n_inputs,
+                             const kmr_normalize_config *cfg, kmr_picks **out);
+int kmr_normalize_read_batch_dev(kmr_handle *h, const kmr_reads *reads, const void *dev_text, uint64_t text_len, const int64_t *read1,
+                                 const int64_t *read2, uint64_t n_pairs, const uint8_t *af_action, const uint32_t *af_min_pass,
+                                 const uint32_t *af_max_pass, const uint64_t *input_starts, uint32_t n_inputs,
+                                 const kmr_normalize_config *cfg, kmr_picks **out);
+/* of picks the four above made (KMR_ERR_INVALID_ARG for others), any may be NULL: the picks as the reference counts them (pairs,
+ * the return value of pickCoverageNormalizedSubset), the chooseRead calls, and those among them that drew (s > T) */
+int kmr_normalize_info(const kmr_picks *p, uint64_t *n_picks, uint64_t *n_candidates, uint64_t *n_draws);
 
 /* ---- ReadSet::identifyPairs: which reads of a batch are the two ends of one fragment, on the device ----------
  * One call equals one ReadSet::identifyPairs() (src/ReadSet.cpp:446-570) on a fresh ReadSet that holds the batch's reads in
@@ -950,8 +1018,8 @@ void *kmr_stream(kmr_handle *h);
  *   "early_entry_share" (>= 0: kmr_count_lists_prefix's entry buffers hold that share of the good k-mers + 16 384 entries; < 0 = from the
  *   list share, the default), "saturated_batch_bytes" (scratch budget of one batch of kmr_finalize's ordered pass over k-mers seen 256
  *   times or more, 0 = 1 GiB; a key whose sightings alone exceed it is a batch of its own).
- *   "select_timing" (1: kmr_select_reads* / kmr_filter_read_batch* / kmr_partition_* time their phases with HIP events, see kmr_build_info; default 0).
- *   "partition_units" (most wavefronts, each over a contiguous range of reads, that kmr_partition_* deals the batch to, 1 - 8192; 0 = the
+ *   "select_timing" (1: kmr_select_reads* / kmr_filter_read_batch* / kmr_partition_* / kmr_normalize_* time their phases with HIP events, see kmr_build_info; default 0).
+ *   "partition_units" (most wavefronts, each over a contiguous range of reads, that kmr_partition_* deals the batch to (kmr_normalize_*: its 2 n slots), 1 - 8192; 0 = the
  *   default, 8192 for up to 32 segments; tests set a few so that one wavefront walks many tiles of 64 reads; may be set at any time).
  *   "dump_timing" (1: kmr_dump_text_size / kmr_dump_text time their size pass and writer with HIP events, see kmr_build_info; default 0),
  *   "dump_piece_bytes" (staging bound of one piece of kmr_dump_mercount / kmr_dump_mergraph's file, 0 = KMR_DUMP_PIECE_BYTES; may be set at any time).

@@ -264,7 +264,8 @@ private:
 };
 
 /* ReadSelector (src/ReadSelector.h) over a device-resident ReadSet: pickAllPassingReads / pickAllPassingPairs (:576-596) and writePicks
- * (:1242-1262), selection and output text made on the device (kmr_select_reads, kmr_filter_read_batch).  mate = paired read or -1 per
+ * (:1242-1262), pickCoverageNormalizedSubset (:673-749), selection and output text made on the device (kmr_select_reads,
+ * kmr_filter_read_batch, kmr_partition_*, kmr_normalize_*).  mate = paired read or -1 per
  * read of the batch `reads` was filtered from (nullptr: all single); af = the artifact filter's results for that batch.  Both are copied
  * and extended over the remnants the filter appended to `reads` (single, untouched reads), so the arrays handed on always have
  * reads.getSize() entries */
@@ -338,6 +339,43 @@ public:
 		}
 		return files;
 	}
+	/* The pair list coverage normalization decides over, as kmr_pairs_copy returns it (-1 = no read on that side); without one every
+	 * read is a half pair, as is a read no pair names */
+	void setPairs(const int64_t *read1, const int64_t *read2, uint64_t nPairs) { _read1.assign(read1, read1 + nPairs); _read2.assign(read2, read2 + nPairs); }
+	static kmr_normalize_config normalizeDefaults() { kmr_normalize_config c; kmr_normalize_config_init(&c); return c; }
+	struct NormalizeInfo { uint64_t picks = 0, candidates = 0, draws = 0; };
+	/* selectReads with --max-kmer-output-depth = cfg.target_depth (apps/FilterReads.h:178-206; pickCoverageNormalizedSubset, RANDOM,
+	 * the draws Philox4x32-10 of (cfg.seed, cfg.first_global_read_idx + read index)): the fused call when trims is null.  Returns the
+	 * files as selectReads above, one round, named output + "-MinDepth<d>" + "-MaxDepth<T>" + "-" + prefix + suffix (:173,180);
+	 * normalizeInfo().picks is the reference's return value (pairs), getNumPicks() counts records */
+	std::vector<std::pair<std::string, std::string> > selectReadsNormalized(const kmr_normalize_config &cfg, const std::vector<uint64_t> &inputStarts = std::vector<uint64_t>(),
+	                                                                        const std::vector<std::string> &inputPrefixes = std::vector<std::string>(), const std::string &output = "",
+	                                                                        bool separateOutputs = true, const KmerSpectrum::TrimResult *trims = nullptr) {
+		reset();
+		const uint64_t *starts = inputStarts.empty() ? nullptr : inputStarts.data();
+		const uint32_t nIn = inputStarts.empty() ? 0 : (uint32_t)(inputStarts.size() - 1);
+		const int64_t *r1 = _read1.empty() ? nullptr : _read1.data(), *r2 = _read2.empty() ? nullptr : _read2.data();
+		if (trims) _sp.check(kmr_normalize_reads(_sp.raw(), _reads.raw(), _reads._text.data(), _reads._text.size(), r1, r2, _read1.size(), action(), minPass(), maxPass(), trims->trimOffset.data(),
+		                                         trims->trimLength.data(), trims->score.data(), trims->wasTrimmed.data(), starts, nIn, &cfg, &_p), "kmr_normalize_reads");
+		else _sp.check(kmr_normalize_read_batch(_sp.raw(), _reads.raw(), _reads._text.data(), _reads._text.size(), r1, r2, _read1.size(), action(), minPass(), maxPass(), starts, nIn, &cfg, &_p), "kmr_normalize_read_batch");
+		const std::string text = writePicks();
+		const Segments s = segments();
+		std::vector<std::pair<std::string, std::string> > files;
+		if (!separateOutputs) { files.push_back(std::make_pair(output, text)); return files; }
+		if (!inputPrefixes.empty() && inputPrefixes.size() != s.nInputs) throw KmerSpectrumError(KMR_ERR_INVALID_ARG, "selectReadsNormalized: one prefix per input");
+		const std::string name = output + "-MinDepth" + std::to_string((unsigned int)cfg.select.minimum_score) + "-MaxDepth" + std::to_string(cfg.target_depth);
+		for (uint32_t j = 0; j < s.nInputs; j++) {
+			if (!s.picks[j]) continue;
+			const std::string prefix = inputPrefixes.empty() ? "transformed-" + std::to_string(j + 1) : inputPrefixes[j];
+			files.push_back(std::make_pair(name + "-" + prefix + (cfg.select.format == 1 ? ".fasta" : ".fastq"), text.substr(s.firstByte[j], s.bytes[j])));
+		}
+		return files;
+	}
+	NormalizeInfo normalizeInfo() const {
+		NormalizeInfo i;
+		if (kmr_normalize_info(_p, &i.picks, &i.candidates, &i.draws) != KMR_OK) throw KmerSpectrumError(KMR_ERR_STATE, "normalizeInfo: the picks are not those of a normalization");
+		return i;
+	}
 	/* the segment table of the picks (kmr_picks_segments_copy): segment = round * nInputs + input */
 	Segments segments() const {
 		Segments s;
@@ -370,7 +408,7 @@ private:
 	const uint8_t *action() const { return _action.empty() ? nullptr : _action.data(); }
 	const uint32_t *minPass() const { return _minPass.empty() ? nullptr : _minPass.data(); }
 	const uint32_t *maxPass() const { return _maxPass.empty() ? nullptr : _maxPass.data(); }
-	KmerSpectrum &_sp; const ReadSet &_reads; std::vector<int64_t> _mate; std::vector<uint8_t> _action; std::vector<uint32_t> _minPass, _maxPass; kmr_picks *_p = nullptr;
+	KmerSpectrum &_sp; const ReadSet &_reads; std::vector<int64_t> _mate; std::vector<uint8_t> _action; std::vector<uint32_t> _minPass, _maxPass; std::vector<int64_t> _read1, _read2; kmr_picks *_p = nullptr;
 };
 
 }  // namespace kmernator

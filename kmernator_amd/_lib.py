@@ -76,6 +76,12 @@ class KmrPartitionConfig(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("select", KmrSelectConfig), ("partition_by_depth", C.c_uint32), ("remainder_trim", C.c_float)]
 
 
+class KmrNormalizeConfig(C.Structure):
+    """kmr_normalize_config"""
+    _fields_ = [("struct_size", C.c_uint32), ("select", KmrSelectConfig), ("target_depth", C.c_uint64), ("seed", C.c_uint64), ("first_global_read_idx", C.c_uint64),
+                ("by_pair", C.c_uint32), ("method", C.c_uint32), ("use_logscale", C.c_uint32)]
+
+
 # every symbol include/kmernator_amd.h declares
 EXPORTS = [
     "kmr_abi_version", "kmr_config_init", "kmr_create", "kmr_destroy", "kmr_last_error", "kmr_num_buckets",
@@ -94,6 +100,7 @@ EXPORTS = [
     "kmr_picks_info", "kmr_picks_copy", "kmr_picks_device_ptr", "kmr_picks_free",
     "kmr_partition_config_init", "kmr_partition_rounds", "kmr_partition_reads", "kmr_partition_reads_dev", "kmr_partition_read_batch", "kmr_partition_read_batch_dev",
     "kmr_picks_segments_info", "kmr_picks_segments_copy",
+    "kmr_normalize_config_init", "kmr_normalize_reads", "kmr_normalize_reads_dev", "kmr_normalize_read_batch", "kmr_normalize_read_batch_dev", "kmr_normalize_info",
     "kmr_dump_text_size", "kmr_dump_text", "kmr_text_info", "kmr_text_copy", "kmr_text_device_ptr", "kmr_text_free",
     "kmr_identify_pairs", "kmr_identify_pairs_dev", "kmr_pairs_info", "kmr_pairs_copy", "kmr_pairs_device_ptrs", "kmr_pairs_free",
     "kmr_dedup_config_init", "kmr_dedup_fragments", "kmr_dedup_fragments_dev", "kmr_dedup_info", "kmr_dedup_copy", "kmr_dedup_device_ptrs",
@@ -226,6 +233,13 @@ def load():
         getattr(lib, name).argtypes = [vp, vp, vp, C.c_uint64, i64p, u8p, u32p, u32p, u32p, u32p, f32p, u8p, u64p, C.c_uint32, pcp, C.POINTER(vp)]
     for name in ("kmr_partition_read_batch", "kmr_partition_read_batch_dev"):
         getattr(lib, name).argtypes = [vp, vp, vp, C.c_uint64, i64p, u8p, u32p, u32p, u64p, C.c_uint32, pcp, C.POINTER(vp)]
+    ncp = C.POINTER(KmrNormalizeConfig)
+    lib.kmr_normalize_config_init.argtypes = [ncp]
+    for name in ("kmr_normalize_reads", "kmr_normalize_reads_dev"):
+        getattr(lib, name).argtypes = [vp, vp, vp, C.c_uint64, i64p, i64p, C.c_uint64, u8p, u32p, u32p, u32p, u32p, f32p, u8p, u64p, C.c_uint32, ncp, C.POINTER(vp)]
+    for name in ("kmr_normalize_read_batch", "kmr_normalize_read_batch_dev"):
+        getattr(lib, name).argtypes = [vp, vp, vp, C.c_uint64, i64p, i64p, C.c_uint64, u8p, u32p, u32p, u64p, C.c_uint32, ncp, C.POINTER(vp)]
+    lib.kmr_normalize_info.argtypes = [vp, u64p, u64p, u64p]
     lib.kmr_picks_segments_info.argtypes = [vp, u32p, u32p]
     lib.kmr_picks_segments_copy.argtypes = [vp, f32p, u8p, u64p, u64p, u64p, u64p, C.POINTER(C.c_int32)]
     lib.kmr_picks_info.argtypes = [vp, u64p, u64p]

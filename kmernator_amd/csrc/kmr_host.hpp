@@ -278,6 +278,9 @@ struct KMR_HIDDEN kmr_picks : OnDevice {
 	uint32_t n_rounds = 1, n_inputs = 1;
 	float round_depth[33] = {};
 	uint8_t round_is_remainder[33] = {};
+	/* kmr_normalize_*: picks (pairs), chooseRead calls, draws (kmr_normalize_info) */
+	bool normalized = false;
+	uint64_t norm_info[3] = {};
 };
 
 /* what kmr_identify_pairs* leaves on the device: the mate of every read and the pair list */

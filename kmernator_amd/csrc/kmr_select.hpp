@@ -29,7 +29,7 @@
 
 namespace kmr {
 
-enum { SEL_ERR_MATE = 1, SEL_ERR_NAME = 2 };
+enum { SEL_ERR_MATE = 1, SEL_ERR_NAME = 2, SEL_ERR_PAIR = 4, SEL_ERR_TWICE = 8 };      /* the last two: the pair list of kmr_normalize.hpp */
 static const int SEL_THREADS = 256, SEL_WAVES = SEL_THREADS / 64, SEL_LABEL_CAP = 128;
 
 struct SelectParams {
@@ -209,7 +209,7 @@ void select_write_kernel(SelectParams P, const uint32_t *name_printed, const uin
  *                              segment table, the totals and the sentinel of pick_off
  *   partition_rank_kernel      per unit again: a read's pick index = its unit's base for the segment + the reads of that segment
  *                              before it in the unit, likewise its byte offset; fills the (pick_read, pick_off) select_write_kernel
- *                              reads
+ *                              reads.  With slot_read it ranks slots that hold reads (kmr_normalize.hpp): pick_read takes the slot's read
  * A unit is one wavefront (a block of 64 threads) over a CONTIGUOUS range of reads, walked 64 reads at a time: consecutive
  * lanes still read consecutive elements, as in a grid stride, but a unit's reads are all before the next unit's, which is what
  * makes the partition stable.  The LDS atomics only add integers (order-free sums); ranks come from ballots and wave scans.
@@ -292,7 +292,7 @@ void partition_scan_kernel(uint32_t *unit_cnt, unsigned long long *unit_bytes, u
 
 __global__ __launch_bounds__(SEL_UNIT)
 void partition_rank_kernel(const int32_t *read_seg, const uint32_t *rec_len, uint64_t n, PartitionParams Q, const uint32_t *unit_cnt, const unsigned long long *unit_bytes,
-                           uint32_t *pick_read, uint64_t *pick_off) {
+                           uint32_t *pick_read, uint64_t *pick_off, const uint32_t *slot_read) {
 	__shared__ uint32_t s_cnt[SEL_MAX_SEGMENTS];            /* where the unit's next read of the segment goes */
 	__shared__ unsigned long long s_bytes[SEL_MAX_SEGMENTS];
 	const uint32_t lane = threadIdx.x, u = blockIdx.x;
@@ -313,7 +313,7 @@ void partition_rank_kernel(const int32_t *read_seg, const uint32_t *rec_len, uin
 			for (int d = 1; d < 64; d <<= 1) { const unsigned long long x = __shfl_up(inc, d); if ((int)lane >= d) inc += x; }
 			const unsigned long long all = __shfl(inc, 63);
 			const uint32_t at = s_cnt[s0]; const unsigned long long byte_at = s_bytes[s0];
-			if (mine) { const uint32_t p = at + (uint32_t)__popcll(members & ((1ull << lane) - 1)); pick_read[p] = (uint32_t)i; pick_off[p] = byte_at + inc - len; }
+			if (mine) { const uint32_t p = at + (uint32_t)__popcll(members & ((1ull << lane) - 1)); pick_read[p] = slot_read ? slot_read[i] : (uint32_t)i; pick_off[p] = byte_at + inc - len; }
 			__syncthreads();
 			if ((int)lane == leader) { s_cnt[s0] = at + (uint32_t)__popcll(members); s_bytes[s0] = byte_at + all; }
 			__syncthreads();

@@ -1,6 +1,6 @@
 /*
  * kmr_stages.hip -- the read stages of include/kmernator_amd.h: FASTQ ingest and the kmr_reads batch, its two-bit form, the artifact
- * filter, read selection and its output text, identifyPairs, duplicate-fragment collapse, and the mercount / mergraph text.
+ * filter, read selection, coverage normalization and their output text, identifyPairs, duplicate-fragment collapse, and the mercount / mergraph text.
  *
  * Host logic only, as kmr_api.hip (the spectrum, which these stages read through kmr_host.hpp); the kernels are the stage headers',
  * each of which this translation unit alone includes.  A stage costs its kernels and a page here: what the stages share is below --
@@ -17,6 +17,7 @@
 #include "kmr_ingest.hpp"
 #include "kmr_artifact.hpp"
 #include "kmr_select.hpp"
+#include "kmr_normalize.hpp"
 #include "kmr_pairs.hpp"
 #include "kmr_dedup.hpp"
 #include "kmr_dump.hpp"
@@ -707,6 +708,8 @@ static int select_write(kmr_handle *h, Scratch &tmp, const SelectParams &P, cons
 	HIPCHK(h, hipMemcpyAsync(host_tot, tot, 8 * n_tot, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
 	if (host_tot[2] & SEL_ERR_MATE) return fail(h, KMR_ERR_INVALID_ARG, "a mate index lies outside the batch");
 	if (host_tot[2] & SEL_ERR_NAME) return fail(h, KMR_ERR_INVALID_ARG, NAME_SPAN_ERROR);
+	if (host_tot[2] & SEL_ERR_PAIR) return fail(h, KMR_ERR_INVALID_ARG, "the pair list holds an index outside the batch or a pair without a read");
+	if (host_tot[2] & SEL_ERR_TWICE) return fail(h, KMR_ERR_INVALID_ARG, "the pair list names a read twice");
 	pk->n_picked = host_tot[0]; pk->bytes = host_tot[1];
 	timer.mark(1, h->stream);
 	if (pk->bytes) {
@@ -784,7 +787,7 @@ static int partition_core(kmr_handle *h, Scratch &tmp, const SelectParams &P, co
 	HIPCHK(h, hipMemsetAsync(tot, 0, 24, h->stream));
 	hipLaunchKernelGGL(partition_classify_kernel, dim3(Q.n_units), dim3(SEL_UNIT), 0, h->stream, P, R, Q, seg, len, nlen, picked, ucnt, ubytes, (uint32_t *)(tot + 2));
 	hipLaunchKernelGGL(partition_scan_kernel, dim3(1), dim3(SEL_SCAN_THREADS), 0, h->stream, ucnt, ubytes, S, Q.n_units, tot + 3, poff, tot);
-	hipLaunchKernelGGL(partition_rank_kernel, dim3(Q.n_units), dim3(SEL_UNIT), 0, h->stream, (const int32_t *)seg, (const uint32_t *)len, n, Q, (const uint32_t *)ucnt, (const unsigned long long *)ubytes, pread, poff);
+	hipLaunchKernelGGL(partition_rank_kernel, dim3(Q.n_units), dim3(SEL_UNIT), 0, h->stream, (const int32_t *)seg, (const uint32_t *)len, n, Q, (const uint32_t *)ucnt, (const unsigned long long *)ubytes, pread, poff, (const uint32_t *)nullptr);
 	HIPCHK(h, hipGetLastError());
 	std::vector<uint64_t> host_tot(3 + (size_t)4 * S, 0);
 	int rc = select_write(h, tmp, P, nlen, pread, poff, tot, host_tot.size(), host_tot.data(), pk, timer); if (rc) return rc;
@@ -819,6 +822,69 @@ static int partition_check(kmr_handle *h, const PartitionArgs *a, SelRounds *R, 
 	return 0;
 }
 
+/* ---- the normalizing branch (kmr_normalize.hpp) ---------------- */
+/* what the four normalizing entry points add to the arguments of the plain four, in place of mate */
+struct NormalizeArgs { const kmr_normalize_config *cfg; const int64_t *read1, *read2; uint64_t n_pairs; const uint64_t *input_starts; uint32_t n_inputs; };
+
+/* cfg, the pair list's shape and the input boundaries, all without a device.  R: the one round.  *n_inputs: 1 for input_starts NULL */
+static int normalize_check(kmr_handle *h, const NormalizeArgs *a, SelRounds *R, uint32_t *n_inputs) {
+	const kmr_normalize_config *c = a->cfg;
+	if (!c) return fail(h, KMR_ERR_INVALID_ARG, "kmr_normalize_config: NULL");
+	if (c->struct_size != sizeof(kmr_normalize_config)) return fail(h, KMR_ERR_INVALID_ARG, "kmr_normalize_config: struct_size " + std::to_string(c->struct_size) + " is not " + std::to_string(sizeof(kmr_normalize_config)));
+	if (c->method != 0) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_normalize_config: method 0 (RANDOM) only; OPTIMAL is a serial greedy heap over a shared count map");
+	if (c->use_logscale) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_normalize_config: use_logscale (the reference's expression has no pinned value)");
+	if (c->target_depth == 0) return fail(h, KMR_ERR_INVALID_ARG, "kmr_normalize_config: target_depth must be above 0");
+	if ((a->read1 != nullptr) != (a->read2 != nullptr)) return fail(h, KMR_ERR_INVALID_ARG, "the pair list: read1 and read2 go together");
+	kmr_partition_config pc;
+	kmr_partition_config_init(&pc);
+	pc.select = c->select;
+	const PartitionArgs pa = {&pc, a->input_starts, a->n_inputs};
+	return partition_check(h, &pa, R, n_inputs);
+}
+
+/* P as select_core's with mate null; dr1 / dr2 the pair list and dstarts the inputs' first reads in device memory (null for none) */
+static int normalize_core(kmr_handle *h, Scratch &tmp, const SelectParams &P, const kmr_normalize_config *c, const int64_t *dr1, const int64_t *dr2, uint64_t n_pairs,
+                          const uint64_t *dstarts, uint32_t n_inputs, kmr_picks *pk) {
+	const uint64_t n = P.n, n_slots = 2 * n;
+	const uint32_t S = n_inputs;
+	pk->n = n; pk->n_rounds = 1; pk->n_inputs = n_inputs; pk->normalized = true;
+	pk->round_depth[0] = P.min_score; pk->round_is_remainder[0] = 0;
+	pk->seg_table.assign((size_t)4 * S, 0);
+	h->last_select_ms = h->last_write_ms = 0;
+	if (n == 0) return KMR_OK;
+	uint8_t *picked; int32_t *rseg;
+	HIPCHK(h, alloc_n(pk->picked, &picked, n)); HIPCHK(h, alloc_n(pk->read_seg, &rseg, n));
+	NormalizeParams N;
+	N.read1 = dr1; N.read2 = dr2; N.n_pairs = n_pairs; N.target = c->target_depth; N.seed = c->seed; N.first_global = c->first_global_read_idx; N.by_pair = c->by_pair ? 1u : 0u;
+	PartitionParams Q;
+	Q.input_starts = dstarts; Q.n_inputs = n_inputs; Q.n_segments = S;
+	partition_units(h, n_slots, S, Q);
+	const size_t cells = (size_t)S * Q.n_units, n_tot = 3 + (size_t)4 * S + 3;
+	uint32_t *zeroed, *slot_read, *nlen, *pread, *ucnt; int32_t *slot_seg; uint64_t *poff, *tot; unsigned long long *ubytes;
+	HIPCHK(h, tmp.take(&zeroed, 3 * n)); HIPCHK(h, tmp.take(&slot_read, n_slots)); HIPCHK(h, tmp.take(&slot_seg, n_slots));
+	/* pread / poff: a slot each, not a read each -- a list that names a read twice (refused below) can fill more than n slots */
+	HIPCHK(h, tmp.take(&nlen, n)); HIPCHK(h, tmp.take(&pread, n_slots)); HIPCHK(h, tmp.take(&poff, n_slots + 1));
+	HIPCHK(h, tmp.take(&ucnt, cells)); HIPCHK(h, tmp.take(&ubytes, cells)); HIPCHK(h, tmp.take(&tot, n_tot));
+	uint32_t *named = zeroed, *slot_len = zeroed + n;      /* one block, one memset: reads named by a pair; record bytes of a slot */
+	SelectTimer timer(h->tune.select_timing);
+	timer.mark(0, h->stream);
+	HIPCHK(h, hipMemsetAsync(tot, 0, 8 * n_tot, h->stream)); HIPCHK(h, hipMemsetAsync(zeroed, 0, 12 * n, h->stream));
+	HIPCHK(h, hipMemsetAsync(slot_seg, 0xff, 4 * n_slots, h->stream)); HIPCHK(h, hipMemsetAsync(rseg, 0xff, 4 * n, h->stream)); HIPCHK(h, hipMemsetAsync(picked, 0, n, h->stream));
+	uint32_t *err = (uint32_t *)(tot + 2);
+	unsigned long long *counters = (unsigned long long *)(tot + 3 + (size_t)4 * S);
+	if (n_pairs) hipLaunchKernelGGL(normalize_mark_kernel, dim3(grid_for(n_pairs)), dim3(256), 0, h->stream, N, n, named, err);
+	hipLaunchKernelGGL(normalize_classify_kernel, dim3(grid_for(n_pairs + n)), dim3(256), 0, h->stream, P, N, Q, (const uint32_t *)named, slot_read, slot_seg, slot_len, nlen, picked, rseg, counters, err);
+	hipLaunchKernelGGL(normalize_count_kernel, dim3(Q.n_units), dim3(SEL_UNIT), 0, h->stream, (const int32_t *)slot_seg, (const uint32_t *)slot_len, n_slots, Q, ucnt, ubytes);
+	hipLaunchKernelGGL(partition_scan_kernel, dim3(1), dim3(SEL_SCAN_THREADS), 0, h->stream, ucnt, ubytes, S, Q.n_units, tot + 3, poff, tot);
+	hipLaunchKernelGGL(partition_rank_kernel, dim3(Q.n_units), dim3(SEL_UNIT), 0, h->stream, (const int32_t *)slot_seg, (const uint32_t *)slot_len, n_slots, Q, (const uint32_t *)ucnt, (const unsigned long long *)ubytes, pread, poff, (const uint32_t *)slot_read);
+	HIPCHK(h, hipGetLastError());
+	std::vector<uint64_t> host_tot(n_tot, 0);
+	int rc = select_write(h, tmp, P, nlen, pread, poff, tot, n_tot, host_tot.data(), pk, timer); if (rc) return rc;
+	std::copy(host_tot.begin() + 3, host_tot.begin() + 3 + (size_t)4 * S, pk->seg_table.begin());
+	std::copy(host_tot.end() - 3, host_tot.end(), pk->norm_info);
+	return KMR_OK;
+}
+
 static int select_check_args(kmr_handle *h, const kmr_reads *r, const void *text, uint64_t text_len, const uint8_t *af_action, const uint32_t *af_min, const uint32_t *af_max,
                              const kmr_select_config *cfg, kmr_picks **out, const char *who) {
 	if (out) *out = nullptr;
@@ -834,17 +900,25 @@ static int select_check_args(kmr_handle *h, const kmr_reads *r, const void *text
 /* text_on_device: `text` is device memory already (the other arrays are the host's) */
 static int select_reads_any(kmr_handle *h, const kmr_reads *r, const void *text, uint64_t text_len, bool text_on_device, const int64_t *mate, const uint8_t *af_action,
                             const uint32_t *af_min, const uint32_t *af_max, const uint32_t *trim_offset, const uint32_t *trim_length, const float *score,
-                            const uint8_t *was_trimmed, const kmr_select_config *cfg, kmr_picks **out, bool fused, const char *who, const PartitionArgs *part = nullptr) {
+                            const uint8_t *was_trimmed, const kmr_select_config *cfg, kmr_picks **out, bool fused, const char *who, const PartitionArgs *part = nullptr,
+                            const NormalizeArgs *norm = nullptr) {
 	SelRounds R; uint32_t n_inputs = 1;
 	int rc;
 	if (part) {
 		if (out) *out = nullptr;
 		rc = partition_check(h, part, &R, &n_inputs); if (rc) return rc;
 		cfg = &part->cfg->select;
+	} else if (norm) {
+		if (out) *out = nullptr;
+		rc = normalize_check(h, norm, &R, &n_inputs); if (rc) return rc;
+		cfg = &norm->cfg->select;
 	}
 	rc = select_check_args(h, r, text, text_len, af_action, af_min, af_max, cfg, out, who); if (rc) return rc;
-	if (part && part->input_starts && part->input_starts[n_inputs] != r->n)
-		return fail(h, KMR_ERR_INVALID_ARG, std::string(who) + ": input_starts ends at " + std::to_string(part->input_starts[n_inputs]) + ", the batch holds " + std::to_string(r->n) + " reads");
+	const uint64_t *starts = part ? part->input_starts : (norm ? norm->input_starts : nullptr);
+	if (starts && starts[n_inputs] != r->n)
+		return fail(h, KMR_ERR_INVALID_ARG, std::string(who) + ": input_starts ends at " + std::to_string(starts[n_inputs]) + ", the batch holds " + std::to_string(r->n) + " reads");
+	const uint64_t n_pairs = norm && norm->read1 ? norm->n_pairs : 0;
+	if (n_pairs && !r->n) return fail(h, KMR_ERR_INVALID_ARG, std::string(who) + ": a pair list for an empty batch");
 	if (fused) { if (!h->finalized) return fail(h, KMR_ERR_STATE, std::string(who) + " before kmr_finalize"); }
 	else if (r->n && (!trim_offset || !trim_length || !score || !was_trimmed)) return fail(h, KMR_ERR_INVALID_ARG, std::string(who) + ": NULL argument");
 	hipSetDevice(h->device);
@@ -873,10 +947,14 @@ static int select_reads_any(kmr_handle *h, const kmr_reads *r, const void *text,
 		rc = to_device(h, tmp, was_trimmed, n, &dwt); if (rc) return rc;
 	}
 	const SelectParams P = select_params(h, r, dtext, text_len, dmate, dact, dmin, dmax, dto, dtl, dsc, dwt, cfg);
-	if (part) {
+	if (part || norm) {
 		const uint64_t *dstarts = nullptr;
-		if (n_inputs > 1) { rc = to_device(h, tmp, part->input_starts, (uint64_t)n_inputs + 1, &dstarts); if (rc) return rc; }
-		rc = partition_core(h, tmp, P, R, dstarts, n_inputs, pk.get());
+		if (n_inputs > 1) { rc = to_device(h, tmp, starts, (uint64_t)n_inputs + 1, &dstarts); if (rc) return rc; }
+		if (norm) {
+			const int64_t *dr1 = nullptr, *dr2 = nullptr;
+			if (n_pairs) { rc = to_device(h, tmp, norm->read1, n_pairs, &dr1); if (rc) return rc; rc = to_device(h, tmp, norm->read2, n_pairs, &dr2); if (rc) return rc; }
+			rc = normalize_core(h, tmp, P, norm->cfg, dr1, dr2, n_pairs, dstarts, n_inputs, pk.get());
+		} else rc = partition_core(h, tmp, P, R, dstarts, n_inputs, pk.get());
 	} else rc = select_core(h, tmp, P, pk.get());
 	if (!rc) *out = pk.release();
 	return rc;
@@ -943,6 +1021,45 @@ int kmr_partition_read_batch_dev(kmr_handle *h, const kmr_reads *reads, const vo
                                  const uint32_t *af_max_pass, const uint64_t *input_starts, uint32_t n_inputs, const kmr_partition_config *cfg, kmr_picks **out) {
 	const PartitionArgs a = {cfg, input_starts, n_inputs};
 	return select_reads_any(h, reads, dev_text, text_len, true, mate, af_action, af_min_pass, af_max_pass, nullptr, nullptr, nullptr, nullptr, nullptr, out, true, "kmr_partition_read_batch_dev", &a);
+}
+/* ---- the normalizing branch: the same four with the pair list in place of mate, and the draws' parameters ---------------- */
+int kmr_normalize_config_init(kmr_normalize_config *c) {
+	if (!c) return KMR_ERR_INVALID_ARG;
+	memset(c, 0, sizeof(*c));
+	c->struct_size = (uint32_t)sizeof(kmr_normalize_config);
+	kmr_select_config_init(&c->select);
+	c->target_depth = 0;               /* --max-kmer-output-depth -1, src/ReadSelector.h:72: off; the caller sets it */
+	c->by_pair = 0;                    /* selectReads passes reads.hasPairs() (apps/FilterReads.h:184) */
+	return KMR_OK;
+}
+int kmr_normalize_reads(kmr_handle *h, const kmr_reads *reads, const char *text, uint64_t text_len, const int64_t *read1, const int64_t *read2, uint64_t n_pairs,
+                        const uint8_t *af_action, const uint32_t *af_min_pass, const uint32_t *af_max_pass, const uint32_t *trim_offset, const uint32_t *trim_length, const float *score,
+                        const uint8_t *was_trimmed, const uint64_t *input_starts, uint32_t n_inputs, const kmr_normalize_config *cfg, kmr_picks **out) {
+	const NormalizeArgs a = {cfg, read1, read2, n_pairs, input_starts, n_inputs};
+	return select_reads_any(h, reads, text, text_len, false, nullptr, af_action, af_min_pass, af_max_pass, trim_offset, trim_length, score, was_trimmed, nullptr, out, false, "kmr_normalize_reads", nullptr, &a);
+}
+int kmr_normalize_reads_dev(kmr_handle *h, const kmr_reads *reads, const void *dev_text, uint64_t text_len, const int64_t *read1, const int64_t *read2, uint64_t n_pairs,
+                            const uint8_t *af_action, const uint32_t *af_min_pass, const uint32_t *af_max_pass, const uint32_t *trim_offset, const uint32_t *trim_length, const float *score,
+                            const uint8_t *was_trimmed, const uint64_t *input_starts, uint32_t n_inputs, const kmr_normalize_config *cfg, kmr_picks **out) {
+	const NormalizeArgs a = {cfg, read1, read2, n_pairs, input_starts, n_inputs};
+	return select_reads_any(h, reads, dev_text, text_len, true, nullptr, af_action, af_min_pass, af_max_pass, trim_offset, trim_length, score, was_trimmed, nullptr, out, false, "kmr_normalize_reads_dev", nullptr, &a);
+}
+int kmr_normalize_read_batch(kmr_handle *h, const kmr_reads *reads, const char *text, uint64_t text_len, const int64_t *read1, const int64_t *read2, uint64_t n_pairs,
+                             const uint8_t *af_action, const uint32_t *af_min_pass, const uint32_t *af_max_pass, const uint64_t *input_starts, uint32_t n_inputs,
+                             const kmr_normalize_config *cfg, kmr_picks **out) {
+	const NormalizeArgs a = {cfg, read1, read2, n_pairs, input_starts, n_inputs};
+	return select_reads_any(h, reads, text, text_len, false, nullptr, af_action, af_min_pass, af_max_pass, nullptr, nullptr, nullptr, nullptr, nullptr, out, true, "kmr_normalize_read_batch", nullptr, &a);
+}
+int kmr_normalize_read_batch_dev(kmr_handle *h, const kmr_reads *reads, const void *dev_text, uint64_t text_len, const int64_t *read1, const int64_t *read2, uint64_t n_pairs,
+                                 const uint8_t *af_action, const uint32_t *af_min_pass, const uint32_t *af_max_pass, const uint64_t *input_starts, uint32_t n_inputs,
+                                 const kmr_normalize_config *cfg, kmr_picks **out) {
+	const NormalizeArgs a = {cfg, read1, read2, n_pairs, input_starts, n_inputs};
+	return select_reads_any(h, reads, dev_text, text_len, true, nullptr, af_action, af_min_pass, af_max_pass, nullptr, nullptr, nullptr, nullptr, nullptr, out, true, "kmr_normalize_read_batch_dev", nullptr, &a);
+}
+int kmr_normalize_info(const kmr_picks *p, uint64_t *n_picks, uint64_t *n_candidates, uint64_t *n_draws) {
+	if (!p || !p->normalized) return KMR_ERR_INVALID_ARG;
+	if (n_picks) *n_picks = p->norm_info[0]; if (n_candidates) *n_candidates = p->norm_info[1]; if (n_draws) *n_draws = p->norm_info[2];
+	return KMR_OK;
 }
 int kmr_picks_segments_info(const kmr_picks *p, uint32_t *n_rounds, uint32_t *n_inputs) {
 	if (!p) return KMR_ERR_INVALID_ARG;

@@ -821,14 +821,31 @@ class ReadSelector(_DeviceObject):
     pickAllPassingPairs (:576-596) and writePicks (:1242-1262), selection and text produced on the device (kmr_select_reads,
     kmr_filter_read_batch).  `mate` = index of each read's pair or -1 (None: every read is single); `filter_results` = the dict
     FilterKnownOddities.applyFilter returned for the batch `read_set` was made from (the remnants it appended count as single,
-    untouched reads).  The output text stays on the device until writePicks copies it."""
+    untouched reads).  `pairs` = the pair list coverage normalization decides over (pickCoverageNormalizedSubset, selectReads with
+    max_kmer_output_depth): a ReadPairs, or (read1, read2) arrays with -1 for a missing side; without it the list is the pairs of
+    `mate`, and every read no pair names is a half pair.  The output text stays on the device until writePicks copies it."""
 
     _HANDLE, _FREE = "_picks", "kmr_picks_free"
     FORMAT = {"fastq": 0, "fasta": 1}
 
-    def __init__(self, spectrum, read_set, mate=None, filter_results=None):
+    def __init__(self, spectrum, read_set, mate=None, filter_results=None, pairs=None):
         self.sp, self.reads = spectrum, read_set
         n = read_set.n
+        self.pairs, self.has_pairs = None, False
+        if pairs is not None:
+            found = pairs if isinstance(pairs, ReadPairs) else None
+            if found is not None:
+                pairs = (found.pairs[:, 0], found.pairs[:, 1])
+            r1, r2 = (np.ascontiguousarray(x, dtype=np.int64) for x in pairs)
+            assert r1.size == r2.size
+            self.pairs = (r1, r2)
+            self.has_pairs = found.hasPairs() if found is not None else 0 < r1.size < n      # ReadSet::hasPairs (src/ReadSet.h:526-529)
+        elif mate is not None:
+            m = np.full(n, -1, dtype=np.int64)
+            m[:np.size(mate)] = np.asarray(mate, dtype=np.int64)
+            first = np.nonzero(m > np.arange(n))[0].astype(np.int64)
+            self.pairs = (first, np.ascontiguousarray(m[first]))
+            self.has_pairs = first.size > 0
         self.mate = None
         if mate is not None:
             self.mate = np.full(n, -1, dtype=np.int64)
@@ -933,15 +950,38 @@ class ReadSelector(_DeviceObject):
     SUFFIX = {0: ".fastq", 1: ".fasta"}
 
     def selectReads(self, min_depth, partition_by_depth=0, remainder_trim=-1.0, min_read_length=None, both_pass=False, scoring="MEDIAN",
-                    output_quality_base=33, format="fastq", input_starts=None, input_prefixes=None, output="", separate_outputs=True):
-        """selectReads (apps/FilterReads.h:159-279) with --max-kmer-output-depth off: the rounds of --partition-by-depth and
+                    output_quality_base=33, format="fastq", input_starts=None, input_prefixes=None, output="", separate_outputs=True,
+                    max_kmer_output_depth=0, normalization_method="RANDOM", seed=0, first_read_idx=0, by_pair=None):
+        """selectReads (apps/FilterReads.h:159-279).  With --max-kmer-output-depth off: the rounds of --partition-by-depth and
         --remainder-trim over the reads of `input_starts` (n_inputs + 1 ascending read indices; None = one input), on the device
         (kmr_partition_read_batch, or kmr_partition_reads over the trims scoreAndTrimReads left).  Returns the ordered list of
         (file name, bytes) the reference writes: with separate_outputs `output` + "-MinDepth<min_depth>" + "-PartitionDepth<depth>"
         or "-Remainder" (only when partitioned) + "-" + the input's prefix + ".fastq" / ".fasta", round-major and by input inside
         a round, a file nothing was written to left out (the reference opens a file at its first read); without, one entry named
         `output` that holds the concatenation.  input_prefixes default to "transformed-<j + 1>", the reference's name for reads
-        that came from no input file (src/ReadSet.cpp:376-382).  .segments and .read_segment hold the tables."""
+        that came from no input file (src/ReadSet.cpp:376-382).  .segments and .read_segment hold the tables.
+        With max_kmer_output_depth > 0 (:178-206): coverage normalization over `pairs` (kmr_normalize_*), one round whose files
+        are named `output` + "-MinDepth<min_depth>" + "-MaxDepth<depth>" + "-" + prefix + suffix; by_pair defaults to the pairs'
+        hasPairs, as the reference passes it; normalization_method "RANDOM" only; together with partition_by_depth it raises, as
+        the reference's option check does (src/ReadSelector.h:137)."""
+        if max_kmer_output_depth > 0:
+            if partition_by_depth > 0:
+                raise KmerSpectrumError("selectReads: max_kmer_output_depth and partition_by_depth exclude each other")
+            if normalization_method not in ("RANDOM", "OPTIMAL"):
+                raise KmerSpectrumError("selectReads: normalization_method %r" % (normalization_method,))
+            cfg = self._normalize(max_kmer_output_depth, min_depth, min_read_length, self.has_pairs if by_pair is None else by_pair, both_pass, seed, first_read_idx,
+                                  scoring, output_quality_base, format, input_starts, method=0 if normalization_method == "RANDOM" else 1)
+            text = self._copy()
+            seg = self._segments()
+            if not separate_outputs:
+                return [(output, text)]
+            n_inputs = seg["picks"].shape[1]
+            prefixes = list(input_prefixes) if input_prefixes is not None else ["transformed-%d" % (j + 1) for j in range(n_inputs)]
+            if len(prefixes) != n_inputs:
+                raise KmerSpectrumError("selectReads: %d input_prefixes for %d inputs" % (len(prefixes), n_inputs))
+            name = "%s-MinDepth%d-MaxDepth%d" % (output, int(min_depth), int(max_kmer_output_depth))
+            return [(name + "-" + prefixes[j] + self.SUFFIX[cfg.select.format], text[int(seg["first_byte"][0, j]):int(seg["first_byte"][0, j]) + int(seg["bytes"][0, j])])
+                    for j in range(n_inputs) if seg["picks"][0, j]]
         fused = self.trims is None
         cfg = _lib.KmrPartitionConfig()
         self.sp.lib.kmr_partition_config_init(C.byref(cfg))
@@ -982,6 +1022,47 @@ class ReadSelector(_DeviceObject):
                     b0 = int(seg["first_byte"][r, j])
                     files.append((name + "-" + prefixes[j] + self.SUFFIX[cfg.select.format], text[b0:b0 + int(seg["bytes"][r, j])]))
         return files
+
+    def _normalize(self, target_depth, min_score, min_read_length, by_pair, both_pass, seed, first_read_idx, scoring, output_quality_base, format,
+                   input_starts=None, method=0, use_logscale=False):
+        """kmr_normalize_reads over the trims scoreAndTrimReads left, or kmr_normalize_read_batch without them"""
+        fused = self.trims is None
+        cfg = _lib.KmrNormalizeConfig()
+        self.sp.lib.kmr_normalize_config_init(C.byref(cfg))
+        cfg.select = self._config(min_score, min_read_length, both_pass, output_quality_base, format, scoring if fused else self.scoring)
+        cfg.target_depth, cfg.seed, cfg.first_global_read_idx = int(target_depth), int(seed), int(first_read_idx)
+        cfg.by_pair, cfg.method, cfg.use_logscale = (1 if by_pair else 0), int(method), (1 if use_logscale else 0)
+        starts, n_inputs = None, 0
+        if input_starts is not None:
+            starts = np.ascontiguousarray(input_starts, dtype=np.uint64)
+            n_inputs = starts.size - 1
+        r1, r2 = self.pairs if self.pairs is not None else (None, None)
+        keep, tp, tn = self._text_args()
+        out = C.c_void_p()
+        head = (self.sp.h, self.reads.r, tp, tn, self._p(r1, C.c_int64), self._p(r2, C.c_int64), 0 if r1 is None else r1.size) + tuple(self._af_args())
+        tail = (self._p(starts, C.c_uint64), n_inputs, C.byref(cfg), C.byref(out))
+        if fused:
+            self.sp._call("normalize_read_batch", *head, *tail)
+        else:
+            to, tl, sc, wt = self.trims
+            to = np.ascontiguousarray(to, dtype=np.uint32); tl = np.ascontiguousarray(tl, dtype=np.uint32)
+            sc = np.ascontiguousarray(sc, dtype=np.float32); wt = np.ascontiguousarray(wt, dtype=np.uint8)
+            self.sp._call("normalize_reads", *head, self._p(to, C.c_uint32), self._p(tl, C.c_uint32), self._p(sc, C.c_float), self._p(wt, C.c_uint8), *tail)
+        self._adopt(out)
+        self._sel, self._fmt = None, (output_quality_base, cfg.select.format)
+        v = [C.c_uint64() for _ in range(3)]
+        _ok(self.sp.lib.kmr_normalize_info(self._picks, *[C.byref(x) for x in v]), "kmr_normalize_info")
+        self.normalize_info = dict(zip(("n_picks", "n_candidates", "n_draws"), (x.value for x in v)))
+        return cfg
+
+    def pickCoverageNormalizedSubset(self, target_depth, min_score=0.0, min_read_length=None, by_pair=False, both_pass=False, seed=0, first_read_idx=0,
+                                     output_quality_base=33, format="fastq"):
+        """ReadSelector::pickCoverageNormalizedSubset (:673-749), RANDOM, over `pairs`, on the device (kmr_normalize_reads, or
+        kmr_normalize_read_batch if scoreAndTrimReads has not run): a pair or read of score s above target_depth is kept if
+        draw % s <= target_depth, draw = Philox4x32-10 of (seed, first_read_idx + read index).  Returns the number of picks as the
+        reference counts them (pairs; n_picked counts records); .normalize_info holds them with the chooseRead calls and the draws."""
+        self._normalize(target_depth, min_score, min_read_length, by_pair, both_pass, seed, first_read_idx, "MEDIAN", output_quality_base, format)
+        return self.normalize_info["n_picks"]
 
     def _segments(self):
         """the segment table (kmr_picks_segments_copy) into .segments -- round_depth and round_is_remainder per round, first_pick,
