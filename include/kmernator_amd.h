@@ -1019,8 +1019,8 @@ void *kmr_stream(kmr_handle *h);
  *   list share, the default), "saturated_batch_bytes" (scratch budget of one batch of kmr_finalize's ordered pass over k-mers seen 256
  *   times or more, 0 = 1 GiB; a key whose sightings alone exceed it is a batch of its own).
  *   "select_timing" (1: kmr_select_reads* / kmr_filter_read_batch* / kmr_partition_* / kmr_normalize_* time their phases with HIP events, see kmr_build_info; default 0).
- *   "partition_units" (most wavefronts, each over a contiguous range of reads, that kmr_partition_* deals the batch to (kmr_normalize_*: its 2 n slots), 1 - 8192; 0 = the
- *   default, 8192 for up to 32 segments; tests set a few so that one wavefront walks many tiles of 64 reads; may be set at any time).
+ *   "partition_units" (most wavefronts, each over a contiguous range of reads, that kmr_select_reads* / kmr_filter_read_batch* / kmr_partition_* deal the batch to
+ *   (kmr_normalize_*: its 2 n slots), 1 - 8192; 0 = the default, 4096 (kmr_normalize_*: 8192) unless there are many segments; tests set a few so that one wavefront walks many tiles of 64 reads; may be set at any time).
  *   "dump_timing" (1: kmr_dump_text_size / kmr_dump_text time their size pass and writer with HIP events, see kmr_build_info; default 0),
  *   "dump_piece_bytes" (staging bound of one piece of kmr_dump_mercount / kmr_dump_mergraph's file, 0 = KMR_DUMP_PIECE_BYTES; may be set at any time).
  *   "pair_hash_bits" (bits of the common name's hash that kmr_identify_pairs* sorts by, 1 - 64, default 64: with a few bits distinct names

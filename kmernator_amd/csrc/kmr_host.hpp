@@ -271,8 +271,8 @@ struct OnDevice { int device = 0; };
 struct KMR_HIDDEN kmr_picks : OnDevice {
 	DevBuf text, picked;
 	uint64_t n = 0, n_picked = 0, bytes = 0;
-	/* the partitioned entry points: segment = round * n_inputs + input.  Picks of the plain entry points are one round and one
-	 * input, hold no read_seg (it follows from picked) and an empty seg_table (it follows from the totals) */
+	/* segment = round * n_inputs + input.  Picks of the plain entry points are one round and one input, and hold no read_seg (it
+	 * follows from picked) */
 	DevBuf read_seg;                        /* int32 per read, -1 = not picked */
 	std::vector<uint64_t> seg_table;        /* per segment {first pick, picks, first byte, bytes} */
 	uint32_t n_rounds = 1, n_inputs = 1;

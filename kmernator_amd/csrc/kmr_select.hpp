@@ -1,21 +1,19 @@
 /*
  * kmr_select.hpp -- read selection and FASTQ / FASTA output of FilterReads on the device.
  *
- * Replaces selectReads (apps/FilterReads.h:159-279) with max-kmer-output-depth off -- the plain branch here, the partitioned
- * one (--partition-by-depth, --remainder-trim, one output per input file) in the second half of this file:
- * ReadSelector::pickAllPassingReads / pickAllPassingPairs (src/ReadSelector.h:547-596), optimizePickOrder (:1212-1221)
- * and writePicks (:1242-1262) = Read::toFastq / toFasta (src/Sequence.cpp:761-779) of every picked read in ascending read
- * index, over the per-read results of the artifact filter and of scoreAndTrimReads.
+ * Replaces selectReads (apps/FilterReads.h:159-279) with max-kmer-output-depth off, plain or partitioned (--partition-by-depth,
+ * --remainder-trim, one output per input file): ReadSelector::pickAllPassingReads / pickAllPassingPairs (src/ReadSelector.h:547-596),
+ * optimizePickOrder (:1212-1221) and writePicks (:1242-1262) = Read::toFastq / toFasta (src/Sequence.cpp:761-779) of every picked
+ * read in ascending read index, over the per-read results of the artifact filter and of scoreAndTrimReads.
  *
- *   select_count_kernel    per read: isPassingRead of the read and of its mate (:550-568, passesLength :209-228 in float as
- *                          the reference computes it), the pair decision, the printed length of its name, and the exact byte
- *                          count of its record (decimal digits are counted, not printed)
- *   (two exclusive scans: pick index, byte offset)
- *   select_compact_kernel  pick p -> (read index, byte offset of its record); totals and the error word in one block of 24 bytes
+ * The first half of this file is what a record is: isPassingRead (passesLength :209-228 in float as the reference computes it), the
+ * label, the printed length of a name and the exact byte count of a record (decimal digits are counted, not printed), and
  *   select_write_kernel    one wavefront per record: name, label with integer-to-decimal, base slice, shifted quality slice,
  *                          consecutive lanes taking consecutive bytes of the record
  * A second writer, which assembled 16 KiB tiles of the output in LDS and stored them as 16-byte vectors, was measured against this
  * one and lost ("Read selection and output text"); it is not kept.
+ * The second half is which reads are picked and where their records go: one stable partition by (round, input file), of which the
+ * plain selection is the case of one round and one input.
  *
  * The number of launches does not depend on the number of reads.
  */
@@ -58,7 +56,7 @@ __device__ __forceinline__ bool sel_passes_length(float length, uint32_t read_le
 }
 __device__ __forceinline__ bool sel_discarded(const SelectParams &P, uint64_t i) { return P.af_action && P.af_action[i] == 2; }
 /* isPassingRead(readIdx, minimumScore, minimumLength) (:550-557), the thresholds being those of one round of selectReads
- * (P.min_score / P.min_read_length of the plain branch, a row of the round table of the partitioned one) */
+ * (a row of the round table; P.min_score / P.min_read_length where there is one round, kmr_normalize.hpp) */
 __device__ __forceinline__ bool sel_passing(const SelectParams &P, uint64_t i, float min_score, float min_read_length) {
 	if (sel_discarded(P, i)) return false;
 	const uint32_t len = (uint32_t)(P.offsets[i + 1] - P.offsets[i]);
@@ -131,29 +129,6 @@ __device__ __forceinline__ uint32_t sel_measure(const SelectParams &P, uint64_t 
 	return sel_record_bytes(P, nlen, sel_label(P, i, nullptr, false), sel_slice(P, i).len);
 }
 
-__global__ __launch_bounds__(256)
-void select_count_kernel(SelectParams P, uint32_t *pick_flag, uint32_t *rec_len, uint32_t *name_printed, uint8_t *picked, uint32_t *err) {
-	for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < P.n; i += (uint64_t)gridDim.x * blockDim.x) {
-		bool pick = sel_passing(P, i);
-		const int64_t m = P.mate ? P.mate[i] : -1;
-		if (m >= 0) {
-			if ((uint64_t)m >= P.n) atomicOr(err, (uint32_t)SEL_ERR_MATE);
-			else { const bool other = sel_passing(P, (uint64_t)m); pick = P.both_pass ? (pick && other) : (pick || other); }      /* isPassingPair :558-568 */
-		}
-		uint32_t bytes = 0, nlen = 0;
-		if (pick) bytes = sel_measure(P, i, &nlen, err);
-		pick_flag[i] = pick ? 1u : 0u; picked[i] = pick ? 1 : 0; rec_len[i] = bytes; name_printed[i] = nlen;
-	}
-}
-
-/* totals[0] = picks, totals[1] = bytes, totals[2] = error word (written by select_count_kernel) */
-__global__ __launch_bounds__(256)
-void select_compact_kernel(const uint32_t *pick_flag, const uint64_t *pick_scan, const uint64_t *byte_scan, uint64_t n, uint32_t *pick_read, uint64_t *pick_off, uint64_t *totals) {
-	for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
-		if (pick_flag[i]) { const uint64_t p = pick_scan[i]; pick_read[p] = (uint32_t)i; pick_off[p] = byte_scan[i]; }
-	if (blockIdx.x == 0 && threadIdx.x == 0) { pick_off[pick_scan[n]] = byte_scan[n]; totals[0] = pick_scan[n]; totals[1] = byte_scan[n]; }
-}
-
 /* Read i's record of `bytes` bytes, by one wavefront, to dst; s_label: SEL_LABEL_CAP bytes of LDS of this wavefront.
  * Consecutive lanes take consecutive bytes, so the loads from the name, the bases and the qualities and the stores coalesce. */
 __device__ __forceinline__ void sel_emit(const SelectParams &P, uint64_t i, uint32_t nlen, uint32_t bytes, uint8_t *dst, int lane, uint8_t *s_label) {
@@ -197,8 +172,8 @@ void select_write_kernel(SelectParams P, const uint32_t *name_printed, const uin
 	}
 }
 
-/* ---- the partitioned branch of selectReads (apps/FilterReads.h:209-278): --partition-by-depth, --remainder-trim and one output
- * per input file.  A read belongs to the first round of the table (kmr_select_rounds.hpp) whose pair decision picks it -- a pick
+/* ---- the rounds of selectReads (apps/FilterReads.h:209-278): --partition-by-depth, --remainder-trim and one output per input
+ * file; without them one round and one segment.  A read belongs to the first round of the table (kmr_select_rounds.hpp) whose pair decision picks it -- a pick
  * makes a read unavailable to every later round (pickIfNew, src/ReadSelector.h:513-542), and both reads of a pair are picked
  * together -- and to the input file its index falls into.  Segment = round * n_inputs + input; the output is the segments in that
  * order, ascending read index inside each (optimizePickOrder sorts the picks of one round only), which is a stable multi-way

@@ -11,6 +11,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <mutex>
 
 #include "kmr_host.hpp"
@@ -688,6 +689,22 @@ static int select_check_config(kmr_handle *h, const kmr_select_config *c) {
 
 typedef EventTimer<3> SelectTimer;
 
+/* What one of the twelve selecting entry points was called with, by name.  Every array but a text that lies on the device is the
+ * host's; an absent one is null.  The plain and the partitioned four pass mate, the normalizing four the pair list in its place. */
+struct SelectCall {
+	const char *who;
+	bool fused;                                  /* the read_batch forms: the four trim arrays are scored here */
+	const kmr_reads *r;
+	const void *text; uint64_t text_len; bool text_on_device;
+	const int64_t *mate, *read1, *read2; uint64_t n_pairs;
+	const uint8_t *af_action; const uint32_t *af_min, *af_max;
+	const uint32_t *trim_offset, *trim_length; const float *score; const uint8_t *was_trimmed;
+	const uint64_t *input_starts; uint32_t n_inputs;      /* as the caller gave them; the check makes n_inputs 1 for no input_starts */
+	/* by the check of the entry point's config: */
+	const kmr_select_config *cfg; SelRounds R; const kmr_normalize_config *norm;
+	bool plain;                                  /* the picks hold no per-read segments (they follow from the flags) */
+};
+
 /* every pointer is device memory (mate and the three af_* may be null) */
 static SelectParams select_params(kmr_handle *h, const kmr_reads *r, const uint8_t *dtext, uint64_t text_len, const int64_t *dmate, const uint8_t *dact, const uint32_t *dmin,
                                   const uint32_t *dmax, const uint32_t *dto, const uint32_t *dtl, const float *dsc, const uint8_t *dwt, const kmr_select_config *cfg) {
@@ -700,12 +717,69 @@ static SelectParams select_params(kmr_handle *h, const kmr_reads *r, const uint8
 	return P;
 }
 
-/* The second half of a selection: the one copy that brings sizes back -- tot: picks, bytes, the error word and whatever the
- * caller put behind them, n_tot words to host_tot --, then the text of the picks (pread, poff) by select_write_kernel.  The
- * timer's mark 0 is the caller's. */
-static int select_write(kmr_handle *h, Scratch &tmp, const SelectParams &P, const uint32_t *nlen, const uint32_t *pread, const uint64_t *poff, const uint64_t *tot, size_t n_tot,
-                        uint64_t *host_tot, kmr_picks *pk, SelectTimer &timer) {
-	HIPCHK(h, hipMemcpyAsync(host_tot, tot, 8 * n_tot, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
+/* the units of the partition: at most `most` wavefronts -- 4096 over reads, 8192 over the slots of the normalization, whose kernels do
+ * less per item (4 and 8 a SIMD on 256 CUs; each measured against the other and against 1024 and 2048) --, fewer when many
+ * segments make the [segment][unit] matrices large (never above 2^18 entries beyond 1024 units; kmr_tune "partition_units" sets them
+ * for tests and sweeps), each over a multiple of 64 items */
+static void partition_units(const kmr_handle *h, uint64_t n, uint32_t n_segments, uint64_t most, PartitionParams &Q) {
+	most = h->tune.partition_units ? h->tune.partition_units : std::min<uint64_t>(most, std::max<uint64_t>(1024, (1u << 18) / n_segments));
+	Q.per_unit = (((n + most - 1) / most) + SEL_UNIT - 1) / SEL_UNIT * SEL_UNIT;
+	Q.n_units = (uint32_t)((n + Q.per_unit - 1) / Q.per_unit);
+}
+
+/* what partition_run hands to a branch's classification */
+struct PartitionWork {
+	PartitionParams Q;
+	uint8_t *picked; int32_t *read_seg; uint32_t *name_printed;      /* per read */
+	uint64_t n_items; int32_t *item_seg; uint32_t *item_len, *slot_read;      /* per item; read_seg is item_seg where the items are the reads */
+	uint32_t *unit_cnt; unsigned long long *unit_bytes;                  /* [segment][unit] */
+	uint32_t *err; unsigned long long *extra;                            /* the error word; the branch's own counters, zero */
+};
+
+/* A selection from its classification on: the stable partition of the picked items by segment, and their text.  The items are the
+ * reads (the partitioned and the plain entry points), or two slots a read that hold reads (`slots`, the normalizing ones).
+ * `classify` queues the kernels that leave every item's segment (-1: not picked) and record bytes, every picked read's printed name
+ * length, every read's flag and segment, and the picks and bytes of every segment per unit.  After it partition_scan_kernel,
+ * partition_rank_kernel, the call's one copy of sizes -- picks, bytes, the error word, the segment table, n_extra counters of the
+ * branch -- and select_write_kernel.  keep_read_seg: the picks keep the per-read segments. */
+static int partition_run(kmr_handle *h, Scratch &tmp, const SelectParams &P, const SelRounds &R, uint32_t n_inputs, uint32_t n_segments, const uint64_t *dstarts, bool slots,
+                         bool keep_read_seg, uint64_t *extra, size_t n_extra, kmr_picks *pk,
+                         const std::function<int(const PartitionWork &)> &classify) {
+	const uint64_t n = P.n;
+	const uint32_t S = n_segments;
+	pk->n = n; pk->n_rounds = R.n; pk->n_inputs = n_inputs;
+	for (uint32_t r = 0; r < R.n; r++) { pk->round_depth[r] = R.min_score[r]; pk->round_is_remainder[r] = R.is_remainder[r]; }
+	pk->seg_table.assign((size_t)4 * S, 0);
+	h->last_select_ms = h->last_write_ms = 0;
+	if (n == 0) return KMR_OK;
+	PartitionWork W;
+	HIPCHK(h, alloc_n(pk->picked, &W.picked, n));
+	HIPCHK(h, keep_read_seg ? alloc_n(pk->read_seg, &W.read_seg, n) : tmp.take(&W.read_seg, n));
+	if (S == 0) {      /* --partition-by-depth below --min-depth: no round runs */
+		HIPCHK(h, hipMemsetAsync(W.picked, 0, n, h->stream)); HIPCHK(h, hipMemsetAsync(W.read_seg, 0xff, 4 * n, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
+		return KMR_OK;
+	}
+	W.n_items = slots ? 2 * n : n; W.item_seg = W.read_seg; W.slot_read = nullptr;
+	W.Q.input_starts = dstarts; W.Q.n_inputs = n_inputs; W.Q.n_segments = S;
+	partition_units(h, W.n_items, S, slots ? 8192 : 4096, W.Q);
+	const size_t cells = (size_t)S * W.Q.n_units, n_tot = 3 + (size_t)4 * S + n_extra;
+	uint32_t *pread; uint64_t *poff, *tot;
+	if (slots) { HIPCHK(h, tmp.take(&W.item_seg, W.n_items)); HIPCHK(h, tmp.take(&W.slot_read, W.n_items)); }
+	/* pread / poff: an item each -- a pair list that names a read twice (refused below) can fill more than n slots */
+	HIPCHK(h, tmp.take(&W.name_printed, n + W.n_items)); HIPCHK(h, tmp.take(&pread, W.n_items)); HIPCHK(h, tmp.take(&poff, W.n_items + 1));
+	W.item_len = W.name_printed + n;      /* one block */
+	HIPCHK(h, tmp.take(&W.unit_cnt, cells)); HIPCHK(h, tmp.take(&W.unit_bytes, cells)); HIPCHK(h, tmp.take(&tot, n_tot));
+	W.err = (uint32_t *)(tot + 2); W.extra = (unsigned long long *)(tot + 3 + (size_t)4 * S);
+	SelectTimer timer(h->tune.select_timing);
+	timer.mark(0, h->stream);
+	HIPCHK(h, hipMemsetAsync(tot, 0, 8 * n_tot, h->stream));
+	int rc = classify(W); if (rc) return rc;
+	hipLaunchKernelGGL(partition_scan_kernel, dim3(1), dim3(SEL_SCAN_THREADS), 0, h->stream, W.unit_cnt, W.unit_bytes, S, W.Q.n_units, tot + 3, poff, tot);
+	hipLaunchKernelGGL(partition_rank_kernel, dim3(W.Q.n_units), dim3(SEL_UNIT), 0, h->stream, (const int32_t *)W.item_seg, (const uint32_t *)W.item_len, W.n_items, W.Q, (const uint32_t *)W.unit_cnt,
+	                   (const unsigned long long *)W.unit_bytes, pread, poff, (const uint32_t *)W.slot_read);
+	HIPCHK(h, hipGetLastError());
+	std::vector<uint64_t> host_tot(n_tot, 0);
+	HIPCHK(h, hipMemcpyAsync(host_tot.data(), tot, 8 * n_tot, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
 	if (host_tot[2] & SEL_ERR_MATE) return fail(h, KMR_ERR_INVALID_ARG, "a mate index lies outside the batch");
 	if (host_tot[2] & SEL_ERR_NAME) return fail(h, KMR_ERR_INVALID_ARG, NAME_SPAN_ERROR);
 	if (host_tot[2] & SEL_ERR_PAIR) return fail(h, KMR_ERR_INVALID_ARG, "the pair list holds an index outside the batch or a pair without a read");
@@ -714,104 +788,47 @@ static int select_write(kmr_handle *h, Scratch &tmp, const SelectParams &P, cons
 	timer.mark(1, h->stream);
 	if (pk->bytes) {
 		HIPCHK(h, pk->text.alloc((pk->bytes + 15) & ~(uint64_t)15));
-		uint8_t *dout = pk->text.get<uint8_t>();
-		hipLaunchKernelGGL(select_write_kernel, dim3((unsigned)std::min<uint64_t>((pk->n_picked + SEL_WAVES - 1) / SEL_WAVES, (uint64_t)num_cus(h) * 8)), dim3(SEL_THREADS), 0, h->stream, P, nlen, pread, poff, pk->n_picked, dout);
+		hipLaunchKernelGGL(select_write_kernel, dim3((unsigned)std::min<uint64_t>((pk->n_picked + SEL_WAVES - 1) / SEL_WAVES, (uint64_t)num_cus(h) * 8)), dim3(SEL_THREADS), 0, h->stream, P,
+		                   (const uint32_t *)W.name_printed, (const uint32_t *)pread, (const uint64_t *)poff, pk->n_picked, pk->text.get<uint8_t>());
 		HIPCHK(h, hipGetLastError());
 	}
 	timer.mark(2, h->stream);
 	HIPCHK(h, hipStreamSynchronize(h->stream));
 	tmp.done();
 	h->last_select_ms = timer.ms(0, 2); h->last_write_ms = timer.ms(1, 2);
+	std::copy(host_tot.begin() + 3, host_tot.end() - n_extra, pk->seg_table.begin());
+	std::copy(host_tot.end() - n_extra, host_tot.end(), extra);
 	return KMR_OK;
 }
 
-static int select_core(kmr_handle *h, Scratch &tmp, const SelectParams &P, kmr_picks *pk) {
-	const uint64_t n = P.n;
-	pk->n = n; pk->round_depth[0] = P.min_score;
-	h->last_select_ms = h->last_write_ms = 0;
-	if (n == 0) return KMR_OK;
-	uint32_t *flag, *len, *nlen, *pread; uint64_t *pscan, *bscan, *poff, *tot; uint8_t *picked;
-	HIPCHK(h, tmp.take(&flag, n)); HIPCHK(h, tmp.take(&len, n)); HIPCHK(h, tmp.take(&nlen, n)); HIPCHK(h, tmp.take(&pread, n));
-	HIPCHK(h, tmp.take(&pscan, n + 1)); HIPCHK(h, tmp.take(&bscan, n + 1)); HIPCHK(h, tmp.take(&poff, n + 1)); HIPCHK(h, tmp.take(&tot, 3));
-	HIPCHK(h, alloc_n(pk->picked, &picked, n));
-	SelectTimer timer(h->tune.select_timing);
-	timer.mark(0, h->stream);
-	HIPCHK(h, hipMemsetAsync(tot, 0, 24, h->stream));
-	hipLaunchKernelGGL(select_count_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, P, flag, len, nlen, picked, (uint32_t *)(tot + 2));
-	HIPCHK(h, hipGetLastError());
-	int rc = exclusive_scan(h, flag, n, pscan); if (rc) return rc;
-	rc = exclusive_scan(h, len, n, bscan); if (rc) return rc;
-	hipLaunchKernelGGL(select_compact_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, (const uint32_t *)flag, (const uint64_t *)pscan, (const uint64_t *)bscan, n, pread, poff, tot);
-	HIPCHK(h, hipGetLastError());
-	uint64_t totals[3] = {0, 0, 0};
-	return select_write(h, tmp, P, nlen, pread, poff, tot, 3, totals, pk, timer);
-}
-
-/* what the four partitioned entry points add to the arguments of the plain four */
-struct PartitionArgs { const kmr_partition_config *cfg; const uint64_t *input_starts; uint32_t n_inputs; };
-
-/* the units of the partition: at most 8192 wavefronts (8 a SIMD on 256 CUs), fewer when many segments make the [segment][unit]
- * matrices large (never above 2^18 entries beyond 1024 units; kmr_tune "partition_units" caps them for tests), each over a multiple of
- * 64 reads */
-static void partition_units(const kmr_handle *h, uint64_t n, uint32_t n_segments, PartitionParams &Q) {
-	const uint64_t most = h->tune.partition_units ? h->tune.partition_units : std::min<uint64_t>(8192, std::max<uint64_t>(1024, (1u << 18) / n_segments));
-	Q.per_unit = (((n + most - 1) / most) + SEL_UNIT - 1) / SEL_UNIT * SEL_UNIT;
-	Q.n_units = (uint32_t)((n + Q.per_unit - 1) / Q.per_unit);
-}
-
-/* the partitioned branch: P as select_core's (its three thresholds are not read), R the rounds, dstarts the inputs' first reads in
+/* the plain and the partitioned entry points: P's three thresholds are not read, R the rounds, dstarts the inputs' first reads in
  * device memory (null for one input) */
-static int partition_core(kmr_handle *h, Scratch &tmp, const SelectParams &P, const SelRounds &R, const uint64_t *dstarts, uint32_t n_inputs, kmr_picks *pk) {
-	const uint64_t n = P.n;
-	const uint32_t S = R.n * n_inputs;
-	pk->n = n; pk->n_rounds = R.n; pk->n_inputs = n_inputs;
-	for (uint32_t r = 0; r < R.n; r++) { pk->round_depth[r] = R.min_score[r]; pk->round_is_remainder[r] = R.is_remainder[r]; }
-	pk->seg_table.assign((size_t)4 * S, 0);
-	h->last_select_ms = h->last_write_ms = 0;
-	if (n == 0) return KMR_OK;
-	uint8_t *picked; int32_t *seg;
-	HIPCHK(h, alloc_n(pk->picked, &picked, n)); HIPCHK(h, alloc_n(pk->read_seg, &seg, n));
-	if (S == 0) {      /* --partition-by-depth below --min-depth: no round runs */
-		HIPCHK(h, hipMemsetAsync(picked, 0, n, h->stream)); HIPCHK(h, hipMemsetAsync(seg, 0xff, 4 * n, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
-		return KMR_OK;
-	}
-	PartitionParams Q;
-	Q.input_starts = dstarts; Q.n_inputs = n_inputs; Q.n_segments = S;
-	partition_units(h, n, S, Q);
-	const size_t cells = (size_t)S * Q.n_units;
-	uint32_t *len, *nlen, *pread, *ucnt; uint64_t *poff, *tot; unsigned long long *ubytes;
-	HIPCHK(h, tmp.take(&len, n)); HIPCHK(h, tmp.take(&nlen, n)); HIPCHK(h, tmp.take(&pread, n)); HIPCHK(h, tmp.take(&poff, n + 1));
-	HIPCHK(h, tmp.take(&ucnt, cells)); HIPCHK(h, tmp.take(&ubytes, cells)); HIPCHK(h, tmp.take(&tot, 3 + (size_t)4 * S));
-	SelectTimer timer(h->tune.select_timing);
-	timer.mark(0, h->stream);
-	HIPCHK(h, hipMemsetAsync(tot, 0, 24, h->stream));
-	hipLaunchKernelGGL(partition_classify_kernel, dim3(Q.n_units), dim3(SEL_UNIT), 0, h->stream, P, R, Q, seg, len, nlen, picked, ucnt, ubytes, (uint32_t *)(tot + 2));
-	hipLaunchKernelGGL(partition_scan_kernel, dim3(1), dim3(SEL_SCAN_THREADS), 0, h->stream, ucnt, ubytes, S, Q.n_units, tot + 3, poff, tot);
-	hipLaunchKernelGGL(partition_rank_kernel, dim3(Q.n_units), dim3(SEL_UNIT), 0, h->stream, (const int32_t *)seg, (const uint32_t *)len, n, Q, (const uint32_t *)ucnt, (const unsigned long long *)ubytes, pread, poff, (const uint32_t *)nullptr);
-	HIPCHK(h, hipGetLastError());
-	std::vector<uint64_t> host_tot(3 + (size_t)4 * S, 0);
-	int rc = select_write(h, tmp, P, nlen, pread, poff, tot, host_tot.size(), host_tot.data(), pk, timer); if (rc) return rc;
-	std::copy(host_tot.begin() + 3, host_tot.end(), pk->seg_table.begin());
-	return KMR_OK;
+static int partition_core(kmr_handle *h, Scratch &tmp, const SelectParams &P, const SelRounds &R, const uint64_t *dstarts, uint32_t n_inputs, bool keep_read_seg, kmr_picks *pk) {
+	return partition_run(h, tmp, P, R, n_inputs, R.n * n_inputs, dstarts, false, keep_read_seg, nullptr, 0, pk, [&](const PartitionWork &W) -> int {
+		hipLaunchKernelGGL(partition_classify_kernel, dim3(W.Q.n_units), dim3(SEL_UNIT), 0, h->stream, P, R, W.Q, W.read_seg, W.item_len, W.name_printed, W.picked, W.unit_cnt, W.unit_bytes, W.err);
+		return 0;
+	});
+}
+
+/* the one round of a kmr_select_config (checked): what the plain entry points pick, and the partitioned ones with partition_by_depth 0 */
+static void select_one_round(const kmr_select_config &c, SelRounds *R) {
+	R->n = 1; R->min_score[0] = (float)c.minimum_score; R->min_read_length[0] = c.min_read_length; R->both_pass[0] = c.both_pass ? 1 : 0; R->is_remainder[0] = 0;
 }
 
 /* cfg, the input boundaries and the table of rounds, all without a device.  *n_inputs: 1 for input_starts NULL */
-static int partition_check(kmr_handle *h, const PartitionArgs *a, SelRounds *R, uint32_t *n_inputs) {
-	const kmr_partition_config *c = a->cfg;
+static int partition_check(kmr_handle *h, const kmr_partition_config *c, const uint64_t *input_starts, SelRounds *R, uint32_t *n_inputs) {
 	if (!c) return fail(h, KMR_ERR_INVALID_ARG, "kmr_partition_config: NULL");
 	if (c->struct_size != sizeof(kmr_partition_config)) return fail(h, KMR_ERR_INVALID_ARG, "kmr_partition_config: struct_size " + std::to_string(c->struct_size) + " is not " + std::to_string(sizeof(kmr_partition_config)));
 	int rc = select_check_config(h, &c->select); if (rc) return rc;
-	*n_inputs = 1;
-	if (a->input_starts) {
-		if (a->n_inputs == 0) return fail(h, KMR_ERR_INVALID_ARG, "input_starts without n_inputs");
+	if (input_starts) {
+		if (*n_inputs == 0) return fail(h, KMR_ERR_INVALID_ARG, "input_starts without n_inputs");
 		bool ok;
-		const uint32_t at = sel_check_input_starts(a->input_starts, a->n_inputs, &ok);
+		const uint32_t at = sel_check_input_starts(input_starts, *n_inputs, &ok);
 		if (!ok) return fail(h, KMR_ERR_INVALID_ARG, "input_starts[" + std::to_string(at) + "]: the read indices start at 0 and ascend");
-		*n_inputs = a->n_inputs;
-	} else if (a->n_inputs > 1) return fail(h, KMR_ERR_INVALID_ARG, "input_starts is NULL for " + std::to_string(a->n_inputs) + " inputs");
-	if (c->partition_by_depth == 0) {      /* one round with the plain branch's own thresholds: kmr_select_reads' picks */
-		R->n = 1; R->min_score[0] = (float)c->select.minimum_score; R->min_read_length[0] = c->select.min_read_length; R->both_pass[0] = c->select.both_pass ? 1 : 0; R->is_remainder[0] = 0;
-	} else {
+	} else if (*n_inputs > 1) return fail(h, KMR_ERR_INVALID_ARG, "input_starts is NULL for " + std::to_string(*n_inputs) + " inputs");
+	else *n_inputs = 1;
+	if (c->partition_by_depth == 0) select_one_round(c->select, R);
+	else {
 		const double d = c->select.minimum_score;      /* selectReads takes minDepth as an unsigned int */
 		if (!(d >= 0.0 && d <= 4294967295.0) || d != std::floor(d)) return fail(h, KMR_ERR_INVALID_ARG, "kmr_partition_config: with partition_by_depth set, minimum_score is a whole number below 2^32");
 		if (sel_round_table((unsigned int)d, c->partition_by_depth, c->remainder_trim, c->select.min_read_length, c->select.both_pass != 0, *R))
@@ -823,160 +840,146 @@ static int partition_check(kmr_handle *h, const PartitionArgs *a, SelRounds *R, 
 }
 
 /* ---- the normalizing branch (kmr_normalize.hpp) ---------------- */
-/* what the four normalizing entry points add to the arguments of the plain four, in place of mate */
-struct NormalizeArgs { const kmr_normalize_config *cfg; const int64_t *read1, *read2; uint64_t n_pairs; const uint64_t *input_starts; uint32_t n_inputs; };
-
 /* cfg, the pair list's shape and the input boundaries, all without a device.  R: the one round.  *n_inputs: 1 for input_starts NULL */
-static int normalize_check(kmr_handle *h, const NormalizeArgs *a, SelRounds *R, uint32_t *n_inputs) {
-	const kmr_normalize_config *c = a->cfg;
+static int normalize_check(kmr_handle *h, const kmr_normalize_config *c, const int64_t *read1, const int64_t *read2, const uint64_t *input_starts, SelRounds *R, uint32_t *n_inputs) {
 	if (!c) return fail(h, KMR_ERR_INVALID_ARG, "kmr_normalize_config: NULL");
 	if (c->struct_size != sizeof(kmr_normalize_config)) return fail(h, KMR_ERR_INVALID_ARG, "kmr_normalize_config: struct_size " + std::to_string(c->struct_size) + " is not " + std::to_string(sizeof(kmr_normalize_config)));
 	if (c->method != 0) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_normalize_config: method 0 (RANDOM) only; OPTIMAL is a serial greedy heap over a shared count map");
 	if (c->use_logscale) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_normalize_config: use_logscale (the reference's expression has no pinned value)");
 	if (c->target_depth == 0) return fail(h, KMR_ERR_INVALID_ARG, "kmr_normalize_config: target_depth must be above 0");
-	if ((a->read1 != nullptr) != (a->read2 != nullptr)) return fail(h, KMR_ERR_INVALID_ARG, "the pair list: read1 and read2 go together");
+	if ((read1 != nullptr) != (read2 != nullptr)) return fail(h, KMR_ERR_INVALID_ARG, "the pair list: read1 and read2 go together");
 	kmr_partition_config pc;
 	kmr_partition_config_init(&pc);
 	pc.select = c->select;
-	const PartitionArgs pa = {&pc, a->input_starts, a->n_inputs};
-	return partition_check(h, &pa, R, n_inputs);
+	return partition_check(h, &pc, input_starts, R, n_inputs);
 }
 
-/* P as select_core's with mate null; dr1 / dr2 the pair list and dstarts the inputs' first reads in device memory (null for none) */
-static int normalize_core(kmr_handle *h, Scratch &tmp, const SelectParams &P, const kmr_normalize_config *c, const int64_t *dr1, const int64_t *dr2, uint64_t n_pairs,
+/* P with mate null; dr1 / dr2 the pair list and dstarts the inputs' first reads in device memory (null for none).  A segment is
+ * an input */
+static int normalize_core(kmr_handle *h, Scratch &tmp, const SelectParams &P, const SelRounds &R, const kmr_normalize_config *c, const int64_t *dr1, const int64_t *dr2, uint64_t n_pairs,
                           const uint64_t *dstarts, uint32_t n_inputs, kmr_picks *pk) {
-	const uint64_t n = P.n, n_slots = 2 * n;
-	const uint32_t S = n_inputs;
-	pk->n = n; pk->n_rounds = 1; pk->n_inputs = n_inputs; pk->normalized = true;
-	pk->round_depth[0] = P.min_score; pk->round_is_remainder[0] = 0;
-	pk->seg_table.assign((size_t)4 * S, 0);
-	h->last_select_ms = h->last_write_ms = 0;
-	if (n == 0) return KMR_OK;
-	uint8_t *picked; int32_t *rseg;
-	HIPCHK(h, alloc_n(pk->picked, &picked, n)); HIPCHK(h, alloc_n(pk->read_seg, &rseg, n));
+	const uint64_t n = P.n;
 	NormalizeParams N;
 	N.read1 = dr1; N.read2 = dr2; N.n_pairs = n_pairs; N.target = c->target_depth; N.seed = c->seed; N.first_global = c->first_global_read_idx; N.by_pair = c->by_pair ? 1u : 0u;
-	PartitionParams Q;
-	Q.input_starts = dstarts; Q.n_inputs = n_inputs; Q.n_segments = S;
-	partition_units(h, n_slots, S, Q);
-	const size_t cells = (size_t)S * Q.n_units, n_tot = 3 + (size_t)4 * S + 3;
-	uint32_t *zeroed, *slot_read, *nlen, *pread, *ucnt; int32_t *slot_seg; uint64_t *poff, *tot; unsigned long long *ubytes;
-	HIPCHK(h, tmp.take(&zeroed, 3 * n)); HIPCHK(h, tmp.take(&slot_read, n_slots)); HIPCHK(h, tmp.take(&slot_seg, n_slots));
-	/* pread / poff: a slot each, not a read each -- a list that names a read twice (refused below) can fill more than n slots */
-	HIPCHK(h, tmp.take(&nlen, n)); HIPCHK(h, tmp.take(&pread, n_slots)); HIPCHK(h, tmp.take(&poff, n_slots + 1));
-	HIPCHK(h, tmp.take(&ucnt, cells)); HIPCHK(h, tmp.take(&ubytes, cells)); HIPCHK(h, tmp.take(&tot, n_tot));
-	uint32_t *named = zeroed, *slot_len = zeroed + n;      /* one block, one memset: reads named by a pair; record bytes of a slot */
-	SelectTimer timer(h->tune.select_timing);
-	timer.mark(0, h->stream);
-	HIPCHK(h, hipMemsetAsync(tot, 0, 8 * n_tot, h->stream)); HIPCHK(h, hipMemsetAsync(zeroed, 0, 12 * n, h->stream));
-	HIPCHK(h, hipMemsetAsync(slot_seg, 0xff, 4 * n_slots, h->stream)); HIPCHK(h, hipMemsetAsync(rseg, 0xff, 4 * n, h->stream)); HIPCHK(h, hipMemsetAsync(picked, 0, n, h->stream));
-	uint32_t *err = (uint32_t *)(tot + 2);
-	unsigned long long *counters = (unsigned long long *)(tot + 3 + (size_t)4 * S);
-	if (n_pairs) hipLaunchKernelGGL(normalize_mark_kernel, dim3(grid_for(n_pairs)), dim3(256), 0, h->stream, N, n, named, err);
-	hipLaunchKernelGGL(normalize_classify_kernel, dim3(grid_for(n_pairs + n)), dim3(256), 0, h->stream, P, N, Q, (const uint32_t *)named, slot_read, slot_seg, slot_len, nlen, picked, rseg, counters, err);
-	hipLaunchKernelGGL(normalize_count_kernel, dim3(Q.n_units), dim3(SEL_UNIT), 0, h->stream, (const int32_t *)slot_seg, (const uint32_t *)slot_len, n_slots, Q, ucnt, ubytes);
-	hipLaunchKernelGGL(partition_scan_kernel, dim3(1), dim3(SEL_SCAN_THREADS), 0, h->stream, ucnt, ubytes, S, Q.n_units, tot + 3, poff, tot);
-	hipLaunchKernelGGL(partition_rank_kernel, dim3(Q.n_units), dim3(SEL_UNIT), 0, h->stream, (const int32_t *)slot_seg, (const uint32_t *)slot_len, n_slots, Q, (const uint32_t *)ucnt, (const unsigned long long *)ubytes, pread, poff, (const uint32_t *)slot_read);
-	HIPCHK(h, hipGetLastError());
-	std::vector<uint64_t> host_tot(n_tot, 0);
-	int rc = select_write(h, tmp, P, nlen, pread, poff, tot, n_tot, host_tot.data(), pk, timer); if (rc) return rc;
-	std::copy(host_tot.begin() + 3, host_tot.begin() + 3 + (size_t)4 * S, pk->seg_table.begin());
-	std::copy(host_tot.end() - 3, host_tot.end(), pk->norm_info);
-	return KMR_OK;
+	uint32_t *named = nullptr;      /* reads named by a pair */
+	if (n) HIPCHK(h, tmp.take(&named, n));
+	pk->normalized = true;
+	return partition_run(h, tmp, P, R, n_inputs, n_inputs, dstarts, true, true, pk->norm_info, 3, pk, [&](const PartitionWork &W) -> int {
+		HIPCHK(h, hipMemsetAsync(named, 0, 4 * n, h->stream)); HIPCHK(h, hipMemsetAsync(W.item_seg, 0xff, 4 * W.n_items, h->stream));
+		HIPCHK(h, hipMemsetAsync(W.read_seg, 0xff, 4 * n, h->stream)); HIPCHK(h, hipMemsetAsync(W.picked, 0, n, h->stream));
+		if (n_pairs) hipLaunchKernelGGL(normalize_mark_kernel, dim3(grid_for(n_pairs)), dim3(256), 0, h->stream, N, n, named, W.err);
+		hipLaunchKernelGGL(normalize_classify_kernel, dim3(grid_for(n_pairs + n)), dim3(256), 0, h->stream, P, N, W.Q, (const uint32_t *)named, W.slot_read, W.item_seg, W.item_len, W.name_printed, W.picked,
+		                   W.read_seg, W.extra, W.err);
+		hipLaunchKernelGGL(normalize_count_kernel, dim3(W.Q.n_units), dim3(SEL_UNIT), 0, h->stream, (const int32_t *)W.item_seg, (const uint32_t *)W.item_len, W.n_items, W.Q, W.unit_cnt, W.unit_bytes);
+		return 0;
+	});
 }
 
-static int select_check_args(kmr_handle *h, const kmr_reads *r, const void *text, uint64_t text_len, const uint8_t *af_action, const uint32_t *af_min, const uint32_t *af_max,
-                             const kmr_select_config *cfg, kmr_picks **out, const char *who) {
+static int select_check_args(kmr_handle *h, const SelectCall &c, kmr_picks **out) {
+	const std::string who = c.who;
 	if (out) *out = nullptr;
-	int rc = select_check_config(h, cfg); if (rc) return rc;
-	if (!h) return fail(h, KMR_ERR_INVALID_ARG, std::string(who) + ": NULL handle");
-	if (!r || !out || (text_len && !text)) return fail(h, KMR_ERR_INVALID_ARG, std::string(who) + ": NULL argument");
-	if ((af_action != nullptr) != (af_min != nullptr) || (af_action != nullptr) != (af_max != nullptr)) return fail(h, KMR_ERR_INVALID_ARG, std::string(who) + ": af_action, af_min_pass and af_max_pass go together");
-	if (r->device != h->device) return fail(h, KMR_ERR_INVALID_ARG, "read batch lives on another device");
-	if (r->n >= 0xffffffffull) return fail(h, KMR_ERR_UNSUPPORTED, std::string(who) + ": a batch holds fewer than 2^32 - 1 reads (pick indices are 32-bit)");
+	int rc = select_check_config(h, c.cfg); if (rc) return rc;
+	if (!h) return fail(h, KMR_ERR_INVALID_ARG, who + ": NULL handle");
+	if (!c.r || !out || (c.text_len && !c.text)) return fail(h, KMR_ERR_INVALID_ARG, who + ": NULL argument");
+	if ((c.af_action != nullptr) != (c.af_min != nullptr) || (c.af_action != nullptr) != (c.af_max != nullptr)) return fail(h, KMR_ERR_INVALID_ARG, who + ": af_action, af_min_pass and af_max_pass go together");
+	if (c.r->device != h->device) return fail(h, KMR_ERR_INVALID_ARG, "read batch lives on another device");
+	if (c.r->n >= 0xffffffffull) return fail(h, KMR_ERR_UNSUPPORTED, who + ": a batch holds fewer than 2^32 - 1 reads (pick indices are 32-bit)");
+	if (c.input_starts && c.input_starts[c.n_inputs] != c.r->n)
+		return fail(h, KMR_ERR_INVALID_ARG, who + ": input_starts ends at " + std::to_string(c.input_starts[c.n_inputs]) + ", the batch holds " + std::to_string(c.r->n) + " reads");
+	if (c.read1 && c.n_pairs && !c.r->n) return fail(h, KMR_ERR_INVALID_ARG, who + ": a pair list for an empty batch");
+	if (c.fused) { if (!h->finalized) return fail(h, KMR_ERR_STATE, who + " before kmr_finalize"); }
+	else if (c.r->n && (!c.trim_offset || !c.trim_length || !c.score || !c.was_trimmed)) return fail(h, KMR_ERR_INVALID_ARG, who + ": NULL argument");
 	return 0;
 }
 
-/* text_on_device: `text` is device memory already (the other arrays are the host's) */
-static int select_reads_any(kmr_handle *h, const kmr_reads *r, const void *text, uint64_t text_len, bool text_on_device, const int64_t *mate, const uint8_t *af_action,
-                            const uint32_t *af_min, const uint32_t *af_max, const uint32_t *trim_offset, const uint32_t *trim_length, const float *score,
-                            const uint8_t *was_trimmed, const kmr_select_config *cfg, kmr_picks **out, bool fused, const char *who, const PartitionArgs *part = nullptr,
-                            const NormalizeArgs *norm = nullptr) {
-	SelRounds R; uint32_t n_inputs = 1;
-	int rc;
-	if (part) {
-		if (out) *out = nullptr;
-		rc = partition_check(h, part, &R, &n_inputs); if (rc) return rc;
-		cfg = &part->cfg->select;
-	} else if (norm) {
-		if (out) *out = nullptr;
-		rc = normalize_check(h, norm, &R, &n_inputs); if (rc) return rc;
-		cfg = &norm->cfg->select;
-	}
-	rc = select_check_args(h, r, text, text_len, af_action, af_min, af_max, cfg, out, who); if (rc) return rc;
-	const uint64_t *starts = part ? part->input_starts : (norm ? norm->input_starts : nullptr);
-	if (starts && starts[n_inputs] != r->n)
-		return fail(h, KMR_ERR_INVALID_ARG, std::string(who) + ": input_starts ends at " + std::to_string(starts[n_inputs]) + ", the batch holds " + std::to_string(r->n) + " reads");
-	const uint64_t n_pairs = norm && norm->read1 ? norm->n_pairs : 0;
-	if (n_pairs && !r->n) return fail(h, KMR_ERR_INVALID_ARG, std::string(who) + ": a pair list for an empty batch");
-	if (fused) { if (!h->finalized) return fail(h, KMR_ERR_STATE, std::string(who) + " before kmr_finalize"); }
-	else if (r->n && (!trim_offset || !trim_length || !score || !was_trimmed)) return fail(h, KMR_ERR_INVALID_ARG, std::string(who) + ": NULL argument");
+/* a call whose config is checked: the arguments to the device, the scores of the fused form, the pipeline */
+static int select_run(kmr_handle *h, const SelectCall &c, kmr_picks **out) {
+	int rc = select_check_args(h, c, out); if (rc) return rc;
 	hipSetDevice(h->device);
-	const uint64_t n = r->n;
+	const kmr_reads *r = c.r;
+	const uint64_t n = r->n, n_pairs = c.read1 ? c.n_pairs : 0;
 	auto pk = make_result<kmr_picks>(h);      /* (ahead of tmp, as in every stage: a failed call waits for the stream before the result's buffers go too) */
 	Scratch tmp(h);
-	const uint8_t *dtext, *dact, *dwt = nullptr; const int64_t *dmate; const uint32_t *dmin, *dmax, *dto = nullptr, *dtl = nullptr; const float *dsc = nullptr;
-	rc = to_device(h, tmp, (const uint8_t *)text, text_len, &dtext, text_on_device); if (rc) return rc;
-	rc = to_device(h, tmp, mate, n, &dmate); if (rc) return rc;
-	rc = to_device(h, tmp, af_action, n, &dact); if (rc) return rc;
-	rc = to_device(h, tmp, af_min, n, &dmin); if (rc) return rc;
-	rc = to_device(h, tmp, af_max, n, &dmax); if (rc) return rc;
+	const uint8_t *dtext, *dact, *dwt = nullptr; const int64_t *dmate, *dr1, *dr2; const uint32_t *dmin, *dmax, *dto = nullptr, *dtl = nullptr; const float *dsc = nullptr; const uint64_t *dstarts;
+	rc = to_device(h, tmp, (const uint8_t *)c.text, c.text_len, &dtext, c.text_on_device); if (rc) return rc;
+	rc = to_device(h, tmp, c.mate, n, &dmate); if (rc) return rc;
+	rc = to_device(h, tmp, c.af_action, n, &dact); if (rc) return rc;
+	rc = to_device(h, tmp, c.af_min, n, &dmin); if (rc) return rc;
+	rc = to_device(h, tmp, c.af_max, n, &dmax); if (rc) return rc;
 	h->last_score_ms = 0;
-	if (fused && n) {
+	if (c.fused && n) {
 		SelectTimer timer(h->tune.select_timing);
 		timer.mark(0, h->stream);
 		ScoreDev sd;
-		rc = score_reads_core(h, r->bases.get<uint8_t>(), r->offsets.get<uint64_t>(), n, cfg->minimum_score, (int)cfg->scoring_type, nullptr, nullptr, nullptr, nullptr, &sd); if (rc) return rc;
+		rc = score_reads_core(h, r->bases.get<uint8_t>(), r->offsets.get<uint64_t>(), n, c.cfg->minimum_score, (int)c.cfg->scoring_type, nullptr, nullptr, nullptr, nullptr, &sd); if (rc) return rc;
 		timer.mark(1, h->stream);
 		if (timer.on) { HIPCHK(h, hipStreamSynchronize(h->stream)); h->last_score_ms = timer.ms(0, 1); }
 		dto = sd.trim_offset; dtl = sd.trim_length; dsc = sd.score; dwt = sd.was_trimmed;
-	} else if (!fused) {
-		rc = to_device(h, tmp, trim_offset, n, &dto); if (rc) return rc;
-		rc = to_device(h, tmp, trim_length, n, &dtl); if (rc) return rc;
-		rc = to_device(h, tmp, score, n, &dsc); if (rc) return rc;
-		rc = to_device(h, tmp, was_trimmed, n, &dwt); if (rc) return rc;
+	} else if (!c.fused) {
+		rc = to_device(h, tmp, c.trim_offset, n, &dto); if (rc) return rc;
+		rc = to_device(h, tmp, c.trim_length, n, &dtl); if (rc) return rc;
+		rc = to_device(h, tmp, c.score, n, &dsc); if (rc) return rc;
+		rc = to_device(h, tmp, c.was_trimmed, n, &dwt); if (rc) return rc;
 	}
-	const SelectParams P = select_params(h, r, dtext, text_len, dmate, dact, dmin, dmax, dto, dtl, dsc, dwt, cfg);
-	if (part || norm) {
-		const uint64_t *dstarts = nullptr;
-		if (n_inputs > 1) { rc = to_device(h, tmp, starts, (uint64_t)n_inputs + 1, &dstarts); if (rc) return rc; }
-		if (norm) {
-			const int64_t *dr1 = nullptr, *dr2 = nullptr;
-			if (n_pairs) { rc = to_device(h, tmp, norm->read1, n_pairs, &dr1); if (rc) return rc; rc = to_device(h, tmp, norm->read2, n_pairs, &dr2); if (rc) return rc; }
-			rc = normalize_core(h, tmp, P, norm->cfg, dr1, dr2, n_pairs, dstarts, n_inputs, pk.get());
-		} else rc = partition_core(h, tmp, P, R, dstarts, n_inputs, pk.get());
-	} else rc = select_core(h, tmp, P, pk.get());
+	rc = to_device(h, tmp, c.n_inputs > 1 ? c.input_starts : nullptr, (uint64_t)c.n_inputs + 1, &dstarts); if (rc) return rc;
+	rc = to_device(h, tmp, c.read1, n_pairs, &dr1); if (rc) return rc;
+	rc = to_device(h, tmp, c.read2, n_pairs, &dr2); if (rc) return rc;
+	const SelectParams P = select_params(h, r, dtext, c.text_len, dmate, dact, dmin, dmax, dto, dtl, dsc, dwt, c.cfg);
+	if (c.norm) rc = normalize_core(h, tmp, P, c.R, c.norm, dr1, dr2, n_pairs, dstarts, c.n_inputs, pk.get());
+	else rc = partition_core(h, tmp, P, c.R, dstarts, c.n_inputs, !c.plain, pk.get());
 	if (!rc) *out = pk.release();
 	return rc;
+}
+
+/* the three kinds of entry point: each checks its config, which gives the call its rounds, and runs the call */
+static int select_plain(kmr_handle *h, SelectCall &c, const kmr_select_config *cfg, kmr_picks **out) {
+	if (out) *out = nullptr;
+	int rc = select_check_config(h, cfg); if (rc) return rc;
+	c.cfg = cfg; c.plain = true; c.n_inputs = 1;
+	select_one_round(*cfg, &c.R);
+	return select_run(h, c, out);
+}
+static int select_partitioned(kmr_handle *h, SelectCall &c, const kmr_partition_config *cfg, kmr_picks **out) {
+	if (out) *out = nullptr;
+	int rc = partition_check(h, cfg, c.input_starts, &c.R, &c.n_inputs); if (rc) return rc;
+	c.cfg = &cfg->select;
+	return select_run(h, c, out);
+}
+static int select_normalized(kmr_handle *h, SelectCall &c, const kmr_normalize_config *cfg, kmr_picks **out) {
+	if (out) *out = nullptr;
+	int rc = normalize_check(h, cfg, c.read1, c.read2, c.input_starts, &c.R, &c.n_inputs); if (rc) return rc;
+	c.cfg = &cfg->select; c.norm = cfg;
+	return select_run(h, c, out);
 }
 
 int kmr_select_reads(kmr_handle *h, const kmr_reads *reads, const char *text, uint64_t text_len, const int64_t *mate, const uint8_t *af_action, const uint32_t *af_min_pass,
                      const uint32_t *af_max_pass, const uint32_t *trim_offset, const uint32_t *trim_length, const float *score, const uint8_t *was_trimmed,
                      const kmr_select_config *cfg, kmr_picks **out) {
-	return select_reads_any(h, reads, text, text_len, false, mate, af_action, af_min_pass, af_max_pass, trim_offset, trim_length, score, was_trimmed, cfg, out, false, "kmr_select_reads");
+	SelectCall c = {};
+	c.who = "kmr_select_reads"; c.r = reads; c.text = text; c.text_len = text_len; c.mate = mate; c.af_action = af_action; c.af_min = af_min_pass; c.af_max = af_max_pass;
+	c.trim_offset = trim_offset; c.trim_length = trim_length; c.score = score; c.was_trimmed = was_trimmed;
+	return select_plain(h, c, cfg, out);
 }
 int kmr_select_reads_dev(kmr_handle *h, const kmr_reads *reads, const void *dev_text, uint64_t text_len, const int64_t *mate, const uint8_t *af_action, const uint32_t *af_min_pass,
                          const uint32_t *af_max_pass, const uint32_t *trim_offset, const uint32_t *trim_length, const float *score, const uint8_t *was_trimmed,
                          const kmr_select_config *cfg, kmr_picks **out) {
-	return select_reads_any(h, reads, dev_text, text_len, true, mate, af_action, af_min_pass, af_max_pass, trim_offset, trim_length, score, was_trimmed, cfg, out, false, "kmr_select_reads_dev");
+	SelectCall c = {};
+	c.who = "kmr_select_reads_dev"; c.r = reads; c.text = dev_text; c.text_len = text_len; c.text_on_device = true; c.mate = mate; c.af_action = af_action; c.af_min = af_min_pass; c.af_max = af_max_pass;
+	c.trim_offset = trim_offset; c.trim_length = trim_length; c.score = score; c.was_trimmed = was_trimmed;
+	return select_plain(h, c, cfg, out);
 }
 int kmr_filter_read_batch(kmr_handle *h, const kmr_reads *reads, const char *text, uint64_t text_len, const int64_t *mate, const uint8_t *af_action, const uint32_t *af_min_pass,
                           const uint32_t *af_max_pass, const kmr_select_config *cfg, kmr_picks **out) {
-	return select_reads_any(h, reads, text, text_len, false, mate, af_action, af_min_pass, af_max_pass, nullptr, nullptr, nullptr, nullptr, cfg, out, true, "kmr_filter_read_batch");
+	SelectCall c = {};
+	c.who = "kmr_filter_read_batch"; c.fused = true; c.r = reads; c.text = text; c.text_len = text_len; c.mate = mate; c.af_action = af_action; c.af_min = af_min_pass; c.af_max = af_max_pass;
+	return select_plain(h, c, cfg, out);
 }
 int kmr_filter_read_batch_dev(kmr_handle *h, const kmr_reads *reads, const void *dev_text, uint64_t text_len, const int64_t *mate, const uint8_t *af_action, const uint32_t *af_min_pass,
                               const uint32_t *af_max_pass, const kmr_select_config *cfg, kmr_picks **out) {
-	return select_reads_any(h, reads, dev_text, text_len, true, mate, af_action, af_min_pass, af_max_pass, nullptr, nullptr, nullptr, nullptr, cfg, out, true, "kmr_filter_read_batch_dev");
+	SelectCall c = {};
+	c.who = "kmr_filter_read_batch_dev"; c.fused = true; c.r = reads; c.text = dev_text; c.text_len = text_len; c.text_on_device = true; c.mate = mate;
+	c.af_action = af_action; c.af_min = af_min_pass; c.af_max = af_max_pass;
+	return select_plain(h, c, cfg, out);
 }
 
 /* ---- the partitioned branch: the same four with the rounds of kmr_partition_config and the inputs' boundaries ---------------- */
@@ -990,9 +993,8 @@ int kmr_partition_config_init(kmr_partition_config *c) {
 	return KMR_OK;
 }
 int kmr_partition_rounds(const kmr_partition_config *cfg, uint32_t *n_rounds, float *round_depth, float *round_min_read_length, uint32_t *round_both_pass, uint8_t *round_is_remainder) {
-	SelRounds R; uint32_t n_inputs;
-	const PartitionArgs a = {cfg, nullptr, 0};
-	int rc = partition_check(nullptr, &a, &R, &n_inputs); if (rc) return rc;
+	SelRounds R; uint32_t n_inputs = 0;
+	int rc = partition_check(nullptr, cfg, nullptr, &R, &n_inputs); if (rc) return rc;
 	if (n_rounds) *n_rounds = R.n;
 	for (uint32_t r = 0; r < R.n; r++) {
 		if (round_depth) round_depth[r] = R.min_score[r]; if (round_min_read_length) round_min_read_length[r] = R.min_read_length[r];
@@ -1003,24 +1005,32 @@ int kmr_partition_rounds(const kmr_partition_config *cfg, uint32_t *n_rounds, fl
 int kmr_partition_reads(kmr_handle *h, const kmr_reads *reads, const char *text, uint64_t text_len, const int64_t *mate, const uint8_t *af_action, const uint32_t *af_min_pass,
                         const uint32_t *af_max_pass, const uint32_t *trim_offset, const uint32_t *trim_length, const float *score, const uint8_t *was_trimmed,
                         const uint64_t *input_starts, uint32_t n_inputs, const kmr_partition_config *cfg, kmr_picks **out) {
-	const PartitionArgs a = {cfg, input_starts, n_inputs};
-	return select_reads_any(h, reads, text, text_len, false, mate, af_action, af_min_pass, af_max_pass, trim_offset, trim_length, score, was_trimmed, nullptr, out, false, "kmr_partition_reads", &a);
+	SelectCall c = {};
+	c.who = "kmr_partition_reads"; c.r = reads; c.text = text; c.text_len = text_len; c.mate = mate; c.af_action = af_action; c.af_min = af_min_pass; c.af_max = af_max_pass;
+	c.trim_offset = trim_offset; c.trim_length = trim_length; c.score = score; c.was_trimmed = was_trimmed; c.input_starts = input_starts; c.n_inputs = n_inputs;
+	return select_partitioned(h, c, cfg, out);
 }
 int kmr_partition_reads_dev(kmr_handle *h, const kmr_reads *reads, const void *dev_text, uint64_t text_len, const int64_t *mate, const uint8_t *af_action, const uint32_t *af_min_pass,
                             const uint32_t *af_max_pass, const uint32_t *trim_offset, const uint32_t *trim_length, const float *score, const uint8_t *was_trimmed,
                             const uint64_t *input_starts, uint32_t n_inputs, const kmr_partition_config *cfg, kmr_picks **out) {
-	const PartitionArgs a = {cfg, input_starts, n_inputs};
-	return select_reads_any(h, reads, dev_text, text_len, true, mate, af_action, af_min_pass, af_max_pass, trim_offset, trim_length, score, was_trimmed, nullptr, out, false, "kmr_partition_reads_dev", &a);
+	SelectCall c = {};
+	c.who = "kmr_partition_reads_dev"; c.r = reads; c.text = dev_text; c.text_len = text_len; c.text_on_device = true; c.mate = mate; c.af_action = af_action; c.af_min = af_min_pass; c.af_max = af_max_pass;
+	c.trim_offset = trim_offset; c.trim_length = trim_length; c.score = score; c.was_trimmed = was_trimmed; c.input_starts = input_starts; c.n_inputs = n_inputs;
+	return select_partitioned(h, c, cfg, out);
 }
 int kmr_partition_read_batch(kmr_handle *h, const kmr_reads *reads, const char *text, uint64_t text_len, const int64_t *mate, const uint8_t *af_action, const uint32_t *af_min_pass,
                              const uint32_t *af_max_pass, const uint64_t *input_starts, uint32_t n_inputs, const kmr_partition_config *cfg, kmr_picks **out) {
-	const PartitionArgs a = {cfg, input_starts, n_inputs};
-	return select_reads_any(h, reads, text, text_len, false, mate, af_action, af_min_pass, af_max_pass, nullptr, nullptr, nullptr, nullptr, nullptr, out, true, "kmr_partition_read_batch", &a);
+	SelectCall c = {};
+	c.who = "kmr_partition_read_batch"; c.fused = true; c.r = reads; c.text = text; c.text_len = text_len; c.mate = mate; c.af_action = af_action; c.af_min = af_min_pass; c.af_max = af_max_pass;
+	c.input_starts = input_starts; c.n_inputs = n_inputs;
+	return select_partitioned(h, c, cfg, out);
 }
 int kmr_partition_read_batch_dev(kmr_handle *h, const kmr_reads *reads, const void *dev_text, uint64_t text_len, const int64_t *mate, const uint8_t *af_action, const uint32_t *af_min_pass,
                                  const uint32_t *af_max_pass, const uint64_t *input_starts, uint32_t n_inputs, const kmr_partition_config *cfg, kmr_picks **out) {
-	const PartitionArgs a = {cfg, input_starts, n_inputs};
-	return select_reads_any(h, reads, dev_text, text_len, true, mate, af_action, af_min_pass, af_max_pass, nullptr, nullptr, nullptr, nullptr, nullptr, out, true, "kmr_partition_read_batch_dev", &a);
+	SelectCall c = {};
+	c.who = "kmr_partition_read_batch_dev"; c.fused = true; c.r = reads; c.text = dev_text; c.text_len = text_len; c.text_on_device = true; c.mate = mate;
+	c.af_action = af_action; c.af_min = af_min_pass; c.af_max = af_max_pass; c.input_starts = input_starts; c.n_inputs = n_inputs;
+	return select_partitioned(h, c, cfg, out);
 }
 /* ---- the normalizing branch: the same four with the pair list in place of mate, and the draws' parameters ---------------- */
 int kmr_normalize_config_init(kmr_normalize_config *c) {
@@ -1035,26 +1045,35 @@ int kmr_normalize_config_init(kmr_normalize_config *c) {
 int kmr_normalize_reads(kmr_handle *h, const kmr_reads *reads, const char *text, uint64_t text_len, const int64_t *read1, const int64_t *read2, uint64_t n_pairs,
                         const uint8_t *af_action, const uint32_t *af_min_pass, const uint32_t *af_max_pass, const uint32_t *trim_offset, const uint32_t *trim_length, const float *score,
                         const uint8_t *was_trimmed, const uint64_t *input_starts, uint32_t n_inputs, const kmr_normalize_config *cfg, kmr_picks **out) {
-	const NormalizeArgs a = {cfg, read1, read2, n_pairs, input_starts, n_inputs};
-	return select_reads_any(h, reads, text, text_len, false, nullptr, af_action, af_min_pass, af_max_pass, trim_offset, trim_length, score, was_trimmed, nullptr, out, false, "kmr_normalize_reads", nullptr, &a);
+	SelectCall c = {};
+	c.who = "kmr_normalize_reads"; c.r = reads; c.text = text; c.text_len = text_len; c.read1 = read1; c.read2 = read2; c.n_pairs = n_pairs; c.af_action = af_action; c.af_min = af_min_pass; c.af_max = af_max_pass;
+	c.trim_offset = trim_offset; c.trim_length = trim_length; c.score = score; c.was_trimmed = was_trimmed; c.input_starts = input_starts; c.n_inputs = n_inputs;
+	return select_normalized(h, c, cfg, out);
 }
 int kmr_normalize_reads_dev(kmr_handle *h, const kmr_reads *reads, const void *dev_text, uint64_t text_len, const int64_t *read1, const int64_t *read2, uint64_t n_pairs,
                             const uint8_t *af_action, const uint32_t *af_min_pass, const uint32_t *af_max_pass, const uint32_t *trim_offset, const uint32_t *trim_length, const float *score,
                             const uint8_t *was_trimmed, const uint64_t *input_starts, uint32_t n_inputs, const kmr_normalize_config *cfg, kmr_picks **out) {
-	const NormalizeArgs a = {cfg, read1, read2, n_pairs, input_starts, n_inputs};
-	return select_reads_any(h, reads, dev_text, text_len, true, nullptr, af_action, af_min_pass, af_max_pass, trim_offset, trim_length, score, was_trimmed, nullptr, out, false, "kmr_normalize_reads_dev", nullptr, &a);
+	SelectCall c = {};
+	c.who = "kmr_normalize_reads_dev"; c.r = reads; c.text = dev_text; c.text_len = text_len; c.text_on_device = true; c.read1 = read1; c.read2 = read2; c.n_pairs = n_pairs;
+	c.af_action = af_action; c.af_min = af_min_pass; c.af_max = af_max_pass;
+	c.trim_offset = trim_offset; c.trim_length = trim_length; c.score = score; c.was_trimmed = was_trimmed; c.input_starts = input_starts; c.n_inputs = n_inputs;
+	return select_normalized(h, c, cfg, out);
 }
 int kmr_normalize_read_batch(kmr_handle *h, const kmr_reads *reads, const char *text, uint64_t text_len, const int64_t *read1, const int64_t *read2, uint64_t n_pairs,
                              const uint8_t *af_action, const uint32_t *af_min_pass, const uint32_t *af_max_pass, const uint64_t *input_starts, uint32_t n_inputs,
                              const kmr_normalize_config *cfg, kmr_picks **out) {
-	const NormalizeArgs a = {cfg, read1, read2, n_pairs, input_starts, n_inputs};
-	return select_reads_any(h, reads, text, text_len, false, nullptr, af_action, af_min_pass, af_max_pass, nullptr, nullptr, nullptr, nullptr, nullptr, out, true, "kmr_normalize_read_batch", nullptr, &a);
+	SelectCall c = {};
+	c.who = "kmr_normalize_read_batch"; c.fused = true; c.r = reads; c.text = text; c.text_len = text_len; c.read1 = read1; c.read2 = read2; c.n_pairs = n_pairs;
+	c.af_action = af_action; c.af_min = af_min_pass; c.af_max = af_max_pass; c.input_starts = input_starts; c.n_inputs = n_inputs;
+	return select_normalized(h, c, cfg, out);
 }
 int kmr_normalize_read_batch_dev(kmr_handle *h, const kmr_reads *reads, const void *dev_text, uint64_t text_len, const int64_t *read1, const int64_t *read2, uint64_t n_pairs,
                                  const uint8_t *af_action, const uint32_t *af_min_pass, const uint32_t *af_max_pass, const uint64_t *input_starts, uint32_t n_inputs,
                                  const kmr_normalize_config *cfg, kmr_picks **out) {
-	const NormalizeArgs a = {cfg, read1, read2, n_pairs, input_starts, n_inputs};
-	return select_reads_any(h, reads, dev_text, text_len, true, nullptr, af_action, af_min_pass, af_max_pass, nullptr, nullptr, nullptr, nullptr, nullptr, out, true, "kmr_normalize_read_batch_dev", nullptr, &a);
+	SelectCall c = {};
+	c.who = "kmr_normalize_read_batch_dev"; c.fused = true; c.r = reads; c.text = dev_text; c.text_len = text_len; c.text_on_device = true; c.read1 = read1; c.read2 = read2; c.n_pairs = n_pairs;
+	c.af_action = af_action; c.af_min = af_min_pass; c.af_max = af_max_pass; c.input_starts = input_starts; c.n_inputs = n_inputs;
+	return select_normalized(h, c, cfg, out);
 }
 int kmr_normalize_info(const kmr_picks *p, uint64_t *n_picks, uint64_t *n_candidates, uint64_t *n_draws) {
 	if (!p || !p->normalized) return KMR_ERR_INVALID_ARG;
@@ -1070,10 +1089,8 @@ int kmr_picks_segments_copy(const kmr_picks *p, float *round_depth, uint8_t *rou
                             uint64_t *seg_bytes, int32_t *read_segment) {
 	if (!p) return KMR_ERR_INVALID_ARG;
 	for (uint32_t r = 0; r < p->n_rounds; r++) { if (round_depth) round_depth[r] = p->round_depth[r]; if (round_is_remainder) round_is_remainder[r] = p->round_is_remainder[r]; }
-	const uint64_t one[4] = {0, p->n_picked, 0, p->bytes};      /* picks of the plain entry points */
-	const size_t S = (size_t)p->n_rounds * p->n_inputs;
-	const uint64_t *t = p->seg_table.empty() ? one : p->seg_table.data();
-	for (size_t s = 0; s < S; s++) {
+	const uint64_t *t = p->seg_table.data();
+	for (size_t s = 0; s < p->seg_table.size() / 4; s++) {
 		if (seg_first_pick) seg_first_pick[s] = t[4 * s]; if (seg_picks) seg_picks[s] = t[4 * s + 1];
 		if (seg_first_byte) seg_first_byte[s] = t[4 * s + 2]; if (seg_bytes) seg_bytes[s] = t[4 * s + 3];
 	}

@@ -890,6 +890,26 @@ class ReadSelector(_DeviceObject):
         a = self.af or (None, None, None)
         return self._p(a[0], C.c_uint8), self._p(a[1], C.c_uint32), self._p(a[2], C.c_uint32)
 
+    def _trim_args(self):
+        """the trims scoreAndTrimReads left as the four array arguments of the unfused entry points: (the arrays, their pointers)"""
+        keep = [np.ascontiguousarray(a, dtype=t) for a, t in zip(self.trims, (np.uint32, np.uint32, np.float32, np.uint8))]
+        return keep, [self._p(a, ct) for a, ct in zip(keep, (C.c_uint32, C.c_uint32, C.c_float, C.c_uint8))]
+
+    def _starts_args(self, input_starts):
+        """input_starts (n_inputs + 1 read indices, or None) as (the array, its pointer, n_inputs)"""
+        starts = None if input_starts is None else np.ascontiguousarray(input_starts, dtype=np.uint64)
+        return starts, self._p(starts, C.c_uint64), 0 if starts is None else starts.size - 1
+
+    def _files(self, text, seg, round_names, input_prefixes, suffix):
+        """(file name, bytes) of every segment that holds a pick, round-major: round_names[r] + "-" + the input's prefix + suffix"""
+        n_rounds, n_inputs = seg["picks"].shape
+        prefixes = list(input_prefixes) if input_prefixes is not None else ["transformed-%d" % (j + 1) for j in range(n_inputs)]
+        if len(prefixes) != n_inputs:
+            raise KmerSpectrumError("selectReads: %d input_prefixes for %d inputs" % (len(prefixes), n_inputs))
+        first, size = seg["first_byte"], seg["bytes"]
+        return [(round_names[r] + "-" + prefixes[j] + suffix, text[int(first[r, j]):int(first[r, j]) + int(size[r, j])])
+                for r in range(n_rounds) for j in range(n_inputs) if seg["picks"][r, j]]
+
     def _adopt(self, handle):
         self.close()
         self._picks = handle
@@ -913,13 +933,10 @@ class ReadSelector(_DeviceObject):
     def _run(self, output_quality_base, format):
         min_score, min_read_length, both_pass = self._sel
         cfg = self._config(min_score, min_read_length, both_pass, output_quality_base, format, self.scoring)
-        to, tl, sc, wt = self.trims
-        to = np.ascontiguousarray(to, dtype=np.uint32); tl = np.ascontiguousarray(tl, dtype=np.uint32)
-        sc = np.ascontiguousarray(sc, dtype=np.float32); wt = np.ascontiguousarray(wt, dtype=np.uint8)
         keep, tp, tn = self._text_args()
+        trims, trim_ptrs = self._trim_args()
         out = C.c_void_p()
-        self.sp._call("select_reads", self.sp.h, self.reads.r, tp, tn, self._p(self.mate, C.c_int64), *self._af_args(),
-                      self._p(to, C.c_uint32), self._p(tl, C.c_uint32), self._p(sc, C.c_float), self._p(wt, C.c_uint8), C.byref(cfg), C.byref(out))
+        self.sp._call("select_reads", self.sp.h, self.reads.r, tp, tn, self._p(self.mate, C.c_int64), *self._af_args(), *trim_ptrs, C.byref(cfg), C.byref(out))
         self._adopt(out)
         self._fmt = (output_quality_base, cfg.format)
         return self.n_picked
@@ -975,53 +992,35 @@ class ReadSelector(_DeviceObject):
             seg = self._segments()
             if not separate_outputs:
                 return [(output, text)]
-            n_inputs = seg["picks"].shape[1]
-            prefixes = list(input_prefixes) if input_prefixes is not None else ["transformed-%d" % (j + 1) for j in range(n_inputs)]
-            if len(prefixes) != n_inputs:
-                raise KmerSpectrumError("selectReads: %d input_prefixes for %d inputs" % (len(prefixes), n_inputs))
-            name = "%s-MinDepth%d-MaxDepth%d" % (output, int(min_depth), int(max_kmer_output_depth))
-            return [(name + "-" + prefixes[j] + self.SUFFIX[cfg.select.format], text[int(seg["first_byte"][0, j]):int(seg["first_byte"][0, j]) + int(seg["bytes"][0, j])])
-                    for j in range(n_inputs) if seg["picks"][0, j]]
+            return self._files(text, seg, ["%s-MinDepth%d-MaxDepth%d" % (output, int(min_depth), int(max_kmer_output_depth))], input_prefixes, self.SUFFIX[cfg.select.format])
         fused = self.trims is None
         cfg = _lib.KmrPartitionConfig()
         self.sp.lib.kmr_partition_config_init(C.byref(cfg))
         cfg.select = self._config(min_depth, min_read_length, both_pass, output_quality_base, format, scoring if fused else self.scoring)
         cfg.partition_by_depth, cfg.remainder_trim = int(partition_by_depth), float(remainder_trim)
-        starts, n_inputs = None, 0
-        if input_starts is not None:
-            starts = np.ascontiguousarray(input_starts, dtype=np.uint64)
-            n_inputs = starts.size - 1
+        starts, starts_p, n_inputs = self._starts_args(input_starts)
         keep, tp, tn = self._text_args()
         out = C.c_void_p()
         head = (self.sp.h, self.reads.r, tp, tn, self._p(self.mate, C.c_int64)) + tuple(self._af_args())
-        tail = (self._p(starts, C.c_uint64), n_inputs, C.byref(cfg), C.byref(out))
+        tail = (starts_p, n_inputs, C.byref(cfg), C.byref(out))
         if fused:
             self.sp._call("partition_read_batch", *head, *tail)
         else:
-            to, tl, sc, wt = self.trims
-            to = np.ascontiguousarray(to, dtype=np.uint32); tl = np.ascontiguousarray(tl, dtype=np.uint32)
-            sc = np.ascontiguousarray(sc, dtype=np.float32); wt = np.ascontiguousarray(wt, dtype=np.uint8)
-            self.sp._call("partition_reads", *head, self._p(to, C.c_uint32), self._p(tl, C.c_uint32), self._p(sc, C.c_float), self._p(wt, C.c_uint8), *tail)
+            trims, trim_ptrs = self._trim_args()
+            self.sp._call("partition_reads", *head, *trim_ptrs, *tail)
         self._adopt(out)
         self._sel, self._fmt = None, (output_quality_base, cfg.select.format)
         text = self._copy()
         seg = self._segments()
         if not separate_outputs:
             return [(output, text)]
-        n_rounds, n_inputs = seg["picks"].shape
-        prefixes = list(input_prefixes) if input_prefixes is not None else ["transformed-%d" % (j + 1) for j in range(n_inputs)]
-        if len(prefixes) != n_inputs:
-            raise KmerSpectrumError("selectReads: %d input_prefixes for %d inputs" % (len(prefixes), n_inputs))
-        files = []
-        for r in range(n_rounds):
+        names = []
+        for r in range(seg["picks"].shape[0]):
             name = "%s-MinDepth%d" % (output, int(min_depth))
             if partition_by_depth > 0:      # lexical_cast<string>(float tmpMinDepth): 16, not 16.0
                 name += "-Remainder" if seg["round_is_remainder"][r] else ("-PartitionDepth%.9g" % seg["round_depth"][r] if seg["round_depth"][r] > 0 else "")
-            for j in range(n_inputs):
-                if seg["picks"][r, j]:
-                    b0 = int(seg["first_byte"][r, j])
-                    files.append((name + "-" + prefixes[j] + self.SUFFIX[cfg.select.format], text[b0:b0 + int(seg["bytes"][r, j])]))
-        return files
+            names.append(name)
+        return self._files(text, seg, names, input_prefixes, self.SUFFIX[cfg.select.format])
 
     def _normalize(self, target_depth, min_score, min_read_length, by_pair, both_pass, seed, first_read_idx, scoring, output_quality_base, format,
                    input_starts=None, method=0, use_logscale=False):
@@ -1032,22 +1031,17 @@ class ReadSelector(_DeviceObject):
         cfg.select = self._config(min_score, min_read_length, both_pass, output_quality_base, format, scoring if fused else self.scoring)
         cfg.target_depth, cfg.seed, cfg.first_global_read_idx = int(target_depth), int(seed), int(first_read_idx)
         cfg.by_pair, cfg.method, cfg.use_logscale = (1 if by_pair else 0), int(method), (1 if use_logscale else 0)
-        starts, n_inputs = None, 0
-        if input_starts is not None:
-            starts = np.ascontiguousarray(input_starts, dtype=np.uint64)
-            n_inputs = starts.size - 1
+        starts, starts_p, n_inputs = self._starts_args(input_starts)
         r1, r2 = self.pairs if self.pairs is not None else (None, None)
         keep, tp, tn = self._text_args()
         out = C.c_void_p()
         head = (self.sp.h, self.reads.r, tp, tn, self._p(r1, C.c_int64), self._p(r2, C.c_int64), 0 if r1 is None else r1.size) + tuple(self._af_args())
-        tail = (self._p(starts, C.c_uint64), n_inputs, C.byref(cfg), C.byref(out))
+        tail = (starts_p, n_inputs, C.byref(cfg), C.byref(out))
         if fused:
             self.sp._call("normalize_read_batch", *head, *tail)
         else:
-            to, tl, sc, wt = self.trims
-            to = np.ascontiguousarray(to, dtype=np.uint32); tl = np.ascontiguousarray(tl, dtype=np.uint32)
-            sc = np.ascontiguousarray(sc, dtype=np.float32); wt = np.ascontiguousarray(wt, dtype=np.uint8)
-            self.sp._call("normalize_reads", *head, self._p(to, C.c_uint32), self._p(tl, C.c_uint32), self._p(sc, C.c_float), self._p(wt, C.c_uint8), *tail)
+            trims, trim_ptrs = self._trim_args()
+            self.sp._call("normalize_reads", *head, *trim_ptrs, *tail)
         self._adopt(out)
         self._sel, self._fmt = None, (output_quality_base, cfg.select.format)
         v = [C.c_uint64() for _ in range(3)]

@@ -1,6 +1,7 @@
 """selectReads' partitioned branch on the device (kmr_partition_reads, kmr_partition_read_batch; kmernator_amd/csrc/kmr_select.hpp):
 --partition-by-depth, --remainder-trim and the per-input-file outputs, every byte and the segment table against the CPU
-restatement of tests/refpartition.py."""
+restatement of tests/refpartition.py; and the plain entry points (kmr_select_reads, kmr_filter_read_batch), which are its one round
+over one input, through many units and tiles."""
 import ctypes as C
 import hashlib
 import os
@@ -236,6 +237,75 @@ def test_many_units_and_tiles_against_the_restatement(sp, many, units):
     assert len(text) == len(want)
 
 
+# ---------------------------------------------------------------- 3b: the plain entry points walk the same units and tiles
+
+def expect_plain(c, min_score, both, mate, lo=0, hi=None):
+    """the restatement's one round at min_score, no input_starts, over reads [lo, hi) of a case, with `mate` (indices into the
+    cut, or None for pickAllPassingReads): (text, flags)"""
+    hi = c.n if hi is None else hi
+    rounds = round_table(min_score, 0, -1.0, 0.40, 2 if both else 1)
+    assert len(rounds) == 1 and rounds[0]["depth"] == min_score and not rounds[0]["is_remainder"]
+    want, table, rseg = partition(c.names[lo:hi], c.seqs[lo:hi], c.quals[lo:hi], c.labels[lo:hi], c.disc[lo:hi], c.to[lo:hi], c.tl[lo:hi], c.sc[lo:hi], mate, rounds, None, 0, 33, False)
+    assert table[0][0][1] == int((rseg >= 0).sum()) and table[0][0][3] == len(want)
+    return want, rseg >= 0
+
+
+@pytest.fixture(scope="module")
+def many_plain_want(many):
+    return {"either": expect_plain(many, 8, False, many.mate), "both": expect_plain(many, 8, True, many.mate), "reads": expect_plain(many, 8, False, None)}
+
+
+@pytest.mark.parametrize("units", [0, 7, 64])
+def test_plain_entry_point_over_many_units_and_tiles(sp, many, many_plain_want, units):
+    """kmr_select_reads over 40 000 reads, pairs i ^ 1: 625 units of one tile by default, 7 units of 90 tiles and 64 of 10"""
+    c = many
+    sp.tune(partition_units=units)
+    try:
+        for key, both in (("either", False), ("both", True)):
+            want, flags = many_plain_want[key]
+            assert c.sel.pickAllPassingPairs(8, None, both) == int(flags.sum())
+            text = c.sel.writePicks()
+            print("units %d, %s: %d picks of %d, %d bytes" % (units, key, c.sel.n_picked, c.n, len(text)))
+            assert 300 < flags.sum() < c.n - 300
+            assert len(text) == len(want) and text == want and np.array_equal(c.sel.picked_flags, flags)
+        want, flags = many_plain_want["reads"]
+        assert c.sel.pickAllPassingReads(8, None) == int(flags.sum())
+        text = c.sel.writePicks()
+        assert 300 < flags.sum() < c.n - 300
+        assert len(text) == len(want) and text == want and np.array_equal(c.sel.picked_flags, flags)
+    finally:
+        sp.tune(partition_units=0)
+
+
+CUT_AT = 2          # reads 2, 3, 4 of the many: the first passes a minimum score of 8, the next two do not
+
+
+@pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 127, 128, 129])
+def test_plain_entry_point_at_unit_and_tile_edges(sp, many, n):
+    """kmr_select_reads with two units over n reads cut from the many, pairs i ^ 1 and the last read single when n is odd: one tile
+    short of, at and past a tile and two tiles.  Every batch of two reads or more picks a read and drops one; for n = 2 that can
+    hold only read by read (a pair is picked or dropped whole), so every batch also runs through pickAllPassingReads"""
+    m = many
+    lo, hi = CUT_AT, CUT_AT + n
+    mate = np.arange(n, dtype=np.int64) ^ 1
+    mate[mate >= n] = -1
+    c = Case(sp, m.names[lo:hi], m.seqs[lo:hi], m.quals[lo:hi], mate, m.action[lo:hi], m.lo[lo:hi], m.hi[lo:hi], m.to[lo:hi], m.tl[lo:hi], m.sc[lo:hi])
+    sp.tune(partition_units=2)
+    try:
+        for use_mate in (True, False):
+            want, flags = expect_plain(m, 8, False, mate if use_mate else None, lo, hi)
+            if n >= (3 if use_mate else 2):
+                assert flags.any() and not flags.all()
+            got = c.sel.pickAllPassingPairs(8, None, False) if use_mate else c.sel.pickAllPassingReads(8, None)
+            text = c.sel.writePicks()
+            print("n %d, %s: %d picks, %d bytes" % (n, "pairs" if use_mate else "reads", got, len(text)))
+            assert got == c.sel.n_picked == int(flags.sum())
+            assert text == want and np.array_equal(c.sel.picked_flags, flags)
+    finally:
+        sp.tune(partition_units=0)
+        c.close()
+
+
 # ---------------------------------------------------------------- 4: the fused form on the reference's own fixture
 
 def test_fused_form_on_the_reference_fixture():
@@ -300,6 +370,24 @@ def test_fused_form_on_the_reference_fixture():
     assert lib.kmr_picks_copy(out, buf.ctypes.data_as(C.c_void_p), nb.value, None) == 0
     lib.kmr_picks_free(out)
     assert buf.tobytes() == want
+    sel.close(); frs.close(); rs.close(); f.close(); sp.close()
+
+
+@pytest.mark.parametrize("units", [0, 7])
+def test_plain_fused_form_on_the_reference_fixture(units):
+    """kmr_filter_read_batch on the same fixture (min depth 2, min read length 25, quality base 64) writes 1000-Filtered.fastq
+    whatever the number of units"""
+    sp = ka.KmerSpectrum(ka.default_config(K, estimated_raw_kmers=46000, device=0))
+    rs = ka.ReadSet(sp, golden("1000.fastq"))
+    f = ka.FilterKnownOddities(sp, golden("artifact_sequences.fa"), edit_distance=1, min_read_length=25.0)
+    res, frs = f.applyFilter(rs)
+    sp.buildKmerSpectrumFromReadSet(frs)
+    sp.finalize(2)
+    sel = ka.ReadSelector(sp, frs, mate=np.arange(1000, dtype=np.int64) ^ 1, filter_results=res)
+    sp.tune(partition_units=units)
+    got = sel.filterReads(2.0, 25.0, False, "MEDIAN", 64, "fastq")
+    want = golden("1000-Filtered.fastq").replace(b"\t", b" ")
+    assert len(want) > 0 and got.replace(b"\t", b" ") == want and sel.n_picked == want.count(b"\n") // 4
     sel.close(); frs.close(); rs.close(); f.close(); sp.close()
 
 

@@ -1,8 +1,9 @@
 """development tool: selectReads' last stage on the C2-shaped synthetic batch (1 M reads x 150 bp, the bench's generator), the scores and
 trims handed in (array form, so no spectrum is built), scores spread evenly over 0 .. 40 so that every round of 16 / 8 / 4 / 2 takes
 reads.  Three calls on the same arrays, the FASTQ text in device memory:
- (a) kmr_select_reads_dev at min depth 2 (the plain branch: per-read count, two scans over the reads, compaction, writer);
- (b) kmr_partition_reads_dev with partition_by_depth 0: one round, the same bytes (checked), through the partition's kernels;
+ (a) kmr_select_reads_dev at min depth 2: the plain entry point's timing.  It runs the kernels of (b) since the plain branch (per-read
+     count, two scans over the reads, compaction) was retired, and keeps no per-read segments;
+ (b) kmr_partition_reads_dev with partition_by_depth 0: one round, the same bytes (checked);
  (c) kmr_partition_reads_dev with partition_by_depth 16 and remainder_trim 25: five rounds.
 The three alternate inside every repetition after a warm-up of each; a call's time is the host clock around it (a call ends in a
 device synchronise and includes the copy of its per-read arrays to the device, the same arrays for all three), and the library's
