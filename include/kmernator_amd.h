@@ -216,7 +216,7 @@ int kmr_lookup_reads_weighted(kmr_handle *h, const char *bases, const uint64_t *
 /* Trim and score whole reads against the weak map: ReadSelector::scoreAndTrimReads
  * (src/ReadSelector.h:1182-1207) = per-position counts (getValue :924-931, weak map only), cut at the first
  * N/X markup (_setNumKmers :1037-1047), first longest run of k-mers with count >= minimum_kmer_score
- * (trimReadByMinimumKmerScore :949-1014, bimodal detection off), score of that run (scoreReadByScoringType
+ * (trimReadByMinimumKmerScore :949-1014; its bimodal cut: kmr_set_bimodal_sigmas below), score of that run (scoreReadByScoringType
  * :1094-1180) and setTrimHeaders (:1015-1036).  Per read: trim_offset (bases), trim_length (bases, run + k - 1,
  * 0 = nothing left), score (-1 if nothing left; KS_SUM leaves 0 as the reference does), was_trimmed.
  * A markup other than N, X and '.' (an IUPAC code, a lower-case n) does not cut: the reference looks the k-mers that hold it up
@@ -229,6 +229,27 @@ typedef enum kmr_scoring { KMR_SCORE_SUM = 0, KMR_SCORE_MEDIAN = 1, KMR_SCORE_MI
 int kmr_score_reads(kmr_handle *h, const char *bases, const uint64_t *offsets, uint64_t n_reads,
                     double minimum_kmer_score, int scoring_type,
                     uint32_t *trim_offset, uint32_t *trim_length, float *score, uint8_t *was_trimmed);
+/* --bimodal-sigmas (ReadSelector::_bimodalSigmas; the default of kmr_create is -1, off), for every scoring call of the handle:
+ * kmr_score_reads, kmr_score_read_batch, kmr_score_counts_dev and the fused kmr_filter_ / kmr_partition_ / kmr_normalize_read_batch*.
+ * With sigmas >= 0 a run of n >= 3 k-mers is searched for the split p in 1 .. n-1 whose halves first = v[0..p), second = v[p..n)
+ * differ most in mean depth (src/ReadSelector.h:981-1008, Statistics::findBimodalPartition src/Utils.h:1031-1056):
+ *   mean     the f64 sum in index order, divided by the count where the count is above 1
+ *   stdDev   the VARIANCE (the reference never takes its root): f64 sum of (x - mean) * (x - mean) in index order over count - 1,
+ *            0 for one value; raised to sqrt(mean) where mean > 0 and it is below that (the Poisson floor)
+ *   diff     abs(first.mean - second.mean), where abs is C's int abs(int): the unqualified call on a double resolves to it with
+ *            the reference's includes (<cstdlib>, <cmath>, no using-directive), so the difference is TRUNCATED toward zero to an
+ *            int first (2.9 - 0.2 gives 2).  That reading is this library's contract
+ *   a split qualifies if diff > sigmas * max(first.stdDev, second.stdDev); the qualifying split of the strictly largest diff wins,
+ *   so of equal diffs the earliest p.
+ * first.mean > second.mean drops the tail (run length p), otherwise the head (offset + p, length n - p); was_trimmed is set and
+ * the score is that of the reduced run.  The record's label gains "Bimodal@<p + k>:<(int)first.mean>/<(int)second.mean>", with
+ * "Inv" in front where the head was dropped, between AFTrim and Trim.  With sigmas < 0 nothing is added to a scoring call: no
+ * kernel, no allocation, no wait.  NaN: KMR_ERR_INVALID_ARG. */
+int kmr_set_bimodal_sigmas(kmr_handle *h, double sigmas);
+/* One word per read of the handle's last scoring call: 0 = not cut, else p + k in bits 0-31, (int)first.mean in bits 32-47,
+ * (int)second.mean in bits 48-63 (Inv where the first is the smaller).  All zero if that call ran with the option off.
+ * KMR_ERR_STATE: no scoring call yet; KMR_ERR_INVALID_ARG: n_reads is not that call's. */
+int kmr_bimodal_copy(kmr_handle *h, uint64_t *words, uint64_t n_reads);
 
 /* Export in the reference's on-disk / mmap format so the caller can
  * WeakMapType::restore(dst) it.  Replaces KmerMapByKmerArrayPair::getSizeToStore /
@@ -692,8 +713,9 @@ int kmr_artifact_filter_apply(kmr_handle *h, const kmr_artifact_filter *f, const
  *               is 1, "Trim:<offset>+<length>" if was_trimmed[i], "<Label>:<(int)(score + 0.5)>" with Label = Score /
  *               MedianScore / MinScore / MaxScore / AvgScore (getKmerScoringTypeLabel, :248-257, in kmr_scoring's order).
  *               A discarded read was never scored (:1195-1197) and has no label
- * Not covered: stored comments are not printed and a Casava "name 1:Y" is not rewritten to "name/1"; the unmasked formats
- * and bimodal trimming.  Markup characters other than N, X and '.' are outside the parity claim: the reference applies a read's
+ * Not covered: stored comments are not printed and a Casava "name 1:Y" is not rewritten to "name/1"; the unmasked formats.
+ * Bimodal trimming: "Bimodal@..." / "InvBimodal@..." stands between AFTrim and Trim (kmr_set_bimodal_sigmas; the fused forms tag
+ * what they score, the host-array forms take the words through kmr_select_bimodal).  Markup characters other than N, X and '.' are outside the parity claim: the reference applies a read's
  * markup positions to the already trimmed string (src/Sequence.cpp:322-325, src/TwoBitSequence.cpp:317-327), so such a
  * character lands on the wrong base when the trim offset is not 0, while the device prints the batch's own characters where
  * they are (N and X never lie inside a k-mer trim: it ends before the first of them).
@@ -713,6 +735,10 @@ typedef struct kmr_select_config {
 } kmr_select_config;
 int kmr_select_config_init(kmr_select_config *cfg);      /* the reference's defaults */
 typedef struct kmr_picks kmr_picks;
+/* The words of kmr_bimodal_copy that belong to the trims of the NEXT kmr_select_reads*, kmr_partition_reads* or kmr_normalize_reads*
+ * on the handle: that call prints their tags and consumes them (a count other than its batch's: KMR_ERR_INVALID_ARG there).
+ * NULL takes them back. */
+int kmr_select_bimodal(kmr_handle *h, const uint64_t *words, uint64_t n_reads);
 /* selection and output from host arrays as kmr_score_read_batch / kmr_score_counts_dev and kmr_artifact_filter_apply return them */
 int kmr_select_reads(kmr_handle *h, const kmr_reads *reads, const char *text, uint64_t text_len, const int64_t *mate,
                      const uint8_t *af_action, const uint32_t *af_min_pass, const uint32_t *af_max_pass,
@@ -772,7 +798,7 @@ void kmr_picks_free(kmr_picks *p);
  * Bounds: at most 33 rounds (32 halvings of a 32-bit depth and the remainder; minimum_score 0 under a depth of 2^31 or more
  * would need 34: KMR_ERR_UNSUPPORTED); rounds x inputs <= 256 segments (KMR_ERR_UNSUPPORTED beyond): the counting pass keeps 12
  * bytes of LDS per segment and wavefront, 3 KiB at 256, which lets 32 wavefronts share a CU's 160 KiB.
- * Not covered: --kmer-size 0 (the tmpMinDepth = 0 special case, :224-227), bimodal trimming.
+ * Not covered: --kmer-size 0 (the tmpMinDepth = 0 special case, :224-227).  Bimodal trimming is the handle's (kmr_set_bimodal_sigmas).
  * KMR_ERR_INVALID_ARG: a wrong struct_size; input_starts that does not start at 0, descends or does not end at n_reads. */
 typedef struct kmr_partition_config {
 	uint32_t struct_size;            /* = sizeof(kmr_partition_config), ABI guard                                           */

@@ -14,6 +14,7 @@
  *     storeMmap / restoreMmap :476-518 (file naming: <name>, <name>-singleton)
  *     dumpCounts / dumpGraphs MeraculousDistributedKmerSpectrum            src/Meraculous.h:107-134
  *     scoreAndTrimReads       ReadSelector::scoreAndTrimReads              src/ReadSelector.h:1182-1207
+ *     setBimodalSigmas        ReadSelector::_bimodalSigmas (--bimodal-sigmas) src/ReadSelector.h:981-1008
  *   kmernator::ReadSet        ReadSet::appendFastq... on the device        src/ReadSet.cpp:311-345
  *
  * Errors surface as kmernator::KmerSpectrumError (the reference throws LoggedException, src/Log.h:442-484).
@@ -166,13 +167,22 @@ public:
 		h.finish();
 		return h;
 	}
-	struct TrimResult { std::vector<uint32_t> trimOffset, trimLength; std::vector<float> score; std::vector<uint8_t> wasTrimmed; };
+	/* --bimodal-sigmas (ReadSelector::_bimodalSigmas; negative = off, the default) of every scoring call of this spectrum from now on */
+	void setBimodalSigmas(double sigmas) { check(kmr_set_bimodal_sigmas(_h, sigmas), "kmr_set_bimodal_sigmas"); _bimodalSigmas = sigmas; }
+	/* bimodal: one word per read where setBimodalSigmas is on (0 = not cut; kmr_bimodal_copy), else empty; the selections that
+	 * take a TrimResult print its tags */
+	struct TrimResult { std::vector<uint32_t> trimOffset, trimLength; std::vector<float> score; std::vector<uint8_t> wasTrimmed; std::vector<uint64_t> bimodal; };
 	TrimResult scoreAndTrimReads(const ReadSet &reads, double minimumKmerScore, ScoringType t = KS_MEDIAN) {
 		TrimResult r; const uint64_t n = reads.getSize();
 		r.trimOffset.resize(n); r.trimLength.resize(n); r.score.resize(n); r.wasTrimmed.resize(n);
-		if (n) check(kmr_score_read_batch(_h, reads.raw(), minimumKmerScore, (int)t, r.trimOffset.data(), r.trimLength.data(), r.score.data(), r.wasTrimmed.data()), "kmr_score_read_batch");
+		if (n) {
+			check(kmr_score_read_batch(_h, reads.raw(), minimumKmerScore, (int)t, r.trimOffset.data(), r.trimLength.data(), r.score.data(), r.wasTrimmed.data()), "kmr_score_read_batch");
+			if (_bimodalSigmas >= 0.0) { r.bimodal.resize(n); check(kmr_bimodal_copy(_h, r.bimodal.data(), n), "kmr_bimodal_copy"); }
+		}
 		return r;
 	}
+	/* hands a TrimResult's tags to the next selection over host arrays (kmr_select_bimodal); none: takes back what is left */
+	void selectBimodal(const TrimResult &t) { check(kmr_select_bimodal(_h, t.bimodal.empty() ? nullptr : t.bimodal.data(), t.bimodal.size()), "kmr_select_bimodal"); }
 
 	std::vector<uint8_t> image(int whichMap) {
 		uint64_t n = 0; check(kmr_image_size(_h, whichMap, &n), "kmr_image_size");
@@ -216,7 +226,7 @@ private:
 		const std::streamsize n = i.tellg(); if (n <= 0) return false;
 		b.resize((size_t)n); i.seekg(0); i.read((char *)b.data(), n); return (bool)i;
 	}
-	kmr_config _cfg; kmr_handle *_h = nullptr;
+	kmr_config _cfg; kmr_handle *_h = nullptr; double _bimodalSigmas = -1.0;
 	friend class ReadSet;
 	friend class FilterKnownOddities;
 };
@@ -298,6 +308,7 @@ public:
 	/* the selection over trims the caller holds (KmerSpectrum::scoreAndTrimReads) */
 	uint64_t pickAllPassingPairs(const KmerSpectrum::TrimResult &t, const kmr_select_config &cfg) {
 		reset();
+		_sp.selectBimodal(t);
 		_sp.check(kmr_select_reads(_sp.raw(), _reads.raw(), _reads._text.data(), _reads._text.size(), mate(), action(), minPass(), maxPass(),
 		                           t.trimOffset.data(), t.trimLength.data(), t.score.data(), t.wasTrimmed.data(), &cfg, &_p), "kmr_select_reads");
 		return getNumPicks();
@@ -316,6 +327,7 @@ public:
 		reset();
 		const uint64_t *starts = inputStarts.empty() ? nullptr : inputStarts.data();
 		const uint32_t nIn = inputStarts.empty() ? 0 : (uint32_t)(inputStarts.size() - 1);
+		if (trims) _sp.selectBimodal(*trims);
 		if (trims) _sp.check(kmr_partition_reads(_sp.raw(), _reads.raw(), _reads._text.data(), _reads._text.size(), mate(), action(), minPass(), maxPass(), trims->trimOffset.data(), trims->trimLength.data(),
 		                                         trims->score.data(), trims->wasTrimmed.data(), starts, nIn, &cfg, &_p), "kmr_partition_reads");
 		else _sp.check(kmr_partition_read_batch(_sp.raw(), _reads.raw(), _reads._text.data(), _reads._text.size(), mate(), action(), minPass(), maxPass(), starts, nIn, &cfg, &_p), "kmr_partition_read_batch");
@@ -355,6 +367,7 @@ public:
 		const uint64_t *starts = inputStarts.empty() ? nullptr : inputStarts.data();
 		const uint32_t nIn = inputStarts.empty() ? 0 : (uint32_t)(inputStarts.size() - 1);
 		const int64_t *r1 = _read1.empty() ? nullptr : _read1.data(), *r2 = _read2.empty() ? nullptr : _read2.data();
+		if (trims) _sp.selectBimodal(*trims);
 		if (trims) _sp.check(kmr_normalize_reads(_sp.raw(), _reads.raw(), _reads._text.data(), _reads._text.size(), r1, r2, _read1.size(), action(), minPass(), maxPass(), trims->trimOffset.data(),
 		                                         trims->trimLength.data(), trims->score.data(), trims->wasTrimmed.data(), starts, nIn, &cfg, &_p), "kmr_normalize_reads");
 		else _sp.check(kmr_normalize_read_batch(_sp.raw(), _reads.raw(), _reads._text.data(), _reads._text.size(), r1, r2, _read1.size(), action(), minPass(), maxPass(), starts, nIn, &cfg, &_p), "kmr_normalize_read_batch");

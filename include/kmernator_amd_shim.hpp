@@ -74,11 +74,17 @@ public:
 	 * reference constructs `KS spectrum(0)` first and assigns the real one later */
 	GpuKmerSpectrum(unsigned long estimatedRawKmers = 0, bool separateSingletons = true, int valueKind = KMR_VALUE_COUNT_DIR, int device = -1)
 	    : KS(estimatedRawKmers, separateSingletons), _estimatedRawKmers(estimatedRawKmers), _separateSingletons(separateSingletons),
-	      _valueKind(valueKind), _device(device), _rank(0), _worldSize(1), _sizeTracking(false), _wantSizeHistory(false) {}
+	      _valueKind(valueKind), _device(device), _rank(0), _worldSize(1), _sizeTracking(false), _wantSizeHistory(false), _bimodalSigmas(-1.0) {}
 	virtual ~GpuKmerSpectrum() {}
 	/* --size-history-file (apps/FilterReads.cpp:141-147): call before the first build of this object.  Off by default: with it on the
 	 * count pass keeps two first sightings per key and cannot cut hot minimizer lists (homopolymers, satellites) into pieces */
 	void setSizeTracking(bool on) { _wantSizeHistory = on; }
+	/* ReadSelector --bimodal-sigmas (Options::getBimodalSigmas; negative = off) for the scoring calls made on this spectrum's device
+	 * handle (kmr_set_bimodal_sigmas): kept here until the handle exists, applied to it from then on */
+	void setBimodalSigmas(double sigmas) {
+		_bimodalSigmas = sigmas;
+		if (_handle.get()) check(kmr_set_bimodal_sigmas(_handle.get(), sigmas), "kmr_set_bimodal_sigmas");
+	}
 	/* copy construction and assignment: KS copies its maps (src/KmerSpectrum.h:423-440), the device handle is shared */
 
 	/* replaces KmerSpectrum::buildKmerSpectrum(const ReadSet &[, bool]) (src/KmerSpectrum.h:2081-2086) */
@@ -162,7 +168,7 @@ protected:
 	template <typename World>
 	GpuKmerSpectrum(WorldTag, World &world, unsigned long estimatedRawKmers, bool separateSingletons, int valueKind, int device)
 	    : KS(world, estimatedRawKmers, separateSingletons), _estimatedRawKmers(estimatedRawKmers), _separateSingletons(separateSingletons),
-	      _valueKind(valueKind), _device(device), _rank(0), _worldSize(1), _sizeTracking(false), _wantSizeHistory(false) {}
+	      _valueKind(valueKind), _device(device), _rank(0), _worldSize(1), _sizeTracking(false), _wantSizeHistory(false), _bimodalSigmas(-1.0) {}
 
 	struct FlatReads {
 		std::string bases, quals;
@@ -246,6 +252,7 @@ protected:
 		const int rc = kmr_create(&c, &h);
 		if (rc != KMR_OK) throw std::runtime_error(std::string("kmr_create: ") + kmr_last_error(NULL));
 		_handle.adopt(h);
+		if (_bimodalSigmas >= 0.0) check(kmr_set_bimodal_sigmas(h, _bimodalSigmas), "kmr_set_bimodal_sigmas");
 	}
 	void requireHandle() { if (!_handle.get()) throw std::runtime_error("GpuKmerSpectrum: no spectrum has been built on the device yet"); }
 
@@ -296,6 +303,7 @@ protected:
 	bool _separateSingletons;
 	int _valueKind, _device, _rank, _worldSize;
 	bool _sizeTracking, _wantSizeHistory;
+	double _bimodalSigmas;
 };
 
 #ifdef KMERNATOR_AMD_SHIM_MPI

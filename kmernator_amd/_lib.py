@@ -101,6 +101,7 @@ EXPORTS = [
     "kmr_partition_config_init", "kmr_partition_rounds", "kmr_partition_reads", "kmr_partition_reads_dev", "kmr_partition_read_batch", "kmr_partition_read_batch_dev",
     "kmr_picks_segments_info", "kmr_picks_segments_copy",
     "kmr_normalize_config_init", "kmr_normalize_reads", "kmr_normalize_reads_dev", "kmr_normalize_read_batch", "kmr_normalize_read_batch_dev", "kmr_normalize_info",
+    "kmr_set_bimodal_sigmas", "kmr_bimodal_copy", "kmr_select_bimodal",
     "kmr_dump_text_size", "kmr_dump_text", "kmr_text_info", "kmr_text_copy", "kmr_text_device_ptr", "kmr_text_free",
     "kmr_identify_pairs", "kmr_identify_pairs_dev", "kmr_pairs_info", "kmr_pairs_copy", "kmr_pairs_device_ptrs", "kmr_pairs_free",
     "kmr_dedup_config_init", "kmr_dedup_fragments", "kmr_dedup_fragments_dev", "kmr_dedup_info", "kmr_dedup_copy", "kmr_dedup_device_ptrs",
@@ -240,6 +241,9 @@ def load():
     for name in ("kmr_normalize_read_batch", "kmr_normalize_read_batch_dev"):
         getattr(lib, name).argtypes = [vp, vp, vp, C.c_uint64, i64p, i64p, C.c_uint64, u8p, u32p, u32p, u64p, C.c_uint32, ncp, C.POINTER(vp)]
     lib.kmr_normalize_info.argtypes = [vp, u64p, u64p, u64p]
+    lib.kmr_set_bimodal_sigmas.argtypes = [vp, C.c_double]
+    lib.kmr_bimodal_copy.argtypes = [vp, u64p, C.c_uint64]
+    lib.kmr_select_bimodal.argtypes = [vp, u64p, C.c_uint64]
     lib.kmr_picks_segments_info.argtypes = [vp, u32p, u32p]
     lib.kmr_picks_segments_copy.argtypes = [vp, f32p, u8p, u64p, u64p, u64p, u64p, C.POINTER(C.c_int32)]
     lib.kmr_picks_info.argtypes = [vp, u64p, u64p]

@@ -2223,6 +2223,7 @@ int kmr_tune(kmr_handle *h, const char *knob, double value) {
 	else if (k == "dump_timing") h->tune.dump_timing = value != 0;
 	else if (k == "pairs_timing") h->tune.pairs_timing = value != 0;
 	else if (k == "dedup_timing") h->tune.dedup_timing = value != 0;
+	else if (k == "bimodal_window") h->tune.bimodal_window = value >= 0 && value <= BM_CAP ? (int)value : -1;
 	else if (k == "partition_units") h->tune.partition_units = value >= 1 && value <= 8192 ? (uint32_t)value : 0;
 	else if (k == "pair_hash_bits") h->tune.pair_hash_bits = value >= 1 && value < 64 ? (uint32_t)value : 64;
 	else if (k == "dump_piece_bytes") h->tune.dump_piece_bytes = value >= 1 ? (uint64_t)value : 0;
@@ -2628,6 +2629,27 @@ int lookup_stream(kmr_handle *h, const ReadsView &rv, uint64_t total_bases, uint
 }
 
 namespace kmr_host {
+/* The scoring of a batch whose counts are at hand, queued on the handle's stream: score_reads_kernel and, with
+ * kmr_set_bimodal_sigmas >= 0 only, bimodal_trim_kernel behind it.  *words: that pass's word per read (in bimodal_buf), null
+ * while the option is off -- then nothing but the first kernel is launched and nothing is allocated. */
+static int launch_scoring(kmr_handle *h, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, const uint32_t *counts, const uint64_t *count_off,
+                          double minimum_kmer_score, int scoring_type, uint32_t *dto, uint32_t *dtl, float *dsc, uint8_t *dwt, const uint64_t **words) {
+	*words = nullptr;
+	h->bimodal_n = n_reads; h->bimodal_on = false;
+	hipLaunchKernelGGL(score_reads_kernel, dim3((unsigned)std::min<uint64_t>(((n_reads + 63) / 64 + SC_WAVES - 1) / SC_WAVES, 1u << 16)), dim3(SC_WAVES * 64), 0, h->stream, bases, offsets, n_reads, h->k, counts, count_off,
+	                   (float)minimum_kmer_score, scoring_type, dto, dtl, dsc, dwt);
+	HIPCHK(h, hipGetLastError());
+	if (!(h->bimodal_sigmas >= 0.0)) return 0;
+	int rc = h->bimodal_buf.reserve(h, "bimodal_buf", 8 * n_reads, 8 * n_reads + n_reads); if (rc) return rc;
+	uint64_t *w = h->bimodal_buf.get<uint64_t>();
+	const uint32_t window = h->tune.bimodal_window < 0 ? (uint32_t)BM_CAP : (uint32_t)h->tune.bimodal_window;
+	hipLaunchKernelGGL(bimodal_trim_kernel, dim3((unsigned)std::min<uint64_t>((n_reads + BM_WAVES - 1) / BM_WAVES, 1u << 16)), dim3(BM_WAVES * 64), 0, h->stream, n_reads, h->k, counts, count_off,
+	                   h->bimodal_sigmas, scoring_type, window, dto, dtl, dsc, dwt, w);
+	HIPCHK(h, hipGetLastError());
+	h->bimodal_on = true; *words = w;
+	return 0;
+}
+
 /* ReadSelector::scoreAndTrimReads (src/ReadSelector.h:1182-1207) on the weak map; s_b / s_o: device bases and offsets,
  * offsets: the same offsets on the host */
 int score_reads_core(kmr_handle *h, const uint8_t *s_b, const uint64_t *s_o, uint64_t n_reads, double minimum_kmer_score, int scoring_type,
@@ -2690,10 +2712,9 @@ int score_reads_core(kmr_handle *h, const uint8_t *s_b, const uint64_t *s_o, uin
 		rc = with_w(h, [&](auto W) { return lookup_reads_t<W()>(h, rv, dcounts, dcoff, true); });
 	}
 	if (!rc) {
-		hipLaunchKernelGGL(score_reads_kernel, dim3((unsigned)std::min<uint64_t>(((n_reads + 63) / 64 + SC_WAVES - 1) / SC_WAVES, 1u << 16)), dim3(SC_WAVES * 64), 0, h->stream, s_b, s_o, n_reads, h->k, dcounts, dcoff,
-		                   (float)minimum_kmer_score, scoring_type, dto, dtl, dsc, dwt);
-		HIPCHK(h, hipGetLastError());
-		if (keep) { keep->trim_offset = dto; keep->trim_length = dtl; keep->score = dsc; keep->was_trimmed = dwt; }      /* the results stay on the device */
+		const uint64_t *dwords;
+		rc = launch_scoring(h, s_b, s_o, n_reads, dcounts, dcoff, minimum_kmer_score, scoring_type, dto, dtl, dsc, dwt, &dwords); if (rc) return rc;
+		if (keep) { keep->trim_offset = dto; keep->trim_length = dtl; keep->score = dsc; keep->was_trimmed = dwt; keep->bimodal = dwords; }      /* the results stay on the device */
 		else {
 			HIPCHK(h, hipMemcpyAsync(trim_offset, dto, 4 * n_reads, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipMemcpyAsync(trim_length, dtl, 4 * n_reads, hipMemcpyDeviceToHost, h->stream));
 			HIPCHK(h, hipMemcpyAsync(score, dsc, 4 * n_reads, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipMemcpyAsync(was_trimmed, dwt, n_reads, hipMemcpyDeviceToHost, h->stream));
@@ -2727,6 +2748,25 @@ int kmr_score_read_batch(kmr_handle *h, const kmr_reads *r, double minimum_kmer_
 	if (r->n == 0) return KMR_OK;
 	hipSetDevice(h->device);
 	return score_reads_core(h, r->bases.get<uint8_t>(), r->offsets.get<uint64_t>(), r->n, minimum_kmer_score, scoring_type, trim_offset, trim_length, score, was_trimmed);
+}
+
+/* --bimodal-sigmas of the handle's scoring calls (ReadSelector::_bimodalSigmas; negative = off, the default) */
+int kmr_set_bimodal_sigmas(kmr_handle *h, double sigmas) {
+	if (!h) return KMR_ERR_INVALID_ARG;
+	if (sigmas != sigmas) return fail(h, KMR_ERR_INVALID_ARG, "kmr_set_bimodal_sigmas: NaN");
+	h->bimodal_sigmas = sigmas;
+	return KMR_OK;
+}
+int kmr_bimodal_copy(kmr_handle *h, uint64_t *words, uint64_t n_reads) {
+	if (!h || (n_reads && !words)) return KMR_ERR_INVALID_ARG;
+	if (h->bimodal_n == ~0ull) return fail(h, KMR_ERR_STATE, "kmr_bimodal_copy before any scoring call");
+	if (n_reads != h->bimodal_n) return fail(h, KMR_ERR_INVALID_ARG, "kmr_bimodal_copy: the last scoring call held " + std::to_string(h->bimodal_n) + " reads, not " + std::to_string(n_reads));
+	if (!n_reads) return KMR_OK;
+	if (!h->bimodal_on) { memset(words, 0, 8 * n_reads); return KMR_OK; }
+	hipSetDevice(h->device);
+	HIPCHK(h, hipMemcpyAsync(words, h->bimodal_buf.get(), 8 * n_reads, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipStreamSynchronize(h->stream));
+	return KMR_OK;
 }
 
 static DevMap *map_of(kmr_handle *h, int which) {
@@ -3023,9 +3063,10 @@ int kmr_score_counts_dev(kmr_handle *h, const void *dev_bases, const void *dev_o
 	HIPCHK(h, b_dto.alloc(4 * n_reads)); HIPCHK(h, b_dtl.alloc(4 * n_reads)); HIPCHK(h, b_dsc.alloc(4 * n_reads)); HIPCHK(h, b_dwt.alloc(n_reads));
 	uint32_t *dto = b_dto.get<uint32_t>(), *dtl = b_dtl.get<uint32_t>(); float *dsc = b_dsc.get<float>(); uint8_t *dwt = b_dwt.get<uint8_t>();
 	/* k-mer i of read r sits at position offsets[r] + i: the offsets are their own count offsets */
-	hipLaunchKernelGGL(score_reads_kernel, dim3((unsigned)std::min<uint64_t>(((n_reads + 63) / 64 + SC_WAVES - 1) / SC_WAVES, 1u << 16)), dim3(SC_WAVES * 64), 0, h->stream, (const uint8_t *)dev_bases, (const uint64_t *)dev_offsets, n_reads, h->k,
-	                   (const uint32_t *)dev_position_counts, (const uint64_t *)dev_offsets, (float)minimum_kmer_score, scoring_type, dto, dtl, dsc, dwt);
-	hipError_t e = hipGetLastError();
+	const uint64_t *dwords;
+	int rc = launch_scoring(h, (const uint8_t *)dev_bases, (const uint64_t *)dev_offsets, n_reads, (const uint32_t *)dev_position_counts, (const uint64_t *)dev_offsets, minimum_kmer_score, scoring_type, dto, dtl, dsc, dwt, &dwords);
+	if (rc) { hipStreamSynchronize(h->stream); return rc; }
+	hipError_t e = hipSuccess;
 	if (e == hipSuccess) e = hipMemcpyAsync(trim_offset, dto, 4 * n_reads, hipMemcpyDeviceToHost, h->stream);
 	if (e == hipSuccess) e = hipMemcpyAsync(trim_length, dtl, 4 * n_reads, hipMemcpyDeviceToHost, h->stream);
 	if (e == hipSuccess) e = hipMemcpyAsync(score, dsc, 4 * n_reads, hipMemcpyDeviceToHost, h->stream);

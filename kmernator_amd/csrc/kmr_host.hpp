@@ -114,6 +114,7 @@ struct HandleMem {                   /* ... by kmr_destroy */
 	DevBuf trk;                      /* size tracker: one record per read of the last call */
 	DevBuf scan_sums;
 	DevBuf score_buf;                /* temporaries of kmr_score_reads*, grow-only */
+	DevBuf bimodal_buf;              /* one word per read of the last scoring call that ran with kmr_set_bimodal_sigmas >= 0 (bimodal_trim_kernel), grow-only; never allocated while the option is off */
 	DevBuf fasta_buf[2][3];          /* scratch of kmr_ingest_fasta* (FASTA text, QUAL text; per block, per line, per record), grow-only */
 	DevBuf lut;                      /* lookup accelerator over the weak map (LutView) */
 	DevBuf dPk;                      /* build_mode 3: table of k-fold quality products */
@@ -184,6 +185,7 @@ struct KMR_HIDDEN Tuning {
 	bool dedup_timing = false;         /* kmr_dedup_fragments*: time the key kernel, the sorts, the consensus kernel and the whole call with HIP events (kmr_build_info; measurement tools) */
 	uint32_t partition_units = 0;      /* kmr_partition_*: most units (wavefronts over contiguous reads) of the partition, 0 = the default of 8192 (tests: a few, so that a unit walks many tiles) */
 	uint32_t pair_hash_bits = 64;      /* kmr_identify_pairs*: bits of the common name's hash the phase-2 sort keys keep (tests: a few bits, so that distinct names share a key) */
+	int bimodal_window = -1;           /* bimodal_trim_kernel: the longest run it stages in LDS (-1: BM_CAP; tests: 0, so that every run is walked in global memory) */
 	bool no_coarse_lists = true;       /* exchange: scatter into the job's fine lists (default) or, kmr_tune("coarse_lists", 1), into coarse ones that the owner splits before the count pass (sk_refine_kernel: not yet fast enough to pay) */
 };
 
@@ -239,6 +241,11 @@ struct KMR_HIDDEN kmr_handle : HandleMem, BuildMem, ExchangeMem {
 	/* the radix partition of the last kmr_finalize (kmr_build_info "bb_path": 0 none, 1 measured bins, 2 bins of one capacity; "bb_fallback": a bin
 	 * overflowed and the build was made again with measured bins), and the overflow word of one that is on the stream (null: none) */
 	int last_bb_path = 0; bool last_bb_fallback = false; uint32_t *bb_overflow = nullptr;
+	/* --bimodal-sigmas (kmr_set_bimodal_sigmas; ReadSelector::_bimodalSigmas, -1 = off) and what the last scoring call left: the number of its reads
+	 * (~0: there was none) and whether bimodal_buf holds their words (kmr_bimodal_copy).  sel_bimodal: the words kmr_select_bimodal handed in for the
+	 * next selecting call over host arrays */
+	double bimodal_sigmas = -1.0; uint64_t bimodal_n = ~0ull; bool bimodal_on = false;
+	std::vector<uint64_t> sel_bimodal; bool sel_bimodal_set = false;
 	int last_score_path = 0;      /* kmr_build_info "score_path": where the last kmr_score_reads / _read_batch / kmr_filter_read_batch got its counts */
 	bool last_early_overflowed = false;                       /* ... or that it voided one because its buffers overflowed */
 	double last_score_ms = 0, last_select_ms = 0, last_write_ms = 0;      /* the last kmr_filter_read_batch* / kmr_select_reads*: scoring, selection + writer, writer alone (HIP events, taken with kmr_tune "select_timing" only; kmr_build_info) */
@@ -381,7 +388,7 @@ void quality_table(double P[256], unsigned minQ, unsigned startChar);
 int exclusive_scan(kmr_handle *h, const uint32_t *in, uint64_t n, uint64_t *out /* n+1 */);
 int exclusive_scan_queue(kmr_handle *h, const uint32_t *in, uint64_t n, uint64_t *out /* n+1 */);      /* the same left on the handle's stream: the host does not wait */
 int num_cus(kmr_handle *h);
-struct ScoreDev { uint32_t *trim_offset, *trim_length; float *score; uint8_t *was_trimmed; };      /* the results in score_buf, good until the handle's next scoring call */
+struct ScoreDev { uint32_t *trim_offset, *trim_length; float *score; uint8_t *was_trimmed; const uint64_t *bimodal; };      /* the results in score_buf (bimodal: the words in bimodal_buf, null while --bimodal-sigmas is off), good until the handle's next scoring call */
 int score_reads_core(kmr_handle *h, const uint8_t *s_b, const uint64_t *s_o, uint64_t n_reads, double minimum_kmer_score, int scoring_type,
                      uint32_t *trim_offset, uint32_t *trim_length, float *score, uint8_t *was_trimmed, ScoreDev *keep = nullptr);
 

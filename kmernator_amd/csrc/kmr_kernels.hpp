@@ -895,9 +895,37 @@ __global__ void scatter_counts_kernel(const uint32_t *counts, const uint32_t *po
 
 /* ReadSelector::scoreAndTrimReads for one read per lane (src/ReadSelector.h:1182-1207): numKmers is cut at the
  * first N/X markup (_setNumKmers :1037-1047), the read is trimmed to the first longest run of k-mers whose count
- * is >= minScore (trimReadByMinimumKmerScore :949-1014, bimodal detection off), the run is scored
+ * is >= minScore (trimReadByMinimumKmerScore :949-1014; its bimodal cut is bimodal_trim_kernel below, a pass of its
+ * own that runs behind this one when --bimodal-sigmas is on), the run is scored
  * (scoreReadByScoringType :1094-1180) and setTrimHeaders (:1015-1036) converts the run to bases. */
 enum { SCORE_SUM = 0, SCORE_MEDIAN = 1, SCORE_MIN = 2, SCORE_MAX = 3, SCORE_AVG = 4 };
+/* scoreReadByScoringType over a run of n >= 1 counts (LDS copy as u16, or global u32) */
+template <typename T>
+__device__ __forceinline__ float score_run(const T *run, uint32_t n, int scoring) {
+	if (scoring == SCORE_MEDIAN) {
+		/* sorted[n/2]: the smallest v with #(x <= v) > n/2, found by bisection on the 16-bit count */
+		const uint32_t t = n / 2;
+		uint32_t lo = 65535, hi = 0;          /* the bisection starts from the run's own range, not from 16 bits */
+		for (uint32_t i = 0; i < n; i++) { const uint32_t v = run[i]; lo = v < lo ? v : lo; hi = v > hi ? v : hi; }
+		while (lo < hi) {
+			const uint32_t mid = (lo + hi) >> 1;
+			uint32_t le = 0;
+			for (uint32_t i = 0; i < n; i++) le += (uint32_t)run[i] <= mid ? 1u : 0u;
+			if (le > t) hi = mid; else lo = mid + 1;
+		}
+		return (float)lo;
+	}
+	if (scoring == SCORE_AVG) {
+		double sum = 0.0; for (uint32_t i = 0; i < n; i++) sum += (float)(uint32_t)run[i];
+		return (float)(sum / (double)n);
+	}
+	if (scoring == SCORE_MIN || scoring == SCORE_MAX) {
+		uint32_t m = run[0];
+		for (uint32_t i = 1; i < n; i++) { const uint32_t v = run[i]; m = scoring == SCORE_MAX ? (v > m ? v : m) : (v < m ? v : m); }
+		return (float)m;
+	}
+	return 0.0f;     /* KS_SUM: scoreReadBySumKmer only assigns the score when byAvg (:1149-1162) */
+}
 /* one read: numKmers is already cut at the first markup; cv = its counts (LDS copy as u16, or global u32) */
 template <typename T>
 __device__ __forceinline__ void score_one_read(const T *cv, uint32_t numKmers, uint32_t k, float minScore, int scoring,
@@ -910,33 +938,9 @@ __device__ __forceinline__ void score_one_read(const T *cv, uint32_t numKmers, u
 	}
 	if (len > bestLen) { bestLen = len; bestOff = off; }
 	trimmedOut = bestLen < numKmers;
-	float sc = -1.0f;
-	if (bestLen > 0) {
-		const T *run = cv + bestOff;
-		if (scoring == SCORE_MEDIAN) {
-			/* sorted[n/2]: the smallest v with #(x <= v) > n/2, found by bisection on the 16-bit count */
-			const uint32_t t = bestLen / 2;
-			uint32_t lo = 65535, hi = 0;          /* the bisection starts from the run's own range, not from 16 bits */
-			for (uint32_t i = 0; i < bestLen; i++) { const uint32_t v = run[i]; lo = v < lo ? v : lo; hi = v > hi ? v : hi; }
-			while (lo < hi) {
-				const uint32_t mid = (lo + hi) >> 1;
-				uint32_t le = 0;
-				for (uint32_t i = 0; i < bestLen; i++) le += (uint32_t)run[i] <= mid ? 1u : 0u;
-				if (le > t) hi = mid; else lo = mid + 1;
-			}
-			sc = (float)lo;
-		} else if (scoring == SCORE_AVG) {
-			double sum = 0.0; for (uint32_t i = 0; i < bestLen; i++) sum += (float)(uint32_t)run[i];
-			sc = (float)(sum / (double)bestLen);
-		} else if (scoring == SCORE_MIN || scoring == SCORE_MAX) {
-			uint32_t m = run[0];
-			for (uint32_t i = 1; i < bestLen; i++) { const uint32_t v = run[i]; m = scoring == SCORE_MAX ? (v > m ? v : m) : (v < m ? v : m); }
-			sc = (float)m;
-		} else sc = 0.0f;     /* KS_SUM: scoreReadBySumKmer only assigns the score when byAvg (:1149-1162) */
-	}
 	tOff = bestLen > 0 ? bestOff : 0u;
 	tLen = bestLen > 0 ? bestLen + k - 1 : 0u;
-	scOut = sc;
+	scOut = bestLen > 0 ? score_run<T>(cv + bestOff, bestLen, scoring) : -1.0f;
 }
 
 /* A wavefront takes 64 consecutive reads: their bases are one contiguous range, searched for markups with coalesced 16-byte
@@ -1010,6 +1014,113 @@ __global__ void other_markup_kernel(const uint8_t *bases, uint64_t b0, uint64_t 
 		}
 	}
 	if (any) *found = 1u;
+}
+
+/* --bimodal-sigmas: the cut trimReadByMinimumKmerScore makes inside the run it found (src/ReadSelector.h:981-1008,
+ * Statistics::findBimodalPartition and MeanStdCount, src/Utils.h:1000-1056), as a pass of its own behind score_reads_kernel.
+ * The run's values v[0..n), n >= 3, are split at every p = 1 .. n-1 into first = v[0..p) and second = v[p..n).  Of a side:
+ *   mean    the f64 sum in index order, divided by the count only where the count is above 1 (the sum of at most 2^32 integers
+ *           <= 65535 is exact, so the means come from integer prefix sums and one division);
+ *   stdDev  what the reference calls so is the VARIANCE, never rooted: the f64 sum of (x - mean) * (x - mean) in index order over
+ *           count - 1, 0 for a single value; then the Poisson floor: where mean > 0 and stdDev < sqrt(mean), sqrt(mean).
+ * diff = abs(first.mean - second.mean) is C's int abs(int) there (an unqualified abs on a double with <cstdlib> and <cmath>
+ * included and no using-directive in scope): the difference is truncated toward zero to an int before it is compared.  That
+ * reading is the contract here.  A split qualifies if diff > sigmas * max(first.stdDev, second.stdDev); the qualifying split
+ * of the strictly largest diff wins, so among equal diffs (they are integers: common) the earliest p.  first.mean > second.mean
+ * keeps the head (run length p), otherwise the tail (offset + p, length n - p); the score is that of the reduced run.
+ *
+ * One wavefront per read.  The run is staged in LDS as u16 where it fits the window, else walked in global memory.  Lane l takes
+ * the splits p = l + 1, l + 65, ...: a wave-wide inclusive scan of 64 values gives every lane its prefix sum, hence both means and
+ * diff.  Both variances are at least their floors, so a split with diff <= sigmas * max(sqrt(m1), sqrt(m2)) cannot qualify, and
+ * one whose diff is not above the lane's best so far cannot win: neither needs the variances.  Where a lane of the wave does need
+ * them, every lane walks the run once, all lanes reading the same element in the same step (an LDS broadcast), each adding the
+ * squared deviation to the accumulator of the side the element is on for its own p.  The sums must not be contracted to fused
+ * multiply-adds (the reference rounds the product, then the sum): fp contract is off in bimodal_search. */
+static const int BM_WAVES = 4, BM_CAP = 4096;
+template <typename T>
+__device__ __forceinline__ uint32_t bimodal_search(const T *v, uint32_t n, double sigmas, int lane, double &m1Out, double &m2Out) {
+#pragma clang fp contract(off)
+	unsigned long long total = 0;
+	for (uint32_t i = lane; i < n; i += 64) total += (uint32_t)v[i];
+	for (int off = 32; off > 0; off >>= 1) total += __shfl_xor(total, off, 64);
+	double myDiff = 0.0, myM1 = 0.0, myM2 = 0.0; uint32_t myP = 0;
+	unsigned long long carry = 0;
+	for (uint32_t base = 0; base + 1 < n; base += 64) {
+		const uint32_t i = base + lane, p = i + 1;
+		unsigned long long x = i < n ? (unsigned long long)(uint32_t)v[i] : 0ull;
+		for (int d = 1; d < 64; d <<= 1) { const unsigned long long y = __shfl_up(x, d, 64); if (lane >= d) x += y; }
+		const unsigned long long s1 = carry + x;
+		carry += __shfl(x, 63, 64);
+		double m1 = 0.0, m2 = 0.0, diff = 0.0; bool need = false;
+		if (p < n) {
+			m1 = (double)s1; if (p > 1) m1 /= (double)p;
+			m2 = (double)(total - s1); if (n - p > 1) m2 /= (double)(n - p);
+			const int t = (int)(m1 - m2);
+			diff = (double)(t < 0 ? -t : t);
+			const double f1 = m1 > 0.0 ? sqrt(m1) : 0.0, f2 = m2 > 0.0 ? sqrt(m2) : 0.0;
+			need = diff > myDiff && diff > sigmas * (f1 < f2 ? f2 : f1);
+		}
+		if (!__any(need)) continue;
+		double q1 = 0.0, q2 = 0.0;
+		for (uint32_t j = 0; j < n; j++) {
+			const double xv = (double)(float)(uint32_t)v[j];
+			const bool inFirst = j < p;
+			const double e = xv - (inFirst ? m1 : m2), sq = e * e;
+			q1 += inFirst ? sq : 0.0; q2 += inFirst ? 0.0 : sq;      /* (adding +0.0 to a sum that is >= +0.0 leaves it as it is) */
+		}
+		if (need) {
+			double sd1 = p > 1 ? q1 / (double)(p - 1) : 0.0, sd2 = n - p > 1 ? q2 / (double)(n - p - 1) : 0.0;
+			if (m1 > 0.0) { const double f = sqrt(m1); if (sd1 < f) sd1 = f; }
+			if (m2 > 0.0) { const double f = sqrt(m2); if (sd2 < f) sd2 = f; }
+			if (diff > sigmas * (sd1 < sd2 ? sd2 : sd1)) { myDiff = diff; myP = p; myM1 = m1; myM2 = m2; }
+		}
+	}
+	/* the largest diff, then the smallest p (diff <= 65535) */
+	unsigned long long key = myP ? ((unsigned long long)(uint32_t)myDiff << 32) | (0xffffffffu - myP) : 0ull, best = key;
+	for (int off = 32; off > 0; off >>= 1) { const unsigned long long o = __shfl_xor(best, off, 64); best = o > best ? o : best; }
+	if (!best) return 0;
+	const int src = __ffsll((unsigned long long)__ballot(key == best)) - 1;
+	m1Out = __shfl(myM1, src, 64); m2Out = __shfl(myM2, src, 64);
+	return __shfl(myP, src, 64);
+}
+
+/* counts / count_off as score_reads_kernel takes them; the four result arrays are that kernel's and are rewritten for the reads
+ * that are cut.  words[r] = 0, or p + k in bits 0-31, (int)first.mean in bits 32-47, (int)second.mean in bits 48-63 (the tag is
+ * InvBimodal where the first is the smaller).  window <= BM_CAP: the longest run staged in LDS. */
+__global__ __launch_bounds__(BM_WAVES * 64)
+void bimodal_trim_kernel(uint64_t n_reads, uint32_t k, const uint32_t *counts, const uint64_t *count_off, double sigmas, int scoring, uint32_t window,
+                         uint32_t *trimOffset, uint32_t *trimLength, float *score, uint8_t *wasTrimmed, uint64_t *words) {
+	__shared__ uint16_t s_v[BM_WAVES][BM_CAP];
+	const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+	for (uint64_t r = (uint64_t)blockIdx.x * BM_WAVES + wave; r < n_reads; r += (uint64_t)gridDim.x * BM_WAVES) {
+		/* (the read is the wavefront's: its run's length, offset and address are the same in every lane, and are told to be) */
+		const uint32_t tl = (uint32_t)__builtin_amdgcn_readfirstlane((int)trimLength[r]);
+		const uint32_t n = tl >= k ? tl - k + 1 : 0;
+		uint64_t word = 0;
+		if (n >= 3) {
+			const uint32_t to = (uint32_t)__builtin_amdgcn_readfirstlane((int)trimOffset[r]);
+			const uint64_t c0 = count_off[r] + to;
+			const uint32_t *g = counts + (((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(c0 >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)c0));
+			const bool staged = n <= window;
+			double m1 = 0.0, m2 = 0.0; uint32_t p;
+			if (staged) {
+				for (uint32_t i = lane; i < n; i += 64) s_v[wave][i] = (uint16_t)g[i];
+				__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
+				p = bimodal_search<uint16_t>(s_v[wave], n, sigmas, lane, m1, m2);
+			} else p = bimodal_search<uint32_t>(g, n, sigmas, lane, m1, m2);
+			if (p) {
+				const bool head = m1 > m2;
+				const uint32_t off = head ? 0u : p, len = head ? p : n - p;
+				word = (uint64_t)(p + k) | ((uint64_t)(uint32_t)(int)m1 << 32) | ((uint64_t)(uint32_t)(int)m2 << 48);
+				if (lane == 0) {
+					score[r] = staged ? score_run<uint16_t>(s_v[wave] + off, len, scoring) : score_run<uint32_t>(g + off, len, scoring);
+					trimOffset[r] = to + off; trimLength[r] = len + k - 1; wasTrimmed[r] = 1;
+				}
+			}
+			__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();      /* s_v is rewritten for the next read */
+		}
+		if (lane == 0) words[r] = word;
+	}
 }
 #endif
 

@@ -29,6 +29,13 @@ namespace kmr {
 
 enum { SEL_ERR_MATE = 1, SEL_ERR_NAME = 2, SEL_ERR_PAIR = 4, SEL_ERR_TWICE = 8 };      /* the last two: the pair list of kmr_normalize.hpp */
 static const int SEL_THREADS = 256, SEL_WAVES = SEL_THREADS / 64, SEL_LABEL_CAP = 128;
+/* the longest label sel_label writes, part by part, each with its leading blank:
+ *   " AFTrim:" u32 "+" i64 of a difference of two u32       8 + 10 + 1 + 11
+ *   " InvBimodal@" u32 ":" u16 "/" u16                     12 + 10 + 1 + 5 + 1 + 5
+ *   " Trim:" u32 "+" u32                                     6 + 10 + 1 + 10
+ *   " MedianScore:" i32 (the longest of the five names)     13 + 11 */
+static const int SEL_LABEL_MOST = (8 + 10 + 1 + 11) + (12 + 10 + 1 + 5 + 1 + 5) + (6 + 10 + 1 + 10) + (13 + 11);
+static_assert(SEL_LABEL_MOST <= SEL_LABEL_CAP, "a label must fit the wavefront's LDS buffer");
 
 struct SelectParams {
 	const uint8_t *bases, *quals;            /* the batch */
@@ -41,6 +48,7 @@ struct SelectParams {
 	const uint32_t *trim_off, *trim_len;
 	const float *score;
 	const uint8_t *was_trimmed;
+	const uint64_t *bimodal;                 /* bimodal_trim_kernel's word per read; null: --bimodal-sigmas off */
 	uint64_t n;
 	float min_score, min_read_length;
 	uint32_t both_pass, fasta, scoring;
@@ -83,13 +91,21 @@ __device__ __forceinline__ const char *sel_score_label(uint32_t scoring) {
 }
 /* The label of read i with its leading blank (Read::LABEL_SEP), as FilterKnownOddities (AFTrim) and setTrimHeaders
  * (src/ReadSelector.h:1015-1036) compose it; a discarded read has none.  Returns the length; writes only when asked to
- * (at most 92 bytes: three tags of 7 + 5 + 12 characters, five numbers of at most 11, four separators). */
+ * (at most SEL_LABEL_MOST bytes).  The tag of the bimodal cut (src/ReadSelector.h:987-1005) stands between AFTrim and Trim: the
+ * trim label holds it before setTrimHeaders appends. */
 __device__ __forceinline__ uint32_t sel_label(const SelectParams &P, uint64_t i, uint8_t *dst, bool write) {
 	if (sel_discarded(P, i)) return 0;
 	uint32_t at = 0;
 	if (P.af_action && P.af_action[i] == 1) {
 		at = sel_put_str(dst, at, " AFTrim:", write);
 		at = sel_put_int(dst, at, P.af_min[i], write); at = sel_put_char(dst, at, '+', write); at = sel_put_int(dst, at, (int64_t)P.af_max[i] - (int64_t)P.af_min[i], write);
+	}
+	const uint64_t bm = P.bimodal ? P.bimodal[i] : 0;
+	if (bm) {
+		const uint32_t m1 = (uint32_t)(bm >> 32) & 0xffffu, m2 = (uint32_t)(bm >> 48);
+		at = sel_put_str(dst, at, m1 < m2 ? " InvBimodal@" : " Bimodal@", write);
+		at = sel_put_int(dst, at, (int64_t)(bm & 0xffffffffu), write); at = sel_put_char(dst, at, ':', write);
+		at = sel_put_int(dst, at, m1, write); at = sel_put_char(dst, at, '/', write); at = sel_put_int(dst, at, m2, write);
 	}
 	if (P.was_trimmed[i]) {
 		at = sel_put_str(dst, at, " Trim:", write);

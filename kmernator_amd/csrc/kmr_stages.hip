@@ -707,11 +707,11 @@ struct SelectCall {
 
 /* every pointer is device memory (mate and the three af_* may be null) */
 static SelectParams select_params(kmr_handle *h, const kmr_reads *r, const uint8_t *dtext, uint64_t text_len, const int64_t *dmate, const uint8_t *dact, const uint32_t *dmin,
-                                  const uint32_t *dmax, const uint32_t *dto, const uint32_t *dtl, const float *dsc, const uint8_t *dwt, const kmr_select_config *cfg) {
+                                  const uint32_t *dmax, const uint32_t *dto, const uint32_t *dtl, const float *dsc, const uint8_t *dwt, const uint64_t *dbm, const kmr_select_config *cfg) {
 	SelectParams P;
 	P.bases = r->bases.get<uint8_t>(); P.quals = r->quals.get<uint8_t>(); P.offsets = r->offsets.get<uint64_t>(); P.name_off = r->name_off.get<uint64_t>(); P.name_len = r->name_len.get<uint32_t>();
 	P.text = dtext; P.text_len = text_len; P.mate = dmate; P.af_action = dact; P.af_min = dmin; P.af_max = dmax;
-	P.trim_off = dto; P.trim_len = dtl; P.score = dsc; P.was_trimmed = dwt; P.n = r->n;
+	P.trim_off = dto; P.trim_len = dtl; P.score = dsc; P.was_trimmed = dwt; P.bimodal = dbm; P.n = r->n;
 	P.min_score = (float)cfg->minimum_score; P.min_read_length = cfg->min_read_length; P.both_pass = cfg->both_pass ? 1u : 0u; P.fasta = cfg->format; P.scoring = cfg->scoring_type;
 	P.out_base = cfg->output_quality_base; P.qual_shift = (int32_t)cfg->output_quality_base - (int32_t)h->cfg.fastq_start_char;
 	return P;
@@ -900,7 +900,11 @@ static int select_run(kmr_handle *h, const SelectCall &c, kmr_picks **out) {
 	const uint64_t n = r->n, n_pairs = c.read1 ? c.n_pairs : 0;
 	auto pk = make_result<kmr_picks>(h);      /* (ahead of tmp, as in every stage: a failed call waits for the stream before the result's buffers go too) */
 	Scratch tmp(h);
-	const uint8_t *dtext, *dact, *dwt = nullptr; const int64_t *dmate, *dr1, *dr2; const uint32_t *dmin, *dmax, *dto = nullptr, *dtl = nullptr; const float *dsc = nullptr; const uint64_t *dstarts;
+	const uint8_t *dtext, *dact, *dwt = nullptr; const int64_t *dmate, *dr1, *dr2; const uint32_t *dmin, *dmax, *dto = nullptr, *dtl = nullptr; const float *dsc = nullptr; const uint64_t *dstarts, *dbm = nullptr;
+	/* the tags kmr_select_bimodal left for this call (the host-array forms; a fused call scores, and tags, its reads itself) */
+	std::vector<uint64_t> tags; bool tagged = false;
+	if (!c.fused) { tags.swap(h->sel_bimodal); tagged = h->sel_bimodal_set; h->sel_bimodal_set = false; }
+	if (tagged && tags.size() != n) return fail(h, KMR_ERR_INVALID_ARG, std::string(c.who) + ": kmr_select_bimodal gave " + std::to_string(tags.size()) + " words, the batch holds " + std::to_string(n) + " reads");
 	rc = to_device(h, tmp, (const uint8_t *)c.text, c.text_len, &dtext, c.text_on_device); if (rc) return rc;
 	rc = to_device(h, tmp, c.mate, n, &dmate); if (rc) return rc;
 	rc = to_device(h, tmp, c.af_action, n, &dact); if (rc) return rc;
@@ -914,17 +918,18 @@ static int select_run(kmr_handle *h, const SelectCall &c, kmr_picks **out) {
 		rc = score_reads_core(h, r->bases.get<uint8_t>(), r->offsets.get<uint64_t>(), n, c.cfg->minimum_score, (int)c.cfg->scoring_type, nullptr, nullptr, nullptr, nullptr, &sd); if (rc) return rc;
 		timer.mark(1, h->stream);
 		if (timer.on) { HIPCHK(h, hipStreamSynchronize(h->stream)); h->last_score_ms = timer.ms(0, 1); }
-		dto = sd.trim_offset; dtl = sd.trim_length; dsc = sd.score; dwt = sd.was_trimmed;
+		dto = sd.trim_offset; dtl = sd.trim_length; dsc = sd.score; dwt = sd.was_trimmed; dbm = sd.bimodal;
 	} else if (!c.fused) {
 		rc = to_device(h, tmp, c.trim_offset, n, &dto); if (rc) return rc;
 		rc = to_device(h, tmp, c.trim_length, n, &dtl); if (rc) return rc;
 		rc = to_device(h, tmp, c.score, n, &dsc); if (rc) return rc;
 		rc = to_device(h, tmp, c.was_trimmed, n, &dwt); if (rc) return rc;
+		rc = to_device(h, tmp, tagged && n ? tags.data() : nullptr, n, &dbm); if (rc) return rc;
 	}
 	rc = to_device(h, tmp, c.n_inputs > 1 ? c.input_starts : nullptr, (uint64_t)c.n_inputs + 1, &dstarts); if (rc) return rc;
 	rc = to_device(h, tmp, c.read1, n_pairs, &dr1); if (rc) return rc;
 	rc = to_device(h, tmp, c.read2, n_pairs, &dr2); if (rc) return rc;
-	const SelectParams P = select_params(h, r, dtext, c.text_len, dmate, dact, dmin, dmax, dto, dtl, dsc, dwt, c.cfg);
+	const SelectParams P = select_params(h, r, dtext, c.text_len, dmate, dact, dmin, dmax, dto, dtl, dsc, dwt, dbm, c.cfg);
 	if (c.norm) rc = normalize_core(h, tmp, P, c.R, c.norm, dr1, dr2, n_pairs, dstarts, c.n_inputs, pk.get());
 	else rc = partition_core(h, tmp, P, c.R, dstarts, c.n_inputs, !c.plain, pk.get());
 	if (!rc) *out = pk.release();
@@ -952,6 +957,15 @@ static int select_normalized(kmr_handle *h, SelectCall &c, const kmr_normalize_c
 	return select_run(h, c, out);
 }
 
+/* the words kmr_bimodal_copy returned for the trims of the next kmr_select_reads* / kmr_partition_reads* / kmr_normalize_reads* on the handle:
+ * their tags go into the labels that call prints.  The call consumes them; NULL takes them back. */
+int kmr_select_bimodal(kmr_handle *h, const uint64_t *words, uint64_t n_reads) {
+	if (!h) return KMR_ERR_INVALID_ARG;
+	h->sel_bimodal.clear(); h->sel_bimodal_set = false;
+	if (!words) return KMR_OK;
+	h->sel_bimodal.assign(words, words + n_reads); h->sel_bimodal_set = true;
+	return KMR_OK;
+}
 int kmr_select_reads(kmr_handle *h, const kmr_reads *reads, const char *text, uint64_t text_len, const int64_t *mate, const uint8_t *af_action, const uint32_t *af_min_pass,
                      const uint32_t *af_max_pass, const uint32_t *trim_offset, const uint32_t *trim_length, const float *score, const uint8_t *was_trimmed,
                      const kmr_select_config *cfg, kmr_picks **out) {

@@ -387,7 +387,9 @@ def score_partitioned(spectrum, bases, offsets, minimum_kmer_score, scoring_type
 
     `spectrum`: finalized, rank / world_size configured (anything with lookup_requests / lookup_keys / scatter_counts /
     score_counts / sync and .k, as KmerSpectrum has).  bases: uint8 tensor, offsets: int64/uint64 tensor [n+1] starting at 0,
-    both on the spectrum's device.  Returns (trim_offset, trim_length, score, was_trimmed) host arrays for this rank's reads."""
+    both on the spectrum's device.  Returns (trim_offset, trim_length, score, was_trimmed) host arrays for this rank's reads.
+    The bimodal cut is the spectrum's setting (setBimodalSigmas, --bimodal-sigmas): the final score_counts honours it on every rank,
+    and spectrum.bimodal() then holds this rank's tags."""
     world = dist.get_world_size(group)
     dev = bases.device
     n = offsets.numel() - 1

@@ -6,6 +6,7 @@ purgeMinDepth (:1805), getCount (:701), storeMmap / restoreMmap (:476-518), getR
 (:455-459); MeraculousDistributedKmerSpectrum::dumpCounts/dumpGraphs (src/Meraculous.h:107-134).
 Errors surface as KmerSpectrumError (the reference throws LoggedException, src/Log.h:442-484).
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -314,15 +315,18 @@ class KmerSpectrum:
     def scatter_counts(self, counts, pos, n, position_counts):
         self._call("scatter_counts_dev", self.h, counts.data_ptr(), pos.data_ptr(), n, position_counts.data_ptr())
 
-    def score_counts(self, bases, offsets, n_reads, position_counts, minimum_kmer_score, scoring_type="MEDIAN"):
+    def score_counts(self, bases, offsets, n_reads, position_counts, minimum_kmer_score, scoring_type="MEDIAN", bimodal_sigmas=-1.0):
+        """kmr_score_counts_dev; bimodal_sigmas as scoreAndTrimReads takes it (the default leaves the handle's setting, which is
+        how the distributed scoring picks it up)"""
         to = np.zeros(n_reads, dtype=np.uint32)
         tl = np.zeros(n_reads, dtype=np.uint32)
         sc = np.zeros(n_reads, dtype=np.float32)
         wt = np.zeros(n_reads, dtype=np.uint8)
         if n_reads:
-            self._call("score_counts_dev", self.h, bases.data_ptr(), offsets.data_ptr(), n_reads, position_counts.data_ptr(), float(minimum_kmer_score),
-                       self.SCORING[scoring_type], to.ctypes.data_as(C.POINTER(C.c_uint32)), tl.ctypes.data_as(C.POINTER(C.c_uint32)),
-                       sc.ctypes.data_as(C.POINTER(C.c_float)), wt.ctypes.data_as(C.POINTER(C.c_uint8)))
+            with self._bimodal_for(bimodal_sigmas, n_reads):
+                self._call("score_counts_dev", self.h, bases.data_ptr(), offsets.data_ptr(), n_reads, position_counts.data_ptr(), float(minimum_kmer_score),
+                           self.SCORING[scoring_type], to.ctypes.data_as(C.POINTER(C.c_uint32)), tl.ctypes.data_as(C.POINTER(C.c_uint32)),
+                           sc.ctypes.data_as(C.POINTER(C.c_float)), wt.ctypes.data_as(C.POINTER(C.c_uint8)))
         return to, tl, sc, wt.astype(bool)
 
     def stream(self):
@@ -388,8 +392,57 @@ class KmerSpectrum:
 
     SCORING = {"SUM": 0, "MEDIAN": 1, "MIN": 2, "MAX": 3, "AVG": 4}
 
-    def scoreAndTrimReads(self, bases, offsets, minimum_kmer_score, scoring_type="MEDIAN"):
-        """ReadSelector::scoreAndTrimReads: (trim_offset, trim_length, score, was_trimmed) per read."""
+    # -- bimodal trimming (ReadSelector --bimodal-sigmas)
+    bimodal_sigmas = -1.0          # the handle's setting, as kmr_create leaves it
+    _scored_reads = None           # the number of reads of the last scoring call made through this object
+    bimodal_active = False         # ... and whether the bimodal cut was on in it
+
+    def setBimodalSigmas(self, sigmas):
+        """kmr_set_bimodal_sigmas: --bimodal-sigmas for every scoring call of this handle from now on (negative = off, the default).
+        With it on, a run of >= 3 k-mers is cut where its two halves differ most in mean depth, if the means lie more than
+        sigmas x max("stdDev") apart (include/kmernator_amd.h has the exact rule); bimodal() tells which reads were cut."""
+        self._call("set_bimodal_sigmas", self.h, float(sigmas))
+        self.bimodal_sigmas = float(sigmas)
+        return self
+
+    @contextlib.contextmanager
+    def _bimodal_for(self, sigmas, n_reads):
+        """one scoring call of n_reads reads: with sigmas >= 0 (or NaN, which the library refuses) under that setting, the handle's
+        own restored afterwards; the default, a negative value, leaves the handle's setting"""
+        sigmas = float(sigmas)
+        override = not sigmas < 0
+        if override:
+            self._call("set_bimodal_sigmas", self.h, sigmas)
+        try:
+            self.bimodal_active = override or self.bimodal_sigmas >= 0
+            self._scored_reads = int(n_reads)
+            yield
+        finally:
+            if override:
+                self._call("set_bimodal_sigmas", self.h, self.bimodal_sigmas)
+
+    def bimodal(self, n_reads=None):
+        """kmr_bimodal_copy: one u64 per read of the last scoring call (n_reads defaults to that call's): 0 = not cut, else
+        p + k in bits 0-31, (int)first.mean in bits 32-47, (int)second.mean in bits 48-63; all zero if the option was off"""
+        n = self._scored_reads if n_reads is None else int(n_reads)
+        if n is None:
+            raise KmerSpectrumError("bimodal: no scoring call yet")
+        words = np.zeros(max(1, n), dtype=np.uint64)
+        self._call("bimodal_copy", self.h, words.ctypes.data_as(C.POINTER(C.c_uint64)), n)
+        return words[:n]
+
+    @staticmethod
+    def bimodal_tag(word):
+        """the label part of one word of bimodal(): b"Bimodal@<pos>:<m1>/<m2>", b"InvBimodal@..." or b"" for 0"""
+        word = int(word)
+        if not word:
+            return b""
+        m1, m2 = (word >> 32) & 0xffff, word >> 48
+        return b"%sBimodal@%d:%d/%d" % (b"Inv" if m1 < m2 else b"", word & 0xffffffff, m1, m2)
+
+    def scoreAndTrimReads(self, bases, offsets, minimum_kmer_score, scoring_type="MEDIAN", bimodal_sigmas=-1.0):
+        """ReadSelector::scoreAndTrimReads: (trim_offset, trim_length, score, was_trimmed) per read.  bimodal_sigmas >= 0 turns
+        the bimodal cut on for this call; the default leaves the handle's setting (setBimodalSigmas; off unless set)."""
         bases = _u8(bases)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         n = offsets.size - 1
@@ -398,12 +451,13 @@ class KmerSpectrum:
         sc = np.zeros(n, dtype=np.float32)
         wt = np.zeros(n, dtype=np.uint8)
         if n:
-            self._call("score_reads", self.h, bases.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), n,
-                       float(minimum_kmer_score), self.SCORING[scoring_type], to.ctypes.data_as(C.POINTER(C.c_uint32)),
-                       tl.ctypes.data_as(C.POINTER(C.c_uint32)), sc.ctypes.data_as(C.POINTER(C.c_float)), wt.ctypes.data_as(C.POINTER(C.c_uint8)))
+            with self._bimodal_for(bimodal_sigmas, n):
+                self._call("score_reads", self.h, bases.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.POINTER(C.c_uint64)), n,
+                           float(minimum_kmer_score), self.SCORING[scoring_type], to.ctypes.data_as(C.POINTER(C.c_uint32)),
+                           tl.ctypes.data_as(C.POINTER(C.c_uint32)), sc.ctypes.data_as(C.POINTER(C.c_float)), wt.ctypes.data_as(C.POINTER(C.c_uint8)))
         return to, tl, sc, wt.astype(bool)
 
-    def scoreAndTrimReadSet(self, read_set, minimum_kmer_score, scoring_type="MEDIAN"):
+    def scoreAndTrimReadSet(self, read_set, minimum_kmer_score, scoring_type="MEDIAN", bimodal_sigmas=-1.0):
         """scoreAndTrimReads on a device-resident ReadSet (kmr_score_read_batch)"""
         n = read_set.n
         to = np.zeros(n, dtype=np.uint32)
@@ -411,8 +465,9 @@ class KmerSpectrum:
         sc = np.zeros(n, dtype=np.float32)
         wt = np.zeros(n, dtype=np.uint8)
         if n:
-            self._call("score_read_batch", self.h, read_set.r, float(minimum_kmer_score), self.SCORING[scoring_type], to.ctypes.data_as(C.POINTER(C.c_uint32)),
-                       tl.ctypes.data_as(C.POINTER(C.c_uint32)), sc.ctypes.data_as(C.POINTER(C.c_float)), wt.ctypes.data_as(C.POINTER(C.c_uint8)))
+            with self._bimodal_for(bimodal_sigmas, n):
+                self._call("score_read_batch", self.h, read_set.r, float(minimum_kmer_score), self.SCORING[scoring_type], to.ctypes.data_as(C.POINTER(C.c_uint32)),
+                           tl.ctypes.data_as(C.POINTER(C.c_uint32)), sc.ctypes.data_as(C.POINTER(C.c_float)), wt.ctypes.data_as(C.POINTER(C.c_uint8)))
         return to, tl, sc, wt.astype(bool)
 
     def histogram(self, nbins=256):
@@ -860,6 +915,7 @@ class ReadSelector(_DeviceObject):
             act[:k] = filter_results["action"]; lo[:k] = filter_results["min_pass"]; hi[:k] = filter_results["max_pass"]
             self.af = (act, lo, hi)
         self.trims = None
+        self.bimodal_words = None      # bimodal() of the scoreAndTrimReads that left the trims, if it ran with the option on
         self.scoring = "MEDIAN"
         self._picks = None
         self._sel = None
@@ -918,11 +974,19 @@ class ReadSelector(_DeviceObject):
         self.n_picked, self.bytes = n.value, b.value
         self._text = None
 
-    def scoreAndTrimReads(self, min_score, scoring="MEDIAN"):
-        """ReadSelector::scoreAndTrimReads(minimumKmerScore): (trim_offset, trim_length, score, was_trimmed) per read"""
+    def scoreAndTrimReads(self, min_score, scoring="MEDIAN", bimodal_sigmas=-1.0):
+        """ReadSelector::scoreAndTrimReads(minimumKmerScore): (trim_offset, trim_length, score, was_trimmed) per read.  With the
+        bimodal cut on (bimodal_sigmas >= 0, or the spectrum's setBimodalSigmas) .bimodal_words keeps the tags for the selection
+        that follows."""
         self.scoring = scoring
-        self.trims = self.sp.scoreAndTrimReadSet(self.reads, min_score, scoring)
+        self.trims = self.sp.scoreAndTrimReadSet(self.reads, min_score, scoring, bimodal_sigmas)
+        self.bimodal_words = self.sp.bimodal(self.reads.n) if self.reads.n and self.sp.bimodal_active else None
         return self.trims
+
+    def _tag_args(self):
+        """hand the tags of the trims to the next host-array selection (kmr_select_bimodal); without tags, take back what is left"""
+        w = self.bimodal_words
+        self.sp._call("select_bimodal", self.sp.h, self._p(w, C.c_uint64), 0 if w is None else w.size)
 
     def _select(self, min_score, min_read_length, both_pass):
         if self.trims is None:
@@ -935,6 +999,7 @@ class ReadSelector(_DeviceObject):
         cfg = self._config(min_score, min_read_length, both_pass, output_quality_base, format, self.scoring)
         keep, tp, tn = self._text_args()
         trims, trim_ptrs = self._trim_args()
+        self._tag_args()
         out = C.c_void_p()
         self.sp._call("select_reads", self.sp.h, self.reads.r, tp, tn, self._p(self.mate, C.c_int64), *self._af_args(), *trim_ptrs, C.byref(cfg), C.byref(out))
         self._adopt(out)
@@ -953,13 +1018,14 @@ class ReadSelector(_DeviceObject):
         """:585-596 over the pairs of `mate`; returns the number of picked reads"""
         return self._select(min_score, min_read_length, both_pass)
 
-    def filterReads(self, min_score=2.0, min_read_length=None, both_pass=False, scoring="MEDIAN", output_quality_base=33, format="fastq"):
+    def filterReads(self, min_score=2.0, min_read_length=None, both_pass=False, scoring="MEDIAN", output_quality_base=33, format="fastq", bimodal_sigmas=-1.0):
         """scoreAndTrimReads + pickAllPassingPairs + writePicks in one call that keeps the trims on the device
-        (kmr_filter_read_batch); returns the text"""
+        (kmr_filter_read_batch); returns the text.  bimodal_sigmas as scoreAndTrimReads takes it."""
         cfg = self._config(min_score, min_read_length, both_pass, output_quality_base, format, scoring)
         keep, tp, tn = self._text_args()
         out = C.c_void_p()
-        self.sp._call("filter_read_batch", self.sp.h, self.reads.r, tp, tn, self._p(self.mate, C.c_int64), *self._af_args(), C.byref(cfg), C.byref(out))
+        with self.sp._bimodal_for(bimodal_sigmas, self.reads.n):
+            self.sp._call("filter_read_batch", self.sp.h, self.reads.r, tp, tn, self._p(self.mate, C.c_int64), *self._af_args(), C.byref(cfg), C.byref(out))
         self._adopt(out)
         self._sel, self._fmt = None, (output_quality_base, cfg.format)
         return self._copy()
@@ -968,7 +1034,7 @@ class ReadSelector(_DeviceObject):
 
     def selectReads(self, min_depth, partition_by_depth=0, remainder_trim=-1.0, min_read_length=None, both_pass=False, scoring="MEDIAN",
                     output_quality_base=33, format="fastq", input_starts=None, input_prefixes=None, output="", separate_outputs=True,
-                    max_kmer_output_depth=0, normalization_method="RANDOM", seed=0, first_read_idx=0, by_pair=None):
+                    max_kmer_output_depth=0, normalization_method="RANDOM", seed=0, first_read_idx=0, by_pair=None, bimodal_sigmas=-1.0):
         """selectReads (apps/FilterReads.h:159-279).  With --max-kmer-output-depth off: the rounds of --partition-by-depth and
         --remainder-trim over the reads of `input_starts` (n_inputs + 1 ascending read indices; None = one input), on the device
         (kmr_partition_read_batch, or kmr_partition_reads over the trims scoreAndTrimReads left).  Returns the ordered list of
@@ -980,14 +1046,16 @@ class ReadSelector(_DeviceObject):
         With max_kmer_output_depth > 0 (:178-206): coverage normalization over `pairs` (kmr_normalize_*), one round whose files
         are named `output` + "-MinDepth<min_depth>" + "-MaxDepth<depth>" + "-" + prefix + suffix; by_pair defaults to the pairs'
         hasPairs, as the reference passes it; normalization_method "RANDOM" only; together with partition_by_depth it raises, as
-        the reference's option check does (src/ReadSelector.h:137)."""
+        the reference's option check does (src/ReadSelector.h:137).
+        bimodal_sigmas: as scoreAndTrimReads takes it, for the scoring a fused call does; where scoreAndTrimReads has run, its
+        trims and tags are what is selected from."""
         if max_kmer_output_depth > 0:
             if partition_by_depth > 0:
                 raise KmerSpectrumError("selectReads: max_kmer_output_depth and partition_by_depth exclude each other")
             if normalization_method not in ("RANDOM", "OPTIMAL"):
                 raise KmerSpectrumError("selectReads: normalization_method %r" % (normalization_method,))
             cfg = self._normalize(max_kmer_output_depth, min_depth, min_read_length, self.has_pairs if by_pair is None else by_pair, both_pass, seed, first_read_idx,
-                                  scoring, output_quality_base, format, input_starts, method=0 if normalization_method == "RANDOM" else 1)
+                                  scoring, output_quality_base, format, input_starts, method=0 if normalization_method == "RANDOM" else 1, bimodal_sigmas=bimodal_sigmas)
             text = self._copy()
             seg = self._segments()
             if not separate_outputs:
@@ -1004,9 +1072,11 @@ class ReadSelector(_DeviceObject):
         head = (self.sp.h, self.reads.r, tp, tn, self._p(self.mate, C.c_int64)) + tuple(self._af_args())
         tail = (starts_p, n_inputs, C.byref(cfg), C.byref(out))
         if fused:
-            self.sp._call("partition_read_batch", *head, *tail)
+            with self.sp._bimodal_for(bimodal_sigmas, self.reads.n):
+                self.sp._call("partition_read_batch", *head, *tail)
         else:
             trims, trim_ptrs = self._trim_args()
+            self._tag_args()
             self.sp._call("partition_reads", *head, *trim_ptrs, *tail)
         self._adopt(out)
         self._sel, self._fmt = None, (output_quality_base, cfg.select.format)
@@ -1023,7 +1093,7 @@ class ReadSelector(_DeviceObject):
         return self._files(text, seg, names, input_prefixes, self.SUFFIX[cfg.select.format])
 
     def _normalize(self, target_depth, min_score, min_read_length, by_pair, both_pass, seed, first_read_idx, scoring, output_quality_base, format,
-                   input_starts=None, method=0, use_logscale=False):
+                   input_starts=None, method=0, use_logscale=False, bimodal_sigmas=-1.0):
         """kmr_normalize_reads over the trims scoreAndTrimReads left, or kmr_normalize_read_batch without them"""
         fused = self.trims is None
         cfg = _lib.KmrNormalizeConfig()
@@ -1038,9 +1108,11 @@ class ReadSelector(_DeviceObject):
         head = (self.sp.h, self.reads.r, tp, tn, self._p(r1, C.c_int64), self._p(r2, C.c_int64), 0 if r1 is None else r1.size) + tuple(self._af_args())
         tail = (starts_p, n_inputs, C.byref(cfg), C.byref(out))
         if fused:
-            self.sp._call("normalize_read_batch", *head, *tail)
+            with self.sp._bimodal_for(bimodal_sigmas, self.reads.n):
+                self.sp._call("normalize_read_batch", *head, *tail)
         else:
             trims, trim_ptrs = self._trim_args()
+            self._tag_args()
             self.sp._call("normalize_reads", *head, *trim_ptrs, *tail)
         self._adopt(out)
         self._sel, self._fmt = None, (output_quality_base, cfg.select.format)
@@ -1050,12 +1122,12 @@ class ReadSelector(_DeviceObject):
         return cfg
 
     def pickCoverageNormalizedSubset(self, target_depth, min_score=0.0, min_read_length=None, by_pair=False, both_pass=False, seed=0, first_read_idx=0,
-                                     output_quality_base=33, format="fastq"):
+                                     output_quality_base=33, format="fastq", bimodal_sigmas=-1.0):
         """ReadSelector::pickCoverageNormalizedSubset (:673-749), RANDOM, over `pairs`, on the device (kmr_normalize_reads, or
         kmr_normalize_read_batch if scoreAndTrimReads has not run): a pair or read of score s above target_depth is kept if
         draw % s <= target_depth, draw = Philox4x32-10 of (seed, first_read_idx + read index).  Returns the number of picks as the
         reference counts them (pairs; n_picked counts records); .normalize_info holds them with the chooseRead calls and the draws."""
-        self._normalize(target_depth, min_score, min_read_length, by_pair, both_pass, seed, first_read_idx, "MEDIAN", output_quality_base, format)
+        self._normalize(target_depth, min_score, min_read_length, by_pair, both_pass, seed, first_read_idx, "MEDIAN", output_quality_base, format, bimodal_sigmas=bimodal_sigmas)
         return self.normalize_info["n_picks"]
 
     def _segments(self):
