@@ -902,6 +902,81 @@ int kmr_normalize_read_batch_dev(kmr_handle *h, const kmr_reads *reads, const vo
  * the return value of pickCoverageNormalizedSubset), the chooseRead calls, and those among them that drew (s > T) */
 int kmr_normalize_info(const kmr_picks *p, uint64_t *n_picks, uint64_t *n_candidates, uint64_t *n_draws);
 
+/* ---- the artifact filter's report: its -Artifact.fastq and -PhiX.fastq files and its per-sequence counters, on the device ----------
+ * What FilterKnownOddities' Recorder (src/FilterKnownOddities.h:296-353) makes of the decisions kmr_artifact_filter_apply returns,
+ * in the order one thread of the reference takes (under OpenMP the reference's own order is arbitrary):
+ *   unit        with a pair list one entry of it, read1 then read2, either may be absent (applyFilterToPair :355-386); without,
+ *               one read (applyFilterToRead with recordEffects :389, :695).  v1, v2 = the reads' own value, 0 for an absent side;
+ *               nothing happens unless v1 != 0 || v2 != 0 (:555-560)
+ *   PhiX unit   isPhiX(v1) || isPhiX(v2) (:556): every present read, a clean mate included, is discarded and counted under phix_idx:
+ *               discarded[phix]++, bases[phix] += length (:569-587, recordDiscard :310-320); with phix_output each is written
+ *               without a label to the PhiX file of the input read1 belongs to (:574), read2's if read1 is absent
+ *   other unit  for each present read with v != 0 (:613, :623): action 2: discarded[v]++, bases[v] += length, and with artifact_output
+ *               a record labelled getFilterName(v) in the Artifact file of read1's input (:603-609, :618); action 1: trimmed[v]++,
+ *               bases[v] += length - (max_pass - min_pass), no record (recordTrim :321-334).  The action is the one
+ *               kmr_artifact_filter_apply returned; a clean mate is neither counted nor written
+ *   record      _writeFilterRead (:734-736) = FormatOutput::FastqUnmasked() after read.discard() (:311): getFastaNoMarkup of a
+ *               discarded read answers N (src/Sequence.cpp:290-296) while getQuals(unmasked) skips its discarded shortcut
+ *               (:729-759): "@name[ label]\nN\n+\n" all `length` qualities "\n", length = the read's before the filter; for a length
+ *               <= 1 the quality line is the one character output_quality_base + 1 (:752-758).  print_bases = 1 prints the read's own
+ *               `length` characters, as the unfiltered batch holds them, in place of N (reads of length <= 1 as before)
+ *   name        as the selection's writer cuts it: up to the first blank or tab; qualities move from the handle's fastq_start_char
+ *               to output_quality_base; stored comments stay uncovered, as in the selection
+ *   label       getFilterName (:543-550): the FASTA header of sequence v after '>' up to the first blank or tab; for
+ *               v == n_sequences "MinQualityTrim<min_quality>"; an empty name prints no label (src/Sequence.cpp:767)
+ *   files       OfstreamMap(out, "-PhiX.fastq") / (out, "-Artifact.fastq") with key "-" + prefix (:670-677): the picks' segment table
+ *               has two rows times n_inputs, row 0 Artifact, row 1 PhiX; a segment without a record is a file the reference never opens
+ *   table       applyFilter :714-725: the counters of every index with bases > 0, ascending
+ * `in` is the batch the filter was applied to (lengths and qualities are the original ones), `text` its name text.  value, action,
+ * min_pass and max_pass are the host arrays kmr_artifact_filter_apply returned (n_reads entries).  read1 / read2 (n_pairs entries, -1 =
+ * no read on that side) have the convention of kmr_pairs_copy and kmr_normalize_reads; NULL = every read is a unit of its own.
+ * input_starts / n_inputs as kmr_partition_reads takes them (at most 128 inputs).
+ * KMR_ERR_INVALID_ARG, with the cause in kmr_last_error: a wrong struct_size, a quality base other than 33 or 64, read1 without
+ * read2, an index outside [-1, n), a pair without a read, a read two pairs name or, under a pair list, a read no pair names
+ * (identifyPairs never leaves one), phix_output with a filter whose phix_idx is 0, a value above n_sequences.
+ * An empty batch and a batch without records are valid and give 0 bytes. */
+typedef struct kmr_artifact_report_config {
+	uint32_t struct_size;            /* = sizeof(kmr_artifact_report_config), ABI guard                 */
+	uint32_t artifact_output;        /* --filter-output: write the Artifact records (1)                  */
+	uint32_t phix_output;            /* --phix-output: write the PhiX records (1)                        */
+	uint32_t output_quality_base;    /* --fastq-output-base-quality: 33 or 64 (33)                       */
+	uint32_t print_bases;            /* 0 = the base line N, as the reference writes it; 1 = the bases   */
+} kmr_artifact_report_config;
+int kmr_artifact_report_config_init(kmr_artifact_report_config *cfg);
+typedef struct kmr_artifact_report kmr_artifact_report;
+int kmr_artifact_filter_report(kmr_handle *h, const kmr_artifact_filter *f, const kmr_reads *in, const char *text, uint64_t text_len,
+                               const int64_t *read1, const int64_t *read2, uint64_t n_pairs, const uint32_t *value, const uint8_t *action,
+                               const uint32_t *min_pass, const uint32_t *max_pass, const uint64_t *input_starts, uint32_t n_inputs,
+                               const kmr_artifact_report_config *cfg, kmr_artifact_report **report);
+/* the same with the name text in device memory */
+int kmr_artifact_filter_report_dev(kmr_handle *h, const kmr_artifact_filter *f, const kmr_reads *in, const void *dev_text, uint64_t text_len,
+                                   const int64_t *read1, const int64_t *read2, uint64_t n_pairs, const uint32_t *value, const uint8_t *action,
+                                   const uint32_t *min_pass, const uint32_t *max_pass, const uint64_t *input_starts, uint32_t n_inputs,
+                                   const kmr_artifact_report_config *cfg, kmr_artifact_report **report);
+/* The fused form: everything kmr_artifact_filter_apply does, with the same optional host outputs and the same *out batch, and the
+ * report from the decisions while they are on the device (no per-read array crosses the bus unless the caller asked for one).  It
+ * takes the pair list; the mate of the apply step is derived from it on the device. */
+int kmr_artifact_filter_apply_report(kmr_handle *h, const kmr_artifact_filter *f, const kmr_reads *in, const char *text, uint64_t text_len,
+                                     const int64_t *read1, const int64_t *read2, uint64_t n_pairs, uint32_t *value, uint32_t *min_pass,
+                                     uint32_t *max_pass, uint8_t *action, uint32_t *remnant_off, uint32_t *remnant_len, kmr_reads **out,
+                                     const uint64_t *input_starts, uint32_t n_inputs, const kmr_artifact_report_config *cfg,
+                                     kmr_artifact_report **report);
+int kmr_artifact_filter_apply_report_dev(kmr_handle *h, const kmr_artifact_filter *f, const kmr_reads *in, const void *dev_text, uint64_t text_len,
+                                         const int64_t *read1, const int64_t *read2, uint64_t n_pairs, uint32_t *value, uint32_t *min_pass,
+                                         uint32_t *max_pass, uint8_t *action, uint32_t *remnant_off, uint32_t *remnant_len, kmr_reads **out,
+                                         const uint64_t *input_starts, uint32_t n_inputs, const kmr_artifact_report_config *cfg,
+                                         kmr_artifact_report **report);
+/* discarded (discardedCounts), trimmed (readCounts) and bases (baseCounts) per sequence index, n_sequences + 1 entries each (each may
+ * be NULL); KMR_ERR_CAPACITY below that */
+int kmr_artifact_report_counts(const kmr_artifact_report *report, uint64_t *discarded, uint64_t *trimmed, uint64_t *bases, uint64_t capacity);
+/* the records: a kmr_picks borrowed from the report (do not free it; it lives as long as the report).  kmr_picks_info, _copy,
+ * _device_ptr, _segments_info and _segments_copy work on it: n_rounds is 2 (row 0 Artifact, row 1 PhiX), a read's segment is
+ * row * n_inputs + input or -1.  The text stays in device memory until it is copied. */
+int kmr_artifact_report_picks(const kmr_artifact_report *report, const kmr_picks **picks);
+void kmr_artifact_report_free(kmr_artifact_report *report);
+/* getFilterName(idx) for idx in [1, n_sequences]: the NUL-terminated label; KMR_ERR_CAPACITY if it does not fit dst */
+int kmr_artifact_filter_name(const kmr_artifact_filter *f, uint32_t idx, char *dst, uint64_t capacity);
+
 /* ---- ReadSet::identifyPairs: which reads of a batch are the two ends of one fragment, on the device ----------
  * One call equals one ReadSet::identifyPairs() (src/ReadSet.cpp:446-570) on a fresh ReadSet that holds the batch's reads in
  * batch order: no earlier pairs, previousReadName empty.  apps/FilterReads.cpp:103 and importAndProcessReadset of FilterReads-P
@@ -1053,6 +1128,9 @@ void *kmr_stream(kmr_handle *h);
  *   share a key, which tests use to reach the byte-for-byte grouping), "pairs_timing" (1: kmr_identify_pairs* times its phases with HIP
  *   events, see kmr_build_info; default 0); both may be set at any time.
  *   "dedup_timing" (1: kmr_dedup_fragments* times its phases with HIP events, see kmr_build_info; default 0; may be set at any time).
+ *   "artifact_report_lds" (where kmr_artifact_filter_report* / kmr_artifact_filter_apply_report* sum the per-sequence counters: 1 = per unit in LDS
+ *   first, while 24 bytes a sequence index fit 48 KiB, 0 = global 64-bit atomics, anything else = the default, LDS while they fit 6 KiB; tests force
+ *   either; see kmr_build_info; may be set at any time).
  * Call before the first kmr_add_reads* of a build.  KMR_ERR_INVALID_ARG for an unknown knob. */
 int kmr_tune(kmr_handle *h, const char *knob, double value);
 /* What the current build decided, for tests and measurement tools (the reference logs such figures, LOG_VERBOSE): "lists" = super-k-mer
@@ -1075,7 +1153,9 @@ int kmr_tune(kmr_handle *h, const char *knob, double value);
  * last kmr_identify_pairs* on this handle: the whole call, its name parse, its radix sort (0 unless kmr_tune "pairs_timing" is set),
  * "pair_hash_collisions" = runs of equal sort keys of that call that held more than one distinct common name,
  * "dedup_ms" / "dedup_key_ms" / "dedup_sort_ms" / "dedup_consensus_ms" = HIP-event times of the last kmr_dedup_fragments* on this
- * handle: the whole call, its key kernel, its radix sorts, its consensus kernel (0 unless kmr_tune "dedup_timing" is set).
+ * handle: the whole call, its key kernel, its radix sorts, its consensus kernel (0 unless kmr_tune "dedup_timing" is set),
+ * "artifact_report_lds" = 1 if the last kmr_artifact_filter_report* / kmr_artifact_filter_apply_report* on this handle summed its counters in LDS, 0 if by
+ * global atomics.
  * KMR_ERR_INVALID_ARG for an unknown name. */
 int kmr_build_info(kmr_handle *h, const char *what, double *value);
 

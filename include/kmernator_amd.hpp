@@ -269,6 +269,42 @@ public:
 		                                    res.remnantOffset.data(), res.remnantLength.data(), &out), "kmr_artifact_filter_apply");
 		return std::unique_ptr<ReadSet>(new ReadSet(reads._text, out));
 	}
+	/* what the Recorder (:296-353) makes of applyFilter's results: the counters and the -Artifact.fastq / -PhiX.fastq records */
+	struct Report {
+		std::vector<uint64_t> discarded, trimmed, bases;      /* per sequence index, n_sequences + 1 entries */
+		std::string text;                                     /* all records: segment after segment */
+		uint32_t nInputs = 1;
+		std::vector<uint64_t> segFirstByte, segBytes, segRecords;      /* [row * nInputs + input], row 0 Artifact, row 1 PhiX */
+	};
+	static kmr_artifact_report_config reportDefaults() { kmr_artifact_report_config c; kmr_artifact_report_config_init(&c); return c; }
+	std::string getFilterName(uint32_t idx) const {
+		char buf[4096];
+		if (kmr_artifact_filter_name(_f, idx, buf, sizeof buf) != KMR_OK) throw KmerSpectrumError(KMR_ERR_INVALID_ARG, "kmr_artifact_filter_name");
+		return buf;
+	}
+	/* kmr_artifact_filter_report over the batch `res` was computed from; read1 / read2 = the pair list (nullptr: every read on its own),
+	 * inputStarts = nInputs + 1 read indices (nullptr: one input) */
+	Report report(const ReadSet &reads, const Results &res, const kmr_artifact_report_config &cfg, const int64_t *read1 = nullptr, const int64_t *read2 = nullptr, uint64_t nPairs = 0,
+	              const uint64_t *inputStarts = nullptr, uint32_t nInputs = 0) {
+		kmr_artifact_report *rep = nullptr;
+		_sp.check(kmr_artifact_filter_report(_sp.raw(), _f, reads.raw(), reads._text.data(), reads._text.size(), read1, read2, nPairs, res.value.data(), res.action.data(),
+		                                     res.minPass.data(), res.maxPass.data(), inputStarts, nInputs, &cfg, &rep), "kmr_artifact_filter_report");
+		std::unique_ptr<kmr_artifact_report, void (*)(kmr_artifact_report *)> hold(rep, kmr_artifact_report_free);
+		Report out;
+		uint64_t nSeq = 0, bytes = 0; uint32_t nRows = 0;
+		kmr_artifact_filter_info(_f, &nSeq, nullptr, nullptr);
+		out.discarded.assign(nSeq + 1, 0); out.trimmed.assign(nSeq + 1, 0); out.bases.assign(nSeq + 1, 0);
+		_sp.check(kmr_artifact_report_counts(rep, out.discarded.data(), out.trimmed.data(), out.bases.data(), nSeq + 1), "kmr_artifact_report_counts");
+		const kmr_picks *pk = nullptr;
+		_sp.check(kmr_artifact_report_picks(rep, &pk), "kmr_artifact_report_picks");
+		kmr_picks_info(pk, nullptr, &bytes); kmr_picks_segments_info(pk, &nRows, &out.nInputs);
+		const size_t segs = (size_t)nRows * out.nInputs;
+		out.segFirstByte.assign(segs, 0); out.segBytes.assign(segs, 0); out.segRecords.assign(segs, 0);
+		_sp.check(kmr_picks_segments_copy(pk, nullptr, nullptr, nullptr, out.segRecords.data(), out.segFirstByte.data(), out.segBytes.data(), nullptr), "kmr_picks_segments_copy");
+		out.text.resize(bytes);
+		if (bytes) _sp.check(kmr_picks_copy(pk, &out.text[0], bytes, nullptr), "kmr_picks_copy");
+		return out;
+	}
 private:
 	KmerSpectrum &_sp; kmr_artifact_filter *_f = nullptr;
 };

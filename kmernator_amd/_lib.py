@@ -60,6 +60,11 @@ class KmrArtifactConfig(C.Structure):
                                           "phix_idx", "reference_begin", "min_quality", "fastq_start_char")] + [("min_read_length", C.c_float)]
 
 
+class KmrArtifactReportConfig(C.Structure):
+    """kmr_artifact_report_config"""
+    _fields_ = [(n, C.c_uint32) for n in ("struct_size", "artifact_output", "phix_output", "output_quality_base", "print_bases")]
+
+
 class KmrDedupConfig(C.Structure):
     """kmr_dedup_config"""
     _fields_ = [(n, C.c_uint32) for n in ("struct_size", "dedup_mode", "paired", "dedup_length", "start_offset", "edit_distance", "consensus")]
@@ -93,7 +98,9 @@ EXPORTS = [
     "kmr_ingest_fastq", "kmr_ingest_fastq_dev", "kmr_ingest_fasta", "kmr_ingest_fasta_dev", "kmr_reads_info", "kmr_reads_device_ptrs", "kmr_reads_copy",
     "kmr_add_read_batch", "kmr_reads_free", "kmr_histogram", "kmr_histogram_bins", "kmr_merge_image", "kmr_subtract_reference", "kmr_subtracted", "kmr_score_read_batch",
     "kmr_artifact_config_init", "kmr_artifact_filter_create", "kmr_artifact_filter_info", "kmr_artifact_filter_entries",
-    "kmr_artifact_filter_free", "kmr_artifact_filter_apply",
+    "kmr_artifact_filter_free", "kmr_artifact_filter_apply", "kmr_artifact_filter_name",
+    "kmr_artifact_report_config_init", "kmr_artifact_filter_report", "kmr_artifact_filter_report_dev", "kmr_artifact_filter_apply_report", "kmr_artifact_filter_apply_report_dev",
+    "kmr_artifact_report_counts", "kmr_artifact_report_picks", "kmr_artifact_report_free",
     "kmr_tune", "kmr_set_stream_origin", "kmr_size_tracker", "kmr_exchange_unique_id", "kmr_exchange_init", "kmr_exchange_init_transport", "kmr_exchange_add_reads_dev", "kmr_exchange_add_read_batch", "kmr_exchange_stats", "kmr_copy_to_host", "kmr_copy_to_device", "kmr_sk_exchange_begin", "kmr_sk_exchange_counts", "kmr_sk_exchange_pack_dev", "kmr_sk_exchange_adopt_dev", "kmr_extract_by_owner_host", "kmr_insert_records", "kmr_reads_from_host", "kmr_reads_from_twobit", "kmr_reads_twobit", "kmr_lookup_requests_dev", "kmr_lookup_keys_dev", "kmr_scatter_counts_dev", "kmr_score_counts_dev",
     "kmr_lookup_weighted", "kmr_lookup_reads_weighted", "kmr_lookup_keys_weighted_dev",
     "kmr_select_config_init", "kmr_select_reads", "kmr_select_reads_dev", "kmr_filter_read_batch", "kmr_filter_read_batch_dev",
@@ -193,6 +200,17 @@ def load():
     lib.kmr_artifact_filter_free.argtypes = [vp]
     lib.kmr_artifact_filter_free.restype = None
     lib.kmr_artifact_filter_apply.argtypes = [vp, vp, vp, C.POINTER(C.c_int64), u32p, u32p, u32p, u8p, u32p, u32p, C.POINTER(vp)]
+    lib.kmr_artifact_filter_name.argtypes = [vp, C.c_uint32, C.c_char_p, C.c_uint64]
+    rcp, i64 = C.POINTER(KmrArtifactReportConfig), C.POINTER(C.c_int64)
+    lib.kmr_artifact_report_config_init.argtypes = [rcp]
+    for name in ("kmr_artifact_filter_report", "kmr_artifact_filter_report_dev"):
+        getattr(lib, name).argtypes = [vp, vp, vp, vp, C.c_uint64, i64, i64, C.c_uint64, u32p, u8p, u32p, u32p, u64p, C.c_uint32, rcp, C.POINTER(vp)]
+    for name in ("kmr_artifact_filter_apply_report", "kmr_artifact_filter_apply_report_dev"):
+        getattr(lib, name).argtypes = [vp, vp, vp, vp, C.c_uint64, i64, i64, C.c_uint64, u32p, u32p, u32p, u8p, u32p, u32p, C.POINTER(vp), u64p, C.c_uint32, rcp, C.POINTER(vp)]
+    lib.kmr_artifact_report_counts.argtypes = [vp, u64p, u64p, u64p, C.c_uint64]
+    lib.kmr_artifact_report_picks.argtypes = [vp, C.POINTER(vp)]
+    lib.kmr_artifact_report_free.argtypes = [vp]
+    lib.kmr_artifact_report_free.restype = None
     lib.kmr_extract_by_owner_host.argtypes = [vp, vp, C.c_uint64, u64p, vp, C.c_uint64]
     lib.kmr_insert_records.argtypes = [vp, vp, C.c_uint64]
     lib.kmr_sk_exchange_begin.argtypes = [vp]

@@ -2225,6 +2225,7 @@ int kmr_tune(kmr_handle *h, const char *knob, double value) {
 	else if (k == "dedup_timing") h->tune.dedup_timing = value != 0;
 	else if (k == "bimodal_window") h->tune.bimodal_window = value >= 0 && value <= BM_CAP ? (int)value : -1;
 	else if (k == "partition_units") h->tune.partition_units = value >= 1 && value <= 8192 ? (uint32_t)value : 0;
+	else if (k == "artifact_report_lds") h->tune.artifact_report_lds = value == 0 ? 0 : value == 1 ? 1 : -1;
 	else if (k == "pair_hash_bits") h->tune.pair_hash_bits = value >= 1 && value < 64 ? (uint32_t)value : 64;
 	else if (k == "dump_piece_bytes") h->tune.dump_piece_bytes = value >= 1 ? (uint64_t)value : 0;
 	else if (k == "narrow_tallies") h->tune.no_narrow = value == 0;
@@ -2259,6 +2260,7 @@ int kmr_build_info(kmr_handle *h, const char *what, double *value) {
 	else if (k == "filter_score_ms") *value = h->last_score_ms;
 	else if (k == "select_ms") *value = h->last_select_ms;
 	else if (k == "select_write_ms") *value = h->last_write_ms;
+	else if (k == "artifact_report_lds") *value = h->last_artifact_report_lds;
 	else if (k == "pairs_ms") *value = h->last_pairs_ms;
 	else if (k == "pairs_parse_ms") *value = h->last_pairs_parse_ms;
 	else if (k == "pairs_sort_ms") *value = h->last_pairs_sort_ms;

@@ -184,6 +184,7 @@ struct KMR_HIDDEN Tuning {
 	bool pairs_timing = false;         /* kmr_identify_pairs*: time the name parse, the sort and the whole call with HIP events (kmr_build_info; measurement tools) */
 	bool dedup_timing = false;         /* kmr_dedup_fragments*: time the key kernel, the sorts, the consensus kernel and the whole call with HIP events (kmr_build_info; measurement tools) */
 	uint32_t partition_units = 0;      /* kmr_partition_*: most units (wavefronts over contiguous reads) of the partition, 0 = the default of 8192 (tests: a few, so that a unit walks many tiles) */
+	int artifact_report_lds = -1;      /* kmr_artifact_filter_report*: where the per-sequence counters are summed (-1: in LDS while they fit ART_REPORT_LDS_CAP; tests: 0 = global atomics, 1 = LDS up to ART_REPORT_LDS_MOST) */
 	uint32_t pair_hash_bits = 64;      /* kmr_identify_pairs*: bits of the common name's hash the phase-2 sort keys keep (tests: a few bits, so that distinct names share a key) */
 	int bimodal_window = -1;           /* bimodal_trim_kernel: the longest run it stages in LDS (-1: BM_CAP; tests: 0, so that every run is walked in global memory) */
 	bool no_coarse_lists = true;       /* exchange: scatter into the job's fine lists (default) or, kmr_tune("coarse_lists", 1), into coarse ones that the owner splits before the count pass (sk_refine_kernel: not yet fast enough to pay) */
@@ -249,6 +250,7 @@ struct KMR_HIDDEN kmr_handle : HandleMem, BuildMem, ExchangeMem {
 	int last_score_path = 0;      /* kmr_build_info "score_path": where the last kmr_score_reads / _read_batch / kmr_filter_read_batch got its counts */
 	bool last_early_overflowed = false;                       /* ... or that it voided one because its buffers overflowed */
 	double last_score_ms = 0, last_select_ms = 0, last_write_ms = 0;      /* the last kmr_filter_read_batch* / kmr_select_reads*: scoring, selection + writer, writer alone (HIP events, taken with kmr_tune "select_timing" only; kmr_build_info) */
+	int last_artifact_report_lds = 0;      /* the last kmr_artifact_filter_report* / _apply_report*: 1 = its counters were summed in LDS, 0 = by global atomics (kmr_build_info) */
 	double last_dump_size_ms = 0, last_dump_write_ms = 0;      /* the last kmr_dump_text_size / kmr_dump_text: size pass with its scan, writer (HIP events, taken with kmr_tune "dump_timing" only; kmr_build_info) */
 	double last_pairs_ms = 0, last_pairs_parse_ms = 0, last_pairs_sort_ms = 0;      /* the last kmr_identify_pairs*: the whole call, its name parse, its radix sort (HIP events, taken with kmr_tune "pairs_timing" only; kmr_build_info) */
 	double last_dedup_ms = 0, last_dedup_key_ms = 0, last_dedup_sort_ms = 0, last_dedup_consensus_ms = 0;      /* the last kmr_dedup_fragments*: the whole call, its key kernel, its radix sorts, its consensus kernel (HIP events, taken with kmr_tune "dedup_timing" only; kmr_build_info) */

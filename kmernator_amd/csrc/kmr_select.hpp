@@ -10,6 +10,7 @@
  * label, the printed length of a name and the exact byte count of a record (decimal digits are counted, not printed), and
  *   select_write_kernel    one wavefront per record: name, label with integer-to-decimal, base slice, shifted quality slice,
  *                          consecutive lanes taking consecutive bytes of the record
+ * (sel_put_record, sel_name_printed and sel_record_bytes are what a record is to any writer; kmr_artifact_report.hpp prints its own through them)
  * A second writer, which assembled 16 KiB tiles of the output in LDS and stored them as 16-byte vectors, was measured against this
  * one and lost ("Read selection and output text"); it is not kept.
  * The second half is which reads are picked and where their records go: one stable partition by (round, input file), of which the
@@ -27,7 +28,8 @@
 
 namespace kmr {
 
-enum { SEL_ERR_MATE = 1, SEL_ERR_NAME = 2, SEL_ERR_PAIR = 4, SEL_ERR_TWICE = 8 };      /* the last two: the pair list of kmr_normalize.hpp */
+enum { SEL_ERR_MATE = 1, SEL_ERR_NAME = 2, SEL_ERR_PAIR = 4, SEL_ERR_TWICE = 8,      /* the last two: the pair list of kmr_normalize.hpp */
+       SEL_ERR_UNNAMED = 16, SEL_ERR_VALUE = 32 };                                    /* kmr_artifact_report.hpp: a read no pair names, a value above n_sequences */
 static const int SEL_THREADS = 256, SEL_WAVES = SEL_THREADS / 64, SEL_LABEL_CAP = 128;
 /* the longest label sel_label writes, part by part, each with its leading blank:
  *   " AFTrim:" u32 "+" i64 of a difference of two u32       8 + 10 + 1 + 11
@@ -131,49 +133,71 @@ __device__ __forceinline__ SelSlice sel_slice(const SelectParams &P, uint64_t i)
 	s.from = b0 + to; s.len = s.masked ? 1u : (uint32_t)tl;
 	return s;
 }
-__device__ __forceinline__ uint32_t sel_record_bytes(const SelectParams &P, uint32_t nlen, uint32_t lablen, uint32_t slice_len) {
-	return 1 + nlen + lablen + 1 + slice_len + 1 + (P.fasta ? 0u : 2u + slice_len + 1u);
+/* A record as its writer sees it (sel_put_record): the lead character, `nlen` bytes of the name, a label WITH its leading blank,
+ * `base_len` bases (no_bases: the single base N), and for FASTQ `qual_len` qualities shifted by qual_shift (no_quals: the single
+ * quality `masked_qual`).  The selection prints as many qualities as bases; the artifact report (kmr_artifact_report.hpp) prints N over
+ * all of a read's qualities. */
+struct SelRecord {
+	const uint8_t *name, *label, *bases, *quals;
+	uint32_t nlen, lablen, base_len, qual_len;
+	int32_t qual_shift;
+	uint8_t masked_qual; bool fasta, no_bases, no_quals;
+};
+__device__ __forceinline__ uint32_t sel_record_bytes(bool fasta, uint32_t nlen, uint32_t lablen, uint32_t base_len, uint32_t qual_len) {
+	return 1 + nlen + lablen + 1 + base_len + 1 + (fasta ? 0u : 2u + qual_len + 1u);
 }
-
-/* the printed length of picked read i's name (up to the first blank or tab) and the exact byte count of its record */
-__device__ __forceinline__ uint32_t sel_measure(const SelectParams &P, uint64_t i, uint32_t *name_printed, uint32_t *err) {
+/* the printed length of a name: up to its first blank or tab; a span outside the text is an error and prints nothing */
+__device__ __forceinline__ uint32_t sel_name_printed(const uint8_t *text, uint64_t text_len, uint64_t no, uint32_t nl, uint32_t *err) {
 	uint32_t nlen = 0;
-	const uint64_t no = P.name_off[i]; const uint32_t nl = P.name_len[i];
-	if (no > P.text_len || nl > P.text_len - no) atomicOr(err, (uint32_t)SEL_ERR_NAME);
-	else while (nlen < nl && P.text[no + nlen] != ' ' && P.text[no + nlen] != '\t') nlen++;
-	*name_printed = nlen;
-	return sel_record_bytes(P, nlen, sel_label(P, i, nullptr, false), sel_slice(P, i).len);
+	if (no > text_len || nl > text_len - no) atomicOr(err, (uint32_t)SEL_ERR_NAME);
+	else while (nlen < nl && text[no + nlen] != ' ' && text[no + nlen] != '\t') nlen++;
+	return nlen;
 }
 
-/* Read i's record of `bytes` bytes, by one wavefront, to dst; s_label: SEL_LABEL_CAP bytes of LDS of this wavefront.
- * Consecutive lanes take consecutive bytes, so the loads from the name, the bases and the qualities and the stores coalesce. */
-__device__ __forceinline__ void sel_emit(const SelectParams &P, uint64_t i, uint32_t nlen, uint32_t bytes, uint8_t *dst, int lane, uint8_t *s_label) {
-	const uint32_t lablen = sel_label(P, i, s_label, lane == 0);
-	const SelSlice sl = sel_slice(P, i);
-	const uint64_t noff = P.name_off[i];
-	const uint32_t hdr = 1 + nlen + lablen + 1;
-	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
+/* the printed length of picked read i's name and the exact byte count of its record */
+__device__ __forceinline__ uint32_t sel_measure(const SelectParams &P, uint64_t i, uint32_t *name_printed, uint32_t *err) {
+	const uint32_t nlen = sel_name_printed(P.text, P.text_len, P.name_off[i], P.name_len[i], err), len = sel_slice(P, i).len;
+	*name_printed = nlen;
+	return sel_record_bytes(P.fasta != 0, nlen, sel_label(P, i, nullptr, false), len, len);
+}
+
+/* The `bytes` bytes of record R, by one wavefront, to dst.  Consecutive lanes take consecutive bytes, so the loads from the name, the
+ * bases and the qualities and the stores coalesce. */
+__device__ __forceinline__ void sel_put_record(const SelRecord &R, uint32_t bytes, uint8_t *dst, int lane) {
+	const uint32_t hdr = 1 + R.nlen + R.lablen + 1;
 	for (uint32_t p = lane; p < bytes; p += 64) {
 		uint8_t c;
 		if (p < hdr) {
-			if (p == 0) c = P.fasta ? '>' : '@';
-			else if (p <= nlen) c = P.text[noff + p - 1];
-			else if (p < hdr - 1) c = s_label[p - 1 - nlen];
+			if (p == 0) c = R.fasta ? '>' : '@';
+			else if (p <= R.nlen) c = R.name[p - 1];
+			else if (p < hdr - 1) c = R.label[p - 1 - R.nlen];
 			else c = '\n';
 		} else {
 			uint32_t q = p - hdr;
-			if (q < sl.len) c = sl.masked ? (uint8_t)'N' : P.bases[sl.from + q];
-			else if (q == sl.len) c = '\n';
+			if (q < R.base_len) c = R.no_bases ? (uint8_t)'N' : R.bases[q];
+			else if (q == R.base_len) c = '\n';
 			else {
-				q -= sl.len + 1;      /* FASTQ only: "+\n", the qualities, "\n" */
+				q -= R.base_len + 1;      /* FASTQ only: "+\n", the qualities, "\n" */
 				if (q == 0) c = '+';
 				else if (q == 1) c = '\n';
-				else if (q - 2 < sl.len) c = sl.masked ? (uint8_t)(P.out_base + 1) : (uint8_t)(P.quals[sl.from + q - 2] + P.qual_shift);
+				else if (q - 2 < R.qual_len) c = R.no_quals ? R.masked_qual : (uint8_t)(R.quals[q - 2] + R.qual_shift);
 				else c = '\n';
 			}
 		}
 		dst[p] = c;
 	}
+}
+
+/* Read i's record of `bytes` bytes, by one wavefront, to dst; s_label: SEL_LABEL_CAP bytes of LDS of this wavefront. */
+__device__ __forceinline__ void sel_emit(const SelectParams &P, uint64_t i, uint32_t nlen, uint32_t bytes, uint8_t *dst, int lane, uint8_t *s_label) {
+	const uint32_t lablen = sel_label(P, i, s_label, lane == 0);
+	const SelSlice sl = sel_slice(P, i);
+	SelRecord R;
+	R.name = P.text + P.name_off[i]; R.nlen = nlen; R.label = s_label; R.lablen = lablen;
+	R.bases = P.bases + sl.from; R.quals = P.quals + sl.from; R.base_len = R.qual_len = sl.len; R.no_bases = R.no_quals = sl.masked;
+	R.qual_shift = P.qual_shift; R.masked_qual = (uint8_t)(P.out_base + 1); R.fasta = P.fasta != 0;
+	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
+	sel_put_record(R, bytes, dst, lane);
 	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();      /* s_label is rewritten for the next record */
 }
 

@@ -1,6 +1,6 @@
 /*
  * kmr_stages.hip -- the read stages of include/kmernator_amd.h: FASTQ ingest and the kmr_reads batch, its two-bit form, the artifact
- * filter, read selection, coverage normalization and their output text, identifyPairs, duplicate-fragment collapse, and the mercount / mergraph text.
+ * filter and its report, read selection, coverage normalization and their output text, identifyPairs, duplicate-fragment collapse, and the mercount / mergraph text.
  *
  * Host logic only, as kmr_api.hip (the spectrum, which these stages read through kmr_host.hpp); the kernels are the stage headers',
  * each of which this translation unit alone includes.  A stage costs its kernels and a page here: what the stages share is below --
@@ -19,6 +19,7 @@
 #include "kmr_artifact.hpp"
 #include "kmr_select.hpp"
 #include "kmr_normalize.hpp"
+#include "kmr_artifact_report.hpp"
 #include "kmr_pairs.hpp"
 #include "kmr_dedup.hpp"
 #include "kmr_dump.hpp"
@@ -437,6 +438,11 @@ struct kmr_artifact_filter : OnDevice {
 	DevBuf d_keys, d_vals;                                         /* open-addressed lookup table */
 	DevBuf d_bits;                                                 /* presence filter in front of it (ART_FILTER_LOG2 bits) */
 	std::vector<uint64_t> keys; std::vector<uint32_t> vals;        /* the same entries on the host, ascending keys */
+	/* getFilterName (:543-550) of every index: [0] empty, [1, n_seq) the FASTA headers up to the first blank or tab, [n_seq]
+	 * "MinQualityTrim<min_quality>"; on the device each with its leading blank (Read::LABEL_SEP; none for an empty name) as
+	 * d_label_bytes behind the n_seq + 2 offsets of d_label_off (kmr_artifact_report.hpp) */
+	std::vector<std::string> names;
+	DevBuf d_label_bytes, d_label_off;
 };
 
 namespace {
@@ -468,6 +474,16 @@ int art_upload(kmr_handle *h, kmr_artifact_filter *f) {
 	HIPCHK(h, hipGetLastError());
 	HIPCHK(h, hipStreamSynchronize(h->stream));
 	tmp.done();
+	return KMR_OK;
+}
+
+/* the label table of the report's writer */
+int art_upload_names(kmr_handle *h, kmr_artifact_filter *f) {
+	std::vector<uint64_t> off(1, 0); std::string bytes;
+	for (const std::string &nm : f->names) { if (!nm.empty()) { bytes.push_back(' '); bytes += nm; } off.push_back(bytes.size()); }
+	HIPCHK(h, f->d_label_off.alloc(8 * off.size())); HIPCHK(h, f->d_label_bytes.alloc(std::max<size_t>(bytes.size(), 256)));
+	HIPCHK(h, hipMemcpy(f->d_label_off.get<uint64_t>(), off.data(), 8 * off.size(), hipMemcpyHostToDevice));
+	if (!bytes.empty()) HIPCHK(h, hipMemcpy(f->d_label_bytes.get<uint8_t>(), bytes.data(), bytes.size(), hipMemcpyHostToDevice));
 	return KMR_OK;
 }
 
@@ -542,11 +558,16 @@ int kmr_artifact_filter_create(kmr_handle *h, const kmr_artifact_config *cfg, co
 	const uint32_t L = cfg->match_length;
 	/* sequences: read 0 is the empty "no match" read, then the FASTA records in file order (:213-231) */
 	std::vector<std::string> seqs(1);
+	f->names.assign(1, std::string());
 	for (uint64_t i = 0; i < len;) {
 		uint64_t e = i; while (e < len && fasta[e] != '\n') e++;
 		uint64_t le = e; if (le > i && fasta[le - 1] == '\r') le--;
 		if (le > i) {
-			if (fasta[i] == '>') seqs.push_back(std::string());
+			if (fasta[i] == '>') {
+				seqs.push_back(std::string());
+				uint64_t ne = i + 1; while (ne < le && fasta[ne] != ' ' && fasta[ne] != '\t') ne++;
+				f->names.push_back(std::string(fasta + i + 1, fasta + ne));
+			}
 			else if (seqs.size() > 1) for (uint64_t j = i; j < le; j++) seqs.back().push_back((char)toupper((unsigned char)fasta[j]));
 		}
 		i = e + 1;
@@ -573,7 +594,10 @@ int kmr_artifact_filter_create(kmr_handle *h, const kmr_artifact_config *cfg, co
 	}
 	if (edits > 2) return fail(h, KMR_ERR_UNSUPPORTED, "artifact filter: more than two edits left for query time");
 	f->remaining_edits = (uint32_t)edits;
-	const int rc = art_upload(h, f.get());
+	int rc = art_upload(h, f.get());
+	if (rc) return rc;
+	f->names.push_back("MinQualityTrim" + std::to_string(cfg->min_quality));
+	rc = art_upload_names(h, f.get());
 	if (rc) return rc;
 	*out = f.release();
 	return KMR_OK;
@@ -592,13 +616,13 @@ int kmr_artifact_filter_entries(const kmr_artifact_filter *f, uint64_t *keys, ui
 }
 void kmr_artifact_filter_free(kmr_artifact_filter *f) { free_on_device(f); }
 
-int kmr_artifact_filter_apply(kmr_handle *h, const kmr_artifact_filter *f, const kmr_reads *in, const int64_t *mate,
-                              uint32_t *value, uint32_t *min_pass, uint32_t *max_pass, uint8_t *action,
-                              uint32_t *remnant_off, uint32_t *remnant_len, kmr_reads **out) {
-	if (!h || !f || !in) return KMR_ERR_INVALID_ARG;
-	if (out) *out = nullptr;
-	if (f->device != h->device || in->device != h->device) return fail(h, KMR_ERR_INVALID_ARG, "filter, reads and handle must live on one device");
-	hipSetDevice(h->device);
+/* the decisions of one apply step in device memory, good while the call's temporaries live */
+struct ArtDecisions { const uint32_t *value, *min_pass, *max_pass; const uint8_t *action; };
+
+/* kmr_artifact_filter_apply with mate in device memory (or null) and the temporaries the caller's: *keep takes the decisions */
+static int art_apply_core(kmr_handle *h, Scratch &tmp, const kmr_artifact_filter *f, const kmr_reads *in, const int64_t *dmate,
+                          uint32_t *value, uint32_t *min_pass, uint32_t *max_pass, uint8_t *action,
+                          uint32_t *remnant_off, uint32_t *remnant_len, kmr_reads **out, ArtDecisions *keep) {
 	const uint64_t n = in->n;
 	ArtifactTable t{f->d_keys.get<uint64_t>(), f->d_vals.get<uint32_t>(), nullptr, f->log2cap, f->d_bits.get<uint32_t>()};
 	ArtifactParams P;
@@ -606,11 +630,10 @@ int kmr_artifact_filter_apply(kmr_handle *h, const kmr_artifact_filter *f, const
 	P.srBegin = f->cfg.simple_repeat_begin; P.srEnd = f->cfg.simple_repeat_end; P.phix = f->cfg.phix_idx; P.refBegin = f->cfg.reference_begin;
 	P.minQualChar = (int32_t)(int8_t)(uint8_t)(f->cfg.fastq_start_char + f->cfg.min_quality);
 	P.minReadLength = f->cfg.min_read_length;
-	Scratch tmp(h);
-	uint32_t *dval, *dmin, *dmax, *dro, *drl, *dlen, *dflag; uint8_t *dact; int64_t *dmate = nullptr; uint64_t *dridx, *dsrc;
+	uint32_t *dval, *dmin, *dmax, *dro, *drl, *dlen, *dflag; uint8_t *dact; uint64_t *dridx, *dsrc;
 	HIPCHK(h, tmp.take(&dval, n)); HIPCHK(h, tmp.take(&dmin, n)); HIPCHK(h, tmp.take(&dmax, n)); HIPCHK(h, tmp.take(&dro, n)); HIPCHK(h, tmp.take(&drl, n));
 	HIPCHK(h, tmp.take(&dact, n)); HIPCHK(h, tmp.take(&dflag, n)); HIPCHK(h, tmp.take(&dridx, n + 1));
-	if (mate && n) { HIPCHK(h, tmp.take(&dmate, n)); HIPCHK(h, hipMemcpyAsync(dmate, mate, 8 * n, hipMemcpyHostToDevice, h->stream)); }
+	if (keep) { keep->value = dval; keep->min_pass = dmin; keep->max_pass = dmax; keep->action = dact; }
 	uint64_t n_rem = 0;
 	if (n) {
 		const unsigned blocks = (unsigned)((n + 255) / 256);
@@ -642,7 +665,7 @@ int kmr_artifact_filter_apply(kmr_handle *h, const kmr_artifact_filter *f, const
 		if (remnant_len && e == hipSuccess) e = hipMemcpy(remnant_len, drl, 4 * n, hipMemcpyDeviceToHost);
 	}
 	HIPCHK(h, e);
-	if (!out) { tmp.done(); return KMR_OK; }
+	if (!out) return KMR_OK;
 	const uint64_t n_out = n + n_rem;
 	auto r = make_result<kmr_reads>(h);
 	r->n = n_out; r->input_base = in->input_base; r->filtered = in->filtered;
@@ -658,8 +681,29 @@ int kmr_artifact_filter_apply(kmr_handle *h, const kmr_artifact_filter *f, const
 		HIPCHK(h, hipGetLastError());
 	}
 	HIPCHK(h, hipStreamSynchronize(h->stream));
-	tmp.done();
 	*out = r.release();
+	return KMR_OK;
+}
+
+int kmr_artifact_filter_apply(kmr_handle *h, const kmr_artifact_filter *f, const kmr_reads *in, const int64_t *mate,
+                              uint32_t *value, uint32_t *min_pass, uint32_t *max_pass, uint8_t *action,
+                              uint32_t *remnant_off, uint32_t *remnant_len, kmr_reads **out) {
+	if (!h || !f || !in) return KMR_ERR_INVALID_ARG;
+	if (out) *out = nullptr;
+	if (f->device != h->device || in->device != h->device) return fail(h, KMR_ERR_INVALID_ARG, "filter, reads and handle must live on one device");
+	hipSetDevice(h->device);
+	Scratch tmp(h);
+	const int64_t *dmate;
+	int rc = to_device(h, tmp, mate, in->n, &dmate); if (rc) return rc;
+	rc = art_apply_core(h, tmp, f, in, dmate, value, min_pass, max_pass, action, remnant_off, remnant_len, out, nullptr);
+	if (!rc) tmp.done();      /* the core has waited for its last work */
+	return rc;
+}
+int kmr_artifact_filter_name(const kmr_artifact_filter *f, uint32_t idx, char *dst, uint64_t capacity) {
+	if (!f || !dst || idx == 0 || idx >= f->names.size()) return KMR_ERR_INVALID_ARG;
+	const std::string &nm = f->names[idx];
+	if (capacity < nm.size() + 1) return KMR_ERR_CAPACITY;
+	memcpy(dst, nm.c_str(), nm.size() + 1);
 	return KMR_OK;
 }
 
@@ -736,16 +780,25 @@ struct PartitionWork {
 	uint32_t *err; unsigned long long *extra;                            /* the error word; the branch's own counters, zero */
 };
 
+/* the writer of a partition_run: queues the kernel that prints pick p = read pread[p] at byte poff[p] of the picks' text */
+typedef std::function<void(const PartitionWork &, const uint32_t *pread, const uint64_t *poff, kmr_picks *pk)> PartitionWriter;
+static PartitionWriter select_writer(kmr_handle *h, const SelectParams &P) {
+	return [h, &P](const PartitionWork &W, const uint32_t *pread, const uint64_t *poff, kmr_picks *pk) {
+		hipLaunchKernelGGL(select_write_kernel, dim3((unsigned)std::min<uint64_t>((pk->n_picked + SEL_WAVES - 1) / SEL_WAVES, (uint64_t)num_cus(h) * 8)), dim3(SEL_THREADS), 0, h->stream, P,
+		                   (const uint32_t *)W.name_printed, pread, poff, pk->n_picked, pk->text.get<uint8_t>());
+	};
+}
+
 /* A selection from its classification on: the stable partition of the picked items by segment, and their text.  The items are the
- * reads (the partitioned and the plain entry points), or two slots a read that hold reads (`slots`, the normalizing ones).
+ * n reads (the partitioned and the plain entry points), or n_items slots that hold reads (`slots`: two a read for the normalizing
+ * entry points, two a pair of the list for the artifact report).
  * `classify` queues the kernels that leave every item's segment (-1: not picked) and record bytes, every picked read's printed name
  * length, every read's flag and segment, and the picks and bytes of every segment per unit.  After it partition_scan_kernel,
  * partition_rank_kernel, the call's one copy of sizes -- picks, bytes, the error word, the segment table, n_extra counters of the
- * branch -- and select_write_kernel.  keep_read_seg: the picks keep the per-read segments. */
-static int partition_run(kmr_handle *h, Scratch &tmp, const SelectParams &P, const SelRounds &R, uint32_t n_inputs, uint32_t n_segments, const uint64_t *dstarts, bool slots,
+ * branch -- and the writer (select_writer, or the report's).  keep_read_seg: the picks keep the per-read segments. */
+static int partition_run(kmr_handle *h, Scratch &tmp, uint64_t n, uint64_t n_items, const SelRounds &R, uint32_t n_inputs, uint32_t n_segments, const uint64_t *dstarts, bool slots,
                          bool keep_read_seg, uint64_t *extra, size_t n_extra, kmr_picks *pk,
-                         const std::function<int(const PartitionWork &)> &classify) {
-	const uint64_t n = P.n;
+                         const std::function<int(const PartitionWork &)> &classify, const PartitionWriter &write) {
 	const uint32_t S = n_segments;
 	pk->n = n; pk->n_rounds = R.n; pk->n_inputs = n_inputs;
 	for (uint32_t r = 0; r < R.n; r++) { pk->round_depth[r] = R.min_score[r]; pk->round_is_remainder[r] = R.is_remainder[r]; }
@@ -759,7 +812,7 @@ static int partition_run(kmr_handle *h, Scratch &tmp, const SelectParams &P, con
 		HIPCHK(h, hipMemsetAsync(W.picked, 0, n, h->stream)); HIPCHK(h, hipMemsetAsync(W.read_seg, 0xff, 4 * n, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
 		return KMR_OK;
 	}
-	W.n_items = slots ? 2 * n : n; W.item_seg = W.read_seg; W.slot_read = nullptr;
+	W.n_items = n_items; W.item_seg = W.read_seg; W.slot_read = nullptr;
 	W.Q.input_starts = dstarts; W.Q.n_inputs = n_inputs; W.Q.n_segments = S;
 	partition_units(h, W.n_items, S, slots ? 8192 : 4096, W.Q);
 	const size_t cells = (size_t)S * W.Q.n_units, n_tot = 3 + (size_t)4 * S + n_extra;
@@ -784,12 +837,13 @@ static int partition_run(kmr_handle *h, Scratch &tmp, const SelectParams &P, con
 	if (host_tot[2] & SEL_ERR_NAME) return fail(h, KMR_ERR_INVALID_ARG, NAME_SPAN_ERROR);
 	if (host_tot[2] & SEL_ERR_PAIR) return fail(h, KMR_ERR_INVALID_ARG, "the pair list holds an index outside the batch or a pair without a read");
 	if (host_tot[2] & SEL_ERR_TWICE) return fail(h, KMR_ERR_INVALID_ARG, "the pair list names a read twice");
+	if (host_tot[2] & SEL_ERR_UNNAMED) return fail(h, KMR_ERR_INVALID_ARG, "the pair list leaves a read out (identifyPairs names every read, a single one as a pair with one side)");
+	if (host_tot[2] & SEL_ERR_VALUE) return fail(h, KMR_ERR_INVALID_ARG, "a value lies above the filter's n_sequences");
 	pk->n_picked = host_tot[0]; pk->bytes = host_tot[1];
 	timer.mark(1, h->stream);
 	if (pk->bytes) {
 		HIPCHK(h, pk->text.alloc((pk->bytes + 15) & ~(uint64_t)15));
-		hipLaunchKernelGGL(select_write_kernel, dim3((unsigned)std::min<uint64_t>((pk->n_picked + SEL_WAVES - 1) / SEL_WAVES, (uint64_t)num_cus(h) * 8)), dim3(SEL_THREADS), 0, h->stream, P,
-		                   (const uint32_t *)W.name_printed, (const uint32_t *)pread, (const uint64_t *)poff, pk->n_picked, pk->text.get<uint8_t>());
+		write(W, pread, poff, pk);
 		HIPCHK(h, hipGetLastError());
 	}
 	timer.mark(2, h->stream);
@@ -804,10 +858,10 @@ static int partition_run(kmr_handle *h, Scratch &tmp, const SelectParams &P, con
 /* the plain and the partitioned entry points: P's three thresholds are not read, R the rounds, dstarts the inputs' first reads in
  * device memory (null for one input) */
 static int partition_core(kmr_handle *h, Scratch &tmp, const SelectParams &P, const SelRounds &R, const uint64_t *dstarts, uint32_t n_inputs, bool keep_read_seg, kmr_picks *pk) {
-	return partition_run(h, tmp, P, R, n_inputs, R.n * n_inputs, dstarts, false, keep_read_seg, nullptr, 0, pk, [&](const PartitionWork &W) -> int {
+	return partition_run(h, tmp, P.n, P.n, R, n_inputs, R.n * n_inputs, dstarts, false, keep_read_seg, nullptr, 0, pk, [&](const PartitionWork &W) -> int {
 		hipLaunchKernelGGL(partition_classify_kernel, dim3(W.Q.n_units), dim3(SEL_UNIT), 0, h->stream, P, R, W.Q, W.read_seg, W.item_len, W.name_printed, W.picked, W.unit_cnt, W.unit_bytes, W.err);
 		return 0;
-	});
+	}, select_writer(h, P));
 }
 
 /* the one round of a kmr_select_config (checked): what the plain entry points pick, and the partitioned ones with partition_by_depth 0 */
@@ -864,7 +918,7 @@ static int normalize_core(kmr_handle *h, Scratch &tmp, const SelectParams &P, co
 	uint32_t *named = nullptr;      /* reads named by a pair */
 	if (n) HIPCHK(h, tmp.take(&named, n));
 	pk->normalized = true;
-	return partition_run(h, tmp, P, R, n_inputs, n_inputs, dstarts, true, true, pk->norm_info, 3, pk, [&](const PartitionWork &W) -> int {
+	return partition_run(h, tmp, n, 2 * n, R, n_inputs, n_inputs, dstarts, true, true, pk->norm_info, 3, pk, [&](const PartitionWork &W) -> int {
 		HIPCHK(h, hipMemsetAsync(named, 0, 4 * n, h->stream)); HIPCHK(h, hipMemsetAsync(W.item_seg, 0xff, 4 * W.n_items, h->stream));
 		HIPCHK(h, hipMemsetAsync(W.read_seg, 0xff, 4 * n, h->stream)); HIPCHK(h, hipMemsetAsync(W.picked, 0, n, h->stream));
 		if (n_pairs) hipLaunchKernelGGL(normalize_mark_kernel, dim3(grid_for(n_pairs)), dim3(256), 0, h->stream, N, n, named, W.err);
@@ -872,7 +926,7 @@ static int normalize_core(kmr_handle *h, Scratch &tmp, const SelectParams &P, co
 		                   W.read_seg, W.extra, W.err);
 		hipLaunchKernelGGL(normalize_count_kernel, dim3(W.Q.n_units), dim3(SEL_UNIT), 0, h->stream, (const int32_t *)W.item_seg, (const uint32_t *)W.item_len, W.n_items, W.Q, W.unit_cnt, W.unit_bytes);
 		return 0;
-	});
+	}, select_writer(h, P));
 }
 
 static int select_check_args(kmr_handle *h, const SelectCall &c, kmr_picks **out) {
@@ -1138,6 +1192,203 @@ int kmr_picks_device_ptr(const kmr_picks *p, void **dev_text) {
 	return KMR_OK;
 }
 void kmr_picks_free(kmr_picks *p) { free_on_device(p); }
+
+/* ---- the artifact filter's report (kmr_artifact_report.hpp) ---------------- */
+}  // extern "C"
+
+struct kmr_artifact_report : OnDevice {
+	kmr_picks picks;                      /* the records; segment = row * n_inputs + input, row 0 Artifact, row 1 PhiX */
+	uint32_t n_seq = 0;
+	std::vector<uint64_t> counts;         /* [3][n_seq + 1]: discarded, trimmed, bases */
+};
+
+extern "C" {
+
+int kmr_artifact_report_config_init(kmr_artifact_report_config *c) {
+	if (!c) return KMR_ERR_INVALID_ARG;
+	memset(c, 0, sizeof(*c));
+	c->struct_size = (uint32_t)sizeof(kmr_artifact_report_config);
+	c->artifact_output = 1; c->phix_output = 1;      /* --filter-output, --phix-output */
+	c->output_quality_base = 33;                     /* --fastq-output-base-quality */
+	c->print_bases = 0;                              /* N, as the reference writes it */
+	return KMR_OK;
+}
+
+/* What one of the four reporting entry points was called with.  Every array but a text that lies on the device is the host's. */
+struct ReportCall {
+	const char *who;
+	const kmr_artifact_filter *f; const kmr_reads *in;
+	const void *text; uint64_t text_len; bool text_on_device;
+	const int64_t *read1, *read2; uint64_t n_pairs;
+	const uint64_t *input_starts; uint32_t n_inputs;
+	const kmr_artifact_report_config *cfg;
+};
+
+/* everything that needs no device; makes n_inputs 1 for no input_starts */
+static int report_check(kmr_handle *h, ReportCall &c, kmr_artifact_report **report) {
+	const std::string who = c.who;
+	if (report) *report = nullptr;
+	if (!c.cfg) return fail(h, KMR_ERR_INVALID_ARG, "kmr_artifact_report_config: NULL");
+	if (c.cfg->struct_size != sizeof(kmr_artifact_report_config))
+		return fail(h, KMR_ERR_INVALID_ARG, "kmr_artifact_report_config: struct_size " + std::to_string(c.cfg->struct_size) + " is not " + std::to_string(sizeof(kmr_artifact_report_config)));
+	if (c.cfg->output_quality_base != 33 && c.cfg->output_quality_base != 64) return fail(h, KMR_ERR_INVALID_ARG, "kmr_artifact_report_config: output_quality_base must be 33 or 64");
+	if (!h) return fail(h, KMR_ERR_INVALID_ARG, who + ": NULL handle");
+	if (!c.f || !c.in || !report || (c.text_len && !c.text)) return fail(h, KMR_ERR_INVALID_ARG, who + ": NULL argument");
+	if (c.f->device != h->device || c.in->device != h->device) return fail(h, KMR_ERR_INVALID_ARG, "filter, reads and handle must live on one device");
+	if (c.cfg->phix_output && c.f->cfg.phix_idx == 0) return fail(h, KMR_ERR_INVALID_ARG, who + ": phix_output with a filter whose phix_idx is 0");
+	if ((c.read1 != nullptr) != (c.read2 != nullptr)) return fail(h, KMR_ERR_INVALID_ARG, "the pair list: read1 and read2 go together");
+	const uint64_t n = c.in->n;
+	if (n >= 0xffffffffull) return fail(h, KMR_ERR_UNSUPPORTED, who + ": a batch holds fewer than 2^32 - 1 reads (pick indices are 32-bit)");
+	if (c.read1 && c.n_pairs && !n) return fail(h, KMR_ERR_INVALID_ARG, who + ": a pair list for an empty batch");
+	if (c.read1 && !c.n_pairs && n) return fail(h, KMR_ERR_INVALID_ARG, "the pair list leaves a read out (it is empty)");
+	if (c.input_starts) {
+		if (c.n_inputs == 0) return fail(h, KMR_ERR_INVALID_ARG, "input_starts without n_inputs");
+		bool ok;
+		const uint32_t at = sel_check_input_starts(c.input_starts, c.n_inputs, &ok);
+		if (!ok) return fail(h, KMR_ERR_INVALID_ARG, "input_starts[" + std::to_string(at) + "]: the read indices start at 0 and ascend");
+		if (c.input_starts[c.n_inputs] != n) return fail(h, KMR_ERR_INVALID_ARG, who + ": input_starts ends at " + std::to_string(c.input_starts[c.n_inputs]) + ", the batch holds " + std::to_string(n) + " reads");
+	} else if (c.n_inputs > 1) return fail(h, KMR_ERR_INVALID_ARG, "input_starts is NULL for " + std::to_string(c.n_inputs) + " inputs");
+	else c.n_inputs = 1;
+	if (2ull * c.n_inputs > (uint64_t)SEL_MAX_SEGMENTS) return fail(h, KMR_ERR_UNSUPPORTED, who + ": more than " + std::to_string(SEL_MAX_SEGMENTS / 2) + " inputs");
+	return 0;
+}
+
+/* the pair list and the input boundaries of a checked call in device memory (null for none) */
+static int report_args(kmr_handle *h, Scratch &tmp, const ReportCall &c, const uint8_t **dtext, const int64_t **dr1, const int64_t **dr2, const uint64_t **dstarts) {
+	int rc = to_device(h, tmp, (const uint8_t *)c.text, c.text_len, dtext, c.text_on_device); if (rc) return rc;
+	rc = to_device(h, tmp, c.read1, c.n_pairs, dr1); if (rc) return rc;
+	rc = to_device(h, tmp, c.read2, c.n_pairs, dr2); if (rc) return rc;
+	return to_device(h, tmp, c.n_inputs > 1 ? c.input_starts : nullptr, (uint64_t)c.n_inputs + 1, dstarts);
+}
+
+/* A checked call from the decisions in device memory on: the pair list's check, the classification with the counters, the stable
+ * partition by (row, input) and the writer.  One wait, for the totals. */
+static int report_core(kmr_handle *h, Scratch &tmp, const ReportCall &c, const uint8_t *dtext, const int64_t *dr1, const int64_t *dr2, const uint64_t *dstarts, const ArtDecisions &D,
+                       kmr_artifact_report *rep) {
+	const kmr_artifact_filter *f = c.f; const kmr_reads *in = c.in;
+	const uint64_t n = in->n, n_pairs = c.read1 ? c.n_pairs : 0;
+	const uint32_t rows = f->n_seq + 1;
+	rep->n_seq = f->n_seq; rep->counts.assign((size_t)3 * rows, 0);
+	rep->picks.device = h->device;
+	ArtReportParams A;
+	A.bases = in->bases.get<uint8_t>(); A.quals = in->quals.get<uint8_t>(); A.offsets = in->offsets.get<uint64_t>(); A.name_off = in->name_off.get<uint64_t>(); A.name_len = in->name_len.get<uint32_t>();
+	A.text = dtext; A.text_len = c.text_len; A.n = n; A.read1 = c.read1 ? dr1 : nullptr; A.read2 = c.read1 ? dr2 : nullptr; A.n_pairs = n_pairs;
+	A.value = D.value; A.min_pass = D.min_pass; A.max_pass = D.max_pass; A.action = D.action;
+	A.label_bytes = f->d_label_bytes.get<uint8_t>(); A.label_off = f->d_label_off.get<uint64_t>();
+	A.n_seq = f->n_seq; A.phix = f->cfg.phix_idx; A.artifact_output = c.cfg->artifact_output ? 1u : 0u; A.phix_output = c.cfg->phix_output ? 1u : 0u; A.print_bases = c.cfg->print_bases ? 1u : 0u;
+	A.out_base = c.cfg->output_quality_base; A.qual_shift = (int32_t)c.cfg->output_quality_base - (int32_t)h->cfg.fastq_start_char;
+	const size_t ctr_bytes = (size_t)24 * rows;
+	const bool lds = h->tune.artifact_report_lds < 0 ? ctr_bytes <= ART_REPORT_LDS_CAP : (h->tune.artifact_report_lds == 1 && ctr_bytes <= ART_REPORT_LDS_MOST);
+	h->last_artifact_report_lds = lds ? 1 : 0;
+	uint32_t *named = nullptr, *read_label = nullptr;
+	if (n) { HIPCHK(h, tmp.take(&read_label, n)); if (A.read1) HIPCHK(h, tmp.take(&named, n)); }
+	SelRounds R = {}; R.n = 2;
+	const bool slots = A.read1 != nullptr;
+	return partition_run(h, tmp, n, slots ? 2 * n_pairs : n, R, c.n_inputs, 2 * c.n_inputs, dstarts, slots, true, rep->counts.data(), rep->counts.size(), &rep->picks,
+		[&](const PartitionWork &W) -> int {
+			HIPCHK(h, hipMemsetAsync(W.item_seg, 0xff, 4 * W.n_items, h->stream)); HIPCHK(h, hipMemsetAsync(W.read_seg, 0xff, 4 * n, h->stream)); HIPCHK(h, hipMemsetAsync(W.picked, 0, n, h->stream));
+			if (slots) {
+				NormalizeParams N = {}; N.read1 = dr1; N.read2 = dr2; N.n_pairs = n_pairs;
+				HIPCHK(h, hipMemsetAsync(named, 0, 4 * n, h->stream));
+				hipLaunchKernelGGL(normalize_mark_kernel, dim3(grid_for(n_pairs)), dim3(256), 0, h->stream, N, n, named, W.err);
+				hipLaunchKernelGGL(artifact_pairs_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, (const uint32_t *)named, n, W.err);
+			}
+			if (lds) hipLaunchKernelGGL(artifact_classify_kernel<true>, dim3(W.Q.n_units), dim3(SEL_UNIT), ctr_bytes, h->stream, A, W.Q, W.n_items, W.slot_read, W.item_seg, W.item_len, W.name_printed, read_label,
+			                            W.picked, W.read_seg, W.unit_cnt, W.unit_bytes, W.extra, W.err);
+			else hipLaunchKernelGGL(artifact_classify_kernel<false>, dim3(W.Q.n_units), dim3(SEL_UNIT), 0, h->stream, A, W.Q, W.n_items, W.slot_read, W.item_seg, W.item_len, W.name_printed, read_label,
+			                        W.picked, W.read_seg, W.unit_cnt, W.unit_bytes, W.extra, W.err);
+			return 0;
+		},
+		[&](const PartitionWork &W, const uint32_t *pread, const uint64_t *poff, kmr_picks *pk) {
+			hipLaunchKernelGGL(artifact_write_kernel, dim3((unsigned)std::min<uint64_t>((pk->n_picked + SEL_WAVES - 1) / SEL_WAVES, (uint64_t)num_cus(h) * 8)), dim3(SEL_THREADS), 0, h->stream, A,
+			                   (const uint32_t *)W.name_printed, (const uint32_t *)read_label, pread, poff, pk->n_picked, pk->text.get<uint8_t>());
+		});
+}
+
+static int report_from_host(kmr_handle *h, ReportCall &c, const uint32_t *value, const uint8_t *action, const uint32_t *min_pass, const uint32_t *max_pass, kmr_artifact_report **report) {
+	int rc = report_check(h, c, report); if (rc) return rc;
+	const uint64_t n = c.in->n;
+	if (n && (!value || !action || !min_pass || !max_pass)) return fail(h, KMR_ERR_INVALID_ARG, std::string(c.who) + ": NULL argument");
+	hipSetDevice(h->device);
+	auto rep = make_result<kmr_artifact_report>(h);
+	Scratch tmp(h);
+	const uint8_t *dtext; const int64_t *dr1, *dr2; const uint64_t *dstarts;
+	rc = report_args(h, tmp, c, &dtext, &dr1, &dr2, &dstarts); if (rc) return rc;
+	ArtDecisions D;
+	rc = to_device(h, tmp, value, n, &D.value); if (rc) return rc;
+	rc = to_device(h, tmp, min_pass, n, &D.min_pass); if (rc) return rc;
+	rc = to_device(h, tmp, max_pass, n, &D.max_pass); if (rc) return rc;
+	rc = to_device(h, tmp, action, n, &D.action); if (rc) return rc;
+	rc = report_core(h, tmp, c, dtext, dr1, dr2, dstarts, D, rep.get());
+	if (!rc) *report = rep.release();
+	return rc;
+}
+
+/* the fused form: mate from the pair list, the apply step, the report from its decisions */
+static int report_fused(kmr_handle *h, ReportCall &c, uint32_t *value, uint32_t *min_pass, uint32_t *max_pass, uint8_t *action, uint32_t *remnant_off, uint32_t *remnant_len, kmr_reads **out,
+                        kmr_artifact_report **report) {
+	if (out) *out = nullptr;
+	int rc = report_check(h, c, report); if (rc) return rc;
+	const uint64_t n = c.in->n, n_pairs = c.read1 ? c.n_pairs : 0;
+	hipSetDevice(h->device);
+	auto rep = make_result<kmr_artifact_report>(h);
+	Scratch tmp(h);
+	const uint8_t *dtext; const int64_t *dr1, *dr2; const uint64_t *dstarts;
+	rc = report_args(h, tmp, c, &dtext, &dr1, &dr2, &dstarts); if (rc) return rc;
+	int64_t *dmate = nullptr;
+	if (n_pairs) {
+		HIPCHK(h, tmp.take(&dmate, n)); HIPCHK(h, hipMemsetAsync(dmate, 0xff, 8 * n, h->stream));
+		hipLaunchKernelGGL(artifact_mate_kernel, dim3(grid_for(n_pairs)), dim3(256), 0, h->stream, dr1, dr2, n_pairs, n, dmate);
+		HIPCHK(h, hipGetLastError());
+	}
+	ArtDecisions D;
+	kmr_reads *made = nullptr;
+	rc = art_apply_core(h, tmp, c.f, c.in, dmate, value, min_pass, max_pass, action, remnant_off, remnant_len, out ? &made : nullptr, &D); if (rc) return rc;
+	rc = report_core(h, tmp, c, dtext, dr1, dr2, dstarts, D, rep.get());
+	if (rc) { free_on_device(made); return rc; }
+	if (out) *out = made;
+	*report = rep.release();
+	return KMR_OK;
+}
+
+int kmr_artifact_filter_report(kmr_handle *h, const kmr_artifact_filter *f, const kmr_reads *in, const char *text, uint64_t text_len, const int64_t *read1, const int64_t *read2, uint64_t n_pairs,
+                               const uint32_t *value, const uint8_t *action, const uint32_t *min_pass, const uint32_t *max_pass, const uint64_t *input_starts, uint32_t n_inputs,
+                               const kmr_artifact_report_config *cfg, kmr_artifact_report **report) {
+	ReportCall c = {"kmr_artifact_filter_report", f, in, text, text_len, false, read1, read2, n_pairs, input_starts, n_inputs, cfg};
+	return report_from_host(h, c, value, action, min_pass, max_pass, report);
+}
+int kmr_artifact_filter_report_dev(kmr_handle *h, const kmr_artifact_filter *f, const kmr_reads *in, const void *dev_text, uint64_t text_len, const int64_t *read1, const int64_t *read2, uint64_t n_pairs,
+                                   const uint32_t *value, const uint8_t *action, const uint32_t *min_pass, const uint32_t *max_pass, const uint64_t *input_starts, uint32_t n_inputs,
+                                   const kmr_artifact_report_config *cfg, kmr_artifact_report **report) {
+	ReportCall c = {"kmr_artifact_filter_report_dev", f, in, dev_text, text_len, true, read1, read2, n_pairs, input_starts, n_inputs, cfg};
+	return report_from_host(h, c, value, action, min_pass, max_pass, report);
+}
+int kmr_artifact_filter_apply_report(kmr_handle *h, const kmr_artifact_filter *f, const kmr_reads *in, const char *text, uint64_t text_len, const int64_t *read1, const int64_t *read2, uint64_t n_pairs,
+                                     uint32_t *value, uint32_t *min_pass, uint32_t *max_pass, uint8_t *action, uint32_t *remnant_off, uint32_t *remnant_len, kmr_reads **out,
+                                     const uint64_t *input_starts, uint32_t n_inputs, const kmr_artifact_report_config *cfg, kmr_artifact_report **report) {
+	ReportCall c = {"kmr_artifact_filter_apply_report", f, in, text, text_len, false, read1, read2, n_pairs, input_starts, n_inputs, cfg};
+	return report_fused(h, c, value, min_pass, max_pass, action, remnant_off, remnant_len, out, report);
+}
+int kmr_artifact_filter_apply_report_dev(kmr_handle *h, const kmr_artifact_filter *f, const kmr_reads *in, const void *dev_text, uint64_t text_len, const int64_t *read1, const int64_t *read2,
+                                         uint64_t n_pairs, uint32_t *value, uint32_t *min_pass, uint32_t *max_pass, uint8_t *action, uint32_t *remnant_off, uint32_t *remnant_len, kmr_reads **out,
+                                         const uint64_t *input_starts, uint32_t n_inputs, const kmr_artifact_report_config *cfg, kmr_artifact_report **report) {
+	ReportCall c = {"kmr_artifact_filter_apply_report_dev", f, in, dev_text, text_len, true, read1, read2, n_pairs, input_starts, n_inputs, cfg};
+	return report_fused(h, c, value, min_pass, max_pass, action, remnant_off, remnant_len, out, report);
+}
+int kmr_artifact_report_counts(const kmr_artifact_report *report, uint64_t *discarded, uint64_t *trimmed, uint64_t *bases, uint64_t capacity) {
+	if (!report) return KMR_ERR_INVALID_ARG;
+	const size_t rows = (size_t)report->n_seq + 1;
+	if (capacity < rows) return KMR_ERR_CAPACITY;
+	const uint64_t *c = report->counts.data();
+	if (discarded) memcpy(discarded, c, 8 * rows); if (trimmed) memcpy(trimmed, c + rows, 8 * rows); if (bases) memcpy(bases, c + 2 * rows, 8 * rows);
+	return KMR_OK;
+}
+int kmr_artifact_report_picks(const kmr_artifact_report *report, const kmr_picks **picks) {
+	if (!report || !picks) return KMR_ERR_INVALID_ARG;
+	*picks = &report->picks;
+	return KMR_OK;
+}
+void kmr_artifact_report_free(kmr_artifact_report *report) { free_on_device(report); }
 
 /* ---- ReadSet::identifyPairs on the device (kmr_pairs.hpp) ---------------- */
 /* dtext: device memory */

@@ -849,10 +849,15 @@ class FilterKnownOddities(_DeviceObject):
         _ok(self.sp.lib.kmr_artifact_filter_entries(self.f, keys.ctypes.data_as(C.POINTER(C.c_uint64)), vals.ctypes.data_as(C.POINTER(C.c_uint32)), keys.size), "kmr_artifact_filter_entries")
         return keys, vals
 
-    def applyFilter(self, reads, mate=None, want_reads=True):
+    def applyFilter(self, reads, mate=None, want_reads=True, report=False, pairs=None, **report_options):
         """applyFilter(ReadSet&) (:663-733).  Returns (results, filtered ReadSet): results = dict of per-read arrays value,
         min_pass, max_pass, action (0 untouched / 1 trimmed / 2 discarded), remnant_off, remnant_len; the new ReadSet holds the
-        trimmed reads in place and the rescued remnants behind them."""
+        trimmed reads in place and the rescued remnants behind them.  report=True: the fused form (applyFilterReport) over the
+        pair list `pairs` in place of `mate`, with its options; returns (results, filtered ReadSet, FilterReport)."""
+        if report:
+            if mate is not None:
+                raise KmerSpectrumError("applyFilter(report=True) takes the pair list (pairs=), not mate")
+            return self.applyFilterReport(reads, pairs=pairs, want_reads=want_reads, **report_options)
         n = reads.n
         res = {k: np.zeros(max(1, n), dtype=np.uint32) for k in ("value", "min_pass", "max_pass", "remnant_off", "remnant_len")}
         res["action"] = np.zeros(max(1, n), dtype=np.uint8)
@@ -868,6 +873,157 @@ class FilterKnownOddities(_DeviceObject):
                       res["remnant_len"].ctypes.data_as(u32), C.byref(out) if want_reads else None)
         res = {k: v[:n] for k, v in res.items()}
         return res, (ReadSet._adopt(self.sp, reads.text, out, getattr(reads, "store_comment", True)) if want_reads else None)
+
+    def getFilterName(self, idx):
+        """getFilterName (:543-550): the header name of sequence idx in [1, n_sequences), "MinQualityTrim<q>" for n_sequences"""
+        buf = C.create_string_buffer(4096)
+        _ok(self.sp.lib.kmr_artifact_filter_name(self._live(), int(idx), buf, len(buf)), "kmr_artifact_filter_name")
+        return buf.value.decode()
+
+    def _report_config(self, artifact_output, phix_output, output_quality_base, print_bases):
+        cfg = _lib.KmrArtifactReportConfig()
+        self.sp.lib.kmr_artifact_report_config_init(C.byref(cfg))
+        cfg.artifact_output, cfg.phix_output = (1 if artifact_output else 0), (1 if phix_output else 0)
+        cfg.output_quality_base, cfg.print_bases = int(output_quality_base), (1 if print_bases else 0)
+        return cfg
+
+    @staticmethod
+    def _pair_args(pairs):
+        """pairs (a ReadPairs, or (read1, read2) arrays with -1 for a missing side, or None) as (the arrays, their pointers, n_pairs)"""
+        if pairs is None:
+            return None, (None, None), 0
+        if isinstance(pairs, ReadPairs):
+            pairs = (pairs.pairs[:, 0], pairs.pairs[:, 1])
+        r1, r2 = (np.ascontiguousarray(x, dtype=np.int64) for x in pairs)
+        assert r1.size == r2.size
+        i64 = C.POINTER(C.c_int64)
+        return (r1, r2), (r1.ctypes.data_as(i64), r2.ctypes.data_as(i64)), r1.size
+
+    def _report_call(self, name, reads, pairs, input_starts, device_text, cfg, *mid):
+        """the arguments every reporting entry point shares around its own `mid`: returns the FilterReport"""
+        keep, (p1, p2), n_pairs = self._pair_args(pairs)
+        starts = None if input_starts is None else np.ascontiguousarray(input_starts, dtype=np.uint64)
+        sp = None if starts is None else starts.ctypes.data_as(C.POINTER(C.c_uint64))
+        buf = np.frombuffer(reads.text, dtype=np.uint8)
+        text = C.c_void_p(device_text) if device_text is not None else (buf.ctypes.data_as(C.c_void_p) if buf.size else None)
+        rep = C.c_void_p()
+        self.sp._call(name + ("_dev" if device_text is not None else ""), self.sp.h, self._live(), reads.r, text, buf.size, p1, p2, n_pairs, *mid,
+                      sp, 0 if starts is None else starts.size - 1, C.byref(cfg), C.byref(rep))
+        return FilterReport(self, rep, reads.n)
+
+    def report(self, read_set, results, pairs=None, input_starts=None, artifact_output=True, phix_output=None, output_quality_base=33, print_bases=False,
+               device_text=None):
+        """What the reference's Recorder makes of applyFilter's `results` for the batch `read_set` they were computed from
+        (kmr_artifact_filter_report): a FilterReport with the -Artifact.fastq / -PhiX.fastq records and the per-sequence counters.
+        pairs = the pair list (a ReadPairs or (read1, read2) arrays; None: every read on its own), input_starts as
+        ReadSelector.selectReads takes them; phix_output defaults to whether the filter knows a PhiX sequence; print_bases writes
+        the read's bases where the reference writes N; device_text = device pointer of the name text."""
+        cfg = self._report_config(artifact_output, self.cfg.phix_idx != 0 if phix_output is None else phix_output, output_quality_base, print_bases)
+        n = read_set.n
+        arr = {k: np.ascontiguousarray(results[k], dtype=t) for k, t in (("value", np.uint32), ("action", np.uint8), ("min_pass", np.uint32), ("max_pass", np.uint32))}
+        for a in arr.values():
+            assert a.size == n
+        u32, u8 = C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)
+        return self._report_call("artifact_filter_report", read_set, pairs, input_starts, device_text, cfg, arr["value"].ctypes.data_as(u32), arr["action"].ctypes.data_as(u8),
+                                 arr["min_pass"].ctypes.data_as(u32), arr["max_pass"].ctypes.data_as(u32))
+
+    def applyFilterReport(self, reads, pairs=None, input_starts=None, want_reads=True, want_results=True, artifact_output=True, phix_output=None, output_quality_base=33,
+                          print_bases=False, device_text=None):
+        """applyFilter and its report in one call that keeps the decisions on the device (kmr_artifact_filter_apply_report): returns
+        (results, filtered ReadSet, FilterReport) with results and the ReadSet as applyFilter gives them (None where not wanted);
+        the mate of every read follows from `pairs`."""
+        cfg = self._report_config(artifact_output, self.cfg.phix_idx != 0 if phix_output is None else phix_output, output_quality_base, print_bases)
+        n = reads.n
+        res = None
+        ptrs = [None] * 6
+        if want_results:
+            res = {k: np.zeros(max(1, n), dtype=np.uint32) for k in ("value", "min_pass", "max_pass", "remnant_off", "remnant_len")}
+            res["action"] = np.zeros(max(1, n), dtype=np.uint8)
+            u32 = C.POINTER(C.c_uint32)
+            ptrs = [res["value"].ctypes.data_as(u32), res["min_pass"].ctypes.data_as(u32), res["max_pass"].ctypes.data_as(u32), res["action"].ctypes.data_as(C.POINTER(C.c_uint8)),
+                    res["remnant_off"].ctypes.data_as(u32), res["remnant_len"].ctypes.data_as(u32)]
+        out = C.c_void_p()
+        rep = self._report_call("artifact_filter_apply_report", reads, pairs, input_starts, device_text, cfg, *ptrs, C.byref(out) if want_reads else None)
+        if res is not None:
+            res = {k: v[:n] for k, v in res.items()}
+        return res, (ReadSet._adopt(self.sp, reads.text, out, getattr(reads, "store_comment", True)) if want_reads else None), rep
+
+
+class FilterReport(_DeviceObject):
+    """The artifact filter's report (kmr_artifact_report): .counts() = (discarded, trimmed, bases) per sequence index, .toString()
+    the table applyFilter logs (:714-725), .files(output, input_prefixes) the (name, bytes) of every -Artifact.fastq / -PhiX.fastq
+    file that holds a record, .device_text() the records where they were written.  .segments and .read_segment as a ReadSelector
+    holds them: two rows (0 Artifact, 1 PhiX) times the inputs."""
+    _HANDLE, _FREE = "_rep", "kmr_artifact_report_free"
+    ROWS = ("-Artifact.fastq", "-PhiX.fastq")
+
+    def __init__(self, flt, handle, n_reads):
+        self.sp, self.filter, self._rep, self.n_reads = flt.sp, flt, handle, n_reads
+        pk = C.c_void_p()
+        _ok(self.sp.lib.kmr_artifact_report_picks(handle, C.byref(pk)), "kmr_artifact_report_picks")
+        self._picks = pk
+        n, b = C.c_uint64(), C.c_uint64()
+        _ok(self.sp.lib.kmr_picks_info(pk, C.byref(n), C.byref(b)), "kmr_picks_info")
+        self.n_records, self.bytes = n.value, b.value
+        self._text = self._counts = None
+        nr, ni = C.c_uint32(), C.c_uint32()
+        _ok(self.sp.lib.kmr_picks_segments_info(pk, C.byref(nr), C.byref(ni)), "kmr_picks_segments_info")
+        nr, ni = nr.value, ni.value
+        cols = [np.zeros(max(1, nr * ni), dtype=np.uint64) for _ in range(4)]
+        rseg = np.full(max(1, n_reads), -1, dtype=np.int32)
+        p = ReadSelector._p
+        _ok(self.sp.lib.kmr_picks_segments_copy(pk, None, None, *[p(c, C.c_uint64) for c in cols], p(rseg, C.c_int32)), "kmr_picks_segments_copy")
+        self.segments = {k: c[:nr * ni].reshape(nr, ni) for k, c in zip(("first_pick", "picks", "first_byte", "bytes"), cols)}
+        self.read_segment = rseg[:n_reads]
+
+    def counts(self):
+        """(discarded, trimmed, bases): uint64 arrays of n_sequences + 1 entries"""
+        if self._counts is None:
+            rows = self.filter.n_sequences + 1
+            a = [np.zeros(rows, dtype=np.uint64) for _ in range(3)]
+            _ok(self.sp.lib.kmr_artifact_report_counts(self._live(), *[ReadSelector._p(x, C.c_uint64) for x in a], rows), "kmr_artifact_report_counts")
+            self._counts = tuple(a)
+        return self._counts
+
+    def toString(self):
+        """the text applyFilter logs (:714-725)"""
+        d, t, b = self.counts()
+        s = "Final Filter Matches to reads:%d\nDiscarded Reads:%d\nTrimmed Reads:%d\nDiscarded/Trimmed Bases:%d\n\n\tDiscarded\tAffected\tBasesRemoved\tMatch\n" % (
+            int(t.sum()), int(d.sum()), int(t.sum()), int(b.sum()))
+        for i in range(d.size):
+            if b[i] > 0:
+                s += "\t%d\t%d\t%d\t%s\n" % (int(d[i]), int(t[i]), int(b[i]), self.filter.getFilterName(i))
+        return s
+
+    def text(self):
+        """all records: the Artifact files input by input, then the PhiX files"""
+        if self._text is None:
+            buf = np.zeros(max(1, self.bytes), dtype=np.uint8)
+            _ok(self.sp.lib.kmr_picks_copy(self._picks, buf.ctypes.data_as(C.c_void_p), self.bytes, None), "kmr_picks_copy")
+            self._text = buf[:self.bytes].tobytes()
+        return self._text
+
+    def files(self, output="", input_prefixes=None):
+        """(file name, bytes) as the reference's OfstreamMaps name them (:670-677): output + "-" + the input's prefix +
+        "-Artifact.fastq" / "-PhiX.fastq", the Artifact files first; a file without a record is left out"""
+        seg, text = self.segments, self.text()
+        n_inputs = seg["picks"].shape[1]
+        prefixes = list(input_prefixes) if input_prefixes is not None else ["transformed-%d" % (j + 1) for j in range(n_inputs)]
+        if len(prefixes) != n_inputs:
+            raise KmerSpectrumError("FilterReport.files: %d input_prefixes for %d inputs" % (len(prefixes), n_inputs))
+        first, size = seg["first_byte"], seg["bytes"]
+        return [("%s-%s%s" % (output, prefixes[j], self.ROWS[r]), text[int(first[r, j]):int(first[r, j]) + int(size[r, j])])
+                for r in range(2) for j in range(n_inputs) if seg["picks"][r, j]]
+
+    def device_text(self):
+        """(device pointer, bytes) of the records (kmr_picks_device_ptr); valid until close()"""
+        p = C.c_void_p()
+        _ok(self.sp.lib.kmr_picks_device_ptr(self._picks, C.byref(p)), "kmr_picks_device_ptr")
+        return p.value, self.bytes
+
+    def close(self):
+        self._picks = None      # borrowed from the report
+        super().close()
 
 
 
