@@ -1701,15 +1701,35 @@ template <int W> SkLong<W> sk_own_lists(kmr_handle *h, bool refined) {
 }
 /* sk_count_kernel's form for (W, ext, tracking, uni) together with the dynamic LDS it wants, the attribute set */
 template <int W> struct SkCountLaunch {
-	void (*kern)(PoolView, const uint64_t *, const uint64_t *, uint64_t, uint32_t, CountOut, FinalizeParams, unsigned int *, uint32_t, SkTrackView, SkLong<W>);
+	void (*kern)(const uint4 *, const uint64_t *, const uint64_t *, uint64_t, uint32_t, SkCountHot, unsigned int *, uint32_t, const SkCountArgs<W> *);
 	size_t smem;
 };
-template <int W, int LOG2S, bool TRACK, bool EXT, bool UNI> SkCountLaunch<W> sk_count_form() { return {sk_count_kernel<W, LOG2S, TRACK, EXT, UNI>, sk_count_smem_bytes<W, LOG2S, TRACK, EXT, UNI>()}; }
-template <int W> int sk_count_select(kmr_handle *h, bool ext, bool tracking, bool uni, SkCountLaunch<W> &k) {
-	k = ext ? sk_count_form<W, COUNT_LOG2S_EXT, false, true, false>() : (tracking ? sk_count_form<W, COUNT_LOG2S, true, false, false>() :
-	    (uni ? sk_count_form<W, COUNT_LOG2S, false, false, true>() : sk_count_form<W, COUNT_LOG2S, false, false, false>()));
+template <int W, int LOG2S, bool TRACK, bool EXT, bool UNI, bool ITEM> SkCountLaunch<W> sk_count_form() { return {sk_count_kernel<W, LOG2S, TRACK, EXT, UNI, ITEM>, sk_count_smem_bytes<W, LOG2S, TRACK, EXT, UNI>()}; }
+template <int W, bool ITEM> SkCountLaunch<W> sk_count_forms(bool ext, bool tracking, bool uni) {
+	if constexpr (!ITEM) { if (tracking && !ext) return sk_count_form<W, COUNT_LOG2S, true, false, false, false>(); }
+	return ext ? sk_count_form<W, COUNT_LOG2S_EXT, false, true, false, ITEM>() :
+	    (uni ? sk_count_form<W, COUNT_LOG2S, false, false, true, ITEM>() : sk_count_form<W, COUNT_LOG2S, false, false, false, ITEM>());
+}
+/* The kernel fixes at compile time what a launch used to tell it through null pointers: `item` (the pass over work items of long lists,
+ * lg.item_c0 and the merge table) and the form of the weak entries (packed without per-bucket counts unless ext).  An `out` or `lg` of
+ * the other form is an internal error here, not a null pointer on the device. */
+template <int W> int sk_count_select(kmr_handle *h, bool ext, bool tracking, bool uni, bool item, const CountOut &out, const SkLong<W> &lg, SkCountLaunch<W> &k) {
+	if (item && tracking) return fail(h, KMR_ERR_STATE, "internal: the size tracker's count pass has no long-list items");
+	if (item != (lg.item_c0 != nullptr) || (item && (!lg.item_c1 || !lg.merge.slots || !lg.merge_used))) return fail(h, KMR_ERR_STATE, "internal: count pass and its work items disagree");
+	if (ext ? (!out.wkeys || !out.wvals || !out.weakCount) : !out.wentries) return fail(h, KMR_ERR_STATE, "internal: count pass and its entry buffers disagree");
+	k = item ? sk_count_forms<W, true>(ext, tracking, uni) : sk_count_forms<W, false>(ext, tracking, uni);
 	const auto kern = k.kern; const size_t smem = k.smem;
 	HIPCHK(h, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+	return 0;
+}
+/* One launch of the count pass: its rarely read arguments go into an SkCountArgs of the finalize arena first (a one-thread kernel on the
+ * same stream writes it: no host buffer that would have to outlive the call), the rest goes by value */
+template <int W> int sk_count_launch(kmr_handle *h, const SkCountLaunch<W> &k, int grid, const uint64_t *ls, const uint64_t *lc, uint64_t nl, const CountOut &out, const FinalizeParams &f, const SkTrackView &tv, const SkLong<W> &lg) {
+	SkCountArgs<W> a{out, f, tv, lg};
+	SkCountArgs<W> *d = nullptr;
+	int rc = arena_get(h, &d, 1); if (rc) return rc;
+	hipLaunchKernelGGL(sk_count_args_kernel<W>, dim3(1), dim3(64), 0, h->stream, a, d);
+	hipLaunchKernelGGL(k.kern, dim3(grid), dim3(SKC_THREADS), k.smem, h->stream, (const uint4 *)pool_view(h, h->l1).base, ls, lc, nl, h->k, sk_count_hot<W>(a), h->work_counter.get<unsigned int>(), sk_dbg_flags("KMR_SK_COUNT_DBG"), (const SkCountArgs<W> *)d);
 	return 0;
 }
 
@@ -1843,10 +1863,10 @@ template <int W> int sk_count_pass(kmr_handle *h, SkFinalize<W> &p) {
 		int rc = 0;
 		const int grid = (int)std::min<uint64_t>((uint64_t)num_cus(h) * 4, (nl / p.lgMain.list_stride + SK_LBATCH) / SK_LBATCH);
 		SkCountLaunch<W> k;
-		rc = sk_count_select<W>(h, p.ext, p.tracking, p.uni, k); if (rc) return rc;
+		rc = sk_count_select<W>(h, p.ext, p.tracking, p.uni, false, out, p.lgMain, k); if (rc) return rc;
 		if (p.tracking) HIPCHK(h, hipMemsetAsync(tv.d_unique, 0, 8 * (tv.n + 1), h->stream));
 		if (dbg()) { int nb = 0; hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)k.kern, SKC_THREADS, k.smem); fprintf(stderr, "sk_count<W=%d>: %d blocks per CU (LDS %zu), %llu lists, %u chunks\n", W, nb, k.smem, (unsigned long long)nl, p.nch); }
-		hipLaunchKernelGGL(k.kern, dim3(grid), dim3(SKC_THREADS), k.smem, h->stream, pool_view(h, h->l1), p.ls, p.lc, nl, h->k, out, p.f, h->work_counter.get<unsigned int>(), sk_dbg_flags("KMR_SK_COUNT_DBG"), tv, p.lgMain);
+		rc = sk_count_launch<W>(h, k, grid, p.ls, p.lc, nl, out, p.f, tv, p.lgMain); if (rc) return rc;
 		HIPCHK(h, hipGetLastError());
 		if (!n_items) return 0;
 		/* the merge table holds the distinct keys of the long lists: few when a list is long because a k-mer repeats, at most the
@@ -1859,7 +1879,8 @@ template <int W> int sk_count_pass(kmr_handle *h, SkFinalize<W> &p) {
 		HIPCHK(h, hipMemsetAsync(lgItems.merge_used, 0, 8, h->stream));
 		rc = zero_work_counter(h); if (rc) return rc;
 		const int grid2 = (int)std::min<uint64_t>((uint64_t)num_cus(h) * 4, n_items);
-		hipLaunchKernelGGL(k.kern, dim3(grid2), dim3(SKC_THREADS), k.smem, h->stream, pool_view(h, h->l1), p.ls, p.lc, nl, h->k, out, p.f, h->work_counter.get<unsigned int>(), sk_dbg_flags("KMR_SK_COUNT_DBG"), tv, lgItems);
+		rc = sk_count_select<W>(h, p.ext, p.tracking, p.uni, true, out, lgItems, k); if (rc) return rc;
+		rc = sk_count_launch<W>(h, k, grid2, p.ls, p.lc, nl, out, p.f, tv, lgItems); if (rc) return rc;
 		hipLaunchKernelGGL(sk_merge_emit_kernel<W>, dim3(grid_for(1ull << merge_log2)), dim3(256), 0, h->stream, lgItems.merge, out, p.f);
 		if (hipGetLastError() != hipSuccess) return fail(h, KMR_ERR_HIP, "long-list launches");
 		if (merge_log2 < 30) repeat_on = ERR_TABLE_FULL;
@@ -1992,10 +2013,11 @@ template <int W> int count_prefix_superkmer_t(kmr_handle *h, uint32_t min_depth,
 	if (n_work) {
 		const int grid = (int)std::min<uint64_t>((uint64_t)num_cus(h) * 4, (n_work + SK_LBATCH) / SK_LBATCH);
 		SkCountLaunch<W> k;
-		rc = sk_count_select<W>(h, false, false, uni, k); if (rc) return rc;
+		rc = sk_count_select<W>(h, false, false, uni, false, out, lg, k); if (rc) return rc;
 		TimeSpan t(h, KMR_TIME_COUNT);
-		hipLaunchKernelGGL(k.kern, dim3(grid), dim3(SKC_THREADS), k.smem, h->stream, pool_view(h, h->l1), ls, lc, hi, h->k, out, f, h->work_counter.get<unsigned int>(), sk_dbg_flags("KMR_SK_COUNT_DBG"), tv, lg);
+		rc = sk_count_launch<W>(h, k, grid, ls, lc, hi, out, f, tv, lg);
 		t.end();
+		if (rc) return rc;
 		HIPCHK(h, hipGetLastError());
 	}
 	h->early.active = true; h->early.hi = hi; h->early.min_depth = min_depth;

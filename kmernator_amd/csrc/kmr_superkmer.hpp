@@ -1517,12 +1517,29 @@ template <int W> struct SkLong {
 	unsigned long long *merge_used;         /* slots of it claimed so far: beyond 5/8 of the table the launch gives up (ERR_TABLE_FULL) and the host comes back with a larger one */
 };
 
+/* The arguments of a count launch.  By value, in scalar registers for the whole kernel, only what every chunk or every kept entry needs
+ * (SkCountHot beside the CSR, k and the work counter); everything else -- the singleton outputs, capacities and counters, the error word,
+ * the bucket hash's parameters, the long lists' items and merge table, the size tracker's view -- waits in one SkCountArgs in device memory
+ * that the host writes before the launch (sk_count_args_kernel) and is read where it is used, with a scalar load on a path taken once per
+ * batch of lists or less.  By value the ~350 bytes filled most of the scalar register file: the pass spilled 145 scalar registers into
+ * lanes of vector registers and reloaded them, a vector instruction each, in every chunk's set-up and in every list's emit. */
+struct SkCountHot {
+	uint64_t *wout;                          /* out.wentries (packed entries) or out.wkeys (extension values: with wvals) */
+	uint32_t *wvals; unsigned long long *wcursor; uint64_t wcap;
+	uint32_t min_depth, has_singletons, uni_wbits, ext_min_q;      /* of FinalizeParams */
+};
+template <int W> struct SkCountArgs { CountOut out; FinalizeParams f; SkTrackView tv; SkLong<W> lg; };
+template <int W> __host__ inline SkCountHot sk_count_hot(const SkCountArgs<W> &a) {
+	return {a.out.wentries ? a.out.wentries : a.out.wkeys, a.out.wvals, a.out.wcursor, a.out.wcap, a.f.min_depth, a.f.has_singletons, a.f.uni_wbits, a.f.ext_min_q};
+}
+template <int W> __global__ void sk_count_args_kernel(SkCountArgs<W> a, SkCountArgs<W> *dst) { if (threadIdx.x == 0 && blockIdx.x == 0) *dst = a; }
+
 /* EXT (extension values): six more words per slot -- the twelve tallies as 16-bit halves, exact while a block's share of a list stays
  * below 65 536 k-mers (the host cuts longer lists into pieces, SK_EXT_LONG_CHUNKS) -- and the packet of one occurrence, read only
  * when the key ends as a singleton: 60 bytes per slot, two blocks per CU */
-/* (the one-weight pass over multi-word keys keeps no weight sums and no state words: 32 instead of 44 bytes per slot at W = 2) */
+/* (the one-weight pass keeps no weight sums, and over multi-word keys no state words: 24 instead of 32 bytes per slot at W = 1, 32 instead of 44 at W = 2) */
 template <int W, int LOG2S, bool TRACK = false, bool EXT = false, bool UNI = false>
-__host__ __device__ constexpr size_t sk_count_smem_bytes() { return (size_t)(1 << LOG2S) * (8 * W + 24 + (W > 1 ? 4 : 0) - (UNI && W > 1 ? 12 : 0) + (TRACK ? 8 : 0) + (EXT ? 28 : 0)) + (size_t)SK_STAGE_G * 16 + 256 + 64 + (TRACK ? 8 * (SK_TRACK_MAX + 1) : 0); }
+__host__ __device__ constexpr size_t sk_count_smem_bytes() { return (size_t)(1 << LOG2S) * (8 * W + 24 + (W > 1 ? 4 : 0) - (UNI ? 8 : 0) - (UNI && W > 1 ? 4 : 0) + (TRACK ? 8 : 0) + (EXT ? 28 : 0)) + (size_t)SK_STAGE_G * 16 + 256 + 64 + (TRACK ? 8 * (SK_TRACK_MAX + 1) : 0); }
 /* a chunk of extension records holds at most ~6.4 k-mers per granule (n = 128: 21 granules): 128 chunks stay below 65 536 k-mers */
 static const uint64_t SK_EXT_LONG_CHUNKS = 128;
 static const int SK_EXT_BLOCKS = 3;      /* blocks per CU of the count pass with extension values (166 registers; four -- 128 registers, 34 dwords spilled -- ran 11 % slower) */
@@ -1558,15 +1575,23 @@ static const unsigned long long SK_OSLAB = 2048;      /* entries a wavefront res
  * extraction with the same quality character, or with none): the weight sum of a slot is its count times that weight -- exact in
  * f64, count * w needs 24 + 20 bits -- so the table takes no ds_add_f64, no weight is read or converted per k-mer, and the weight
  * part of the first-sighting word is a constant of the launch (a sixth of the inner loop's vector instructions). */
-template <int W, int LOG2S, bool TRACK = false, bool EXT = false, bool UNI = false>
+template <int W, int LOG2S, bool TRACK = false, bool EXT = false, bool UNI = false, bool ITEM = false>
 __global__ __launch_bounds__(SKC_THREADS, EXT ? (W == 1 ? (LOG2S <= 9 ? SK_EXT_BLOCKS : 2) : 1) : ((W == 1 && LOG2S <= 10 && !TRACK) ? 4 : (W == 2 && LOG2S <= 10 && !TRACK ? (UNI ? 4 : 3) : 1)))
-void sk_count_kernel(PoolView pool, const uint64_t *list_start, const uint64_t *list_chunks, uint64_t n_lists, uint32_t k,
-                     CountOut out, FinalizeParams f, unsigned int *work_counter, uint32_t dbgFlags, SkTrackView tv, SkLong<W> lg) {
+void sk_count_kernel(const uint4 *poolg, const uint64_t *list_start, const uint64_t *list_chunks, uint64_t n_lists, uint32_t k,
+                     SkCountHot hot, unsigned int *work_counter, uint32_t dbgFlags, const SkCountArgs<W> *__restrict__ args) {
+	const CountOut &out = args->out; const FinalizeParams &f = args->f; const SkTrackView &tv = args->tv; const SkLong<W> &lg = args->lg;      /* (device memory: read where used) */
 	static_assert(!UNI || (!TRACK && !EXT), "the one-weight count pass is the plain one's");
 	constexpr int S = 1 << LOG2S;
-	/* LEAN: the one-weight pass over multi-word keys keeps neither weight sums (count x weight at emit) nor state words (the host sends only
-	 * k with pad bits in the last key word here: the claim protocol of SK_KEY_PENDING needs none) -- W = 2: 37 KB a block, four to a CU */
+	/* LEAN: the one-weight pass over multi-word keys keeps no state words (the host sends only k with pad bits in the last key word here: the
+	 * claim protocol of SK_KEY_PENDING needs none) and, like every one-weight pass, no weight sums (WSUM: count x weight at emit) -- W = 2:
+	 * 37 KB a block, four to a CU */
 	constexpr bool LEAN = UNI && W > 1;
+	constexpr bool WSUM = !UNI;      /* the one-weight pass keeps no weight sums at any key width: 24 instead of 32 bytes per slot at W = 1 */
+	/* What the launch side fixes per instance (sk_count_select): ITEM, the pass over work items of long lists into the merge table, and the
+	 * form of the weak entries -- packed in hot.wout without per-bucket counts (PACKED: every build without extension values, whose map
+	 * kmr_buckets.hpp buckets and counts for itself) or keys and values apart in hot.wout / hot.wvals with out.weakCount (EXT) */
+	constexpr bool PACKED = !EXT;
+	static_assert(!ITEM || !TRACK, "the size tracker's pass has no long-list items");
 #ifndef KMR_SKC_LIMIT_PCT
 #define KMR_SKC_LIMIT_PCT 80      /* share of the table a list may fill before it is redone in sub-passes (C2 count pass at 70 / 80 / 85 / 90: 9.84 / 9.54 / 9.57 / 9.55 ms: overflowing lists are not what the uneven lists cost) */
 #endif
@@ -1576,7 +1601,7 @@ void sk_count_kernel(PoolView pool, const uint64_t *list_start, const uint64_t *
 	uint64_t *tkeys = (uint64_t *)csm;                                 /* [S][W] */
 	unsigned long long *tcnt = (unsigned long long *)(tkeys + (size_t)S * W);
 	double *twsum = (double *)(tcnt + S);
-	unsigned long long *tfirst = (unsigned long long *)(twsum + (LEAN ? 0 : S));
+	unsigned long long *tfirst = (unsigned long long *)(twsum + (WSUM ? S : 0));
 	uint32_t *tstate = (uint32_t *)(tfirst + S);                       /* W > 1 only, and not LEAN */
 	uint32_t *ttally = tstate + (W > 1 && !LEAN ? S : 0);                       /* EXT only: [S][6] tallies (left A C | G T | N X, right A C | G T | N X as 16-bit halves), [S] packets */
 	uint32_t *tpkt = ttally + (EXT ? 6 * S : 0);
@@ -1587,6 +1612,7 @@ void sk_count_kernel(PoolView pool, const uint64_t *list_start, const uint64_t *
 	unsigned int *trkU = (unsigned int *)(tsecond + (TRACK ? S : 0)), *trkS = trkU + (SK_TRACK_MAX + 1);
 	__shared__ uint32_t s_list, s_sp;
 	__shared__ uint32_t s_claimed[2], s_overflow[2];
+	__shared__ unsigned long long s_sat[2];      /* keys seen SK_ORDERED_FROM times or more, and their sightings */
 	__shared__ uint32_t s_stackBits[40], s_stackVal[40];
 	__shared__ unsigned long long s_c0[SK_LBATCH + 1], s_c1[SK_LBATCH + 1];      /* chunk range of every list (work item) of the batch */
 	__shared__ uint32_t s_dchunk[SK_DESC_CAP];
@@ -1594,26 +1620,26 @@ void sk_count_kernel(PoolView pool, const uint64_t *list_start, const uint64_t *
 	const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
 	if (TRACK) for (int i = t; i < 2 * (int)(SK_TRACK_MAX + 1); i += SKC_THREADS) trkU[i] = 0;
 	const uint32_t vw = EXT ? 15 : 3;
-	unsigned long long uniq = 0, single = 0, keptW = 0, keptS = 0, satK = 0, satS = 0;
-	unsigned long long uniqW = 0, singleW = 0;      /* wave-uniform: used slots and slots with a count of one, from ballots */
+	/* wave-uniform counters (scalars, not a 64-bit vector register pair each): used slots and slots with a count of one, kept entries --
+	 * all from ballots; the saturated keys, rare, are added up in LDS as they are met (s_sat) */
+	unsigned long long uniqW = 0, singleW = 0, keptW = 0, keptS = 0;
 	/* this wavefront's output slabs: [wpos, wend) of the weak entries, [spos, send) of the singletons */
 	unsigned long long wpos = 0, wend = 0, spos = 0, send = 0;
 	bool outFull = false;
-	if (t == 0) { s_claimed[0] = s_claimed[1] = 0; s_overflow[0] = s_overflow[1] = 0; s_sp = 0; }
-	for (int i = t; i < S; i += SKC_THREADS) { tkeys[(size_t)i * W] = EMPTY_KEY; if (W > 1) tkeys[(size_t)i * W + W - 1] = SK_KEY_PENDING; tcnt[i] = 0; if constexpr (!LEAN) twsum[i] = 0.0; tfirst[i] = NO_FIRST; if constexpr (W > 1 && !LEAN) tstate[i] = 0; if (TRACK) tsecond[i] = NO_FIRST; }
+	if (t == 0) { s_claimed[0] = s_claimed[1] = 0; s_overflow[0] = s_overflow[1] = 0; s_sp = 0; s_sat[0] = s_sat[1] = 0; }
+	for (int i = t; i < S; i += SKC_THREADS) { tkeys[(size_t)i * W] = EMPTY_KEY; if (W > 1) tkeys[(size_t)i * W + W - 1] = SK_KEY_PENDING; tcnt[i] = 0; if constexpr (WSUM) twsum[i] = 0.0; tfirst[i] = NO_FIRST; if constexpr (W > 1 && !LEAN) tstate[i] = 0; if (TRACK) tsecond[i] = NO_FIRST; }
 	if (EXT) for (int i = t; i < 6 * S; i += SKC_THREADS) ttally[i] = 0;
 	lds_barrier();
 	/* classify() of kmr_kernels.hpp folded into launch-wide scalars: a count of one goes to class singC when singletons are separate,
 	 * any other count below weakMin is dropped */
-	const uint32_t singC = f.has_singletons ? (f.min_depth > 1 ? 0u : 2u) : 3u;
-	const uint32_t weakMin = ((!f.has_singletons || f.min_depth > 2) && f.min_depth != 1) ? f.min_depth : 0u;
-	const uint32_t uniFirst = UNI ? (first_weight_bits(__uint_as_float(f.uni_wbits)) & 0x7fffffu) : 0u;      /* the weight bits of every first-sighting word */
-	const uint4 *poolg = (const uint4 *)pool.base;
+	const uint32_t singC = hot.has_singletons ? (hot.min_depth > 1 ? 0u : 2u) : 3u;
+	const uint32_t weakMin = ((!hot.has_singletons || hot.min_depth > 2) && hot.min_depth != 1) ? hot.min_depth : 0u;
+	const uint32_t uniFirst = UNI ? (first_weight_bits(__uint_as_float(hot.uni_wbits)) & 0x7fffffu) : 0u;      /* the weight bits of every first-sighting word */
 	uint4 pre = make_uint4(0, 0, 0, 0); uint32_t preCount = 0; uint64_t preList = ~0ull;      /* this wavefront's first chunk of the list named */
 	uint32_t gen = 0;                                  /* lists this block has counted: the flag pair in use is gen & 1 */
 
-	const bool itemMode = lg.item_c0 != nullptr;
-	const uint32_t grab = itemMode ? 1u : SK_LBATCH;      /* work items are large: one at a time */
+	constexpr bool itemMode = ITEM;
+	constexpr uint32_t grab = itemMode ? 1u : SK_LBATCH;      /* work items are large: one at a time */
 	for (;;) {
 		if (t == 0) s_list = atomicAdd(work_counter, grab);
 		lds_barrier();
@@ -1741,8 +1767,22 @@ void sk_count_kernel(PoolView pool, const uint64_t *list_start, const uint64_t *
 								rcIn = (uint32_t)(wsel >> (62u - 2u * (k & 31u))) & 3u; }
 							else { const uint32_t b = j + k; rcIn = (((const uint32_t *)(wstage + rs + 1))[b >> 4] >> (30 - 2 * (b & 15u))) & 3u; }
 						}
-						key_clip_tail<W>(kf, k);
-						st.key = key_canonical<W>(kf, k, st.fwd);
+						if constexpr (W == 1) {
+							/* one-word keys: what key_clip_tail and key_revcomp decide from k alone -- a mask and a shift of 64 - 2 k bits -- is
+							 * scalar here, and the bits of a base are put back in order on the two 32-bit halves (the same words, without the
+							 * selects on k and with half the shift and mask instructions) */
+							const uint32_t padBits = 64u - 2u * k;
+							kf.w[0] &= ~0ull << padBits;
+							uint32_t rh = __builtin_bitreverse32((uint32_t)kf.w[0]), rl = __builtin_bitreverse32((uint32_t)(kf.w[0] >> 32));
+							rh = ((rh >> 1) & 0x55555555u) | ((rh & 0x55555555u) << 1);
+							rl = ((rl >> 1) & 0x55555555u) | ((rl & 0x55555555u) << 1);
+							const uint64_t kr = (((uint64_t)~rh << 32) | (uint32_t)~rl) << padBits;
+							st.fwd = kf.w[0] <= kr;
+							st.key.w[0] = st.fwd ? kf.w[0] : kr;
+						} else {
+							key_clip_tail<W>(kf, k);
+							st.key = key_canonical<W>(kf, k, st.fwd);
+						}
 						const uint64_t h = slot_hash<W>(st.key.w);
 						st.slot = (uint32_t)(h >> (64 - LOG2S));
 						/* a key that does not find its home slot free (or its own) goes on in steps of an odd number taken from other bits of its
@@ -1780,7 +1820,7 @@ void sk_count_kernel(PoolView pool, const uint64_t *list_start, const uint64_t *
 					auto step_one = [&](KState &cur, KState &nxt) {
 						if (left) {
 							uint32_t s = cur.slot;
-							const float wa = __uint_as_float(UNI ? f.uni_wbits : cur.w);
+							const float wa = __uint_as_float(UNI ? hot.uni_wbits : cur.w);
 							/* (one-word keys: a compare-and-swap against "empty" returns what the slot holds whether it wins or not, so the slot is
 							 * not read first) */
 							unsigned long long old = EMPTY_KEY;
@@ -1881,8 +1921,8 @@ void sk_count_kernel(PoolView pool, const uint64_t *list_start, const uint64_t *
 									} else atomicMin(&tfirst[s], fp);
 									if constexpr (EXT) {      /* ExtensionTracking::trackExtension (src/KmerTrackingData.h:195-201) */
 										const uint32_t lc = cur.x & 0xffu, rc = (cur.x >> 8) & 0xffu, lq = (cur.x >> 16) & 0xffu, rq = cur.x >> 24;
-										if (lq >= f.ext_min_q || lc > 3u) atomicAdd(&ttally[(size_t)s * 6 + (lc >> 1)], 1u << (16 * (lc & 1u)));
-										if (rq >= f.ext_min_q || rc > 3u) atomicAdd(&ttally[(size_t)s * 6 + 3 + (rc >> 1)], 1u << (16 * (rc & 1u)));
+										if (lq >= hot.ext_min_q || lc > 3u) atomicAdd(&ttally[(size_t)s * 6 + (lc >> 1)], 1u << (16 * (lc & 1u)));
+										if (rq >= hot.ext_min_q || rc > 3u) atomicAdd(&ttally[(size_t)s * 6 + 3 + (rc >> 1)], 1u << (16 * (rc & 1u)));
 										if (claimedHere != claimedBefore) tpkt[s] = sk_ext_char(lc) | (sk_ext_char(rc) << 8) | (cur.x & 0xffff0000u);      /* the packet of the sighting that claimed the slot: read only when it stays the only one */
 									}
 								}
@@ -1937,7 +1977,7 @@ void sk_count_kernel(PoolView pool, const uint64_t *list_start, const uint64_t *
 #pragma unroll
 					for (int q = 0; q < W; q++) key.w[q] = used ? tkeys[(size_t)s * W + q] : 0ull;
 					const unsigned long long fst = used ? tfirst[s] : NO_FIRST;
-					const double wsum = UNI ? (double)count * (double)__uint_as_float(f.uni_wbits) : (used ? twsum[s] : 0.0);
+					const double wsum = UNI ? (double)count * (double)__uint_as_float(hot.uni_wbits) : (used ? twsum[s] : 0.0);
 					if (TRACK && used) {
 						/* the key counts as seen from the first boundary behind its first sighting on, and as a singleton until the
 						 * first boundary behind its second one: index = number of boundaries <= the ordinal */
@@ -1982,31 +2022,31 @@ void sk_count_kernel(PoolView pool, const uint64_t *list_start, const uint64_t *
 					if (mw) {
 						const uint32_t cnt = (uint32_t)__builtin_popcountll(mw);
 						if (wpos + cnt > wend) {           /* the slab is full: its tail becomes a hole, a new one is taken */
-							for (unsigned long long e = wpos + lane; e < wend && e < out.wcap; e += 64) { if (out.wentries) out.wentries[e * (W + 1) + W] = 0; else out.wvals[e * vw] = 0; }
+							for (unsigned long long e = wpos + lane; e < wend && e < hot.wcap; e += 64) { if (PACKED) hot.wout[e * (W + 1) + W] = 0; else hot.wvals[e * vw] = 0; }
 							unsigned long long g = 0;
-							if (lane == 0) g = atomicAdd(out.wcursor, SK_OSLAB);
+							if (lane == 0) g = atomicAdd(hot.wcursor, SK_OSLAB);
 							wpos = ((unsigned long long)(uint32_t)__shfl((int)(g >> 32), 0, 64) << 32) | (uint32_t)__shfl((int)(uint32_t)g, 0, 64);
 							wend = wpos + SK_OSLAB;
-							if (wend > out.wcap) { if (lane == 0) atomicOr(out.err, (uint32_t)ERR_ENTRIES_FULL); outFull = true; wend = wpos; }
+							if (wend > hot.wcap) { if (lane == 0) atomicOr(out.err, (uint32_t)ERR_ENTRIES_FULL); outFull = true; wend = wpos; }
 						}
 						if (!outFull) {
 							if (cls == 1) {
 								const uint64_t pos = wpos + (uint32_t)__builtin_popcountll(mw & below);
 								uint32_t fwdc = (uint32_t)(cf >> 32), cnt16 = count;
-								if (f.has_singletons && first_forward(fst)) fwdc -= 1;
-								if (cnt16 >= SK_ORDERED_FROM) { satK++; satS += count; if (cnt16 > 65535u) { cnt16 = 65535u; if (fwdc > 65534u) fwdc = 65534u; } }      /* (weight and direction of such a key are redone from its first 65 535 sightings in input order, sat_*_kernel) */
+								if (hot.has_singletons && first_forward(fst)) fwdc -= 1;
+								if (cnt16 >= SK_ORDERED_FROM) { atomicAdd(&s_sat[0], 1ull); atomicAdd(&s_sat[1], (unsigned long long)count); if (cnt16 > 65535u) { cnt16 = 65535u; if (fwdc > 65534u) fwdc = 65534u; } }      /* (weight and direction of such a key are redone from its first 65 535 sightings in input order, sat_*_kernel) */
 								if (fwdc > 65535u) fwdc = 65535u;
-								const uint32_t wbits = __float_as_uint((float)(f.has_singletons ? wsum + first_weight_shift(fst) : wsum));
-								if (out.wentries) {
+								const uint32_t wbits = __float_as_uint((float)(hot.has_singletons ? wsum + first_weight_shift(fst) : wsum));
+								if constexpr (PACKED) {
 									uint64_t ew[W + 1];
 #pragma unroll
 									for (int q = 0; q < W; q++) ew[q] = key.w[q];
 									ew[W] = bb_pack_value(cnt16, wbits, fwdc);
-									bb_store_entry<W>(out.wentries, pos, ew);
+									bb_store_entry<W>(hot.wout, pos, ew);
 								} else {
 #pragma unroll
-									for (int q = 0; q < W; q++) out.wkeys[pos * W + q] = key.w[q];
-									uint32_t *v = out.wvals + pos * vw;
+									for (int q = 0; q < W; q++) hot.wout[pos * W + q] = key.w[q];
+									uint32_t *v = hot.wvals + pos * vw;
 									v[0] = cnt16; v[1] = wbits; v[2] = fwdc;
 									if constexpr (EXT) {
 #pragma unroll
@@ -2014,10 +2054,10 @@ void sk_count_kernel(PoolView pool, const uint64_t *list_start, const uint64_t *
 									}
 								}
 							}
-							wpos += cnt; keptW += lane == 0 ? cnt : 0u;
+							wpos += cnt; keptW += cnt;
 						}
 					}
-					if (out.weakCount) {      /* (null in build_mode 3's own finalize: the map is bucketed by kmr_buckets.hpp, which counts for itself) */
+					if constexpr (!PACKED) {      /* (packed entries: the map is bucketed by kmr_buckets.hpp, which counts for itself) */
 						const uint64_t bucket = cls == 1 ? key_hash<W>(key, f.kb) & (f.nb_weak - 1) : 0;
 						bucket_count_add(out.weakCount, bucket, cls == 1 && !outFull);
 					}
@@ -2042,7 +2082,7 @@ void sk_count_kernel(PoolView pool, const uint64_t *list_start, const uint64_t *
 							if constexpr (EXT) out.spkt[pos] = tpkt[s];
 						}
 						bucket_count_add(out.singCount, bucket, cls == 2 && !outFull);
-						if (!outFull) { spos += cnt; keptS += lane == 0 ? cnt : 0u; }
+						if (!outFull) { spos += cnt; keptS += cnt; }
 					}
 				}
 				sk_wave_lds_order();
@@ -2050,7 +2090,7 @@ void sk_count_kernel(PoolView pool, const uint64_t *list_start, const uint64_t *
 				for (int i = 0; i < WSLOTS / 64; i++) {
 					const int s = wv * WSLOTS + i * 64 + lane;
 					if ((usedMask[i] >> lane) & 1ull) {
-						tkeys[(size_t)s * W] = EMPTY_KEY; if (W > 1) tkeys[(size_t)s * W + W - 1] = SK_KEY_PENDING; tcnt[s] = 0; if constexpr (!LEAN) twsum[s] = 0.0; tfirst[s] = NO_FIRST; if constexpr (W > 1 && !LEAN) tstate[s] = 0; if (TRACK) tsecond[s] = NO_FIRST;
+						tkeys[(size_t)s * W] = EMPTY_KEY; if (W > 1) tkeys[(size_t)s * W + W - 1] = SK_KEY_PENDING; tcnt[s] = 0; if constexpr (WSUM) twsum[s] = 0.0; tfirst[s] = NO_FIRST; if constexpr (W > 1 && !LEAN) tstate[s] = 0; if (TRACK) tsecond[s] = NO_FIRST;
 						if constexpr (EXT) {
 #pragma unroll
 							for (int q = 0; q < 6; q++) ttally[(size_t)s * 6 + q] = 0;
@@ -2059,7 +2099,7 @@ void sk_count_kernel(PoolView pool, const uint64_t *list_start, const uint64_t *
 				}
 			};
 			auto clear_table = [&]() {
-				for (int i = t; i < S; i += SKC_THREADS) { tkeys[(size_t)i * W] = EMPTY_KEY; if (W > 1) tkeys[(size_t)i * W + W - 1] = SK_KEY_PENDING; tcnt[i] = 0; if constexpr (!LEAN) twsum[i] = 0.0; tfirst[i] = NO_FIRST; if constexpr (W > 1 && !LEAN) tstate[i] = 0; if (TRACK) tsecond[i] = NO_FIRST; }
+				for (int i = t; i < S; i += SKC_THREADS) { tkeys[(size_t)i * W] = EMPTY_KEY; if (W > 1) tkeys[(size_t)i * W + W - 1] = SK_KEY_PENDING; tcnt[i] = 0; if constexpr (WSUM) twsum[i] = 0.0; tfirst[i] = NO_FIRST; if constexpr (W > 1 && !LEAN) tstate[i] = 0; if (TRACK) tsecond[i] = NO_FIRST; }
 				if (EXT) for (int i = t; i < 6 * S; i += SKC_THREADS) ttally[i] = 0;
 			};
 
@@ -2105,14 +2145,13 @@ void sk_count_kernel(PoolView pool, const uint64_t *list_start, const uint64_t *
 		}
 	}
 	/* the unused tails of this wavefront's slabs are holes */
-	for (unsigned long long e = wpos + lane; e < wend && e < out.wcap; e += 64) { if (out.wentries) out.wentries[e * (W + 1) + W] = 0; else out.wvals[e * vw] = 0; }
+	for (unsigned long long e = wpos + lane; e < wend && e < hot.wcap; e += 64) { if (PACKED) hot.wout[e * (W + 1) + W] = 0; else hot.wvals[e * vw] = 0; }
 	for (unsigned long long e = spos + lane; e < send && e < out.scap; e += 64) out.sweight[e] = 0;
-	uniq = wave_sum(uniq) + uniqW; single = wave_sum(single) + singleW; satK = wave_sum(satK); satS = wave_sum(satS);
 	if (lane == 0) {
-		if (uniq) atomicAdd(&out.fc->unique, uniq); if (single) atomicAdd(&out.fc->singletons, single);
+		if (uniqW) atomicAdd(&out.fc->unique, uniqW); if (singleW) atomicAdd(&out.fc->singletons, singleW);
 		if (keptW) atomicAdd(&out.fc->weak_kept, keptW); if (keptS) atomicAdd(&out.fc->sing_kept, keptS);
-		if (satK) { atomicAdd(&out.fc->saturated, satK); atomicAdd(&out.fc->sat_sightings, satS); }
 	}
+	if (t == 0 && s_sat[0]) { atomicAdd(&out.fc->saturated, s_sat[0]); atomicAdd(&out.fc->sat_sightings, s_sat[1]); }      /* (final: every emit lies before the barrier behind the last look at the work counter) */
 	if (TRACK) {
 		lds_barrier();
 		for (uint32_t i = (uint32_t)t; i <= tv.n && i <= SK_TRACK_MAX; i += SKC_THREADS) { if (trkU[i]) atomicAdd(&tv.d_unique[i], trkU[i]); if (trkS[i]) atomicAdd(&tv.d_single[i], trkS[i]); }
