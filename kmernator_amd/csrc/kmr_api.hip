@@ -10,7 +10,8 @@
  * Shared decisions have one place each: key width / value kind / minimizer window as template arguments (with_w, with_w_ext,
  * with_win), kernel-argument structs (reads_view, finalize_params, count_out, sk_own_lists), the plan of the count pass over
  * super-k-mer lists (sk_count_uniform, sk_count_select), the entry buffers' policy and the attempt loop of a count pass (count_entry_buffers,
- * count_attempts), the end of a finalize (publish_maps), the host-to-device piece pipeline (tb_feed_pieces).  The heavy kernel
+ * count_attempts), the end of a finalize (publish_maps), the host-to-device piece pipeline (tb_feed_pieces), what a feed call hands down
+ * (FeedHints) and its one way into the build (add_reads_dev_call, the sk_* parts of add_reads_superkmer_t).  The heavy kernel
  * templates are compiled elsewhere (kmr_instances.hpp, kmr_inst.hip); the headers' plain kernels here.
  */
 #include <hip/hip_runtime.h>
@@ -115,7 +116,7 @@ DevParams dev_params(kmr_handle *h) {
 	p.k = h->k; p.kb = h->hkb; p.min_weight = h->cfg.min_weight; p.fastq_start = h->cfg.fastq_start_char; p.ext_min_q = h->cfg.ext_min_quality;
 	p.qzero = h->cfg.fastq_start_char + std::max<uint32_t>(1u, h->cfg.min_quality_score);   /* Q0 has probability 0 too */
 	p.subsample = h->cfg.kmer_subsample; p.rank = h->cfg.rank; p.world = h->cfg.world_size; p.num_parts = h->cfg.num_parts; p.part_idx = h->cfg.part_idx;
-	p.count_sender_bad = h->sender_launch ? 1u : 0u;
+	p.count_sender_bad = 0u;      /* (extract_by_owner_t's build-mode launch sets it) */
 	p.P = h->dP.get<double>(); p.stats = h->dstats.get<DevStats>(); p.err = h->derr.get<uint32_t>();
 	p.sub_wstart = p.sub_wkeys = p.sub_sstart = p.sub_skeys = nullptr; p.sub_wvals = nullptr; p.sub_sweight = nullptr; p.sub_wnb = p.sub_snb = 0; p.sub_vw = 0;
 	if (h->subtract) {
@@ -234,8 +235,7 @@ int prepare_units(kmr_handle *h, ReadsView &rv, uint32_t span = (uint32_t)TILE_S
 	return 0;
 }
 
-template <int W, bool EXT, class Op> int launch_extract(kmr_handle *h, const ReadsView &rv, const Op &op, uint64_t max_blocks = 0) {
-	const DevParams dp = dev_params(h);
+template <int W, bool EXT, class Op> int launch_extract(kmr_handle *h, const ReadsView &rv, const DevParams &dp, const Op &op, uint64_t max_blocks = 0) {
 	const bool sub = Op::NEEDS_WEIGHT && (dp.sub_wnb | dp.sub_snb) != 0;      /* lookups ignore the subtracting reference */
 	auto kern = sub ? extract_kernel<W, EXT, Op, true> : extract_kernel<W, EXT, Op, false>;
 	HIPCHK(h, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)EXTRACT_SMEM));
@@ -270,7 +270,7 @@ template <int W, bool EXT> int add_reads_dev_t(kmr_handle *h, const ReadsView &r
 		rc = prepare_units(h, rv); if (rc) return rc;
 		InsertOp<W, EXT> op; op.table = table_of<W>(h);
 		TimeSpan t(h, 0);
-		rc = launch_extract<W, EXT>(h, rv, op);
+		rc = launch_extract<W, EXT>(h, rv, dev_params(h), op);
 		t.end();
 		if (rc) return rc;
 	}
@@ -540,12 +540,12 @@ template <int W> int lookup_reads_t(kmr_handle *h, const ReadsView &rv, uint32_t
 	LookupOp<W> op; const uint32_t vw = h->ext ? 15 : 3; op.weak_only = weak_only;
 	op.lut = weak_only ? lut_of<W>(h) : LutView<W>{nullptr, 0, 0};
 	op.weak = view_of<W>(h->weak, vw); op.sing = view_of<W>(h->sing, vw); op.out = dout; op.out_offsets = dout_off; op.first_read_idx = rv.first_read_idx;
-	return launch_extract<W, false>(h, rv, op);
+	return launch_extract<W, false>(h, rv, dev_params(h), op);
 }
 template <int W> int lookup_reads_weighted_t(kmr_handle *h, const ReadsView &rv, double *dout, const uint64_t *dout_off) {
 	LookupWeightOp<W> op; const uint32_t vw = h->ext ? 15 : 3;
 	op.weak = view_of<W>(h->weak, vw); op.sing = view_of<W>(h->sing, vw); op.out = dout; op.out_offsets = dout_off; op.first_read_idx = rv.first_read_idx;
-	return launch_extract<W, false>(h, rv, op);
+	return launch_extract<W, false>(h, rv, dev_params(h), op);
 }
 
 /* stage host read arrays on the device (padded so 16-byte tile loads stay inside the allocation) */
@@ -723,42 +723,43 @@ void choose_bits1(kmr_handle *h, uint64_t records_hint) {
 	h->bits1 = std::max(0, std::min(mb, T + 2 - mb));
 }
 
+/* k-mer capacity of every work unit of rv (cut here: prepare_units) -> region of each 64-unit tile in the linear buffer of rec_size-byte
+ * records: h->koff, h->linear and h->tile_count are ready for a LinearOp launch, which may write total_cap records in `tiles` tiles */
+int linear_regions(kmr_handle *h, ReadsView &rv, size_t rec_size, uint64_t &tiles, uint64_t &total_cap) {
+	int rc = prepare_units(h, rv); if (rc) return rc;
+	const uint64_t nu = rv.u_start ? rv.n_units : rv.n_reads;
+	rc = h->kcap.reserve(h, "kcap", 4 * std::max<uint64_t>(nu + 1, 16)); if (rc) return rc;
+	rc = h->koff.reserve(h, "koff", 8 * std::max<uint64_t>(nu + 1, 16)); if (rc) return rc;
+	hipLaunchKernelGGL(kmer_capacity_kernel, dim3(grid_for(nu)), dim3(256), 0, h->stream, rv, h->k, h->kcap.get<uint32_t>());
+	HIPCHK(h, hipGetLastError());
+	rc = exclusive_scan(h, h->kcap.get<uint32_t>(), nu, h->koff.get<uint64_t>()); if (rc) return rc;
+	HIPCHK(h, hipMemcpy(&total_cap, h->koff.get<uint64_t>() + nu, 8, hipMemcpyDeviceToHost));
+	tiles = (nu + 63) / 64;
+	rc = h->linear.reserve(h, "linear", rec_size * std::max<uint64_t>(total_cap, 16)); if (rc) return rc;
+	return h->tile_count.reserve(h, "tile_count", 4 * std::max<uint64_t>(tiles, 16));
+}
 /* sender side of the exchange: reads -> linear records (every owner's) -> owner segments */
 template <int W, bool EXT> int extract_by_owner_t(kmr_handle *h, const ReadsView &rvAll, uint64_t total_bases, void *dev_records, uint64_t seg_capacity, void *dev_seg_counts, uint32_t *dev_pos = nullptr) {
 	const uint64_t n = rvAll.n_reads;
 	const uint64_t avg = n ? std::max<uint64_t>(1, total_bases / n) : 1;
 	const uint64_t chunk = std::max<uint64_t>(64, (SUB_BATCH_BASES / avg) & ~63ull);
+	DevParams dp = dev_params(h);
+	dp.count_sender_bad = dev_pos == nullptr ? 1u : 0u;      /* build (not request) mode: the kernel counts what it does not send */
 	for (uint64_t r = 0; r < n; r += chunk) {
 		const uint64_t m = std::min(chunk, n - r);
 		ReadsView rv = reads_slice(rvAll, r, m);
-		int rc = prepare_units(h, rv); if (rc) return rc;
-		const uint64_t nu = rv.u_start ? rv.n_units : m;
-		rc = h->kcap.reserve(h, "kcap", 4 * std::max<uint64_t>(nu + 1, 16)); if (rc) return rc;
-		rc = h->koff.reserve(h, "koff", 8 * std::max<uint64_t>(nu + 1, 16)); if (rc) return rc;
-		hipLaunchKernelGGL(kmer_capacity_kernel, dim3(grid_for(nu)), dim3(256), 0, h->stream, rv, h->k, h->kcap.get<uint32_t>());
-		HIPCHK(h, hipGetLastError());
-		rc = exclusive_scan(h, h->kcap.get<uint32_t>(), nu, h->koff.get<uint64_t>()); if (rc) return rc;
-		uint64_t total_cap = 0;
-		HIPCHK(h, hipMemcpy(&total_cap, h->koff.get<uint64_t>() + nu, 8, hipMemcpyDeviceToHost));
-		const uint64_t tiles = (nu + 63) / 64;
-		rc = h->linear.reserve(h, "linear", sizeof(typename PoolRec<W, EXT>::type) * std::max<uint64_t>(total_cap, 16)); if (rc) return rc;      /* (rec_bytes() is the granule size on a super-k-mer handle) */
-		rc = h->tile_count.reserve(h, "tile_count", 4 * std::max<uint64_t>(tiles, 16)); if (rc) return rc;
+		uint64_t tiles = 0, total_cap = 0;
+		int rc = linear_regions(h, rv, sizeof(typename PoolRec<W, EXT>::type), tiles, total_cap); if (rc) return rc;      /* (rec_bytes() is the granule size on a super-k-mer handle) */
 		LinearOp<W, EXT, false> op; op.records = (typename PoolRec<W, EXT>::type *)h->linear.get(); op.koff = h->koff.get<uint64_t>(); op.tile_count = h->tile_count.get<uint32_t>(); op.first_read_idx = rv.first_read_idx;
-		h->sender_launch = dev_pos == nullptr;
-		rc = launch_extract<W, EXT>(h, rv, op);
-		h->sender_launch = false;
-		if (rc) return rc;
+		rc = launch_extract<W, EXT>(h, rv, dp, op); if (rc) return rc;
 		rc = zero_work_counter(h); if (rc) return rc;
 		const int grid = (int)std::min<uint64_t>((uint64_t)num_cus(h) * 8, tiles);
 		/* who owns a k-mer: getDistributedThreadId, or -- a spectrum that was built through the list exchange -- the list of its minimizer */
 		OwnerFn of; of.m = 0; of.off = of.win = of.list_bits = 0;
 		if (h->superkmer_mode && h->sk_exchange) { of.m = h->sk_m; of.off = h->sk_off; of.win = h->sk_win; of.list_bits = h->sk_bits; }
-		if (dev_pos)
-			hipLaunchKernelGGL((owner_scatter_kernel<W, EXT, true>), dim3(grid), dim3(OWNER_THREADS), 0, h->stream, (const typename PoolRec<W, EXT>::type *)h->linear.get(), h->koff.get<uint64_t>(), h->tile_count.get<uint32_t>(), tiles, h->hkb,
-			                   h->cfg.world_size, (uint32_t *)dev_records, seg_capacity, (unsigned long long *)dev_seg_counts, h->work_counter.get<unsigned int>(), h->derr.get<uint32_t>(), dev_pos, of);
-		else
-			hipLaunchKernelGGL((owner_scatter_kernel<W, EXT>), dim3(grid), dim3(OWNER_THREADS), 0, h->stream, (const typename PoolRec<W, EXT>::type *)h->linear.get(), h->koff.get<uint64_t>(), h->tile_count.get<uint32_t>(), tiles, h->hkb,
-			                   h->cfg.world_size, (uint32_t *)dev_records, seg_capacity, (unsigned long long *)dev_seg_counts, h->work_counter.get<unsigned int>(), h->derr.get<uint32_t>(), (uint32_t *)nullptr, of);
+		auto scatter = dev_pos ? owner_scatter_kernel<W, EXT, true> : owner_scatter_kernel<W, EXT>;      /* (request mode writes positions too) */
+		hipLaunchKernelGGL(scatter, dim3(grid), dim3(OWNER_THREADS), 0, h->stream, (const typename PoolRec<W, EXT>::type *)h->linear.get(), h->koff.get<uint64_t>(), h->tile_count.get<uint32_t>(), tiles, h->hkb,
+		                   h->cfg.world_size, (uint32_t *)dev_records, seg_capacity, (unsigned long long *)dev_seg_counts, h->work_counter.get<unsigned int>(), h->derr.get<uint32_t>(), dev_pos, of);
 		HIPCHK(h, hipGetLastError());
 	}
 	return 0;
@@ -773,22 +774,11 @@ template <int W, bool EXT> int add_reads_partition_t(kmr_handle *h, const ReadsV
 	for (uint64_t r = 0; r < n; r += chunk) {
 		const uint64_t m = std::min(chunk, n - r);
 		ReadsView rv = reads_slice(rvAll, r, m);
-		/* k-mer capacity of every work unit -> region of each 64-unit tile in the linear buffer */
-		int rc = prepare_units(h, rv); if (rc) return rc;
-		const uint64_t nu = rv.u_start ? rv.n_units : m;
-		rc = h->kcap.reserve(h, "kcap", 4 * std::max<uint64_t>(nu + 1, 16)); if (rc) return rc;
-		rc = h->koff.reserve(h, "koff", 8 * std::max<uint64_t>(nu + 1, 16)); if (rc) return rc;
-		hipLaunchKernelGGL(kmer_capacity_kernel, dim3(grid_for(nu)), dim3(256), 0, h->stream, rv, h->k, h->kcap.get<uint32_t>());
-		HIPCHK(h, hipGetLastError());
-		rc = exclusive_scan(h, h->kcap.get<uint32_t>(), nu, h->koff.get<uint64_t>()); if (rc) return rc;
-		uint64_t total_cap = 0;
-		HIPCHK(h, hipMemcpy(&total_cap, h->koff.get<uint64_t>() + nu, 8, hipMemcpyDeviceToHost));
-		const uint64_t tiles = (nu + 63) / 64;
-		rc = h->linear.reserve(h, "linear", rec_bytes(h) * std::max<uint64_t>(total_cap, 16)); if (rc) return rc;
-		rc = h->tile_count.reserve(h, "tile_count", 4 * std::max<uint64_t>(tiles, 16)); if (rc) return rc;
+		uint64_t tiles = 0, total_cap = 0;
+		int rc = linear_regions(h, rv, rec_bytes(h), tiles, total_cap); if (rc) return rc;
 		LinearOp<W, EXT> op; op.records = (typename PoolRec<W, EXT>::type *)h->linear.get(); op.koff = h->koff.get<uint64_t>(); op.tile_count = h->tile_count.get<uint32_t>(); op.first_read_idx = rv.first_read_idx;
 		TimeSpan tb(h, KMR_TIME_BUILD), te(h, KMR_TIME_EXTRACT);
-		rc = launch_extract<W, EXT>(h, rv, op);
+		rc = launch_extract<W, EXT>(h, rv, dev_params(h), op);
 		te.end();
 #ifdef KMR_DEBUG_HOOKS
 		if (!rc && getenv("KMR_DEBUG_SAME_TILE")) {
@@ -846,7 +836,7 @@ int build_csr(kmr_handle *h, HostPool &p, uint64_t nl, uint32_t first, uint64_t 
 	return 0;
 }
 
-int finish_maps_from_entries(kmr_handle *h, uint32_t *wc, uint32_t *sc, uint64_t wslots, uint64_t sslots, uint64_t wn, uint64_t sn, bool keepSing, bool weak_uncounted = false, bool fixed_bins = false);
+int finish_maps_from_entries(kmr_handle *h, uint32_t *wc, uint32_t *sc, uint64_t wslots, uint64_t sslots, uint64_t wn, uint64_t sn, bool keepSing, uint32_t *&overflow, bool weak_uncounted = false, bool fixed_bins = false);
 CountOut count_out(kmr_handle *h, bool packed, unsigned long long *cursors, uint32_t *wc, uint32_t *sc, FinalizeCounters *fc);
 
 /* one launch of the count pass over k-mer records: the kernel for (W, EXT, table size, NARROW) with the dynamic LDS it wants;
@@ -1113,7 +1103,7 @@ template <int W, bool EXT> int finalize_partition_t(kmr_handle *h, uint32_t min_
 	rc = partition_count_pass<W, EXT>(h, p, G, ls, lc, nl, count_log2s); if (rc) return rc;
 	h->stats.unique_kmers = p.c.unique;
 	h->stats.singleton_kmers = p.f.has_singletons ? p.c.singletons : 0;
-	{ TimeSpan t(h, KMR_TIME_BUCKETS); rc = finish_maps_from_entries(h, p.wc, p.sc, p.cur[0], p.cur[1], p.c.weak_kept, p.c.sing_kept, p.keepSing); }
+	{ TimeSpan t(h, KMR_TIME_BUCKETS); uint32_t *none = nullptr; rc = finish_maps_from_entries(h, p.wc, p.sc, p.cur[0], p.cur[1], p.c.weak_kept, p.c.sing_kept, p.keepSing, none); }      /* (measured bins: nothing is left on the stream) */
 	if (rc) return rc;
 	whole.end();
 	return publish_maps(h, p.keepSing);
@@ -1129,10 +1119,11 @@ uint64_t bb_fixed_limit(uint64_t n, uint64_t bins, double scale) {
 
 /* The weak map out of the count pass's packed entries (h->ue) by the radix partition of kmr_buckets.hpp (COUNT_DIR values).
  * done = false and nothing changed when the geometry does not fit: the caller takes the scatter + per-bucket sort.
- * fixed_bins: bins of one capacity -- everything is left on the stream, h->bb_overflow is the word the caller reads once the
- * stream is drained (set: the map is void, h->ue overwritten); else, or where the buffers do not fit them, measured bins. */
-template <int W> int binned_buckets_t(kmr_handle *h, uint64_t wslots, uint64_t wn, bool fixed_bins, bool &done) {
-	done = false; h->bb_overflow = nullptr;
+ * fixed_bins: bins of one capacity -- everything is left on the stream, `overflow` is the device word the caller reads once the
+ * stream is drained (set: the map is void, h->ue overwritten); else, or where the buffers do not fit them, measured bins and
+ * overflow = null: nothing is left on the stream. */
+template <int W> int binned_buckets_t(kmr_handle *h, uint64_t wslots, uint64_t wn, bool fixed_bins, bool &done, uint32_t *&overflow) {
+	done = false; overflow = nullptr;
 	DevMap &wm = h->weak;
 	const uint64_t nb = wm.nb;
 	uint32_t B = 0; while ((1ull << (B + 1)) <= nb) B++;
@@ -1169,17 +1160,17 @@ template <int W> int binned_buckets_t(kmr_handle *h, uint64_t wslots, uint64_t w
 	const uint64_t lim2 = std::min<uint64_t>(bb_fixed_limit(wn, groups, h->tune.bb_slack_groups), bb_group_cap<W>()), stride2 = std::max<uint64_t>(lim2, 1);
 	const uint64_t lim1 = bits2 ? bb_fixed_limit(wn, bins1, h->tune.bb_slack_bins) : 0, stride1 = std::max<uint64_t>((lim1 + BB_TILE - 1) / BB_TILE, 1) * BB_TILE;
 	if (fixed_bins && lim1 < (1ull << 32) && (!bits2 || groups * stride2 <= packed_entries(h, h->ue))) {
-		uint32_t *fill = nullptr, *overflow = nullptr;      /* fill: [bins1] of the first level, then [groups] of the second when there are two */
+		uint32_t *fill = nullptr, *ovf = nullptr;      /* fill: [bins1] of the first level, then [groups] of the second when there are two */
 		rc = scratch(bits2 ? bins1 * stride1 : groups * stride2); if (rc) return rc;
 		rc = map_arrays(); if (rc) return rc;
 		rc = arena_get(h, &fill, bits2 ? bins1 + groups : groups); if (rc) return rc;
 		rc = arena_get(h, &gstart, groups + 1); if (rc) return rc;
-		rc = arena_get(h, &overflow, 1); if (rc) return rc;
-		HIPCHK(h, hipMemsetAsync(fill, 0, 4 * (bits2 ? bins1 + groups : groups), h->stream)); HIPCHK(h, hipMemsetAsync(overflow, 0, 4, h->stream));
+		rc = arena_get(h, &ovf, 1); if (rc) return rc;
+		HIPCHK(h, hipMemsetAsync(fill, 0, 4 * (bits2 ? bins1 + groups : groups), h->stream)); HIPCHK(h, hipMemsetAsync(ovf, 0, 4, h->stream));
 		auto scatter = [&](const BbInput &in, uint32_t shift, uint32_t bits, uint32_t *f, uint64_t limit, uint64_t stride, uint64_t *out) {
 			const unsigned grid = scatter_grid(in.n_slots);
-			if (W == 1 && !h->tune.bb_reload) hipLaunchKernelGGL((bb_scatter_fixed_kernel<W, W == 1>), dim3(grid), dim3(BB_THREADS), 0, h->stream, in, shift, bits, h->hkb, nb, f, (uint32_t)limit, stride, out, overflow);
-			else hipLaunchKernelGGL((bb_scatter_fixed_kernel<W, false>), dim3(grid), dim3(BB_THREADS), 0, h->stream, in, shift, bits, h->hkb, nb, f, (uint32_t)limit, stride, out, overflow);
+			if (W == 1 && !h->tune.bb_reload) hipLaunchKernelGGL((bb_scatter_fixed_kernel<W, W == 1>), dim3(grid), dim3(BB_THREADS), 0, h->stream, in, shift, bits, h->hkb, nb, f, (uint32_t)limit, stride, out, ovf);
+			else hipLaunchKernelGGL((bb_scatter_fixed_kernel<W, false>), dim3(grid), dim3(BB_THREADS), 0, h->stream, in, shift, bits, h->hkb, nb, f, (uint32_t)limit, stride, out, ovf);
 		};
 		uint32_t *gfill = fill;
 		if (!bits2) scatter(in1, shift1, bits1, fill, lim2, stride2, h->ue2.get<uint64_t>());
@@ -1192,8 +1183,8 @@ template <int W> int binned_buckets_t(kmr_handle *h, uint64_t wslots, uint64_t w
 		HIPCHK(h, hipGetLastError());
 		/* the map is dense: a group's entries go where the groups before it end */
 		rc = exclusive_scan_queue(h, gfill, groups, gstart); if (rc) return rc;
-		rc = group_launch(bits2 ? h->ue.get<uint64_t>() : h->ue2.get<uint64_t>(), gstart, gfill, stride2, overflow); if (rc) return rc;
-		h->bb_overflow = overflow; h->last_bb_path = 2;
+		rc = group_launch(bits2 ? h->ue.get<uint64_t>() : h->ue2.get<uint64_t>(), gstart, gfill, stride2, ovf); if (rc) return rc;
+		overflow = ovf; h->last_bb_path = 2;
 		done = true;
 		return 0;
 	}
@@ -1250,8 +1241,9 @@ template <int W> int binned_buckets_t(kmr_handle *h, uint64_t wslots, uint64_t w
 }
 
 /* weak_uncounted: the count pass kept no per-bucket counts of the weak entries (wc is scratch): the radix partition of
- * kmr_buckets.hpp needs none, and if it declines they are counted here */
-template <int W> int finish_maps_t(kmr_handle *h, uint32_t *wc, uint32_t *sc, uint64_t wslots, uint64_t sslots, uint64_t wn, uint64_t sn, bool keepSing, bool weak_uncounted, bool fixed_bins) {
+ * kmr_buckets.hpp needs none, and if it declines they are counted here.  overflow: null when the maps are complete and the stream
+ * drained; else (bins of one capacity, binned_buckets_t) everything is on the stream and the caller waits once, for this word */
+template <int W> int finish_maps_t(kmr_handle *h, uint32_t *wc, uint32_t *sc, uint64_t wslots, uint64_t sslots, uint64_t wn, uint64_t sn, bool keepSing, uint32_t *&overflow, bool weak_uncounted, bool fixed_bins) {
 	const uint32_t vw = h->ext ? 15 : 3;
 	DevMap &wm = h->weak, &sm = h->sing;
 	clear_map(wm); clear_map(sm);          /* the buffers of the previous build are reused when they are large enough */
@@ -1260,9 +1252,9 @@ template <int W> int finish_maps_t(kmr_handle *h, uint32_t *wc, uint32_t *sc, ui
 	int rc = wm.start.reserve(h, "weak map start", 8 * (wm.nb + 1)); if (rc) return rc;
 	rc = sm.start.reserve(h, "singleton map start", 8 * (sm.nb + 1)); if (rc) return rc;
 	bool weakDone = false;
-	h->last_bb_path = 0; h->bb_overflow = nullptr;
+	h->last_bb_path = 0; overflow = nullptr;
 	if (weak_uncounted) {
-		rc = binned_buckets_t<W>(h, wslots, wn, fixed_bins, weakDone); if (rc) return rc;
+		rc = binned_buckets_t<W>(h, wslots, wn, fixed_bins, weakDone, overflow); if (rc) return rc;
 		if (!weakDone) {      /* the other path wants keys and values apart and a count per bucket */
 			rc = ensure_weak_apart(h, std::max<uint64_t>(wslots, 16), vw); if (rc) return rc;
 			HIPCHK(h, hipMemsetAsync(wc, 0, 4 * wm.nb, h->stream));
@@ -1271,7 +1263,7 @@ template <int W> int finish_maps_t(kmr_handle *h, uint32_t *wc, uint32_t *sc, ui
 		}
 	}
 	if (!weakDone) { rc = exclusive_scan(h, wc, wm.nb, wm.start.get<uint64_t>()); if (rc) return rc; }
-	if (keepSing) { rc = h->bb_overflow ? exclusive_scan_queue(h, sc, sm.nb, sm.start.get<uint64_t>()) : exclusive_scan(h, sc, sm.nb, sm.start.get<uint64_t>()); if (rc) return rc; }      /* (bins of one capacity: nothing waits here either) */
+	if (keepSing) { rc = overflow ? exclusive_scan_queue(h, sc, sm.nb, sm.start.get<uint64_t>()) : exclusive_scan(h, sc, sm.nb, sm.start.get<uint64_t>()); if (rc) return rc; }      /* (bins of one capacity: nothing waits here either) */
 	else HIPCHK(h, hipMemsetAsync(sm.start.get<uint64_t>(), 0, 8 * (sm.nb + 1), h->stream));      /* no singleton map is kept: every bucket starts (and ends) at 0 */
 	if (!weakDone) {
 		rc = wm.keys.reserve(h, "weak map keys", std::max<uint64_t>(8ull * W * wm.n, 8)); if (rc) return rc;
@@ -1305,11 +1297,11 @@ template <int W> int finish_maps_t(kmr_handle *h, uint32_t *wc, uint32_t *sc, ui
 		hipLaunchKernelGGL((sort_buckets_kernel<W, 0>), dim3(grid_for(sm.nb, 4, 1 << 20)), dim3(256), 0, h->stream, ss, sm.start.get<uint64_t>(), sm.nb);
 	}
 	HIPCHK(h, hipGetLastError());
-	if (!h->bb_overflow) HIPCHK(h, hipStreamSynchronize(h->stream));      /* (bins of one capacity: the caller waits once, for the overflow word) */
+	if (!overflow) HIPCHK(h, hipStreamSynchronize(h->stream));      /* (bins of one capacity: the caller waits once, for the overflow word) */
 	return 0;
 }
-int finish_maps_from_entries(kmr_handle *h, uint32_t *wc, uint32_t *sc, uint64_t wslots, uint64_t sslots, uint64_t wn, uint64_t sn, bool keepSing, bool weak_uncounted, bool fixed_bins) {
-	return with_w(h, [&](auto W) { return finish_maps_t<W()>(h, wc, sc, wslots, sslots, wn, sn, keepSing, weak_uncounted, fixed_bins); });
+int finish_maps_from_entries(kmr_handle *h, uint32_t *wc, uint32_t *sc, uint64_t wslots, uint64_t sslots, uint64_t wn, uint64_t sn, bool keepSing, uint32_t *&overflow, bool weak_uncounted, bool fixed_bins) {
+	return with_w(h, [&](auto W) { return finish_maps_t<W()>(h, wc, sc, wslots, sslots, wn, sn, keepSing, overflow, weak_uncounted, fixed_bins); });
 }
 int finalize_partition(kmr_handle *h, uint32_t min_depth) { return with_w_ext(h, [&](auto W, auto EXT) { return finalize_partition_t<W(), EXT()>(h, min_depth); }); }
 template <int W, bool EXT> int insert_records_partition_t(kmr_handle *h, const void *recs, uint64_t n) {
@@ -1359,29 +1351,39 @@ template <typename... P, typename... A> int launch_sk_tiles(kmr_handle *h, void 
 	HIPCHK(h, hipGetLastError());
 	return 0;
 }
-template <int W, int WIN, bool FILT, bool EXT = false> int launch_sk_extract(kmr_handle *h, const ReadsView &rv, const SkParams &sp, const DevParams *override_params = nullptr) {
-	return launch_sk_tiles(h, sk_extract_kernel<W, WIN, FILT, EXT>, "sk_extract", W, WIN, SK_WAVES, 2, SK_EXTRACT_SMEM, rv, sp, override_params ? *override_params : dev_params(h), sp, pool_view(h, h->l1));
+template <int W, int WIN, bool FILT, bool EXT = false> int launch_sk_extract(kmr_handle *h, const ReadsView &rv, const SkParams &sp, const DevParams &dp) {
+	return launch_sk_tiles(h, sk_extract_kernel<W, WIN, FILT, EXT>, "sk_extract", W, WIN, SK_WAVES, 2, SK_EXTRACT_SMEM, rv, sp, dp, sp, pool_view(h, h->l1));
 }
-uint32_t sk_dbg_flags(const char *name);
+uint32_t sk_dbg_flags(const char *name) {
+#ifdef KMR_DEBUG_HOOKS
+	const char *e = getenv(name); return e ? (uint32_t)atoi(e) : 0u;
+#else
+	(void)name; return 0u;
+#endif
+}
 bool sp_debug_extract(kmr_handle *h) { (void)h; return sk_dbg_flags("KMR_SK_EXTRACT_DBG") != 0; }      /* the ablation switches live in the general kernel */
-template <int W, int WIN, bool PACKED = false> int launch_sk_extract_lean(kmr_handle *h, const ReadsView &rv, const SkParams &sp, float wK, const DevParams *override_params = nullptr, const SkPacked *packed = nullptr) {
-	return launch_sk_tiles(h, sk_extract_lean_kernel<W, WIN, PACKED>, "sk_extract_lean", W, WIN, SKL_WAVES, SKL_MIN_BLOCKS, SKL_EXTRACT_SMEM, rv, sp, override_params ? *override_params : dev_params(h), sp, pool_view(h, h->l1), wK, PACKED ? *packed : SkPacked{});
+template <int W, int WIN, bool PACKED = false> int launch_sk_extract_lean(kmr_handle *h, const ReadsView &rv, const SkParams &sp, const DevParams &dp, float wK, const SkPacked &packed = SkPacked{}) {
+	return launch_sk_tiles(h, sk_extract_lean_kernel<W, WIN, PACKED>, "sk_extract_lean", W, WIN, SKL_WAVES, SKL_MIN_BLOCKS, SKL_EXTRACT_SMEM, rv, sp, dp, sp, pool_view(h, h->l1), wK, packed);
+}
+/* Does the extraction of this build drop k-mers?  Then the general kernel's filtering form takes every launch.  world_size > 1: without
+ * the exchange a rank keeps the k-mers the reference's owner function gives it (getDistributedThreadId, as the other build modes do);
+ * inside an exchange (kmr_sk_exchange_begin) every k-mer is kept, the lists decide the owner */
+bool sk_build_filters(const kmr_handle *h, const DevParams &dp) { return dp.subsample > 1 || dp.num_parts > 1 || (dp.sub_wnb | dp.sub_snb) != 0 || (dp.world > 1 && !h->sk_exchange); }
+/* What a k-mer without an N weighs when all its bases have quality character q, as the general kernel would form it: (float) of the k-fold
+ * product of the character's probability, 1 for Read::REF_QUAL.  lean = false below the floor: the general kernel's zero handling */
+void sk_weight_of_quality(const kmr_handle *h, unsigned int q, bool &lean, float &wK) {
+	lean = false; wK = 1.0f;
+	if (q == 127) lean = true;
+	else if (h->hP[q] > 0.0) { lean = true; wK = (float)h->hPk[q]; }
 }
 /* Do all k-mers without an N of these reads weigh the same (no qualities, or one quality character throughout)?  Then wK is that
- * weight as the general kernel would form it -- (float) of the k-fold product of the character's probability, 1 for REF_QUAL --
- * and sk_extract_lean_kernel may take the launch. */
-int sk_uniform_weight(kmr_handle *h, const ReadsView &rv, bool &lean, float &wK) {
+ * weight and sk_extract_lean_kernel may take the launch. */
+int sk_uniform_weight(kmr_handle *h, const ReadsView &rv, const FeedHints &hints, bool &lean, float &wK) {
 	lean = false; wK = 1.0f;
 	if (h->tune.no_lean_extract) return 0;
-	if (!rv.quals && h->uniform_q_hint < 0) { lean = true; return 0; }
+	if (!rv.quals && hints.uniform_q < 0) { lean = true; return 0; }
 	if (h->qual_mixed || rv.n_reads == 0) return 0;
-	if (h->uniform_q_hint >= 0) {      /* the caller said so (kmr_add_reads_twobit*): no pass over the quality bytes, no round trip */
-		const unsigned int q0 = (unsigned int)h->uniform_q_hint;
-		if (q0 == 127) { lean = true; wK = 1.0f; return 0; }
-		if (!(h->hP[q0] > 0.0)) return 0;
-		lean = true; wK = (float)h->hPk[q0];
-		return 0;
-	}
+	if (hints.uniform_q >= 0) { sk_weight_of_quality(h, (unsigned int)hints.uniform_q, lean, wK); return 0; }      /* the caller said so (kmr_add_reads_twobit*): no pass over the quality bytes, no round trip */
 	{ int rc = h->qrange.reserve(h, "qrange", 8); if (rc) return rc; }
 	const unsigned int init[2] = {255u, 0u};
 	HIPCHK(h, hipMemcpyAsync(h->qrange.get<unsigned int>(), init, 8, hipMemcpyHostToDevice, h->stream));
@@ -1391,159 +1393,156 @@ int sk_uniform_weight(kmr_handle *h, const ReadsView &rv, bool &lean, float &wK)
 	HIPCHK(h, hipMemcpyAsync(got, h->qrange.get<unsigned int>(), 8, hipMemcpyDeviceToHost, h->stream));
 	HIPCHK(h, hipStreamSynchronize(h->stream));
 	if (got[0] != got[1]) { h->qual_mixed = got[0] < got[1]; return 0; }      /* (255 > 0: no quality byte at all) */
-	const unsigned int q0 = got[0];
-	if (q0 == 127) { lean = true; wK = 1.0f; return 0; }                       /* Read::REF_QUAL */
-	if (!(h->hP[q0] > 0.0)) return 0;                                          /* below the floor: the general kernel's zero handling */
-	lean = true; wK = (float)h->hPk[q0];
+	sk_weight_of_quality(h, got[0], lean, wK);
 	return 0;
 }
-uint32_t sk_dbg_flags(const char *name) {
-#ifdef KMR_DEBUG_HOOKS
-	const char *e = getenv(name); return e ? (uint32_t)atoi(e) : 0u;
-#else
-	(void)name; return 0u;
-#endif
-}
 SkParams sk_params(kmr_handle *h) { SkParams sp; sp.dbg = sk_dbg_flags("KMR_SK_EXTRACT_DBG"); sp.keep_all_owners = h->sk_exchange ? 1u : 0u; sp.track = nullptr; sp.m = h->sk_m; sp.off = h->sk_off; sp.list_bits = h->sk_bits; sp.state = h->sk_state.get<unsigned long long>(); sp.Pk = h->dPk.get<double>(); sp.Rp = h->dPk.get<double>() + 256; sp.fast_div = h->sk_fast_div ? 1u : 0u; return sp; }
-template <int W> int add_reads_superkmer_t(kmr_handle *h, const ReadsView &rvAll, uint64_t total_bases) {
+/* one weight for the whole build so far? (the count pass's UNI form): a call that had reads went lean with weight wK, or did not */
+void sk_note_call_weight(kmr_handle *h, bool lean, float wK) {
+	uint32_t wb; memcpy(&wb, &wK, 4);
+	if (!lean) h->sk_uni_mixed = true;
+	else if (h->sk_uni_w == SK_UNI_NONE) h->sk_uni_w = wb;
+	else if (h->sk_uni_w != wb) h->sk_uni_mixed = true;
+}
+/* The list space of a build, before its first extraction: h->sk_bits (and sk_fine_shift), the list words allocated and set.  job_bases:
+ * the bases of the first call, or of the whole host call it is a piece of; lean: the first call's qualities decide.
+ * - est: the list space is the whole job's (with world_size > 1 a rank owns every world_size-th list), sized from the caller's estimate of
+ *   all the k-mers (estimateRawKmers), else from job_bases times the ranks.
+ * - per_list, k-mers per list (about 1100, as the final lists of the two-level partition): the list's distinct keys have to fit the 1024-slot
+ *   table of the count pass (80 %), or the list is redone in sub-passes.  At k <= 32 a list of ~1200 k-mers holds ~350 distinct ones in
+ *   sequencing data; longer k-mers are hit by read errors more often (k = 51, 1 % errors: 40 % of the k-mers hold one and are nearly all
+ *   distinct), so their lists are cut half as long (C4: count pass 133 -> 93 ms; another halving costs more in per-list work than it
+ *   saves).  Extension values: a 512-slot table, COUNT_LOG2S_EXT.  One-word keys: the count pass costs 8.8 ms per 10^9 k-mers of C2-like
+ *   reads with lists of 1300-1600 k-mers, 9.25 at 1144 and at 1830, 10.2 at 2000 -- overflowing tables --, 11.2 at 715 and ~13 at 570 --
+ *   twice the per-list work: between two powers of two the longer lists win up to ~1900 k-mers; 1536 leaves the table room for inputs
+ *   with more distinct k-mers than C2's 30 % (the bound was 1224 once: HISTORY.md).
+ * - Inside an exchange with coarse lists the bits are those of the wire: as many lists and as full as one GPU's.
+ * - aim, one GPU: the list count the count pass likes best instead of a power of two (the code of such a count is the count, sk_list_of).
+ *   One-word keys: lists of ~1450 k-mers (8.8 ms per 10^9 k-mers; C2's 2^20 lists of 1144: 9.25).  Two-word keys: lists just below their
+ *   bound instead of anywhere between half of it and the bound -- C4 at 665 / 850 / 1100 k-mers per list: 195.7 / 201 / 275 ms.  Extension
+ *   values, 10 M reads at k = 21: 2^22 lists of 310 69.4 ms; 570 / 800 / 1000 / 1300 per list: 58.6 / 55.8 / 55.2 / 62.4 ms.  est counts
+ *   raw k-mers: reads with qualities of their own lose some of them to the weight floor -- the noisy C2 batch at 1300 / 1450 / 1600 / 1750
+ *   raw k-mers per list: count pass 12.7 / 11.4 / 11.1 / 11.0 ms; flat qualities at 1450 / 1550 / 1650: 10.6 / 10.8 / 10.8. */
+template <int W> int sk_size_lists(kmr_handle *h, uint64_t job_bases, bool lean) {
+	const uint64_t est = h->cfg.estimated_raw_kmers ? h->cfg.estimated_raw_kmers : job_bases * std::max<uint32_t>(1, h->cfg.world_size);
+	const uint64_t per_list = h->ext ? (W > 1 ? 400 : 600) : ((h->tune.target_list == 2048 && W > 1) ? 700 : h->tune.target_list * 3 / 4);
+	uint32_t bits = 6; while (bits < 24 && (est >> bits) > per_list) bits++;
+	h->sk_fine_shift = 0;
+	if (h->sk_exchange && h->cfg.world_size > 1 && !h->tune.no_coarse_lists) {
+		uint32_t sh = 0; while ((1u << sh) < h->cfg.world_size) sh++;
+		if (bits >= 6 + sh) { h->sk_fine_shift = sh; bits -= sh; }
+	}
+	h->sk_bits = bits;
+	if (h->cfg.world_size <= 1 && !h->sk_exchange && h->tune.target_list == 2048 && !h->tune.pow2_lists) {
+		const uint64_t aim = h->tune.list_aim ? h->tune.list_aim : (W == 1 ? (h->ext ? 800 : (lean ? 1450 : 1700)) : per_list * 19 / 20);
+		const uint64_t nlists = (est / aim + 63) & ~63ull;
+		if (nlists > 64 && (nlists < (1ull << bits) || h->tune.list_aim) && nlists < (1ull << 31)) h->sk_bits = (uint32_t)nlists;
+	}
+	const uint64_t nl0 = sk_list_count(h->sk_bits);
+	HIPCHK(h, h->sk_state.alloc(8 * nl0));
+	hipLaunchKernelGGL(sk_state_init_kernel, dim3(grid_for(nl0)), dim3(256), 0, h->stream, h->sk_state.get<unsigned long long>(), nl0);
+	HIPCHK(h, hipGetLastError());
+	return 0;
+}
+/* A job fed in many calls (estimated_raw_kmers says how much is to come) or in the pieces of one host call (call_bases) gets its pool in ONE
+ * allocation: before the pool exists, h->l1.presize is what the rest of the job typically takes beyond this call's worst case (flat qualities
+ * ~0.25 granules per base, a weight per k-mer ~0.55), a quarter of the free memory at most -- an estimate, and kmr_finalize needs room of its
+ * own.  Growing call by call frees the old pool every time, and an allocation right after tens of GB were freed waits seconds for the driver to
+ * clear them (config 3's whole input in eight calls: 5.1 s for the first build, HISTORY.md section 6); denser input still grows the pool as before */
+void sk_presize_pool(kmr_handle *h, uint64_t call_bases, uint64_t total_bases, uint64_t avg, bool lean) {
+	if (h->l1.base || h->cfg.world_size > 1 || h->sk_exchange || !(h->cfg.estimated_raw_kmers || call_bases > total_bases)) return;
+	const double job_bases = h->cfg.estimated_raw_kmers ? (double)h->cfg.estimated_raw_kmers * (double)avg / (double)(avg > h->k ? avg - h->k + 1 : 1) : (double)call_bases;
+	const double rest = job_bases - (double)total_bases;
+	size_t fr = 0, tot = 0;
+	if (rest > 0 && hipMemGetInfo(&fr, &tot) == hipSuccess) {
+		const uint64_t want = (uint64_t)(rest * (h->ext ? 2.0 : 1.0) * (lean ? 0.3 : 0.65) / SK_CHUNK_G);
+		h->l1.presize = std::min<uint64_t>(want, (uint64_t)(fr / 4) / ((size_t)CH * rec_bytes(h)));
+	}
+}
+/* room in the pool for one launch over `bases` bases: a granule per k-mer is more than any input takes (flat qualities: a quarter of that), one open
+ * chunk per list -- inside an exchange the lists of other owners start afresh after every pack: for every call --, two slabs of 64 chunks per wavefront */
+uint64_t sk_launch_chunks(kmr_handle *h, uint64_t bases) { return (h->ext ? 2 : 1) * bases / SK_CHUNK_G + ((h->l1.base && !h->sk_exchange) ? 0 : sk_list_count(h->sk_bits)) + (uint64_t)num_cus(h) * SK_EXTRACT_WAVES_PER_CU * 130 + 64; }
+/* One extraction launch over reads [r, r + rv.n_reads) of a call, in the form the call chose: the packed batch as it is (lean), the
+ * general kernel where values carry extensions or the build filters k-mers, else the lean kernel for one weight wK or the general one */
+template <int W> int sk_launch_extraction(kmr_handle *h, const ReadsView &rv, const SkParams &sp, const DevParams &dp, bool filt, bool lean, float wK, const SkPacked *packed, uint64_t r) {
+	if (packed) {
+		SkPacked pkd = *packed; pkd.off += r; if (pkd.mk_off) pkd.mk_off += r;
+		return with_win<W>(h->sk_win, [&](auto WIN) { return launch_sk_extract_lean<W, WIN(), true>(h, rv, sp, dp, wK, pkd); });
+	}
+	return with_win<W>(h->sk_win, [&](auto WIN) {
+		if (h->ext) return filt ? launch_sk_extract<W, WIN(), true, true>(h, rv, sp, dp) : launch_sk_extract<W, WIN(), false, true>(h, rv, sp, dp);
+		if (filt) return launch_sk_extract<W, WIN(), true>(h, rv, sp, dp);
+		return lean ? launch_sk_extract_lean<W, WIN()>(h, rv, sp, dp, wK) : launch_sk_extract<W, WIN(), false>(h, rv, sp, dp);
+	});
+}
+/* size tracker, behind a call's launches, which filled h->trk with per-read records (raw and good k-mers, end ordinal).  SizeTracker::track
+ * (src/KmerSpectrum.h:879-894) is called before every k-mer: the thresholds this call's reads pass, each at the t-th raw k-mer of some
+ * read; the walk of those reads (sk_track_boundary_kernel) gives the ordinal and the good k-mers */
+template <int W> int sk_track_call(kmr_handle *h, const ReadsView &rvAll, const DevParams &dp) {
+	const uint64_t n = rvAll.n_reads;
+	std::vector<SkTrackRec> recs(n);
+	HIPCHK(h, hipMemcpyAsync(recs.data(), h->trk.get<SkTrackRec>(), n * sizeof(SkTrackRec), hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipStreamSynchronize(h->stream));
+	std::vector<SkBoundary> bd; std::vector<uint64_t> good_before;
+	const bool walkable = (dp.sub_wnb | dp.sub_snb) == 0;      /* (a subtracting reference decides per k-mer what is raw: read ends there) */
+	for (uint64_t r = 0; r < n; r++) {
+		while ((uint64_t)h->trk_next <= h->trk_raw + recs[r].raw) {
+			SkBoundary b; b.read = r; b.t = (uint32_t)((uint64_t)h->trk_next - h->trk_raw); b.good = 0; b.ordinal = 0;
+			if (!walkable) { b.t = recs[r].raw; b.good = recs[r].good; b.ordinal = recs[r].end_ordinal; }
+			bd.push_back(b); good_before.push_back(h->trk_good);
+			h->trk_snap_raw.push_back(walkable ? (uint64_t)h->trk_next : h->trk_raw + recs[r].raw);
+			h->trk_next = (long)((double)h->trk_next * 1.05);
+			if (!walkable) break;      /* one element per read end */
+		}
+		if (!walkable) while ((uint64_t)h->trk_next <= h->trk_raw + recs[r].raw) h->trk_next = (long)((double)h->trk_next * 1.05);
+		h->trk_raw += recs[r].raw; h->trk_good += recs[r].good;
+	}
+	if (h->trk_bounds.size() + bd.size() > SK_TRACK_MAX) return fail(h, KMR_ERR_UNSUPPORTED, "size tracker: more than 512 elements");
+	if (!bd.empty() && walkable) {
+		DevBuf dbdb; HIPCHK(h, dbdb.alloc(bd.size() * sizeof(SkBoundary)));
+		SkBoundary *dbd = dbdb.get<SkBoundary>();
+		auto chk = [&](hipError_t e) { return e == hipSuccess ? 0 : fail(h, KMR_ERR_HIP, std::string("size tracker boundaries: ") + hipGetErrorString(e)); };
+		int rc = chk(hipMemcpyAsync(dbd, bd.data(), bd.size() * sizeof(SkBoundary), hipMemcpyHostToDevice, h->stream)); if (rc) return rc;
+		ReadsView rv = rvAll; rv.u_start = rv.u_end = rv.u_read = nullptr; rv.n_units = 0;      /* (whole reads: the caller's work units do not apply) */
+		hipLaunchKernelGGL(sk_track_boundary_kernel<W>, dim3((unsigned)((bd.size() + 63) / 64)), dim3(64), 0, h->stream, rv, dp, dbd, (uint32_t)bd.size());
+		rc = chk(hipGetLastError()); if (rc) return rc;
+		rc = chk(hipMemcpyAsync(bd.data(), dbd, bd.size() * sizeof(SkBoundary), hipMemcpyDeviceToHost, h->stream)); if (rc) return rc;
+		rc = chk(hipStreamSynchronize(h->stream)); if (rc) return rc;
+	}
+	for (size_t i = 0; i < bd.size(); i++) { h->trk_bounds.push_back(bd[i].ordinal); h->trk_snap_good.push_back(good_before[i] + bd[i].good); }
+	return 0;
+}
+/* One call's reads into the lists: the form of its extraction, the build's one-weight state, before the first launch of a build the
+ * list space, then a launch per sub-batch, and the size tracker's thresholds where it is on */
+template <int W> int add_reads_superkmer_t(kmr_handle *h, const ReadsView &rvAll, uint64_t total_bases, const FeedHints &hints) {
 	const uint64_t n = rvAll.n_reads;
 	const DevParams dp = dev_params(h);
-	/* world_size > 1: without the exchange a rank keeps the k-mers the reference's owner function gives it (getDistributedThreadId,
-	 * as the other build modes do); inside an exchange (kmr_sk_exchange_begin) every k-mer is kept, the lists decide the owner */
-	const bool filt = dp.subsample > 1 || dp.num_parts > 1 || (dp.sub_wnb | dp.sub_snb) != 0 || (dp.world > 1 && !h->sk_exchange);
-	bool lean = false; float wK = 1.0f;
-	if (!filt && !h->ext && !sp_debug_extract(h)) { int rcq = sk_uniform_weight(h, rvAll, lean, wK); if (rcq) return rcq; }      /* (extension values want every neighbour's quality: the general kernel) */
-	if (h->packed_direct && (!lean || h->cfg.size_tracker)) return fail(h, KMR_ERR_STATE, "internal: a packed batch handed to an extraction that wants text");      /* (sk_packed_direct_ok said otherwise) */
-	if (rvAll.n_reads) {      /* one weight for the whole build so far? (the count pass's UNI form) */
-		uint32_t wb; memcpy(&wb, &wK, 4);
-		if (!lean) h->sk_uni_mixed = true;
-		else if (h->sk_uni_w == SK_UNI_NONE) h->sk_uni_w = wb;
-		else if (h->sk_uni_w != wb) h->sk_uni_mixed = true;
-	}
-	if (!h->sk_state) {
-		/* lists: about 1100 k-mers each, as the final lists of the two-level partition */
-		/* the list space is the whole job's (with world_size > 1 a rank owns every world_size-th list): sized from the caller's estimate
-		 * of all the k-mers (estimateRawKmers), else from this call's bases times the ranks */
-		const uint64_t est = h->cfg.estimated_raw_kmers ? h->cfg.estimated_raw_kmers : std::max<uint64_t>(total_bases, h->call_bases_hint) * std::max<uint32_t>(1, h->cfg.world_size);
-		/* k-mers per list: the list's distinct keys have to fit the 1024-slot table of the count pass (80 %), or the list is redone in
-		 * sub-passes.  At k <= 32 a list of ~1200 k-mers holds ~350 distinct ones in sequencing data; longer k-mers are hit by read
-		 * errors more often (k = 51, 1 % errors: 40 % of the k-mers hold one and are nearly all distinct), so their lists are cut
-		 * half as long (C4: count pass 133 -> 93 ms; another halving costs more in per-list work than it saves) */
-		/* (extension values: a 512-slot table, COUNT_LOG2S_EXT) */
-		/* (one-word keys: the count pass costs 8.8 ms per 10^9 k-mers of C2-like reads with lists of 1300-1600 k-mers, 9.25 at 1144 and at
-		 * 1830, 10.2 at 2000 -- overflowing tables --, 11.2 at 715 and ~13 at 570 -- twice the per-list work: between two powers of two
-		 * the longer lists win up to ~1900 k-mers; 1536 leaves the table room for inputs with more distinct k-mers than C2's 30 %.  Until
-		 * round 3 the bound was 1224: a 12.5 M-read batch went to 2^21 lists of 715 and took 32.2 ms instead of 27.8) */
-		const uint64_t per_list = h->ext ? (W > 1 ? 400 : 600) : ((h->tune.target_list == 2048 && W > 1) ? 700 : h->tune.target_list * 3 / 4);
-		uint32_t bits = 6; while (bits < 24 && (est >> bits) > per_list) bits++;
-		h->sk_fine_shift = 0;
-		if (h->sk_exchange && h->cfg.world_size > 1 && !h->tune.no_coarse_lists) {
-			uint32_t sh = 0; while ((1u << sh) < h->cfg.world_size) sh++;
-			if (bits >= 6 + sh) { h->sk_fine_shift = sh; bits -= sh; }      /* the lists of the wire: as many and as full as one GPU's */
-		}
-		h->sk_bits = bits;
-		/* one GPU, one-word keys, direction-counting values: the list count the count pass likes best instead of a power of two -- lists
-		 * of ~1450 k-mers (8.8 ms per 10^9 k-mers; C2's 2^20 lists of 1144: 9.25).  The code of such a count is the count (sk_list_of). */
-		if (h->cfg.world_size <= 1 && !h->sk_exchange && h->tune.target_list == 2048 && !h->tune.pow2_lists) {
-			/* (two-word keys: lists just below their bound instead of anywhere between half of it and the bound -- C4 at 665 / 850 / 1100
-			 * k-mers per list: 195.7 / 201 / 275 ms.  Extension values, 10 M reads at k = 21: 2^22 lists of 310 69.4 ms; 570 / 800 / 1000 /
-			 * 1300 per list: 58.6 / 55.8 / 55.2 / 62.4 ms) */
-			/* (est counts raw k-mers: reads with qualities of their own lose some of them to the weight floor -- the noisy C2 batch at 1300 /
-			 * 1450 / 1600 / 1750 raw k-mers per list: count pass 12.7 / 11.4 / 11.1 / 11.0 ms; flat qualities at 1450 / 1550 / 1650: 10.6 /
-			 * 10.8 / 10.8.  The first call's qualities decide) */
-			const uint64_t aim = h->tune.list_aim ? h->tune.list_aim : (W == 1 ? (h->ext ? 800 : (lean ? 1450 : 1700)) : per_list * 19 / 20);
-			const uint64_t nlists = (est / aim + 63) & ~63ull;
-			if (nlists > 64 && (nlists < (1ull << bits) || h->tune.list_aim) && nlists < (1ull << 31)) h->sk_bits = (uint32_t)nlists;
-		}
-		const uint64_t nl0 = sk_list_count(h->sk_bits);
-		HIPCHK(h, h->sk_state.alloc(8 * nl0));
-		hipLaunchKernelGGL(sk_state_init_kernel, dim3(grid_for(nl0)), dim3(256), 0, h->stream, h->sk_state.get<unsigned long long>(), nl0);
-		HIPCHK(h, hipGetLastError());
-	}
+	const bool filt = sk_build_filters(h, dp), tracking = h->cfg.size_tracker && n;
+	bool lean = false; float wK = 1.0f; int rc = 0;
+	if (!filt && !h->ext && !sp_debug_extract(h)) { rc = sk_uniform_weight(h, rvAll, hints, lean, wK); if (rc) return rc; }      /* (extension values want every neighbour's quality: the general kernel) */
+	if (hints.packed && (!lean || h->cfg.size_tracker)) return fail(h, KMR_ERR_STATE, "internal: a packed batch handed to an extraction that wants text");      /* (sk_packed_direct_ok said otherwise) */
+	if (n) sk_note_call_weight(h, lean, wK);
+	if (!h->sk_state) { rc = sk_size_lists<W>(h, std::max<uint64_t>(total_bases, hints.call_bases), lean); if (rc) return rc; }
 	const uint64_t avg = n ? std::max<uint64_t>(1, total_bases / n) : 1;
 	const uint64_t sub_bases = h->tune.sub_batch_bases ? h->tune.sub_batch_bases : (1ull << 31);
 	const uint64_t chunk = std::max<uint64_t>(64, (sub_bases / avg) & ~63ull);
-	if (h->cfg.size_tracker && n) {      /* per-read records of this call (raw and good k-mers, end ordinal) */
-		h->trk_n = 0;
-		{ int rc = h->trk.reserve(h, "trk", n * sizeof(SkTrackRec)); if (rc) return rc; }
-		HIPCHK(h, hipMemsetAsync(h->trk.get<SkTrackRec>(), 0, n * sizeof(SkTrackRec), h->stream));
-	}
+	if (tracking) { h->trk_n = 0; rc = h->trk.reserve(h, "trk", n * sizeof(SkTrackRec)); if (rc) return rc; HIPCHK(h, hipMemsetAsync(h->trk.get<SkTrackRec>(), 0, n * sizeof(SkTrackRec), h->stream)); }      /* (sk_track_call) */
 	for (uint64_t r = 0; r < n; r += chunk) {
 		const uint64_t m = std::min(chunk, n - r);
 		ReadsView rv = reads_slice(rvAll, r, m);
-		int rc = prepare_units(h, rv, h->packed_direct ? SK_PACKED_SPAN : (uint32_t)TILE_SPAN); if (rc) return rc;
-		/* room for this launch: a granule per k-mer is more than any input takes (flat qualities: a quarter of that), one open
-		 * chunk per list and two slabs of 64 chunks per wavefront */
-		const uint64_t bases = m * avg + avg;
-		/* A job fed in many calls (estimated_raw_kmers says how much is to come) gets its pool in ONE allocation: this call's worst case
-		 * plus what the rest of the job typically takes (flat qualities ~0.25 granules per base, a weight per k-mer ~0.55), at most half
-		 * of the free memory.  Growing call by call frees the old pool every time, and an allocation right after tens of GB were freed
-		 * waits seconds for the driver to clear them (config 3's whole input in eight calls: 5.1 s for the first build, HISTORY.md section 6);
-		 * denser input than that still grows the pool as before */
-		if (!h->l1.base && r == 0 && h->cfg.world_size <= 1 && !h->sk_exchange && (h->cfg.estimated_raw_kmers || h->call_bases_hint > total_bases)) {
-			const double job_bases = h->cfg.estimated_raw_kmers ? (double)h->cfg.estimated_raw_kmers * (double)avg / (double)(avg > h->k ? avg - h->k + 1 : 1) : (double)h->call_bases_hint;
-			const double rest = job_bases - (double)total_bases;
-			size_t fr = 0, tot = 0;
-			if (rest > 0 && hipMemGetInfo(&fr, &tot) == hipSuccess) {
-				const uint64_t want = (uint64_t)(rest * (h->ext ? 2.0 : 1.0) * (lean ? 0.3 : 0.65) / SK_CHUNK_G);
-				h->l1.presize = std::min<uint64_t>(want, (uint64_t)(fr / 4) / ((size_t)CH * rec_bytes(h)));      /* (an estimate: a quarter of what is free at most, kmr_finalize needs room of its own) */
-			}
-		}
-		/* (inside an exchange the lists of other owners start afresh after every pack: an open chunk per list for every call) */
-		rc = pool_reserve(h, h->l1, (h->ext ? 2 : 1) * bases / SK_CHUNK_G + ((h->l1.base && !h->sk_exchange) ? 0 : sk_list_count(h->sk_bits)) + (uint64_t)num_cus(h) * SK_EXTRACT_WAVES_PER_CU * 130 + 64, true); if (rc) return rc;
+		rc = prepare_units(h, rv, hints.packed ? SK_PACKED_SPAN : (uint32_t)TILE_SPAN); if (rc) return rc;
+		if (r == 0) sk_presize_pool(h, hints.call_bases, total_bases, avg, lean);
+		rc = pool_reserve(h, h->l1, sk_launch_chunks(h, m * avg + avg), true); if (rc) return rc;
 		TimeSpan tb(h, KMR_TIME_BUILD), te(h, KMR_TIME_EXTRACT);
 		SkParams sp = sk_params(h);
 		if (h->cfg.size_tracker) sp.track = h->trk.get<SkTrackRec>() + r;
-		if (h->packed_direct) {
-			SkPacked pkd = *h->packed_direct; pkd.off += r; if (pkd.mk_off) pkd.mk_off += r;
-			rc = with_win<W>(h->sk_win, [&](auto WIN) { return launch_sk_extract_lean<W, WIN(), true>(h, rv, sp, wK, nullptr, &pkd); });
-		} else rc = with_win<W>(h->sk_win, [&](auto WIN) {
-			if (h->ext) return filt ? launch_sk_extract<W, WIN(), true, true>(h, rv, sp) : launch_sk_extract<W, WIN(), false, true>(h, rv, sp);
-			if (filt) return launch_sk_extract<W, WIN(), true>(h, rv, sp);
-			return lean ? launch_sk_extract_lean<W, WIN()>(h, rv, sp, wK) : launch_sk_extract<W, WIN(), false>(h, rv, sp);
-		});
+		rc = sk_launch_extraction<W>(h, rv, sp, dp, filt, lean, wK, hints.packed, r);
 		te.end(); tb.end();
 		if (rc) return rc;
 	}
-	if (h->cfg.size_tracker && n) {
-		/* SizeTracker::track (src/KmerSpectrum.h:879-894) is called before every k-mer: the thresholds this call's reads pass, each at
-		 * the t-th raw k-mer of some read; the walk of those reads (sk_track_boundary_kernel) gives the ordinal and the good k-mers */
-		std::vector<SkTrackRec> recs(n);
-		HIPCHK(h, hipMemcpyAsync(recs.data(), h->trk.get<SkTrackRec>(), n * sizeof(SkTrackRec), hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(h, hipStreamSynchronize(h->stream));
-		std::vector<SkBoundary> bd; std::vector<uint64_t> good_before;
-		const bool walkable = (dp.sub_wnb | dp.sub_snb) == 0;      /* (a subtracting reference decides per k-mer what is raw: read ends there) */
-		for (uint64_t r = 0; r < n; r++) {
-			while ((uint64_t)h->trk_next <= h->trk_raw + recs[r].raw) {
-				SkBoundary b; b.read = r; b.t = (uint32_t)((uint64_t)h->trk_next - h->trk_raw); b.good = 0; b.ordinal = 0;
-				if (!walkable) { b.t = recs[r].raw; b.good = recs[r].good; b.ordinal = recs[r].end_ordinal; }
-				bd.push_back(b); good_before.push_back(h->trk_good);
-				h->trk_snap_raw.push_back(walkable ? (uint64_t)h->trk_next : h->trk_raw + recs[r].raw);
-				h->trk_next = (long)((double)h->trk_next * 1.05);
-				if (!walkable) break;      /* one element per read end */
-			}
-			if (!walkable) while ((uint64_t)h->trk_next <= h->trk_raw + recs[r].raw) h->trk_next = (long)((double)h->trk_next * 1.05);
-			h->trk_raw += recs[r].raw; h->trk_good += recs[r].good;
-		}
-		if (h->trk_bounds.size() + bd.size() > SK_TRACK_MAX) return fail(h, KMR_ERR_UNSUPPORTED, "size tracker: more than 512 elements");
-		if (!bd.empty() && walkable) {
-			DevBuf dbdb; HIPCHK(h, dbdb.alloc(bd.size() * sizeof(SkBoundary)));
-			SkBoundary *dbd = dbdb.get<SkBoundary>();
-			hipError_t e = hipMemcpyAsync(dbd, bd.data(), bd.size() * sizeof(SkBoundary), hipMemcpyHostToDevice, h->stream);
-			if (e == hipSuccess) {
-				ReadsView rv = rvAll; rv.u_start = rv.u_end = rv.u_read = nullptr; rv.n_units = 0;      /* (whole reads: the caller's work units do not apply) */
-				hipLaunchKernelGGL(sk_track_boundary_kernel<W>, dim3((unsigned)((bd.size() + 63) / 64)), dim3(64), 0, h->stream, rv, dp, dbd, (uint32_t)bd.size());
-				e = hipGetLastError();
-			}
-			if (e == hipSuccess) e = hipMemcpyAsync(bd.data(), dbd, bd.size() * sizeof(SkBoundary), hipMemcpyDeviceToHost, h->stream);
-			if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-			if (e != hipSuccess) return fail(h, KMR_ERR_HIP, std::string("size tracker boundaries: ") + hipGetErrorString(e));
-		}
-		for (size_t i = 0; i < bd.size(); i++) { h->trk_bounds.push_back(bd[i].ordinal); h->trk_snap_good.push_back(good_before[i] + bd[i].good); }
-	}
-	return 0;
+	return tracking ? sk_track_call<W>(h, rvAll, dp) : 0;
 }
-int add_reads_superkmer(kmr_handle *h, const ReadsView &rv, uint64_t total_bases) { return with_w(h, [&](auto W) { return add_reads_superkmer_t<W()>(h, rv, total_bases); }); }
+int add_reads_superkmer(kmr_handle *h, const ReadsView &rv, uint64_t total_bases, const FeedHints &hints) { return with_w(h, [&](auto W) { return add_reads_superkmer_t<W()>(h, rv, total_bases, hints); }); }
 /* k-mers seen SK_ORDERED_FROM times or more (sat_*_kernel in kmr_superkmer.hpp): weightedCount and directionBias of their entries in the
  * finished weak map from their first 65 535 sightings in input order, added into a float one after the other as the serial reference
  * does.  n_clamped: how many such keys the count pass kept, n_sightings: their sightings.
@@ -1935,29 +1934,29 @@ template <int W> int finalize_superkmer_t(kmr_handle *h, uint32_t min_depth) {
 	rc = sk_early_takeover<W>(h, p, min_depth, device_error); if (rc) return rc;
 	if (device_error) { whole.end(); return sync_state(h); }
 	rc = sk_long_items<W>(h, p); if (rc) return rc;
-	rc = sk_count_pass<W>(h, p); if (rc) return rc;
-	h->stats.unique_kmers = p.c.unique;
-	h->stats.singleton_kmers = p.f.has_singletons ? p.c.singletons : 0;
-	if (p.tracking) { rc = sk_track_elements(h, p.tv, p.f.has_singletons); if (rc) return rc; }
-	if (p.early_slots) { rc = sk_append_early<W>(h, p); if (rc) return rc; }
-	h->early.active = false;
-	{ TimeSpan t(h, KMR_TIME_BUCKETS); rc = finish_maps_from_entries(h, p.wc, p.sc, p.cur[0], p.cur[1], p.c.weak_kept, p.c.sing_kept, p.keepSing, p.packed, h->tune.bb_fixed_bins); }
-	if (rc) return rc;
+	/* the lists counted, the early count's entries behind them, the maps out of the entries; overflow as finish_maps_t leaves it */
+	uint32_t *overflow = nullptr;
+	auto count_and_bucket = [&](bool fixed_bins) -> int {
+		int rc2 = sk_count_pass<W>(h, p); if (rc2) return rc2;
+		h->stats.unique_kmers = p.c.unique; h->stats.singleton_kmers = p.f.has_singletons ? p.c.singletons : 0;
+		if (p.tracking && !h->last_bb_fallback) { rc2 = sk_track_elements(h, p.tv, p.f.has_singletons); if (rc2) return rc2; }      /* (a second pass counts the same elements) */
+		if (p.early_slots) { rc2 = sk_append_early<W>(h, p); if (rc2) return rc2; }
+		h->early.active = false;
+		TimeSpan t(h, KMR_TIME_BUCKETS);
+		return finish_maps_from_entries(h, p.wc, p.sc, p.cur[0], p.cur[1], p.c.weak_kept, p.c.sing_kept, p.keepSing, overflow, p.packed, fixed_bins);
+	};
 	h->last_bb_fallback = false;
-	if (h->bb_overflow) {
+	rc = count_and_bucket(h->tune.bb_fixed_bins); if (rc) return rc;
+	if (overflow) {
 		/* bins of one capacity: the partition and the group kernel are on the stream, this is where the host waits for them.  A bin or
 		 * group that was fuller than its capacity voids the map, and the packed entries may be overwritten: the lists are counted
 		 * again and bucketed with measured bins */
 		uint32_t ovf = 0;
-		HIPCHK(h, hipMemcpyAsync(&ovf, h->bb_overflow, 4, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
-		h->bb_overflow = nullptr;
+		HIPCHK(h, hipMemcpyAsync(&ovf, overflow, 4, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
 		if (ovf) {
 			if (dbg()) fprintf(stderr, "bucket build: a bin of the radix partition overflowed its capacity, again with measured bins\n");
 			h->last_bb_fallback = true;
-			rc = sk_count_pass<W>(h, p); if (rc) return rc;
-			if (p.early_slots) { rc = sk_append_early<W>(h, p); if (rc) return rc; }
-			{ TimeSpan t(h, KMR_TIME_BUCKETS); rc = finish_maps_from_entries(h, p.wc, p.sc, p.cur[0], p.cur[1], p.c.weak_kept, p.c.sing_kept, p.keepSing, p.packed, false); }
-			if (rc) return rc;
+			rc = count_and_bucket(false); if (rc) return rc;
 		}
 	}
 	h->last_saturated_keys = 0; h->last_saturated_batches = 0;
@@ -2299,6 +2298,19 @@ int kmr_build_info(kmr_handle *h, const char *what, double *value) {
 
 int kmr_sync(kmr_handle *h) { if (!h) return KMR_ERR_INVALID_ARG; hipSetDevice(h->device); return sync_state(h); }
 
+/* Reads on the device go into the build: the one form the feed entry points end in, behind their own argument checks (dev_bases
+ * is null where hints.packed holds the batch).  hints: what the caller knows of this call, FeedHints */
+static int add_reads_dev_call(kmr_handle *h, const void *dev_bases, const void *dev_quals, const void *dev_offsets, uint64_t n_reads, uint64_t total_bases, uint64_t first_global_read_idx, const void *dev_discarded, const FeedHints &hints) {
+	const ReadsView rv = reads_view(dev_bases, dev_quals, dev_offsets, n_reads, dev_discarded, h->stream_base - hints.piece_origin, first_global_read_idx);
+	/* the stream ordinal of an occurrence decides which sighting of a k-mer was its first (directionBias, the quantised first
+	 * weight): 40 bits in the table slots, and the 16-byte records of build_mode 2 without extension values carry 32 of them */
+	if (h->stream_base + total_bases > MAX_STREAM_ORDINAL) return fail(h, KMR_ERR_CAPACITY, "more than 2^40 input bases on one handle");
+	if (h->partition_mode && !h->superkmer_mode && !h->ext && h->stream_base + total_bases > (1ull << 32))
+		return fail(h, KMR_ERR_CAPACITY, "build_mode 2 orders occurrences by a 32-bit stream ordinal: at most 2^32 input bases per handle without extension values (use build_mode 0 / 3 or 1)");
+	int rc = h->superkmer_mode ? add_reads_superkmer(h, rv, total_bases, hints) : (h->partition_mode ? add_reads_partition(h, rv, total_bases) : add_reads_dev_any(h, rv, total_bases));
+	h->stream_base += total_bases; h->reads += n_reads; h->stats.reads = h->reads;
+	return rc;
+}
 int kmr_add_reads_dev(kmr_handle *h, const void *dev_bases, const void *dev_quals, const void *dev_offsets, uint64_t n_reads,
                       uint64_t total_bases, uint64_t first_global_read_idx, const void *dev_discarded) {
 	if (!h) return KMR_ERR_INVALID_ARG;
@@ -2306,15 +2318,7 @@ int kmr_add_reads_dev(kmr_handle *h, const void *dev_bases, const void *dev_qual
 	if (n_reads == 0) return KMR_OK;
 	if (!dev_bases || !dev_offsets) return fail(h, KMR_ERR_INVALID_ARG, "null device buffer");
 	hipSetDevice(h->device);
-	const ReadsView rv = reads_view(dev_bases, dev_quals, dev_offsets, n_reads, dev_discarded, h->stream_base, first_global_read_idx);
-	/* the stream ordinal of an occurrence decides which sighting of a k-mer was its first (directionBias, the quantised first
-	 * weight): 40 bits in the table slots, and the 16-byte records of build_mode 2 without extension values carry 32 of them */
-	if (h->stream_base + total_bases > MAX_STREAM_ORDINAL) return fail(h, KMR_ERR_CAPACITY, "more than 2^40 input bases on one handle");
-	if (h->partition_mode && !h->superkmer_mode && !h->ext && h->stream_base + total_bases > (1ull << 32))
-		return fail(h, KMR_ERR_CAPACITY, "build_mode 2 orders occurrences by a 32-bit stream ordinal: at most 2^32 input bases per handle without extension values (use build_mode 0 / 3 or 1)");
-	int rc = h->superkmer_mode ? add_reads_superkmer(h, rv, total_bases) : (h->partition_mode ? add_reads_partition(h, rv, total_bases) : add_reads_dev_any(h, rv, total_bases));
-	h->stream_base += total_bases; h->reads += n_reads; h->stats.reads = h->reads;
-	return rc;
+	return add_reads_dev_call(h, dev_bases, dev_quals, dev_offsets, n_reads, total_bases, first_global_read_idx, dev_discarded, FeedHints());
 }
 
 /* one piece of a host batch onto the device: staging set `set` of the handle (grow-only), the copy on the handle's copy stream */
@@ -2339,15 +2343,14 @@ static int tb_pipeline_ready(kmr_handle *h) {
 /* A host batch goes over in pieces of about 2^28 bases (kmr_tune "twobit_piece_bases") through two sets of staging buffers and a copy
  * stream of the handle's own: while the device extracts piece i, piece i + 1 is on the bus (the host's pageable memory: the calling
  * thread feeds the copies, the device does not wait for it).  stage(set, r0, r1) puts the copies of reads [r0, r1) on the copy stream
- * (tb_stage_copy into staging set `set`), feed(r0, r1) hands the staged piece to the device entry; both return a KMR code.  Per piece:
+ * (tb_stage_copy into staging set `set`), feed(r0, r1, call_bases) hands the staged piece to the device entry; both return a KMR code.  Per piece:
  * wait for the set's last piece to be consumed, stage, record ready, the handle's stream waits for it, feed, record consumed. */
 }  // extern "C"
 template <class Stage, class Feed> static int tb_feed_pieces(kmr_handle *h, const uint64_t *offsets, uint64_t n_reads, Stage &&stage, Feed &&feed) {
 	{ int rcp = tb_pipeline_ready(h); if (rcp) return rcp; }
 	const uint64_t piece_bases = h->tune.twobit_piece_bases ? h->tune.twobit_piece_bases : (1ull << 28);
 	int rc = KMR_OK; int set = 0;
-	h->call_bases_hint = n_reads ? offsets[n_reads] - offsets[0] : 0;      /* what the first piece sizes is the whole call's */
-	struct HintReset { kmr_handle *h; ~HintReset() { h->call_bases_hint = 0; } } hint_reset{h};
+	const uint64_t call_bases = n_reads ? offsets[n_reads] - offsets[0] : 0;      /* what the first piece sizes is the whole call's (FeedHints) */
 	for (uint64_t r0 = 0; r0 < n_reads && rc == KMR_OK; set ^= 1) {
 		uint64_t r1 = r0 + 1;
 		while (r1 < n_reads && offsets[r1 + 1] - offsets[r0] <= piece_bases) r1++;
@@ -2355,7 +2358,7 @@ template <class Stage, class Feed> static int tb_feed_pieces(kmr_handle *h, cons
 		{ int rcs = stage(set, r0, r1); if (rcs) return rcs; }
 		TBCHK(hipEventRecord(h->tb_ready[set], h->tb_copy_stream));
 		TBCHK(hipStreamWaitEvent(h->stream, h->tb_ready[set], 0));
-		rc = feed(r0, r1);
+		rc = feed(r0, r1, call_bases);
 		TBCHK(hipEventRecord(h->tb_consumed[set], h->stream)); h->tb_set_used[set] = true;
 		r0 = r1;
 	}
@@ -2384,8 +2387,8 @@ int kmr_add_reads(kmr_handle *h, const char *bases, const char *quals, const uin
 		TBCHK(hipMemsetAsync((uint8_t *)db + total, 0, 64, h->tb_copy_stream)); if (dq) TBCHK(hipMemsetAsync((uint8_t *)dq + total, 0, 64, h->tb_copy_stream));
 		return KMR_OK;
 	};
-	auto feed = [&](uint64_t r0, uint64_t r1) {
-		return kmr_add_reads_dev(h, (uint8_t *)db - offsets[r0], dq ? (uint8_t *)dq - offsets[r0] : nullptr, doff, r1 - r0, offsets[r1] - offsets[r0], first_global_read_idx + r0, dd);
+	auto feed = [&](uint64_t r0, uint64_t r1, uint64_t call_bases) {
+		return add_reads_dev_call(h, (uint8_t *)db - offsets[r0], dq ? (uint8_t *)dq - offsets[r0] : nullptr, doff, r1 - r0, offsets[r1] - offsets[r0], first_global_read_idx + r0, dd, FeedHints{nullptr, -1, call_bases, offsets[r0]});
 	};
 	return tb_feed_pieces(h, offsets, n_reads, stage, feed);
 }
@@ -2394,15 +2397,14 @@ int kmr_add_reads(kmr_handle *h, const char *bases, const char *quals, const uin
  * batch to the lean extraction: lists, direction-counting values, nothing that filters k-mers, and one weight for every k-mer. */
 static bool sk_packed_direct_ok(kmr_handle *h, bool has_quals, int uniform_quality) {
 	if (!h->superkmer_mode || h->ext || h->cfg.size_tracker || h->tune.no_lean_extract || h->tune.no_packed_direct || sp_debug_extract(h) || has_quals || h->qual_mixed) return false;
-	const DevParams dp = dev_params(h);
-	if (dp.subsample > 1 || dp.num_parts > 1 || (dp.sub_wnb | dp.sub_snb) != 0 || (dp.world > 1 && !h->sk_exchange)) return false;
-	return uniform_quality == 0 || uniform_quality == 127 || h->hP[uniform_quality] > 0.0;
+	if (sk_build_filters(h, dev_params(h))) return false;
+	bool lean = true; float wK = 1.0f;
+	if (uniform_quality) sk_weight_of_quality(h, (unsigned int)uniform_quality, lean, wK);
+	return lean;
 }
-int kmr_add_reads_twobit_dev(kmr_handle *h, const void *dev_twobit, const void *dev_twobit_offsets, const void *dev_offsets,
-                             const void *dev_markup_offsets, const void *dev_markup_pos, const void *dev_markup_char,
-                             const void *dev_quals, int uniform_quality, uint64_t n_reads, uint64_t total_bases,
-                             uint64_t first_global_read_idx, const void *dev_discarded) {
-	if (!h) return KMR_ERR_INVALID_ARG;
+/* kmr_add_reads_twobit_dev, and a piece of kmr_add_reads_twobit (call_bases: the bases of that whole call, FeedHints) */
+static int add_reads_twobit_dev_call(kmr_handle *h, const void *dev_twobit, const void *dev_twobit_offsets, const void *dev_offsets, const void *dev_markup_offsets, const void *dev_markup_pos, const void *dev_markup_char,
+                                     const void *dev_quals, int uniform_quality, uint64_t n_reads, uint64_t total_bases, uint64_t first_global_read_idx, const void *dev_discarded, uint64_t call_bases) {
 	if (h->finalized) return fail(h, KMR_ERR_STATE, "kmr_add_reads after kmr_finalize");
 	if (n_reads == 0) return KMR_OK;
 	if (!dev_twobit || !dev_offsets) return fail(h, KMR_ERR_INVALID_ARG, "null device buffer");
@@ -2412,6 +2414,7 @@ int kmr_add_reads_twobit_dev(kmr_handle *h, const void *dev_twobit, const void *
 	/* grow-only scratch of the handle; everything below is ordered on the handle's stream, so the next call's unpack waits for
 	 * this call's extraction */
 	const bool direct = sk_packed_direct_ok(h, dev_quals != nullptr, uniform_quality);
+	FeedHints hints; hints.call_bases = call_bases; hints.uniform_q = (!dev_quals && uniform_quality) ? uniform_quality : -1;
 	if (!direct && h->tb_bases.cap() < total_bases + 64) {
 		if (h->tb_bases) HIPCHK(h, hipStreamSynchronize(h->stream));
 		HIPCHK(h, h->tb_bases.alloc(total_bases + 64));
@@ -2430,14 +2433,9 @@ int kmr_add_reads_twobit_dev(kmr_handle *h, const void *dev_twobit, const void *
 	if (direct) {
 		/* the lean extraction stages the packed bytes as they are: no unpacked copy of the batch, no quality bytes */
 		{ int rc = twobit_rel_offsets(h, (const uint64_t *)dev_offsets, n_reads, h->tb_rel.get<uint64_t>()); if (rc) return rc; }
-		if (h->stream_base + total_bases > MAX_STREAM_ORDINAL) return fail(h, KMR_ERR_CAPACITY, "more than 2^40 input bases on one handle");
-		const ReadsView rv = reads_view(nullptr, nullptr, h->tb_rel.get<uint64_t>(), n_reads, dev_discarded, h->stream_base, first_global_read_idx);
 		SkPacked pkd; pkd.bytes = (const uint8_t *)dev_twobit; pkd.off = tboff; pkd.mk_off = (const uint64_t *)dev_markup_offsets; pkd.mk_pos = (const uint32_t *)dev_markup_pos; pkd.mk_char = (const uint8_t *)dev_markup_char;
-		h->packed_direct = &pkd; h->uniform_q_hint = uniform_quality ? uniform_quality : -1;
-		const int rc = add_reads_superkmer(h, rv, total_bases);
-		h->packed_direct = nullptr; h->uniform_q_hint = -1;
-		h->stream_base += total_bases; h->reads += n_reads; h->stats.reads = h->reads;
-		return rc;
+		hints.packed = &pkd;
+		return add_reads_dev_call(h, nullptr, nullptr, h->tb_rel.get<uint64_t>(), n_reads, total_bases, first_global_read_idx, dev_discarded, hints);
 	}
 	{ int rc = twobit_unpack(h, (const uint8_t *)dev_twobit, tboff, (const uint64_t *)dev_offsets, (const uint64_t *)dev_markup_offsets, (const uint32_t *)dev_markup_pos,
 	                         (const uint8_t *)dev_markup_char, n_reads, h->tb_bases.get<uint8_t>(), h->tb_rel.get<uint64_t>()); if (rc) return rc; }
@@ -2454,10 +2452,12 @@ int kmr_add_reads_twobit_dev(kmr_handle *h, const void *dev_twobit, const void *
 		q = h->tb_quals.get<uint8_t>();
 	}
 	/* (dev_quals[0] is the quality of the call's first base: the unpacked batch and its offsets start there too) */
-	h->uniform_q_hint = (!dev_quals && uniform_quality) ? uniform_quality : -1;
-	const int rc = kmr_add_reads_dev(h, h->tb_bases.get<uint8_t>(), q, h->tb_rel.get<uint64_t>(), n_reads, total_bases, first_global_read_idx, dev_discarded);
-	h->uniform_q_hint = -1;
-	return rc;
+	return add_reads_dev_call(h, h->tb_bases.get<uint8_t>(), q, h->tb_rel.get<uint64_t>(), n_reads, total_bases, first_global_read_idx, dev_discarded, hints);
+}
+int kmr_add_reads_twobit_dev(kmr_handle *h, const void *dev_twobit, const void *dev_twobit_offsets, const void *dev_offsets, const void *dev_markup_offsets, const void *dev_markup_pos, const void *dev_markup_char,
+                             const void *dev_quals, int uniform_quality, uint64_t n_reads, uint64_t total_bases, uint64_t first_global_read_idx, const void *dev_discarded) {
+	if (!h) return KMR_ERR_INVALID_ARG;
+	return add_reads_twobit_dev_call(h, dev_twobit, dev_twobit_offsets, dev_offsets, dev_markup_offsets, dev_markup_pos, dev_markup_char, dev_quals, uniform_quality, n_reads, total_bases, first_global_read_idx, dev_discarded, 0);
 }
 
 int kmr_add_reads_twobit(kmr_handle *h, const uint8_t *twobit, const uint64_t *twobit_offsets, const uint64_t *offsets,
@@ -2485,8 +2485,8 @@ int kmr_add_reads_twobit(kmr_handle *h, const uint8_t *twobit, const uint64_t *t
 		if (discarded) TBCHK(tb_stage_copy(h, set, 7, discarded + r0, m, &dd));
 		return KMR_OK;
 	};
-	auto feed = [&](uint64_t r0, uint64_t r1) {
-		return kmr_add_reads_twobit_dev(h, dtb, dto, doff, dmo, dmp, dmc, dq, quals ? 0 : uniform_quality, r1 - r0, offsets[r1] - offsets[r0], first_global_read_idx + r0, dd);
+	auto feed = [&](uint64_t r0, uint64_t r1, uint64_t call_bases) {
+		return add_reads_twobit_dev_call(h, dtb, dto, doff, dmo, dmp, dmc, dq, quals ? 0 : uniform_quality, r1 - r0, offsets[r1] - offsets[r0], first_global_read_idx + r0, dd, call_bases);
 	};
 	return tb_feed_pieces(h, offsets, n_reads, stage, feed);
 }
@@ -2611,7 +2611,7 @@ template <int W> int lookup_stream_t(kmr_handle *h, const ReadsView &rvAll, uint
 	DevParams dp = dev_params(h);
 	dp.min_weight = 0.5f; dp.subsample = 1; dp.world = 1; dp.num_parts = 1; dp.sub_wnb = 0; dp.sub_snb = 0; dp.stats = h->scratch_stats.get<DevStats>();
 	SkParams sp = sk_params(h); sp.keep_all_owners = 1; sp.track = nullptr;
-	rc = with_win<W>(h->sk_win, [&](auto WIN) { return (!rv.quals && !h->tune.no_lean_extract) ? launch_sk_extract_lean<W, WIN()>(h, rv, sp, 1.0f, &dp) : launch_sk_extract<W, WIN(), false>(h, rv, sp, &dp); });
+	rc = with_win<W>(h->sk_win, [&](auto WIN) { return (!rv.quals && !h->tune.no_lean_extract) ? launch_sk_extract_lean<W, WIN()>(h, rv, sp, dp, 1.0f) : launch_sk_extract<W, WIN(), false>(h, rv, sp, dp); });
 	if (rc) return rc;
 	hipLaunchKernelGGL(sk_close_kernel, dim3(grid_for(nl)), dim3(256), 0, h->stream, h->sk_state.get<unsigned long long>(), nl, h->l1.chunk_count.get<uint32_t>(), h->l1.cap);
 	HIPCHK(h, hipGetLastError());
@@ -3194,7 +3194,7 @@ int kmr_sk_exchange_begin(kmr_handle *h) {
 }
 static int sk_ensure_state(kmr_handle *h) {      /* a rank without reads still owns lists */
 	if (h->sk_state) return 0;
-	return add_reads_superkmer(h, reads_view(nullptr, nullptr, nullptr, 0), 0);
+	return add_reads_superkmer(h, reads_view(nullptr, nullptr, nullptr, 0), 0, FeedHints());
 }
 int kmr_sk_exchange_counts(kmr_handle *h, uint64_t *chunks, uint64_t *granules) {
 	if (!h || !chunks || !granules) return KMR_ERR_INVALID_ARG;

@@ -172,7 +172,7 @@ struct KMR_HIDDEN Tuning {
 	double bb_slack_bins = 1.0, bb_slack_groups = 1.0;      /* scale of the room above the mean in a first-level bin / in a group (bb_fixed_limit); tests: 0 leaves less than the mean, so that the level overflows */
 	bool bb_reload = false;            /* bb_scatter_fixed_kernel reads a tile's entries a second time instead of keeping them in registers (A/B runs) */
 	uint64_t twobit_piece_bases = 0;   /* kmr_add_reads_twobit: bases per piece of the host-to-device pipeline (0 = 2^26) */
-	uint64_t list_aim = 0;             /* k-mers per list the list count of a single GPU's build aims for (0: the defaults of add_reads_superkmer_t) */
+	uint64_t list_aim = 0;             /* k-mers per list the list count of a single GPU's build aims for (0: the defaults of sk_size_lists) */
 	bool pow2_lists = false;           /* the list count of build_mode 3 always a power of two (A/B runs, tests of both list functions) */
 	bool no_packed_direct = false;     /* kmr_add_reads_twobit* always unpack to text first (A/B runs, tests of the unpack path) */
 	bool no_uniform_count = false;     /* never take sk_count_kernel<.., UNI> (A/B runs, tests of the general count pass on one-weight builds) */
@@ -188,6 +188,15 @@ struct KMR_HIDDEN Tuning {
 	uint32_t pair_hash_bits = 64;      /* kmr_identify_pairs*: bits of the common name's hash the phase-2 sort keys keep (tests: a few bits, so that distinct names share a key) */
 	int bimodal_window = -1;           /* bimodal_trim_kernel: the longest run it stages in LDS (-1: BM_CAP; tests: 0, so that every run is walked in global memory) */
 	bool no_coarse_lists = true;       /* exchange: scatter into the job's fine lists (default) or, kmr_tune("coarse_lists", 1), into coarse ones that the owner splits before the count pass (sk_refine_kernel: not yet fast enough to pay) */
+};
+
+/* What the caller of one feed call knows about it, handed down from the entry point to the extraction (add_reads_dev_call,
+ * add_reads_superkmer_t, sk_uniform_weight); it ends with the call */
+struct KMR_HIDDEN FeedHints {
+	const kmr::SkPacked *packed = nullptr;      /* the batch is two-bit packed and sk_extract_lean_kernel<.., PACKED> takes it as it is (sk_packed_direct_ok) */
+	int uniform_q = -1;                         /* >= 0: the qualities of the batch are this one character */
+	uint64_t call_bases = 0;                    /* a host batch goes to the device in pieces: the bases of the WHOLE call, for what the first piece sizes (lists, chunk pool) */
+	uint64_t piece_origin = 0;                  /* ... and a piece that keeps the call's offsets: its first one, which stream_base has counted already (stream ordinals) */
 };
 
 struct KMR_HIDDEN kmr_handle : HandleMem, BuildMem, ExchangeMem {
@@ -218,17 +227,13 @@ struct KMR_HIDDEN kmr_handle : HandleMem, BuildMem, ExchangeMem {
 	 * reads are still at hand: the stream ordinal behind the k-mer at which rawKmers reached the threshold, rawKmers, rawGoodKmers */
 	long trk_next = 128; uint64_t trk_raw = 0, trk_good = 0; std::vector<unsigned long long> trk_bounds; std::vector<uint64_t> trk_snap_raw, trk_snap_good;
 	bool sk_fast_div = false;          /* see kmr_create: the chain's divide as multiply-and-correct */
-	bool sender_launch = false;        /* extract_by_owner_t, build (not request) mode: dev_params tells the kernel to count what it does not send */
 	bool sk_exchange = false;          /* kmr_sk_exchange_begin: the lists are the whole job's, every owner's k-mers are kept until the exchange */
 	bool auto_mode = false;            /* build_mode 0: a handle that is fed k-mer records (the owner exchange) before any reads falls back to mode 2 */
 	int bits1 = 0;
 	uint64_t inserted_records = 0;     /* records fed through kmr_insert_records_dev (counted on the host) */
-	uint64_t call_bases_hint = 0;      /* a host batch goes to the device in pieces: the bases of the WHOLE call, for what the first piece sizes (lists, chunk pool) */
 	uint32_t lut_log2 = 0;
 	uint64_t lut_gen = ~0ull, map_gen = 0;                           /* the lookup table belongs to the maps of generation lut_gen */
 	hipStream_t tb_copy_stream = nullptr; hipEvent_t tb_ready[2] = {nullptr, nullptr}, tb_consumed[2] = {nullptr, nullptr}; bool tb_set_used[2] = {false, false};
-	const kmr::SkPacked *packed_direct = nullptr;      /* set while kmr_add_reads_twobit_dev feeds a batch that sk_extract_lean_kernel<.., PACKED> takes as it is */
-	int uniform_q_hint = -1;           /* >= 0 while kmr_add_reads_twobit_dev feeds a batch whose qualities are this one character */
 	/* build_mode 3 (kmr_superkmer.hpp): list count and minimizer geometry */
 	uint32_t sk_bits = 0, sk_m = 0, sk_off = 0, sk_win = 0;
 	double hP[256], hPk[256];              /* host copies of the probability table and of its k-fold products */
@@ -240,8 +245,8 @@ struct KMR_HIDDEN kmr_handle : HandleMem, BuildMem, ExchangeMem {
 	uint64_t xr_lo = 0, xr_hi = ~0ull;      /* kmr_sk_exchange_range */
 	uint64_t last_early_hi = 0, last_early_entries = 0;      /* what the last kmr_finalize took over from an early count (kmr_build_info) */
 	/* the radix partition of the last kmr_finalize (kmr_build_info "bb_path": 0 none, 1 measured bins, 2 bins of one capacity; "bb_fallback": a bin
-	 * overflowed and the build was made again with measured bins), and the overflow word of one that is on the stream (null: none) */
-	int last_bb_path = 0; bool last_bb_fallback = false; uint32_t *bb_overflow = nullptr;
+	 * overflowed and the build was made again with measured bins) */
+	int last_bb_path = 0; bool last_bb_fallback = false;
 	/* --bimodal-sigmas (kmr_set_bimodal_sigmas; ReadSelector::_bimodalSigmas, -1 = off) and what the last scoring call left: the number of its reads
 	 * (~0: there was none) and whether bimodal_buf holds their words (kmr_bimodal_copy).  sel_bimodal: the words kmr_select_bimodal handed in for the
 	 * next selecting call over host arrays */
@@ -261,7 +266,6 @@ struct KMR_HIDDEN kmr_handle : HandleMem, BuildMem, ExchangeMem {
 	/* exchange with world_size > 1: sk_bits are the COARSE lists reads are scattered into and that travel; each holds 2^sk_fine_shift
 	 * fine lists, made by sk_refine_kernel before the count pass (fine state: sk_fine_state) */
 	uint32_t sk_fine_shift = 0;
-	uint32_t sk_min_override = 0;
 	uint64_t xo_segcap = 0; std::vector<uint64_t> xo_counts; const void *xo_batch = nullptr; uint64_t xo_first = 0;      /* xo_dev's segments */
 	/* kmr_exchange_* (kmr_exchange_rccl.hpp): communicator, transport, what the job was fed so far */
 	void *xc_comm = nullptr; kmr_transport xc_tr = {nullptr, nullptr, nullptr};

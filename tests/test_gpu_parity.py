@@ -1642,6 +1642,80 @@ def test_twobit_packed_bytes_staged_directly(k, uq):
             assert np.array_equal(pa.image(which), pt.image(which)), (layout, direct, which)
 
 
+def _reads_of_genome(genome, n, seed, quality="flat", n_rate=0.0, read_len=100, err=0.01):
+    """synth_reads over a genome that is given, so that batches of different seeds hold the same k-mers"""
+    rng = np.random.default_rng(seed)
+    codes = genome[rng.integers(0, genome.size - read_len + 1, size=n)[:, None] + np.arange(read_len)[None, :]]
+    strand = rng.integers(0, 2, size=n).astype(bool)
+    codes[strand] = (3 - codes[strand])[:, ::-1]
+    errs = rng.random(codes.shape) < err
+    codes = np.where(errs, (codes + rng.integers(1, 4, size=codes.shape, dtype=np.uint8)) & 3, codes).astype(np.uint8)
+    bases = np.frombuffer(b"ACGT", np.uint8)[codes]
+    quals = np.full(codes.shape, ord("I"), np.uint8)
+    if quality == "noisy":
+        quals = (np.array([40, 30, 20, 10, 2], np.uint8)[rng.choice(5, size=codes.shape, p=[0.80, 0.10, 0.05, 0.04, 0.01])] + 33).astype(np.uint8)
+        quals[errs] = 10 + 33
+    ns = rng.random(codes.shape) < n_rate
+    bases = np.where(ns, ord("N"), bases).astype(np.uint8); quals = np.where(ns, 33 + 2, quals).astype(np.uint8)
+    return ReadBatch.from_arrays(np.ascontiguousarray(bases.reshape(-1)), np.ascontiguousarray(quals.reshape(-1)), np.arange(n + 1, dtype=np.uint64) * np.uint64(read_len))
+
+
+@pytest.mark.parametrize("k", [31, 51])
+def test_a_feed_calls_hints_end_with_the_call(k):
+    """What a feed call knows of its batch -- the packed bytes the lean extraction may take as they are, the one quality character, the
+    bases of the whole host call -- is handed down with the call (FeedHints) and gone when it returns.  Four batches into one handle: packed
+    reads from host memory in pieces with one quality character (packed-direct), text without qualities (REF_QUAL, weight 1: a weight or a
+    packed source left over from the first call would change its first-sighting weights), packed reads again with the unpack forced (the
+    character as a hint alone), text with noisy qualities.  Then two packed batches alone: one weight for the whole build, the lists of the
+    same batches fed as single device calls.  One- and two-word keys.  (The batches share one genome and the text calls go over in pieces
+    too: the stream ordinals of a call's later pieces must stay below the next call's, or a k-mer's first sighting -- whose weight is
+    quantised -- is taken from the wrong call.)"""
+    torch = pytest.importorskip("torch")
+    genome = np.random.default_rng(4000 + k).integers(0, 4, size=40000, dtype=np.uint8)
+    a, b, c, a2 = (_reads_of_genome(genome, 1500, seed) for seed in (1, 2, 3, 5))
+    d = _reads_of_genome(genome, 1500, 4, quality="noisy", n_rate=0.002)
+    b.quals = None
+    cfg = default_config(k, estimated_raw_kmers=4 * 1500 * (100 - k + 1))
+    uq = ord("I")
+
+    def packed(p, rb, first):      # kmr_add_reads_twobit: the flat quality as uniform_quality, four pieces
+        tw, to, mk = _pack_twobit(rb)
+        p.buildKmerSpectrumTwoBit(tw, to, rb.offsets, uniform_quality=uq, markups=mk, first_read_idx=first)
+
+    o = OracleSpectrum(cfg)
+    p = product(cfg, 3, twobit_piece_bases=40000)
+    for i, rb in enumerate((a, b, c, d)):
+        o.add_reads(rb, first_idx=1500 * i)
+        if i == 2:
+            p.tune(packed_direct=0)
+        if i in (0, 2):
+            packed(p, rb, 1500 * i)
+        else:
+            add(p, rb, first=1500 * i)
+    o.finalize(2); p.finalize(2)
+    assert o.stats() == p.stats()
+    assert compare_weak_images(o.image(KMR_MAP_WEAK), p.image(KMR_MAP_WEAK), p.kb, False) == o.stats()["weak_entries"]
+    assert p.build_info("uniform_count") == 0.0
+
+    o = OracleSpectrum(cfg)
+    p = product(cfg, 3, twobit_piece_bases=40000)
+    q = product(cfg, 3)
+    dev = torch.device("cuda", 0)
+    for i, rb in enumerate((a, a2)):
+        o.add_reads(rb, first_idx=1500 * i)
+        packed(p, rb, 1500 * i)
+        tw, to, (mp, mc, mo) = _pack_twobit(rb)
+        d_tw, d_to, d_off = (torch.from_numpy(np.ascontiguousarray(x).view(dt)).to(dev) for x, dt in ((tw, np.uint8), (to, np.int64), (rb.offsets, np.int64)))
+        assert mp.size == 0      # (no N in these batches: no markups)
+        q.buildKmerSpectrumTwoBitDevice(d_tw.data_ptr(), d_to.data_ptr(), d_off.data_ptr(), rb.n, int(rb.bases.size), uniform_quality=uq, first_read_idx=1500 * i)
+        q.sync()
+    assert p.build_info("lists") == q.build_info("lists") > 64
+    o.finalize(2); p.finalize(2)
+    assert p.build_info("uniform_count") == 1.0
+    assert o.stats() == p.stats()
+    assert compare_weak_images(o.image(KMR_MAP_WEAK), p.image(KMR_MAP_WEAK), p.kb, False) == o.stats()["weak_entries"]
+
+
 WALK_TILE_SPAN = 9824      # TILE_SPAN of kmr_kernels.hpp: the bytes of reads one staging pass of an extraction wavefront takes
 
 
