@@ -1131,6 +1131,9 @@ void *kmr_stream(kmr_handle *h);
  *   "artifact_report_lds" (where kmr_artifact_filter_report* / kmr_artifact_filter_apply_report* sum the per-sequence counters: 1 = per unit in LDS
  *   first, while 24 bytes a sequence index fit 48 KiB, 0 = global 64-bit atomics, anything else = the default, LDS while they fit 6 KiB; tests force
  *   either; see kmr_build_info; may be set at any time).
+ *   "csr_partition" (how kmr_finalize, kmr_count_lists_prefix and the streaming lookups find every list's chunks: 1, the default, by a radix
+ *   partition of the (list, chunk) pairs, 0 by one device atomic per chunk, which builds of more than 2^24 lists take anyway; see
+ *   kmr_build_info "csr_path"; may be set at any time).
  * Call before the first kmr_add_reads* of a build.  KMR_ERR_INVALID_ARG for an unknown knob. */
 int kmr_tune(kmr_handle *h, const char *knob, double value);
 /* What the current build decided, for tests and measurement tools (the reference logs such figures, LOG_VERBOSE): "lists" = super-k-mer
@@ -1155,7 +1158,10 @@ int kmr_tune(kmr_handle *h, const char *knob, double value);
  * "dedup_ms" / "dedup_key_ms" / "dedup_sort_ms" / "dedup_consensus_ms" = HIP-event times of the last kmr_dedup_fragments* on this
  * handle: the whole call, its key kernel, its radix sorts, its consensus kernel (0 unless kmr_tune "dedup_timing" is set),
  * "artifact_report_lds" = 1 if the last kmr_artifact_filter_report* / kmr_artifact_filter_apply_report* on this handle summed its counters in LDS, 0 if by
- * global atomics.
+ * global atomics,
+ * "csr_path" / "csr_chunks" = how the last chunk index of this handle was made (1: radix partition, 0: an atomic per chunk, -1: none yet) and
+ * how many chunks of the pool it looked at, "unit_batches" = batches fed to this handle so far that held a read longer than an extraction
+ * tile and were cut into work units.
  * KMR_ERR_INVALID_ARG for an unknown name. */
 int kmr_build_info(kmr_handle *h, const char *what, double *value);
 

@@ -148,8 +148,11 @@ int alloc_table(kmr_handle *h, uint32_t log2cap, DevBuf &slots, DevBuf &ext) {
 	return 0;
 }
 
-/* read the device error word and counters; synchronises the stream */
-int sync_state(kmr_handle *h) {
+/* read the device error word and counters; synchronises the stream.  with_pool_head: the record pool's head comes back with the same
+ * wait (h->l1_head_seen, for a build_csr that follows with no launch in between that takes chunks) */
+int sync_state(kmr_handle *h, bool with_pool_head = false) {
+	h->l1_head_seen = 0;
+	if (with_pool_head && h->l1.head) HIPCHK(h, hipMemcpyAsync(&h->l1_head_seen, h->l1.head.get<unsigned int>(), 4, hipMemcpyDeviceToHost, h->stream));
 	HIPCHK(h, hipStreamSynchronize(h->stream));
 	for (int which = 0; which < KMR_TIME_GROUPS; which++) {
 		for (auto &pr : h->pending_events[which]) {
@@ -208,23 +211,33 @@ int ensure_capacity(kmr_handle *h, uint64_t incoming) {
 const size_t EXTRACT_SMEM = (size_t)WAVES_PER_BLOCK * 2 * TILE_BUF;
 
 /* If the batch holds reads longer than one LDS tile, cut them into work units (see ReadsView) and point rv at them. */
-int prepare_units(kmr_handle *h, ReadsView &rv, uint32_t span = (uint32_t)TILE_SPAN) {
+/* longest: the batch's longest read where the caller has it already (sk_uniform_weight's pass over the qualities takes it along);
+ * otherwise it is learned here first, and only a batch that holds a read longer than `span` has its units counted and cut. */
+int prepare_units(kmr_handle *h, ReadsView &rv, uint32_t span = (uint32_t)TILE_SPAN, const unsigned int *longest = nullptr) {
 	rv.u_start = rv.u_end = rv.u_read = nullptr; rv.n_units = 0;
 	const uint64_t n = rv.n_reads;
 	if (n == 0) return 0;
-	int rc = h->umax.reserve(h, "umax", 4); if (rc) return rc;
-	HIPCHK(h, hipMemsetAsync(h->umax.get<unsigned int>(), 0, 4, h->stream));
-	rc = h->ucnt.reserve(h, "ucnt", 4 * (n + 1)); if (rc) return rc;
-	hipLaunchKernelGGL(unit_count_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, rv.offsets, n, h->k, span, h->ucnt.get<uint32_t>(), h->umax.get<unsigned int>());
-	HIPCHK(h, hipGetLastError());
+	int rc = 0;
 	unsigned int mx = 0;
-	HIPCHK(h, hipMemcpyAsync(&mx, h->umax.get<unsigned int>(), 4, hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(h, hipStreamSynchronize(h->stream));
+	if (longest) mx = *longest;
+	else {
+		rc = h->umax.reserve(h, "umax", 4); if (rc) return rc;
+		HIPCHK(h, hipMemsetAsync(h->umax.get<unsigned int>(), 0, 4, h->stream));
+		hipLaunchKernelGGL(unit_max_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, rv.offsets, n, h->umax.get<unsigned int>());
+		HIPCHK(h, hipGetLastError());
+		HIPCHK(h, hipMemcpyAsync(&mx, h->umax.get<unsigned int>(), 4, hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, hipStreamSynchronize(h->stream));
+	}
 	if (mx <= span) return 0;                   /* the usual case: every read is one unit */
+	h->unit_batches++;
+	rc = h->ucnt.reserve(h, "ucnt", 4 * (n + 1)); if (rc) return rc;
+	hipLaunchKernelGGL(unit_count_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, rv.offsets, n, h->k, span, h->ucnt.get<uint32_t>());
+	HIPCHK(h, hipGetLastError());
 	rc = h->ufirst.reserve(h, "ufirst", 8 * (n + 1)); if (rc) return rc;
-	rc = exclusive_scan(h, h->ucnt.get<uint32_t>(), n, h->ufirst.get<uint64_t>()); if (rc) return rc;
+	rc = exclusive_scan_queue(h, h->ucnt.get<uint32_t>(), n, h->ufirst.get<uint64_t>()); if (rc) return rc;
 	uint64_t U = 0;
-	HIPCHK(h, hipMemcpy(&U, h->ufirst.get<uint64_t>() + n, 8, hipMemcpyDeviceToHost));
+	HIPCHK(h, hipMemcpyAsync(&U, h->ufirst.get<uint64_t>() + n, 8, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipStreamSynchronize(h->stream));
 	if (h->u_read.cap() < 8 * U) {      /* (u_read is allocated last) */
 		h->u_start.reset(); h->u_end.reset(); h->u_read.reset();
 		HIPCHK(h, h->u_start.alloc(8 * U)); HIPCHK(h, h->u_end.alloc(8 * U)); HIPCHK(h, h->u_read.alloc(8 * U));
@@ -798,22 +811,48 @@ template <int W, bool EXT> int add_reads_partition_t(kmr_handle *h, const ReadsV
 int add_reads_partition(kmr_handle *h, const ReadsView &rv, uint64_t total_bases) { return with_w_ext(h, [&](auto W, auto EXT) { return add_reads_partition_t<W(), EXT()>(h, rv, total_bases); }); }
 
 /* chunk CSR of a pool: list_start[nl+1] (device) and list_chunks[n_chunks] (device) */
-int build_csr(kmr_handle *h, HostPool &p, uint64_t nl, uint32_t first, uint64_t **list_start, uint64_t **list_chunks, uint32_t *n_chunks_out) {
+/* ... by the radix partition of the (list, chunk) pairs (csr_bin_*_kernel in kmr_partition.hpp): four launches, no device atomic per chunk */
+int build_csr_partition(kmr_handle *h, HostPool &p, uint64_t nl, uint32_t first, unsigned int used, uint64_t *list_start, uint64_t *list_chunks) {
+	const uint32_t width = (uint32_t)((nl + CSRP_BINS - 1) / CSRP_BINS), nbins = (uint32_t)((nl + width - 1) / width);
+	uint32_t *bins, *pair_list; uint64_t *pair_val;      /* bins: counts, cursors, starts (+ 1) */
+	{ int arc = arena_get(h, &bins, 3 * (size_t)CSRP_BINS + 1); if (arc) return arc; arc = arena_get(h, &pair_list, std::max<unsigned>(used, 1)); if (arc) return arc;
+	  arc = arena_get(h, &pair_val, std::max<unsigned>(used, 1)); if (arc) return arc; }
+	uint32_t *bin_count = bins, *bin_cursor = bins + CSRP_BINS, *bin_start = bins + 2 * CSRP_BINS;
+	const uint32_t *cl = p.chunk_list.get<uint32_t>() + first, *cc = p.chunk_count.get<uint32_t>() + first;
+	const unsigned grid = (unsigned)(((uint64_t)used + CSRP_TILE - 1) / CSRP_TILE);
+	const uint64_t magic = csrp_magic(width);
+	HIPCHK(h, hipMemsetAsync(bin_count, 0, 4 * CSRP_BINS, h->stream));
+	if (used) hipLaunchKernelGGL(csr_bin_hist_kernel, dim3(grid), dim3(CSRP_THREADS), 0, h->stream, cl, used, (uint32_t)nl, magic, nbins, bin_count);
+	hipLaunchKernelGGL(csr_bin_scan_kernel, dim3(1), dim3(CSRP_BINS), 0, h->stream, bin_count, nbins, bin_start, bin_cursor);
+	if (used) hipLaunchKernelGGL(csr_bin_scatter_kernel, dim3(grid), dim3(CSRP_THREADS), 0, h->stream, cl, cc, used, first, (uint32_t)nl, magic, nbins, bin_cursor, pair_list, pair_val);
+	HIPCHK(h, hipFuncSetAttribute((const void *)csr_bin_place_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * width)));
+	hipLaunchKernelGGL(csr_bin_place_kernel, dim3(nbins), dim3(CSRP_PLACE_THREADS), 4 * (size_t)width, h->stream, bin_start, pair_list, pair_val, (uint32_t)nl, width, nbins, list_start, list_chunks);
+	HIPCHK(h, hipGetLastError());
+	return 0;
+}
+/* head_seen: the pool's head where the caller has it from a wait of its own (sync_state) and nothing has taken a chunk since; without
+ * it the head is fetched here, which is this function's only wait. */
+int build_csr(kmr_handle *h, HostPool &p, uint64_t nl, uint32_t first, uint64_t **list_start, uint64_t **list_chunks, uint32_t *n_chunks_out, const unsigned int *head_seen = nullptr) {
 	unsigned int used = 0;
-	HIPCHK(h, hipStreamSynchronize(h->stream));
-	HIPCHK(h, hipMemcpy(&used, p.head.get<unsigned int>(), 4, hipMemcpyDeviceToHost));
+	if (head_seen) used = *head_seen;
+	else { HIPCHK(h, hipMemcpyAsync(&used, p.head.get<unsigned int>(), 4, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream)); }
 	if (used > p.cap) used = p.cap;
 	used = used > first ? used - first : 0;            /* only chunks [first, head) are looked at */
-	uint32_t *cnt;
-	{ int arc = arena_get(h, &cnt, nl); if (arc) return arc; arc = arena_get(h, list_start, nl + 1); if (arc) return arc;
-	  arc = arena_get(h, list_chunks, std::max<unsigned>(used, 1)); if (arc) return arc; }
-	HIPCHK(h, hipMemsetAsync(cnt, 0, 4 * nl, h->stream));
-	const unsigned csr_grid = (unsigned)(((uint64_t)used + CSR_THREADS * CSR_ITEMS - 1) / (CSR_THREADS * CSR_ITEMS));
-	if (used) hipLaunchKernelGGL(chunk_hist_kernel, dim3(csr_grid), dim3(CSR_THREADS), 0, h->stream, p.chunk_list.get<uint32_t>() + first, used, cnt, (uint32_t)nl);
-	int rc = exclusive_scan(h, cnt, nl, *list_start); if (rc) return rc;
-	HIPCHK(h, hipMemsetAsync(cnt, 0, 4 * nl, h->stream));
-	if (used) hipLaunchKernelGGL(chunk_scatter_kernel, dim3(csr_grid), dim3(CSR_THREADS), 0, h->stream, p.chunk_list.get<uint32_t>() + first, p.chunk_count.get<uint32_t>() + first, used, first, *list_start, cnt, *list_chunks, (uint32_t)nl);
-	HIPCHK(h, hipGetLastError());
+	const bool by_partition = h->tune.csr_partition && nl >= 1 && nl <= CSRP_MAX_LISTS;
+	h->last_csr_path = by_partition ? 1 : 0; h->last_csr_chunks = used;
+	{ int arc = arena_get(h, list_start, nl + 1); if (arc) return arc; arc = arena_get(h, list_chunks, std::max<unsigned>(used, 1)); if (arc) return arc; }
+	if (by_partition) { int rc = build_csr_partition(h, p, nl, first, used, *list_start, *list_chunks); if (rc) return rc; }
+	else {
+		uint32_t *cnt;
+		{ int arc = arena_get(h, &cnt, nl); if (arc) return arc; }
+		HIPCHK(h, hipMemsetAsync(cnt, 0, 4 * nl, h->stream));
+		const unsigned csr_grid = (unsigned)(((uint64_t)used + CSR_THREADS * CSR_ITEMS - 1) / (CSR_THREADS * CSR_ITEMS));
+		if (used) hipLaunchKernelGGL(chunk_hist_kernel, dim3(csr_grid), dim3(CSR_THREADS), 0, h->stream, p.chunk_list.get<uint32_t>() + first, used, cnt, (uint32_t)nl);
+		int rc = exclusive_scan_queue(h, cnt, nl, *list_start); if (rc) return rc;
+		HIPCHK(h, hipMemsetAsync(cnt, 0, 4 * nl, h->stream));
+		if (used) hipLaunchKernelGGL(chunk_scatter_kernel, dim3(csr_grid), dim3(CSR_THREADS), 0, h->stream, p.chunk_list.get<uint32_t>() + first, p.chunk_count.get<uint32_t>() + first, used, first, *list_start, cnt, *list_chunks, (uint32_t)nl);
+		HIPCHK(h, hipGetLastError());
+	}
 	*n_chunks_out = used;
 	if (dbg()) {
 		unsigned long long hv[2] = {0, 0};
@@ -1377,21 +1416,27 @@ void sk_weight_of_quality(const kmr_handle *h, unsigned int q, bool &lean, float
 	else if (h->hP[q] > 0.0) { lean = true; wK = (float)h->hPk[q]; }
 }
 /* Do all k-mers without an N of these reads weigh the same (no qualities, or one quality character throughout)?  Then wK is that
- * weight and sk_extract_lean_kernel may take the launch. */
-int sk_uniform_weight(kmr_handle *h, const ReadsView &rv, const FeedHints &hints, bool &lean, float &wK) {
+ * weight and sk_extract_lean_kernel may take the launch.
+ * longest (may be NULL): where the answer takes a pass over the quality bytes, the pass also finds the longest read and its one wait
+ * serves both; *have_longest says whether it did (prepare_units then has nothing to ask the device). */
+int sk_uniform_weight(kmr_handle *h, const ReadsView &rv, const FeedHints &hints, bool &lean, float &wK, unsigned int *longest = nullptr, bool *have_longest = nullptr) {
 	lean = false; wK = 1.0f;
+	if (have_longest) *have_longest = false;
 	if (h->tune.no_lean_extract) return 0;
 	if (!rv.quals && hints.uniform_q < 0) { lean = true; return 0; }
 	if (h->qual_mixed || rv.n_reads == 0) return 0;
 	if (hints.uniform_q >= 0) { sk_weight_of_quality(h, (unsigned int)hints.uniform_q, lean, wK); return 0; }      /* the caller said so (kmr_add_reads_twobit*): no pass over the quality bytes, no round trip */
-	{ int rc = h->qrange.reserve(h, "qrange", 8); if (rc) return rc; }
-	const unsigned int init[2] = {255u, 0u};
-	HIPCHK(h, hipMemcpyAsync(h->qrange.get<unsigned int>(), init, 8, hipMemcpyHostToDevice, h->stream));
-	hipLaunchKernelGGL(sk_qual_range_kernel, dim3(num_cus(h) * 8), dim3(256), 0, h->stream, rv.quals, rv.offsets, rv.n_reads, h->qrange.get<unsigned int>());
+	const int QR_MAX = 32;      /* word of the longest read: 128 bytes behind the characters' pair, away from their atomics */
+	{ int rc = h->qrange.reserve(h, "qrange", 4 * (QR_MAX + 1)); if (rc) return rc; }
+	unsigned int got[QR_MAX + 1] = {255u, 0u};      /* lowest, highest character; ...; longest read */
+	HIPCHK(h, hipMemcpyAsync(h->qrange.get<unsigned int>(), got, sizeof(got), hipMemcpyHostToDevice, h->stream));
+	/* half a block per CU of the launch's eight walks the offsets (a C2 batch: 80 MB of them beside 1.5 GB of qualities) */
+	const unsigned qr_blocks = (unsigned)num_cus(h) * 8, len_blocks = longest ? (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(qr_blocks / 16, (rv.n_reads + 4095) / 4096)) : 0u;
+	hipLaunchKernelGGL(sk_qual_range_kernel, dim3(qr_blocks), dim3(256), 0, h->stream, rv.quals, rv.offsets, rv.n_reads, h->qrange.get<unsigned int>(), h->qrange.get<unsigned int>() + QR_MAX, len_blocks);
 	HIPCHK(h, hipGetLastError());
-	unsigned int got[2] = {0, 0};
-	HIPCHK(h, hipMemcpyAsync(got, h->qrange.get<unsigned int>(), 8, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipMemcpyAsync(got, h->qrange.get<unsigned int>(), sizeof(got), hipMemcpyDeviceToHost, h->stream));
 	HIPCHK(h, hipStreamSynchronize(h->stream));
+	if (longest) { *longest = got[QR_MAX]; *have_longest = true; }
 	if (got[0] != got[1]) { h->qual_mixed = got[0] < got[1]; return 0; }      /* (255 > 0: no quality byte at all) */
 	sk_weight_of_quality(h, got[0], lean, wK);
 	return 0;
@@ -1519,18 +1564,20 @@ template <int W> int add_reads_superkmer_t(kmr_handle *h, const ReadsView &rvAll
 	const DevParams dp = dev_params(h);
 	const bool filt = sk_build_filters(h, dp), tracking = h->cfg.size_tracker && n;
 	bool lean = false; float wK = 1.0f; int rc = 0;
-	if (!filt && !h->ext && !sp_debug_extract(h)) { rc = sk_uniform_weight(h, rvAll, hints, lean, wK); if (rc) return rc; }      /* (extension values want every neighbour's quality: the general kernel) */
-	if (hints.packed && (!lean || h->cfg.size_tracker)) return fail(h, KMR_ERR_STATE, "internal: a packed batch handed to an extraction that wants text");      /* (sk_packed_direct_ok said otherwise) */
-	if (n) sk_note_call_weight(h, lean, wK);
-	if (!h->sk_state) { rc = sk_size_lists<W>(h, std::max<uint64_t>(total_bases, hints.call_bases), lean); if (rc) return rc; }
 	const uint64_t avg = n ? std::max<uint64_t>(1, total_bases / n) : 1;
 	const uint64_t sub_bases = h->tune.sub_batch_bases ? h->tune.sub_batch_bases : (1ull << 31);
 	const uint64_t chunk = std::max<uint64_t>(64, (sub_bases / avg) & ~63ull);
+	/* one sub-batch: the call's longest read is the batch's, and the pass over the qualities (where one runs) brings it along */
+	unsigned int longest = 0; bool have_longest = false;
+	if (!filt && !h->ext && !sp_debug_extract(h)) { rc = sk_uniform_weight(h, rvAll, hints, lean, wK, n <= chunk ? &longest : nullptr, &have_longest); if (rc) return rc; }      /* (extension values want every neighbour's quality: the general kernel) */
+	if (hints.packed && (!lean || h->cfg.size_tracker)) return fail(h, KMR_ERR_STATE, "internal: a packed batch handed to an extraction that wants text");      /* (sk_packed_direct_ok said otherwise) */
+	if (n) sk_note_call_weight(h, lean, wK);
+	if (!h->sk_state) { rc = sk_size_lists<W>(h, std::max<uint64_t>(total_bases, hints.call_bases), lean); if (rc) return rc; }
 	if (tracking) { h->trk_n = 0; rc = h->trk.reserve(h, "trk", n * sizeof(SkTrackRec)); if (rc) return rc; HIPCHK(h, hipMemsetAsync(h->trk.get<SkTrackRec>(), 0, n * sizeof(SkTrackRec), h->stream)); }      /* (sk_track_call) */
 	for (uint64_t r = 0; r < n; r += chunk) {
 		const uint64_t m = std::min(chunk, n - r);
 		ReadsView rv = reads_slice(rvAll, r, m);
-		rc = prepare_units(h, rv, hints.packed ? SK_PACKED_SPAN : (uint32_t)TILE_SPAN); if (rc) return rc;
+		rc = prepare_units(h, rv, hints.packed ? SK_PACKED_SPAN : (uint32_t)TILE_SPAN, have_longest ? &longest : nullptr); if (rc) return rc;
 		if (r == 0) sk_presize_pool(h, hints.call_bases, total_bases, avg, lean);
 		rc = pool_reserve(h, h->l1, sk_launch_chunks(h, m * avg + avg), true); if (rc) return rc;
 		TimeSpan tb(h, KMR_TIME_BUILD), te(h, KMR_TIME_EXTRACT);
@@ -1905,7 +1952,7 @@ template <int W> int sk_append_early(kmr_handle *h, SkFinalize<W> &p) {
 }
 
 template <int W> int finalize_superkmer_t(kmr_handle *h, uint32_t min_depth) {
-	int rc = sync_state(h);
+	int rc = sync_state(h, true);
 	if (rc) return rc;
 	TimeSpan whole(h, KMR_TIME_FINALIZE);
 	const uint64_t G = h->stats.raw_good_kmers;
@@ -1923,7 +1970,7 @@ template <int W> int finalize_superkmer_t(kmr_handle *h, uint32_t min_depth) {
 	}
 	p.refined = h->sk_state && h->sk_fine_shift > 0;
 	if (p.refined) { rc = sk_refine_lists(h, p.nl); if (rc) return rc; }
-	rc = build_csr(h, h->l1, p.nl, 0, &p.ls, &p.lc, &p.nch); if (rc) return rc;
+	rc = build_csr(h, h->l1, p.nl, 0, &p.ls, &p.lc, &p.nch, p.refined ? nullptr : &h->l1_head_seen); if (rc) return rc;      /* (refining takes chunks) */
 	/* entry buffers: sequencing data keeps a few per cent of its k-mers as weak entries */
 	rc = count_entry_buffers(h, p, G, sk_entry_slack(h), G / (p.f.has_singletons ? 8 : 3), G / 3, h->sk_exchange && h->cfg.world_size > 1); if (rc) return rc;
 	rc = sk_count_uniform<W>(h, p.tracking, p.uni, p.f.uni_wbits); if (rc) return rc;
@@ -1969,7 +2016,7 @@ template <int W> int finalize_superkmer_t(kmr_handle *h, uint32_t min_depth) {
  * over.  Direction-counting values without a singleton map in the result (min_depth >= 2 or no separate singletons), fine lists only;
  * anything else, or buffers that turn out too small, leaves the lists to kmr_finalize. */
 template <int W> int count_prefix_superkmer_t(kmr_handle *h, uint32_t min_depth, uint64_t hi) {
-	int rc = sync_state(h); if (rc) return rc;
+	int rc = sync_state(h, true); if (rc) return rc;
 	FinalizeParams f = finalize_params(h, min_depth);
 	const bool keepSing = f.has_singletons && min_depth <= 1;
 	h->early.active = false;      /* an earlier early count is replaced */
@@ -1981,7 +2028,7 @@ template <int W> int count_prefix_superkmer_t(kmr_handle *h, uint32_t min_depth,
 	hipLaunchKernelGGL(sk_close_kernel, dim3(grid_for(nl)), dim3(256), 0, h->stream, h->sk_state.get<unsigned long long>(), nl, h->l1.chunk_count.get<uint32_t>(), h->l1.cap);
 	HIPCHK(h, hipGetLastError());
 	uint64_t *ls = nullptr, *lc = nullptr; uint32_t nch = 0;
-	rc = build_csr(h, h->l1, nl, 0, &ls, &lc, &nch); if (rc) return rc;
+	rc = build_csr(h, h->l1, nl, 0, &ls, &lc, &nch, &h->l1_head_seen); if (rc) return rc;
 	/* room: the share of the good k-mers that lies below hi, at the rate kmr_finalize starts with.  Too little (low coverage, or an
 	 * owner whose lists hold more than its own reads' share) sets ERR_ENTRIES_FULL in the early pass's own error word, which only
 	 * kmr_finalize reads: it voids the early count and counts every list itself (kmr_build_info "early_overflowed") */
@@ -2251,6 +2298,7 @@ int kmr_tune(kmr_handle *h, const char *knob, double value) {
 	else if (k == "dump_piece_bytes") h->tune.dump_piece_bytes = value >= 1 ? (uint64_t)value : 0;
 	else if (k == "narrow_tallies") h->tune.no_narrow = value == 0;
 	else if (k == "keep_level1_state") h->tune.no_l1_state = value == 0;
+	else if (k == "csr_partition") h->tune.csr_partition = value != 0;
 	else if (k == "superkmer_window") {      /* largest minimizer window the geometry may take (32 / 16 / 8 / 4): A/B runs, tests of the narrower windows at large k */
 		if (h->superkmer_mode && !h->sk_state) { uint32_t w, m, o; if (!sk_geometry(h->k, 0, w, m, o, (uint32_t)value)) return fail(h, KMR_ERR_INVALID_ARG, "no minimizer geometry under that window"); h->sk_win = w; h->sk_m = m; h->sk_off = o; }
 	}
@@ -2277,6 +2325,9 @@ int kmr_build_info(kmr_handle *h, const char *what, double *value) {
 	else if (k == "saturated_keys") *value = (double)h->last_saturated_keys;
 	else if (k == "saturated_batches") *value = (double)h->last_saturated_batches;
 	else if (k == "count_attempts") *value = (double)h->last_count_attempts;
+	else if (k == "csr_path") *value = (double)h->last_csr_path;
+	else if (k == "csr_chunks") *value = (double)h->last_csr_chunks;
+	else if (k == "unit_batches") *value = (double)h->unit_batches;
 	else if (k == "device_blocks_live") *value = (double)g_blocks_live.load();
 	else if (k == "filter_score_ms") *value = h->last_score_ms;
 	else if (k == "select_ms") *value = h->last_select_ms;

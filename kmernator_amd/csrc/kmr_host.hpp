@@ -187,6 +187,7 @@ struct KMR_HIDDEN Tuning {
 	int artifact_report_lds = -1;      /* kmr_artifact_filter_report*: where the per-sequence counters are summed (-1: in LDS while they fit ART_REPORT_LDS_CAP; tests: 0 = global atomics, 1 = LDS up to ART_REPORT_LDS_MOST) */
 	uint32_t pair_hash_bits = 64;      /* kmr_identify_pairs*: bits of the common name's hash the phase-2 sort keys keep (tests: a few bits, so that distinct names share a key) */
 	int bimodal_window = -1;           /* bimodal_trim_kernel: the longest run it stages in LDS (-1: BM_CAP; tests: 0, so that every run is walked in global memory) */
+	bool csr_partition = true;         /* build_csr: the chunk CSR by the radix partition of csr_bin_*_kernel (default) or, 0, by chunk_hist_kernel / chunk_scatter_kernel's atomic per chunk (A/B runs, tests of both, and what more than 2^24 lists take) */
 	bool no_coarse_lists = true;       /* exchange: scatter into the job's fine lists (default) or, kmr_tune("coarse_lists", 1), into coarse ones that the owner splits before the count pass (sk_refine_kernel: not yet fast enough to pay) */
 };
 
@@ -261,6 +262,9 @@ struct KMR_HIDDEN kmr_handle : HandleMem, BuildMem, ExchangeMem {
 	double last_dedup_ms = 0, last_dedup_key_ms = 0, last_dedup_sort_ms = 0, last_dedup_consensus_ms = 0;      /* the last kmr_dedup_fragments*: the whole call, its key kernel, its radix sorts, its consensus kernel (HIP events, taken with kmr_tune "dedup_timing" only; kmr_build_info) */
 	uint64_t last_pair_hash_collisions = 0;      /* ... and how many of its runs of equal hash keys held more than one distinct common name */
 	uint64_t last_saturated_keys = 0, last_saturated_batches = 0;      /* what the last kmr_finalize's saturated-key pass redid, in how many batches */
+	int last_csr_path = -1; uint32_t last_csr_chunks = 0;      /* the last build_csr: 1 = radix partition, 0 = an atomic per chunk, and the chunks it looked at (kmr_build_info "csr_path", "csr_chunks") */
+	unsigned int l1_head_seen = 0;     /* the record pool's head as of the last sync_state(h, true) */
+	uint64_t unit_batches = 0;         /* batches that held a read longer than a tile and were cut into work units (kmr_build_info "unit_batches") */
 	int last_count_attempts = 0;       /* how often the last count pass of a kmr_finalize ran before its entries fit (kmr_build_info "count_attempts") */
 	bool qual_mixed = false;           /* a build that has seen two different quality characters stops asking (qrange) */
 	/* exchange with world_size > 1: sk_bits are the COARSE lists reads are scattered into and that travel; each holds 2^sk_fine_shift

@@ -129,18 +129,25 @@ struct ReadsView {
 };
 
 static const uint32_t UNIT_KMERS = 9216;     /* k-mers per segment: 9 * 1024, and 9216 + 127 bases fit a tile */
+/* the longest read of a batch (capped at 2^32 - 1): all that the usual batch, whose reads are one unit each, is asked */
 #ifndef KMR_INSTANCE_TU
-__global__ void unit_count_kernel(const uint64_t *offsets, uint64_t n, uint32_t k, uint32_t span, uint32_t *counts, unsigned int *maxLen) {
+__global__ void unit_max_kernel(const uint64_t *offsets, uint64_t n, unsigned int *maxLen) {
 	unsigned int mx = 0;
 	for (uint64_t r = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; r < n; r += (uint64_t)gridDim.x * blockDim.x) {
 		const uint64_t L = offsets[r + 1] - offsets[r];
 		mx = L > mx ? (unsigned int)(L > 0xffffffffull ? 0xffffffffu : L) : mx;
-		counts[r] = L <= span ? 1u : (uint32_t)((L - k + 1 + UNIT_KMERS - 1) / UNIT_KMERS);
 	}
 #pragma unroll
 	for (int off = 32; off > 0; off >>= 1) { unsigned int o = __shfl_xor(mx, off, 64); mx = o > mx ? o : mx; }
 	/* one word serves ~90 M atomics/s: only a wavefront that would raise the maximum it can see touches it */
 	if ((threadIdx.x & 63) == 0 && mx > __hip_atomic_load(maxLen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(maxLen, mx);
+}
+/* units per read, for a batch that holds a read longer than `span` */
+__global__ void unit_count_kernel(const uint64_t *offsets, uint64_t n, uint32_t k, uint32_t span, uint32_t *counts) {
+	for (uint64_t r = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; r < n; r += (uint64_t)gridDim.x * blockDim.x) {
+		const uint64_t L = offsets[r + 1] - offsets[r];
+		counts[r] = L <= span ? 1u : (uint32_t)((L - k + 1 + UNIT_KMERS - 1) / UNIT_KMERS);
+	}
 }
 #endif
 #ifndef KMR_INSTANCE_TU

@@ -696,6 +696,118 @@ void chunk_scatter_kernel(const uint32_t *chunk_list, const uint32_t *chunk_coun
 }
 #endif
 
+/* The same CSR without a device atomic per chunk (kmr_tune "csr_partition", the default; the two kernels above are the other path):
+ * with 10^6 lists the per-list counters no longer fit a block's LDS, and hist + scatter each made one device atomic per chunk.
+ * Here the (list, chunk | count << 32) pairs are radix-partitioned by list: bins of `width` = ceil(nl / 1024) neighbouring lists
+ * (at most CSRP_BINS of them), ranked in LDS tile by tile as bb_scatter_* ranks entries --
+ *   csr_bin_hist_kernel     chunks per bin: a tile of CSRP_TILE chunks counted in LDS, one device atomic per (tile, non-empty bin)
+ *   csr_bin_scan_kernel     where every bin starts (one block; it also sets the cursors the next kernel bumps)
+ *   csr_bin_scatter_kernel  the pairs to their bins, ranked in LDS, one returning atomic per (tile, non-empty bin)
+ *   csr_bin_place_kernel    one block per bin: chunks per list in LDS (width <= 2^14 counters for nl <= CSRP_MAX_LISTS), block scan,
+ *                           list_start[] of the bin's lists, every pair through the LDS cursors to its place in list_chunks[]
+ * A bin of any size is walked by its block in strides with the same LDS counters: a list that owns most of a bin is only slower.
+ * Chunks of no list (NO_CHUNK) or of a list >= nl are skipped; the order of a list's chunks is arbitrary, as it is above. */
+static const int CSRP_BINS = 1024, CSRP_THREADS = 1024, CSRP_ITEMS = 8, CSRP_TILE = CSRP_THREADS * CSRP_ITEMS, CSRP_PLACE_THREADS = 1024;
+static const uint64_t CSRP_MAX_LISTS = 1ull << 24;      /* more lists take the other path */
+/* list / width without a divide: magic = 2^40 / width + 1 is exact for list < 2^24 and width <= 2^14 (the error term list * (magic * width - 2^40)
+ * stays below 2^38, and the product below 2^64) */
+__host__ __device__ __forceinline__ uint64_t csrp_magic(uint32_t width) { return (1ull << 40) / width + 1; }
+__device__ __forceinline__ uint32_t csrp_bin(uint32_t l, uint64_t magic) { return (uint32_t)(((uint64_t)l * magic) >> 40); }
+/* exclusive scan of one value per thread over the block (whole wavefronts, at most 16 of them); ws: 17 words of LDS */
+__device__ __forceinline__ uint32_t csrp_block_scan(uint32_t v, uint32_t *ws, uint32_t &total) {
+	const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+	uint32_t inc = v;
+#pragma unroll
+	for (int o = 1; o < 64; o <<= 1) { const uint32_t u = __shfl_up(inc, o, 64); if (lane >= o) inc += u; }
+	if (lane == 63) ws[w] = inc;
+	__syncthreads();
+	if (threadIdx.x == 0) { uint32_t s = 0; for (int i = 0; i < nw; i++) { const uint32_t x = ws[i]; ws[i] = s; s += x; } ws[16] = s; }
+	__syncthreads();
+	const uint32_t r = ws[w] + inc - v;
+	total = ws[16];
+	__syncthreads();
+	return r;
+}
+#ifndef KMR_INSTANCE_TU
+__global__ __launch_bounds__(CSRP_THREADS)
+void csr_bin_hist_kernel(const uint32_t *chunk_list, uint32_t n_chunks, uint32_t nl, uint64_t magic, uint32_t nbins, uint32_t *bin_count) {
+	__shared__ uint32_t lh[CSRP_BINS];
+	for (uint32_t i = threadIdx.x; i < (uint32_t)CSRP_BINS; i += CSRP_THREADS) lh[i] = 0;
+	__syncthreads();
+	const uint64_t base = (uint64_t)blockIdx.x * CSRP_TILE;
+#pragma unroll
+	for (int j = 0; j < CSRP_ITEMS; j++) {
+		const uint64_t c = base + (uint64_t)j * CSRP_THREADS + threadIdx.x;
+		const uint32_t l = c < n_chunks ? chunk_list[c] : NO_CHUNK;
+		if (l != NO_CHUNK && l < nl) atomicAdd(&lh[csrp_bin(l, magic)], 1u);
+	}
+	__syncthreads();
+	for (uint32_t i = threadIdx.x; i < nbins; i += CSRP_THREADS) if (lh[i]) atomicAdd(&bin_count[i], lh[i]);
+}
+__global__ __launch_bounds__(CSRP_BINS)
+void csr_bin_scan_kernel(const uint32_t *bin_count, uint32_t nbins, uint32_t *bin_start /* nbins + 1 */, uint32_t *bin_cursor) {
+	__shared__ uint32_t ws[17];
+	const uint32_t t = threadIdx.x, v = t < nbins ? bin_count[t] : 0u;
+	uint32_t total;
+	const uint32_t s = csrp_block_scan(v, ws, total);
+	if (t < nbins) { bin_start[t] = s; bin_cursor[t] = s; }
+	if (t == 0) bin_start[nbins] = total;
+}
+__global__ __launch_bounds__(CSRP_THREADS)
+void csr_bin_scatter_kernel(const uint32_t *chunk_list, const uint32_t *chunk_count, uint32_t n_chunks, uint32_t first, uint32_t nl, uint64_t magic,
+                            uint32_t nbins, uint32_t *bin_cursor, uint32_t *pair_list, uint64_t *pair_val) {
+	__shared__ uint32_t lh[CSRP_BINS];
+	for (uint32_t i = threadIdx.x; i < (uint32_t)CSRP_BINS; i += CSRP_THREADS) lh[i] = 0;
+	__syncthreads();
+	const uint64_t base = (uint64_t)blockIdx.x * CSRP_TILE;
+	uint32_t myl[CSRP_ITEMS], myb[CSRP_ITEMS], myr[CSRP_ITEMS];
+#pragma unroll
+	for (int j = 0; j < CSRP_ITEMS; j++) {
+		const uint64_t c = base + (uint64_t)j * CSRP_THREADS + threadIdx.x;
+		uint32_t l = c < n_chunks ? chunk_list[c] : NO_CHUNK;
+		if (l >= nl) l = NO_CHUNK;
+		myl[j] = l; myb[j] = 0; myr[j] = 0;
+		if (l != NO_CHUNK) { myb[j] = csrp_bin(l, magic); myr[j] = atomicAdd(&lh[myb[j]], 1u); }      /* rank inside the tile */
+	}
+	__syncthreads();
+	for (uint32_t i = threadIdx.x; i < nbins; i += CSRP_THREADS) { const uint32_t n = lh[i]; lh[i] = n ? atomicAdd(&bin_cursor[i], n) : 0u; }      /* the tile's place in the bin */
+	__syncthreads();
+#pragma unroll
+	for (int j = 0; j < CSRP_ITEMS; j++) {
+		const uint32_t l = myl[j];
+		if (l == NO_CHUNK) continue;
+		const uint64_t c = base + (uint64_t)j * CSRP_THREADS + threadIdx.x;
+		const uint32_t pos = lh[myb[j]] + myr[j];
+		pair_list[pos] = l;
+		pair_val[pos] = ((uint64_t)chunk_count[c] << 32) | (c + first);      /* chunk_list/chunk_count point at chunk `first` */
+	}
+}
+__global__ __launch_bounds__(CSRP_PLACE_THREADS)
+void csr_bin_place_kernel(const uint32_t *bin_start, const uint32_t *pair_list, const uint64_t *pair_val, uint32_t nl, uint32_t width, uint32_t nbins,
+                          uint64_t *list_start /* nl + 1 */, uint64_t *list_chunks) {
+	extern __shared__ __attribute__((aligned(16))) uint32_t csrp_cnt[];      /* width words */
+	__shared__ uint32_t ws[17];
+	const uint32_t b = blockIdx.x, t = threadIdx.x, l0 = b * width, w = nl - l0 < width ? nl - l0 : width;
+	const uint32_t bs = bin_start[b], be = bin_start[b + 1];
+	for (uint32_t j = t; j < w; j += CSRP_PLACE_THREADS) csrp_cnt[j] = 0;
+	__syncthreads();
+	for (uint32_t i = bs + t; i < be; i += CSRP_PLACE_THREADS) atomicAdd(&csrp_cnt[pair_list[i] - l0], 1u);
+	__syncthreads();
+	/* every thread scans a run of neighbouring lists; the counters become the lists' cursors inside the bin */
+	const uint32_t seg = (w + CSRP_PLACE_THREADS - 1) / CSRP_PLACE_THREADS, j0 = t * seg < w ? t * seg : w, j1 = j0 + seg < w ? j0 + seg : w;
+	uint32_t s = 0, total;
+	for (uint32_t j = j0; j < j1; j++) s += csrp_cnt[j];
+	uint32_t run = csrp_block_scan(s, ws, total);
+	for (uint32_t j = j0; j < j1; j++) { const uint32_t n = csrp_cnt[j]; csrp_cnt[j] = run; list_start[(uint64_t)l0 + j] = (uint64_t)bs + run; run += n; }
+	if (b == nbins - 1 && t == 0) list_start[nl] = be;
+	__syncthreads();
+	for (uint32_t i = bs + t; i < be; i += CSRP_PLACE_THREADS) {
+		const uint32_t pos = atomicAdd(&csrp_cnt[pair_list[i] - l0], 1u);
+		list_chunks[(uint64_t)bs + pos] = pair_val[i];
+	}
+}
+#endif
+
 /* debugging aid (KMR_DEBUG): records held by a pool */
 #ifndef KMR_INSTANCE_TU
 __global__ void pool_records_kernel(const uint32_t *chunk_list, const uint32_t *chunk_count, uint32_t n_chunks, unsigned long long *total, unsigned long long *nvalid) {

@@ -1082,16 +1082,35 @@ static const size_t SKL_EXTRACT_SMEM = (size_t)SKL_WAVES * SKL_WAVE_LDS;
 
 /* Are the quality characters of the reads offsets[0] .. offsets[n_reads] all the same one?  range[0] gets a lower bound of the smallest
  * and range[1] an upper bound of the largest (the bytes of the AND and of the OR of all dwords: two instructions a dword instead of
- * a minimum and a maximum per byte), equal -- and then exact -- iff one character fills the range; 255 / 0 are left alone when there is none */
+ * a minimum and a maximum per byte), equal -- and then exact -- iff one character fills the range; 255 / 0 are left alone when there is none.
+ * umax (may be NULL; a word on a cache line of its own): the launch also takes the longest read into it, max(offsets[r + 1] - offsets[r]) capped
+ * at 2^32 - 1 -- what prepare_units asks of a batch, so that a call that needs both answers runs one kernel and waits once.  Its first
+ * len_blocks blocks walk the offsets in a grid-stride loop of their own while the others read the qualities (a loop over the offsets behind
+ * every thread's quality loop ran when the memory pipes had drained: 0.38 -> 0.66 ms on a C2 batch). */
 #ifndef KMR_INSTANCE_TU
 __global__ __launch_bounds__(256)
-void sk_qual_range_kernel(const uint8_t *quals, const uint64_t *offsets, uint64_t n_reads, unsigned int *range) {
+void sk_qual_range_kernel(const uint8_t *quals, const uint64_t *offsets, uint64_t n_reads, unsigned int *range, unsigned int *umax, uint32_t len_blocks) {
+	if (blockIdx.x < len_blocks) {
+		const uint64_t lt = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x, ln = (uint64_t)len_blocks * blockDim.x;
+		unsigned int mx = 0;
+		for (uint64_t r0 = lt; r0 < n_reads; r0 += 4 * ln) {
+			uint64_t L[4];
+#pragma unroll
+			for (int u = 0; u < 4; u++) { const uint64_t r = r0 + (uint64_t)u * ln, rr = r < n_reads ? r : r0; L[u] = offsets[rr + 1] - offsets[rr]; }
+#pragma unroll
+			for (int u = 0; u < 4; u++) mx = L[u] > mx ? (unsigned int)(L[u] > 0xffffffffull ? 0xffffffffu : L[u]) : mx;
+		}
+		for (int o = 32; o > 0; o >>= 1) { const unsigned int a = (unsigned int)__shfl_xor((int)mx, o, 64); mx = a > mx ? a : mx; }
+		/* (one word serves few atomics: only a wavefront that would raise the maximum it can see touches it, as in unit_max_kernel) */
+		if ((threadIdx.x & 63) == 0 && mx > __hip_atomic_load(umax, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(umax, mx);
+		return;
+	}
 	unsigned int lo = 255, hi = 0;
 	uint32_t all = 0xffffffffu, any = 0u;
 	const uint64_t b0 = offsets[0], b1 = offsets[n_reads];
 	const uintptr_t p0 = (uintptr_t)(quals + b0), p1 = (uintptr_t)(quals + b1);
 	const uintptr_t a0 = (p0 + 15) & ~(uintptr_t)15, a1 = p1 & ~(uintptr_t)15;      /* the 16-byte aligned middle */
-	const uint64_t tid = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x, nthreads = (uint64_t)gridDim.x * blockDim.x;
+	const uint64_t tid = (blockIdx.x - len_blocks) * (uint64_t)blockDim.x + threadIdx.x, nthreads = (uint64_t)(gridDim.x - len_blocks) * blockDim.x;
 	if (a0 < a1) {
 		const uint4 *q4 = (const uint4 *)a0;
 		const uint64_t n16 = (a1 - a0) / 16;
