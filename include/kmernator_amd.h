@@ -1097,6 +1097,64 @@ void kmr_dedup_free(kmr_dedup *d);
  * answered from the 39 doubles at which that expression steps -- the table the device compares against.  prob >= 0.  Needs no device. */
 char kmr_consensus_qual(double prob);
 
+/* ---- CompareSpectrums (apps/CompareSpectrums.cpp): the distinct k-mers and the k-mer occurrences two read sets share ----
+ *
+ * The reference builds both spectra solid-only with TrackingDataMinimal4 (src/KmerTrackingData.h:1132-1212: every occurrence that
+ * passes TrackingData::isDiscard, f32 |weight| > min-kmer-quality, adds 1 to a u32; a k-mer over a markup weighs 0 and never passes;
+ * no singleton split, no saturation) and reports, for maps m1 and m2 (countCommonKmers :146-162, evaluate :225-242):
+ *   size1, size2                   m1.size(), m2.size()
+ *   common                         keys of m1 that m2 holds
+ *   common_count1, common_count2   sum over those keys of m1's count, and of m2's count
+ *   total_count1, total_count2     sum of all counts of m1, and of m2
+ *
+ * The map a handle stands for is what KmerSpectrum::getCount(kmer, false) answers from (src/KmerSpectrum.h:642-695): the weak entries
+ * with their u16 count, plus the singleton entries with count 1 where the handle keeps that map.  A handle built with
+ * separate_singletons 0 or 1 and finalized with min_depth <= 1 equals the reference's solid map key for key; one finalized with
+ * min_depth 2 compares what it still holds.
+ *
+ * Saturation: a stored count stops at 65535, the reference's u32 does not.  `saturated` counts the entries read, on either side, whose
+ * stored count is 65535: the figures are the reference's whenever it is 0 and lower bounds otherwise.  In the per-read form a read's
+ * own counts are exact sums; only map 2's counts can saturate, and `saturated` is the number of map 2's entries at 65535. */
+typedef struct kmr_compare_counts {
+	uint64_t size1, size2, common, common_count1, common_count2, total_count1, total_count2;
+	uint64_t saturated;
+} kmr_compare_counts;
+
+/* Set against set (evaluate :225-242): h1's map against h2's.  Both handles must be finalized (KMR_ERR_STATE), on the same device, with
+ * the same k and the same hash_kind (KMR_ERR_INVALID_ARG); either value kind is accepted, h1 == h2 is allowed, and the two maps may
+ * have different bucket counts.  Runs on h2's stream after h1's work has finished, and waits for the result. */
+int kmr_compare_spectrums(kmr_handle *h1, kmr_handle *h2, kmr_compare_counts *out);
+
+/* Every read of a batch on its own against the whole of h2's map (--per-read, evaluatePerRead :243-257, which builds a KmerSpectrum
+ * per read): read r is map 1 all by itself -- its keys the canonical k-mers of the read whose occurrences pass the weight test, a
+ * key's count the number of such occurrences --, found by the build's own extraction.  k, min_weight, min_quality_score, the quality
+ * base and the hash kind are h2's; the batch was ingested through h2 (or a handle of the same configuration), so that its qualities
+ * are on the handle's scale.  size2 and total_count2 are the same in every record; a read shorter than k gives a record of zeros apart
+ * from those two (and `saturated`).  Records are in read order.  Reads of up to 256 k-mers are answered by one wavefront each out of LDS,
+ * longer ones (contigs, genomes) through a radix sort of their (read, k-mer) pairs; the batch is walked in runs of whole reads whose
+ * k-mers fit a staging buffer (kmr_tune "compare_lds_kmers", "compare_stage_kmers"); neither changes a result.
+ * KMR_ERR_STATE before kmr_finalize; KMR_ERR_UNSUPPORTED for a handle with world_size > 1, num_parts > 1 or kmer_subsample > 1 (the
+ * owner-partitioned form adds up over ranks: not built yet), and for a read of 2^32 k-mers or more.
+ * kmr_compare_reads: per_read is host memory of n_reads records.  kmr_compare_reads_dev: dev_per_read is device memory of n_reads
+ * records, written by work queued on h2's stream (the call itself waits only for the sizes it needs: the batch's k-mers to cut the
+ * runs and, where reads take the sorted path, their number per run). */
+int kmr_compare_reads(kmr_handle *h2, const kmr_reads *set1, kmr_compare_counts *per_read);
+int kmr_compare_reads_dev(kmr_handle *h2, const kmr_reads *set1, void *dev_per_read);
+
+/* The header of CompareSpectrums' table (:211-212) is "\nSet 1\tSet 2\tCommon\t%Uniq1\t%Tot1\t%Uniq2\t%Tot2\n"; this writes one line of it
+ * (:234-241, :250-256): size1 \t size2 \t common \t P(common * 100.0 / size1) \t P(common_count1 * 100.0 / total_count1) \t
+ * P(common * 100.0 / size2) \t P(common_count2 * 100.0 / total_count2) \t label \n, P being setprecision(4) in the default float
+ * format ("%.4g").  A zero denominator is 0.0 / 0.0 at run time in the reference, which an x86-64 glibc build prints as "-nan": that
+ * is written here, whatever the host.  The label is empty in the whole form and the read's name in the per-read form.  Host only, needs
+ * no device; *bytes is the length of the line (no terminating 0 is written); KMR_ERR_CAPACITY if cap is smaller, with *bytes set. */
+int kmr_compare_line(const kmr_compare_counts *c, const char *label, uint64_t label_len, char *dst, uint64_t cap, uint64_t *bytes);
+
+/* ReadSet::circularize (src/ReadSet.cpp:120-130; CompareSpectrums --circular-reference passes extra_length = k, not k - 1, so that the
+ * first k-mer of a circular sequence is counted twice): a new batch in which every read is bases + bases[0 : min(extra_length, L)], its
+ * qualities extended the same way.  Offsets are rebuilt, the 64 bytes of padding kept, the name spans carried over; an empty read stays
+ * empty and extra_length 0 is a copy.  Free the result with kmr_reads_free. */
+int kmr_reads_circularize(kmr_handle *h, const kmr_reads *in, uint32_t extra_length, kmr_reads **out);
+
 /* Raw HIP stream of the handle (hipStream_t) so callers can order their own
  * work (torch.cuda.ExternalStream) against it. */
 void *kmr_stream(kmr_handle *h);
@@ -1134,6 +1192,9 @@ void *kmr_stream(kmr_handle *h);
  *   "csr_partition" (how kmr_finalize, kmr_count_lists_prefix and the streaming lookups find every list's chunks: 1, the default, by a radix
  *   partition of the (list, chunk) pairs, 0 by one device atomic per chunk, which builds of more than 2^24 lists take anyway; see
  *   kmr_build_info "csr_path"; may be set at any time).
+ *   "compare_lds_kmers" (kmr_compare_reads*: the most k-mers of a read that one wavefront answers out of LDS, 1 - 512; 0 sends every read
+ *   through the sorted path; anything else = the default, 256), "compare_stage_kmers" (k-mers of one run of whole reads of
+ *   kmr_compare_reads*, 0 = 2^26; a read that alone exceeds it is a run of its own); both may be set at any time.
  * Call before the first kmr_add_reads* of a build.  KMR_ERR_INVALID_ARG for an unknown knob. */
 int kmr_tune(kmr_handle *h, const char *knob, double value);
 /* What the current build decided, for tests and measurement tools (the reference logs such figures, LOG_VERBOSE): "lists" = super-k-mer

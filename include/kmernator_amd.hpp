@@ -15,6 +15,8 @@
  *     dumpCounts / dumpGraphs MeraculousDistributedKmerSpectrum            src/Meraculous.h:107-134
  *     scoreAndTrimReads       ReadSelector::scoreAndTrimReads              src/ReadSelector.h:1182-1207
  *     setBimodalSigmas        ReadSelector::_bimodalSigmas (--bimodal-sigmas) src/ReadSelector.h:981-1008
+ *     countCommonKmers        countCommonKmers + evaluate                  apps/CompareSpectrums.cpp:146-162, :225-242
+ *     compareReads            evaluatePerRead                              apps/CompareSpectrums.cpp:243-257
  *   kmernator::ReadSet        ReadSet::appendFastq... on the device        src/ReadSet.cpp:311-345
  *
  * Errors surface as kmernator::KmerSpectrumError (the reference throws LoggedException, src/Log.h:442-484).
@@ -168,6 +170,15 @@ public:
 		return h;
 	}
 	/* --bimodal-sigmas (ReadSelector::_bimodalSigmas; negative = off, the default) of every scoring call of this spectrum from now on */
+	/* CompareSpectrums: this spectrum as map 1 against `other` as map 2; `saturated` counts the entries read whose stored count is
+	 * 65535 (the figures are the reference's while it is 0, lower bounds otherwise) */
+	kmr_compare_counts countCommonKmers(KmerSpectrum &other) { kmr_compare_counts c; other.check(kmr_compare_spectrums(_h, other._h, &c), "kmr_compare_spectrums"); return c; }
+	/* ... and every read of a device ReadSet on its own against this spectrum as map 2, one record per read */
+	std::vector<kmr_compare_counts> compareReads(const ReadSet &reads) {
+		std::vector<kmr_compare_counts> out(reads.getSize());
+		check(kmr_compare_reads(_h, reads.raw(), out.empty() ? nullptr : out.data()), "kmr_compare_reads");
+		return out;
+	}
 	void setBimodalSigmas(double sigmas) { check(kmr_set_bimodal_sigmas(_h, sigmas), "kmr_set_bimodal_sigmas"); _bimodalSigmas = sigmas; }
 	/* bimodal: one word per read where setBimodalSigmas is on (0 = not cut; kmr_bimodal_copy), else empty; the selections that
 	 * take a TrimResult print its tags */

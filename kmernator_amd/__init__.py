@@ -4,9 +4,9 @@ Everything that computes lives in csrc/ (hand-written HIP for gfx950 behind the 
 include/kmernator_amd.h); this package is the thin host-side mirror of the reference's
 KmerSpectrum interface plus the one-process-per-GPU owner-partitioned driver.
 """
-from ._lib import (KMR_MAP_SINGLETON, KMR_MAP_WEAK, KMR_VALUE_COUNT_DIR, KMR_VALUE_EXT, KmrArtifactReportConfig, KmrConfig, KmrDedupConfig, KmrNormalizeConfig, KmrPartitionConfig, KmrSelectConfig, default_config, load,
+from ._lib import (KMR_MAP_SINGLETON, KMR_MAP_WEAK, KMR_VALUE_COUNT_DIR, KMR_VALUE_EXT, KmrArtifactReportConfig, KmrCompareCounts, KmrConfig, KmrDedupConfig, KmrNormalizeConfig, KmrPartitionConfig, KmrSelectConfig, default_config, load,
                    record_bytes)
-from .spectrum import ConsensusReadSet, DedupPass, DumpText, DuplicateFragmentFilter, FilterKnownOddities, FilterReport, KmerSpectrum, KmerSpectrumError, Histogram, ReadPairs, ReadSelector, ReadSet, synth_reads_device
+from .spectrum import COMPARE_DTYPE, COMPARE_HEADER, CompareSpectrums, ConsensusReadSet, DedupPass, DumpText, DuplicateFragmentFilter, FilterKnownOddities, FilterReport, KmerSpectrum, KmerSpectrumError, Histogram, ReadPairs, ReadSelector, ReadSet, compare_line, synth_reads_device
 
-__all__ = ["KmerSpectrum", "DumpText", "KmerSpectrumError", "ReadSet", "ReadPairs", "Histogram", "FilterKnownOddities", "FilterReport", "DuplicateFragmentFilter", "DedupPass", "ConsensusReadSet", "ReadSelector", "synth_reads_device", "KmrConfig", "KmrSelectConfig", "KmrPartitionConfig", "KmrNormalizeConfig", "KmrDedupConfig", "KmrArtifactReportConfig", "default_config", "load", "record_bytes",
+__all__ = ["KmerSpectrum", "DumpText", "KmerSpectrumError", "ReadSet", "ReadPairs", "Histogram", "FilterKnownOddities", "FilterReport", "DuplicateFragmentFilter", "DedupPass", "ConsensusReadSet", "ReadSelector", "synth_reads_device", "CompareSpectrums", "compare_line", "COMPARE_DTYPE", "COMPARE_HEADER", "KmrCompareCounts", "KmrConfig", "KmrSelectConfig", "KmrPartitionConfig", "KmrNormalizeConfig", "KmrDedupConfig", "KmrArtifactReportConfig", "default_config", "load", "record_bytes",
            "KMR_MAP_WEAK", "KMR_MAP_SINGLETON", "KMR_VALUE_COUNT_DIR", "KMR_VALUE_EXT"]

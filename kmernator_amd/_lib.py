@@ -70,6 +70,14 @@ class KmrDedupConfig(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("struct_size", "dedup_mode", "paired", "dedup_length", "start_offset", "edit_distance", "consensus")]
 
 
+class KmrCompareCounts(C.Structure):
+    """kmr_compare_counts"""
+    _fields_ = [(n, C.c_uint64) for n in ("size1", "size2", "common", "common_count1", "common_count2", "total_count1", "total_count2", "saturated")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class KmrSelectConfig(C.Structure):
     """kmr_select_config"""
     _fields_ = [("struct_size", C.c_uint32), ("both_pass", C.c_uint32), ("minimum_score", C.c_double), ("min_read_length", C.c_float),
@@ -113,6 +121,7 @@ EXPORTS = [
     "kmr_identify_pairs", "kmr_identify_pairs_dev", "kmr_pairs_info", "kmr_pairs_copy", "kmr_pairs_device_ptrs", "kmr_pairs_free",
     "kmr_dedup_config_init", "kmr_dedup_fragments", "kmr_dedup_fragments_dev", "kmr_dedup_info", "kmr_dedup_copy", "kmr_dedup_device_ptrs",
     "kmr_dedup_reads", "kmr_dedup_names_copy", "kmr_dedup_free", "kmr_consensus_qual",
+    "kmr_compare_spectrums", "kmr_compare_reads", "kmr_compare_reads_dev", "kmr_compare_line", "kmr_reads_circularize",
     "kmr_map_digest", "kmr_synth_reads_dev", "kmr_build_info", "kmr_sk_exchange_uniform", "kmr_sk_exchange_peer_uniform", "kmr_sk_exchange_range", "kmr_count_lists_prefix",
 ]
 
@@ -296,6 +305,12 @@ def load():
     lib.kmr_dedup_free.restype = None
     lib.kmr_consensus_qual.argtypes = [C.c_double]
     lib.kmr_consensus_qual.restype = C.c_char
+    ccp = C.POINTER(KmrCompareCounts)
+    lib.kmr_compare_spectrums.argtypes = [vp, vp, ccp]
+    lib.kmr_compare_reads.argtypes = [vp, vp, vp]
+    lib.kmr_compare_reads_dev.argtypes = [vp, vp, vp]
+    lib.kmr_compare_line.argtypes = [ccp, C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, u64p]
+    lib.kmr_reads_circularize.argtypes = [vp, vp, C.c_uint32, C.POINTER(vp)]
     _lib = lib
     return lib
 

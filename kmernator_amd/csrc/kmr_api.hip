@@ -2299,6 +2299,8 @@ int kmr_tune(kmr_handle *h, const char *knob, double value) {
 	else if (k == "narrow_tallies") h->tune.no_narrow = value == 0;
 	else if (k == "keep_level1_state") h->tune.no_l1_state = value == 0;
 	else if (k == "csr_partition") h->tune.csr_partition = value != 0;
+	else if (k == "compare_lds_kmers") h->tune.compare_lds_kmers = value >= 0 && value <= CMP_CAP_MOST ? (int)value : -1;
+	else if (k == "compare_stage_kmers") h->tune.compare_stage_kmers = value >= 1 ? std::min<uint64_t>((uint64_t)value, 1ull << 31) : 0;
 	else if (k == "superkmer_window") {      /* largest minimizer window the geometry may take (32 / 16 / 8 / 4): A/B runs, tests of the narrower windows at large k */
 		if (h->superkmer_mode && !h->sk_state) { uint32_t w, m, o; if (!sk_geometry(h->k, 0, w, m, o, (uint32_t)value)) return fail(h, KMR_ERR_INVALID_ARG, "no minimizer geometry under that window"); h->sk_win = w; h->sk_m = m; h->sk_off = o; }
 	}
@@ -3393,3 +3395,170 @@ int kmr_kernel_time_reset(kmr_handle *h) {
 }
 
 }  // extern "C"
+
+/* ---- CompareSpectrums (kmr_compare.hpp): the spectrum side of kmr_compare_spectrums / kmr_compare_reads* (kmr_stages.hip) ---- */
+namespace {
+
+/* h->cmp_buf: what compare_reads_core keeps between calls */
+enum { CMP_B_ACC = 0, CMP_B_NK, CMP_B_KOFF, CMP_B_STAGE, CMP_B_CNT, CMP_B_LOFF, CMP_B_SRC, CMP_B_RID, CMP_B_PERM, CMP_B_PERM2, CMP_B_KIN, CMP_B_KOUT, CMP_B_HSCAN, CMP_B_START, CMP_B_SORT };
+
+uint64_t map_entries(const DevMap &m) { return m.present ? m.n : 0; }
+
+/* size, count sum and saturated entries of h's map into tot (CMP_T_WORDS words, zeroed here), on stream s */
+int compare_totals(kmr_handle *h, kmr_handle *on, unsigned long long *tot) {
+	HIPCHK(on, hipMemsetAsync(tot, 0, 8 * CMP_T_WORDS, on->stream));
+	const uint64_t nw = map_entries(h->weak), ns = map_entries(h->sing);
+	if (nw + ns == 0) return 0;
+	hipLaunchKernelGGL(compare_totals_kernel, dim3(grid_for(nw + ns)), dim3(256), 0, on->stream, h->weak.vals.get<uint32_t>(), h->ext ? 15u : 3u, nw, h->sing.sweight.get<uint8_t>(), ns, tot);
+	HIPCHK(on, hipGetLastError());
+	return 0;
+}
+
+template <int W> int compare_spectrums_t(kmr_handle *h1, kmr_handle *h2, kmr_compare_counts *out) {
+	int rc = h2->cmp_buf[CMP_B_ACC].reserve(h2, "compare counters", 256); if (rc) return rc;
+	CompareRec *acc = h2->cmp_buf[CMP_B_ACC].get<CompareRec>();
+	unsigned long long *tot2 = (unsigned long long *)(acc + 1);
+	if (h1 != h2) HIPCHK(h2, hipStreamSynchronize(h1->stream));      /* h1's maps are complete before h2's stream reads them */
+	HIPCHK(h2, hipMemsetAsync(acc, 0, sizeof(CompareRec), h2->stream));
+	rc = compare_totals(h2, h2, tot2); if (rc) return rc;
+	const uint64_t nw1 = map_entries(h1->weak), ns1 = map_entries(h1->sing);
+	if (nw1 + ns1) {
+		hipLaunchKernelGGL(compare_maps_kernel<W>, dim3(grid_for(nw1 + ns1)), dim3(256), 0, h2->stream, view_of<W>(h1->weak, h1->ext ? 15u : 3u), nw1, view_of<W>(h1->sing, 0), ns1,
+		                   view_of<W>(h2->weak, h2->ext ? 15u : 3u), view_of<W>(h2->sing, 0), h2->hkb, acc);
+		HIPCHK(h2, hipGetLastError());
+	}
+	unsigned long long host[8 + CMP_T_WORDS];
+	HIPCHK(h2, hipMemcpyAsync(host, acc, sizeof(host), hipMemcpyDeviceToHost, h2->stream));
+	HIPCHK(h2, hipStreamSynchronize(h2->stream));
+	const CompareRec *a = (const CompareRec *)host; const unsigned long long *t = host + 8;
+	out->size1 = a->size1; out->size2 = t[CMP_T_SIZE]; out->common = a->common; out->common_count1 = a->common_count1; out->common_count2 = a->common_count2;
+	out->total_count1 = a->total_count1; out->total_count2 = t[CMP_T_TOTAL]; out->saturated = a->saturated + t[CMP_T_SATURATED];
+	return KMR_OK;
+}
+
+/* the sorted path over the run's reads of more than cap k-mers (all of them at cap 0): see kmr_compare.hpp */
+template <int W> int compare_long_run(kmr_handle *h, const uint64_t *stage, const uint64_t *koff, uint64_t r0, uint64_t m, uint32_t cap, const unsigned long long *tot2, CompareRec *out) {
+	DevBuf *B = h->cmp_buf;
+	const dim3 block(256);
+	int rc = B[CMP_B_CNT].reserve(h, "compare long counts", 4 * m); if (rc) return rc;
+	rc = B[CMP_B_LOFF].reserve(h, "compare long offsets", 8 * (m + 1)); if (rc) return rc;
+	uint32_t *cnt = B[CMP_B_CNT].get<uint32_t>(); uint64_t *loff = B[CMP_B_LOFF].get<uint64_t>();
+	hipLaunchKernelGGL(compare_long_count_kernel, dim3(grid_for(m)), block, 0, h->stream, koff, r0, m, cap, tot2, cnt, out);
+	HIPCHK(h, hipGetLastError());
+	rc = exclusive_scan_queue(h, cnt, m, loff); if (rc) return rc;
+	uint64_t c = 0;
+	HIPCHK(h, hipMemcpyAsync(&c, loff + m, 8, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipStreamSynchronize(h->stream));
+	if (c == 0) return 0;
+	if (c >= 0xffffffffull) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_compare_reads: a run of the sorted path holds 2^32 - 1 k-mers or more (lower kmr_tune \"compare_stage_kmers\")");
+	rc = B[CMP_B_SRC].reserve(h, "compare sort slots", 4 * c); if (rc) return rc;
+	rc = B[CMP_B_RID].reserve(h, "compare sort reads", 4 * c); if (rc) return rc;
+	rc = B[CMP_B_PERM].reserve(h, "compare sort order", 4 * c); if (rc) return rc;
+	rc = B[CMP_B_PERM2].reserve(h, "compare sort order", 4 * c); if (rc) return rc;
+	rc = B[CMP_B_KIN].reserve(h, "compare sort keys", 8 * c); if (rc) return rc;
+	rc = B[CMP_B_KOUT].reserve(h, "compare sort keys", 8 * c); if (rc) return rc;
+	rc = B[CMP_B_HSCAN].reserve(h, "compare heads", 8 * (c + 1)); if (rc) return rc;
+	rc = B[CMP_B_START].reserve(h, "compare head starts", 8 * (c + 1)); if (rc) return rc;
+	size_t sort_bytes = 0;
+	if (kmr::sort_pairs_u64_u32(nullptr, &sort_bytes, nullptr, nullptr, nullptr, nullptr, c, h->stream) != 0) return fail(h, KMR_ERR_HIP, "kmr_compare_reads: radix sort (size query)");
+	rc = B[CMP_B_SORT].reserve(h, "compare sort scratch", std::max<size_t>(sort_bytes, 256)); if (rc) return rc;
+	uint32_t *src = B[CMP_B_SRC].get<uint32_t>(), *rid = B[CMP_B_RID].get<uint32_t>(), *perm = B[CMP_B_PERM].get<uint32_t>(), *perm2 = B[CMP_B_PERM2].get<uint32_t>();
+	unsigned long long *kin = B[CMP_B_KIN].get<unsigned long long>(), *kout = B[CMP_B_KOUT].get<unsigned long long>();
+	uint64_t *hscan = B[CMP_B_HSCAN].get<uint64_t>(), *start = B[CMP_B_START].get<uint64_t>();
+	uint32_t *head = (uint32_t *)kout;      /* the sort keys are dead once the order stands */
+	const dim3 cgrid(grid_for(c));
+	hipLaunchKernelGGL(compare_long_fill_kernel, cgrid, block, 0, h->stream, koff, r0, m, (const uint64_t *)loff, c, src, rid, perm);
+	HIPCHK(h, hipGetLastError());
+	/* least significant first: the key words, then the read; the sort is stable */
+	for (uint32_t w = 0; w <= (uint32_t)W; w++) {
+		hipLaunchKernelGGL(compare_long_gather_kernel, cgrid, block, 0, h->stream, stage, (uint32_t)W, w, (const uint32_t *)src, (const uint32_t *)rid, (const uint32_t *)perm, c, kin);
+		HIPCHK(h, hipGetLastError());
+		size_t sb = B[CMP_B_SORT].cap();
+		if (kmr::sort_pairs_u64_u32(B[CMP_B_SORT].get(), &sb, kin, kout, perm, perm2, c, h->stream) != 0) return fail(h, KMR_ERR_HIP, "kmr_compare_reads: radix sort");
+		std::swap(perm, perm2);
+	}
+	hipLaunchKernelGGL(compare_long_heads_kernel, cgrid, block, 0, h->stream, stage, (uint32_t)W, (const uint32_t *)src, (const uint32_t *)rid, (const uint32_t *)perm, c, head);
+	HIPCHK(h, hipGetLastError());
+	rc = exclusive_scan_queue(h, head, c, hscan); if (rc) return rc;
+	hipLaunchKernelGGL(compare_long_starts_kernel, cgrid, block, 0, h->stream, (const uint32_t *)head, (const uint64_t *)hscan, c, start);
+	hipLaunchKernelGGL(compare_long_add_kernel<W>, cgrid, block, 0, h->stream, stage, (const uint32_t *)src, (const uint32_t *)rid, (const uint32_t *)perm, (const uint32_t *)head, (const uint64_t *)hscan,
+	                   (const uint64_t *)start, c, r0, view_of<W>(h->weak, h->ext ? 15u : 3u), view_of<W>(h->sing, 0), h->hkb, out);
+	HIPCHK(h, hipGetLastError());
+	return 0;
+}
+
+template <int W> int compare_reads_t(kmr_handle *h, const ReadsView &all, CompareRec *out) {
+	DevBuf *B = h->cmp_buf;
+	const uint64_t n = all.n_reads;
+	const dim3 block(256);
+	int rc = B[CMP_B_ACC].reserve(h, "compare counters", 256); if (rc) return rc;
+	rc = B[CMP_B_NK].reserve(h, "compare k-mer counts", 4 * n); if (rc) return rc;
+	rc = B[CMP_B_KOFF].reserve(h, "compare k-mer offsets", 8 * (n + 1)); if (rc) return rc;
+	unsigned long long *tot2 = (unsigned long long *)(B[CMP_B_ACC].get<CompareRec>() + 1);
+	unsigned int *most = (unsigned int *)(tot2 + CMP_T_WORDS); uint32_t *err = most + 1;
+	uint32_t *nk = B[CMP_B_NK].get<uint32_t>(); uint64_t *koff = B[CMP_B_KOFF].get<uint64_t>();
+	rc = compare_totals(h, h, tot2); if (rc) return rc;
+	HIPCHK(h, hipMemsetAsync(most, 0, 8, h->stream));
+	hipLaunchKernelGGL(compare_nk_kernel, dim3(grid_for(n)), block, 0, h->stream, all.offsets, n, h->k, nk, most, err);
+	HIPCHK(h, hipGetLastError());
+	rc = exclusive_scan_queue(h, nk, n, koff); if (rc) return rc;
+	/* the call's one fixed-size copy: all k-mers, the most of a read, the error word */
+	uint64_t total = 0; unsigned int hm[2] = {0, 0};
+	HIPCHK(h, hipMemcpyAsync(&total, koff + n, 8, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipMemcpyAsync(hm, most, 8, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipStreamSynchronize(h->stream));
+	if (hm[1]) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_compare_reads: a read of 2^32 k-mers or more");
+	const uint32_t cap = h->tune.compare_lds_kmers < 0 ? CMP_CAP : (uint32_t)h->tune.compare_lds_kmers;
+	const uint64_t budget = h->tune.compare_stage_kmers ? h->tune.compare_stage_kmers : CMP_STAGE_SLOTS;
+	/* runs of whole reads whose slots fit the budget; a read that alone exceeds it is a run of its own.  Only a batch of more
+	 * k-mers than one run holds has its offsets looked at by the host */
+	std::vector<uint64_t> cut;      /* first read of every run, and n */
+	std::vector<uint64_t> hk;
+	cut.push_back(0);
+	if (total > budget) {
+		hk.resize(n + 1);
+		HIPCHK(h, hipMemcpy(hk.data(), koff, 8 * (n + 1), hipMemcpyDeviceToHost));
+		uint64_t r0 = 0;
+		for (uint64_t r = 0; r < n; r++) if (hk[r + 1] - hk[r0] > budget && r > r0) { cut.push_back(r); r0 = r; }
+	}
+	cut.push_back(n);
+	DevParams dp = dev_params(h);
+	dp.sub_wstart = dp.sub_wkeys = dp.sub_sstart = dp.sub_skeys = nullptr; dp.sub_wvals = nullptr; dp.sub_sweight = nullptr; dp.sub_wnb = dp.sub_snb = 0;      /* a read's own map subtracts nothing */
+	const MapView<W> weak = view_of<W>(h->weak, h->ext ? 15u : 3u), sing = view_of<W>(h->sing, 0);
+	for (size_t i = 0; i + 1 < cut.size(); i++) {
+		const uint64_t r0 = cut[i], m = cut[i + 1] - r0;
+		const uint64_t slots = hk.empty() ? total : hk[r0 + m] - hk[r0];
+		if (slots) {
+			rc = B[CMP_B_STAGE].reserve(h, "compare staging", 8ull * W * slots); if (rc) return rc;
+			uint64_t *stage = B[CMP_B_STAGE].get<uint64_t>();
+			HIPCHK(h, hipMemsetAsync(stage, 0xff, 8ull * W * slots, h->stream));
+			ReadsView rv = reads_slice(all, r0, m);
+			rc = prepare_units(h, rv); if (rc) return rc;
+			CompareOp<W> op; op.stage = stage; op.koff = koff; op.slot_base = hk.empty() ? 0 : hk[r0];
+			rc = launch_extract<W, false>(h, rv, dp, op); if (rc) return rc;
+		}
+		const uint64_t *stage = B[CMP_B_STAGE].get<uint64_t>();
+		if (cap) {
+			const size_t smem = (size_t)CMP_WAVES * cap * W * 8;
+			HIPCHK(h, hipFuncSetAttribute((const void *)compare_reads_lds_kernel<W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)CMP_WAVES * CMP_CAP_MOST * W * 8)));
+			const uint64_t blocks = std::min<uint64_t>((m + CMP_WAVES - 1) / CMP_WAVES, (uint64_t)num_cus(h) * 16);
+			hipLaunchKernelGGL(compare_reads_lds_kernel<W>, dim3((unsigned)blocks), dim3(CMP_WAVES * 64), smem, h->stream, stage, (const uint64_t *)koff, r0, m, cap, weak, sing, h->hkb,
+			                   (const unsigned long long *)tot2, out);
+			HIPCHK(h, hipGetLastError());
+		}
+		if (cap == 0 || hm[0] > cap) { rc = compare_long_run<W>(h, stage, koff, r0, m, cap, tot2, out); if (rc) return rc; }
+	}
+	return KMR_OK;
+}
+
+}  // namespace
+
+namespace kmr_host {
+int compare_spectrums_core(kmr_handle *h1, kmr_handle *h2, kmr_compare_counts *out) { return with_w(h2, [&](auto W) { return compare_spectrums_t<W()>(h1, h2, out); }); }
+int compare_reads_core(kmr_handle *h2, const uint8_t *bases, const uint8_t *quals, const uint64_t *offsets, uint64_t n_reads, void *dev_out) {
+	const ReadsView rv = reads_view(bases, quals, offsets, n_reads);
+	const int rc = with_w(h2, [&](auto W) { return compare_reads_t<W()>(h2, rv, (CompareRec *)dev_out); });
+	if (rc) hipStreamSynchronize(h2->stream);
+	return rc;
+}
+}  // namespace kmr_host

@@ -126,6 +126,7 @@ struct HandleMem {                   /* ... by kmr_destroy */
 	struct Early { bool active = false; uint64_t hi = 0; uint32_t min_depth = 0; DevBuf ue, cursor, fc, err; } early;      /* err: the early pass's own error word, read by kmr_finalize alone */
 	DevBuf dedup_tab;                /* kmr_dedup_fragments*: the probability and quality-step tables (DedupTables), made by the first call */
 	DevBuf xo_dev;                   /* kmr_extract_by_owner_host: owner segments of one batch kept on the device between the sizing call and the copy-out */
+	DevBuf cmp_buf[16];              /* temporaries of kmr_compare_spectrums / kmr_compare_reads* (compare_reads_core's CMP_* indices), grow-only */
 };
 struct BuildMem {                    /* ... by kmr_release_table too: the streaming build's state */
 	DevBuf sk_state;                 /* build_mode 3 (kmr_superkmer.hpp): list words */
@@ -188,6 +189,8 @@ struct KMR_HIDDEN Tuning {
 	uint32_t pair_hash_bits = 64;      /* kmr_identify_pairs*: bits of the common name's hash the phase-2 sort keys keep (tests: a few bits, so that distinct names share a key) */
 	int bimodal_window = -1;           /* bimodal_trim_kernel: the longest run it stages in LDS (-1: BM_CAP; tests: 0, so that every run is walked in global memory) */
 	bool csr_partition = true;         /* build_csr: the chunk CSR by the radix partition of csr_bin_*_kernel (default) or, 0, by chunk_hist_kernel / chunk_scatter_kernel's atomic per chunk (A/B runs, tests of both, and what more than 2^24 lists take) */
+	int compare_lds_kmers = -1;        /* kmr_compare_reads*: the most k-mers of a read that compare_reads_lds_kernel takes (-1: CMP_CAP; 0: every read goes through the sorted path; tests: a few) */
+	uint64_t compare_stage_kmers = 0;  /* kmr_compare_reads*: staging slots of one run of whole reads (0: CMP_STAGE_SLOTS; tests: a few, so that a batch takes several runs and a read alone exceeds one) */
 	bool no_coarse_lists = true;       /* exchange: scatter into the job's fine lists (default) or, kmr_tune("coarse_lists", 1), into coarse ones that the owner splits before the count pass (sk_refine_kernel: not yet fast enough to pay) */
 };
 
@@ -401,6 +404,11 @@ int num_cus(kmr_handle *h);
 struct ScoreDev { uint32_t *trim_offset, *trim_length; float *score; uint8_t *was_trimmed; const uint64_t *bimodal; };      /* the results in score_buf (bimodal: the words in bimodal_buf, null while --bimodal-sigmas is off), good until the handle's next scoring call */
 int score_reads_core(kmr_handle *h, const uint8_t *s_b, const uint64_t *s_o, uint64_t n_reads, double minimum_kmer_score, int scoring_type,
                      uint32_t *trim_offset, uint32_t *trim_length, float *score, uint8_t *was_trimmed, ScoreDev *keep = nullptr);
+
+/* CompareSpectrums (kmr_compare.hpp).  compare_spectrums_core: map 1 of h1 against map 2 of h2, the eight figures to host memory (waits).
+ * compare_reads_core: one record per read of the device batch to dev_out (device memory, n_reads records), queued on h2's stream */
+int compare_spectrums_core(kmr_handle *h1, kmr_handle *h2, kmr_compare_counts *out);
+int compare_reads_core(kmr_handle *h2, const uint8_t *bases, const uint8_t *quals, const uint64_t *offsets, uint64_t n_reads, void *dev_out);
 
 /* ---- defined in kmr_stages.hip (its kmr_ingest.hpp holds the two-bit kernels): what the spectrum's packed feed path launches.  All
  * pointers are device memory; the work is queued on the handle's stream. */

@@ -599,5 +599,25 @@ __global__ void ingest_shift_quals(uint8_t *quals, uint64_t n, int delta) {
 	for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) quals[i] = (uint8_t)(quals[i] + delta);
 }
 
+/* ReadSet::circularize (src/ReadSet.cpp:120-130): read r becomes bases + bases[0 : min(extra, L)].  The new lengths, then the copy:
+ * one wavefront per read, bases and qualities alike */
+__global__ void circularize_lengths_kernel(const uint64_t *offsets, uint64_t n, uint32_t extra, uint32_t *len, uint32_t *err) {
+	for (uint64_t r = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; r < n; r += (uint64_t)gridDim.x * blockDim.x) {
+		const uint64_t L = offsets[r + 1] - offsets[r], nl = L + (L < extra ? L : extra);
+		if (nl > 0xffffffffull) { atomicOr(err, 1u); len[r] = 0; continue; }
+		len[r] = (uint32_t)nl;
+	}
+}
+__global__ void circularize_copy_kernel(const uint8_t *bases, const uint8_t *quals, const uint64_t *offsets, uint64_t n, const uint64_t *new_off, uint8_t *out_b, uint8_t *out_q) {
+	const uint32_t lane = threadIdx.x & 63;
+	for (uint64_t r = (blockIdx.x * (uint64_t)blockDim.x + threadIdx.x) >> 6; r < n; r += ((uint64_t)gridDim.x * blockDim.x) >> 6) {
+		const uint64_t s = offsets[r], L = offsets[r + 1] - s, d = new_off[r], nl = new_off[r + 1] - d;
+		for (uint64_t i = lane; i < nl; i += 64) {
+			const uint64_t from = s + (i < L ? i : i - L);
+			out_b[d + i] = bases[from]; out_q[d + i] = quals[from];
+		}
+	}
+}
+
 }  // namespace kmr
 #endif

@@ -428,6 +428,102 @@ int kmr_reads_copy(const kmr_reads *r, char *bases, char *quals, uint64_t *offse
 	return e == hipSuccess ? KMR_OK : KMR_ERR_HIP;
 }
 
+/* ReadSet::circularize (src/ReadSet.cpp:120-130) */
+int kmr_reads_circularize(kmr_handle *h, const kmr_reads *in, uint32_t extra_length, kmr_reads **out) {
+	if (out) *out = nullptr;
+	if (!h || !in || !out) return fail(h, KMR_ERR_INVALID_ARG, "kmr_reads_circularize: NULL argument");
+	if (in->device != h->device) return fail(h, KMR_ERR_INVALID_ARG, "read batch lives on another device");
+	hipSetDevice(h->device);
+	const uint64_t n = in->n, n1 = std::max<uint64_t>(n, 1);
+	auto r = make_result<kmr_reads>(h);
+	r->n = n; r->input_base = in->input_base; r->filtered = in->filtered;
+	Scratch tmp(h);
+	uint32_t *len, *err; uint64_t *off;
+	HIPCHK(h, tmp.take(&len, n1)); HIPCHK(h, tmp.take(&err, (size_t)1));
+	HIPCHK(h, alloc_n(r->offsets, &off, n + 1));
+	HIPCHK(h, r->name_off.alloc(8 * n1)); HIPCHK(h, r->name_len.alloc(4 * n1));
+	HIPCHK(h, hipMemsetAsync(err, 0, 4, h->stream)); HIPCHK(h, hipMemsetAsync(off, 0, 8, h->stream));
+	HIPCHK(h, hipMemsetAsync(r->name_off.get(), 0, 8 * n1, h->stream)); HIPCHK(h, hipMemsetAsync(r->name_len.get(), 0, 4 * n1, h->stream));
+	uint32_t herr = 0;
+	if (n) {
+		HIPCHK(h, hipMemcpyAsync(r->name_off.get(), in->name_off.get(), 8 * n, hipMemcpyDeviceToDevice, h->stream));
+		HIPCHK(h, hipMemcpyAsync(r->name_len.get(), in->name_len.get(), 4 * n, hipMemcpyDeviceToDevice, h->stream));
+		hipLaunchKernelGGL(circularize_lengths_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, in->offsets.get<uint64_t>(), n, extra_length, len, err);
+		HIPCHK(h, hipGetLastError());
+		int rc = exclusive_scan(h, len, n, off); if (rc) return rc;
+		HIPCHK(h, hipMemcpy(&r->total, off + n, 8, hipMemcpyDeviceToHost));
+		HIPCHK(h, hipMemcpy(&herr, err, 4, hipMemcpyDeviceToHost));
+		if (herr) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_reads_circularize: a read of 2^32 bases or more");
+	}
+	uint8_t *cb, *cq;
+	HIPCHK(h, alloc_n(r->bases, &cb, r->total + 64)); HIPCHK(h, alloc_n(r->quals, &cq, r->total + 64));
+	HIPCHK(h, hipMemsetAsync(cb + r->total, 0, 64, h->stream)); HIPCHK(h, hipMemsetAsync(cq + r->total, 0, 64, h->stream));
+	if (r->total) {
+		hipLaunchKernelGGL(circularize_copy_kernel, dim3((unsigned)std::min<uint64_t>((n + 3) / 4, (uint64_t)num_cus(h) * 32)), dim3(256), 0, h->stream,
+		                   in->bases.get<uint8_t>(), in->quals.get<uint8_t>(), in->offsets.get<uint64_t>(), n, (const uint64_t *)off, cb, cq);
+		HIPCHK(h, hipGetLastError());
+	}
+	HIPCHK(h, hipStreamSynchronize(h->stream));
+	tmp.done();
+	*out = r.release();
+	return KMR_OK;
+}
+
+/* ---- CompareSpectrums (apps/CompareSpectrums.cpp; kernels: kmr_compare.hpp, launched by kmr_api.hip's compare_*_core) ---- */
+int kmr_compare_spectrums(kmr_handle *h1, kmr_handle *h2, kmr_compare_counts *out) {
+	if (!h1 || !h2 || !out) return fail(h2, KMR_ERR_INVALID_ARG, "kmr_compare_spectrums: NULL argument");
+	if (!h1->finalized || !h2->finalized) return fail(h2, KMR_ERR_STATE, "kmr_compare_spectrums before kmr_finalize");
+	if (h1->device != h2->device) return fail(h2, KMR_ERR_INVALID_ARG, "kmr_compare_spectrums: the spectra live on different devices");
+	if (h1->k != h2->k || h1->cfg.hash_kind != h2->cfg.hash_kind) return fail(h2, KMR_ERR_INVALID_ARG, "kmr_compare_spectrums: the spectra differ in k or hash_kind");
+	hipSetDevice(h2->device);
+	return compare_spectrums_core(h1, h2, out);
+}
+static int compare_reads_check(kmr_handle *h2, const kmr_reads *set1, const void *dst) {
+	if (!h2 || !set1 || (set1->n && !dst)) return fail(h2, KMR_ERR_INVALID_ARG, "kmr_compare_reads: NULL argument");
+	if (!h2->finalized) return fail(h2, KMR_ERR_STATE, "kmr_compare_reads before kmr_finalize");
+	if (set1->device != h2->device) return fail(h2, KMR_ERR_INVALID_ARG, "read batch lives on another device");
+	if (h2->cfg.world_size > 1 || h2->cfg.num_parts > 1 || h2->cfg.kmer_subsample > 1)
+		return fail(h2, KMR_ERR_UNSUPPORTED, "kmr_compare_reads: a handle with world_size > 1, num_parts > 1 or kmer_subsample > 1 holds a part of the spectrum only");
+	return KMR_OK;
+}
+int kmr_compare_reads_dev(kmr_handle *h2, const kmr_reads *set1, void *dev_per_read) {
+	int rc = compare_reads_check(h2, set1, dev_per_read); if (rc) return rc;
+	if (set1->n == 0) return KMR_OK;
+	hipSetDevice(h2->device);
+	return compare_reads_core(h2, set1->bases.get<uint8_t>(), set1->quals.get<uint8_t>(), set1->offsets.get<uint64_t>(), set1->n, dev_per_read);
+}
+int kmr_compare_reads(kmr_handle *h2, const kmr_reads *set1, kmr_compare_counts *per_read) {
+	int rc = compare_reads_check(h2, set1, per_read); if (rc) return rc;
+	if (set1->n == 0) return KMR_OK;
+	hipSetDevice(h2->device);
+	Scratch tmp(h2);
+	kmr_compare_counts *d;
+	HIPCHK(h2, tmp.take(&d, set1->n));
+	rc = compare_reads_core(h2, set1->bases.get<uint8_t>(), set1->quals.get<uint8_t>(), set1->offsets.get<uint64_t>(), set1->n, d); if (rc) return rc;
+	HIPCHK(h2, hipMemcpyAsync(per_read, d, sizeof(kmr_compare_counts) * set1->n, hipMemcpyDeviceToHost, h2->stream));
+	HIPCHK(h2, hipStreamSynchronize(h2->stream));
+	tmp.done();
+	return KMR_OK;
+}
+/* one line of the table (:234-241); needs no device */
+int kmr_compare_line(const kmr_compare_counts *c, const char *label, uint64_t label_len, char *dst, uint64_t cap, uint64_t *bytes) {
+	if (!c || !bytes || (label_len && !label) || (cap && !dst)) return KMR_ERR_INVALID_ARG;
+	char buf[256];
+	int n = snprintf(buf, sizeof(buf), "%llu\t%llu\t%llu", (unsigned long long)c->size1, (unsigned long long)c->size2, (unsigned long long)c->common);
+	const uint64_t num[4] = {c->common, c->common_count1, c->common, c->common_count2}, den[4] = {c->size1, c->total_count1, c->size2, c->total_count2};
+	for (int i = 0; i < 4; i++) {
+		/* 0.0 / 0.0 in the reference: "-nan" from an x86-64 glibc build, written as that on every host */
+		if (den[i] == 0) n += snprintf(buf + n, sizeof(buf) - n, "\t-nan");
+		else n += snprintf(buf + n, sizeof(buf) - n, "\t%.4g", (double)num[i] * 100.0 / (double)den[i]);
+	}
+	*bytes = (uint64_t)n + 1 + label_len + 1;
+	if (cap < *bytes) return KMR_ERR_CAPACITY;
+	memcpy(dst, buf, n); dst[n] = '\t';
+	if (label_len) memcpy(dst + n + 1, label, label_len);
+	dst[n + 1 + label_len] = '\n';
+	return KMR_OK;
+}
+
 /* ---- f4: artifact filter (FilterKnownOddities) --------------------------- */
 }  // extern "C"
 

@@ -74,6 +74,52 @@ class _DeviceObject:
             pass
 
 
+# one kmr_compare_counts
+COMPARE_DTYPE = np.dtype([(n, np.uint64) for n in ("size1", "size2", "common", "common_count1", "common_count2", "total_count1", "total_count2", "saturated")])
+COMPARE_HEADER = b"\nSet 1\tSet 2\tCommon\t%Uniq1\t%Tot1\t%Uniq2\t%Tot2\n"      # apps/CompareSpectrums.cpp:211-212
+
+
+def compare_line(counts, label=b""):
+    """one line of CompareSpectrums' table (apps/CompareSpectrums.cpp:234-241) as bytes, through kmr_compare_line: `counts` is a
+    dict or a COMPARE_DTYPE record.  A zero denominator prints as -nan, as the reference's x86-64 glibc build does."""
+    lib = _lib.load()
+    c = _lib.KmrCompareCounts(*[int(counts[n]) for n in COMPARE_DTYPE.names])
+    label = bytes(label)
+    buf = C.create_string_buffer(160 + len(label))
+    nb = C.c_uint64()
+    _ok(lib.kmr_compare_line(C.byref(c), label, len(label), buf, len(buf), C.byref(nb)), "kmr_compare_line")
+    return buf.raw[:nb.value]
+
+
+def CompareSpectrums(spectrum2, set1, per_read=False, circular_reference=False, spectrum1=None):
+    """apps/CompareSpectrums.cpp's output as bytes: the header and one line for set 1 as a whole against `spectrum2`, or with
+    `per_read` one line per read of the ReadSet `set1`, labelled with the read's name.  `circular_reference` runs
+    ReadSet::circularize(k) over set 1 first.  The whole form compares `spectrum1` if given (the finalized spectrum of set 1),
+    else builds one of spectrum2's configuration from `set1` (solid-only: finalized with min_depth 1)."""
+    reads = set1.circularize() if circular_reference and set1 is not None else set1
+    out = [COMPARE_HEADER]
+    try:
+        if per_read:
+            rec = spectrum2.compareReads(reads)
+            names = reads.arrays()[3]
+            out += [compare_line(rec[i], names[i]) for i in range(reads.n)]
+        else:
+            sp1, own = spectrum1, False
+            if sp1 is None:
+                sp1, own = KmerSpectrum(spectrum2.cfg), True
+                sp1.buildKmerSpectrumFromReadSet(reads)
+                sp1.purgeMinDepth(1)
+            try:
+                out.append(compare_line(sp1.countCommonKmers(spectrum2)))
+            finally:
+                if own:
+                    sp1.close()
+    finally:
+        if reads is not set1:
+            reads.close()
+    return b"".join(out)
+
+
 class KmerSpectrum:
     """One spectrum (weak + singleton maps) resident on one MI355X."""
 
@@ -566,6 +612,23 @@ class KmerSpectrum:
         """dumpGraphs' text (src/Meraculous.h:121-133) likewise; needs KMR_VALUE_EXT"""
         return self._dump_text(1, min_depth, lo, hi)
 
+    # -- CompareSpectrums (apps/CompareSpectrums.cpp)
+    def countCommonKmers(self, other):
+        """countCommonKmers / evaluate (apps/CompareSpectrums.cpp:146-162, :225-242) of this spectrum as map 1 against `other` as
+        map 2 (kmr_compare_spectrums): a dict of size1, size2, common, common_count1, common_count2, total_count1, total_count2 and
+        saturated -- the entries read whose stored count is 65535; the figures are the reference's while that is 0, lower bounds
+        otherwise."""
+        c = _lib.KmrCompareCounts()
+        other._call("compare_spectrums", self.h, other.h, C.byref(c))
+        return c.as_dict()
+
+    def compareReads(self, read_set):
+        """evaluatePerRead (:243-257): every read of `read_set` on its own as map 1 against this spectrum as map 2
+        (kmr_compare_reads): a structured array of one COMPARE_DTYPE record per read, in read order"""
+        out = np.zeros(read_set.n, dtype=COMPARE_DTYPE)
+        self._call("compare_reads", self.h, read_set._live(), out.ctypes.data_as(C.c_void_p) if read_set.n else None)
+        return out
+
     def kernel_time(self, which=0):
         ms, n = C.c_double(), C.c_uint64()
         self._call("kernel_time", self.h, which, C.byref(ms), C.byref(n))
@@ -753,6 +816,14 @@ class ReadSet(_DeviceObject):
                                         no.ctypes.data_as(C.POINTER(C.c_uint64)), nl.ctypes.data_as(C.POINTER(C.c_uint32))), "kmr_reads_copy")
         names = [self.text[int(no[i]):int(no[i]) + int(nl[i])] for i in range(self.n)]
         return b, q, o, names
+
+    def circularize(self, extra=None):
+        """ReadSet::circularize (src/ReadSet.cpp:120-130) as a new set: every read becomes bases + bases[0 : min(extra, L)], its
+        qualities extended alike, its name kept (kmr_reads_circularize).  `extra` defaults to k, which CompareSpectrums
+        --circular-reference passes: the first k-mer of a circular sequence is then counted twice, as in the reference."""
+        r = C.c_void_p()
+        self.sp._call("reads_circularize", self.sp.h, self._live(), self.sp.k if extra is None else int(extra), C.byref(r))
+        return ReadSet._adopt(self.sp, self.text, r, self.store_comment)
 
     def identifyPairs(self, store_comment=None, device_text=None):
         """ReadSet::identifyPairs (src/ReadSet.cpp:446-570) of this batch as a fresh set, on the device (kmr_identify_pairs): a
