@@ -1155,6 +1155,98 @@ int kmr_compare_line(const kmr_compare_counts *c, const char *label, uint64_t la
  * empty and extra_length 0 is a copy.  Free the result with kmr_reads_free. */
 int kmr_reads_circularize(kmr_handle *h, const kmr_reads *in, uint32_t extra_length, kmr_reads **out);
 
+/* ---- TnfDistance (apps/TnfDistance.cpp): tetranucleotide-frequency vectors of sequences and windows, and the distances between them ----
+ *
+ * The reference counts the canonical k-mers of a very small k (--kmer-size, default 4) per sequence by building a whole KmerSpectrum for
+ * it (buildTnfs :462-484), reads the counts out in the order of a fixed map (TNF::stdMap) and compares the vectors by a Euclidean or a
+ * Spearman distance.  The k of every call below is the handle's k, as KmerSizer is global in the reference: a handle created with k = 4 and
+ * never fed is enough, none of the calls needs a finalized spectrum, and world_size, num_parts and kmer_subsample do not matter to any of
+ * them.  k > 6 is KMR_ERR_UNSUPPORTED (4^6 u32 bins are the 16 KiB of LDS a wavefront counts in; the reference sizes its map "for hexamers").
+ *
+ * Columns.  D(k) canonical k-mers: 2, 10, 32, 136, 512, 2080 for k = 1 .. 6.  Their order is the iteration order of TNF::stdMap, a KmerMap
+ * asked for 2112 buckets, which makes 4096 (getMinPowerOf2, src/Kmer.h:2199-2212): ascending bucket = hash & 4095 of the hash kind over the
+ * packed key bytes, and ascending key within a bucket (the map appends and re-sorts a bucket on every insert, src/Kmer.h:3095-3106 with
+ * getNumUnsorted :1701-1704).  The order matters to the bits of a distance, because the sums run in it.
+ *   kmr_tnf_dims      D(k); KMR_ERR_UNSUPPORTED for k = 0 or k > 6
+ *   kmr_tnf_columns   codes[D]: column -> the 2k-bit code of the canonical k-mer, first base in the high bits, A C G T = 0 1 2 3
+ *   kmr_tnf_header    "Count\tLength" and "\t<k-mer>" per column (toHeader :295-303), no line end; *bytes is its length,
+ *                     KMR_ERR_CAPACITY if cap is smaller (with *bytes set)
+ * These three need no device.
+ *
+ * Vectors.  A kmr_tnf holds n vectors of D counts on the device, for each the sequence it came from, its first base and its number of
+ * bases (the origin), its float length, and the bounds of the groups (input files) the vectors fall into.
+ *   kmr_tnf_reads       one vector per sequence of the batch (buildTnfs): column c is the number of occurrences of that canonical k-mer
+ *                       that pass the build's weight test (TrackingDataMinimal4, as above kmr_compare_counts): a sequence with real
+ *                       qualities loses its low-weight k-mers, a FASTA sequence (quality 127) only the k-mers over a markup.  A sequence
+ *                       shorter than k is a vector of zeros.  The batch was ingested through h or a handle of its configuration.
+ *   kmr_tnf_windows     shredReadByWindow (:486-494) and purgeShortTNFS (:506-518): of a sequence of L bases a window of `window` bases at
+ *                       every i = 0, step, 2 step, ... with i < L - window (strictly: L <= window gives none).  Windows carry reference
+ *                       quality: every k-mer without a markup counts, whatever the sequence's own qualities.  A window whose counts sum to
+ *                       less than min_count is dropped (the tool passes window * 3 / 4); the survivors keep the input order (the
+ *                       reference's swap-with-last order shows only in its per-thread .data files).  step >= 1.
+ *   input_starts / n_inputs   as for kmr_partition_reads: n_inputs + 1 ascending sequence indices from 0 to n; NULL / 0 = one input.  The
+ *                       groups of the result are the inputs.
+ *   kmr_tnf_group_sums  one vector per group, the group's vectors added (wholeTnfs :717), each a group of its own.  The reference adds floats
+ *                       in read order; here the counts add as u64 and are converted once, which is the same while every sum stays <= 2^24.
+ *   kmr_tnf_info        n, D, the number of groups, and `inexact`: the columns (of all vectors) above 2^24, where a float no longer holds
+ *                       the count -- the figures are the reference's while it is 0, in the manner of `saturated` above.
+ *   kmr_tnf_copy        to host memory, each where the pointer is not NULL: counts[n * D] (vector-major, column order), lengths[n]
+ *                       (calcLength / buildLength :396-416: double l += (double)(v * v) with the product in float, (float)sqrt(l), 0
+ *                       becomes 1), origin[3 n] (sequence, first base, bases; a group sum: group, 0, 0), group_bounds[groups + 1].
+ * Sequences are cut into pieces of bases (kmr_tune "tnf_piece_bases", default 4096) that the wavefronts of the device count separately; it
+ * changes no result.  A sequence of 2^32 k-mers or more is KMR_ERR_UNSUPPORTED.
+ *
+ * Distances, to the bit of an x86-64 build of the reference without -ffast-math (the Release build's -ffast-math is not followed, as for
+ * the oracle): no multiply-add is contracted, every sum runs in column order.
+ *   KMR_TNF_EUCLIDEAN (getDistance :434-441)   float d = (float)((double)a[i] / (double)la - (double)b[i] / (double)lb);
+ *                                              dist = dist + d * d in float; then sqrtf(dist)
+ *   KMR_TNF_SPEARMAN (RankVector, src/Utils.h:2090-2160)   ranks 1 .. D, ties (float)tieRankSum / (float)tieSize; mean = (D + 1) / 2 in
+ *                                              integer division; three float sums of float products; (1 - sum_xy / sqrtf(sum_x2 * sum_y2)) / 2
+ *   kmr_tnf_distances / _dev   with b: rows [first_row, first_row + n_rows) of a against all of b, row-major n_rows x n_b floats (b = one vector
+ *                       is the --reference-file form).  With b == NULL: the strict lower triangle of a, row i holding j < i, the rows
+ *                       packed: row i begins at i (i - 1) / 2 - first_row (first_row - 1) / 2 (--inter-distance-file, :649-662).
+ *                       first_row / n_rows let a caller stream a matrix that does not fit.  out is host memory (_dev: device memory, written
+ *                       by work queued on h's stream).  The first distance call of a formula on a vector set makes its per-vector part
+ *                       (quotients, or ranks) and keeps it with the set.  a, b and h on one device, same D and hash kind.
+ *   kmr_tnf_likelihoods   the whole --intra-inter-file computation (:664-902) over a batch: windows of (window, step) and, where window2 >
+ *                       window, of (window2, step2) (window2 < window takes window's values, as the option parser does), each purged at
+ *                       3/4; out = four histograms of bins + 2 u64 (GenericHistogram, src/Utils.h:2163-2254: _step = (float)(end - 0) / bins,
+ *                       idx = (int)(v / _step) + 1, v > end in the last, end = (float)sqrt(2.0) Euclidean / 1 Spearman): intra, inter,
+ *                       intra-vs-whole, inter-vs-whole.  The loops are the reference's: a file with fewer than two surviving windows adds
+ *                       nothing to the two intra histograms; equal window sizes take the lower triangle within a file and file pairs j < i,
+ *                       different sizes every window against every window2 of the same file and of every other file; every window against
+ *                       the group sum of every other file.  No distance is stored.  A distance that is not a number (undefined in the
+ *                       reference) is counted in bin 0.  A block the reference would subsample (numSamples >= its share of max_samples, :689-691
+ *                       and :827-832; the default, INT64_MAX, never) is refused with KMR_ERR_UNSUPPORTED, naming the block: the reference
+ *                       draws from a time-seeded generator there.  1 <= bins <= 4094.
+ * Not built: --cluster-file (a serial greedy merge), --include-intra-inter-data-file, the five-part labels of reads within 0.20 of the
+ * reference (:560-574), subsampling, k > 6. */
+typedef struct kmr_tnf kmr_tnf;
+enum kmr_tnf_formula { KMR_TNF_EUCLIDEAN = 0, KMR_TNF_SPEARMAN = 1 };
+typedef struct kmr_tnf_likelihood_config {
+	uint32_t struct_size;
+	uint32_t formula;          /* kmr_tnf_formula */
+	uint64_t window, step;     /* --window-size, --window-step */
+	uint64_t window2, step2;   /* --window2-size, --window2-step */
+	uint32_t bins;             /* --likelihood-bins */
+	uint32_t reserved;
+	int64_t max_samples;       /* --max-samples */
+} kmr_tnf_likelihood_config;
+int kmr_tnf_dims(uint32_t k, uint32_t *dims);
+int kmr_tnf_columns(uint32_t k, uint32_t hash_kind, uint16_t *codes);
+int kmr_tnf_header(uint32_t k, uint32_t hash_kind, char *dst, uint64_t cap, uint64_t *bytes);
+int kmr_tnf_reads(kmr_handle *h, const kmr_reads *reads, const uint64_t *input_starts, uint32_t n_inputs, kmr_tnf **out);
+int kmr_tnf_windows(kmr_handle *h, const kmr_reads *reads, const uint64_t *input_starts, uint32_t n_inputs, uint64_t window, uint64_t step, int64_t min_count, kmr_tnf **out);
+int kmr_tnf_group_sums(kmr_handle *h, const kmr_tnf *tnf, kmr_tnf **out);
+int kmr_tnf_info(const kmr_tnf *tnf, uint64_t *n, uint32_t *dims, uint32_t *n_groups, uint64_t *inexact);
+int kmr_tnf_copy(const kmr_tnf *tnf, uint64_t *counts, float *lengths, uint64_t *origin, uint64_t *group_bounds);
+void kmr_tnf_free(kmr_tnf *tnf);
+int kmr_tnf_distances(kmr_handle *h, const kmr_tnf *a, const kmr_tnf *b, int formula, uint64_t first_row, uint64_t n_rows, float *out);
+int kmr_tnf_distances_dev(kmr_handle *h, const kmr_tnf *a, const kmr_tnf *b, int formula, uint64_t first_row, uint64_t n_rows, void *dev_out);
+/* window 10000, step 1000, window2 10000, step2 1000, 100 bins, Euclidean, max_samples INT64_MAX */
+int kmr_tnf_likelihood_config_init(kmr_tnf_likelihood_config *cfg);
+int kmr_tnf_likelihoods(kmr_handle *h, const kmr_reads *reads, const uint64_t *input_starts, uint32_t n_inputs, const kmr_tnf_likelihood_config *cfg, uint64_t *out);
+
 /* Raw HIP stream of the handle (hipStream_t) so callers can order their own
  * work (torch.cuda.ExternalStream) against it. */
 void *kmr_stream(kmr_handle *h);
@@ -1195,6 +1287,8 @@ void *kmr_stream(kmr_handle *h);
  *   "compare_lds_kmers" (kmr_compare_reads*: the most k-mers of a read that one wavefront answers out of LDS, 1 - 512; 0 sends every read
  *   through the sorted path; anything else = the default, 256), "compare_stage_kmers" (k-mers of one run of whole reads of
  *   kmr_compare_reads*, 0 = 2^26; a read that alone exceeds it is a run of its own); both may be set at any time.
+ *   "tnf_piece_bases" (kmr_tnf_reads / kmr_tnf_windows / kmr_tnf_likelihoods: bases of one piece of a sequence, the unit the wavefronts share
+ *   out, 0 = 4096; tests set 64 or 65 so that a short input crosses piece edges; may be set at any time).
  * Call before the first kmr_add_reads* of a build.  KMR_ERR_INVALID_ARG for an unknown knob. */
 int kmr_tune(kmr_handle *h, const char *knob, double value);
 /* What the current build decided, for tests and measurement tools (the reference logs such figures, LOG_VERBOSE): "lists" = super-k-mer

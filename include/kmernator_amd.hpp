@@ -257,6 +257,73 @@ inline void ReadSet::load() {
 	if (kmr_reads_copy(_r, nullptr, nullptr, nullptr, _nameOff.data(), _nameLen.data()) != KMR_OK) throw KmerSpectrumError(KMR_ERR_HIP, "kmr_reads_copy");
 }
 
+/* TnfDistance (apps/TnfDistance.cpp): vectors of canonical k-mer counts on the device (kmr_tnf), k the spectrum's (1 - 6); see the
+ * TnfDistance block of kmernator_amd.h.  tnfDims / tnfColumns / tnfHeader need no device. */
+inline uint32_t tnfDims(uint32_t k) { uint32_t d = 0; const int rc = kmr_tnf_dims(k, &d); if (rc != KMR_OK) throw KmerSpectrumError(rc, "kmr_tnf_dims"); return d; }
+inline std::vector<uint16_t> tnfColumns(uint32_t k, uint32_t hashKind = 0) {
+	std::vector<uint16_t> codes(tnfDims(k));
+	const int rc = kmr_tnf_columns(k, hashKind, codes.data()); if (rc != KMR_OK) throw KmerSpectrumError(rc, "kmr_tnf_columns");
+	return codes;
+}
+inline std::string tnfHeader(uint32_t k, uint32_t hashKind = 0) {
+	uint64_t bytes = 0;
+	std::string s((size_t)16 + (k + 1) * tnfDims(k), '\0');
+	const int rc = kmr_tnf_header(k, hashKind, &s[0], s.size(), &bytes); if (rc != KMR_OK) throw KmerSpectrumError(rc, "kmr_tnf_header");
+	s.resize(bytes);
+	return s;
+}
+class TnfVectors {
+public:
+	/* buildTnfs (:462-484): one vector per sequence; inputStarts = n_inputs + 1 sequence indices, empty = one input */
+	static std::unique_ptr<TnfVectors> ofReads(KmerSpectrum &sp, const ReadSet &reads, const std::vector<uint64_t> &inputStarts = std::vector<uint64_t>()) {
+		kmr_tnf *t = nullptr;
+		sp.check(kmr_tnf_reads(sp.raw(), reads.raw(), inputStarts.empty() ? nullptr : inputStarts.data(), inputStarts.empty() ? 0 : (uint32_t)inputStarts.size() - 1, &t), "kmr_tnf_reads");
+		return std::unique_ptr<TnfVectors>(new TnfVectors(sp, t));
+	}
+	/* shredReadByWindow + purgeShortTNFS (:486-518); the tool's minCount is window * 3 / 4 */
+	static std::unique_ptr<TnfVectors> ofWindows(KmerSpectrum &sp, const ReadSet &reads, uint64_t window, uint64_t step, int64_t minCount, const std::vector<uint64_t> &inputStarts = std::vector<uint64_t>()) {
+		kmr_tnf *t = nullptr;
+		sp.check(kmr_tnf_windows(sp.raw(), reads.raw(), inputStarts.empty() ? nullptr : inputStarts.data(), inputStarts.empty() ? 0 : (uint32_t)inputStarts.size() - 1, window, step, minCount, &t), "kmr_tnf_windows");
+		return std::unique_ptr<TnfVectors>(new TnfVectors(sp, t));
+	}
+	~TnfVectors() { kmr_tnf_free(_t); }
+	TnfVectors(const TnfVectors &) = delete; TnfVectors &operator=(const TnfVectors &) = delete;
+	uint64_t size() const { return _n; }
+	uint32_t dims() const { return _d; }
+	uint32_t numGroups() const { return _g; }
+	uint64_t inexact() const { return _inexact; }      /* columns above 2^24: the reference's floats are followed while this is 0 */
+	std::vector<uint64_t> counts() const { std::vector<uint64_t> a(_n * _d); copy(a.data(), nullptr, nullptr, nullptr); return a; }
+	std::vector<float> lengths() const { std::vector<float> a(_n); copy(nullptr, a.data(), nullptr, nullptr); return a; }
+	std::vector<uint64_t> origin() const { std::vector<uint64_t> a(3 * _n); copy(nullptr, nullptr, a.data(), nullptr); return a; }
+	std::vector<uint64_t> groups() const { std::vector<uint64_t> a((size_t)_g + 1); copy(nullptr, nullptr, nullptr, a.data()); return a; }
+	/* wholeTnfs (:717): one vector per group */
+	std::unique_ptr<TnfVectors> groupSums() const {
+		kmr_tnf *t = nullptr;
+		_sp.check(kmr_tnf_group_sums(_sp.raw(), _t, &t), "kmr_tnf_group_sums");
+		return std::unique_ptr<TnfVectors>(new TnfVectors(_sp, t));
+	}
+	/* getDistance (:434-446) of rows [firstRow, firstRow + nRows) against every vector of `other` (row-major), or with other == nullptr the
+	 * packed strict lower triangle; formula: KMR_TNF_EUCLIDEAN / KMR_TNF_SPEARMAN */
+	std::vector<float> distances(const TnfVectors *other, int formula, uint64_t firstRow = 0, uint64_t nRows = UINT64_MAX) const {
+		if (nRows == UINT64_MAX) nRows = _n - firstRow;
+		const uint64_t e = firstRow + nRows;
+		std::vector<float> out(other ? nRows * other->_n : (e ? e * (e - 1) / 2 : 0) - (firstRow ? firstRow * (firstRow - 1) / 2 : 0));
+		_sp.check(kmr_tnf_distances(_sp.raw(), _t, other ? other->_t : nullptr, formula, firstRow, nRows, out.empty() ? nullptr : out.data()), "kmr_tnf_distances");
+		return out;
+	}
+	/* the four histograms of --intra-inter-file (:664-902), bins + 2 counters each */
+	static std::vector<uint64_t> likelihoods(KmerSpectrum &sp, const ReadSet &reads, const kmr_tnf_likelihood_config &cfg, const std::vector<uint64_t> &inputStarts = std::vector<uint64_t>()) {
+		std::vector<uint64_t> out((size_t)4 * (cfg.bins + 2));
+		sp.check(kmr_tnf_likelihoods(sp.raw(), reads.raw(), inputStarts.empty() ? nullptr : inputStarts.data(), inputStarts.empty() ? 0 : (uint32_t)inputStarts.size() - 1, &cfg, out.data()), "kmr_tnf_likelihoods");
+		return out;
+	}
+	const kmr_tnf *raw() const { return _t; }
+private:
+	TnfVectors(KmerSpectrum &sp, kmr_tnf *t) : _sp(sp), _t(t) { kmr_tnf_info(t, &_n, &_d, &_g, &_inexact); }
+	void copy(uint64_t *c, float *l, uint64_t *o, uint64_t *g) const { const int rc = kmr_tnf_copy(_t, c, l, o, g); if (rc != KMR_OK) throw KmerSpectrumError(rc, "kmr_tnf_copy"); }
+	KmerSpectrum &_sp; kmr_tnf *_t; uint64_t _n = 0, _inexact = 0; uint32_t _d = 0, _g = 0;
+};
+
 /* FilterKnownOddities (src/FilterKnownOddities.h): the artifact screen FilterReads runs before the spectrum build */
 class FilterKnownOddities {
 public:

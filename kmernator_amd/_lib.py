@@ -78,6 +78,15 @@ class KmrCompareCounts(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+KMR_TNF_EUCLIDEAN, KMR_TNF_SPEARMAN = 0, 1
+
+
+class KmrTnfLikelihoodConfig(C.Structure):
+    """kmr_tnf_likelihood_config"""
+    _fields_ = [("struct_size", C.c_uint32), ("formula", C.c_uint32), ("window", C.c_uint64), ("step", C.c_uint64), ("window2", C.c_uint64), ("step2", C.c_uint64),
+                ("bins", C.c_uint32), ("reserved", C.c_uint32), ("max_samples", C.c_int64)]
+
+
 class KmrSelectConfig(C.Structure):
     """kmr_select_config"""
     _fields_ = [("struct_size", C.c_uint32), ("both_pass", C.c_uint32), ("minimum_score", C.c_double), ("min_read_length", C.c_float),
@@ -122,6 +131,8 @@ EXPORTS = [
     "kmr_dedup_config_init", "kmr_dedup_fragments", "kmr_dedup_fragments_dev", "kmr_dedup_info", "kmr_dedup_copy", "kmr_dedup_device_ptrs",
     "kmr_dedup_reads", "kmr_dedup_names_copy", "kmr_dedup_free", "kmr_consensus_qual",
     "kmr_compare_spectrums", "kmr_compare_reads", "kmr_compare_reads_dev", "kmr_compare_line", "kmr_reads_circularize",
+    "kmr_tnf_dims", "kmr_tnf_columns", "kmr_tnf_header", "kmr_tnf_reads", "kmr_tnf_windows", "kmr_tnf_group_sums", "kmr_tnf_info", "kmr_tnf_copy", "kmr_tnf_free",
+    "kmr_tnf_distances", "kmr_tnf_distances_dev", "kmr_tnf_likelihood_config_init", "kmr_tnf_likelihoods",
     "kmr_map_digest", "kmr_synth_reads_dev", "kmr_build_info", "kmr_sk_exchange_uniform", "kmr_sk_exchange_peer_uniform", "kmr_sk_exchange_range", "kmr_count_lists_prefix",
 ]
 
@@ -311,6 +322,21 @@ def load():
     lib.kmr_compare_reads_dev.argtypes = [vp, vp, vp]
     lib.kmr_compare_line.argtypes = [ccp, C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, u64p]
     lib.kmr_reads_circularize.argtypes = [vp, vp, C.c_uint32, C.POINTER(vp)]
+    u16p, lcp = C.POINTER(C.c_uint16), C.POINTER(KmrTnfLikelihoodConfig)
+    lib.kmr_tnf_dims.argtypes = [C.c_uint32, u32p]
+    lib.kmr_tnf_columns.argtypes = [C.c_uint32, C.c_uint32, u16p]
+    lib.kmr_tnf_header.argtypes = [C.c_uint32, C.c_uint32, C.c_char_p, C.c_uint64, u64p]
+    lib.kmr_tnf_reads.argtypes = [vp, vp, u64p, C.c_uint32, C.POINTER(vp)]
+    lib.kmr_tnf_windows.argtypes = [vp, vp, u64p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int64, C.POINTER(vp)]
+    lib.kmr_tnf_group_sums.argtypes = [vp, vp, C.POINTER(vp)]
+    lib.kmr_tnf_info.argtypes = [vp, u64p, u32p, u32p, u64p]
+    lib.kmr_tnf_copy.argtypes = [vp, u64p, C.POINTER(C.c_float), u64p, u64p]
+    lib.kmr_tnf_free.argtypes = [vp]
+    lib.kmr_tnf_free.restype = None
+    lib.kmr_tnf_distances.argtypes = [vp, vp, vp, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(C.c_float)]
+    lib.kmr_tnf_distances_dev.argtypes = [vp, vp, vp, C.c_int, C.c_uint64, C.c_uint64, vp]
+    lib.kmr_tnf_likelihood_config_init.argtypes = [lcp]
+    lib.kmr_tnf_likelihoods.argtypes = [vp, vp, u64p, C.c_uint32, lcp, u64p]
     _lib = lib
     return lib
 

@@ -2301,6 +2301,7 @@ int kmr_tune(kmr_handle *h, const char *knob, double value) {
 	else if (k == "csr_partition") h->tune.csr_partition = value != 0;
 	else if (k == "compare_lds_kmers") h->tune.compare_lds_kmers = value >= 0 && value <= CMP_CAP_MOST ? (int)value : -1;
 	else if (k == "compare_stage_kmers") h->tune.compare_stage_kmers = value >= 1 ? std::min<uint64_t>((uint64_t)value, 1ull << 31) : 0;
+	else if (k == "tnf_piece_bases") h->tune.tnf_piece_bases = value >= 1 ? (uint32_t)std::min<double>(value, 1u << 30) : 0;
 	else if (k == "superkmer_window") {      /* largest minimizer window the geometry may take (32 / 16 / 8 / 4): A/B runs, tests of the narrower windows at large k */
 		if (h->superkmer_mode && !h->sk_state) { uint32_t w, m, o; if (!sk_geometry(h->k, 0, w, m, o, (uint32_t)value)) return fail(h, KMR_ERR_INVALID_ARG, "no minimizer geometry under that window"); h->sk_win = w; h->sk_m = m; h->sk_off = o; }
 	}
@@ -3551,9 +3552,49 @@ template <int W> int compare_reads_t(kmr_handle *h, const ReadsView &all, Compar
 	return KMR_OK;
 }
 
+/* the staging of compare_reads_t for the whole batch in one run, for a handle of one key word (see kmr_host.hpp) */
+int tnf_stage(kmr_handle *h, const ReadsView &all, const uint64_t **koff_out, const uint64_t **stage_out, uint64_t *slots) {
+	DevBuf *B = h->cmp_buf;
+	const uint64_t n = all.n_reads;
+	int rc = B[CMP_B_ACC].reserve(h, "compare counters", 256); if (rc) return rc;
+	rc = B[CMP_B_NK].reserve(h, "compare k-mer counts", 4 * std::max<uint64_t>(n, 1)); if (rc) return rc;
+	rc = B[CMP_B_KOFF].reserve(h, "compare k-mer offsets", 8 * (n + 1)); if (rc) return rc;
+	unsigned int *most = (unsigned int *)((unsigned long long *)(B[CMP_B_ACC].get<CompareRec>() + 1) + CMP_T_WORDS); uint32_t *err = most + 1;
+	uint32_t *nk = B[CMP_B_NK].get<uint32_t>(); uint64_t *koff = B[CMP_B_KOFF].get<uint64_t>();
+	HIPCHK(h, hipMemsetAsync(most, 0, 8, h->stream));
+	hipLaunchKernelGGL(compare_nk_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, all.offsets, n, h->k, nk, most, err);
+	HIPCHK(h, hipGetLastError());
+	rc = exclusive_scan_queue(h, nk, n, koff); if (rc) return rc;
+	uint64_t total = 0; unsigned int hm[2] = {0, 0};
+	HIPCHK(h, hipMemcpyAsync(&total, koff + n, 8, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipMemcpyAsync(hm, most, 8, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipStreamSynchronize(h->stream));
+	if (hm[1]) return fail(h, KMR_ERR_UNSUPPORTED, "a sequence of 2^32 k-mers or more");
+	*koff_out = koff; *slots = total; *stage_out = nullptr;
+	if (total == 0) return KMR_OK;
+	rc = B[CMP_B_STAGE].reserve(h, "compare staging", 8 * total); if (rc) return rc;
+	uint64_t *stage = B[CMP_B_STAGE].get<uint64_t>();
+	HIPCHK(h, hipMemsetAsync(stage, 0xff, 8 * total, h->stream));
+	DevParams dp = dev_params(h);
+	dp.sub_wstart = dp.sub_wkeys = dp.sub_sstart = dp.sub_skeys = nullptr; dp.sub_wvals = nullptr; dp.sub_sweight = nullptr; dp.sub_wnb = dp.sub_snb = 0;
+	dp.subsample = 1; dp.world = 1; dp.rank = 0; dp.num_parts = 1; dp.part_idx = 0;      /* every k-mer of the batch is this call's */
+	ReadsView rv = all;
+	rc = prepare_units(h, rv); if (rc) return rc;
+	CompareOp<1> op; op.stage = stage; op.koff = koff; op.slot_base = 0;
+	rc = launch_extract<1, false>(h, rv, dp, op); if (rc) return rc;
+	*stage_out = stage;
+	return KMR_OK;
+}
+
 }  // namespace
 
 namespace kmr_host {
+int tnf_stage_core(kmr_handle *h, const uint8_t *bases, const uint8_t *quals, const uint64_t *offsets, uint64_t n_reads, const uint64_t **koff, const uint64_t **stage, uint64_t *slots) {
+	if (h->W != 1) return fail(h, KMR_ERR_UNSUPPORTED, "tnf_stage_core: a key of more than one word");
+	const int rc = tnf_stage(h, reads_view(bases, quals, offsets, n_reads), koff, stage, slots);
+	if (rc) hipStreamSynchronize(h->stream);
+	return rc;
+}
 int compare_spectrums_core(kmr_handle *h1, kmr_handle *h2, kmr_compare_counts *out) { return with_w(h2, [&](auto W) { return compare_spectrums_t<W()>(h1, h2, out); }); }
 int compare_reads_core(kmr_handle *h2, const uint8_t *bases, const uint8_t *quals, const uint64_t *offsets, uint64_t n_reads, void *dev_out) {
 	const ReadsView rv = reads_view(bases, quals, offsets, n_reads);

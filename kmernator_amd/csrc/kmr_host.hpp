@@ -191,7 +191,8 @@ struct KMR_HIDDEN Tuning {
 	bool csr_partition = true;         /* build_csr: the chunk CSR by the radix partition of csr_bin_*_kernel (default) or, 0, by chunk_hist_kernel / chunk_scatter_kernel's atomic per chunk (A/B runs, tests of both, and what more than 2^24 lists take) */
 	int compare_lds_kmers = -1;        /* kmr_compare_reads*: the most k-mers of a read that compare_reads_lds_kernel takes (-1: CMP_CAP; 0: every read goes through the sorted path; tests: a few) */
 	uint64_t compare_stage_kmers = 0;  /* kmr_compare_reads*: staging slots of one run of whole reads (0: CMP_STAGE_SLOTS; tests: a few, so that a batch takes several runs and a read alone exceeds one) */
-	bool no_coarse_lists = true;       /* exchange: scatter into the job's fine lists (default) or, kmr_tune("coarse_lists", 1), into coarse ones that the owner splits before the count pass (sk_refine_kernel: not yet fast enough to pay) */
+	uint32_t tnf_piece_bases = 0;      /* kmr_tnf_reads / kmr_tnf_windows: bases of one piece of a sequence (0: TNF_PIECE_BASES; tests: a few, so that short inputs cross piece edges) */
+	bool no_coarse_lists = true;      /* exchange: scatter into the job's fine lists (default) or, kmr_tune("coarse_lists", 1), into coarse ones that the owner splits before the count pass (sk_refine_kernel: not yet fast enough to pay) */
 };
 
 /* What the caller of one feed call knows about it, handed down from the entry point to the extraction (add_reads_dev_call,
@@ -333,6 +334,21 @@ struct KMR_HIDDEN kmr_dedup : OnDevice {
 	uint64_t skipped[4] = {0, 0, 0, 0};
 };
 
+/* what kmr_tnf_reads / kmr_tnf_windows / kmr_tnf_group_sums leave on the device: n vectors of D counts in column order, their origin and
+ * float lengths, and -- made by the first distance call that needs them, kept since -- the per-vector part of either distance */
+struct KMR_HIDDEN kmr_tnf : OnDevice {
+	DevBuf counts;                                /* [n][D] u32; u64 for group sums (wide) */
+	DevBuf origin;                                /* [n][3] u64: sequence, first base, bases */
+	DevBuf len;                                   /* [n] f32 */
+	DevBuf group;                                 /* [n] u32: the group of every vector */
+	mutable DevBuf qt;                            /* Euclidean: [D][n] f64 value / length */
+	mutable DevBuf xt, x2;                        /* Spearman: [D][n] f32 rank - mean, [n] f32 sum_x2 */
+	std::vector<uint64_t> bounds;                 /* groups + 1 */
+	uint64_t n = 0, inexact = 0;
+	uint32_t D = 0, k = 0, hash_kind = 0;
+	bool wide = false;
+};
+
 namespace kmr_host KMR_HIDDEN {
 
 inline std::string oom_note() { std::string s(g_oom_note); g_oom_note[0] = 0; return s; }
@@ -409,6 +425,11 @@ int score_reads_core(kmr_handle *h, const uint8_t *s_b, const uint64_t *s_o, uin
  * compare_reads_core: one record per read of the device batch to dev_out (device memory, n_reads records), queued on h2's stream */
 int compare_spectrums_core(kmr_handle *h1, kmr_handle *h2, kmr_compare_counts *out);
 int compare_reads_core(kmr_handle *h2, const uint8_t *bases, const uint8_t *quals, const uint64_t *offsets, uint64_t n_reads, void *dev_out);
+/* TnfDistance (kmr_tnf.hpp) takes a batch's k-mers from the same extraction: for a handle of one key word, slot koff[r] + i of *stage holds the
+ * canonical key word of k-mer i of read r where it passes the weight test and all ones where it does not (CompareOp).  *koff (n_reads + 1) and
+ * *stage live in h->cmp_buf until the handle's next kmr_compare_reads* or tnf_stage_core; the work is queued on h's stream, and the call waits
+ * for the sizes.  The handle's world_size, num_parts and kmer_subsample are not applied. */
+int tnf_stage_core(kmr_handle *h, const uint8_t *bases, const uint8_t *quals, const uint64_t *offsets, uint64_t n_reads, const uint64_t **koff, const uint64_t **stage, uint64_t *slots);
 
 /* ---- defined in kmr_stages.hip (its kmr_ingest.hpp holds the two-bit kernels): what the spectrum's packed feed path launches.  All
  * pointers are device memory; the work is queued on the handle's stream. */

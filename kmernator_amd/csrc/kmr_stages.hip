@@ -1,6 +1,6 @@
 /*
  * kmr_stages.hip -- the read stages of include/kmernator_amd.h: FASTQ ingest and the kmr_reads batch, its two-bit form, the artifact
- * filter and its report, read selection, coverage normalization and their output text, identifyPairs, duplicate-fragment collapse, and the mercount / mergraph text.
+ * filter and its report, read selection, coverage normalization and their output text, identifyPairs, duplicate-fragment collapse, the mercount / mergraph text, and TnfDistance's vectors and distances.
  *
  * Host logic only, as kmr_api.hip (the spectrum, which these stages read through kmr_host.hpp); the kernels are the stage headers',
  * each of which this translation unit alone includes.  A stage costs its kernels and a page here: what the stages share is below --
@@ -23,6 +23,7 @@
 #include "kmr_pairs.hpp"
 #include "kmr_dedup.hpp"
 #include "kmr_dump.hpp"
+#include "kmr_tnf.hpp"
 
 using namespace kmr;
 
@@ -521,6 +522,455 @@ int kmr_compare_line(const kmr_compare_counts *c, const char *label, uint64_t la
 	memcpy(dst, buf, n); dst[n] = '\t';
 	if (label_len) memcpy(dst + n + 1, label, label_len);
 	dst[n + 1 + label_len] = '\n';
+	return KMR_OK;
+}
+
+}  // extern "C"
+
+/* ---- TnfDistance (apps/TnfDistance.cpp; kernels: kmr_tnf.hpp; the k-mers come out of kmr_api.hip's tnf_stage_core) ---- */
+namespace {
+
+uint32_t tnf_dims(uint32_t k) { const uint32_t all = 1u << (2 * k); return (k & 1) ? all / 2 : (all + (1u << k)) / 2; }
+uint32_t tnf_revcomp(uint32_t code, uint32_t k) { uint32_t r = 0; for (uint32_t i = 0; i < k; i++) { r = (r << 2) | (3u - (code & 3u)); code >>= 2; } return r; }
+
+/* column -> code, in the iteration order of TNF::stdMap: bucket = hash & 4095, ascending key within a bucket */
+std::vector<uint16_t> tnf_columns(uint32_t k, uint32_t hash_kind) {
+	std::vector<std::pair<uint32_t, uint32_t> > e;
+	const uint32_t kb = (k + 3) / 4;
+	for (uint32_t code = 0; code < (1u << (2 * k)); code++) {
+		if (code > tnf_revcomp(code, k)) continue;
+		const uint32_t w16 = code << (16 - 2 * k);      /* left-justified, pad bits zero (TwoBitSequence) */
+		const uint8_t key[2] = {(uint8_t)(w16 >> 8), (uint8_t)w16};
+		e.push_back(std::make_pair((uint32_t)(kmr_hash_of_kind(key, kb, hash_kind) & 4095u), code));
+	}
+	std::sort(e.begin(), e.end());
+	std::vector<uint16_t> codes;
+	for (const auto &p : e) codes.push_back((uint16_t)p.second);
+	return codes;
+}
+
+int tnf_check_k(kmr_handle *h, const char *who) {
+	if (h->k > TNF_MAX_K) return fail(h, KMR_ERR_UNSUPPORTED, std::string(who) + ": k = " + std::to_string(h->k) + " (TnfDistance is built for k <= 6)");
+	return KMR_OK;
+}
+
+/* the group bounds of a call as a checked host vector */
+int tnf_starts(kmr_handle *h, const char *who, const uint64_t *input_starts, uint32_t n_inputs, uint64_t n, std::vector<uint64_t> &starts) {
+	if (!input_starts) {
+		if (n_inputs > 1) return fail(h, KMR_ERR_INVALID_ARG, std::string(who) + ": input_starts is NULL for " + std::to_string(n_inputs) + " inputs");
+		starts = {0, n};
+		return KMR_OK;
+	}
+	if (n_inputs == 0) return fail(h, KMR_ERR_INVALID_ARG, std::string(who) + ": input_starts without n_inputs");
+	if (n_inputs > 65535) return fail(h, KMR_ERR_UNSUPPORTED, std::string(who) + ": more than 65535 inputs");
+	bool ok = false;
+	const uint32_t at = sel_check_input_starts(input_starts, n_inputs, &ok);
+	if (!ok) return fail(h, KMR_ERR_INVALID_ARG, std::string(who) + ": input_starts[" + std::to_string(at) + "]: the sequence indices start at 0 and ascend");
+	if (input_starts[n_inputs] != n) return fail(h, KMR_ERR_INVALID_ARG, std::string(who) + ": input_starts ends at " + std::to_string(input_starts[n_inputs]) + ", the batch holds " + std::to_string(n) + " sequences");
+	starts.assign(input_starts, input_starts + n_inputs + 1);
+	return KMR_OK;
+}
+
+/* lengths, the inexact columns and the group of every vector: what every kmr_tnf has from the start.  The root is taken on the host:
+ * the radicand is a sum of n doubles per set, and the host's sqrt is the correctly rounded one the reference calls */
+template <class T> int tnf_finish_t(kmr_handle *h, kmr_tnf *t) {
+	Scratch tmp(h);
+	double *l2; unsigned long long *bad;
+	HIPCHK(h, tmp.take(&l2, t->n)); HIPCHK(h, tmp.take(&bad, (size_t)1));
+	HIPCHK(h, hipMemsetAsync(bad, 0, 8, h->stream));
+	hipLaunchKernelGGL(tnf_len2_kernel<T>, dim3(grid_for(t->n, 64)), dim3(64), 0, h->stream, t->counts.get<T>(), t->n, t->D, l2, bad);
+	HIPCHK(h, hipGetLastError());
+	std::vector<double> hl(t->n); unsigned long long hbad = 0;
+	HIPCHK(h, hipMemcpyAsync(hl.data(), l2, 8 * t->n, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipMemcpyAsync(&hbad, bad, 8, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipStreamSynchronize(h->stream));
+	tmp.done();
+	t->inexact = hbad;
+	std::vector<float> len(t->n);
+	for (uint64_t v = 0; v < t->n; v++) { float f = (float)std::sqrt(hl[v]); if (f == 0.0f) f = 1.0f; len[v] = f; }
+	std::vector<uint32_t> grp(t->n);
+	for (size_t g = 0; g + 1 < t->bounds.size(); g++) for (uint64_t v = t->bounds[g]; v < t->bounds[g + 1]; v++) grp[v] = (uint32_t)g;
+	HIPCHK(h, t->len.alloc(4 * t->n)); HIPCHK(h, t->group.alloc(4 * t->n));
+	HIPCHK(h, hipMemcpy(t->len.get(), len.data(), 4 * t->n, hipMemcpyHostToDevice));
+	HIPCHK(h, hipMemcpy(t->group.get(), grp.data(), 4 * t->n, hipMemcpyHostToDevice));
+	return KMR_OK;
+}
+int tnf_finish(kmr_handle *h, kmr_tnf *t) {
+	if (t->n == 0) return KMR_OK;
+	return t->wide ? tnf_finish_t<unsigned long long>(h, t) : tnf_finish_t<uint32_t>(h, t);
+}
+
+/* the vectors of a batch: one per sequence, or (windows) one per surviving window */
+int tnf_count(kmr_handle *h, const char *who, const kmr_reads *r, const std::vector<uint64_t> &starts, bool windows, uint64_t window, uint64_t step, int64_t min_count, kmr_tnf *t) {
+	const uint64_t n = r->n;
+	const uint32_t k = h->k, D = tnf_dims(k), n_groups = (uint32_t)starts.size() - 1;
+	t->k = k; t->D = D; t->hash_kind = h->cfg.hash_kind; t->wide = false; t->n = 0;
+	t->bounds.assign(n_groups + 1, 0);
+	if (n == 0) return KMR_OK;
+	Scratch tmp(h);
+	const dim3 block(256);
+	/* windows carry reference quality (Kmernator::PRINT_REF_QUAL, :491) */
+	const uint8_t *quals = r->quals.get<uint8_t>();
+	if (windows) {
+		uint8_t *q; HIPCHK(h, tmp.take(&q, r->total + 64));
+		HIPCHK(h, hipMemsetAsync(q, 127, r->total + 64, h->stream));
+		quals = q;
+	}
+	const uint64_t *offsets = r->offsets.get<uint64_t>(), *koff = nullptr, *stage = nullptr; uint64_t slots = 0;
+	int rc = tnf_stage_core(h, r->bases.get<uint8_t>(), quals, offsets, n, &koff, &stage, &slots); if (rc) return rc;
+	/* the vectors: their slots and origins */
+	uint64_t nv = n; uint64_t *woff = nullptr;
+	if (windows) {
+		uint32_t *nwin, *werr;
+		HIPCHK(h, tmp.take(&nwin, n)); HIPCHK(h, tmp.take(&werr, (size_t)1)); HIPCHK(h, tmp.take(&woff, n + 1));
+		HIPCHK(h, hipMemsetAsync(werr, 0, 4, h->stream));
+		hipLaunchKernelGGL(tnf_win_count_kernel, dim3(grid_for(n)), block, 0, h->stream, offsets, n, window, step, nwin, werr);
+		HIPCHK(h, hipGetLastError());
+		rc = exclusive_scan_queue(h, nwin, n, woff); if (rc) return rc;
+		uint32_t herr = 0;
+		HIPCHK(h, hipMemcpyAsync(&nv, woff + n, 8, hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, hipMemcpyAsync(&herr, werr, 4, hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, hipStreamSynchronize(h->stream));
+		if (herr) return fail(h, KMR_ERR_UNSUPPORTED, std::string(who) + ": a sequence of 2^32 windows or more");
+		if (nv == 0) { tmp.done(); return KMR_OK; }
+	}
+	DevBuf counts, origin;
+	uint64_t *vslot, *poff; uint32_t *vnk, *pcnt;
+	HIPCHK(h, tmp.take(&vslot, nv)); HIPCHK(h, tmp.take(&vnk, nv)); HIPCHK(h, tmp.take(&pcnt, nv)); HIPCHK(h, tmp.take(&poff, nv + 1));
+	HIPCHK(h, counts.alloc(std::max<size_t>(4 * nv * D, 256))); HIPCHK(h, origin.alloc(24 * nv));
+	HIPCHK(h, hipMemsetAsync(counts.get(), 0, 4 * nv * D, h->stream));
+	if (windows) hipLaunchKernelGGL(tnf_win_desc_kernel, dim3(grid_for(nv)), block, 0, h->stream, koff, (const uint64_t *)woff, n, nv, window, step, k, vslot, vnk, origin.get<uint64_t>());
+	else hipLaunchKernelGGL(tnf_reads_desc_kernel, dim3(grid_for(nv)), block, 0, h->stream, offsets, koff, n, vslot, vnk, origin.get<uint64_t>());
+	HIPCHK(h, hipGetLastError());
+	uint32_t piece = h->tune.tnf_piece_bases ? h->tune.tnf_piece_bases : TNF_PIECE_BASES;
+	piece = piece > k - 1 ? piece - (k - 1) : 1;      /* pieces of bases overlap by k - 1: as many k-mers begin in one */
+	hipLaunchKernelGGL(tnf_piece_count_kernel, dim3(grid_for(nv)), block, 0, h->stream, (const uint32_t *)vnk, nv, piece, pcnt);
+	HIPCHK(h, hipGetLastError());
+	rc = exclusive_scan_queue(h, pcnt, nv, poff); if (rc) return rc;
+	uint64_t n_pieces = 0;
+	HIPCHK(h, hipMemcpyAsync(&n_pieces, poff + nv, 8, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipStreamSynchronize(h->stream));
+	if (n_pieces && slots) {
+		const std::vector<uint16_t> codes = tnf_columns(k, h->cfg.hash_kind);
+		std::vector<uint16_t> col(1u << (2 * k), (uint16_t)TNF_NO_COLUMN);
+		for (uint32_t c = 0; c < D; c++) col[codes[c]] = (uint16_t)c;
+		uint16_t *dcol; HIPCHK(h, tmp.take(&dcol, col.size()));
+		HIPCHK(h, hipMemcpyAsync(dcol, col.data(), 2 * col.size(), hipMemcpyHostToDevice, h->stream));
+		uint64_t blocks = std::min<uint64_t>((n_pieces + TNF_WAVES - 1) / TNF_WAVES, (uint64_t)num_cus(h) * 8);
+		const uint64_t per_wave = (n_pieces + blocks * TNF_WAVES - 1) / (blocks * TNF_WAVES);
+		blocks = (n_pieces + per_wave * TNF_WAVES - 1) / (per_wave * TNF_WAVES);
+		const size_t smem = (size_t)TNF_WAVES * 4 << (2 * k);
+		HIPCHK(h, hipFuncSetAttribute((const void *)tnf_hist_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)TNF_WAVES * 4 << (2 * TNF_MAX_K))));
+		hipLaunchKernelGGL(tnf_hist_kernel, dim3((unsigned)blocks), dim3(TNF_WAVES * 64), smem, h->stream, stage, (const uint64_t *)vslot, (const uint32_t *)vnk, (const uint64_t *)poff, nv, n_pieces,
+		                   per_wave, piece, k, (const uint16_t *)dcol, D, counts.get<uint32_t>());
+		HIPCHK(h, hipGetLastError());
+		HIPCHK(h, hipStreamSynchronize(h->stream));      /* col leaves with this scope */
+	}
+	if (!windows) {
+		t->n = nv; t->counts = std::move(counts); t->origin = std::move(origin); t->bounds = starts;
+		tmp.done();
+		return KMR_OK;
+	}
+	/* purgeShortTNFS, the input order kept */
+	unsigned long long *sums; uint32_t *keep; uint64_t *kpos, *dstarts, *dbounds;
+	HIPCHK(h, tmp.take(&sums, nv)); HIPCHK(h, tmp.take(&keep, nv)); HIPCHK(h, tmp.take(&kpos, nv + 1));
+	HIPCHK(h, tmp.take(&dstarts, starts.size())); HIPCHK(h, tmp.take(&dbounds, starts.size()));
+	HIPCHK(h, hipMemcpyAsync(dstarts, starts.data(), 8 * starts.size(), hipMemcpyHostToDevice, h->stream));
+	hipLaunchKernelGGL(tnf_rowsum_kernel, dim3(grid_for(nv * 64)), block, 0, h->stream, counts.get<uint32_t>(), nv, D, sums);
+	hipLaunchKernelGGL(tnf_keep_kernel, dim3(grid_for(nv)), block, 0, h->stream, (const unsigned long long *)sums, nv, (long long)min_count, keep);
+	HIPCHK(h, hipGetLastError());
+	rc = exclusive_scan_queue(h, keep, nv, kpos); if (rc) return rc;
+	hipLaunchKernelGGL(tnf_bounds_kernel, dim3(1), block, 0, h->stream, (const uint64_t *)dstarts, n_groups, (const uint64_t *)woff, (const uint64_t *)kpos, dbounds);
+	HIPCHK(h, hipGetLastError());
+	std::vector<uint64_t> hb(starts.size());
+	HIPCHK(h, hipMemcpyAsync(hb.data(), dbounds, 8 * hb.size(), hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipStreamSynchronize(h->stream));
+	const uint64_t kept = hb[n_groups];
+	if (kept) {
+		HIPCHK(h, t->counts.alloc(std::max<size_t>(4 * kept * D, 256))); HIPCHK(h, t->origin.alloc(24 * kept));
+		hipLaunchKernelGGL(tnf_compact_kernel, dim3(grid_for(nv * (D + 3))), block, 0, h->stream, counts.get<uint32_t>(), origin.get<uint64_t>(), (const uint32_t *)keep, (const uint64_t *)kpos, nv, D,
+		                   t->counts.get<uint32_t>(), t->origin.get<uint64_t>());
+		HIPCHK(h, hipGetLastError());
+		HIPCHK(h, hipStreamSynchronize(h->stream));
+	}
+	t->n = kept; t->bounds = hb;
+	tmp.done();
+	return KMR_OK;
+}
+
+int tnf_vectors(kmr_handle *h, const char *who, const kmr_reads *reads, const uint64_t *input_starts, uint32_t n_inputs, bool windows, uint64_t window, uint64_t step, int64_t min_count, kmr_tnf **out) {
+	if (!h || !reads || !out) return fail(h, KMR_ERR_INVALID_ARG, std::string(who) + ": NULL argument");
+	*out = nullptr;
+	int rc = tnf_check_k(h, who); if (rc) return rc;
+	if (reads->device != h->device) return fail(h, KMR_ERR_INVALID_ARG, "read batch lives on another device");
+	if (windows && step == 0) return fail(h, KMR_ERR_INVALID_ARG, std::string(who) + ": a window step of 0");
+	std::vector<uint64_t> starts;
+	rc = tnf_starts(h, who, input_starts, n_inputs, reads->n, starts); if (rc) return rc;
+	hipSetDevice(h->device);
+	auto t = make_result<kmr_tnf>(h);
+	rc = tnf_count(h, who, reads, starts, windows, window, step, min_count, t.get()); if (rc) return rc;
+	rc = tnf_finish(h, t.get()); if (rc) return rc;
+	*out = t.release();
+	return KMR_OK;
+}
+
+int tnf_group_sums(kmr_handle *h, const kmr_tnf *in, kmr_tnf *t) {
+	const uint32_t G = (uint32_t)in->bounds.size() - 1, D = in->D;
+	t->k = in->k; t->D = D; t->hash_kind = in->hash_kind; t->wide = true; t->n = G;
+	t->bounds.resize(G + 1);
+	for (uint32_t g = 0; g <= G; g++) t->bounds[g] = g;
+	if (G == 0) return KMR_OK;
+	HIPCHK(h, t->counts.alloc(std::max<size_t>(8ull * G * D, 256))); HIPCHK(h, t->origin.alloc(24ull * G));
+	HIPCHK(h, hipMemsetAsync(t->counts.get(), 0, 8ull * G * D, h->stream));
+	std::vector<uint64_t> org(3ull * G, 0); uint64_t most = 0;
+	for (uint32_t g = 0; g < G; g++) { org[3 * g] = g; most = std::max(most, in->bounds[g + 1] - in->bounds[g]); }
+	HIPCHK(h, hipMemcpy(t->origin.get(), org.data(), 24ull * G, hipMemcpyHostToDevice));
+	if (most) {
+		Scratch tmp(h);
+		uint64_t *db; HIPCHK(h, tmp.take(&db, (size_t)G + 1));
+		HIPCHK(h, hipMemcpyAsync(db, in->bounds.data(), 8ull * (G + 1), hipMemcpyHostToDevice, h->stream));
+		hipLaunchKernelGGL(tnf_group_sum_kernel, dim3((unsigned)((most + 255) / 256), G), dim3(256), 0, h->stream, in->counts.get<uint32_t>(), (const uint64_t *)db, D, t->counts.get<unsigned long long>());
+		HIPCHK(h, hipGetLastError());
+		HIPCHK(h, hipStreamSynchronize(h->stream));
+		tmp.done();
+	}
+	return KMR_OK;
+}
+
+/* the per-vector part of a formula, made once per set */
+template <class T> int tnf_prepare_t(kmr_handle *h, const kmr_tnf *t, int formula) {
+	const uint64_t n = t->n; const uint32_t D = t->D;
+	if (formula == KMR_TNF_EUCLIDEAN) {
+		if (t->qt) return KMR_OK;
+		DevBuf q; HIPCHK(h, q.alloc(8 * n * D));
+		hipLaunchKernelGGL(tnf_quot_kernel<T>, dim3(grid_for(n * D)), dim3(256), 0, h->stream, t->counts.get<T>(), t->len.get<float>(), n, D, q.get<double>());
+		HIPCHK(h, hipGetLastError());
+		HIPCHK(h, hipStreamSynchronize(h->stream));
+		t->qt = std::move(q);
+		return KMR_OK;
+	}
+	if (t->xt) return KMR_OK;
+	DevBuf x, s; HIPCHK(h, x.alloc(4 * n * D)); HIPCHK(h, s.alloc(4 * n));
+	hipLaunchKernelGGL(tnf_rank_kernel<T>, dim3((unsigned)std::min<uint64_t>(n, (uint64_t)num_cus(h) * 16)), dim3(256), 4 * D, h->stream, t->counts.get<T>(), n, D, x.get<float>());
+	hipLaunchKernelGGL(tnf_x2_kernel, dim3(grid_for(n, 64)), dim3(64), 0, h->stream, x.get<float>(), n, D, s.get<float>());
+	HIPCHK(h, hipGetLastError());
+	HIPCHK(h, hipStreamSynchronize(h->stream));
+	t->xt = std::move(x); t->x2 = std::move(s);
+	return KMR_OK;
+}
+int tnf_prepare(kmr_handle *h, const kmr_tnf *t, int formula) {
+	if (t->n == 0) return KMR_OK;
+	return t->wide ? tnf_prepare_t<unsigned long long>(h, t, formula) : tnf_prepare_t<uint32_t>(h, t, formula);
+}
+
+TnfSide tnf_side(const kmr_tnf *t, int formula) {
+	TnfSide s;
+	s.t = formula == KMR_TNF_SPEARMAN ? t->xt.get() : t->qt.get(); s.x2 = t->x2.get<float>(); s.group = t->group.get<uint32_t>(); s.n = t->n;
+	return s;
+}
+
+/* rows [first_row, first_row + n_rows) of a against b (triangle: against a itself, j < i), on h's stream */
+int tnf_pairs(kmr_handle *h, const kmr_tnf *a, const kmr_tnf *b, int formula, TnfPairs P) {
+	if (P.n_rows == 0 || b->n == 0) return KMR_OK;
+	int rc = tnf_prepare(h, a, formula); if (rc) return rc;
+	rc = tnf_prepare(h, b, formula); if (rc) return rc;
+	const bool hist = P.hist != nullptr, sp = formula == KMR_TNF_SPEARMAN;
+	const uint64_t tiles = ((P.n_rows + TNF_TILE - 1) / TNF_TILE) * ((b->n + TNF_TILE - 1) / TNF_TILE);
+	/* blocks walk the tiles; with HIST a block's u32 counters in LDS must hold its pairs: fewer than 2^19 tiles of 4096 a block */
+	const uint64_t blocks = std::max<uint64_t>(std::min<uint64_t>(tiles, (uint64_t)num_cus(h) * 32), (tiles + (1u << 19) - 1) >> 19);
+	if (blocks > 0x7fffffffull) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_tnf: too many pairs for one call (take fewer rows)");
+	const size_t smem = (size_t)2 * TNF_SLICE * TNF_TILE * (sp ? 4 : 8) + (hist ? (size_t)8 * (P.bins + 2) : 0);
+	const void *kern = sp ? (hist ? (const void *)tnf_pairs_kernel<true, true> : (const void *)tnf_pairs_kernel<true, false>)
+	                      : (hist ? (const void *)tnf_pairs_kernel<false, true> : (const void *)tnf_pairs_kernel<false, false>);
+	HIPCHK(h, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
+	const TnfSide sa = tnf_side(a, formula), sb = tnf_side(b, formula);
+	const dim3 grid((unsigned)blocks), block(TNF_BLOCK);
+	if (sp) { if (hist) hipLaunchKernelGGL((tnf_pairs_kernel<true, true>), grid, block, smem, h->stream, sa, sb, P); else hipLaunchKernelGGL((tnf_pairs_kernel<true, false>), grid, block, smem, h->stream, sa, sb, P); }
+	else { if (hist) hipLaunchKernelGGL((tnf_pairs_kernel<false, true>), grid, block, smem, h->stream, sa, sb, P); else hipLaunchKernelGGL((tnf_pairs_kernel<false, false>), grid, block, smem, h->stream, sa, sb, P); }
+	HIPCHK(h, hipGetLastError());
+	return KMR_OK;
+}
+
+int tnf_distances_check(kmr_handle *h, const kmr_tnf *a, const kmr_tnf *b, int formula, uint64_t first_row, uint64_t n_rows, const void *out, uint64_t *floats) {
+	if (!h || !a) return fail(h, KMR_ERR_INVALID_ARG, "kmr_tnf_distances: NULL argument");
+	if (formula != KMR_TNF_EUCLIDEAN && formula != KMR_TNF_SPEARMAN) return fail(h, KMR_ERR_INVALID_ARG, "kmr_tnf_distances: formula is 0 (Euclidean) or 1 (Spearman)");
+	if (a->device != h->device || (b && b->device != h->device)) return fail(h, KMR_ERR_INVALID_ARG, "kmr_tnf_distances: the vectors live on another device");
+	if (b && (b->D != a->D || b->hash_kind != a->hash_kind)) return fail(h, KMR_ERR_INVALID_ARG, "kmr_tnf_distances: the two sets differ in k or hash_kind");
+	if (first_row > a->n || n_rows > a->n - first_row) return fail(h, KMR_ERR_INVALID_ARG, "kmr_tnf_distances: rows beyond the " + std::to_string(a->n) + " vectors of a");
+	const uint64_t e = first_row + n_rows;
+	*floats = b ? n_rows * b->n : (e ? e * (e - 1) / 2 : 0) - (first_row ? first_row * (first_row - 1) / 2 : 0);
+	if (*floats && !out) return fail(h, KMR_ERR_INVALID_ARG, "kmr_tnf_distances: NULL argument");
+	return KMR_OK;
+}
+int tnf_distances_queue(kmr_handle *h, const kmr_tnf *a, const kmr_tnf *b, int formula, uint64_t first_row, uint64_t n_rows, float *dev_out) {
+	TnfPairs P{};
+	P.D = a->D; P.triangle = b ? 0 : 1; P.first_row = first_row; P.n_rows = n_rows; P.out = dev_out;
+	return tnf_pairs(h, a, b ? b : a, formula, P);
+}
+
+}  // namespace
+
+extern "C" {
+
+int kmr_tnf_dims(uint32_t k, uint32_t *dims) {
+	if (!dims) return KMR_ERR_INVALID_ARG;
+	if (k < 1 || k > TNF_MAX_K) return KMR_ERR_UNSUPPORTED;
+	*dims = tnf_dims(k);
+	return KMR_OK;
+}
+int kmr_tnf_columns(uint32_t k, uint32_t hash_kind, uint16_t *codes) {
+	if (!codes || hash_kind > KMR_HASH_LOOKUP8) return KMR_ERR_INVALID_ARG;
+	if (k < 1 || k > TNF_MAX_K) return KMR_ERR_UNSUPPORTED;
+	const std::vector<uint16_t> c = tnf_columns(k, hash_kind);
+	memcpy(codes, c.data(), 2 * c.size());
+	return KMR_OK;
+}
+int kmr_tnf_header(uint32_t k, uint32_t hash_kind, char *dst, uint64_t cap, uint64_t *bytes) {
+	if (!bytes || (cap && !dst) || hash_kind > KMR_HASH_LOOKUP8) return KMR_ERR_INVALID_ARG;
+	if (k < 1 || k > TNF_MAX_K) return KMR_ERR_UNSUPPORTED;
+	std::string s = "Count\tLength";
+	for (uint16_t code : tnf_columns(k, hash_kind)) { s.push_back('\t'); for (uint32_t i = 0; i < k; i++) s.push_back("ACGT"[(code >> (2 * (k - 1 - i))) & 3]); }
+	*bytes = s.size();
+	if (cap < s.size()) return KMR_ERR_CAPACITY;
+	memcpy(dst, s.data(), s.size());
+	return KMR_OK;
+}
+int kmr_tnf_reads(kmr_handle *h, const kmr_reads *reads, const uint64_t *input_starts, uint32_t n_inputs, kmr_tnf **out) {
+	return tnf_vectors(h, "kmr_tnf_reads", reads, input_starts, n_inputs, false, 0, 0, 0, out);
+}
+int kmr_tnf_windows(kmr_handle *h, const kmr_reads *reads, const uint64_t *input_starts, uint32_t n_inputs, uint64_t window, uint64_t step, int64_t min_count, kmr_tnf **out) {
+	return tnf_vectors(h, "kmr_tnf_windows", reads, input_starts, n_inputs, true, window, step, min_count, out);
+}
+int kmr_tnf_group_sums(kmr_handle *h, const kmr_tnf *tnf, kmr_tnf **out) {
+	if (!h || !tnf || !out) return fail(h, KMR_ERR_INVALID_ARG, "kmr_tnf_group_sums: NULL argument");
+	*out = nullptr;
+	if (tnf->device != h->device) return fail(h, KMR_ERR_INVALID_ARG, "kmr_tnf_group_sums: the vectors live on another device");
+	if (tnf->wide) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_tnf_group_sums: the vectors are group sums already");
+	hipSetDevice(h->device);
+	auto t = make_result<kmr_tnf>(h);
+	int rc = tnf_group_sums(h, tnf, t.get()); if (rc) return rc;
+	rc = tnf_finish(h, t.get()); if (rc) return rc;
+	*out = t.release();
+	return KMR_OK;
+}
+int kmr_tnf_info(const kmr_tnf *t, uint64_t *n, uint32_t *dims, uint32_t *n_groups, uint64_t *inexact) {
+	if (!t) return KMR_ERR_INVALID_ARG;
+	if (n) *n = t->n;
+	if (dims) *dims = t->D;
+	if (n_groups) *n_groups = (uint32_t)t->bounds.size() - 1;
+	if (inexact) *inexact = t->inexact;
+	return KMR_OK;
+}
+int kmr_tnf_copy(const kmr_tnf *t, uint64_t *counts, float *lengths, uint64_t *origin, uint64_t *group_bounds) {
+	if (!t) return KMR_ERR_INVALID_ARG;
+	hipSetDevice(t->device);
+	hipError_t e = hipSuccess;
+	const uint64_t cells = t->n * t->D;
+	if (counts && cells && !t->wide) {
+		std::vector<uint32_t> c(cells);
+		e = hipMemcpy(c.data(), t->counts.get(), 4 * cells, hipMemcpyDeviceToHost);
+		for (uint64_t i = 0; i < cells; i++) counts[i] = c[i];
+	} else copy_out(e, counts, t->counts, cells);
+	copy_out(e, lengths, t->len, t->n);
+	copy_out(e, origin, t->origin, 3 * t->n);
+	if (group_bounds) memcpy(group_bounds, t->bounds.data(), 8 * t->bounds.size());
+	return e == hipSuccess ? KMR_OK : KMR_ERR_HIP;
+}
+void kmr_tnf_free(kmr_tnf *t) { free_on_device(t); }
+
+int kmr_tnf_distances_dev(kmr_handle *h, const kmr_tnf *a, const kmr_tnf *b, int formula, uint64_t first_row, uint64_t n_rows, void *dev_out) {
+	uint64_t floats = 0;
+	int rc = tnf_distances_check(h, a, b, formula, first_row, n_rows, dev_out, &floats); if (rc) return rc;
+	if (!floats) return KMR_OK;
+	hipSetDevice(h->device);
+	rc = tnf_distances_queue(h, a, b, formula, first_row, n_rows, (float *)dev_out);
+	if (rc) hipStreamSynchronize(h->stream);
+	return rc;
+}
+int kmr_tnf_distances(kmr_handle *h, const kmr_tnf *a, const kmr_tnf *b, int formula, uint64_t first_row, uint64_t n_rows, float *out) {
+	uint64_t floats = 0;
+	int rc = tnf_distances_check(h, a, b, formula, first_row, n_rows, out, &floats); if (rc) return rc;
+	if (!floats) return KMR_OK;
+	hipSetDevice(h->device);
+	Scratch tmp(h);
+	float *d; HIPCHK(h, tmp.take(&d, floats));
+	rc = tnf_distances_queue(h, a, b, formula, first_row, n_rows, d); if (rc) return rc;
+	HIPCHK(h, hipMemcpyAsync(out, d, 4 * floats, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipStreamSynchronize(h->stream));
+	tmp.done();
+	return KMR_OK;
+}
+
+int kmr_tnf_likelihood_config_init(kmr_tnf_likelihood_config *c) {
+	if (!c) return KMR_ERR_INVALID_ARG;
+	memset(c, 0, sizeof(*c));
+	c->struct_size = sizeof(*c); c->formula = KMR_TNF_EUCLIDEAN; c->window = 10000; c->step = 1000; c->window2 = 10000; c->step2 = 1000; c->bins = 100; c->max_samples = INT64_MAX;
+	return KMR_OK;
+}
+int kmr_tnf_likelihoods(kmr_handle *h, const kmr_reads *reads, const uint64_t *input_starts, uint32_t n_inputs, const kmr_tnf_likelihood_config *cfg, uint64_t *out) {
+	const char *who = "kmr_tnf_likelihoods";
+	if (!h || !reads || !cfg || !out) return fail(h, KMR_ERR_INVALID_ARG, std::string(who) + ": NULL argument");
+	if (cfg->struct_size != sizeof(*cfg)) return fail(h, KMR_ERR_INVALID_ARG, std::string(who) + ": kmr_tnf_likelihood_config.struct_size mismatch (ABI)");
+	if (cfg->formula > KMR_TNF_SPEARMAN) return fail(h, KMR_ERR_INVALID_ARG, std::string(who) + ": formula is 0 (Euclidean) or 1 (Spearman)");
+	if (cfg->bins < 1 || cfg->bins > TNF_MAX_BINS) return fail(h, KMR_ERR_INVALID_ARG, std::string(who) + ": 1 <= bins <= 4094");
+	if (cfg->step == 0) return fail(h, KMR_ERR_INVALID_ARG, std::string(who) + ": a window step of 0");
+	int rc = tnf_check_k(h, who); if (rc) return rc;
+	if (reads->device != h->device) return fail(h, KMR_ERR_INVALID_ARG, "read batch lives on another device");
+	std::vector<uint64_t> starts;
+	rc = tnf_starts(h, who, input_starts, n_inputs, reads->n, starts); if (rc) return rc;
+	const uint64_t window = cfg->window;
+	uint64_t window2 = cfg->window2, step2 = cfg->step2;
+	if (window2 < window) { window2 = window; step2 = cfg->step; }      /* _parseOptions :198-203 */
+	if (step2 == 0) return fail(h, KMR_ERR_INVALID_ARG, std::string(who) + ": a window2 step of 0");
+	const bool equal = window == window2;
+	const uint32_t G = (uint32_t)starts.size() - 1, nbin = cfg->bins + 2;
+	hipSetDevice(h->device);
+	auto R = make_result<kmr_tnf>(h), W1 = make_result<kmr_tnf>(h), W2 = make_result<kmr_tnf>(h), whole = make_result<kmr_tnf>(h);
+	rc = tnf_count(h, who, reads, starts, true, window, cfg->step, (int64_t)(window * 3 / 4), W1.get()); if (rc) return rc;
+	rc = tnf_finish(h, W1.get()); if (rc) return rc;
+	if (!equal) {
+		rc = tnf_count(h, who, reads, starts, true, window2, step2, (int64_t)(window2 * 3 / 4), W2.get()); if (rc) return rc;
+		rc = tnf_finish(h, W2.get()); if (rc) return rc;
+	}
+	const kmr_tnf *w1 = W1.get(), *w2 = equal ? W1.get() : W2.get();
+	/* the blocks the reference would subsample (:689-691, :750, :781, :827-832, :857) */
+	auto size1 = [&](uint32_t g) { return (long long)(w1->bounds[g + 1] - w1->bounds[g]); };
+	auto size2 = [&](uint32_t g) { return (long long)(w2->bounds[g + 1] - w2->bounds[g]); };
+	const long long max_samples = cfg->max_samples, inputs = G;
+	long long max_intra = max_samples / inputs; if (inputs > 1) max_intra += 1;
+	long long max_inter = max_samples / inputs;
+	if (inputs >= 2) { max_inter = max_samples / (inputs * (inputs - 1) / 2); if (inputs > 2) max_inter += 1; }
+	std::vector<uint8_t> intra_ok(G, 0);
+	for (uint32_t g = 0; g < G; g++) {
+		if (size1(g) <= 1) continue;
+		intra_ok[g] = 1;
+		const long long samples = equal ? size1(g) * (size1(g) - 1) / 2 : size1(g) * size2(g);
+		if (!(samples < max_intra)) return fail(h, KMR_ERR_UNSUPPORTED, std::string(who) + ": the reference would subsample the intra block of input " + std::to_string(g) + " (" + std::to_string(samples) + " pairs, max_samples allows fewer than " + std::to_string(max_intra) + "): not built");
+	}
+	for (uint32_t i = 0; i < G; i++) for (uint32_t j = 0; j < (equal ? i : G); j++) {
+		if (i == j) continue;
+		const long long samples = size1(i) * size2(j);
+		if (!(samples < max_inter)) return fail(h, KMR_ERR_UNSUPPORTED, std::string(who) + ": the reference would subsample the inter block of inputs " + std::to_string(i) + " and " + std::to_string(j) + " (" + std::to_string(samples) + " pairs, max_samples allows fewer than " + std::to_string(max_inter) + "): not built");
+	}
+	rc = tnf_count(h, who, reads, starts, false, 0, 0, 0, R.get()); if (rc) return rc;
+	rc = tnf_group_sums(h, R.get(), whole.get()); if (rc) return rc;
+	rc = tnf_finish(h, whole.get()); if (rc) return rc;
+	Scratch tmp(h);
+	unsigned long long *dh; uint8_t *dok;
+	HIPCHK(h, tmp.take(&dh, (size_t)4 * nbin)); HIPCHK(h, tmp.take(&dok, (size_t)G));
+	HIPCHK(h, hipMemsetAsync(dh, 0, 8ull * 4 * nbin, h->stream));
+	HIPCHK(h, hipMemcpyAsync(dok, intra_ok.data(), G, hipMemcpyHostToDevice, h->stream));
+	TnfPairs P{};
+	P.D = w1->D; P.first_row = 0; P.n_rows = w1->n; P.out = nullptr; P.intra_ok = dok; P.bins = cfg->bins;
+	P.end = cfg->formula == KMR_TNF_EUCLIDEAN ? (float)std::sqrt(2.0) : 1.0f;
+	P.step = (P.end - 0.0f) / (float)(int)cfg->bins;
+	P.triangle = equal ? 1 : 0; P.hist = dh;
+	rc = tnf_pairs(h, w1, w2, (int)cfg->formula, P); if (rc) return rc;
+	P.triangle = 0; P.hist = dh + 2 * nbin;
+	rc = tnf_pairs(h, w1, whole.get(), (int)cfg->formula, P); if (rc) return rc;
+	HIPCHK(h, hipMemcpyAsync(out, dh, 8ull * 4 * nbin, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipStreamSynchronize(h->stream));
+	tmp.done();
 	return KMR_OK;
 }
 

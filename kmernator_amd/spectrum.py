@@ -825,6 +825,42 @@ class ReadSet(_DeviceObject):
         self.sp._call("reads_circularize", self.sp.h, self._live(), self.sp.k if extra is None else int(extra), C.byref(r))
         return ReadSet._adopt(self.sp, self.text, r, self.store_comment)
 
+    # -- TnfDistance (apps/TnfDistance.cpp)
+    @staticmethod
+    def _starts(input_starts):
+        if input_starts is None:
+            return None, 0
+        s = np.ascontiguousarray(input_starts, dtype=np.uint64)
+        return s, s.size - 1
+
+    def tnf(self, input_starts=None):
+        """buildTnfs (:462-484): one vector of canonical k-mer counts per sequence, k the spectrum's (kmr_tnf_reads): a TnfVectors
+        whose groups are the inputs (`input_starts`: n_inputs + 1 ascending sequence indices; None = one input)"""
+        s, n = self._starts(input_starts)
+        out = C.c_void_p()
+        self.sp._call("tnf_reads", self.sp.h, self._live(), None if s is None else s.ctypes.data_as(C.POINTER(C.c_uint64)), n, C.byref(out))
+        return TnfVectors(self.sp, out)
+
+    def tnfWindows(self, window, step, min_count=None, input_starts=None):
+        """shredReadByWindow and purgeShortTNFS (:486-518): one vector per window of `window` bases every `step` bases that holds at
+        least `min_count` k-mers (default window * 3 // 4, what the tool passes), in input order (kmr_tnf_windows)"""
+        s, n = self._starts(input_starts)
+        out = C.c_void_p()
+        self.sp._call("tnf_windows", self.sp.h, self._live(), None if s is None else s.ctypes.data_as(C.POINTER(C.c_uint64)), n, int(window), int(step),
+                      int(window) * 3 // 4 if min_count is None else int(min_count), C.byref(out))
+        return TnfVectors(self.sp, out)
+
+    def tnfLikelihoods(self, input_starts=None, window=10000, step=1000, window2=0, step2=1000, bins=100, formula=0, max_samples=(1 << 63) - 1):
+        """the four histograms of --intra-inter-file (:664-902; kmr_tnf_likelihoods): a uint64 array [4][bins + 2] of intra, inter,
+        intra-vs-whole and inter-vs-whole, outlier bins first and last"""
+        s, n = self._starts(input_starts)
+        cfg = _lib.KmrTnfLikelihoodConfig()
+        _ok(self.sp.lib.kmr_tnf_likelihood_config_init(C.byref(cfg)), "kmr_tnf_likelihood_config_init")
+        cfg.window, cfg.step, cfg.window2, cfg.step2, cfg.bins, cfg.formula, cfg.max_samples = int(window), int(step), int(window2), int(step2), int(bins), int(formula), int(max_samples)
+        out = np.zeros((4, int(bins) + 2), dtype=np.uint64)
+        self.sp._call("tnf_likelihoods", self.sp.h, self._live(), None if s is None else s.ctypes.data_as(C.POINTER(C.c_uint64)), n, C.byref(cfg), out.ctypes.data_as(C.POINTER(C.c_uint64)))
+        return out
+
     def identifyPairs(self, store_comment=None, device_text=None):
         """ReadSet::identifyPairs (src/ReadSet.cpp:446-570) of this batch as a fresh set, on the device (kmr_identify_pairs): a
         ReadPairs.  `store_comment` defaults to what the batch was ingested with; `device_text` = device pointer of the FASTQ
@@ -838,6 +874,141 @@ class ReadSet(_DeviceObject):
             self.sp._call("identify_pairs", self.sp.h, self.r, buf.ctypes.data_as(C.c_void_p) if buf.size else None, buf.size, 1 if sc else 0, C.byref(out))
         return ReadPairs(self.sp, out)
 
+
+
+def tnf_dims(k):
+    """D(k), the number of canonical k-mers (kmr_tnf_dims)"""
+    d = C.c_uint32()
+    _ok(_lib.load().kmr_tnf_dims(int(k), C.byref(d)), "kmr_tnf_dims")
+    return d.value
+
+
+def tnf_columns(k, hash_kind=0):
+    """column -> 2k-bit code of its canonical k-mer, in the iteration order of the reference's TNF::stdMap (kmr_tnf_columns)"""
+    codes = np.zeros(tnf_dims(k), dtype=np.uint16)
+    _ok(_lib.load().kmr_tnf_columns(int(k), int(hash_kind), codes.ctypes.data_as(C.POINTER(C.c_uint16))), "kmr_tnf_columns")
+    return codes
+
+
+def tnf_header(k, hash_kind=0):
+    """TNF::toHeader (:295-303) as bytes (kmr_tnf_header)"""
+    buf = C.create_string_buffer(16 + (int(k) + 1) * tnf_dims(k))
+    nb = C.c_uint64()
+    _ok(_lib.load().kmr_tnf_header(int(k), int(hash_kind), buf, len(buf), C.byref(nb)), "kmr_tnf_header")
+    return buf.raw[:nb.value]
+
+
+class TnfVectors(_DeviceObject):
+    """Vectors of canonical k-mer counts on the device (kmr_tnf): .n vectors of .dims columns in .n_groups groups; .inexact = the
+    columns above 2^24, where the reference's float no longer holds the count (its figures are followed while that is 0)."""
+    _HANDLE, _FREE = "_t", "kmr_tnf_free"
+
+    def __init__(self, sp, handle):
+        self.sp, self._t = sp, handle
+        n, d, g, bad = C.c_uint64(), C.c_uint32(), C.c_uint32(), C.c_uint64()
+        _ok(sp.lib.kmr_tnf_info(handle, C.byref(n), C.byref(d), C.byref(g), C.byref(bad)), "kmr_tnf_info")
+        self.n, self.dims, self.n_groups, self.inexact = n.value, d.value, g.value, bad.value
+
+    def _copy(self, counts=None, lengths=None, origin=None, groups=None):
+        p = lambda a, t: None if a is None else a.ctypes.data_as(C.POINTER(t))
+        _ok(self.sp.lib.kmr_tnf_copy(self._live(), p(counts, C.c_uint64), p(lengths, C.c_float), p(origin, C.c_uint64), p(groups, C.c_uint64)), "kmr_tnf_copy")
+
+    def counts(self):
+        """uint64 [n][dims], columns in tnf_columns order"""
+        a = np.zeros((self.n, self.dims), dtype=np.uint64)
+        self._copy(counts=a)
+        return a
+
+    def lengths(self):
+        """float32 [n]: buildLength (:396-416)"""
+        a = np.zeros(self.n, dtype=np.float32)
+        self._copy(lengths=a)
+        return a
+
+    def origin(self):
+        """uint64 [n][3]: the sequence a vector came from, its first base, its bases"""
+        a = np.zeros((self.n, 3), dtype=np.uint64)
+        self._copy(origin=a)
+        return a
+
+    def groups(self):
+        """uint64 [n_groups + 1]: group g holds the vectors [groups[g], groups[g + 1])"""
+        a = np.zeros(self.n_groups + 1, dtype=np.uint64)
+        self._copy(groups=a)
+        return a
+
+    def groupSums(self):
+        """one vector per group, its vectors added (wholeTnfs, :717; kmr_tnf_group_sums)"""
+        out = C.c_void_p()
+        self.sp._call("tnf_group_sums", self.sp.h, self._live(), C.byref(out))
+        return TnfVectors(self.sp, out)
+
+    def distances(self, other=None, formula=0, first_row=0, n_rows=None):
+        """getDistance (:434-446) of rows [first_row, first_row + n_rows) of this set, to the reference's bits (kmr_tnf_distances):
+        against every vector of `other` as a float32 [n_rows][other.n], or with other None the strict lower triangle, row i holding
+        j < i, as one packed float32 array.  formula 0 = Euclidean, 1 = Spearman."""
+        n_rows = self.n - first_row if n_rows is None else int(n_rows)
+        if other is not None:
+            out = np.zeros((n_rows, other.n), dtype=np.float32)
+        else:
+            e = first_row + n_rows
+            out = np.zeros(e * (e - 1) // 2 - first_row * (first_row - 1) // 2 if e else 0, dtype=np.float32)
+        self.sp._call("tnf_distances", self.sp.h, self._live(), None if other is None else other._live(), int(formula), int(first_row), n_rows,
+                      out.ctypes.data_as(C.POINTER(C.c_float)) if out.size else None)
+        return out
+
+
+def _ostream(x):
+    """a float or double as an ostream prints it by default: %g of the value widened to double (a NaN with its sign, as glibc does)"""
+    x = float(x)
+    if x != x:
+        return b"-nan" if np.signbit(x) else b"nan"
+    return ("%g" % x).encode()
+
+
+def TnfDistance(read_set, input_starts=None, reference=None, inter_distance=False, intra_inter=None, formula=0):
+    """apps/TnfDistance.cpp's texts as a dict of bytes, computed on the device and formatted here:
+      "output"          the default table ("Label\\t" + header, then name, count, length and value / length per sequence, :636-646) or, with a
+                        ReadSet `reference`, the distance of every sequence to the reference's one vector as "distance\\tname" lines ordered by
+                        distance, then by sequence (:621-634; the reference's std::sort leaves ties open)
+      "inter_distance"  with inter_distance: the lower triangle of distances, one line per sequence (:649-662)
+      "intra_inter"     with intra_inter = dict(window, step, window2, step2, bins, max_samples), all optional: the likelihood table (:664-902)
+    Not built: --cluster-file, the .data files, the five-part labels of sequences within 0.20 of the reference, subsampling."""
+    sp = read_set.sp
+    hash_kind = int(sp.cfg.hash_kind)
+    names = read_set.arrays()[3]
+    out = {}
+    with read_set.tnf(input_starts) as t:
+        if reference is not None:
+            with reference.tnf() as rt, rt.groupSums() as ref:
+                d = t.distances(ref, formula)[:, 0] if t.n else np.zeros(0, dtype=np.float32)
+            order = sorted(range(t.n), key=lambda i: (float(d[i]), i))
+            out["output"] = b"".join(_ostream(d[i]) + b"\t" + names[i] + b"\n" for i in order)
+        else:
+            cnt, ln = t.counts(), t.lengths()
+            lines = [b"Label\t" + tnf_header(sp.k, hash_kind) + b"\n"]
+            for i in range(t.n):
+                v = cnt[i].astype(np.float32)
+                lines.append(names[i] + b"\t" + _ostream(np.float64(v.astype(np.float64).sum())) + b"\t" + _ostream(ln[i]) + b"".join(b"\t" + _ostream(x) for x in v / ln[i]) + b"\n")
+            out["output"] = b"".join(lines)
+        if inter_distance:
+            tri = t.distances(None, formula)
+            out["inter_distance"] = b"".join(names[i] + b"".join(b"\t" + _ostream(x) for x in tri[i * (i - 1) // 2:i * (i + 1) // 2]) + b"\n" for i in range(t.n))
+    if intra_inter is not None:
+        o = dict(window=10000, step=1000, window2=0, step2=1000, bins=100, max_samples=(1 << 63) - 1)
+        o.update(intra_inter)
+        h = read_set.tnfLikelihoods(input_starts, formula=formula, **o)
+        window2 = o["window"] if o["window2"] < o["window"] else o["window2"]
+        bins = int(o["bins"])
+        end = np.float32(np.sqrt(2.0)) if formula == 0 else np.float32(1.0)
+        step = np.float32(end / np.float32(bins))
+        tot = [float(int(h[j, 1:bins + 1].sum())) for j in range(4)]
+        lines = [b"Distance\twindow\twindow2\tIntraLikelihood\tInterLikelihood\tIntraVsWholeLikelihood\tInterVsWholeLikelihood\n"]
+        for i in range(bins):
+            start = np.float32(np.float32(0.0) + np.float32(i) * step)
+            lines.append(_ostream(start) + b"\t%d\t%d" % (int(o["window"]), int(window2)) + b"".join(b"\t" + (_ostream(int(h[j, i + 1]) / tot[j]) if tot[j] else b"-nan") for j in range(4)) + b"\n")
+        out["intra_inter"] = b"".join(lines)
+    return out
 
 
 class ReadPairs(_DeviceObject):
