@@ -1247,6 +1247,76 @@ int kmr_tnf_distances_dev(kmr_handle *h, const kmr_tnf *a, const kmr_tnf *b, int
 int kmr_tnf_likelihood_config_init(kmr_tnf_likelihood_config *cfg);
 int kmr_tnf_likelihoods(kmr_handle *h, const kmr_reads *reads, const uint64_t *input_starts, uint32_t n_inputs, const kmr_tnf_likelihood_config *cfg, uint64_t *out);
 
+/* ---- KmerMatch (src/KmerMatch.h, src/MatcherInterface.h): the reads that share a k-mer with the ends of contigs ----
+ *
+ * DistributedNucleatingAssembler's matching step: for every contig the reads of the target set that share a k-mer with the first or
+ * last match-max-positions-from-edge bases of the contig, sampled where there are too many, with their mates, in ascending order of
+ * their global read index.  The reference looks every edge k-mer of a contig up in a spectrum whose values hold every (read, position)
+ * instance of the k-mer (TrackingDataWithAllReads, src/KmerTrackingData.h:779-887).  Here the join is turned around: the contigs' edge
+ * k-mers are a small table on the device and the reads stream through the build's extraction once per call, probing it.
+ *
+ * A read r matches contig c exactly when some k-mer occurrence of r passes the build's weight test (TrackingData::isDiscard: f32
+ * |weight| > min_weight; a reference-quality read weighs 1, a k-mer over a markup 0; a discarded read gives no k-mers), its canonical
+ * key is an edge key of c, and the handle's finalized spectrum holds the key -- which stands for purgeMinDepth(minDepth) of KmerMatch's
+ * constructor (KmerMatch.h:100-107, src/KmerSpectrum.h:1805-1815): with min_depth <= 1 the singleton map counts (KmerMatch.h:155-161),
+ * with 2 it is gone, above 2 the weak entries below the depth are gone too.  The caller's contract: the handle was built from exactly
+ * the reads that are streamed, and finalized with the depth KmerMatch would get.
+ *
+ * Contig k-mers (KmerMatch.h:136, src/Kmer.h:885, KmerWeights(twoBit, len, true)): every window of the packed sequence, canonical, no
+ * weights, qualities or markups -- a non-ACGT base is the 2-bit code 0 ('A'), and a window over an N is still looked up.  A contig
+ * shorter than k has no k-mers and an empty result.
+ * Edge windows (KmerMatch.h:124-149): with M = max_positions_from_edge - k + 1 as an int and n k-mers, k-mer j is considered if
+ * j <= (unsigned)M || j >= upperMinKmer, upperMinKmer = n - M if (int)n > M and 0 otherwise.  So the left side takes M + 1 k-mers and
+ * the right side M (the reference's asymmetry), M = 0 takes the first k-mer only, and M < 0 (an edge setting below k - 1, 0 included)
+ * takes every k-mer, (unsigned)M being huge.
+ * Hit set (:114-120): a contig's hits are a set of global read indices (first_global_read_idx + index in the batch); a key that lies
+ * in several contigs gives the read to each.
+ * Sampling (KmerMatch.h:127,168-171, MatcherInterface.h:280-287): a set of size > maxHits reads, maxHits = 2.0f * max_read_matches,
+ * keeps a read when u <= maxHits / (float)size, in f32.  The reference draws u from a time-seeded uniform_01<float>; here
+ * u = (float)(draw >> 8) * 2^-24, draw = word 0 of Philox4x32-10 over the counter (read & 0xffffffff, read >> 32, contig index, 1)
+ * and the key (seed & 0xffffffff, seed >> 32), so that a result repeats and does not depend on how the reads are cut into batches.
+ * size is the set's size over all batches: the sampling happens in kmr_match_finish.  max_read_matches = 0 means no sampling, as the
+ * option's help says (the reference's code would keep almost nothing then: the fraction is 0).
+ * Mates (MatcherInterface.h:772-792): with include_mate and a pairing given, the mate of every read that survived the sampling joins
+ * the set (the mates of sampled-away reads do not).
+ * Result (MatcherInterface.h:311-321): every set in ascending global read index without the reads whose discard flag is set -- a
+ * discarded read never hits, but it can come in as a mate.
+ * Not built: the second cut to exactly 20 * max_read_matches reads (Random::sample, :304), --max-read-depth-matches, the overhang screen
+ * through KmerAlign (return-overlap-only, :599-662) and the Vmatch back-end.  The sizes before and after sampling are reported per
+ * contig, so that a caller can apply a cut of its own.
+ * Bounds: at most 2^24 contigs, each shorter than 2^31 - 1 bases, fewer than 2^32 - 1 edge k-mers in all, global read indices below 2^40,
+ * fewer than 2^32 - 1 hit records: KMR_ERR_UNSUPPORTED beyond. */
+typedef struct kmr_match_config {
+	uint32_t struct_size;
+	int32_t max_positions_from_edge;      /* --match-max-positions-from-edge, 500 */
+	uint32_t max_read_matches;            /* --max-read-matches, 450; 0 = no sampling */
+	uint32_t include_mate;                /* --include-mate, 1 */
+	uint64_t seed;                        /* of the sampling's random numbers, 0 */
+} kmr_match_config;
+typedef struct kmr_match kmr_match;
+int kmr_match_config_init(kmr_match_config *cfg);
+/* The table of the contigs' edge keys (KmerMatch.h:124-149), filtered against h's spectrum once.  KMR_ERR_STATE before kmr_finalize;
+ * KMR_ERR_UNSUPPORTED for a handle that holds part of a spectrum (world_size > 1, num_parts > 1, kmer_subsample > 1);
+ * KMR_ERR_INVALID_ARG for contigs of another device.  The object refers to h, which must outlive it; free it with kmr_match_free. */
+int kmr_match_create(kmr_handle *h, const kmr_reads *contigs, const kmr_match_config *cfg, kmr_match **out);
+/* contigs, considered k-mers (with repeats), distinct keys among them, and those of them the spectrum holds; any may be NULL */
+int kmr_match_edge_info(const kmr_match *m, uint64_t *n_contigs, uint64_t *n_edge_kmers, uint64_t *n_distinct_keys, uint64_t *n_keys_in_spectrum);
+/* Stream one batch of the target reads (_matchLocal's lookups :151-161 from the reads' side); may be called repeatedly.  pairs: the
+ * batch's own pairing (kmr_identify_pairs), NULL = no mates; discarded: host array of one flag per read, NULL = none.  Waits for the
+ * batch's hit count; if the hit buffers were too small they grow and the batch is streamed again (kmr_tune "match_hit_capacity").
+ * KMR_ERR_STATE after kmr_match_finish; KMR_ERR_INVALID_ARG for a batch or pairing of another device or another number of reads. */
+int kmr_match_add_read_batch(kmr_match *m, const kmr_reads *reads, uint64_t first_global_read_idx, const kmr_pairs *pairs, const uint8_t *discarded);
+/* sets made unique, sampled, mates added, sorted, discarded reads dropped (KmerMatch.h:163-171, MatcherInterface.h:772-792, :311-321) */
+int kmr_match_finish(kmr_match *m);
+/* after kmr_match_finish (KMR_ERR_STATE before): contigs, reads of all sets, contigs whose set was sampled; any may be NULL */
+int kmr_match_info(const kmr_match *m, uint64_t *n_contigs, uint64_t *n_reads_total, uint64_t *n_sampled_contigs);
+/* offsets (n_contigs + 1), read_ids (n_reads_total: contig i's reads are read_ids[offsets[i] .. offsets[i + 1]), ascending), and per
+ * contig the set's size before sampling and after it (before the mates join); any may be NULL.  KMR_ERR_STATE before kmr_match_finish */
+int kmr_match_copy(const kmr_match *m, uint64_t *offsets, uint64_t *read_ids, uint64_t *size_before_sampling, uint64_t *size_after_sampling);
+/* the same four arrays (uint64) where they lie; any may be NULL; valid until kmr_match_free */
+int kmr_match_device_ptrs(const kmr_match *m, void **dev_offsets, void **dev_read_ids, void **dev_size_before_sampling, void **dev_size_after_sampling);
+void kmr_match_free(kmr_match *m);
+
 /* Raw HIP stream of the handle (hipStream_t) so callers can order their own
  * work (torch.cuda.ExternalStream) against it. */
 void *kmr_stream(kmr_handle *h);
@@ -1289,6 +1359,8 @@ void *kmr_stream(kmr_handle *h);
  *   kmr_compare_reads*, 0 = 2^26; a read that alone exceeds it is a run of its own); both may be set at any time.
  *   "tnf_piece_bases" (kmr_tnf_reads / kmr_tnf_windows / kmr_tnf_likelihoods: bases of one piece of a sequence, the unit the wavefronts share
  *   out, 0 = 4096; tests set 64 or 65 so that a short input crosses piece edges; may be set at any time).
+ *   "match_hit_capacity" (hit records the buffers of a kmr_match hold before they first grow, 0 = 2^20; tests set a few so that a handful
+ *   of reads overflows them and the batch is streamed again; read by kmr_match_add_read_batch; may be set at any time).
  * Call before the first kmr_add_reads* of a build.  KMR_ERR_INVALID_ARG for an unknown knob. */
 int kmr_tune(kmr_handle *h, const char *knob, double value);
 /* What the current build decided, for tests and measurement tools (the reference logs such figures, LOG_VERBOSE): "lists" = super-k-mer
@@ -1316,7 +1388,8 @@ int kmr_tune(kmr_handle *h, const char *knob, double value);
  * global atomics,
  * "csr_path" / "csr_chunks" = how the last chunk index of this handle was made (1: radix partition, 0: an atomic per chunk, -1: none yet) and
  * how many chunks of the pool it looked at, "unit_batches" = batches fed to this handle so far that held a read longer than an extraction
- * tile and were cut into work units.
+ * tile and were cut into work units, "match_add_attempts" = how often the last kmr_match_add_read_batch on this handle streamed its
+ * batch before the hit records fit their buffers (1 unless they had to grow).
  * KMR_ERR_INVALID_ARG for an unknown name. */
 int kmr_build_info(kmr_handle *h, const char *what, double *value);
 

@@ -324,6 +324,42 @@ private:
 	KmerSpectrum &_sp; kmr_tnf *_t; uint64_t _n = 0, _inexact = 0; uint32_t _d = 0, _g = 0;
 };
 
+/* KmerMatch (src/KmerMatch.h:93-185, src/MatcherInterface.h): for every contig the reads that share a k-mer with one of its edge windows,
+ * sampled, with their mates, sorted (kmr_match_*).  `sp` is the finalized spectrum of exactly the reads that are streamed, and outlives
+ * the object */
+struct MatchResults {
+	std::vector<uint64_t> offsets, reads, sizeBeforeSampling, sizeAfterSampling;      /* contig i: reads[offsets[i] .. offsets[i + 1]), ascending */
+	uint64_t sampledContigs = 0;
+	size_t size() const { return offsets.empty() ? 0 : offsets.size() - 1; }
+	std::vector<uint64_t> operator[](size_t i) const { return std::vector<uint64_t>(reads.begin() + (ptrdiff_t)offsets[i], reads.begin() + (ptrdiff_t)offsets[i + 1]); }
+};
+class KmerMatch {
+public:
+	static kmr_match_config defaults() { kmr_match_config c; kmr_match_config_init(&c); return c; }
+	KmerMatch(KmerSpectrum &sp, const ReadSet &contigs, const kmr_match_config &cfg = defaults()) : _sp(sp) { sp.check(kmr_match_create(sp.raw(), contigs.raw(), &cfg, &_m), "kmr_match_create"); }
+	~KmerMatch() { kmr_match_free(_m); }
+	KmerMatch(const KmerMatch &) = delete; KmerMatch &operator=(const KmerMatch &) = delete;
+	/* one batch of the target reads; pairs: the batch's own pairing (kmr_identify_pairs) or nullptr, discarded: one flag per read or empty */
+	void addReads(const ReadSet &reads, uint64_t firstGlobalReadIdx = 0, const kmr_pairs *pairs = nullptr, const std::vector<uint8_t> &discarded = std::vector<uint8_t>()) {
+		if (!discarded.empty() && discarded.size() != reads.getSize()) throw KmerSpectrumError(KMR_ERR_INVALID_ARG, "KmerMatch::addReads: one discard flag per read");
+		_sp.check(kmr_match_add_read_batch(_m, reads.raw(), firstGlobalReadIdx, pairs, discarded.empty() ? nullptr : discarded.data()), "kmr_match_add_read_batch");
+	}
+	MatchResults finish() {
+		_sp.check(kmr_match_finish(_m), "kmr_match_finish");
+		uint64_t nc = 0, nr = 0;
+		MatchResults r;
+		_sp.check(kmr_match_info(_m, &nc, &nr, &r.sampledContigs), "kmr_match_info");
+		r.offsets.resize(nc + 1); r.reads.resize(nr); r.sizeBeforeSampling.resize(nc); r.sizeAfterSampling.resize(nc);
+		_sp.check(kmr_match_copy(_m, r.offsets.data(), nr ? r.reads.data() : nullptr, nc ? r.sizeBeforeSampling.data() : nullptr, nc ? r.sizeAfterSampling.data() : nullptr), "kmr_match_copy");
+		return r;
+	}
+	/* contigs, considered k-mers, distinct keys, keys the spectrum holds */
+	void edgeInfo(uint64_t &contigs, uint64_t &edgeKmers, uint64_t &distinctKeys, uint64_t &keysInSpectrum) const { kmr_match_edge_info(_m, &contigs, &edgeKmers, &distinctKeys, &keysInSpectrum); }
+	const kmr_match *raw() const { return _m; }
+private:
+	KmerSpectrum &_sp; kmr_match *_m = nullptr;
+};
+
 /* FilterKnownOddities (src/FilterKnownOddities.h): the artifact screen FilterReads runs before the spectrum build */
 class FilterKnownOddities {
 public:

@@ -78,6 +78,11 @@ class KmrCompareCounts(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class KmrMatchConfig(C.Structure):
+    """kmr_match_config"""
+    _fields_ = [("struct_size", C.c_uint32), ("max_positions_from_edge", C.c_int32), ("max_read_matches", C.c_uint32), ("include_mate", C.c_uint32), ("seed", C.c_uint64)]
+
+
 KMR_TNF_EUCLIDEAN, KMR_TNF_SPEARMAN = 0, 1
 
 
@@ -133,6 +138,8 @@ EXPORTS = [
     "kmr_compare_spectrums", "kmr_compare_reads", "kmr_compare_reads_dev", "kmr_compare_line", "kmr_reads_circularize",
     "kmr_tnf_dims", "kmr_tnf_columns", "kmr_tnf_header", "kmr_tnf_reads", "kmr_tnf_windows", "kmr_tnf_group_sums", "kmr_tnf_info", "kmr_tnf_copy", "kmr_tnf_free",
     "kmr_tnf_distances", "kmr_tnf_distances_dev", "kmr_tnf_likelihood_config_init", "kmr_tnf_likelihoods",
+    "kmr_match_config_init", "kmr_match_create", "kmr_match_edge_info", "kmr_match_add_read_batch", "kmr_match_finish", "kmr_match_info", "kmr_match_copy",
+    "kmr_match_device_ptrs", "kmr_match_free",
     "kmr_map_digest", "kmr_synth_reads_dev", "kmr_build_info", "kmr_sk_exchange_uniform", "kmr_sk_exchange_peer_uniform", "kmr_sk_exchange_range", "kmr_count_lists_prefix",
 ]
 
@@ -337,6 +344,17 @@ def load():
     lib.kmr_tnf_distances_dev.argtypes = [vp, vp, vp, C.c_int, C.c_uint64, C.c_uint64, vp]
     lib.kmr_tnf_likelihood_config_init.argtypes = [lcp]
     lib.kmr_tnf_likelihoods.argtypes = [vp, vp, u64p, C.c_uint32, lcp, u64p]
+    mcp = C.POINTER(KmrMatchConfig)
+    lib.kmr_match_config_init.argtypes = [mcp]
+    lib.kmr_match_create.argtypes = [vp, vp, mcp, C.POINTER(vp)]
+    lib.kmr_match_edge_info.argtypes = [vp, u64p, u64p, u64p, u64p]
+    lib.kmr_match_add_read_batch.argtypes = [vp, vp, C.c_uint64, vp, u8p]
+    lib.kmr_match_finish.argtypes = [vp]
+    lib.kmr_match_info.argtypes = [vp, u64p, u64p, u64p]
+    lib.kmr_match_copy.argtypes = [vp, u64p, u64p, u64p, u64p]
+    lib.kmr_match_device_ptrs.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    lib.kmr_match_free.argtypes = [vp]
+    lib.kmr_match_free.restype = None
     _lib = lib
     return lib
 

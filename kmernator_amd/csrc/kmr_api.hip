@@ -2302,6 +2302,7 @@ int kmr_tune(kmr_handle *h, const char *knob, double value) {
 	else if (k == "compare_lds_kmers") h->tune.compare_lds_kmers = value >= 0 && value <= CMP_CAP_MOST ? (int)value : -1;
 	else if (k == "compare_stage_kmers") h->tune.compare_stage_kmers = value >= 1 ? std::min<uint64_t>((uint64_t)value, 1ull << 31) : 0;
 	else if (k == "tnf_piece_bases") h->tune.tnf_piece_bases = value >= 1 ? (uint32_t)std::min<double>(value, 1u << 30) : 0;
+	else if (k == "match_hit_capacity") h->tune.match_hit_capacity = value >= 1 ? (uint64_t)std::min<double>(value, 4294967294.0) : 0;
 	else if (k == "superkmer_window") {      /* largest minimizer window the geometry may take (32 / 16 / 8 / 4): A/B runs, tests of the narrower windows at large k */
 		if (h->superkmer_mode && !h->sk_state) { uint32_t w, m, o; if (!sk_geometry(h->k, 0, w, m, o, (uint32_t)value)) return fail(h, KMR_ERR_INVALID_ARG, "no minimizer geometry under that window"); h->sk_win = w; h->sk_m = m; h->sk_off = o; }
 	}
@@ -2331,6 +2332,7 @@ int kmr_build_info(kmr_handle *h, const char *what, double *value) {
 	else if (k == "csr_path") *value = (double)h->last_csr_path;
 	else if (k == "csr_chunks") *value = (double)h->last_csr_chunks;
 	else if (k == "unit_batches") *value = (double)h->unit_batches;
+	else if (k == "match_add_attempts") *value = (double)h->last_match_attempts;
 	else if (k == "device_blocks_live") *value = (double)g_blocks_live.load();
 	else if (k == "filter_score_ms") *value = h->last_score_ms;
 	else if (k == "select_ms") *value = h->last_select_ms;
@@ -3586,12 +3588,134 @@ int tnf_stage(kmr_handle *h, const ReadsView &all, const uint64_t **koff_out, co
 	return KMR_OK;
 }
 
+/* ---- KmerMatch (kmr_match.hpp): the table of kmr_match_create and the streaming pass of kmr_match_add_read_batch (kmr_stages.hip) ---- */
+template <int W> int match_create_t(kmr_handle *h, kmr_match *m, const uint8_t *bases, const uint64_t *offsets, uint64_t nc) {
+	const dim3 block(256);
+	const int64_t M64 = (int64_t)m->cfg.max_positions_from_edge - (int64_t)h->k + 1;
+	const int32_t M = (int32_t)std::max<int64_t>(M64, -1);      /* every negative value means the same: all k-mers */
+	DevBuf b_cnt, b_eoff, b_err;
+	uint32_t *cnt, *err; uint64_t *eoff;
+	HIPCHK(h, alloc_n(b_cnt, &cnt, nc + 1)); HIPCHK(h, alloc_n(b_eoff, &eoff, nc + 1)); HIPCHK(h, alloc_n(b_err, &err, (size_t)1));
+	HIPCHK(h, hipMemsetAsync(err, 0, 4, h->stream)); HIPCHK(h, hipMemsetAsync(eoff, 0, 8, h->stream));
+	uint64_t E = 0; uint32_t herr = 0;
+	if (nc) {
+		hipLaunchKernelGGL(match_edge_count_kernel, dim3(grid_for(nc)), block, 0, h->stream, offsets, nc, h->k, M, cnt, err);
+		HIPCHK(h, hipGetLastError());
+		int rc = exclusive_scan_queue(h, cnt, nc, eoff); if (rc) return rc;
+		HIPCHK(h, hipMemcpyAsync(&E, eoff + nc, 8, hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, hipStreamSynchronize(h->stream));
+	}
+	if (herr) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_match_create: a contig of 2^31 - 1 bases or more");
+	if (E >= 0xffffffffull) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_match_create: 2^32 - 1 edge k-mers or more");
+	m->n_contigs = nc; m->n_edge_kmers = E; m->n_distinct_keys = m->n_keys_in_spectrum = 0;
+	uint64_t n_lists = 0;      /* (key, contig) pairs of the kept keys */
+	DevBuf b_keys, b_contig, b_perm, b_perm2, b_kin, b_kout, b_sort, b_flags, b_scans;
+	uint64_t *keys = nullptr, *scans = nullptr; uint32_t *contig = nullptr, *perm = nullptr, *perm2 = nullptr, *flags = nullptr;
+	unsigned long long *kin = nullptr, *kout = nullptr;
+	if (E) {
+		HIPCHK(h, alloc_n(b_keys, &keys, E * W)); HIPCHK(h, alloc_n(b_contig, &contig, E)); HIPCHK(h, alloc_n(b_perm, &perm, E)); HIPCHK(h, alloc_n(b_perm2, &perm2, E));
+		HIPCHK(h, alloc_n(b_kin, &kin, E)); HIPCHK(h, alloc_n(b_kout, &kout, E)); HIPCHK(h, alloc_n(b_flags, &flags, 3 * E)); HIPCHK(h, alloc_n(b_scans, &scans, 3 * (E + 1)));
+		size_t sort_bytes = 0;
+		if (kmr::sort_pairs_u64_u32(nullptr, &sort_bytes, nullptr, nullptr, nullptr, nullptr, E, h->stream) != 0) return fail(h, KMR_ERR_HIP, "kmr_match_create: radix sort (size query)");
+		HIPCHK(h, b_sort.alloc(std::max<size_t>(sort_bytes, 256)));
+		const dim3 egrid(grid_for(E));
+		hipLaunchKernelGGL(match_edge_keys_kernel<W>, egrid, block, 0, h->stream, bases, offsets, nc, h->k, M, (const uint64_t *)eoff, E, keys, contig, perm);
+		HIPCHK(h, hipGetLastError());
+		/* least significant first: the contig, then the key words from the last to the first; the sort is stable */
+		for (int pass = 0; pass <= W; pass++) {
+			hipLaunchKernelGGL(match_gather_kernel, egrid, block, 0, h->stream, (const uint64_t *)keys, (const uint32_t *)contig, (uint32_t)W, (uint32_t)(W - pass), (const uint32_t *)perm, E, kin);
+			HIPCHK(h, hipGetLastError());
+			size_t sb = b_sort.cap();
+			if (kmr::sort_pairs_u64_u32(b_sort.get(), &sb, kin, kout, perm, perm2, E, h->stream) != 0) return fail(h, KMR_ERR_HIP, "kmr_match_create: radix sort");
+			std::swap(perm, perm2);
+		}
+		MapView<W> weak = view_of<W>(h->weak, h->ext ? 15u : 3u), sing = view_of<W>(h->sing, 0);
+		if (!h->has_singletons) sing.nb = 0;
+		uint32_t *khead = flags, *kkept = flags + E, *phead = flags + 2 * E;
+		uint64_t *hscan = scans, *kscan = scans + (E + 1), *pscan = scans + 2 * (E + 1);
+		hipLaunchKernelGGL(match_flags_kernel<W>, egrid, block, 0, h->stream, (const uint64_t *)keys, (const uint32_t *)contig, (const uint32_t *)perm, E, weak, sing, h->hkb, khead, kkept, phead);
+		HIPCHK(h, hipGetLastError());
+		int rc = exclusive_scan_queue(h, khead, E, hscan); if (rc) return rc;
+		rc = exclusive_scan_queue(h, kkept, E, kscan); if (rc) return rc;
+		rc = exclusive_scan_queue(h, phead, E, pscan); if (rc) return rc;
+		HIPCHK(h, hipMemcpyAsync(&m->n_distinct_keys, hscan + E, 8, hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, hipMemcpyAsync(&m->n_keys_in_spectrum, kscan + E, 8, hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, hipMemcpyAsync(&n_lists, pscan + E, 8, hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, hipStreamSynchronize(h->stream));
+	}
+	m->log2cap = 6;
+	while ((1ull << m->log2cap) < 2 * m->n_keys_in_spectrum) m->log2cap++;      /* at most half full */
+	const size_t slot_bytes_ = (size_t)(W + 1) * 8 << m->log2cap;
+	HIPCHK(h, m->slots.alloc(slot_bytes_));
+	HIPCHK(h, m->tcontig.alloc(std::max<size_t>(4 * n_lists, 256)));
+	HIPCHK(h, hipMemsetAsync(m->slots.get(), 0xff, slot_bytes_, h->stream));
+	if (m->n_keys_in_spectrum) {
+		hipLaunchKernelGGL(match_table_fill_kernel<W>, dim3(grid_for(E)), block, 0, h->stream, (const uint64_t *)keys, (const uint32_t *)contig, (const uint32_t *)perm, E,
+		                   (const uint32_t *)flags, (const uint32_t *)(flags + E), (const uint32_t *)(flags + 2 * E), (const uint64_t *)(scans + 2 * (E + 1)),
+		                   m->slots.get<uint64_t>(), 64u - m->log2cap, m->tcontig.get<uint32_t>());
+		HIPCHK(h, hipGetLastError());
+	}
+	HIPCHK(h, hipStreamSynchronize(h->stream));      /* the temporaries go */
+	return KMR_OK;
+}
+
+template <int W> int match_add_t(kmr_handle *h, kmr_match *m, const ReadsView &all, uint64_t first_global, const int64_t *mate) {
+	if (!m->hit_count) { HIPCHK(h, m->hit_count.alloc(256)); HIPCHK(h, hipMemsetAsync(m->hit_count.get(), 0, 8, h->stream)); }
+	if (m->hit_cap == 0) {
+		const uint64_t cap = h->tune.match_hit_capacity ? h->tune.match_hit_capacity : MATCH_HIT_CAP;
+		HIPCHK(h, m->hit_key.alloc(std::max<size_t>(8 * cap, 256))); HIPCHK(h, m->hit_mate.alloc(std::max<size_t>(8 * cap, 256)));
+		m->hit_cap = cap;
+	}
+	DevParams dp = dev_params(h);
+	dp.sub_wstart = dp.sub_wkeys = dp.sub_sstart = dp.sub_skeys = nullptr; dp.sub_wvals = nullptr; dp.sub_sweight = nullptr; dp.sub_wnb = dp.sub_snb = 0;      /* the spectrum's own reads: nothing is subtracted */
+	ReadsView rv = all;
+	int rc = prepare_units(h, rv); if (rc) return rc;
+	for (int attempt = 1;; attempt++) {
+		MatchOp<W> op;
+		op.table.slots = m->slots.get<uint64_t>(); op.table.contigs = m->tcontig.get<uint32_t>(); op.table.shift = 64u - m->log2cap;
+		op.hit_key = m->hit_key.get<unsigned long long>(); op.hit_mate = m->hit_mate.get<unsigned long long>(); op.count = m->hit_count.get<unsigned long long>();
+		op.cap = m->hit_cap; op.mate = mate; op.first_global = first_global;
+		rc = launch_extract<W, false>(h, rv, dp, op); if (rc) return rc;
+		uint64_t count = 0;
+		HIPCHK(h, hipMemcpyAsync(&count, m->hit_count.get(), 8, hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, hipStreamSynchronize(h->stream));
+		h->last_match_attempts = attempt;
+		if (count <= m->hit_cap) { m->n_hits = count; return KMR_OK; }
+		/* the records did not fit: room for all of them (the count of a batch repeats), the earlier batches' records kept, and once more */
+		if (count >= 0xffffffffull) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_match_add_read_batch: 2^32 - 1 hit records or more");
+		if (attempt >= 3) return fail(h, KMR_ERR_CAPACITY, "kmr_match_add_read_batch: the hit records did not fit after their buffers grew (internal sizing error)");
+		const uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(count, 2 * m->hit_cap), 0xfffffffeull);
+		DevBuf nk, nm;
+		HIPCHK(h, nk.alloc(8 * cap)); HIPCHK(h, nm.alloc(8 * cap));
+		if (m->n_hits) {
+			HIPCHK(h, hipMemcpyAsync(nk.get(), m->hit_key.get(), 8 * m->n_hits, hipMemcpyDeviceToDevice, h->stream));
+			HIPCHK(h, hipMemcpyAsync(nm.get(), m->hit_mate.get(), 8 * m->n_hits, hipMemcpyDeviceToDevice, h->stream));
+		}
+		HIPCHK(h, hipMemcpyAsync(m->hit_count.get(), &m->n_hits, 8, hipMemcpyHostToDevice, h->stream));
+		HIPCHK(h, hipStreamSynchronize(h->stream));
+		m->hit_key = std::move(nk); m->hit_mate = std::move(nm); m->hit_cap = cap;
+	}
+}
+
 }  // namespace
 
 namespace kmr_host {
 int tnf_stage_core(kmr_handle *h, const uint8_t *bases, const uint8_t *quals, const uint64_t *offsets, uint64_t n_reads, const uint64_t **koff, const uint64_t **stage, uint64_t *slots) {
 	if (h->W != 1) return fail(h, KMR_ERR_UNSUPPORTED, "tnf_stage_core: a key of more than one word");
 	const int rc = tnf_stage(h, reads_view(bases, quals, offsets, n_reads), koff, stage, slots);
+	if (rc) hipStreamSynchronize(h->stream);
+	return rc;
+}
+int match_create_core(kmr_handle *h, kmr_match *m, const uint8_t *bases, const uint64_t *offsets, uint64_t n_contigs) {
+	const int rc = with_w(h, [&](auto W) { return match_create_t<W()>(h, m, bases, offsets, n_contigs); });
+	if (rc) hipStreamSynchronize(h->stream);
+	return rc;
+}
+int match_add_core(kmr_handle *h, kmr_match *m, const uint8_t *bases, const uint8_t *quals, const uint64_t *offsets, uint64_t n_reads, uint64_t first_global,
+                   const int64_t *mate, const uint8_t *discarded) {
+	const ReadsView rv = reads_view(bases, quals, offsets, n_reads, discarded);      /* first_read_idx 0: the Op adds first_global itself */
+	const int rc = with_w(h, [&](auto W) { return match_add_t<W()>(h, m, rv, first_global, mate); });
 	if (rc) hipStreamSynchronize(h->stream);
 	return rc;
 }

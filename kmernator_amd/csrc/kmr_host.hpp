@@ -192,7 +192,8 @@ struct KMR_HIDDEN Tuning {
 	int compare_lds_kmers = -1;        /* kmr_compare_reads*: the most k-mers of a read that compare_reads_lds_kernel takes (-1: CMP_CAP; 0: every read goes through the sorted path; tests: a few) */
 	uint64_t compare_stage_kmers = 0;  /* kmr_compare_reads*: staging slots of one run of whole reads (0: CMP_STAGE_SLOTS; tests: a few, so that a batch takes several runs and a read alone exceeds one) */
 	uint32_t tnf_piece_bases = 0;      /* kmr_tnf_reads / kmr_tnf_windows: bases of one piece of a sequence (0: TNF_PIECE_BASES; tests: a few, so that short inputs cross piece edges) */
-	bool no_coarse_lists = true;      /* exchange: scatter into the job's fine lists (default) or, kmr_tune("coarse_lists", 1), into coarse ones that the owner splits before the count pass (sk_refine_kernel: not yet fast enough to pay) */
+	uint64_t match_hit_capacity = 0;   /* kmr_match_add_read_batch: hit records the buffers hold before they first grow (0: MATCH_HIT_CAP; tests: a few, so that the batch is streamed again) */
+	bool no_coarse_lists = true;     /* exchange: scatter into the job's fine lists (default) or, kmr_tune("coarse_lists", 1), into coarse ones that the owner splits before the count pass (sk_refine_kernel: not yet fast enough to pay) */
 };
 
 /* What the caller of one feed call knows about it, handed down from the entry point to the extraction (add_reads_dev_call,
@@ -269,7 +270,8 @@ struct KMR_HIDDEN kmr_handle : HandleMem, BuildMem, ExchangeMem {
 	int last_csr_path = -1; uint32_t last_csr_chunks = 0;      /* the last build_csr: 1 = radix partition, 0 = an atomic per chunk, and the chunks it looked at (kmr_build_info "csr_path", "csr_chunks") */
 	unsigned int l1_head_seen = 0;     /* the record pool's head as of the last sync_state(h, true) */
 	uint64_t unit_batches = 0;         /* batches that held a read longer than a tile and were cut into work units (kmr_build_info "unit_batches") */
-	int last_count_attempts = 0;       /* how often the last count pass of a kmr_finalize ran before its entries fit (kmr_build_info "count_attempts") */
+	int last_match_attempts = 0;       /* how often the last kmr_match_add_read_batch streamed its batch before the hit records fit (kmr_build_info "match_add_attempts") */
+	int last_count_attempts = 0;    /* how often the last count pass of a kmr_finalize ran before its entries fit (kmr_build_info "count_attempts") */
 	bool qual_mixed = false;           /* a build that has seen two different quality characters stops asking (qrange) */
 	/* exchange with world_size > 1: sk_bits are the COARSE lists reads are scattered into and that travel; each holds 2^sk_fine_shift
 	 * fine lists, made by sk_refine_kernel before the count pass (fine state: sk_fine_state) */
@@ -347,6 +349,22 @@ struct KMR_HIDDEN kmr_tnf : OnDevice {
 	uint64_t n = 0, inexact = 0;
 	uint32_t D = 0, k = 0, hash_kind = 0;
 	bool wide = false;
+};
+
+/* KmerMatch (kmr_match.hpp): the table of the contigs' edge keys, the hit records of the batches streamed so far, and after
+ * kmr_match_finish the result.  Refers to the handle it was made from */
+struct KMR_HIDDEN kmr_match : OnDevice {
+	kmr_handle *h = nullptr;
+	kmr_match_config cfg;
+	uint64_t n_contigs = 0, n_edge_kmers = 0, n_distinct_keys = 0, n_keys_in_spectrum = 0;
+	DevBuf slots, tcontig; uint32_t log2cap = 6;      /* the table: 2^log2cap slots of W + 1 words; the contigs of every key */
+	DevBuf hit_key, hit_mate, hit_count;              /* packed (contig, global read), global mate or MATCH_NO_MATE; one u64 counter */
+	uint64_t hit_cap = 0, n_hits = 0;
+	struct Batch { uint64_t first = 0, n = 0; DevBuf discarded; };      /* the discard flags live until the finish drops the reads */
+	std::vector<Batch> batches;
+	bool finished = false;
+	DevBuf offsets, read_ids, size_before, size_after;
+	uint64_t n_reads_total = 0, n_sampled = 0;
 };
 
 namespace kmr_host KMR_HIDDEN {
@@ -430,6 +448,13 @@ int compare_reads_core(kmr_handle *h2, const uint8_t *bases, const uint8_t *qual
  * *stage live in h->cmp_buf until the handle's next kmr_compare_reads* or tnf_stage_core; the work is queued on h's stream, and the call waits
  * for the sizes.  The handle's world_size, num_parts and kmer_subsample are not applied. */
 int tnf_stage_core(kmr_handle *h, const uint8_t *bases, const uint8_t *quals, const uint64_t *offsets, uint64_t n_reads, const uint64_t **koff, const uint64_t **stage, uint64_t *slots);
+
+/* KmerMatch (kmr_match.hpp): the parts that need the spectrum and the extraction.  match_create_core fills m's table from the contigs
+ * (device batch) and waits; match_add_core streams one device batch through MatchOp, appending to m's hit records (grown and the batch
+ * streamed again where they did not fit), and waits for the count.  mate / discarded: device arrays of the batch, or NULL */
+int match_create_core(kmr_handle *h, kmr_match *m, const uint8_t *bases, const uint64_t *offsets, uint64_t n_contigs);
+int match_add_core(kmr_handle *h, kmr_match *m, const uint8_t *bases, const uint8_t *quals, const uint64_t *offsets, uint64_t n_reads, uint64_t first_global,
+                   const int64_t *mate, const uint8_t *discarded);
 
 /* ---- defined in kmr_stages.hip (its kmr_ingest.hpp holds the two-bit kernels): what the spectrum's packed feed path launches.  All
  * pointers are device memory; the work is queued on the handle's stream. */

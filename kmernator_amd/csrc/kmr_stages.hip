@@ -1,6 +1,6 @@
 /*
  * kmr_stages.hip -- the read stages of include/kmernator_amd.h: FASTQ ingest and the kmr_reads batch, its two-bit form, the artifact
- * filter and its report, read selection, coverage normalization and their output text, identifyPairs, duplicate-fragment collapse, the mercount / mergraph text, and TnfDistance's vectors and distances.
+ * filter and its report, read selection, coverage normalization and their output text, identifyPairs, duplicate-fragment collapse, the mercount / mergraph text, TnfDistance's vectors and distances, and KmerMatch's entry points with its finish.
  *
  * Host logic only, as kmr_api.hip (the spectrum, which these stages read through kmr_host.hpp); the kernels are the stage headers',
  * each of which this translation unit alone includes.  A stage costs its kernels and a page here: what the stages share is below --
@@ -24,6 +24,8 @@
 #include "kmr_dedup.hpp"
 #include "kmr_dump.hpp"
 #include "kmr_tnf.hpp"
+#define KMR_MATCH_FINISH      /* the finish kernels; the table and the Op are kmr_api.hip's */
+#include "kmr_match.hpp"
 
 using namespace kmr;
 
@@ -524,6 +526,192 @@ int kmr_compare_line(const kmr_compare_counts *c, const char *label, uint64_t la
 	dst[n + 1 + label_len] = '\n';
 	return KMR_OK;
 }
+
+/* ---- KmerMatch (src/KmerMatch.h, src/MatcherInterface.h; kernels: kmr_match.hpp; the table and the streaming pass are kmr_api.hip's match_*_core) ---- */
+int kmr_match_config_init(kmr_match_config *c) {
+	if (!c) return KMR_ERR_INVALID_ARG;
+	memset(c, 0, sizeof(*c));
+	c->struct_size = (uint32_t)sizeof(kmr_match_config);
+	c->max_positions_from_edge = 500;      /* --match-max-positions-from-edge, KmerMatch.h:60 */
+	c->max_read_matches = 450;             /* --max-read-matches, MatcherInterface.h:77 */
+	c->include_mate = 1;                   /* --include-mate, MatcherInterface.h:71 */
+	c->seed = 0;
+	return KMR_OK;
+}
+/* KmerMatch's constructor and the contig side of _matchLocal (KmerMatch.h:100-107, :124-149) */
+int kmr_match_create(kmr_handle *h, const kmr_reads *contigs, const kmr_match_config *cfg, kmr_match **out) {
+	if (out) *out = nullptr;
+	if (!h || !contigs || !cfg || !out) return fail(h, KMR_ERR_INVALID_ARG, "kmr_match_create: NULL argument");
+	if (cfg->struct_size != sizeof(kmr_match_config)) return fail(h, KMR_ERR_INVALID_ARG, "kmr_match_config: struct_size " + std::to_string(cfg->struct_size) + " is not " + std::to_string(sizeof(kmr_match_config)));
+	if (!h->finalized) return fail(h, KMR_ERR_STATE, "kmr_match_create before kmr_finalize");
+	if (contigs->device != h->device) return fail(h, KMR_ERR_INVALID_ARG, "kmr_match_create: the contigs live on another device");
+	if (h->cfg.world_size > 1 || h->cfg.num_parts > 1 || h->cfg.kmer_subsample > 1)
+		return fail(h, KMR_ERR_UNSUPPORTED, "kmr_match_create: a handle with world_size > 1, num_parts > 1 or kmer_subsample > 1 holds a part of the spectrum only");
+	if (contigs->n > MATCH_MAX_CONTIGS) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_match_create: more than 2^24 contigs");
+	hipSetDevice(h->device);
+	auto m = make_result<kmr_match>(h);
+	m->h = h; m->cfg = *cfg;
+	const int rc = match_create_core(h, m.get(), contigs->bases.get<uint8_t>(), contigs->offsets.get<uint64_t>(), contigs->n); if (rc) return rc;
+	*out = m.release();
+	return KMR_OK;
+}
+int kmr_match_edge_info(const kmr_match *m, uint64_t *n_contigs, uint64_t *n_edge_kmers, uint64_t *n_distinct_keys, uint64_t *n_keys_in_spectrum) {
+	if (!m) return KMR_ERR_INVALID_ARG;
+	if (n_contigs) *n_contigs = m->n_contigs;
+	if (n_edge_kmers) *n_edge_kmers = m->n_edge_kmers;
+	if (n_distinct_keys) *n_distinct_keys = m->n_distinct_keys;
+	if (n_keys_in_spectrum) *n_keys_in_spectrum = m->n_keys_in_spectrum;
+	return KMR_OK;
+}
+/* the reads' side of _matchLocal's lookups (KmerMatch.h:151-161) and the mate of every hit (MatcherInterface.h:785-791) */
+int kmr_match_add_read_batch(kmr_match *m, const kmr_reads *reads, uint64_t first_global_read_idx, const kmr_pairs *pairs, const uint8_t *discarded) {
+	if (!m) return KMR_ERR_INVALID_ARG;
+	kmr_handle *h = m->h;
+	if (!reads) return fail(h, KMR_ERR_INVALID_ARG, "kmr_match_add_read_batch: NULL argument");
+	if (m->finished) return fail(h, KMR_ERR_STATE, "kmr_match_add_read_batch after kmr_match_finish");
+	if (reads->device != m->device || (pairs && pairs->device != m->device)) return fail(h, KMR_ERR_INVALID_ARG, "kmr_match_add_read_batch: the batch or its pairing lives on another device");
+	if (pairs && pairs->n != reads->n) return fail(h, KMR_ERR_INVALID_ARG, "kmr_match_add_read_batch: the pairing is of another number of reads");
+	if (first_global_read_idx > MATCH_READ_MASK || reads->n > MATCH_READ_MASK - first_global_read_idx) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_match_add_read_batch: a global read index of 2^40 or more");
+	if (reads->n == 0) return KMR_OK;
+	hipSetDevice(m->device);
+	kmr_match::Batch b;      /* kept only if the batch went through */
+	b.first = first_global_read_idx; b.n = reads->n;
+	if (discarded) {
+		HIPCHK(h, b.discarded.alloc(std::max<size_t>(reads->n, 256)));
+		HIPCHK(h, hipMemcpy(b.discarded.get(), discarded, reads->n, hipMemcpyHostToDevice));
+	}
+	const int rc = match_add_core(h, m, reads->bases.get<uint8_t>(), reads->quals.get<uint8_t>(), reads->offsets.get<uint64_t>(), reads->n, first_global_read_idx,
+	                              (pairs && m->cfg.include_mate) ? pairs->mate.get<int64_t>() : nullptr, b.discarded.get<uint8_t>());      /* (waits for the stream) */
+	if (rc) return rc;
+	m->batches.push_back(std::move(b));
+	return KMR_OK;
+}
+/* the end of _matchLocal (KmerMatch.h:163-171), exchangeGlobalReadIdxs' mates (MatcherInterface.h:772-792) and getLocalReads' sorted,
+ * undiscarded reads (:311-321) */
+int kmr_match_finish(kmr_match *m) {
+	if (!m) return KMR_ERR_INVALID_ARG;
+	kmr_handle *h = m->h;
+	if (m->finished) return fail(h, KMR_ERR_STATE, "kmr_match_finish twice");
+	hipSetDevice(m->device);
+	const uint64_t nc = m->n_contigs, nh = m->n_hits;
+	if (nh >= 0xffffffffull) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_match_finish: 2^32 - 1 hit records or more");
+	const dim3 block(256);
+	Scratch tmp(h);
+	uint64_t *offsets, *before, *after, *bound, *bound2;
+	HIPCHK(h, alloc_n(m->offsets, &offsets, nc + 1)); HIPCHK(h, alloc_n(m->size_before, &before, std::max<uint64_t>(nc, 1))); HIPCHK(h, alloc_n(m->size_after, &after, std::max<uint64_t>(nc, 1)));
+	HIPCHK(h, hipMemsetAsync(offsets, 0, 8 * (nc + 1), h->stream)); HIPCHK(h, hipMemsetAsync(before, 0, 8 * std::max<uint64_t>(nc, 1), h->stream)); HIPCHK(h, hipMemsetAsync(after, 0, 8 * std::max<uint64_t>(nc, 1), h->stream));
+	m->n_reads_total = 0; m->n_sampled = 0;
+	uint64_t n_out = 0;
+	if (nh && nc) {
+		/* 1: the records in (contig, read) order, made unique */
+		unsigned long long *k1, *ukey, *umate; uint32_t *p0, *p1, *flag; uint64_t *scan;
+		HIPCHK(h, tmp.take(&k1, nh)); HIPCHK(h, tmp.take(&ukey, nh)); HIPCHK(h, tmp.take(&umate, nh)); HIPCHK(h, tmp.take(&p0, nh)); HIPCHK(h, tmp.take(&p1, nh));
+		HIPCHK(h, tmp.take(&flag, 2 * nh)); HIPCHK(h, tmp.take(&scan, 2 * (nh + 1))); HIPCHK(h, tmp.take(&bound, nc + 1)); HIPCHK(h, tmp.take(&bound2, nc + 1));
+		int rc = sort_reserve(h, tmp, nh, "kmr_match_finish"); if (rc) return rc;
+		const dim3 hgrid(grid_for(nh)), cgrid(grid_for(nc + 1));
+		hipLaunchKernelGGL(match_iota_kernel, hgrid, block, 0, h->stream, p0, nh);
+		HIPCHK(h, hipGetLastError());
+		rc = sort_pairs(h, tmp, m->hit_key.get<unsigned long long>(), k1, p0, p1, nh, "kmr_match_finish"); if (rc) return rc;
+		hipLaunchKernelGGL(match_heads_kernel, hgrid, block, 0, h->stream, (const unsigned long long *)k1, nh, flag);
+		HIPCHK(h, hipGetLastError());
+		rc = exclusive_scan_queue(h, flag, nh, scan); if (rc) return rc;
+		hipLaunchKernelGGL(match_compact_kernel, hgrid, block, 0, h->stream, (const unsigned long long *)k1, (const uint32_t *)p1, m->hit_mate.get<unsigned long long>(), (const uint32_t *)flag,
+		                   (const uint64_t *)scan, nh, ukey, umate);
+		HIPCHK(h, hipGetLastError());
+		uint64_t nu = 0;
+		HIPCHK(h, hipMemcpyAsync(&nu, scan + nh, 8, hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, hipStreamSynchronize(h->stream));
+		/* 2: the sets' sizes, the sampling, the mates of the reads that stay */
+		const dim3 ugrid(grid_for(nu));
+		uint32_t *keep = flag, *cnt = flag + nh; uint64_t *kscan = scan, *escan = scan + (nh + 1);
+		hipLaunchKernelGGL(match_bounds_kernel, cgrid, block, 0, h->stream, (const unsigned long long *)ukey, nu, nc, bound);
+		hipLaunchKernelGGL(match_sample_kernel, ugrid, block, 0, h->stream, (const unsigned long long *)ukey, (const unsigned long long *)umate, nu, (const uint64_t *)bound, m->cfg.max_read_matches,
+		                   m->cfg.include_mate, m->cfg.seed, keep, cnt);
+		HIPCHK(h, hipGetLastError());
+		rc = exclusive_scan_queue(h, keep, nu, kscan); if (rc) return rc;
+		rc = exclusive_scan_queue(h, cnt, nu, escan); if (rc) return rc;
+		hipLaunchKernelGGL(match_sizes_kernel, cgrid, block, 0, h->stream, (const uint64_t *)bound, (const uint64_t *)kscan, nc, before, after);
+		HIPCHK(h, hipGetLastError());
+		uint64_t ne = 0;
+		HIPCHK(h, hipMemcpyAsync(&ne, escan + nu, 8, hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, hipStreamSynchronize(h->stream));
+		if (ne >= 0xffffffffull) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_match_finish: 2^32 - 1 reads and mates or more");
+		if (ne) {
+			unsigned long long *e0, *e1; uint32_t *q0, *q1, *fflag; uint64_t *fscan;
+			HIPCHK(h, tmp.take(&e0, ne)); HIPCHK(h, tmp.take(&e1, ne)); HIPCHK(h, tmp.take(&q0, ne)); HIPCHK(h, tmp.take(&q1, ne)); HIPCHK(h, tmp.take(&fflag, ne)); HIPCHK(h, tmp.take(&fscan, ne + 1));
+			const dim3 egrid(grid_for(ne));
+			hipLaunchKernelGGL(match_emit_kernel, ugrid, block, 0, h->stream, (const unsigned long long *)ukey, (const unsigned long long *)umate, nu, (const uint32_t *)cnt, (const uint64_t *)escan, e0);
+			hipLaunchKernelGGL(match_iota_kernel, egrid, block, 0, h->stream, q0, ne);
+			HIPCHK(h, hipGetLastError());
+			/* 3: sorted and made unique again, without the discarded reads */
+			rc = sort_reserve(h, tmp, ne, "kmr_match_finish"); if (rc) return rc;
+			rc = sort_pairs(h, tmp, e0, e1, q0, q1, ne, "kmr_match_finish"); if (rc) return rc;
+			const uint32_t nb = (uint32_t)m->batches.size();
+			std::vector<uint64_t> bf(nb), bn(nb); std::vector<const uint8_t *> bp(nb);
+			for (uint32_t i = 0; i < nb; i++) { bf[i] = m->batches[i].first; bn[i] = m->batches[i].n; bp[i] = m->batches[i].discarded.get<uint8_t>(); }
+			MatchBatches B; B.nb = nb;
+			const uint64_t *dbf, *dbn; const uint8_t *const *dbp;
+			rc = to_device(h, tmp, (const uint64_t *)bf.data(), (uint64_t)nb, &dbf); if (rc) return rc;
+			rc = to_device(h, tmp, (const uint64_t *)bn.data(), (uint64_t)nb, &dbn); if (rc) return rc;
+			rc = to_device(h, tmp, (const uint8_t *const *)bp.data(), (uint64_t)nb, &dbp); if (rc) return rc;
+			B.first = dbf; B.n = dbn; B.flags = dbp;
+			hipLaunchKernelGGL(match_final_kernel, egrid, block, 0, h->stream, (const unsigned long long *)e1, ne, B, fflag);
+			HIPCHK(h, hipGetLastError());
+			rc = exclusive_scan_queue(h, fflag, ne, fscan); if (rc) return rc;
+			HIPCHK(h, hipMemcpyAsync(&n_out, fscan + ne, 8, hipMemcpyDeviceToHost, h->stream));
+			HIPCHK(h, hipStreamSynchronize(h->stream));      /* (bf, bn, bp have been read) */
+			uint64_t *ids;
+			HIPCHK(h, alloc_n(m->read_ids, &ids, std::max<uint64_t>(n_out, 1)));
+			hipLaunchKernelGGL(match_bounds_kernel, cgrid, block, 0, h->stream, (const unsigned long long *)e1, ne, nc, bound2);
+			hipLaunchKernelGGL(match_output_kernel, egrid, block, 0, h->stream, (const unsigned long long *)e1, ne, (const uint32_t *)fflag, (const uint64_t *)fscan, ids);
+			hipLaunchKernelGGL(match_offsets_kernel, cgrid, block, 0, h->stream, (const uint64_t *)bound2, (const uint64_t *)fscan, nc, offsets);
+			HIPCHK(h, hipGetLastError());
+		}
+		/* the sets that were sampled: the sizes are small, the host counts them */
+		std::vector<uint64_t> hb(nc);
+		HIPCHK(h, hipMemcpyAsync(hb.data(), before, 8 * nc, hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, hipStreamSynchronize(h->stream));
+		const float maxHits = (float)(2.0 * (double)m->cfg.max_read_matches);
+		if (m->cfg.max_read_matches) for (uint64_t c = 0; c < nc; c++) if ((float)(long long)hb[c] > maxHits) m->n_sampled++;
+	}
+	if (!m->read_ids) { uint64_t *ids; HIPCHK(h, alloc_n(m->read_ids, &ids, (size_t)1)); }
+	HIPCHK(h, hipStreamSynchronize(h->stream));
+	tmp.done();
+	m->n_reads_total = n_out;
+	m->hit_key.reset(); m->hit_mate.reset(); m->batches.clear();      /* the stream is idle */
+	m->finished = true;
+	return KMR_OK;
+}
+int kmr_match_info(const kmr_match *m, uint64_t *n_contigs, uint64_t *n_reads_total, uint64_t *n_sampled_contigs) {
+	if (!m) return KMR_ERR_INVALID_ARG;
+	if (!m->finished) return fail(m->h, KMR_ERR_STATE, "kmr_match_info before kmr_match_finish");
+	if (n_contigs) *n_contigs = m->n_contigs;
+	if (n_reads_total) *n_reads_total = m->n_reads_total;
+	if (n_sampled_contigs) *n_sampled_contigs = m->n_sampled;
+	return KMR_OK;
+}
+int kmr_match_copy(const kmr_match *m, uint64_t *offsets, uint64_t *read_ids, uint64_t *size_before_sampling, uint64_t *size_after_sampling) {
+	if (!m) return KMR_ERR_INVALID_ARG;
+	if (!m->finished) return fail(m->h, KMR_ERR_STATE, "kmr_match_copy before kmr_match_finish");
+	hipSetDevice(m->device);
+	hipError_t e = hipSuccess;
+	copy_out(e, offsets, m->offsets, m->n_contigs + 1);
+	copy_out(e, read_ids, m->read_ids, m->n_reads_total);
+	copy_out(e, size_before_sampling, m->size_before, m->n_contigs);
+	copy_out(e, size_after_sampling, m->size_after, m->n_contigs);
+	HIPCHK(m->h, e);
+	return KMR_OK;
+}
+int kmr_match_device_ptrs(const kmr_match *m, void **dev_offsets, void **dev_read_ids, void **dev_size_before_sampling, void **dev_size_after_sampling) {
+	if (!m) return KMR_ERR_INVALID_ARG;
+	if (!m->finished) return fail(m->h, KMR_ERR_STATE, "kmr_match_device_ptrs before kmr_match_finish");
+	if (dev_offsets) *dev_offsets = m->offsets.get();
+	if (dev_read_ids) *dev_read_ids = m->read_ids.get();
+	if (dev_size_before_sampling) *dev_size_before_sampling = m->size_before.get();
+	if (dev_size_after_sampling) *dev_size_after_sampling = m->size_after.get();
+	return KMR_OK;
+}
+void kmr_match_free(kmr_match *m) { free_on_device(m); }
 
 }  // extern "C"
 

@@ -1058,6 +1058,73 @@ class ReadPairs(_DeviceObject):
         return a.value or 0, b.value or 0, c.value or 0
 
 
+class MatchResults:
+    """What KmerMatch.finish() answers: for contig i the ascending global read indices reads[offsets[i]:offsets[i + 1]] (= self[i]),
+    and per contig the size of its hit set before the sampling and after it (before the mates join)."""
+
+    def __init__(self, offsets, reads, size_before_sampling, size_after_sampling, n_sampled_contigs=0):
+        self.offsets, self.reads = offsets, reads
+        self.size_before_sampling, self.size_after_sampling, self.n_sampled_contigs = size_before_sampling, size_after_sampling, n_sampled_contigs
+
+    def __len__(self):
+        return len(self.offsets) - 1
+
+    def __getitem__(self, i):
+        if not -len(self) <= i < len(self):
+            raise IndexError(i)
+        i %= len(self)
+        return self.reads[int(self.offsets[i]):int(self.offsets[i + 1])]
+
+
+class KmerMatch(_DeviceObject):
+    """KmerMatch (src/KmerMatch.h:93-185, src/MatcherInterface.h): for every contig of the ReadSet `contigs` the reads that share a
+    k-mer with the first or last `match_max_positions_from_edge` bases of the contig (kmr_match_*).  `spectrum` is the finalized
+    spectrum of exactly the reads that are then streamed with addReads; sets of more than 2 * max_read_matches reads are sampled
+    (0 = never), the random numbers a function of (seed, global read index, contig) alone; with `include_mate` the mates of the reads
+    that stay join, where addReads is given the batch's ReadPairs."""
+    _HANDLE, _FREE = "_m", "kmr_match_free"
+
+    def __init__(self, spectrum, contigs, match_max_positions_from_edge=500, max_read_matches=450, include_mate=True, seed=0):
+        self.sp = spectrum
+        cfg = _lib.KmrMatchConfig()
+        _ok(spectrum.lib.kmr_match_config_init(C.byref(cfg)), "kmr_match_config_init")
+        cfg.max_positions_from_edge, cfg.max_read_matches, cfg.include_mate, cfg.seed = int(match_max_positions_from_edge), int(max_read_matches), 1 if include_mate else 0, int(seed)
+        m = C.c_void_p()
+        spectrum._call("match_create", spectrum.h, contigs._live(), C.byref(cfg), C.byref(m))
+        self._m = m
+        v = [C.c_uint64() for _ in range(4)]
+        _ok(spectrum.lib.kmr_match_edge_info(m, *[C.byref(x) for x in v]), "kmr_match_edge_info")
+        self.n_contigs, self.n_edge_kmers, self.n_distinct_keys, self.n_keys_in_spectrum = [x.value for x in v]
+
+    def addReads(self, read_set, first_global_read_idx=0, pairs=None, discarded=None):
+        """stream one batch of the target reads; `pairs`: the batch's ReadPairs (None: no mates), `discarded`: one flag per read"""
+        d = None if discarded is None else _u8(discarded)
+        if d is not None and d.size != read_set.n:
+            raise KmerSpectrumError("KmerMatch.addReads: one discard flag per read")
+        self.sp._call("match_add_read_batch", self._live(), read_set._live(), int(first_global_read_idx), None if pairs is None else pairs._live(),
+                      None if d is None or not d.size else d.ctypes.data_as(C.POINTER(C.c_uint8)))
+        return self
+
+    def finish(self):
+        """sample, add the mates, sort, drop the discarded reads: a MatchResults"""
+        m = self._live()
+        self.sp._call("match_finish", m)
+        v = [C.c_uint64() for _ in range(3)]
+        self.sp._call("match_info", m, *[C.byref(x) for x in v])
+        nc, nr, ns = [x.value for x in v]
+        off, ids = np.zeros(nc + 1, dtype=np.uint64), np.zeros(nr, dtype=np.uint64)
+        before, after = np.zeros(nc, dtype=np.uint64), np.zeros(nc, dtype=np.uint64)
+        u64 = C.POINTER(C.c_uint64)
+        self.sp._call("match_copy", m, off.ctypes.data_as(u64), ids.ctypes.data_as(u64) if nr else None, before.ctypes.data_as(u64) if nc else None, after.ctypes.data_as(u64) if nc else None)
+        return MatchResults(off, ids, before, after, ns)
+
+    def device_ptrs(self):
+        """device pointers of (offsets, reads, size_before_sampling, size_after_sampling), uint64 each; after finish(), valid until close()"""
+        p = [C.c_void_p() for _ in range(4)]
+        self.sp._call("match_device_ptrs", self._live(), *[C.byref(x) for x in p])
+        return tuple(x.value or 0 for x in p)
+
+
 
 class FilterKnownOddities(_DeviceObject):
     """The artifact filter FilterReads runs before the spectrum build (src/FilterKnownOddities.h, apps/FilterReads.cpp:107-118):
