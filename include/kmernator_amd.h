@@ -1317,6 +1317,79 @@ int kmr_match_copy(const kmr_match *m, uint64_t *offsets, uint64_t *read_ids, ui
 int kmr_match_device_ptrs(const kmr_match *m, void **dev_offsets, void **dev_read_ids, void **dev_size_before_sampling, void **dev_size_after_sampling);
 void kmr_match_free(kmr_match *m);
 
+/* ---- ContigExtender (src/ContigExtender.h:157-247, src/KmerSpectrum.h:2311-2373): the other half of a round of
+ * DistributedNucleatingAssembler (apps/DistributedNucleatingAssembler.cpp:230-275) -- every contig walks outwards base by base while the
+ * k-mer spectrum of its own pool of reads agrees.  All (contig, pool) pairs of a call are worked on at once (kmr_extend.hpp).
+ *
+ * Pool spectrum: buildKmerSpectrum(pool, false) under h's config -- min_weight, the quality settings, separate_singletons; h supplies k
+ * and that config only and need not have been fed.  world_size, num_parts and kmer_subsample are not applied.  A key's value is
+ * getWeightedCount() (use_weights) or getCount(); the weighted count is an f32 that takes one f32 addition per sighting in the serial
+ * order (pool order, then position), the first sighting quantised through the singleton map's byte where that map is on; with it on a
+ * key seen once is invisible, since extendContig reads the weak map only.  No purgeMinDepth.
+ * One step (extendContig): the contig must be longer than k; the edge k-mer is the first or last k bases as compressSequence packs
+ * them (a non-ACGT base is the code 0, 'A'; lower case is upper case); its canonical key's value, as a double, must not be 0.0; the
+ * four one-base extensions in the order A, C, G, T, canonical, are summed in that order into total; the step goes on if
+ * total >= minimum_coverage && total / edge > maximum_delta_ratio; the first i with value[i] / total >= minimum_consensus / 100 is
+ * taken, and the step ends without a base if that candidate key is in the contig's solid spectrum: the contig's own k-mers that pass
+ * the weight test at quality Read::REF_QUAL, plus the new edge k-mer of every step of this call on either side (recordKmer).
+ * One contig (extendContigs with minKmerSize == maxKmerSize == k): while (iteration++ < max_extend && (left | right)), left before
+ * right, a side that failed is not tried again, a contig shorter than k ends the loop.  The multi-k form of extendContigs (spectra
+ * built with kmerStep but walked with += 2, freed by a shifted index) is not built: the assembler never takes it.
+ * Stop records: per contig and side why the side stopped and the f64 values of the last step it tried (zero where the step did not
+ * get that far) -- the reference's debug lines.
+ * Result: the sequences as Read::getFasta gives them (ACGT in upper case, '.' as 'N', other markups as they are) with the new bases,
+ * all of quality Read::REF_QUAL, as a read batch without names that kmr_match_create and a further kmr_extend_contigs take.
+ * Bounds: k <= 128 as everywhere; max_extend <= KMR_EXTEND_MAX_EXTEND, fewer than 2^31 contigs, fewer than 2^32 - 1 pooled reads and
+ * contigs, sequences shorter than 2^31 - 1 bases: KMR_ERR_UNSUPPORTED beyond. */
+#define KMR_EXTEND_MAX_EXTEND 65536u
+enum kmr_extend_stop_reason {
+	KMR_EXTEND_STOP_LIMIT = 0,        /* the iteration limit: the side was still growing */
+	KMR_EXTEND_STOP_SHORT = 1,        /* the contig is not longer than k */
+	KMR_EXTEND_STOP_NO_EDGE = 2,      /* the edge k-mer has no value in the pool's weak map */
+	KMR_EXTEND_STOP_COVERAGE = 3,     /* total < minimum_coverage or total / edge <= maximum_delta_ratio */
+	KMR_EXTEND_STOP_AMBIGUOUS = 4,    /* no extension reaches minimum_consensus */
+	KMR_EXTEND_STOP_REPEAT = 5,       /* the chosen k-mer is in the contig's solid spectrum */
+	KMR_EXTEND_STOP_INACTIVE = 6      /* the contig's `active` flag is 0: it was not looked at */
+};
+typedef struct kmr_extend_config {
+	uint32_t struct_size;
+	uint32_t max_extend;              /* maxExtend, 50 */
+	double minimum_consensus;         /* --minimum-consensus in percent, 85 */
+	double minimum_coverage;          /* --minimum-coverage, 4.8 */
+	double maximum_delta_ratio;       /* --maximum-delta-ratio, 0.33 */
+	uint32_t use_weights;             /* TrackingData::useWeighted(), 1 */
+	uint32_t reserved;
+} kmr_extend_config;
+typedef struct kmr_extend_stop {
+	uint32_t reason, reserved;        /* kmr_extend_stop_reason */
+	double edge, ext[4], total;       /* of the last step the side tried */
+} kmr_extend_stop;
+typedef struct kmr_extend kmr_extend;
+int kmr_extend_config_init(kmr_extend_config *cfg);
+/* contigs and reads: batches of h's device (KMR_ERR_INVALID_ARG otherwise).  Contig i's pool: reads pool_reads[pool_offsets[i] ..
+ * pool_offsets[i + 1]) of `reads`, in that order; a read may sit in many pools.  pool_offsets must start at 0 and ascend, every pool
+ * index must lie in the batch (KMR_ERR_INVALID_ARG).  active: one byte per contig, 0 = leave the contig as it is; NULL = all.  The
+ * three arrays are host memory here and device memory in the _dev form (e.g. kmr_match_device_ptrs' offsets, and its read ids once
+ * the caller has made them local to `reads`).  Free the result with kmr_extend_free. */
+int kmr_extend_contigs(kmr_handle *h, const kmr_reads *contigs, const kmr_reads *reads, const uint64_t *pool_offsets, const uint64_t *pool_reads, const uint8_t *active,
+                       const kmr_extend_config *cfg, kmr_extend **out);
+int kmr_extend_contigs_dev(kmr_handle *h, const kmr_reads *contigs, const kmr_reads *reads, const void *dev_pool_offsets, const void *dev_pool_reads, const void *dev_active,
+                           const kmr_extend_config *cfg, kmr_extend **out);
+/* contigs, contigs that grew, bases added in all; any may be NULL */
+int kmr_extend_info(const kmr_extend *e, uint64_t *n_contigs, uint64_t *n_extended, uint64_t *bases_added);
+/* per contig the new length and the bases added on the left and on the right; stops: two records per contig, left then right; any may
+ * be NULL.  All arrays are host memory */
+int kmr_extend_copy(const kmr_extend *e, uint32_t *new_len, uint32_t *left, uint32_t *right, kmr_extend_stop *stops);
+/* the new sequences (owned by e: do not kmr_reads_free them) */
+int kmr_extend_reads(const kmr_extend *e, const kmr_reads **reads);
+void kmr_extend_free(kmr_extend *e);
+/* ContigExtender::getNewName (src/ContigExtender.h:249-268), byte for byte: find_last_of("-l") finds the last '-' OR 'l'; host work, no
+ * device.  Writes the NUL-terminated name to buf; KMR_ERR_CAPACITY if it does not fit cap bytes */
+int kmr_extend_new_name(const char *old_name, uint64_t left, uint64_t right, char *buf, uint64_t cap);
+/* ContigExtender::getMinMaxKmerSize (:269-279) from the option's k-mer size, the longest read, the bases and the number of reads */
+int kmr_extend_min_max_kmer_size(uint32_t kmer_size, uint32_t max_sequence_length, uint64_t base_count, uint64_t n_reads, uint32_t max_steps,
+                                 uint32_t *min_kmer_size, uint32_t *max_kmer_size, uint32_t *kmer_step);
+
 /* Raw HIP stream of the handle (hipStream_t) so callers can order their own
  * work (torch.cuda.ExternalStream) against it. */
 void *kmr_stream(kmr_handle *h);
@@ -1361,6 +1434,9 @@ void *kmr_stream(kmr_handle *h);
  *   out, 0 = 4096; tests set 64 or 65 so that a short input crosses piece edges; may be set at any time).
  *   "match_hit_capacity" (hit records the buffers of a kmr_match hold before they first grow, 0 = 2^20; tests set a few so that a handful
  *   of reads overflows them and the batch is streamed again; read by kmr_match_add_read_batch; may be set at any time).
+ *   "extend_stage_kmers" (k-mers of one run of whole contigs with their pools of kmr_extend_contigs*, 0 = 2^24; a contig whose pool alone
+ *   exceeds it is a run of its own; tests set a few hundred so that a call takes several runs), "extend_timing" (1: kmr_extend_contigs*
+ *   times its phases with HIP events and waits after every run, see kmr_build_info; default 0); both may be set at any time.
  * Call before the first kmr_add_reads* of a build.  KMR_ERR_INVALID_ARG for an unknown knob. */
 int kmr_tune(kmr_handle *h, const char *knob, double value);
 /* What the current build decided, for tests and measurement tools (the reference logs such figures, LOG_VERBOSE): "lists" = super-k-mer
@@ -1389,7 +1465,10 @@ int kmr_tune(kmr_handle *h, const char *knob, double value);
  * "csr_path" / "csr_chunks" = how the last chunk index of this handle was made (1: radix partition, 0: an atomic per chunk, -1: none yet) and
  * how many chunks of the pool it looked at, "unit_batches" = batches fed to this handle so far that held a read longer than an extraction
  * tile and were cut into work units, "match_add_attempts" = how often the last kmr_match_add_read_batch on this handle streamed its
- * batch before the hit records fit their buffers (1 unless they had to grow).
+ * batch before the hit records fit their buffers (1 unless they had to grow), "extend_runs" = the runs of whole contigs the last
+ * kmr_extend_contigs* on this handle took, "extend_gather_ms" / "extend_extract_ms" / "extend_sort_ms" / "extend_reduce_ms" /
+ * "extend_walk_ms" = HIP-event times of that call: the gathered batch with its slot scan, the extraction into the staging array, the
+ * radix sort passes, the reduce with its scans and tables, extend_contigs_kernel (0 unless kmr_tune "extend_timing" is set).
  * KMR_ERR_INVALID_ARG for an unknown name. */
 int kmr_build_info(kmr_handle *h, const char *what, double *value);
 

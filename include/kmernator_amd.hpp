@@ -29,6 +29,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <fstream>
 #include <sstream>
 #include <stdexcept>
@@ -97,6 +98,7 @@ public:
 private:
 	friend class FilterKnownOddities;
 	friend class ReadSelector;
+	friend class ContigExtender;
 	ReadSet(const std::string &text, kmr_reads *r) : _text(text), _r(r) { load(); }      /* a batch the library derived from another one */
 	void load();
 	std::string _text; kmr_reads *_r = nullptr; uint64_t _n = 0, _bases = 0, _filtered = 0; uint32_t _qbase = 0;
@@ -358,6 +360,68 @@ public:
 	const kmr_match *raw() const { return _m; }
 private:
 	KmerSpectrum &_sp; kmr_match *_m = nullptr;
+};
+
+/* ContigExtender (src/ContigExtender.h:157-247 at one k-mer size, over KmerSpectrum::extendContig, src/KmerSpectrum.h:2311-2373): every
+ * contig walks outwards while the spectrum of its own pool of reads agrees (kmr_extend_*).  `sp` supplies k and the build's config
+ * and need not have been fed.  getNewName / getMinMaxKmerSize need no device. */
+struct ExtendResults {
+	std::vector<std::string> sequences, names;             /* the new sequences; getNewName of the names handed in (empty without names) */
+	std::vector<uint32_t> left, right, newLength;          /* bases added per contig */
+	std::vector<kmr_extend_stop> stops;                    /* two per contig: left, right */
+	uint64_t extended = 0, basesAdded = 0;
+	std::unique_ptr<ReadSet> readSet;                      /* the sequences as a batch of quality Read::REF_QUAL, for the next round's KmerMatch */
+};
+class ContigExtender {
+public:
+	static kmr_extend_config defaults() { kmr_extend_config c; kmr_extend_config_init(&c); return c; }
+	explicit ContigExtender(KmerSpectrum &sp, const kmr_extend_config &cfg = defaults()) : _sp(sp), _cfg(cfg) {}
+	/* contig i's pool: reads poolReads[poolOffsets[i] .. poolOffsets[i + 1]) of `reads`; active: one flag per contig or empty */
+	ExtendResults extendContigs(const ReadSet &contigs, const ReadSet &reads, const std::vector<uint64_t> &poolOffsets, const std::vector<uint64_t> &poolReads,
+	                            const std::vector<std::string> &names = std::vector<std::string>(), const std::vector<uint8_t> &active = std::vector<uint8_t>()) {
+		if (poolOffsets.size() != contigs.getSize() + 1 || (!active.empty() && active.size() != contigs.getSize()) || (!names.empty() && names.size() != contigs.getSize()))
+			throw KmerSpectrumError(KMR_ERR_INVALID_ARG, "ContigExtender::extendContigs: one pool, name and flag per contig");
+		kmr_extend *e = nullptr;
+		_sp.check(kmr_extend_contigs(_sp.raw(), contigs.raw(), reads.raw(), poolOffsets.data(), poolReads.empty() ? nullptr : poolReads.data(), active.empty() ? nullptr : active.data(), &_cfg, &e),
+		          "kmr_extend_contigs");
+		std::unique_ptr<kmr_extend, void (*)(kmr_extend *)> hold(e, kmr_extend_free);
+		ExtendResults r;
+		uint64_t n = 0;
+		kmr_extend_info(e, &n, &r.extended, &r.basesAdded);
+		const uint64_t m = n ? n : 1;
+		r.left.assign(m, 0); r.right.assign(m, 0); r.newLength.assign(m, 0); r.stops.resize(2 * m);
+		_sp.check(kmr_extend_copy(e, r.newLength.data(), r.left.data(), r.right.data(), r.stops.data()), "kmr_extend_copy");
+		r.left.resize(n); r.right.resize(n); r.newLength.resize(n); r.stops.resize(2 * n);
+		const kmr_reads *batch = nullptr;
+		_sp.check(kmr_extend_reads(e, &batch), "kmr_extend_reads");
+		uint64_t total = 0;
+		kmr_reads_info(batch, nullptr, &total, nullptr, nullptr);
+		std::string bases(total, '\0'), quals(total, '\0');
+		std::vector<uint64_t> off(n + 1);
+		if (kmr_reads_copy(batch, &bases[0], &quals[0], off.data(), nullptr, nullptr) != KMR_OK) throw KmerSpectrumError(KMR_ERR_HIP, "kmr_reads_copy");
+		for (uint64_t i = 0; i < n; i++) {
+			r.sequences.push_back(bases.substr(off[i], off[i + 1] - off[i]));
+			if (!names.empty()) r.names.push_back(getNewName(names[i], r.left[i], r.right[i]));
+		}
+		kmr_reads *own = nullptr;      /* a batch of its own: the result object goes with this call */
+		_sp.check(kmr_reads_from_host(_sp.raw(), bases.data(), quals.data(), off.data(), n, &own), "kmr_reads_from_host");
+		r.readSet.reset(new ReadSet(std::string(), own));
+		return r;
+	}
+	/* ContigExtender::getNewName (:249-268) */
+	static std::string getNewName(const std::string &oldName, uint64_t leftTotal, uint64_t rightTotal) {
+		std::string buf(oldName.size() + 48, '\0');
+		const int rc = kmr_extend_new_name(oldName.c_str(), leftTotal, rightTotal, &buf[0], buf.size()); if (rc != KMR_OK) throw KmerSpectrumError(rc, "kmr_extend_new_name");
+		buf.resize(std::strlen(buf.c_str()));
+		return buf;
+	}
+	/* ContigExtender::getMinMaxKmerSize (:269-279) */
+	static void getMinMaxKmerSize(uint32_t kmerSize, const ReadSet &reads, uint32_t maxSequenceLength, uint32_t &minKmerSize, uint32_t &maxKmerSize, uint32_t &kmerStep, uint32_t maxSteps = 6) {
+		const int rc = kmr_extend_min_max_kmer_size(kmerSize, maxSequenceLength, reads.getBaseCount(), reads.getSize(), maxSteps, &minKmerSize, &maxKmerSize, &kmerStep);
+		if (rc != KMR_OK) throw KmerSpectrumError(rc, "kmr_extend_min_max_kmer_size");
+	}
+private:
+	KmerSpectrum &_sp; kmr_extend_config _cfg;
 };
 
 /* FilterKnownOddities (src/FilterKnownOddities.h): the artifact screen FilterReads runs before the spectrum build */

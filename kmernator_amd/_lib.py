@@ -83,6 +83,21 @@ class KmrMatchConfig(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("max_positions_from_edge", C.c_int32), ("max_read_matches", C.c_uint32), ("include_mate", C.c_uint32), ("seed", C.c_uint64)]
 
 
+class KmrExtendConfig(C.Structure):
+    """kmr_extend_config"""
+    _fields_ = [("struct_size", C.c_uint32), ("max_extend", C.c_uint32), ("minimum_consensus", C.c_double), ("minimum_coverage", C.c_double),
+                ("maximum_delta_ratio", C.c_double), ("use_weights", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class KmrExtendStop(C.Structure):
+    """kmr_extend_stop"""
+    _fields_ = [("reason", C.c_uint32), ("reserved", C.c_uint32), ("edge", C.c_double), ("ext", C.c_double * 4), ("total", C.c_double)]
+
+
+# kmr_extend_stop_reason
+KMR_EXTEND_STOP_LIMIT, KMR_EXTEND_STOP_SHORT, KMR_EXTEND_STOP_NO_EDGE, KMR_EXTEND_STOP_COVERAGE, KMR_EXTEND_STOP_AMBIGUOUS, KMR_EXTEND_STOP_REPEAT, KMR_EXTEND_STOP_INACTIVE = range(7)
+KMR_EXTEND_MAX_EXTEND = 65536
+
 KMR_TNF_EUCLIDEAN, KMR_TNF_SPEARMAN = 0, 1
 
 
@@ -140,6 +155,8 @@ EXPORTS = [
     "kmr_tnf_distances", "kmr_tnf_distances_dev", "kmr_tnf_likelihood_config_init", "kmr_tnf_likelihoods",
     "kmr_match_config_init", "kmr_match_create", "kmr_match_edge_info", "kmr_match_add_read_batch", "kmr_match_finish", "kmr_match_info", "kmr_match_copy",
     "kmr_match_device_ptrs", "kmr_match_free",
+    "kmr_extend_config_init", "kmr_extend_contigs", "kmr_extend_contigs_dev", "kmr_extend_info", "kmr_extend_copy", "kmr_extend_reads", "kmr_extend_free",
+    "kmr_extend_new_name", "kmr_extend_min_max_kmer_size",
     "kmr_map_digest", "kmr_synth_reads_dev", "kmr_build_info", "kmr_sk_exchange_uniform", "kmr_sk_exchange_peer_uniform", "kmr_sk_exchange_range", "kmr_count_lists_prefix",
 ]
 
@@ -355,6 +372,17 @@ def load():
     lib.kmr_match_device_ptrs.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     lib.kmr_match_free.argtypes = [vp]
     lib.kmr_match_free.restype = None
+    ecp = C.POINTER(KmrExtendConfig)
+    lib.kmr_extend_config_init.argtypes = [ecp]
+    lib.kmr_extend_contigs.argtypes = [vp, vp, vp, u64p, u64p, u8p, ecp, C.POINTER(vp)]
+    lib.kmr_extend_contigs_dev.argtypes = [vp, vp, vp, vp, vp, vp, ecp, C.POINTER(vp)]
+    lib.kmr_extend_info.argtypes = [vp, u64p, u64p, u64p]
+    lib.kmr_extend_copy.argtypes = [vp, u32p, u32p, u32p, C.POINTER(KmrExtendStop)]
+    lib.kmr_extend_reads.argtypes = [vp, C.POINTER(vp)]
+    lib.kmr_extend_free.argtypes = [vp]
+    lib.kmr_extend_free.restype = None
+    lib.kmr_extend_new_name.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64, C.c_char_p, C.c_uint64]
+    lib.kmr_extend_min_max_kmer_size.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, u32p, u32p, u32p]
     _lib = lib
     return lib
 

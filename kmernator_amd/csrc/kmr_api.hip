@@ -2303,6 +2303,8 @@ int kmr_tune(kmr_handle *h, const char *knob, double value) {
 	else if (k == "compare_stage_kmers") h->tune.compare_stage_kmers = value >= 1 ? std::min<uint64_t>((uint64_t)value, 1ull << 31) : 0;
 	else if (k == "tnf_piece_bases") h->tune.tnf_piece_bases = value >= 1 ? (uint32_t)std::min<double>(value, 1u << 30) : 0;
 	else if (k == "match_hit_capacity") h->tune.match_hit_capacity = value >= 1 ? (uint64_t)std::min<double>(value, 4294967294.0) : 0;
+	else if (k == "extend_stage_kmers") h->tune.extend_stage_kmers = value >= 1 ? std::min<uint64_t>((uint64_t)value, 1ull << 31) : 0;
+	else if (k == "extend_timing") h->tune.extend_timing = value != 0;
 	else if (k == "superkmer_window") {      /* largest minimizer window the geometry may take (32 / 16 / 8 / 4): A/B runs, tests of the narrower windows at large k */
 		if (h->superkmer_mode && !h->sk_state) { uint32_t w, m, o; if (!sk_geometry(h->k, 0, w, m, o, (uint32_t)value)) return fail(h, KMR_ERR_INVALID_ARG, "no minimizer geometry under that window"); h->sk_win = w; h->sk_m = m; h->sk_off = o; }
 	}
@@ -2333,6 +2335,12 @@ int kmr_build_info(kmr_handle *h, const char *what, double *value) {
 	else if (k == "csr_chunks") *value = (double)h->last_csr_chunks;
 	else if (k == "unit_batches") *value = (double)h->unit_batches;
 	else if (k == "match_add_attempts") *value = (double)h->last_match_attempts;
+	else if (k == "extend_runs") *value = (double)h->last_extend_runs;
+	else if (k == "extend_gather_ms") *value = h->last_extend_ms[0];
+	else if (k == "extend_extract_ms") *value = h->last_extend_ms[1];
+	else if (k == "extend_sort_ms") *value = h->last_extend_ms[2];
+	else if (k == "extend_reduce_ms") *value = h->last_extend_ms[3];
+	else if (k == "extend_walk_ms") *value = h->last_extend_ms[4];
 	else if (k == "device_blocks_live") *value = (double)g_blocks_live.load();
 	else if (k == "filter_score_ms") *value = h->last_score_ms;
 	else if (k == "select_ms") *value = h->last_select_ms;
@@ -3698,9 +3706,215 @@ template <int W> int match_add_t(kmr_handle *h, kmr_match *m, const ReadsView &a
 	}
 }
 
+/* ---- ContigExtender (kmr_extend.hpp): everything of kmr_extend_contigs* behind the argument checks (kmr_stages.hip) ---- */
+template <int W> int extend_t(kmr_handle *h, const kmr_reads *contigs, const kmr_reads *reads, const uint64_t *po, const uint64_t *pr, const uint8_t *active,
+                              const kmr_extend_config *cfg, kmr_extend *out) {
+	const dim3 block(256);
+	const uint64_t nc = contigs->n;
+	const uint32_t maxx = cfg->max_extend;
+	const uint8_t *cbases = contigs->bases.get<uint8_t>(); const uint64_t *coff = contigs->offsets.get<uint64_t>();
+	out->n = nc; out->n_extended = out->bases_added = 0;
+	h->last_extend_runs = 0;
+	for (double &t : h->last_extend_ms) t = 0;
+	auto result = std::unique_ptr<kmr_reads>(new kmr_reads);
+	result->device = h->device; result->n = nc; result->input_base = h->cfg.fastq_start_char;
+	uint64_t *noff;
+	HIPCHK(h, alloc_n(result->offsets, &noff, nc + 1));
+	HIPCHK(h, hipMemsetAsync(noff, 0, 8 * (nc + 1), h->stream));
+	HIPCHK(h, result->name_off.alloc(8 * std::max<uint64_t>(nc, 1))); HIPCHK(h, result->name_len.alloc(4 * std::max<uint64_t>(nc, 1)));
+	HIPCHK(h, hipMemsetAsync(result->name_off.get(), 0, 8 * std::max<uint64_t>(nc, 1), h->stream)); HIPCHK(h, hipMemsetAsync(result->name_len.get(), 0, 4 * std::max<uint64_t>(nc, 1), h->stream));
+	uint32_t *newlen, *left, *right, *reason; double *vals;
+	HIPCHK(h, alloc_n(out->newlen, &newlen, nc)); HIPCHK(h, alloc_n(out->left, &left, nc)); HIPCHK(h, alloc_n(out->right, &right, nc));
+	HIPCHK(h, alloc_n(out->reason, &reason, 2 * nc)); HIPCHK(h, alloc_n(out->vals, &vals, 2 * nc * EXT_VALS));
+	if (nc == 0) {
+		HIPCHK(h, result->bases.alloc(64)); HIPCHK(h, result->quals.alloc(64));
+		HIPCHK(h, hipStreamSynchronize(h->stream));
+		out->result = result.release();
+		return KMR_OK;
+	}
+	/* 1: the offsets, then the items */
+	DevBuf b_small, b_len, b_grp, b_goff, b_nk, b_koff;
+	uint32_t *err; HIPCHK(h, alloc_n(b_small, &err, (size_t)64));
+	unsigned int *most = err + 2; unsigned long long *info = (unsigned long long *)(err + 8);
+	HIPCHK(h, hipMemsetAsync(err, 0, 256, h->stream));
+	hipLaunchKernelGGL(extend_check_offsets_kernel, dim3(grid_for(nc + 1)), block, 0, h->stream, po, nc, err);
+	HIPCHK(h, hipGetLastError());
+	std::vector<uint64_t> hpo(nc + 1);
+	uint32_t herr = 0;
+	HIPCHK(h, hipMemcpyAsync(hpo.data(), po, 8 * (nc + 1), hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipStreamSynchronize(h->stream));
+	if (herr) return fail(h, KMR_ERR_INVALID_ARG, "kmr_extend_contigs: pool_offsets does not start at 0 or does not ascend");
+	const uint64_t P = hpo[nc], n_items = P + nc;
+	if (n_items >= 0xffffffffull) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_extend_contigs: 2^32 - 1 pooled reads and contigs or more");
+	EventTimer<2> tg(h->tune.extend_timing);
+	tg.mark(0, h->stream);
+	uint32_t *len, *grp, *nk; uint64_t *goff, *koff;
+	HIPCHK(h, alloc_n(b_len, &len, n_items)); HIPCHK(h, alloc_n(b_grp, &grp, n_items)); HIPCHK(h, alloc_n(b_goff, &goff, n_items + 1));
+	HIPCHK(h, alloc_n(b_nk, &nk, n_items)); HIPCHK(h, alloc_n(b_koff, &koff, n_items + 1));
+	hipLaunchKernelGGL(extend_item_kernel, dim3(grid_for(n_items)), block, 0, h->stream, po, pr, active, reads->offsets.get<uint64_t>(), reads->n, coff, nc, n_items, len, grp, err);
+	HIPCHK(h, hipGetLastError());
+	int rc = exclusive_scan_queue(h, len, n_items, goff); if (rc) return rc;
+	uint64_t G = 0;
+	HIPCHK(h, hipMemcpyAsync(&G, goff + n_items, 8, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipStreamSynchronize(h->stream));
+	if (herr & 2u) return fail(h, KMR_ERR_INVALID_ARG, "kmr_extend_contigs: a pool index lies outside the read batch");
+	if (herr & 4u) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_extend_contigs: a sequence of 2^31 - 1 bases or more");
+	/* 2: the gathered batch and its k-mer slots */
+	DevBuf b_gb, b_gq;
+	HIPCHK(h, b_gb.alloc(G + 64)); HIPCHK(h, b_gq.alloc(G + 64));
+	uint8_t *gb = b_gb.get<uint8_t>(), *gq = b_gq.get<uint8_t>();
+	HIPCHK(h, hipMemsetAsync(gb + G, 0, 64, h->stream)); HIPCHK(h, hipMemsetAsync(gq + G, 0, 64, h->stream));
+	if (G) {
+		hipLaunchKernelGGL(extend_gather_kernel, dim3(grid_for((G + 63) / 64)), block, 0, h->stream, (const uint64_t *)goff, n_items, G, po, pr, (const uint32_t *)grp, reads->bases.get<uint8_t>(),
+		                   reads->quals.get<uint8_t>(), reads->offsets.get<uint64_t>(), cbases, coff, gb, gq);
+		HIPCHK(h, hipGetLastError());
+	}
+	hipLaunchKernelGGL(compare_nk_kernel, dim3(grid_for(n_items)), block, 0, h->stream, (const uint64_t *)goff, n_items, h->k, nk, most, err + 3);
+	HIPCHK(h, hipGetLastError());
+	rc = exclusive_scan_queue(h, nk, n_items, koff); if (rc) return rc;
+	tg.mark(1, h->stream);
+	std::vector<uint64_t> hk(n_items + 1);
+	HIPCHK(h, hipMemcpyAsync(hk.data(), koff, 8 * (n_items + 1), hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipStreamSynchronize(h->stream));
+	h->last_extend_ms[0] = tg.ms(0, 1);
+	/* 3: runs of whole contigs whose slots fit the budget; a contig that alone exceeds it is a run of its own */
+	const uint64_t budget = h->tune.extend_stage_kmers ? h->tune.extend_stage_kmers : EXT_STAGE_SLOTS;
+	std::vector<uint64_t> cut;
+	cut.push_back(0);
+	{
+		uint64_t c0 = 0;
+		for (uint64_t c = 0; c < nc; c++) if (hk[hpo[c + 1] + c + 1] - hk[hpo[c0] + c0] > budget && c > c0) { cut.push_back(c); c0 = c; }
+	}
+	cut.push_back(nc);
+	/* the sequences with max_extend free bases on either side, the recorded keys */
+	DevBuf b_seq, b_rec;
+	HIPCHK(h, b_seq.alloc(std::max<uint64_t>(contigs->total + 2ull * maxx * nc, 256)));
+	const size_t rec_wave = (size_t)2 * maxx * W * 8;
+	const bool rec_lds = rec_wave <= EXT_LDS_WAVE_BYTES;
+	DevParams dp = dev_params(h);
+	dp.sub_wstart = dp.sub_wkeys = dp.sub_sstart = dp.sub_skeys = nullptr; dp.sub_wvals = nullptr; dp.sub_sweight = nullptr; dp.sub_wnb = dp.sub_snb = 0;
+	dp.subsample = 1; dp.world = 1; dp.rank = 0; dp.num_parts = 1; dp.part_idx = 0;      /* a pool's spectrum is whole */
+	const ReadsView all = reads_view(gb, gq, goff, n_items);
+	DevBuf b_stage, b_sgrp, b_perm, b_perm2, b_kin, b_kout, b_sort, b_flags, b_scans, b_cnt, b_val, b_wkeys, b_wcnt, b_wval, b_skeys, b_bounds;
+	for (size_t ri = 0; ri + 1 < cut.size(); ri++) {
+		const uint64_t c0 = cut[ri], m = cut[ri + 1] - c0;
+		const uint64_t i0 = hpo[c0] + c0, i1 = hpo[c0 + m] + c0 + m, S = hk[i1] - hk[i0];
+		if (S >= 0xffffffffull) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_extend_contigs: a run of 2^32 - 1 k-mers or more (lower kmr_tune \"extend_stage_kmers\")");
+		EventTimer<5> tr(h->tune.extend_timing);
+		tr.mark(0, h->stream);
+		uint64_t *bounds;
+		HIPCHK(h, alloc_n(b_bounds, &bounds, 4 * m));
+		HIPCHK(h, hipMemsetAsync(bounds, 0, 32 * m, h->stream));
+		uint64_t *wkeys = nullptr, *skeys = nullptr; uint32_t *wcnt = nullptr; float *wval = nullptr;
+		if (S) {
+			rc = b_stage.reserve(h, "extend staging", 8ull * (W + 1) * S); if (rc) return rc;
+			uint64_t *stage = b_stage.get<uint64_t>();
+			HIPCHK(h, hipMemsetAsync(stage, 0xff, 8ull * (W + 1) * S, h->stream));
+			ReadsView rv = reads_slice(all, i0, i1 - i0);
+			rc = prepare_units(h, rv); if (rc) return rc;
+			ExtendOp<W> op; op.stage = stage; op.koff = koff; op.slot_base = hk[i0];
+			rc = launch_extract<W, false>(h, rv, dp, op); if (rc) return rc;
+			tr.mark(1, h->stream);
+			rc = b_sgrp.reserve(h, "extend groups", 4 * S); if (rc) return rc;
+			rc = b_perm.reserve(h, "extend sort order", 4 * S); if (rc) return rc;
+			rc = b_perm2.reserve(h, "extend sort order", 4 * S); if (rc) return rc;
+			rc = b_kin.reserve(h, "extend sort keys", 8 * S); if (rc) return rc;
+			rc = b_kout.reserve(h, "extend sort keys", 8 * S); if (rc) return rc;
+			rc = b_flags.reserve(h, "extend flags", 8 * S); if (rc) return rc;
+			rc = b_scans.reserve(h, "extend scans", 16 * (S + 1)); if (rc) return rc;
+			rc = b_cnt.reserve(h, "extend counts", 4 * S); if (rc) return rc;
+			rc = b_val.reserve(h, "extend weights", 4 * S); if (rc) return rc;
+			size_t sort_bytes = 0;
+			if (kmr::sort_pairs_u64_u32(nullptr, &sort_bytes, nullptr, nullptr, nullptr, nullptr, S, h->stream) != 0) return fail(h, KMR_ERR_HIP, "kmr_extend_contigs: radix sort (size query)");
+			rc = b_sort.reserve(h, "extend sort scratch", std::max<size_t>(sort_bytes, 256)); if (rc) return rc;
+			uint32_t *sgrp = b_sgrp.get<uint32_t>(), *perm = b_perm.get<uint32_t>(), *perm2 = b_perm2.get<uint32_t>();
+			unsigned long long *kin = b_kin.get<unsigned long long>(), *kout = b_kout.get<unsigned long long>();
+			uint32_t *wflag = b_flags.get<uint32_t>(), *sflag = wflag + S, *cnt = b_cnt.get<uint32_t>(); float *val = b_val.get<float>();
+			uint64_t *wscan = b_scans.get<uint64_t>(), *sscan = wscan + (S + 1);
+			const dim3 sgrid(grid_for(S));
+			hipLaunchKernelGGL(extend_fill_kernel, sgrid, block, 0, h->stream, (const uint64_t *)koff, i0, i1 - i0, (const uint32_t *)grp, S, sgrp, perm);
+			HIPCHK(h, hipGetLastError());
+			/* least significant first: the key words from the last to the first, then (contig, source); the sort is stable */
+			for (int pass = 0; pass <= W; pass++) {
+				hipLaunchKernelGGL(extend_sortkey_kernel, sgrid, block, 0, h->stream, (const uint64_t *)stage, (uint32_t)W, (uint32_t)(pass == W ? W : W - 1 - pass), (const uint32_t *)sgrp,
+				                   (const uint32_t *)perm, S, kin);
+				HIPCHK(h, hipGetLastError());
+				size_t sb = b_sort.cap();
+				if (kmr::sort_pairs_u64_u32(b_sort.get(), &sb, kin, kout, perm, perm2, S, h->stream) != 0) return fail(h, KMR_ERR_HIP, "kmr_extend_contigs: radix sort");
+				std::swap(perm, perm2);
+			}
+			tr.mark(2, h->stream);
+			hipLaunchKernelGGL(extend_reduce_kernel, sgrid, block, 0, h->stream, (const uint64_t *)stage, (uint32_t)W, (const uint32_t *)sgrp, (const uint32_t *)perm, S,
+			                   h->cfg.separate_singletons ? 1u : 0u, wflag, sflag, cnt, val);
+			HIPCHK(h, hipGetLastError());
+			rc = exclusive_scan_queue(h, wflag, S, wscan); if (rc) return rc;
+			rc = exclusive_scan_queue(h, sflag, S, sscan); if (rc) return rc;
+			uint64_t nw = 0, ns = 0;
+			HIPCHK(h, hipMemcpyAsync(&nw, wscan + S, 8, hipMemcpyDeviceToHost, h->stream));
+			HIPCHK(h, hipMemcpyAsync(&ns, sscan + S, 8, hipMemcpyDeviceToHost, h->stream));
+			HIPCHK(h, hipStreamSynchronize(h->stream));
+			rc = b_wkeys.reserve(h, "extend weak keys", std::max<size_t>(8ull * W * nw, 256)); if (rc) return rc;
+			rc = b_wcnt.reserve(h, "extend weak counts", std::max<size_t>(4 * nw, 256)); if (rc) return rc;
+			rc = b_wval.reserve(h, "extend weak weights", std::max<size_t>(4 * nw, 256)); if (rc) return rc;
+			rc = b_skeys.reserve(h, "extend solid keys", std::max<size_t>(8ull * W * ns, 256)); if (rc) return rc;
+			wkeys = b_wkeys.get<uint64_t>(); wcnt = b_wcnt.get<uint32_t>(); wval = b_wval.get<float>(); skeys = b_skeys.get<uint64_t>();
+			hipLaunchKernelGGL(extend_compact_kernel, sgrid, block, 0, h->stream, (const uint64_t *)stage, (uint32_t)W, (const uint32_t *)perm, S, (const uint32_t *)wflag, (const uint32_t *)sflag,
+			                   (const uint64_t *)wscan, (const uint64_t *)sscan, (const uint32_t *)cnt, (const float *)val, wkeys, wcnt, wval, skeys);
+			hipLaunchKernelGGL(extend_bounds_kernel, dim3(grid_for(m)), block, 0, h->stream, (const unsigned long long *)kout, S, (const uint64_t *)wscan, (const uint64_t *)sscan, c0, m, bounds);
+			HIPCHK(h, hipGetLastError());
+		} else { tr.mark(1, h->stream); tr.mark(2, h->stream); }
+		tr.mark(3, h->stream);
+		ExtendArgs A;
+		A.cbases = cbases; A.coff = coff; A.active = active; A.c0 = c0; A.m = m;
+		A.wkeys = wkeys; A.wcnt = wcnt; A.wval = wval; A.skeys = skeys; A.bounds = bounds;
+		A.k = h->k; A.max_extend = maxx; A.use_weights = cfg->use_weights ? 1u : 0u;
+		A.min_consensus = cfg->minimum_consensus / 100; A.min_coverage = cfg->minimum_coverage; A.max_delta = cfg->maximum_delta_ratio;
+		A.seq = b_seq.get<uint8_t>(); A.left = left; A.right = right; A.reason = reason; A.vals = vals;
+		const uint64_t blocks = std::min<uint64_t>((m + EXT_WAVES - 1) / EXT_WAVES, (uint64_t)num_cus(h) * 8);
+		A.rec_global = nullptr;
+		if (!rec_lds) { rc = b_rec.reserve(h, "extend recorded keys", std::max<size_t>(rec_wave * EXT_WAVES * blocks, 256)); if (rc) return rc; A.rec_global = b_rec.get<uint64_t>(); }
+		hipLaunchKernelGGL(extend_contigs_kernel<W>, dim3((unsigned)blocks), dim3(EXT_WAVES * 64), rec_lds ? rec_wave * EXT_WAVES : 0, h->stream, A);
+		HIPCHK(h, hipGetLastError());
+		tr.mark(4, h->stream);
+		h->last_extend_runs++;
+		if (tr.on) {
+			HIPCHK(h, hipStreamSynchronize(h->stream));
+			for (int i = 0; i < 4; i++) h->last_extend_ms[1 + i] += tr.ms(i, i + 1);
+		}
+	}
+	/* 4: the result batch */
+	hipLaunchKernelGGL(extend_newlen_kernel, dim3(grid_for(nc)), block, 0, h->stream, coff, nc, (const uint32_t *)left, (const uint32_t *)right, newlen, info);
+	HIPCHK(h, hipGetLastError());
+	rc = exclusive_scan_queue(h, newlen, nc, noff); if (rc) return rc;
+	unsigned long long hinfo[2] = {0, 0};
+	HIPCHK(h, hipMemcpyAsync(&result->total, noff + nc, 8, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipMemcpyAsync(hinfo, info, 16, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipStreamSynchronize(h->stream));
+	out->n_extended = hinfo[0]; out->bases_added = hinfo[1];
+	const uint64_t T = result->total;
+	HIPCHK(h, result->bases.alloc(T + 64)); HIPCHK(h, result->quals.alloc(T + 64));
+	HIPCHK(h, hipMemsetAsync(result->bases.get<uint8_t>() + T, 0, 64, h->stream)); HIPCHK(h, hipMemsetAsync(result->quals.get<uint8_t>() + T, 0, 64, h->stream));
+	if (T) {
+		hipLaunchKernelGGL(extend_result_kernel, dim3(grid_for((T + 63) / 64)), block, 0, h->stream, (const uint64_t *)noff, nc, T, b_seq.get<uint8_t>(), coff, (const uint32_t *)left, maxx,
+		                   result->bases.get<uint8_t>(), result->quals.get<uint8_t>());
+		HIPCHK(h, hipGetLastError());
+	}
+	HIPCHK(h, hipStreamSynchronize(h->stream));      /* the temporaries go */
+	out->result = result.release();
+	return KMR_OK;
+}
+
 }  // namespace
 
 namespace kmr_host {
+int extend_core(kmr_handle *h, const kmr_reads *contigs, const kmr_reads *reads, const uint64_t *pool_offsets, const uint64_t *pool_reads, const uint8_t *active,
+                const kmr_extend_config *cfg, kmr_extend *out) {
+	const int rc = with_w(h, [&](auto W) { return extend_t<W()>(h, contigs, reads, pool_offsets, pool_reads, active, cfg, out); });
+	if (rc) hipStreamSynchronize(h->stream);
+	return rc;
+}
 int tnf_stage_core(kmr_handle *h, const uint8_t *bases, const uint8_t *quals, const uint64_t *offsets, uint64_t n_reads, const uint64_t **koff, const uint64_t **stage, uint64_t *slots) {
 	if (h->W != 1) return fail(h, KMR_ERR_UNSUPPORTED, "tnf_stage_core: a key of more than one word");
 	const int rc = tnf_stage(h, reads_view(bases, quals, offsets, n_reads), koff, stage, slots);

@@ -193,6 +193,8 @@ struct KMR_HIDDEN Tuning {
 	uint64_t compare_stage_kmers = 0;  /* kmr_compare_reads*: staging slots of one run of whole reads (0: CMP_STAGE_SLOTS; tests: a few, so that a batch takes several runs and a read alone exceeds one) */
 	uint32_t tnf_piece_bases = 0;      /* kmr_tnf_reads / kmr_tnf_windows: bases of one piece of a sequence (0: TNF_PIECE_BASES; tests: a few, so that short inputs cross piece edges) */
 	uint64_t match_hit_capacity = 0;   /* kmr_match_add_read_batch: hit records the buffers hold before they first grow (0: MATCH_HIT_CAP; tests: a few, so that the batch is streamed again) */
+	uint64_t extend_stage_kmers = 0;   /* kmr_extend_contigs*: staging slots of one run of whole contigs (0: EXT_STAGE_SLOTS; tests: a few, so that a call takes several runs and a contig alone exceeds one) */
+	bool extend_timing = false;        /* kmr_extend_contigs*: time gather, extraction, sort, reduce and the walk with HIP events (kmr_build_info; measurement tools) */
 	bool no_coarse_lists = true;     /* exchange: scatter into the job's fine lists (default) or, kmr_tune("coarse_lists", 1), into coarse ones that the owner splits before the count pass (sk_refine_kernel: not yet fast enough to pay) */
 };
 
@@ -271,6 +273,7 @@ struct KMR_HIDDEN kmr_handle : HandleMem, BuildMem, ExchangeMem {
 	unsigned int l1_head_seen = 0;     /* the record pool's head as of the last sync_state(h, true) */
 	uint64_t unit_batches = 0;         /* batches that held a read longer than a tile and were cut into work units (kmr_build_info "unit_batches") */
 	int last_match_attempts = 0;       /* how often the last kmr_match_add_read_batch streamed its batch before the hit records fit (kmr_build_info "match_add_attempts") */
+	int last_extend_runs = 0; double last_extend_ms[5] = {0, 0, 0, 0, 0};      /* the last kmr_extend_contigs*: its runs of whole contigs (kmr_build_info "extend_runs") and, with kmr_tune "extend_timing", the HIP-event times of gather, extraction, sort, reduce and walk */
 	int last_count_attempts = 0;    /* how often the last count pass of a kmr_finalize ran before its entries fit (kmr_build_info "count_attempts") */
 	bool qual_mixed = false;           /* a build that has seen two different quality characters stops asking (qrange) */
 	/* exchange with world_size > 1: sk_bits are the COARSE lists reads are scattered into and that travel; each holds 2^sk_fine_shift
@@ -367,6 +370,15 @@ struct KMR_HIDDEN kmr_match : OnDevice {
 	uint64_t n_reads_total = 0, n_sampled = 0;
 };
 
+/* what kmr_extend_contigs* leaves on the device: per contig the new length and the bases added on either side, per contig and side the
+ * stop record (reason; edge, A, C, G, T, total), and the new sequences as a read batch */
+struct KMR_HIDDEN kmr_extend : OnDevice {
+	DevBuf newlen, left, right, reason, vals;
+	kmr_reads *result = nullptr;                  /* owned */
+	~kmr_extend() { delete result; }
+	uint64_t n = 0, n_extended = 0, bases_added = 0;
+};
+
 namespace kmr_host KMR_HIDDEN {
 
 inline std::string oom_note() { std::string s(g_oom_note); g_oom_note[0] = 0; return s; }
@@ -455,6 +467,11 @@ int tnf_stage_core(kmr_handle *h, const uint8_t *bases, const uint8_t *quals, co
 int match_create_core(kmr_handle *h, kmr_match *m, const uint8_t *bases, const uint64_t *offsets, uint64_t n_contigs);
 int match_add_core(kmr_handle *h, kmr_match *m, const uint8_t *bases, const uint8_t *quals, const uint64_t *offsets, uint64_t n_reads, uint64_t first_global,
                    const int64_t *mate, const uint8_t *discarded);
+
+/* ContigExtender (kmr_extend.hpp): gathers the pools, builds their spectra and walks the contigs; fills `out` and waits.  The batches are
+ * of h's device, cfg is checked; pool_offsets (n_contigs + 1), pool_reads and active (or NULL) are device memory */
+int extend_core(kmr_handle *h, const kmr_reads *contigs, const kmr_reads *reads, const uint64_t *pool_offsets, const uint64_t *pool_reads, const uint8_t *active,
+                const kmr_extend_config *cfg, kmr_extend *out);
 
 /* ---- defined in kmr_stages.hip (its kmr_ingest.hpp holds the two-bit kernels): what the spectrum's packed feed path launches.  All
  * pointers are device memory; the work is queued on the handle's stream. */

@@ -14,6 +14,7 @@
 #include "kmr_superkmer.hpp"
 #include "kmr_compare.hpp"
 #include "kmr_match.hpp"
+#include "kmr_extend.hpp"
 
 namespace kmr {
 
@@ -46,7 +47,7 @@ static const int PD_THREADS = 1024, PD_RPT = 8, PD_LINE = 4;
 #define KMR_SKC_W(W) KMR_SKC(W, false) KMR_SKCU(W) KMR_SKC(W, true) KMR_SKCX(W, false, true) \
 	KMR_SKCI(W, false, false, false, true) KMR_SKCI(W, false, false, true, true) KMR_SKCI(W, false, true, false, true) KMR_SKL(W)
 
-/* build modes 1 and 2, lookups, owner requests, per-read spectrum comparison (kmr_compare.hpp), read-to-contig matching (kmr_match.hpp): the k-mer extraction with its Ops */
+/* build modes 1 and 2, lookups, owner requests, per-read spectrum comparison (kmr_compare.hpp), read-to-contig matching (kmr_match.hpp), the pools' spectra of the contig extension (kmr_extend.hpp): the k-mer extraction with its Ops */
 #define KMR_EX(W, EXT, OP, SUB) KMR_T __global__ void extract_kernel<W, EXT, OP, SUB>(ReadsView, DevParams, OP);
 #define KMR_EX_OP(W, EXT, ...) KMR_T __global__ void extract_kernel<W, EXT, __VA_ARGS__, false>(ReadsView, DevParams, __VA_ARGS__); KMR_T __global__ void extract_kernel<W, EXT, __VA_ARGS__, true>(ReadsView, DevParams, __VA_ARGS__);
 #define KMR_EX_W(W) \
@@ -55,7 +56,7 @@ static const int PD_THREADS = 1024, PD_RPT = 8, PD_LINE = 4;
 	KMR_EX_OP(W, true, LinearOp<W, true, false>) KMR_EX_OP(W, true, LinearOp<W, true, true>) \
 	KMR_T __global__ void extract_kernel<W, false, LookupOp<W>, false>(ReadsView, DevParams, LookupOp<W>); \
 	KMR_T __global__ void extract_kernel<W, false, LookupWeightOp<W>, false>(ReadsView, DevParams, LookupWeightOp<W>); \
-	KMR_EX_OP(W, false, CompareOp<W>) KMR_EX_OP(W, false, MatchOp<W>)
+	KMR_EX_OP(W, false, CompareOp<W>) KMR_EX_OP(W, false, MatchOp<W>) KMR_EX_OP(W, false, ExtendOp<W>)
 
 /* build_mode 2: partition passes, owner scatter, count pass over k-mer records */
 #define KMR_PD(W, EXT, LEVEL) KMR_T __global__ void partition_direct_kernel<W, EXT, LEVEL, PD_THREADS, PD_RPT, PD_LINE>(PartSource<W>, PoolView, unsigned int *, const int, const int);

@@ -1,6 +1,6 @@
 /*
  * kmr_stages.hip -- the read stages of include/kmernator_amd.h: FASTQ ingest and the kmr_reads batch, its two-bit form, the artifact
- * filter and its report, read selection, coverage normalization and their output text, identifyPairs, duplicate-fragment collapse, the mercount / mergraph text, TnfDistance's vectors and distances, and KmerMatch's entry points with its finish.
+ * filter and its report, read selection, coverage normalization and their output text, identifyPairs, duplicate-fragment collapse, the mercount / mergraph text, TnfDistance's vectors and distances, KmerMatch's entry points with its finish, and ContigExtender's entry points.
  *
  * Host logic only, as kmr_api.hip (the spectrum, which these stages read through kmr_host.hpp); the kernels are the stage headers',
  * each of which this translation unit alone includes.  A stage costs its kernels and a page here: what the stages share is below --
@@ -26,6 +26,8 @@
 #include "kmr_tnf.hpp"
 #define KMR_MATCH_FINISH      /* the finish kernels; the table and the Op are kmr_api.hip's */
 #include "kmr_match.hpp"
+
+static const int EXT_VALS = 6;      /* values of a stop record (kmr_extend.hpp, whose kernels are kmr_api.hip's): edge, A, C, G, T, total */
 
 using namespace kmr;
 
@@ -712,6 +714,122 @@ int kmr_match_device_ptrs(const kmr_match *m, void **dev_offsets, void **dev_rea
 	return KMR_OK;
 }
 void kmr_match_free(kmr_match *m) { free_on_device(m); }
+
+/* ---- ContigExtender (src/ContigExtender.h, src/KmerSpectrum.h:2311-2373; kernels: kmr_extend.hpp, launched by kmr_api.hip's extend_core) ---- */
+int kmr_extend_config_init(kmr_extend_config *c) {
+	if (!c) return KMR_ERR_INVALID_ARG;
+	memset(c, 0, sizeof(*c));
+	c->struct_size = (uint32_t)sizeof(kmr_extend_config);
+	c->max_extend = 50;                    /* extendContigs' maxExtend, ContigExtender.h:152 */
+	c->minimum_consensus = 85;             /* _ContigExtenderBaseOptions, ContigExtender.h:63 */
+	c->minimum_coverage = 4.8;
+	c->maximum_delta_ratio = 0.33;
+	c->use_weights = 1;
+	return KMR_OK;
+}
+static int extend_any(kmr_handle *h, const kmr_reads *contigs, const kmr_reads *reads, const uint64_t *pool_offsets, const uint64_t *pool_reads, const uint8_t *active, bool on_device,
+                      const kmr_extend_config *cfg, kmr_extend **out) {
+	if (out) *out = nullptr;
+	if (!h || !contigs || !reads || !cfg || !out || !pool_offsets) return fail(h, KMR_ERR_INVALID_ARG, "kmr_extend_contigs: NULL argument");
+	if (cfg->struct_size != sizeof(kmr_extend_config)) return fail(h, KMR_ERR_INVALID_ARG, "kmr_extend_config: struct_size " + std::to_string(cfg->struct_size) + " is not " + std::to_string(sizeof(kmr_extend_config)));
+	if (contigs->device != h->device || reads->device != h->device) return fail(h, KMR_ERR_INVALID_ARG, "kmr_extend_contigs: the contigs or the reads live on another device");
+	if (cfg->max_extend > KMR_EXTEND_MAX_EXTEND) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_extend_contigs: max_extend above " + std::to_string(KMR_EXTEND_MAX_EXTEND));
+	if (cfg->minimum_consensus != cfg->minimum_consensus || cfg->minimum_coverage != cfg->minimum_coverage || cfg->maximum_delta_ratio != cfg->maximum_delta_ratio)
+		return fail(h, KMR_ERR_INVALID_ARG, "kmr_extend_config: a NaN option");
+	if (contigs->n >= 0x7fffffffull) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_extend_contigs: 2^31 - 1 contigs or more");
+	hipSetDevice(h->device);
+	Scratch tmp(h);
+	const uint64_t nc = contigs->n;
+	const uint64_t *dpo, *dpr; const uint8_t *dact;
+	uint64_t P = 0;
+	if (!on_device) {      /* the host sees the offsets: what the device would refuse is refused before anything is copied */
+		if (pool_offsets[0] != 0) return fail(h, KMR_ERR_INVALID_ARG, "kmr_extend_contigs: pool_offsets does not start at 0 or does not ascend");
+		for (uint64_t c = 0; c < nc; c++) if (pool_offsets[c + 1] < pool_offsets[c]) return fail(h, KMR_ERR_INVALID_ARG, "kmr_extend_contigs: pool_offsets does not start at 0 or does not ascend");
+		P = pool_offsets[nc];
+		if (P && !pool_reads) return fail(h, KMR_ERR_INVALID_ARG, "kmr_extend_contigs: NULL argument");
+	}
+	int rc = to_device(h, tmp, pool_offsets, nc + 1, &dpo, on_device); if (rc) return rc;
+	rc = to_device(h, tmp, pool_reads, P, &dpr, on_device); if (rc) return rc;
+	rc = to_device(h, tmp, active, nc, &dact, on_device); if (rc) return rc;
+	auto e = make_result<kmr_extend>(h);
+	rc = extend_core(h, contigs, reads, dpo, dpr, dact, cfg, e.get()); if (rc) return rc;      /* (waits for the stream) */
+	tmp.done();
+	*out = e.release();
+	return KMR_OK;
+}
+int kmr_extend_contigs(kmr_handle *h, const kmr_reads *contigs, const kmr_reads *reads, const uint64_t *pool_offsets, const uint64_t *pool_reads, const uint8_t *active,
+                       const kmr_extend_config *cfg, kmr_extend **out) {
+	return extend_any(h, contigs, reads, pool_offsets, pool_reads, active, false, cfg, out);
+}
+int kmr_extend_contigs_dev(kmr_handle *h, const kmr_reads *contigs, const kmr_reads *reads, const void *dev_pool_offsets, const void *dev_pool_reads, const void *dev_active,
+                           const kmr_extend_config *cfg, kmr_extend **out) {
+	return extend_any(h, contigs, reads, (const uint64_t *)dev_pool_offsets, (const uint64_t *)dev_pool_reads, (const uint8_t *)dev_active, true, cfg, out);
+}
+int kmr_extend_info(const kmr_extend *e, uint64_t *n_contigs, uint64_t *n_extended, uint64_t *bases_added) {
+	if (!e) return KMR_ERR_INVALID_ARG;
+	if (n_contigs) *n_contigs = e->n;
+	if (n_extended) *n_extended = e->n_extended;
+	if (bases_added) *bases_added = e->bases_added;
+	return KMR_OK;
+}
+int kmr_extend_copy(const kmr_extend *e, uint32_t *new_len, uint32_t *left, uint32_t *right, kmr_extend_stop *stops) {
+	if (!e) return KMR_ERR_INVALID_ARG;
+	hipSetDevice(e->device);
+	hipError_t err = hipSuccess;
+	copy_out(err, new_len, e->newlen, e->n); copy_out(err, left, e->left, e->n); copy_out(err, right, e->right, e->n);
+	if (stops && e->n) {
+		std::vector<uint32_t> reason(2 * e->n); std::vector<double> vals(2 * e->n * EXT_VALS);
+		copy_out(err, reason.data(), e->reason, 2 * e->n); copy_out(err, vals.data(), e->vals, 2 * e->n * EXT_VALS);
+		for (uint64_t i = 0; i < 2 * e->n && err == hipSuccess; i++) {
+			kmr_extend_stop &s = stops[i];
+			const double *v = &vals[i * EXT_VALS];
+			s.reason = reason[i]; s.reserved = 0; s.edge = v[0]; s.ext[0] = v[1]; s.ext[1] = v[2]; s.ext[2] = v[3]; s.ext[3] = v[4]; s.total = v[5];
+		}
+	}
+	return err == hipSuccess ? KMR_OK : KMR_ERR_HIP;
+}
+int kmr_extend_reads(const kmr_extend *e, const kmr_reads **reads) {
+	if (!e || !reads) return KMR_ERR_INVALID_ARG;
+	*reads = e->result;
+	return KMR_OK;
+}
+void kmr_extend_free(kmr_extend *e) { free_on_device(e); }
+/* ContigExtender::getNewName (ContigExtender.h:249-268) */
+int kmr_extend_new_name(const char *old_name, uint64_t left, uint64_t right, char *buf, uint64_t cap) {
+	if (!old_name || !buf) return KMR_ERR_INVALID_ARG;
+	const std::string oldName(old_name);
+	std::string newName = oldName;
+	if (left + right != 0) {
+		std::string::size_type preLeft = 0, preRight = 0;
+		const std::string::size_type pos = oldName.find_last_of("-l");      /* the last '-' or 'l' */
+		if (pos != std::string::npos) {
+			const std::string::size_type pos2 = oldName.find_first_of("r", pos);
+			if (pos2 != std::string::npos) {
+				preLeft = (std::string::size_type)atoi(oldName.substr(pos + 1, pos2 - pos - 1).c_str());
+				preRight = (std::string::size_type)atoi(oldName.substr(pos2 + 1).c_str());
+				newName = oldName.substr(0, pos - 1);      /* (pos == 0: npos characters, the whole name) */
+			}
+		}
+		newName = newName + "-l" + std::to_string(left + preLeft) + "r" + std::to_string(right + preRight);
+	}
+	if (newName.size() + 1 > cap) return KMR_ERR_CAPACITY;
+	memcpy(buf, newName.c_str(), newName.size() + 1);
+	return KMR_OK;
+}
+/* ContigExtender::getMinMaxKmerSize (ContigExtender.h:269-279), SequenceLengthType being 32 bits wide */
+int kmr_extend_min_max_kmer_size(uint32_t kmer_size, uint32_t max_sequence_length, uint64_t base_count, uint64_t n_reads, uint32_t max_steps,
+                                 uint32_t *min_kmer_size, uint32_t *max_kmer_size, uint32_t *kmer_step) {
+	if (!n_reads || !max_steps || !min_kmer_size || !max_kmer_size || !kmer_step) return KMR_ERR_INVALID_ARG;
+	const uint32_t minK = kmer_size;
+	const uint32_t maxLen = std::min<uint32_t>(max_sequence_length, (uint32_t)(base_count / n_reads));
+	uint32_t maxK = std::min<uint32_t>((uint32_t)(maxLen * 0.95), maxLen - 1u);
+	maxK = std::max(minK, maxK);
+	uint32_t step = (maxK - minK) / max_steps;
+	step = (step & 1u) == 1u ? step + 1u : step;
+	step = std::max<uint32_t>(2u, step);
+	*min_kmer_size = minK; *max_kmer_size = maxK; *kmer_step = step;
+	return KMR_OK;
+}
 
 }  // extern "C"
 

@@ -1125,6 +1125,175 @@ class KmerMatch(_DeviceObject):
         return tuple(x.value or 0 for x in p)
 
 
+# one kmr_extend_stop: why a side of a contig stopped and the f64 values of the last step it tried
+EXTEND_STOP_DTYPE = np.dtype([("reason", np.uint32), ("reserved", np.uint32), ("edge", np.float64), ("ext", np.float64, (4,)), ("total", np.float64)])
+MAX_KMER_SIZE = 128      # the library's longest k-mer
+_FASTA = bytes((c & 0xDF) if chr(c) in "acgt" else (ord("N") if c == ord(".") else c) for c in range(256))      # Read::getFasta of a stored base
+
+
+def _sequences(read_set):
+    b, _, o, _ = read_set.arrays()
+    return [b[int(o[i]):int(o[i + 1])].tobytes() for i in range(read_set.n)]
+
+
+class ExtendResults(_DeviceObject):
+    """What ContigExtender.extendContigs answers (kmr_extend), kept on the device until close(): .read_set = the new sequences, every
+    quality Read::REF_QUAL, as a ReadSet that KmerMatch and a further extendContigs take (it lives as long as this object);
+    .names (ContigExtender.getNewName of the names handed in), .left / .right = bases added per contig, .new_len, .stops = an
+    (n, 2) array of EXTEND_STOP_DTYPE, left and right; .n_extended, .bases_added."""
+    _HANDLE, _FREE = "_e", "kmr_extend_free"
+
+    def __init__(self, sp, handle, names):
+        self.sp, self._e = sp, handle
+        v = [C.c_uint64() for _ in range(3)]
+        _ok(sp.lib.kmr_extend_info(handle, *[C.byref(x) for x in v]), "kmr_extend_info")
+        self.n, self.n_extended, self.bases_added = [x.value for x in v]
+        n1 = max(1, self.n)
+        nl, lt, rt = np.zeros(n1, dtype=np.uint32), np.zeros(n1, dtype=np.uint32), np.zeros(n1, dtype=np.uint32)
+        st = np.zeros((n1, 2), dtype=EXTEND_STOP_DTYPE)
+        u32 = C.POINTER(C.c_uint32)
+        _ok(sp.lib.kmr_extend_copy(handle, nl.ctypes.data_as(u32), lt.ctypes.data_as(u32), rt.ctypes.data_as(u32), st.ctypes.data_as(C.POINTER(_lib.KmrExtendStop))), "kmr_extend_copy")
+        self.new_len, self.left, self.right, self.stops = nl[:self.n], lt[:self.n], rt[:self.n], st[:self.n]
+        r = C.c_void_p()
+        _ok(sp.lib.kmr_extend_reads(handle, C.byref(r)), "kmr_extend_reads")
+        self.read_set = ConsensusReadSet._borrow(self, sp, b"", r)
+        self.names = None if names is None else [ContigExtender.getNewName(nm, int(l), int(r_)) for nm, l, r_ in zip(names, self.left, self.right)]
+
+    def sequences(self):
+        """the new sequences as a list of bytes"""
+        return _sequences(self.read_set)
+
+    def close(self):
+        if getattr(self, "_e", None):
+            self.read_set.r = None
+        super().close()
+
+
+class ContigExtender:
+    """ContigExtender<KS>::extendContigs at one k-mer size (src/ContigExtender.h:157-247 with minKmerSize == maxKmerSize, over
+    KmerSpectrum::extendContig, src/KmerSpectrum.h:2311-2373), every contig with its own pool of reads, all at once on the device
+    (kmr_extend_*).  `spectrum` supplies k and the build's config -- min_weight, qualities, separate_singletons -- and need not have
+    been fed.  Options: max_extend (50), minimum_consensus in percent (85), minimum_coverage (4.8), maximum_delta_ratio (0.33),
+    use_weights (True)."""
+
+    def __init__(self, spectrum, max_extend=50, minimum_consensus=85.0, minimum_coverage=4.8, maximum_delta_ratio=0.33, use_weights=True):
+        self.sp = spectrum
+        cfg = _lib.KmrExtendConfig()
+        _ok(spectrum.lib.kmr_extend_config_init(C.byref(cfg)), "kmr_extend_config_init")
+        cfg.max_extend, cfg.minimum_consensus, cfg.minimum_coverage = int(max_extend), float(minimum_consensus), float(minimum_coverage)
+        cfg.maximum_delta_ratio, cfg.use_weights = float(maximum_delta_ratio), 1 if use_weights else 0
+        self.cfg = cfg
+
+    @staticmethod
+    def _pools(pools, first_global_read_idx):
+        if isinstance(pools, MatchResults):
+            return np.ascontiguousarray(pools.offsets, dtype=np.uint64), np.ascontiguousarray(pools.reads, dtype=np.uint64) - np.uint64(first_global_read_idx)
+        off, idx = pools
+        return np.ascontiguousarray(off, dtype=np.uint64), np.ascontiguousarray(idx, dtype=np.uint64)
+
+    def extendContigs(self, contigs, read_set, pools, names=None, active=None, first_global_read_idx=0):
+        """`pools`: a MatchResults (its global read indices less `first_global_read_idx` index `read_set`) or an (offsets, indices)
+        pair; `names`: the contigs' names, for ExtendResults.names; `active`: one flag per contig, 0 = leave it as it is"""
+        off, idx = self._pools(pools, first_global_read_idx)
+        if off.size != contigs.n + 1:
+            raise KmerSpectrumError("ContigExtender.extendContigs: one pool per contig")
+        a = None if active is None else _u8(active)
+        if a is not None and a.size != contigs.n:
+            raise KmerSpectrumError("ContigExtender.extendContigs: one active flag per contig")
+        u64 = C.POINTER(C.c_uint64)
+        e = C.c_void_p()
+        self.sp._call("extend_contigs", self.sp.h, contigs._live(), read_set._live(), off.ctypes.data_as(u64), idx.ctypes.data_as(u64) if idx.size else None,
+                      None if a is None or not a.size else a.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(self.cfg), C.byref(e))
+        return ExtendResults(self.sp, e, names)
+
+    def extendContigsDevice(self, contigs, read_set, dev_offsets, dev_indices, names=None, dev_active=0):
+        """the same with the pools (uint64 offsets, uint64 indices into `read_set`) and the flags as device pointers, e.g. KmerMatch.device_ptrs()"""
+        e = C.c_void_p()
+        self.sp._call("extend_contigs_dev", self.sp.h, contigs._live(), read_set._live(), C.c_void_p(dev_offsets), C.c_void_p(dev_indices or None), C.c_void_p(dev_active or None),
+                      C.byref(self.cfg), C.byref(e))
+        return ExtendResults(self.sp, e, names)
+
+    @staticmethod
+    def getNewName(old_name, left_total, right_total):
+        """ContigExtender::getNewName (src/ContigExtender.h:249-268) through kmr_extend_new_name; bytes in, bytes out"""
+        old = old_name.encode() if isinstance(old_name, str) else bytes(old_name)
+        buf = C.create_string_buffer(len(old) + 48)
+        _ok(_lib.load().kmr_extend_new_name(old, int(left_total), int(right_total), buf, len(buf)), "kmr_extend_new_name")
+        return buf.value
+
+    @staticmethod
+    def getMinMaxKmerSize(kmer_size, max_sequence_length, base_count, n_reads, max_steps=6):
+        """ContigExtender::getMinMaxKmerSize (:269-279): (min_kmer_size, max_kmer_size, kmer_step)"""
+        v = [C.c_uint32() for _ in range(3)]
+        _ok(_lib.load().kmr_extend_min_max_kmer_size(int(kmer_size), int(max_sequence_length), int(base_count), int(n_reads), int(max_steps), *[C.byref(x) for x in v]),
+            "kmr_extend_min_max_kmer_size")
+        return tuple(x.value for x in v)
+
+
+class ExtendRound(tuple):
+    """(changed, final, log text) of extendContigsWithContigExtender -- changed and final are lists of (name, sequence) --, and
+    .skipped_k: the k-mer sizes of the sweep that the library does not reach"""
+
+    def __new__(cls, changed, final, log, skipped_k):
+        self = super().__new__(cls, (changed, final, log))
+        self.skipped_k = skipped_k
+        return self
+
+
+def extendContigsWithContigExtender(make_spectrum, contigs, names, read_set, pools, min_kmer_size, max_kmer_size, kmer_step, minimum_coverage=4.8, max_extend=50,
+                                    first_global_read_idx=0, **options):
+    """extendContigsWithContigExtender (apps/DistributedNucleatingAssembler.cpp:230-275): every contig whose pool holds more than
+    `minimum_coverage` reads is extended at min_kmer_size, and again at the next k-mer size -- from its original sequence -- while it
+    has not grown and the size is not above max_kmer_size.  One never-fed spectrum per k-mer size comes from make_spectrum(k); a pass
+    works on all contigs that have not grown at once, the others are switched off through `active`.  Sizes above 128, the library's
+    longest k-mer, are skipped (ExtendRound.skipped_k): for 150-base reads the reference's sweep would reach 142.
+    Returns (changed, final, log text) as the reference fills and logs them."""
+    off, _ = ContigExtender._pools(pools, first_global_read_idx)
+    nc = contigs.n
+    names = [nm.encode() if isinstance(nm, str) else bytes(nm) for nm in names]
+    seqs = _sequences(contigs)
+    pool_size = [int(off[i + 1]) - int(off[i]) for i in range(nc)]
+    old_len = [len(s) for s in seqs]
+    new_len = [0] * nc
+    new_seq, new_name, used_k = list(seqs), list(names), [0] * nc
+    active = np.array([1 if pool_size[i] > minimum_coverage else 0 for i in range(nc)], dtype=np.uint8)
+    skipped = []
+    k = int(min_kmer_size)
+    while k <= max_kmer_size and active.any():
+        if k > MAX_KMER_SIZE:
+            skipped.append(k)
+        else:
+            sp = make_spectrum(k)
+            with ContigExtender(sp, max_extend=max_extend, minimum_coverage=minimum_coverage, **options).extendContigs(
+                    contigs, read_set, pools, names=names, active=active, first_global_read_idx=first_global_read_idx) as res:
+                rs = res.sequences()
+                for i in range(nc):
+                    if active[i]:
+                        new_len[i], new_seq[i], new_name[i], used_k[i] = len(rs[i]), rs[i], res.names[i], k
+                        if new_len[i] > old_len[i]:
+                            active[i] = 0
+        k += int(kmer_step)
+    changed, final, log = [], [], []
+    for i in range(nc):
+        delta = new_len[i] - old_len[i]
+        if delta > 0:
+            log.append(b"\nKmer Extended %s %d bases to %d: %s with %d reads in the pool K %d" % (names[i], delta, new_len[i], new_name[i], pool_size[i], used_k[i]))
+            changed.append((new_name[i], new_seq[i]))
+        else:
+            log.append(b"\nDid not extend %s with %d reads in the pool" % (names[i], pool_size[i]))
+            final.append((names[i], seqs[i].translate(_FASTA)))
+    return ExtendRound(changed, final, b"".join(log), skipped)
+
+
+def finishLongContigs(max_contig_length, changed, final):
+    """finishLongContigs (apps/DistributedNucleatingAssembler.cpp:277-288): the changed contigs of at least max_contig_length bases move
+    to the end of `final`; returns the (changed, final) lists that remain"""
+    keep = []
+    final = list(final)
+    for name, seq in changed:
+        (final if len(seq) >= max_contig_length else keep).append((name, seq))
+    return keep, final
+
 
 class FilterKnownOddities(_DeviceObject):
     """The artifact filter FilterReads runs before the spectrum build (src/FilterKnownOddities.h, apps/FilterReads.cpp:107-118):
