@@ -11,7 +11,8 @@
  * with_win), kernel-argument structs (reads_view, finalize_params, count_out, sk_own_lists), the plan of the count pass over
  * super-k-mer lists (sk_count_uniform, sk_count_select), the entry buffers' policy and the attempt loop of a count pass (count_entry_buffers,
  * count_attempts), the end of a finalize (publish_maps), the host-to-device piece pipeline (tb_feed_pieces), what a feed call hands down
- * (FeedHints) and its one way into the build (add_reads_dev_call, the sk_* parts of add_reads_superkmer_t).  The heavy kernel
+ * (FeedHints) and its one way into the build (add_reads_dev_call, the sk_* parts of add_reads_superkmer_t), and what the stages at the
+ * end of the file share (CompareSpectrums per read, TnfDistance, KmerMatch, ContigExtender: kmer_slot_plan, stage_run, own_reads_params, kmr_runs.hpp).  The heavy kernel
  * templates are compiled elsewhere (kmr_instances.hpp, kmr_inst.hip); the headers' plain kernels here.
  */
 #include <hip/hip_runtime.h>
@@ -33,6 +34,7 @@
 #include <vector>
 
 #include "kmr_host.hpp"
+#include "kmr_runs.hpp"
 #include "kmr_kernels.hpp"
 #include "kmr_partition.hpp"
 #include "kmr_superkmer.hpp"
@@ -3410,8 +3412,55 @@ int kmr_kernel_time_reset(kmr_handle *h) {
 /* ---- CompareSpectrums (kmr_compare.hpp): the spectrum side of kmr_compare_spectrums / kmr_compare_reads* (kmr_stages.hip) ---- */
 namespace {
 
-/* h->cmp_buf: what compare_reads_core keeps between calls */
-enum { CMP_B_ACC = 0, CMP_B_NK, CMP_B_KOFF, CMP_B_STAGE, CMP_B_CNT, CMP_B_LOFF, CMP_B_SRC, CMP_B_RID, CMP_B_PERM, CMP_B_PERM2, CMP_B_KIN, CMP_B_KOUT, CMP_B_HSCAN, CMP_B_START, CMP_B_SORT };
+/* h->cmp_buf: what compare_reads_core keeps between calls (the sorted path's sort: h->cmp_sort) */
+enum { CMP_B_ACC = 0, CMP_B_NK, CMP_B_KOFF, CMP_B_STAGE, CMP_B_CNT, CMP_B_LOFF, CMP_B_SRC, CMP_B_RID, CMP_B_PERM, CMP_B_HSCAN, CMP_B_START, CMP_B_COUNT };
+static_assert(CMP_B_COUNT == sizeof(HandleMem::cmp_buf) / sizeof(DevBuf), "kmr_host.hpp's cmp_buf holds one block per CMP_B_ index");
+
+/* dev_params for an extraction whose reads are the call's own: nothing is subtracted.  whole: every k-mer of the batch is this
+ * call's too, whatever the handle's kmer_subsample, world_size and num_parts */
+DevParams own_reads_params(kmr_handle *h, bool whole) {
+	DevParams dp = dev_params(h);
+	dp.sub_wstart = dp.sub_wkeys = dp.sub_sstart = dp.sub_skeys = nullptr; dp.sub_wvals = nullptr; dp.sub_sweight = nullptr; dp.sub_wnb = dp.sub_snb = 0;
+	if (whole) { dp.subsample = 1; dp.world = 1; dp.rank = 0; dp.num_parts = 1; dp.part_idx = 0; }
+	return dp;
+}
+
+/* k-mers per read into nk (n) and their exclusive scan into koff (n + 1), queued: k-mer i of read r has slot koff[r] + i.  most_err:
+ * two device words, zero before: the most k-mers of a read, and 1 if a read holds 2^32 or more */
+int kmer_slots_queue(kmr_handle *h, const uint64_t *offsets, uint64_t n, uint32_t *nk, uint64_t *koff, unsigned int *most_err) {
+	hipLaunchKernelGGL(compare_nk_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, offsets, n, h->k, nk, most_err, most_err + 1);
+	HIPCHK(h, hipGetLastError());
+	return exclusive_scan_queue(h, nk, n, koff);
+}
+/* ... in h->cmp_buf (*koff), with the call's one fixed-size copy behind: all slots, the most of a read, the error word (waits).  A read
+ * of 2^32 k-mers or more is refused with the caller's text */
+int kmer_slot_plan(kmr_handle *h, const uint64_t *offsets, uint64_t n, uint64_t **koff, uint64_t *total, unsigned int *most, const char *refusal) {
+	DevBuf *B = h->cmp_buf;
+	int rc = B[CMP_B_ACC].reserve(h, "compare counters", 256); if (rc) return rc;
+	rc = B[CMP_B_NK].reserve(h, "compare k-mer counts", 4 * std::max<uint64_t>(n, 1)); if (rc) return rc;
+	rc = B[CMP_B_KOFF].reserve(h, "compare k-mer offsets", 8 * (n + 1)); if (rc) return rc;
+	unsigned int *most_err = (unsigned int *)((unsigned long long *)(B[CMP_B_ACC].get<CompareRec>() + 1) + CMP_T_WORDS), hm[2] = {0, 0};
+	*koff = B[CMP_B_KOFF].get<uint64_t>(); *total = 0;
+	HIPCHK(h, hipMemsetAsync(most_err, 0, 8, h->stream));
+	rc = kmer_slots_queue(h, offsets, n, B[CMP_B_NK].get<uint32_t>(), *koff, most_err); if (rc) return rc;
+	HIPCHK(h, hipMemcpyAsync(total, *koff + n, 8, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipMemcpyAsync(hm, most_err, 8, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipStreamSynchronize(h->stream));
+	*most = hm[0];
+	return hm[1] ? fail(h, KMR_ERR_UNSUPPORTED, refusal) : 0;
+}
+
+/* Stages one run: `slots` slots of `words` words in buf, all ones, then reads [first, first + count) of the batch through
+ * extract_kernel with op, whose stage this sets */
+template <int W, class Op> int stage_run(kmr_handle *h, DevBuf &buf, const char *what, const ReadsView &all, uint64_t first, uint64_t count, uint64_t slots, uint32_t words,
+                                         const DevParams &dp, Op op) {
+	int rc = buf.reserve(h, what, 8ull * words * slots); if (rc) return rc;
+	op.stage = buf.get<uint64_t>();
+	HIPCHK(h, hipMemsetAsync(op.stage, 0xff, 8ull * words * slots, h->stream));
+	ReadsView rv = reads_slice(all, first, count);
+	rc = prepare_units(h, rv); if (rc) return rc;
+	return launch_extract<W, false>(h, rv, dp, op);
+}
 
 uint64_t map_entries(const DevMap &m) { return m.present ? m.n : 0; }
 
@@ -3465,34 +3514,25 @@ template <int W> int compare_long_run(kmr_handle *h, const uint64_t *stage, cons
 	rc = B[CMP_B_SRC].reserve(h, "compare sort slots", 4 * c); if (rc) return rc;
 	rc = B[CMP_B_RID].reserve(h, "compare sort reads", 4 * c); if (rc) return rc;
 	rc = B[CMP_B_PERM].reserve(h, "compare sort order", 4 * c); if (rc) return rc;
-	rc = B[CMP_B_PERM2].reserve(h, "compare sort order", 4 * c); if (rc) return rc;
-	rc = B[CMP_B_KIN].reserve(h, "compare sort keys", 8 * c); if (rc) return rc;
-	rc = B[CMP_B_KOUT].reserve(h, "compare sort keys", 8 * c); if (rc) return rc;
 	rc = B[CMP_B_HSCAN].reserve(h, "compare heads", 8 * (c + 1)); if (rc) return rc;
 	rc = B[CMP_B_START].reserve(h, "compare head starts", 8 * (c + 1)); if (rc) return rc;
-	size_t sort_bytes = 0;
-	if (kmr::sort_pairs_u64_u32(nullptr, &sort_bytes, nullptr, nullptr, nullptr, nullptr, c, h->stream) != 0) return fail(h, KMR_ERR_HIP, "kmr_compare_reads: radix sort (size query)");
-	rc = B[CMP_B_SORT].reserve(h, "compare sort scratch", std::max<size_t>(sort_bytes, 256)); if (rc) return rc;
-	uint32_t *src = B[CMP_B_SRC].get<uint32_t>(), *rid = B[CMP_B_RID].get<uint32_t>(), *perm = B[CMP_B_PERM].get<uint32_t>(), *perm2 = B[CMP_B_PERM2].get<uint32_t>();
-	unsigned long long *kin = B[CMP_B_KIN].get<unsigned long long>(), *kout = B[CMP_B_KOUT].get<unsigned long long>();
+	uint32_t *src = B[CMP_B_SRC].get<uint32_t>(), *rid = B[CMP_B_RID].get<uint32_t>();
 	uint64_t *hscan = B[CMP_B_HSCAN].get<uint64_t>(), *start = B[CMP_B_START].get<uint64_t>();
-	uint32_t *head = (uint32_t *)kout;      /* the sort keys are dead once the order stands */
 	const dim3 cgrid(grid_for(c));
-	hipLaunchKernelGGL(compare_long_fill_kernel, cgrid, block, 0, h->stream, koff, r0, m, (const uint64_t *)loff, c, src, rid, perm);
+	hipLaunchKernelGGL(compare_long_fill_kernel, cgrid, block, 0, h->stream, koff, r0, m, (const uint64_t *)loff, c, src, rid, B[CMP_B_PERM].get<uint32_t>());
 	HIPCHK(h, hipGetLastError());
 	/* least significant first: the key words, then the read; the sort is stable */
-	for (uint32_t w = 0; w <= (uint32_t)W; w++) {
-		hipLaunchKernelGGL(compare_long_gather_kernel, cgrid, block, 0, h->stream, stage, (uint32_t)W, w, (const uint32_t *)src, (const uint32_t *)rid, (const uint32_t *)perm, c, kin);
-		HIPCHK(h, hipGetLastError());
-		size_t sb = B[CMP_B_SORT].cap();
-		if (kmr::sort_pairs_u64_u32(B[CMP_B_SORT].get(), &sb, kin, kout, perm, perm2, c, h->stream) != 0) return fail(h, KMR_ERR_HIP, "kmr_compare_reads: radix sort");
-		std::swap(perm, perm2);
-	}
-	hipLaunchKernelGGL(compare_long_heads_kernel, cgrid, block, 0, h->stream, stage, (uint32_t)W, (const uint32_t *)src, (const uint32_t *)rid, (const uint32_t *)perm, c, head);
+	SortColumn cols[W + 1];
+	for (int w = 0; w < W; w++) cols[w] = SortColumn{stage + w, (uint64_t)W, src, nullptr};
+	cols[W] = SortColumn{nullptr, 0, nullptr, rid};
+	const uint32_t *perm; unsigned long long *kout;
+	rc = sort_by_columns(h, h->cmp_sort, cols, W + 1, B[CMP_B_PERM].get<uint32_t>(), c, "kmr_compare_reads", &perm, &kout); if (rc) return rc;
+	uint32_t *head = (uint32_t *)kout;      /* the sort keys are dead once the order stands */
+	hipLaunchKernelGGL(compare_long_heads_kernel, cgrid, block, 0, h->stream, stage, (uint32_t)W, (const uint32_t *)src, (const uint32_t *)rid, perm, c, head);
 	HIPCHK(h, hipGetLastError());
 	rc = exclusive_scan_queue(h, head, c, hscan); if (rc) return rc;
-	hipLaunchKernelGGL(compare_long_starts_kernel, cgrid, block, 0, h->stream, (const uint32_t *)head, (const uint64_t *)hscan, c, start);
-	hipLaunchKernelGGL(compare_long_add_kernel<W>, cgrid, block, 0, h->stream, stage, (const uint32_t *)src, (const uint32_t *)rid, (const uint32_t *)perm, (const uint32_t *)head, (const uint64_t *)hscan,
+	rc = group_starts(h, head, hscan, c, start); if (rc) return rc;
+	hipLaunchKernelGGL(compare_long_add_kernel<W>, cgrid, block, 0, h->stream, stage, (const uint32_t *)src, (const uint32_t *)rid, perm, (const uint32_t *)head, (const uint64_t *)hscan,
 	                   (const uint64_t *)start, c, r0, view_of<W>(h->weak, h->ext ? 15u : 3u), view_of<W>(h->sing, 0), h->hkb, out);
 	HIPCHK(h, hipGetLastError());
 	return 0;
@@ -3501,52 +3541,28 @@ template <int W> int compare_long_run(kmr_handle *h, const uint64_t *stage, cons
 template <int W> int compare_reads_t(kmr_handle *h, const ReadsView &all, CompareRec *out) {
 	DevBuf *B = h->cmp_buf;
 	const uint64_t n = all.n_reads;
-	const dim3 block(256);
 	int rc = B[CMP_B_ACC].reserve(h, "compare counters", 256); if (rc) return rc;
-	rc = B[CMP_B_NK].reserve(h, "compare k-mer counts", 4 * n); if (rc) return rc;
-	rc = B[CMP_B_KOFF].reserve(h, "compare k-mer offsets", 8 * (n + 1)); if (rc) return rc;
 	unsigned long long *tot2 = (unsigned long long *)(B[CMP_B_ACC].get<CompareRec>() + 1);
-	unsigned int *most = (unsigned int *)(tot2 + CMP_T_WORDS); uint32_t *err = most + 1;
-	uint32_t *nk = B[CMP_B_NK].get<uint32_t>(); uint64_t *koff = B[CMP_B_KOFF].get<uint64_t>();
 	rc = compare_totals(h, h, tot2); if (rc) return rc;
-	HIPCHK(h, hipMemsetAsync(most, 0, 8, h->stream));
-	hipLaunchKernelGGL(compare_nk_kernel, dim3(grid_for(n)), block, 0, h->stream, all.offsets, n, h->k, nk, most, err);
-	HIPCHK(h, hipGetLastError());
-	rc = exclusive_scan_queue(h, nk, n, koff); if (rc) return rc;
-	/* the call's one fixed-size copy: all k-mers, the most of a read, the error word */
-	uint64_t total = 0; unsigned int hm[2] = {0, 0};
-	HIPCHK(h, hipMemcpyAsync(&total, koff + n, 8, hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(h, hipMemcpyAsync(hm, most, 8, hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(h, hipStreamSynchronize(h->stream));
-	if (hm[1]) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_compare_reads: a read of 2^32 k-mers or more");
+	uint64_t *koff, total; unsigned int most;
+	rc = kmer_slot_plan(h, all.offsets, n, &koff, &total, &most, "kmr_compare_reads: a read of 2^32 k-mers or more"); if (rc) return rc;
 	const uint32_t cap = h->tune.compare_lds_kmers < 0 ? CMP_CAP : (uint32_t)h->tune.compare_lds_kmers;
 	const uint64_t budget = h->tune.compare_stage_kmers ? h->tune.compare_stage_kmers : CMP_STAGE_SLOTS;
-	/* runs of whole reads whose slots fit the budget; a read that alone exceeds it is a run of its own.  Only a batch of more
-	 * k-mers than one run holds has its offsets looked at by the host */
-	std::vector<uint64_t> cut;      /* first read of every run, and n */
-	std::vector<uint64_t> hk;
-	cut.push_back(0);
+	/* runs of whole reads (cut_runs).  Only a batch of more k-mers than one run holds has its offsets looked at by the host */
+	std::vector<uint64_t> hk, cut = {0, n};
 	if (total > budget) {
 		hk.resize(n + 1);
 		HIPCHK(h, hipMemcpy(hk.data(), koff, 8 * (n + 1), hipMemcpyDeviceToHost));
-		uint64_t r0 = 0;
-		for (uint64_t r = 0; r < n; r++) if (hk[r + 1] - hk[r0] > budget && r > r0) { cut.push_back(r); r0 = r; }
+		cut = cut_runs(n, budget, [&](uint64_t r) { return hk[r]; });
 	}
-	cut.push_back(n);
-	DevParams dp = dev_params(h);
-	dp.sub_wstart = dp.sub_wkeys = dp.sub_sstart = dp.sub_skeys = nullptr; dp.sub_wvals = nullptr; dp.sub_sweight = nullptr; dp.sub_wnb = dp.sub_snb = 0;      /* a read's own map subtracts nothing */
+	const DevParams dp = own_reads_params(h, false);      /* a read's own map subtracts nothing */
 	const MapView<W> weak = view_of<W>(h->weak, h->ext ? 15u : 3u), sing = view_of<W>(h->sing, 0);
 	for (size_t i = 0; i + 1 < cut.size(); i++) {
 		const uint64_t r0 = cut[i], m = cut[i + 1] - r0;
 		const uint64_t slots = hk.empty() ? total : hk[r0 + m] - hk[r0];
 		if (slots) {
-			rc = B[CMP_B_STAGE].reserve(h, "compare staging", 8ull * W * slots); if (rc) return rc;
-			uint64_t *stage = B[CMP_B_STAGE].get<uint64_t>();
-			HIPCHK(h, hipMemsetAsync(stage, 0xff, 8ull * W * slots, h->stream));
-			ReadsView rv = reads_slice(all, r0, m);
-			rc = prepare_units(h, rv); if (rc) return rc;
-			CompareOp<W> op; op.stage = stage; op.koff = koff; op.slot_base = hk.empty() ? 0 : hk[r0];
-			rc = launch_extract<W, false>(h, rv, dp, op); if (rc) return rc;
+			CompareOp<W> op; op.koff = koff; op.slot_base = hk.empty() ? 0 : hk[r0];
+			rc = stage_run<W>(h, B[CMP_B_STAGE], "compare staging", all, r0, m, slots, W, dp, op); if (rc) return rc;
 		}
 		const uint64_t *stage = B[CMP_B_STAGE].get<uint64_t>();
 		if (cap) {
@@ -3557,42 +3573,20 @@ template <int W> int compare_reads_t(kmr_handle *h, const ReadsView &all, Compar
 			                   (const unsigned long long *)tot2, out);
 			HIPCHK(h, hipGetLastError());
 		}
-		if (cap == 0 || hm[0] > cap) { rc = compare_long_run<W>(h, stage, koff, r0, m, cap, tot2, out); if (rc) return rc; }
+		if (cap == 0 || most > cap) { rc = compare_long_run<W>(h, stage, koff, r0, m, cap, tot2, out); if (rc) return rc; }
 	}
 	return KMR_OK;
 }
 
 /* the staging of compare_reads_t for the whole batch in one run, for a handle of one key word (see kmr_host.hpp) */
 int tnf_stage(kmr_handle *h, const ReadsView &all, const uint64_t **koff_out, const uint64_t **stage_out, uint64_t *slots) {
-	DevBuf *B = h->cmp_buf;
-	const uint64_t n = all.n_reads;
-	int rc = B[CMP_B_ACC].reserve(h, "compare counters", 256); if (rc) return rc;
-	rc = B[CMP_B_NK].reserve(h, "compare k-mer counts", 4 * std::max<uint64_t>(n, 1)); if (rc) return rc;
-	rc = B[CMP_B_KOFF].reserve(h, "compare k-mer offsets", 8 * (n + 1)); if (rc) return rc;
-	unsigned int *most = (unsigned int *)((unsigned long long *)(B[CMP_B_ACC].get<CompareRec>() + 1) + CMP_T_WORDS); uint32_t *err = most + 1;
-	uint32_t *nk = B[CMP_B_NK].get<uint32_t>(); uint64_t *koff = B[CMP_B_KOFF].get<uint64_t>();
-	HIPCHK(h, hipMemsetAsync(most, 0, 8, h->stream));
-	hipLaunchKernelGGL(compare_nk_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, all.offsets, n, h->k, nk, most, err);
-	HIPCHK(h, hipGetLastError());
-	rc = exclusive_scan_queue(h, nk, n, koff); if (rc) return rc;
-	uint64_t total = 0; unsigned int hm[2] = {0, 0};
-	HIPCHK(h, hipMemcpyAsync(&total, koff + n, 8, hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(h, hipMemcpyAsync(hm, most, 8, hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(h, hipStreamSynchronize(h->stream));
-	if (hm[1]) return fail(h, KMR_ERR_UNSUPPORTED, "a sequence of 2^32 k-mers or more");
+	uint64_t *koff, total; unsigned int most;
+	int rc = kmer_slot_plan(h, all.offsets, all.n_reads, &koff, &total, &most, "a sequence of 2^32 k-mers or more"); if (rc) return rc;
 	*koff_out = koff; *slots = total; *stage_out = nullptr;
 	if (total == 0) return KMR_OK;
-	rc = B[CMP_B_STAGE].reserve(h, "compare staging", 8 * total); if (rc) return rc;
-	uint64_t *stage = B[CMP_B_STAGE].get<uint64_t>();
-	HIPCHK(h, hipMemsetAsync(stage, 0xff, 8 * total, h->stream));
-	DevParams dp = dev_params(h);
-	dp.sub_wstart = dp.sub_wkeys = dp.sub_sstart = dp.sub_skeys = nullptr; dp.sub_wvals = nullptr; dp.sub_sweight = nullptr; dp.sub_wnb = dp.sub_snb = 0;
-	dp.subsample = 1; dp.world = 1; dp.rank = 0; dp.num_parts = 1; dp.part_idx = 0;      /* every k-mer of the batch is this call's */
-	ReadsView rv = all;
-	rc = prepare_units(h, rv); if (rc) return rc;
-	CompareOp<1> op; op.stage = stage; op.koff = koff; op.slot_base = 0;
-	rc = launch_extract<1, false>(h, rv, dp, op); if (rc) return rc;
-	*stage_out = stage;
+	CompareOp<1> op; op.koff = koff; op.slot_base = 0;
+	rc = stage_run<1>(h, h->cmp_buf[CMP_B_STAGE], "compare staging", all, 0, all.n_reads, total, 1, own_reads_params(h, true), op); if (rc) return rc;
+	*stage_out = h->cmp_buf[CMP_B_STAGE].get<uint64_t>();
 	return KMR_OK;
 }
 
@@ -3618,33 +3612,26 @@ template <int W> int match_create_t(kmr_handle *h, kmr_match *m, const uint8_t *
 	if (E >= 0xffffffffull) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_match_create: 2^32 - 1 edge k-mers or more");
 	m->n_contigs = nc; m->n_edge_kmers = E; m->n_distinct_keys = m->n_keys_in_spectrum = 0;
 	uint64_t n_lists = 0;      /* (key, contig) pairs of the kept keys */
-	DevBuf b_keys, b_contig, b_perm, b_perm2, b_kin, b_kout, b_sort, b_flags, b_scans;
-	uint64_t *keys = nullptr, *scans = nullptr; uint32_t *contig = nullptr, *perm = nullptr, *perm2 = nullptr, *flags = nullptr;
-	unsigned long long *kin = nullptr, *kout = nullptr;
+	DevBuf b_keys, b_contig, b_order, b_flags, b_scans; SortBufs sort;
+	uint64_t *keys = nullptr, *scans = nullptr; uint32_t *contig = nullptr, *order = nullptr, *flags = nullptr; const uint32_t *perm = nullptr;
 	if (E) {
-		HIPCHK(h, alloc_n(b_keys, &keys, E * W)); HIPCHK(h, alloc_n(b_contig, &contig, E)); HIPCHK(h, alloc_n(b_perm, &perm, E)); HIPCHK(h, alloc_n(b_perm2, &perm2, E));
-		HIPCHK(h, alloc_n(b_kin, &kin, E)); HIPCHK(h, alloc_n(b_kout, &kout, E)); HIPCHK(h, alloc_n(b_flags, &flags, 3 * E)); HIPCHK(h, alloc_n(b_scans, &scans, 3 * (E + 1)));
-		size_t sort_bytes = 0;
-		if (kmr::sort_pairs_u64_u32(nullptr, &sort_bytes, nullptr, nullptr, nullptr, nullptr, E, h->stream) != 0) return fail(h, KMR_ERR_HIP, "kmr_match_create: radix sort (size query)");
-		HIPCHK(h, b_sort.alloc(std::max<size_t>(sort_bytes, 256)));
+		HIPCHK(h, alloc_n(b_keys, &keys, E * W)); HIPCHK(h, alloc_n(b_contig, &contig, E)); HIPCHK(h, alloc_n(b_order, &order, E));
+		HIPCHK(h, alloc_n(b_flags, &flags, 3 * E)); HIPCHK(h, alloc_n(b_scans, &scans, 3 * (E + 1)));
 		const dim3 egrid(grid_for(E));
-		hipLaunchKernelGGL(match_edge_keys_kernel<W>, egrid, block, 0, h->stream, bases, offsets, nc, h->k, M, (const uint64_t *)eoff, E, keys, contig, perm);
+		hipLaunchKernelGGL(match_edge_keys_kernel<W>, egrid, block, 0, h->stream, bases, offsets, nc, h->k, M, (const uint64_t *)eoff, E, keys, contig, order);
 		HIPCHK(h, hipGetLastError());
 		/* least significant first: the contig, then the key words from the last to the first; the sort is stable */
-		for (int pass = 0; pass <= W; pass++) {
-			hipLaunchKernelGGL(match_gather_kernel, egrid, block, 0, h->stream, (const uint64_t *)keys, (const uint32_t *)contig, (uint32_t)W, (uint32_t)(W - pass), (const uint32_t *)perm, E, kin);
-			HIPCHK(h, hipGetLastError());
-			size_t sb = b_sort.cap();
-			if (kmr::sort_pairs_u64_u32(b_sort.get(), &sb, kin, kout, perm, perm2, E, h->stream) != 0) return fail(h, KMR_ERR_HIP, "kmr_match_create: radix sort");
-			std::swap(perm, perm2);
-		}
+		SortColumn cols[W + 1];
+		cols[0] = SortColumn{nullptr, 0, nullptr, contig};
+		for (int w = 0; w < W; w++) cols[1 + w] = SortColumn{keys + (W - 1 - w), (uint64_t)W, nullptr, nullptr};
+		int rc = sort_by_columns(h, sort, cols, W + 1, order, E, "kmr_match_create", &perm, nullptr); if (rc) return rc;
 		MapView<W> weak = view_of<W>(h->weak, h->ext ? 15u : 3u), sing = view_of<W>(h->sing, 0);
 		if (!h->has_singletons) sing.nb = 0;
 		uint32_t *khead = flags, *kkept = flags + E, *phead = flags + 2 * E;
 		uint64_t *hscan = scans, *kscan = scans + (E + 1), *pscan = scans + 2 * (E + 1);
 		hipLaunchKernelGGL(match_flags_kernel<W>, egrid, block, 0, h->stream, (const uint64_t *)keys, (const uint32_t *)contig, (const uint32_t *)perm, E, weak, sing, h->hkb, khead, kkept, phead);
 		HIPCHK(h, hipGetLastError());
-		int rc = exclusive_scan_queue(h, khead, E, hscan); if (rc) return rc;
+		rc = exclusive_scan_queue(h, khead, E, hscan); if (rc) return rc;
 		rc = exclusive_scan_queue(h, kkept, E, kscan); if (rc) return rc;
 		rc = exclusive_scan_queue(h, phead, E, pscan); if (rc) return rc;
 		HIPCHK(h, hipMemcpyAsync(&m->n_distinct_keys, hscan + E, 8, hipMemcpyDeviceToHost, h->stream));
@@ -3675,8 +3662,7 @@ template <int W> int match_add_t(kmr_handle *h, kmr_match *m, const ReadsView &a
 		HIPCHK(h, m->hit_key.alloc(std::max<size_t>(8 * cap, 256))); HIPCHK(h, m->hit_mate.alloc(std::max<size_t>(8 * cap, 256)));
 		m->hit_cap = cap;
 	}
-	DevParams dp = dev_params(h);
-	dp.sub_wstart = dp.sub_wkeys = dp.sub_sstart = dp.sub_skeys = nullptr; dp.sub_wvals = nullptr; dp.sub_sweight = nullptr; dp.sub_wnb = dp.sub_snb = 0;      /* the spectrum's own reads: nothing is subtracted */
+	const DevParams dp = own_reads_params(h, false);      /* the spectrum's own reads: nothing is subtracted */
 	ReadsView rv = all;
 	int rc = prepare_units(h, rv); if (rc) return rc;
 	for (int attempt = 1;; attempt++) {
@@ -3707,6 +3693,54 @@ template <int W> int match_add_t(kmr_handle *h, kmr_match *m, const ReadsView &a
 }
 
 /* ---- ContigExtender (kmr_extend.hpp): everything of kmr_extend_contigs* behind the argument checks (kmr_stages.hip) ---- */
+struct ExtendBufs { DevBuf stage, sgrp, order, flags, scans, cnt, val, wkeys, wcnt, wval, skeys, bounds, rec; SortBufs sort; };      /* what extend_t keeps across the runs of a call, grow-only */
+
+/* The pool spectra of one run: items [i0, i0 + ni) of the gathered batch, S > 0 slots from slot0, contigs [A.c0, A.c0 + A.m).  Stage,
+ * sort, reduce: A's tables set, A.bounds (zero before) filled.  Waits once, for the sizes of the tables */
+template <int W> int extend_run_spectra(kmr_handle *h, ExtendBufs &B, const ReadsView &all, const DevParams &dp, const uint64_t *koff, const uint32_t *grp, uint64_t i0, uint64_t ni,
+                                        uint64_t slot0, uint64_t S, EventTimer<5> &tr, ExtendArgs &A) {
+	const dim3 block(256), sgrid(grid_for(S));
+	ExtendOp<W> op; op.koff = koff; op.slot_base = slot0;
+	int rc = stage_run<W>(h, B.stage, "extend staging", all, i0, ni, S, W + 1, dp, op); if (rc) return rc;
+	const uint64_t *stage = B.stage.get<uint64_t>();
+	tr.mark(1, h->stream);
+	rc = B.sgrp.reserve(h, "extend groups", 4 * S); if (rc) return rc;
+	rc = B.order.reserve(h, "extend sort order", 4 * S); if (rc) return rc;
+	rc = B.flags.reserve(h, "extend flags", 8 * S); if (rc) return rc;
+	rc = B.scans.reserve(h, "extend scans", 16 * (S + 1)); if (rc) return rc;
+	rc = B.cnt.reserve(h, "extend counts", 4 * S); if (rc) return rc;
+	rc = B.val.reserve(h, "extend weights", 4 * S); if (rc) return rc;
+	uint32_t *sgrp = B.sgrp.get<uint32_t>(), *wflag = B.flags.get<uint32_t>(), *sflag = wflag + S, *cnt = B.cnt.get<uint32_t>(); float *val = B.val.get<float>();
+	uint64_t *wscan = B.scans.get<uint64_t>(), *sscan = wscan + (S + 1);
+	hipLaunchKernelGGL(extend_fill_kernel, sgrid, block, 0, h->stream, koff, i0, ni, grp, S, sgrp, B.order.get<uint32_t>());
+	HIPCHK(h, hipGetLastError());
+	/* least significant first: the key words from the last to the first, then (contig, source); the sort is stable */
+	SortColumn cols[W + 1];
+	for (int w = 0; w < W; w++) cols[w] = SortColumn{stage + (W - 1 - w), (uint64_t)W + 1, nullptr, nullptr};
+	cols[W] = SortColumn{nullptr, 0, nullptr, sgrp};
+	const uint32_t *perm; unsigned long long *sorted_grp;      /* the last pass's keys */
+	rc = sort_by_columns(h, B.sort, cols, W + 1, B.order.get<uint32_t>(), S, "kmr_extend_contigs", &perm, &sorted_grp); if (rc) return rc;
+	tr.mark(2, h->stream);
+	hipLaunchKernelGGL(extend_reduce_kernel, sgrid, block, 0, h->stream, stage, (uint32_t)W, (const uint32_t *)sgrp, perm, S, h->cfg.separate_singletons ? 1u : 0u, wflag, sflag, cnt, val);
+	HIPCHK(h, hipGetLastError());
+	rc = exclusive_scan_queue(h, wflag, S, wscan); if (rc) return rc;
+	rc = exclusive_scan_queue(h, sflag, S, sscan); if (rc) return rc;
+	uint64_t nw = 0, ns = 0;
+	HIPCHK(h, hipMemcpyAsync(&nw, wscan + S, 8, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipMemcpyAsync(&ns, sscan + S, 8, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipStreamSynchronize(h->stream));
+	rc = B.wkeys.reserve(h, "extend weak keys", std::max<size_t>(8ull * W * nw, 256)); if (rc) return rc;
+	rc = B.wcnt.reserve(h, "extend weak counts", std::max<size_t>(4 * nw, 256)); if (rc) return rc;
+	rc = B.wval.reserve(h, "extend weak weights", std::max<size_t>(4 * nw, 256)); if (rc) return rc;
+	rc = B.skeys.reserve(h, "extend solid keys", std::max<size_t>(8ull * W * ns, 256)); if (rc) return rc;
+	A.wkeys = B.wkeys.get<uint64_t>(); A.wcnt = B.wcnt.get<uint32_t>(); A.wval = B.wval.get<float>(); A.skeys = B.skeys.get<uint64_t>();
+	hipLaunchKernelGGL(extend_compact_kernel, sgrid, block, 0, h->stream, stage, (uint32_t)W, perm, S, (const uint32_t *)wflag, (const uint32_t *)sflag, (const uint64_t *)wscan,
+	                   (const uint64_t *)sscan, (const uint32_t *)cnt, (const float *)val, B.wkeys.get<uint64_t>(), B.wcnt.get<uint32_t>(), B.wval.get<float>(), B.skeys.get<uint64_t>());
+	hipLaunchKernelGGL(extend_bounds_kernel, dim3(grid_for(A.m)), block, 0, h->stream, (const unsigned long long *)sorted_grp, S, (const uint64_t *)wscan, (const uint64_t *)sscan, A.c0, A.m, (uint64_t *)A.bounds);
+	HIPCHK(h, hipGetLastError());
+	return 0;
+}
+
 template <int W> int extend_t(kmr_handle *h, const kmr_reads *contigs, const kmr_reads *reads, const uint64_t *po, const uint64_t *pr, const uint8_t *active,
                               const kmr_extend_config *cfg, kmr_extend *out) {
 	const dim3 block(256);
@@ -3735,7 +3769,7 @@ template <int W> int extend_t(kmr_handle *h, const kmr_reads *contigs, const kmr
 	/* 1: the offsets, then the items */
 	DevBuf b_small, b_len, b_grp, b_goff, b_nk, b_koff;
 	uint32_t *err; HIPCHK(h, alloc_n(b_small, &err, (size_t)64));
-	unsigned int *most = err + 2; unsigned long long *info = (unsigned long long *)(err + 8);
+	unsigned long long *info = (unsigned long long *)(err + 8);      /* (err + 2: kmer_slots_queue's two words) */
 	HIPCHK(h, hipMemsetAsync(err, 0, 256, h->stream));
 	hipLaunchKernelGGL(extend_check_offsets_kernel, dim3(grid_for(nc + 1)), block, 0, h->stream, po, nc, err);
 	HIPCHK(h, hipGetLastError());
@@ -3771,33 +3805,23 @@ template <int W> int extend_t(kmr_handle *h, const kmr_reads *contigs, const kmr
 		                   reads->quals.get<uint8_t>(), reads->offsets.get<uint64_t>(), cbases, coff, gb, gq);
 		HIPCHK(h, hipGetLastError());
 	}
-	hipLaunchKernelGGL(compare_nk_kernel, dim3(grid_for(n_items)), block, 0, h->stream, (const uint64_t *)goff, n_items, h->k, nk, most, err + 3);
-	HIPCHK(h, hipGetLastError());
-	rc = exclusive_scan_queue(h, nk, n_items, koff); if (rc) return rc;
+	rc = kmer_slots_queue(h, goff, n_items, nk, koff, err + 2); if (rc) return rc;      /* (an item of 2^32 k-mers was refused above) */
 	tg.mark(1, h->stream);
 	std::vector<uint64_t> hk(n_items + 1);
 	HIPCHK(h, hipMemcpyAsync(hk.data(), koff, 8 * (n_items + 1), hipMemcpyDeviceToHost, h->stream));
 	HIPCHK(h, hipStreamSynchronize(h->stream));
 	h->last_extend_ms[0] = tg.ms(0, 1);
-	/* 3: runs of whole contigs whose slots fit the budget; a contig that alone exceeds it is a run of its own */
+	/* 3: runs of whole contigs, each with its pool (cut_runs); contig c's items begin at hpo[c] + c */
 	const uint64_t budget = h->tune.extend_stage_kmers ? h->tune.extend_stage_kmers : EXT_STAGE_SLOTS;
-	std::vector<uint64_t> cut;
-	cut.push_back(0);
-	{
-		uint64_t c0 = 0;
-		for (uint64_t c = 0; c < nc; c++) if (hk[hpo[c + 1] + c + 1] - hk[hpo[c0] + c0] > budget && c > c0) { cut.push_back(c); c0 = c; }
-	}
-	cut.push_back(nc);
+	const std::vector<uint64_t> cut = cut_runs(nc, budget, [&](uint64_t c) { return hk[hpo[c] + c]; });
 	/* the sequences with max_extend free bases on either side, the recorded keys */
-	DevBuf b_seq, b_rec;
+	DevBuf b_seq;
 	HIPCHK(h, b_seq.alloc(std::max<uint64_t>(contigs->total + 2ull * maxx * nc, 256)));
 	const size_t rec_wave = (size_t)2 * maxx * W * 8;
 	const bool rec_lds = rec_wave <= EXT_LDS_WAVE_BYTES;
-	DevParams dp = dev_params(h);
-	dp.sub_wstart = dp.sub_wkeys = dp.sub_sstart = dp.sub_skeys = nullptr; dp.sub_wvals = nullptr; dp.sub_sweight = nullptr; dp.sub_wnb = dp.sub_snb = 0;
-	dp.subsample = 1; dp.world = 1; dp.rank = 0; dp.num_parts = 1; dp.part_idx = 0;      /* a pool's spectrum is whole */
+	const DevParams dp = own_reads_params(h, true);      /* a pool's spectrum is whole */
 	const ReadsView all = reads_view(gb, gq, goff, n_items);
-	DevBuf b_stage, b_sgrp, b_perm, b_perm2, b_kin, b_kout, b_sort, b_flags, b_scans, b_cnt, b_val, b_wkeys, b_wcnt, b_wval, b_skeys, b_bounds;
+	ExtendBufs B;
 	for (size_t ri = 0; ri + 1 < cut.size(); ri++) {
 		const uint64_t c0 = cut[ri], m = cut[ri + 1] - c0;
 		const uint64_t i0 = hpo[c0] + c0, i1 = hpo[c0 + m] + c0 + m, S = hk[i1] - hk[i0];
@@ -3805,76 +3829,20 @@ template <int W> int extend_t(kmr_handle *h, const kmr_reads *contigs, const kmr
 		EventTimer<5> tr(h->tune.extend_timing);
 		tr.mark(0, h->stream);
 		uint64_t *bounds;
-		HIPCHK(h, alloc_n(b_bounds, &bounds, 4 * m));
+		HIPCHK(h, alloc_n(B.bounds, &bounds, 4 * m));
 		HIPCHK(h, hipMemsetAsync(bounds, 0, 32 * m, h->stream));
-		uint64_t *wkeys = nullptr, *skeys = nullptr; uint32_t *wcnt = nullptr; float *wval = nullptr;
-		if (S) {
-			rc = b_stage.reserve(h, "extend staging", 8ull * (W + 1) * S); if (rc) return rc;
-			uint64_t *stage = b_stage.get<uint64_t>();
-			HIPCHK(h, hipMemsetAsync(stage, 0xff, 8ull * (W + 1) * S, h->stream));
-			ReadsView rv = reads_slice(all, i0, i1 - i0);
-			rc = prepare_units(h, rv); if (rc) return rc;
-			ExtendOp<W> op; op.stage = stage; op.koff = koff; op.slot_base = hk[i0];
-			rc = launch_extract<W, false>(h, rv, dp, op); if (rc) return rc;
-			tr.mark(1, h->stream);
-			rc = b_sgrp.reserve(h, "extend groups", 4 * S); if (rc) return rc;
-			rc = b_perm.reserve(h, "extend sort order", 4 * S); if (rc) return rc;
-			rc = b_perm2.reserve(h, "extend sort order", 4 * S); if (rc) return rc;
-			rc = b_kin.reserve(h, "extend sort keys", 8 * S); if (rc) return rc;
-			rc = b_kout.reserve(h, "extend sort keys", 8 * S); if (rc) return rc;
-			rc = b_flags.reserve(h, "extend flags", 8 * S); if (rc) return rc;
-			rc = b_scans.reserve(h, "extend scans", 16 * (S + 1)); if (rc) return rc;
-			rc = b_cnt.reserve(h, "extend counts", 4 * S); if (rc) return rc;
-			rc = b_val.reserve(h, "extend weights", 4 * S); if (rc) return rc;
-			size_t sort_bytes = 0;
-			if (kmr::sort_pairs_u64_u32(nullptr, &sort_bytes, nullptr, nullptr, nullptr, nullptr, S, h->stream) != 0) return fail(h, KMR_ERR_HIP, "kmr_extend_contigs: radix sort (size query)");
-			rc = b_sort.reserve(h, "extend sort scratch", std::max<size_t>(sort_bytes, 256)); if (rc) return rc;
-			uint32_t *sgrp = b_sgrp.get<uint32_t>(), *perm = b_perm.get<uint32_t>(), *perm2 = b_perm2.get<uint32_t>();
-			unsigned long long *kin = b_kin.get<unsigned long long>(), *kout = b_kout.get<unsigned long long>();
-			uint32_t *wflag = b_flags.get<uint32_t>(), *sflag = wflag + S, *cnt = b_cnt.get<uint32_t>(); float *val = b_val.get<float>();
-			uint64_t *wscan = b_scans.get<uint64_t>(), *sscan = wscan + (S + 1);
-			const dim3 sgrid(grid_for(S));
-			hipLaunchKernelGGL(extend_fill_kernel, sgrid, block, 0, h->stream, (const uint64_t *)koff, i0, i1 - i0, (const uint32_t *)grp, S, sgrp, perm);
-			HIPCHK(h, hipGetLastError());
-			/* least significant first: the key words from the last to the first, then (contig, source); the sort is stable */
-			for (int pass = 0; pass <= W; pass++) {
-				hipLaunchKernelGGL(extend_sortkey_kernel, sgrid, block, 0, h->stream, (const uint64_t *)stage, (uint32_t)W, (uint32_t)(pass == W ? W : W - 1 - pass), (const uint32_t *)sgrp,
-				                   (const uint32_t *)perm, S, kin);
-				HIPCHK(h, hipGetLastError());
-				size_t sb = b_sort.cap();
-				if (kmr::sort_pairs_u64_u32(b_sort.get(), &sb, kin, kout, perm, perm2, S, h->stream) != 0) return fail(h, KMR_ERR_HIP, "kmr_extend_contigs: radix sort");
-				std::swap(perm, perm2);
-			}
-			tr.mark(2, h->stream);
-			hipLaunchKernelGGL(extend_reduce_kernel, sgrid, block, 0, h->stream, (const uint64_t *)stage, (uint32_t)W, (const uint32_t *)sgrp, (const uint32_t *)perm, S,
-			                   h->cfg.separate_singletons ? 1u : 0u, wflag, sflag, cnt, val);
-			HIPCHK(h, hipGetLastError());
-			rc = exclusive_scan_queue(h, wflag, S, wscan); if (rc) return rc;
-			rc = exclusive_scan_queue(h, sflag, S, sscan); if (rc) return rc;
-			uint64_t nw = 0, ns = 0;
-			HIPCHK(h, hipMemcpyAsync(&nw, wscan + S, 8, hipMemcpyDeviceToHost, h->stream));
-			HIPCHK(h, hipMemcpyAsync(&ns, sscan + S, 8, hipMemcpyDeviceToHost, h->stream));
-			HIPCHK(h, hipStreamSynchronize(h->stream));
-			rc = b_wkeys.reserve(h, "extend weak keys", std::max<size_t>(8ull * W * nw, 256)); if (rc) return rc;
-			rc = b_wcnt.reserve(h, "extend weak counts", std::max<size_t>(4 * nw, 256)); if (rc) return rc;
-			rc = b_wval.reserve(h, "extend weak weights", std::max<size_t>(4 * nw, 256)); if (rc) return rc;
-			rc = b_skeys.reserve(h, "extend solid keys", std::max<size_t>(8ull * W * ns, 256)); if (rc) return rc;
-			wkeys = b_wkeys.get<uint64_t>(); wcnt = b_wcnt.get<uint32_t>(); wval = b_wval.get<float>(); skeys = b_skeys.get<uint64_t>();
-			hipLaunchKernelGGL(extend_compact_kernel, sgrid, block, 0, h->stream, (const uint64_t *)stage, (uint32_t)W, (const uint32_t *)perm, S, (const uint32_t *)wflag, (const uint32_t *)sflag,
-			                   (const uint64_t *)wscan, (const uint64_t *)sscan, (const uint32_t *)cnt, (const float *)val, wkeys, wcnt, wval, skeys);
-			hipLaunchKernelGGL(extend_bounds_kernel, dim3(grid_for(m)), block, 0, h->stream, (const unsigned long long *)kout, S, (const uint64_t *)wscan, (const uint64_t *)sscan, c0, m, bounds);
-			HIPCHK(h, hipGetLastError());
-		} else { tr.mark(1, h->stream); tr.mark(2, h->stream); }
-		tr.mark(3, h->stream);
 		ExtendArgs A;
 		A.cbases = cbases; A.coff = coff; A.active = active; A.c0 = c0; A.m = m;
-		A.wkeys = wkeys; A.wcnt = wcnt; A.wval = wval; A.skeys = skeys; A.bounds = bounds;
+		A.wkeys = A.skeys = nullptr; A.wcnt = nullptr; A.wval = nullptr; A.bounds = bounds;
+		if (S) { rc = extend_run_spectra<W>(h, B, all, dp, koff, grp, i0, i1 - i0, hk[i0], S, tr, A); if (rc) return rc; }
+		else { tr.mark(1, h->stream); tr.mark(2, h->stream); }
+		tr.mark(3, h->stream);
 		A.k = h->k; A.max_extend = maxx; A.use_weights = cfg->use_weights ? 1u : 0u;
 		A.min_consensus = cfg->minimum_consensus / 100; A.min_coverage = cfg->minimum_coverage; A.max_delta = cfg->maximum_delta_ratio;
 		A.seq = b_seq.get<uint8_t>(); A.left = left; A.right = right; A.reason = reason; A.vals = vals;
 		const uint64_t blocks = std::min<uint64_t>((m + EXT_WAVES - 1) / EXT_WAVES, (uint64_t)num_cus(h) * 8);
 		A.rec_global = nullptr;
-		if (!rec_lds) { rc = b_rec.reserve(h, "extend recorded keys", std::max<size_t>(rec_wave * EXT_WAVES * blocks, 256)); if (rc) return rc; A.rec_global = b_rec.get<uint64_t>(); }
+		if (!rec_lds) { rc = B.rec.reserve(h, "extend recorded keys", std::max<size_t>(rec_wave * EXT_WAVES * blocks, 256)); if (rc) return rc; A.rec_global = B.rec.get<uint64_t>(); }
 		hipLaunchKernelGGL(extend_contigs_kernel<W>, dim3((unsigned)blocks), dim3(EXT_WAVES * 64), rec_lds ? rec_wave * EXT_WAVES : 0, h->stream, A);
 		HIPCHK(h, hipGetLastError());
 		tr.mark(4, h->stream);

@@ -16,8 +16,8 @@
  *                                       distinct keys and multiplicities by comparing every key with every other, one lookup per
  *                                       distinct key, the record reduced across the wavefront; no atomics, nothing but the
  *                                       record leaves the CU
- *               compare_long_*_kernel   longer reads (contigs, genomes): (read, key) ordered by the library's stable radix
- *                                       sort, one pass per key word and one for the read, heads flagged, one lookup per head
+ *               compare_long_*_kernel   longer reads (contigs, genomes): (read, key) ordered by sort_by_columns (kmr_sort.hip),
+ *                                       one pass per key word and one for the read, heads flagged, one lookup per head
  *                                       added into the read's record (one atomic per wavefront and field while a wavefront's
  *                                       heads belong to one read)
  *
@@ -133,13 +133,6 @@ __global__ void compare_long_fill_kernel(const uint64_t *koff, uint64_t r0, uint
 		perm[j] = (uint32_t)j;
 	}
 }
-/* sort keys of one pass: key word w of the slots in their current order, or (w == words) their reads */
-__global__ void compare_long_gather_kernel(const uint64_t *stage, uint32_t words, uint32_t w, const uint32_t *src, const uint32_t *rid, const uint32_t *perm, uint64_t c, unsigned long long *kin) {
-	for (uint64_t j = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; j < c; j += (uint64_t)gridDim.x * blockDim.x) {
-		const uint32_t p = perm[j];
-		kin[j] = w == words ? (unsigned long long)rid[p] : stage[(uint64_t)src[p] * words + w];
-	}
-}
 /* head[j]: the slot opens a run of one (read, key) */
 __global__ void compare_long_heads_kernel(const uint64_t *stage, uint32_t words, const uint32_t *src, const uint32_t *rid, const uint32_t *perm, uint64_t c, uint32_t *head) {
 	for (uint64_t j = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; j < c; j += (uint64_t)gridDim.x * blockDim.x) {
@@ -150,13 +143,6 @@ __global__ void compare_long_heads_kernel(const uint64_t *stage, uint32_t words,
 			for (uint32_t w = 0; w < words && !h; w++) h = stage[(uint64_t)src[p] * words + w] != stage[(uint64_t)src[q] * words + w];
 		}
 		head[j] = h ? 1u : 0u;
-	}
-}
-/* start[g]: the slot of head g; start[heads] = c */
-__global__ void compare_long_starts_kernel(const uint32_t *head, const uint64_t *hscan, uint64_t c, uint64_t *start) {
-	for (uint64_t j = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; j < c; j += (uint64_t)gridDim.x * blockDim.x) {
-		if (head[j]) start[hscan[j]] = j;
-		if (j + 1 == c) start[hscan[c]] = c;
 	}
 }
 #endif

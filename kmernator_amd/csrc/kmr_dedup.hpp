@@ -8,11 +8,11 @@
  *                           than start_offset + L up to the first X, unpaired for this pass), the 2-bit key of the window(s), its
  *                           reverse complement on the key words, the canonical choice of dedup_mode 2 and the flip flag
  *   (scan of the candidate flags, dedup_compact_kernel: candidate -> its position in the pair list)
- *   dedup_gather_kernel +   one stable radix sort (kmr_sort.hip) per key word from the last to the first, the payload being the
- *   sort                    pair position, which gathers the next word: members of one key end up adjacent and in ascending
+ *   sort_by_columns         (kmr_sort.hip) one stable radix sort per key word from the last to the first, the payload being the
+ *                           pair position, which gathers the next word: members of one key end up adjacent and in ascending
  *                           pair position (the instance order of a serial build, src/KmerTrackingData.h:810-841)
  *   dedup_heads_kernel      where the key changes
- *   (scan) dedup_starts_kernel, dedup_keep_kernel, (scan) dedup_kept_kernel: group sizes, the groups of 2 and more, each with the
+ *   (scan) group_starts, dedup_keep_kernel, (scan) dedup_kept_kernel: group sizes, the groups of 2 and more, each with the
  *                           pair position of its first member (the smallest of the group, the sort being stable)
  *   (sort of (first member, group): the order the consensus reads come out in)
  *   dedup_size_kernel       per (group, side): the longest member, the exact length of the name "C<m>-<name of the first member>"
@@ -206,12 +206,6 @@ void dedup_compact_kernel(const uint32_t *cand, const uint64_t *cand_scan, uint6
 		if (cand[i]) perm[cand_scan[i]] = (uint32_t)i;
 }
 
-/* the next sort's keys: one plane of the key words in the order the payload has now */
-__global__ __launch_bounds__(256)
-void dedup_gather_kernel(const unsigned long long *plane, const uint32_t *perm, uint64_t c, unsigned long long *out) {
-	for (uint64_t j = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; j < c; j += (uint64_t)gridDim.x * blockDim.x) out[j] = plane[perm[j]];
-}
-
 /* perm: the c candidates sorted by key, ascending pair position inside a key; head[j] = 1 where a new key begins */
 __global__ __launch_bounds__(256)
 void dedup_heads_kernel(const unsigned long long *keys, uint64_t np, uint32_t W, const uint32_t *perm, uint64_t c, uint32_t *head) {
@@ -222,15 +216,8 @@ void dedup_heads_kernel(const unsigned long long *keys, uint64_t np, uint32_t W,
 	}
 }
 
-/* head_scan: exclusive scan of head, so head_scan[c] = the number of groups G; start[g] = sorted index of group g's first member, start[G] = c */
-__global__ __launch_bounds__(256)
-void dedup_starts_kernel(const uint32_t *head, const uint64_t *head_scan, uint64_t c, uint64_t *start) {
-	for (uint64_t j = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; j < c; j += (uint64_t)gridDim.x * blockDim.x)
-		if (head[j]) start[head_scan[j]] = j;
-	if (blockIdx.x == 0 && threadIdx.x == 0) start[head_scan[c]] = c;
-}
-
-/* keep[g] = group g has at least two members (cutoffThreshold 2); 0 behind the last group */
+/* head_scan: exclusive scan of head, so head_scan[c] = the number of groups G; start (group_starts): start[g] = sorted index of group g's
+ * first member, start[G] = c.  keep[g] = group g has at least two members (cutoffThreshold 2); 0 behind the last group */
 __global__ __launch_bounds__(256)
 void dedup_keep_kernel(const uint64_t *head_scan, const uint64_t *start, uint64_t c, uint32_t *keep) {
 	const uint64_t G = head_scan[c];

@@ -12,9 +12,9 @@
  *  Extract  ExtendOp                 extract_kernel's Op: the canonical key and the f32 weight of every k-mer that passes the
  *                                    build's weight test (TrackingData::isDiscard) to slot koff[item] + position of a staging array
  *                                    of W + 1 words a slot that was filled with ones -- CompareOp's staging plus a weight word
- *  Order    extend_fill_kernel, extend_sortkey_kernel and the library's stable radix sort: (contig, source, key words), one pass
- *                                    per key word, the last word first; stability keeps a key's sightings in arrival order (pool
- *                                    order, then position)
+ *  Order    extend_fill_kernel and sort_by_columns (kmr_sort.hip): (contig, source, key words), one stable pass per key word,
+ *                                    the last word first, then one for (contig, source); stability keeps a key's sightings in
+ *                                    arrival order (pool order, then position)
  *  Reduce   extend_reduce_kernel     one lane per (contig, source, key) run: count and weightedCount as the serial build makes them
  *                                    (src/KmerSpectrum.h:1590-1640, src/KmerTrackingData.h:427-448, :641-659): one f32 addition
  *                                    after the other, the first sighting quantised through the singleton map's byte where that
@@ -151,13 +151,6 @@ __global__ void extend_fill_kernel(const uint64_t *koff, uint64_t i0, uint64_t m
 		while (hi - lo > 1) { const uint64_t mid = (lo + hi) >> 1; if (koff[i0 + mid] - base <= j) lo = mid; else hi = mid; }
 		sgrp[j] = grp[i0 + lo];
 		perm[j] = (uint32_t)j;
-	}
-}
-/* sort keys of one pass: key word w of the slots in their current order, or (w == words) their groups */
-__global__ void extend_sortkey_kernel(const uint64_t *stage, uint32_t words, uint32_t w, const uint32_t *sgrp, const uint32_t *perm, uint64_t S, unsigned long long *kin) {
-	for (uint64_t j = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; j < S; j += (uint64_t)gridDim.x * blockDim.x) {
-		const uint32_t p = perm[j];
-		kin[j] = w == words ? (unsigned long long)sgrp[p] : stage[(uint64_t)p * (words + 1) + w];
 	}
 }
 __device__ __forceinline__ bool ext_same_run(const uint64_t *stage, uint32_t words, const uint32_t *sgrp, uint32_t p, uint32_t q) {

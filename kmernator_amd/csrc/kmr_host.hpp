@@ -1,8 +1,9 @@
 /*
  * kmr_host.hpp -- what the host side of the library shares between its translation units (kmr_api.hip: the spectrum; kmr_stages.hip:
  * the read stages): device memory (dev_malloc, DevBuf, the live-block counter), the handle and the result objects, error reporting
- * (HIPCHK, fail), launch and dispatch helpers, and the few spectrum-side functions the stages call.  Internal: nothing here is an
- * exported symbol of the library (namespace kmr_host and the structs are of hidden visibility), and no kernel is defined here.
+ * (HIPCHK, fail), launch and dispatch helpers, the few spectrum-side functions the stages call, and the sorts of kmr_sort.hip.
+ * Internal: nothing here is an exported symbol of the library (namespace kmr_host and the structs are of hidden visibility), and no
+ * kernel is defined here.
  */
 #ifndef KMR_HOST_HPP_
 #define KMR_HOST_HPP_
@@ -84,6 +85,9 @@ private:
 	size_t cap_ = 0;
 };
 
+/* scratch of kmr_sort.hip's sorts (declared below), grow-only: a pass's keys before and after, the second order array, rocPRIM's storage */
+struct SortBufs { DevBuf kin, kout, perm2, tmp; };
+
 struct DevMap {                      /* a finalized map resident in HBM */
 	uint64_t nb = 0, n = 0;
 	DevBuf start;                    /* [nb+1] */
@@ -126,7 +130,8 @@ struct HandleMem {                   /* ... by kmr_destroy */
 	struct Early { bool active = false; uint64_t hi = 0; uint32_t min_depth = 0; DevBuf ue, cursor, fc, err; } early;      /* err: the early pass's own error word, read by kmr_finalize alone */
 	DevBuf dedup_tab;                /* kmr_dedup_fragments*: the probability and quality-step tables (DedupTables), made by the first call */
 	DevBuf xo_dev;                   /* kmr_extract_by_owner_host: owner segments of one batch kept on the device between the sizing call and the copy-out */
-	DevBuf cmp_buf[16];              /* temporaries of kmr_compare_spectrums / kmr_compare_reads* (compare_reads_core's CMP_* indices), grow-only */
+	DevBuf cmp_buf[11];              /* temporaries of kmr_compare_spectrums / kmr_compare_reads* (compare_reads_core's CMP_* indices), grow-only */
+	SortBufs cmp_sort;               /* ... and of the sorted path's sort */
 };
 struct BuildMem {                    /* ... by kmr_release_table too: the streaming build's state */
 	DevBuf sk_state;                 /* build_mode 3 (kmr_superkmer.hpp): list words */
@@ -483,9 +488,22 @@ int twobit_rel_offsets(kmr_handle *h, const uint64_t *offsets, uint64_t n, uint6
 int twobit_unpack(kmr_handle *h, const uint8_t *twobit, const uint64_t *twobit_off, const uint64_t *offsets, const uint64_t *mk_off, const uint32_t *mk_pos, const uint8_t *mk_char,
                   uint64_t n, uint8_t *bases, uint64_t *rel);
 
+/* ---- defined in kmr_sort.hip: the stable sort of (u64 key, u32 value) pairs on the handle's stream; `who` names the entry point in the
+ * error text.  sort_reserve: the size query; bufs.tmp is grown to it, so one reservation serves every sort_pairs of no more pairs */
+int sort_reserve(kmr_handle *h, SortBufs &bufs, size_t n, const char *who);
+int sort_pairs(kmr_handle *h, SortBufs &bufs, const unsigned long long *kin, unsigned long long *kout, const uint32_t *vin, uint32_t *vout, size_t n, const char *who);
+/* the sort key of element p in one pass of sort_by_columns: tags[p] if tags is set, else words[(row ? row[p] : p) * stride] */
+struct SortColumn { const uint64_t *words; uint64_t stride; const uint32_t *row; const uint32_t *tags; };
+/* n elements by ncols columns, cols[0] the least significant: one stable pass per column.  order: the element indices in their starting
+ * order (overwritten).  *sorted: the sorted order, in `order` or in bufs.perm2, whichever the pass count leaves it in; *last_keys (unless
+ * null): the last column in sorted order, the caller's to overwrite.  All queued; the host waits only where a buffer of bufs has to grow */
+int sort_by_columns(kmr_handle *h, SortBufs &bufs, const SortColumn *cols, int ncols, uint32_t *order, uint64_t n, const char *who, const uint32_t **sorted, unsigned long long **last_keys);
+/* head[j] = 1 where sorted element j opens a group, hscan its exclusive scan (n + 1): start[g] = the opener of group g, start[groups] = n */
+int group_starts(kmr_handle *h, const uint32_t *head, const uint64_t *hscan, uint64_t n, uint64_t *start);
+
 }  // namespace kmr_host
 
-namespace kmr {      /* kmr_sort.hip */
+namespace kmr {      /* kmr_sort.hip: rocPRIM's radix sort as it is (saturated_fix_t) */
 int sort_pairs_u64_u32(void *tmp, size_t *tmp_bytes, const unsigned long long *keys_in, unsigned long long *keys_out, const unsigned int *vals_in, unsigned int *vals_out, size_t n, hipStream_t stream);
 }
 

@@ -10,7 +10,7 @@
  *           match_edge_keys_kernel    one thread per considered k-mer: its canonical key from the packed sequence (a non-ACGT base is
  *                                     code 0, as KmerWeights(twoBit, len, true) sees it) and its contig -- a long contig is spread
  *                                     over as many lanes as it has edge k-mers
- *           match_gather_kernel       sort keys of one pass of the stable radix sort: the contig, then the key words, last word first
+ *           sort_by_columns           (kmr_sort.hip) one stable radix pass for the contig, then one per key word, last word first
  *           match_flags_kernel        per sorted record: first of its key, first of its (key, contig), and whether the spectrum holds
  *                                     the key (map_find on the weak map, then on the singleton map)
  *           match_table_fill_kernel   the contigs of every kept key, distinct and contiguous, and the key into the table
@@ -130,13 +130,6 @@ __global__ void match_edge_count_kernel(const uint64_t *offsets, uint64_t nc, ui
 		if (L >= 0x7fffffffull) { atomicOr(err, 1u); cnt[c] = 0; continue; }      /* (int) kmers.size() of the reference */
 		bool split;
 		cnt[c] = (uint32_t)match_edge_shape(L >= k ? L - k + 1 : 0, M, &split);
-	}
-}
-/* sort keys of one pass: word w of the records in their current order, or (w == words) their contigs */
-__global__ void match_gather_kernel(const uint64_t *keys, const uint32_t *contig, uint32_t words, uint32_t w, const uint32_t *perm, uint64_t n, unsigned long long *kin) {
-	for (uint64_t j = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; j < n; j += (uint64_t)gridDim.x * blockDim.x) {
-		const uint32_t p = perm[j];
-		kin[j] = w == words ? (unsigned long long)contig[p] : keys[(uint64_t)p * words + w];
 	}
 }
 #endif

@@ -4,8 +4,8 @@
  *
  * Host logic only, as kmr_api.hip (the spectrum, which these stages read through kmr_host.hpp); the kernels are the stage headers',
  * each of which this translation unit alone includes.  A stage costs its kernels and a page here: what the stages share is below --
- * the call's temporaries (Scratch), inputs from host or device memory (to_device), the radix sort with its scratch (sort_reserve,
- * sort_pairs), result objects (make_result, free_on_device, copy_out).
+ * the call's temporaries (Scratch, with the scratch of kmr_sort.hip's sorts), inputs from host or device memory (to_device), result
+ * objects (make_result, free_on_device, copy_out).
  */
 #include <cctype>
 #include <cmath>
@@ -35,14 +35,15 @@ namespace {
 
 /* The temporaries of one call on the handle's stream: take() allocates a block of n elements of T (alloc_n: one allocation, 256 bytes
  * at least) that lives until the call returns.  A return with work still queued -- an error path -- waits for the stream before the
- * blocks go; a call that has waited for its last work itself says done().  sort_buf: the radix sort's scratch (sort_reserve). */
+ * blocks go; a call that has waited for its last work itself says done().  sort: the scratch of the call's sorts (sort_reserve,
+ * sort_pairs, sort_by_columns of kmr_sort.hip), of which tmp is held whenever any is. */
 class Scratch {
 public:
 	explicit Scratch(kmr_handle *h) : h_(h) {}
-	~Scratch() { if (armed_ && (!bufs_.empty() || sort_buf)) hipStreamSynchronize(h_->stream); }
+	~Scratch() { if (armed_ && (!bufs_.empty() || sort.tmp)) hipStreamSynchronize(h_->stream); }
 	template <class T> hipError_t take(T **p, size_t n) { bufs_.emplace_back(); return alloc_n(bufs_.back(), p, n); }
 	void done() { armed_ = false; }
-	DevBuf sort_buf; size_t sort_bytes = 0;
+	SortBufs sort;
 private:
 	kmr_handle *h_; std::vector<DevBuf> bufs_; bool armed_ = true;
 };
@@ -56,20 +57,6 @@ template <class T> int to_device(kmr_handle *h, Scratch &tmp, const T *src, uint
 	HIPCHK(h, tmp.take(&p, n));
 	HIPCHK(h, hipMemcpyAsync(p, src, sizeof(T) * n, hipMemcpyHostToDevice, h->stream));
 	*dev = p;
-	return 0;
-}
-
-/* the library's radix sort (kmr_sort.hip) of n (u64, u32) pairs on the stream.  sort_reserve: the size query; tmp.sort_buf is grown to
- * it (the stream drained first if the block was in use), so one reservation serves every sort of no more pairs */
-int sort_reserve(kmr_handle *h, Scratch &tmp, size_t n, const char *who) {
-	if (kmr::sort_pairs_u64_u32(nullptr, &tmp.sort_bytes, nullptr, nullptr, nullptr, nullptr, n, h->stream) != 0) return fail(h, KMR_ERR_HIP, std::string(who) + ": radix sort (size query)");
-	if (tmp.sort_buf && tmp.sort_buf.cap() >= tmp.sort_bytes) return 0;
-	if (tmp.sort_buf) HIPCHK(h, hipStreamSynchronize(h->stream));
-	HIPCHK(h, tmp.sort_buf.alloc(std::max<size_t>(tmp.sort_bytes, 256)));
-	return 0;
-}
-int sort_pairs(kmr_handle *h, Scratch &tmp, const unsigned long long *kin, unsigned long long *kout, const uint32_t *vin, uint32_t *vout, size_t n, const char *who) {
-	if (kmr::sort_pairs_u64_u32(tmp.sort_buf.get(), &tmp.sort_bytes, kin, kout, vin, vout, n, h->stream) != 0) return fail(h, KMR_ERR_HIP, std::string(who) + ": radix sort");
 	return 0;
 }
 
@@ -609,11 +596,11 @@ int kmr_match_finish(kmr_match *m) {
 		unsigned long long *k1, *ukey, *umate; uint32_t *p0, *p1, *flag; uint64_t *scan;
 		HIPCHK(h, tmp.take(&k1, nh)); HIPCHK(h, tmp.take(&ukey, nh)); HIPCHK(h, tmp.take(&umate, nh)); HIPCHK(h, tmp.take(&p0, nh)); HIPCHK(h, tmp.take(&p1, nh));
 		HIPCHK(h, tmp.take(&flag, 2 * nh)); HIPCHK(h, tmp.take(&scan, 2 * (nh + 1))); HIPCHK(h, tmp.take(&bound, nc + 1)); HIPCHK(h, tmp.take(&bound2, nc + 1));
-		int rc = sort_reserve(h, tmp, nh, "kmr_match_finish"); if (rc) return rc;
+		int rc = sort_reserve(h, tmp.sort, nh, "kmr_match_finish"); if (rc) return rc;
 		const dim3 hgrid(grid_for(nh)), cgrid(grid_for(nc + 1));
 		hipLaunchKernelGGL(match_iota_kernel, hgrid, block, 0, h->stream, p0, nh);
 		HIPCHK(h, hipGetLastError());
-		rc = sort_pairs(h, tmp, m->hit_key.get<unsigned long long>(), k1, p0, p1, nh, "kmr_match_finish"); if (rc) return rc;
+		rc = sort_pairs(h, tmp.sort, m->hit_key.get<unsigned long long>(), k1, p0, p1, nh, "kmr_match_finish"); if (rc) return rc;
 		hipLaunchKernelGGL(match_heads_kernel, hgrid, block, 0, h->stream, (const unsigned long long *)k1, nh, flag);
 		HIPCHK(h, hipGetLastError());
 		rc = exclusive_scan_queue(h, flag, nh, scan); if (rc) return rc;
@@ -646,8 +633,8 @@ int kmr_match_finish(kmr_match *m) {
 			hipLaunchKernelGGL(match_iota_kernel, egrid, block, 0, h->stream, q0, ne);
 			HIPCHK(h, hipGetLastError());
 			/* 3: sorted and made unique again, without the discarded reads */
-			rc = sort_reserve(h, tmp, ne, "kmr_match_finish"); if (rc) return rc;
-			rc = sort_pairs(h, tmp, e0, e1, q0, q1, ne, "kmr_match_finish"); if (rc) return rc;
+			rc = sort_reserve(h, tmp.sort, ne, "kmr_match_finish"); if (rc) return rc;
+			rc = sort_pairs(h, tmp.sort, e0, e1, q0, q1, ne, "kmr_match_finish"); if (rc) return rc;
 			const uint32_t nb = (uint32_t)m->batches.size();
 			std::vector<uint64_t> bf(nb), bn(nb); std::vector<const uint8_t *> bp(nb);
 			for (uint32_t i = 0; i < nb; i++) { bf[i] = m->batches[i].first; bn[i] = m->batches[i].n; bp[i] = m->batches[i].discarded.get<uint8_t>(); }
@@ -2302,9 +2289,9 @@ static int pairs_core(kmr_handle *h, Scratch &tmp, const kmr_reads *r, const uin
 		hipLaunchKernelGGL(pairs_keys_kernel, grid, block, 0, h->stream, (const uint32_t *)unp, (const uint64_t *)uscan, (const uint64_t *)hash, bits >= 64 ? ~0ull : (1ull << bits) - 1, n, kin, vin);
 		HIPCHK(h, hipGetLastError());
 		HIPCHK(h, hipMemsetAsync(push, 0, 4 * n, h->stream)); HIPCHK(h, hipMemsetAsync(side, 0, n, h->stream));
-		rc = sort_reserve(h, tmp, m, "kmr_identify_pairs"); if (rc) return rc;
+		rc = sort_reserve(h, tmp.sort, m, "kmr_identify_pairs"); if (rc) return rc;
 		timer.mark(2, h->stream);
-		rc = sort_pairs(h, tmp, kin, kout, vin, vout, m, "kmr_identify_pairs"); if (rc) return rc;
+		rc = sort_pairs(h, tmp.sort, kin, kout, vin, vout, m, "kmr_identify_pairs"); if (rc) return rc;
 		timer.mark(3, h->stream);
 		hipLaunchKernelGGL(pairs_group_kernel, dim3(grid_for(m)), block, 0, h->stream, P, N, (const unsigned long long *)kout, (const uint32_t *)vout, m, mate, push, side, tot);
 		HIPCHK(h, hipGetLastError());
@@ -2456,7 +2443,7 @@ static int dedup_core(kmr_handle *h, Scratch &tmp, const kmr_reads *r, const uin
 	P.min_q = h->cfg.fastq_start_char + h->cfg.min_quality_score; P.start_char = h->cfg.fastq_start_char;
 	const dim3 block(256);
 	uint64_t totals[DEDUP_T_WORDS] = {0}, c = 0, K = 0;
-	unsigned long long *keys, *kin, *kout, *first, *first2; uint32_t *cand, *perm = nullptr, *perm2, *head, *keep = nullptr, *grp, *grp2; uint8_t *flip = nullptr; uint64_t *cscan, *tot, *hscan = nullptr, *start = nullptr, *kscan;
+	unsigned long long *keys, *first, *first2; uint32_t *cand, *order, *head, *keep = nullptr, *grp, *grp2; const uint32_t *perm = nullptr; uint8_t *flip = nullptr; uint64_t *cscan, *tot, *hscan = nullptr, *start = nullptr, *kscan;
 	HIPCHK(h, tmp.take(&tot, (size_t)DEDUP_T_WORDS));
 	HIPCHK(h, hipMemsetAsync(tot, 0, 8 * DEDUP_T_WORDS, h->stream));
 	if (n && np && cfg->dedup_mode) {
@@ -2475,17 +2462,14 @@ static int dedup_core(kmr_handle *h, Scratch &tmp, const kmr_reads *r, const uin
 	timer.mark(2, h->stream);
 	if (c >= 2) {
 		const dim3 cgrid(grid_for(c));
-		HIPCHK(h, tmp.take(&perm, c)); HIPCHK(h, tmp.take(&perm2, c)); HIPCHK(h, tmp.take(&kin, c)); HIPCHK(h, tmp.take(&kout, c));
-		hipLaunchKernelGGL(dedup_compact_kernel, dim3(grid_for(np)), block, 0, h->stream, (const uint32_t *)cand, (const uint64_t *)cscan, np, perm);
+		HIPCHK(h, tmp.take(&order, c));
+		hipLaunchKernelGGL(dedup_compact_kernel, dim3(grid_for(np)), block, 0, h->stream, (const uint32_t *)cand, (const uint64_t *)cscan, np, order);
 		HIPCHK(h, hipGetLastError());
-		rc = sort_reserve(h, tmp, c, "kmr_dedup_fragments"); if (rc) return rc;
 		/* least significant word first; the sort is stable, so equal keys keep ascending pair position */
-		for (uint32_t w = P.W; w-- > 0;) {
-			hipLaunchKernelGGL(dedup_gather_kernel, cgrid, block, 0, h->stream, (const unsigned long long *)(keys + (size_t)w * np), (const uint32_t *)perm, c, kin);
-			HIPCHK(h, hipGetLastError());
-			rc = sort_pairs(h, tmp, kin, kout, perm, perm2, c, "kmr_dedup_fragments"); if (rc) return rc;
-			std::swap(perm, perm2);
-		}
+		SortColumn cols[4];      /* a key holds at most 128 bases (kmr_dedup_config_check) */
+		if (P.W > 4) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_dedup_fragments: a key of more than 4 words");
+		for (uint32_t w = 0; w < P.W; w++) cols[w] = SortColumn{(const uint64_t *)keys + (size_t)(P.W - 1 - w) * np, 1, nullptr, nullptr};
+		rc = sort_by_columns(h, tmp.sort, cols, (int)P.W, order, c, "kmr_dedup_fragments", &perm, nullptr); if (rc) return rc;
 		timer.mark(3, h->stream);
 		/* groups, and those of two members and more */
 		HIPCHK(h, tmp.take(&head, c)); HIPCHK(h, tmp.take(&hscan, c + 1)); HIPCHK(h, tmp.take(&start, c + 1));
@@ -2493,7 +2477,7 @@ static int dedup_core(kmr_handle *h, Scratch &tmp, const kmr_reads *r, const uin
 		hipLaunchKernelGGL(dedup_heads_kernel, cgrid, block, 0, h->stream, (const unsigned long long *)keys, np, P.W, (const uint32_t *)perm, c, head);
 		HIPCHK(h, hipGetLastError());
 		rc = exclusive_scan(h, head, c, hscan); if (rc) return rc;
-		hipLaunchKernelGGL(dedup_starts_kernel, cgrid, block, 0, h->stream, (const uint32_t *)head, (const uint64_t *)hscan, c, start);
+		rc = group_starts(h, head, hscan, c, start); if (rc) return rc;
 		hipLaunchKernelGGL(dedup_keep_kernel, cgrid, block, 0, h->stream, (const uint64_t *)hscan, (const uint64_t *)start, c, keep);
 		HIPCHK(h, hipGetLastError());
 		rc = exclusive_scan(h, keep, c, kscan); if (rc) return rc;
@@ -2517,8 +2501,8 @@ static int dedup_core(kmr_handle *h, Scratch &tmp, const kmr_reads *r, const uin
 	if (K) {
 		/* output order: ascending position of the first member */
 		HIPCHK(h, tmp.take(&first2, K)); HIPCHK(h, tmp.take(&grp2, K));
-		rc = sort_reserve(h, tmp, K, "kmr_dedup_fragments"); if (rc) return rc;
-		rc = sort_pairs(h, tmp, first, first2, grp, grp2, K, "kmr_dedup_fragments"); if (rc) return rc;
+		rc = sort_reserve(h, tmp.sort, K, "kmr_dedup_fragments"); if (rc) return rc;
+		rc = sort_pairs(h, tmp.sort, first, first2, grp, grp2, K, "kmr_dedup_fragments"); if (rc) return rc;
 		DedupGroups G; G.perm = perm; G.flip = flip; G.start = start; G.ogroup = grp2; G.K = K;
 		uint32_t *len, *nb; uint64_t *nscan; DedupMember *members;
 		HIPCHK(h, tmp.take(&len, n_new)); HIPCHK(h, tmp.take(&nb, n_new)); HIPCHK(h, tmp.take(&nscan, n_new + 1)); HIPCHK(h, tmp.take(&members, (size_t)c * P.sides));

@@ -159,7 +159,7 @@ def f32_edge():
     return case("f32_edge", k, [c], reads, max_read_matches=3, first=F32_EDGE_READ - 6, include_mate=False)
 
 
-KS = (21, 22, 33, 65)              # one, one (even), two and three key words
+KS = (21, 22, 33, 65, 97)          # one, one (even), two, three and four key words
 
 
 def all_cases():

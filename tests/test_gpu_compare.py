@@ -150,10 +150,11 @@ SETTINGS = {"default": {}, "cap_8": dict(compare_lds_kmers=8), "cap_0": dict(com
 
 
 @pytest.mark.parametrize("setting", sorted(SETTINGS))
-@pytest.mark.parametrize("k", [31, 65, 97])
+@pytest.mark.parametrize("k", [31, 33, 65, 97])
 def test_records_do_not_depend_on_cap_or_staging(dev, k, setting):
     """reads of CAP - 1, CAP and CAP + 1 k-mers and one of several tile spans; a staging budget that forces several runs and a lone
-    oversize read"""
+    oversize read.  One to four key words: the sorted path (cap_0) takes one sort pass per word and one more, and its order ends in
+    a different buffer for an odd and an even count.  The families bring a read of one k-mer and an empty read"""
     fam = cap_batch(k)
     sp = dev.set2(k)
     try:

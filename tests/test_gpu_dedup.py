@@ -80,7 +80,7 @@ def generated(seed):
     return reads, discarded, refdedup.pair_list(reads), refdedup.fastq_text(reads)
 
 
-@pytest.mark.parametrize("geometry", [(4, 0), (24, 0), (24, 4), (32, 8), (64, 0)], ids=lambda g: "len%d_off%d" % g)
+@pytest.mark.parametrize("geometry", [(4, 0), (24, 0), (24, 4), (32, 8), (48, 0), (64, 0)], ids=lambda g: "len%d_off%d" % g)
 @pytest.mark.parametrize("mode", [1, 2])
 @pytest.mark.parametrize("seed", [1, 2, 3])
 def test_generated_batches(seed, mode, geometry):
