@@ -35,6 +35,7 @@
 
 #include "kmr_host.hpp"
 #include "kmr_runs.hpp"
+#include "kmr_image_layout.hpp"
 #include "kmr_kernels.hpp"
 #include "kmr_partition.hpp"
 #include "kmr_superkmer.hpp"
@@ -421,25 +422,17 @@ template <int W> int build_image_t(kmr_handle *h, DevMap &m, bool weakMap) {
 }
 int build_image(kmr_handle *h, DevMap &m, bool weakMap) { return with_w(h, [&](auto W) { return build_image_t<W()>(h, m, weakMap); }); }
 
-template <int W> int load_image_t(kmr_handle *h, DevMap &m, bool weakMap, const uint8_t *src, uint64_t len) {
-	if (len < 16) return fail(h, KMR_ERR_INVALID_ARG, "image too short");
-	uint64_t nb, mask; memcpy(&nb, src, 8); memcpy(&mask, src + 8, 8);
-	if (nb == 0 || (nb & (nb - 1)) || mask != nb - 1 || len < 8 * (2 + nb) + 4 * nb) return fail(h, KMR_ERR_INVALID_ARG, "bad image header");
+/* A stored map becomes the map `out`.  The layout is checked on the host first (kmr_image_layout.hpp), before any kernel follows an
+ * offset or a count of it, and the map is built on the side: `out` changes only once the check, every allocation and every launch
+ * have succeeded, so a refused or failed load leaves the map it was to replace as it was. */
+template <int W> int load_image_t(kmr_handle *h, DevMap &out, bool weakMap, const uint8_t *src, uint64_t len) {
 	const uint32_t vw = h->ext ? 15 : 3;
 	const uint32_t vbytes = weakMap ? (h->ext ? 60 : 12) : (h->ext ? 5 : 1);
-	if ((len - 8 * (2 + nb) - 4 * nb) % (h->kb + vbytes) != 0) return fail(h, KMR_ERR_INVALID_ARG, "image size does not match k / value type");
-	m = DevMap();
-	m.nb = nb; m.n = (len - 8 * (2 + nb) - 4 * nb) / (h->kb + vbytes); m.present = true;
-	/* validate offsets on the host before any kernel dereferences them */
-	const uint64_t *offs = (const uint64_t *)(src + 16);
-	uint64_t expect = 8 * (2 + nb);
-	for (uint64_t b = 0; b < nb; b++) {
-		if (offs[b] != expect || expect + 4 > len) return fail(h, KMR_ERR_INVALID_ARG, "image offsets are not the packed store() layout");
-		uint32_t cnt; memcpy(&cnt, src + expect, 4);
-		expect += 4 + (uint64_t)cnt * (h->kb + vbytes);
-		if (expect > len) return fail(h, KMR_ERR_INVALID_ARG, "image bucket runs past the end");
-	}
-	if (expect != len) return fail(h, KMR_ERR_INVALID_ARG, "image length mismatch");
+	const kmr_host::ImageLayout lay = kmr_host::check_image_layout(src, len, h->kb, vbytes);
+	if (lay.reason) return fail(h, KMR_ERR_INVALID_ARG, lay.reason);
+	const uint64_t nb = lay.nb;
+	DevMap m;
+	m.nb = nb; m.n = lay.n; m.present = true;
 	HIPCHK(h, m.image.alloc(len));
 	HIPCHK(h, hipMemcpy(m.image.get<uint8_t>(), src, len, hipMemcpyHostToDevice));
 	{
@@ -460,7 +453,7 @@ template <int W> int load_image_t(kmr_handle *h, DevMap &m, bool weakMap, const 
 	HIPCHK(h, hipGetLastError());
 	HIPCHK(h, hipStreamSynchronize(h->stream));
 	m.image.reset();    /* rebuilt (sorted) on demand */
-
+	out = std::move(m);
 	return 0;
 }
 
@@ -2871,7 +2864,7 @@ int kmr_image_size(kmr_handle *h, int which, uint64_t *bytes) {
 	DevMap *m = map_of(h, which);
 	if (!m) return fail(h, KMR_ERR_UNSUPPORTED, "solid map is not built on this path");
 	const uint32_t vbytes = which == KMR_MAP_WEAK ? (h->ext ? 60 : 12) : (h->ext ? 5 : 1);
-	const uint64_t n = (which == KMR_MAP_SINGLETON && !m->present) ? 0 : m->n;
+	const uint64_t n = m->present ? m->n : 0;
 	*bytes = 8 * (2 + m->nb) + 4 * m->nb + n * (h->kb + vbytes);
 	return KMR_OK;
 }
@@ -2882,7 +2875,7 @@ int kmr_write_image(kmr_handle *h, int which, void *dst, uint64_t capacity) {
 	if (capacity < need) return fail(h, KMR_ERR_CAPACITY, "image buffer too small");
 	hipSetDevice(h->device);
 	DevMap *m = map_of(h, which);
-	if (which == KMR_MAP_SINGLETON && !m->present) {   /* cleared singleton map: numBuckets empty buckets */
+	if (!m->present) {   /* a cleared singleton map, or the weak map of a handle that only loaded a singleton image: numBuckets empty buckets */
 		uint8_t *p = (uint8_t *)dst; uint64_t nb = m->nb, mask = nb - 1; memcpy(p, &nb, 8); memcpy(p + 8, &mask, 8);
 		for (uint64_t b = 0; b < nb; b++) { uint64_t off = 8 * (2 + nb) + 4 * b; memcpy(p + 16 + 8 * b, &off, 8); uint32_t z = 0; memcpy(p + off, &z, 4); }
 		return KMR_OK;
