@@ -1417,6 +1417,9 @@ void *kmr_stream(kmr_handle *h);
  *   (kmr_normalize_*: its 2 n slots), 1 - 8192; 0 = the default, 4096 (kmr_normalize_*: 8192) unless there are many segments; tests set a few so that one wavefront walks many tiles of 64 reads; may be set at any time).
  *   "dump_timing" (1: kmr_dump_text_size / kmr_dump_text time their size pass and writer with HIP events, see kmr_build_info; default 0),
  *   "dump_piece_bytes" (staging bound of one piece of kmr_dump_mercount / kmr_dump_mergraph's file, 0 = KMR_DUMP_PIECE_BYTES; may be set at any time).
+ *   "dump_tiles_per_block" (32 KiB tiles of the text that one block of kmr_dump_text's writer walks, 0 = the default, as many as leave 16 blocks
+ *   a compute unit; tests set 1, 2, 3 or more than the text has so that a small text takes the writer's tile-to-tile hand-off; changes no
+ *   byte of the text; see kmr_build_info; may be set at any time).
  *   "pair_hash_bits" (bits of the common name's hash that kmr_identify_pairs* sorts by, 1 - 64, default 64: with a few bits distinct names
  *   share a key, which tests use to reach the byte-for-byte grouping), "pairs_timing" (1: kmr_identify_pairs* times its phases with HIP
  *   events, see kmr_build_info; default 0); both may be set at any time.
@@ -1455,7 +1458,8 @@ int kmr_tune(kmr_handle *h, const char *knob, double value);
  * and artifact filter; not only h's), "filter_score_ms" / "select_ms" / "select_write_ms" = HIP-event times of the last kmr_filter_read_batch* /
  * kmr_select_reads* on this handle: its scoring, its selection with the writer, the writer alone (0 unless kmr_tune "select_timing" is set),
  * "dump_size_ms" / "dump_write_ms" = HIP-event times of the last kmr_dump_text_size / kmr_dump_text on this handle: its size pass with
- * the scan, its writer (0 unless kmr_tune "dump_timing" is set), "pairs_ms" / "pairs_parse_ms" / "pairs_sort_ms" = HIP-event times of the
+ * the scan, its writer (0 unless kmr_tune "dump_timing" is set), "dump_tiles_per_block" / "dump_blocks" = tiles per block and blocks of the
+ * writer of the last kmr_dump_text on this handle that made a text (a block of more than one tile took the hand-off), "pairs_ms" / "pairs_parse_ms" / "pairs_sort_ms" = HIP-event times of the
  * last kmr_identify_pairs* on this handle: the whole call, its name parse, its radix sort (0 unless kmr_tune "pairs_timing" is set),
  * "pair_hash_collisions" = runs of equal sort keys of that call that held more than one distinct common name,
  * "dedup_ms" / "dedup_key_ms" / "dedup_sort_ms" / "dedup_consensus_ms" = HIP-event times of the last kmr_dedup_fragments* on this

@@ -2291,6 +2291,7 @@ int kmr_tune(kmr_handle *h, const char *knob, double value) {
 	else if (k == "artifact_report_lds") h->tune.artifact_report_lds = value == 0 ? 0 : value == 1 ? 1 : -1;
 	else if (k == "pair_hash_bits") h->tune.pair_hash_bits = value >= 1 && value < 64 ? (uint32_t)value : 64;
 	else if (k == "dump_piece_bytes") h->tune.dump_piece_bytes = value >= 1 ? (uint64_t)value : 0;
+	else if (k == "dump_tiles_per_block") h->tune.dump_tiles_per_block = value >= 1 ? (uint64_t)std::min(value, 4294967296.0) : 0;
 	else if (k == "narrow_tallies") h->tune.no_narrow = value == 0;
 	else if (k == "keep_level1_state") h->tune.no_l1_state = value == 0;
 	else if (k == "csr_partition") h->tune.csr_partition = value != 0;
@@ -2351,6 +2352,8 @@ int kmr_build_info(kmr_handle *h, const char *what, double *value) {
 	else if (k == "dedup_consensus_ms") *value = h->last_dedup_consensus_ms;
 	else if (k == "dump_size_ms") *value = h->last_dump_size_ms;
 	else if (k == "dump_write_ms") *value = h->last_dump_write_ms;
+	else if (k == "dump_tiles_per_block") *value = (double)h->last_dump_tiles_per_block;
+	else if (k == "dump_blocks") *value = (double)h->last_dump_blocks;
 	else return fail(h, KMR_ERR_INVALID_ARG, "unknown build figure '" + k + "'");
 	return KMR_OK;
 }

@@ -185,6 +185,7 @@ struct KMR_HIDDEN Tuning {
 	bool no_lean_extract = false;      /* never take sk_extract_lean_kernel (A/B runs, tests of the general kernel on uniform qualities) */
 	bool exchange_fail_once = false;   /* tests: the next kmr_exchange_add_reads_dev of this rank fails locally (the other ranks must come back with an error, not hang) */
 	uint64_t dump_piece_bytes = 0;     /* kmr_dump_mercount / kmr_dump_mergraph: staging bound of one piece of the file (0 = KMR_DUMP_PIECE_BYTES) */
+	uint64_t dump_tiles_per_block = 0; /* kmr_dump_text*: output tiles one block of dump_write_kernel walks (0 = enough for 16 blocks per CU; tests: small values, so that a small text reaches the tile-to-tile hand-off) */
 	bool dump_timing = false;          /* kmr_dump_text*: time the size pass and the writer with HIP events (kmr_build_info; measurement tools) */
 	bool select_timing = false;        /* kmr_select_* / kmr_filter_*: time scoring, selection and writer with HIP events (kmr_build_info; measurement tools) */
 	bool pairs_timing = false;         /* kmr_identify_pairs*: time the name parse, the sort and the whole call with HIP events (kmr_build_info; measurement tools) */
@@ -270,6 +271,7 @@ struct KMR_HIDDEN kmr_handle : HandleMem, BuildMem, ExchangeMem {
 	double last_score_ms = 0, last_select_ms = 0, last_write_ms = 0;      /* the last kmr_filter_read_batch* / kmr_select_reads*: scoring, selection + writer, writer alone (HIP events, taken with kmr_tune "select_timing" only; kmr_build_info) */
 	int last_artifact_report_lds = 0;      /* the last kmr_artifact_filter_report* / _apply_report*: 1 = its counters were summed in LDS, 0 = by global atomics (kmr_build_info) */
 	double last_dump_size_ms = 0, last_dump_write_ms = 0;      /* the last kmr_dump_text_size / kmr_dump_text: size pass with its scan, writer (HIP events, taken with kmr_tune "dump_timing" only; kmr_build_info) */
+	uint64_t last_dump_tiles_per_block = 0, last_dump_blocks = 0;      /* the last kmr_dump_text that wrote a text: tiles per block and blocks of dump_write_kernel (kmr_build_info) */
 	double last_pairs_ms = 0, last_pairs_parse_ms = 0, last_pairs_sort_ms = 0;      /* the last kmr_identify_pairs*: the whole call, its name parse, its radix sort (HIP events, taken with kmr_tune "pairs_timing" only; kmr_build_info) */
 	double last_dedup_ms = 0, last_dedup_key_ms = 0, last_dedup_sort_ms = 0, last_dedup_consensus_ms = 0;      /* the last kmr_dedup_fragments*: the whole call, its key kernel, its radix sorts, its consensus kernel (HIP events, taken with kmr_tune "dedup_timing" only; kmr_build_info) */
 	uint64_t last_pair_hash_collisions = 0;      /* ... and how many of its runs of equal hash keys held more than one distinct common name */

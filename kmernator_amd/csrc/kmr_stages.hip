@@ -2632,8 +2632,9 @@ static int dump_core(kmr_handle *h, int kind, uint32_t min_depth, uint64_t lo, u
 		timer.mark(1, h->stream);      /* (behind the allocation: the events then bracket the writer alone) */
 		if (out && tx->bytes) {
 			const uint64_t tiles = (tx->bytes + DUMP_TILE - 1) / DUMP_TILE;
-			const uint64_t per_block = (tiles + (uint64_t)num_cus(h) * 16 - 1) / ((uint64_t)num_cus(h) * 16);
+			const uint64_t per_block = h->tune.dump_tiles_per_block ? h->tune.dump_tiles_per_block : (tiles + (uint64_t)num_cus(h) * 16 - 1) / ((uint64_t)num_cus(h) * 16);
 			const unsigned blocks = (unsigned)((tiles + per_block - 1) / per_block);
+			h->last_dump_tiles_per_block = per_block; h->last_dump_blocks = blocks;
 			uint8_t *dout = tx->text.get<uint8_t>();
 			with_w(h, [&](auto W) { hipLaunchKernelGGL(dump_write_kernel<W()>, dim3(blocks), dim3(DUMP_THREADS), 0, h->stream, P, (const uint64_t *)off, tx->bytes, per_block, dout); return 0; });
 			HIPCHK(h, hipGetLastError());

@@ -259,3 +259,21 @@ def test_memory_returns_and_texts_are_independent(big):
         a.numpy()
     p.dumpTextSize("mergraph", 3)
     assert live(p) == base
+
+
+def test_tiles_per_block_change_no_byte(big):
+    """kmr_tune "dump_tiles_per_block" at 2, 7 and more tiles than the text has: every block but the last walks several tiles, so
+    all but a few hundredths of the 8 MB text's tile borders are crossed by the hand-off from tile to tile (at the default every
+    block of a text this small bisects); the bytes stay the oracle's"""
+    o, p, want, _ = big
+    for graph in (False, True):
+        tiles = -(-len(want[graph]) // 32768)
+        assert tiles > 250
+        for per_block in (2, 7, 100000):
+            p.tune(dump_tiles_per_block=per_block)
+            assert device_text(p, 3, graph)[0] == want[graph], (graph, per_block)
+            assert int(p.build_info("dump_tiles_per_block")) == per_block
+            assert int(p.build_info("dump_blocks")) == -(-tiles // per_block) < tiles
+    p.tune(dump_tiles_per_block=0)
+    assert device_text(p, 3, False)[0] == want[False]
+    assert int(p.build_info("dump_tiles_per_block")) == 1 and int(p.build_info("dump_blocks")) == -(-len(want[False]) // 32768)
