@@ -894,9 +894,10 @@ struct CountPass {
 	FinalizeCounters c{}; unsigned long long cur[2] = {0, 0};                    /* what the count pass reported */
 };
 
-/* room the blocks of a count pass leave unused: one partly used output slab of 8192 slots each */
+/* room the blocks of a count pass leave unused: one partly used output slab of 8192 slots each (the pass over super-k-mer lists: a slab
+ * of SK_OSLAB entries per wavefront, four wavefronts a block; blocks_per_cu: what its launch is sized for, sk_count_blocks) */
 uint64_t entry_slack(uint64_t slabs) { return slabs * 8192 + 16; }
-uint64_t sk_entry_slack(kmr_handle *h) { return entry_slack((uint64_t)num_cus(h) * 4); }
+uint64_t sk_entry_slack(kmr_handle *h, int blocks_per_cu) { return entry_slack((uint64_t)num_cus(h) * (uint64_t)blocks_per_cu); }
 
 /* Entry buffers of the pass over G good k-mers: how many entries to start with (wfirst / sfirst and the slack) and their upper bounds;
  * the per-bucket counts, counters and cursors.  The worst case (every second record a weak entry, or every record a singleton) is
@@ -1744,10 +1745,20 @@ template <int W> SkLong<W> sk_own_lists(kmr_handle *h, bool refined) {
 template <int W> struct SkCountLaunch {
 	void (*kern)(const uint4 *, const uint64_t *, const uint64_t *, uint64_t, uint32_t, SkCountHot, unsigned int *, uint32_t, const SkCountArgs<W> *);
 	size_t smem;
+	int blocks;      /* blocks per CU the grid is sized for */
 };
-template <int W, int LOG2S, bool TRACK, bool EXT, bool UNI, bool ITEM> SkCountLaunch<W> sk_count_form() { return {sk_count_kernel<W, LOG2S, TRACK, EXT, UNI, ITEM>, sk_count_smem_bytes<W, LOG2S, TRACK, EXT, UNI>()}; }
-template <int W, bool ITEM> SkCountLaunch<W> sk_count_forms(bool ext, bool tracking, bool uni) {
+/* Blocks per CU a launch of the count pass is sized for: four (every form's grid has been num_cus x 4 all along, whatever its instance is
+ * compiled for), or five for the one form that exists as a five-block instance -- one-weight, one-word keys, lists (not work items) --
+ * where kmr_tune "count_blocks" asks for it.  The entry buffers' slack follows it (a slab tail per wavefront launched). */
+static const int SK_COUNT_BLOCKS_DEFAULT = 5;      /* what "count_blocks" 0 means for that form: C2's count pass 8.72 -> 7.7 ms (profiles/count_blocks_ab.jsonl) */
+template <int W> int sk_count_blocks(kmr_handle *h, bool ext, bool tracking, bool uni, bool item) {
+	if (W != 1 || ext || tracking || !uni || item) return 4;
+	return h->tune.count_blocks ? h->tune.count_blocks : SK_COUNT_BLOCKS_DEFAULT;
+}
+template <int W, int LOG2S, bool TRACK, bool EXT, bool UNI, bool ITEM, int BLOCKS = 0> SkCountLaunch<W> sk_count_form() { return {sk_count_kernel<W, LOG2S, TRACK, EXT, UNI, ITEM, BLOCKS>, sk_count_smem_bytes<W, LOG2S, TRACK, EXT, UNI>(), BLOCKS ? BLOCKS : 4}; }
+template <int W, bool ITEM> SkCountLaunch<W> sk_count_forms(bool ext, bool tracking, bool uni, int blocks) {
 	if constexpr (!ITEM) { if (tracking && !ext) return sk_count_form<W, COUNT_LOG2S, true, false, false, false>(); }
+	if constexpr (W == 1 && !ITEM) { if (blocks == 5) return sk_count_form<1, COUNT_LOG2S, false, false, true, false, 5>(); }
 	return ext ? sk_count_form<W, COUNT_LOG2S_EXT, false, true, false, ITEM>() :
 	    (uni ? sk_count_form<W, COUNT_LOG2S, false, false, true, ITEM>() : sk_count_form<W, COUNT_LOG2S, false, false, false, ITEM>());
 }
@@ -1758,7 +1769,10 @@ template <int W> int sk_count_select(kmr_handle *h, bool ext, bool tracking, boo
 	if (item && tracking) return fail(h, KMR_ERR_STATE, "internal: the size tracker's count pass has no long-list items");
 	if (item != (lg.item_c0 != nullptr) || (item && (!lg.item_c1 || !lg.merge.slots || !lg.merge_used))) return fail(h, KMR_ERR_STATE, "internal: count pass and its work items disagree");
 	if (ext ? (!out.wkeys || !out.wvals || !out.weakCount) : !out.wentries) return fail(h, KMR_ERR_STATE, "internal: count pass and its entry buffers disagree");
-	k = item ? sk_count_forms<W, true>(ext, tracking, uni) : sk_count_forms<W, false>(ext, tracking, uni);
+	const int blocks = sk_count_blocks<W>(h, ext, tracking, uni, item);
+	k = item ? sk_count_forms<W, true>(ext, tracking, uni, blocks) : sk_count_forms<W, false>(ext, tracking, uni, blocks);
+	if (k.blocks != blocks) return fail(h, KMR_ERR_STATE, "internal: count pass and its blocks per CU disagree");
+	if (!item) h->last_count_blocks = k.blocks;
 	const auto kern = k.kern; const size_t smem = k.smem;
 	HIPCHK(h, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
 	return 0;
@@ -1902,9 +1916,9 @@ template <int W> int sk_count_pass(kmr_handle *h, SkFinalize<W> &p) {
 	return count_attempts(h, p, [&]() -> int { mslots.reset(); mext.reset(); return 0; }, [&](const CountOut &out, bool repeated, uint32_t &repeat_on) -> int {
 		if (repeated) merge_log2 += 3;
 		int rc = 0;
-		const int grid = (int)std::min<uint64_t>((uint64_t)num_cus(h) * 4, (nl / p.lgMain.list_stride + SK_LBATCH) / SK_LBATCH);
 		SkCountLaunch<W> k;
 		rc = sk_count_select<W>(h, p.ext, p.tracking, p.uni, false, out, p.lgMain, k); if (rc) return rc;
+		const int grid = (int)std::min<uint64_t>((uint64_t)num_cus(h) * k.blocks, (nl / p.lgMain.list_stride + SK_LBATCH) / SK_LBATCH);
 		if (p.tracking) HIPCHK(h, hipMemsetAsync(tv.d_unique, 0, 8 * (tv.n + 1), h->stream));
 		if (dbg()) { int nb = 0; hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)k.kern, SKC_THREADS, k.smem); fprintf(stderr, "sk_count<W=%d>: %d blocks per CU (LDS %zu), %llu lists, %u chunks\n", W, nb, k.smem, (unsigned long long)nl, p.nch); }
 		rc = sk_count_launch<W>(h, k, grid, p.ls, p.lc, nl, out, p.f, tv, p.lgMain); if (rc) return rc;
@@ -1919,8 +1933,8 @@ template <int W> int sk_count_pass(kmr_handle *h, SkFinalize<W> &p) {
 		lgItems.merge.slots = mslots.get<Slot<W>>(); lgItems.merge.ext = mext.get<ExtSlot>(); lgItems.merge.log2cap = merge_log2;
 		HIPCHK(h, hipMemsetAsync(lgItems.merge_used, 0, 8, h->stream));
 		rc = zero_work_counter(h); if (rc) return rc;
-		const int grid2 = (int)std::min<uint64_t>((uint64_t)num_cus(h) * 4, n_items);
 		rc = sk_count_select<W>(h, p.ext, p.tracking, p.uni, true, out, lgItems, k); if (rc) return rc;
+		const int grid2 = (int)std::min<uint64_t>((uint64_t)num_cus(h) * k.blocks, n_items);
 		rc = sk_count_launch<W>(h, k, grid2, p.ls, p.lc, nl, out, p.f, tv, lgItems); if (rc) return rc;
 		hipLaunchKernelGGL(sk_merge_emit_kernel<W>, dim3(grid_for(1ull << merge_log2)), dim3(256), 0, h->stream, lgItems.merge, out, p.f);
 		if (hipGetLastError() != hipSuccess) return fail(h, KMR_ERR_HIP, "long-list launches");
@@ -1967,9 +1981,9 @@ template <int W> int finalize_superkmer_t(kmr_handle *h, uint32_t min_depth) {
 	if (p.refined) { rc = sk_refine_lists(h, p.nl); if (rc) return rc; }
 	rc = build_csr(h, h->l1, p.nl, 0, &p.ls, &p.lc, &p.nch, p.refined ? nullptr : &h->l1_head_seen); if (rc) return rc;      /* (refining takes chunks) */
 	/* entry buffers: sequencing data keeps a few per cent of its k-mers as weak entries */
-	rc = count_entry_buffers(h, p, G, sk_entry_slack(h), G / (p.f.has_singletons ? 8 : 3), G / 3, h->sk_exchange && h->cfg.world_size > 1); if (rc) return rc;
 	rc = sk_count_uniform<W>(h, p.tracking, p.uni, p.f.uni_wbits); if (rc) return rc;
 	h->last_count_uniform = p.uni;
+	rc = count_entry_buffers(h, p, G, sk_entry_slack(h, sk_count_blocks<W>(h, p.ext, p.tracking, p.uni, false)), G / (p.f.has_singletons ? 8 : 3), G / 3, h->sk_exchange && h->cfg.world_size > 1); if (rc) return rc;
 	if (p.tracking) { rc = sk_track_view(h, p.tv); if (rc) return rc; }
 	p.lgMain = sk_own_lists<W>(h, p.refined);
 	bool device_error = false;
@@ -2028,7 +2042,9 @@ template <int W> int count_prefix_superkmer_t(kmr_handle *h, uint32_t min_depth,
 	 * owner whose lists hold more than its own reads' share) sets ERR_ENTRIES_FULL in the early pass's own error word, which only
 	 * kmr_finalize reads: it voids the early count and counts every list itself (kmr_build_info "early_overflowed") */
 	const uint64_t G = h->stats.raw_good_kmers;      /* (an owner's lists hold about as many k-mers as its own reads gave: the job's share of one rank) */
-	uint64_t want = (uint64_t)((double)G * ((double)hi / (double)nl) / (f.has_singletons ? 6.0 : 2.5)) + sk_entry_slack(h);
+	bool uni = false;
+	if (!h->peer_uni_mixed) { rc = sk_count_uniform<W>(h, false, uni, f.uni_wbits); if (rc) return rc; }      /* (senders that declared mixed weights settle it here without a look at the device pair) */
+	uint64_t want = (uint64_t)((double)G * ((double)hi / (double)nl) / (f.has_singletons ? 6.0 : 2.5)) + sk_entry_slack(h, sk_count_blocks<W>(h, false, false, uni, false));
 	if (h->tune.early_entry_share >= 0) { want = (uint64_t)((double)G * h->tune.early_entry_share) + 16384; h->early.ue.reset(); }      /* kmr_tune "early_entry_share" */
 	rc = h->early.ue.reserve(h, "early count ue", 8ull * (W + 1) * want); if (rc) return rc;
 	rc = h->early.cursor.reserve(h, "early count cursor", 16); if (rc) return rc;
@@ -2036,8 +2052,6 @@ template <int W> int count_prefix_superkmer_t(kmr_handle *h, uint32_t min_depth,
 	rc = h->early.err.reserve(h, "early count error word", 4); if (rc) return rc;
 	HIPCHK(h, hipMemsetAsync(h->early.cursor.get<unsigned long long>(), 0, 16, h->stream)); HIPCHK(h, hipMemsetAsync(h->early.fc.get(), 0, sizeof(FinalizeCounters), h->stream));
 	HIPCHK(h, hipMemsetAsync(h->early.err.get<uint32_t>(), 0, 4, h->stream));      /* (a replaced early count leaves no flag behind) */
-	bool uni = false;
-	if (!h->peer_uni_mixed) { rc = sk_count_uniform<W>(h, false, uni, f.uni_wbits); if (rc) return rc; }      /* (senders that declared mixed weights settle it here without a look at the device pair) */
 	const SkTrackView tv{};
 	SkLong<W> lg = sk_own_lists<W>(h, false);
 	/* (lists too long for one block are left to kmr_finalize's pass over work items, which covers the whole list space) */
@@ -2052,9 +2066,9 @@ template <int W> int count_prefix_superkmer_t(kmr_handle *h, uint32_t min_depth,
 	rc = zero_work_counter(h); if (rc) return rc;
 	const uint64_t n_work = hi > lg.list_first ? (hi - lg.list_first + lg.list_stride - 1) / lg.list_stride : 0;
 	if (n_work) {
-		const int grid = (int)std::min<uint64_t>((uint64_t)num_cus(h) * 4, (n_work + SK_LBATCH) / SK_LBATCH);
 		SkCountLaunch<W> k;
 		rc = sk_count_select<W>(h, false, false, uni, false, out, lg, k); if (rc) return rc;
+		const int grid = (int)std::min<uint64_t>((uint64_t)num_cus(h) * k.blocks, (n_work + SK_LBATCH) / SK_LBATCH);
 		TimeSpan t(h, KMR_TIME_COUNT);
 		rc = sk_count_launch<W>(h, k, grid, ls, lc, hi, out, f, tv, lg);
 		t.end();
@@ -2271,6 +2285,7 @@ int kmr_tune(kmr_handle *h, const char *knob, double value) {
 	else if (k == "long_list_chunks") h->tune.long_list_chunks = value < 2 ? 2 : (uint64_t)value;
 	else if (k == "lean_extract") h->tune.no_lean_extract = value == 0;
 	else if (k == "uniform_count") h->tune.no_uniform_count = value == 0;
+	else if (k == "count_blocks") { if (value != 0 && value != 4 && value != 5) return fail(h, KMR_ERR_INVALID_ARG, "count_blocks is 0 (default), 4 or 5"); h->tune.count_blocks = (int)value; }
 	else if (k == "packed_direct") h->tune.no_packed_direct = value == 0;
 	else if (k == "pow2_lists") h->tune.pow2_lists = value != 0;
 	else if (k == "list_aim") h->tune.list_aim = value >= 1 ? (uint64_t)value : 0;
@@ -2316,6 +2331,7 @@ int kmr_build_info(kmr_handle *h, const char *what, double *value) {
 	const std::string k(what);
 	if (k == "lists") *value = h->sk_state ? (double)sk_list_count(h->sk_bits) : 0.0;
 	else if (k == "uniform_count") *value = h->last_count_uniform ? 1.0 : 0.0;
+	else if (k == "count_blocks") *value = (double)h->last_count_blocks;
 	else if (k == "chunk_pool_chunks") *value = (double)h->l1.cap;
 	else if (k == "superkmer_window") *value = (double)h->sk_win;
 	else if (k == "early_lists") *value = (double)h->last_early_hi;

@@ -182,6 +182,7 @@ struct KMR_HIDDEN Tuning {
 	bool pow2_lists = false;           /* the list count of build_mode 3 always a power of two (A/B runs, tests of both list functions) */
 	bool no_packed_direct = false;     /* kmr_add_reads_twobit* always unpack to text first (A/B runs, tests of the unpack path) */
 	bool no_uniform_count = false;     /* never take sk_count_kernel<.., UNI> (A/B runs, tests of the general count pass on one-weight builds) */
+	int count_blocks = 0;              /* blocks per CU of the one-weight, one-word count pass over lists: 4, 5, or 0 = the default choice (sk_count_blocks; A/B runs, tests of both instances) */
 	bool no_lean_extract = false;      /* never take sk_extract_lean_kernel (A/B runs, tests of the general kernel on uniform qualities) */
 	bool exchange_fail_once = false;   /* tests: the next kmr_exchange_add_reads_dev of this rank fails locally (the other ranks must come back with an error, not hang) */
 	uint64_t dump_piece_bytes = 0;     /* kmr_dump_mercount / kmr_dump_mergraph: staging bound of one piece of the file (0 = KMR_DUMP_PIECE_BYTES) */
@@ -281,6 +282,7 @@ struct KMR_HIDDEN kmr_handle : HandleMem, BuildMem, ExchangeMem {
 	uint64_t unit_batches = 0;         /* batches that held a read longer than a tile and were cut into work units (kmr_build_info "unit_batches") */
 	int last_match_attempts = 0;       /* how often the last kmr_match_add_read_batch streamed its batch before the hit records fit (kmr_build_info "match_add_attempts") */
 	int last_extend_runs = 0; double last_extend_ms[5] = {0, 0, 0, 0, 0};      /* the last kmr_extend_contigs*: its runs of whole contigs (kmr_build_info "extend_runs") and, with kmr_tune "extend_timing", the HIP-event times of gather, extraction, sort, reduce and walk */
+	int last_count_blocks = 0;      /* blocks per CU the last launch of the count pass over super-k-mer lists was compiled and sized for (kmr_build_info "count_blocks") */
 	int last_count_attempts = 0;    /* how often the last count pass of a kmr_finalize ran before its entries fit (kmr_build_info "count_attempts") */
 	bool qual_mixed = false;           /* a build that has seen two different quality characters stops asking (qrange) */
 	/* exchange with world_size > 1: sk_bits are the COARSE lists reads are scattered into and that travel; each holds 2^sk_fine_shift

@@ -1594,12 +1594,26 @@ static const unsigned long long SK_OSLAB = 2048;      /* entries a wavefront res
  * extraction with the same quality character, or with none): the weight sum of a slot is its count times that weight -- exact in
  * f64, count * w needs 24 + 20 bits -- so the table takes no ds_add_f64, no weight is read or converted per k-mer, and the weight
  * part of the first-sighting word is a constant of the launch (a sixth of the inner loop's vector instructions). */
-template <int W, int LOG2S, bool TRACK = false, bool EXT = false, bool UNI = false, bool ITEM = false>
-__global__ __launch_bounds__(SKC_THREADS, EXT ? (W == 1 ? (LOG2S <= 9 ? SK_EXT_BLOCKS : 2) : 1) : ((W == 1 && LOG2S <= 10 && !TRACK) ? 4 : (W == 2 && LOG2S <= 10 && !TRACK ? (UNI ? 4 : 3) : 1)))
+/* The five-block instance's way to a scalar (BLOCKS == 5; the identity otherwise): v_readfirstlane of a value that every lane of the
+ * wavefront holds alike, see the kernel's opening lines */
+template <int BLOCKS> __device__ __forceinline__ uint32_t skc_uni(uint32_t x) { if constexpr (BLOCKS == 5) return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); else return x; }
+template <int BLOCKS> __device__ __forceinline__ unsigned long long skc_uni64(unsigned long long x) { if constexpr (BLOCKS == 5) return ((unsigned long long)skc_uni<5>((uint32_t)(x >> 32)) << 32) | skc_uni<5>((uint32_t)x); else return x; }
+/* lane 0's slab base (the value its device atomic returned) for the whole wavefront: every lane is active where a slab is taken */
+template <int BLOCKS> __device__ __forceinline__ unsigned long long skc_slab_base(unsigned long long g) {
+	if constexpr (BLOCKS == 5) return skc_uni64<5>(g);
+	else return ((unsigned long long)(uint32_t)__shfl((int)(g >> 32), 0, 64) << 32) | (uint32_t)__shfl((int)(uint32_t)g, 0, 64);
+}
+/* BLOCKS: blocks per CU the instance is compiled for (its register budget); 0 = what the form has had all along.  Only the one-weight,
+ * one-word pass over lists exists a second time, for five (96 registers; its 30 560 bytes of LDS fit five times), see sk_count_blocks */
+template <int W, int LOG2S, bool TRACK, bool EXT, bool UNI, bool ITEM>
+__host__ __device__ constexpr int sk_count_default_blocks() { return EXT ? (W == 1 ? (LOG2S <= 9 ? SK_EXT_BLOCKS : 2) : 1) : ((W == 1 && LOG2S <= 10 && !TRACK) ? 4 : (W == 2 && LOG2S <= 10 && !TRACK ? (UNI ? 4 : 3) : 1)); }
+template <int W, int LOG2S, bool TRACK = false, bool EXT = false, bool UNI = false, bool ITEM = false, int BLOCKS = 0>
+__global__ __launch_bounds__(SKC_THREADS, (BLOCKS ? BLOCKS : sk_count_default_blocks<W, LOG2S, TRACK, EXT, UNI, ITEM>()))
 void sk_count_kernel(const uint4 *poolg, const uint64_t *list_start, const uint64_t *list_chunks, uint64_t n_lists, uint32_t k,
                      SkCountHot hot, unsigned int *work_counter, uint32_t dbgFlags, const SkCountArgs<W> *__restrict__ args) {
 	const CountOut &out = args->out; const FinalizeParams &f = args->f; const SkTrackView &tv = args->tv; const SkLong<W> &lg = args->lg;      /* (device memory: read where used) */
 	static_assert(!UNI || (!TRACK && !EXT), "the one-weight count pass is the plain one's");
+	static_assert(BLOCKS == 0 || (BLOCKS == 5 && W == 1 && UNI && !ITEM), "only the one-weight, one-word pass over lists has a five-block instance");
 	constexpr int S = 1 << LOG2S;
 	/* LEAN: the one-weight pass over multi-word keys keeps no state words (the host sends only k with pad bits in the last key word here: the
 	 * claim protocol of SK_KEY_PENDING needs none) and, like every one-weight pass, no weight sums (WSUM: count x weight at emit) -- W = 2:
@@ -1636,7 +1650,12 @@ void sk_count_kernel(const uint4 *poolg, const uint64_t *list_start, const uint6
 	__shared__ unsigned long long s_c0[SK_LBATCH + 1], s_c1[SK_LBATCH + 1];      /* chunk range of every list (work item) of the batch */
 	__shared__ uint32_t s_dchunk[SK_DESC_CAP];
 	__shared__ uint8_t s_dcount[SK_DESC_CAP];
-	const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+	/* What every lane of a wavefront reads alike out of LDS or computes alike from its thread number -- the batch's first list, a list's chunk
+	 * range, the overflow flags, a chunk's descriptor, the wavefront's number -- is a per-lane value to the compiler, and so is everything
+	 * that a branch on it carries across: the slab cursors, the kept counters, the prefetch's bookkeeping, sixteen vector registers and
+	 * more that the 96 of a five-block instance do not have.  That instance takes such values through v_readfirstlane (all lanes are
+	 * active wherever it does); the other instances keep their code and their register allocation as they are. */
+	const int t = threadIdx.x, lane = t & 63, wv = (int)skc_uni<BLOCKS>((uint32_t)(t >> 6));
 	if (TRACK) for (int i = t; i < 2 * (int)(SK_TRACK_MAX + 1); i += SKC_THREADS) trkU[i] = 0;
 	const uint32_t vw = EXT ? 15 : 3;
 	/* wave-uniform counters (scalars, not a 64-bit vector register pair each): used slots and slots with a count of one, kept entries --
@@ -1662,7 +1681,7 @@ void sk_count_kernel(const uint4 *poolg, const uint64_t *list_start, const uint6
 	for (;;) {
 		if (t == 0) s_list = atomicAdd(work_counter, grab);
 		lds_barrier();
-		const uint64_t lfirst = s_list;
+		const uint64_t lfirst = skc_uni<BLOCKS>(s_list);
 		const uint64_t stride = lg.list_stride ? lg.list_stride : 1u;
 		const uint64_t n_work = itemMode ? lg.n_items : (n_lists > lg.list_first ? (n_lists - lg.list_first + stride - 1) / stride : 0);
 		if (lfirst >= n_work) break;
@@ -1677,7 +1696,7 @@ void sk_count_kernel(const uint4 *poolg, const uint64_t *list_start, const uint6
 		/* the batch's chunk descriptors are contiguous in list_chunks: the first SK_DESC_CAP of them wait in LDS, so that a chunk can be
 		 * requested a whole list ahead without a descriptor load in front of it */
 		/* (with a stride the lists in between hold no chunks -- they went to their owners -- so the batch's descriptors are still one run) */
-		const uint64_t dbase = itemMode ? s_c0[0] : list_start[lg.list_first + lfirst * stride], dend = itemMode ? s_c1[0] : list_start[lg.list_first + (lfirst + nl - 1) * stride + 1];
+		const uint64_t dbase = skc_uni64<BLOCKS>(itemMode ? s_c0[0] : list_start[lg.list_first + lfirst * stride]), dend = skc_uni64<BLOCKS>(itemMode ? s_c1[0] : list_start[lg.list_first + (lfirst + nl - 1) * stride + 1]);
 		const uint64_t dcached = dend - dbase < (uint64_t)SK_DESC_CAP ? dend - dbase : (uint64_t)SK_DESC_CAP;      /* descriptors [dbase, dbase + dcached) are in LDS (item mode: the first item's) */
 		for (uint64_t i = (uint64_t)t; i < dcached; i += SKC_THREADS) { const uint64_t d = list_chunks[dbase + i]; s_dchunk[i] = (uint32_t)d; s_dcount[i] = (uint8_t)(d >> 32); }
 		lds_barrier();
@@ -1685,6 +1704,7 @@ void sk_count_kernel(const uint4 *poolg, const uint64_t *list_start, const uint6
 		auto describe = [&](uint64_t ci, uint32_t &chunk, uint32_t &count) {
 			if (ci - dbase < dcached) { chunk = s_dchunk[ci - dbase]; count = s_dcount[ci - dbase]; }
 			else { const uint64_t d = list_chunks[ci]; chunk = (uint32_t)d; count = (uint32_t)(d >> 32); }
+			if constexpr (BLOCKS == 5) { chunk = skc_uni<BLOCKS>(chunk); count = skc_uni<BLOCKS>(count); }
 		};
 		auto fetch = [&](uint64_t ci, uint4 &v, uint32_t &count) {
 			uint32_t chunk;
@@ -1693,7 +1713,7 @@ void sk_count_kernel(const uint4 *poolg, const uint64_t *list_start, const uint6
 			if ((uint32_t)lane < count) v = poolg[(size_t)chunk * SK_CHUNK_G + lane];
 		};
 		for (uint32_t lj = 0; lj < nl; lj++) {
-			const uint64_t c0 = s_c0[lj], c1 = s_c1[lj];
+			const uint64_t c0 = skc_uni64<BLOCKS>(s_c0[lj]), c1 = skc_uni64<BLOCKS>(s_c1[lj]);
 			if (c0 == c1) continue;
 			if (itemMode && (__hip_atomic_load(out.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & ERR_TABLE_FULL)) continue;      /* uniform enough: the launch is void anyway */
 			uint32_t fl = gen & 1u;                    /* this list's flags */
@@ -1711,7 +1731,7 @@ void sk_count_kernel(const uint4 *poolg, const uint64_t *list_start, const uint6
 				else if (c0 + wv < c1) fetch(c0 + wv, cur, curCount);
 				bool wantPre = firstPass;      /* this wavefront's first chunk of the next list is requested below, once the current chunk is out of its registers */
 				if (firstPass) preList = ~0ull;
-				for (uint64_t ci = c0 + wv; ci < c1 && !s_overflow[fl] && s_claimed[fl] <= LIMIT; ci += SKC_WAVES) {
+				for (uint64_t ci = c0 + wv; ci < c1 && !skc_uni<BLOCKS>(s_overflow[fl]) && skc_uni<BLOCKS>(s_claimed[fl]) <= LIMIT; ci += SKC_WAVES) {
 					wstage[lane] = cur;
 					uint32_t claimedHere = 0;
 					/* record starts, then the chunk's k-mers dealt evenly over the lanes; the table slot of a lane's next k-mer is read while
@@ -1733,7 +1753,7 @@ void sk_count_kernel(const uint4 *poolg, const uint64_t *list_start, const uint6
 					if (wantNxt) describe(ci + SKC_WAVES, nxtChunk, nxtCount);
 					if (wantPre) {
 						wantPre = false;
-						if (lj + 1 < nl) { const uint64_t n0 = s_c0[lj + 1], n1 = s_c1[lj + 1]; if (n0 + wv < n1) { describe(n0 + wv, preChunk, preCount); havePre = true; preList = lfirst + lj + 1; } }
+						if (lj + 1 < nl) { const uint64_t n0 = skc_uni64<BLOCKS>(s_c0[lj + 1]), n1 = skc_uni64<BLOCKS>(s_c1[lj + 1]); if (n0 + wv < n1) { describe(n0 + wv, preChunk, preCount); havePre = true; preList = lfirst + lj + 1; } }
 					}
 					if (wantNxt && (uint32_t)lane < nxtCount) nxt = poolg[(size_t)nxtChunk * SK_CHUNK_G + lane];
 					if (havePre) { pre = make_uint4(0, 0, 0, 0); if ((uint32_t)lane < preCount) pre = poolg[(size_t)preChunk * SK_CHUNK_G + lane]; }
@@ -1955,7 +1975,7 @@ void sk_count_kernel(const uint4 *poolg, const uint64_t *list_start, const uint6
 					sk_wave_lds_order();
 					cur = nxt; curCount = nxtCount;
 				}
-				if (wantPre && lj + 1 < nl) { const uint64_t n0 = s_c0[lj + 1], n1 = s_c1[lj + 1]; if (n0 + wv < n1) { fetch(n0 + wv, pre, preCount); preList = lfirst + lj + 1; } }      /* (no chunk of this list was this wavefront's) */
+				if (wantPre && lj + 1 < nl) { const uint64_t n0 = skc_uni64<BLOCKS>(s_c0[lj + 1]), n1 = skc_uni64<BLOCKS>(s_c1[lj + 1]); if (n0 + wv < n1) { fetch(n0 + wv, pre, preCount); preList = lfirst + lj + 1; } }      /* (no chunk of this list was this wavefront's) */
 			};
 			/* ---- emit: this wavefront's quarter of the table -> entries of its output slabs (or the merge table / the size tracker's
 			 * difference arrays), every slot cleared behind it */
@@ -2044,7 +2064,7 @@ void sk_count_kernel(const uint4 *poolg, const uint64_t *list_start, const uint6
 							for (unsigned long long e = wpos + lane; e < wend && e < hot.wcap; e += 64) { if (PACKED) hot.wout[e * (W + 1) + W] = 0; else hot.wvals[e * vw] = 0; }
 							unsigned long long g = 0;
 							if (lane == 0) g = atomicAdd(hot.wcursor, SK_OSLAB);
-							wpos = ((unsigned long long)(uint32_t)__shfl((int)(g >> 32), 0, 64) << 32) | (uint32_t)__shfl((int)(uint32_t)g, 0, 64);
+							wpos = skc_slab_base<BLOCKS>(g);
 							wend = wpos + SK_OSLAB;
 							if (wend > hot.wcap) { if (lane == 0) atomicOr(out.err, (uint32_t)ERR_ENTRIES_FULL); outFull = true; wend = wpos; }
 						}
@@ -2086,7 +2106,7 @@ void sk_count_kernel(const uint4 *poolg, const uint64_t *list_start, const uint6
 							for (unsigned long long e = spos + lane; e < send && e < out.scap; e += 64) out.sweight[e] = 0;
 							unsigned long long g = 0;
 							if (lane == 0) g = atomicAdd(out.scursor, SK_OSLAB);
-							spos = ((unsigned long long)(uint32_t)__shfl((int)(g >> 32), 0, 64) << 32) | (uint32_t)__shfl((int)(uint32_t)g, 0, 64);
+							spos = skc_slab_base<BLOCKS>(g);
 							send = spos + SK_OSLAB;
 							if (send > out.scap) { if (lane == 0) atomicOr(out.err, (uint32_t)ERR_ENTRIES_FULL); outFull = true; send = spos; }
 						}
@@ -2124,7 +2144,7 @@ void sk_count_kernel(const uint4 *poolg, const uint64_t *list_start, const uint6
 
 			insert_pass(0, 0, true);
 			lds_barrier();                                                   /* A: every insert of the list is in the table */
-			const bool ovf = s_overflow[fl] != 0 || s_claimed[fl] > LIMIT;
+			const bool ovf = skc_uni<BLOCKS>(s_overflow[fl]) != 0 || skc_uni<BLOCKS>(s_claimed[fl]) > LIMIT;
 			if (t == 0) { s_claimed[fl ^ 1u] = 0; s_overflow[fl ^ 1u] = 0; }      /* the other pair: last read before the barrier B of the list before, next raised after this list's */
 			if (!ovf) {
 				emit_pass();
@@ -2135,14 +2155,14 @@ void sk_count_kernel(const uint4 *poolg, const uint64_t *list_start, const uint6
 			clear_table();
 			if (t == 0) { s_sp = 2; s_stackBits[0] = 1; s_stackVal[0] = 0; s_stackBits[1] = 1; s_stackVal[1] = 1; }
 			lds_barrier();
-			while (s_sp > 0) {
-				const uint32_t bits = s_stackBits[s_sp - 1], val = s_stackVal[s_sp - 1];
+			while (skc_uni<BLOCKS>(s_sp) > 0) {
+				const uint32_t bits = skc_uni<BLOCKS>(s_stackBits[s_sp - 1]), val = skc_uni<BLOCKS>(s_stackVal[s_sp - 1]);
 				lds_barrier();
 				if (t == 0) { s_sp--; s_claimed[fl] = 0; s_overflow[fl] = 0; }
 				lds_barrier();
 				insert_pass(bits, val, false);
 				lds_barrier();
-				if (s_overflow[fl] || s_claimed[fl] > LIMIT) {       /* split this sub-pass in two by one more hash bit */
+				if (skc_uni<BLOCKS>(s_overflow[fl]) || skc_uni<BLOCKS>(s_claimed[fl]) > LIMIT) {       /* split this sub-pass in two by one more hash bit */
 					lds_barrier();
 					clear_table();
 					if (t == 0) {
