@@ -1411,6 +1411,10 @@ void *kmr_stream(kmr_handle *h);
  *   "count_blocks" (blocks per compute unit of the one-weight count pass over lists of one-word keys: 4, 5 -- its instance compiled for
  *   96 registers -- or 0, the default choice; every other form of the count pass runs as before whatever this says; anything else is
  *   KMR_ERR_INVALID_ARG; see kmr_build_info "count_blocks"; may be set at any time),
+ *   "count_six" (the six-block instance of that pass -- table slots of 20 bytes, whose first-sighting word holds a 32-bit ordinal relative
+ *   to the build's lowest -- where "count_blocks" is 0: 0 = the default: taken when every record was stamped by this handle's own
+ *   kmr_add_reads* calls, their stream ordinals span less than 2^31 and the build has at least compute units x 6 x 24 lists; 1 = taken
+ *   wherever the ordinals allow it, whatever the list count; 2 = never; anything else is KMR_ERR_INVALID_ARG; may be set at any time),
  *   "superkmer_window" (the widest minimizer window build_mode 3 may take: 32 (k >= 45) / 16 / 8 / 4).
  *   "early_entry_share" (>= 0: kmr_count_lists_prefix's entry buffers hold that share of the good k-mers + 16 384 entries; < 0 = from the
  *   list share, the default), "saturated_batch_bytes" (scratch budget of one batch of kmr_finalize's ordered pass over k-mers seen 256
@@ -1448,7 +1452,7 @@ int kmr_tune(kmr_handle *h, const char *knob, double value);
 /* What the current build decided, for tests and measurement tools (the reference logs such figures, LOG_VERBOSE): "lists" = super-k-mer
  * lists of the build (0 before the first reads, or in another build mode), "uniform_count" = 1 if the last kmr_finalize ran the
  * count pass's one-weight form, "count_blocks" = blocks per compute unit the last launch of the count pass over lists (kmr_finalize or
- * kmr_count_lists_prefix) was sized for: 5 where kmr_tune "count_blocks" or the default chose the five-block instance, else 4, "chunk_pool_chunks" = 1 KB chunks the pool holds, "superkmer_window" = the minimizer window in use, "early_lists" / "early_entries" = the bound below which the last
+ * kmr_count_lists_prefix) was sized for: 5 or 6 where kmr_tune "count_blocks" / "count_six" or the default chose the five- or the six-block instance, else 4, "chunk_pool_chunks" = 1 KB chunks the pool holds, "superkmer_window" = the minimizer window in use, "early_lists" / "early_entries" = the bound below which the last
  * kmr_finalize took its lists' entries from kmr_count_lists_prefix (0: it counted everything itself) and how many entries those were,
  * "early_overflowed" = 1 if the last kmr_finalize voided an early count because its buffers had overflowed, "saturated_keys" /
  * "saturated_batches" = the weak entries of count 256 or more the last kmr_finalize of build_mode 3 redid in input order (all of them,

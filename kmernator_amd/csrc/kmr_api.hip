@@ -174,6 +174,7 @@ int sync_state(kmr_handle *h, bool with_pool_head = false) {
 	/* (through the k-mer record exchange: good k-mers are counted where they arrive, bad ones where they were read) */
 	h->stats.raw_kmers = s.raw + s.inserted + s.sender_bad; h->stats.raw_good_kmers = s.good + s.inserted; h->stats.discarded = s.raw - s.good + s.sender_bad;
 	h->occupied = s.claimed; h->pending_kmers = 0; h->subtracted = s.subtracted;
+	h->ord_seen = s.ord_nlo != 0; h->ord_lo = ~s.ord_nlo; h->ord_hi = s.ord_hi;
 	if (e & ERR_READ_TOO_LONG) return fail(h, KMR_ERR_UNSUPPORTED, "a read is longer than the per-wavefront LDS tile (" + std::to_string(TILE_SPAN) + " bases)");
 	if (e & ERR_TABLE_FULL) return fail(h, KMR_ERR_CAPACITY, "device k-mer table is full; raise kmr_config.max_table_entries / estimated_raw_kmers");
 	if (e & ERR_SEGMENT_OVERFLOW) return fail(h, KMR_ERR_CAPACITY, "an owner segment overflowed seg_capacity");
@@ -1568,6 +1569,10 @@ template <int W> int add_reads_superkmer_t(kmr_handle *h, const ReadsView &rvAll
 	if (!filt && !h->ext && !sp_debug_extract(h)) { rc = sk_uniform_weight(h, rvAll, hints, lean, wK, n <= chunk ? &longest : nullptr, &have_longest); if (rc) return rc; }      /* (extension values want every neighbour's quality: the general kernel) */
 	if (hints.packed && (!lean || h->cfg.size_tracker)) return fail(h, KMR_ERR_STATE, "internal: a packed batch handed to an extraction that wants text");      /* (sk_packed_direct_ok said otherwise) */
 	if (n) sk_note_call_weight(h, lean, wK);
+	if (n) {      /* the ordinals this call stamps, for sk_count_blocks: rv.stream_base (kmr_set_stream_origin, what earlier calls added, less FeedHints' piece origin) + a base's offset */
+		hipLaunchKernelGGL(sk_ord_span_kernel, dim3(1), dim3(64), 0, h->stream, rvAll.offsets, n, rvAll.stream_base, h->dstats.get<DevStats>());
+		HIPCHK(h, hipGetLastError());
+	}
 	if (!h->sk_state) { rc = sk_size_lists<W>(h, std::max<uint64_t>(total_bases, hints.call_bases), lean); if (rc) return rc; }
 	if (tracking) { h->trk_n = 0; rc = h->trk.reserve(h, "trk", n * sizeof(SkTrackRec)); if (rc) return rc; HIPCHK(h, hipMemsetAsync(h->trk.get<SkTrackRec>(), 0, n * sizeof(SkTrackRec), h->stream)); }      /* (sk_track_call) */
 	for (uint64_t r = 0; r < n; r += chunk) {
@@ -1748,28 +1753,42 @@ template <int W> struct SkCountLaunch {
 	int blocks;      /* blocks per CU the grid is sized for */
 };
 /* Blocks per CU a launch of the count pass is sized for: four (every form's grid has been num_cus x 4 all along, whatever its instance is
- * compiled for), or five for the one form that exists as a five-block instance -- one-weight, one-word keys, lists (not work items) --
- * where kmr_tune "count_blocks" asks for it.  The entry buffers' slack follows it (a slab tail per wavefront launched). */
-static const int SK_COUNT_BLOCKS_DEFAULT = 5;      /* what "count_blocks" 0 means for that form: C2's count pass 8.72 -> 7.7 ms (profiles/count_blocks_ab.jsonl) */
-template <int W> int sk_count_blocks(kmr_handle *h, bool ext, bool tracking, bool uni, bool item) {
+ * compiled for), or five or six for the one form that exists as such instances -- one-weight, one-word keys, lists (not work items).
+ * The entry buffers' slack follows it (a slab tail per wavefront launched).  n_lists: the lists the launch goes over.
+ * Six (slots of 20 bytes: a first-sighting word of 32 bits, the ordinal relative to the build's lowest) wants
+ *   - kmr_tune "count_blocks" 0 (an explicit 4 or 5 means that instance) and "count_six" below 2,
+ *   - every record stamped by this handle's own feed calls, so that their lowest and highest ordinal are known (ord_lo, ord_hi: what
+ *     sk_ord_span_kernel collected, as the sync_state at the head of kmr_finalize and of kmr_count_lists_prefix read it; records adopted
+ *     from an exchange carry their senders' ordinals), and highest - lowest < 2^31,
+ *   - enough lists that a sixth block per CU gets a batch of SK_LBATCH of them from the work counter at all ("count_six" 1 waives this). */
+static const int SK_COUNT_BLOCKS_DEFAULT = 5;      /* what "count_blocks" 0 means for that form where six does not apply: C2's count pass 8.72 -> 7.7 ms (profiles/count_blocks_ab.jsonl) */
+static const bool SK_COUNT_SIX_DEFAULT = true;     /* "count_six" 0 takes the six-block instance where the rule allows it (profiles/count_six_ab.jsonl) */
+template <int W> int sk_count_blocks(kmr_handle *h, bool ext, bool tracking, bool uni, bool item, uint64_t n_lists) {
 	if (W != 1 || ext || tracking || !uni || item) return 4;
-	return h->tune.count_blocks ? h->tune.count_blocks : SK_COUNT_BLOCKS_DEFAULT;
+	if (h->tune.count_blocks) return h->tune.count_blocks;
+	const bool ordinals = h->ord_seen && !h->ord_foreign && h->ord_hi >= h->ord_lo && h->ord_hi - h->ord_lo < (1ull << 31);
+	const bool fed = n_lists >= (uint64_t)num_cus(h) * 6 * SK_LBATCH;
+	if (ordinals && (h->tune.count_six == 1 || (h->tune.count_six == 0 && SK_COUNT_SIX_DEFAULT && fed))) return 6;
+	return SK_COUNT_BLOCKS_DEFAULT;
 }
-template <int W, int LOG2S, bool TRACK, bool EXT, bool UNI, bool ITEM, int BLOCKS = 0> SkCountLaunch<W> sk_count_form() { return {sk_count_kernel<W, LOG2S, TRACK, EXT, UNI, ITEM, BLOCKS>, sk_count_smem_bytes<W, LOG2S, TRACK, EXT, UNI>(), BLOCKS ? BLOCKS : 4}; }
+template <int W, int LOG2S, bool TRACK, bool EXT, bool UNI, bool ITEM, int BLOCKS = 0> SkCountLaunch<W> sk_count_form() { return {sk_count_kernel<W, LOG2S, TRACK, EXT, UNI, ITEM, BLOCKS>, sk_count_smem_bytes<W, LOG2S, TRACK, EXT, UNI, BLOCKS == 6>(), BLOCKS ? BLOCKS : 4}; }
 template <int W, bool ITEM> SkCountLaunch<W> sk_count_forms(bool ext, bool tracking, bool uni, int blocks) {
 	if constexpr (!ITEM) { if (tracking && !ext) return sk_count_form<W, COUNT_LOG2S, true, false, false, false>(); }
-	if constexpr (W == 1 && !ITEM) { if (blocks == 5) return sk_count_form<1, COUNT_LOG2S, false, false, true, false, 5>(); }
+	if constexpr (W == 1 && !ITEM) {
+		if (blocks == 5) return sk_count_form<1, COUNT_LOG2S, false, false, true, false, 5>();
+		if (blocks == 6) return sk_count_form<1, COUNT_LOG2S, false, false, true, false, 6>();
+	}
 	return ext ? sk_count_form<W, COUNT_LOG2S_EXT, false, true, false, ITEM>() :
 	    (uni ? sk_count_form<W, COUNT_LOG2S, false, false, true, ITEM>() : sk_count_form<W, COUNT_LOG2S, false, false, false, ITEM>());
 }
 /* The kernel fixes at compile time what a launch used to tell it through null pointers: `item` (the pass over work items of long lists,
  * lg.item_c0 and the merge table) and the form of the weak entries (packed without per-bucket counts unless ext).  An `out` or `lg` of
  * the other form is an internal error here, not a null pointer on the device. */
-template <int W> int sk_count_select(kmr_handle *h, bool ext, bool tracking, bool uni, bool item, const CountOut &out, const SkLong<W> &lg, SkCountLaunch<W> &k) {
+template <int W> int sk_count_select(kmr_handle *h, bool ext, bool tracking, bool uni, bool item, uint64_t n_lists, const CountOut &out, const SkLong<W> &lg, SkCountLaunch<W> &k) {
 	if (item && tracking) return fail(h, KMR_ERR_STATE, "internal: the size tracker's count pass has no long-list items");
 	if (item != (lg.item_c0 != nullptr) || (item && (!lg.item_c1 || !lg.merge.slots || !lg.merge_used))) return fail(h, KMR_ERR_STATE, "internal: count pass and its work items disagree");
 	if (ext ? (!out.wkeys || !out.wvals || !out.weakCount) : !out.wentries) return fail(h, KMR_ERR_STATE, "internal: count pass and its entry buffers disagree");
-	const int blocks = sk_count_blocks<W>(h, ext, tracking, uni, item);
+	const int blocks = sk_count_blocks<W>(h, ext, tracking, uni, item, n_lists);
 	k = item ? sk_count_forms<W, true>(ext, tracking, uni, blocks) : sk_count_forms<W, false>(ext, tracking, uni, blocks);
 	if (k.blocks != blocks) return fail(h, KMR_ERR_STATE, "internal: count pass and its blocks per CU disagree");
 	if (!item) h->last_count_blocks = k.blocks;
@@ -1784,7 +1803,9 @@ template <int W> int sk_count_launch(kmr_handle *h, const SkCountLaunch<W> &k, i
 	SkCountArgs<W> *d = nullptr;
 	int rc = arena_get(h, &d, 1); if (rc) return rc;
 	hipLaunchKernelGGL(sk_count_args_kernel<W>, dim3(1), dim3(64), 0, h->stream, a, d);
-	hipLaunchKernelGGL(k.kern, dim3(grid), dim3(SKC_THREADS), k.smem, h->stream, (const uint4 *)pool_view(h, h->l1).base, ls, lc, nl, h->k, sk_count_hot<W>(a), h->work_counter.get<unsigned int>(), sk_dbg_flags("KMR_SK_COUNT_DBG"), (const SkCountArgs<W> *)d);
+	SkCountHot hot = sk_count_hot<W>(a);
+	if (k.blocks == 6) hot.ord_base = (uint32_t)h->ord_lo;      /* (that instance has no extension values: the word is free) */
+	hipLaunchKernelGGL(k.kern, dim3(grid), dim3(SKC_THREADS), k.smem, h->stream, (const uint4 *)pool_view(h, h->l1).base, ls, lc, nl, h->k, hot, h->work_counter.get<unsigned int>(), sk_dbg_flags("KMR_SK_COUNT_DBG"), (const SkCountArgs<W> *)d);
 	return 0;
 }
 
@@ -1917,7 +1938,7 @@ template <int W> int sk_count_pass(kmr_handle *h, SkFinalize<W> &p) {
 		if (repeated) merge_log2 += 3;
 		int rc = 0;
 		SkCountLaunch<W> k;
-		rc = sk_count_select<W>(h, p.ext, p.tracking, p.uni, false, out, p.lgMain, k); if (rc) return rc;
+		rc = sk_count_select<W>(h, p.ext, p.tracking, p.uni, false, nl, out, p.lgMain, k); if (rc) return rc;
 		const int grid = (int)std::min<uint64_t>((uint64_t)num_cus(h) * k.blocks, (nl / p.lgMain.list_stride + SK_LBATCH) / SK_LBATCH);
 		if (p.tracking) HIPCHK(h, hipMemsetAsync(tv.d_unique, 0, 8 * (tv.n + 1), h->stream));
 		if (dbg()) { int nb = 0; hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)k.kern, SKC_THREADS, k.smem); fprintf(stderr, "sk_count<W=%d>: %d blocks per CU (LDS %zu), %llu lists, %u chunks\n", W, nb, k.smem, (unsigned long long)nl, p.nch); }
@@ -1933,7 +1954,7 @@ template <int W> int sk_count_pass(kmr_handle *h, SkFinalize<W> &p) {
 		lgItems.merge.slots = mslots.get<Slot<W>>(); lgItems.merge.ext = mext.get<ExtSlot>(); lgItems.merge.log2cap = merge_log2;
 		HIPCHK(h, hipMemsetAsync(lgItems.merge_used, 0, 8, h->stream));
 		rc = zero_work_counter(h); if (rc) return rc;
-		rc = sk_count_select<W>(h, p.ext, p.tracking, p.uni, true, out, lgItems, k); if (rc) return rc;
+		rc = sk_count_select<W>(h, p.ext, p.tracking, p.uni, true, n_items, out, lgItems, k); if (rc) return rc;
 		const int grid2 = (int)std::min<uint64_t>((uint64_t)num_cus(h) * k.blocks, n_items);
 		rc = sk_count_launch<W>(h, k, grid2, p.ls, p.lc, nl, out, p.f, tv, lgItems); if (rc) return rc;
 		hipLaunchKernelGGL(sk_merge_emit_kernel<W>, dim3(grid_for(1ull << merge_log2)), dim3(256), 0, h->stream, lgItems.merge, out, p.f);
@@ -1983,7 +2004,7 @@ template <int W> int finalize_superkmer_t(kmr_handle *h, uint32_t min_depth) {
 	/* entry buffers: sequencing data keeps a few per cent of its k-mers as weak entries */
 	rc = sk_count_uniform<W>(h, p.tracking, p.uni, p.f.uni_wbits); if (rc) return rc;
 	h->last_count_uniform = p.uni;
-	rc = count_entry_buffers(h, p, G, sk_entry_slack(h, sk_count_blocks<W>(h, p.ext, p.tracking, p.uni, false)), G / (p.f.has_singletons ? 8 : 3), G / 3, h->sk_exchange && h->cfg.world_size > 1); if (rc) return rc;
+	rc = count_entry_buffers(h, p, G, sk_entry_slack(h, sk_count_blocks<W>(h, p.ext, p.tracking, p.uni, false, p.nl)), G / (p.f.has_singletons ? 8 : 3), G / 3, h->sk_exchange && h->cfg.world_size > 1); if (rc) return rc;
 	if (p.tracking) { rc = sk_track_view(h, p.tv); if (rc) return rc; }
 	p.lgMain = sk_own_lists<W>(h, p.refined);
 	bool device_error = false;
@@ -2044,7 +2065,7 @@ template <int W> int count_prefix_superkmer_t(kmr_handle *h, uint32_t min_depth,
 	const uint64_t G = h->stats.raw_good_kmers;      /* (an owner's lists hold about as many k-mers as its own reads gave: the job's share of one rank) */
 	bool uni = false;
 	if (!h->peer_uni_mixed) { rc = sk_count_uniform<W>(h, false, uni, f.uni_wbits); if (rc) return rc; }      /* (senders that declared mixed weights settle it here without a look at the device pair) */
-	uint64_t want = (uint64_t)((double)G * ((double)hi / (double)nl) / (f.has_singletons ? 6.0 : 2.5)) + sk_entry_slack(h, sk_count_blocks<W>(h, false, false, uni, false));
+	uint64_t want = (uint64_t)((double)G * ((double)hi / (double)nl) / (f.has_singletons ? 6.0 : 2.5)) + sk_entry_slack(h, sk_count_blocks<W>(h, false, false, uni, false, hi));
 	if (h->tune.early_entry_share >= 0) { want = (uint64_t)((double)G * h->tune.early_entry_share) + 16384; h->early.ue.reset(); }      /* kmr_tune "early_entry_share" */
 	rc = h->early.ue.reserve(h, "early count ue", 8ull * (W + 1) * want); if (rc) return rc;
 	rc = h->early.cursor.reserve(h, "early count cursor", 16); if (rc) return rc;
@@ -2067,7 +2088,7 @@ template <int W> int count_prefix_superkmer_t(kmr_handle *h, uint32_t min_depth,
 	const uint64_t n_work = hi > lg.list_first ? (hi - lg.list_first + lg.list_stride - 1) / lg.list_stride : 0;
 	if (n_work) {
 		SkCountLaunch<W> k;
-		rc = sk_count_select<W>(h, false, false, uni, false, out, lg, k); if (rc) return rc;
+		rc = sk_count_select<W>(h, false, false, uni, false, hi, out, lg, k); if (rc) return rc;
 		const int grid = (int)std::min<uint64_t>((uint64_t)num_cus(h) * k.blocks, (n_work + SK_LBATCH) / SK_LBATCH);
 		TimeSpan t(h, KMR_TIME_COUNT);
 		rc = sk_count_launch<W>(h, k, grid, ls, lc, hi, out, f, tv, lg);
@@ -2243,7 +2264,7 @@ int kmr_reset(kmr_handle *h) {
 	HIPCHK(h, hipMemsetAsync(h->dstats.get<DevStats>(), 0, sizeof(DevStats), h->stream));
 	HIPCHK(h, hipMemsetAsync(h->derr.get<uint32_t>(), 0, 4, h->stream));
 	memset(&h->stats, 0, sizeof(h->stats));
-	h->occupied = h->pending_kmers = 0; h->stream_base = 0; h->reads = 0; h->subtracted = 0; h->xc_job_bases = 0; h->xc_bytes_to_peers = 0;
+	h->occupied = h->pending_kmers = 0; h->stream_base = 0; h->reads = 0; h->ord_lo = h->ord_hi = 0; h->ord_seen = h->ord_foreign = false; h->subtracted = 0; h->xc_job_bases = 0; h->xc_bytes_to_peers = 0;
 	h->trk_n = 0; h->trk_elems.clear();
 	h->trk_next = 128; h->trk_raw = h->trk_good = 0; h->trk_bounds.clear(); h->trk_snap_raw.clear(); h->trk_snap_good.clear();
 	h->finalized = false; h->map_gen++; h->has_singletons = h->cfg.separate_singletons != 0;
@@ -2286,6 +2307,7 @@ int kmr_tune(kmr_handle *h, const char *knob, double value) {
 	else if (k == "lean_extract") h->tune.no_lean_extract = value == 0;
 	else if (k == "uniform_count") h->tune.no_uniform_count = value == 0;
 	else if (k == "count_blocks") { if (value != 0 && value != 4 && value != 5) return fail(h, KMR_ERR_INVALID_ARG, "count_blocks is 0 (default), 4 or 5"); h->tune.count_blocks = (int)value; }
+	else if (k == "count_six") { if (value != 0 && value != 1 && value != 2) return fail(h, KMR_ERR_INVALID_ARG, "count_six is 0 (default), 1 (wherever the ordinals allow) or 2 (never)"); h->tune.count_six = (int)value; }
 	else if (k == "packed_direct") h->tune.no_packed_direct = value == 0;
 	else if (k == "pow2_lists") h->tune.pow2_lists = value != 0;
 	else if (k == "list_aim") h->tune.list_aim = value >= 1 ? (uint64_t)value : 0;
@@ -3360,6 +3382,7 @@ int kmr_sk_exchange_adopt_dev(kmr_handle *h, const void *dev_data, const void *d
 	if (n_chunks == 0) return KMR_OK;
 	hipSetDevice(h->device);
 	rc = sk_ensure_state(h); if (rc) return rc;
+	h->ord_foreign = true;      /* records with their senders' ordinals: the build's span is no longer this handle's to know (sk_count_blocks) */
 	const int grid = (int)std::min<uint64_t>((n_chunks + SK_ADOPT_WAVES * SK_ADOPT_GROUP - 1) / (SK_ADOPT_WAVES * SK_ADOPT_GROUP), (uint64_t)num_cus(h) * 8);
 	/* (a received chunk is appended as one piece: at worst every one of them opens a chunk of its own) */
 	rc = pool_reserve(h, h->l1, n_chunks + n_granules / SK_CHUNK_G + (sk_list_count(h->sk_bits) / h->cfg.world_size) + (uint64_t)grid * SK_ADOPT_WAVES * 130 + 64, true); if (rc) return rc;

@@ -182,6 +182,7 @@ struct KMR_HIDDEN Tuning {
 	bool pow2_lists = false;           /* the list count of build_mode 3 always a power of two (A/B runs, tests of both list functions) */
 	bool no_packed_direct = false;     /* kmr_add_reads_twobit* always unpack to text first (A/B runs, tests of the unpack path) */
 	bool no_uniform_count = false;     /* never take sk_count_kernel<.., UNI> (A/B runs, tests of the general count pass on one-weight builds) */
+	int count_six = 0;                 /* the six-block instance of that pass (20-byte slots, sk_count_blocks): 0 = where the build's ordinals allow it and the lists are enough to feed six blocks per CU, 1 = wherever the ordinals allow it, 2 = never (kmr_tune "count_six"; A/B runs, tests) */
 	int count_blocks = 0;              /* blocks per CU of the one-weight, one-word count pass over lists: 4, 5, or 0 = the default choice (sk_count_blocks; A/B runs, tests of both instances) */
 	bool no_lean_extract = false;      /* never take sk_extract_lean_kernel (A/B runs, tests of the general kernel on uniform qualities) */
 	bool exchange_fail_once = false;   /* tests: the next kmr_exchange_add_reads_dev of this rank fails locally (the other ranks must come back with an error, not hang) */
@@ -227,6 +228,10 @@ struct KMR_HIDDEN kmr_handle : HandleMem, BuildMem, ExchangeMem {
 	uint64_t occupied = 0;           /* exact as of the last sync */
 	uint64_t pending_kmers = 0;      /* upper bound of keys added since */
 	uint64_t stream_base = 0, reads = 0;
+	/* build_mode 3: lowest and highest stream ordinal a feed call of this build may have stamped (DevStats' pair as the last sync_state
+	 * read it; ord_seen: there was such a call), and whether records came in that this handle did not stamp (adopted from an
+	 * exchange): sk_count_blocks */
+	uint64_t ord_lo = 0, ord_hi = 0; bool ord_seen = false, ord_foreign = false;
 	uint64_t nb_weak = 0, nb_sing = 0;
 	bool finalized = false, has_singletons = true;
 	kmr_handle *subtract = nullptr;    /* finalized spectrum whose k-mers are skipped (kmr_subtract_reference) */

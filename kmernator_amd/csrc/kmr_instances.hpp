@@ -44,6 +44,8 @@ static const int PD_THREADS = 1024, PD_RPT = 8, PD_LINE = 4;
 #define KMR_SKCI(W, TRACK, EXT, UNI, ITEM) KMR_SKCB(W, TRACK, EXT, UNI, ITEM, 0)
 /* the one-weight pass over lists of one-word keys a second time, compiled for five blocks per CU (kmr_tune "count_blocks") */
 #define KMR_SKC5 KMR_SKCB(1, false, false, true, false, 5)
+/* ... and a third time for six, with 20-byte slots (a 32-bit first-sighting word; kmr_tune "count_six") */
+#define KMR_SKC6 KMR_SKCB(1, false, false, true, false, 6)
 #define KMR_SKCX(W, TRACK, EXT) KMR_SKCI(W, TRACK, EXT, false, false)
 #define KMR_SKL(W) KMR_T __global__ void sk_lookup_kernel<W>(PoolView, const uint64_t *, const uint64_t *, uint64_t, uint32_t, const uint64_t *, const uint64_t *, const uint32_t *, uint32_t *, uint64_t, unsigned int *, const uint64_t *, const uint64_t *, const uint32_t *, uint64_t, uint64_t);
 #define KMR_SKCU(W) KMR_SKCI(W, false, false, true, false)
@@ -73,7 +75,7 @@ static const int PD_THREADS = 1024, PD_RPT = 8, PD_LINE = 4;
 #if defined(KMR_INSTANCES_EXTERN)
 KMR_SKX_W(1) KMR_SKX_W(2) KMR_SKX_W(3) KMR_SKX_W(4)
 KMR_SKX_W32(2) KMR_SKX_W32(3) KMR_SKX_W32(4)
-KMR_SKC_W(1) KMR_SKC_W(2) KMR_SKC_W(3) KMR_SKC_W(4) KMR_SKC5
+KMR_SKC_W(1) KMR_SKC_W(2) KMR_SKC_W(3) KMR_SKC_W(4) KMR_SKC5 KMR_SKC6
 KMR_EX_W(1) KMR_EX_W(2) KMR_EX_W(3) KMR_EX_W(4)
 KMR_PART_W(1) KMR_PART_W(2) KMR_PART_W(3) KMR_PART_W(4)
 KMR_CK(1, true, COUNT_LOG2S, true)
@@ -87,7 +89,7 @@ KMR_SKX_W32(KMR_INST_W)
 #ifdef KMR_INST_SKC
 KMR_SKC_W(KMR_INST_W)
 #if KMR_INST_W == 1
-KMR_SKC5
+KMR_SKC5 KMR_SKC6
 #endif
 #endif
 #ifdef KMR_INST_EX

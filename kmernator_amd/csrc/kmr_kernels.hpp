@@ -95,6 +95,7 @@ struct DevStats {
 	unsigned long long inserted;             /* records received through the owner exchange (holes excluded) */
 	unsigned long long subtracted;           /* occurrences found in the subtracting reference spectrum */
 	unsigned long long sender_bad;           /* sender side of the k-mer record exchange: k-mers of this rank's reads that were not good enough to send */
+	unsigned long long ord_nlo, ord_hi;      /* build_mode 3: the lowest (as its complement: zero = no call yet) and the highest stream ordinal the feed calls of the build could stamp (sk_ord_span_kernel) */
 };
 
 struct DevParams {

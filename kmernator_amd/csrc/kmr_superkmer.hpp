@@ -31,6 +31,7 @@
 #ifndef KMR_SUPERKMER_HPP_
 #define KMR_SUPERKMER_HPP_
 
+#include <type_traits>
 #include "kmr_partition.hpp"
 #include "kmr_buckets.hpp"
 
@@ -169,6 +170,17 @@ __device__ __forceinline__ bool sk_pend_live(uint32_t q) { return (q >> 31) != 0
 #ifndef KMR_INSTANCE_TU
 __global__ void sk_state_init_kernel(unsigned long long *state, uint64_t n) {
 	for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) state[i] = ((unsigned long long)NO_CHUNK << 32) | SK_CHUNK_G;
+}
+#endif
+/* The span of stream ordinals a feed call can stamp its records with -- rv.stream_base + a base's offset, from the call's first offset
+ * to its last (which the host does not know of a device batch: callers hand in absolute offsets beside a stream origin that stays
+ * put) -- folded into the build's pair in DevStats; the host reads it with the statistics (sync_state, sk_count_blocks) */
+#ifndef KMR_INSTANCE_TU
+__global__ void sk_ord_span_kernel(const uint64_t *offsets, uint64_t n_reads, uint64_t stream_base, DevStats *st) {
+	if (blockIdx.x == 0 && threadIdx.x == 0 && offsets[n_reads] > offsets[0]) {
+		atomicMax(&st->ord_nlo, ~(unsigned long long)(stream_base + offsets[0]));
+		atomicMax(&st->ord_hi, (unsigned long long)(stream_base + offsets[n_reads] - 1));
+	}
 }
 #endif
 /* the open chunk of every list gets its fill count (chunks closed by an append already have theirs) */
@@ -1545,11 +1557,14 @@ template <int W> struct SkLong {
 struct SkCountHot {
 	uint64_t *wout;                          /* out.wentries (packed entries) or out.wkeys (extension values: with wvals) */
 	uint32_t *wvals; unsigned long long *wcursor; uint64_t wcap;
-	uint32_t min_depth, has_singletons, uni_wbits, ext_min_q;      /* of FinalizeParams */
+	uint32_t min_depth, has_singletons, uni_wbits;      /* of FinalizeParams */
+	/* one word for two forms that exclude each other: extension values' quality floor (FinalizeParams), or -- the six-block instance --
+	 * the low word of the build's lowest stream ordinal: an ordinal less than 2^31 above it is (uint32_t)ordinal - ord_base to the bit */
+	union { uint32_t ext_min_q; uint32_t ord_base; };
 };
 template <int W> struct SkCountArgs { CountOut out; FinalizeParams f; SkTrackView tv; SkLong<W> lg; };
 template <int W> __host__ inline SkCountHot sk_count_hot(const SkCountArgs<W> &a) {
-	return {a.out.wentries ? a.out.wentries : a.out.wkeys, a.out.wvals, a.out.wcursor, a.out.wcap, a.f.min_depth, a.f.has_singletons, a.f.uni_wbits, a.f.ext_min_q};
+	return {a.out.wentries ? a.out.wentries : a.out.wkeys, a.out.wvals, a.out.wcursor, a.out.wcap, a.f.min_depth, a.f.has_singletons, a.f.uni_wbits, {a.f.ext_min_q}};
 }
 template <int W> __global__ void sk_count_args_kernel(SkCountArgs<W> a, SkCountArgs<W> *dst) { if (threadIdx.x == 0 && blockIdx.x == 0) *dst = a; }
 
@@ -1557,8 +1572,9 @@ template <int W> __global__ void sk_count_args_kernel(SkCountArgs<W> a, SkCountA
  * below 65 536 k-mers (the host cuts longer lists into pieces, SK_EXT_LONG_CHUNKS) -- and the packet of one occurrence, read only
  * when the key ends as a singleton: 60 bytes per slot, two blocks per CU */
 /* (the one-weight pass keeps no weight sums, and over multi-word keys no state words: 24 instead of 32 bytes per slot at W = 1, 32 instead of 44 at W = 2) */
-template <int W, int LOG2S, bool TRACK = false, bool EXT = false, bool UNI = false>
-__host__ __device__ constexpr size_t sk_count_smem_bytes() { return (size_t)(1 << LOG2S) * (8 * W + 24 + (W > 1 ? 4 : 0) - (UNI ? 8 : 0) - (UNI && W > 1 ? 4 : 0) + (TRACK ? 8 : 0) + (EXT ? 28 : 0)) + (size_t)SK_STAGE_G * 16 + 256 + 64 + (TRACK ? 8 * (SK_TRACK_MAX + 1) : 0); }
+/* (FIRST32: the six-block instance's first-sighting word of 32 bits, 20 bytes per slot) */
+template <int W, int LOG2S, bool TRACK = false, bool EXT = false, bool UNI = false, bool FIRST32 = false>
+__host__ __device__ constexpr size_t sk_count_smem_bytes() { return (size_t)(1 << LOG2S) * (8 * W + 24 + (W > 1 ? 4 : 0) - (UNI ? 8 : 0) - (UNI && W > 1 ? 4 : 0) + (TRACK ? 8 : 0) + (EXT ? 28 : 0) - (FIRST32 ? 4 : 0)) + (size_t)SK_STAGE_G * 16 + 256 + 64 + (TRACK ? 8 * (SK_TRACK_MAX + 1) : 0); }
 /* a chunk of extension records holds at most ~6.4 k-mers per granule (n = 128: 21 granules): 128 chunks stay below 65 536 k-mers */
 static const uint64_t SK_EXT_LONG_CHUNKS = 128;
 static const int SK_EXT_BLOCKS = 3;      /* blocks per CU of the count pass with extension values (166 registers; four -- 128 registers, 34 dwords spilled -- ran 11 % slower) */
@@ -1594,17 +1610,32 @@ static const unsigned long long SK_OSLAB = 2048;      /* entries a wavefront res
  * extraction with the same quality character, or with none): the weight sum of a slot is its count times that weight -- exact in
  * f64, count * w needs 24 + 20 bits -- so the table takes no ds_add_f64, no weight is read or converted per k-mer, and the weight
  * part of the first-sighting word is a constant of the launch (a sixth of the inner loop's vector instructions). */
-/* The five-block instance's way to a scalar (BLOCKS == 5; the identity otherwise): v_readfirstlane of a value that every lane of the
+/* The five- and six-block instances' way to a scalar (BLOCKS >= 5; the identity otherwise): v_readfirstlane of a value that every lane of the
  * wavefront holds alike, see the kernel's opening lines */
-template <int BLOCKS> __device__ __forceinline__ uint32_t skc_uni(uint32_t x) { if constexpr (BLOCKS == 5) return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); else return x; }
-template <int BLOCKS> __device__ __forceinline__ unsigned long long skc_uni64(unsigned long long x) { if constexpr (BLOCKS == 5) return ((unsigned long long)skc_uni<5>((uint32_t)(x >> 32)) << 32) | skc_uni<5>((uint32_t)x); else return x; }
+template <int BLOCKS> __device__ __forceinline__ uint32_t skc_uni(uint32_t x) { if constexpr (BLOCKS >= 5) return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); else return x; }
+template <int BLOCKS> __device__ __forceinline__ unsigned long long skc_uni64(unsigned long long x) { if constexpr (BLOCKS >= 5) return ((unsigned long long)skc_uni<5>((uint32_t)(x >> 32)) << 32) | skc_uni<5>((uint32_t)x); else return x; }
 /* lane 0's slab base (the value its device atomic returned) for the whole wavefront: every lane is active where a slab is taken */
 template <int BLOCKS> __device__ __forceinline__ unsigned long long skc_slab_base(unsigned long long g) {
-	if constexpr (BLOCKS == 5) return skc_uni64<5>(g);
+	if constexpr (BLOCKS >= 5) return skc_uni64<5>(g);
 	else return ((unsigned long long)(uint32_t)__shfl((int)(g >> 32), 0, 64) << 32) | (uint32_t)__shfl((int)(uint32_t)g, 0, 64);
 }
+/* The six-block instance's first-sighting word (F32): 32 bits, (ordinal - lowest ordinal of the build) << 1 | forward, kept by
+ * ds_min_u32 -- the weight bits of the 64-bit word are a constant of a one-weight launch (uniFirst), and a build whose ordinals span
+ * less than 2^31 has 31 bits of ordinal to order its sightings by.  The array stands where tfirst[] does, half as long. */
+template <bool F32> __device__ __forceinline__ void skc_first_clear(unsigned long long *tfirst, int s) { if constexpr (F32) ((uint32_t *)tfirst)[s] = ~0u; else tfirst[s] = NO_FIRST; }
+template <typename ORD> __device__ __forceinline__ void skc_first_min32(unsigned long long *tfirst, uint32_t s, ORD ord, bool fwd) { atomicMin(&((uint32_t *)tfirst)[s], ((uint32_t)ord << 1) | (fwd ? 1u : 0u)); }
+/* a slot's first sighting as emit reads it (first_forward, first_weight_shift): strand and weight bits of the 64-bit word, rebuilt;
+ * its ordinal, the build's lowest + (word >> 1), is wanted by nobody here (no size tracker, no merge table in that instance) */
+/* A thread's number taken afresh where a rarely run stretch uses it (BLOCKS == 6; the identity otherwise): the compiler otherwise keeps
+ * what such a stretch derives from it -- the addresses of clear_table(), of a batch's set-up, of the slabs' tails -- in registers across
+ * the whole kernel, a dozen of the 80 a six-block wavefront has, and spills what the step loop needs */
+template <int BLOCKS> __device__ __forceinline__ int skc_afresh(int x) { if constexpr (BLOCKS == 6) asm volatile("" : "+v"(x)); return x; }
+__device__ __forceinline__ unsigned long long skc_first_word32(const unsigned long long *tfirst, int s, uint32_t uniFirst) {
+	return ((unsigned long long)(((const uint32_t *)tfirst)[s] & 1u) << 23) | (unsigned long long)uniFirst;
+}
 /* BLOCKS: blocks per CU the instance is compiled for (its register budget); 0 = what the form has had all along.  Only the one-weight,
- * one-word pass over lists exists a second time, for five (96 registers; its 30 560 bytes of LDS fit five times), see sk_count_blocks */
+ * one-word pass over lists exists again, for five (96 registers; its 30 560 bytes of LDS fit five times) and for six (80 registers;
+ * 20-byte slots, 26 464 bytes), see sk_count_blocks */
 template <int W, int LOG2S, bool TRACK, bool EXT, bool UNI, bool ITEM>
 __host__ __device__ constexpr int sk_count_default_blocks() { return EXT ? (W == 1 ? (LOG2S <= 9 ? SK_EXT_BLOCKS : 2) : 1) : ((W == 1 && LOG2S <= 10 && !TRACK) ? 4 : (W == 2 && LOG2S <= 10 && !TRACK ? (UNI ? 4 : 3) : 1)); }
 template <int W, int LOG2S, bool TRACK = false, bool EXT = false, bool UNI = false, bool ITEM = false, int BLOCKS = 0>
@@ -1613,7 +1644,10 @@ void sk_count_kernel(const uint4 *poolg, const uint64_t *list_start, const uint6
                      SkCountHot hot, unsigned int *work_counter, uint32_t dbgFlags, const SkCountArgs<W> *__restrict__ args) {
 	const CountOut &out = args->out; const FinalizeParams &f = args->f; const SkTrackView &tv = args->tv; const SkLong<W> &lg = args->lg;      /* (device memory: read where used) */
 	static_assert(!UNI || (!TRACK && !EXT), "the one-weight count pass is the plain one's");
-	static_assert(BLOCKS == 0 || (BLOCKS == 5 && W == 1 && UNI && !ITEM), "only the one-weight, one-word pass over lists has a five-block instance");
+	static_assert(BLOCKS == 0 || ((BLOCKS == 5 || BLOCKS == 6) && W == 1 && UNI && !ITEM), "only the one-weight, one-word pass over lists has a five- and a six-block instance");
+	constexpr bool F32 = BLOCKS == 6;      /* 32-bit first-sighting words, skc_first_min32 */
+	constexpr bool XPRE = BLOCKS != 6;     /* a wavefront's first chunk of the next list is requested a list ahead */
+	using Ord = std::conditional_t<F32, uint32_t, uint64_t>;      /* a k-mer's stream ordinal: relative to the build's lowest in 32 bits, or whole */
 	constexpr int S = 1 << LOG2S;
 	/* LEAN: the one-weight pass over multi-word keys keeps no state words (the host sends only k with pad bits in the last key word here: the
 	 * claim protocol of SK_KEY_PENDING needs none) and, like every one-weight pass, no weight sums (WSUM: count x weight at emit) -- W = 2:
@@ -1635,7 +1669,7 @@ void sk_count_kernel(const uint4 *poolg, const uint64_t *list_start, const uint6
 	unsigned long long *tcnt = (unsigned long long *)(tkeys + (size_t)S * W);
 	double *twsum = (double *)(tcnt + S);
 	unsigned long long *tfirst = (unsigned long long *)(twsum + (WSUM ? S : 0));
-	uint32_t *tstate = (uint32_t *)(tfirst + S);                       /* W > 1 only, and not LEAN */
+	uint32_t *tstate = F32 ? (uint32_t *)tfirst + S : (uint32_t *)(tfirst + S);                       /* W > 1 only, and not LEAN */
 	uint32_t *ttally = tstate + (W > 1 && !LEAN ? S : 0);                       /* EXT only: [S][6] tallies (left A C | G T | N X, right A C | G T | N X as 16-bit halves), [S] packets */
 	uint32_t *tpkt = ttally + (EXT ? 6 * S : 0);
 	uint4 *stage = (uint4 *)(tpkt + (EXT ? S : 0));                    /* 16-byte aligned: every table array is a multiple of 16 bytes */
@@ -1665,7 +1699,7 @@ void sk_count_kernel(const uint4 *poolg, const uint64_t *list_start, const uint6
 	unsigned long long wpos = 0, wend = 0, spos = 0, send = 0;
 	bool outFull = false;
 	if (t == 0) { s_claimed[0] = s_claimed[1] = 0; s_overflow[0] = s_overflow[1] = 0; s_sp = 0; s_sat[0] = s_sat[1] = 0; }
-	for (int i = t; i < S; i += SKC_THREADS) { tkeys[(size_t)i * W] = EMPTY_KEY; if (W > 1) tkeys[(size_t)i * W + W - 1] = SK_KEY_PENDING; tcnt[i] = 0; if constexpr (WSUM) twsum[i] = 0.0; tfirst[i] = NO_FIRST; if constexpr (W > 1 && !LEAN) tstate[i] = 0; if (TRACK) tsecond[i] = NO_FIRST; }
+	for (int i = skc_afresh<BLOCKS>(t); i < S; i += SKC_THREADS) { tkeys[(size_t)i * W] = EMPTY_KEY; if (W > 1) tkeys[(size_t)i * W + W - 1] = SK_KEY_PENDING; tcnt[i] = 0; if constexpr (WSUM) twsum[i] = 0.0; skc_first_clear<F32>(tfirst, i); if constexpr (W > 1 && !LEAN) tstate[i] = 0; if (TRACK) tsecond[i] = NO_FIRST; }
 	if (EXT) for (int i = t; i < 6 * S; i += SKC_THREADS) ttally[i] = 0;
 	lds_barrier();
 	/* classify() of kmr_kernels.hpp folded into launch-wide scalars: a count of one goes to class singC when singletons are separate,
@@ -1687,10 +1721,11 @@ void sk_count_kernel(const uint4 *poolg, const uint64_t *list_start, const uint6
 		if (lfirst >= n_work) break;
 		const uint32_t nl = (uint32_t)(n_work - lfirst < (uint64_t)grab ? n_work - lfirst : (uint64_t)grab);
 		if ((uint32_t)t < nl) {
+			const int tb = skc_afresh<BLOCKS>(t);
 			uint64_t a, b;
-			if (itemMode) { a = lg.item_c0[lfirst + t]; b = lg.item_c1[lfirst + t]; }
-			else { const uint64_t l = lg.list_first + (lfirst + t) * stride; a = list_start[l]; b = list_start[l + 1]; if (lg.long_threshold && b - a > lg.long_threshold) b = a; }      /* a long list: the second launch's */
-			s_c0[t] = a; s_c1[t] = b;
+			if (itemMode) { a = lg.item_c0[lfirst + tb]; b = lg.item_c1[lfirst + tb]; }
+			else { const uint64_t l = lg.list_first + (lfirst + tb) * stride; a = list_start[l]; b = list_start[l + 1]; if (lg.long_threshold && b - a > lg.long_threshold) b = a; }      /* a long list: the second launch's */
+			s_c0[tb] = a; s_c1[tb] = b;
 		}
 		lds_barrier();
 		/* the batch's chunk descriptors are contiguous in list_chunks: the first SK_DESC_CAP of them wait in LDS, so that a chunk can be
@@ -1698,13 +1733,13 @@ void sk_count_kernel(const uint4 *poolg, const uint64_t *list_start, const uint6
 		/* (with a stride the lists in between hold no chunks -- they went to their owners -- so the batch's descriptors are still one run) */
 		const uint64_t dbase = skc_uni64<BLOCKS>(itemMode ? s_c0[0] : list_start[lg.list_first + lfirst * stride]), dend = skc_uni64<BLOCKS>(itemMode ? s_c1[0] : list_start[lg.list_first + (lfirst + nl - 1) * stride + 1]);
 		const uint64_t dcached = dend - dbase < (uint64_t)SK_DESC_CAP ? dend - dbase : (uint64_t)SK_DESC_CAP;      /* descriptors [dbase, dbase + dcached) are in LDS (item mode: the first item's) */
-		for (uint64_t i = (uint64_t)t; i < dcached; i += SKC_THREADS) { const uint64_t d = list_chunks[dbase + i]; s_dchunk[i] = (uint32_t)d; s_dcount[i] = (uint8_t)(d >> 32); }
+		for (uint64_t i = (uint64_t)skc_afresh<BLOCKS>(t); i < dcached; i += SKC_THREADS) { const uint64_t d = list_chunks[dbase + i]; s_dchunk[i] = (uint32_t)d; s_dcount[i] = (uint8_t)(d >> 32); }
 		lds_barrier();
 		/* this wavefront's chunk ci: granule `lane` of it (zeros past its fill count) and the fill count */
 		auto describe = [&](uint64_t ci, uint32_t &chunk, uint32_t &count) {
 			if (ci - dbase < dcached) { chunk = s_dchunk[ci - dbase]; count = s_dcount[ci - dbase]; }
 			else { const uint64_t d = list_chunks[ci]; chunk = (uint32_t)d; count = (uint32_t)(d >> 32); }
-			if constexpr (BLOCKS == 5) { chunk = skc_uni<BLOCKS>(chunk); count = skc_uni<BLOCKS>(count); }
+			if constexpr (BLOCKS >= 5) { chunk = skc_uni<BLOCKS>(chunk); count = skc_uni<BLOCKS>(count); }
 		};
 		auto fetch = [&](uint64_t ci, uint4 &v, uint32_t &count) {
 			uint32_t chunk;
@@ -1729,7 +1764,7 @@ void sk_count_kernel(const uint4 *poolg, const uint64_t *list_start, const uint6
 				uint4 cur = make_uint4(0, 0, 0, 0); uint32_t curCount = 0;
 				if (firstPass && preList == lfirst + lj) { cur = pre; curCount = preCount; }        /* requested while the list before was counted */
 				else if (c0 + wv < c1) fetch(c0 + wv, cur, curCount);
-				bool wantPre = firstPass;      /* this wavefront's first chunk of the next list is requested below, once the current chunk is out of its registers */
+				bool wantPre = firstPass && XPRE;      /* this wavefront's first chunk of the next list is requested below, once the current chunk is out of its registers */
 				if (firstPass) preList = ~0ull;
 				for (uint64_t ci = c0 + wv; ci < c1 && !skc_uni<BLOCKS>(s_overflow[fl]) && skc_uni<BLOCKS>(s_claimed[fl]) <= LIMIT; ci += SKC_WAVES) {
 					wstage[lane] = cur;
@@ -1758,12 +1793,13 @@ void sk_count_kernel(const uint4 *poolg, const uint64_t *list_start, const uint6
 					if (wantNxt && (uint32_t)lane < nxtCount) nxt = poolg[(size_t)nxtChunk * SK_CHUNK_G + lane];
 					if (havePre) { pre = make_uint4(0, 0, 0, 0); if ((uint32_t)lane < preCount) pre = poolg[(size_t)preChunk * SK_CHUNK_G + lane]; }
 					/* the record the lane is in: its k-mer count, weights, first ordinal */
-					uint32_t n = 0; const uint32_t *ww = nullptr; bool uniformW = true; uint64_t ord0 = 0;
+					uint32_t n = 0; const uint32_t *ww = nullptr; bool uniformW = true; Ord ord0 = 0;
 					const uint8_t *xq = nullptr;      /* EXT: the record's neighbour qualities */
 					uint32_t leftCarry = 0;           /* EXT: the base left of the next k-mer to be made, when it is a base of the same record */
 					auto enter_record = [&]() {      /* header in hx, hy, hw */
 						const SkRec rec = sk_enter_record(wstage, rs, hx, hy, k);
-						n = rec.n; ww = rec.weights; uniformW = rec.uniform; ord0 = rec.ord0;
+						n = rec.n; ww = rec.weights; uniformW = rec.uniform;
+						if constexpr (F32) ord0 = (uint32_t)rec.ord0 - hot.ord_base; else ord0 = rec.ord0;
 						if (EXT) xq = (const uint8_t *)(ww + (uniformW ? 0u : 4u * ((n + 3) / 4)));
 					};
 					/* The bases of the k-mers a lane expands lie in REGISTERS: a window of 2 W + 2 dwords of its record's packed bases, the
@@ -1782,7 +1818,7 @@ void sk_count_kernel(const uint4 *poolg, const uint64_t *list_start, const uint6
 					/* a k-mer on its way to the table: canonical key, strand, home slot and probe step, weight, stream ordinal.  Two of them
 					 * exist per lane -- the one being inserted and the one being made -- and the loop below alternates their roles instead of
 					 * copying one into the other every step (the copies were a quarter of the loop's vector instructions) */
-					struct KState { Key<W> key; bool fwd, mine; uint32_t slot, step, w; uint64_t ord; uint32_t x; };      /* x (EXT): left code | right code << 8 | left quality << 16 | right quality << 24, as the canonical strand sees them */
+					struct KState { Key<W> key; bool fwd, mine; uint32_t slot, step, w; Ord ord; uint32_t x; };      /* x (EXT): left code | right code << 8 | left quality << 16 | right quality << 24, as the canonical strand sees them */
 					KState kA, kB;
 #pragma unroll
 					for (int wi = 0; wi < W; wi++) { kA.key.w[wi] = 0; kB.key.w[wi] = 0; }
@@ -1952,12 +1988,15 @@ void sk_count_kernel(const uint4 *poolg, const uint64_t *list_start, const uint6
 								else {
 									atomicAdd(&tcnt[s], 1ull | ((unsigned long long)(cur.fwd ? 1 : 0) << 32));
 									if constexpr (!UNI) atomicAdd(&twsum[s], (double)wa);
-									const unsigned long long fp = UNI ? (((unsigned long long)cur.ord << FIRST_ORD_SHIFT) | ((unsigned long long)(cur.fwd ? 1u : 0u) << 23) | (unsigned long long)uniFirst) : first_pack(cur.ord, cur.fwd, wa);
-									if (TRACK) {      /* the two smallest: whichever of (old first, this one) is larger is a candidate for second */
-										const unsigned long long was = atomicMin(&tfirst[s], fp);
-										const unsigned long long cand = was > fp ? was : fp;
-										if (cand != NO_FIRST) atomicMin(&tsecond[s], cand);
-									} else atomicMin(&tfirst[s], fp);
+									if constexpr (F32) skc_first_min32(tfirst, s, cur.ord, cur.fwd);
+									else {
+										const unsigned long long fp = UNI ? (((unsigned long long)cur.ord << FIRST_ORD_SHIFT) | ((unsigned long long)(cur.fwd ? 1u : 0u) << 23) | (unsigned long long)uniFirst) : first_pack(cur.ord, cur.fwd, wa);
+										if (TRACK) {      /* the two smallest: whichever of (old first, this one) is larger is a candidate for second */
+											const unsigned long long was = atomicMin(&tfirst[s], fp);
+											const unsigned long long cand = was > fp ? was : fp;
+											if (cand != NO_FIRST) atomicMin(&tsecond[s], cand);
+										} else atomicMin(&tfirst[s], fp);
+									}
 									if constexpr (EXT) {      /* ExtensionTracking::trackExtension (src/KmerTrackingData.h:195-201) */
 										const uint32_t lc = cur.x & 0xffu, rc = (cur.x >> 8) & 0xffu, lq = (cur.x >> 16) & 0xffu, rq = cur.x >> 24;
 										if (lq >= hot.ext_min_q || lc > 3u) atomicAdd(&ttally[(size_t)s * 6 + (lc >> 1)], 1u << (16 * (lc & 1u)));
@@ -2015,7 +2054,8 @@ void sk_count_kernel(const uint4 *poolg, const uint64_t *list_start, const uint6
 					Key<W> key;
 #pragma unroll
 					for (int q = 0; q < W; q++) key.w[q] = used ? tkeys[(size_t)s * W + q] : 0ull;
-					const unsigned long long fst = used ? tfirst[s] : NO_FIRST;
+					unsigned long long fst = NO_FIRST;
+					if constexpr (F32) { if (used) fst = skc_first_word32(tfirst, s, uniFirst); } else fst = used ? tfirst[s] : NO_FIRST;
 					const double wsum = UNI ? (double)count * (double)__uint_as_float(hot.uni_wbits) : (used ? twsum[s] : 0.0);
 					if (TRACK && used) {
 						/* the key counts as seen from the first boundary behind its first sighting on, and as a singleton until the
@@ -2129,7 +2169,7 @@ void sk_count_kernel(const uint4 *poolg, const uint64_t *list_start, const uint6
 				for (int i = 0; i < WSLOTS / 64; i++) {
 					const int s = wv * WSLOTS + i * 64 + lane;
 					if ((usedMask[i] >> lane) & 1ull) {
-						tkeys[(size_t)s * W] = EMPTY_KEY; if (W > 1) tkeys[(size_t)s * W + W - 1] = SK_KEY_PENDING; tcnt[s] = 0; if constexpr (WSUM) twsum[s] = 0.0; tfirst[s] = NO_FIRST; if constexpr (W > 1 && !LEAN) tstate[s] = 0; if (TRACK) tsecond[s] = NO_FIRST;
+						tkeys[(size_t)s * W] = EMPTY_KEY; if (W > 1) tkeys[(size_t)s * W + W - 1] = SK_KEY_PENDING; tcnt[s] = 0; if constexpr (WSUM) twsum[s] = 0.0; skc_first_clear<F32>(tfirst, s); if constexpr (W > 1 && !LEAN) tstate[s] = 0; if (TRACK) tsecond[s] = NO_FIRST;
 						if constexpr (EXT) {
 #pragma unroll
 							for (int q = 0; q < 6; q++) ttally[(size_t)s * 6 + q] = 0;
@@ -2138,7 +2178,7 @@ void sk_count_kernel(const uint4 *poolg, const uint64_t *list_start, const uint6
 				}
 			};
 			auto clear_table = [&]() {
-				for (int i = t; i < S; i += SKC_THREADS) { tkeys[(size_t)i * W] = EMPTY_KEY; if (W > 1) tkeys[(size_t)i * W + W - 1] = SK_KEY_PENDING; tcnt[i] = 0; if constexpr (WSUM) twsum[i] = 0.0; tfirst[i] = NO_FIRST; if constexpr (W > 1 && !LEAN) tstate[i] = 0; if (TRACK) tsecond[i] = NO_FIRST; }
+				for (int i = skc_afresh<BLOCKS>(t); i < S; i += SKC_THREADS) { tkeys[(size_t)i * W] = EMPTY_KEY; if (W > 1) tkeys[(size_t)i * W + W - 1] = SK_KEY_PENDING; tcnt[i] = 0; if constexpr (WSUM) twsum[i] = 0.0; skc_first_clear<F32>(tfirst, i); if constexpr (W > 1 && !LEAN) tstate[i] = 0; if (TRACK) tsecond[i] = NO_FIRST; }
 				if (EXT) for (int i = t; i < 6 * S; i += SKC_THREADS) ttally[i] = 0;
 			};
 
@@ -2184,8 +2224,9 @@ void sk_count_kernel(const uint4 *poolg, const uint64_t *list_start, const uint6
 		}
 	}
 	/* the unused tails of this wavefront's slabs are holes */
-	for (unsigned long long e = wpos + lane; e < wend && e < hot.wcap; e += 64) { if (PACKED) hot.wout[e * (W + 1) + W] = 0; else hot.wvals[e * vw] = 0; }
-	for (unsigned long long e = spos + lane; e < send && e < out.scap; e += 64) out.sweight[e] = 0;
+	const int laneT = skc_afresh<BLOCKS>(lane);
+	for (unsigned long long e = wpos + laneT; e < wend && e < hot.wcap; e += 64) { if (PACKED) hot.wout[e * (W + 1) + W] = 0; else hot.wvals[e * vw] = 0; }
+	for (unsigned long long e = spos + laneT; e < send && e < out.scap; e += 64) out.sweight[e] = 0;
 	if (lane == 0) {
 		if (uniqW) atomicAdd(&out.fc->unique, uniqW); if (singleW) atomicAdd(&out.fc->singletons, singleW);
 		if (keptW) atomicAdd(&out.fc->weak_kept, keptW); if (keptS) atomicAdd(&out.fc->sing_kept, keptS);
