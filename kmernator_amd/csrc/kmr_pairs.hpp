@@ -124,7 +124,7 @@ void pairs_parse_kernel(PairsParams P, uint64_t *hash, uint32_t *cn_len, uint8_t
 		} else {
 			rn = (casava && P.store_comment) ? (c0 == '2' ? 2u : 1u) : (slash ? pairs_suffix_num(last) : 0u);
 			if (L > 2 && slash) { cl = L - 1; hv = hprev; } else { cl = L; hv = h; }
-			fl = L ? PAIRS_NAMED : 0u;
+			fl = L ? (uint32_t)PAIRS_NAMED : 0u;
 		}
 		hash[i] = pairs_mix(hv); cn_len[i] = cl; flags[i] = (uint8_t)(rn | fl);
 	}

@@ -2413,6 +2413,9 @@ static int dedup_tables(kmr_handle *h, const DedupTables **out) {
 		double P[256]; quality_table(P, h->cfg.min_quality_score, h->cfg.fastq_start_char);
 		for (int q = 0; q < 256; q++) {      /* Read::getProbabilityBases (src/Sequence.cpp:573-576), ProbabilityBase::observe (:871) */
 			double prob = P[q];
+			/* the table is indexed by the byte a read holds, and from PRINT_REF_QUAL (103) on a byte means "no quality data" at either
+			 * quality base (src/Sequence.cpp:535-536); quality_table counts from the Phred value, which is the same thing at base 33 only */
+			if (q >= 103) prob = 1.0;
 			if (prob < 0.2501) prob = 0.2501;
 			t->prob[q] = prob; t->other[q] = (1.0 - prob) / 3.0;
 		}

@@ -1,5 +1,6 @@
-/* What kmernator_amd/csrc/kmr_dump.hpp needs of the HIP runtime, for a host compiler: tests/cpp/dump_line_test.cpp calls the
- * header's device functions as plain functions, one "lane" at a time.  Not a runtime: the kernels compile and are never launched. */
+/* What kmernator_amd/csrc/kmr_dump.hpp, kmr_pairs.hpp and kmr_dedup.hpp need of the HIP runtime, for a host compiler:
+ * tests/cpp/dump_line_test.cpp and tests/cpp/dedup_key_test.cpp call the headers' device functions, and kernels whose lanes do not
+ * talk to each other, as plain functions: a grid of one block of one thread, a wavefront of one lane.  Not a runtime. */
 #ifndef KMR_TEST_HIP_RUNTIME_STUB_H_
 #define KMR_TEST_HIP_RUNTIME_STUB_H_
 #include <stdint.h>
@@ -18,4 +19,11 @@ inline void __syncthreads() {}
 inline uint32_t atomicOr(uint32_t *p, uint32_t v) { const uint32_t old = *p; *p = old | v; return old; }
 inline unsigned long long atomicAdd(unsigned long long *p, unsigned long long v) { const unsigned long long old = *p; *p = old + v; return old; }
 template <class T> inline T __shfl_down(T, int) { return T(); }      /* a wavefront of one lane: nothing comes from the lanes above */
+template <class T> inline T __shfl_xor(T, int, int) { return T(); }    /* ... nor from any other lane: a wave sum is the lane's own value */
+inline unsigned long long atomicOr(unsigned long long *p, unsigned long long v) { const unsigned long long old = *p; *p = old | v; return old; }
+inline unsigned long long __brevll(unsigned long long x) { unsigned long long r = 0; for (int i = 0; i < 64; i++) r |= ((x >> i) & 1ull) << (63 - i); return r; }
+inline unsigned long long __ballot(int predicate) { return predicate ? 1ull : 0ull; }
+inline int __ffsll(long long x) { return __builtin_ffsll(x); }
+#define __builtin_amdgcn_fence(...) ((void)0)      /* one lane: nothing to order, nobody to wait for */
+#define __builtin_amdgcn_wave_barrier() ((void)0)
 #endif

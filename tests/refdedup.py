@@ -14,43 +14,92 @@ import refpairs
 NONE = refpairs.NONE
 PRINT_REF_QUAL = 103          # src/Sequence.h: qualities from here on mean "no quality data"
 
+# ---- named deviations: every function below takes `deviation` (None, a name or a set of names); each name switches one rule of the
+# restatement to a plausible wrong one, so that tests/test_dedup_cases.py can prove that the directed cases of tests/dedupcases.py
+# notice it.  Without a deviation nothing below changes.
+DEVIATIONS = (
+    "key_window_shifted",                # the window starts a base late
+    "x_before_window_ignored",           # an X in front of start_offset does not make the read too short
+    "n_is_its_own_code",                 # N does not pack as A
+    "last_key_word_ignored",             # the last 64-bit word of the key takes no part in the grouping
+    "canonical_first_word_only",         # mode 2 compares only the first 64-bit word of the forward and the reverse key
+    "canonical_tie_takes_reverse",       # a key equal to its reverse complement counts as flipped
+    "members_not_in_pair_order",         # a group's members in descending pair position
+    "flip_sides_not_swapped",            # a flipped member still gives read 1 to side 1
+    "name_of_unflipped_first_read",      # the consensus is named after read 1 (side 1) / read 2 (side 2) of a flipped first member
+    "low_quality_skips",                 # getProbabilityBases goes on behind a quality below the minimum
+    "no_floor",                          # no 0.2501 floor
+    "ref_qual_not_one",                  # qualities from 103 upward follow the formula
+    "count_is_int",                      # the member count does not wrap as a short
+    "copy_does_not_raise_top",           # the copy inside operator+ leaves `top` alone
+    "set_top_not_strict",                # setTop with <=
+    "tree_not_strict",                   # getBaseQual's tree with >=
+    "get_ignores_best",                  # getA .. getT answer `top` whatever `best` names
+    "qual_rounds",                       # probToQual rounds
+    "forty_from_0_9999_off",             # getQualChar's shortcut to 40 only from 1.0
+    "name_cut_at_blank_only",            # a tab stays in the printed name
+    "count_digits_fixed",                # the member count printed as three digits
+    "groups_in_key_order",               # groups come out in key order, not by first member
+    "cutoff_three",                      # a group needs three members
+    "pair_short_counted_twice",          # a pair with both ends too short counts twice
+)
+# Deviations that cannot change any output and are therefore not listed:
+#  - `self.top < x * self.count` with <= in getA .. getT: equality needs top == x * count.  top is at most the largest single sum
+#    the position has held, so equality needs count == 1 (or all sums 0, where top == x == 0), and there both branches answer x.
+#  - testing the flags as the pass goes instead of the flags handed in: a read stands in one pair record only, so no record can
+#    see a flag that an earlier record of the same pass set; and the flags are only set behind the loop over the pair list.
+#  - the order of the discard test and the too-short test is observable (P family, one count), the order of the two too-short
+#    tests of a pair is not: either way the pair counts once.
 
-def quality_to_probability(min_quality, start_char):
+
+def _dev(deviation):
+    if deviation is None:
+        return frozenset()
+    d = frozenset([deviation]) if isinstance(deviation, str) else frozenset(deviation)
+    assert d <= set(DEVIATIONS), d - set(DEVIATIONS)
+    return d
+
+
+def quality_to_probability(min_quality, start_char, deviation=None):
     """Read::initializeQualityToProbability (src/Sequence.cpp:522-540)"""
     t = [0.0] * 256
     for i in range(start_char + min_quality, PRINT_REF_QUAL):
         t[i] = 1.0 - math.pow(10.0, (start_char - i) / 10.0)
     for i in range(PRINT_REF_QUAL, 256):
-        t[i] = 1.0
+        t[i] = 1.0 - math.pow(10.0, (start_char - i) / 10.0) if "ref_qual_not_one" in _dev(deviation) and i >= start_char + min_quality else 1.0
     return t
 
 
-def prob_to_qual(prob):
+def prob_to_qual(prob, deviation=None):
     """probToQual (src/Sequence.cpp:807-809): (char) truncates toward zero"""
+    if "qual_rounds" in _dev(deviation):
+        return int(round(-10. * math.log10(1.0 - prob)))
     return int(-10. * math.log10(1.0 - prob))
 
 
-def get_qual_char(prob, start_char=33):
+def get_qual_char(prob, start_char=33, deviation=None):
     """BaseQual::getQualChar(prob, ignoreLow = false) (src/Sequence.cpp:811-819) as a character code"""
-    if prob >= 0.9999:
+    if prob >= (1.0 if "forty_from_0_9999_off" in _dev(deviation) else 0.9999):
         return start_char + 40
-    return start_char + prob_to_qual(prob)
+    return start_char + prob_to_qual(prob, deviation)
 
 
 class ProbabilityBase:
     """src/Sequence.h:304-338"""
 
-    def __init__(self):
+    def __init__(self, dev=frozenset()):
         self.a = self.c = self.g = self.t = 0.0
         self.top = 0.0
         self.best = " "
         self.count = 0
+        self.dev = dev
 
     def copy(self):
         """the copy constructor (src/Sequence.h:313-315): the fields, then setTop(*this)"""
-        o = ProbabilityBase()
+        o = ProbabilityBase(self.dev)
         o.a, o.c, o.g, o.t, o.top, o.best, o.count = self.a, self.c, self.g, self.t, self.top, self.best, self.count
-        o.set_top(o.a, o.c, o.g, o.t)
+        if "copy_does_not_raise_top" not in self.dev:
+            o.set_top(o.a, o.c, o.g, o.t)
         return o
 
     def observe(self, nuc, prob):
@@ -68,6 +117,11 @@ class ProbabilityBase:
 
     def set_top(self, a, c, g, t):
         """src/Sequence.cpp:886-903"""
+        if "set_top_not_strict" in self.dev:
+            for x, name in ((a, "A"), (c, "C"), (g, "G"), (t, "T")):
+                if self.top <= x:
+                    self.top, self.best = x, name
+            return
         if self.top < a:
             self.top, self.best = a, "A"
         if self.top < c:
@@ -81,19 +135,29 @@ class ProbabilityBase:
         """operator+ (src/Sequence.cpp:833-842); operator+= assigns its result field by field (:843-847, :823-832)"""
         tmp = self.copy()
         tmp.a += other.a; tmp.c += other.c; tmp.g += other.g; tmp.t += other.t
-        tmp.count = ((tmp.count + other.count + 32768) % 65536) - 32768          # a short
+        tmp.count = tmp.count + other.count
+        if "count_is_int" not in self.dev:
+            tmp.count = ((tmp.count + 32768) % 65536) - 32768          # a short
         tmp.set_top(other.a, other.c, other.g, other.t)
         return tmp
 
     def _get(self, base, x):
         """getA .. getT (src/Sequence.cpp:905-928)"""
-        if self.best == base and self.top < x * self.count:
+        if (self.best == base or "get_ignores_best" in self.dev) and self.top < x * self.count:
             return self.top
         return x
 
     def get_base_qual(self):
         """getBaseQual (src/Sequence.cpp:930-965): (base, the value handed to getQualChar)"""
         a, c, g, t = self.a, self.c, self.g, self.t
+        if "tree_not_strict" in self.dev:
+            if a >= c:
+                if a >= g:
+                    return ("A", self._get("A", a)) if a >= t else ("T", self._get("T", t))
+                return ("G", self._get("G", g)) if g >= t else ("T", self._get("T", t))
+            if c >= g:
+                return ("C", self._get("C", c)) if c >= t else ("T", self._get("T", t))
+            return ("G", self._get("G", g)) if g >= t else ("T", self._get("T", t))
         if a > c:
             if a > g:
                 return ("A", self._get("A", a)) if a > t else ("T", self._get("T", t))
@@ -103,45 +167,51 @@ class ProbabilityBase:
         return ("G", self._get("G", g)) if g > t else ("T", self._get("T", t))
 
 
-def read_probability_bases(bases, quals, min_quality, start_char, table):
+def read_probability_bases(bases, quals, min_quality, start_char, table, deviation=None):
     """Read::getProbabilityBases (src/Sequence.cpp:563-582)"""
-    probs = [ProbabilityBase() for _ in bases]
+    dev = _dev(deviation)
+    probs = [ProbabilityBase(dev) for _ in bases]
     for i, nuc in enumerate(bases):
         q = ord(quals[i])
         if q < min_quality + start_char:
+            if "low_quality_skips" in dev:
+                continue
             break
         prob = table[q]
-        if prob < 0.2501:
+        if prob < 0.2501 and "no_floor" not in dev:
             prob = 0.2501
         probs[i].observe(nuc, prob)
     return probs
 
 
-def consensus_read(reads, min_quality, start_char=33, table=None):
+def consensus_read(reads, min_quality, start_char=33, table=None, deviation=None, name_from=None):
     """ReadSet::getConsensusRead(minQual) (src/ReadSet.cpp:599-629) over ReadSet::getProbabilityBases (:572-579) and
     ProbabilityBases::operator+= (src/Sequence.cpp:986-995): (name, bases, qualities)"""
+    dev = _dev(deviation)
     if table is None:
-        table = quality_to_probability(min_quality, start_char)
+        table = quality_to_probability(min_quality, start_char, dev)
     probs = []
     for _, bases, quals in reads:
-        other = read_probability_bases(bases, quals, min_quality, start_char, table)
+        other = read_probability_bases(bases, quals, min_quality, start_char, table, dev)
         while len(probs) < len(other):
-            probs.append(ProbabilityBase())
+            probs.append(ProbabilityBase(dev))
         for i in range(len(other)):
             probs[i] = probs[i].plus(other[i])
-    name = "C%d-%s" % (len(reads), read_name(reads[0][0]))
+    count = "%03d" % (len(reads) % 1000) if "count_digits_fixed" in dev else "%d" % len(reads)
+    name = "C%s-%s" % (count, read_name((reads[0] if name_from is None else name_from)[0], dev))
     out_b, out_q = [], []
     for p in probs:
         base, value = p.get_base_qual()
         out_b.append(base)
-        out_q.append(chr(get_qual_char(value, start_char)))
+        out_q.append(chr(get_qual_char(value, start_char, dev)))
     return name, "".join(out_b), "".join(out_q)
 
 
-def read_name(name_line):
+def read_name(name_line, deviation=None):
     """what is printed of a name: up to the first blank or tab (the span kmr_select_reads prints; the Casava rewrite is not covered)"""
+    stops = " " if "name_cut_at_blank_only" in _dev(deviation) else " \t"
     for i, ch in enumerate(name_line):
-        if ch in " \t":
+        if ch in stops:
             return name_line[:i]
     return name_line
 
@@ -187,9 +257,36 @@ class Result:
         return np.array(self.groups, dtype=np.int64).reshape(-1, 2)
 
 
-def filter_duplicate_fragments(reads, pairs, discarded=None, dedup_mode=1, paired=True, dedup_length=24, start_offset=0, min_quality=3, start_char=33):
+def _window_key(bases, start_offset, need, dev):
+    """the 2-bit codes of the window [start_offset, need) of one read"""
+    if "key_window_shifted" in dev:
+        w = (bases + "A")[start_offset + 1:need + 1]
+    else:
+        w = bases[start_offset:need]
+    if "n_is_its_own_code" in dev:
+        return [4 if ch in "Nn" else c for ch, c in zip(w, two_bit(w))]
+    return two_bit(w)
+
+
+def _rc(codes):
+    return [3 - v if v < 4 else v for v in reversed(codes)]
+
+
+def _key(codes, dev):
+    """key_bytes; with n_is_its_own_code a code does not fit two bits: one byte per base, which compares in the same order"""
+    return bytes(codes) if "n_is_its_own_code" in dev else key_bytes(codes)
+
+
+def _too_short(bases, start_offset, need, dev):
+    if "x_before_window_ignored" in dev:
+        return len(bases) < need or first_markup_x_length(bases[start_offset:]) < need - start_offset
+    return first_markup_x_length(bases) < need
+
+
+def filter_duplicate_fragments(reads, pairs, discarded=None, dedup_mode=1, paired=True, dedup_length=24, start_offset=0, min_quality=3, start_char=33, deviation=None):
     """_buildDuplicateFragmentMap (:172-292) with one thread, then _buildConsensusPairedReads (:420-503) or
     _buildConsensusUnPairedReads (:361-418); groups in ascending position of their first member"""
+    dev = _dev(deviation)
     n = len(reads)
     res = Result(n)
     if discarded is not None:
@@ -197,7 +294,14 @@ def filter_duplicate_fragments(reads, pairs, discarded=None, dedup_mode=1, paire
     before = list(res.discarded)
     length = dedup_length if paired else 2 * dedup_length          # :188-190
     need = length + start_offset
-    table = quality_to_probability(min_quality, start_char)
+    table = quality_to_probability(min_quality, start_char, dev)
+    per_base = 1 if "n_is_its_own_code" in dev else 4              # bases a key byte holds
+    word = 8 * 4 // per_base                                       # key bytes of one 64-bit word
+
+    def grouping(key):
+        if "last_key_word_ignored" in dev:
+            return key[:(len(key) - 1) // word * word]
+        return key
     groups = {}                                                    # key -> [(pair position, flipped)], in the order met
     for pos, (r1, r2) in enumerate(pairs):
         if paired and r1 != NONE and r2 != NONE:
@@ -207,16 +311,23 @@ def filter_duplicate_fragments(reads, pairs, discarded=None, dedup_mode=1, paire
             if before[r1] or before[r2]:
                 res.skipped[0] += 1
                 continue
-            if first_markup_x_length(reads[r1][1]) < need or first_markup_x_length(reads[r2][1]) < need:
-                res.skipped[1] += 1
+            s1, s2 = _too_short(reads[r1][1], start_offset, need, dev), _too_short(reads[r2][1], start_offset, need, dev)
+            if s1 or s2:
+                res.skipped[1] += 2 if (s1 and s2 and "pair_short_counted_twice" in dev) else 1
                 continue
-            fwd = two_bit(reads[r1][1][start_offset:need]) + reverse_complement(two_bit(reads[r2][1][start_offset:need]))
-            key, flipped = key_bytes(fwd), False
+            fwd = _window_key(reads[r1][1], start_offset, need, dev) + _rc(_window_key(reads[r2][1], start_offset, need, dev))
+            key, flipped = _key(fwd, dev), False
             if dedup_mode == 2:
-                rev = key_bytes(reverse_complement(fwd))
-                if not key <= rev:                                 # Kmer::buildLeastComplement (src/Kmer.h:356-364)
+                rev = _key(_rc(fwd), dev)
+                if "canonical_first_word_only" in dev:
+                    least = key[:word] <= rev[:word]
+                elif "canonical_tie_takes_reverse" in dev:
+                    least = key < rev
+                else:
+                    least = key <= rev                             # Kmer::buildLeastComplement (src/Kmer.h:356-364)
+                if not least:
                     key, flipped = rev, True
-            groups.setdefault(key, []).append((pos, flipped))
+            groups.setdefault(grouping(key), []).append((pos, flipped))
         elif (not paired) and (r1 != NONE) != (r2 != NONE):
             rid = r1 if r1 != NONE else r2
             if not rid < n:
@@ -225,32 +336,40 @@ def filter_duplicate_fragments(reads, pairs, discarded=None, dedup_mode=1, paire
             if before[rid]:
                 res.skipped[0] += 1
                 continue
-            if first_markup_x_length(reads[rid][1]) < need:
+            if _too_short(reads[rid][1], start_offset, need, dev):
                 res.skipped[1] += 1
                 continue
-            groups.setdefault(key_bytes(two_bit(reads[rid][1][start_offset:need])), []).append((pos, False))
+            groups.setdefault(grouping(_key(_window_key(reads[rid][1], start_offset, need, dev), dev)), []).append((pos, False))
         else:
             res.skipped[2] += 1
-    for members in groups.values():
-        if len(members) < 2:
+    order = sorted(groups) if "groups_in_key_order" in dev else list(groups)
+    for key in order:
+        members = groups[key]
+        if len(members) < (3 if "cutoff_three" in dev else 2):
             continue
+        if "members_not_in_pair_order" in dev:
+            members = members[::-1]
         res.groups.append((members[0][0], len(members)))
         if paired:
             side1, side2 = [], []
             for pos, flipped in members:
                 r1, r2 = pairs[pos]
                 if flipped:
-                    r1, r2 = r2, r1
                     res.flipped += 1
+                    if "flip_sides_not_swapped" not in dev:
+                        r1, r2 = r2, r1
                 side1.append(reads[r1]); side2.append(reads[r2])
-            res.consensus.append(consensus_read(side1, min_quality, start_char, table))
-            res.consensus.append(consensus_read(side2, min_quality, start_char, table))
+            named = (None, None)
+            if "name_of_unflipped_first_read" in dev:
+                named = tuple(reads[r] for r in pairs[members[0][0]])
+            res.consensus.append(consensus_read(side1, min_quality, start_char, table, dev, named[0]))
+            res.consensus.append(consensus_read(side2, min_quality, start_char, table, dev, named[1]))
             res.affected += 2 * len(members)
             for pos, _ in members:
                 res.discarded[pairs[pos][0]] = res.discarded[pairs[pos][1]] = 1
         else:
             rids = [pairs[pos][0] if pairs[pos][0] != NONE else pairs[pos][1] for pos, _ in members]
-            res.consensus.append(consensus_read([reads[r] for r in rids], min_quality, start_char, table))
+            res.consensus.append(consensus_read([reads[r] for r in rids], min_quality, start_char, table, dev))
             res.affected += len(members)
             for r in rids:
                 res.discarded[r] = 1
