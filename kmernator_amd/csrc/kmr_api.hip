@@ -7,8 +7,10 @@
  * scatter -> sort -> image) and the stateless helpers.  There is no CPU
  * fallback: every compute entry point needs a HIP device and fails with
  * KMR_ERR_NO_DEVICE otherwise.
- * Shared decisions have one place each: key width / value kind / minimizer window as template arguments (with_w, with_w_ext,
- * with_win), kernel-argument structs (reads_view, finalize_params, count_out, sk_own_lists), the plan of the count pass over
+ * Shared decisions have one place each: the checked launch and the read-backs of small results (kmr_host.hpp: LAUNCH, launch_status,
+ * fetch_queue / stream_wait / fetch), key width / value kind / minimizer window as template arguments (with_w, with_w_ext,
+ * with_win), the sizes of a value and the set-up of a finalized map (value_words, image_value_bytes, alloc_map_arrays,
+ * sort_map_buckets), kernel-argument structs (reads_view, finalize_params, count_out, sk_own_lists), the plan of the count pass over
  * super-k-mer lists (sk_count_uniform, sk_count_select), the entry buffers' policy and the attempt loop of a count pass (count_entry_buffers,
  * count_attempts), the end of a finalize (publish_maps), the host-to-device piece pipeline (tb_feed_pieces), what a feed call hands down
  * (FeedHints) and its one way into the build (add_reads_dev_call, the sk_* parts of add_reads_superkmer_t), and what the stages at the
@@ -93,6 +95,10 @@ template <int W, class F> auto with_win(uint32_t win, F &&f) {
 }
 
 size_t slot_bytes(kmr_handle *h) { return with_w(h, [](auto W) { return sizeof(Slot<W()>); }); }
+/* words of a weak entry's value (count, weight, forward count; with extension values twelve tallies more), and the bytes an entry's value
+ * takes in a stored map's image */
+uint32_t value_words(const kmr_handle *h) { return h->ext ? 15 : 3; }
+uint32_t image_value_bytes(const kmr_handle *h, bool weakMap) { return weakMap ? (h->ext ? 60 : 12) : (h->ext ? 5 : 1); }
 
 /* Kernel-argument structs leave their makers with every field set, a site states only what differs.  reads_view: a batch of reads on
  * the device (no work units: prepare_units cuts them where a read is longer than a tile) */
@@ -124,7 +130,7 @@ DevParams dev_params(kmr_handle *h) {
 	p.sub_wstart = p.sub_wkeys = p.sub_sstart = p.sub_skeys = nullptr; p.sub_wvals = nullptr; p.sub_sweight = nullptr; p.sub_wnb = p.sub_snb = 0; p.sub_vw = 0;
 	if (h->subtract) {
 		const kmr_handle *o = h->subtract;
-		if (o->weak.present && o->weak.n) { p.sub_wstart = o->weak.start.get<uint64_t>(); p.sub_wkeys = o->weak.keys.get<uint64_t>(); p.sub_wvals = o->weak.vals.get<uint32_t>(); p.sub_wnb = o->weak.nb; p.sub_vw = o->ext ? 15 : 3; }
+		if (o->weak.present && o->weak.n) { p.sub_wstart = o->weak.start.get<uint64_t>(); p.sub_wkeys = o->weak.keys.get<uint64_t>(); p.sub_wvals = o->weak.vals.get<uint32_t>(); p.sub_wnb = o->weak.nb; p.sub_vw = value_words(o); }
 		if (o->sing.present && o->sing.n) { p.sub_sstart = o->sing.start.get<uint64_t>(); p.sub_skeys = o->sing.keys.get<uint64_t>(); p.sub_sweight = o->sing.sweight.get<uint8_t>(); p.sub_snb = o->sing.nb; }
 	}
 	return p;
@@ -134,8 +140,7 @@ DevParams dev_params(kmr_handle *h) {
 template <int W> Table<W> table_of(kmr_handle *h) { Table<W> t; t.slots = h->slots.get<Slot<W>>(); t.ext = h->extslots.get<ExtSlot>(); t.log2cap = h->log2cap; return t; }
 
 template <int W> int clear_table(kmr_handle *h, void *slots, ExtSlot *ext, uint32_t log2cap) {
-	hipLaunchKernelGGL(table_clear_kernel<W>, dim3(grid_for(1ull << log2cap)), dim3(256), 0, h->stream, (Slot<W> *)slots, ext, 1ull << log2cap);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, table_clear_kernel<W>, dim3(grid_for(1ull << log2cap)), dim3(256), 0, (Slot<W> *)slots, ext, 1ull << log2cap);
 	return 0;
 }
 int clear_table_any(kmr_handle *h, void *slots, ExtSlot *ext, uint32_t log2cap) { return with_w(h, [&](auto W) { return clear_table<W()>(h, slots, ext, log2cap); }); }
@@ -155,7 +160,7 @@ int alloc_table(kmr_handle *h, uint32_t log2cap, DevBuf &slots, DevBuf &ext) {
  * wait (h->l1_head_seen, for a build_csr that follows with no launch in between that takes chunks) */
 int sync_state(kmr_handle *h, bool with_pool_head = false) {
 	h->l1_head_seen = 0;
-	if (with_pool_head && h->l1.head) HIPCHK(h, hipMemcpyAsync(&h->l1_head_seen, h->l1.head.get<unsigned int>(), 4, hipMemcpyDeviceToHost, h->stream));
+	if (with_pool_head && h->l1.head) HIPCHK(h, fetch_queue(h, &h->l1_head_seen, h->l1.head.get<unsigned int>()));
 	HIPCHK(h, hipStreamSynchronize(h->stream));
 	for (int which = 0; which < KMR_TIME_GROUPS; which++) {
 		for (auto &pr : h->pending_events[which]) {
@@ -188,8 +193,7 @@ template <int W, bool EXT> int grow_table_t(kmr_handle *h, uint32_t newlog) {
 	int rc = alloc_table(h, newlog, ns, ne);
 	if (rc) return rc;
 	Table<W> src = table_of<W>(h), dst; dst.slots = ns.get<Slot<W>>(); dst.ext = ne.get<ExtSlot>(); dst.log2cap = newlog;
-	hipLaunchKernelGGL((rehash_kernel<W, EXT>), dim3(grid_for(1ull << h->log2cap)), dim3(256), 0, h->stream, src, dst, h->hkb, h->derr.get<uint32_t>());
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, (rehash_kernel<W, EXT>), dim3(grid_for(1ull << h->log2cap)), dim3(256), 0, src, dst, h->hkb, h->derr.get<uint32_t>());
 	HIPCHK(h, hipStreamSynchronize(h->stream));
 	h->slots = std::move(ns); h->extslots = std::move(ne); h->log2cap = newlog;
 	return 0;
@@ -227,27 +231,22 @@ int prepare_units(kmr_handle *h, ReadsView &rv, uint32_t span = (uint32_t)TILE_S
 	else {
 		rc = h->umax.reserve(h, "umax", 4); if (rc) return rc;
 		HIPCHK(h, hipMemsetAsync(h->umax.get<unsigned int>(), 0, 4, h->stream));
-		hipLaunchKernelGGL(unit_max_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, rv.offsets, n, h->umax.get<unsigned int>());
-		HIPCHK(h, hipGetLastError());
-		HIPCHK(h, hipMemcpyAsync(&mx, h->umax.get<unsigned int>(), 4, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(h, hipStreamSynchronize(h->stream));
+		LAUNCH(h, unit_max_kernel, dim3(grid_for(n)), dim3(256), 0, rv.offsets, n, h->umax.get<unsigned int>());
+		HIPCHK(h, fetch(h, &mx, h->umax.get<unsigned int>()));
 	}
 	if (mx <= span) return 0;                   /* the usual case: every read is one unit */
 	h->unit_batches++;
 	rc = h->ucnt.reserve(h, "ucnt", 4 * (n + 1)); if (rc) return rc;
-	hipLaunchKernelGGL(unit_count_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, rv.offsets, n, h->k, span, h->ucnt.get<uint32_t>());
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, unit_count_kernel, dim3(grid_for(n)), dim3(256), 0, rv.offsets, n, h->k, span, h->ucnt.get<uint32_t>());
 	rc = h->ufirst.reserve(h, "ufirst", 8 * (n + 1)); if (rc) return rc;
 	rc = exclusive_scan_queue(h, h->ucnt.get<uint32_t>(), n, h->ufirst.get<uint64_t>()); if (rc) return rc;
 	uint64_t U = 0;
-	HIPCHK(h, hipMemcpyAsync(&U, h->ufirst.get<uint64_t>() + n, 8, hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(h, hipStreamSynchronize(h->stream));
+	HIPCHK(h, fetch(h, &U, h->ufirst.get<uint64_t>() + n));
 	if (h->u_read.cap() < 8 * U) {      /* (u_read is allocated last) */
 		h->u_start.reset(); h->u_end.reset(); h->u_read.reset();
 		HIPCHK(h, h->u_start.alloc(8 * U)); HIPCHK(h, h->u_end.alloc(8 * U)); HIPCHK(h, h->u_read.alloc(8 * U));
 	}
-	hipLaunchKernelGGL(unit_fill_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, rv.offsets, n, h->k, span, h->ufirst.get<uint64_t>(), h->u_start.get<uint64_t>(), h->u_end.get<uint64_t>(), h->u_read.get<uint64_t>());
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, unit_fill_kernel, dim3(grid_for(n)), dim3(256), 0, rv.offsets, n, h->k, span, h->ufirst.get<uint64_t>(), h->u_start.get<uint64_t>(), h->u_end.get<uint64_t>(), h->u_read.get<uint64_t>());
 	rv.u_start = h->u_start.get<uint64_t>(); rv.u_end = h->u_end.get<uint64_t>(); rv.u_read = h->u_read.get<uint64_t>(); rv.n_units = U;
 	return 0;
 }
@@ -263,8 +262,7 @@ template <int W, bool EXT, class Op> int launch_extract(kmr_handle *h, const Rea
 	if (blocks == 0) return 0;
 	if (max_blocks && blocks > max_blocks) blocks = max_blocks;      /* wavefronts then walk several tiles */
 	if (blocks > 0x7fffffffull) return fail(h, KMR_ERR_INVALID_ARG, "too many reads in one batch");
-	hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(WAVES_PER_BLOCK * 64), EXTRACT_SMEM, h->stream, rv, dp, op);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, kern, dim3((unsigned)blocks), dim3(WAVES_PER_BLOCK * 64), EXTRACT_SMEM, rv, dp, op);
 	return 0;
 }
 
@@ -277,9 +275,9 @@ template <int W, bool EXT> int add_reads_dev_t(kmr_handle *h, const ReadsView &r
 	for (uint64_t r = 0; r < n; r += chunk) {
 		const uint64_t m = std::min(chunk, n - r);
 		/* bases in this chunk: read the two boundary offsets */
-		HIPCHK(h, hipMemcpyAsync(&off2[0], rvAll.offsets + r, 8, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(h, hipMemcpyAsync(&off2[1], rvAll.offsets + r + m, 8, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(h, hipStreamSynchronize(h->stream));
+		HIPCHK(h, fetch_queue(h, &off2[0], rvAll.offsets + r));
+		HIPCHK(h, fetch_queue(h, &off2[1], rvAll.offsets + r + m));
+		HIPCHK(h, stream_wait(h));
 		const uint64_t bases = off2[1] - off2[0];
 		int rc = ensure_capacity(h, bases);     /* #k-mers <= #bases */
 		if (rc) return rc;
@@ -303,10 +301,9 @@ int exclusive_scan_queue(kmr_handle *h, const uint32_t *in, uint64_t n, uint64_t
 	const size_t eb = sizeof(unsigned long long);
 	int rc = h->scan_sums.reserve(h, "scan_sums", eb * (nblocks + 1), eb * std::max<uint64_t>(nblocks + 1, 4096)); if (rc) return rc;
 	unsigned long long *sums = h->scan_sums.get<unsigned long long>(), *total = sums + nblocks;
-	hipLaunchKernelGGL(scan_block_sums_kernel, dim3((unsigned)nblocks), dim3(256), 0, h->stream, in, n, sums);
-	hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(256), 0, h->stream, sums, nblocks, total);
-	hipLaunchKernelGGL(scan_apply_kernel, dim3((unsigned)nblocks), dim3(256), 0, h->stream, in, n, sums, out);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, scan_block_sums_kernel, dim3((unsigned)nblocks), dim3(256), 0, in, n, sums);
+	LAUNCH(h, scan_sums_kernel, dim3(1), dim3(256), 0, sums, nblocks, total);
+	LAUNCH(h, scan_apply_kernel, dim3((unsigned)nblocks), dim3(256), 0, in, n, sums, out);
 	return 0;
 }
 int exclusive_scan(kmr_handle *h, const uint32_t *in, uint64_t n, uint64_t *out /* n+1 */) {
@@ -361,6 +358,29 @@ template <int W> MapView<W> view_of(const DevMap &m, uint32_t vw) {
 	return v;
 }
 
+/* The arrays of a finalized map of m.n entries, 8 bytes at least each: keys and values of a weak map; keys, weights and, with extension
+ * values, packets of a singleton map */
+template <int W> int alloc_map_arrays(kmr_handle *h, DevMap &m, bool weakMap) {
+	HIPCHK(h, m.keys.alloc(std::max<uint64_t>(8, 8ull * W * m.n)));
+	if (weakMap) HIPCHK(h, m.vals.alloc(std::max<uint64_t>(8, 4ull * value_words(h) * m.n)));
+	else {
+		HIPCHK(h, m.sweight.alloc(std::max<uint64_t>(8, m.n)));
+		if (h->ext) HIPCHK(h, m.spkt.alloc(std::max<uint64_t>(8, 4 * m.n)));
+	}
+	return 0;
+}
+/* Sort every bucket of a map by key.  The view names the arrays of the map's kind only (a weak map owns no weights or packets, a
+ * singleton map no values, and none but a build with extension values packets: their buffers are empty) */
+template <int W> int sort_map_buckets(kmr_handle *h, DevMap &m, bool weakMap) {
+	SortView<W> sv; sv.keys = m.keys.get<uint64_t>(); sv.vw = weakMap ? value_words(h) : 0;
+	sv.vals = weakMap ? m.vals.get<uint32_t>() : nullptr; sv.b8 = weakMap ? nullptr : m.sweight.get<uint8_t>(); sv.pkt = weakMap ? nullptr : m.spkt.get<uint32_t>();
+	const dim3 grid(grid_for(m.nb, 4, 1 << 20));
+	if (!weakMap) LAUNCH(h, (sort_buckets_kernel<W, 0>), grid, dim3(256), 0, sv, m.start.get<uint64_t>(), m.nb);
+	else if (h->ext) LAUNCH(h, (sort_buckets_kernel<W, 15>), grid, dim3(256), 0, sv, m.start.get<uint64_t>(), m.nb);
+	else LAUNCH(h, (sort_buckets_kernel<W, 3>), grid, dim3(256), 0, sv, m.start.get<uint64_t>(), m.nb);
+	return 0;
+}
+
 template <int W, bool EXT> int finalize_t(kmr_handle *h, uint32_t min_depth) {
 	int rc = sync_state(h);
 	if (rc) return rc;
@@ -373,11 +393,9 @@ template <int W, bool EXT> int finalize_t(kmr_handle *h, uint32_t min_depth) {
 	HIPCHK(h, hipMemsetAsync(wc, 0, 4 * h->nb_weak, h->stream)); HIPCHK(h, hipMemsetAsync(sc, 0, 4 * h->nb_sing, h->stream)); HIPCHK(h, hipMemsetAsync(fc, 0, sizeof(FinalizeCounters), h->stream));
 	Table<W> t = table_of<W>(h);
 	const int g = grid_for(1ull << h->log2cap);
-	hipLaunchKernelGGL(classify_kernel<W>, dim3(g), dim3(256), 0, h->stream, t, f, wc, sc, fc);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, classify_kernel<W>, dim3(g), dim3(256), 0, t, f, wc, sc, fc);
 	FinalizeCounters c;
-	HIPCHK(h, hipMemcpyAsync(&c, fc, sizeof(c), hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(h, hipStreamSynchronize(h->stream));
+	HIPCHK(h, fetch(h, &c, fc));
 	h->stats.unique_kmers = c.unique;
 	/* singletonKmers only moves inside the hasSingletons branches of append() (src/KmerSpectrum.h:1625,1649) */
 	h->stats.singleton_kmers = f.has_singletons ? c.singletons : 0;
@@ -385,23 +403,15 @@ template <int W, bool EXT> int finalize_t(kmr_handle *h, uint32_t min_depth) {
 	wm = DevMap(); sm = DevMap();
 	wm.nb = h->nb_weak; wm.n = c.weak_kept; wm.present = true;
 	sm.nb = h->nb_sing; sm.n = c.sing_kept; sm.present = keepSing;
-	const uint32_t vw = EXT ? 15 : 3;
 	HIPCHK(h, wm.start.alloc(8 * (wm.nb + 1))); HIPCHK(h, sm.start.alloc(8 * (sm.nb + 1)));
 	rc = exclusive_scan(h, wc, wm.nb, wm.start.get<uint64_t>()); if (rc) return rc;
 	rc = exclusive_scan(h, sc, sm.nb, sm.start.get<uint64_t>()); if (rc) return rc;
-	HIPCHK(h, wm.keys.alloc(std::max<uint64_t>(8, 8ull * W * wm.n))); HIPCHK(h, wm.vals.alloc(std::max<uint64_t>(8, 4ull * vw * wm.n)));
-	HIPCHK(h, sm.keys.alloc(std::max<uint64_t>(8, 8ull * W * sm.n))); HIPCHK(h, sm.sweight.alloc(std::max<uint64_t>(8, sm.n)));
-	if (EXT) HIPCHK(h, sm.spkt.alloc(std::max<uint64_t>(8, 4ull * sm.n)));
+	rc = alloc_map_arrays<W>(h, wm, true); if (rc) return rc;
+	rc = alloc_map_arrays<W>(h, sm, false); if (rc) return rc;
 	HIPCHK(h, hipMemsetAsync(wc, 0, 4 * h->nb_weak, h->stream)); HIPCHK(h, hipMemsetAsync(sc, 0, 4 * h->nb_sing, h->stream));
-	hipLaunchKernelGGL((scatter_kernel<W, EXT>), dim3(g), dim3(256), 0, h->stream, t, f, wm.start.get<uint64_t>(), wc, wm.keys.get<uint64_t>(), wm.vals.get<uint32_t>(), sm.start.get<uint64_t>(), sc, sm.keys.get<uint64_t>(), sm.sweight.get<uint8_t>(), sm.spkt.get<uint32_t>());
-	HIPCHK(h, hipGetLastError());
-	SortView<W> sv; sv.keys = wm.keys.get<uint64_t>(); sv.vals = wm.vals.get<uint32_t>(); sv.b8 = nullptr; sv.pkt = nullptr; sv.vw = vw;
-	hipLaunchKernelGGL((sort_buckets_kernel<W, EXT ? 15 : 3>), dim3(grid_for(wm.nb, 4, 1 << 20)), dim3(256), 0, h->stream, sv, wm.start.get<uint64_t>(), wm.nb);
-	if (sm.n) {
-		SortView<W> ss; ss.keys = sm.keys.get<uint64_t>(); ss.vals = nullptr; ss.b8 = sm.sweight.get<uint8_t>(); ss.pkt = sm.spkt.get<uint32_t>(); ss.vw = 0;
-		hipLaunchKernelGGL((sort_buckets_kernel<W, 0>), dim3(grid_for(sm.nb, 4, 1 << 20)), dim3(256), 0, h->stream, ss, sm.start.get<uint64_t>(), sm.nb);
-	}
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, (scatter_kernel<W, EXT>), dim3(g), dim3(256), 0, t, f, wm.start.get<uint64_t>(), wc, wm.keys.get<uint64_t>(), wm.vals.get<uint32_t>(), sm.start.get<uint64_t>(), sc, sm.keys.get<uint64_t>(), sm.sweight.get<uint8_t>(), sm.spkt.get<uint32_t>());
+	rc = sort_map_buckets<W>(h, wm, true); if (rc) return rc;
+	if (sm.n) { rc = sort_map_buckets<W>(h, sm, false); if (rc) return rc; }
 	whole.end();
 	HIPCHK(h, hipStreamSynchronize(h->stream));
 	/* the table allocation is kept for kmr_reset(); kmr_release_table() frees it */
@@ -411,13 +421,11 @@ template <int W, bool EXT> int finalize_t(kmr_handle *h, uint32_t min_depth) {
 
 template <int W> int build_image_t(kmr_handle *h, DevMap &m, bool weakMap) {
 	if (m.image) return 0;
-	const uint32_t vw = h->ext ? 15 : 3;
-	const uint32_t vbytes = weakMap ? (h->ext ? 60 : 12) : (h->ext ? 5 : 1);
+	const uint32_t vw = value_words(h), vbytes = image_value_bytes(h, weakMap);
 	HIPCHK(h, m.image.alloc(8 * (2 + m.nb) + 4 * m.nb + m.n * (h->kb + vbytes)));
-	hipLaunchKernelGGL(image_header_kernel, dim3(grid_for(m.nb)), dim3(256), 0, h->stream, m.image.get<uint8_t>(), m.start.get<uint64_t>(), m.nb, h->kb, vbytes);
-	if (m.n) hipLaunchKernelGGL(image_entries_kernel<W>, dim3(grid_for(m.n)), dim3(256), 0, h->stream, m.image.get<uint8_t>(), m.start.get<uint64_t>(), m.nb, h->kb, vbytes,
-	                           m.keys.get<uint64_t>(), weakMap ? m.vals.get<uint32_t>() : nullptr, vw, m.sweight.get<uint8_t>(), m.spkt.get<uint32_t>(), m.n);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, image_header_kernel, dim3(grid_for(m.nb)), dim3(256), 0, m.image.get<uint8_t>(), m.start.get<uint64_t>(), m.nb, h->kb, vbytes);
+	if (m.n) LAUNCH(h, image_entries_kernel<W>, dim3(grid_for(m.n)), dim3(256), 0, m.image.get<uint8_t>(), m.start.get<uint64_t>(), m.nb, h->kb, vbytes,
+	               m.keys.get<uint64_t>(), weakMap ? m.vals.get<uint32_t>() : nullptr, vw, m.sweight.get<uint8_t>(), m.spkt.get<uint32_t>(), m.n);
 	HIPCHK(h, hipStreamSynchronize(h->stream));
 	return 0;
 }
@@ -427,8 +435,7 @@ int build_image(kmr_handle *h, DevMap &m, bool weakMap) { return with_w(h, [&](a
  * offset or a count of it, and the map is built on the side: `out` changes only once the check, every allocation and every launch
  * have succeeded, so a refused or failed load leaves the map it was to replace as it was. */
 template <int W> int load_image_t(kmr_handle *h, DevMap &out, bool weakMap, const uint8_t *src, uint64_t len) {
-	const uint32_t vw = h->ext ? 15 : 3;
-	const uint32_t vbytes = weakMap ? (h->ext ? 60 : 12) : (h->ext ? 5 : 1);
+	const uint32_t vw = value_words(h), vbytes = image_value_bytes(h, weakMap);
 	const kmr_host::ImageLayout lay = kmr_host::check_image_layout(src, len, h->kb, vbytes);
 	if (lay.reason) return fail(h, KMR_ERR_INVALID_ARG, lay.reason);
 	const uint64_t nb = lay.nb;
@@ -438,68 +445,54 @@ template <int W> int load_image_t(kmr_handle *h, DevMap &out, bool weakMap, cons
 	HIPCHK(h, hipMemcpy(m.image.get<uint8_t>(), src, len, hipMemcpyHostToDevice));
 	{
 		DevBuf counts; HIPCHK(h, counts.alloc(4 * nb));
-		hipLaunchKernelGGL(image_counts_kernel, dim3(grid_for(nb)), dim3(256), 0, h->stream, m.image.get<uint8_t>(), nb, counts.get<uint32_t>());
+		LAUNCH(h, image_counts_kernel, dim3(grid_for(nb)), dim3(256), 0, m.image.get<uint8_t>(), nb, counts.get<uint32_t>());
 		HIPCHK(h, m.start.alloc(8 * (nb + 1)));
 		int rc = exclusive_scan(h, counts.get<uint32_t>(), nb, m.start.get<uint64_t>()); if (rc) return rc;
 	}
-	HIPCHK(h, m.keys.alloc(std::max<uint64_t>(8, 8ull * W * m.n)));
-	if (weakMap) HIPCHK(h, m.vals.alloc(std::max<uint64_t>(8, 4ull * vw * m.n)));
-	else { HIPCHK(h, m.sweight.alloc(std::max<uint64_t>(8, m.n))); if (h->ext) HIPCHK(h, m.spkt.alloc(std::max<uint64_t>(8, 4 * m.n))); }
-	if (m.n) hipLaunchKernelGGL(image_unpack_kernel<W>, dim3(grid_for(m.n)), dim3(256), 0, h->stream, m.image.get<uint8_t>(), m.start.get<uint64_t>(), nb, h->kb, vbytes, m.keys.get<uint64_t>(), m.vals.get<uint32_t>(), vw, m.sweight.get<uint8_t>(), m.spkt.get<uint32_t>(), m.n);
+	int rc = alloc_map_arrays<W>(h, m, weakMap); if (rc) return rc;
+	if (m.n) LAUNCH(h, image_unpack_kernel<W>, dim3(grid_for(m.n)), dim3(256), 0, m.image.get<uint8_t>(), m.start.get<uint64_t>(), nb, h->kb, vbytes, m.keys.get<uint64_t>(), m.vals.get<uint32_t>(), vw, m.sweight.get<uint8_t>(), m.spkt.get<uint32_t>(), m.n);
 	/* restore() accepts unsorted buckets (setLastSorted); lookups here need them sorted */
-	SortView<W> sv; sv.keys = m.keys.get<uint64_t>(); sv.vals = m.vals.get<uint32_t>(); sv.b8 = m.sweight.get<uint8_t>(); sv.pkt = m.spkt.get<uint32_t>(); sv.vw = weakMap ? vw : 0;
-	if (!weakMap) hipLaunchKernelGGL((sort_buckets_kernel<W, 0>), dim3(grid_for(nb, 4, 1 << 20)), dim3(256), 0, h->stream, sv, m.start.get<uint64_t>(), nb);
-	else if (h->ext) hipLaunchKernelGGL((sort_buckets_kernel<W, 15>), dim3(grid_for(nb, 4, 1 << 20)), dim3(256), 0, h->stream, sv, m.start.get<uint64_t>(), nb);
-	else hipLaunchKernelGGL((sort_buckets_kernel<W, 3>), dim3(grid_for(nb, 4, 1 << 20)), dim3(256), 0, h->stream, sv, m.start.get<uint64_t>(), nb);
-	HIPCHK(h, hipGetLastError());
+	rc = sort_map_buckets<W>(h, m, weakMap); if (rc) return rc;
 	HIPCHK(h, hipStreamSynchronize(h->stream));
 	m.image.reset();    /* rebuilt (sorted) on demand */
 	out = std::move(m);
 	return 0;
 }
 
-template <int W, int VW> void launch_sort(kmr_handle *h, DevMap &m, bool weakMap) {
-	SortView<W> sv; sv.keys = m.keys.get<uint64_t>(); sv.vals = weakMap ? m.vals.get<uint32_t>() : nullptr; sv.b8 = m.sweight.get<uint8_t>(); sv.pkt = m.spkt.get<uint32_t>(); sv.vw = weakMap ? VW : 0;
-	hipLaunchKernelGGL((sort_buckets_kernel<W, VW>), dim3(grid_for(m.nb, 4, 1 << 20)), dim3(256), 0, h->stream, sv, m.start.get<uint64_t>(), m.nb);
-}
 /* union of the handle's map with a stored map of the same shape (see merge_copy_kernel) */
 template <int W> int merge_image_t(kmr_handle *h, DevMap &m, bool weakMap, const uint8_t *src, uint64_t len) {
 	DevMap t;
 	int rc = load_image_t<W>(h, t, weakMap, src, len);
 	if (rc) return rc;
 	if (t.nb != m.nb) return fail(h, KMR_ERR_INVALID_ARG, "Can not merge two maps of differing sizes (src/Kmer.h:3210)");
-	const uint32_t vw = h->ext ? 15 : 3;
+	const uint32_t vw = value_words(h);
 	DevMap d; d.nb = m.nb; d.n = m.n + t.n; d.present = true;
 	DevBuf countsb, dupb;
 	HIPCHK(h, countsb.alloc(4 * m.nb)); HIPCHK(h, dupb.alloc(4));
 	uint32_t *counts = countsb.get<uint32_t>(), *dup = dupb.get<uint32_t>();
 	HIPCHK(h, hipMemsetAsync(dup, 0, 4, h->stream));
 	HIPCHK(h, d.start.alloc(8 * (m.nb + 1)));
-	hipLaunchKernelGGL(merge_counts_kernel, dim3(grid_for(m.nb)), dim3(256), 0, h->stream, m.start.get<uint64_t>(), t.start.get<uint64_t>(), m.nb, counts);
+	LAUNCH(h, merge_counts_kernel, dim3(grid_for(m.nb)), dim3(256), 0, m.start.get<uint64_t>(), t.start.get<uint64_t>(), m.nb, counts);
 	rc = exclusive_scan(h, counts, m.nb, d.start.get<uint64_t>()); if (rc) return rc;
-	HIPCHK(h, d.keys.alloc(std::max<uint64_t>(8, 8ull * W * d.n)));
-	if (weakMap) HIPCHK(h, d.vals.alloc(std::max<uint64_t>(8, 4ull * vw * d.n)));
-	else { HIPCHK(h, d.sweight.alloc(std::max<uint64_t>(8, d.n))); if (h->ext) HIPCHK(h, d.spkt.alloc(std::max<uint64_t>(8, 4 * d.n))); }
-	if (m.n) hipLaunchKernelGGL(merge_copy_kernel<W>, dim3(grid_for(m.n)), dim3(256), 0, h->stream, m.start.get<uint64_t>(), t.start.get<uint64_t>(), false, m.nb, m.n, m.keys.get<uint64_t>(), weakMap ? m.vals.get<uint32_t>() : nullptr, vw, m.sweight.get<uint8_t>(), m.spkt.get<uint32_t>(), d.start.get<uint64_t>(), d.keys.get<uint64_t>(), d.vals.get<uint32_t>(), d.sweight.get<uint8_t>(), d.spkt.get<uint32_t>());
-	if (t.n) hipLaunchKernelGGL(merge_copy_kernel<W>, dim3(grid_for(t.n)), dim3(256), 0, h->stream, t.start.get<uint64_t>(), m.start.get<uint64_t>(), true, m.nb, t.n, t.keys.get<uint64_t>(), weakMap ? t.vals.get<uint32_t>() : nullptr, vw, t.sweight.get<uint8_t>(), t.spkt.get<uint32_t>(), d.start.get<uint64_t>(), d.keys.get<uint64_t>(), d.vals.get<uint32_t>(), d.sweight.get<uint8_t>(), d.spkt.get<uint32_t>());
-	if (!weakMap) launch_sort<W, 0>(h, d, false); else if (h->ext) launch_sort<W, 15>(h, d, true); else launch_sort<W, 3>(h, d, true);
-	hipLaunchKernelGGL(duplicate_keys_kernel<W>, dim3(grid_for(d.nb)), dim3(256), 0, h->stream, d.start.get<uint64_t>(), d.nb, d.keys.get<uint64_t>(), dup);
-	HIPCHK(h, hipGetLastError());
+	rc = alloc_map_arrays<W>(h, d, weakMap); if (rc) return rc;
+	if (m.n) LAUNCH(h, merge_copy_kernel<W>, dim3(grid_for(m.n)), dim3(256), 0, m.start.get<uint64_t>(), t.start.get<uint64_t>(), false, m.nb, m.n, m.keys.get<uint64_t>(), weakMap ? m.vals.get<uint32_t>() : nullptr, vw, m.sweight.get<uint8_t>(), m.spkt.get<uint32_t>(), d.start.get<uint64_t>(), d.keys.get<uint64_t>(), d.vals.get<uint32_t>(), d.sweight.get<uint8_t>(), d.spkt.get<uint32_t>());
+	if (t.n) LAUNCH(h, merge_copy_kernel<W>, dim3(grid_for(t.n)), dim3(256), 0, t.start.get<uint64_t>(), m.start.get<uint64_t>(), true, m.nb, t.n, t.keys.get<uint64_t>(), weakMap ? t.vals.get<uint32_t>() : nullptr, vw, t.sweight.get<uint8_t>(), t.spkt.get<uint32_t>(), d.start.get<uint64_t>(), d.keys.get<uint64_t>(), d.vals.get<uint32_t>(), d.sweight.get<uint8_t>(), d.spkt.get<uint32_t>());
+	rc = sort_map_buckets<W>(h, d, weakMap); if (rc) return rc;
+	LAUNCH(h, duplicate_keys_kernel<W>, dim3(grid_for(d.nb)), dim3(256), 0, d.start.get<uint64_t>(), d.nb, d.keys.get<uint64_t>(), dup);
 	uint32_t hdup = 0;
-	HIPCHK(h, hipMemcpyAsync(&hdup, dup, 4, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
+	HIPCHK(h, fetch(h, &hdup, dup));
 	/* (a k-mer in both singleton maps would have to be promoted into the weak map: KmerMap::mergePromote, which the reference
 	 * itself refuses -- "This method is broken", src/Kmer.h:2675-2677) */
 	if (hdup && !weakMap) return fail(h, KMR_ERR_UNSUPPORTED, "the two singleton maps share k-mers: merging them means promoting those into the weak map (mergePromote, which the reference refuses too)");
 	if (hdup) {      /* mergeAdd proper: the k-mers both maps hold add their values */
 		DevMap d2; d2.nb = d.nb; d2.present = true;
-		hipLaunchKernelGGL(merge_distinct_kernel<W>, dim3(grid_for(d.nb)), dim3(256), 0, h->stream, d.start.get<uint64_t>(), d.nb, d.keys.get<uint64_t>(), counts);
+		LAUNCH(h, merge_distinct_kernel<W>, dim3(grid_for(d.nb)), dim3(256), 0, d.start.get<uint64_t>(), d.nb, d.keys.get<uint64_t>(), counts);
 		HIPCHK(h, d2.start.alloc(8 * (d.nb + 1)));
 		rc = exclusive_scan(h, counts, d.nb, d2.start.get<uint64_t>()); if (rc) return rc;
-		HIPCHK(h, hipMemcpyAsync(&d2.n, d2.start.get<uint64_t>() + d.nb, 8, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
-		HIPCHK(h, d2.keys.alloc(std::max<uint64_t>(8, 8ull * W * d2.n)));
-		HIPCHK(h, d2.vals.alloc(std::max<uint64_t>(8, 4ull * vw * d2.n)));
-		hipLaunchKernelGGL(merge_add_kernel<W>, dim3(grid_for(d.nb)), dim3(256), 0, h->stream, d.start.get<uint64_t>(), d.nb, d.keys.get<uint64_t>(), d.vals.get<uint32_t>(), vw, d2.start.get<uint64_t>(), d2.keys.get<uint64_t>(), d2.vals.get<uint32_t>());
-		HIPCHK(h, hipGetLastError()); HIPCHK(h, hipStreamSynchronize(h->stream));
+		HIPCHK(h, fetch(h, &d2.n, d2.start.get<uint64_t>() + d.nb));
+		rc = alloc_map_arrays<W>(h, d2, true); if (rc) return rc;
+		LAUNCH(h, merge_add_kernel<W>, dim3(grid_for(d.nb)), dim3(256), 0, d.start.get<uint64_t>(), d.nb, d.keys.get<uint64_t>(), d.vals.get<uint32_t>(), vw, d2.start.get<uint64_t>(), d2.keys.get<uint64_t>(), d2.vals.get<uint32_t>());
+		HIPCHK(h, hipStreamSynchronize(h->stream));
 		d = std::move(d2);
 	}
 	m = std::move(d);
@@ -512,10 +505,9 @@ template <int W> int lookup_t(kmr_handle *h, const uint8_t *packed, uint64_t n, 
 	DevBuf dk, dc;
 	HIPCHK(h, dk.alloc(std::max<uint64_t>(8, n * h->kb))); HIPCHK(h, dc.alloc(std::max<uint64_t>(8, ob * n)));
 	HIPCHK(h, hipMemcpyAsync(dk.get(), packed, n * h->kb, hipMemcpyHostToDevice, h->stream));
-	const uint32_t vw = h->ext ? 15 : 3;
-	hipLaunchKernelGGL(lookup_keys_kernel<W>, dim3(grid_for(n)), dim3(256), 0, h->stream, view_of<W>(h->weak, vw), view_of<W>(h->sing, vw), dk.get<uint8_t>(), n, h->hkb,
-	                   counts ? dc.get<uint32_t>() : nullptr, counts ? nullptr : dc.get<double>());
-	HIPCHK(h, hipGetLastError());
+	const uint32_t vw = value_words(h);
+	LAUNCH(h, lookup_keys_kernel<W>, dim3(grid_for(n)), dim3(256), 0, view_of<W>(h->weak, vw), view_of<W>(h->sing, vw), dk.get<uint8_t>(), n, h->hkb,
+	       counts ? dc.get<uint32_t>() : nullptr, counts ? nullptr : dc.get<double>());
 	HIPCHK(h, hipMemcpyAsync(counts ? (void *)counts : (void *)weights, dc.get(), ob * n, hipMemcpyDeviceToHost, h->stream));
 	HIPCHK(h, hipStreamSynchronize(h->stream));
 	return 0;
@@ -535,10 +527,9 @@ template <int W> LutView<W> lut_of(kmr_handle *h) {
 			if (hipMemGetInfo(&fr, &tot) != hipSuccess || fr < bytes + (1ull << 30) || h->lut.alloc(bytes) != hipSuccess) { (void)hipGetLastError(); return v; }
 		}
 
-		const uint32_t vw = h->ext ? 15 : 3;
-		hipLaunchKernelGGL(lut_clear_kernel, dim3(4096), dim3(256), 0, h->stream, h->lut.get<uint64_t>(), 1ull << l2, (uint32_t)(W + 1));
-		hipLaunchKernelGGL(lut_build_kernel<W>, dim3(grid_for(h->weak.n)), dim3(256), 0, h->stream, view_of<W>(h->weak, vw), h->weak.n, h->lut.get<uint64_t>(), (1ull << l2) - 1, 64 - l2, h->hkb);
-		if (hipGetLastError() != hipSuccess) return v;
+		const uint32_t vw = value_words(h);
+		if (launch_status(h->stream, lut_clear_kernel, dim3(4096), dim3(256), 0, h->lut.get<uint64_t>(), 1ull << l2, (uint32_t)(W + 1)) != hipSuccess) return v;
+		if (launch_status(h->stream, lut_build_kernel<W>, dim3(grid_for(h->weak.n)), dim3(256), 0, view_of<W>(h->weak, vw), h->weak.n, h->lut.get<uint64_t>(), (1ull << l2) - 1, 64 - l2, h->hkb) != hipSuccess) return v;
 		h->lut_log2 = l2; h->lut_gen = h->map_gen;
 	}
 	v.slots = h->lut.get<uint64_t>(); v.mask = (1ull << h->lut_log2) - 1; v.shift = 64 - h->lut_log2;
@@ -546,13 +537,13 @@ template <int W> LutView<W> lut_of(kmr_handle *h) {
 }
 
 template <int W> int lookup_reads_t(kmr_handle *h, const ReadsView &rv, uint32_t *dout, const uint64_t *dout_off, bool weak_only = false) {
-	LookupOp<W> op; const uint32_t vw = h->ext ? 15 : 3; op.weak_only = weak_only;
+	LookupOp<W> op; const uint32_t vw = value_words(h); op.weak_only = weak_only;
 	op.lut = weak_only ? lut_of<W>(h) : LutView<W>{nullptr, 0, 0};
 	op.weak = view_of<W>(h->weak, vw); op.sing = view_of<W>(h->sing, vw); op.out = dout; op.out_offsets = dout_off; op.first_read_idx = rv.first_read_idx;
 	return launch_extract<W, false>(h, rv, dev_params(h), op);
 }
 template <int W> int lookup_reads_weighted_t(kmr_handle *h, const ReadsView &rv, double *dout, const uint64_t *dout_off) {
-	LookupWeightOp<W> op; const uint32_t vw = h->ext ? 15 : 3;
+	LookupWeightOp<W> op; const uint32_t vw = value_words(h);
 	op.weak = view_of<W>(h->weak, vw); op.sing = view_of<W>(h->sing, vw); op.out = dout; op.out_offsets = dout_off; op.first_read_idx = rv.first_read_idx;
 	return launch_extract<W, false>(h, rv, dev_params(h), op);
 }
@@ -595,8 +586,7 @@ template <int W, bool EXT, int LEVEL> int launch_partition(kmr_handle *h, const 
 	if (dbg()) fprintf(stderr, "partition level %d W=%d bits=%d shift=%d smem=%zu grid=%d\n", LEVEL, W, bits, shift, smem, grid);
 	HIPCHK(h, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
 	                              (int)partition_direct_smem_bytes<W, EXT, PD_THREADS, PD_RPT, PD_LINE>(max_part_bits(h))));
-	hipLaunchKernelGGL(kern, dim3(grid), dim3(PD_THREADS), smem, h->stream, S, pool_view(h, pool), h->work_counter.get<unsigned int>(), bits, shift);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, kern, dim3(grid), dim3(PD_THREADS), smem, S, pool_view(h, pool), h->work_counter.get<unsigned int>(), bits, shift);
 	return 0;
 }
 
@@ -663,8 +653,7 @@ template <int W, bool EXT> int ensure_l1_state(kmr_handle *h) {
 	if (h->l1_state.cap() == need) return 0;
 	if (h->l1_state) HIPCHK(h, hipStreamSynchronize(h->stream));
 	HIPCHK(h, h->l1_state.alloc(need));
-	hipLaunchKernelGGL(partition_state_init_kernel, dim3(partition_blocks(h)), dim3(256), 0, h->stream, h->l1_state.get<uint8_t>(), stride, h->bits1, (uint32_t)partition_blocks(h));
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, partition_state_init_kernel, dim3(partition_blocks(h)), dim3(256), 0, h->l1_state.get<uint8_t>(), stride, h->bits1, (uint32_t)partition_blocks(h));
 	h->l1_state_dirty = false;
 	return 0;
 }
@@ -739,8 +728,7 @@ int linear_regions(kmr_handle *h, ReadsView &rv, size_t rec_size, uint64_t &tile
 	const uint64_t nu = rv.u_start ? rv.n_units : rv.n_reads;
 	rc = h->kcap.reserve(h, "kcap", 4 * std::max<uint64_t>(nu + 1, 16)); if (rc) return rc;
 	rc = h->koff.reserve(h, "koff", 8 * std::max<uint64_t>(nu + 1, 16)); if (rc) return rc;
-	hipLaunchKernelGGL(kmer_capacity_kernel, dim3(grid_for(nu)), dim3(256), 0, h->stream, rv, h->k, h->kcap.get<uint32_t>());
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, kmer_capacity_kernel, dim3(grid_for(nu)), dim3(256), 0, rv, h->k, h->kcap.get<uint32_t>());
 	rc = exclusive_scan(h, h->kcap.get<uint32_t>(), nu, h->koff.get<uint64_t>()); if (rc) return rc;
 	HIPCHK(h, hipMemcpy(&total_cap, h->koff.get<uint64_t>() + nu, 8, hipMemcpyDeviceToHost));
 	tiles = (nu + 63) / 64;
@@ -767,9 +755,8 @@ template <int W, bool EXT> int extract_by_owner_t(kmr_handle *h, const ReadsView
 		OwnerFn of; of.m = 0; of.off = of.win = of.list_bits = 0;
 		if (h->superkmer_mode && h->sk_exchange) { of.m = h->sk_m; of.off = h->sk_off; of.win = h->sk_win; of.list_bits = h->sk_bits; }
 		auto scatter = dev_pos ? owner_scatter_kernel<W, EXT, true> : owner_scatter_kernel<W, EXT>;      /* (request mode writes positions too) */
-		hipLaunchKernelGGL(scatter, dim3(grid), dim3(OWNER_THREADS), 0, h->stream, (const typename PoolRec<W, EXT>::type *)h->linear.get(), h->koff.get<uint64_t>(), h->tile_count.get<uint32_t>(), tiles, h->hkb,
-		                   h->cfg.world_size, (uint32_t *)dev_records, seg_capacity, (unsigned long long *)dev_seg_counts, h->work_counter.get<unsigned int>(), h->derr.get<uint32_t>(), dev_pos, of);
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, scatter, dim3(grid), dim3(OWNER_THREADS), 0, (const typename PoolRec<W, EXT>::type *)h->linear.get(), h->koff.get<uint64_t>(), h->tile_count.get<uint32_t>(), tiles, h->hkb,
+		       h->cfg.world_size, (uint32_t *)dev_records, seg_capacity, (unsigned long long *)dev_seg_counts, h->work_counter.get<unsigned int>(), h->derr.get<uint32_t>(), dev_pos, of);
 	}
 	return 0;
 }
@@ -795,7 +782,7 @@ template <int W, bool EXT> int add_reads_partition_t(kmr_handle *h, const ReadsV
 			 * input comes out of L2 and only the scatter writes go to HBM -- what the pass would cost if extract fed it from
 			 * registers.  The result is not a spectrum. */
 			const uint64_t distinct = std::max<uint64_t>(1, strtoull(getenv("KMR_DEBUG_SAME_TILE"), nullptr, 10));
-			hipLaunchKernelGGL(same_tile_kernel, dim3(grid_for(tiles)), dim3(256), 0, h->stream, h->koff.get<uint64_t>(), tiles, distinct, total_cap / std::max<uint64_t>(tiles, 1));
+			LAUNCH(h, same_tile_kernel, dim3(grid_for(tiles)), dim3(256), 0, h->koff.get<uint64_t>(), tiles, distinct, total_cap / std::max<uint64_t>(tiles, 1));
 		}
 #endif
 		if (!rc) rc = partition_level1<W, EXT>(h, h->linear.get(), h->koff.get<uint64_t>(), h->tile_count.get<uint32_t>(), tiles, 64, 0, 0, total_cap);
@@ -818,12 +805,11 @@ int build_csr_partition(kmr_handle *h, HostPool &p, uint64_t nl, uint32_t first,
 	const unsigned grid = (unsigned)(((uint64_t)used + CSRP_TILE - 1) / CSRP_TILE);
 	const uint64_t magic = csrp_magic(width);
 	HIPCHK(h, hipMemsetAsync(bin_count, 0, 4 * CSRP_BINS, h->stream));
-	if (used) hipLaunchKernelGGL(csr_bin_hist_kernel, dim3(grid), dim3(CSRP_THREADS), 0, h->stream, cl, used, (uint32_t)nl, magic, nbins, bin_count);
-	hipLaunchKernelGGL(csr_bin_scan_kernel, dim3(1), dim3(CSRP_BINS), 0, h->stream, bin_count, nbins, bin_start, bin_cursor);
-	if (used) hipLaunchKernelGGL(csr_bin_scatter_kernel, dim3(grid), dim3(CSRP_THREADS), 0, h->stream, cl, cc, used, first, (uint32_t)nl, magic, nbins, bin_cursor, pair_list, pair_val);
+	if (used) LAUNCH(h, csr_bin_hist_kernel, dim3(grid), dim3(CSRP_THREADS), 0, cl, used, (uint32_t)nl, magic, nbins, bin_count);
+	LAUNCH(h, csr_bin_scan_kernel, dim3(1), dim3(CSRP_BINS), 0, bin_count, nbins, bin_start, bin_cursor);
+	if (used) LAUNCH(h, csr_bin_scatter_kernel, dim3(grid), dim3(CSRP_THREADS), 0, cl, cc, used, first, (uint32_t)nl, magic, nbins, bin_cursor, pair_list, pair_val);
 	HIPCHK(h, hipFuncSetAttribute((const void *)csr_bin_place_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * width)));
-	hipLaunchKernelGGL(csr_bin_place_kernel, dim3(nbins), dim3(CSRP_PLACE_THREADS), 4 * (size_t)width, h->stream, bin_start, pair_list, pair_val, (uint32_t)nl, width, nbins, list_start, list_chunks);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, csr_bin_place_kernel, dim3(nbins), dim3(CSRP_PLACE_THREADS), 4 * (size_t)width, bin_start, pair_list, pair_val, (uint32_t)nl, width, nbins, list_start, list_chunks);
 	return 0;
 }
 /* head_seen: the pool's head where the caller has it from a wait of its own (sync_state) and nothing has taken a chunk since; without
@@ -831,7 +817,7 @@ int build_csr_partition(kmr_handle *h, HostPool &p, uint64_t nl, uint32_t first,
 int build_csr(kmr_handle *h, HostPool &p, uint64_t nl, uint32_t first, uint64_t **list_start, uint64_t **list_chunks, uint32_t *n_chunks_out, const unsigned int *head_seen = nullptr) {
 	unsigned int used = 0;
 	if (head_seen) used = *head_seen;
-	else { HIPCHK(h, hipMemcpyAsync(&used, p.head.get<unsigned int>(), 4, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream)); }
+	else HIPCHK(h, fetch(h, &used, p.head.get<unsigned int>()));
 	if (used > p.cap) used = p.cap;
 	used = used > first ? used - first : 0;            /* only chunks [first, head) are looked at */
 	const bool by_partition = h->tune.csr_partition && nl >= 1 && nl <= CSRP_MAX_LISTS;
@@ -843,18 +829,17 @@ int build_csr(kmr_handle *h, HostPool &p, uint64_t nl, uint32_t first, uint64_t 
 		{ int arc = arena_get(h, &cnt, nl); if (arc) return arc; }
 		HIPCHK(h, hipMemsetAsync(cnt, 0, 4 * nl, h->stream));
 		const unsigned csr_grid = (unsigned)(((uint64_t)used + CSR_THREADS * CSR_ITEMS - 1) / (CSR_THREADS * CSR_ITEMS));
-		if (used) hipLaunchKernelGGL(chunk_hist_kernel, dim3(csr_grid), dim3(CSR_THREADS), 0, h->stream, p.chunk_list.get<uint32_t>() + first, used, cnt, (uint32_t)nl);
+		if (used) LAUNCH(h, chunk_hist_kernel, dim3(csr_grid), dim3(CSR_THREADS), 0, p.chunk_list.get<uint32_t>() + first, used, cnt, (uint32_t)nl);
 		int rc = exclusive_scan_queue(h, cnt, nl, *list_start); if (rc) return rc;
 		HIPCHK(h, hipMemsetAsync(cnt, 0, 4 * nl, h->stream));
-		if (used) hipLaunchKernelGGL(chunk_scatter_kernel, dim3(csr_grid), dim3(CSR_THREADS), 0, h->stream, p.chunk_list.get<uint32_t>() + first, p.chunk_count.get<uint32_t>() + first, used, first, *list_start, cnt, *list_chunks, (uint32_t)nl);
-		HIPCHK(h, hipGetLastError());
+		if (used) LAUNCH(h, chunk_scatter_kernel, dim3(csr_grid), dim3(CSR_THREADS), 0, p.chunk_list.get<uint32_t>() + first, p.chunk_count.get<uint32_t>() + first, used, first, *list_start, cnt, *list_chunks, (uint32_t)nl);
 	}
 	*n_chunks_out = used;
 	if (dbg()) {
 		unsigned long long hv[2] = {0, 0};
 		DevBuf db; HIPCHK(h, db.alloc(16)); HIPCHK(h, hipMemset(db.get(), 0, 16));
 		unsigned long long *d = db.get<unsigned long long>();
-		if (used) hipLaunchKernelGGL(pool_records_kernel, dim3(grid_for(used)), dim3(256), 0, h->stream, p.chunk_list.get<uint32_t>(), p.chunk_count.get<uint32_t>(), used, d, d + 1);
+		if (used) LAUNCH(h, pool_records_kernel, dim3(grid_for(used)), dim3(256), 0, p.chunk_list.get<uint32_t>(), p.chunk_count.get<uint32_t>(), used, d, d + 1);
 		HIPCHK(h, hipStreamSynchronize(h->stream));
 		HIPCHK(h, hipMemcpy(hv, d, 16, hipMemcpyDeviceToHost));
 		fprintf(stderr, "build_csr: lists %llu chunks %u valid %llu records %llu (expected %llu)\n", (unsigned long long)nl, used, hv[1], hv[0], (unsigned long long)h->stats.raw_good_kmers);
@@ -863,7 +848,7 @@ int build_csr(kmr_handle *h, HostPool &p, uint64_t nl, uint32_t first, uint64_t 
 		DevBuf vb; HIPCHK(h, vb.alloc(24)); HIPCHK(h, hipMemset(vb.get(), 0, 24));
 		unsigned long long *v = vb.get<unsigned long long>();
 		PoolView pvw = pool_view(h, p);
-		with_w_ext(h, [&](auto W, auto EXT) { hipLaunchKernelGGL((verify_lists_kernel<W(), EXT()>), dim3(4096), dim3(256), 0, h->stream, pvw, *list_start, *list_chunks, nl, bits, h->hkb, part_rot(h), v, v + 1, v + 2); });
+		{ int vrc = with_w_ext(h, [&](auto W, auto EXT) -> int { LAUNCH(h, (verify_lists_kernel<W(), EXT()>), dim3(4096), dim3(256), 0, pvw, *list_start, *list_chunks, nl, bits, h->hkb, part_rot(h), v, v + 1, v + 2); return 0; }); if (vrc) return vrc; }
 		HIPCHK(h, hipStreamSynchronize(h->stream));
 		HIPCHK(h, hipMemcpy(vv, v, 24, hipMemcpyDeviceToHost));
 		fprintf(stderr, "verify_lists: records via CSR %llu misfiled %llu zero-weight %llu\n", vv[0], vv[1], vv[2]);
@@ -880,7 +865,7 @@ template <int W, bool EXT, int LOG2S, bool NARROW = false> int launch_count(kmr_
 	auto kern = count_kernel<W, EXT, LOG2S, NARROW>;
 	const size_t smem = count_smem_bytes<W, EXT, LOG2S, NARROW>();
 	HIPCHK(h, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-	hipLaunchKernelGGL(kern, dim3(grid), dim3(COUNT_THREADS), smem, h->stream, pool_view(h, h->l1), ls, lc, nl, out, f, h->work_counter.get<unsigned int>(), list_filter);
+	LAUNCH(h, kern, dim3(grid), dim3(COUNT_THREADS), smem, pool_view(h, h->l1), ls, lc, nl, out, f, h->work_counter.get<unsigned int>(), list_filter);
 	return 0;
 }
 
@@ -946,9 +931,9 @@ int count_clear(kmr_handle *h, const CountPass &p) {
 }
 /* the counters, the cursors and the device error word with one wait */
 int count_read_back(kmr_handle *h, CountPass &p, uint32_t &err) {
-	HIPCHK(h, hipMemcpyAsync(&p.c, p.fc, sizeof(p.c), hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipMemcpyAsync(p.cur, p.cursors, 16, hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(h, hipMemcpyAsync(&err, h->derr.get<uint32_t>(), 4, hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(h, hipStreamSynchronize(h->stream));
+	HIPCHK(h, fetch_queue(h, &p.c, p.fc)); HIPCHK(h, fetch_queue(h, p.cur, p.cursors, 2));
+	HIPCHK(h, fetch_queue(h, &err, h->derr.get<uint32_t>()));
+	HIPCHK(h, stream_wait(h));
 	return 0;
 }
 /* The count pass, run again with doubled entry buffers while they overflow (ERR_ENTRIES_FULL), up to their bounds and eight times at
@@ -992,10 +977,9 @@ template <int W, bool EXT> int probe_distinct_share(kmr_handle *h, const uint64_
 	const size_t tbytes = 8 * ((size_t)n_probes * PROBE_SLOTS + 4);
 	int rc = arena_alloc(h, (void **)&dpr, tbytes); if (rc) return rc;
 	HIPCHK(h, hipMemsetAsync(dpr, 0, tbytes, h->stream));
-	hipLaunchKernelGGL((distinct_probe_kernel<W, EXT>), dim3(n_probes * PROBE_SPLIT), dim3(256), 0, h->stream, pool_view(h, h->l1), ls1, lc1, nl1, h->hkb, part_rot(h),
-	                   (int)h->bits1, n_probes, dpr + 4, dpr);
-	HIPCHK(h, hipGetLastError());
-	HIPCHK(h, hipMemcpyAsync(hpr, dpr, 32, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
+	LAUNCH(h, (distinct_probe_kernel<W, EXT>), dim3(n_probes * PROBE_SPLIT), dim3(256), 0, pool_view(h, h->l1), ls1, lc1, nl1, h->hkb, part_rot(h),
+	       (int)h->bits1, n_probes, dpr + 4, dpr);
+	HIPCHK(h, fetch(h, hpr, dpr, 4));
 	if (hpr[0] >= 256) { distinct_share = std::min(1.0, std::max(0.01, (double)hpr[1] / (double)hpr[0])); repeated_share = std::min(0.5, (double)hpr[2] / (double)hpr[0]); }
 	if (dbg()) fprintf(stderr, "distinct probe: %llu records, %llu distinct (%llu repeated) -> shares %.3f %.3f\n", hpr[0], hpr[1], hpr[2], distinct_share, repeated_share);
 	return 0;
@@ -1072,19 +1056,16 @@ template <int W, bool EXT> int partition_count_pass(kmr_handle *h, CountPass &p,
 			/* extension values at k <= 32: 16-bit tallies for every list of at most 65 535 records (two blocks per CU), then
 			 * the wide table for whatever is longer */
 			rc = launch_count<W, EXT, COUNT_LOG2S, true>(h, grid, ls, lc, nl, out, p.f, 1); if (rc) return rc;
-			HIPCHK(h, hipGetLastError());
 			/* is any list longer than the narrow tallies can take?  (the work counter word doubles as the maximum) */
 			rc = zero_work_counter(h); if (rc) return rc;
-			hipLaunchKernelGGL(max_list_chunks_kernel, dim3(grid_for(nl)), dim3(256), 0, h->stream, ls, nl, h->work_counter.get<unsigned int>());
+			LAUNCH(h, max_list_chunks_kernel, dim3(grid_for(nl)), dim3(256), 0, ls, nl, h->work_counter.get<unsigned int>());
 			unsigned int longest = 0;
-			HIPCHK(h, hipMemcpyAsync(&longest, h->work_counter.get<unsigned int>(), 4, hipMemcpyDeviceToHost, h->stream));
-			HIPCHK(h, hipStreamSynchronize(h->stream));
+			HIPCHK(h, fetch(h, &longest, h->work_counter.get<unsigned int>()));
 			rc = zero_work_counter(h); if (rc) return rc;
 			if (longest > COUNT_NARROW_CHUNKS) { rc = launch_count<W, EXT, COUNT_LOG2S>(h, std::min(grid, part_grid(h)), ls, lc, nl, out, p.f, 2); if (rc) return rc; }
 		} else {
 			rc = launch_count<W, EXT, COUNT_LOG2S>(h, grid, ls, lc, nl, out, p.f, 0); if (rc) return rc;
 		}
-		HIPCHK(h, hipGetLastError());
 		return 0;
 	};
 	return count_attempts(h, p, make_room, [&](const CountOut &out, bool, uint32_t &) -> int {
@@ -1186,8 +1167,7 @@ template <int W> int binned_buckets_t(kmr_handle *h, uint64_t wslots, uint64_t w
 		int per_cu = 0;
 		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)gk, BB_GROUP_THREADS, bb_group_smem_bytes<W>()) != hipSuccess || per_cu < 1) per_cu = 4;
 		if (dbg()) fprintf(stderr, "bb_group<W=%d>: %d blocks per CU, %llu groups\n", W, per_cu, (unsigned long long)groups);
-		hipLaunchKernelGGL(gk, dim3((unsigned)std::min<uint64_t>(groups, (uint64_t)num_cus(h) * per_cu)), dim3(BB_GROUP_THREADS), bb_group_smem_bytes<W>(), h->stream, entries, wm.keys.get<uint64_t>(), wm.vals.get<uint32_t>(), gs, gc, groups, g, h->hkb, nb, wm.start.get<uint64_t>(), wn, h->derr.get<uint32_t>(), in_stride, overflow);
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, gk, dim3((unsigned)std::min<uint64_t>(groups, (uint64_t)num_cus(h) * per_cu)), dim3(BB_GROUP_THREADS), bb_group_smem_bytes<W>(), entries, wm.keys.get<uint64_t>(), wm.vals.get<uint32_t>(), gs, gc, groups, g, h->hkb, nb, wm.start.get<uint64_t>(), wn, h->derr.get<uint32_t>(), in_stride, overflow);
 		return 0;
 	};
 	const uint32_t shift1 = B - bits1, shift2 = g;
@@ -1203,20 +1183,20 @@ template <int W> int binned_buckets_t(kmr_handle *h, uint64_t wslots, uint64_t w
 		rc = arena_get(h, &gstart, groups + 1); if (rc) return rc;
 		rc = arena_get(h, &ovf, 1); if (rc) return rc;
 		HIPCHK(h, hipMemsetAsync(fill, 0, 4 * (bits2 ? bins1 + groups : groups), h->stream)); HIPCHK(h, hipMemsetAsync(ovf, 0, 4, h->stream));
-		auto scatter = [&](const BbInput &in, uint32_t shift, uint32_t bits, uint32_t *f, uint64_t limit, uint64_t stride, uint64_t *out) {
+		auto scatter = [&](const BbInput &in, uint32_t shift, uint32_t bits, uint32_t *f, uint64_t limit, uint64_t stride, uint64_t *out) -> int {
 			const unsigned grid = scatter_grid(in.n_slots);
-			if (W == 1 && !h->tune.bb_reload) hipLaunchKernelGGL((bb_scatter_fixed_kernel<W, W == 1>), dim3(grid), dim3(BB_THREADS), 0, h->stream, in, shift, bits, h->hkb, nb, f, (uint32_t)limit, stride, out, ovf);
-			else hipLaunchKernelGGL((bb_scatter_fixed_kernel<W, false>), dim3(grid), dim3(BB_THREADS), 0, h->stream, in, shift, bits, h->hkb, nb, f, (uint32_t)limit, stride, out, ovf);
+			if (W == 1 && !h->tune.bb_reload) LAUNCH(h, (bb_scatter_fixed_kernel<W, W == 1>), dim3(grid), dim3(BB_THREADS), 0, in, shift, bits, h->hkb, nb, f, (uint32_t)limit, stride, out, ovf);
+			else LAUNCH(h, (bb_scatter_fixed_kernel<W, false>), dim3(grid), dim3(BB_THREADS), 0, in, shift, bits, h->hkb, nb, f, (uint32_t)limit, stride, out, ovf);
+			return 0;
 		};
 		uint32_t *gfill = fill;
-		if (!bits2) scatter(in1, shift1, bits1, fill, lim2, stride2, h->ue2.get<uint64_t>());
+		if (!bits2) { rc = scatter(in1, shift1, bits1, fill, lim2, stride2, h->ue2.get<uint64_t>()); if (rc) return rc; }
 		else {
-			scatter(in1, shift1, bits1, fill, lim1, stride1, h->ue2.get<uint64_t>());
+			rc = scatter(in1, shift1, bits1, fill, lim1, stride1, h->ue2.get<uint64_t>()); if (rc) return rc;
 			BbInput in2; in2.entries = h->ue2.get<uint64_t>(); in2.seg_start = nullptr; in2.seg_count = fill; in2.n_seg = (uint32_t)bins1; in2.n_slots = bins1 * stride1; in2.holes = 0; in2.seg_stride = stride1;
 			gfill = fill + bins1;
-			scatter(in2, shift2, bits2, gfill, lim2, stride2, h->ue.get<uint64_t>());
+			rc = scatter(in2, shift2, bits2, gfill, lim2, stride2, h->ue.get<uint64_t>()); if (rc) return rc;
 		}
-		HIPCHK(h, hipGetLastError());
 		/* the map is dense: a group's entries go where the groups before it end */
 		rc = exclusive_scan_queue(h, gfill, groups, gstart); if (rc) return rc;
 		rc = group_launch(bits2 ? h->ue.get<uint64_t>() : h->ue2.get<uint64_t>(), gstart, gfill, stride2, ovf); if (rc) return rc;
@@ -1232,17 +1212,17 @@ template <int W> int binned_buckets_t(kmr_handle *h, uint64_t wslots, uint64_t w
 	HIPCHK(h, hipMemsetAsync(hist1, 0, 4 * bins1, h->stream)); HIPCHK(h, hipMemsetAsync(dmax, 0, 4, h->stream));
 	auto hist_grid = [&](uint64_t n_slots, uint32_t &tpb) { const uint64_t tiles = (n_slots + BB_TILE - 1) / BB_TILE; tpb = (uint32_t)std::max<uint64_t>(1, (tiles + 2047) / 2048); return (unsigned)((tiles + tpb - 1) / tpb); };
 	uint32_t tpb = 1; unsigned grid = hist_grid(wslots, tpb);
-	hipLaunchKernelGGL(bb_hist_kernel<W>, dim3(grid), dim3(BB_THREADS), 0, h->stream, in1, shift1, bits1, h->hkb, nb, tpb, hist1);
+	LAUNCH(h, bb_hist_kernel<W>, dim3(grid), dim3(BB_THREADS), 0, in1, shift1, bits1, h->hkb, nb, tpb, hist1);
 	unsigned int mx = 0;
 	if (!bits2) {
 		/* one level: its bins are the groups, their scan is where the groups lie in the map */
-		hipLaunchKernelGGL(bb_pad_kernel, dim3(grid_for(bins1)), dim3(256), 0, h->stream, (const uint32_t *)hist1, bins1, (uint32_t *)nullptr, dmax);
-		HIPCHK(h, hipMemcpyAsync(&mx, dmax, 4, hipMemcpyDeviceToHost, h->stream));
+		LAUNCH(h, bb_pad_kernel, dim3(grid_for(bins1)), dim3(256), 0, (const uint32_t *)hist1, bins1, (uint32_t *)nullptr, dmax);
+		HIPCHK(h, fetch_queue(h, &mx, dmax));
 		rc = exclusive_scan(h, hist1, bins1, start1); if (rc) return rc;      /* (synchronises) */
 		if (mx > bb_group_cap<W>()) return 0;
 		rc = scratch(wn); if (rc) return rc;
-		hipLaunchKernelGGL(bb_cursor_init_kernel, dim3(grid_for(bins1)), dim3(256), 0, h->stream, (const uint64_t *)start1, bins1, cursor);
-		hipLaunchKernelGGL(bb_scatter_kernel<W>, dim3(scatter_grid(wslots)), dim3(BB_THREADS), 0, h->stream, in1, shift1, bits1, h->hkb, nb, cursor, h->ue2.get<uint64_t>());
+		LAUNCH(h, bb_cursor_init_kernel, dim3(grid_for(bins1)), dim3(256), 0, (const uint64_t *)start1, bins1, cursor);
+		LAUNCH(h, bb_scatter_kernel<W>, dim3(scatter_grid(wslots)), dim3(BB_THREADS), 0, in1, shift1, bits1, h->hkb, nb, cursor, h->ue2.get<uint64_t>());
 		rc = map_arrays(); if (rc) return rc;
 		rc = group_launch(h->ue2.get<uint64_t>(), start1, hist1, 0, nullptr); if (rc) return rc;
 		h->last_bb_path = 1;
@@ -1250,25 +1230,25 @@ template <int W> int binned_buckets_t(kmr_handle *h, uint64_t wslots, uint64_t w
 		return 0;
 	}
 	/* two levels: the first one's bins start at tile boundaries (the second level reads them tile by tile) */
-	hipLaunchKernelGGL(bb_pad_kernel, dim3(grid_for(bins1)), dim3(256), 0, h->stream, (const uint32_t *)hist1, bins1, pad1, dmax);
+	LAUNCH(h, bb_pad_kernel, dim3(grid_for(bins1)), dim3(256), 0, (const uint32_t *)hist1, bins1, pad1, dmax);
 	rc = exclusive_scan(h, pad1, bins1, start1); if (rc) return rc;
 	uint64_t padded_total = 0;
 	HIPCHK(h, hipMemcpy(&padded_total, start1 + bins1, 8, hipMemcpyDeviceToHost));
 	rc = scratch(std::max(padded_total, wn)); if (rc) return rc;
-	hipLaunchKernelGGL(bb_cursor_init_kernel, dim3(grid_for(bins1)), dim3(256), 0, h->stream, (const uint64_t *)start1, bins1, cursor);
-	hipLaunchKernelGGL(bb_scatter_kernel<W>, dim3(scatter_grid(wslots)), dim3(BB_THREADS), 0, h->stream, in1, shift1, bits1, h->hkb, nb, cursor, h->ue2.get<uint64_t>());
+	LAUNCH(h, bb_cursor_init_kernel, dim3(grid_for(bins1)), dim3(256), 0, (const uint64_t *)start1, bins1, cursor);
+	LAUNCH(h, bb_scatter_kernel<W>, dim3(scatter_grid(wslots)), dim3(BB_THREADS), 0, in1, shift1, bits1, h->hkb, nb, cursor, h->ue2.get<uint64_t>());
 	BbInput in2; in2.entries = h->ue2.get<uint64_t>(); in2.seg_start = start1; in2.seg_count = hist1; in2.n_seg = (uint32_t)bins1; in2.n_slots = padded_total; in2.holes = 0; in2.seg_stride = 0;
 	HIPCHK(h, hipMemsetAsync(hist2, 0, 4 * groups, h->stream)); HIPCHK(h, hipMemsetAsync(dmax, 0, 4, h->stream));
 	grid = hist_grid(padded_total, tpb);
-	hipLaunchKernelGGL(bb_hist_kernel<W>, dim3(grid), dim3(BB_THREADS), 0, h->stream, in2, shift2, bits2, h->hkb, nb, tpb, hist2);
-	hipLaunchKernelGGL(bb_pad_kernel, dim3(grid_for(groups)), dim3(256), 0, h->stream, (const uint32_t *)hist2, groups, (uint32_t *)nullptr, dmax);
-	HIPCHK(h, hipMemcpyAsync(&mx, dmax, 4, hipMemcpyDeviceToHost, h->stream));
+	LAUNCH(h, bb_hist_kernel<W>, dim3(grid), dim3(BB_THREADS), 0, in2, shift2, bits2, h->hkb, nb, tpb, hist2);
+	LAUNCH(h, bb_pad_kernel, dim3(grid_for(groups)), dim3(256), 0, (const uint32_t *)hist2, groups, (uint32_t *)nullptr, dmax);
+	HIPCHK(h, fetch_queue(h, &mx, dmax));
 	rc = exclusive_scan(h, hist2, groups, gstart); if (rc) return rc;
 	/* the packed entries the count pass wrote are about to be overwritten (the second level writes where the first one read): a
 	 * group too large for the LDS arrays sends the build down the other path BEFORE that */
 	if (mx > bb_group_cap<W>() || packed_entries(h, h->ue) < wn) return 0;
-	hipLaunchKernelGGL(bb_cursor_init_kernel, dim3(grid_for(groups)), dim3(256), 0, h->stream, (const uint64_t *)gstart, groups, cursor);
-	hipLaunchKernelGGL(bb_scatter_kernel<W>, dim3(scatter_grid(padded_total)), dim3(BB_THREADS), 0, h->stream, in2, shift2, bits2, h->hkb, nb, cursor, h->ue.get<uint64_t>());
+	LAUNCH(h, bb_cursor_init_kernel, dim3(grid_for(groups)), dim3(256), 0, (const uint64_t *)gstart, groups, cursor);
+	LAUNCH(h, bb_scatter_kernel<W>, dim3(scatter_grid(padded_total)), dim3(BB_THREADS), 0, in2, shift2, bits2, h->hkb, nb, cursor, h->ue.get<uint64_t>());
 	rc = map_arrays(); if (rc) return rc;
 	rc = group_launch(h->ue.get<uint64_t>(), gstart, hist2, 0, nullptr); if (rc) return rc;
 	h->last_bb_path = 1;
@@ -1280,7 +1260,7 @@ template <int W> int binned_buckets_t(kmr_handle *h, uint64_t wslots, uint64_t w
  * kmr_buckets.hpp needs none, and if it declines they are counted here.  overflow: null when the maps are complete and the stream
  * drained; else (bins of one capacity, binned_buckets_t) everything is on the stream and the caller waits once, for this word */
 template <int W> int finish_maps_t(kmr_handle *h, uint32_t *wc, uint32_t *sc, uint64_t wslots, uint64_t sslots, uint64_t wn, uint64_t sn, bool keepSing, uint32_t *&overflow, bool weak_uncounted, bool fixed_bins) {
-	const uint32_t vw = h->ext ? 15 : 3;
+	const uint32_t vw = value_words(h);
 	DevMap &wm = h->weak, &sm = h->sing;
 	clear_map(wm); clear_map(sm);          /* the buffers of the previous build are reused when they are large enough */
 	wm.nb = h->nb_weak; wm.n = wn; wm.present = true;
@@ -1294,8 +1274,7 @@ template <int W> int finish_maps_t(kmr_handle *h, uint32_t *wc, uint32_t *sc, ui
 		if (!weakDone) {      /* the other path wants keys and values apart and a count per bucket */
 			rc = ensure_weak_apart(h, std::max<uint64_t>(wslots, 16), vw); if (rc) return rc;
 			HIPCHK(h, hipMemsetAsync(wc, 0, 4 * wm.nb, h->stream));
-			if (wslots) hipLaunchKernelGGL(bb_unpack_kernel<W>, dim3(grid_for(wslots)), dim3(256), 0, h->stream, (const uint64_t *)h->ue.get<uint64_t>(), wslots, h->hkb, wm.nb, (uint64_t *)h->uw_keys.get(), (uint32_t *)h->uw_vals.get(), wc);
-			HIPCHK(h, hipGetLastError());
+			if (wslots) LAUNCH(h, bb_unpack_kernel<W>, dim3(grid_for(wslots)), dim3(256), 0, (const uint64_t *)h->ue.get<uint64_t>(), wslots, h->hkb, wm.nb, (uint64_t *)h->uw_keys.get(), (uint32_t *)h->uw_vals.get(), wc);
 		}
 	}
 	if (!weakDone) { rc = exclusive_scan(h, wc, wm.nb, wm.start.get<uint64_t>()); if (rc) return rc; }
@@ -1310,29 +1289,21 @@ template <int W> int finish_maps_t(kmr_handle *h, uint32_t *wc, uint32_t *sc, ui
 	if (h->ext) { rc = sm.spkt.reserve(h, "singleton map spkt", std::max<uint64_t>(4 * sm.n, 8)); if (rc) return rc; }
 	HIPCHK(h, hipMemsetAsync(wc, 0, 4 * wm.nb, h->stream)); HIPCHK(h, hipMemsetAsync(sc, 0, 4 * sm.nb, h->stream));
 	if (weakDone) { /* keys, values and bucket starts are in place */ }
-	else if (wm.n && vw > 4) hipLaunchKernelGGL((entry_scatter_kernel<W, true>), dim3(grid_for(wslots)), dim3(256), 0, h->stream, (const uint64_t *)h->uw_keys.get(), (const uint32_t *)h->uw_vals.get(),
-	                            (const uint8_t *)nullptr, (const uint32_t *)nullptr, wslots, vw, h->hkb, wm.nb, wm.start.get<uint64_t>(), wc, wm.keys.get<uint64_t>(), wm.vals.get<uint32_t>(), (uint8_t *)nullptr, (uint32_t *)nullptr);
+	else if (wm.n && vw > 4) LAUNCH(h, (entry_scatter_kernel<W, true>), dim3(grid_for(wslots)), dim3(256), 0, (const uint64_t *)h->uw_keys.get(), (const uint32_t *)h->uw_vals.get(),
+	                (const uint8_t *)nullptr, (const uint32_t *)nullptr, wslots, vw, h->hkb, wm.nb, wm.start.get<uint64_t>(), wc, wm.keys.get<uint64_t>(), wm.vals.get<uint32_t>(), (uint8_t *)nullptr, (uint32_t *)nullptr, nullptr, 6);
 	else if (wm.n) {
 		/* lists cut by minimizer (build_mode 3) scatter their entries over unrelated buckets: 64-bit cursors that start at the buckets'
 		 * first entries, one returning add per entry */
 		unsigned long long *cur64 = nullptr;
 		if (h->superkmer_mode && arena_get(h, &cur64, wm.nb) == 0) HIPCHK(h, hipMemcpyAsync(cur64, wm.start.get<uint64_t>(), 8 * wm.nb, hipMemcpyDeviceToDevice, h->stream));
 		else cur64 = nullptr;
-		hipLaunchKernelGGL(entry_scatter_kernel<W>, dim3(grid_for(wslots)), dim3(256), 0, h->stream, (const uint64_t *)h->uw_keys.get(), (const uint32_t *)h->uw_vals.get(),
-		                            (const uint8_t *)nullptr, (const uint32_t *)nullptr, wslots, vw, h->hkb, wm.nb, wm.start.get<uint64_t>(), wc, wm.keys.get<uint64_t>(), wm.vals.get<uint32_t>(), (uint8_t *)nullptr, (uint32_t *)nullptr, cur64, 6);
+		LAUNCH(h, entry_scatter_kernel<W>, dim3(grid_for(wslots)), dim3(256), 0, (const uint64_t *)h->uw_keys.get(), (const uint32_t *)h->uw_vals.get(),
+		                (const uint8_t *)nullptr, (const uint32_t *)nullptr, wslots, vw, h->hkb, wm.nb, wm.start.get<uint64_t>(), wc, wm.keys.get<uint64_t>(), wm.vals.get<uint32_t>(), (uint8_t *)nullptr, (uint32_t *)nullptr, cur64, 6);
 	}
-	if (sm.n) hipLaunchKernelGGL(entry_scatter_kernel<W>, dim3(grid_for(sslots)), dim3(256), 0, h->stream, (const uint64_t *)h->us_keys.get(), (const uint32_t *)nullptr,
-	                            (const uint8_t *)h->us_b8.get(), (const uint32_t *)h->us_pkt.get(), sslots, 0u, h->hkb, sm.nb, sm.start.get<uint64_t>(), sc, sm.keys.get<uint64_t>(), (uint32_t *)nullptr, sm.sweight.get<uint8_t>(), h->ext ? sm.spkt.get<uint32_t>() : (uint32_t *)nullptr);
-	HIPCHK(h, hipGetLastError());
-	SortView<W> sv; sv.keys = wm.keys.get<uint64_t>(); sv.vals = wm.vals.get<uint32_t>(); sv.b8 = nullptr; sv.pkt = nullptr; sv.vw = vw;
-	if (weakDone) { /* sorted by bb_group_kernel */ }
-	else if (h->ext) hipLaunchKernelGGL((sort_buckets_kernel<W, 15>), dim3(grid_for(wm.nb, 4, 1 << 20)), dim3(256), 0, h->stream, sv, wm.start.get<uint64_t>(), wm.nb);
-	else hipLaunchKernelGGL((sort_buckets_kernel<W, 3>), dim3(grid_for(wm.nb, 4, 1 << 20)), dim3(256), 0, h->stream, sv, wm.start.get<uint64_t>(), wm.nb);
-	if (sm.n) {
-		SortView<W> ss; ss.keys = sm.keys.get<uint64_t>(); ss.vals = nullptr; ss.b8 = sm.sweight.get<uint8_t>(); ss.pkt = h->ext ? sm.spkt.get<uint32_t>() : nullptr; ss.vw = 0;
-		hipLaunchKernelGGL((sort_buckets_kernel<W, 0>), dim3(grid_for(sm.nb, 4, 1 << 20)), dim3(256), 0, h->stream, ss, sm.start.get<uint64_t>(), sm.nb);
-	}
-	HIPCHK(h, hipGetLastError());
+	if (sm.n) LAUNCH(h, entry_scatter_kernel<W>, dim3(grid_for(sslots)), dim3(256), 0, (const uint64_t *)h->us_keys.get(), (const uint32_t *)nullptr,
+	                (const uint8_t *)h->us_b8.get(), (const uint32_t *)h->us_pkt.get(), sslots, 0u, h->hkb, sm.nb, sm.start.get<uint64_t>(), sc, sm.keys.get<uint64_t>(), (uint32_t *)nullptr, sm.sweight.get<uint8_t>(), h->ext ? sm.spkt.get<uint32_t>() : (uint32_t *)nullptr, nullptr, 6);
+	if (!weakDone) { rc = sort_map_buckets<W>(h, wm, true); if (rc) return rc; }      /* (else sorted by bb_group_kernel) */
+	if (sm.n) { rc = sort_map_buckets<W>(h, sm, false); if (rc) return rc; }
 	if (!overflow) HIPCHK(h, hipStreamSynchronize(h->stream));      /* (bins of one capacity: the caller waits once, for the overflow word) */
 	return 0;
 }
@@ -1383,8 +1354,7 @@ template <typename... P, typename... A> int launch_sk_tiles(kmr_handle *h, void 
 	if (blocks == 0) return 0;
 	blocks = std::min<uint64_t>(blocks, (uint64_t)num_cus(h) * per_cu);
 	if (dbg()) { int nb = 0; hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)kern, waves * 64, smem); fprintf(stderr, "%s<W=%d,WIN=%d>: %d blocks of %d waves per CU (LDS %zu), grid %llu, m=%u off=%u bits=%u\n", name, w, win, nb, waves, smem, (unsigned long long)blocks, sp.m, sp.off, sp.list_bits); }
-	hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(waves * 64), smem, h->stream, rv, args...);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, kern, dim3((unsigned)blocks), dim3(waves * 64), smem, rv, args...);
 	return 0;
 }
 template <int W, int WIN, bool FILT, bool EXT = false> int launch_sk_extract(kmr_handle *h, const ReadsView &rv, const SkParams &sp, const DevParams &dp) {
@@ -1429,10 +1399,8 @@ int sk_uniform_weight(kmr_handle *h, const ReadsView &rv, const FeedHints &hints
 	HIPCHK(h, hipMemcpyAsync(h->qrange.get<unsigned int>(), got, sizeof(got), hipMemcpyHostToDevice, h->stream));
 	/* half a block per CU of the launch's eight walks the offsets (a C2 batch: 80 MB of them beside 1.5 GB of qualities) */
 	const unsigned qr_blocks = (unsigned)num_cus(h) * 8, len_blocks = longest ? (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(qr_blocks / 16, (rv.n_reads + 4095) / 4096)) : 0u;
-	hipLaunchKernelGGL(sk_qual_range_kernel, dim3(qr_blocks), dim3(256), 0, h->stream, rv.quals, rv.offsets, rv.n_reads, h->qrange.get<unsigned int>(), h->qrange.get<unsigned int>() + QR_MAX, len_blocks);
-	HIPCHK(h, hipGetLastError());
-	HIPCHK(h, hipMemcpyAsync(got, h->qrange.get<unsigned int>(), sizeof(got), hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(h, hipStreamSynchronize(h->stream));
+	LAUNCH(h, sk_qual_range_kernel, dim3(qr_blocks), dim3(256), 0, rv.quals, rv.offsets, rv.n_reads, h->qrange.get<unsigned int>(), h->qrange.get<unsigned int>() + QR_MAX, len_blocks);
+	HIPCHK(h, fetch(h, got, h->qrange.get<unsigned int>(), QR_MAX + 1));
 	if (longest) { *longest = got[QR_MAX]; *have_longest = true; }
 	if (got[0] != got[1]) { h->qual_mixed = got[0] < got[1]; return 0; }      /* (255 > 0: no quality byte at all) */
 	sk_weight_of_quality(h, got[0], lean, wK);
@@ -1482,8 +1450,7 @@ template <int W> int sk_size_lists(kmr_handle *h, uint64_t job_bases, bool lean)
 	}
 	const uint64_t nl0 = sk_list_count(h->sk_bits);
 	HIPCHK(h, h->sk_state.alloc(8 * nl0));
-	hipLaunchKernelGGL(sk_state_init_kernel, dim3(grid_for(nl0)), dim3(256), 0, h->stream, h->sk_state.get<unsigned long long>(), nl0);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, sk_state_init_kernel, dim3(grid_for(nl0)), dim3(256), 0, h->sk_state.get<unsigned long long>(), nl0);
 	return 0;
 }
 /* A job fed in many calls (estimated_raw_kmers says how much is to come) or in the pieces of one host call (call_bases) gets its pool in ONE
@@ -1523,8 +1490,7 @@ template <int W> int sk_launch_extraction(kmr_handle *h, const ReadsView &rv, co
 template <int W> int sk_track_call(kmr_handle *h, const ReadsView &rvAll, const DevParams &dp) {
 	const uint64_t n = rvAll.n_reads;
 	std::vector<SkTrackRec> recs(n);
-	HIPCHK(h, hipMemcpyAsync(recs.data(), h->trk.get<SkTrackRec>(), n * sizeof(SkTrackRec), hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(h, hipStreamSynchronize(h->stream));
+	HIPCHK(h, fetch(h, recs.data(), h->trk.get<SkTrackRec>(), n));
 	std::vector<SkBoundary> bd; std::vector<uint64_t> good_before;
 	const bool walkable = (dp.sub_wnb | dp.sub_snb) == 0;      /* (a subtracting reference decides per k-mer what is raw: read ends there) */
 	for (uint64_t r = 0; r < n; r++) {
@@ -1546,9 +1512,8 @@ template <int W> int sk_track_call(kmr_handle *h, const ReadsView &rvAll, const 
 		auto chk = [&](hipError_t e) { return e == hipSuccess ? 0 : fail(h, KMR_ERR_HIP, std::string("size tracker boundaries: ") + hipGetErrorString(e)); };
 		int rc = chk(hipMemcpyAsync(dbd, bd.data(), bd.size() * sizeof(SkBoundary), hipMemcpyHostToDevice, h->stream)); if (rc) return rc;
 		ReadsView rv = rvAll; rv.u_start = rv.u_end = rv.u_read = nullptr; rv.n_units = 0;      /* (whole reads: the caller's work units do not apply) */
-		hipLaunchKernelGGL(sk_track_boundary_kernel<W>, dim3((unsigned)((bd.size() + 63) / 64)), dim3(64), 0, h->stream, rv, dp, dbd, (uint32_t)bd.size());
-		rc = chk(hipGetLastError()); if (rc) return rc;
-		rc = chk(hipMemcpyAsync(bd.data(), dbd, bd.size() * sizeof(SkBoundary), hipMemcpyDeviceToHost, h->stream)); if (rc) return rc;
+		rc = chk(launch_status(h->stream, sk_track_boundary_kernel<W>, dim3((unsigned)((bd.size() + 63) / 64)), dim3(64), 0, rv, dp, dbd, (uint32_t)bd.size())); if (rc) return rc;
+		rc = chk(fetch_queue(h, bd.data(), dbd, bd.size())); if (rc) return rc;
 		rc = chk(hipStreamSynchronize(h->stream)); if (rc) return rc;
 	}
 	for (size_t i = 0; i < bd.size(); i++) { h->trk_bounds.push_back(bd[i].ordinal); h->trk_snap_good.push_back(good_before[i] + bd[i].good); }
@@ -1570,8 +1535,7 @@ template <int W> int add_reads_superkmer_t(kmr_handle *h, const ReadsView &rvAll
 	if (hints.packed && (!lean || h->cfg.size_tracker)) return fail(h, KMR_ERR_STATE, "internal: a packed batch handed to an extraction that wants text");      /* (sk_packed_direct_ok said otherwise) */
 	if (n) sk_note_call_weight(h, lean, wK);
 	if (n) {      /* the ordinals this call stamps, for sk_count_blocks: rv.stream_base (kmr_set_stream_origin, what earlier calls added, less FeedHints' piece origin) + a base's offset */
-		hipLaunchKernelGGL(sk_ord_span_kernel, dim3(1), dim3(64), 0, h->stream, rvAll.offsets, n, rvAll.stream_base, h->dstats.get<DevStats>());
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, sk_ord_span_kernel, dim3(1), dim3(64), 0, rvAll.offsets, n, rvAll.stream_base, h->dstats.get<DevStats>());
 	}
 	if (!h->sk_state) { rc = sk_size_lists<W>(h, std::max<uint64_t>(total_bases, hints.call_bases), lean); if (rc) return rc; }
 	if (tracking) { h->trk_n = 0; rc = h->trk.reserve(h, "trk", n * sizeof(SkTrackRec)); if (rc) return rc; HIPCHK(h, hipMemsetAsync(h->trk.get<SkTrackRec>(), 0, n * sizeof(SkTrackRec), h->stream)); }      /* (sk_track_call) */
@@ -1622,9 +1586,8 @@ template <int W> int saturated_fix_t(kmr_handle *h, const uint64_t *ls, const ui
 		if (dalloc(bentry, 8 * cap) != hipSuccess || dalloc(blist, 4 * cap) != hipSuccess) return no_mem("the key list", 12 * cap);
 		d_entry = bentry.get<uint64_t>(); d_list = blist.get<uint32_t>();
 		HIPCHK(h, hipMemsetAsync(dfound, 0, 8, h->stream));
-		hipLaunchKernelGGL(sat_find_kernel<W>, dim3(grid_for(wm.n)), dim3(256), 0, h->stream, (const uint64_t *)wm.keys.get<uint64_t>(), (const uint32_t *)wm.vals.get<uint32_t>(), wm.n, h->sk_m, h->sk_off, h->sk_win, list_bits, dfound, cap, d_entry, d_list, h->ext ? 15u : 3u);
-		HIPCHK(h, hipGetLastError());
-		HIPCHK(h, hipMemcpyAsync(&found, dfound, 8, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
+		LAUNCH(h, sat_find_kernel<W>, dim3(grid_for(wm.n)), dim3(256), 0, (const uint64_t *)wm.keys.get<uint64_t>(), (const uint32_t *)wm.vals.get<uint32_t>(), wm.n, h->sk_m, h->sk_off, h->sk_win, list_bits, dfound, cap, d_entry, d_list, value_words(h));
+		HIPCHK(h, fetch(h, &found, dfound));
 		if (found <= cap) break;
 		cap = found;      /* more entries at 256 or more than expected: again with room for all */
 	}
@@ -1647,8 +1610,7 @@ template <int W> int saturated_fix_t(kmr_handle *h, const uint64_t *ls, const ui
 	{
 		DevBuf bc0, bc1;
 		if (dalloc(bc0, 8 * dl.size()) != hipSuccess || dalloc(bc1, 8 * dl.size()) != hipSuccess) return no_mem("the chunk ranges", 16 * dl.size());
-		hipLaunchKernelGGL(sat_gather_kernel, dim3(grid_for(dl.size())), dim3(256), 0, h->stream, ls, (const uint32_t *)d_list, (uint64_t)dl.size(), bc0.get<uint64_t>(), bc1.get<uint64_t>());
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, sat_gather_kernel, dim3(grid_for(dl.size())), dim3(256), 0, ls, (const uint32_t *)d_list, (uint64_t)dl.size(), bc0.get<uint64_t>(), bc1.get<uint64_t>());
 		HIPCHK(h, hipMemcpy(c0.data(), bc0.get<uint64_t>(), 8 * dl.size(), hipMemcpyDeviceToHost)); HIPCHK(h, hipMemcpy(c1.data(), bc1.get<uint64_t>(), 8 * dl.size(), hipMemcpyDeviceToHost));
 	}
 	blist = DevBuf();
@@ -1690,11 +1652,10 @@ template <int W> int saturated_fix_t(kmr_handle *h, const uint64_t *ls, const ui
 			unsigned long long *pk_in = bk_in.get<unsigned long long>(), *pk_out = bk_out.get<unsigned long long>(); uint32_t *pv_in = bv_in.get<uint32_t>(), *pv_out = bv_out.get<uint32_t>();
 			HIPCHK(h, hipMemsetAsync(dfound, 0, 8, h->stream));
 			int rc = zero_work_counter(h); if (rc) return rc;
-			hipLaunchKernelGGL(sat_collect_kernel<W>, dim3((unsigned)std::min<uint64_t>(ni, (uint64_t)num_cus(h) * 4)), dim3(256), 0, h->stream, pool_view(h, h->l1), lc, h->k, (const uint64_t *)wm.keys.get<uint64_t>(), (const uint64_t *)(d_entry + k0),
-			                   (const uint64_t *)d_items, (const uint64_t *)(d_items + ni), (const uint64_t *)(d_items + 2 * ni), (const uint64_t *)(d_items + 3 * ni), (uint64_t)ni, dfound, pcap, pk_in, pv_in, h->work_counter.get<unsigned int>());
-			HIPCHK(h, hipGetLastError());
+			LAUNCH(h, sat_collect_kernel<W>, dim3((unsigned)std::min<uint64_t>(ni, (uint64_t)num_cus(h) * 4)), dim3(256), 0, pool_view(h, h->l1), lc, h->k, (const uint64_t *)wm.keys.get<uint64_t>(), (const uint64_t *)(d_entry + k0),
+			       (const uint64_t *)d_items, (const uint64_t *)(d_items + ni), (const uint64_t *)(d_items + 2 * ni), (const uint64_t *)(d_items + 3 * ni), (uint64_t)ni, dfound, pcap, pk_in, pv_in, h->work_counter.get<unsigned int>());
 			unsigned long long n_pairs = 0;
-			HIPCHK(h, hipMemcpyAsync(&n_pairs, dfound, 8, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
+			HIPCHK(h, fetch(h, &n_pairs, dfound));
 			if (n_pairs > pcap) {      /* denser than the estimate: the batch again with room for exactly what it holds */
 				if (attempt) return fail(h, KMR_ERR_CAPACITY, "saturated-key pass: sightings of a batch changed between two passes (internal error)");
 				pcap = n_pairs;
@@ -1704,8 +1665,7 @@ template <int W> int saturated_fix_t(kmr_handle *h, const uint64_t *ls, const ui
 			if (kmr::sort_pairs_u64_u32(nullptr, &tmp_bytes, pk_in, pk_out, pv_in, pv_out, n_pairs, h->stream) != 0) return fail(h, KMR_ERR_HIP, "saturated-key pass: radix sort (size query)");
 			if (dalloc(btmp, tmp_bytes) != hipSuccess) return no_mem("the sort's temporary storage", tmp_bytes);
 			if (kmr::sort_pairs_u64_u32(btmp.get(), &tmp_bytes, pk_in, pk_out, pv_in, pv_out, n_pairs, h->stream) != 0) return fail(h, KMR_ERR_HIP, "saturated-key pass: radix sort");
-			hipLaunchKernelGGL(sat_reduce_kernel, dim3((unsigned)std::min<uint64_t>(nk, 4096)), dim3(256), 0, h->stream, (const unsigned long long *)pk_out, (const uint32_t *)pv_out, (uint64_t)n_pairs, (const uint64_t *)(d_entry + k0), (uint64_t)nk, has_singletons, wm.vals.get<uint32_t>(), h->ext ? 15u : 3u);
-			HIPCHK(h, hipGetLastError());
+			LAUNCH(h, sat_reduce_kernel, dim3((unsigned)std::min<uint64_t>(nk, 4096)), dim3(256), 0, (const unsigned long long *)pk_out, (const uint32_t *)pv_out, (uint64_t)n_pairs, (const uint64_t *)(d_entry + k0), (uint64_t)nk, has_singletons, wm.vals.get<uint32_t>(), value_words(h));
 			HIPCHK(h, hipStreamSynchronize(h->stream));
 			break;
 		}
@@ -1802,10 +1762,10 @@ template <int W> int sk_count_launch(kmr_handle *h, const SkCountLaunch<W> &k, i
 	SkCountArgs<W> a{out, f, tv, lg};
 	SkCountArgs<W> *d = nullptr;
 	int rc = arena_get(h, &d, 1); if (rc) return rc;
-	hipLaunchKernelGGL(sk_count_args_kernel<W>, dim3(1), dim3(64), 0, h->stream, a, d);
+	LAUNCH(h, sk_count_args_kernel<W>, dim3(1), dim3(64), 0, a, d);
 	SkCountHot hot = sk_count_hot<W>(a);
 	if (k.blocks == 6) hot.ord_base = (uint32_t)h->ord_lo;      /* (that instance has no extension values: the word is free) */
-	hipLaunchKernelGGL(k.kern, dim3(grid), dim3(SKC_THREADS), k.smem, h->stream, (const uint4 *)pool_view(h, h->l1).base, ls, lc, nl, h->k, hot, h->work_counter.get<unsigned int>(), sk_dbg_flags("KMR_SK_COUNT_DBG"), (const SkCountArgs<W> *)d);
+	LAUNCH(h, k.kern, dim3(grid), dim3(SKC_THREADS), k.smem, (const uint4 *)pool_view(h, h->l1).base, ls, lc, nl, h->k, hot, h->work_counter.get<unsigned int>(), sk_dbg_flags("KMR_SK_COUNT_DBG"), (const SkCountArgs<W> *)d);
 	return 0;
 }
 
@@ -1827,13 +1787,12 @@ int sk_refine_lists(kmr_handle *h, uint64_t &nl) {
 	HIPCHK(h, hipMemcpy(&head, h->l1.head.get<unsigned int>(), 4, hipMemcpyDeviceToHost));
 	if (head > h->l1.cap) head = h->l1.cap;
 	int rc = h->sk_fine_state.reserve(h, "sk_fine_state", 8 * nlf); if (rc) return rc;
-	hipLaunchKernelGGL(sk_state_init_kernel, dim3(grid_for(nlf)), dim3(256), 0, h->stream, h->sk_fine_state.get<unsigned long long>(), nlf);
+	LAUNCH(h, sk_state_init_kernel, dim3(grid_for(nlf)), dim3(256), 0, h->sk_fine_state.get<unsigned long long>(), nlf);
 	const int rgrid = (int)std::min<uint64_t>(((uint64_t)head + SK_REFINE_WAVES - 1) / SK_REFINE_WAVES + 1, (uint64_t)num_cus(h) * 8);
 	/* every old chunk's records again, cut into at most 2^shift pieces per chunk (a piece may open a chunk), an open chunk per owned fine list */
 	rc = pool_reserve(h, h->l1, (uint64_t)head * 2 + nlf / h->cfg.world_size + (uint64_t)rgrid * SK_REFINE_WAVES * 130 + 64, true); if (rc) return rc;
-	if (head) hipLaunchKernelGGL(sk_refine_kernel, dim3(rgrid), dim3(SK_REFINE_WAVES * 64), 0, h->stream, pool_view(h, h->l1), head, fine_bits, h->sk_fine_state.get<unsigned long long>());
-	hipLaunchKernelGGL(sk_close_kernel, dim3(grid_for(nlf)), dim3(256), 0, h->stream, h->sk_fine_state.get<unsigned long long>(), nlf, h->l1.chunk_count.get<uint32_t>(), h->l1.cap);
-	HIPCHK(h, hipGetLastError());
+	if (head) LAUNCH(h, sk_refine_kernel, dim3(rgrid), dim3(SK_REFINE_WAVES * 64), 0, pool_view(h, h->l1), head, fine_bits, h->sk_fine_state.get<unsigned long long>());
+	LAUNCH(h, sk_close_kernel, dim3(grid_for(nlf)), dim3(256), 0, h->sk_fine_state.get<unsigned long long>(), nlf, h->l1.chunk_count.get<uint32_t>(), h->l1.cap);
 	nl = nlf;
 	return 0;
 }
@@ -1905,10 +1864,9 @@ template <int W> int sk_long_items(kmr_handle *h, SkFinalize<W> &p) {
 	uint64_t *ic0 = nullptr, *ic1 = nullptr; unsigned long long *dn = nullptr;
 	int rc = arena_get(h, &ic0, cap); if (rc) return rc; rc = arena_get(h, &ic1, cap); if (rc) return rc; rc = arena_get(h, &dn, 1); if (rc) return rc;
 	HIPCHK(h, hipMemsetAsync(dn, 0, 8, h->stream));
-	hipLaunchKernelGGL(sk_long_items_kernel, dim3(grid_for(p.nl)), dim3(256), 0, h->stream, p.ls, p.nl, LONG_CHUNKS, PIECE, ic0, ic1, cap, dn);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, sk_long_items_kernel, dim3(grid_for(p.nl)), dim3(256), 0, p.ls, p.nl, LONG_CHUNKS, PIECE, ic0, ic1, cap, dn, nullptr);
 	unsigned long long hn = 0;
-	HIPCHK(h, hipMemcpyAsync(&hn, dn, 8, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
+	HIPCHK(h, fetch(h, &hn, dn));
 	if (hn > cap) return fail(h, KMR_ERR_CAPACITY, "long-list work items (internal sizing error)");
 	p.n_items = hn;
 	if (p.n_items) {
@@ -1943,22 +1901,20 @@ template <int W> int sk_count_pass(kmr_handle *h, SkFinalize<W> &p) {
 		if (p.tracking) HIPCHK(h, hipMemsetAsync(tv.d_unique, 0, 8 * (tv.n + 1), h->stream));
 		if (dbg()) { int nb = 0; hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)k.kern, SKC_THREADS, k.smem); fprintf(stderr, "sk_count<W=%d>: %d blocks per CU (LDS %zu), %llu lists, %u chunks\n", W, nb, k.smem, (unsigned long long)nl, p.nch); }
 		rc = sk_count_launch<W>(h, k, grid, p.ls, p.lc, nl, out, p.f, tv, p.lgMain); if (rc) return rc;
-		HIPCHK(h, hipGetLastError());
 		if (!n_items) return 0;
 		/* the merge table holds the distinct keys of the long lists: few when a list is long because a k-mer repeats, at most the
 		 * k-mers of those lists; it starts small and the attempt is repeated with a larger one if it fills */
 		SkLong<W> &lgItems = p.lgItems;
 		if (mslots.alloc(sizeof(Slot<W>) << merge_log2) != hipSuccess) return fail(h, KMR_ERR_OOM, "merge table of the long lists");
 		if (p.ext && mext.alloc(sizeof(ExtSlot) << merge_log2) != hipSuccess) return fail(h, KMR_ERR_OOM, "merge table of the long lists");
-		hipLaunchKernelGGL(table_clear_kernel<W>, dim3(grid_for(1ull << merge_log2)), dim3(256), 0, h->stream, mslots.get<Slot<W>>(), mext.get<ExtSlot>(), 1ull << merge_log2);
+		LAUNCH(h, table_clear_kernel<W>, dim3(grid_for(1ull << merge_log2)), dim3(256), 0, mslots.get<Slot<W>>(), mext.get<ExtSlot>(), 1ull << merge_log2);
 		lgItems.merge.slots = mslots.get<Slot<W>>(); lgItems.merge.ext = mext.get<ExtSlot>(); lgItems.merge.log2cap = merge_log2;
 		HIPCHK(h, hipMemsetAsync(lgItems.merge_used, 0, 8, h->stream));
 		rc = zero_work_counter(h); if (rc) return rc;
 		rc = sk_count_select<W>(h, p.ext, p.tracking, p.uni, true, n_items, out, lgItems, k); if (rc) return rc;
 		const int grid2 = (int)std::min<uint64_t>((uint64_t)num_cus(h) * k.blocks, n_items);
 		rc = sk_count_launch<W>(h, k, grid2, p.ls, p.lc, nl, out, p.f, tv, lgItems); if (rc) return rc;
-		hipLaunchKernelGGL(sk_merge_emit_kernel<W>, dim3(grid_for(1ull << merge_log2)), dim3(256), 0, h->stream, lgItems.merge, out, p.f);
-		if (hipGetLastError() != hipSuccess) return fail(h, KMR_ERR_HIP, "long-list launches");
+		LAUNCH(h, sk_merge_emit_kernel<W>, dim3(grid_for(1ull << merge_log2)), dim3(256), 0, lgItems.merge, out, p.f);
 		if (merge_log2 < 30) repeat_on = ERR_TABLE_FULL;
 		return 0;
 	});
@@ -1995,8 +1951,7 @@ template <int W> int finalize_superkmer_t(kmr_handle *h, uint32_t min_depth) {
 	rc = arena_reset(h); if (rc) return rc;
 	p.nl = h->sk_state ? sk_list_count(h->sk_bits) : 1;
 	if (h->sk_state) {
-		hipLaunchKernelGGL(sk_close_kernel, dim3(grid_for(p.nl)), dim3(256), 0, h->stream, h->sk_state.get<unsigned long long>(), p.nl, h->l1.chunk_count.get<uint32_t>(), h->l1.cap);
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, sk_close_kernel, dim3(grid_for(p.nl)), dim3(256), 0, h->sk_state.get<unsigned long long>(), p.nl, h->l1.chunk_count.get<uint32_t>(), h->l1.cap);
 	}
 	p.refined = h->sk_state && h->sk_fine_shift > 0;
 	if (p.refined) { rc = sk_refine_lists(h, p.nl); if (rc) return rc; }
@@ -2029,7 +1984,7 @@ template <int W> int finalize_superkmer_t(kmr_handle *h, uint32_t min_depth) {
 		 * group that was fuller than its capacity voids the map, and the packed entries may be overwritten: the lists are counted
 		 * again and bucketed with measured bins */
 		uint32_t ovf = 0;
-		HIPCHK(h, hipMemcpyAsync(&ovf, overflow, 4, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
+		HIPCHK(h, fetch(h, &ovf, overflow));
 		if (ovf) {
 			if (dbg()) fprintf(stderr, "bucket build: a bin of the radix partition overflowed its capacity, again with measured bins\n");
 			h->last_bb_fallback = true;
@@ -2055,8 +2010,7 @@ template <int W> int count_prefix_superkmer_t(kmr_handle *h, uint32_t min_depth,
 	if (hi > nl) hi = nl;
 	if (hi == 0) return KMR_OK;
 	rc = arena_reset(h); if (rc) return rc;
-	hipLaunchKernelGGL(sk_close_kernel, dim3(grid_for(nl)), dim3(256), 0, h->stream, h->sk_state.get<unsigned long long>(), nl, h->l1.chunk_count.get<uint32_t>(), h->l1.cap);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, sk_close_kernel, dim3(grid_for(nl)), dim3(256), 0, h->sk_state.get<unsigned long long>(), nl, h->l1.chunk_count.get<uint32_t>(), h->l1.cap);
 	uint64_t *ls = nullptr, *lc = nullptr; uint32_t nch = 0;
 	rc = build_csr(h, h->l1, nl, 0, &ls, &lc, &nch, &h->l1_head_seen); if (rc) return rc;
 	/* room: the share of the good k-mers that lies below hi, at the rate kmr_finalize starts with.  Too little (low coverage, or an
@@ -2094,7 +2048,6 @@ template <int W> int count_prefix_superkmer_t(kmr_handle *h, uint32_t min_depth,
 		rc = sk_count_launch<W>(h, k, grid, ls, lc, hi, out, f, tv, lg);
 		t.end();
 		if (rc) return rc;
-		HIPCHK(h, hipGetLastError());
 	}
 	h->early.active = true; h->early.hi = hi; h->early.min_depth = min_depth;
 	return KMR_OK;      /* asynchronous: the handle's stream carries the pass; kmr_finalize (or kmr_sync) waits for it */
@@ -2250,10 +2203,10 @@ int kmr_reset(kmr_handle *h) {
 		h->sk_uni_w = SK_UNI_NONE; h->sk_uni_mixed = false; h->peer_uni_w = SK_UNI_NONE; h->peer_uni_mixed = false; h->peers_declare = false;
 		h->xr_lo = 0; h->xr_hi = ~0ull; h->early.active = false;
 		if (h->d_uni) { const uint32_t init[2] = {SK_UNI_NONE, 0u}; HIPCHK(h, hipMemcpyAsync(h->d_uni.get<uint32_t>(), init, 8, hipMemcpyHostToDevice, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream)); }
-		if (h->sk_state) hipLaunchKernelGGL(sk_state_init_kernel, dim3(grid_for(sk_list_count(h->sk_bits))), dim3(256), 0, h->stream, h->sk_state.get<unsigned long long>(), sk_list_count(h->sk_bits));
+		if (h->sk_state) LAUNCH(h, sk_state_init_kernel, dim3(grid_for(sk_list_count(h->sk_bits))), dim3(256), 0, h->sk_state.get<unsigned long long>(), sk_list_count(h->sk_bits));
 		if (h->l1_state) {      /* what an unfinished build kept back is dropped with its pool */
-			hipLaunchKernelGGL(partition_state_init_kernel, dim3(partition_blocks(h)), dim3(256), 0, h->stream, h->l1_state.get<uint8_t>(),
-			                   h->l1_state.cap() / (size_t)partition_blocks(h), h->bits1, (uint32_t)partition_blocks(h));
+			LAUNCH(h, partition_state_init_kernel, dim3(partition_blocks(h)), dim3(256), 0, h->l1_state.get<uint8_t>(),
+			       h->l1_state.cap() / (size_t)partition_blocks(h), h->bits1, (uint32_t)partition_blocks(h));
 			h->l1_state_dirty = false;
 		}
 	} else {
@@ -2672,7 +2625,7 @@ bool stream_lookups_possible(kmr_handle *h) {
 template <int W> int sk_index_t(kmr_handle *h) {
 	if (h->ix_gen == h->map_gen && h->ix_start) return 0;
 	const uint64_t nl = sk_list_count(h->sk_bits), n = h->weak.n;
-	const uint32_t vw = h->ext ? 15 : 3;
+	const uint32_t vw = value_words(h);
 	if (h->ix_lists != nl) { h->ix_lists = 0; HIPCHK(h, h->ix_start.alloc(8 * (nl + 1))); h->ix_lists = nl; }
 	if (h->ix_counts.cap() < 4 * n) {      /* (ix_counts is allocated last) */
 		h->ix_keys.reset(); h->ix_counts.reset();
@@ -2682,12 +2635,10 @@ template <int W> int sk_index_t(kmr_handle *h) {
 	int rc = arena_get(h, &elist, n); if (rc) return rc;
 	rc = arena_get(h, &hist, nl); if (rc) return rc;
 	HIPCHK(h, hipMemsetAsync(hist, 0, 4 * nl, h->stream));
-	hipLaunchKernelGGL(sk_index_hist_kernel<W>, dim3(grid_for(n)), dim3(256), 0, h->stream, (const uint64_t *)h->weak.keys.get<uint64_t>(), n, h->sk_m, h->sk_off, h->sk_win, h->sk_bits, elist, hist);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, sk_index_hist_kernel<W>, dim3(grid_for(n)), dim3(256), 0, (const uint64_t *)h->weak.keys.get<uint64_t>(), n, h->sk_m, h->sk_off, h->sk_win, h->sk_bits, elist, hist);
 	rc = exclusive_scan(h, hist, nl, h->ix_start.get<uint64_t>()); if (rc) return rc;
 	HIPCHK(h, hipMemsetAsync(hist, 0, 4 * nl, h->stream));
-	hipLaunchKernelGGL(sk_index_scatter_kernel<W>, dim3(grid_for(n)), dim3(256), 0, h->stream, (const uint64_t *)h->weak.keys.get<uint64_t>(), (const uint32_t *)h->weak.vals.get<uint32_t>(), vw, n, elist, h->ix_start.get<uint64_t>(), hist, h->ix_keys.get<uint64_t>(), h->ix_counts.get<uint32_t>());
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, sk_index_scatter_kernel<W>, dim3(grid_for(n)), dim3(256), 0, (const uint64_t *)h->weak.keys.get<uint64_t>(), (const uint32_t *)h->weak.vals.get<uint32_t>(), vw, n, elist, h->ix_start.get<uint64_t>(), hist, h->ix_keys.get<uint64_t>(), h->ix_counts.get<uint32_t>());
 	h->ix_gen = h->map_gen;
 	return 0;
 }
@@ -2701,7 +2652,7 @@ template <int W> int lookup_stream_t(kmr_handle *h, const ReadsView &rvAll, uint
 	rc = h->scratch_stats.reserve(h, "scratch_stats", sizeof(DevStats)); if (rc) return rc;
 	rc = sk_index_t<W>(h); if (rc) return rc;
 	const uint64_t nl = sk_list_count(h->sk_bits);
-	hipLaunchKernelGGL(sk_state_init_kernel, dim3(grid_for(nl)), dim3(256), 0, h->stream, h->sk_state.get<unsigned long long>(), nl);
+	LAUNCH(h, sk_state_init_kernel, dim3(grid_for(nl)), dim3(256), 0, h->sk_state.get<unsigned long long>(), nl);
 	if (h->l1.head) HIPCHK(h, hipMemsetAsync(h->l1.head.get<unsigned int>(), 0, 4, h->stream));
 	h->l1.used_ub = 0;
 	ReadsView rv = rvAll;
@@ -2713,8 +2664,7 @@ template <int W> int lookup_stream_t(kmr_handle *h, const ReadsView &rvAll, uint
 	SkParams sp = sk_params(h); sp.keep_all_owners = 1; sp.track = nullptr;
 	rc = with_win<W>(h->sk_win, [&](auto WIN) { return (!rv.quals && !h->tune.no_lean_extract) ? launch_sk_extract_lean<W, WIN()>(h, rv, sp, dp, 1.0f) : launch_sk_extract<W, WIN(), false>(h, rv, sp, dp); });
 	if (rc) return rc;
-	hipLaunchKernelGGL(sk_close_kernel, dim3(grid_for(nl)), dim3(256), 0, h->stream, h->sk_state.get<unsigned long long>(), nl, h->l1.chunk_count.get<uint32_t>(), h->l1.cap);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, sk_close_kernel, dim3(grid_for(nl)), dim3(256), 0, h->sk_state.get<unsigned long long>(), nl, h->l1.chunk_count.get<uint32_t>(), h->l1.cap);
 	uint64_t *ls = nullptr, *lc = nullptr; uint32_t nch = 0;
 	rc = build_csr(h, h->l1, nl, 0, &ls, &lc, &nch); if (rc) return rc;
 	rc = zero_work_counter(h); if (rc) return rc;
@@ -2730,21 +2680,18 @@ template <int W> int lookup_stream_t(kmr_handle *h, const ReadsView &rvAll, uint
 		unsigned long long *dn = nullptr;
 		rc = arena_get(h, &ic0, cap); if (rc) return rc; rc = arena_get(h, &ic1, cap); if (rc) return rc; rc = arena_get(h, &il, cap); if (rc) return rc; rc = arena_get(h, &dn, 1); if (rc) return rc;
 		HIPCHK(h, hipMemsetAsync(dn, 0, 8, h->stream));
-		hipLaunchKernelGGL(sk_long_items_kernel, dim3(grid_for(nl)), dim3(256), 0, h->stream, ls, nl, LONG_CHUNKS, PIECE, ic0, ic1, cap, dn, il);
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, sk_long_items_kernel, dim3(grid_for(nl)), dim3(256), 0, ls, nl, LONG_CHUNKS, PIECE, ic0, ic1, cap, dn, il);
 		unsigned long long hn = 0;
-		HIPCHK(h, hipMemcpyAsync(&hn, dn, 8, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
+		HIPCHK(h, fetch(h, &hn, dn));
 		if (hn > cap) return fail(h, KMR_ERR_CAPACITY, "long-list work items (internal sizing error)");
 		n_items = hn;
 	}
-	hipLaunchKernelGGL(kern, dim3(grid), dim3(COUNT_THREADS), smem, h->stream, pool_view(h, h->l1), ls, lc, nl, h->k, h->ix_start.get<uint64_t>(), h->ix_keys.get<uint64_t>(), h->ix_counts.get<uint32_t>(), position_counts, out_n, h->work_counter.get<unsigned int>(),
-	                   (const uint64_t *)nullptr, (const uint64_t *)nullptr, (const uint32_t *)nullptr, (uint64_t)0, n_items ? LONG_CHUNKS : (uint64_t)0);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, kern, dim3(grid), dim3(COUNT_THREADS), smem, pool_view(h, h->l1), ls, lc, nl, h->k, h->ix_start.get<uint64_t>(), h->ix_keys.get<uint64_t>(), h->ix_counts.get<uint32_t>(), position_counts, out_n, h->work_counter.get<unsigned int>(),
+	       (const uint64_t *)nullptr, (const uint64_t *)nullptr, (const uint32_t *)nullptr, (uint64_t)0, n_items ? LONG_CHUNKS : (uint64_t)0);
 	if (n_items) {
 		rc = zero_work_counter(h); if (rc) return rc;
-		hipLaunchKernelGGL(kern, dim3((unsigned)std::min<uint64_t>((uint64_t)num_cus(h) * 4, n_items)), dim3(COUNT_THREADS), smem, h->stream, pool_view(h, h->l1), ls, lc, nl, h->k, h->ix_start.get<uint64_t>(), h->ix_keys.get<uint64_t>(), h->ix_counts.get<uint32_t>(),
-		                   position_counts, out_n, h->work_counter.get<unsigned int>(), (const uint64_t *)ic0, (const uint64_t *)ic1, (const uint32_t *)il, n_items, (uint64_t)0);
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, kern, dim3((unsigned)std::min<uint64_t>((uint64_t)num_cus(h) * 4, n_items)), dim3(COUNT_THREADS), smem, pool_view(h, h->l1), ls, lc, nl, h->k, h->ix_start.get<uint64_t>(), h->ix_keys.get<uint64_t>(), h->ix_counts.get<uint32_t>(),
+		       position_counts, out_n, h->work_counter.get<unsigned int>(), (const uint64_t *)ic0, (const uint64_t *)ic1, (const uint32_t *)il, n_items, (uint64_t)0);
 	}
 	return 0;
 }
@@ -2760,16 +2707,14 @@ static int launch_scoring(kmr_handle *h, const uint8_t *bases, const uint64_t *o
                           double minimum_kmer_score, int scoring_type, uint32_t *dto, uint32_t *dtl, float *dsc, uint8_t *dwt, const uint64_t **words) {
 	*words = nullptr;
 	h->bimodal_n = n_reads; h->bimodal_on = false;
-	hipLaunchKernelGGL(score_reads_kernel, dim3((unsigned)std::min<uint64_t>(((n_reads + 63) / 64 + SC_WAVES - 1) / SC_WAVES, 1u << 16)), dim3(SC_WAVES * 64), 0, h->stream, bases, offsets, n_reads, h->k, counts, count_off,
-	                   (float)minimum_kmer_score, scoring_type, dto, dtl, dsc, dwt);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, score_reads_kernel, dim3((unsigned)std::min<uint64_t>(((n_reads + 63) / 64 + SC_WAVES - 1) / SC_WAVES, 1u << 16)), dim3(SC_WAVES * 64), 0, bases, offsets, n_reads, h->k, counts, count_off,
+	       (float)minimum_kmer_score, scoring_type, dto, dtl, dsc, dwt);
 	if (!(h->bimodal_sigmas >= 0.0)) return 0;
 	int rc = h->bimodal_buf.reserve(h, "bimodal_buf", 8 * n_reads, 8 * n_reads + n_reads); if (rc) return rc;
 	uint64_t *w = h->bimodal_buf.get<uint64_t>();
 	const uint32_t window = h->tune.bimodal_window < 0 ? (uint32_t)BM_CAP : (uint32_t)h->tune.bimodal_window;
-	hipLaunchKernelGGL(bimodal_trim_kernel, dim3((unsigned)std::min<uint64_t>((n_reads + BM_WAVES - 1) / BM_WAVES, 1u << 16)), dim3(BM_WAVES * 64), 0, h->stream, n_reads, h->k, counts, count_off,
-	                   h->bimodal_sigmas, scoring_type, window, dto, dtl, dsc, dwt, w);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, bimodal_trim_kernel, dim3((unsigned)std::min<uint64_t>((n_reads + BM_WAVES - 1) / BM_WAVES, 1u << 16)), dim3(BM_WAVES * 64), 0, n_reads, h->k, counts, count_off,
+	       h->bimodal_sigmas, scoring_type, window, dto, dtl, dsc, dwt, w);
 	h->bimodal_on = true; *words = w;
 	return 0;
 }
@@ -2801,15 +2746,13 @@ int score_reads_core(kmr_handle *h, const uint8_t *s_b, const uint64_t *s_o, uin
 		if (outN > first_off) {
 			uint32_t other = 0;
 			HIPCHK(h, hipMemsetAsync(dkc, 0, 4, h->stream));
-			hipLaunchKernelGGL(other_markup_kernel, dim3(grid_for((outN - first_off) / 16 + 2)), dim3(256), 0, h->stream, s_b, first_off, outN, dkc);
-			HIPCHK(h, hipGetLastError());
-			HIPCHK(h, hipMemcpyAsync(&other, dkc, 4, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
+			LAUNCH(h, other_markup_kernel, dim3(grid_for((outN - first_off) / 16 + 2)), dim3(256), 0, s_b, first_off, outN, dkc);
+			HIPCHK(h, fetch(h, &other, dkc));
 			if (other) { stream = false; h->last_score_path = 3; }
 		}
 	}
 	if (!stream) {
-		hipLaunchKernelGGL(kmer_capacity_kernel, dim3(grid_for(n_reads)), dim3(256), 0, h->stream, rv, h->k, dkc);
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, kmer_capacity_kernel, dim3(grid_for(n_reads)), dim3(256), 0, rv, h->k, dkc);
 		rc = exclusive_scan(h, dkc, n_reads, dcoff); if (rc) return rc;
 		HIPCHK(h, hipMemcpy(&outN, dcoff + n_reads, 8, hipMemcpyDeviceToHost));
 	}
@@ -2950,8 +2893,7 @@ int kmr_count_histogram(kmr_handle *h, uint64_t *counts, double *weights, uint32
 	if (weights) { HIPCHK(h, dwb.alloc(8 * n_bins)); HIPCHK(h, hipMemsetAsync(dwb.get(), 0, 8 * n_bins, h->stream)); }
 	unsigned long long *dc = dcb.get<unsigned long long>(); double *dw = dwb.get<double>();
 	if (h->weak.present && h->weak.n)
-		hipLaunchKernelGGL(histogram_kernel, dim3(grid_for(h->weak.n)), dim3(256), 0, h->stream, h->weak.vals.get<uint32_t>(), h->ext ? 15u : 3u, h->weak.n, n_bins, dc, dw);
-	HIPCHK(h, hipGetLastError());
+		LAUNCH(h, histogram_kernel, dim3(grid_for(h->weak.n)), dim3(256), 0, h->weak.vals.get<uint32_t>(), value_words(h), h->weak.n, n_bins, dc, dw);
 	HIPCHK(h, hipMemcpyAsync(counts, dc, 8 * n_bins, hipMemcpyDeviceToHost, h->stream));
 	if (weights) HIPCHK(h, hipMemcpyAsync(weights, dw, 8 * n_bins, hipMemcpyDeviceToHost, h->stream));
 	HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2974,10 +2916,9 @@ int kmr_map_digest(kmr_handle *h, int which_map, kmr_digest *out) {
 	synth::Digest *d = db.get<synth::Digest>();
 	HIPCHK(h, hipMemsetAsync(d, 0, sizeof(synth::Digest), h->stream));
 	if (which_map == KMR_MAP_WEAK)
-		hipLaunchKernelGGL(synth::map_digest_kernel, dim3(grid_for(m.n, 256, 4096)), dim3(256), 0, h->stream, m.keys.get<uint64_t>(), (uint32_t)h->W, m.vals.get<uint32_t>(), h->ext ? 15u : 3u, (const uint8_t *)nullptr, (const uint32_t *)nullptr, m.n, d);
+		LAUNCH(h, synth::map_digest_kernel, dim3(grid_for(m.n, 256, 4096)), dim3(256), 0, m.keys.get<uint64_t>(), (uint32_t)h->W, m.vals.get<uint32_t>(), value_words(h), (const uint8_t *)nullptr, (const uint32_t *)nullptr, m.n, d);
 	else
-		hipLaunchKernelGGL(synth::map_digest_kernel, dim3(grid_for(m.n, 256, 4096)), dim3(256), 0, h->stream, m.keys.get<uint64_t>(), (uint32_t)h->W, (const uint32_t *)nullptr, 0u, m.sweight.get<uint8_t>(), h->ext ? m.spkt.get<uint32_t>() : (const uint32_t *)nullptr, m.n, d);
-	HIPCHK(h, hipGetLastError());
+		LAUNCH(h, synth::map_digest_kernel, dim3(grid_for(m.n, 256, 4096)), dim3(256), 0, m.keys.get<uint64_t>(), (uint32_t)h->W, (const uint32_t *)nullptr, 0u, m.sweight.get<uint8_t>(), h->ext ? m.spkt.get<uint32_t>() : (const uint32_t *)nullptr, m.n, d);
 	HIPCHK(h, hipMemcpyAsync(out, d, sizeof(synth::Digest), hipMemcpyDeviceToHost, h->stream));
 	HIPCHK(h, hipStreamSynchronize(h->stream));
 	out->entries = m.n;
@@ -2992,9 +2933,8 @@ int kmr_synth_reads_dev(uint64_t seed, uint64_t first_read, uint64_t n_reads, ui
 	if (n_reads == 0 && !dev_offsets) return KMR_OK;
 	const uint64_t blocks = (n_reads + 1 + 255) / 256;
 	if (blocks > 0x7fffffffull) return KMR_ERR_CAPACITY;
-	hipLaunchKernelGGL(synth::synth_reads_kernel, dim3((uint32_t)blocks), dim3(256), 0, 0, seed, first_read, n_reads, read_len, genome_len, noisy_quals,
-	                   (uint8_t *)dev_bases, (uint8_t *)dev_quals, dev_offsets);
-	if (hipGetLastError() != hipSuccess) return KMR_ERR_HIP;
+	if (launch_status(nullptr, synth::synth_reads_kernel, dim3((uint32_t)blocks), dim3(256), 0, seed, first_read, n_reads, read_len, genome_len, noisy_quals,
+	                  (uint8_t *)dev_bases, (uint8_t *)dev_quals, dev_offsets) != hipSuccess) return KMR_ERR_HIP;
 	return hipStreamSynchronize(0) == hipSuccess ? KMR_OK : KMR_ERR_HIP;
 }
 
@@ -3058,10 +2998,9 @@ int kmr_histogram(kmr_handle *h, uint32_t zoom_max, double log_base, uint64_t *v
 	HIPCHK(h, hipMemcpyAsync(dl, lut.data(), 4 * 65536, hipMemcpyHostToDevice, h->stream));
 	HIPCHK(h, hipMemsetAsync(dv, 0, 8ull * nb, h->stream)); HIPCHK(h, hipMemsetAsync(dc, 0, 8ull * nb, h->stream)); HIPCHK(h, hipMemsetAsync(dw, 0, 8ull * nb, h->stream));
 	if (h->weak.present && h->weak.n)
-		hipLaunchKernelGGL(ref_histogram_kernel, dim3(grid_for(h->weak.n, 256, 2048)), dim3(256), 0, h->stream, h->weak.vals.get<uint32_t>(), h->ext ? 15u : 3u, (const uint8_t *)nullptr, h->weak.n, dl, dv, dc, dw);
+		LAUNCH(h, ref_histogram_kernel, dim3(grid_for(h->weak.n, 256, 2048)), dim3(256), 0, h->weak.vals.get<uint32_t>(), value_words(h), (const uint8_t *)nullptr, h->weak.n, dl, dv, dc, dw);
 	if (h->has_singletons && h->sing.present && h->sing.n)
-		hipLaunchKernelGGL(ref_histogram_kernel, dim3(grid_for(h->sing.n, 256, 2048)), dim3(256), 0, h->stream, (const uint32_t *)nullptr, 0u, h->sing.sweight.get<uint8_t>(), h->sing.n, dl, dv, dc, dw);
-	HIPCHK(h, hipGetLastError());
+		LAUNCH(h, ref_histogram_kernel, dim3(grid_for(h->sing.n, 256, 2048)), dim3(256), 0, (const uint32_t *)nullptr, 0u, h->sing.sweight.get<uint8_t>(), h->sing.n, dl, dv, dc, dw);
 	HIPCHK(h, hipMemcpyAsync(visits, dv, 8ull * nb, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipMemcpyAsync(visited_count, dc, 8ull * nb, hipMemcpyDeviceToHost, h->stream));
 	HIPCHK(h, hipMemcpyAsync(visited_weight, dw, 8ull * nb, hipMemcpyDeviceToHost, h->stream));
 	HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -3153,28 +3092,23 @@ int kmr_lookup_keys_dev(kmr_handle *h, const void *dev_keys, uint64_t n, void *d
 	if (!h->finalized) return fail(h, KMR_ERR_STATE, "kmr_lookup_keys_dev before kmr_finalize");
 	if (n == 0) return KMR_OK;
 	hipSetDevice(h->device);
-	const uint32_t vw = h->ext ? 15 : 3;
-	with_w(h, [&](auto W) { hipLaunchKernelGGL(lookup_words_kernel<W()>, dim3(grid_for(n)), dim3(256), 0, h->stream, view_of<W()>(h->weak, vw), lut_of<W()>(h), (const uint64_t *)dev_keys, n, h->hkb, (uint32_t *)dev_counts); });
-	HIPCHK(h, hipGetLastError());
-	return KMR_OK;
+	const uint32_t vw = value_words(h);
+	return with_w(h, [&](auto W) -> int { LAUNCH(h, lookup_words_kernel<W()>, dim3(grid_for(n)), dim3(256), 0, view_of<W()>(h->weak, vw), lut_of<W()>(h), (const uint64_t *)dev_keys, n, h->hkb, (uint32_t *)dev_counts); return KMR_OK; });
 }
 int kmr_lookup_keys_weighted_dev(kmr_handle *h, const void *dev_keys, uint64_t n, void *dev_weights) {
 	if (!h || (n && (!dev_keys || !dev_weights))) return KMR_ERR_INVALID_ARG;
 	if (!h->finalized) return fail(h, KMR_ERR_STATE, "kmr_lookup_keys_weighted_dev before kmr_finalize");
 	if (n == 0) return KMR_OK;
 	hipSetDevice(h->device);
-	const uint32_t vw = h->ext ? 15 : 3;
-	with_w(h, [&](auto W) { hipLaunchKernelGGL(lookup_words_weight_kernel<W()>, dim3(grid_for(n)), dim3(256), 0, h->stream, view_of<W()>(h->weak, vw), view_of<W()>(h->sing, vw), lut_of<W()>(h),
-	                                           (const uint64_t *)dev_keys, n, h->hkb, (double *)dev_weights); });
-	HIPCHK(h, hipGetLastError());
-	return KMR_OK;
+	const uint32_t vw = value_words(h);
+	return with_w(h, [&](auto W) -> int { LAUNCH(h, lookup_words_weight_kernel<W()>, dim3(grid_for(n)), dim3(256), 0, view_of<W()>(h->weak, vw), view_of<W()>(h->sing, vw), lut_of<W()>(h),
+	                                      (const uint64_t *)dev_keys, n, h->hkb, (double *)dev_weights); return KMR_OK; });
 }
 int kmr_scatter_counts_dev(kmr_handle *h, const void *dev_counts, const void *dev_pos, uint64_t n, void *dev_position_counts) {
 	if (!h || (n && (!dev_counts || !dev_pos || !dev_position_counts))) return KMR_ERR_INVALID_ARG;
 	if (n == 0) return KMR_OK;
 	hipSetDevice(h->device);
-	hipLaunchKernelGGL(scatter_counts_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, (const uint32_t *)dev_counts, (const uint32_t *)dev_pos, n, (uint32_t *)dev_position_counts);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, scatter_counts_kernel, dim3(grid_for(n)), dim3(256), 0, (const uint32_t *)dev_counts, (const uint32_t *)dev_pos, n, (uint32_t *)dev_position_counts);
 	return KMR_OK;
 }
 int kmr_score_counts_dev(kmr_handle *h, const void *dev_bases, const void *dev_offsets, uint64_t n_reads, const void *dev_position_counts,
@@ -3210,9 +3144,9 @@ int kmr_insert_records_dev(kmr_handle *h, const void *dev_records, uint64_t n) {
 	if (h->partition_mode) { int prc = insert_records_partition(h, dev_records, n); h->stream_base += n; return prc; }
 	int rc = ensure_capacity(h, n); if (rc) return rc;
 	TimeSpan t(h, 0);
-	with_w_ext(h, [&](auto W, auto EXT) { hipLaunchKernelGGL((insert_records_kernel<W(), EXT()>), dim3(grid_for(n)), dim3(256), 0, h->stream, table_of<W()>(h), (const uint32_t *)dev_records, n, dev_params(h), h->stream_base); });
+	rc = with_w_ext(h, [&](auto W, auto EXT) -> int { LAUNCH(h, (insert_records_kernel<W(), EXT()>), dim3(grid_for(n)), dim3(256), 0, table_of<W()>(h), (const uint32_t *)dev_records, n, dev_params(h), h->stream_base); return 0; });
 	t.end();
-	HIPCHK(h, hipGetLastError());
+	if (rc) return rc;
 	h->stream_base += n;
 	return KMR_OK;
 }
@@ -3310,13 +3244,10 @@ int kmr_sk_exchange_counts(kmr_handle *h, uint64_t *chunks, uint64_t *granules) 
 	DevBuf db; HIPCHK(h, db.alloc(16 * SK_OWNER_MAX));
 	unsigned long long *d = db.get<unsigned long long>();
 	HIPCHK(h, hipMemsetAsync(d, 0, 16 * SK_OWNER_MAX, h->stream));
-	hipLaunchKernelGGL(sk_close_kernel, dim3(grid_for(nl)), dim3(256), 0, h->stream, h->sk_state.get<unsigned long long>(), nl, h->l1.chunk_count.get<uint32_t>(), h->l1.cap);
-	if (head) hipLaunchKernelGGL(sk_owner_count_kernel, dim3(grid_for(head)), dim3(256), 0, h->stream, h->l1.chunk_list.get<uint32_t>(), h->l1.chunk_count.get<uint32_t>(), head, world, d, d + SK_OWNER_MAX, h->xr_lo, h->xr_hi);
-	hipError_t e = hipGetLastError();
+	LAUNCH(h, sk_close_kernel, dim3(grid_for(nl)), dim3(256), 0, h->sk_state.get<unsigned long long>(), nl, h->l1.chunk_count.get<uint32_t>(), h->l1.cap);
+	if (head) LAUNCH(h, sk_owner_count_kernel, dim3(grid_for(head)), dim3(256), 0, h->l1.chunk_list.get<uint32_t>(), h->l1.chunk_count.get<uint32_t>(), head, world, d, d + SK_OWNER_MAX, h->xr_lo, h->xr_hi);
 	std::vector<unsigned long long> hv(2 * SK_OWNER_MAX, 0);
-	if (e == hipSuccess) e = hipMemcpyAsync(hv.data(), d, 16 * SK_OWNER_MAX, hipMemcpyDeviceToHost, h->stream);
-	if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-	HIPCHK(h, e);
+	HIPCHK(h, fetch(h, hv.data(), d, 2 * SK_OWNER_MAX));
 	for (uint32_t r = 0; r < world; r++) { chunks[r] = hv[r]; granules[r] = hv[SK_OWNER_MAX + r]; }
 	return KMR_OK;
 }
@@ -3332,15 +3263,13 @@ int kmr_sk_exchange_pack_dev(kmr_handle *h, void *dev_data, void *dev_meta, cons
 	unsigned long long *d = db.get<unsigned long long>();
 	std::vector<unsigned long long> hv(4 * SK_OWNER_MAX, 0);
 	for (uint32_t r = 0; r < world; r++) { hv[r] = granule_offset[r]; hv[SK_OWNER_MAX + r] = chunk_offset[r]; }
-	hipError_t e = hipMemcpyAsync(d, hv.data(), 32 * SK_OWNER_MAX, hipMemcpyHostToDevice, h->stream);
-	if (e == hipSuccess && head) {
-		hipLaunchKernelGGL(sk_pack_kernel, dim3(grid_for((uint64_t)head * 64, 256, num_cus(h) * 8)), dim3(256), 0, h->stream, pool_view(h, h->l1), head, world, h->cfg.rank,
-		                   d, d + SK_OWNER_MAX, d + 2 * SK_OWNER_MAX, d + 3 * SK_OWNER_MAX, (uint4 *)dev_data, (uint2 *)dev_meta, h->xr_lo, h->xr_hi);
-		hipLaunchKernelGGL(sk_state_drop_kernel, dim3(grid_for(sk_list_count(h->sk_bits))), dim3(256), 0, h->stream, h->sk_state.get<unsigned long long>(), sk_list_count(h->sk_bits), world, h->cfg.rank, h->xr_lo, h->xr_hi);
-		e = hipGetLastError();
+	HIPCHK(h, hipMemcpyAsync(d, hv.data(), 32 * SK_OWNER_MAX, hipMemcpyHostToDevice, h->stream));
+	if (head) {
+		LAUNCH(h, sk_pack_kernel, dim3(grid_for((uint64_t)head * 64, 256, num_cus(h) * 8)), dim3(256), 0, pool_view(h, h->l1), head, world, h->cfg.rank,
+		       d, d + SK_OWNER_MAX, d + 2 * SK_OWNER_MAX, d + 3 * SK_OWNER_MAX, (uint4 *)dev_data, (uint2 *)dev_meta, h->xr_lo, h->xr_hi);
+		LAUNCH(h, sk_state_drop_kernel, dim3(grid_for(sk_list_count(h->sk_bits))), dim3(256), 0, h->sk_state.get<unsigned long long>(), sk_list_count(h->sk_bits), world, h->cfg.rank, h->xr_lo, h->xr_hi);
 	}
-	if (e == hipSuccess) e = hipStreamSynchronize(h->stream);      /* hv and d go out of scope */
-	HIPCHK(h, e);
+	HIPCHK(h, stream_wait(h));      /* hv and d go out of scope */
 	return KMR_OK;
 }
 /* the part of the list space the next kmr_sk_exchange_counts / kmr_sk_exchange_pack_dev are about ([0, ~0) = all of it) */
@@ -3390,19 +3319,17 @@ int kmr_sk_exchange_adopt_dev(kmr_handle *h, const void *dev_data, const void *d
 	const size_t need = 8 * (n_chunks + 1) + 4 * (n_chunks + 1) + 256;
 	rc = h->adopt_buf.reserve(h, "adopt_buf", need, need + need / 4); if (rc) return rc;
 	uint64_t *start = (uint64_t *)h->adopt_buf.get<uint8_t>(); uint32_t *cnt = (uint32_t *)(h->adopt_buf.get<uint8_t>() + 8 * (n_chunks + 1));
-	hipLaunchKernelGGL(sk_meta_counts_kernel, dim3(grid_for(n_chunks)), dim3(256), 0, h->stream, (const uint2 *)dev_meta, n_chunks, cnt);
-	rc = exclusive_scan(h, cnt, n_chunks, start);
+	/* (from here on a failure is carried to the wait at the end) */
+	rc = [&]() -> int { LAUNCH(h, sk_meta_counts_kernel, dim3(grid_for(n_chunks)), dim3(256), 0, (const uint2 *)dev_meta, n_chunks, cnt); return 0; }();
+	if (!rc) rc = exclusive_scan(h, cnt, n_chunks, start);
 	if (!rc && !h->d_uni && !declared) {
 		if (h->d_uni.alloc(8) != hipSuccess) rc = fail(h, KMR_ERR_OOM, "uniform-weight flags");
 		else { const uint32_t init[2] = {SK_UNI_NONE, 0u}; if (hipMemcpyAsync(h->d_uni.get<uint32_t>(), init, 8, hipMemcpyHostToDevice, h->stream) != hipSuccess) rc = fail(h, KMR_ERR_HIP, "uniform-weight flags"); else hipStreamSynchronize(h->stream); }
 	}
 	/* (senders that declare their weights -- kmr_sk_exchange_peer_uniform, what both drivers do -- spare the owner this look at every
 	 * received header: 3.5 ms for 4.2 GB at 8 ranks) */
-	if (!rc && !declared) hipLaunchKernelGGL(sk_uniform_check_kernel, dim3(grid_for(n_chunks)), dim3(256), 0, h->stream, (const uint4 *)dev_data, start, cnt, n_chunks, h->d_uni.get<uint32_t>());
-	if (!rc) {
-		hipLaunchKernelGGL(sk_adopt_kernel, dim3(grid), dim3(SK_ADOPT_WAVES * 64), 0, h->stream, (const uint4 *)dev_data, (const uint2 *)dev_meta, start, n_chunks, sk_params(h), pool_view(h, h->l1));
-		if (hipGetLastError() != hipSuccess) rc = fail(h, KMR_ERR_HIP, "sk_adopt_kernel launch");
-	}
+	if (!rc && !declared && launch_status(h->stream, sk_uniform_check_kernel, dim3(grid_for(n_chunks)), dim3(256), 0, (const uint4 *)dev_data, start, cnt, n_chunks, h->d_uni.get<uint32_t>()) != hipSuccess) rc = fail(h, KMR_ERR_HIP, "sk_uniform_check_kernel launch");
+	if (!rc && launch_status(h->stream, sk_adopt_kernel, dim3(grid), dim3(SK_ADOPT_WAVES * 64), 0, (const uint4 *)dev_data, (const uint2 *)dev_meta, start, n_chunks, sk_params(h), pool_view(h, h->l1)) != hipSuccess) rc = fail(h, KMR_ERR_HIP, "sk_adopt_kernel launch");
 	hipStreamSynchronize(h->stream);
 	return rc ? rc : sync_state(h);
 }
@@ -3463,8 +3390,7 @@ DevParams own_reads_params(kmr_handle *h, bool whole) {
 /* k-mers per read into nk (n) and their exclusive scan into koff (n + 1), queued: k-mer i of read r has slot koff[r] + i.  most_err:
  * two device words, zero before: the most k-mers of a read, and 1 if a read holds 2^32 or more */
 int kmer_slots_queue(kmr_handle *h, const uint64_t *offsets, uint64_t n, uint32_t *nk, uint64_t *koff, unsigned int *most_err) {
-	hipLaunchKernelGGL(compare_nk_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, offsets, n, h->k, nk, most_err, most_err + 1);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, compare_nk_kernel, dim3(grid_for(n)), dim3(256), 0, offsets, n, h->k, nk, most_err, most_err + 1);
 	return exclusive_scan_queue(h, nk, n, koff);
 }
 /* ... in h->cmp_buf (*koff), with the call's one fixed-size copy behind: all slots, the most of a read, the error word (waits).  A read
@@ -3478,9 +3404,9 @@ int kmer_slot_plan(kmr_handle *h, const uint64_t *offsets, uint64_t n, uint64_t 
 	*koff = B[CMP_B_KOFF].get<uint64_t>(); *total = 0;
 	HIPCHK(h, hipMemsetAsync(most_err, 0, 8, h->stream));
 	rc = kmer_slots_queue(h, offsets, n, B[CMP_B_NK].get<uint32_t>(), *koff, most_err); if (rc) return rc;
-	HIPCHK(h, hipMemcpyAsync(total, *koff + n, 8, hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(h, hipMemcpyAsync(hm, most_err, 8, hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(h, hipStreamSynchronize(h->stream));
+	HIPCHK(h, fetch_queue(h, total, *koff + n));
+	HIPCHK(h, fetch_queue(h, hm, most_err, 2));
+	HIPCHK(h, stream_wait(h));
 	*most = hm[0];
 	return hm[1] ? fail(h, KMR_ERR_UNSUPPORTED, refusal) : 0;
 }
@@ -3504,8 +3430,7 @@ int compare_totals(kmr_handle *h, kmr_handle *on, unsigned long long *tot) {
 	HIPCHK(on, hipMemsetAsync(tot, 0, 8 * CMP_T_WORDS, on->stream));
 	const uint64_t nw = map_entries(h->weak), ns = map_entries(h->sing);
 	if (nw + ns == 0) return 0;
-	hipLaunchKernelGGL(compare_totals_kernel, dim3(grid_for(nw + ns)), dim3(256), 0, on->stream, h->weak.vals.get<uint32_t>(), h->ext ? 15u : 3u, nw, h->sing.sweight.get<uint8_t>(), ns, tot);
-	HIPCHK(on, hipGetLastError());
+	LAUNCH(on, compare_totals_kernel, dim3(grid_for(nw + ns)), dim3(256), 0, h->weak.vals.get<uint32_t>(), value_words(h), nw, h->sing.sweight.get<uint8_t>(), ns, tot);
 	return 0;
 }
 
@@ -3518,13 +3443,11 @@ template <int W> int compare_spectrums_t(kmr_handle *h1, kmr_handle *h2, kmr_com
 	rc = compare_totals(h2, h2, tot2); if (rc) return rc;
 	const uint64_t nw1 = map_entries(h1->weak), ns1 = map_entries(h1->sing);
 	if (nw1 + ns1) {
-		hipLaunchKernelGGL(compare_maps_kernel<W>, dim3(grid_for(nw1 + ns1)), dim3(256), 0, h2->stream, view_of<W>(h1->weak, h1->ext ? 15u : 3u), nw1, view_of<W>(h1->sing, 0), ns1,
-		                   view_of<W>(h2->weak, h2->ext ? 15u : 3u), view_of<W>(h2->sing, 0), h2->hkb, acc);
-		HIPCHK(h2, hipGetLastError());
+		LAUNCH(h2, compare_maps_kernel<W>, dim3(grid_for(nw1 + ns1)), dim3(256), 0, view_of<W>(h1->weak, value_words(h1)), nw1, view_of<W>(h1->sing, 0), ns1,
+		       view_of<W>(h2->weak, value_words(h2)), view_of<W>(h2->sing, 0), h2->hkb, acc);
 	}
 	unsigned long long host[8 + CMP_T_WORDS];
-	HIPCHK(h2, hipMemcpyAsync(host, acc, sizeof(host), hipMemcpyDeviceToHost, h2->stream));
-	HIPCHK(h2, hipStreamSynchronize(h2->stream));
+	HIPCHK(h2, fetch(h2, host, acc, 8 + CMP_T_WORDS));
 	const CompareRec *a = (const CompareRec *)host; const unsigned long long *t = host + 8;
 	out->size1 = a->size1; out->size2 = t[CMP_T_SIZE]; out->common = a->common; out->common_count1 = a->common_count1; out->common_count2 = a->common_count2;
 	out->total_count1 = a->total_count1; out->total_count2 = t[CMP_T_TOTAL]; out->saturated = a->saturated + t[CMP_T_SATURATED];
@@ -3538,12 +3461,10 @@ template <int W> int compare_long_run(kmr_handle *h, const uint64_t *stage, cons
 	int rc = B[CMP_B_CNT].reserve(h, "compare long counts", 4 * m); if (rc) return rc;
 	rc = B[CMP_B_LOFF].reserve(h, "compare long offsets", 8 * (m + 1)); if (rc) return rc;
 	uint32_t *cnt = B[CMP_B_CNT].get<uint32_t>(); uint64_t *loff = B[CMP_B_LOFF].get<uint64_t>();
-	hipLaunchKernelGGL(compare_long_count_kernel, dim3(grid_for(m)), block, 0, h->stream, koff, r0, m, cap, tot2, cnt, out);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, compare_long_count_kernel, dim3(grid_for(m)), block, 0, koff, r0, m, cap, tot2, cnt, out);
 	rc = exclusive_scan_queue(h, cnt, m, loff); if (rc) return rc;
 	uint64_t c = 0;
-	HIPCHK(h, hipMemcpyAsync(&c, loff + m, 8, hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(h, hipStreamSynchronize(h->stream));
+	HIPCHK(h, fetch(h, &c, loff + m));
 	if (c == 0) return 0;
 	if (c >= 0xffffffffull) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_compare_reads: a run of the sorted path holds 2^32 - 1 k-mers or more (lower kmr_tune \"compare_stage_kmers\")");
 	rc = B[CMP_B_SRC].reserve(h, "compare sort slots", 4 * c); if (rc) return rc;
@@ -3554,8 +3475,7 @@ template <int W> int compare_long_run(kmr_handle *h, const uint64_t *stage, cons
 	uint32_t *src = B[CMP_B_SRC].get<uint32_t>(), *rid = B[CMP_B_RID].get<uint32_t>();
 	uint64_t *hscan = B[CMP_B_HSCAN].get<uint64_t>(), *start = B[CMP_B_START].get<uint64_t>();
 	const dim3 cgrid(grid_for(c));
-	hipLaunchKernelGGL(compare_long_fill_kernel, cgrid, block, 0, h->stream, koff, r0, m, (const uint64_t *)loff, c, src, rid, B[CMP_B_PERM].get<uint32_t>());
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, compare_long_fill_kernel, cgrid, block, 0, koff, r0, m, (const uint64_t *)loff, c, src, rid, B[CMP_B_PERM].get<uint32_t>());
 	/* least significant first: the key words, then the read; the sort is stable */
 	SortColumn cols[W + 1];
 	for (int w = 0; w < W; w++) cols[w] = SortColumn{stage + w, (uint64_t)W, src, nullptr};
@@ -3563,13 +3483,11 @@ template <int W> int compare_long_run(kmr_handle *h, const uint64_t *stage, cons
 	const uint32_t *perm; unsigned long long *kout;
 	rc = sort_by_columns(h, h->cmp_sort, cols, W + 1, B[CMP_B_PERM].get<uint32_t>(), c, "kmr_compare_reads", &perm, &kout); if (rc) return rc;
 	uint32_t *head = (uint32_t *)kout;      /* the sort keys are dead once the order stands */
-	hipLaunchKernelGGL(compare_long_heads_kernel, cgrid, block, 0, h->stream, stage, (uint32_t)W, (const uint32_t *)src, (const uint32_t *)rid, perm, c, head);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, compare_long_heads_kernel, cgrid, block, 0, stage, (uint32_t)W, (const uint32_t *)src, (const uint32_t *)rid, perm, c, head);
 	rc = exclusive_scan_queue(h, head, c, hscan); if (rc) return rc;
 	rc = group_starts(h, head, hscan, c, start); if (rc) return rc;
-	hipLaunchKernelGGL(compare_long_add_kernel<W>, cgrid, block, 0, h->stream, stage, (const uint32_t *)src, (const uint32_t *)rid, perm, (const uint32_t *)head, (const uint64_t *)hscan,
-	                   (const uint64_t *)start, c, r0, view_of<W>(h->weak, h->ext ? 15u : 3u), view_of<W>(h->sing, 0), h->hkb, out);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, compare_long_add_kernel<W>, cgrid, block, 0, stage, (const uint32_t *)src, (const uint32_t *)rid, perm, (const uint32_t *)head, (const uint64_t *)hscan,
+	       (const uint64_t *)start, c, r0, view_of<W>(h->weak, value_words(h)), view_of<W>(h->sing, 0), h->hkb, out);
 	return 0;
 }
 
@@ -3591,7 +3509,7 @@ template <int W> int compare_reads_t(kmr_handle *h, const ReadsView &all, Compar
 		cut = cut_runs(n, budget, [&](uint64_t r) { return hk[r]; });
 	}
 	const DevParams dp = own_reads_params(h, false);      /* a read's own map subtracts nothing */
-	const MapView<W> weak = view_of<W>(h->weak, h->ext ? 15u : 3u), sing = view_of<W>(h->sing, 0);
+	const MapView<W> weak = view_of<W>(h->weak, value_words(h)), sing = view_of<W>(h->sing, 0);
 	for (size_t i = 0; i + 1 < cut.size(); i++) {
 		const uint64_t r0 = cut[i], m = cut[i + 1] - r0;
 		const uint64_t slots = hk.empty() ? total : hk[r0 + m] - hk[r0];
@@ -3604,9 +3522,8 @@ template <int W> int compare_reads_t(kmr_handle *h, const ReadsView &all, Compar
 			const size_t smem = (size_t)CMP_WAVES * cap * W * 8;
 			HIPCHK(h, hipFuncSetAttribute((const void *)compare_reads_lds_kernel<W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)CMP_WAVES * CMP_CAP_MOST * W * 8)));
 			const uint64_t blocks = std::min<uint64_t>((m + CMP_WAVES - 1) / CMP_WAVES, (uint64_t)num_cus(h) * 16);
-			hipLaunchKernelGGL(compare_reads_lds_kernel<W>, dim3((unsigned)blocks), dim3(CMP_WAVES * 64), smem, h->stream, stage, (const uint64_t *)koff, r0, m, cap, weak, sing, h->hkb,
-			                   (const unsigned long long *)tot2, out);
-			HIPCHK(h, hipGetLastError());
+			LAUNCH(h, compare_reads_lds_kernel<W>, dim3((unsigned)blocks), dim3(CMP_WAVES * 64), smem, stage, (const uint64_t *)koff, r0, m, cap, weak, sing, h->hkb,
+			       (const unsigned long long *)tot2, out);
 		}
 		if (cap == 0 || most > cap) { rc = compare_long_run<W>(h, stage, koff, r0, m, cap, tot2, out); if (rc) return rc; }
 	}
@@ -3636,12 +3553,11 @@ template <int W> int match_create_t(kmr_handle *h, kmr_match *m, const uint8_t *
 	HIPCHK(h, hipMemsetAsync(err, 0, 4, h->stream)); HIPCHK(h, hipMemsetAsync(eoff, 0, 8, h->stream));
 	uint64_t E = 0; uint32_t herr = 0;
 	if (nc) {
-		hipLaunchKernelGGL(match_edge_count_kernel, dim3(grid_for(nc)), block, 0, h->stream, offsets, nc, h->k, M, cnt, err);
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, match_edge_count_kernel, dim3(grid_for(nc)), block, 0, offsets, nc, h->k, M, cnt, err);
 		int rc = exclusive_scan_queue(h, cnt, nc, eoff); if (rc) return rc;
-		HIPCHK(h, hipMemcpyAsync(&E, eoff + nc, 8, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(h, hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(h, hipStreamSynchronize(h->stream));
+		HIPCHK(h, fetch_queue(h, &E, eoff + nc));
+		HIPCHK(h, fetch_queue(h, &herr, err));
+		HIPCHK(h, stream_wait(h));
 	}
 	if (herr) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_match_create: a contig of 2^31 - 1 bases or more");
 	if (E >= 0xffffffffull) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_match_create: 2^32 - 1 edge k-mers or more");
@@ -3653,26 +3569,24 @@ template <int W> int match_create_t(kmr_handle *h, kmr_match *m, const uint8_t *
 		HIPCHK(h, alloc_n(b_keys, &keys, E * W)); HIPCHK(h, alloc_n(b_contig, &contig, E)); HIPCHK(h, alloc_n(b_order, &order, E));
 		HIPCHK(h, alloc_n(b_flags, &flags, 3 * E)); HIPCHK(h, alloc_n(b_scans, &scans, 3 * (E + 1)));
 		const dim3 egrid(grid_for(E));
-		hipLaunchKernelGGL(match_edge_keys_kernel<W>, egrid, block, 0, h->stream, bases, offsets, nc, h->k, M, (const uint64_t *)eoff, E, keys, contig, order);
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, match_edge_keys_kernel<W>, egrid, block, 0, bases, offsets, nc, h->k, M, (const uint64_t *)eoff, E, keys, contig, order);
 		/* least significant first: the contig, then the key words from the last to the first; the sort is stable */
 		SortColumn cols[W + 1];
 		cols[0] = SortColumn{nullptr, 0, nullptr, contig};
 		for (int w = 0; w < W; w++) cols[1 + w] = SortColumn{keys + (W - 1 - w), (uint64_t)W, nullptr, nullptr};
 		int rc = sort_by_columns(h, sort, cols, W + 1, order, E, "kmr_match_create", &perm, nullptr); if (rc) return rc;
-		MapView<W> weak = view_of<W>(h->weak, h->ext ? 15u : 3u), sing = view_of<W>(h->sing, 0);
+		MapView<W> weak = view_of<W>(h->weak, value_words(h)), sing = view_of<W>(h->sing, 0);
 		if (!h->has_singletons) sing.nb = 0;
 		uint32_t *khead = flags, *kkept = flags + E, *phead = flags + 2 * E;
 		uint64_t *hscan = scans, *kscan = scans + (E + 1), *pscan = scans + 2 * (E + 1);
-		hipLaunchKernelGGL(match_flags_kernel<W>, egrid, block, 0, h->stream, (const uint64_t *)keys, (const uint32_t *)contig, (const uint32_t *)perm, E, weak, sing, h->hkb, khead, kkept, phead);
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, match_flags_kernel<W>, egrid, block, 0, (const uint64_t *)keys, (const uint32_t *)contig, (const uint32_t *)perm, E, weak, sing, h->hkb, khead, kkept, phead);
 		rc = exclusive_scan_queue(h, khead, E, hscan); if (rc) return rc;
 		rc = exclusive_scan_queue(h, kkept, E, kscan); if (rc) return rc;
 		rc = exclusive_scan_queue(h, phead, E, pscan); if (rc) return rc;
-		HIPCHK(h, hipMemcpyAsync(&m->n_distinct_keys, hscan + E, 8, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(h, hipMemcpyAsync(&m->n_keys_in_spectrum, kscan + E, 8, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(h, hipMemcpyAsync(&n_lists, pscan + E, 8, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(h, hipStreamSynchronize(h->stream));
+		HIPCHK(h, fetch_queue(h, &m->n_distinct_keys, hscan + E));
+		HIPCHK(h, fetch_queue(h, &m->n_keys_in_spectrum, kscan + E));
+		HIPCHK(h, fetch_queue(h, &n_lists, pscan + E));
+		HIPCHK(h, stream_wait(h));
 	}
 	m->log2cap = 6;
 	while ((1ull << m->log2cap) < 2 * m->n_keys_in_spectrum) m->log2cap++;      /* at most half full */
@@ -3681,10 +3595,9 @@ template <int W> int match_create_t(kmr_handle *h, kmr_match *m, const uint8_t *
 	HIPCHK(h, m->tcontig.alloc(std::max<size_t>(4 * n_lists, 256)));
 	HIPCHK(h, hipMemsetAsync(m->slots.get(), 0xff, slot_bytes_, h->stream));
 	if (m->n_keys_in_spectrum) {
-		hipLaunchKernelGGL(match_table_fill_kernel<W>, dim3(grid_for(E)), block, 0, h->stream, (const uint64_t *)keys, (const uint32_t *)contig, (const uint32_t *)perm, E,
-		                   (const uint32_t *)flags, (const uint32_t *)(flags + E), (const uint32_t *)(flags + 2 * E), (const uint64_t *)(scans + 2 * (E + 1)),
-		                   m->slots.get<uint64_t>(), 64u - m->log2cap, m->tcontig.get<uint32_t>());
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, match_table_fill_kernel<W>, dim3(grid_for(E)), block, 0, (const uint64_t *)keys, (const uint32_t *)contig, (const uint32_t *)perm, E,
+		       (const uint32_t *)flags, (const uint32_t *)(flags + E), (const uint32_t *)(flags + 2 * E), (const uint64_t *)(scans + 2 * (E + 1)),
+		       m->slots.get<uint64_t>(), 64u - m->log2cap, m->tcontig.get<uint32_t>());
 	}
 	HIPCHK(h, hipStreamSynchronize(h->stream));      /* the temporaries go */
 	return KMR_OK;
@@ -3707,8 +3620,7 @@ template <int W> int match_add_t(kmr_handle *h, kmr_match *m, const ReadsView &a
 		op.cap = m->hit_cap; op.mate = mate; op.first_global = first_global;
 		rc = launch_extract<W, false>(h, rv, dp, op); if (rc) return rc;
 		uint64_t count = 0;
-		HIPCHK(h, hipMemcpyAsync(&count, m->hit_count.get(), 8, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(h, hipStreamSynchronize(h->stream));
+		HIPCHK(h, fetch(h, &count, m->hit_count.get()));
 		h->last_match_attempts = attempt;
 		if (count <= m->hit_cap) { m->n_hits = count; return KMR_OK; }
 		/* the records did not fit: room for all of them (the count of a batch repeats), the earlier batches' records kept, and once more */
@@ -3747,8 +3659,7 @@ template <int W> int extend_run_spectra(kmr_handle *h, ExtendBufs &B, const Read
 	rc = B.val.reserve(h, "extend weights", 4 * S); if (rc) return rc;
 	uint32_t *sgrp = B.sgrp.get<uint32_t>(), *wflag = B.flags.get<uint32_t>(), *sflag = wflag + S, *cnt = B.cnt.get<uint32_t>(); float *val = B.val.get<float>();
 	uint64_t *wscan = B.scans.get<uint64_t>(), *sscan = wscan + (S + 1);
-	hipLaunchKernelGGL(extend_fill_kernel, sgrid, block, 0, h->stream, koff, i0, ni, grp, S, sgrp, B.order.get<uint32_t>());
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, extend_fill_kernel, sgrid, block, 0, koff, i0, ni, grp, S, sgrp, B.order.get<uint32_t>());
 	/* least significant first: the key words from the last to the first, then (contig, source); the sort is stable */
 	SortColumn cols[W + 1];
 	for (int w = 0; w < W; w++) cols[w] = SortColumn{stage + (W - 1 - w), (uint64_t)W + 1, nullptr, nullptr};
@@ -3756,23 +3667,21 @@ template <int W> int extend_run_spectra(kmr_handle *h, ExtendBufs &B, const Read
 	const uint32_t *perm; unsigned long long *sorted_grp;      /* the last pass's keys */
 	rc = sort_by_columns(h, B.sort, cols, W + 1, B.order.get<uint32_t>(), S, "kmr_extend_contigs", &perm, &sorted_grp); if (rc) return rc;
 	tr.mark(2, h->stream);
-	hipLaunchKernelGGL(extend_reduce_kernel, sgrid, block, 0, h->stream, stage, (uint32_t)W, (const uint32_t *)sgrp, perm, S, h->cfg.separate_singletons ? 1u : 0u, wflag, sflag, cnt, val);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, extend_reduce_kernel, sgrid, block, 0, stage, (uint32_t)W, (const uint32_t *)sgrp, perm, S, h->cfg.separate_singletons ? 1u : 0u, wflag, sflag, cnt, val);
 	rc = exclusive_scan_queue(h, wflag, S, wscan); if (rc) return rc;
 	rc = exclusive_scan_queue(h, sflag, S, sscan); if (rc) return rc;
 	uint64_t nw = 0, ns = 0;
-	HIPCHK(h, hipMemcpyAsync(&nw, wscan + S, 8, hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(h, hipMemcpyAsync(&ns, sscan + S, 8, hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(h, hipStreamSynchronize(h->stream));
+	HIPCHK(h, fetch_queue(h, &nw, wscan + S));
+	HIPCHK(h, fetch_queue(h, &ns, sscan + S));
+	HIPCHK(h, stream_wait(h));
 	rc = B.wkeys.reserve(h, "extend weak keys", std::max<size_t>(8ull * W * nw, 256)); if (rc) return rc;
 	rc = B.wcnt.reserve(h, "extend weak counts", std::max<size_t>(4 * nw, 256)); if (rc) return rc;
 	rc = B.wval.reserve(h, "extend weak weights", std::max<size_t>(4 * nw, 256)); if (rc) return rc;
 	rc = B.skeys.reserve(h, "extend solid keys", std::max<size_t>(8ull * W * ns, 256)); if (rc) return rc;
 	A.wkeys = B.wkeys.get<uint64_t>(); A.wcnt = B.wcnt.get<uint32_t>(); A.wval = B.wval.get<float>(); A.skeys = B.skeys.get<uint64_t>();
-	hipLaunchKernelGGL(extend_compact_kernel, sgrid, block, 0, h->stream, stage, (uint32_t)W, perm, S, (const uint32_t *)wflag, (const uint32_t *)sflag, (const uint64_t *)wscan,
-	                   (const uint64_t *)sscan, (const uint32_t *)cnt, (const float *)val, B.wkeys.get<uint64_t>(), B.wcnt.get<uint32_t>(), B.wval.get<float>(), B.skeys.get<uint64_t>());
-	hipLaunchKernelGGL(extend_bounds_kernel, dim3(grid_for(A.m)), block, 0, h->stream, (const unsigned long long *)sorted_grp, S, (const uint64_t *)wscan, (const uint64_t *)sscan, A.c0, A.m, (uint64_t *)A.bounds);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, extend_compact_kernel, sgrid, block, 0, stage, (uint32_t)W, perm, S, (const uint32_t *)wflag, (const uint32_t *)sflag, (const uint64_t *)wscan,
+	       (const uint64_t *)sscan, (const uint32_t *)cnt, (const float *)val, B.wkeys.get<uint64_t>(), B.wcnt.get<uint32_t>(), B.wval.get<float>(), B.skeys.get<uint64_t>());
+	LAUNCH(h, extend_bounds_kernel, dim3(grid_for(A.m)), block, 0, (const unsigned long long *)sorted_grp, S, (const uint64_t *)wscan, (const uint64_t *)sscan, A.c0, A.m, (uint64_t *)A.bounds);
 	return 0;
 }
 
@@ -3806,13 +3715,12 @@ template <int W> int extend_t(kmr_handle *h, const kmr_reads *contigs, const kmr
 	uint32_t *err; HIPCHK(h, alloc_n(b_small, &err, (size_t)64));
 	unsigned long long *info = (unsigned long long *)(err + 8);      /* (err + 2: kmer_slots_queue's two words) */
 	HIPCHK(h, hipMemsetAsync(err, 0, 256, h->stream));
-	hipLaunchKernelGGL(extend_check_offsets_kernel, dim3(grid_for(nc + 1)), block, 0, h->stream, po, nc, err);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, extend_check_offsets_kernel, dim3(grid_for(nc + 1)), block, 0, po, nc, err);
 	std::vector<uint64_t> hpo(nc + 1);
 	uint32_t herr = 0;
-	HIPCHK(h, hipMemcpyAsync(hpo.data(), po, 8 * (nc + 1), hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(h, hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(h, hipStreamSynchronize(h->stream));
+	HIPCHK(h, fetch_queue(h, hpo.data(), po, nc + 1));
+	HIPCHK(h, fetch_queue(h, &herr, err));
+	HIPCHK(h, stream_wait(h));
 	if (herr) return fail(h, KMR_ERR_INVALID_ARG, "kmr_extend_contigs: pool_offsets does not start at 0 or does not ascend");
 	const uint64_t P = hpo[nc], n_items = P + nc;
 	if (n_items >= 0xffffffffull) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_extend_contigs: 2^32 - 1 pooled reads and contigs or more");
@@ -3821,13 +3729,12 @@ template <int W> int extend_t(kmr_handle *h, const kmr_reads *contigs, const kmr
 	uint32_t *len, *grp, *nk; uint64_t *goff, *koff;
 	HIPCHK(h, alloc_n(b_len, &len, n_items)); HIPCHK(h, alloc_n(b_grp, &grp, n_items)); HIPCHK(h, alloc_n(b_goff, &goff, n_items + 1));
 	HIPCHK(h, alloc_n(b_nk, &nk, n_items)); HIPCHK(h, alloc_n(b_koff, &koff, n_items + 1));
-	hipLaunchKernelGGL(extend_item_kernel, dim3(grid_for(n_items)), block, 0, h->stream, po, pr, active, reads->offsets.get<uint64_t>(), reads->n, coff, nc, n_items, len, grp, err);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, extend_item_kernel, dim3(grid_for(n_items)), block, 0, po, pr, active, reads->offsets.get<uint64_t>(), reads->n, coff, nc, n_items, len, grp, err);
 	int rc = exclusive_scan_queue(h, len, n_items, goff); if (rc) return rc;
 	uint64_t G = 0;
-	HIPCHK(h, hipMemcpyAsync(&G, goff + n_items, 8, hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(h, hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(h, hipStreamSynchronize(h->stream));
+	HIPCHK(h, fetch_queue(h, &G, goff + n_items));
+	HIPCHK(h, fetch_queue(h, &herr, err));
+	HIPCHK(h, stream_wait(h));
 	if (herr & 2u) return fail(h, KMR_ERR_INVALID_ARG, "kmr_extend_contigs: a pool index lies outside the read batch");
 	if (herr & 4u) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_extend_contigs: a sequence of 2^31 - 1 bases or more");
 	/* 2: the gathered batch and its k-mer slots */
@@ -3836,15 +3743,13 @@ template <int W> int extend_t(kmr_handle *h, const kmr_reads *contigs, const kmr
 	uint8_t *gb = b_gb.get<uint8_t>(), *gq = b_gq.get<uint8_t>();
 	HIPCHK(h, hipMemsetAsync(gb + G, 0, 64, h->stream)); HIPCHK(h, hipMemsetAsync(gq + G, 0, 64, h->stream));
 	if (G) {
-		hipLaunchKernelGGL(extend_gather_kernel, dim3(grid_for((G + 63) / 64)), block, 0, h->stream, (const uint64_t *)goff, n_items, G, po, pr, (const uint32_t *)grp, reads->bases.get<uint8_t>(),
-		                   reads->quals.get<uint8_t>(), reads->offsets.get<uint64_t>(), cbases, coff, gb, gq);
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, extend_gather_kernel, dim3(grid_for((G + 63) / 64)), block, 0, (const uint64_t *)goff, n_items, G, po, pr, (const uint32_t *)grp, reads->bases.get<uint8_t>(),
+		       reads->quals.get<uint8_t>(), reads->offsets.get<uint64_t>(), cbases, coff, gb, gq);
 	}
 	rc = kmer_slots_queue(h, goff, n_items, nk, koff, err + 2); if (rc) return rc;      /* (an item of 2^32 k-mers was refused above) */
 	tg.mark(1, h->stream);
 	std::vector<uint64_t> hk(n_items + 1);
-	HIPCHK(h, hipMemcpyAsync(hk.data(), koff, 8 * (n_items + 1), hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(h, hipStreamSynchronize(h->stream));
+	HIPCHK(h, fetch(h, hk.data(), koff, n_items + 1));
 	h->last_extend_ms[0] = tg.ms(0, 1);
 	/* 3: runs of whole contigs, each with its pool (cut_runs); contig c's items begin at hpo[c] + c */
 	const uint64_t budget = h->tune.extend_stage_kmers ? h->tune.extend_stage_kmers : EXT_STAGE_SLOTS;
@@ -3878,8 +3783,7 @@ template <int W> int extend_t(kmr_handle *h, const kmr_reads *contigs, const kmr
 		const uint64_t blocks = std::min<uint64_t>((m + EXT_WAVES - 1) / EXT_WAVES, (uint64_t)num_cus(h) * 8);
 		A.rec_global = nullptr;
 		if (!rec_lds) { rc = B.rec.reserve(h, "extend recorded keys", std::max<size_t>(rec_wave * EXT_WAVES * blocks, 256)); if (rc) return rc; A.rec_global = B.rec.get<uint64_t>(); }
-		hipLaunchKernelGGL(extend_contigs_kernel<W>, dim3((unsigned)blocks), dim3(EXT_WAVES * 64), rec_lds ? rec_wave * EXT_WAVES : 0, h->stream, A);
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, extend_contigs_kernel<W>, dim3((unsigned)blocks), dim3(EXT_WAVES * 64), rec_lds ? rec_wave * EXT_WAVES : 0, A);
 		tr.mark(4, h->stream);
 		h->last_extend_runs++;
 		if (tr.on) {
@@ -3888,21 +3792,19 @@ template <int W> int extend_t(kmr_handle *h, const kmr_reads *contigs, const kmr
 		}
 	}
 	/* 4: the result batch */
-	hipLaunchKernelGGL(extend_newlen_kernel, dim3(grid_for(nc)), block, 0, h->stream, coff, nc, (const uint32_t *)left, (const uint32_t *)right, newlen, info);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, extend_newlen_kernel, dim3(grid_for(nc)), block, 0, coff, nc, (const uint32_t *)left, (const uint32_t *)right, newlen, info);
 	rc = exclusive_scan_queue(h, newlen, nc, noff); if (rc) return rc;
 	unsigned long long hinfo[2] = {0, 0};
-	HIPCHK(h, hipMemcpyAsync(&result->total, noff + nc, 8, hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(h, hipMemcpyAsync(hinfo, info, 16, hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(h, hipStreamSynchronize(h->stream));
+	HIPCHK(h, fetch_queue(h, &result->total, noff + nc));
+	HIPCHK(h, fetch_queue(h, hinfo, info, 2));
+	HIPCHK(h, stream_wait(h));
 	out->n_extended = hinfo[0]; out->bases_added = hinfo[1];
 	const uint64_t T = result->total;
 	HIPCHK(h, result->bases.alloc(T + 64)); HIPCHK(h, result->quals.alloc(T + 64));
 	HIPCHK(h, hipMemsetAsync(result->bases.get<uint8_t>() + T, 0, 64, h->stream)); HIPCHK(h, hipMemsetAsync(result->quals.get<uint8_t>() + T, 0, 64, h->stream));
 	if (T) {
-		hipLaunchKernelGGL(extend_result_kernel, dim3(grid_for((T + 63) / 64)), block, 0, h->stream, (const uint64_t *)noff, nc, T, b_seq.get<uint8_t>(), coff, (const uint32_t *)left, maxx,
-		                   result->bases.get<uint8_t>(), result->quals.get<uint8_t>());
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, extend_result_kernel, dim3(grid_for((T + 63) / 64)), block, 0, (const uint64_t *)noff, nc, T, b_seq.get<uint8_t>(), coff, (const uint32_t *)left, maxx,
+		       result->bases.get<uint8_t>(), result->quals.get<uint8_t>());
 	}
 	HIPCHK(h, hipStreamSynchronize(h->stream));      /* the temporaries go */
 	out->result = result.release();

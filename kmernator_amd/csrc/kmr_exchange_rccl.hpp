@@ -99,8 +99,7 @@ static int rccl_allgather_u64(void *user, const uint64_t *mine, uint64_t n, uint
 	unsigned long long *d = h->xc_small.get<unsigned long long>();      /* [n] mine, then [world][n] */
 	HIPCHK(h, hipMemcpyAsync(d, mine, 8 * n, hipMemcpyHostToDevice, h->stream));
 	RCCLCHK(h, g_rccl.AllGather(d, d + n, n, ncclUint64, (ncclComm_t)h->xc_comm, h->stream));
-	HIPCHK(h, hipMemcpyAsync(all, d + n, 8 * n * world, hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(h, hipStreamSynchronize(h->stream));
+	HIPCHK(h, fetch(h, all, d + n, n * world));
 	return 0;
 }
 static int rccl_alltoallv_dev(void *user, const void *send, const uint64_t *send_off, const uint64_t *send_bytes,

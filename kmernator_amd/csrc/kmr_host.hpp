@@ -1,7 +1,8 @@
 /*
  * kmr_host.hpp -- what the host side of the library shares between its translation units (kmr_api.hip: the spectrum; kmr_stages.hip:
  * the read stages): device memory (dev_malloc, DevBuf, the live-block counter), the handle and the result objects, error reporting
- * (HIPCHK, fail), launch and dispatch helpers, the few spectrum-side functions the stages call, and the sorts of kmr_sort.hip.
+ * (HIPCHK, fail), the checked launch (LAUNCH, launch_status), read-backs (fetch_queue, stream_wait, fetch), dispatch helpers, the few
+ * spectrum-side functions the stages call, and the sorts of kmr_sort.hip.
  * Internal: nothing here is an exported symbol of the library (namespace kmr_host and the structs are of hidden visibility), and no
  * kernel is defined here.
  */
@@ -402,6 +403,26 @@ inline std::string hip_err_text(hipError_t e) { return std::string(hipGetErrorSt
 #define HIPCHK(h, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
 	(h)->err = std::string(#call) + ": " + hip_err_text(e_); \
 	return e_ == hipErrorOutOfMemory ? KMR_ERR_OOM : KMR_ERR_HIP; } } while (0)
+
+/* The one kernel launch of the library: the arguments converted to the kernel's parameter types as in an ordinary call (a kernel's
+ * default arguments are spelled out), and what hipGetLastError() says of it.  launch_status hands that back and touches nothing
+ * else (the sites that go on without the kernel or report in their own way, and the one entry point without a handle: its result
+ * is never dropped, tests/test_host_launch_sites.py); LAUNCH is the launch on the handle's stream as a statement: a failure names
+ * the kernel in h->err and leaves the enclosing function with HIPCHK's code.  A grid of no blocks is an error: `if (n) LAUNCH(...)`
+ * keeps its condition. */
+template <class... P, class... A> hipError_t launch_status(hipStream_t stream, void (*kern)(P...), dim3 grid, dim3 block, size_t lds, A... args) {
+	hipLaunchKernelGGL(kern, grid, block, lds, stream, args...);
+	return hipGetLastError();
+}
+#define LAUNCH(h, kern, grid, block, lds, ...) do { hipError_t e_ = launch_status((h)->stream, kern, grid, block, lds, ##__VA_ARGS__); if (e_ != hipSuccess) { \
+	(h)->err = std::string(#kern) + ": " + hip_err_text(e_); \
+	return e_ == hipErrorOutOfMemory ? KMR_ERR_OOM : KMR_ERR_HIP; } } while (0)
+
+/* Small results back to the host over the handle's stream, each under HIPCHK: fetch_queue queues the copy of n elements of T,
+ * stream_wait waits for what is queued (several copies, one wait), fetch is both for a single value or array */
+template <class T> hipError_t fetch_queue(kmr_handle *h, T *dst, const void *src, size_t n = 1) { return hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToHost, h->stream); }
+inline hipError_t stream_wait(kmr_handle *h) { return hipStreamSynchronize(h->stream); }
+template <class T> hipError_t fetch(kmr_handle *h, T *dst, const void *src, size_t n = 1) { const hipError_t e = fetch_queue(h, dst, src, n); return e != hipSuccess ? e : stream_wait(h); }
 
 inline int DevBuf::reserve(kmr_handle *h, const char *what, size_t need, size_t bytes) {
 	if (p_ && cap_ >= need) return 0;

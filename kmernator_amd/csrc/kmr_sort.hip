@@ -50,8 +50,7 @@ int sort_by_columns(kmr_handle *h, SortBufs &bufs, const SortColumn *cols, int n
 	rc = bufs.kout.reserve(h, "sort keys", 8 * n); if (rc) return rc;
 	uint32_t *perm = order, *perm2 = bufs.perm2.get<uint32_t>();
 	for (int i = 0; i < ncols; i++) {
-		hipLaunchKernelGGL(sort_column_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, cols[i], (const uint32_t *)perm, n, bufs.kin.get<unsigned long long>());
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, sort_column_kernel, dim3(grid_for(n)), dim3(256), 0, cols[i], (const uint32_t *)perm, n, bufs.kin.get<unsigned long long>());
 		rc = sort_pairs(h, bufs, bufs.kin.get<unsigned long long>(), bufs.kout.get<unsigned long long>(), perm, perm2, n, who); if (rc) return rc;
 		std::swap(perm, perm2);
 	}
@@ -61,8 +60,7 @@ int sort_by_columns(kmr_handle *h, SortBufs &bufs, const SortColumn *cols, int n
 }
 
 int group_starts(kmr_handle *h, const uint32_t *head, const uint64_t *hscan, uint64_t n, uint64_t *start) {
-	hipLaunchKernelGGL(group_starts_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, head, hscan, n, start);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, group_starts_kernel, dim3(grid_for(n)), dim3(256), 0, head, hscan, n, start);
 	return 0;
 }
 

@@ -80,22 +80,18 @@ template <class T> void copy_out(hipError_t &e, T *dst, const DevBuf &buf, uint6
 /* the two-bit launches of the spectrum's packed feed path (kmr_add_reads_twobit_dev) */
 namespace kmr_host {
 int twobit_byte_offsets(kmr_handle *h, const uint64_t *offsets, uint64_t n, uint32_t *len, uint64_t *off) {
-	hipLaunchKernelGGL(twobit_bytes_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, offsets, n, len);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, twobit_bytes_kernel, dim3(grid_for(n)), dim3(256), 0, offsets, n, len);
 	return exclusive_scan(h, len, n, off);
 }
 int twobit_rel_offsets(kmr_handle *h, const uint64_t *offsets, uint64_t n, uint64_t *rel) {
-	hipLaunchKernelGGL(offsets_rel_kernel, dim3(grid_for(n + 1)), dim3(256), 0, h->stream, offsets, n, rel);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, offsets_rel_kernel, dim3(grid_for(n + 1)), dim3(256), 0, offsets, n, rel);
 	return 0;
 }
 int twobit_unpack(kmr_handle *h, const uint8_t *twobit, const uint64_t *twobit_off, const uint64_t *offsets, const uint64_t *mk_off, const uint32_t *mk_pos, const uint8_t *mk_char,
                   uint64_t n, uint8_t *bases, uint64_t *rel) {
-	hipLaunchKernelGGL(twobit_unpack_kernel, dim3((unsigned)std::min<uint64_t>((n + 255) / 256, (uint64_t)num_cus(h) * 32)), dim3(256), 0, h->stream, twobit, twobit_off, offsets, n, bases, rel);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, twobit_unpack_kernel, dim3((unsigned)std::min<uint64_t>((n + 255) / 256, (uint64_t)num_cus(h) * 32)), dim3(256), 0, twobit, twobit_off, offsets, n, bases, rel);
 	if (mk_off) {
-		hipLaunchKernelGGL(twobit_markup_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, mk_off, mk_pos, mk_char, (const uint64_t *)rel, n, bases);
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, twobit_markup_kernel, dim3(grid_for(n)), dim3(256), 0, mk_off, mk_pos, mk_char, (const uint64_t *)rel, n, bases);
 	}
 	return 0;
 }
@@ -118,8 +114,7 @@ static int ingest_dev(kmr_handle *h, const uint8_t *text, uint64_t len, uint32_t
 	if (nblk) {
 		if (nblk > 0x7fffffffull) return fail(h, KMR_ERR_INVALID_ARG, "FASTQ block too large for one call");
 		HIPCHK(h, blk.alloc(4 * nblk)); HIPCHK(h, bbase.alloc(8 * (nblk + 1)));
-		hipLaunchKernelGGL(ingest_count_lines, dim3((unsigned)nblk), dim3(ING_THREADS), 0, h->stream, text, len, blk.get<uint32_t>());
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, ingest_count_lines, dim3((unsigned)nblk), dim3(ING_THREADS), 0, text, len, blk.get<uint32_t>());
 		{ int rc = exclusive_scan(h, blk.get<uint32_t>(), nblk, bbase.get<uint64_t>()); if (rc) return rc; }
 		HIPCHK(h, hipMemcpy(&n_lines, bbase.get<uint64_t>() + nblk, 8, hipMemcpyDeviceToHost));
 	}
@@ -128,12 +123,11 @@ static int ingest_dev(kmr_handle *h, const uint8_t *text, uint64_t len, uint32_t
 	uint64_t n_kept = 0, total = 0;
 	if (nrec) {
 		HIPCHK(h, lstart.alloc(8 * n_lines)); HIPCHK(h, llen.alloc(4 * n_lines));
-		hipLaunchKernelGGL(ingest_index_lines, dim3((unsigned)nblk), dim3(ING_THREADS), 0, h->stream, text, len, bbase.get<uint64_t>(), lstart.get<uint64_t>());
-		hipLaunchKernelGGL(ingest_line_lengths, dim3(grid_for(n_lines)), dim3(256), 0, h->stream, text, len, lstart.get<uint64_t>(), n_lines, llen.get<uint32_t>(), derr.get<uint32_t>(), false);
+		LAUNCH(h, ingest_index_lines, dim3((unsigned)nblk), dim3(ING_THREADS), 0, text, len, bbase.get<uint64_t>(), lstart.get<uint64_t>());
+		LAUNCH(h, ingest_line_lengths, dim3(grid_for(n_lines)), dim3(256), 0, text, len, lstart.get<uint64_t>(), n_lines, llen.get<uint32_t>(), derr.get<uint32_t>(), false);
 		HIPCHK(h, keep.alloc(4 * nrec)); HIPCHK(h, klen.alloc(4 * nrec));
 		HIPCHK(h, kidx.alloc(8 * (nrec + 1))); HIPCHK(h, boff.alloc(8 * (nrec + 1)));
-		hipLaunchKernelGGL(ingest_records, dim3(grid_for(nrec)), dim3(256), 0, h->stream, text, lstart.get<uint64_t>(), llen.get<uint32_t>(), nrec, store_comment, keep.get<uint32_t>(), klen.get<uint32_t>(), derr.get<uint32_t>());
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, ingest_records, dim3(grid_for(nrec)), dim3(256), 0, text, lstart.get<uint64_t>(), llen.get<uint32_t>(), nrec, store_comment, keep.get<uint32_t>(), klen.get<uint32_t>(), derr.get<uint32_t>());
 		{ int rc = exclusive_scan(h, keep.get<uint32_t>(), nrec, kidx.get<uint64_t>()); if (rc) return rc; }
 		{ int rc = exclusive_scan(h, klen.get<uint32_t>(), nrec, boff.get<uint64_t>()); if (rc) return rc; }
 		uint32_t e = 0;
@@ -155,15 +149,13 @@ static int ingest_dev(kmr_handle *h, const uint8_t *text, uint64_t len, uint32_t
 	HIPCHK(h, hipMemcpyAsync(R->offsets.get<uint64_t>() + n_kept, &total, 8, hipMemcpyHostToDevice, h->stream));
 	if (nrec) {
 		/* appendFasta rescales every read from the input base to Read::FASTQ_START_CHAR as it is read (src/ReadSet.cpp:324,336) */
-		hipLaunchKernelGGL(ingest_copy, dim3(grid_for(nrec, 4, 1 << 16)), dim3(256), 0, h->stream, text, len, lstart.get<uint64_t>(), llen.get<uint32_t>(), nrec, keep.get<uint32_t>(), kidx.get<uint64_t>(), boff.get<uint64_t>(),
-		                   (int)start - (int)input_base, start, R->bases.get<uint8_t>(), R->quals.get<uint8_t>(), R->offsets.get<uint64_t>(), R->name_off.get<uint64_t>(), R->name_len.get<uint32_t>(), derr.get<uint32_t>() + 1);
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, ingest_copy, dim3(grid_for(nrec, 4, 1 << 16)), dim3(256), 0, text, len, lstart.get<uint64_t>(), llen.get<uint32_t>(), nrec, keep.get<uint32_t>(), kidx.get<uint64_t>(), boff.get<uint64_t>(),
+		       (int)start - (int)input_base, start, R->bases.get<uint8_t>(), R->quals.get<uint8_t>(), R->offsets.get<uint64_t>(), R->name_off.get<uint64_t>(), R->name_len.get<uint32_t>(), derr.get<uint32_t>() + 1);
 		uint32_t flip = 0;
-		HIPCHK(h, hipMemcpyAsync(&flip, derr.get<uint32_t>() + 1, 4, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
+		HIPCHK(h, fetch(h, &flip, derr.get<uint32_t>() + 1));
 		const uint32_t want = start == 33 ? 64u : 33u;        /* __setFastqStart(the other base), src/ReadSet.h:174-186 */
 		if (flip && want != input_base) {
-			if (total) hipLaunchKernelGGL(ingest_shift_quals, dim3(grid_for(total)), dim3(256), 0, h->stream, R->quals.get<uint8_t>(), total, (int)input_base - (int)want);
-			HIPCHK(h, hipGetLastError());
+			if (total) LAUNCH(h, ingest_shift_quals, dim3(grid_for(total)), dim3(256), 0, R->quals.get<uint8_t>(), total, (int)input_base - (int)want);
 			R->input_base = want;
 		}
 	}
@@ -234,7 +226,7 @@ std::string fasta_why(uint32_t e) {
 /* what the error word at derr holds after the work queued so far: 0, or the call's return code with its message */
 int fasta_check(kmr_handle *h, const uint32_t *derr, const char *what) {
 	uint32_t e = 0;
-	HIPCHK(h, hipMemcpyAsync(&e, derr, 4, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
+	HIPCHK(h, fetch(h, &e, derr));
 	if (e & (FA_ERR_LONG | ING_ERR_LEN)) return fail(h, KMR_ERR_UNSUPPORTED, std::string(what) + ": a line or record of more than 2^32 - 2 bytes (SequenceLengthType)");
 	if (e) return fail(h, KMR_ERR_INVALID_ARG, std::string("malformed ") + what + ":" + fasta_why(e));
 	return 0;
@@ -248,8 +240,7 @@ int fasta_index(kmr_handle *h, const uint8_t *text, uint64_t len, int store_comm
 	X.per_block.take(X.blk, 4 * X.nblk); X.per_block.take(X.bbase, 8 * (X.nblk + 1));
 	if (!is_fasta) { X.per_block.take(X.btok, 4 * X.nblk); X.per_block.take(X.tbase, 8 * (X.nblk + 1)); }
 	{ int rc = X.per_block.reserve(h, bufs[0]); if (rc) return rc; }
-	hipLaunchKernelGGL(ingest_count_lines, dim3((unsigned)X.nblk), dim3(ING_THREADS), 0, h->stream, text, len, X.blk.get<uint32_t>());
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, ingest_count_lines, dim3((unsigned)X.nblk), dim3(ING_THREADS), 0, text, len, X.blk.get<uint32_t>());
 	{ int rc = exclusive_scan(h, X.blk.get<uint32_t>(), X.nblk, X.bbase.get<uint64_t>()); if (rc) return rc; }
 	HIPCHK(h, hipMemcpy(&X.n_lines, X.bbase.get<uint64_t>() + X.nblk, 8, hipMemcpyDeviceToHost));
 	if (!X.n_lines) return fail(h, KMR_ERR_INVALID_ARG, std::string("malformed ") + what + ":" + fasta_why(FA_ERR_LEAD));      /* newlines only */
@@ -258,19 +249,17 @@ int fasta_index(kmr_handle *h, const uint8_t *text, uint64_t len, int store_comm
 	if (is_fasta) { X.per_line.take(X.klen, 4 * nl); X.per_line.take(X.loff, 8 * (nl + 1)); }
 	else { X.per_line.take(X.tline, 8 * (nl + 1)); X.per_line.take(X.lout, 8 * nl); X.per_line.take(X.lread, 4 * nl); }
 	{ int rc = X.per_line.reserve(h, bufs[1]); if (rc) return rc; }
-	hipLaunchKernelGGL(ingest_index_lines, dim3((unsigned)X.nblk), dim3(ING_THREADS), 0, h->stream, text, len, X.bbase.get<uint64_t>(), X.lstart.get<uint64_t>());
-	hipLaunchKernelGGL(ingest_line_lengths, dim3(grid_for(nl)), dim3(256), 0, h->stream, text, len, X.lstart.get<uint64_t>(), nl, X.llen.get<uint32_t>(), derr, true);
-	hipLaunchKernelGGL(fasta_classify, dim3(grid_for(nl)), dim3(256), 0, h->stream, text, X.lstart.get<uint64_t>(), X.llen.get<uint32_t>(), nl, X.ishdr.get<uint32_t>(), derr);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, ingest_index_lines, dim3((unsigned)X.nblk), dim3(ING_THREADS), 0, text, len, X.bbase.get<uint64_t>(), X.lstart.get<uint64_t>());
+	LAUNCH(h, ingest_line_lengths, dim3(grid_for(nl)), dim3(256), 0, text, len, X.lstart.get<uint64_t>(), nl, X.llen.get<uint32_t>(), derr, true);
+	LAUNCH(h, fasta_classify, dim3(grid_for(nl)), dim3(256), 0, text, X.lstart.get<uint64_t>(), X.llen.get<uint32_t>(), nl, X.ishdr.get<uint32_t>(), derr);
 	{ int rc = exclusive_scan(h, X.ishdr.get<uint32_t>(), nl, X.hidx.get<uint64_t>()); if (rc) return rc; }
 	{ int rc = fasta_check(h, derr, what); if (rc) return rc; }
 	HIPCHK(h, hipMemcpy(&X.nrec, X.hidx.get<uint64_t>() + nl, 8, hipMemcpyDeviceToHost));
 	X.per_record.take(X.recline, 8 * X.nrec);
 	if (is_fasta) { X.per_record.take(X.keep, 4 * X.nrec); X.per_record.take(X.kidx, 8 * (X.nrec + 1)); }
 	{ int rc = X.per_record.reserve(h, bufs[2]); if (rc) return rc; }
-	hipLaunchKernelGGL(fasta_headers, dim3(grid_for(nl)), dim3(256), 0, h->stream, text, X.lstart.get<uint64_t>(), X.llen.get<uint32_t>(), X.ishdr.get<uint32_t>(), X.hidx.get<uint64_t>(), nl,
-	                   store_comment, X.recline.get<uint64_t>(), X.keep.get<uint32_t>(), derr);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, fasta_headers, dim3(grid_for(nl)), dim3(256), 0, text, X.lstart.get<uint64_t>(), X.llen.get<uint32_t>(), X.ishdr.get<uint32_t>(), X.hidx.get<uint64_t>(), nl,
+	       store_comment, X.recline.get<uint64_t>(), X.keep.get<uint32_t>(), derr);
 	return 0;
 }
 
@@ -291,8 +280,7 @@ int ingest_fasta_dev(kmr_handle *h, const uint8_t *text, uint64_t len, const uin
 	const uint64_t nl = F.n_lines, nrec = F.nrec;
 	uint64_t n_kept = 0, total = 0;
 	if (nrec) {
-		hipLaunchKernelGGL(fasta_kept_lengths, dim3(grid_for(nl)), dim3(256), 0, h->stream, F.llen.get<uint32_t>(), F.ishdr.get<uint32_t>(), F.hidx.get<uint64_t>(), F.keep.get<uint32_t>(), nl, F.klen.get<uint32_t>());
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, fasta_kept_lengths, dim3(grid_for(nl)), dim3(256), 0, F.llen.get<uint32_t>(), F.ishdr.get<uint32_t>(), F.hidx.get<uint64_t>(), F.keep.get<uint32_t>(), nl, F.klen.get<uint32_t>());
 		{ int rc = exclusive_scan(h, F.keep.get<uint32_t>(), nrec, F.kidx.get<uint64_t>()); if (rc) return rc; }
 		{ int rc = exclusive_scan(h, F.klen.get<uint32_t>(), nl, F.loff.get<uint64_t>()); if (rc) return rc; }
 		{ int rc = fasta_check(h, ferr, "FASTA"); if (rc) return rc; }      /* the names */
@@ -304,15 +292,13 @@ int ingest_fasta_dev(kmr_handle *h, const uint8_t *text, uint64_t len, const uin
 	HIPCHK(h, hipMemsetAsync(R->bases.get<uint8_t>() + total, 0, 64, h->stream)); HIPCHK(h, hipMemsetAsync(R->quals.get<uint8_t>() + total, 0, 64, h->stream));
 	HIPCHK(h, hipMemcpyAsync(R->offsets.get<uint64_t>() + n_kept, &total, 8, hipMemcpyHostToDevice, h->stream));
 	if (nrec) {
-		hipLaunchKernelGGL(fasta_records, dim3(grid_for(nrec)), dim3(256), 0, h->stream, F.lstart.get<uint64_t>(), F.llen.get<uint32_t>(), F.recline.get<uint64_t>(), F.keep.get<uint32_t>(), F.kidx.get<uint64_t>(),
-		                   F.loff.get<uint64_t>(), nrec, nl, R->offsets.get<uint64_t>(), R->name_off.get<uint64_t>(), R->name_len.get<uint32_t>(), ferr);
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, fasta_records, dim3(grid_for(nrec)), dim3(256), 0, F.lstart.get<uint64_t>(), F.llen.get<uint32_t>(), F.recline.get<uint64_t>(), F.keep.get<uint32_t>(), F.kidx.get<uint64_t>(),
+		       F.loff.get<uint64_t>(), nrec, nl, R->offsets.get<uint64_t>(), R->name_off.get<uint64_t>(), R->name_len.get<uint32_t>(), ferr);
 	}
 	if (total) {
 		const uint64_t nb = (total + (uint64_t)ING_THREADS * ING_BYTES - 1) / ((uint64_t)ING_THREADS * ING_BYTES);
 		if (nb > 0x7fffffffull) return fail(h, KMR_ERR_INVALID_ARG, "FASTA text too large for one call");
-		hipLaunchKernelGGL(fasta_copy, dim3((unsigned)nb), dim3(ING_THREADS), 0, h->stream, text, len, F.lstart.get<uint64_t>(), F.loff.get<uint64_t>(), nl, total, R->bases.get<uint8_t>());
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, fasta_copy, dim3((unsigned)nb), dim3(ING_THREADS), 0, text, len, F.lstart.get<uint64_t>(), F.loff.get<uint64_t>(), nl, total, R->bases.get<uint8_t>());
 	}
 	if (!with_qual) {
 		if (total) HIPCHK(h, hipMemsetAsync(R->quals.get<uint8_t>(), 127, total, h->stream));      /* Read::REF_QUAL, src/ReadFileReader.h:892,901 */
@@ -320,29 +306,26 @@ int ingest_fasta_dev(kmr_handle *h, const uint8_t *text, uint64_t len, const uin
 		const uint64_t ql = Q.n_lines, n_window = std::min<uint64_t>(n_kept, ING_VALIDATE_READS - 1);
 		DevBuf inrange;
 		HIPCHK(h, inrange.alloc(4 * std::max<uint64_t>(1, n_window))); HIPCHK(h, hipMemsetAsync(inrange.get<uint32_t>(), 0, 4 * std::max<uint64_t>(1, n_window), h->stream));
-		auto tokens = [&](auto mode) {
-			hipLaunchKernelGGL(fasta_qual_tokens<decltype(mode)::value>, dim3((unsigned)Q.nblk), dim3(ING_THREADS), 0, h->stream, qtext, qlen, Q.bbase.get<uint64_t>(), Q.ishdr.get<uint32_t>(), ql,
-			                   Q.btok.get<uint32_t>(), Q.tbase.get<uint64_t>(), Q.tline.get<uint64_t>(), Q.lout.get<uint64_t>(), Q.lread.get<uint32_t>(), start, R->quals.get<uint8_t>(), inrange.get<uint32_t>(), qerr);
+		auto tokens = [&](auto mode) -> int {
+			LAUNCH(h, fasta_qual_tokens<decltype(mode)::value>, dim3((unsigned)Q.nblk), dim3(ING_THREADS), 0, qtext, qlen, Q.bbase.get<uint64_t>(), Q.ishdr.get<uint32_t>(), ql,
+			       Q.btok.get<uint32_t>(), Q.tbase.get<uint64_t>(), Q.tline.get<uint64_t>(), Q.lout.get<uint64_t>(), Q.lread.get<uint32_t>(), start, R->quals.get<uint8_t>(), inrange.get<uint32_t>(), qerr);
+			return 0;
 		};
-		tokens(int_c<0>());
-		HIPCHK(h, hipGetLastError());
+		{ int rc = tokens(int_c<0>()); if (rc) return rc; }
 		{ int rc = exclusive_scan(h, Q.btok.get<uint32_t>(), Q.nblk, Q.tbase.get<uint64_t>()); if (rc) return rc; }
-		tokens(int_c<1>());
-		hipLaunchKernelGGL(fasta_qual_lines, dim3(grid_for(ql)), dim3(256), 0, h->stream, qtext, Q.lstart.get<uint64_t>(), Q.llen.get<uint32_t>(), Q.ishdr.get<uint32_t>(), Q.hidx.get<uint64_t>(), Q.recline.get<uint64_t>(), ql,
-		                   Q.tline.get<uint64_t>(), text, F.lstart.get<uint64_t>(), F.llen.get<uint32_t>(), F.recline.get<uint64_t>(), F.keep.get<uint32_t>(), F.kidx.get<uint64_t>(), R->offsets.get<uint64_t>(), nrec,
-		                   store_comment, Q.lout.get<uint64_t>(), Q.lread.get<uint32_t>(), qerr);
-		HIPCHK(h, hipGetLastError());
+		{ int rc = tokens(int_c<1>()); if (rc) return rc; }
+		LAUNCH(h, fasta_qual_lines, dim3(grid_for(ql)), dim3(256), 0, qtext, Q.lstart.get<uint64_t>(), Q.llen.get<uint32_t>(), Q.ishdr.get<uint32_t>(), Q.hidx.get<uint64_t>(), Q.recline.get<uint64_t>(), ql,
+		       Q.tline.get<uint64_t>(), text, F.lstart.get<uint64_t>(), F.llen.get<uint32_t>(), F.recline.get<uint64_t>(), F.keep.get<uint32_t>(), F.kidx.get<uint64_t>(), R->offsets.get<uint64_t>(), nrec,
+		       store_comment, Q.lout.get<uint64_t>(), Q.lread.get<uint32_t>(), qerr);
 		/* every kept record has as many numbers as bases before a single one is written */
 		{ int rc = fasta_check(h, qerr, "QUAL"); if (rc) return rc; }
-		tokens(int_c<2>());
-		if (n_window) hipLaunchKernelGGL(fasta_qual_flip, dim3(grid_for(n_window)), dim3(256), 0, h->stream, inrange.get<uint32_t>(), n_window, flip);
-		HIPCHK(h, hipGetLastError());
+		{ int rc = tokens(int_c<2>()); if (rc) return rc; }
+		if (n_window) LAUNCH(h, fasta_qual_flip, dim3(grid_for(n_window)), dim3(256), 0, inrange.get<uint32_t>(), n_window, flip);
 		uint32_t f = 0;
-		HIPCHK(h, hipMemcpyAsync(&f, flip, 4, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
+		HIPCHK(h, fetch(h, &f, flip));
 		if (f) {      /* __setFastqStart(the other base), src/ReadSet.h:174-186, with the input base equal to the start character */
 			const uint32_t want = start == 33 ? 64u : 33u;
-			if (total) hipLaunchKernelGGL(ingest_shift_quals, dim3(grid_for(total)), dim3(256), 0, h->stream, R->quals.get<uint8_t>(), total, (int)start - (int)want);
-			HIPCHK(h, hipGetLastError());
+			if (total) LAUNCH(h, ingest_shift_quals, dim3(grid_for(total)), dim3(256), 0, R->quals.get<uint8_t>(), total, (int)start - (int)want);
 			R->input_base = want;
 		}
 	}
@@ -440,8 +423,7 @@ int kmr_reads_circularize(kmr_handle *h, const kmr_reads *in, uint32_t extra_len
 	if (n) {
 		HIPCHK(h, hipMemcpyAsync(r->name_off.get(), in->name_off.get(), 8 * n, hipMemcpyDeviceToDevice, h->stream));
 		HIPCHK(h, hipMemcpyAsync(r->name_len.get(), in->name_len.get(), 4 * n, hipMemcpyDeviceToDevice, h->stream));
-		hipLaunchKernelGGL(circularize_lengths_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, in->offsets.get<uint64_t>(), n, extra_length, len, err);
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, circularize_lengths_kernel, dim3(grid_for(n)), dim3(256), 0, in->offsets.get<uint64_t>(), n, extra_length, len, err);
 		int rc = exclusive_scan(h, len, n, off); if (rc) return rc;
 		HIPCHK(h, hipMemcpy(&r->total, off + n, 8, hipMemcpyDeviceToHost));
 		HIPCHK(h, hipMemcpy(&herr, err, 4, hipMemcpyDeviceToHost));
@@ -451,9 +433,8 @@ int kmr_reads_circularize(kmr_handle *h, const kmr_reads *in, uint32_t extra_len
 	HIPCHK(h, alloc_n(r->bases, &cb, r->total + 64)); HIPCHK(h, alloc_n(r->quals, &cq, r->total + 64));
 	HIPCHK(h, hipMemsetAsync(cb + r->total, 0, 64, h->stream)); HIPCHK(h, hipMemsetAsync(cq + r->total, 0, 64, h->stream));
 	if (r->total) {
-		hipLaunchKernelGGL(circularize_copy_kernel, dim3((unsigned)std::min<uint64_t>((n + 3) / 4, (uint64_t)num_cus(h) * 32)), dim3(256), 0, h->stream,
-		                   in->bases.get<uint8_t>(), in->quals.get<uint8_t>(), in->offsets.get<uint64_t>(), n, (const uint64_t *)off, cb, cq);
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, circularize_copy_kernel, dim3((unsigned)std::min<uint64_t>((n + 3) / 4, (uint64_t)num_cus(h) * 32)), dim3(256), 0,
+		       in->bases.get<uint8_t>(), in->quals.get<uint8_t>(), in->offsets.get<uint64_t>(), n, (const uint64_t *)off, cb, cq);
 	}
 	HIPCHK(h, hipStreamSynchronize(h->stream));
 	tmp.done();
@@ -598,40 +579,32 @@ int kmr_match_finish(kmr_match *m) {
 		HIPCHK(h, tmp.take(&flag, 2 * nh)); HIPCHK(h, tmp.take(&scan, 2 * (nh + 1))); HIPCHK(h, tmp.take(&bound, nc + 1)); HIPCHK(h, tmp.take(&bound2, nc + 1));
 		int rc = sort_reserve(h, tmp.sort, nh, "kmr_match_finish"); if (rc) return rc;
 		const dim3 hgrid(grid_for(nh)), cgrid(grid_for(nc + 1));
-		hipLaunchKernelGGL(match_iota_kernel, hgrid, block, 0, h->stream, p0, nh);
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, match_iota_kernel, hgrid, block, 0, p0, nh);
 		rc = sort_pairs(h, tmp.sort, m->hit_key.get<unsigned long long>(), k1, p0, p1, nh, "kmr_match_finish"); if (rc) return rc;
-		hipLaunchKernelGGL(match_heads_kernel, hgrid, block, 0, h->stream, (const unsigned long long *)k1, nh, flag);
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, match_heads_kernel, hgrid, block, 0, (const unsigned long long *)k1, nh, flag);
 		rc = exclusive_scan_queue(h, flag, nh, scan); if (rc) return rc;
-		hipLaunchKernelGGL(match_compact_kernel, hgrid, block, 0, h->stream, (const unsigned long long *)k1, (const uint32_t *)p1, m->hit_mate.get<unsigned long long>(), (const uint32_t *)flag,
-		                   (const uint64_t *)scan, nh, ukey, umate);
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, match_compact_kernel, hgrid, block, 0, (const unsigned long long *)k1, (const uint32_t *)p1, m->hit_mate.get<unsigned long long>(), (const uint32_t *)flag,
+		       (const uint64_t *)scan, nh, ukey, umate);
 		uint64_t nu = 0;
-		HIPCHK(h, hipMemcpyAsync(&nu, scan + nh, 8, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(h, hipStreamSynchronize(h->stream));
+		HIPCHK(h, fetch(h, &nu, scan + nh));
 		/* 2: the sets' sizes, the sampling, the mates of the reads that stay */
 		const dim3 ugrid(grid_for(nu));
 		uint32_t *keep = flag, *cnt = flag + nh; uint64_t *kscan = scan, *escan = scan + (nh + 1);
-		hipLaunchKernelGGL(match_bounds_kernel, cgrid, block, 0, h->stream, (const unsigned long long *)ukey, nu, nc, bound);
-		hipLaunchKernelGGL(match_sample_kernel, ugrid, block, 0, h->stream, (const unsigned long long *)ukey, (const unsigned long long *)umate, nu, (const uint64_t *)bound, m->cfg.max_read_matches,
-		                   m->cfg.include_mate, m->cfg.seed, keep, cnt);
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, match_bounds_kernel, cgrid, block, 0, (const unsigned long long *)ukey, nu, nc, bound);
+		LAUNCH(h, match_sample_kernel, ugrid, block, 0, (const unsigned long long *)ukey, (const unsigned long long *)umate, nu, (const uint64_t *)bound, m->cfg.max_read_matches,
+		       m->cfg.include_mate, m->cfg.seed, keep, cnt);
 		rc = exclusive_scan_queue(h, keep, nu, kscan); if (rc) return rc;
 		rc = exclusive_scan_queue(h, cnt, nu, escan); if (rc) return rc;
-		hipLaunchKernelGGL(match_sizes_kernel, cgrid, block, 0, h->stream, (const uint64_t *)bound, (const uint64_t *)kscan, nc, before, after);
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, match_sizes_kernel, cgrid, block, 0, (const uint64_t *)bound, (const uint64_t *)kscan, nc, before, after);
 		uint64_t ne = 0;
-		HIPCHK(h, hipMemcpyAsync(&ne, escan + nu, 8, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(h, hipStreamSynchronize(h->stream));
+		HIPCHK(h, fetch(h, &ne, escan + nu));
 		if (ne >= 0xffffffffull) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_match_finish: 2^32 - 1 reads and mates or more");
 		if (ne) {
 			unsigned long long *e0, *e1; uint32_t *q0, *q1, *fflag; uint64_t *fscan;
 			HIPCHK(h, tmp.take(&e0, ne)); HIPCHK(h, tmp.take(&e1, ne)); HIPCHK(h, tmp.take(&q0, ne)); HIPCHK(h, tmp.take(&q1, ne)); HIPCHK(h, tmp.take(&fflag, ne)); HIPCHK(h, tmp.take(&fscan, ne + 1));
 			const dim3 egrid(grid_for(ne));
-			hipLaunchKernelGGL(match_emit_kernel, ugrid, block, 0, h->stream, (const unsigned long long *)ukey, (const unsigned long long *)umate, nu, (const uint32_t *)cnt, (const uint64_t *)escan, e0);
-			hipLaunchKernelGGL(match_iota_kernel, egrid, block, 0, h->stream, q0, ne);
-			HIPCHK(h, hipGetLastError());
+			LAUNCH(h, match_emit_kernel, ugrid, block, 0, (const unsigned long long *)ukey, (const unsigned long long *)umate, nu, (const uint32_t *)cnt, (const uint64_t *)escan, e0);
+			LAUNCH(h, match_iota_kernel, egrid, block, 0, q0, ne);
 			/* 3: sorted and made unique again, without the discarded reads */
 			rc = sort_reserve(h, tmp.sort, ne, "kmr_match_finish"); if (rc) return rc;
 			rc = sort_pairs(h, tmp.sort, e0, e1, q0, q1, ne, "kmr_match_finish"); if (rc) return rc;
@@ -644,22 +617,18 @@ int kmr_match_finish(kmr_match *m) {
 			rc = to_device(h, tmp, (const uint64_t *)bn.data(), (uint64_t)nb, &dbn); if (rc) return rc;
 			rc = to_device(h, tmp, (const uint8_t *const *)bp.data(), (uint64_t)nb, &dbp); if (rc) return rc;
 			B.first = dbf; B.n = dbn; B.flags = dbp;
-			hipLaunchKernelGGL(match_final_kernel, egrid, block, 0, h->stream, (const unsigned long long *)e1, ne, B, fflag);
-			HIPCHK(h, hipGetLastError());
+			LAUNCH(h, match_final_kernel, egrid, block, 0, (const unsigned long long *)e1, ne, B, fflag);
 			rc = exclusive_scan_queue(h, fflag, ne, fscan); if (rc) return rc;
-			HIPCHK(h, hipMemcpyAsync(&n_out, fscan + ne, 8, hipMemcpyDeviceToHost, h->stream));
-			HIPCHK(h, hipStreamSynchronize(h->stream));      /* (bf, bn, bp have been read) */
+			HIPCHK(h, fetch(h, &n_out, fscan + ne));      /* (bf, bn, bp have been read) */
 			uint64_t *ids;
 			HIPCHK(h, alloc_n(m->read_ids, &ids, std::max<uint64_t>(n_out, 1)));
-			hipLaunchKernelGGL(match_bounds_kernel, cgrid, block, 0, h->stream, (const unsigned long long *)e1, ne, nc, bound2);
-			hipLaunchKernelGGL(match_output_kernel, egrid, block, 0, h->stream, (const unsigned long long *)e1, ne, (const uint32_t *)fflag, (const uint64_t *)fscan, ids);
-			hipLaunchKernelGGL(match_offsets_kernel, cgrid, block, 0, h->stream, (const uint64_t *)bound2, (const uint64_t *)fscan, nc, offsets);
-			HIPCHK(h, hipGetLastError());
+			LAUNCH(h, match_bounds_kernel, cgrid, block, 0, (const unsigned long long *)e1, ne, nc, bound2);
+			LAUNCH(h, match_output_kernel, egrid, block, 0, (const unsigned long long *)e1, ne, (const uint32_t *)fflag, (const uint64_t *)fscan, ids);
+			LAUNCH(h, match_offsets_kernel, cgrid, block, 0, (const uint64_t *)bound2, (const uint64_t *)fscan, nc, offsets);
 		}
 		/* the sets that were sampled: the sizes are small, the host counts them */
 		std::vector<uint64_t> hb(nc);
-		HIPCHK(h, hipMemcpyAsync(hb.data(), before, 8 * nc, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(h, hipStreamSynchronize(h->stream));
+		HIPCHK(h, fetch(h, hb.data(), before, nc));
 		const float maxHits = (float)(2.0 * (double)m->cfg.max_read_matches);
 		if (m->cfg.max_read_matches) for (uint64_t c = 0; c < nc; c++) if ((float)(long long)hb[c] > maxHits) m->n_sampled++;
 	}
@@ -871,12 +840,11 @@ template <class T> int tnf_finish_t(kmr_handle *h, kmr_tnf *t) {
 	double *l2; unsigned long long *bad;
 	HIPCHK(h, tmp.take(&l2, t->n)); HIPCHK(h, tmp.take(&bad, (size_t)1));
 	HIPCHK(h, hipMemsetAsync(bad, 0, 8, h->stream));
-	hipLaunchKernelGGL(tnf_len2_kernel<T>, dim3(grid_for(t->n, 64)), dim3(64), 0, h->stream, t->counts.get<T>(), t->n, t->D, l2, bad);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, tnf_len2_kernel<T>, dim3(grid_for(t->n, 64)), dim3(64), 0, t->counts.get<T>(), t->n, t->D, l2, bad);
 	std::vector<double> hl(t->n); unsigned long long hbad = 0;
-	HIPCHK(h, hipMemcpyAsync(hl.data(), l2, 8 * t->n, hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(h, hipMemcpyAsync(&hbad, bad, 8, hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(h, hipStreamSynchronize(h->stream));
+	HIPCHK(h, fetch_queue(h, hl.data(), l2, t->n));
+	HIPCHK(h, fetch_queue(h, &hbad, bad));
+	HIPCHK(h, stream_wait(h));
 	tmp.done();
 	t->inexact = hbad;
 	std::vector<float> len(t->n);
@@ -917,13 +885,12 @@ int tnf_count(kmr_handle *h, const char *who, const kmr_reads *r, const std::vec
 		uint32_t *nwin, *werr;
 		HIPCHK(h, tmp.take(&nwin, n)); HIPCHK(h, tmp.take(&werr, (size_t)1)); HIPCHK(h, tmp.take(&woff, n + 1));
 		HIPCHK(h, hipMemsetAsync(werr, 0, 4, h->stream));
-		hipLaunchKernelGGL(tnf_win_count_kernel, dim3(grid_for(n)), block, 0, h->stream, offsets, n, window, step, nwin, werr);
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, tnf_win_count_kernel, dim3(grid_for(n)), block, 0, offsets, n, window, step, nwin, werr);
 		rc = exclusive_scan_queue(h, nwin, n, woff); if (rc) return rc;
 		uint32_t herr = 0;
-		HIPCHK(h, hipMemcpyAsync(&nv, woff + n, 8, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(h, hipMemcpyAsync(&herr, werr, 4, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(h, hipStreamSynchronize(h->stream));
+		HIPCHK(h, fetch_queue(h, &nv, woff + n));
+		HIPCHK(h, fetch_queue(h, &herr, werr));
+		HIPCHK(h, stream_wait(h));
 		if (herr) return fail(h, KMR_ERR_UNSUPPORTED, std::string(who) + ": a sequence of 2^32 windows or more");
 		if (nv == 0) { tmp.done(); return KMR_OK; }
 	}
@@ -932,17 +899,14 @@ int tnf_count(kmr_handle *h, const char *who, const kmr_reads *r, const std::vec
 	HIPCHK(h, tmp.take(&vslot, nv)); HIPCHK(h, tmp.take(&vnk, nv)); HIPCHK(h, tmp.take(&pcnt, nv)); HIPCHK(h, tmp.take(&poff, nv + 1));
 	HIPCHK(h, counts.alloc(std::max<size_t>(4 * nv * D, 256))); HIPCHK(h, origin.alloc(24 * nv));
 	HIPCHK(h, hipMemsetAsync(counts.get(), 0, 4 * nv * D, h->stream));
-	if (windows) hipLaunchKernelGGL(tnf_win_desc_kernel, dim3(grid_for(nv)), block, 0, h->stream, koff, (const uint64_t *)woff, n, nv, window, step, k, vslot, vnk, origin.get<uint64_t>());
-	else hipLaunchKernelGGL(tnf_reads_desc_kernel, dim3(grid_for(nv)), block, 0, h->stream, offsets, koff, n, vslot, vnk, origin.get<uint64_t>());
-	HIPCHK(h, hipGetLastError());
+	if (windows) LAUNCH(h, tnf_win_desc_kernel, dim3(grid_for(nv)), block, 0, koff, (const uint64_t *)woff, n, nv, window, step, k, vslot, vnk, origin.get<uint64_t>());
+	else LAUNCH(h, tnf_reads_desc_kernel, dim3(grid_for(nv)), block, 0, offsets, koff, n, vslot, vnk, origin.get<uint64_t>());
 	uint32_t piece = h->tune.tnf_piece_bases ? h->tune.tnf_piece_bases : TNF_PIECE_BASES;
 	piece = piece > k - 1 ? piece - (k - 1) : 1;      /* pieces of bases overlap by k - 1: as many k-mers begin in one */
-	hipLaunchKernelGGL(tnf_piece_count_kernel, dim3(grid_for(nv)), block, 0, h->stream, (const uint32_t *)vnk, nv, piece, pcnt);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, tnf_piece_count_kernel, dim3(grid_for(nv)), block, 0, (const uint32_t *)vnk, nv, piece, pcnt);
 	rc = exclusive_scan_queue(h, pcnt, nv, poff); if (rc) return rc;
 	uint64_t n_pieces = 0;
-	HIPCHK(h, hipMemcpyAsync(&n_pieces, poff + nv, 8, hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(h, hipStreamSynchronize(h->stream));
+	HIPCHK(h, fetch(h, &n_pieces, poff + nv));
 	if (n_pieces && slots) {
 		const std::vector<uint16_t> codes = tnf_columns(k, h->cfg.hash_kind);
 		std::vector<uint16_t> col(1u << (2 * k), (uint16_t)TNF_NO_COLUMN);
@@ -954,9 +918,8 @@ int tnf_count(kmr_handle *h, const char *who, const kmr_reads *r, const std::vec
 		blocks = (n_pieces + per_wave * TNF_WAVES - 1) / (per_wave * TNF_WAVES);
 		const size_t smem = (size_t)TNF_WAVES * 4 << (2 * k);
 		HIPCHK(h, hipFuncSetAttribute((const void *)tnf_hist_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)TNF_WAVES * 4 << (2 * TNF_MAX_K))));
-		hipLaunchKernelGGL(tnf_hist_kernel, dim3((unsigned)blocks), dim3(TNF_WAVES * 64), smem, h->stream, stage, (const uint64_t *)vslot, (const uint32_t *)vnk, (const uint64_t *)poff, nv, n_pieces,
-		                   per_wave, piece, k, (const uint16_t *)dcol, D, counts.get<uint32_t>());
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, tnf_hist_kernel, dim3((unsigned)blocks), dim3(TNF_WAVES * 64), smem, stage, (const uint64_t *)vslot, (const uint32_t *)vnk, (const uint64_t *)poff, nv, n_pieces,
+		       per_wave, piece, k, (const uint16_t *)dcol, D, counts.get<uint32_t>());
 		HIPCHK(h, hipStreamSynchronize(h->stream));      /* col leaves with this scope */
 	}
 	if (!windows) {
@@ -969,21 +932,17 @@ int tnf_count(kmr_handle *h, const char *who, const kmr_reads *r, const std::vec
 	HIPCHK(h, tmp.take(&sums, nv)); HIPCHK(h, tmp.take(&keep, nv)); HIPCHK(h, tmp.take(&kpos, nv + 1));
 	HIPCHK(h, tmp.take(&dstarts, starts.size())); HIPCHK(h, tmp.take(&dbounds, starts.size()));
 	HIPCHK(h, hipMemcpyAsync(dstarts, starts.data(), 8 * starts.size(), hipMemcpyHostToDevice, h->stream));
-	hipLaunchKernelGGL(tnf_rowsum_kernel, dim3(grid_for(nv * 64)), block, 0, h->stream, counts.get<uint32_t>(), nv, D, sums);
-	hipLaunchKernelGGL(tnf_keep_kernel, dim3(grid_for(nv)), block, 0, h->stream, (const unsigned long long *)sums, nv, (long long)min_count, keep);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, tnf_rowsum_kernel, dim3(grid_for(nv * 64)), block, 0, counts.get<uint32_t>(), nv, D, sums);
+	LAUNCH(h, tnf_keep_kernel, dim3(grid_for(nv)), block, 0, (const unsigned long long *)sums, nv, (long long)min_count, keep);
 	rc = exclusive_scan_queue(h, keep, nv, kpos); if (rc) return rc;
-	hipLaunchKernelGGL(tnf_bounds_kernel, dim3(1), block, 0, h->stream, (const uint64_t *)dstarts, n_groups, (const uint64_t *)woff, (const uint64_t *)kpos, dbounds);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, tnf_bounds_kernel, dim3(1), block, 0, (const uint64_t *)dstarts, n_groups, (const uint64_t *)woff, (const uint64_t *)kpos, dbounds);
 	std::vector<uint64_t> hb(starts.size());
-	HIPCHK(h, hipMemcpyAsync(hb.data(), dbounds, 8 * hb.size(), hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(h, hipStreamSynchronize(h->stream));
+	HIPCHK(h, fetch(h, hb.data(), dbounds, hb.size()));
 	const uint64_t kept = hb[n_groups];
 	if (kept) {
 		HIPCHK(h, t->counts.alloc(std::max<size_t>(4 * kept * D, 256))); HIPCHK(h, t->origin.alloc(24 * kept));
-		hipLaunchKernelGGL(tnf_compact_kernel, dim3(grid_for(nv * (D + 3))), block, 0, h->stream, counts.get<uint32_t>(), origin.get<uint64_t>(), (const uint32_t *)keep, (const uint64_t *)kpos, nv, D,
-		                   t->counts.get<uint32_t>(), t->origin.get<uint64_t>());
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, tnf_compact_kernel, dim3(grid_for(nv * (D + 3))), block, 0, counts.get<uint32_t>(), origin.get<uint64_t>(), (const uint32_t *)keep, (const uint64_t *)kpos, nv, D,
+		       t->counts.get<uint32_t>(), t->origin.get<uint64_t>());
 		HIPCHK(h, hipStreamSynchronize(h->stream));
 	}
 	t->n = kept; t->bounds = hb;
@@ -1022,8 +981,7 @@ int tnf_group_sums(kmr_handle *h, const kmr_tnf *in, kmr_tnf *t) {
 		Scratch tmp(h);
 		uint64_t *db; HIPCHK(h, tmp.take(&db, (size_t)G + 1));
 		HIPCHK(h, hipMemcpyAsync(db, in->bounds.data(), 8ull * (G + 1), hipMemcpyHostToDevice, h->stream));
-		hipLaunchKernelGGL(tnf_group_sum_kernel, dim3((unsigned)((most + 255) / 256), G), dim3(256), 0, h->stream, in->counts.get<uint32_t>(), (const uint64_t *)db, D, t->counts.get<unsigned long long>());
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, tnf_group_sum_kernel, dim3((unsigned)((most + 255) / 256), G), dim3(256), 0, in->counts.get<uint32_t>(), (const uint64_t *)db, D, t->counts.get<unsigned long long>());
 		HIPCHK(h, hipStreamSynchronize(h->stream));
 		tmp.done();
 	}
@@ -1036,17 +994,15 @@ template <class T> int tnf_prepare_t(kmr_handle *h, const kmr_tnf *t, int formul
 	if (formula == KMR_TNF_EUCLIDEAN) {
 		if (t->qt) return KMR_OK;
 		DevBuf q; HIPCHK(h, q.alloc(8 * n * D));
-		hipLaunchKernelGGL(tnf_quot_kernel<T>, dim3(grid_for(n * D)), dim3(256), 0, h->stream, t->counts.get<T>(), t->len.get<float>(), n, D, q.get<double>());
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, tnf_quot_kernel<T>, dim3(grid_for(n * D)), dim3(256), 0, t->counts.get<T>(), t->len.get<float>(), n, D, q.get<double>());
 		HIPCHK(h, hipStreamSynchronize(h->stream));
 		t->qt = std::move(q);
 		return KMR_OK;
 	}
 	if (t->xt) return KMR_OK;
 	DevBuf x, s; HIPCHK(h, x.alloc(4 * n * D)); HIPCHK(h, s.alloc(4 * n));
-	hipLaunchKernelGGL(tnf_rank_kernel<T>, dim3((unsigned)std::min<uint64_t>(n, (uint64_t)num_cus(h) * 16)), dim3(256), 4 * D, h->stream, t->counts.get<T>(), n, D, x.get<float>());
-	hipLaunchKernelGGL(tnf_x2_kernel, dim3(grid_for(n, 64)), dim3(64), 0, h->stream, x.get<float>(), n, D, s.get<float>());
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, tnf_rank_kernel<T>, dim3((unsigned)std::min<uint64_t>(n, (uint64_t)num_cus(h) * 16)), dim3(256), 4 * D, t->counts.get<T>(), n, D, x.get<float>());
+	LAUNCH(h, tnf_x2_kernel, dim3(grid_for(n, 64)), dim3(64), 0, x.get<float>(), n, D, s.get<float>());
 	HIPCHK(h, hipStreamSynchronize(h->stream));
 	t->xt = std::move(x); t->x2 = std::move(s);
 	return KMR_OK;
@@ -1078,9 +1034,8 @@ int tnf_pairs(kmr_handle *h, const kmr_tnf *a, const kmr_tnf *b, int formula, Tn
 	HIPCHK(h, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
 	const TnfSide sa = tnf_side(a, formula), sb = tnf_side(b, formula);
 	const dim3 grid((unsigned)blocks), block(TNF_BLOCK);
-	if (sp) { if (hist) hipLaunchKernelGGL((tnf_pairs_kernel<true, true>), grid, block, smem, h->stream, sa, sb, P); else hipLaunchKernelGGL((tnf_pairs_kernel<true, false>), grid, block, smem, h->stream, sa, sb, P); }
-	else { if (hist) hipLaunchKernelGGL((tnf_pairs_kernel<false, true>), grid, block, smem, h->stream, sa, sb, P); else hipLaunchKernelGGL((tnf_pairs_kernel<false, false>), grid, block, smem, h->stream, sa, sb, P); }
-	HIPCHK(h, hipGetLastError());
+	if (sp) { if (hist) LAUNCH(h, (tnf_pairs_kernel<true, true>), grid, block, smem, sa, sb, P); else LAUNCH(h, (tnf_pairs_kernel<true, false>), grid, block, smem, sa, sb, P); }
+	else { if (hist) LAUNCH(h, (tnf_pairs_kernel<false, true>), grid, block, smem, sa, sb, P); else LAUNCH(h, (tnf_pairs_kernel<false, false>), grid, block, smem, sa, sb, P); }
 	return KMR_OK;
 }
 
@@ -1308,9 +1263,8 @@ int art_upload(kmr_handle *h, kmr_artifact_filter *f) {
 	HIPCHK(h, tmp.take(&dk, f->n_keys)); HIPCHK(h, tmp.take(&dv, f->n_keys));
 	if (f->n_keys) { HIPCHK(h, hipMemcpyAsync(dk, f->keys.data(), 8 * f->n_keys, hipMemcpyHostToDevice, h->stream)); HIPCHK(h, hipMemcpyAsync(dv, f->vals.data(), 4 * f->n_keys, hipMemcpyHostToDevice, h->stream)); }
 	ArtifactTable t{f->d_keys.get<uint64_t>(), f->d_vals.get<uint32_t>(), nullptr, f->log2cap, f->d_bits.get<uint32_t>()};
-	hipLaunchKernelGGL(artifact_fill, dim3(1024), dim3(256), 0, h->stream, f->d_keys.get<uint64_t>(), (uint32_t *)nullptr, cap);
-	if (f->n_keys) hipLaunchKernelGGL(artifact_insert, dim3((unsigned)std::min<uint64_t>((f->n_keys + 255) / 256, 4096)), dim3(256), 0, h->stream, t, dk, dv, f->n_keys);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, artifact_fill, dim3(1024), dim3(256), 0, f->d_keys.get<uint64_t>(), (uint32_t *)nullptr, cap);
+	if (f->n_keys) LAUNCH(h, artifact_insert, dim3((unsigned)std::min<uint64_t>((f->n_keys + 255) / 256, 4096)), dim3(256), 0, t, dk, dv, f->n_keys);
 	HIPCHK(h, hipStreamSynchronize(h->stream));
 	tmp.done();
 	return KMR_OK;
@@ -1352,18 +1306,15 @@ int art_build_round(kmr_handle *h, kmr_artifact_filter *f) {
 	HIPCHK(h, hipMemcpyAsync(dv, sv.data(), 4 * n, hipMemcpyHostToDevice, h->stream));
 	HIPCHK(h, hipMemsetAsync(cnt, 0, 8, h->stream));
 	ArtifactTable t{tk, tv, tr, log2cap, nullptr};
-	hipLaunchKernelGGL(artifact_fill, dim3(2048), dim3(256), 0, h->stream, tk, tr, cap);
-	hipLaunchKernelGGL(artifact_insert, dim3((unsigned)std::min<uint64_t>((n + 255) / 256, 4096)), dim3(256), 0, h->stream, t, dk, dv, n);
-	hipLaunchKernelGGL(artifact_neighbours, dim3((unsigned)std::min<uint64_t>((n * L + 255) / 256, 1u << 20)), dim3(256), 0, h->stream, t, dk, n, L);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, artifact_fill, dim3(2048), dim3(256), 0, tk, tr, cap);
+	LAUNCH(h, artifact_insert, dim3((unsigned)std::min<uint64_t>((n + 255) / 256, 4096)), dim3(256), 0, t, dk, dv, n);
+	LAUNCH(h, artifact_neighbours, dim3((unsigned)std::min<uint64_t>((n * L + 255) / 256, 1u << 20)), dim3(256), 0, t, dk, n, L);
 	HIPCHK(h, hipStreamSynchronize(h->stream));
 	/* the table is sparse (<= 50 % by construction, a few % in practice): count first, then compact */
 	HIPCHK(h, tmp.take(&ok, worst)); HIPCHK(h, tmp.take(&ov, worst));
-	hipLaunchKernelGGL(artifact_compact, dim3(2048), dim3(256), 0, h->stream, t, dv, ok, ov, cnt);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, artifact_compact, dim3(2048), dim3(256), 0, t, dv, ok, ov, cnt);
 	unsigned long long m = 0;
-	HIPCHK(h, hipMemcpyAsync(&m, cnt, 8, hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(h, hipStreamSynchronize(h->stream));
+	HIPCHK(h, fetch(h, &m, cnt));
 	std::vector<uint64_t> nk(m); std::vector<uint32_t> nv(m);
 	HIPCHK(h, hipMemcpy(nk.data(), ok, 8 * m, hipMemcpyDeviceToHost)); HIPCHK(h, hipMemcpy(nv.data(), ov, 4 * m, hipMemcpyDeviceToHost));
 	tmp.done();
@@ -1476,22 +1427,19 @@ static int art_apply_core(kmr_handle *h, Scratch &tmp, const kmr_artifact_filter
 	uint64_t n_rem = 0;
 	if (n) {
 		const unsigned blocks = (unsigned)((n + 255) / 256);
-		hipLaunchKernelGGL(artifact_screen, dim3(blocks), dim3(256), 0, h->stream, in->bases.get<uint8_t>(), in->quals.get<uint8_t>(), in->offsets.get<uint64_t>(), n, t, P, dval, dmin, dmax, dro, drl);
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, artifact_screen, dim3(blocks), dim3(256), 0, in->bases.get<uint8_t>(), in->quals.get<uint8_t>(), in->offsets.get<uint64_t>(), n, t, P, dval, dmin, dmax, dro, drl);
 	}
 	/* lengths after the filter: n reads, then the remnants */
 	HIPCHK(h, tmp.take(&dlen, 2 * n + 1));
 	if (n) {
 		const unsigned blocks = (unsigned)((n + 255) / 256);
-		hipLaunchKernelGGL(artifact_action, dim3(blocks), dim3(256), 0, h->stream, in->offsets.get<uint64_t>(), n, dmate, P, dval, dmin, dmax, drl, dact, dlen, dflag);
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, artifact_action, dim3(blocks), dim3(256), 0, in->offsets.get<uint64_t>(), n, dmate, P, dval, dmin, dmax, drl, dact, dlen, dflag);
 		int rc = exclusive_scan(h, dflag, n, dridx); if (rc) return rc;
 		HIPCHK(h, hipMemcpy(&n_rem, dridx + n, 8, hipMemcpyDeviceToHost));
 	}
 	HIPCHK(h, tmp.take(&dsrc, n_rem));
 	if (n_rem) {
-		hipLaunchKernelGGL(artifact_remnants, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, n, drl, dridx, dlen, dsrc);
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, artifact_remnants, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, n, drl, dridx, dlen, dsrc);
 	}
 	HIPCHK(h, hipStreamSynchronize(h->stream));
 	hipError_t e = hipSuccess;
@@ -1515,9 +1463,8 @@ static int art_apply_core(kmr_handle *h, Scratch &tmp, const kmr_artifact_filter
 	HIPCHK(h, hipMemsetAsync(r->bases.get<uint8_t>() + r->total, 0, 64, h->stream)); HIPCHK(h, hipMemsetAsync(r->quals.get<uint8_t>() + r->total, 0, 64, h->stream));
 	HIPCHK(h, r->name_off.alloc(8 * std::max<uint64_t>(n_out, 1))); HIPCHK(h, r->name_len.alloc(4 * std::max<uint64_t>(n_out, 1)));
 	if (n_out) {
-		hipLaunchKernelGGL(artifact_gather, dim3((unsigned)std::min<uint64_t>((n_out + 3) / 4, 1u << 16)), dim3(256), 0, h->stream,
-		                   in->bases.get<uint8_t>(), in->quals.get<uint8_t>(), in->offsets.get<uint64_t>(), in->name_off.get<uint64_t>(), in->name_len.get<uint32_t>(), n, n_out, dact, dmin, dro, dsrc, r->offsets.get<uint64_t>(), r->bases.get<uint8_t>(), r->quals.get<uint8_t>(), r->name_off.get<uint64_t>(), r->name_len.get<uint32_t>());
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, artifact_gather, dim3((unsigned)std::min<uint64_t>((n_out + 3) / 4, 1u << 16)), dim3(256), 0,
+		       in->bases.get<uint8_t>(), in->quals.get<uint8_t>(), in->offsets.get<uint64_t>(), in->name_off.get<uint64_t>(), in->name_len.get<uint32_t>(), n, n_out, dact, dmin, dro, dsrc, r->offsets.get<uint64_t>(), r->bases.get<uint8_t>(), r->quals.get<uint8_t>(), r->name_off.get<uint64_t>(), r->name_len.get<uint32_t>());
 	}
 	HIPCHK(h, hipStreamSynchronize(h->stream));
 	*out = r.release();
@@ -1620,11 +1567,12 @@ struct PartitionWork {
 };
 
 /* the writer of a partition_run: queues the kernel that prints pick p = read pread[p] at byte poff[p] of the picks' text */
-typedef std::function<void(const PartitionWork &, const uint32_t *pread, const uint64_t *poff, kmr_picks *pk)> PartitionWriter;
+typedef std::function<int(const PartitionWork &, const uint32_t *pread, const uint64_t *poff, kmr_picks *pk)> PartitionWriter;
 static PartitionWriter select_writer(kmr_handle *h, const SelectParams &P) {
-	return [h, &P](const PartitionWork &W, const uint32_t *pread, const uint64_t *poff, kmr_picks *pk) {
-		hipLaunchKernelGGL(select_write_kernel, dim3((unsigned)std::min<uint64_t>((pk->n_picked + SEL_WAVES - 1) / SEL_WAVES, (uint64_t)num_cus(h) * 8)), dim3(SEL_THREADS), 0, h->stream, P,
+	return [h, &P](const PartitionWork &W, const uint32_t *pread, const uint64_t *poff, kmr_picks *pk) -> int {
+		LAUNCH(h, select_write_kernel, dim3((unsigned)std::min<uint64_t>((pk->n_picked + SEL_WAVES - 1) / SEL_WAVES, (uint64_t)num_cus(h) * 8)), dim3(SEL_THREADS), 0, P,
 		                   (const uint32_t *)W.name_printed, pread, poff, pk->n_picked, pk->text.get<uint8_t>());
+		return 0;
 	};
 }
 
@@ -1666,12 +1614,11 @@ static int partition_run(kmr_handle *h, Scratch &tmp, uint64_t n, uint64_t n_ite
 	timer.mark(0, h->stream);
 	HIPCHK(h, hipMemsetAsync(tot, 0, 8 * n_tot, h->stream));
 	int rc = classify(W); if (rc) return rc;
-	hipLaunchKernelGGL(partition_scan_kernel, dim3(1), dim3(SEL_SCAN_THREADS), 0, h->stream, W.unit_cnt, W.unit_bytes, S, W.Q.n_units, tot + 3, poff, tot);
-	hipLaunchKernelGGL(partition_rank_kernel, dim3(W.Q.n_units), dim3(SEL_UNIT), 0, h->stream, (const int32_t *)W.item_seg, (const uint32_t *)W.item_len, W.n_items, W.Q, (const uint32_t *)W.unit_cnt,
-	                   (const unsigned long long *)W.unit_bytes, pread, poff, (const uint32_t *)W.slot_read);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, partition_scan_kernel, dim3(1), dim3(SEL_SCAN_THREADS), 0, W.unit_cnt, W.unit_bytes, S, W.Q.n_units, tot + 3, poff, tot);
+	LAUNCH(h, partition_rank_kernel, dim3(W.Q.n_units), dim3(SEL_UNIT), 0, (const int32_t *)W.item_seg, (const uint32_t *)W.item_len, W.n_items, W.Q, (const uint32_t *)W.unit_cnt,
+	       (const unsigned long long *)W.unit_bytes, pread, poff, (const uint32_t *)W.slot_read);
 	std::vector<uint64_t> host_tot(n_tot, 0);
-	HIPCHK(h, hipMemcpyAsync(host_tot.data(), tot, 8 * n_tot, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
+	HIPCHK(h, fetch(h, host_tot.data(), tot, n_tot));
 	if (host_tot[2] & SEL_ERR_MATE) return fail(h, KMR_ERR_INVALID_ARG, "a mate index lies outside the batch");
 	if (host_tot[2] & SEL_ERR_NAME) return fail(h, KMR_ERR_INVALID_ARG, NAME_SPAN_ERROR);
 	if (host_tot[2] & SEL_ERR_PAIR) return fail(h, KMR_ERR_INVALID_ARG, "the pair list holds an index outside the batch or a pair without a read");
@@ -1682,8 +1629,7 @@ static int partition_run(kmr_handle *h, Scratch &tmp, uint64_t n, uint64_t n_ite
 	timer.mark(1, h->stream);
 	if (pk->bytes) {
 		HIPCHK(h, pk->text.alloc((pk->bytes + 15) & ~(uint64_t)15));
-		write(W, pread, poff, pk);
-		HIPCHK(h, hipGetLastError());
+		{ int rc = write(W, pread, poff, pk); if (rc) return rc; }
 	}
 	timer.mark(2, h->stream);
 	HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1698,7 +1644,7 @@ static int partition_run(kmr_handle *h, Scratch &tmp, uint64_t n, uint64_t n_ite
  * device memory (null for one input) */
 static int partition_core(kmr_handle *h, Scratch &tmp, const SelectParams &P, const SelRounds &R, const uint64_t *dstarts, uint32_t n_inputs, bool keep_read_seg, kmr_picks *pk) {
 	return partition_run(h, tmp, P.n, P.n, R, n_inputs, R.n * n_inputs, dstarts, false, keep_read_seg, nullptr, 0, pk, [&](const PartitionWork &W) -> int {
-		hipLaunchKernelGGL(partition_classify_kernel, dim3(W.Q.n_units), dim3(SEL_UNIT), 0, h->stream, P, R, W.Q, W.read_seg, W.item_len, W.name_printed, W.picked, W.unit_cnt, W.unit_bytes, W.err);
+		LAUNCH(h, partition_classify_kernel, dim3(W.Q.n_units), dim3(SEL_UNIT), 0, P, R, W.Q, W.read_seg, W.item_len, W.name_printed, W.picked, W.unit_cnt, W.unit_bytes, W.err);
 		return 0;
 	}, select_writer(h, P));
 }
@@ -1760,10 +1706,10 @@ static int normalize_core(kmr_handle *h, Scratch &tmp, const SelectParams &P, co
 	return partition_run(h, tmp, n, 2 * n, R, n_inputs, n_inputs, dstarts, true, true, pk->norm_info, 3, pk, [&](const PartitionWork &W) -> int {
 		HIPCHK(h, hipMemsetAsync(named, 0, 4 * n, h->stream)); HIPCHK(h, hipMemsetAsync(W.item_seg, 0xff, 4 * W.n_items, h->stream));
 		HIPCHK(h, hipMemsetAsync(W.read_seg, 0xff, 4 * n, h->stream)); HIPCHK(h, hipMemsetAsync(W.picked, 0, n, h->stream));
-		if (n_pairs) hipLaunchKernelGGL(normalize_mark_kernel, dim3(grid_for(n_pairs)), dim3(256), 0, h->stream, N, n, named, W.err);
-		hipLaunchKernelGGL(normalize_classify_kernel, dim3(grid_for(n_pairs + n)), dim3(256), 0, h->stream, P, N, W.Q, (const uint32_t *)named, W.slot_read, W.item_seg, W.item_len, W.name_printed, W.picked,
-		                   W.read_seg, W.extra, W.err);
-		hipLaunchKernelGGL(normalize_count_kernel, dim3(W.Q.n_units), dim3(SEL_UNIT), 0, h->stream, (const int32_t *)W.item_seg, (const uint32_t *)W.item_len, W.n_items, W.Q, W.unit_cnt, W.unit_bytes);
+		if (n_pairs) LAUNCH(h, normalize_mark_kernel, dim3(grid_for(n_pairs)), dim3(256), 0, N, n, named, W.err);
+		LAUNCH(h, normalize_classify_kernel, dim3(grid_for(n_pairs + n)), dim3(256), 0, P, N, W.Q, (const uint32_t *)named, W.slot_read, W.item_seg, W.item_len, W.name_printed, W.picked,
+		       W.read_seg, W.extra, W.err);
+		LAUNCH(h, normalize_count_kernel, dim3(W.Q.n_units), dim3(SEL_UNIT), 0, (const int32_t *)W.item_seg, (const uint32_t *)W.item_len, W.n_items, W.Q, W.unit_cnt, W.unit_bytes);
 		return 0;
 	}, select_writer(h, P));
 }
@@ -2129,18 +2075,19 @@ static int report_core(kmr_handle *h, Scratch &tmp, const ReportCall &c, const u
 			if (slots) {
 				NormalizeParams N = {}; N.read1 = dr1; N.read2 = dr2; N.n_pairs = n_pairs;
 				HIPCHK(h, hipMemsetAsync(named, 0, 4 * n, h->stream));
-				hipLaunchKernelGGL(normalize_mark_kernel, dim3(grid_for(n_pairs)), dim3(256), 0, h->stream, N, n, named, W.err);
-				hipLaunchKernelGGL(artifact_pairs_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, (const uint32_t *)named, n, W.err);
+				LAUNCH(h, normalize_mark_kernel, dim3(grid_for(n_pairs)), dim3(256), 0, N, n, named, W.err);
+				LAUNCH(h, artifact_pairs_kernel, dim3(grid_for(n)), dim3(256), 0, (const uint32_t *)named, n, W.err);
 			}
-			if (lds) hipLaunchKernelGGL(artifact_classify_kernel<true>, dim3(W.Q.n_units), dim3(SEL_UNIT), ctr_bytes, h->stream, A, W.Q, W.n_items, W.slot_read, W.item_seg, W.item_len, W.name_printed, read_label,
-			                            W.picked, W.read_seg, W.unit_cnt, W.unit_bytes, W.extra, W.err);
-			else hipLaunchKernelGGL(artifact_classify_kernel<false>, dim3(W.Q.n_units), dim3(SEL_UNIT), 0, h->stream, A, W.Q, W.n_items, W.slot_read, W.item_seg, W.item_len, W.name_printed, read_label,
-			                        W.picked, W.read_seg, W.unit_cnt, W.unit_bytes, W.extra, W.err);
+			if (lds) LAUNCH(h, artifact_classify_kernel<true>, dim3(W.Q.n_units), dim3(SEL_UNIT), ctr_bytes, A, W.Q, W.n_items, W.slot_read, W.item_seg, W.item_len, W.name_printed, read_label,
+			                W.picked, W.read_seg, W.unit_cnt, W.unit_bytes, W.extra, W.err);
+			else LAUNCH(h, artifact_classify_kernel<false>, dim3(W.Q.n_units), dim3(SEL_UNIT), 0, A, W.Q, W.n_items, W.slot_read, W.item_seg, W.item_len, W.name_printed, read_label,
+			            W.picked, W.read_seg, W.unit_cnt, W.unit_bytes, W.extra, W.err);
 			return 0;
 		},
-		[&](const PartitionWork &W, const uint32_t *pread, const uint64_t *poff, kmr_picks *pk) {
-			hipLaunchKernelGGL(artifact_write_kernel, dim3((unsigned)std::min<uint64_t>((pk->n_picked + SEL_WAVES - 1) / SEL_WAVES, (uint64_t)num_cus(h) * 8)), dim3(SEL_THREADS), 0, h->stream, A,
+		[&](const PartitionWork &W, const uint32_t *pread, const uint64_t *poff, kmr_picks *pk) -> int {
+			LAUNCH(h, artifact_write_kernel, dim3((unsigned)std::min<uint64_t>((pk->n_picked + SEL_WAVES - 1) / SEL_WAVES, (uint64_t)num_cus(h) * 8)), dim3(SEL_THREADS), 0, A,
 			                   (const uint32_t *)W.name_printed, (const uint32_t *)read_label, pread, poff, pk->n_picked, pk->text.get<uint8_t>());
+			return 0;
 		});
 }
 
@@ -2177,8 +2124,7 @@ static int report_fused(kmr_handle *h, ReportCall &c, uint32_t *value, uint32_t 
 	int64_t *dmate = nullptr;
 	if (n_pairs) {
 		HIPCHK(h, tmp.take(&dmate, n)); HIPCHK(h, hipMemsetAsync(dmate, 0xff, 8 * n, h->stream));
-		hipLaunchKernelGGL(artifact_mate_kernel, dim3(grid_for(n_pairs)), dim3(256), 0, h->stream, dr1, dr2, n_pairs, n, dmate);
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, artifact_mate_kernel, dim3(grid_for(n_pairs)), dim3(256), 0, dr1, dr2, n_pairs, n, dmate);
 	}
 	ArtDecisions D;
 	kmr_reads *made = nullptr;
@@ -2245,16 +2191,14 @@ static int pairs_core(kmr_handle *h, Scratch &tmp, const kmr_reads *r, const uin
 	EventTimer<5> timer(h->tune.pairs_timing);
 	timer.mark(0, h->stream);
 	HIPCHK(h, hipMemsetAsync(tot, 0, 8 * PAIRS_T_WORDS, h->stream));
-	hipLaunchKernelGGL(pairs_parse_kernel, grid, block, 0, h->stream, P, hash, cn, fl, tot);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, pairs_parse_kernel, grid, block, 0, P, hash, cn, fl, tot);
 	timer.mark(1, h->stream);
 	uint64_t totals[PAIRS_T_WORDS] = {0};
 	if (text_len == 0) {      /* no names (kmr_reads_from_host, kmr_reads_from_twobit): every read is a half pair of its own */
 		int64_t *r1, *r2;
 		HIPCHK(h, alloc_n(pr->read1, &r1, n)); HIPCHK(h, alloc_n(pr->read2, &r2, n));
-		hipLaunchKernelGGL(pairs_single_kernel, grid, block, 0, h->stream, n, mate, r1, r2);
-		HIPCHK(h, hipGetLastError());
-		HIPCHK(h, hipMemcpyAsync(totals, tot, 8 * PAIRS_T_WORDS, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
+		LAUNCH(h, pairs_single_kernel, grid, block, 0, n, mate, r1, r2);
+		HIPCHK(h, fetch(h, totals, tot, PAIRS_T_WORDS));
 		if (totals[PAIRS_T_ERR] & PAIRS_ERR_NAME) return fail(h, KMR_ERR_INVALID_ARG, NAME_SPAN_ERROR);
 		pr->n_pairs = n;
 		tmp.done();
@@ -2264,19 +2208,17 @@ static int pairs_core(kmr_handle *h, Scratch &tmp, const kmr_reads *r, const uin
 	/* phase 1 */
 	HIPCHK(h, tmp.take(&link, n)); HIPCHK(h, tmp.take(&brk, n)); HIPCHK(h, tmp.take(&bscan, n + 1)); HIPCHK(h, tmp.take(&run, n + 1));
 	HIPCHK(h, tmp.take(&sec, n)); HIPCHK(h, tmp.take(&unp, n)); HIPCHK(h, tmp.take(&sscan, n + 1)); HIPCHK(h, tmp.take(&uscan, n + 1));
-	hipLaunchKernelGGL(pairs_link_kernel, grid, block, 0, h->stream, P, N, link, brk);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, pairs_link_kernel, grid, block, 0, P, N, link, brk);
 	int rc = exclusive_scan(h, brk, n, bscan); if (rc) return rc;
-	hipLaunchKernelGGL(pairs_runstart_kernel, grid, block, 0, h->stream, (const uint8_t *)link, (const uint64_t *)bscan, n, run);
-	hipLaunchKernelGGL(pairs_seq_kernel, grid, block, 0, h->stream, (const uint8_t *)link, (const uint64_t *)bscan, (const uint32_t *)run, n, sec, unp, mate);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, pairs_runstart_kernel, grid, block, 0, (const uint8_t *)link, (const uint64_t *)bscan, n, run);
+	LAUNCH(h, pairs_seq_kernel, grid, block, 0, (const uint8_t *)link, (const uint64_t *)bscan, (const uint32_t *)run, n, sec, unp, mate);
 	rc = exclusive_scan(h, sec, n, sscan); if (rc) return rc;
 	rc = exclusive_scan(h, unp, n, uscan); if (rc) return rc;
 	/* the first of the call's two fixed-size copies: phase 1's totals size phase 2 (an interleaved file leaves it nothing) */
-	HIPCHK(h, hipMemcpyAsync(&totals[PAIRS_T_SEQ], sscan + n, 8, hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(h, hipMemcpyAsync(&totals[PAIRS_T_UNPAIRED], uscan + n, 8, hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(h, hipMemcpyAsync(&totals[PAIRS_T_ERR], tot + PAIRS_T_ERR, 8, hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(h, hipStreamSynchronize(h->stream));
+	HIPCHK(h, fetch_queue(h, &totals[PAIRS_T_SEQ], sscan + n));
+	HIPCHK(h, fetch_queue(h, &totals[PAIRS_T_UNPAIRED], uscan + n));
+	HIPCHK(h, fetch_queue(h, &totals[PAIRS_T_ERR], tot + PAIRS_T_ERR));
+	HIPCHK(h, stream_wait(h));
 	if (totals[PAIRS_T_ERR] & PAIRS_ERR_NAME) return fail(h, KMR_ERR_INVALID_ARG, NAME_SPAN_ERROR);
 	const uint64_t n_seq = totals[PAIRS_T_SEQ], m = totals[PAIRS_T_UNPAIRED];
 	/* phase 2 */
@@ -2286,29 +2228,26 @@ static int pairs_core(kmr_handle *h, Scratch &tmp, const kmr_reads *r, const uin
 		HIPCHK(h, tmp.take(&kin, m)); HIPCHK(h, tmp.take(&kout, m)); HIPCHK(h, tmp.take(&vin, m)); HIPCHK(h, tmp.take(&vout, m));
 		HIPCHK(h, tmp.take(&push, n)); HIPCHK(h, tmp.take(&side, n)); HIPCHK(h, tmp.take(&pscan, n + 1));
 		const uint32_t bits = h->tune.pair_hash_bits;
-		hipLaunchKernelGGL(pairs_keys_kernel, grid, block, 0, h->stream, (const uint32_t *)unp, (const uint64_t *)uscan, (const uint64_t *)hash, bits >= 64 ? ~0ull : (1ull << bits) - 1, n, kin, vin);
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, pairs_keys_kernel, grid, block, 0, (const uint32_t *)unp, (const uint64_t *)uscan, (const uint64_t *)hash, bits >= 64 ? ~0ull : (1ull << bits) - 1, n, kin, vin);
 		HIPCHK(h, hipMemsetAsync(push, 0, 4 * n, h->stream)); HIPCHK(h, hipMemsetAsync(side, 0, n, h->stream));
 		rc = sort_reserve(h, tmp.sort, m, "kmr_identify_pairs"); if (rc) return rc;
 		timer.mark(2, h->stream);
 		rc = sort_pairs(h, tmp.sort, kin, kout, vin, vout, m, "kmr_identify_pairs"); if (rc) return rc;
 		timer.mark(3, h->stream);
-		hipLaunchKernelGGL(pairs_group_kernel, dim3(grid_for(m)), block, 0, h->stream, P, N, (const unsigned long long *)kout, (const uint32_t *)vout, m, mate, push, side, tot);
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, pairs_group_kernel, dim3(grid_for(m)), block, 0, P, N, (const unsigned long long *)kout, (const uint32_t *)vout, m, mate, push, side, tot);
 		rc = exclusive_scan(h, push, n, pscan); if (rc) return rc;
 		/* the second: what phase 2 made */
-		HIPCHK(h, hipMemcpyAsync(&totals[PAIRS_T_PUSHED], pscan + n, 8, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(h, hipMemcpyAsync(&totals[PAIRS_T_FULL2], tot + PAIRS_T_FULL2, 8 * (PAIRS_T_WORDS - PAIRS_T_FULL2), hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(h, hipStreamSynchronize(h->stream));
+		HIPCHK(h, fetch_queue(h, &totals[PAIRS_T_PUSHED], pscan + n));
+		HIPCHK(h, fetch_queue(h, &totals[PAIRS_T_FULL2], tot + PAIRS_T_FULL2, PAIRS_T_WORDS - PAIRS_T_FULL2));
+		HIPCHK(h, stream_wait(h));
 	}
 	pr->n_seq = n_seq; pr->n_pairs = n_seq + totals[PAIRS_T_PUSHED]; pr->n_full = n_seq + totals[PAIRS_T_FULL2];
 	pr->n_conflicts = totals[PAIRS_T_CONFLICT1] + totals[PAIRS_T_CONFLICT2];
 	h->last_pair_hash_collisions = totals[PAIRS_T_COLLISIONS];
 	int64_t *r1, *r2;
 	HIPCHK(h, alloc_n(pr->read1, &r1, pr->n_pairs)); HIPCHK(h, alloc_n(pr->read2, &r2, pr->n_pairs));
-	hipLaunchKernelGGL(pairs_scatter_kernel, grid, block, 0, h->stream, (const uint32_t *)sec, (const uint64_t *)sscan, (const uint32_t *)push, (const uint64_t *)pscan, (const uint8_t *)side, (const int64_t *)mate,
-	                   n, n_seq, r1, r2);
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, pairs_scatter_kernel, grid, block, 0, (const uint32_t *)sec, (const uint64_t *)sscan, (const uint32_t *)push, (const uint64_t *)pscan, (const uint8_t *)side, (const int64_t *)mate,
+	       n, n_seq, r1, r2);
 	timer.mark(4, h->stream);
 	HIPCHK(h, hipStreamSynchronize(h->stream));
 	tmp.done();
@@ -2452,22 +2391,20 @@ static int dedup_core(kmr_handle *h, Scratch &tmp, const kmr_reads *r, const uin
 	if (n && np && cfg->dedup_mode) {
 		/* candidates and their keys */
 		HIPCHK(h, tmp.take(&keys, (size_t)P.W * np)); HIPCHK(h, tmp.take(&cand, np)); HIPCHK(h, tmp.take(&flip, np)); HIPCHK(h, tmp.take(&cscan, np + 1));
-		hipLaunchKernelGGL(dedup_key_kernel, dim3(grid_for(np)), block, 0, h->stream, P, keys, cand, flip, tot);
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, dedup_key_kernel, dim3(grid_for(np)), block, 0, P, keys, cand, flip, tot);
 		timer.mark(1, h->stream);
 		rc = exclusive_scan(h, cand, np, cscan); if (rc) return rc;
 		/* the first of the call's three fixed-size copies: the number of candidates sizes the sorts */
-		HIPCHK(h, hipMemcpyAsync(&c, cscan + np, 8, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(h, hipMemcpyAsync(totals, tot, 8 * DEDUP_T_AFFECTED, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(h, hipStreamSynchronize(h->stream));
+		HIPCHK(h, fetch_queue(h, &c, cscan + np));
+		HIPCHK(h, fetch_queue(h, totals, tot, DEDUP_T_AFFECTED));
+		HIPCHK(h, stream_wait(h));
 	} else timer.mark(1, h->stream);
 	for (int i = 0; i < 4; i++) dd->skipped[i] = totals[i];
 	timer.mark(2, h->stream);
 	if (c >= 2) {
 		const dim3 cgrid(grid_for(c));
 		HIPCHK(h, tmp.take(&order, c));
-		hipLaunchKernelGGL(dedup_compact_kernel, dim3(grid_for(np)), block, 0, h->stream, (const uint32_t *)cand, (const uint64_t *)cscan, np, order);
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, dedup_compact_kernel, dim3(grid_for(np)), block, 0, (const uint32_t *)cand, (const uint64_t *)cscan, np, order);
 		/* least significant word first; the sort is stable, so equal keys keep ascending pair position */
 		SortColumn cols[4];      /* a key holds at most 128 bases (kmr_dedup_config_check) */
 		if (P.W > 4) return fail(h, KMR_ERR_UNSUPPORTED, "kmr_dedup_fragments: a key of more than 4 words");
@@ -2477,18 +2414,14 @@ static int dedup_core(kmr_handle *h, Scratch &tmp, const kmr_reads *r, const uin
 		/* groups, and those of two members and more */
 		HIPCHK(h, tmp.take(&head, c)); HIPCHK(h, tmp.take(&hscan, c + 1)); HIPCHK(h, tmp.take(&start, c + 1));
 		HIPCHK(h, tmp.take(&keep, c)); HIPCHK(h, tmp.take(&kscan, c + 1)); HIPCHK(h, tmp.take(&first, c)); HIPCHK(h, tmp.take(&grp, c));
-		hipLaunchKernelGGL(dedup_heads_kernel, cgrid, block, 0, h->stream, (const unsigned long long *)keys, np, P.W, (const uint32_t *)perm, c, head);
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, dedup_heads_kernel, cgrid, block, 0, (const unsigned long long *)keys, np, P.W, (const uint32_t *)perm, c, head);
 		rc = exclusive_scan(h, head, c, hscan); if (rc) return rc;
 		rc = group_starts(h, head, hscan, c, start); if (rc) return rc;
-		hipLaunchKernelGGL(dedup_keep_kernel, cgrid, block, 0, h->stream, (const uint64_t *)hscan, (const uint64_t *)start, c, keep);
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, dedup_keep_kernel, cgrid, block, 0, (const uint64_t *)hscan, (const uint64_t *)start, c, keep);
 		rc = exclusive_scan(h, keep, c, kscan); if (rc) return rc;
-		hipLaunchKernelGGL(dedup_kept_kernel, cgrid, block, 0, h->stream, (const uint32_t *)keep, (const uint64_t *)kscan, (const uint64_t *)start, (const uint32_t *)perm, c, first, grp);
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, dedup_kept_kernel, cgrid, block, 0, (const uint32_t *)keep, (const uint64_t *)kscan, (const uint64_t *)start, (const uint32_t *)perm, c, first, grp);
 		/* the second: the number of groups sizes everything behind */
-		HIPCHK(h, hipMemcpyAsync(&K, kscan + c, 8, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(h, hipStreamSynchronize(h->stream));
+		HIPCHK(h, fetch(h, &K, kscan + c));
 	} else timer.mark(3, h->stream);
 	/* the consensus batch (empty if nothing was collapsed) */
 	const uint64_t n_new = K * P.sides;
@@ -2509,26 +2442,23 @@ static int dedup_core(kmr_handle *h, Scratch &tmp, const kmr_reads *r, const uin
 		DedupGroups G; G.perm = perm; G.flip = flip; G.start = start; G.ogroup = grp2; G.K = K;
 		uint32_t *len, *nb; uint64_t *nscan; DedupMember *members;
 		HIPCHK(h, tmp.take(&len, n_new)); HIPCHK(h, tmp.take(&nb, n_new)); HIPCHK(h, tmp.take(&nscan, n_new + 1)); HIPCHK(h, tmp.take(&members, (size_t)c * P.sides));
-		hipLaunchKernelGGL(dedup_size_kernel, dim3(grid_for(n_new)), block, 0, h->stream, P, G, len, nb, gfirst, gsize, tot);
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, dedup_size_kernel, dim3(grid_for(n_new)), block, 0, P, G, len, nb, gfirst, gsize, tot);
 		rc = exclusive_scan(h, len, n_new, coff); if (rc) return rc;
 		rc = exclusive_scan(h, nb, n_new, nscan); if (rc) return rc;
 		/* the third: the bases and name bytes of the batch, what was collapsed, the error word */
-		HIPCHK(h, hipMemcpyAsync(&cr->total, coff + n_new, 8, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(h, hipMemcpyAsync(&name_total, nscan + n_new, 8, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(h, hipMemcpyAsync(&totals[DEDUP_T_AFFECTED], tot + DEDUP_T_AFFECTED, 16, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(h, hipStreamSynchronize(h->stream));
+		HIPCHK(h, fetch_queue(h, &cr->total, coff + n_new));
+		HIPCHK(h, fetch_queue(h, &name_total, nscan + n_new));
+		HIPCHK(h, fetch_queue(h, &totals[DEDUP_T_AFFECTED], tot + DEDUP_T_AFFECTED, 2));
+		HIPCHK(h, stream_wait(h));
 		if (totals[DEDUP_T_ERR] & DEDUP_ERR_NAME) return fail(h, KMR_ERR_INVALID_ARG, NAME_SPAN_ERROR);
 		uint8_t *cb, *cq, *names;
 		HIPCHK(h, alloc_n(cr->bases, &cb, cr->total + 64)); HIPCHK(h, alloc_n(cr->quals, &cq, cr->total + 64)); HIPCHK(h, alloc_n(dd->names, &names, name_total));
 		HIPCHK(h, hipMemsetAsync(cb + cr->total, 0, 64, h->stream)); HIPCHK(h, hipMemsetAsync(cq + cr->total, 0, 64, h->stream));
 		timer.mark(4, h->stream);
-		hipLaunchKernelGGL(dedup_consensus_kernel, dim3((unsigned)std::min<uint64_t>((n_new + DEDUP_WAVES - 1) / DEDUP_WAVES, (uint64_t)num_cus(h) * 8)), dim3(DEDUP_THREADS), 0, h->stream,
-		                   P, G, tables, (const uint64_t *)coff, (const uint64_t *)nscan, members, cb, cq, names, cno, cnl);
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, dedup_consensus_kernel, dim3((unsigned)std::min<uint64_t>((n_new + DEDUP_WAVES - 1) / DEDUP_WAVES, (uint64_t)num_cus(h) * 8)), dim3(DEDUP_THREADS), 0,
+		       P, G, tables, (const uint64_t *)coff, (const uint64_t *)nscan, members, cb, cq, names, cno, cnl);
 		timer.mark(5, h->stream);
-		hipLaunchKernelGGL(dedup_discard_kernel, dim3(grid_for(c)), block, 0, h->stream, P, (const uint32_t *)perm, (const uint64_t *)hscan, (const uint32_t *)keep, c, disc);
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, dedup_discard_kernel, dim3(grid_for(c)), block, 0, P, (const uint32_t *)perm, (const uint64_t *)hscan, (const uint32_t *)keep, c, disc);
 		timer.mark(6, h->stream);
 		HIPCHK(h, hipStreamSynchronize(h->stream));      /* the temporaries above go */
 	} else {
@@ -2625,11 +2555,10 @@ static int dump_core(kmr_handle *h, int kind, uint32_t min_depth, uint64_t lo, u
 		SelectTimer timer(h->tune.dump_timing);
 		timer.mark(0, h->stream);
 		HIPCHK(h, hipMemsetAsync(off + n + 1, 0, 8, h->stream));
-		hipLaunchKernelGGL(dump_size_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, P, len, (unsigned long long *)(off + n + 1));
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, dump_size_kernel, dim3(grid_for(n)), dim3(256), 0, P, len, (unsigned long long *)(off + n + 1));
 		int rc = exclusive_scan(h, len, n, off); if (rc) return rc;
 		uint64_t totals[2] = {0, 0};
-		HIPCHK(h, hipMemcpyAsync(totals, off + n, 16, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));      /* the one copy that brings sizes back */
+		HIPCHK(h, fetch(h, totals, off + n, 2));      /* the one copy that brings sizes back */
 		tx->bytes = totals[0]; tx->kept = totals[1];
 		if (out && tx->bytes) HIPCHK(h, tx->text.alloc((tx->bytes + 15) & ~(uint64_t)15));
 		timer.mark(1, h->stream);      /* (behind the allocation: the events then bracket the writer alone) */
@@ -2639,8 +2568,7 @@ static int dump_core(kmr_handle *h, int kind, uint32_t min_depth, uint64_t lo, u
 			const unsigned blocks = (unsigned)((tiles + per_block - 1) / per_block);
 			h->last_dump_tiles_per_block = per_block; h->last_dump_blocks = blocks;
 			uint8_t *dout = tx->text.get<uint8_t>();
-			with_w(h, [&](auto W) { hipLaunchKernelGGL(dump_write_kernel<W()>, dim3(blocks), dim3(DUMP_THREADS), 0, h->stream, P, (const uint64_t *)off, tx->bytes, per_block, dout); return 0; });
-			HIPCHK(h, hipGetLastError());
+			{ int rc = with_w(h, [&](auto W) -> int { LAUNCH(h, dump_write_kernel<W()>, dim3(blocks), dim3(DUMP_THREADS), 0, P, (const uint64_t *)off, tx->bytes, per_block, dout); return 0; }); if (rc) return rc; }
 		}
 		timer.mark(2, h->stream);
 		HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2718,8 +2646,7 @@ int kmr_reads_twobit(kmr_handle *h, const kmr_reads *r, uint8_t *twobit, uint64_
 	HIPCHK(h, tmp.take(&dlen, n + 1)); HIPCHK(h, tmp.take(&dcnt, n + 1)); HIPCHK(h, tmp.take(&dtb, n + 1)); HIPCHK(h, tmp.take(&dmk, n + 1));
 	uint64_t tb_total = 0, mk_total = 0;
 	if (n) {
-		hipLaunchKernelGGL(twobit_count_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, r->bases.get<uint8_t>(), r->offsets.get<uint64_t>(), n, dlen, dcnt);
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, twobit_count_kernel, dim3(grid_for(n)), dim3(256), 0, r->bases.get<uint8_t>(), r->offsets.get<uint64_t>(), n, dlen, dcnt);
 		int rc = exclusive_scan(h, dlen, n, dtb); if (rc) return rc;
 		rc = exclusive_scan(h, dcnt, n, dmk); if (rc) return rc;
 		HIPCHK(h, hipMemcpy(&tb_total, dtb + n, 8, hipMemcpyDeviceToHost)); HIPCHK(h, hipMemcpy(&mk_total, dmk + n, 8, hipMemcpyDeviceToHost));
@@ -2730,8 +2657,7 @@ int kmr_reads_twobit(kmr_handle *h, const kmr_reads *r, uint8_t *twobit, uint64_
 	uint8_t *dtw, *dmc; uint32_t *dmp;
 	HIPCHK(h, tmp.take(&dtw, tb_total)); HIPCHK(h, tmp.take(&dmp, mk_total)); HIPCHK(h, tmp.take(&dmc, mk_total));
 	if (n) {
-		hipLaunchKernelGGL(twobit_pack_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, r->bases.get<uint8_t>(), r->offsets.get<uint64_t>(), n, dtb, dmk, dtw, dmp, dmc);
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, twobit_pack_kernel, dim3(grid_for(n)), dim3(256), 0, r->bases.get<uint8_t>(), r->offsets.get<uint64_t>(), n, dtb, dmk, dtw, dmp, dmc);
 	}
 	HIPCHK(h, hipStreamSynchronize(h->stream));
 	tmp.done();
@@ -2771,14 +2697,12 @@ int kmr_reads_from_twobit(kmr_handle *h, const uint8_t *twobit, const uint64_t *
 	for (uint64_t i = 0; i <= n_reads; i++) { rel[i] = offsets[i] - first; trel[i] = twobit_offsets[i] - twobit_offsets[0]; if (markup_offsets) mrel[i] = markup_offsets[i] - markup_offsets[0]; }
 	if (tbytes) HIPCHK(h, hipMemcpy(dtb, twobit + twobit_offsets[0], tbytes, hipMemcpyHostToDevice));
 	HIPCHK(h, hipMemcpy(dto, trel.data(), 8 * (n_reads + 1), hipMemcpyHostToDevice)); HIPCHK(h, hipMemcpy(doff, rel.data(), 8 * (n_reads + 1), hipMemcpyHostToDevice));
-	hipLaunchKernelGGL(twobit_unpack_kernel, dim3((unsigned)std::min<uint64_t>((n_reads + 255) / 256, (uint64_t)num_cus(h) * 32)), dim3(256), 0, h->stream, (const uint8_t *)dtb, (const uint64_t *)dto, (const uint64_t *)doff, n_reads, r->bases.get<uint8_t>(), r->offsets.get<uint64_t>());
-	HIPCHK(h, hipGetLastError());
+	LAUNCH(h, twobit_unpack_kernel, dim3((unsigned)std::min<uint64_t>((n_reads + 255) / 256, (uint64_t)num_cus(h) * 32)), dim3(256), 0, (const uint8_t *)dtb, (const uint64_t *)dto, (const uint64_t *)doff, n_reads, r->bases.get<uint8_t>(), r->offsets.get<uint64_t>());
 	if (nm) {
 		HIPCHK(h, tmp.take(&dmo, n_reads + 1)); HIPCHK(h, tmp.take(&dmp, nm)); HIPCHK(h, tmp.take(&dmc, nm));
 		HIPCHK(h, hipMemcpy(dmo, mrel.data(), 8 * (n_reads + 1), hipMemcpyHostToDevice));
 		HIPCHK(h, hipMemcpy(dmp, markup_pos + markup_offsets[0], 4 * nm, hipMemcpyHostToDevice)); HIPCHK(h, hipMemcpy(dmc, markup_char + markup_offsets[0], nm, hipMemcpyHostToDevice));
-		hipLaunchKernelGGL(twobit_markup_kernel, dim3(grid_for(n_reads)), dim3(256), 0, h->stream, (const uint64_t *)dmo, (const uint32_t *)dmp, (const uint8_t *)dmc, (const uint64_t *)r->offsets.get<uint64_t>(), n_reads, r->bases.get<uint8_t>());
-		HIPCHK(h, hipGetLastError());
+		LAUNCH(h, twobit_markup_kernel, dim3(grid_for(n_reads)), dim3(256), 0, (const uint64_t *)dmo, (const uint32_t *)dmp, (const uint8_t *)dmc, (const uint64_t *)r->offsets.get<uint64_t>(), n_reads, r->bases.get<uint8_t>());
 	}
 	HIPCHK(h, hipStreamSynchronize(h->stream));
 	tmp.done();
