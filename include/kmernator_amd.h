@@ -706,13 +706,24 @@ int kmr_artifact_filter_apply(kmr_handle *h, const kmr_artifact_filter *f, const
  *               ">name[ label]\n" bases "\n"; bases and quals are [trim_offset, trim_offset + trim_length) of the read.  A
  *               discarded read, or a trim of at most one base, prints as the base N with the quality output_quality_base + 1
  *               (src/Sequence.cpp:305-311, 729-733).  Qualities move from the handle's fastq_start_char to
- *               output_quality_base (--fastq-output-base-quality)
+ *               output_quality_base (--fastq-output-base-quality).  Read::REF_QUAL (127) is not a quality: a read whose first
+ *               quality in the batch is 127 has none (Read::setRead, src/Sequence.cpp:652-655: what kmr_ingest_fasta without a
+ *               qual text and kmr_extend_contigs give), and every base of such a read, and of a slice that starts on a 127,
+ *               prints as PRINT_REF_QUAL (103, 'g') at either output base (Read::getQuals :744-746).  A 127 elsewhere moves
+ *               like any byte.  Where the two quality bases differ this is the library's own rule: the reference's serial readers
+ *               rescale a 127 with every other byte on the way in (src/ReadSet.cpp:324-337), after which it is no REF_QUAL.
+ *               A trim_offset equal to the read's length leaves no base and prints the masked N, as in the reference; past the
+ *               end, where the reference asserts, the same
  *   name        the read's name span (name_off / name_len of kmr_reads_copy) in `text`, the FASTQ text the batch was
  *               ingested from, up to the first blank or tab.  The caller hands that text in again (the library keeps no copy)
  *   label       parts joined by single blanks (Read::LABEL_SEP): "AFTrim:<min_pass>+<max_pass - min_pass>" if af_action[i]
  *               is 1, "Trim:<offset>+<length>" if was_trimmed[i], "<Label>:<(int)(score + 0.5)>" with Label = Score /
  *               MedianScore / MinScore / MaxScore / AvgScore (getKmerScoringTypeLabel, :248-257, in kmr_scoring's order).
- *               A discarded read was never scored (:1195-1197) and has no label
+ *               A discarded read was never scored (:1195-1197) and has no label.  Where the reference leaves the number open
+ *               the rule is this library's: (int)(score + 0.5) is taken in double and truncates toward zero; a NaN score, for
+ *               which the cast is undefined in C++, prints 0, and a sum outside int prints the nearest of -2147483648 and
+ *               2147483647 (a NaN never passes the score test).  max_pass < min_pass, which the reference asserts against,
+ *               prints the signed difference
  * Not covered: stored comments are not printed and a Casava "name 1:Y" is not rewritten to "name/1"; the unmasked formats.
  * Bimodal trimming: "Bimodal@..." / "InvBimodal@..." stands between AFTrim and Trim (kmr_set_bimodal_sigmas; the fused forms tag
  * what they score, the host-array forms take the words through kmr_select_bimodal).  Markup characters other than N, X and '.' are outside the parity claim: the reference applies a read's

@@ -30,6 +30,7 @@ namespace kmr {
 
 enum { SEL_ERR_MATE = 1, SEL_ERR_NAME = 2, SEL_ERR_PAIR = 4, SEL_ERR_TWICE = 8,      /* the last two: the pair list of kmr_normalize.hpp */
        SEL_ERR_UNNAMED = 16, SEL_ERR_VALUE = 32 };                                    /* kmr_artifact_report.hpp: a read no pair names, a value above n_sequences */
+static const uint8_t SEL_REF_QUAL = 127, SEL_PRINT_REF_QUAL = 103;      /* Read::REF_QUAL, Read::PRINT_REF_QUAL (src/config.h:140-141) */
 static const int SEL_THREADS = 256, SEL_WAVES = SEL_THREADS / 64, SEL_LABEL_CAP = 128;
 /* the longest label sel_label writes, part by part, each with its leading blank:
  *   " AFTrim:" u32 "+" i64 of a difference of two u32       8 + 10 + 1 + 11
@@ -116,7 +117,8 @@ __device__ __forceinline__ uint32_t sel_label(const SelectParams &P, uint64_t i,
 	at = sel_put_char(dst, at, ' ', write);
 	at = sel_put_str(dst, at, sel_score_label(P.scoring), write);
 	double s = (double)P.score[i] + 0.5;      /* (int)(score + 0.5), src/ReadSelector.h:1032 */
-	s = s > 2147483647.0 ? 2147483647.0 : (s < -2147483648.0 ? -2147483648.0 : s);
+	/* where that cast is undefined in C++ the rule is this library's own (kmernator_amd.h): a NaN prints 0, a sum outside int the nearest int */
+	s = s != s ? 0.0 : (s > 2147483647.0 ? 2147483647.0 : (s < -2147483648.0 ? -2147483648.0 : s));
 	at = sel_put_int(dst, at, (int64_t)(int32_t)s, write);
 	return at;
 }
@@ -134,8 +136,8 @@ __device__ __forceinline__ SelSlice sel_slice(const SelectParams &P, uint64_t i)
 	return s;
 }
 /* A record as its writer sees it (sel_put_record): the lead character, `nlen` bytes of the name, a label WITH its leading blank,
- * `base_len` bases (no_bases: the single base N), and for FASTQ `qual_len` qualities shifted by qual_shift (no_quals: the single
- * quality `masked_qual`).  The selection prints as many qualities as bases; the artifact report (kmr_artifact_report.hpp) prints N over
+ * `base_len` bases (no_bases: the single base N), and for FASTQ `qual_len` qualities shifted by qual_shift (no_quals: `qual_len`
+ * times the quality `masked_qual`).  The selection prints as many qualities as bases; the artifact report (kmr_artifact_report.hpp) prints N over
  * all of a read's qualities. */
 struct SelRecord {
 	const uint8_t *name, *label, *bases, *quals;
@@ -196,6 +198,9 @@ __device__ __forceinline__ void sel_emit(const SelectParams &P, uint64_t i, uint
 	R.name = P.text + P.name_off[i]; R.nlen = nlen; R.label = s_label; R.lablen = lablen;
 	R.bases = P.bases + sl.from; R.quals = P.quals + sl.from; R.base_len = R.qual_len = sl.len; R.no_bases = R.no_quals = sl.masked;
 	R.qual_shift = P.qual_shift; R.masked_qual = (uint8_t)(P.out_base + 1); R.fasta = P.fasta != 0;
+	/* A read whose first quality is Read::REF_QUAL has none (Read::setRead src/Sequence.cpp:652-655), and getQuals prints PRINT_REF_QUAL
+	 * for every base of such a read and of a slice that starts on a REF_QUAL (:744-746), whatever the output base */
+	if (!R.fasta && !sl.masked && (P.quals[P.offsets[i]] == SEL_REF_QUAL || P.quals[sl.from] == SEL_REF_QUAL)) { R.no_quals = true; R.masked_qual = SEL_PRINT_REF_QUAL; }
 	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
 	sel_put_record(R, bytes, dst, lane);
 	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();      /* s_label is rewritten for the next record */

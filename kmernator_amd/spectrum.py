@@ -1551,6 +1551,7 @@ class ReadSelector(_DeviceObject):
         self.trims = None
         self.bimodal_words = None      # bimodal() of the scoreAndTrimReads that left the trims, if it ran with the option on
         self.scoring = "MEDIAN"
+        self.device_text_of_reads = None      # set to (device pointer, bytes) of a copy of read_set.text: pickAllPassing* / writePicks read the names there
         self._picks = None
         self._sel = None
         self.picked_flags = np.zeros(n, dtype=bool)
@@ -1622,31 +1623,32 @@ class ReadSelector(_DeviceObject):
         w = self.bimodal_words
         self.sp._call("select_bimodal", self.sp.h, self._p(w, C.c_uint64), 0 if w is None else w.size)
 
-    def _select(self, min_score, min_read_length, both_pass):
+    def _select(self, min_score, min_read_length, both_pass, by_pair=True):
         if self.trims is None:
             raise KmerSpectrumError("pickAllPassing*: scoreAndTrimReads has not run")
-        self._sel = (min_score, min_read_length, both_pass)
+        self._sel = (min_score, min_read_length, both_pass, by_pair)
         return self._run(33, "fastq")
 
     def _run(self, output_quality_base, format):
-        min_score, min_read_length, both_pass = self._sel
+        min_score, min_read_length, both_pass, by_pair = self._sel
+        mate = self.mate if by_pair else None      # writePicks in another format selects again, as the pick did
         cfg = self._config(min_score, min_read_length, both_pass, output_quality_base, format, self.scoring)
         keep, tp, tn = self._text_args()
         trims, trim_ptrs = self._trim_args()
         self._tag_args()
         out = C.c_void_p()
-        self.sp._call("select_reads", self.sp.h, self.reads.r, tp, tn, self._p(self.mate, C.c_int64), *self._af_args(), *trim_ptrs, C.byref(cfg), C.byref(out))
+        entry = "select_reads"
+        if self.device_text_of_reads is not None:      # (device pointer, bytes) of the text the names point into: kmr_select_reads_dev
+            entry, (tp, tn) = "select_reads_dev", self.device_text_of_reads
+            tp = tp or None
+        self.sp._call(entry, self.sp.h, self.reads.r, tp, tn, self._p(mate, C.c_int64), *self._af_args(), *trim_ptrs, C.byref(cfg), C.byref(out))
         self._adopt(out)
         self._fmt = (output_quality_base, cfg.format)
         return self.n_picked
 
     def pickAllPassingReads(self, min_score=0.0, min_read_length=None):
         """every read on its own, whatever `mate` says (:576-583); returns the number of picks"""
-        mate, self.mate = self.mate, None
-        try:
-            return self._select(min_score, min_read_length, False)
-        finally:
-            self.mate = mate
+        return self._select(min_score, min_read_length, False, by_pair=False)
 
     def pickAllPassingPairs(self, min_score=0.0, min_read_length=None, both_pass=False):
         """:585-596 over the pairs of `mate`; returns the number of picked reads"""

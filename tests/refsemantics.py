@@ -88,13 +88,7 @@ def score_and_trim(counts, seq, k, min_score, scoring):
     return toff, tlen + k - 1, sc, trimmed
 
 
-def passes_length(length, read_length, minimum_length):
-    """ReadSelectorUtil::passesLength (src/ReadSelector.h:209-228): a minimum <= 1 is a fraction of the read, above 1 a length"""
-    if length <= 1.0:
-        return False
-    if minimum_length <= 1.0:
-        return read_length * minimum_length <= length
-    return minimum_length <= length
+from refpartition import passes_length      # ReadSelectorUtil::passesLength in the reference's float arithmetic: the one definition
 
 
 def filterreads_output(names, seqs, quals, labels, discarded, trim_off, trim_len, scores, min_depth, min_read_length, both_pass, qual_shift=0, out_base=33):
